@@ -183,6 +183,34 @@ def cpu_baseline(size, weights, alpha):
                       'CPU-TF conv stack; %.2f s per frame (min %.2f, max %.2f)' % (size, size, alpha, what, med, min(times), max(times))}
 
 
+DUMP_BUDGET_BYTES = 64 << 20              # --dump-outputs: at most this much in all
+DUMP_SAMPLE = 1 << 22                     # elements of the seeded sample of frames too large to write whole
+
+
+def dump_outputs(out_dir, frames):
+    """--dump-outputs: the frames of the last timed step as the caller of stylize_batch_dev receives them (uint8
+    [pairs][S][S][3], rank 0's gathered tensor for N > 1), written as float32 .npy for output-for-output comparison of two
+    builds.  Whole when they take at most 3/4 of the budget; otherwise a fixed sample -- flat indices drawn with seed 0,
+    sorted, a function of the shape alone -- and those indices (float64, exact).  Returns {name: shape}."""
+    os.makedirs(out_dir, exist_ok=True)
+    written = {}
+
+    def save(name, a):
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+        written[name] = list(a.shape)
+
+    flat = frames.reshape(-1)
+    if flat.size * 4 <= DUMP_BUDGET_BYTES * 3 // 4:
+        save('frames', frames.astype(np.float32))
+    else:
+        idx = np.unique(np.random.default_rng(0).integers(0, flat.size, DUMP_SAMPLE))
+        save('frames_sample', flat[idx].astype(np.float32))
+        save('frames_sample_index', idx.astype(np.float64))
+        save('frames_shape', np.asarray(frames.shape, np.float64))
+    assert sum(os.path.getsize(os.path.join(out_dir, n + '.npy')) for n in written) <= DUMP_BUDGET_BYTES
+    return written
+
+
 def real_image_leg(ctx, alpha, n=10):
     """The headline's spectra are those of synthetic noise images; this leg puts a PHOTOGRAPH next to them: the reference's
     sample photo (samples/gilbert.jpg resampled to 512 x 512: tests/golden/gilbert_512.npz, written by oracle/make_golden.py)
@@ -247,10 +275,17 @@ def main():
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-latency', action='store_true', help='skip the batch-1 host-in/host-out latency leg')
     ap.add_argument('--no-prof', action='store_true', help='no per-class HIP-event timing inside the timed region')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps write the frames of the last one to DIR/*.npy (float32; a fixed seeded sample if '
+                         'they exceed the size budget) for comparison of two builds on identical inputs; bench_outputs/ is git-ignored')
     ap.add_argument('--spectrum', choices=['frames', 'graded'], default='frames',
                     help="'graded': only the eigensolver's hard-spectrum leg (graded 512-channel covariances, N = 4096 and "
                          "N = 256 < C): sweeps and ms")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    if args.dump_outputs and args.spectrum == 'graded':
+        ap.error('--dump-outputs dumps the frames of the stylize steps; --spectrum graded runs none')
 
     import torch
     import torch.distributed as dist
@@ -378,8 +413,10 @@ def main():
         # the digest of `total_pairs` pairs is the same for every N: a wrong shard offset or gather order changes it.
         if rank == 0 and steps + warmup > 0:
             last = state['frames'] if world > 1 else d_out[(state['k'] - 1) & 1]
-            info['frames_sha256'] = hashlib.sha256(last.cpu().numpy().tobytes()).hexdigest()
+            host = last.cpu().numpy()
+            info['frames_sha256'] = hashlib.sha256(host.tobytes()).hexdigest()
             info['frames'] = int(last.shape[0])
+            info['last_frames'] = host
         if world > 1 and gather_once:
             # the exchange step alone, once, NOT overlapped: a barrier, then the gather of the last step's frames, timed on
             # the host around a device synchronisation (max over the ranks)
@@ -398,6 +435,8 @@ def main():
     strong = args.global_batch > 0
     total_pairs = args.global_batch if strong else args.batch * world
     dt, n_local, prof, eig, info = measure(total_pairs, args.steps, args.warmup, not args.no_prof, gather_once=world > 1)
+    dumped = dump_outputs(args.dump_outputs, info['last_frames']) if rank == 0 and args.dump_outputs else None
+    info.pop('last_frames', None)
     # the same steps without the per-class events (they cost 1-2 %): reported beside the headline, never instead of it
     dt_np = None
     if not args.no_prof:
@@ -456,6 +495,9 @@ def main():
         if proj is not None:
             line['configs3_projection'] = proj
         line['frames_sha256'] = info.get('frames_sha256')
+        if dumped is not None:
+            line['dump_outputs'] = {'dir': args.dump_outputs, 'arrays': dumped,
+                                    'note': 'the frames of the last timed step (uint8 values as float32)'}
         if world > 1:
             try:
                 rccl = '.'.join(str(v) for v in torch.cuda.nccl.version())

@@ -109,3 +109,31 @@ def test_launch_ranks_starts_n_processes(tmp_path):
     assert launch_ranks(2, [str(tmp_path)], script=str(script), timeout=300) == 0
     assert sorted(p.name for p in tmp_path.iterdir() if p.name.startswith('rank')) == ['rank0_of_2', 'rank1_of_2']
     assert (tmp_path / 'rank1_of_2').read_text() == '127.0.0.1'
+
+
+def test_bench_dump_outputs_sample_is_fixed_and_within_budget(tmp_path):
+    """bench.py --dump-outputs on frames too large to write whole (the default 32 x 512^2 batch): a seeded sample, the same
+    indices on every call, float32 values and float64 indices that select them, 64 MB at most in all."""
+    import sys
+    from conftest import ROOT
+    sys.path.insert(0, ROOT)
+    import bench
+    frames = np.random.default_rng(3).integers(0, 256, (32, 512, 512, 3)).astype(np.uint8)
+    got = [bench.dump_outputs(str(tmp_path / d), frames) for d in ('a', 'b')]
+    assert got[0] == got[1] and set(got[0]) == {'frames_sample', 'frames_sample_index', 'frames_shape'}
+    assert sum(f.stat().st_size for f in (tmp_path / 'a').iterdir()) <= 64 << 20
+    idx = np.load(str(tmp_path / 'a' / 'frames_sample_index.npy'))
+    vals = np.load(str(tmp_path / 'a' / 'frames_sample.npy'))
+    assert idx.dtype == np.float64 and vals.dtype == np.float32
+    assert np.array_equal(idx, np.load(str(tmp_path / 'b' / 'frames_sample_index.npy')))
+    assert np.array_equal(vals, frames.reshape(-1)[idx.astype(np.int64)])
+    assert np.array_equal(np.load(str(tmp_path / 'a' / 'frames_shape.npy')), frames.shape)
+
+
+def test_bench_refuses_zero_steps():
+    """--steps is the number of timed steps and ms_per_step divides by it: 0 is refused before anything runs."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--steps', '0'], capture_output=True, text=True, timeout=300)
+    assert r.returncode != 0 and '--steps' in r.stderr and '"ms_per_step"' not in r.stdout

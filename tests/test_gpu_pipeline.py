@@ -587,6 +587,28 @@ def test_bench_cli_small(tmp_path):
     assert abs(sum(line['breakdown_ms_per_step'].values()) - line['ms_per_step']) < 0.5 * line['ms_per_step']
 
 
+def test_bench_dump_outputs_are_the_frames_of_the_last_step(tmp_path, ctx, weights):
+    """bench.py --dump-outputs: --steps timed steps (the line says so), then the frames of the last one in DIR/frames.npy as
+    float32 -- the frames stylize_batch computes for the same six pairs, value for value."""
+    import json
+    import subprocess
+    import sys
+    from conftest import ROOT
+    n, size = 6, 64
+    content = np.stack([synthetic_image(1000 + i, size, size) for i in range(n)])
+    style = np.stack([synthetic_image(2000 + i, size, size) for i in range(n)])
+    direct = ctx.stylize_batch(content, style, RELU_TARGETS, alpha=0.8)
+    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--size', str(size), '--global-batch', str(n), '--steps', '3',
+                          '--warmup', '1', '--no-cpu-baseline', '--no-latency', '--no-prof', '--dump-outputs', str(tmp_path / 'dump')],
+                         capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    line = json.loads(out.stdout.strip().splitlines()[-1])
+    assert line['steps'] == 3 and line['ms_per_step'] > 0 and line['dump_outputs']['arrays'] == {'frames': [n, size, size, 3]}
+    frames = np.load(str(tmp_path / 'dump' / 'frames.npy'))
+    assert frames.dtype == np.float32 and frames.shape == direct.shape
+    assert np.array_equal(frames, direct.astype(np.float32))
+
+
 def test_bench_gpus2_self_launches_two_ranks():
     """`python bench.py --gpus 2` WITHOUT a launcher starts two ranks itself (VERDICT r3 missing #1).  Dry run on the one
     GPU of this box: both ranks share it, the exchange goes through gloo; the line says n_gpus = 2 and carries the `strong`
