@@ -13,9 +13,6 @@ namespace emul { thread_local Idx tidx; thread_local Idx bidx; thread_local Bloc
 #include <stdio.h>
 #include <stdlib.h>
 #include "../../wct_tf_amd/csrc/jacobi_dev.h"
-#ifndef EMUL_VAR
-#define EMUL_VAR 0              // strip layout: 0 = 8 strips on 4 waves (the shipped one), 1 = 16 strips on 8 waves
-#endif
 
 static int failures = 0;
 static void check(const char* what, double err, double tol) {
@@ -153,20 +150,20 @@ struct Solver {
 #endif
     a.Sr = Sb[par].data(); a.Sw = Sb[par ^ 1].data();
     a.st = &st; a.C = C; a.nmat = 1; a.step_d = step_d; a.step_u = step_u; a.has_d = has_d; a.has_u = has_u; a.first = first;
-    a.with_v = with_v; a.dbg = 0;
+    a.with_v = with_v;
     return a;
   }
   void run_d(const JacobiFusedArgs& a) {
-    const size_t bytes = r4::lds_bytes<M2, EMUL_VAR>(1, 0, a.first, a.step_d);
+    const size_t bytes = r4::lds_bytes<M2, 0>(1, 0, a.first, a.step_d);
     for (int g = 0; g < npair; ++g) {
       arm(bytes);
-      emul::run_block(r4::Lay<EMUL_VAR>::NTD, g, [&](int) { r4::fused_d<M2, EMUL_VAR>(a, 0, g, lds.data()); });
+      emul::run_block(r4::Lay<0>::NTD, g, [&](int) { r4::fused_d<M2, 0>(a, 0, g, lds.data()); });
       guard_ok(bytes, "fused_d");
     }
   }
   void run_u(const JacobiFusedArgs& a, bool with_v) {
     const int ntask = npair * (npair - 1) / 2 + npair + (with_v ? npair * npair : 0);
-    const size_t bytes = r4::lds_bytes<M2, EMUL_VAR>(0, 1, 0, 0);
+    const size_t bytes = r4::lds_bytes<M2, 0>(0, 1, 0, 0);
     for (int task = 0; task < ntask; ++task) {
       arm(bytes);
       emul::run_block(r4::NT, task, [&](int) { r4::fused_u<M2>(a, 0, task, lds.data()); });

@@ -1,6 +1,5 @@
-"""Accuracy of the transform on the teacher-forced level features of a 512x512 five-level frame, as a function of the
-eigensolver's convergence tolerance (WCT_JACOBI_CONV_TOL, read once per process): prints rel. error vs the oracle and
-the sweeps used, per level.  usage: python tests/probes/wct_tol_probe.py [cache.npz]"""
+"""Accuracy of the transform on the teacher-forced level features of a 512x512 five-level frame: prints rel. error vs the
+oracle and the sweeps used, per level.  usage: python tests/probes/wct_tol_probe.py [cache.npz]"""
 import os
 import sys
 import numpy as np
@@ -26,4 +25,4 @@ for i, relu in enumerate(RELU_TARGETS):
     got, sweeps = ctx.transform(fc.reshape(-1, c), fs.reshape(-1, c), 0.8, _lib.WCT_TF, return_sweeps=True)
     e = np.linalg.norm(got.reshape(t.shape).astype(np.float64) - t) / np.linalg.norm(t)
     line.append('%s %.2e %s' % (relu, e, sweeps))
-print('tol=%s pw=%s | ' % (os.environ.get('WCT_JACOBI_CONV_TOL', 'default'), os.environ.get('WCT_JACOBI_PW', '1')) + ' | '.join(line))
+print(' | '.join(line))

@@ -54,14 +54,11 @@ struct Decoder {
 };
 
 struct ProfRec { hipEvent_t a, b; int cls; double flops, bytes; };
-constexpr int WCT_EIG_WORDS = 8 + 4 * 6 * 3;
+constexpr int WCT_EIG_WORDS = 2 + 6 * 3;
 
 struct wct_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
-  hipStream_t side[3] = {nullptr, nullptr, nullptr};   // extra streams: each level's eigenproblems run in up to 4 groups
-  int nside = 3;
-  hipEvent_t ev_fork = nullptr, ev_join[3] = {nullptr, nullptr, nullptr};
   bool enc_loaded = false;
   half_t* first_w = nullptr;       // folded conv1_1 as fp16 hi/lo MFMA fragments (ConvFirstArgs::wfrag)
   float* first_b = nullptr;
@@ -73,9 +70,9 @@ struct wct_ctx {
   DevBuf act[2], feat_c, feat_s[6], img_c, img_s, img_t[2], wct_out, wct_ws, stage[4];
   DevBuf usum_c, usum_s[6], umax;     // feature statistics from the tap epilogues (ConvArgs::usum / umax); umax: [7][32][UMAX_SLOTS] words
 
-  int* eig_fail = nullptr;         // pinned host memory mapped into the device: [4 stream groups][2] eigenproblems that did
-                                   // (then [4 groups][6 size classes][3] solver statistics: matrices, sweeps, max sweeps)
-  int* eig_fail_dev = nullptr;     // not converge / had non-finite input -- bumped by jacobi_finalize_kernel
+  int* eig_fail = nullptr;         // pinned host memory mapped into the device: [2] eigenproblems that did not converge / had
+                                   // non-finite input -- bumped by jacobi_finalize_kernel (then [6 size classes][3] solver
+  int* eig_fail_dev = nullptr;     // statistics: matrices, sweeps, max sweeps)
   float ss_alpha = 0.6f;           // style-swap settings (stylize.py:34-37 defaults)
   int ss_patch = 3, ss_stride = 1;
   bool prof = false;
@@ -148,24 +145,14 @@ extern "C" int wct_create(int device, wct_ctx** out) {
     delete c;
     return WCT_ERR_HIP;
   }
-  bool ok = hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming) == hipSuccess;
-  for (int i = 0; i < 3 && ok; ++i)
-    ok = hipStreamCreateWithFlags(&c->side[i], hipStreamNonBlocking) == hipSuccess &&
-         hipEventCreateWithFlags(&c->ev_join[i], hipEventDisableTiming) == hipSuccess;
-  if (!ok) {
-    wct_set_error("hipStreamCreate/hipEventCreate failed");
-    delete c;
-    return WCT_ERR_HIP;
-  }
-  if (ok) ok = hipHostMalloc((void**)&c->eig_fail, WCT_EIG_WORDS * sizeof(int), hipHostMallocMapped) == hipSuccess &&
-               hipHostGetDevicePointer((void**)&c->eig_fail_dev, c->eig_fail, 0) == hipSuccess;
+  const bool ok = hipHostMalloc((void**)&c->eig_fail, WCT_EIG_WORDS * sizeof(int), hipHostMallocMapped) == hipSuccess &&
+                  hipHostGetDevicePointer((void**)&c->eig_fail_dev, c->eig_fail, 0) == hipSuccess;
   if (!ok) {
     wct_set_error("hipHostMalloc (mapped status words) failed");
     delete c;
     return WCT_ERR_HIP;
   }
   for (int i = 0; i < WCT_EIG_WORDS; ++i) c->eig_fail[i] = 0;
-  { const int n = tune_int("WCT_EIG_GROUPS", -1); if (n >= 0) c->nside = n < 1 ? 0 : (n > 4 ? 3 : n - 1); }
   *out = c;
   return WCT_OK;
 }
@@ -207,8 +194,6 @@ extern "C" void wct_destroy(wct_ctx* c) {
   for (auto& r : c->recs) { hipEventDestroy(r.a); hipEventDestroy(r.b); }
   for (auto& e : c->free_events) { hipEventDestroy(e.first); hipEventDestroy(e.second); }
   if (c->eig_fail) hipHostFree(c->eig_fail);
-  hipEventDestroy(c->ev_fork);
-  for (int i = 0; i < 3; ++i) { hipStreamSynchronize(c->side[i]); hipEventDestroy(c->ev_join[i]); hipStreamDestroy(c->side[i]); }
   hipStreamDestroy(c->stream);
   delete c;
 }
@@ -216,10 +201,9 @@ extern "C" void wct_destroy(wct_ctx* c) {
 // After a stream sync: did any eigensolve since the last check fail?  The frames / features of the call are still
 // written (best effort, like LAPACK's "did not converge" info > 0), but the status is loud: WCT_STATUS_NOCONV.
 static int eig_status(wct_ctx* c) {
-  int n_open = 0, n_nan = 0;
-  for (int g = 0; g < 4; ++g) { n_open += c->eig_fail[2 * g]; n_nan += c->eig_fail[2 * g + 1]; }
+  const int n_open = c->eig_fail[0], n_nan = c->eig_fail[1];
   if (!n_open && !n_nan) return WCT_OK;
-  for (int i = 0; i < 8; ++i) c->eig_fail[i] = 0;
+  c->eig_fail[0] = c->eig_fail[1] = 0;
   wct_set_error("eigensolver: %d covariance matri%s still rotating after the sweep budget, %d with non-finite entries "
                 "(NaN/Inf features?); the outputs of this call are not reliable", n_open, n_open == 1 ? "x" : "ces", n_nan);
   return WCT_ERR_NOCONV;
@@ -230,10 +214,9 @@ static int eig_status(wct_ctx* c) {
 // they are, and before this call runs, so that its own status and sweep counts are never mixed with them.
 static int eig_stale(wct_ctx* c) {
   HIP_TRY(hipStreamSynchronize(c->stream));
-  int n_open = 0, n_nan = 0;
-  for (int g = 0; g < 4; ++g) { n_open += c->eig_fail[2 * g]; n_nan += c->eig_fail[2 * g + 1]; }
+  const int n_open = c->eig_fail[0], n_nan = c->eig_fail[1];
   if (!n_open && !n_nan) return WCT_OK;
-  for (int i = 0; i < 8; ++i) c->eig_fail[i] = 0;
+  c->eig_fail[0] = c->eig_fail[1] = 0;
   wct_set_error("eigensolver failures of an EARLIER asynchronous wct_stylize_batch_dev call that was not followed by wct_sync "
                 "(%d matri%s still rotating after the sweep budget, %d with non-finite entries): the frames of that call are "
                 "not reliable; the present call was not started", n_open, n_open == 1 ? "x" : "ces", n_nan);
@@ -251,14 +234,11 @@ extern "C" int wct_sync(wct_ctx* c) {
 extern "C" int wct_eig_stats(wct_ctx* c, long long out[18]) {
   ARG_CHECK(c && out);
   HIP_TRY(hipStreamSynchronize(c->stream));
-  for (int k = 0; k < 18; ++k) out[k] = 0;
-  for (int g = 0; g < 4; ++g)
-    for (int k = 0; k < 6; ++k) {
-      int* s = c->eig_fail + 8 + (g * 6 + k) * 3;
-      out[3 * k] += s[0]; out[3 * k + 1] += s[1];
-      if (s[2] > out[3 * k + 2]) out[3 * k + 2] = s[2];
-      s[0] = s[1] = s[2] = 0;
-    }
+  for (int k = 0; k < 6; ++k) {
+    int* s = c->eig_fail + 2 + k * 3;
+    out[3 * k] = s[0]; out[3 * k + 1] = s[1]; out[3 * k + 2] = s[2];
+    s[0] = s[1] = s[2] = 0;
+  }
   return WCT_OK;
 }
 
@@ -345,11 +325,10 @@ static int upload(wct_ctx* c, const void* host, size_t bytes, void** dev) {
 
 // Which layers also get their filters packed for the reduced-FLOP kernel (conv_wino.hip).  Decided by the layer's channel counts
 // alone -- never by the batch or the image size: a frame must not depend on the batch it is computed in.  WCT_WINOGRAD=0 is a TEST
-// hook (read once per process, like WCT_FUSE_CONV1): every layer on the direct kernel, the round-5 bits.  A -DWCT_TUNING build
-// takes the channel threshold from WCT_WINO_MIN.
+// hook (read once per process, like WCT_FUSE_CONV1): every layer on the direct kernel, the round-5 bits.
 static bool wino_layer(int cin, int cout) {
   static const int on = getenv("WCT_WINOGRAD") ? atoi(getenv("WCT_WINOGRAD")) : 1;
-  static const int min_ch = tune_int("WCT_WINO_MIN", 256);
+  constexpr int min_ch = 256;
   return on && cin >= min_ch && cout >= min_ch && cin % 64 == 0 && cout % 64 == 0;
 }
 
@@ -576,16 +555,15 @@ static int run_encoder(wct_ctx* c, const float* img, int B, int H, int W, int cl
   if (deepest == 1) return WCT_OK;
   // enc[i]: level whose relu*_1 it produces (0 = none), and whether a 'same' max-pool follows it
   // (conv1_2, conv2_2, conv3_4, conv4_4 -- their outputs feed nothing but the pool, so it is fused
-  // into their epilogue; WCT_FUSE_POOL=0 runs the separate pool kernel instead)
+  // into their epilogue)
   static const int seq_tap[12] = {0, 2, 0, 3, 0, 0, 0, 4, 0, 0, 0, 5};
   static const int pool_after[12] = {1, 0, 1, 0, 0, 0, 1, 0, 0, 0, 1, 0};
-  static const int fuse_pool = tune_int("WCT_FUSE_POOL", 1);
   int h = H, w = W;
   for (int i = 0; i < 12; ++i) {
     const ConvLayer& l = c->enc[i];
     const int tap = seq_tap[i];
     const bool last = tap == deepest;
-    const bool fuse = pool_after[i] && fuse_pool;
+    const bool fuse = pool_after[i];
     float* const us = tap && taps32[tap] && usum ? usum[tap] : nullptr;
     if (i == 0 && fuse_conv1) {
       ConvArgs a;
@@ -599,14 +577,7 @@ static int run_encoder(wct_ctx* c, const float* img, int B, int H, int W, int cl
     TRY(run_conv(c, l, cur, last ? nullptr : nxt, tap ? taps32[tap] : nullptr, B, h, w, 0, 1, fuse, us, us ? umax[tap] : nullptr, tap != 0));
     half_t* t = cur; cur = nxt; nxt = t;
     if (last) break;
-    if (pool_after[i]) {
-      if (!fuse) {
-        ProfScope ps(c, 3, 0, (double)B * h * w * l.cout * 2 * 1.25);
-        TRY(launch_maxpool2x2(cur, nxt, B, h, w, l.cout, c->stream));
-        t = cur; cur = nxt; nxt = t;
-      }
-      h = (h + 1) / 2; w = (w + 1) / 2;
-    }
+    if (fuse) { h = (h + 1) / 2; w = (w + 1) / 2; }
   }
   return WCT_OK;
 }
@@ -623,26 +594,10 @@ static int run_decoder(wct_ctx* c, int level, const half_t* feat16, int B, int h
   const half_t* cur = feat16;
   half_t* bufs[2] = {(half_t*)c->act[0].p, (half_t*)c->act[1].p};
   int which = 0, ci = 0, up = 0;
-  // WCT_FUSE_TAIL=1 (test hook, read once per process): the last 64 -> 64 conv and the 64 -> 3 output conv as ONE launch
-  // (csrc/conv_tail.hip): the 64-channel full-resolution map is neither written nor read, and the bits are the same.  NOT the
-  // default: measured on one box (profiles/r06_conv_tail.txt) the fused launch takes what the two launches take (+0.25 ms per
-  // 32-pair step) -- the 64 -> 64 layer is bound by MFMA work and per-tile fixed costs, not by the bytes the fusion removes, and
-  // the 18 x 18 halo costs 1.37 x its MFMA work.
-  static const int fuse_tail_env = getenv("WCT_FUSE_TAIL") ? atoi(getenv("WCT_FUSE_TAIL")) : 0;
   const size_t nsteps = d.plan.size();
   for (size_t si = 0; si < nsteps; ++si) {
     const PlanStep& s = d.plan[si];
     if (s.kind == 'U') { up = 1; h *= 2; w *= 2; continue; }
-    if (fuse_tail_env && !c->no_wino /* (the training forward keeps every activation) */ && s.cin == 64 && s.cout == 64 &&
-        si + 1 < nsteps && d.plan[si + 1].kind == 'C' && d.plan[si + 1].cout == 3) {
-      const ConvLayer& l = d.convs[ci++];
-      ConvTailArgs a;
-      a.x = cur; a.w = l.w; a.bias = l.b; a.wlast = d.last_w; a.blast = d.last_b; a.y = img_out; a.B = B; a.H = h; a.W = w; a.upsample = up;
-      const double px = (double)B * h * w;
-      ProfScope ps(c, 10, 2.0 * px * (9 * 64 * 64 + 576 * 3), px * ((up ? 32 : 128) + 12) + 9.0 * 64 * 64 * 2);
-      TRY(launch_conv_tail(a, c->stream));
-      break;
-    }
     if (s.cout == 3) {
       ARG_CHECK(up == 0);
       ConvLastArgs a;
@@ -672,14 +627,14 @@ static int run_transform(wct_ctx* c, const float* fc, int Nc, const float* fs, i
   const int mode = (flags & WCT_FLAG_MODE_NP) ? WCT_MODE_NP : WCT_MODE_TF;
   {
     ProfScope ps(c, 4, (double)P * 2.0 * C * C * ((double)Nc + Ns), (double)P * 2.0 * ((double)Nc + Ns) * C * 4);
-    TRY(launch_wct(fc, Nc, fs, Ns, C, P, alpha, mode, eps, out16, out32, c->wct_ws.p, c->wct_ws.cap, sweeps_dev, WCT_STAGE_COV, c->stream, nullptr, 0, nullptr, nullptr, shared, c->eig_fail_dev, st));
+    TRY(launch_wct(fc, Nc, fs, Ns, C, P, alpha, mode, eps, out16, out32, c->wct_ws.p, c->wct_ws.cap, sweeps_dev, WCT_STAGE_COV, c->stream, shared, c->eig_fail_dev, st));
   }
   {
     ProfScope ps(c, 5, 0, 0);
-    TRY(launch_wct(fc, Nc, fs, Ns, C, P, alpha, mode, eps, out16, out32, c->wct_ws.p, c->wct_ws.cap, sweeps_dev, WCT_STAGE_EIG, c->stream, c->side, c->nside, c->ev_fork, c->ev_join, shared, c->eig_fail_dev));
+    TRY(launch_wct(fc, Nc, fs, Ns, C, P, alpha, mode, eps, out16, out32, c->wct_ws.p, c->wct_ws.cap, sweeps_dev, WCT_STAGE_EIG, c->stream, shared, c->eig_fail_dev));
   }
   ProfScope ps(c, 6, (double)P * (2.0 * C * C * Nc + 6.0 * C * C * C), (double)P * Nc * C * (4 + (out16 ? 2 : 0) + (out32 ? 4 : 0)));
-  return launch_wct(fc, Nc, fs, Ns, C, P, alpha, mode, eps, out16, out32, c->wct_ws.p, c->wct_ws.cap, sweeps_dev, WCT_STAGE_APPLY, c->stream, nullptr, 0, nullptr, nullptr, shared, c->eig_fail_dev);
+  return launch_wct(fc, Nc, fs, Ns, C, P, alpha, mode, eps, out16, out32, c->wct_ws.p, c->wct_ws.cap, sweeps_dev, WCT_STAGE_APPLY, c->stream, shared, c->eig_fail_dev);
 }
 
 // ---------------------------------------------------------------------------

@@ -39,23 +39,12 @@ void wct_set_error(const char* fmt, ...);
 
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 
-// A-B / tuning switches.  In the product build they are constants: a stray environment variable must never change the
-// numerics of a library whose contract is bit-reproducible output.  Only a -DWCT_TUNING build (tools/, experiments on the
-// GPU box) reads them from the environment.  THREE documented TEST hooks stay live in every build, all safe by
-// construction: WCT_JACOBI_MAX_SWEEPS can only LOWER the sweep budget (clamped to the compiled one; the solve then fails
-// loudly, never silently); WCT_FUSE_STATS=0, WCT_FUSE_CONV1=0 and WCT_FUSE_TAIL=1 each select a path whose output is
-// bit-identical (asserted by tests/test_gpu_pipeline.py); WCT_WINOGRAD=0 keeps every 3x3 layer on the direct kernel (the
-// round-5 arithmetic: other roundings, same tolerances).  grep getenv: these five and nothing else outside #ifdef WCT_TUNING.
-#ifdef WCT_TUNING
-#include <stdlib.h>
-static inline int tune_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
-static inline float tune_float(const char* name, float dflt) { const char* e = getenv(name); return e ? (float)atof(e) : dflt; }
-static inline bool tune_set(const char* name) { return getenv(name) != nullptr; }
-#else
-static inline int tune_int(const char*, int dflt) { return dflt; }
-static inline float tune_float(const char*, float dflt) { return dflt; }
-static inline bool tune_set(const char*) { return false; }
-#endif
+// Environment variables: the library reads four TEST hooks and nothing else, all safe by construction (a library whose
+// contract is bit-reproducible output must not change its numerics on a stray variable): WCT_JACOBI_MAX_SWEEPS can only
+// LOWER the sweep budget (clamped to the compiled one; the solve then fails loudly, never silently); WCT_FUSE_STATS=0 and
+// WCT_FUSE_CONV1=0 each select a path whose output is bit-identical (asserted by tests/test_gpu_pipeline.py); WCT_WINOGRAD=0
+// keeps every 3x3 layer on the direct kernel (the round-5 arithmetic: other roundings, same tolerances).  The A-B switches of
+// the tuning rounds and the variants they selected were removed after round 6.
 
 // ---- conv.hip -------------------------------------------------------------
 struct ConvArgs {
@@ -69,7 +58,6 @@ struct ConvArgs {
   int upsample;        // input is the x2 nearest upsample of x (model.py:293)
   int relu;
   int pool;            // fuse the following 2x2/2 'same' max-pool: outputs are [(H+1)/2][(W+1)/2][Cout]
-  int xcd_map = 0;     // (tuning switch WCT_CONV_XCD) tile order that keeps the blocks of a pixel tile on one XCD (conv.hip)
   // feature statistics from the fp32 epilogue (null: off; need y32, relu, W % 16 == 0): usum [B][H*W/16][Cout] = the sum of
   // every run of 16 consecutive pixels (unit_row_sum's fixed tree -- what colsum_kernel computes from the stored features),
   // umax [B][UMAX_SLOTS] = bit patterns whose maximum is the largest value of the image (>= 0 after the ReLU), merged with
@@ -150,19 +138,6 @@ struct ConvLastArgs {    // 64 -> 3, no activation (model.py:298)
 };
 int launch_conv_last(const ConvLastArgs& a, hipStream_t s);
 
-// conv_tail.hip: the last 64 -> 64 conv of a decoder (ReLU; its input x2-upsampled if `upsample`) and the 64 -> 3 output conv in one
-// kernel -- the 64-channel full-resolution map stays in LDS.  The bits of launch_conv3x3 + launch_conv_last.
-struct ConvTailArgs {
-  const half_t* x;      // [B][Hin][Win][64] fp16 (Hin = H / 2 if upsample)
-  const half_t* w;      // the 64 -> 64 conv's fragments (ConvArgs::w)
-  const float* bias;    // [64]
-  const half_t* wlast;  // the output conv's fragments (ConvLastArgs::wfrag)
-  const float* blast;   // [3]
-  float* y;             // [B][H][W][3] fp32, unclipped
-  int B, H, W, upsample;
-};
-int launch_conv_tail(const ConvTailArgs& a, hipStream_t s);
-
 int launch_maxpool2x2(const half_t* x, half_t* y, int B, int H, int W, int C, hipStream_t s);
 int launch_u8_to_f32(const uint8_t* x, float* y, size_t n, hipStream_t s);       // /255 (wct.py:64)
 int launch_f32_to_u8(const float* x, uint8_t* y, size_t n, hipStream_t s);       // uint8(clip*255) (wct.py:68)
@@ -215,12 +190,10 @@ size_t wct_workspace_bytes(int C, int Nc, int Ns, int P);
 int launch_wct(const float* content, int Nc, const float* style, int Ns, int C, int P,
                float alpha, int mode, float eps /* <0: reference default */, half_t* out16, float* out32,
                void* workspace, size_t workspace_bytes, int* sweeps_dev, int stages, hipStream_t s,
-               const hipStream_t* side /* optional extra streams: the eigenproblems are split over 1+nside */,
-               int nside, hipEvent_t ev_fork, const hipEvent_t* ev_join,
                int shared_style /* style holds ONE feature map used by all P pairs: its statistics and
                                    eigensystem are computed once */,
-               int* eig_fail /* device-visible status words [4 stream groups][2] (not converged, non-finite), bumped by the
-                                eigensolver, or null */,
+               int* eig_fail /* device-visible status words: [2] (not converged, non-finite), bumped by the eigensolver,
+                                then [6 size classes][3] solver statistics; or null */,
                const struct WctFeatStats* stats = nullptr /* unit sums / maxima a conv epilogue left beside the features */);
 // WCT_STAGE_EIG_FP32UPDATE (with WCT_STAGE_EIG): the eigensolver's tile updates on fp32 MFMA instead of split fp16 -- style-swap, whose
 // patch matching is an argmax over the whitened features (csrc/jacobi_dev.h r4::fused_u)

@@ -13,20 +13,11 @@
 // so every lane ends up holding 4 consecutive output channels of one pixel and
 // the epilogue stores 8 B (fp16) / 16 B (fp32) per lane.
 #include "common.h"
-#include <stdio.h>
 
 // ---------------------------------------------------------------------------
 // generic 3x3 conv, Cin % 32 == 0, Cout % BN == 0
 // ---------------------------------------------------------------------------
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-// Phase timing build (-DCONV_TS, tools/conv_phase_timing.sh): lane 0 of every block stamps s_memtime at its phase
-// boundaries; the launcher prints the per-launch means.  Compiled out of the product.
-#ifdef CONV_TS
-__device__ unsigned long long conv_ts[16384 * 10];
-#define TS(slot) do { if (ts_on && threadIdx.x == 0) { const unsigned fl_ = blockIdx.x + gridDim.x * blockIdx.y; if (fl_ < 16384) conv_ts[fl_ * 10 + (slot)] = __builtin_amdgcn_s_memtime(); } } while (0)
-#else
-#define TS(slot) do {} while (0)
-#endif
 constexpr int TW = 16;          // tile width in pixels (one MFMA B-fragment = 2 rows x 16)
 constexpr int PITCH = 20;       // patch row pitch in pixels (18 used; multiple of 4 keeps the swizzle aligned)
 constexpr int BK = 32;          // input channels per K-chunk
@@ -180,22 +171,8 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& p, f32x16 (&acc)[N
 //    771 TFLOP/s over the layer mix vs 943 for this one.)
 //  * __launch_bounds__(256, 2): two blocks resident per CU cover each other's chunk boundaries.
 // ---------------------------------------------------------------------------
-// WLDS (round 5, tuning builds: the block DESIGN 8.2 of rounds 3-4 asked for): BOTH operands of the implicit GEMM come out of
-// LDS.  The weights of a STAGE -- the three taps of one kernel row ky of the current K-chunk, BN x 3 x 32 fp16 = 48 KB for the
-// 256-channel block, already in MFMA A-fragment order in global memory -- are copied global -> LDS by LDS-DMA
-// (global_load_lds_dwordx4: 1 KiB = one fragment per wave instruction, no registers, lane-linear on both sides), one whole stage
-// ahead into the other of two buffers; a wave takes its fragments with ds_read_b128 at immediate offsets one tap ahead.  Every
-// weight byte enters the CU once per 256 pixels x 256 channels (the register path streams it once per wave: 2 x per 256 x 128).
-// Protocol: the barrier that opens the LAST tap of stage S (a) publishes stage S + 1 (issued a stage earlier; __syncthreads
-// drains the DMA queue because LDS-DMA sits on vmcnt) before the first fragment of its first tap is prefetched, and (b) retires
-// buffer S % 2 for every wave (its last fragment read was a tap earlier), so the DMA of stage S + 2 follows at once.
-// STRIPS (round 5): the generic loader walks a strip of horizontally adjacent tiles as well, and the FIRST patch of the next tile
-// is copied global -> LDS by LDS-DMA (no registers) under the current tile's epilogue.  A 64-channel layer has two K-chunks per
-// tile: its first patch (7 k cycles of exposed latency, profiles/r02_conv_phase_timing.txt) and its epilogue were 45 % of a tile.
-template <int TH, int BN, int WM, int WN, bool FUSE1 = false, bool WLDS = false, bool STRIPS = false>
+template <int TH, int BN, int WM, int WN, bool FUSE1 = false>
 __global__ __launch_bounds__(256, ((TH / 2) / WM) * ((BN / 32) / WN) > 8 ? 1 : 2) void conv3x3_mfma_kernel(ConvArgs p, int tiles_x, int tiles_y, int n_tiles, int strip) {
-  constexpr bool LOOP = FUSE1 || STRIPS;           // the block walks `strip` tiles
-  static_assert(!(FUSE1 && STRIPS) && !(WLDS && STRIPS), "one loader variant at a time");
   constexpr int PH = TH + 2;
   constexpr int MT = (TH / 2) / WM;
   constexpr int NT = (BN / 32) / WN;
@@ -219,10 +196,6 @@ __global__ __launch_bounds__(256, ((TH / 2) / WM) * ((BN / 32) / WN) > 8 ? 1 : 2
   // [pixel slot i][channel][thread] because the hardware writes lane l of a wave at base + 4 l; the 12-byte form of the
   // instruction did not land the pixels at base + 12 l -- parity test red -- and was worth 2.5 % of this kernel)
   constexpr int STG_OFF = B1_OFF + 256;
-  // WLDS: two weight-stage buffers behind the bias (1-KiB aligned): [cout tile BN/32][tap of the row 3][k-step 2][lane 64][16 B]
-  constexpr int WST_BYTES = (BN / 32) * 3 * 2 * 1024;
-  constexpr int WST_OFF = ((BIAS_OFF + BN * 4 + 1023) / 1024) * 1024;
-  static_assert(!WLDS || !FUSE1, "WLDS: generic loader only");
   static_assert(!FUSE1 || (BN == 64 && !(((TH / 2) / WM) * ((BN / 32) / WN) > 8)), "FUSE1: 64 output channels, single patch buffer");
   // tap at which the next K-chunk's patch loads are issued (their registers are live from there to the
   // chunk boundary only); the tall tile has no registers to spare and loads at the boundary
@@ -231,24 +204,13 @@ __global__ __launch_bounds__(256, ((TH / 2) / WM) * ((BN / 32) / WN) > 8 ? 1 : 2
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   unsigned char* const patch_lds = smem;
 
-  [[maybe_unused]] bool ts_on = true;          // (-DCONV_TS) a strip block stamps its SECOND tile: entry = the end of the first
-  TS(8);
   int bid = blockIdx.x;
-  int ntile = bid % n_tiles;
+  const int ntile = bid % n_tiles;
   bid /= n_tiles;
-  if (!FUSE1 && p.xcd_map) {
-    // (tuning switch) blocks reach the 8 XCDs round-robin by their linear index; with the channel tile running fastest the
-    // n_tiles blocks that read the SAME pixel patch sat on n_tiles different XCDs (every L2 fetched every patch).  Here the
-    // 8 consecutive indices of a group work on 8 different pixel tiles and the channel tile advances with the group:
-    // index = (pixel group * n_tiles + channel tile) * 8 + pixel in group -- the blocks of a pixel tile share an XCD.
-    const int lin = (int)blockIdx.x, g8 = lin >> 3;
-    ntile = g8 % n_tiles;
-    bid = (g8 / n_tiles) * 8 + (lin & 7);
-  }
   // FUSE1: a block walks a strip of `strip` horizontally adjacent tiles (the next tile's image patch is fetched under the
   // epilogue of the current one); blockIdx.x counts strips
-  const int strips_x = LOOP ? (tiles_x + strip - 1) / strip : tiles_x;
-  const int tx = LOOP ? (bid % strips_x) * strip : bid % strips_x;
+  const int strips_x = FUSE1 ? (tiles_x + strip - 1) / strip : tiles_x;
+  const int tx = FUSE1 ? (bid % strips_x) * strip : bid % strips_x;
   const int ty = bid / strips_x;
   const int b = blockIdx.y;
   int y0 = ty * TH;
@@ -261,9 +223,7 @@ next_tile:   // (FUSE1: the strip loop -- the whole body; otherwise passed once)
   // (thread index and tile row are made opaque per iteration: hoisted out of the strip loop, everything that depends on the lane
   //  and y0 only -- fragment addresses, reflected rows, patch and store offsets -- stayed live across the tile's epilogue and
   //  27 registers were spilled; recomputing them costs a few dozen instructions per tile)
-  if (LOOP) asm volatile("" : "+v"(tid_), "+s"(y0));
-  ts_on = !FUSE1 || strip < 2 || strip_i == 1;
-  if (FUSE1 && strip >= 2) TS(8);
+  if (FUSE1) asm volatile("" : "+v"(tid_), "+s"(y0));
   const int tid = tid_;
   const int lane = tid & 63;
   const int wave = tid >> 6;
@@ -315,44 +275,6 @@ next_tile:   // (FUSE1: the strip loop -- the whole body; otherwise passed once)
   const __amdgpu_buffer_rsrc_t w_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.w, 0, 0x7FFFFFFF, 0x00020000);
   const __amdgpu_buffer_rsrc_t x_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)xb, 0, 0x7FFFFFFF, 0x00020000);
 
-  // STRIPS: chunk 0 of the patch of the tile at xt, global -> LDS.  One wave instruction fills 64 consecutive 16-byte slots of
-  // the [PH][PITCH] x 4 slot image (lane-linear destination); the XOR swizzle of patch_dst is applied on the SOURCE side
-  // (slot s of pixel px takes channel piece s ^ ((px >> 2) & 3)), the two padding pixels of a row re-read pixel 17, and the
-  // lanes past the image (half an instruction) land in the dump area behind it.
-  auto dma_patch0 = [&](int xt) {
-    constexpr int NINS = (PH * PITCH * 4 + 63) / 64;
-    const int wave_u = __builtin_amdgcn_readfirstlane(wave);
-#pragma unroll 1                         // (rolled: unrolled, the eleven lane offsets live at once next to the accumulators spilled 62 registers)
-    for (int i0 = 0; i0 < (NINS + 3) / 4; ++i0) {
-      const int i = wave_u + i0 * 4;
-      if (i < NINS) {                                          // (uniform)
-        const int d = i * 64 + lane, ps = d >> 2, slot = d & 3;
-        int py = ps / PITCH;
-        const int px = ps - py * PITCH;
-        py = py < PH ? py : PH - 1;
-        int iy = reflect_idx(y0 - 1 + py, p.H), ix = reflect_idx(xt - 1 + (px < 18 ? px : 17), p.W);
-        if (p.upsample) { iy >>= 1; ix >>= 1; }
-        const int piece = slot ^ ((px >> 2) & 3);
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(x_rsrc, reinterpret_cast<__attribute__((address_space(3))) void*>(
-            (__attribute__((address_space(3))) unsigned char*)smem + i * 1024), 16, ((iy * Win + ix) * p.Cin + piece * 8) * 2, 0, 0, 0);
-      }
-    }
-  };
-  // WLDS: this wave's share of a stage: fragments f = wave, wave + 4, ... of the (BN / 32) * 6; fragment f = (ct * 3 + tap3) * 2 + ks
-  // = 1 KiB at p.w + ((n0 / 32 + ct) * 9 * c16 + (3 ky + tap3) * c16 + 2 chunk + ks) * 1024 bytes
-  auto dma_stage = [&](int stage) {           // stage = chunk * 3 + ky (uniform)
-    constexpr int NF = (BN / 32) * 6;
-    const int chunk = stage / 3, ky = stage - chunk * 3, bufw = stage & 1;
-    const int wave_u = __builtin_amdgcn_readfirstlane(wave);       // (M0 and the scalar offset must be SGPRs: no waterfall loops)
-#pragma unroll
-    for (int i = 0; i < NF / 4; ++i) {
-      const int f = wave_u + i * 4, ks = f & 1, t3 = (f >> 1) % 3, ct = (f >> 1) / 3;
-      // buffer form: SGPR resource + one loop-invariant lane offset + a scalar fragment offset -- no per-fragment VGPR address
-      const int soff = ((((n0 >> 5) + ct) * 9 + ky * 3 + t3) * c16 + chunk * 2 + ks) * 1024;
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(w_rsrc, reinterpret_cast<__attribute__((address_space(3))) void*>(
-          (__attribute__((address_space(3))) unsigned char*)smem + WST_OFF + bufw * WST_BYTES + f * 1024), 16, lane * 16, soff, 0, 0);
-    }
-  };
   f32x16 acc[NT][MT];
   // the block's bias values -> LDS (read back by the epilogue; visible after the first patch barrier)
   if (tid < BN / 4 && strip_i == 0)
@@ -361,20 +283,6 @@ next_tile:   // (FUSE1: the strip loop -- the whole body; otherwise passed once)
   const int n_chunks = p.Cin / BK;           // even: Cin is a multiple of 64 on this path
   u32x4 patch_regs[PATCH_PER_THREAD];
   half8 wf[2][NT][2];                        // ping-pong weight fragments, loaded a full tap ahead
-  half8 wa[2][NT];                           // WLDS: ping-pong weight fragments by k-step, read out of LDS one k-step ahead
-  auto read_wfrag = [&](half8 (&dst)[NT], int stage, int t3, int ks) {     // the fragments of k-step ks of tap (stage, t3)
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt)
-      dst[nt] = *reinterpret_cast<const half8*>(smem + WST_OFF + (stage & 1) * WST_BYTES +
-                                                ((((wn * NT + nt) * 3 + t3) * 2 + ks) * 64 + lane) * 16);
-  };
-  auto mma_group_w = [&](half8 (&w)[NT], half8 (&bq)[MT]) {
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-      for (int nt = 0; nt < NT; ++nt)
-        acc[nt][mt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(w[nt], bq[mt], acc[nt][mt], 0, 0, 0);
-  };
   half8 bf[2][MT];                           // ping-pong pixel fragments, read one k-step (8 MFMAs) ahead
 
   auto read_group = [&](half8 (&dst)[MT], int ky, int kx, int ks, int buf) {
@@ -532,39 +440,24 @@ next_tile:   // (FUSE1: the strip loop -- the whole body; otherwise passed once)
     for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[nt][mt][r] = 0.f;
-  TS(1);
   if (FUSE1) {
     // (the image patch in LDS was last read by the previous tile's second make_patch, which ends in a barrier)
     park_img();
-    TS(9);
-  } else if (STRIPS) {
-    // the first patch of EVERY tile of a strip comes by LDS-DMA: the first tile's here, the others' under the previous epilogue
-    // (one code path: a register-path first patch beside it left part of patch_regs in scratch memory)
-    if (strip_i == 0) dma_patch0(x0);
   } else {
     load_patch(0);
   }
-  if (WLDS) {
-    dma_stage(0);
-    if (n_chunks * 3 > 1) dma_stage(1);
-  } else {
 #pragma unroll
-    for (int nt = 0; nt < NT; ++nt)
+  for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
-      for (int ks = 0; ks < 2; ++ks)
-        wf[0][nt][ks] = __builtin_bit_cast(half8, __builtin_amdgcn_raw_buffer_load_b128(w_rsrc, wfrag[nt] + ks * 1024, 0, 0));
-  }
+    for (int ks = 0; ks < 2; ++ks)
+      wf[0][nt][ks] = __builtin_bit_cast(half8, __builtin_amdgcn_raw_buffer_load_b128(w_rsrc, wfrag[nt] + ks * 1024, 0, 0));
   if (FUSE1) {
     __syncthreads();
     make_patch(0);
-  } else if (STRIPS) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // this wave's pieces of the patch (and everything older) have landed
   } else {
     store_patch(0);
   }
-  __syncthreads();                           // (WLDS: drains the DMA queue as well -- stages 0 and 1 are in LDS for every wave)
-  TS(2);
-  if (WLDS) read_wfrag(wa[0], 0, 0, 0);
+  __syncthreads();
   read_group(bf[0], 0, 0, 0, 0);
 
 #pragma unroll 1
@@ -576,40 +469,6 @@ next_tile:   // (FUSE1: the strip loop -- the whole body; otherwise passed once)
       const int ntap = (tap + 1) % 9, nky = ntap / 3, nkx = ntap % 3;
       const bool more = chunk_i + 1 < n_chunks;
       const int buf = DB ? t / 9 : 0;            // compile-time: an immediate in the fragment reads
-      if constexpr (WLDS) {
-        // ---- both operands out of LDS.  wa[0] / bf[0] hold the fragments of this tap's first k-step (read during the previous
-        // tap), the second k-step's go out now; under ITS MFMAs the first k-step of the next tap is read -- across a stage
-        // boundary (kx = 2) behind the barrier that publishes the next stage's weights (and, at a chunk boundary, the next
-        // patch, parked in the other buffer just before: ONE barrier per stage, none per chunk).
-        const int stage = chunk_i * 3 + ky;
-        const bool last = stage + 1 >= n_chunks * 3;           // (uniform)
-        if (tap == PF_TAP && more) load_patch(chunk_i + 1);
-        read_group(bf[1], ky, kx, 1, buf);
-        read_wfrag(wa[1], stage, kx, 1);
-        if (DB && tap == 8 && more) store_patch(buf ^ 1);
-        __builtin_amdgcn_sched_barrier(0);
-        mma_group_w(wa[0], bf[0]);
-        __builtin_amdgcn_sched_barrier(0);
-        if (kx == 2) {
-          if (!last) {
-            __syncthreads();                                   // stage + 1 has landed for everybody; nobody reads this stage's buffer again
-            if (stage + 2 < n_chunks * 3) dma_stage(stage + 2);
-            read_wfrag(wa[0], stage + 1, 0, 0);
-            if (!DB && tap == 8) {                             // single patch buffer: it is free now (every wave's reads have returned)
-              store_patch(0);
-              __syncthreads();
-            }
-            read_group(bf[0], ky == 2 ? 0 : ky + 1, 0, 0, ky == 2 ? (DB ? buf ^ 1 : 0) : buf);
-          }
-        } else {
-          read_wfrag(wa[0], stage, kx + 1, 0);
-          read_group(bf[0], ky, kx + 1, 0, buf);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        mma_group_w(wa[1], bf[1]);
-        __builtin_amdgcn_sched_barrier(0);
-        continue;
-      }
       // 1) next tap's weight fragments (past the very end: re-read, unused); the next patch leaves PF_TAP early
       {
         const int nchunk = tap == 8 ? (more ? chunk_i + 1 : chunk_i) : chunk_i;
@@ -639,10 +498,8 @@ next_tile:   // (FUSE1: the strip loop -- the whole body; otherwise passed once)
         if (more) {
           __syncthreads();
           if (FUSE1) {
-            TS(3);
             make_patch(chunk_i + 1);
             __syncthreads();
-            TS(4);
           } else if (!DB) {
             if (PF_TAP > 8) load_patch(chunk_i + 1);
             store_patch(0);
@@ -654,45 +511,28 @@ next_tile:   // (FUSE1: the strip loop -- the whole body; otherwise passed once)
       __builtin_amdgcn_sched_barrier(0);
     }
   }
-  TS(5);
-  const bool more_tiles = LOOP && strip_i + 1 < strip && tx + strip_i + 1 < tiles_x;      // uniform
-  if (FUSE1 && more_tiles) fetch_img(x0 + TW);        // arrives under the epilogue (whose stores sit on the same in-order counter)
-  if (STRIPS && more_tiles) {
-    __syncthreads();                         // every wave has taken its last fragments out of the patch
-    dma_patch0(x0 + TW);
-  }
-  TS(0);
+  const bool more_tiles = FUSE1 && strip_i + 1 < strip && tx + strip_i + 1 < tiles_x;      // uniform
+  if (more_tiles) fetch_img(x0 + TW);        // arrives under the epilogue (whose stores sit on the same in-order counter)
   conv_epilogue<MT, NT>(p, acc, b, y0, x0, n0, wm, wn, lane, smem + BIAS_OFF);
-  TS(6);
   if (more_tiles) {
-    TS(7);
     ++strip_i;
     x0 += TW;
     goto next_tile;
   }
-#ifdef CONV_TS
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  TS(7);
-#endif
 }
 
-template <int TH, int BN, int WM, int WN, bool FUSE1 = false, bool WLDS = false, bool STRIPS = false>
+template <int TH, int BN, int WM, int WN, bool FUSE1 = false>
 static int launch_conv_cfg(const ConvArgs& a, hipStream_t s) {
   const int tiles_x = cdiv(a.W, TW), tiles_y = cdiv(a.H, TH);
   const int n_tiles = a.Cout / BN;
   constexpr int PH = TH + 2;
   constexpr int NBUF = ((TH / 2) / WM) * ((BN / 32) / WN) > 8 ? 2 : 1;
-  size_t lds = (size_t)NBUF * (PH * PITCH * 64 + 4096) + BN * sizeof(float)      // NBUF x (patch, dump slots), bias
-               + (FUSE1 ? (size_t)(TH + 4) * 20 * 3 * 4 + 64 + 8192 + 256 + 9 * 1024 : 0);  // image patch, zero words, conv1_1 weights and bias, landing area
-  if (WLDS) lds = ((lds + 1023) / 1024) * 1024 + 2 * (size_t)(BN / 32) * 3 * 2 * 1024;      // two weight-stage buffers
+  const size_t lds = (size_t)NBUF * (PH * PITCH * 64 + 4096) + BN * sizeof(float)      // NBUF x (patch, dump slots), bias
+                     + (FUSE1 ? (size_t)(TH + 4) * 20 * 3 * 4 + 64 + 8192 + 256 + 9 * 1024 : 0);  // image patch, zero words, conv1_1 weights and bias, landing area
   // FUSE1: strips of 4 / 2 tiles per block while that leaves the chip >= 4 blocks per resident slot (512 slots)
   const long tiles = (long)tiles_x * tiles_y * a.B;
-  static const int strip_force = tune_int("WCT_FUSE1_STRIP", 0);   // tuning switch
-  const int strip = !(FUSE1 || STRIPS) ? 1 : strip_force ? strip_force : tiles >= 8192 ? 4 : tiles >= 4096 ? 2 : 1;
-  dim3 grid(((FUSE1 || STRIPS) ? cdiv(tiles_x, strip) : tiles_x) * tiles_y * n_tiles, a.B);
-  ConvArgs ax = a;
-  static const int xcd = tune_int("WCT_CONV_XCD", 0);     // tuning switch: XCD-aware tile order (needs a multiple of 8 pixel tiles per image)
-  ax.xcd_map = !FUSE1 && !STRIPS && xcd && (tiles_x * tiles_y) % 8 == 0;
+  const int strip = !FUSE1 ? 1 : tiles >= 8192 ? 4 : tiles >= 4096 ? 2 : 1;
+  dim3 grid((FUSE1 ? cdiv(tiles_x, strip) : tiles_x) * tiles_y * n_tiles, a.B);
   if (lds > 64 * 1024) {
     // more dynamic LDS than the 64 KiB a runtime may enforce by default (gfx950 has 160 KiB per CU): say so, once per device
     // and instantiation; a refusal surfaces here and not at a later synchronisation
@@ -700,38 +540,12 @@ static int launch_conv_cfg(const ConvArgs& a, hipStream_t s) {
     int dev = 0;
     HIP_TRY(hipGetDevice(&dev));
     if (dev >= 0 && dev < 16 && !raised[dev]) {
-      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_mfma_kernel<TH, BN, WM, WN, FUSE1, WLDS, STRIPS>),
+      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_mfma_kernel<TH, BN, WM, WN, FUSE1>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
       raised[dev] = true;
     }
   }
-  hipLaunchKernelGGL((conv3x3_mfma_kernel<TH, BN, WM, WN, FUSE1, WLDS, STRIPS>), grid, dim3(256), lds, s, ax, tiles_x, tiles_y, n_tiles, strip);
-#ifdef CONV_TS
-  if (a.B >= 8) {
-    static int nlaunch = 0;
-    ++nlaunch;
-    (void)hipStreamSynchronize(s);
-    static unsigned long long host[16384 * 10];
-    (void)hipMemcpyFromSymbol(host, HIP_SYMBOL(conv_ts), sizeof(host));
-    const int nb = (int)(grid.x * grid.y < 16384 ? grid.x * grid.y : 16384);
-    double sum[6] = {0}, mid = 0;   // slots: 8 entry, 1 addresses ready, 2 first patch in LDS, (FUSE1: 3-4 the second chunk's patch,) 5 taps done, 6 epilogue issued, 7 stores drained
-    for (int i = 0; i < nb; ++i) {
-      const unsigned long long* h = host + (size_t)i * 10;
-      sum[0] += (double)(h[1] - h[8]); sum[1] += (double)(h[2] - h[1]); sum[2] += (double)(h[5] - h[2]);
-      sum[3] += (double)(h[6] - h[5]); sum[4] += (double)(h[7] - h[6]); sum[5] += (double)(h[7] - h[8]);
-      if (FUSE1) mid += (double)(h[4] - h[3]);
-    }
-    if (FUSE1) {
-      double park = 0, fetch = 0;
-      for (int i = 0; i < nb; ++i) { const unsigned long long* h = host + (size_t)i * 10; park += (double)(h[9] - h[1]); fetch += (double)(h[0] - h[5]); }
-      fprintf(stderr, "TS (conv1_1 in the loader, strip %d: the second tile) second patch %.0f of the mainloop cycles; image patch parked %.0f of the load0 cycles; next fetch issued %.0f of the epilogue cycles\n",
-              strip, mid / nb, park / nb, fetch / nb);
-    }
-    fprintf(stderr, "TS launch %d <%d,%d,%d,%d> Cin %d Cout %d H %d up %d pool %d y32 %d blocks %d: setup %.0f load0 %.0f mainloop %.0f epilogue %.0f drain %.0f total %.0f\n",
-            nlaunch, TH, BN, WM, WN, a.Cin, a.Cout, a.H, a.upsample, a.pool, a.y32 != nullptr, nb,
-            sum[0] / nb, sum[1] / nb, sum[2] / nb, sum[3] / nb, sum[4] / nb, sum[5] / nb);
-  }
-#endif
+  hipLaunchKernelGGL((conv3x3_mfma_kernel<TH, BN, WM, WN, FUSE1>), grid, dim3(256), lds, s, a, tiles_x, tiles_y, n_tiles, strip);
   HIP_TRY(hipGetLastError());
   return WCT_OK;
 }
@@ -753,39 +567,11 @@ int launch_conv3x3(const ConvArgs& a, hipStream_t s) {
   }
   const long px16 = (long)cdiv(a.W, TW) * cdiv(a.H, 16) * a.B;
   const long px32 = (long)cdiv(a.W, TW) * cdiv(a.H, 32) * a.B;
-  static const int force = tune_int("WCT_CONV_CFG", 0);   // tuning switch
-  if (force == 1 && a.Cout % 128 == 0) return launch_conv_cfg<16, 128, 2, 2>(a, s);
-  if (force == 2) return launch_conv_cfg<32, 64, 4, 1>(a, s);
-  if (force == 3) return launch_conv_cfg<16, 64, 4, 1>(a, s);
-  if (force == 4) return launch_conv_cfg<8, 64, 2, 2>(a, s);
-  // (round 3: a 256-pixel x 256-channel block, 4 x 4 MFMA tiles per wave with the accumulators in AGPRs, ONE wave per SIMD --
-  //  half the LDS fragment reads per MFMA.  As it stands it ties the 128-channel block: 512->512 @64 1156 vs 1136 TFLOP/s
-  //  (1175 vs 1143 with the double-buffered patch, DB), 256->256 @128 1057-1068 vs 1066-1085, worse where the grid gets
-  //  small (512->512 @32: 381 vs 590); without a partner block the first patch and the epilogue of every tile are exposed.
-  //  Kept as a switch: the starting point of DESIGN 8.2)
-#ifdef WCT_TUNING      // (2 VGPR spills: not instantiated in the product build -- VERDICT r4)
-  if (force == 5 && a.Cout % 256 == 0) return launch_conv_cfg<16, 256, 2, 2>(a, s);
-  // (round 5: the same block with BOTH operands through LDS -- weights by LDS-DMA a stage ahead; see the kernel's WLDS note)
-  if (force == 6 && a.Cout % 256 == 0) return launch_conv_cfg<16, 256, 2, 2, false, true>(a, s);
-  if (force == 7 && a.Cout % 256 == 0 && px16 * (a.Cout / 256) >= 256) return launch_conv_cfg<16, 256, 2, 2, false, true>(a, s);
-  // ... and on the shipped 256-pixel x 128-channel block: 76 KB of LDS, still two blocks per CU
-  if (force == 8 && a.Cout % 128 == 0 && px16 * (a.Cout / 128) >= 512) return launch_conv_cfg<16, 128, 2, 2, false, true>(a, s);
-#endif
   // (round 2: <32,64,2,2> and <16,128,1,4> -- the waves of a block split the output channels instead of the pixels,
   //  halving / removing the redundant weight streams -- measured 593 vs 601 TFLOP/s on 64->64 @512^2 and 5-8 % slower on
-  //  the wide layers, profiles/r02_conv_cfg_sweep.txt: the weight streams are not what bounds these layers; removed)
-#ifdef WCT_TUNING
-  // (round 5, tuning builds: WCT_CONV_STRIPS=1 -- strips with the next tile's first patch by LDS-DMA under the epilogue, on the layers
-  //  with few K-chunks per tile and many tiles.  Bit-identical, 10 % SLOWER on 64 -> 64 @512 (0.194 -> 0.215 ms at batch 8,
-  //  profiles/r05_conv_strips.txt): the strip serialises a tile's store drain with the next tile's start, which two independent
-  //  blocks per CU overlap for free)
-  static const int strips_on = tune_int("WCT_CONV_STRIPS", 0);
-  if (strips_on && a.Cin <= 128) {
-    if (a.Cout % 128 == 0 && px16 * (a.Cout / 128) >= 512 && px16 >= 4096) return launch_conv_cfg<16, 128, 2, 2, false, false, true>(a, s);
-    if (!(a.Cout % 128 == 0 && px16 * (a.Cout / 128) >= 512) && px32 * (a.Cout / 64) >= 512 && px32 >= 4096)
-      return launch_conv_cfg<32, 64, 4, 1, false, false, true>(a, s);
-  }
-#endif
+  //  the wide layers, profiles/r02_conv_cfg_sweep.txt: the weight streams are not what bounds these layers; removed.
+  //  Rounds 3-5 tried a 256-pixel x 256-channel block, weights through LDS by LDS-DMA and strips of tiles per block: none
+  //  was faster)
   if (a.Cout % 128 == 0 && px16 * (a.Cout / 128) >= 512) return launch_conv_cfg<16, 128, 2, 2>(a, s);
   if (px32 * (a.Cout / 64) >= 512) return launch_conv_cfg<32, 64, 4, 1>(a, s);      // 512 px x 64 ch
   if (a.Cout % 128 == 0 && px16 * (a.Cout / 128) >= 256) return launch_conv_cfg<16, 128, 2, 2>(a, s);

@@ -23,17 +23,8 @@
 // B = pixels, one ds_read_b128 per fragment a tap ahead; a wave owns MT pixel tiles (2 pair-rows x 16 columns) x NT channel tiles
 // x 4 row frequencies.  One LDS-only barrier per K-chunk (s_waitcnt lgkmcnt(0) + s_barrier: the weight loads stay in flight).
 #include "common.h"
-#include <algorithm>
 
-#include <stdio.h>
 namespace {
-// Phase timing build (-DWINO_TS): lane 0 of every wave stamps s_memtime at its phase boundaries; the launcher prints the means.
-#ifdef WINO_TS
-__device__ unsigned long long wino_ts[8192 * 4 * 8];
-#define WTS(slot) do { if ((threadIdx.x & 63) == 0) { const unsigned fl_ = blockIdx.x + gridDim.x * blockIdx.y; if (fl_ < 8192) wino_ts[(fl_ * 4 + (threadIdx.x >> 6)) * 8 + (slot)] = __builtin_amdgcn_s_memtime(); } } while (0)
-#else
-#define WTS(slot) do {} while (0)
-#endif
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 h2 __attribute__((ext_vector_type(2)));
 constexpr int TW = 16;          // tile width in pixels
@@ -67,12 +58,7 @@ __device__ __forceinline__ int reflect_idx(int i, int n) {      // 1-px REFLECT 
 // barrier after tap 10) -- no branch in the loop body: the last chunk stages a patch nobody reads.
 template <int TH, int BN, int WM, int WN, bool IL>
 __global__ __launch_bounds__(256, TH >= 16 ? 1 : 2)
-void conv3x3_wino_kernel(ConvArgs p, int tiles_x, int n_tiles, int dbg_arg) {
-#ifdef WCT_TUNING
-  const int dbg = dbg_arg;      // ablation switches (tuning builds, WCT_WINO_DBG): 1 no weight loads, 2 no patch staging, 4 no MFMAs, 8 no fragment reads, 16 no epilogue
-#else
-  constexpr int dbg = 0;
-#endif
+void conv3x3_wino_kernel(ConvArgs p, int tiles_x, int n_tiles) {
   constexpr int PR = TH / 2;                 // pair-rows of the tile
   constexpr int MT = (PR / 2) / WM;          // MFMA pixel tiles (2 pair-rows x 16 columns) per wave
   constexpr int NT = (BN / 32) / WN;
@@ -84,7 +70,6 @@ void conv3x3_wino_kernel(ConvArgs p, int tiles_x, int n_tiles, int dbg_arg) {
   static_assert(PR % 2 == 0 && (PR / 2) % WM == 0 && 256 % PR == 0 && WM * WN == 4, "tile shape");
 
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  WTS(0);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave / WN, wn = wave % WN;
   int bid = blockIdx.x;
@@ -232,9 +217,7 @@ void conv3x3_wino_kernel(ConvArgs p, int tiles_x, int n_tiles, int dbg_arg) {
       *reinterpret_cast<half8*>(d + 2 * PITCH * 64) = pk_sub(d2, d1);
       *reinterpret_cast<half8*>(d + 3 * PITCH * 64) = pk_sub(d1, d3);
     }
-    WTS(1);
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    WTS(2);
     read_b(bf[0], 0, 0, 0);
     read_b(bf[1], 0, 1, 0);
 #pragma unroll 1
@@ -287,7 +270,6 @@ void conv3x3_wino_kernel(ConvArgs p, int tiles_x, int n_tiles, int dbg_arg) {
         if (tt == 9) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
       }
     }
-    WTS(3);
   } else {
   load_rows(0);
   load_w(wf[0], 0, 0);
@@ -307,17 +289,14 @@ void conv3x3_wino_kernel(ConvArgs p, int tiles_x, int n_tiles, int dbg_arg) {
       {
         const int t2 = (tt + 2) % 12;
         const int c2 = tt + 2 >= 12 ? (more ? chunk_i + 1 : chunk_i) : chunk_i;
-        if (!(dbg & 1)) load_w(wf[(t + 2) % 3], t2, c2);
+        load_w(wf[(t + 2) % 3], t2, c2);
       }
-      if (tt == PF_TAP && more && !(dbg & 2)) load_rows(chunk_i + 1);
+      if (tt == PF_TAP && more) load_rows(chunk_i + 1);
       // 2) the pixels of tap t + 1; across the chunk boundary from the other buffer (published by the barrier of tap 10)
-      if (!(dbg & 8)) {
-        if (tt != 11) read_b(bf[(t + 1) & 1], (tt + 1) / 3, (tt + 1) % 3, buf);
-        else if (more) read_b(bf[(t + 1) & 1], 0, 0, buf ^ 1);
-      }
+      if (tt != 11) read_b(bf[(t + 1) & 1], (tt + 1) / 3, (tt + 1) % 3, buf);
+      else if (more) read_b(bf[(t + 1) & 1], 0, 0, buf ^ 1);
       __builtin_amdgcn_sched_barrier(0);
       // 3) this tap's MFMAs
-      if (!(dbg & 4))
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
@@ -328,14 +307,13 @@ void conv3x3_wino_kernel(ConvArgs p, int tiles_x, int n_tiles, int dbg_arg) {
       __builtin_amdgcn_sched_barrier(0);
       // 4) the next chunk's patch: parked in the other buffer, published for tap 11's reads
       if (tt == 10 && more) {
-        if (!(dbg & 2)) park_rows(buf ^ 1);
+        park_rows(buf ^ 1);
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
       }
     }
   }
 
   }     // !IL
-  if (dbg & 16) return;
   // ---- epilogue: y(2r) = M0 + M1 + M2, y(2r+1) = M1 - M2 - M3 (the bias came in with M1), ReLU on the rounded pairs, (2x2 max-pool), stores.
   // acc register r of a tile holds channel (r & 3) + 8 (r >> 2) + 4 kgrp of pixel (pair-row frag_pr, column frag_px).
   constexpr int OOB = (int)0x80000000u;
@@ -405,39 +383,15 @@ void conv3x3_wino_kernel(ConvArgs p, int tiles_x, int n_tiles, int dbg_arg) {
       }
     }
   }
-  WTS(4);
-#ifdef WINO_TS
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  WTS(5);
-#endif
 }
 
 template <int TH, int BN, int WM, int WN, bool IL = false>
 int launch_wino_cfg(const ConvArgs& a, hipStream_t s) {
   const int tiles_x = cdiv(a.W, TW), tiles_y = cdiv(a.H, TH), n_tiles = a.Cout / BN;
   const size_t lds = 2 * (size_t)(TH / 2) * 4 * PITCH * 64 + (IL ? 8192 : 0);
-  static const int dbg = tune_int("WCT_WINO_DBG", 0);
   HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_wino_kernel<TH, BN, WM, WN, IL>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL((conv3x3_wino_kernel<TH, BN, WM, WN, IL>), dim3(tiles_x * tiles_y * n_tiles, a.B), dim3(256), lds, s, a, tiles_x, n_tiles, dbg);
-#ifdef WINO_TS
-  if (IL) {
-    (void)hipStreamSynchronize(s);
-    static unsigned long long host[8192 * 4 * 8];
-    (void)hipMemcpyFromSymbol(host, HIP_SYMBOL(wino_ts), sizeof(host));
-    const int nb = (int)std::min<long>((long)tiles_x * tiles_y * n_tiles * a.B, 8192);
-    double sum[5] = {0}; unsigned long long t0 = ~0ull, t1 = 0;
-    for (int i = 0; i < nb * 4; ++i) {
-      const unsigned long long* h = host + (size_t)i * 8;
-      sum[0] += (double)(h[1] - h[0]); sum[1] += (double)(h[2] - h[1]); sum[2] += (double)(h[3] - h[2]);
-      sum[3] += (double)(h[4] - h[3]); sum[4] += (double)(h[5] - h[4]);
-      t0 = std::min(t0, h[0]); t1 = std::max(t1, h[5]);
-    }
-    fprintf(stderr, "WTS <%d,%d,%d,%d> Cin %d Cout %d H %d B %d blocks %d: prologue (entry -> first patch parked) %.0f, barrier %.0f, mainloop %.0f (%d chunks: %.0f per chunk), epilogue %.0f, store drain %.0f; first entry -> last exit %.0f cycles\n",
-            TH, BN, WM, WN, a.Cin, a.Cout, a.H, a.B, nb, sum[0] / (nb * 4), sum[1] / (nb * 4), sum[2] / (nb * 4), a.Cin / 32, sum[2] / (nb * 4) / (a.Cin / 32),
-            sum[3] / (nb * 4), sum[4] / (nb * 4), (double)(t1 - t0));
-  }
-#endif
+  hipLaunchKernelGGL((conv3x3_wino_kernel<TH, BN, WM, WN, IL>), dim3(tiles_x * tiles_y * n_tiles, a.B), dim3(256), lds, s, a, tiles_x, n_tiles);
   HIP_TRY(hipGetLastError());
   return WCT_OK;
 }
@@ -457,14 +411,6 @@ int launch_conv3x3_wino(const ConvArgs& a, hipStream_t s) {
   ARG_CHECK((size_t)a.H * a.W * a.Cin * 2 < ((size_t)1 << 31));
   ARG_CHECK((size_t)a.H * a.W * a.Cout * 2 < ((size_t)1 << 31));
   const long px16 = (long)cdiv(a.W, TW) * cdiv(a.H, 16) * a.B;
-  static const int force = tune_int("WCT_WINO_CFG", 0);   // tuning switch
-  if (force == 1 && a.Cout % 128 == 0) return launch_wino_cfg<16, 128, 2, 2>(a, s);
-  if (force == 2) return launch_wino_cfg<16, 64, 2, 2>(a, s);
-  if (force == 3) return launch_wino_cfg<8, 64, 2, 2>(a, s);
-  if (force == 4 && a.Cout % 128 == 0) return launch_wino_cfg<8, 128, 1, 4>(a, s);
-  if (force == 5 && a.Cout % 128 == 0) return launch_wino_cfg<16, 128, 1, 4>(a, s);
-  if (force == 6 && a.Cout % 128 == 0) return launch_wino_cfg<16, 128, 1, 4, true>(a, s);
-  if (force == 7 && a.Cout % 128 == 0) return launch_wino_cfg<16, 128, 2, 2, true>(a, s);
   // one 256-pixel x 128-channel block per CU with the interleaved schedule where that fills the chip; below, blocks of 8 rows at
   // two per CU (the second block covers the first one's prologue and epilogue)
   const long px8 = (long)cdiv(a.W, TW) * cdiv(a.H, 8) * a.B;

@@ -9,9 +9,6 @@
 #ifndef R4_OPAQUE
 #define R4_OPAQUE(x) asm volatile("" : "+v"(x))     // the optimiser may not look through the value (no instruction emitted)
 #endif
-#ifndef JTS
-#define JTS(slot) do {} while (0)       // phase stamps of the -DJACOBI_TS build (wct.hip defines the real one)
-#endif
 
 struct JacobiState {
   unsigned int offmax;   // max |a_pq|/sqrt(a_pp a_qq) over the pairs rotated this sweep (float bits)
@@ -266,8 +263,6 @@ struct JacobiFusedArgs {
   int has_d, has_u;
   int first;            // the D part loads its pair problems straight from Pr (nothing is pending on it)
   int with_v;           // the U part also updates V (otherwise jacobi_vstrip_kernel applies the segment's rotations later)
-  int dbg;              // timing experiments (WCT_JACOBI_DBG): 1 U blocks exit at once, 2 D blocks exit at once, 4 no rotation sets
-  int mat_major;        // pair-problem blocks are numbered matrix-fastest (XCD locality; jacobi_fused4_kernel)
 };
 
 // Rotation matrices are stored in FRAGMENT order (the A operand of v_mfma_f32_16x16x4_f32 for V Q, see
@@ -350,27 +345,16 @@ constexpr int NT = 256;                    // threads per pair problem / per upd
 // Exchange per lane and set: 2 W + 3 floats -- qq[0..W) and qp[0..W) to lane k - 1 (qp[W-1] to the next strip's),
 // {pq, Qpq, Qqq} of the first column to the previous strip.
 // ---------------------------------------------------------------------------------------------------------------------
-// Two splits of the 32 columns over half-waves (strips), LAY:
-//   0   8 strips on 4 waves (256 threads): 1, 1 | 5 x 6
-//   1  16 strips on 8 waves (512 threads): 1, 1 | 3, 3 | 2 x 12 -- two waves per SIMD: a wave's LDS and transcendental
-//      latencies hide behind its SIMD partner, and no wave carries more than three cells
+// The split of the 32 columns over half-waves (strips), LAY 0: 8 strips on 4 waves (256 threads): 1, 1 | 5 x 6.  (A second
+// layout, 16 strips on 8 waves, measured slower -- profiles/r04_jacobi_ab.txt -- and was removed.)
 template <int LAY> struct Lay;
 template <> struct Lay<0> {
   static constexpr int NS = 8, NTD = 256;
-  __device__ static constexpr int w(int sg) { return sg < 2 ? 1 : 5; }
   __device__ static constexpr int d0(int sg) { return sg < 2 ? sg : 2 + 5 * (sg - 2); }
   // one exchange buffer: QQ4 f32x4[192] (qq of columns 0..3 of the W = 5 lanes, index t - 64) | QP4 f32x4[192] (qp 0..3) |
   // PQ f32x2[256] ({pq, Qpq} of column 0) | E[3][256] floats (qq of the LAST column, qp of the LAST column, Qqq of column 0).
   // 11 KB a buffer: S image + two buffers + (c, s) = 38.8 KB, so that FOUR blocks of a {D, U} launch share a CU's 160 KB.
   static constexpr int QQ4 = 0, QP4 = 3072, PQ = 6144, E = 8192, BUF = 11264;
-};
-template <> struct Lay<1> {
-  static constexpr int NS = 16, NTD = 512;
-  __device__ static constexpr int w(int sg) { return sg < 2 ? 1 : (sg < 4 ? 3 : 2); }
-  __device__ static constexpr int d0(int sg) { return sg < 2 ? sg : (sg < 4 ? 2 + 3 * (sg - 2) : 8 + 2 * (sg - 4)); }
-  // one exchange buffer: A f32x4[512] (qq of columns 0..2, Qqq of column 0) | B f32x4[512] (qp 0..2 -- the LAST column's is
-  // element W - 1 --, pq of column 0) | C float[512] (Qpq of column 0)
-  static constexpr int A = 0, B = 8192, C = 16384, BUF = 18432;
 };
 template <int LAY> struct Xchg {
   static constexpr int CS = 2 * Lay<LAY>::BUF;       // CS[2][32] float2 (c, s)
@@ -437,7 +421,7 @@ __device__ __forceinline__ void run_period(F& body, std::integer_sequence<int, I
   (body(std::integral_constant<int, (Is + 1) % LCM>{}, std::true_type{}), ...);
 }
 
-template <int LAY, int W, bool PWAVE, int PRIO = 0>
+template <int LAY, int W, bool PWAVE>
 __device__ __forceinline__ void strip_sets(Strip<W>& R, unsigned char* xb, float* simg, int t, float floor_m, float& my_off, float& my_sig) {
   using L = Lay<LAY>;
   constexpr int LCM = (W % 2) ? 2 * W : W, NS = L::NS, SX_CS = Xchg<LAY>::CS, SX_DUMMY = Xchg<LAY>::DUMMY, SX_BUF = L::BUF;
@@ -447,7 +431,6 @@ __device__ __forceinline__ void strip_sets(Strip<W>& R, unsigned char* xb, float
   const int dn = sg * 32 + ((k + 1) & 31);                             // lane (k + 1, same strip)
   const int dl = ((sg + NS - 1) % NS) * 32 + ((k + 1) & 31);           // lane (k + 1, previous strip)
   const int rt = ((sg + 1) % NS) * 32 + k;                             // lane (k, next strip)
-  const int wprev = L::w((sg + NS - 1) % NS);                          // width of the previous strip
   int a_l[W];
 #pragma unroll
   for (int j = 0; j < W; ++j) a_l[j] = SX_CS + ((k + L::d0(sg) + j + 1) & 31) * 8;
@@ -474,67 +457,38 @@ __device__ __forceinline__ void strip_sets(Strip<W>& R, unsigned char* xb, float
     tpk = s0 * __builtin_amdgcn_rcpf(c0);                              // (no rotation: s = 0)
     f32x2 r; r[0] = tpk; r[1] = tpk;
     *reinterpret_cast<f32x2*>(xb + a_csw) = r;
-  } else if (PRIO > 0) {
-    __builtin_amdgcn_s_setprio(PRIO);                                  // (tuning builds: WCT_JACOBI_DBG & 8)
   }
   __syncthreads();                                                     // (the S image is free from here on)
 
   auto take_rim = [&](auto SC) {                                       // the strip's rim for set S out of buffer S & 1
     constexpr int S = decltype(SC)::value, LASTP = (W - 1 + S) % W;
     const unsigned char* b = xb + (S & 1) * SX_BUF;
-    if constexpr (LAY == 0) {
-      if constexpr (W == 5) {
-        const f32x4 q4 = *reinterpret_cast<const f32x4*>(b + L::QQ4 + (dn - 64) * 16);
-        const f32x4 p4 = *reinterpret_cast<const f32x4*>(b + L::QP4 + (dn - 64) * 16);
-        const float q5 = *reinterpret_cast<const float*>(b + L::E + dn * 4);
-        const float pl = *reinterpret_cast<const float*>(b + L::E + 1024 + dl * 4);
-        static_for<W>([&](auto J) {
-          constexpr int j = decltype(J)::value;
-          // (opaque: four consecutive array elements assigned from one float4 are fused into a 16-byte store, which keeps the
-          //  whole array in scratch memory)
-          float vq = j < 4 ? q4[j < 4 ? j : 0] : q5, vp = j == 0 ? pl : p4[j > 0 ? j - 1 : 0];
-          R4_OPAQUE(vq); R4_OPAQUE(vp);
-          R.Sqq[(j + S) % W] = vq;
-          R.Sqp[j] = vp;
-        });
-      } else {
-        R.Sqq[0] = *reinterpret_cast<const float*>(b + L::E + dn * 4);
-        R.Sqp[0] = *reinterpret_cast<const float*>(b + L::E + 1024 + dl * 4);
-      }
-      const f32x2 pqin = *reinterpret_cast<const f32x2*>(b + L::PQ + rt * 8);
-      R.Spq[LASTP] = pqin[0]; R.Qpq[LASTP] = pqin[1];
-      R.Qqq[LASTP] = *reinterpret_cast<const float*>(b + L::E + 2048 + rt * 4);
+    if constexpr (W == 5) {
+      const f32x4 q4 = *reinterpret_cast<const f32x4*>(b + L::QQ4 + (dn - 64) * 16);
+      const f32x4 p4 = *reinterpret_cast<const f32x4*>(b + L::QP4 + (dn - 64) * 16);
+      const float q5 = *reinterpret_cast<const float*>(b + L::E + dn * 4);
+      const float pl = *reinterpret_cast<const float*>(b + L::E + 1024 + dl * 4);
+      static_for<W>([&](auto J) {
+        constexpr int j = decltype(J)::value;
+        // (opaque: four consecutive array elements assigned from one float4 are fused into a 16-byte store, which keeps the
+        //  whole array in scratch memory)
+        float vq = j < 4 ? q4[j < 4 ? j : 0] : q5, vp = j == 0 ? pl : p4[j > 0 ? j - 1 : 0];
+        R4_OPAQUE(vq); R4_OPAQUE(vp);
+        R.Sqq[(j + S) % W] = vq;
+        R.Sqp[j] = vp;
+      });
     } else {
-      const float pl = *reinterpret_cast<const float*>(b + L::B + dl * 16 + (wprev - 1) * 4);
-      if constexpr (W > 1) {
-        const f32x4 a4 = *reinterpret_cast<const f32x4*>(b + L::A + dn * 16);
-        const f32x4 b4 = *reinterpret_cast<const f32x4*>(b + L::B + dn * 16);
-        static_for<W>([&](auto J) {
-          constexpr int j = decltype(J)::value;
-          float vq = a4[j], vp = j == 0 ? pl : b4[j > 0 ? j - 1 : 0];
-          R4_OPAQUE(vq); R4_OPAQUE(vp);
-          R.Sqq[(j + S) % W] = vq;
-          R.Sqp[j] = vp;
-        });
-      } else {
-        R.Sqq[0] = *reinterpret_cast<const float*>(b + L::A + dn * 16);
-        R.Sqp[0] = pl;
-      }
-      R.Spq[LASTP] = *reinterpret_cast<const float*>(b + L::B + rt * 16 + 12);
-      R.Qpq[LASTP] = *reinterpret_cast<const float*>(b + L::C + rt * 4);
-      R.Qqq[LASTP] = *reinterpret_cast<const float*>(b + L::A + rt * 16 + 12);
+      R.Sqq[0] = *reinterpret_cast<const float*>(b + L::E + dn * 4);
+      R.Sqp[0] = *reinterpret_cast<const float*>(b + L::E + 1024 + dl * 4);
     }
+    const f32x2 pqin = *reinterpret_cast<const f32x2*>(b + L::PQ + rt * 8);
+    R.Spq[LASTP] = pqin[0]; R.Qpq[LASTP] = pqin[1];
+    R.Qqq[LASTP] = *reinterpret_cast<const float*>(b + L::E + 2048 + rt * 4);
   };
 
-#ifdef JACOBI_TS
-  unsigned long long busy = 0;
-#endif
   auto body = [&](auto SC, auto INC) {
     constexpr int S = decltype(SC)::value, CUR = S & 1, NX = CUR ^ 1;
     constexpr bool IN = decltype(INC)::value;
-#ifdef JACOBI_TS
-    const unsigned long long ts0 = __builtin_amdgcn_s_memtime();
-#endif
     const f32x2 rk = *reinterpret_cast<const f32x2*>(xb + CUR * 256 + a_k);
     f32x2 rl[W];
     static_for<W>([&](auto J) { constexpr int j = decltype(J)::value; rl[j] = *reinterpret_cast<const f32x2*>(xb + CUR * 256 + a_l[j]); });
@@ -584,26 +538,14 @@ __device__ __forceinline__ void strip_sets(Strip<W>& R, unsigned char* xb, float
       logw += log_step;
     }
     unsigned char* b = xb + NX * SX_BUF;
-    if constexpr (LAY == 0) {
-      if constexpr (W == 5) {
-        *reinterpret_cast<f32x4*>(b + L::QQ4 + (t - 64) * 16) = f32x4{nqq[0], nqq[1], nqq[2], nqq[3]};
-        *reinterpret_cast<f32x4*>(b + L::QP4 + (t - 64) * 16) = f32x4{nqp[0], nqp[1], nqp[2], nqp[3]};
-      }
-      *reinterpret_cast<float*>(b + L::E + t * 4) = nqq[W - 1];
-      *reinterpret_cast<float*>(b + L::E + 1024 + t * 4) = nqp[W - 1];
-      *reinterpret_cast<f32x2*>(b + L::PQ + t * 8) = f32x2{R.Spq[P0], R.Qpq[P0]};
-      *reinterpret_cast<float*>(b + L::E + 2048 + t * 4) = R.Qqq[P0];
-    } else {
-      float e0 = R.Spq[P0], e1 = R.Qpq[P0], e2 = R.Qqq[P0];
-      R4_OPAQUE(e0); R4_OPAQUE(e1); R4_OPAQUE(e2);
-      *reinterpret_cast<f32x4*>(b + L::A + t * 16) = f32x4{nqq[0], W > 1 ? nqq[W > 1 ? 1 : 0] : 0.f, W > 2 ? nqq[W > 2 ? 2 : 0] : 0.f, e2};
-      *reinterpret_cast<f32x4*>(b + L::B + t * 16) = f32x4{nqp[0], W > 1 ? nqp[W > 1 ? 1 : 0] : 0.f, W > 2 ? nqp[W > 2 ? 2 : 0] : 0.f, e0};
-      *reinterpret_cast<float*>(b + L::C + t * 4) = e1;
+    if constexpr (W == 5) {
+      *reinterpret_cast<f32x4*>(b + L::QQ4 + (t - 64) * 16) = f32x4{nqq[0], nqq[1], nqq[2], nqq[3]};
+      *reinterpret_cast<f32x4*>(b + L::QP4 + (t - 64) * 16) = f32x4{nqp[0], nqp[1], nqp[2], nqp[3]};
     }
-#ifdef JACOBI_TS
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    busy += __builtin_amdgcn_s_memtime() - ts0;                        // release of the previous barrier -> arrival at this one
-#endif
+    *reinterpret_cast<float*>(b + L::E + t * 4) = nqq[W - 1];
+    *reinterpret_cast<float*>(b + L::E + 1024 + t * 4) = nqp[W - 1];
+    *reinterpret_cast<f32x2*>(b + L::PQ + t * 8) = f32x2{R.Spq[P0], R.Qpq[P0]};
+    *reinterpret_cast<float*>(b + L::E + 2048 + t * 4) = R.Qqq[P0];
     __syncthreads();
   };
   body(std::integral_constant<int, 0>{}, std::false_type{});           // set 0: the strip is as loaded
@@ -611,7 +553,7 @@ __device__ __forceinline__ void strip_sets(Strip<W>& R, unsigned char* xb, float
   for (int it = 0; it < 30 / LCM; ++it) run_period<LCM>(body, std::make_integer_sequence<int, LCM>{});     // sets 1 .. 30
   body(std::integral_constant<int, 31 % LCM>{}, std::true_type{});     // set 31
   take_rim(std::integral_constant<int, 32 % LCM>{});                   // the arrangement of "set 32" = that of set 0
-  if (PWAVE || PRIO > 0) __builtin_amdgcn_s_setprio(0);
+  if (PWAVE) __builtin_amdgcn_s_setprio(0);
   // the scales of the 64 indices for strip_wave's scatter (the (a, b) slots of the buffer nobody reads any more: the last set
   // read the other one, and a barrier lies between)
   if (piv) {
@@ -627,13 +569,10 @@ __device__ __forceinline__ void strip_sets(Strip<W>& R, unsigned char* xb, float
     jacobi_rotation_stats(e[0], e[1], e[2], floor_m, e[3] != 0.f, off, sig);
     my_off = fmaxf(my_off, off); my_sig = fmaxf(my_sig, sig);
   }
-#ifdef JACOBI_TS
-  if ((t & 63) == 0 && blockIdx.x < 8192) jac_busy[blockIdx.x * 8 + (t >> 6)] = busy;
-#endif
 }
 
 // gather -> sets -> scatter for the lanes of one wave (strip width W); contains the barriers of the set loop and one more
-template <int LAY, int W, bool PWAVE, int PRIO = 0>
+template <int LAY, int W, bool PWAVE>
 __device__ __forceinline__ void strip_wave(float* simg, float* qimg, unsigned char* xb, int t, float floor_m, float& my_off, float& my_sig) {
   constexpr int B = 32;
   const int k = t & 31, sg = t >> 5;
@@ -649,7 +588,7 @@ __device__ __forceinline__ void strip_wave(float* simg, float* qimg, unsigned ch
     R.Sqp[j] = simg[(B + k) * SP + l];  R.Sqq[j] = simg[(B + k) * SP + B + l];
     R.Qpp[j] = one;  R.Qpq[j] = 0.f;  R.Qqp[j] = 0.f;  R.Qqq[j] = one;
   });
-  strip_sets<LAY, W, PWAVE, PRIO>(R, xb, simg, t, floor_m, my_off, my_sig);
+  strip_sets<LAY, W, PWAVE>(R, xb, simg, t, floor_m, my_off, my_sig);
   __syncthreads();                                  // every lane has taken its last rim: the exchange area becomes the Q image
   constexpr int LCM = (W % 2) ? 2 * W : W, SF = 32 % LCM;
   // the pending scales of the scaled rotations: S[i][j] = rho_i rho_j x stored, Q[r][j] = rho_j x stored (behind the Q image)
@@ -820,7 +759,6 @@ __device__ __forceinline__ void fused_d(const JacobiFusedArgs& p, int m, int g, 
   if (p.first) {
     if (p.st[m].done) return;
     floor_m = p.st[m].floor;
-    JTS(1);
     const float* Am = p.Pr + (size_t)m * C * C;
     {
       // (round 6: 16-byte pieces -- four consecutive columns lie in one block of the pair; 4 loads per lane where 16 scalar ones,
@@ -899,7 +837,6 @@ __device__ __forceinline__ void fused_d(const JacobiFusedArgs& p, int m, int g, 
     }
     if (p.st[m].done) return;                       // (block-uniform)
     floor_m = p.st[m].floor;
-    JTS(1);
     f32x4 crit = {0.f, 0.f, 0.f, 0.f};
     if (!same) {
 #pragma unroll
@@ -914,7 +851,6 @@ __device__ __forceinline__ void fused_d(const JacobiFusedArgs& p, int m, int g, 
         for (int r = 0; r < 4; ++r) Ws[(16 * trw + 4 * lq + r) * P4 + 16 * tj + li] = acc[r];
       }
       __syncthreads();
-      JTS(2);
       if (wave < (B / 16) * (B / 16)) {
 #pragma unroll
         for (int gg = 0; gg < NW; ++gg) {
@@ -923,7 +859,6 @@ __device__ __forceinline__ void fused_d(const JacobiFusedArgs& p, int m, int g, 
           for (int sx = 0; sx < 4; ++sx) crit = __builtin_amdgcn_mfma_f32_16x16x4f32(w4[sx], q2[gg][sx], crit, 0, 0, 0);
         }
       }
-      JTS(3);
     }
 #pragma unroll
     for (int i = 0; i < NV4; ++i) {
@@ -949,27 +884,19 @@ __device__ __forceinline__ void fused_d(const JacobiFusedArgs& p, int m, int g, 
     __syncthreads();
   }
   float* Qimg = jsm + SIMG_F;                       // [M2][SP] floats, TRANSPOSED (cross steps: epilogue only)
-  JTS(4);
   if (p.step_d >= 0) {
     {
       // ---- strips: gather, 32 sets, scatter, by wave (the branches execute the same barriers)
       unsigned char* xb = reinterpret_cast<unsigned char*>(jsm + SIMG_F);
       const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
       if (wv == 0) strip_wave<LAY, 1, true>(Simg, Qimg, xb, tid, floor_m, my_off, my_sig);
-#ifdef WCT_TUNING
-      else if (LAY == 0 && (p.dbg & 8)) strip_wave<LAY, 5, false, 1>(Simg, Qimg, xb, tid, floor_m, my_off, my_sig);   // strip waves at priority 1
-#endif
-      else if (LAY == 0) strip_wave<LAY, 5, false>(Simg, Qimg, xb, tid, floor_m, my_off, my_sig);
-      else if (wv == 1) strip_wave<LAY, 3, false>(Simg, Qimg, xb, tid, floor_m, my_off, my_sig);
-      else strip_wave<LAY, 2, false>(Simg, Qimg, xb, tid, floor_m, my_off, my_sig);
-      JTS(5);
+      else strip_wave<LAY, 5, false>(Simg, Qimg, xb, tid, floor_m, my_off, my_sig);
     }
   } else {
     // ---- intra step (always the first launch of a segment): waves 0 / 1 diagonalise the two 32 x 32 diagonal blocks in
     // registers (intra_wave); the off-diagonal block follows by two fp32-MFMA products, S_AB' = Q_A^T S_AB Q_B
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     if (wv < 2) intra_wave<M2>(Simg, Qimg, wv, lane, floor_m, my_off, my_sig);
-    JTS(5);
     __syncthreads();
     constexpr int WP = B + 4;
     float* Ws = jsm + 2 * SIMG_F;                   // [B][WP]
@@ -1030,11 +957,6 @@ __device__ __forceinline__ void fused_d(const JacobiFusedArgs& p, int m, int g, 
     if (my_sig > 0.f) atomicMax(&p.st[m].offsig, __float_as_uint(my_sig));
     if (my_dm > 0.f && my_dm < 3.0e38f) atomicMax(&p.st[m].dmax, __float_as_uint(my_dm));
   }
-  JTS(6);
-#ifdef JACOBI_TS
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  JTS(7);
-#endif
 }
 
 // U part: one task of the tile update (see jacobi_fused_u) by 256 threads: a wave owns a 16-row strip of the 64 x 64 tile

@@ -11,11 +11,9 @@
 //                     blend and re-centring folded into M and b)
 #include "common.h"
 #include <stdlib.h>
-#include <stdio.h>
 #include <algorithm>
 #include <type_traits>
 #include <utility>
-#include <vector>
 
 // A launcher that returns void (the per-launch helpers of the eigensolver's trains) notes a refused launch here, with the kernel's
 // name, the moment it happens; the train's driver returns it (launch_rc_take) instead of a generic failure at a later sync.
@@ -594,21 +592,7 @@ __global__ __launch_bounds__(256) void cov_finish_kernel(const float* partial, c
 //   fp32 MFMA (jacobi_update_kernel).  Two launches per step, C/B-1 steps per sweep.
 //   A per-matrix `done` flag turns later launches into no-ops.
 // ---------------------------------------------------------------------------
-#ifdef JACOBI_TS
-__device__ unsigned long long jac_ts[8192 * 10];
-__device__ unsigned long long jac_busy[8192 * 8];      // strip_sets: cycles each wave spent between the barriers of its 32 sets
-#define JTS(slot) do { if (threadIdx.x == 0 && blockIdx.x < 8192) { jac_ts[blockIdx.x * 10 + (slot)] = __builtin_amdgcn_s_memtime(); if ((slot) == 0) jac_ts[blockIdx.x * 10 + 8] = wall_clock64(); if ((slot) == 7) jac_ts[blockIdx.x * 10 + 9] = wall_clock64(); } } while (0)
-#else
-#define JTS(slot) do {} while (0)
-#endif
 #include "jacobi_dev.h"
-#ifdef WCT_TUNING
-#define JDBG(p) ((p).dbg)       // WCT_JACOBI_DBG timing experiments (results invalid): tuning builds only
-#else
-#define JDBG(p) 0
-#endif
-
-
 
 // The cross sweep with ONE wave carrying the rotation parameters ("pivot wave"), the default since round 2.
 // In jacobi_cross_sets every thread derives rotation(l) itself (~35 instructions with three transcendentals on a
@@ -623,15 +607,8 @@ __device__ unsigned long long jac_busy[8192 * 8];      // strip_sets: cycles eac
 //   * within a set every element of the {S, Q} image is read and written by exactly one thread, so the image is
 //     updated in place (one image instead of two); with PITCH = N the 8-byte accesses of a diagonal are conflict-free.
 // Per set a bulk wave issues ~45 instructions instead of ~100, and the dependent chain of a set is the pivot wave's.
-// exp_mode: timing experiments of a -DWCT_TUNING build (WCT_JACOBI_DBG: results INVALID); constant 0 in the product, so
-// none of their predicates exists in the shipped kernels
 template <int N>
-__device__ __forceinline__ void jacobi_cross_sets_pw(unsigned char* sq, unsigned char* csb, int t, float floor_m, float& my_off, float& my_sig, int exp_mode_in = 0) {
-#ifdef WCT_TUNING
-  const int exp_mode = exp_mode_in;
-#else
-  constexpr int exp_mode = 0;
-#endif
+__device__ __forceinline__ void jacobi_cross_sets_pw(unsigned char* sq, unsigned char* csb, int t, float floor_m, float& my_off, float& my_sig) {
   constexpr int NP = N / 2, ROWB = N * 8;                            // bytes per image row
   constexpr int CSB = NP * 8, DUMMY = 2 * CSB;                       // csb layout: CS[2][NP] float2 (c, s), dummy float2
   const int k = t & (NP - 1), d = t / NP;
@@ -686,21 +663,18 @@ __device__ __forceinline__ void jacobi_cross_sets_pw(unsigned char* sq, unsigned
       const int first = __builtin_amdgcn_readlane(qqn_i, 0);
       const float qq_next = __builtin_bit_cast(float, k == NP - 1 ? first : shl);
       ppk = ppn; qqk = qq_next; pqk = npq[0];
-      bool rot = false;
-      if (!(exp_mode & 16)) rot = jacobi_rotation_cs(ppk, qqk, pqk, ck, sk);     // (timing experiment: no rotation on the chain)
+      const bool rot = jacobi_rotation_cs(ppk, qqk, pqk, ck, sk);
       f32x2 r; r[0] = ck; r[1] = sk;
       *reinterpret_cast<f32x2*>(csb + (NX ? cs_w1 : cs_w0)) = r;
       float off, sig;
       jacobi_rotation_stats(ppk, qqk, pqk, floor_m, rot, off, sig);
       if (piv) { my_off = fmaxf(my_off, off); my_sig = fmaxf(my_sig, sig); }
     }
-    if (!(exp_mode & 64)) {                                          // (timing experiment: no image stores)
     *reinterpret_cast<f32x2*>(sq + a_pp) = npp;  *reinterpret_cast<f32x2*>(sq + a_pq) = npq;
     *reinterpret_cast<f32x2*>(sq + a_qp) = nqp;  *reinterpret_cast<f32x2*>(sq + a_qq) = nqq;
-    } else { my_off += npp[0] + npq[1] + nqp[0] + nqq[1]; }
     qk = NP | ((qk + 1) & (NP - 1));
     ql = NP | ((ql + 1) & (NP - 1));
-    if (!(exp_mode & 32)) __syncthreads();                           // (timing experiment: no barrier per set)
+    __syncthreads();
   };
 #pragma unroll 1
   for (int s = 0; s < NP; s += 2) {
@@ -730,8 +704,6 @@ static size_t jacobi_diag_lds(int step, bool pw) {
 // per wave.  The chain of a solve becomes D -> D -> D ...; the tile updates run beside it.
 // Data routing checked against the plain sequence in tools/jacobi_lookahead_proto.py.
 // ---------------------------------------------------------------------------
-// Phase timing build (-DJACOBI_TS, tools/r03_jacobi_ts.sh): lane 0 of every pair-problem block stamps s_memtime at its
-// phase boundaries; the launcher prints per-launch means.  Compiled out of the product.
 
 template <int M2>
 static size_t jacobi_fused_lds(int has_d, int has_u, int first, int step_d) {
@@ -764,9 +736,8 @@ __device__ __forceinline__ void jacobi_fused_d(const JacobiFusedArgs& p, int m, 
   float* Qo = p.Qw + ((size_t)m * npair + g) * (M2 * M2);
   float* So = p.Sw + ((size_t)m * npair + g) * (M2 * M2);
   if (p.first) {
-    if (p.st[m].done || (JDBG(p) & 2)) return;
+    if (p.st[m].done) return;
     floor_m = p.st[m].floor;
-    JTS(1);
     const float* Am = p.Pr + (size_t)m * C * C;
     const int PITCH = p.step_d >= 0 ? M2 : M2 + 1;
     for (int e = tid; e < M2 * M2; e += NT) {
@@ -822,15 +793,13 @@ __device__ __forceinline__ void jacobi_fused_d(const JacobiFusedArgs& p, int m, 
       qv = *reinterpret_cast<const f32x4*>(p.Qr + ((size_t)m * npair + (one ? g1 : g2)) * (M2 * M2) + (size_t)f * 4);
       Qdst = (one ? Q1s : Q2s) + qr * (B + 1) + qc;
     }
-    if (p.st[m].done || (JDBG(p) & 2)) return;        // (block-uniform)
+    if (p.st[m].done) return;        // (block-uniform)
     floor_m = p.st[m].floor;
-    JTS(1);
     f32x4 crit = {0.f, 0.f, 0.f, 0.f};
     if (!same) {
 #pragma unroll
       for (int j = 0; j < 4; ++j) { Xs[sr * (M2 + 1) + sc + j] = xv[j]; Qdst[j * (B + 1)] = qv[j]; }
       __syncthreads();
-      JTS(2);
       const int li = lane & 15, lq = lane >> 4;
       if (wave < (B / 16) * NW) {                   // W = Q_g1[:, h1]^T X   (B x M2)
         const int tr = wave / NW, tj = wave % NW;
@@ -849,7 +818,6 @@ __device__ __forceinline__ void jacobi_fused_d(const JacobiFusedArgs& p, int m, 
           crit = __builtin_amdgcn_mfma_f32_16x16x4f32(Ws[(16 * tr + li) * (M2 + 1) + kk + lq], Q2s[(kk + lq) * (B + 1) + 16 * tc + li], crit, 0, 0, 0);
       }
       __syncthreads();                              // the staging area becomes the image
-      JTS(3);
     }
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -874,10 +842,8 @@ __device__ __forceinline__ void jacobi_fused_d(const JacobiFusedArgs& p, int m, 
     }
     __syncthreads();
   }
-  JTS(4);
   if (p.step_d >= 0) {
-    if (!(JDBG(p) & 4)) jacobi_cross_sets_pw<M2>(reinterpret_cast<unsigned char*>(SQ), reinterpret_cast<unsigned char*>(jsm + 2 * M2 * M2), tid, floor_m, my_off, my_sig, JDBG(p));
-    JTS(5);
+    jacobi_cross_sets_pw<M2>(reinterpret_cast<unsigned char*>(SQ), reinterpret_cast<unsigned char*>(jsm + 2 * M2 * M2), tid, floor_m, my_off, my_sig);
     for (int e = tid; e < M2 * M2; e += NT) So[e] = SQ[e][0];
     int qr, qc;
     qfrag_rc<M2>(tid, qr, qc);                      // NT float4 = one tile, fragment order
@@ -899,7 +865,6 @@ __device__ __forceinline__ void jacobi_fused_d(const JacobiFusedArgs& p, int m, 
     constexpr int PITCH = M2 + 1;
     float* DO = jsm + 4 * M2 * PITCH;
     const int cur = jacobi_sets<SWEEP_INTRA, M2, KB>(SQ, DO, tid, floor_m, my_off, my_sig);
-    JTS(5);
     for (int e = tid; e < M2 * M2; e += NT) So[e] = SQ[cur * M2 * PITCH + (e / M2) * PITCH + (e % M2)][0];
     int qr, qc;
     qfrag_rc<M2>(tid, qr, qc);
@@ -929,11 +894,6 @@ __device__ __forceinline__ void jacobi_fused_d(const JacobiFusedArgs& p, int m, 
     if (my_sig > 0.f) atomicMax(&p.st[m].offsig, __float_as_uint(my_sig));
     if (my_dm > 0.f && my_dm < 3.0e38f) atomicMax(&p.st[m].dmax, __float_as_uint(my_dm));
   }
-  JTS(6);
-#ifdef JACOBI_TS
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  JTS(7);
-#endif
 }
 
 // tasks of one matrix: [off-diagonal tiles g < h][diagonal tile copies][V tiles (row block, column pair)]
@@ -1037,12 +997,11 @@ __global__ __launch_bounds__((M2 / 2) * (M2 / 2), M2 == 64 ? 8 : 2) void jacobi_
   int b = blockIdx.x;
   if (b < n_d) {
     const int m = b / npair, g = b % npair;
-    JTS(0);
     jacobi_fused_d<M2>(p, m, g, jsm);               // (checks the matrix' done flag itself, after issuing its loads)
   } else {
     b -= n_d;
     const int task = b / p.nmat, m = b % p.nmat;
-    if (p.st[m].done || (JDBG(p) & 1)) return;
+    if (p.st[m].done) return;
     jacobi_fused_u<M2>(p, m, task, jsm);
   }
 }
@@ -1065,16 +1024,12 @@ __global__ __launch_bounds__(r4::Lay<LAY>::NTD, 4) void jacobi_fused4_kernel(Jac
   const int n_d = p.has_d ? p.nmat * npair : 0;
   int b = blockIdx.x;
   if (b < n_d) {
-    // (p.mat_major: matrix index fastest, like the update tasks behind them -- with a multiple of 8 matrices every block that
-    //  touches matrix m, in this launch and the next, runs on XCD m % 8 and finds the images, logs and tiles in its L2)
-    const int m = p.mat_major ? b % p.nmat : b / npair, g = p.mat_major ? b / p.nmat : b % npair;
-    JTS(0);
-    if (JDBG(p) & 2) return;                 // (tuning builds, timing experiment: the pair problems exit at once -- results invalid)
+    const int m = b / npair, g = b % npair;
     r4::fused_d<M2, LAY>(p, m, g, jsm);
   } else {
     b -= n_d;
     const int task = b / p.nmat, m = b % p.nmat;
-    if (p.st[m].done || (JDBG(p) & 1)) return;   // (JDBG 1: the tile updates exit at once)
+    if (p.st[m].done) return;
     r4::fused_u<M2>(p, m, task, jsm);
   }
 }
@@ -1100,7 +1055,6 @@ struct VStripArgs {
   float* V; const half_t* Qlog;     // Qlog: [slot][nmat][npair][2*M2*M2] fp16 hi/lo fragments (qfrag16), slot = step - step_begin
   const JacobiState* st;
   int C, nmat, step_begin, step_end, seg;
-  int dbg;       // timing experiment (WCT_JACOBI_DBG & 128): return at once
   int mat_major; // grid (nmat, strips) instead of (strips, nmat): see vstrip_launch
 };
 
@@ -1131,7 +1085,7 @@ __global__ __launch_bounds__(W * 64) void jacobi_vstrip_kernel(VStripArgs p) {
   static_assert(NDMA >= 1 && NDMA * W * 1024 == TILE_BYTES, "a tile is a whole number of 1-KiB pieces per wave");
   extern __shared__ __attribute__((aligned(16))) unsigned char vs_ring[];
   const int m = p.mat_major ? blockIdx.x : blockIdx.y;
-  if (p.st[m].seg_stop <= p.seg || JDBG(p)) return;   // no rotations of this segment belong to the matrix (done before it began)
+  if (p.st[m].seg_stop <= p.seg) return;   // no rotations of this segment belong to the matrix (done before it began)
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int li = lane & 15, lq = lane >> 4;
   const int row0 = ((p.mat_major ? blockIdx.y : blockIdx.x) * W + wave) * 16;
@@ -1261,7 +1215,7 @@ __global__ __launch_bounds__(256) void jacobi_gather_kernel(float* A, const floa
 }
 
 constexpr int JACOBI_ROWSUM_MAX = 1024;                // words of row sums per matrix (C <= 1024; see JACOBI_ROW_K below)
-// mat0 = index of the group's first matrix in the 2P batch; skipped style matrices start out `done`
+// mat0 = index of the first matrix in the 2P batch (0: a solve takes the whole batch); skipped style matrices start out `done`
 __global__ __launch_bounds__(256) void jacobi_init_kernel(const float* A, float* V, JacobiState* st, int C, int mat0, int shared_style, unsigned* rowsum) {
   __shared__ float red[4];
   const int m = blockIdx.y;
@@ -1330,7 +1284,7 @@ struct JacobiCheckArgs {
   int mid;                   // 1: the test in the middle of a sweep (jacobi_check_mid)
   float tol_max, tol_fn;
   int buf, segs, lenient_from;
-  float row_k;               // JACOBI_ROW_K (tuning builds: WCT_JACOBI_ROW_K)
+  float row_k;               // JACOBI_ROW_K
 };
 
 // done: 0 = still rotating, 1 = converged, 2 = failed (a non-finite element reached a pair problem).
@@ -1516,12 +1470,10 @@ __global__ __launch_bounds__(64) void jacobi_check_kernel(JacobiState* st, const
 // a failed solve is never silently dropped.
 // stats (or null): this group's slot of the caller's solver statistics (host memory mapped into the device):
 // [0] matrices solved, [1] sum of their sweeps, [2] the largest sweep count -- wct_eig_stats reads and clears them
-__global__ void jacobi_finalize_kernel(const JacobiState* st, int* sweeps_out, int nmat, float tol_max, float tol_fn, volatile int* fail, int debug,
+__global__ void jacobi_finalize_kernel(const JacobiState* st, int* sweeps_out, int nmat, float tol_max, float tol_fn, volatile int* fail,
                                        volatile int* stats = nullptr) {
   const int m = threadIdx.x;
   int d = m < nmat ? st[m].done : 1;
-  if (debug && m < nmat)
-    printf("jacobi m=%d done=%d sweeps=%d last_sig=%.3e r2=%.3e r2l=%.3e floor=%.3e\n", m, st[m].done, st[m].sweeps, __uint_as_float(st[m].last_sig), st[m].r2, st[m].r2l, st[m].floor);
   // out of sweeps: good enough after all if the last sweep's significant pairs were below tol_max, or if the lenient
   // residual is within 4x of the target (second-order error 16x the target's: still inside the 1e-3 budget)
   // (second-order completion: error ~ r^3, and its stop threshold is already 4e-2 -- twice that is the most the 1e-3 budget takes)
@@ -1547,16 +1499,11 @@ __global__ void jacobi_finalize_kernel(const JacobiState* st, int* sweeps_out, i
 constexpr int JACOBI_MAX_SWEEPS = 16;   // round 3: 12 -> 16 (graded rank-deficient 512-channel spectra used 10-12; a failure stays loud)
 // WCT_JACOBI_MAX_SWEEPS (read at every solve): LOWERS the sweep budget so that the non-convergence path can be tested.  It
 // cannot raise it: a larger budget moves `lenient_from` and with it the sweep counts -- the output bits -- of slowly
-// converging matrices; only a tuning build accepts values above the compiled budget.
+// converging matrices.
 static int jacobi_max_sweeps() {
   const char* e = getenv("WCT_JACOBI_MAX_SWEEPS");
   const int n = e ? atoi(e) : JACOBI_MAX_SWEEPS;
-#ifdef WCT_TUNING
-  constexpr int cap = 30;
-#else
-  constexpr int cap = JACOBI_MAX_SWEEPS;
-#endif
-  return n < 1 ? 1 : (n > cap ? cap : n);
+  return n < 1 ? 1 : (n > JACOBI_MAX_SWEEPS ? JACOBI_MAX_SWEEPS : n);
 }
 
 size_t jacobi_workspace_bytes(int C, int nmat) {
@@ -1567,8 +1514,10 @@ size_t jacobi_workspace_bytes(int C, int nmat) {
          (size_t)nmat * (sizeof(JacobiState) + JACOBI_RESID_MAXTILES * JACOBI_RESID_STRIDE * sizeof(float) + JACOBI_ROWSUM_MAX * sizeof(unsigned));
 }
 
-// One group = a set of matrices on its own stream (the two halves of a batch run as two groups so
-// that one half's latency-bound pair problems hide under the other half's chip-wide tile update).
+// One solve: a batch of matrices on one stream.  (Until round 3 a batch could be split over up to four streams so that one
+// part's latency-bound pair problems hid under another's tile update -- profiles/r02_eig_groups.txt; with the look-ahead
+// launches a solve's pair problems run beside its own tile update, and more streams only split the chip: Jacobi ms per step
+// with 1 / 2 / 4 groups, batch 32: 20.6 / 21.0 / 22.5, batch 8: 9.3 / 11.9 / 10.0.)
 struct JacobiGroup {
   float* A; float* V; int nmat; float* Qbuf; JacobiState* st; float* resid; hipStream_t stream; int* sweeps_out;
   half_t* Qlog16[2];                         // the same rotation logs as fp16 hi/lo fragments (V <- V Q)
@@ -1576,24 +1525,26 @@ struct JacobiGroup {
                                              // consecutive steps, the two matrix buffers (P[0] = A)
   int cur, par, lg, segs;                    // buffer holding the matrices; generation of the last pair problems; log in use;
                                              // segments completed
-  int* done_host = nullptr;                  // the group's slot of JacobiHost::flags_dev (jacobi_check_kernel), or null
+  int* done_host = nullptr;                  // JacobiHost::flags_dev (jacobi_check_kernel), or null
   int u_f16 = 0;                             // tile updates on split fp16 (the batched transform path) or fp32 MFMA (wct_eigh, style-swap)
   int vstrip;                                // V is updated per segment by jacobi_vstrip_kernel on the side stream `vs`
   hipStream_t vs; hipEvent_t ev_seg, ev_v[2];// main -> side (segment enqueued), side -> main (log buffer free again)
   bool v_busy[2];
-  int mat0, shared_style;      // position in a WCT batch (skip_style_mat); 0, 0 for a plain batch
+  int shared_style;            // position in a WCT batch (skip_style_mat); 0 for a plain batch
   float tol_fn;                // > 0: also stop on the measured residual (callers that complete f(A) to first order)
-  int* fail;                   // device view of this group's slot [2] of the caller's status words, or null
-  int* stats;                  // device view of this group's statistics slot [3] for matrices of this size class, or null
+  int* fail;                   // device view of the caller's failure words [2], or null
+  int* stats;                  // device view of the caller's statistics slot [3] for matrices of this size class, or null
 };
 
-// per host thread (= per ctx user): pinned copies of the groups' convergence flags and one event per group
-// (events belong to the device that was current when they were created: one set per device, so that a thread driving
-//  contexts on several GPUs never records an event of GPU 0 on a stream of GPU 1 -- ADVICE r2)
-// flags: the `done` words of the groups' matrices, host memory MAPPED into the device ([4 groups][64]): jacobi_check_kernel stores
-// them there itself, and the host reads them after the sweep's event -- up to round 5 a device-to-host copy of the JacobiState
-// array per group and sweep carried them (45 copy kernels of ~5 us per step in the solver's launch trains, at every batch size)
-struct JacobiHost { int* flags; int* flags_dev; hipEvent_t ev[4]; hipStream_t vs[4]; hipEvent_t ev_seg[4], ev_v[4][2]; };
+// per host thread (= per ctx user) and device: pinned copies of the convergence flags, the event behind them, and the V pass's
+// stream and events (events belong to the device that was current when they were created: one set per device, so that a thread
+// driving contexts on several GPUs never records an event of GPU 0 on a stream of GPU 1 -- ADVICE r2)
+// flags: the `done` words of the solve's matrices, host memory MAPPED into the device ([64]): jacobi_check_kernel stores them
+// there itself, and the host reads them after the sweep's event -- up to round 5 a device-to-host copy of the JacobiState array
+// per sweep carried them (45 copy kernels of ~5 us per step in the solver's launch trains, at every batch size)
+// (the V-pass stream has the default priority: the lowest or the highest made the eigensolver 12.2 -> 22 ms per 32-pair step --
+//  profiles/r05_vprio.txt)
+struct JacobiHost { int* flags; int* flags_dev; hipEvent_t ev; hipStream_t vs; hipEvent_t ev_seg, ev_v[2]; };
 static JacobiHost* jacobi_host() {
   constexpr int MAXDEV = 16;
   static thread_local JacobiHost hs[MAXDEV] = {};
@@ -1601,35 +1552,16 @@ static JacobiHost* jacobi_host() {
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAXDEV) return nullptr;
   JacobiHost& h = hs[dev];
   if (!h.flags) {
-    if (hipHostMalloc((void**)&h.flags, 4 * 64 * sizeof(int), hipHostMallocMapped) != hipSuccess ||
+    if (hipHostMalloc((void**)&h.flags, 64 * sizeof(int), hipHostMallocMapped) != hipSuccess ||
         hipHostGetDevicePointer((void**)&h.flags_dev, h.flags, 0) != hipSuccess) { h.flags = nullptr; return nullptr; }
-    bool ok = true;
-    // (tuning builds: WCT_JACOBI_VPRIO = 1 / 2 puts the V-pass streams at the lowest / highest stream priority.  Measured, either
-    //  way: the eigensolver 12.2 -> 22 ms per 32-pair step, nothing at 8 pairs where the V pass does not run -- profiles/r05_vprio.txt)
-    static const int vprio = tune_int("WCT_JACOBI_VPRIO", 0);
-    int prio_lo = 0, prio_hi = 0;
-    if (vprio && hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi) != hipSuccess) prio_lo = prio_hi = 0;
-    const int prio = vprio == 1 ? prio_lo : vprio == 2 ? prio_hi : 0;
-    for (int g = 0; g < 4 && ok; ++g) {
-      ok = hipEventCreateWithFlags(&h.ev[g], hipEventDisableTiming) == hipSuccess &&
-           (vprio ? hipStreamCreateWithPriority(&h.vs[g], hipStreamNonBlocking, prio) : hipStreamCreateWithFlags(&h.vs[g], hipStreamNonBlocking)) == hipSuccess &&
-           hipEventCreateWithFlags(&h.ev_seg[g], hipEventDisableTiming) == hipSuccess &&
-           hipEventCreateWithFlags(&h.ev_v[g][0], hipEventDisableTiming) == hipSuccess &&
-           hipEventCreateWithFlags(&h.ev_v[g][1], hipEventDisableTiming) == hipSuccess;
-    }
+    const bool ok = hipEventCreateWithFlags(&h.ev, hipEventDisableTiming) == hipSuccess &&
+                    hipStreamCreateWithFlags(&h.vs, hipStreamNonBlocking) == hipSuccess &&
+                    hipEventCreateWithFlags(&h.ev_seg, hipEventDisableTiming) == hipSuccess &&
+                    hipEventCreateWithFlags(&h.ev_v[0], hipEventDisableTiming) == hipSuccess &&
+                    hipEventCreateWithFlags(&h.ev_v[1], hipEventDisableTiming) == hipSuccess;
     if (!ok) { (void)hipHostFree(h.flags); h.flags = nullptr; return nullptr; }
   }
   return &h;
-}
-
-// Pair-problem kernel of the 64-wide block pairs: 1 = strips over 4 waves (256 threads; the product), 2 = strips over 8 waves
-// (512 threads), 0 = the round-3 kernel (LDS-resident {S, Q} image, 1024 threads).  A-B switch of a tuning build
-// (WCT_JACOBI_R4); the product build compiles mode 1 only.  Measured (profiles/r04_jacobi_ab.txt), eigensolver ms per step at
-// batch 32 / 8 / 1: mode 1 14.4 / 7.6 / 6.0, mode 2 16.2 / 7.7 / 6.1 (same per-SIMD instruction load, more exchange
-// instructions), mode 0 17.1 / 8.0 / 6.4.
-static int jacobi_r4_mode() {
-  static const int on = tune_int("WCT_JACOBI_R4", 1);
-  return on;
 }
 
 // ---- look-ahead orchestration -------------------------------------------------------------------------------------
@@ -1647,98 +1579,33 @@ static void jacobi_fused_launch(JacobiGroup& G, int C, int seg_begin, bool has_d
   a.Sr = G.Sb[G.par]; a.Sw = G.Sb[G.par ^ 1];
   a.st = G.st; a.C = C; a.nmat = G.nmat; a.step_d = step_d; a.step_u = step_u;
   a.has_d = has_d; a.has_u = has_u; a.first = first; a.with_v = !G.vstrip; a.u_f16 = G.u_f16;
-  static const int xcd = tune_int("WCT_JACOBI_XCD", 1);
-  a.mat_major = (xcd & 2) && M2 == 64 && G.nmat % 8 == 0;
-  static const int dbg = tune_int("WCT_JACOBI_DBG", 0);
-  a.dbg = dbg;
   const unsigned grid = (has_d ? G.nmat * npair : 0) + (has_u ? G.nmat * ntask : 0);
-  // round 4 (M2 = 64): pair problems resident in registers (namespace r4, csrc/jacobi_dev.h); the 32-wide block pairs of
-  // C <= 128 keep the round-3 kernel
-  const int r4m = M2 == 64 ? jacobi_r4_mode() : 0;
+  // round 4 (M2 = 64): pair problems resident in registers, strips over 4 waves (namespace r4, csrc/jacobi_dev.h; against an
+  // 8-wave layout and the round-3 kernel, eigensolver ms per step at batch 32 / 8 / 1: 14.4 / 7.6 / 6.0 vs 16.2 / 7.7 / 6.1 and
+  // 17.1 / 8.0 / 6.4 -- profiles/r04_jacobi_ab.txt); the 32-wide block pairs of C <= 128 keep the round-3 kernel
   if constexpr (M2 == 64) {
-#ifdef WCT_TUNING
-    if (r4m == 2) hipLaunchKernelGGL((jacobi_fused4_kernel<M2, 1>), dim3(grid), dim3(r4::Lay<1>::NTD), (r4::fused_lds<M2, 1>(has_d, has_u, first, step_d)), G.stream, a);
-    else if (r4m == 0) hipLaunchKernelGGL((jacobi_fused_kernel<M2>), dim3(grid), dim3(NT), jacobi_fused_lds<M2>(has_d, has_u, first, step_d), G.stream, a);
-    else
-#endif
     hipLaunchKernelGGL((jacobi_fused4_kernel<M2, 0>), dim3(grid), dim3(r4::Lay<0>::NTD), (r4::fused_lds<M2, 0>(has_d, has_u, first, step_d)), G.stream, a);
     LAUNCH_NOTE("jacobi_fused4_kernel");
   } else {
     hipLaunchKernelGGL((jacobi_fused_kernel<M2>), dim3(grid), dim3(NT), jacobi_fused_lds<M2>(has_d, has_u, first, step_d), G.stream, a);
     LAUNCH_NOTE("jacobi_fused_kernel");
   }
-#ifdef JACOBI_TS
-  static const int ts_intra = getenv("WCT_TS_INTRA") != nullptr;      // (-DJACOBI_TS builds only) summarise the intra steps instead
-  if (has_d && M2 == 64 && (ts_intra ? step_d < 0 : (!first && step_d >= 0))) {
-    static int nlaunch = 0, last_nmat = 0;
-    static double sum[8] = {0}, span = 0;
-    if (G.nmat != last_nmat) { nlaunch = 0; span = 0; for (double& v : sum) v = 0; last_nmat = G.nmat; }
-    (void)hipStreamSynchronize(G.stream);
-    static unsigned long long host[8192 * 10];
-    (void)hipMemcpyFromSymbol(host, HIP_SYMBOL(jac_ts), sizeof(host));
-    const int nb = G.nmat * npair < 8192 ? G.nmat * npair : 8192;
-    unsigned long long lo = ~0ull, hi = 0;
-    for (int i = 0; i < nb; ++i) {
-      const unsigned long long* t = host + i * 10;
-      for (int k = 0; k < 7; ++k) sum[k] += (double)(t[k + 1] - t[k]) / nb;
-      if (t[8] < lo) lo = t[8];
-      if (t[9] > hi) hi = t[9];
-    }
-    if (nlaunch == 0) {
-      int occ = 0;
-      (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, jacobi_fused4_kernel<64, 0>, r4::Lay<0>::NTD, r4::fused_lds<64, 0>(has_d, has_u, first, step_d));
-      printf("jacobi_ts: occupancy API says %d blocks of %d threads per CU with %zu B of LDS\n", occ, r4::Lay<0>::NTD, r4::fused_lds<64, 0>(has_d, has_u, first, step_d));
-    }
-    span += (double)(hi - lo);
-    if (nlaunch == 40) {
-      std::vector<unsigned long long> st0, en0;
-      for (int i = 0; i < nb; ++i) { st0.push_back(host[i * 10 + 8] - lo); en0.push_back(host[i * 10 + 9] - lo); }
-      std::sort(st0.begin(), st0.end()); std::sort(en0.begin(), en0.end());
-      printf("jacobi_ts nmat %d launch 40: block start offsets (10 ns ticks) p0 %llu p25 %llu p50 %llu p75 %llu p90 %llu p100 %llu | end offsets p0 %llu p50 %llu p100 %llu\n", G.nmat,
-             st0[0], st0[nb / 4], st0[nb / 2], st0[3 * nb / 4], st0[9 * nb / 10], st0[nb - 1], en0[0], en0[nb / 2], en0[nb - 1]);
-    }
-    if (r4m) {
-      static unsigned long long hb[8192 * 8];
-      static double bs[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-      if (nlaunch == 0) for (double& v : bs) v = 0;
-      (void)hipMemcpyFromSymbol(hb, HIP_SYMBOL(jac_busy), sizeof(hb));
-      for (int i = 0; i < nb; ++i) for (int w = 0; w < 8; ++w) bs[w] += (double)hb[i * 8 + w] / nb;
-      if ((nlaunch + 1) % 32 == 0)
-        printf("jacobi_ts nmat %d: cycles between barrier release and next arrival, summed over the 32 sets, by wave: pivots %.0f | strips %.0f %.0f %.0f %.0f %.0f %.0f %.0f\n",
-               G.nmat, bs[0] / (nlaunch + 1), bs[1] / (nlaunch + 1), bs[2] / (nlaunch + 1), bs[3] / (nlaunch + 1), bs[4] / (nlaunch + 1), bs[5] / (nlaunch + 1), bs[6] / (nlaunch + 1), bs[7] / (nlaunch + 1));
-    }
-    if (++nlaunch % 32 == 0) {
-      printf("jacobi_ts nmat %d (%d launches): state %.0f | loads->LDS %.0f | crit %.0f | image %.0f | sets %.0f | stores issued %.0f | drained %.0f | first start -> last end %.0f wall-clock ticks (100 MHz) (others: s_memtime ticks)\n",
-             G.nmat, nlaunch, sum[0] / nlaunch, sum[1] / nlaunch, sum[2] / nlaunch, sum[3] / nlaunch, sum[4] / nlaunch, sum[5] / nlaunch, sum[6] / nlaunch, span / nlaunch);
-      fflush(stdout);
-    }
-  }
-#endif
   if (has_d) G.par ^= 1;
   if (has_u) G.cur ^= 1;
 }
 
-// which (block width, block count) combinations jacobi_vstrip_kernel is instantiated for
-template <int M2>
-static bool vstrip_supported(int C) {
-  const int nblk = C / (M2 / 2);
-  return M2 == 64 ? (nblk == 8 || nblk == 16) : (nblk == 2 || nblk == 4 || nblk == 8);
-}
-template <int M2>
+// V pass of a segment: the 64-wide block pairs of C = 256 and 512, the block counts jacobi_vstrip_kernel is instantiated for
 static void vstrip_launch(const JacobiGroup& G, int C, int step_begin, int step_end, hipStream_t s) {
-  const int nblk = C / (M2 / 2);
+  const int nblk = C / 32;
   VStripArgs a;
   a.V = G.V; a.Qlog = G.Qlog16[G.lg]; a.st = G.st; a.C = C; a.nmat = G.nmat; a.step_begin = step_begin; a.step_end = step_end; a.seg = G.segs;
-  static const int dbg = tune_int("WCT_JACOBI_DBG", 0);
-  a.dbg = dbg & 128;
   // Round 5: blocks are handed to the 8 XCDs round-robin by their linear index.  All the row strips of a matrix stream the SAME
   // rotation log (1 MB per 512-channel matrix and segment); with the strip index running fastest they sat on 8 different XCDs
   // and every one of the 8 L2s fetched every log from HBM.  With the MATRIX index running fastest (and a multiple of 8 matrices)
-  // the strips of matrix m all run on XCD m % 8 and share its L2.  WCT_JACOBI_XCD=0 (tuning builds): the old order.
-  static const int xcd = tune_int("WCT_JACOBI_XCD", 1);
-  a.mat_major = xcd && G.nmat % 8 == 0;
+  // the strips of matrix m all run on XCD m % 8 and share its L2.
+  a.mat_major = G.nmat % 8 == 0;
 #define VSTRIP_CASE(m2, nb, w) \
-  if (M2 == m2 && nblk == nb) {                                                                                      \
+  if (nblk == nb) {                                                                                                  \
     const size_t vs_lds = (vstrip_lds_bytes<m2, w>());                                                               \
     /* (every launch: cheap, idempotent, no per-device flag to race on -- ADVICE r5; a refusal is reported here) */   \
     if (vs_lds > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(&jacobi_vstrip_kernel<m2, nb, w>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)vs_lds) != hipSuccess) \
@@ -1746,52 +1613,39 @@ static void vstrip_launch(const JacobiGroup& G, int C, int step_begin, int step_
     hipLaunchKernelGGL((jacobi_vstrip_kernel<m2, nb, w>), a.mat_major ? dim3(G.nmat, C / 16 / w) : dim3(C / 16 / w, G.nmat), dim3(w * 64), vs_lds, s, a); \
     LAUNCH_NOTE("jacobi_vstrip_kernel");                                                                             \
   }
-  VSTRIP_CASE(64, 16, 4) VSTRIP_CASE(64, 8, 4) VSTRIP_CASE(32, 8, 4) VSTRIP_CASE(32, 4, 4) VSTRIP_CASE(32, 2, 2)
+  VSTRIP_CASE(64, 16, 4) VSTRIP_CASE(64, 8, 4)
 #undef VSTRIP_CASE
 }
 
 // before the first launch of a segment: its log buffer must not be in use by a V pass any more
-static int jacobi_segment_begin(JacobiGroup* grp, int ngrp) {
-  for (int g = 0; g < ngrp; ++g) {
-    JacobiGroup& G = grp[g];
-    if (G.vstrip && G.v_busy[G.lg]) { HIP_TRY(hipStreamWaitEvent(G.stream, G.ev_v[G.lg], 0)); G.v_busy[G.lg] = false; }
-  }
+static int jacobi_segment_begin(JacobiGroup& G) {
+  if (G.vstrip && G.v_busy[G.lg]) { HIP_TRY(hipStreamWaitEvent(G.stream, G.ev_v[G.lg], 0)); G.v_busy[G.lg] = false; }
   return WCT_OK;
 }
 // after the last launch of a segment (steps [step_begin, step_end)): hand its log to the V pass, switch logs
-template <int M2>
-static int jacobi_segment_end(JacobiGroup* grp, int ngrp, int C, int step_begin, int step_end) {
-  for (int g = 0; g < ngrp; ++g) {
-    JacobiGroup& G = grp[g];
-    if (G.vstrip) {
-      HIP_TRY(hipEventRecord(G.ev_seg, G.stream));
-      HIP_TRY(hipStreamWaitEvent(G.vs, G.ev_seg, 0));
-      vstrip_launch<M2>(G, C, step_begin, step_end, G.vs);
-      HIP_TRY(hipEventRecord(G.ev_v[G.lg], G.vs));
-      G.v_busy[G.lg] = true;
-      G.lg ^= 1;
-    }
-    G.segs += 1;
+static int jacobi_segment_end(JacobiGroup& G, int C, int step_begin, int step_end) {
+  if (G.vstrip) {
+    HIP_TRY(hipEventRecord(G.ev_seg, G.stream));
+    HIP_TRY(hipStreamWaitEvent(G.vs, G.ev_seg, 0));
+    vstrip_launch(G, C, step_begin, step_end, G.vs);
+    HIP_TRY(hipEventRecord(G.ev_v[G.lg], G.vs));
+    G.v_busy[G.lg] = true;
+    G.lg ^= 1;
   }
+  G.segs += 1;
   return WCT_OK;
 }
 
 // steps [step_begin, step_end) of one sweep as look-ahead launches: D(begin) | {D(s), U(s-1)} ... | U(end-1); afterwards
-// the matrices are complete in P[cur].  Launches of the groups are interleaved.  [lo, hi) restricts the launches that
-// are enqueued by this call to those of index lo..hi-1 (index = step of the D part; hi = step_end is the closing U).
+// the matrices are complete in P[cur].  [lo, hi) restricts the launches that are enqueued by this call to those of index
+// lo..hi-1 (index = step of the D part; hi = step_end is the closing U).
 template <int M2>
-static void jacobi_enqueue_segment(JacobiGroup* grp, int ngrp, int C, int step_begin, int step_end, int lo, int hi) {
+static void jacobi_enqueue_segment(JacobiGroup& G, int C, int step_begin, int step_end, int lo, int hi) {
   for (int step = lo; step < hi; ++step)
-    for (int g = 0; g < ngrp; ++g)
-      jacobi_fused_launch<M2>(grp[g], C, step_begin, step < step_end, step, step > step_begin, step - 1, step == step_begin);
+    jacobi_fused_launch<M2>(G, C, step_begin, step < step_end, step, step > step_begin, step - 1, step == step_begin);
 }
 
-static float jacobi_row_k() {
-  static const float k = tune_float("WCT_JACOBI_ROW_K", JACOBI_ROW_K);
-  return k;
-}
-
-// residual measurement of the group's matrices (in P[cur]), then the test `ck`
+// residual measurement of the matrices (in P[cur]), then the test `ck`
 static void jacobi_measure(JacobiGroup& G, int C, const JacobiCheckArgs& ck) {
   const int ntr = (C + JACOBI_RESID_T - 1) / JACOBI_RESID_T;
   const int ntile = ntr * (ntr + 1) / 2;
@@ -1802,86 +1656,77 @@ static void jacobi_measure(JacobiGroup& G, int C, const JacobiCheckArgs& ck) {
   LAUNCH_NOTE("jacobi_resid_kernel / jacobi_check_kernel");
 }
 
+constexpr int JACOBI_MID_FROM = 3;     // from this sweep on, a solve of 8 or more blocks with tol_fn > 0 also tests half-way through
+constexpr int JACOBI_VSTRIP_MIN = 24;  // the V pass (jacobi_vstrip_kernel) takes V out of the tile update from this many matrices on
+
 template <int M2>
-static int jacobi_run_groups_fused(JacobiGroup* grp, int ngrp, int C) {
+static int jacobi_run_fused(JacobiGroup& G, int C) {
   constexpr int B = M2 / 2;
   const int nblk = C / B;
   const int half = -1 + nblk / 2;                 // steps [-1, half) | [half, nblk - 1)
   const int max_sweeps = jacobi_max_sweeps();
-  static const float conv_tol = tune_float("WCT_JACOBI_CONV_TOL", JACOBI_CONV_TOL);
-  static const int mid_env = tune_int("WCT_JACOBI_MID", 3);
-  // V in registers, per segment (jacobi_vstrip_kernel): 0 never, 1 from WCT_JACOBI_VSTRIP_MIN matrices per group on, 2 always
-  static const int vs_env = tune_int("WCT_JACOBI_VSTRIP", 1);
-  static const int vs_min = tune_int("WCT_JACOBI_VSTRIP_MIN", 24);
-  const int mid_from = nblk >= 8 ? mid_env : -1;
+  const bool mid_test = nblk >= 8 && G.tol_fn > 0.f;
   JacobiHost* host = jacobi_host();
-  for (int g = 0; g < ngrp; ++g) {
-    JacobiGroup& G = grp[g];
-    G.cur = 0; G.par = 0; G.lg = 0; G.segs = 0; G.v_busy[0] = G.v_busy[1] = false;
-    G.vstrip = host && g < 4 && vstrip_supported<M2>(C) && (vs_env == 2 || (vs_env == 1 && G.nmat >= vs_min && C >= 256));
-    if (G.vstrip) { G.vs = host->vs[g]; G.ev_seg = host->ev_seg[g]; G.ev_v[0] = host->ev_v[g][0]; G.ev_v[1] = host->ev_v[g][1]; }
-    G.done_host = host && g < 4 ? host->flags_dev + g * 64 : nullptr;
-    hipLaunchKernelGGL(jacobi_init_kernel, dim3(64, G.nmat), dim3(256), 0, G.stream, G.A, G.V, G.st, C, G.mat0, G.shared_style,
-                       reinterpret_cast<unsigned*>(G.resid + (size_t)G.nmat * JACOBI_RESID_MAXTILES * JACOBI_RESID_STRIDE));
-    HIP_TRY(hipGetLastError());
-  }
+  G.cur = 0; G.par = 0; G.lg = 0; G.segs = 0; G.v_busy[0] = G.v_busy[1] = false;
+  // V in registers, per segment: C = 256 and 512 (64-wide block pairs; the V pass is not instantiated for others)
+  G.vstrip = host && M2 == 64 && (nblk == 8 || nblk == 16) && G.nmat >= JACOBI_VSTRIP_MIN;
+  if (G.vstrip) { G.vs = host->vs; G.ev_seg = host->ev_seg; G.ev_v[0] = host->ev_v[0]; G.ev_v[1] = host->ev_v[1]; }
+  G.done_host = host ? host->flags_dev : nullptr;
+  hipLaunchKernelGGL(jacobi_init_kernel, dim3(64, G.nmat), dim3(256), 0, G.stream, G.A, G.V, G.st, C, 0, G.shared_style,
+                     reinterpret_cast<unsigned*>(G.resid + (size_t)G.nmat * JACOBI_RESID_MAXTILES * JACOBI_RESID_STRIDE));
+  HIP_TRY(hipGetLastError());
   bool pending = false;
   int rc;
   for (int sweep = 0; sweep < max_sweeps; ++sweep) {
-    bool mid = false;
-    if (mid_from >= 0 && sweep >= mid_from)
-      for (int g = 0; g < ngrp; ++g) mid = mid || grp[g].tol_fn > 0.f;
+    const bool mid = mid_test && sweep >= JACOBI_MID_FROM;
     // segments of this sweep: [-1, half) + [half, nblk - 1) around a residual test, or the whole sweep in one
     const int end1 = mid ? half : nblk - 1;
-    if ((rc = jacobi_segment_begin(grp, ngrp))) return rc;
+    if ((rc = jacobi_segment_begin(G))) return rc;
     // the flags of the previous sweep are looked at once half a sweep of launches is enqueued (the GPU never idles)
-    jacobi_enqueue_segment<M2>(grp, ngrp, C, -1, end1, -1, half);
+    jacobi_enqueue_segment<M2>(G, C, -1, end1, -1, half);
     if (pending) {
+      HIP_TRY(hipEventSynchronize(host->ev));
       bool all = true;
-      for (int g = 0; g < ngrp; ++g) {
-        HIP_TRY(hipEventSynchronize(host->ev[g]));
-        for (int m = 0; m < grp[g].nmat; ++m) all = all && host->flags[g * 64 + m] != 0;
-      }
+      for (int m = 0; m < G.nmat; ++m) all = all && host->flags[m] != 0;
       pending = false;
       if (all) break;          // every matrix was done before this sweep began: its launches were no-ops
     }
-    jacobi_enqueue_segment<M2>(grp, ngrp, C, -1, end1, half, end1 + 1);
-    if ((rc = jacobi_segment_end<M2>(grp, ngrp, C, -1, end1))) return rc;
+    jacobi_enqueue_segment<M2>(G, C, -1, end1, half, end1 + 1);
+    if ((rc = jacobi_segment_end(G, C, -1, end1))) return rc;
     if (mid) {
-      for (int g = 0; g < ngrp; ++g)
-        if (grp[g].tol_fn > 0.f) {
-          jacobi_measure(grp[g], C, JacobiCheckArgs{1, conv_tol, grp[g].tol_fn, grp[g].cur, grp[g].segs, 1 << 30, jacobi_row_k()});
-        }
-      if ((rc = jacobi_segment_begin(grp, ngrp))) return rc;
-      jacobi_enqueue_segment<M2>(grp, ngrp, C, half, nblk - 1, half, nblk);
-      if ((rc = jacobi_segment_end<M2>(grp, ngrp, C, half, nblk - 1))) return rc;
+      jacobi_measure(G, C, JacobiCheckArgs{1, JACOBI_CONV_TOL, G.tol_fn, G.cur, G.segs, 1 << 30, JACOBI_ROW_K});
+      if ((rc = jacobi_segment_begin(G))) return rc;
+      jacobi_enqueue_segment<M2>(G, C, half, nblk - 1, half, nblk);
+      if ((rc = jacobi_segment_end(G, C, half, nblk - 1))) return rc;
     }
-    for (int g = 0; g < ngrp; ++g) {
-      jacobi_measure(grp[g], C, JacobiCheckArgs{0, conv_tol, grp[g].tol_fn, grp[g].cur, grp[g].segs, max_sweeps - 3, jacobi_row_k()});
-    }
+    jacobi_measure(G, C, JacobiCheckArgs{0, JACOBI_CONV_TOL, G.tol_fn, G.cur, G.segs, max_sweeps - 3, JACOBI_ROW_K});
     if (host && sweep >= 2 && sweep + 1 < max_sweeps) {
-      for (int g = 0; g < ngrp; ++g) {
-        HIP_TRY(hipEventRecord(host->ev[g], grp[g].stream));      // (behind the sweep's jacobi_check_kernel, which stored the flags)
-      }
+      HIP_TRY(hipEventRecord(host->ev, G.stream));      // (behind the sweep's jacobi_check_kernel, which stored the flags)
       pending = true;
     }
   }
-  for (int g = 0; g < ngrp; ++g) {
-    JacobiGroup& G = grp[g];
-    for (int l = 0; l < 2; ++l)            // the V passes still in flight belong to this solve
-      if (G.vstrip && G.v_busy[l]) { HIP_TRY(hipStreamWaitEvent(G.stream, G.ev_v[l], 0)); G.v_busy[l] = false; }
-    hipLaunchKernelGGL(jacobi_gather_kernel, dim3(32, G.nmat), dim3(256), 0, G.stream, G.A, G.P[1], G.st, C, G.cur);
-    HIP_TRY(hipGetLastError());
-    if (G.sweeps_out || G.fail || G.stats)
-      hipLaunchKernelGGL(jacobi_finalize_kernel, dim3(1), dim3(64), 0, G.stream, G.st, G.sweeps_out, G.nmat, conv_tol, G.tol_fn, G.fail, tune_set("WCT_JACOBI_DEBUG"), G.stats);
-      HIP_TRY(hipGetLastError());
-  }
+  for (int l = 0; l < 2; ++l)            // the V passes still in flight belong to this solve
+    if (G.vstrip && G.v_busy[l]) { HIP_TRY(hipStreamWaitEvent(G.stream, G.ev_v[l], 0)); G.v_busy[l] = false; }
+  hipLaunchKernelGGL(jacobi_gather_kernel, dim3(32, G.nmat), dim3(256), 0, G.stream, G.A, G.P[1], G.st, C, G.cur);
   HIP_TRY(hipGetLastError());
-  return launch_rc_take();           // a launch one of the train's void helpers saw refused (named there)
+  if (G.sweeps_out || G.fail || G.stats) {
+    hipLaunchKernelGGL(jacobi_finalize_kernel, dim3(1), dim3(64), 0, G.stream, G.st, G.sweeps_out, G.nmat, JACOBI_CONV_TOL, G.tol_fn, G.fail, G.stats);
+    HIP_TRY(hipGetLastError());
+  }
+  return WCT_OK;
+}
+
+// statistics slot for matrices of order C inside the caller's status words: after the 2 failure words come [6 size classes][3]
+// counters (size class = log2(C / 32), capped)
+static int* jacobi_stats_slot(int* eig_fail, int C) {
+  if (!eig_fail) return nullptr;
+  int cls = 0;
+  for (int c = C / 32; c > 1 && cls < 5; c >>= 1) ++cls;
+  return eig_fail + 2 + cls * 3;
 }
 
 static int jacobi_make_group(JacobiGroup* G, float* A, float* V, int C, int nmat, void* workspace, size_t workspace_bytes,
-                             int* sweeps_out, int* fail, hipStream_t s, int* stats = nullptr) {
+                             int* sweeps_out, int* eig_fail, hipStream_t s) {
   ARG_CHECK(C % 32 == 0 && C >= 32 && C <= 1024 && nmat >= 1 && nmat <= 64);
   ARG_CHECK(workspace_bytes >= jacobi_workspace_bytes(C, nmat));
   const size_t cc = (size_t)C * C;
@@ -1895,37 +1740,27 @@ static int jacobi_make_group(JacobiGroup* G, float* A, float* V, int C, int nmat
   G->st = reinterpret_cast<JacobiState*>(reinterpret_cast<char*>(workspace) + ((qbytes + 255) / 256) * 256);
   G->resid = reinterpret_cast<float*>(reinterpret_cast<char*>(G->st) + (((size_t)nmat * sizeof(JacobiState) + 255) / 256) * 256);
   G->tol_fn = 0.f;
-  G->stream = s; G->sweeps_out = sweeps_out; G->fail = fail; G->stats = stats;
-  G->mat0 = 0; G->shared_style = 0;
+  G->stream = s; G->sweeps_out = sweeps_out; G->fail = eig_fail; G->stats = jacobi_stats_slot(eig_fail, C);
+  G->shared_style = 0;
   return WCT_OK;
 }
 
-static int jacobi_dispatch(JacobiGroup* grp, int ngrp, int C) {
-  // block pairs of 64 indices (32-column blocks) by default; WCT_JACOBI_M2=32 selects 16-column blocks
-  static const int force32 = tune_int("WCT_JACOBI_M2", 0) == 32;
-  static const int force64 = tune_int("WCT_JACOBI_M2", 0) == 64;
+static int jacobi_dispatch(JacobiGroup& G, int C) {
   // measured (16 matrices): 64-wide pairs win from C = 256 up (half the tile traffic), 32-wide below
   // (the round-2 two-launch steps -- separate pair-problem and tile-update kernels -- were deleted in round 4: the
   //  look-ahead launches have been the only path since round 3)
-  const bool m64 = !force32 && C % 64 == 0 && (C >= 256 || force64);
-  return m64 ? jacobi_run_groups_fused<64>(grp, ngrp, C) : jacobi_run_groups_fused<32>(grp, ngrp, C);
-}
-
-// statistics slot of stream group g for matrices of order C inside the caller's status words: after the 8 failure
-// words come [4 groups][6 size classes][3] counters (size class = log2(C / 32), capped)
-static int* jacobi_stats_slot(int* eig_fail, int g, int C) {
-  if (!eig_fail) return nullptr;
-  int cls = 0;
-  for (int c = C / 32; c > 1 && cls < 5; c >>= 1) ++cls;
-  return eig_fail + 8 + (g * 6 + cls) * 3;
+  const bool m64 = C % 64 == 0 && C >= 256;
+  const int rc = m64 ? jacobi_run_fused<64>(G, C) : jacobi_run_fused<32>(G, C);
+  const int noted = launch_rc_take();  // a launch one of the train's void helpers saw refused (named there); cleared on every exit
+  return rc ? rc : noted;
 }
 
 int launch_jacobi_eigh(float* A, float* V, int C, int nmat, void* workspace, size_t workspace_bytes,
                        int* sweeps_done_dev, int* eig_fail, hipStream_t s) {
   JacobiGroup G;
-  int rc = jacobi_make_group(&G, A, V, C, nmat, workspace, workspace_bytes, sweeps_done_dev, eig_fail, s, jacobi_stats_slot(eig_fail, 0, C));
+  int rc = jacobi_make_group(&G, A, V, C, nmat, workspace, workspace_bytes, sweeps_done_dev, eig_fail, s);
   if (rc) return rc;
-  return jacobi_dispatch(&G, 1, C);
+  return jacobi_dispatch(G, C);
 }
 
 // ---------------------------------------------------------------------------
@@ -2269,11 +2104,8 @@ __global__ __launch_bounds__(256) void spectral_add2_all_kernel(SpecAllArgs a) {
   }
 }
 
-// 0: spectral functions of the diagonal only, 1: + first-order completion, 2 (default): + second-order completion
-static int eig_correct_enabled() {
-  static const int on = tune_int("WCT_EIG_CORRECT", 2);
-  return on;
-}
+// 0: spectral functions of the diagonal only, 1: + first-order completion, 2 (the product): + second-order completion
+constexpr int EIG_CORRECT = 2;
 // residual at which the WCT path stops sweeping.  Calibrated on the level features of a 512x512 frame
 // (profiles/r02_eig_calibration.txt): with r2 the strict measure at the stop, the transform error is ~0.55 sqrt(r2)
 // without the first-order completion and ~0.8 r2 (+ ~3e-5 from the other stages) with it, so 1.5e-2 bounds the
@@ -2281,10 +2113,7 @@ static int eig_correct_enabled() {
 constexpr float JACOBI_TOL_FN = 1.5e-2f;
 constexpr float JACOBI_TOL_FN2 = 4e-2f;            // with the second-order completion (profiles/r03_eig_calibration.txt: the transform error
                                                    // at 4e-2 with it, 3.1e-5 .. 1.3e-4, is what 1.5e-2 gave without it, one sweep later)
-static float jacobi_tol_fn() {
-  static const float t = tune_float("WCT_JACOBI_TOL_FN", eig_correct_enabled() >= 2 ? JACOBI_TOL_FN2 : (eig_correct_enabled() ? JACOBI_TOL_FN : 0.f));
-  return t;          // (tuning builds: an explicit WCT_JACOBI_TOL_FN also applies without the completion -- calibration runs)
-}
+constexpr float JACOBI_TOL_FN_WCT = EIG_CORRECT >= 2 ? JACOBI_TOL_FN2 : (EIG_CORRECT ? JACOBI_TOL_FN : 0.f);   // the one in use
 
 // out[b] = V[b] G[b] V[b]^T for nbatch matrices (strides in elements); X: scratch of the same shape as G
 // scratch2: 5 * nbatch * C * C floats for the second-order completion (or null: first order at most)
@@ -2292,9 +2121,9 @@ static int launch_spectral_function(const float* A, const float* V, float* G, fl
                                     size_t stride, size_t out_stride, int kind, float shift, hipStream_t s, float* scratch2 = nullptr) {
   const size_t cc = (size_t)C * C;
   const dim3 tiles(cdiv(C, 64), cdiv(C, 64), nbatch);
-  hipLaunchKernelGGL(spectral_matrix_kernel, tiles, dim3(256), 0, s, A, G, C, stride, kind, shift, eig_correct_enabled());
+  hipLaunchKernelGGL(spectral_matrix_kernel, tiles, dim3(256), 0, s, A, G, C, stride, kind, shift, EIG_CORRECT);
   HIP_TRY(hipGetLastError());
-  if (scratch2 && eig_correct_enabled() >= 2) {
+  if (scratch2 && EIG_CORRECT >= 2) {
     float* N = scratch2; float* R = N + nbatch * cc; float* Pm = R + nbatch * cc; float* X1 = Pm + nbatch * cc; float* X2 = X1 + nbatch * cc;
     hipLaunchKernelGGL(spectral_prep2_kernel, tiles, dim3(256), 0, s, A, N, R, Pm, C, stride, kind, shift);
     HIP_TRY(hipGetLastError());
@@ -2560,7 +2389,8 @@ static WctCarve carve(void* base, int C, int Nc, int Ns, int P) {
   w.M = (float*)take(P * cc);
   w.bias = (float*)take((size_t)P * C * sizeof(float));
   w.mabs = (unsigned*)take((size_t)P * sizeof(unsigned));
-  w.jacobi_bytes = jacobi_workspace_bytes(C, 2 * P) + 4 * (1024 + 64 * sizeof(JacobiState));   // up to 4 groups
+  w.jacobi_bytes = jacobi_workspace_bytes(C, 2 * P) + 4 * (1024 + 64 * sizeof(JacobiState));   // (+ the alignment slack of
+                                                                                                 //  the former four-group split)
   w.jacobi_ws = take(w.jacobi_bytes);
   w.total = off;
   return w;
@@ -2611,27 +2441,12 @@ static int launch_refresh(const WctCarve& w, int C, int P, int shared_style, hip
   r2.M = C; r2.N = C; r2.K = C; r2.ksplit = C; r2.out32 = w.A; r2.ldo = C; r2.s_out = cc;
   if (!always) r2.mask_in = w.refresh;
   rc = launch_gemm(r2, 1, 2 * P, s);
-#ifdef WCT_TUNING
-  // WCT_REFRESH_STATS=1 (tuning builds): how often the predicate fires -- the flags are read back after every call (a stream
-  // sync: measurement only) and the running totals printed, per channel count
-  if (!rc && !always && tune_set("WCT_REFRESH_STATS")) {
-    static long fired[5] = {0, 0, 0, 0, 0}, seen[5] = {0, 0, 0, 0, 0};
-    int flags[64];
-    if (hipMemcpyAsync(flags, w.refresh, (size_t)2 * P * sizeof(int), hipMemcpyDeviceToHost, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess) {
-      const int cls = C >= 512 ? 4 : (C >= 256 ? 3 : (C >= 128 ? 2 : (C >= 64 ? 1 : 0)));
-      for (int m = 0; m < 2 * P; ++m) if (!skip_style_mat(m, shared_style)) { seen[cls] += 1; fired[cls] += flags[m] != 0; }
-      fprintf(stderr, "refresh fired (running totals) C<=32 %ld/%ld | 64 %ld/%ld | 128 %ld/%ld | 256 %ld/%ld | 512+ %ld/%ld\n",
-              fired[0], seen[0], fired[1], seen[1], fired[2], seen[2], fired[3], seen[3], fired[4], seen[4]);
-    }
-  }
-#endif
   return rc;
 }
 
 int launch_wct(const float* content, int Nc, const float* style, int Ns, int C, int P, float alpha, int mode, float eps_in,
                half_t* out16, float* out32, void* workspace, size_t workspace_bytes, int* sweeps_dev,
-               int stages, hipStream_t s, const hipStream_t* side, int nside, hipEvent_t ev_fork,
-               const hipEvent_t* ev_join, int shared_style, int* eig_fail, const WctFeatStats* stats) {
+               int stages, hipStream_t s, int shared_style, int* eig_fail, const WctFeatStats* stats) {
   ARG_CHECK(C % 32 == 0 && C >= 32 && C <= 1024 && Nc >= 2 && Ns >= 2 && P >= 1 && P <= 32);
   ARG_CHECK(mode == WCT_MODE_NP || mode == WCT_MODE_TF);
   // the covariance kernel addresses one feature map through a buffer resource with 32-bit byte offsets
@@ -2664,48 +2479,11 @@ int launch_wct(const float* content, int Nc, const float* style, int Ns, int C, 
   HIP_TRY(hipGetLastError());
   }
   if (stages & WCT_STAGE_EIG) {
-    if (nside > 0 && P >= 2) {
-      // The eigensolver alternates a latency-bound kernel on a few workgroups (pair problems) with a
-      // chip-wide tile update.  Splitting the batch into groups on separate streams lets one group's
-      // pair problems hide under the other groups' tile updates.
-      // measured per 5-level step with the pivot-wave pair kernel (round 2, profiles/r02_eig_groups.txt), Jacobi ms:
-      // batch 32: 1 group 31.6, 2: 30.0, 3: 28.4, 4: 28.0; batch 16: 19.9 / 19.5 / - / 18.2; batch 8: 15.6 / 15.5 / 15.2 /
-      // 15.6; batch 4: 13.2 / 13.5 / - / 14.1; batch 2: 11.8 / 12.1 / - / 12.9 -- many matrices: one group's pair
-      // problems hide under the other groups' tile updates; few: every extra stream only adds launch traffic
-      // round 3: with the look-ahead launches a group's pair problems already run beside its own tile update, and more
-      // groups only split the chip (Jacobi ms per step, 1 / 2 / 4 groups: batch 32: 20.6 / 21.0 / 22.5, batch 8: 9.3 / 11.9 / 10.0)
-      static const int fused_on = tune_int("WCT_JACOBI_FUSED", 1);
-      int ngrp = fused_on ? 1 : (P >= 12 ? 4 : (P >= 6 ? 2 : 1));
-      if (ngrp > nside + 1) ngrp = nside + 1;
-      static const int force_ngrp = tune_int("WCT_EIG_NGRP", 0);   // tuning switch
-      if (force_ngrp >= 1 && force_ngrp <= 4 && force_ngrp <= nside + 1) ngrp = force_ngrp;
-      JacobiGroup grp[4];
-      HIP_TRY(hipEventRecord(ev_fork, s));
-      size_t off = 0;
-      int m0 = 0;
-      for (int g = 0; g < ngrp; ++g) {
-        const int n = (2 * P * (g + 1)) / ngrp - (2 * P * g) / ngrp;
-        const size_t bytes = (jacobi_workspace_bytes(C, n) + 255) & ~(size_t)255;
-        hipStream_t sg = g == 0 ? s : side[g - 1];
-        if (g > 0) HIP_TRY(hipStreamWaitEvent(sg, ev_fork, 0));
-        if ((rc = jacobi_make_group(&grp[g], w.A + (size_t)m0 * cc, w.V + (size_t)m0 * cc, C, n, (char*)w.jacobi_ws + off,
-                                    bytes, sweeps_dev ? sweeps_dev + m0 : nullptr, eig_fail ? eig_fail + 2 * g : nullptr, sg, jacobi_stats_slot(eig_fail, g, C)))) return rc;
-        grp[g].mat0 = m0; grp[g].shared_style = shared_style; grp[g].tol_fn = jacobi_tol_fn();
-        grp[g].u_f16 = (stages & WCT_STAGE_EIG_FP32UPDATE) ? 0 : 1;
-        off += bytes; m0 += n;
-      }
-      if ((rc = jacobi_dispatch(grp, ngrp, C))) return rc;
-      for (int g = 1; g < ngrp; ++g) {
-        HIP_TRY(hipEventRecord(ev_join[g - 1], side[g - 1]));
-        HIP_TRY(hipStreamWaitEvent(s, ev_join[g - 1], 0));
-      }
-    } else {
-      JacobiGroup G;
-      if ((rc = jacobi_make_group(&G, w.A, w.V, C, 2 * P, w.jacobi_ws, w.jacobi_bytes, sweeps_dev, eig_fail, s, jacobi_stats_slot(eig_fail, 0, C)))) return rc;
-      G.shared_style = shared_style; G.tol_fn = jacobi_tol_fn();
-      G.u_f16 = (stages & WCT_STAGE_EIG_FP32UPDATE) ? 0 : 1;
-      if ((rc = jacobi_dispatch(&G, 1, C))) return rc;
-    }
+    JacobiGroup G;
+    if ((rc = jacobi_make_group(&G, w.A, w.V, C, 2 * P, w.jacobi_ws, w.jacobi_bytes, sweeps_dev, eig_fail, s))) return rc;
+    G.shared_style = shared_style; G.tol_fn = JACOBI_TOL_FN_WCT;
+    G.u_f16 = (stages & WCT_STAGE_EIG_FP32UPDATE) ? 0 : 1;
+    if ((rc = jacobi_dispatch(G, C))) return rc;
   }
   if (!(stages & WCT_STAGE_APPLY)) return WCT_OK;
 
@@ -2714,11 +2492,11 @@ int launch_wct(const float* content, int Nc, const float* style, int Ns, int C, 
     // off-diagonals; the wct_np semantics shift the kept eigenvalues by eps inside the gains (ops.py:114,127), wct_tf does not.
     // One launch of each kind over all 2P matrices of the level (see spectral_open_all_kernel).
     const float shift = mode == WCT_MODE_NP ? (eps_in >= 0.f ? eps_in : 1e-5f) : 0.f;
-    const int second = eig_correct_enabled() >= 2;
+    const int second = EIG_CORRECT >= 2;
     const dim3 tiles(cdiv(C, 64), cdiv(C, 64), 2 * P);
     if ((rc = launch_refresh(w, C, P, shared_style, s))) return rc;
     SpecAllArgs sa = {};
-    sa.A = w.A; sa.G = w.G; sa.C = C; sa.shift = shift; sa.correct = eig_correct_enabled(); sa.second = second; sa.shared_style = shared_style;
+    sa.A = w.A; sa.G = w.G; sa.C = C; sa.shift = shift; sa.correct = EIG_CORRECT; sa.second = second; sa.shared_style = shared_style;
     sa.N = w.S2; float* X2 = sa.N + 2 * P * cc; sa.R = X2 + 2 * P * cc; sa.Pm = sa.R + P * cc; float* X1 = sa.Pm + P * cc;
     sa.X1 = X1; sa.X2 = X2;
     sa.mabs = w.mabs; sa.mean = w.mean; sa.bias = w.bias; sa.alpha = alpha; sa.mode = mode;
@@ -2969,7 +2747,7 @@ int launch_style_swap(const float* content, int hc, int wc, const float* style, 
   int rc;
   // statistics, covariances (+eps I), eigendecompositions: the same stages as wct_tf
   if ((rc = launch_wct(content, Nc, style, Ns, C, 1, alpha, WCT_MODE_TF, eps, nullptr, nullptr, workspace, wct_bytes,
-                       nullptr, WCT_STAGE_COV | WCT_STAGE_EIG | WCT_STAGE_EIG_FP32UPDATE, s, nullptr, 0, nullptr, nullptr, 0, eig_fail))) return rc;
+                       nullptr, WCT_STAGE_COV | WCT_STAGE_EIG | WCT_STAGE_EIG_FP32UPDATE, s, 0, eig_fail))) return rc;
   const size_t cc = (size_t)C * C;
   // content whitening, style whitening, style colouring: S^-1/2 | S^1/2 over the kept singular values, no eps in the
   // gains (ops.py:187-189,197-198,208-209), with the first-order completion on the solver's residual
