@@ -98,6 +98,20 @@ int wct_transform(wct_ctx* ctx, const float* content, int Nc, const float* style
 /* adain (ops.py:282-294), epsilon as in the reference signature */
 int wct_adain(wct_ctx* ctx, const float* content, int Nc, const float* style, int Ns,
               int C, float alpha, float epsilon, float* out);
+/* Style mixes -- interpolation between styles (Li et al. 2017, sec. 4.2 "controlling the style"; the reference's README
+ * TODO "Interpolation between styles", the original Torch WCT's -style a,b -styleInterpWeights w1,w2):
+ *   lambda_k = weights[k] / sum(weights),   mix(fc) = sum_k lambda_k T(fc, fs_k, alpha)
+ * with T the single-style transform of the call below it.  K = 1 .. 8 styles of any pixel counts Ns[k]; weights finite,
+ * >= 0, summing to > 0 -- else WCT_STATUS_ARG.  T is affine in the colouring side, so the mix is ONE transform: the content
+ * is whitened once, the K colouring matrices and style means are mixed (fp32, k in order, from 0), then one blend and one
+ * apply.  K = 1, and one-hot weights, give the single-style call's output bit for bit.
+ * wct_transform_mix: wct_np / wct_tf (ops.py:24-140) as wct_transform; NOCONV under wct_transform's rules.
+ *   sweeps_out [1 + K] or NULL: the content's sweeps, then style k's (wct_transform's contract). */
+int wct_transform_mix(wct_ctx* ctx, const float* content, int Nc, const float* const* styles, const int* Ns, int K,
+                      const float* weights, int C, float alpha, int mode, float eps, float* out, int* sweeps_out);
+/* adain (ops.py:282-294) with sqrt(var_s) -> sum_k lambda_k sqrt(var_k) and mean_s -> sum_k lambda_k mean_k */
+int wct_adain_mix(wct_ctx* ctx, const float* content, int Nc, const float* const* styles, const int* Ns, int K,
+                  const float* weights, int C, float alpha, float epsilon, float* out);
 /* wct_style_swap (ops.py:145-278): content [hc*wc][C], style [hs*ws][C], out [hc*wc][C]; `alpha` is the
  * reference's ss_alpha; eps < 0 = its default 1e-8.  (hc, wc) must survive the patch/stride round trip
  * (utils.swap_filter_fit, wct.py:84-90) -- always true for stride 1. */
@@ -154,6 +168,13 @@ int wct_stylize(wct_ctx* ctx, const uint8_t* content, int Hc, int Wc,
                 const uint8_t* style, int Hs, int Ws,
                 const int* levels, int n_levels, float alpha, unsigned flags,
                 uint8_t* out);
+/* WCT.predict with a style mix at every level (see wct_transform_mix): styles[k] is an Hs[k] x Ws[k] image (sizes may differ),
+ * lambda_k = weights[k] / sum(weights).  Every level applies the mix; each level encodes the clipped decode of the level before.
+ * Honours WCT_FLAG_MODE_NP, WCT_FLAG_ADAIN, WCT_FLAG_IMAGES_F32 (all K images), and WCT_FLAG_SWAP5 only at K = 1 (style-swap is
+ * not linear: K > 1 is WCT_STATUS_ARG); K = 1, and one-hot weights, give wct_stylize's frame bit for bit. */
+int wct_stylize_mix(wct_ctx* ctx, const uint8_t* content, int Hc, int Wc, const uint8_t* const* styles, const int* Hs,
+                    const int* Ws, int K, const float* weights, const int* levels, int n_levels, float alpha, unsigned flags,
+                    uint8_t* out);
 /* batched, device-resident variant: B independent pairs (same sizes), content [B][Hc][Wc][3],
  * style [B][Hs][Ws][3], out [B][Ho][Wo][3], all device pointers; asynchronous on the ctx
  * stream (call wct_sync).  This is what bench.py times. */

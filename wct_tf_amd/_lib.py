@@ -30,6 +30,9 @@ SIGNATURES = [
     ('wct_set_decoder', C.c_int, [_P, C.c_int, C.POINTER(_F), C.POINTER(_F), C.c_int]),
     ('wct_transform', C.c_int, [_P, _F, C.c_int, _F, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float, _F, _I]),
     ('wct_adain', C.c_int, [_P, _F, C.c_int, _F, C.c_int, C.c_int, C.c_float, C.c_float, _F]),
+    ('wct_transform_mix', C.c_int, [_P, _F, C.c_int, C.POINTER(_F), _I, C.c_int, _F, C.c_int, C.c_float, C.c_int, C.c_float,
+                                    _F, _I]),
+    ('wct_adain_mix', C.c_int, [_P, _F, C.c_int, C.POINTER(_F), _I, C.c_int, _F, C.c_int, C.c_float, C.c_float, _F]),
     ('wct_style_swap', C.c_int, [_P, _F, C.c_int, C.c_int, _F, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_float, _F]),
     ('wct_set_style_swap', C.c_int, [_P, C.c_float, C.c_int, C.c_int]),
     ('wct_eigh', C.c_int, [_P, _F, C.c_int, C.c_int, _F, _F, _I]),
@@ -43,6 +46,8 @@ SIGNATURES = [
     ('wct_output_size', C.c_int, [C.c_int, C.c_int, _I, C.c_int, _I, _I]),
     ('wct_stylize', C.c_int, [_P, _U8, C.c_int, C.c_int, _U8, C.c_int, C.c_int, _I, C.c_int,
                               C.c_float, C.c_uint, _U8]),
+    ('wct_stylize_mix', C.c_int, [_P, _U8, C.c_int, C.c_int, C.POINTER(_U8), _I, _I, C.c_int, _F, _I, C.c_int,
+                                  C.c_float, C.c_uint, _U8]),
     ('wct_stylize_batch_dev', C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, _I,
                                         C.c_int, C.c_float, C.c_uint, _P]),
     ('wct_train_step', C.c_int, [_P, C.c_int, _F, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float,
@@ -77,6 +82,7 @@ class WCTNotConverged(WCTHipError):
 
 
 STATUS_NOCONV = -5
+MIX_MAX = 8                  # styles per mix (WCT_MIX_MAX)
 
 
 def load():
@@ -117,3 +123,20 @@ def ptr_array(arrays):
     """float** from a list of contiguous float32 arrays (keeps them alive via the return)."""
     arr = (_F * len(arrays))(*[fptr(a) for a in arrays])
     return arr
+
+
+def mix_weights(weights, k):
+    """Validated style-mix weights as float32 [k] (None: equal weights).  They must be finite, >= 0 and sum to > 0 --
+    the rule the library applies (lambda_k = w_k / sum(w), include/wct_hip.h), checked here before any GPU call."""
+    if not 1 <= k <= MIX_MAX:
+        raise ValueError('a style mix takes 1 .. %d styles, got %d' % (MIX_MAX, k))
+    if weights is None:
+        return np.ones(k, np.float32)
+    w = np.asarray(weights, np.float64).reshape(-1)
+    if w.size != k:
+        raise ValueError('%d weights for %d styles' % (w.size, k))
+    if not np.all(np.isfinite(w)) or np.any(w < 0):
+        raise ValueError('style weights must be finite and >= 0, got %s' % (list(w),))
+    if not w.sum() > 0:
+        raise ValueError('style weights sum to 0')
+    return np.ascontiguousarray(w, np.float32)

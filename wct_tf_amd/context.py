@@ -108,6 +108,35 @@ class Context(object):
                                  float(alpha), float(epsilon), fptr(out)))
         return out
 
+    def transform_mix(self, content, styles, weights, alpha, mode, eps=-1.0, return_sweeps=False):
+        """Style mix (wct_transform_mix): content [Nc][C], styles K x [Ns_k][C] float32, weights [K] (None: equal) ->
+        sum_k lambda_k transform(content, styles[k]) [Nc][C], lambda = weights / sum(weights).  Sweeps: content, then style k."""
+        c = f32(content)
+        ss = [f32(s) for s in styles]
+        w = _lib.mix_weights(weights, len(ss))
+        if c.ndim != 2 or any(s.ndim != 2 or s.shape[1] != c.shape[1] for s in ss):
+            raise ValueError('expected [N][C] feature matrices with equal C')
+        out = np.empty_like(c)
+        ns = (C.c_int * len(ss))(*[s.shape[0] for s in ss])
+        sweeps = (C.c_int * (1 + len(ss)))()
+        self.last_sweeps = sweeps
+        check(self.lib.wct_transform_mix(self.h, fptr(c), c.shape[0], _lib.ptr_array(ss), ns, len(ss), fptr(w), c.shape[1],
+                                         float(alpha), int(mode), float(eps), fptr(out), sweeps))
+        return (out, list(sweeps)) if return_sweeps else out
+
+    def adain_mix(self, content, styles, weights, alpha, epsilon=1e-5):
+        """AdaIN with a style mix (wct_adain_mix): the style's deviation and mean are the lambda-weighted ones."""
+        c = f32(content)
+        ss = [f32(s) for s in styles]
+        w = _lib.mix_weights(weights, len(ss))
+        if c.ndim != 2 or any(s.ndim != 2 or s.shape[1] != c.shape[1] for s in ss):
+            raise ValueError('expected [N][C] feature matrices with equal C')
+        out = np.empty_like(c)
+        ns = (C.c_int * len(ss))(*[s.shape[0] for s in ss])
+        check(self.lib.wct_adain_mix(self.h, fptr(c), c.shape[0], _lib.ptr_array(ss), ns, len(ss), fptr(w), c.shape[1],
+                                     float(alpha), float(epsilon), fptr(out)))
+        return out
+
     def style_swap(self, content, style, alpha, patch_size=3, stride=1, eps=-1.0):
         """content [hc][wc][C], style [hs][ws][C] float32 -> [hc][wc][C] (ops.py:145-278)"""
         c = f32(content)
@@ -241,6 +270,33 @@ class Context(object):
         check(self.lib.wct_stylize(self.h, c.ctypes.data_as(_lib._U8), c.shape[0], c.shape[1],
                                    s.ctypes.data_as(_lib._U8), s.shape[0], s.shape[1], arr, len(lv),
                                    float(alpha), flags, out.ctypes.data_as(_lib._U8)))
+        return out
+
+    def stylize_mix(self, content, styles, weights, relu_targets, alpha=1.0, adain=False, wct_mode='tf', swap5=False):
+        """One predict() with a style mix at every level (wct_stylize_mix): `styles` is a list of K HxWx3 images (sizes may
+        differ), `weights` [K] (None: equal).  Inputs as in stylize: all uint8 go as they are, otherwise every image is
+        `/ 255.` in float64 and handed over as float32 in [0,1]."""
+        content = np.asarray(content)
+        styles = [np.asarray(s) for s in styles]
+        w = _lib.mix_weights(weights, len(styles))
+        as_f32 = content.dtype != np.uint8 or any(s.dtype != np.uint8 for s in styles)
+        if as_f32:
+            c = np.ascontiguousarray(np.asarray(content / 255.), np.float32)
+            ss = [np.ascontiguousarray(np.asarray(s / 255.), np.float32) for s in styles]
+        else:
+            c, ss = u8(content), [u8(s) for s in styles]
+        lv = _levels(relu_targets)
+        arr = (C.c_int * len(lv))(*lv)
+        ho, wo = self.output_size(c.shape[0], c.shape[1], lv)
+        out = np.empty((ho, wo, 3), np.uint8)
+        flags = (_lib.FLAG_ADAIN if adain else 0) | (_lib.FLAG_MODE_NP if wct_mode == 'np' else 0) | \
+            (_lib.FLAG_SWAP5 if swap5 else 0) | (_lib.FLAG_IMAGES_F32 if as_f32 else 0)
+        k = len(ss)
+        ptrs = (_lib._U8 * k)(*[s.ctypes.data_as(_lib._U8) for s in ss])
+        hs = (C.c_int * k)(*[s.shape[0] for s in ss])
+        ws = (C.c_int * k)(*[s.shape[1] for s in ss])
+        check(self.lib.wct_stylize_mix(self.h, c.ctypes.data_as(_lib._U8), c.shape[0], c.shape[1], ptrs, hs, ws, k, fptr(w),
+                                       arr, len(lv), float(alpha), flags, out.ctypes.data_as(_lib._U8)))
         return out
 
     # device-resident batch (what bench.py times)

@@ -9,6 +9,7 @@
 #include <string.h>
 #include <stdlib.h>
 #include <vector>
+#include <cmath>
 
 // ---------------------------------------------------------------------------
 // errors
@@ -69,6 +70,7 @@ struct wct_ctx {
   Decoder dec[6];
   DevBuf act[2], feat_c, feat_s[6], img_c, img_s, img_t[2], wct_out, wct_ws, stage[4];
   DevBuf usum_c, usum_s[6], umax;     // feature statistics from the tap epilogues (ConvArgs::usum / umax); umax: [7][32][UMAX_SLOTS] words
+  DevBuf mix_in, feat_mix[6];      // a style mix: the K style inputs, and their features per level (K maps back to back)
 
   int* eig_fail = nullptr;         // pinned host memory mapped into the device: [2] eigenproblems that did not converge / had
                                    // non-finite input -- bumped by jacobi_finalize_kernel (then [6 size classes][3] solver
@@ -189,6 +191,8 @@ extern "C" void wct_destroy(wct_ctx* c) {
   for (DevBuf* b : bufs) if (b->p) hipFree(b->p);
   for (auto& b : c->feat_s) if (b.p) hipFree(b.p);
   for (auto& b : c->usum_s) if (b.p) hipFree(b.p);
+  for (auto& b : c->feat_mix) if (b.p) hipFree(b.p);
+  if (c->mix_in.p) hipFree(c->mix_in.p);
   if (c->usum_c.p) hipFree(c->usum_c.p);
   if (c->umax.p) hipFree(c->umax.p);
   for (auto& r : c->recs) { hipEventDestroy(r.a); hipEventDestroy(r.b); }
@@ -637,6 +641,53 @@ static int run_transform(wct_ctx* c, const float* fc, int Nc, const float* fs, i
   return launch_wct(fc, Nc, fs, Ns, C, P, alpha, mode, eps, out16, out32, c->wct_ws.p, c->wct_ws.cap, sweeps_dev, WCT_STAGE_APPLY, c->stream, shared, c->eig_fail_dev);
 }
 
+// lambda[k] = weights[k] / sum(weights) (Li et al. 2017, sec. 4.2); refuses K outside 1 .. WCT_MIX_MAX and weights that are
+// negative, not finite or sum to zero
+static int mix_weights(const float* weights, int K, float* lambda) {
+  if (K < 1 || K > WCT_MIX_MAX) { wct_set_error("style mix: K = %d styles, must be 1 .. %d", K, (int)WCT_MIX_MAX); return WCT_ERR_ARG; }
+  if (!weights) { wct_set_error("style mix: no weights"); return WCT_ERR_ARG; }
+  double sum = 0.0;
+  for (int k = 0; k < K; ++k) {
+    if (!(weights[k] >= 0.f) || !std::isfinite(weights[k])) {
+      wct_set_error("style mix: weight %d is %g; weights must be finite and >= 0", k, (double)weights[k]);
+      return WCT_ERR_ARG;
+    }
+    sum += weights[k];
+  }
+  if (!(sum > 0.0) || !std::isfinite(sum)) { wct_set_error("style mix: the weights sum to %g, must be > 0", sum); return WCT_ERR_ARG; }
+  for (int k = 0; k < K; ++k) lambda[k] = (float)(weights[k] / sum);
+  return WCT_OK;
+}
+
+// the style-mix counterpart of run_transform (device pointers; one content, K styles); sweeps_dev [2K] or null
+static int run_transform_mix(wct_ctx* c, const float* fc, int Nc, const float* const* fs, const int* Ns, int K, const float* lambda,
+                             int C, float alpha, unsigned flags, float eps, half_t* out16, float* out32, int* sweeps_dev,
+                             const WctFeatStats* st = nullptr) {
+  TRY(ensure(c, c->wct_ws, wct_mix_workspace_bytes(C, Nc, Ns, K, lambda)));
+  double ns = 0;
+  for (int k = 0; k < K; ++k) ns += Ns[k];
+  if (flags & WCT_FLAG_ADAIN) {
+    ProfScope ps(c, 7, 0, (2.0 * Nc + 2.0 * ns) * C * 4 + (double)Nc * C * 6);
+    return launch_adain_mix(fc, Nc, fs, Ns, K, lambda, C, alpha, 1e-5f, out16, out32, c->wct_ws.p, c->wct_ws.cap, c->stream, st);
+  }
+  const int mode = (flags & WCT_FLAG_MODE_NP) ? WCT_MODE_NP : WCT_MODE_TF;
+  {
+    ProfScope ps(c, 4, 2.0 * C * C * (Nc + ns), 2.0 * (Nc + ns) * C * 4);
+    TRY(launch_wct_mix(fc, Nc, fs, Ns, K, lambda, C, alpha, mode, eps, out16, out32, c->wct_ws.p, c->wct_ws.cap, sweeps_dev,
+                       WCT_STAGE_COV, c->stream, c->eig_fail_dev, st));
+  }
+  {
+    ProfScope ps(c, 5, 0, 0);
+    TRY(launch_wct_mix(fc, Nc, fs, Ns, K, lambda, C, alpha, mode, eps, out16, out32, c->wct_ws.p, c->wct_ws.cap, sweeps_dev,
+                       WCT_STAGE_EIG, c->stream, c->eig_fail_dev));
+  }
+  // (the mix of the K colouring matrices is timed with the tail it belongs to)
+  ProfScope ps(c, 6, 2.0 * C * C * Nc + 6.0 * C * C * C * (K + 1) + 2.0 * C * C * K,
+               (double)Nc * C * (4 + (out16 ? 2 : 0) + (out32 ? 4 : 0)));
+  return launch_wct_mix(fc, Nc, fs, Ns, K, lambda, C, alpha, mode, eps, out16, out32, c->wct_ws.p, c->wct_ws.cap, sweeps_dev,
+                        WCT_STAGE_APPLY, c->stream, c->eig_fail_dev);
+}
+
 // ---------------------------------------------------------------------------
 // op-level host entry points
 // ---------------------------------------------------------------------------
@@ -680,6 +731,63 @@ extern "C" int wct_adain(wct_ctx* c, const float* content, int Nc, const float* 
   TRY(ensure(c, c->wct_ws, wct_workspace_bytes(C, Nc, Ns, 1)));
   TRY(launch_adain((float*)dc, Nc, (float*)ds, Ns, C, 1, alpha, epsilon, nullptr, (float*)c->stage[2].p,
                    c->wct_ws.p, c->wct_ws.cap, c->stream, 0));
+  return fetch(c, out, c->stage[2].p, (size_t)Nc * C * 4);
+}
+
+// the K host feature maps [Ns[k]][C] back to back in c->mix_in; dev[k] points at map k
+static int stage_in_mix(wct_ctx* c, const float* const* styles, const int* Ns, int K, int C, const float* dev[]) {
+  size_t total = 0;
+  for (int k = 0; k < K; ++k) { ARG_CHECK(styles[k] && Ns[k] >= 1); total += (size_t)Ns[k] * C * 4; }
+  TRY(ensure(c, c->mix_in, total));
+  size_t off = 0;
+  for (int k = 0; k < K; ++k) {
+    char* d = (char*)c->mix_in.p + off;
+    HIP_TRY(hipMemcpyAsync(d, styles[k], (size_t)Ns[k] * C * 4, hipMemcpyHostToDevice, c->stream));
+    dev[k] = (const float*)d;
+    off += (size_t)Ns[k] * C * 4;
+  }
+  return WCT_OK;
+}
+
+extern "C" int wct_transform_mix(wct_ctx* c, const float* content, int Nc, const float* const* styles, const int* Ns, int K,
+                                 const float* weights, int C, float alpha, int mode, float eps, float* out, int* sweeps_out) {
+  ARG_CHECK(c && content && styles && Ns && out && (mode == WCT_NP || mode == WCT_TF));
+  float lambda[WCT_MIX_MAX];
+  TRY(mix_weights(weights, K, lambda));
+  HIP_TRY(hipSetDevice(c->device));
+  TRY(eig_stale(c));
+  void* dc;
+  const float* ds[WCT_MIX_MAX];
+  TRY(stage_in(c, 0, content, (size_t)Nc * C * 4, &dc));
+  TRY(stage_in_mix(c, styles, Ns, K, C, ds));
+  TRY(ensure(c, c->stage[2], (size_t)Nc * C * 4));
+  TRY(ensure(c, c->stage[3], 2 * WCT_MIX_MAX * sizeof(int)));
+  TRY(run_transform_mix(c, (float*)dc, Nc, ds, Ns, K, lambda, C, alpha, mode == WCT_NP ? WCT_FLAG_MODE_NP : 0, eps,
+                        nullptr, (float*)c->stage[2].p, (int*)c->stage[3].p));
+  TRY(fetch(c, out, c->stage[2].p, (size_t)Nc * C * 4));
+  if (sweeps_out) {
+    int sw[2 * WCT_MIX_MAX];
+    TRY(fetch(c, sw, c->stage[3].p, 2 * K * sizeof(int)));
+    sweeps_out[0] = sw[0];                                     // the content, then style k at slot 2k + 1
+    for (int k = 0; k < K; ++k) sweeps_out[1 + k] = sw[2 * k + 1];
+  }
+  return eig_status(c);
+}
+
+extern "C" int wct_adain_mix(wct_ctx* c, const float* content, int Nc, const float* const* styles, const int* Ns, int K,
+                             const float* weights, int C, float alpha, float epsilon, float* out) {
+  ARG_CHECK(c && content && styles && Ns && out);
+  float lambda[WCT_MIX_MAX];
+  TRY(mix_weights(weights, K, lambda));
+  HIP_TRY(hipSetDevice(c->device));
+  void* dc;
+  const float* ds[WCT_MIX_MAX];
+  TRY(stage_in(c, 0, content, (size_t)Nc * C * 4, &dc));
+  TRY(stage_in_mix(c, styles, Ns, K, C, ds));
+  TRY(ensure(c, c->stage[2], (size_t)Nc * C * 4));
+  TRY(ensure(c, c->wct_ws, wct_mix_workspace_bytes(C, Nc, Ns, K, lambda)));
+  TRY(launch_adain_mix((float*)dc, Nc, ds, Ns, K, lambda, C, alpha, epsilon, nullptr, (float*)c->stage[2].p,
+                       c->wct_ws.p, c->wct_ws.cap, c->stream));
   return fetch(c, out, c->stage[2].p, (size_t)Nc * C * 4);
 }
 
@@ -1043,6 +1151,129 @@ extern "C" int wct_stylize(wct_ctx* c, const uint8_t* content, int Hc, int Wc, c
   TRY(ensure(c, c->stage[2], (size_t)Ho * Wo * 3));
   TRY(wct_stylize_batch_dev(c, (uint8_t*)dc, Hc, Wc, (uint8_t*)ds, Hs, Ws, 1, levels, n_levels, alpha, flags,
                             (uint8_t*)c->stage[2].p));
+  TRY(fetch(c, out, c->stage[2].p, (size_t)Ho * Wo * 3));
+  return eig_status(c);
+}
+
+// One predict() with a style mix at every level (Li et al. 2017, sec. 4.2): the style encoder runs once per style (sizes may
+// differ), then the content chain of wct_stylize_batch_dev with B = 1 and the mix in the place of the single-style transform.
+extern "C" int wct_stylize_mix(wct_ctx* c, const uint8_t* content, int Hc, int Wc, const uint8_t* const* styles, const int* Hs,
+                               const int* Ws, int K, const float* weights, const int* levels, int n_levels, float alpha,
+                               unsigned flags, uint8_t* out) {
+  ARG_CHECK(c && content && styles && Hs && Ws && out && levels && n_levels >= 1 && n_levels <= 16);
+  float lambda[WCT_MIX_MAX];
+  TRY(mix_weights(weights, K, lambda));
+  if ((flags & WCT_FLAG_SWAP5) && K > 1) {
+    wct_set_error("style mix: WCT_FLAG_SWAP5 needs K = 1 (style-swap is not linear in the style; got K = %d)", K);
+    return WCT_ERR_ARG;
+  }
+  if (flags & WCT_FLAG_STYLE_SHARED) { wct_set_error("style mix: WCT_FLAG_STYLE_SHARED is for wct_stylize_batch_dev"); return WCT_ERR_ARG; }
+  HIP_TRY(hipSetDevice(c->device));
+  int deepest = 0;
+  for (int i = 0; i < n_levels; ++i) {
+    ARG_CHECK(levels[i] >= 1 && levels[i] <= 5);
+    if (levels[i] > deepest) deepest = levels[i];
+    if (!c->dec[levels[i]].loaded) { wct_set_error("decoder weights for relu%d_1 not set", levels[i]); return WCT_ERR_STATE; }
+  }
+  int Ho, Wo;
+  TRY(wct_output_size(Hc, Wc, levels, n_levels, &Ho, &Wo));
+  for (int k = 0; k < K; ++k) { ARG_CHECK(styles[k]); TRY(check_min_size("style", Hs[k], Ws[k], deepest)); }
+  TRY(eig_stale(c));
+
+  // inputs: the content in stage 0, the K styles back to back in mix_in; to fp32 in [0,1] (wct.py:60-64)
+  const bool f32in = (flags & WCT_FLAG_IMAGES_F32) != 0;
+  const size_t px = f32in ? sizeof(float) : 1;
+  size_t ns_tot = 0, soff[WCT_MIX_MAX];
+  for (int k = 0; k < K; ++k) { soff[k] = ns_tot; ns_tot += (size_t)Hs[k] * Ws[k] * 3; }
+  const size_t nc = (size_t)Hc * Wc * 3;
+  void* dc;
+  TRY(stage_in(c, 0, content, nc * px, &dc));
+  TRY(ensure(c, c->mix_in, ns_tot * px));
+  for (int k = 0; k < K; ++k)
+    HIP_TRY(hipMemcpyAsync((char*)c->mix_in.p + soff[k] * px, styles[k], (size_t)Hs[k] * Ws[k] * 3 * px, hipMemcpyHostToDevice, c->stream));
+  const float* img_c = (const float*)dc;
+  const float* img_s = (const float*)c->mix_in.p;
+  if (!f32in) {
+    TRY(ensure(c, c->img_c, nc * 4));
+    TRY(ensure(c, c->img_s, ns_tot * 4));
+    ProfScope ps(c, 7, 0, (double)(nc + ns_tot) * 5);
+    TRY(launch_u8_to_f32((const uint8_t*)dc, (float*)c->img_c.p, nc, c->stream));
+    TRY(launch_u8_to_f32((const uint8_t*)c->mix_in.p, (float*)c->img_s.p, ns_tot, c->stream));
+    img_c = (const float*)c->img_c.p; img_s = (const float*)c->img_s.p;
+  }
+
+  // one style pass per style, a tap per requested level (model.py:69-75); style k's map of level l at feat_mix[l] + foff[l][k]
+  // (statistics from the stored features: the same bits as the epilogue's unit sums, colsum_kernel)
+  size_t foff[6][WCT_MIX_MAX];
+  for (int i = 0; i < n_levels; ++i) {
+    const int l = levels[i];
+    size_t tot = 0;
+    for (int k = 0; k < K; ++k) {
+      int h, w;
+      level_dims(Hs[k], Ws[k], l, &h, &w);
+      foff[l][k] = tot;
+      tot += (size_t)h * w * LEVEL_C[l];
+    }
+    TRY(ensure(c, c->feat_mix[l], tot * 4));
+  }
+  for (int k = 0; k < K; ++k) {
+    float* taps[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    for (int i = 0; i < n_levels; ++i) taps[levels[i]] = (float*)c->feat_mix[levels[i]].p + foff[levels[i]][k];
+    TRY(run_encoder(c, img_s + soff[k], 1, Hs[k], Ws[k], 0, deepest, taps));
+  }
+
+  // the content chain (wct_stylize_batch_dev, B = 1)
+  static const int fuse_stats = getenv("WCT_FUSE_STATS") ? atoi(getenv("WCT_FUSE_STATS")) : 1;
+  TRY(ensure(c, c->umax, 32 * UMAX_SLOTS * sizeof(unsigned)));
+  unsigned* const umax_c = (unsigned*)c->umax.p;
+  const float* cur = img_c;
+  int H = Hc, W = Wc;
+  for (int i = 0; i < n_levels; ++i) {
+    const int l = levels[i], C = LEVEL_C[l];
+    int h, w;
+    level_dims(H, W, l, &h, &w);
+    TRY(ensure(c, c->feat_c, (size_t)h * w * C * 4));
+    float* ctaps[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    ctaps[l] = (float*)c->feat_c.p;
+    float* us_c[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    unsigned* um_c[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    if (fuse_stats && w % 16 == 0) {
+      TRY(ensure(c, c->usum_c, (size_t)h * (w / 16) * C * 4));
+      us_c[l] = (float*)c->usum_c.p; um_c[l] = umax_c;
+      HIP_TRY(hipMemsetAsync(umax_c, 0, UMAX_SLOTS * sizeof(unsigned), c->stream));
+    }
+    WctFeatStats st = {};
+    st.u[0] = us_c[l]; st.umax[0] = um_c[l];
+    TRY(run_encoder(c, cur, 1, H, W, i > 0, l, ctaps, us_c, um_c));     // level i > 0 encodes clip(previous decoded) (model.py:86)
+    TRY(ensure(c, c->wct_out, (size_t)h * w * C * 2));
+    const float* fs[WCT_MIX_MAX];
+    int Ns[WCT_MIX_MAX], hs[WCT_MIX_MAX], ws[WCT_MIX_MAX];
+    for (int k = 0; k < K; ++k) {
+      level_dims(Hs[k], Ws[k], l, &hs[k], &ws[k]);
+      fs[k] = (const float*)c->feat_mix[l].p + foff[l][k];
+      Ns[k] = hs[k] * ws[k];
+    }
+    if (l == 5 && (flags & WCT_FLAG_SWAP5)) {            // K = 1 (checked above): wct_stylize's style-swap at relu5_1
+      ARG_CHECK(h >= c->ss_patch && w >= c->ss_patch && hs[0] >= c->ss_patch && ws[0] >= c->ss_patch);
+      TRY(ensure(c, c->wct_ws, style_swap_workspace_bytes(C, h, w, hs[0], ws[0], c->ss_patch, c->ss_stride)));
+      ProfScope ps(c, 7, 0, 0);
+      TRY(launch_style_swap((float*)c->feat_c.p, h, w, fs[0], hs[0], ws[0], C, c->ss_alpha, c->ss_patch, c->ss_stride, -1.f,
+                            (half_t*)c->wct_out.p, nullptr, c->wct_ws.p, c->wct_ws.cap, c->stream, c->eig_fail_dev));
+    } else
+      TRY(run_transform_mix(c, (float*)c->feat_c.p, h * w, fs, Ns, K, lambda, C, alpha, flags, -1.f, (half_t*)c->wct_out.p, nullptr,
+                            nullptr, &st));
+    const int scale = 1 << (l - 1);
+    const int H2 = h * scale, W2 = w * scale;
+    DevBuf& dst = c->img_t[i & 1];
+    TRY(ensure(c, dst, (size_t)H2 * W2 * 3 * 4));
+    TRY(run_decoder(c, l, (half_t*)c->wct_out.p, 1, h, w, (float*)dst.p));
+    cur = (float*)dst.p; H = H2; W = W2;
+  }
+  TRY(ensure(c, c->stage[2], (size_t)Ho * Wo * 3));
+  {
+    ProfScope ps(c, 7, 0, (double)H * W * 3 * 5);
+    TRY(launch_f32_to_u8(cur, (uint8_t*)c->stage[2].p, (size_t)H * W * 3, c->stream));     // wct.py:66-68
+  }
   TRY(fetch(c, out, c->stage[2].p, (size_t)Ho * Wo * 3));
   return eig_status(c);
 }

@@ -165,7 +165,8 @@ struct GemmArgs {
   // round 5 (the transform tail in merged launches over the 2P matrices of a level, batch b = matrix 2 * pair + side):
   const float* A_odd;     // if set: A of an odd batch b is A_odd + (b >> 1) * sA_odd, that of an even one A + (b >> 1) * sA
   size_t sA_odd;
-  int skip_shared;        // batches b with skip_style_mat(b, 1) have nothing to do (one style for all pairs: WCT_FLAG_STYLE_SHARED)
+  int skip_shared;        // batches b with skip_style_mat(b, skip_shared) have nothing to do (1: one style for all pairs,
+                          // WCT_FLAG_STYLE_SHARED; 2: one content for a style mix, launch_wct_mix)
   // blend epilogue (T = Tcs Tw -> M = alpha T + (1 - alpha) I, ops.py:83 folded into the apply matrix): the store carries the
   // blend and the block merges max |M| into mabs[batch] (bit patterns of non-negative floats; zeroed by an earlier kernel)
   int blend; float alpha; unsigned* mabs;
@@ -202,6 +203,18 @@ int launch_adain(const float* content, int Nc, const float* style, int Ns, int C
                  float alpha, float eps, half_t* out16, float* out32,
                  void* workspace, size_t workspace_bytes, hipStream_t s, int shared_style,
                  const struct WctFeatStats* stats = nullptr);
+// Style mix (Li et al. 2017, sec. 4.2): out = sum_k lambda[k] T(content, styles[k]) for K <= WCT_MIX_MAX styles of any sizes
+// Ns[k]; lambda[k] in [0, 1] summing to 1 (normalised by the caller).  One content whitening, K colourings mixed before ONE
+// blend product and apply.  sweeps_dev [2K]: slot 2k + 1 style k, slot 0 the content (the even slots k >= 1 read 0).  stats:
+// the content side only (u[0] / umax[0]).
+enum { WCT_MIX_MAX = 8 };
+size_t wct_mix_workspace_bytes(int C, int Nc, const int* Ns, int K, const float* lambda);
+int launch_wct_mix(const float* content, int Nc, const float* const* styles, const int* Ns, int K, const float* lambda, int C,
+                   float alpha, int mode, float eps, half_t* out16, float* out32, void* workspace, size_t workspace_bytes,
+                   int* sweeps_dev, int stages, hipStream_t s, int* eig_fail, const struct WctFeatStats* stats = nullptr);
+int launch_adain_mix(const float* content, int Nc, const float* const* styles, const int* Ns, int K, const float* lambda, int C,
+                     float alpha, float eps, half_t* out16, float* out32, void* workspace, size_t workspace_bytes, hipStream_t s,
+                     const struct WctFeatStats* stats = nullptr);
 // Symmetric eigensolver (batched): A [nmat][C][C] is overwritten (diag -> eigenvalues),
 // V [nmat][C][C] gets eigenvectors in columns.  C multiple of 32, 32 <= C <= 1024.
 // sweeps_done_dev[m]: sweeps used (> 0) if matrix m converged, -sweeps if it was still rotating when the sweep

@@ -27,10 +27,13 @@ static inline int launch_rc_take() { const int r = launch_rc_sticky; launch_rc_s
 // ---------------------------------------------------------------------------
 // grid (nslab, 2P): matrix m = 2*pair + side (0 content, 1 style); slab s reduces rows
 // [s*rows_per_slab, ...) of X_m[N_side][C]
-// With a shared style (one style image for every pair of the batch: video) only pair 0's style matrix
+// With a shared style (one style image for every pair of the batch: video; shared_style == 1) only pair 0's style matrix
 // (matrix 1) is computed; the style matrices of the other pairs are skipped and their consumers read pair 0's.
+// A style mix (launch_wct_mix; shared_style == WCT_SKIP_MIX) is the mirror image: K styles share ONE content, matrix 0;
+// the content slots 2k of the pairs k >= 1 are skipped.
+constexpr int WCT_SKIP_MIX = 2;
 __device__ __host__ __forceinline__ bool skip_style_mat(int mat, int shared_style) {
-  return shared_style && (mat & 1) && mat > 1;
+  return shared_style == WCT_SKIP_MIX ? ((mat & 1) == 0 && mat > 0) : (shared_style && (mat & 1) && mat > 1);
 }
 
 struct StatArgs {
@@ -255,7 +258,7 @@ __global__ __launch_bounds__(256, 4) void gemm_f32_kernel(GemmArgs p) {
   const int wm = wave >> 1, wn = wave & 1;
   const int m0 = blockIdx.y * BM, n0 = blockIdx.x * BN;
   const int batch = blockIdx.z / p.nsplit, split = blockIdx.z % p.nsplit;
-  if (p.skip_shared && skip_style_mat(batch, 1)) return;
+  if (p.skip_shared && skip_style_mat(batch, p.skip_shared)) return;
   if (p.mask_in && !p.mask_in[batch]) return;
   if (p.mask_diag) {                             // (uniform per block)
     const bool need = refresh_needed(p.mask_diag + batch * p.s_mask, p.M, tid);
@@ -2003,8 +2006,8 @@ __global__ __launch_bounds__(256) void spectral_open_all_kernel(SpecAllArgs a) {
   if (kind == 0 && blockIdx.x == 0 && blockIdx.y == 0) {
     // what blend_matrix_kernel did besides the blend: bias = alpha ms (+ (1 - alpha) mc in tf mode); and mabs starts at 0
     if (tid == 0) a.mabs[pair] = 0u;
-    const float* mp = a.mean + (size_t)pair * 2 * C;
-    const float* ms = a.mean + (size_t)(a.shared_style ? 0 : pair) * 2 * C + C;
+    const float* mp = a.mean + (size_t)(a.shared_style == WCT_SKIP_MIX ? 0 : pair) * 2 * C;     // (a mix: the one content)
+    const float* ms = a.mean + (size_t)(a.shared_style == 1 ? 0 : pair) * 2 * C + C;
     for (int i = tid; i < C; i += 256) {
       float b = a.alpha * ms[i];
       if (a.mode == WCT_MODE_TF) b += (1.f - a.alpha) * mp[i];
@@ -2338,7 +2341,7 @@ __global__ __launch_bounds__(256, 2) void apply_f16x2_kernel(ApplyArgs p) {
 static inline size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
 
 struct WctCarve {
-  float *mean, *var, *stat_partial, *absmax, *scale, *cov_partial, *A, *A0, *V, *d, *G, *X, *S2, *Tw, *Tcs, *T, *M, *bias;
+  float *mean, *var, *stat_partial, *absmax, *scale, *cov_partial, *A, *A0, *V, *d, *G, *X, *S2, *Tw, *Tcs, *T, *M, *bias, *mix;
   unsigned* mabs; int* refresh;
   void* jacobi_ws; size_t jacobi_bytes;
   int nslab, nsplit, ksplit;
@@ -2360,11 +2363,15 @@ static void cov_split(int C, int Nmax, int P, int* nsplit, int* ksplit) {
   *nsplit = cdiv(Nmax, ks);
 }
 
-static WctCarve carve(void* base, int C, int Nc, int Ns, int P) {
+// nslab_max / nsplit_max > 0: size the per-matrix partial buffers for that many slabs / K-slices (a style mix, whose matrices
+// each keep the layout of their own (content, style) pair -- launch_wct_mix)
+static WctCarve carve(void* base, int C, int Nc, int Ns, int P, int nslab_max = 0, int nsplit_max = 0) {
   WctCarve w;
   const int Nmax = Nc > Ns ? Nc : Ns;
   w.nslab = wct_nslab(Nmax);
   cov_split(C, Nmax, 1, &w.nsplit, &w.ksplit);   // independent of P: a pair's result must not depend on its batch
+  if (nslab_max > 0) w.nslab = nslab_max;
+  if (nsplit_max > 0) w.nsplit = nsplit_max;
   size_t off = 0;
   char* b = reinterpret_cast<char*>(base);
   auto take = [&](size_t bytes) { void* p = b ? b + off : nullptr; off += align_up(bytes); return p; };
@@ -2392,6 +2399,7 @@ static WctCarve carve(void* base, int C, int Nc, int Ns, int P) {
   w.jacobi_bytes = jacobi_workspace_bytes(C, 2 * P) + 4 * (1024 + 64 * sizeof(JacobiState));   // (+ the alignment slack of
                                                                                                  //  the former four-group split)
   w.jacobi_ws = take(w.jacobi_bytes);
+  w.mix = (float*)take((size_t)2 * C * sizeof(float));      // the AdaIN mix's mean and standard deviation (launch_adain_mix)
   w.total = off;
   return w;
 }
@@ -2444,6 +2452,74 @@ static int launch_refresh(const WctCarve& w, int C, int P, int shared_style, hip
   return rc;
 }
 
+// The spectral tail of a level, all 2P matrices in merged launches: Tw / Tcs [m] = V f(A) V^T (whitening for the even matrices,
+// colouring for the odd ones), plus the bias vectors and cleared mabs words of the opening pass.  nwhite: the pairs whose
+// whitening side is live (P; 1 for a style mix, whose content is matrix 0 alone).
+static int launch_spectral_tail(const WctCarve& w, int C, int P, float alpha, int mode, float eps_in, int shared_style, int nwhite,
+                                hipStream_t s) {
+  int rc;
+  const size_t cc = (size_t)C * C;
+  // Tw = Vc f_c(Ac) Vc^T, Tcs = Vs f_s(As) Vs^T with the first- and second-order completion of f on the residual
+  // off-diagonals; the wct_np semantics shift the kept eigenvalues by eps inside the gains (ops.py:114,127), wct_tf does not.
+  // One launch of each kind over all 2P matrices of the level (see spectral_open_all_kernel).
+  const float shift = mode == WCT_MODE_NP ? (eps_in >= 0.f ? eps_in : 1e-5f) : 0.f;
+  const int second = EIG_CORRECT >= 2;
+  const dim3 tiles(cdiv(C, 64), cdiv(C, 64), 2 * P);
+  if ((rc = launch_refresh(w, C, P, shared_style, s))) return rc;
+  SpecAllArgs sa = {};
+  sa.A = w.A; sa.G = w.G; sa.C = C; sa.shift = shift; sa.correct = EIG_CORRECT; sa.second = second; sa.shared_style = shared_style;
+  sa.N = w.S2; float* X2 = sa.N + 2 * P * cc; sa.R = X2 + 2 * P * cc; sa.Pm = sa.R + P * cc; float* X1 = sa.Pm + P * cc;
+  sa.X1 = X1; sa.X2 = X2;
+  sa.mabs = w.mabs; sa.mean = w.mean; sa.bias = w.bias; sa.alpha = alpha; sa.mode = mode;
+  hipLaunchKernelGGL(spectral_open_all_kernel, tiles, dim3(256), 0, s, sa);
+  HIP_TRY(hipGetLastError());
+  if (second) {
+    GemmArgs a = {};   // X2[m] = (colouring: N[m], whitening: Pm[pair]) . N[m]
+    a.A = sa.Pm; a.sA = cc; a.A_odd = sa.N + cc; a.sA_odd = 2 * cc; a.lda = C; a.a_kmajor = 0;
+    a.B = sa.N; a.ldb = C; a.b_kmajor = 1; a.sB = cc; a.skip_shared = shared_style;
+    a.M = C; a.N = C; a.K = C; a.ksplit = C; a.out32 = X2; a.ldo = C; a.s_out = cc;
+    if ((rc = launch_gemm(a, 1, 2 * P, s))) return rc;
+    GemmArgs b = {};   // X1[pair] = R[pair] . N[2 pair]   (whitening side only)
+    b.A = sa.R; b.sA = cc; b.lda = C; b.a_kmajor = 0; b.B = sa.N; b.ldb = C; b.b_kmajor = 1; b.sB = 2 * cc;
+    b.M = C; b.N = C; b.K = C; b.ksplit = C; b.out32 = X1; b.ldo = C; b.s_out = cc;
+    if ((rc = launch_gemm(b, 1, nwhite, s))) return rc;
+    hipLaunchKernelGGL(spectral_add2_all_kernel, tiles, dim3(256), 0, s, sa);
+    HIP_TRY(hipGetLastError());
+  }
+  GemmArgs g = {};   // X[m] = V[m] G[m]
+  g.A = w.V; g.lda = C; g.a_kmajor = 0; g.B = w.G; g.ldb = C; g.b_kmajor = 1; g.sA = g.sB = cc; g.skip_shared = shared_style;
+  g.M = C; g.N = C; g.K = C; g.ksplit = C; g.out32 = w.X; g.ldo = C; g.s_out = cc;
+  if ((rc = launch_gemm(g, 1, 2 * P, s))) return rc;
+  GemmArgs h = {};   // Tw / Tcs [m] = X[m] V[m]^T
+  h.A = w.X; h.lda = C; h.a_kmajor = 0; h.B = w.V; h.ldb = C; h.b_kmajor = 0; h.sA = h.sB = cc; h.skip_shared = shared_style;
+  h.M = C; h.N = C; h.K = C; h.ksplit = C; h.out32 = w.Tw; h.ldo = C; h.s_out = cc;
+  if ((rc = launch_gemm(h, 1, 2 * P, s))) return rc;
+  return WCT_OK;
+}
+
+// M = alpha (Tcs . Tw) + (1 - alpha) I for P pairs, then the apply out = (x - mc) M^T + bias
+static int launch_blend_apply(const WctCarve& w, const float* content, int Nc, int C, int P, float alpha, int shared_style,
+                              half_t* out16, float* out32, hipStream_t s) {
+  int rc;
+  const size_t cc = (size_t)C * C;
+  {
+    GemmArgs g = {};   // M = alpha (Tcs . Tw) + (1 - alpha) I, max |M| -> mabs: the blend in the product's epilogue
+    g.A = w.Tcs; g.lda = C; g.a_kmajor = 0; g.B = w.Tw; g.ldb = C; g.b_kmajor = 1; g.sA = shared_style ? 0 : 2 * cc; g.sB = 2 * cc;
+    g.M = C; g.N = C; g.K = C; g.ksplit = C; g.out32 = w.M; g.ldo = C; g.s_out = cc;
+    g.blend = 1; g.alpha = alpha; g.mabs = w.mabs;
+    if ((rc = launch_gemm(g, 1, P, s))) return rc;
+  }
+  {  // out[n][j] = sum_k (x[n][k]-mc[k]) M[j][k] + bias[j]
+    ApplyArgs a;
+    a.x = content; a.N = Nc; a.C = C; a.mean = w.mean; a.M = w.M; a.bias = w.bias;
+    a.xscale = w.scale; a.mabs = w.mabs; a.out16 = out16; a.out32 = out32;
+    if (C >= 128) hipLaunchKernelGGL((apply_f16x2_kernel<128, 128>), dim3(cdiv(Nc, 128), cdiv(C, 128), P), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((apply_f16x2_kernel<64, 128>), dim3(cdiv(Nc, 128), cdiv(C, 64), P), dim3(256), 0, s, a);
+  }
+  HIP_TRY(hipGetLastError());
+  return WCT_OK;
+}
+
 int launch_wct(const float* content, int Nc, const float* style, int Ns, int C, int P, float alpha, int mode, float eps_in,
                half_t* out16, float* out32, void* workspace, size_t workspace_bytes, int* sweeps_dev,
                int stages, hipStream_t s, int shared_style, int* eig_fail, const WctFeatStats* stats) {
@@ -2454,7 +2530,6 @@ int launch_wct(const float* content, int Nc, const float* style, int Ns, int C, 
   WctCarve w = carve(workspace, C, Nc, Ns, P);
   ARG_CHECK(workspace_bytes >= w.total);
   int rc;
-  const size_t cc = (size_t)C * C;
   if (stages & WCT_STAGE_COV) {
   if ((rc = launch_means(content, Nc, style, Ns, C, P, w, false, shared_style, s, stats))) return rc;
 
@@ -2487,71 +2562,171 @@ int launch_wct(const float* content, int Nc, const float* style, int Ns, int C, 
   }
   if (!(stages & WCT_STAGE_APPLY)) return WCT_OK;
 
-  {
-    // Tw = Vc f_c(Ac) Vc^T, Tcs = Vs f_s(As) Vs^T with the first- and second-order completion of f on the residual
-    // off-diagonals; the wct_np semantics shift the kept eigenvalues by eps inside the gains (ops.py:114,127), wct_tf does not.
-    // One launch of each kind over all 2P matrices of the level (see spectral_open_all_kernel).
-    const float shift = mode == WCT_MODE_NP ? (eps_in >= 0.f ? eps_in : 1e-5f) : 0.f;
-    const int second = EIG_CORRECT >= 2;
-    const dim3 tiles(cdiv(C, 64), cdiv(C, 64), 2 * P);
-    if ((rc = launch_refresh(w, C, P, shared_style, s))) return rc;
-    SpecAllArgs sa = {};
-    sa.A = w.A; sa.G = w.G; sa.C = C; sa.shift = shift; sa.correct = EIG_CORRECT; sa.second = second; sa.shared_style = shared_style;
-    sa.N = w.S2; float* X2 = sa.N + 2 * P * cc; sa.R = X2 + 2 * P * cc; sa.Pm = sa.R + P * cc; float* X1 = sa.Pm + P * cc;
-    sa.X1 = X1; sa.X2 = X2;
-    sa.mabs = w.mabs; sa.mean = w.mean; sa.bias = w.bias; sa.alpha = alpha; sa.mode = mode;
-    hipLaunchKernelGGL(spectral_open_all_kernel, tiles, dim3(256), 0, s, sa);
-    HIP_TRY(hipGetLastError());
-    if (second) {
-      GemmArgs a = {};   // X2[m] = (colouring: N[m], whitening: Pm[pair]) . N[m]
-      a.A = sa.Pm; a.sA = cc; a.A_odd = sa.N + cc; a.sA_odd = 2 * cc; a.lda = C; a.a_kmajor = 0;
-      a.B = sa.N; a.ldb = C; a.b_kmajor = 1; a.sB = cc; a.skip_shared = shared_style;
-      a.M = C; a.N = C; a.K = C; a.ksplit = C; a.out32 = X2; a.ldo = C; a.s_out = cc;
-      if ((rc = launch_gemm(a, 1, 2 * P, s))) return rc;
-      GemmArgs b = {};   // X1[pair] = R[pair] . N[2 pair]   (whitening side only)
-      b.A = sa.R; b.sA = cc; b.lda = C; b.a_kmajor = 0; b.B = sa.N; b.ldb = C; b.b_kmajor = 1; b.sB = 2 * cc;
-      b.M = C; b.N = C; b.K = C; b.ksplit = C; b.out32 = X1; b.ldo = C; b.s_out = cc;
-      if ((rc = launch_gemm(b, 1, P, s))) return rc;
-      hipLaunchKernelGGL(spectral_add2_all_kernel, tiles, dim3(256), 0, s, sa);
-      HIP_TRY(hipGetLastError());
-    }
-    GemmArgs g = {};   // X[m] = V[m] G[m]
-    g.A = w.V; g.lda = C; g.a_kmajor = 0; g.B = w.G; g.ldb = C; g.b_kmajor = 1; g.sA = g.sB = cc; g.skip_shared = shared_style;
-    g.M = C; g.N = C; g.K = C; g.ksplit = C; g.out32 = w.X; g.ldo = C; g.s_out = cc;
-    if ((rc = launch_gemm(g, 1, 2 * P, s))) return rc;
-    GemmArgs h = {};   // Tw / Tcs [m] = X[m] V[m]^T
-    h.A = w.X; h.lda = C; h.a_kmajor = 0; h.B = w.V; h.ldb = C; h.b_kmajor = 0; h.sA = h.sB = cc; h.skip_shared = shared_style;
-    h.M = C; h.N = C; h.K = C; h.ksplit = C; h.out32 = w.Tw; h.ldo = C; h.s_out = cc;
-    if ((rc = launch_gemm(h, 1, 2 * P, s))) return rc;
+  if ((rc = launch_spectral_tail(w, C, P, alpha, mode, eps_in, shared_style, P, s))) return rc;
+  return launch_blend_apply(w, content, Nc, C, P, alpha, shared_style, out16, out32, s);
+}
+
+// ---------------------------------------------------------------------------
+// Style mix (Li et al. 2017, sec. 4.2): mix(fc) = sum_k lambda_k T(fc, fs_k, alpha), sum_k lambda_k = 1.  T is affine in the
+// colouring side, so the mix is ONE transform with Tcs_mix = sum_k lambda_k Tcs_k and bias_mix = sum_k lambda_k bias_k.
+// Slot layout: the P = K pair layout of carve(), matrix 0 the content, matrix 2k + 1 style k; the content slots 2k (k >= 1) are
+// skipped everywhere (WCT_SKIP_MIX), so the content's statistics, covariance, eigensystem and whitening run once, and the K + 1
+// live matrices share one batched eigensolve.  Every matrix keeps the slab / K-slice layout it has in the single-pair
+// transform of its own (content, style) pair -- style k that of (content, style k), the content that of (content, style
+// ref), ref = the style of the largest weight -- so each of them comes out bit for bit as launch_wct computes it: K = 1, and
+// one-hot weights, give launch_wct's output exactly (the mix below starts from 0 and 0 + 1 x = x).
+// ---------------------------------------------------------------------------
+struct MixLayout { int nslab[2 * WCT_MIX_MAX], nsplit[2 * WCT_MIX_MAX], ksplit[2 * WCT_MIX_MAX], nslab_max, nsplit_max, Nsmax; };
+
+static void mix_layout(int C, int Nc, const int* Ns, int K, const float* lambda, MixLayout* L) {
+  int ref = 0;
+  for (int k = 1; k < K; ++k) if (lambda[k] > lambda[ref]) ref = k;
+  L->nslab_max = L->nsplit_max = L->Nsmax = 0;
+  for (int m = 0; m < 2 * K; ++m) {
+    if (m > 0 && (m & 1) == 0) { L->nslab[m] = L->nsplit[m] = L->ksplit[m] = 0; continue; }   // skipped content slots
+    const int ns = Ns[m == 0 ? ref : m >> 1];
+    const int Nmax = Nc > ns ? Nc : ns;
+    L->nslab[m] = wct_nslab(Nmax);
+    cov_split(C, Nmax, 1, &L->nsplit[m], &L->ksplit[m]);
+    L->nslab_max = std::max(L->nslab_max, L->nslab[m]);
+    L->nsplit_max = std::max(L->nsplit_max, L->nsplit[m]);
+    L->Nsmax = std::max(L->Nsmax, ns);
   }
-  {
-    GemmArgs g = {};   // M = alpha (Tcs . Tw) + (1 - alpha) I, max |M| -> mabs: the blend in the product's epilogue
-    g.A = w.Tcs; g.lda = C; g.a_kmajor = 0; g.B = w.Tw; g.ldb = C; g.b_kmajor = 1; g.sA = shared_style ? 0 : 2 * cc; g.sB = 2 * cc;
-    g.M = C; g.N = C; g.K = C; g.ksplit = C; g.out32 = w.M; g.ldo = C; g.s_out = cc;
-    g.blend = 1; g.alpha = alpha; g.mabs = w.mabs;
-    if ((rc = launch_gemm(g, 1, P, s))) return rc;
-  }
-  {  // out[n][j] = sum_k (x[n][k]-mc[k]) M[j][k] + bias[j]
-    ApplyArgs a;
-    a.x = content; a.N = Nc; a.C = C; a.mean = w.mean; a.M = w.M; a.bias = w.bias;
-    a.xscale = w.scale; a.mabs = w.mabs; a.out16 = out16; a.out32 = out32;
-    if (C >= 128) hipLaunchKernelGGL((apply_f16x2_kernel<128, 128>), dim3(cdiv(Nc, 128), cdiv(C, 128), P), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((apply_f16x2_kernel<64, 128>), dim3(cdiv(Nc, 128), cdiv(C, 64), P), dim3(256), 0, s, a);
+}
+
+static WctCarve carve_mix(void* base, int C, int Nc, const int* Ns, int K, const float* lambda, MixLayout* L) {
+  mix_layout(C, Nc, Ns, K, lambda, L);
+  return carve(base, C, Nc, L->Nsmax, K, L->nslab_max, L->nsplit_max);
+}
+
+size_t wct_mix_workspace_bytes(int C, int Nc, const int* Ns, int K, const float* lambda) {
+  MixLayout L;
+  return carve_mix(nullptr, C < 32 ? 32 : C, Nc, Ns, K, lambda, &L).total;
+}
+
+static bool mix_args_ok(const float* const* styles, const int* Ns, int K, const float* lambda, int nmin) {
+  if (!styles || !Ns || !lambda || K < 1 || K > WCT_MIX_MAX) return false;
+  for (int k = 0; k < K; ++k)
+    if (!styles[k] || Ns[k] < nmin || !(lambda[k] >= 0.f && lambda[k] <= 1.f)) return false;
+  return true;
+}
+
+// first statistics pass (means, the fp16 scale; with_var: the variances) of ONE matrix, slot `m` of the workspace, with its own
+// slab count: the kernels of launch_means on a one-matrix grid (side 0), pointed at the slot
+static int launch_slot_means(const float* x, int N, int C, int m, int nslab, const WctCarve& w, bool with_var, hipStream_t s,
+                             const float* u = nullptr, const unsigned* umax = nullptr) {
+  StatArgs sa = {};
+  sa.x[0] = sa.x[1] = x; sa.n[0] = sa.n[1] = N;
+  sa.u[0] = umax ? u : nullptr; sa.umax[0] = sa.u[0] ? umax : nullptr;
+  float* partial = w.stat_partial + (size_t)m * w.nslab * C;
+  float* absmax = w.absmax + (size_t)m * w.nslab;
+  sa.mean = nullptr; sa.partial = partial; sa.absmax = absmax; sa.C = C; sa.nslab = nslab; sa.shared_style = 0;
+  hipLaunchKernelGGL(colsum_kernel, dim3(nslab, 1), dim3(256), 0, s, sa);
+  hipLaunchKernelGGL(colsum_finish_kernel, dim3(cdiv(C, 256), 1), dim3(256), 0, s, partial, w.mean + (size_t)m * C, C, nslab, (float)N,
+                     (float)N, 0, (const float*)absmax, w.scale + m);
+  if (with_var) {
+    sa.mean = w.mean + (size_t)m * C; sa.absmax = nullptr;
+    hipLaunchKernelGGL(colsum_kernel, dim3(nslab, 1), dim3(256), 0, s, sa);
+    hipLaunchKernelGGL(colsum_finish_kernel, dim3(cdiv(C, 256), 1), dim3(256), 0, s, partial, w.var + (size_t)m * C, C, nslab, (float)N,
+                       (float)N, 0, (const float*)nullptr, (float*)nullptr);
   }
   HIP_TRY(hipGetLastError());
   return WCT_OK;
 }
 
+// covariance of ONE matrix into slot m (A and A0), K-slices of its own layout
+static int launch_slot_cov(const float* x, int N, int C, int m, int nsplit, int ksplit, float eps, const WctCarve& w, hipStream_t s) {
+  const int BT = C >= 128 ? 128 : 64;
+  const size_t cc = (size_t)C * C;
+  CovArgs ca;
+  ca.x[0] = ca.x[1] = x; ca.n[0] = ca.n[1] = N;
+  ca.mean = w.mean + (size_t)m * C; ca.scale = w.scale + m; ca.partial = w.cov_partial + (size_t)m * w.nsplit * cc;
+  ca.C = C; ca.ksplit = ksplit; ca.nsplit = nsplit; ca.ntile = cdiv(C, BT); ca.shared_style = 0;
+  dim3 grid(ca.ntile * (ca.ntile + 1) / 2, nsplit, 1);
+  if (BT == 128) hipLaunchKernelGGL((cov_f16x2_kernel<128>), grid, dim3(256), 0, s, ca);
+  else hipLaunchKernelGGL((cov_f16x2_kernel<64>), grid, dim3(256), 0, s, ca);
+  hipLaunchKernelGGL(cov_finish_kernel, dim3(cdiv(C, 64), cdiv(C, 64), 1), dim3(256), 0, s,
+                     ca.partial, ca.scale, w.A + m * cc, C, nsplit, BT, 1.f / (float)(N - 1), 1.f / (float)(N - 1), eps, 0, w.A0 + m * cc);
+  HIP_TRY(hipGetLastError());
+  return WCT_OK;
+}
+
+struct MixWeights { float lambda[WCT_MIX_MAX]; int K; };
+
+// Tcs_mix = sum_k lambda_k Tcs_k (Tcs_k = matrix 2k + 1 of Tw) into matrix 1, bias_mix = sum_k lambda_k bias_k into bias[0]:
+// fp32, k in order, from 0.  In place: an element is read (all k) and written by one thread.
+__global__ __launch_bounds__(256) void wct_mix_kernel(float* Tw, float* bias, int C, MixWeights mw) {
+  const size_t cc = (size_t)C * C, n4 = cc / 4;
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    for (int k = 0; k < mw.K; ++k) {
+      const f32x4 t = *reinterpret_cast<const f32x4*>(Tw + (2 * k + 1) * cc + i * 4);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) acc[j] = fmaf(mw.lambda[k], t[j], acc[j]);
+    }
+    *reinterpret_cast<f32x4*>(Tw + cc + i * 4) = acc;
+  }
+  if (blockIdx.x == 0)
+    for (int c = threadIdx.x; c < C; c += blockDim.x) {
+      float acc = 0.f;
+      for (int k = 0; k < mw.K; ++k) acc = fmaf(mw.lambda[k], bias[(size_t)k * C + c], acc);
+      bias[c] = acc;
+    }
+}
+
+int launch_wct_mix(const float* content, int Nc, const float* const* styles, const int* Ns, int K, const float* lambda, int C,
+                   float alpha, int mode, float eps_in, half_t* out16, float* out32, void* workspace, size_t workspace_bytes,
+                   int* sweeps_dev, int stages, hipStream_t s, int* eig_fail, const WctFeatStats* stats) {
+  ARG_CHECK(C % 32 == 0 && C >= 32 && C <= 1024 && Nc >= 2 && content && mix_args_ok(styles, Ns, K, lambda, 2));
+  ARG_CHECK(mode == WCT_MODE_NP || mode == WCT_MODE_TF);
+  ARG_CHECK((size_t)Nc * C * 4 < ((size_t)1 << 31));
+  for (int k = 0; k < K; ++k) ARG_CHECK((size_t)Ns[k] * C * 4 < ((size_t)1 << 31));
+  MixLayout L;
+  WctCarve w = carve_mix(workspace, C, Nc, Ns, K, lambda, &L);
+  ARG_CHECK(workspace_bytes >= w.total);
+  int rc;
+  if (stages & WCT_STAGE_COV) {
+    const float eps_user = eps_in >= 0.f ? eps_in : (mode == WCT_MODE_TF ? 1e-8f : 1e-5f);   // (as launch_wct)
+    const float eps = mode == WCT_MODE_TF ? eps_user : 0.f;
+    const WctFeatStats* fs = stats && stats->umax[0] ? stats : nullptr;
+    if ((rc = launch_slot_means(content, Nc, C, 0, L.nslab[0], w, false, s, fs ? fs->u[0] : nullptr, fs ? fs->umax[0] : nullptr))) return rc;
+    if ((rc = launch_slot_cov(content, Nc, C, 0, L.nsplit[0], L.ksplit[0], eps, w, s))) return rc;
+    for (int k = 0; k < K; ++k) {
+      const int m = 2 * k + 1;
+      if ((rc = launch_slot_means(styles[k], Ns[k], C, m, L.nslab[m], w, false, s))) return rc;
+      if ((rc = launch_slot_cov(styles[k], Ns[k], C, m, L.nsplit[m], L.ksplit[m], eps, w, s))) return rc;
+    }
+  }
+  if (stages & WCT_STAGE_EIG) {
+    JacobiGroup G;
+    if ((rc = jacobi_make_group(&G, w.A, w.V, C, 2 * K, w.jacobi_ws, w.jacobi_bytes, sweeps_dev, eig_fail, s))) return rc;
+    G.shared_style = WCT_SKIP_MIX; G.tol_fn = JACOBI_TOL_FN_WCT; G.u_f16 = 1;
+    if ((rc = jacobi_dispatch(G, C))) return rc;
+  }
+  if (!(stages & WCT_STAGE_APPLY)) return WCT_OK;
+  if ((rc = launch_spectral_tail(w, C, K, alpha, mode, eps_in, WCT_SKIP_MIX, 1, s))) return rc;
+  MixWeights mw = {};
+  mw.K = K;
+  for (int k = 0; k < K; ++k) mw.lambda[k] = lambda[k];
+  const size_t n4 = (size_t)C * C / 4;
+  hipLaunchKernelGGL(wct_mix_kernel, dim3((unsigned)std::min<size_t>((n4 + 255) / 256, 1024)), dim3(256), 0, s, w.Tw, w.bias, C, mw);
+  HIP_TRY(hipGetLastError());
+  return launch_blend_apply(w, content, Nc, C, 1, alpha, 0, out16, out32, s);
+}
+
 // ---------------------------------------------------------------------------
 // AdaIN (ops.py:282-294): out = alpha*((x-mu_c)*rsqrt(var_c+eps)*sqrt(var_s)+mu_s) + (1-alpha)*x
 // ---------------------------------------------------------------------------
+// mix_mu / mix_sd (or null): the style moments as a mean and a STANDARD DEVIATION (a style mix, launch_adain_mix: squaring the
+// mixed deviation to hand it over as a variance would not round-trip through sqrtf)
 __global__ void adain_apply_kernel(const float* x, size_t n4_per_pair, int C, const float* mean, const float* var,
-                                   float alpha, float eps, half_t* out16, float* out32, int shared_style) {
+                                   float alpha, float eps, half_t* out16, float* out32, int shared_style,
+                                   const float* mix_mu = nullptr, const float* mix_sd = nullptr) {
   const int pair = blockIdx.y;
   const int cq = C / 4;
   const float* mp = mean + (size_t)pair * 2 * C;
   const float* vp = var + (size_t)pair * 2 * C;
-  const float* ms = mean + (size_t)(shared_style ? 0 : pair) * 2 * C + C;   // style moments
+  const float* ms = mix_mu ? mix_mu : mean + (size_t)(shared_style ? 0 : pair) * 2 * C + C;   // style moments
   const float* vs = var + (size_t)(shared_style ? 0 : pair) * 2 * C + C;
   const size_t base = (size_t)pair * n4_per_pair;
   for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n4_per_pair; i += (size_t)gridDim.x * blockDim.x) {
@@ -2561,7 +2736,8 @@ __global__ void adain_apply_kernel(const float* x, size_t n4_per_pair, int C, co
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const float inv = 1.f / sqrtf(vp[c + j] + eps);
-      const float y = (v[j] - mp[c + j]) * inv * sqrtf(vs[c + j]) + ms[c + j];
+      const float sd = mix_sd ? mix_sd[c + j] : sqrtf(vs[c + j]);
+      const float y = (v[j] - mp[c + j]) * inv * sd + ms[c + j];
       o[j] = alpha * y + (1.f - alpha) * v[j];
     }
     if (out32) *reinterpret_cast<f32x4*>(out32 + (base + i) * 4) = o;
@@ -2586,6 +2762,44 @@ int launch_adain(const float* content, int Nc, const float* style, int Ns, int C
   size_t blocks = (n4 + 255) / 256;
   if (blocks > 2048) blocks = 2048;
   hipLaunchKernelGGL(adain_apply_kernel, dim3((unsigned)blocks, P), dim3(256), 0, s, content, n4, C, w.mean, w.var, alpha, eps, out16, out32, shared_style);
+  HIP_TRY(hipGetLastError());
+  return WCT_OK;
+}
+
+// AdaIN style mix: mu_mix = sum_k lambda_k mu_k, sd_mix = sum_k lambda_k sqrt(var_k) (fp32, k in order, from 0) into w.mix
+__global__ void adain_mix_moments_kernel(const float* mean, const float* var, float* mix, int C, MixWeights mw) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= C) return;
+  float mu = 0.f, sd = 0.f;
+  for (int k = 0; k < mw.K; ++k) {
+    mu = fmaf(mw.lambda[k], mean[(size_t)(2 * k + 1) * C + c], mu);
+    sd = fmaf(mw.lambda[k], sqrtf(var[(size_t)(2 * k + 1) * C + c]), sd);
+  }
+  mix[c] = mu;
+  mix[C + c] = sd;
+}
+
+int launch_adain_mix(const float* content, int Nc, const float* const* styles, const int* Ns, int K, const float* lambda, int C,
+                     float alpha, float eps, half_t* out16, float* out32, void* workspace, size_t workspace_bytes, hipStream_t s,
+                     const WctFeatStats* stats) {
+  ARG_CHECK(C % 4 == 0 && C <= 1024 && Nc >= 1 && content && mix_args_ok(styles, Ns, K, lambda, 1));
+  MixLayout L;
+  WctCarve w = carve_mix(workspace, C < 32 ? 32 : C, Nc, Ns, K, lambda, &L);
+  ARG_CHECK(workspace_bytes >= w.total);
+  int rc;
+  const WctFeatStats* fs = stats && stats->umax[0] ? stats : nullptr;
+  if ((rc = launch_slot_means(content, Nc, C, 0, L.nslab[0], w, true, s, fs ? fs->u[0] : nullptr, fs ? fs->umax[0] : nullptr))) return rc;
+  for (int k = 0; k < K; ++k)
+    if ((rc = launch_slot_means(styles[k], Ns[k], C, 2 * k + 1, L.nslab[2 * k + 1], w, true, s))) return rc;
+  MixWeights mw = {};
+  mw.K = K;
+  for (int k = 0; k < K; ++k) mw.lambda[k] = lambda[k];
+  hipLaunchKernelGGL(adain_mix_moments_kernel, dim3(cdiv(C, 256)), dim3(256), 0, s, w.mean, w.var, w.mix, C, mw);
+  const size_t n4 = (size_t)Nc * C / 4;
+  size_t blocks = (n4 + 255) / 256;
+  if (blocks > 2048) blocks = 2048;
+  hipLaunchKernelGGL(adain_apply_kernel, dim3((unsigned)blocks, 1), dim3(256), 0, s, content, n4, C, w.mean, w.var, alpha, eps, out16, out32, 0,
+                     (const float*)w.mix, (const float*)(w.mix + C));
   HIP_TRY(hipGetLastError());
   return WCT_OK;
 }

@@ -2,7 +2,8 @@
 MI355X path.  Flag names, defaults and the output naming `{content}_{style}{ext}` are the reference's; `--checkpoints`
 takes TF checkpoint directories or .npz files (see wct.py), `--vgg-path` the .t7 or a .npz, and
 `--synthetic-weights SEED` stands in when neither exists.  Under torchrun each rank takes a shard of the content
-files (rank_shard); `--gpus N` without a launcher starts the N ranks itself."""
+files (rank_shard); `--gpus N` without a launcher starts the N ranks itself.  `--interp-styles a b [--interp-weights wa wb]`
+stylizes with a weighted mix of the styles (Li et al. 2017, sec. 4.2; the reference's README TODO)."""
 import argparse
 import os
 import time
@@ -36,6 +37,11 @@ _FLAGS = [
     (('--ss-stride',), dict(type=int, default=1, help='style-swap stride')),
     (('--synthetic-weights',), dict(type=int, default=None, metavar='SEED', help='seeded synthetic weights instead of files')),
     (('--wct-mode',), dict(choices=['tf', 'np'], default='tf', help='wct_tf (the graph) or wct_np semantics')),
+    (('--interp-styles',), dict(nargs='+', default=None, metavar='PATH',
+                                help='interpolate between these style images (Li et al. 2017, sec. 4.2): one output per '
+                                     'content, named {content}_{style1}+{style2}+...; not with --style-path / -r')),
+    (('--interp-weights',), dict(nargs='+', type=float, default=None, metavar='W',
+                                 help='one weight >= 0 per --interp-styles image, normalised to sum 1 (default: equal)')),
     (('--gpus',), dict(type=int, default=0, metavar='N',
                        help='shard the content files over N GPUs of this node, one process per GPU: started here when no '
                             'launcher did (0: whatever the launcher set, else one GPU)')),
@@ -98,9 +104,51 @@ def stylize_pair(model, content, style, args):
     return out
 
 
+def check_interp_args(parser, args):
+    """--interp-styles / --interp-weights: the argument errors of a style mix (parser.error exits)."""
+    if args.interp_styles is None:
+        if args.interp_weights is not None:
+            parser.error('--interp-weights needs --interp-styles')
+        return
+    if args.style_path is not None or args.random > 0:
+        parser.error('--interp-styles replaces --style-path and -r/--random: give one or the other')
+    if args.swap5 and len(args.interp_styles) > 1:
+        parser.error('--swap5 takes one style: style-swap is not linear in the style')
+    if args.interp_weights is not None:
+        if len(args.interp_weights) != len(args.interp_styles):
+            parser.error('--interp-weights has %d values for %d --interp-styles' % (len(args.interp_weights), len(args.interp_styles)))
+        if any(not np.isfinite(w) or w < 0 for w in args.interp_weights):
+            parser.error('--interp-weights must be finite and >= 0')
+        if not sum(args.interp_weights) > 0:
+            parser.error('--interp-weights sum to 0')
+    if len(args.interp_styles) > 8:
+        parser.error('--interp-styles takes at most 8 styles')
+
+
+def interp_name(content_path, style_paths):
+    """output file of a style mix: {content}_{style1}+{style2}+...{ext of the content}"""
+    return '%s_%s%s' % (_stem(content_path), '+'.join(_stem(p) for p in style_paths), os.path.splitext(content_path)[1])
+
+
+def stylize_mix_pair(model, content, styles, args):
+    """one output of a style mix: stylize_pair with every style taking part -- CORAL per style (--keep-colors), `--passes`
+    mixes, and --concat with the K styles to the left of the result"""
+    if args.keep_colors:
+        from .ops import preserve_colors_np
+        styles = [preserve_colors_np(s, content, ctx=model.sess) for s in styles]
+    out = content
+    for _ in range(max(1, args.passes)):
+        out = model.predict_mix(out, styles, args.interp_weights, args.alpha, args.adain, args.swap5, args.ss_alpha)
+    if args.concat:
+        side = out.shape[0]
+        out = np.hstack([utils._imresize(s, (side, side)) for s in styles] + [out])
+    return out
+
+
 def main(argv=None):
     parser = build_parser()
     args = parser.parse_args(argv)
+    check_interp_args(parser, args)
     if args.synthetic_weights is None and not args.checkpoints:
         parser.error('--checkpoints is required (stylize.py:17) unless --synthetic-weights SEED is given')
     if args.gpus > 0:
@@ -122,11 +170,23 @@ def main(argv=None):
     model = WCT(checkpoints=args.checkpoints, relu_targets=args.relu_targets, vgg_path=args.vgg_path,
                 device=device or args.device, ss_patch_size=args.ss_patch_size, ss_stride=args.ss_stride,
                 weights=weights, wct_mode=args.wct_mode)
+    os.makedirs(args.out_path, exist_ok=True)
+    written = 0
+    if args.interp_styles is not None:
+        mix = [load_style(p, args) for p in args.interp_styles]
+        for cpath in contents:
+            content = utils.get_img(cpath)
+            if args.content_size > 0:
+                content = utils.resize_to(content, args.content_size)
+            target = os.path.join(args.out_path, interp_name(cpath, args.interp_styles))
+            utils.save_img(target, stylize_mix_pair(model, content, mix, args))
+            written += 1
+            print('%d: wrote %s' % (written, target))
+        print('%d outputs in %.1f s' % (written, time.time() - t0))
+        return written
     styles = _listing(args.style_path)
     if os.path.isdir(args.style_path) and args.random > 0:
         styles = list(np.random.choice(styles, args.random))
-    os.makedirs(args.out_path, exist_ok=True)
-    written = 0
     for cpath in contents:
         content = utils.get_img(cpath)
         if args.content_size > 0:

@@ -2,6 +2,7 @@
 
     WCT(checkpoints, relu_targets, vgg_path, device='/gpu:0', ss_patch_size=3, ss_stride=1)
     WCT.predict(content, style, alpha=1, swap5=False, ss_alpha=1, adain=False) -> uint8 HxWx3
+    WCT.predict_mix(content, styles, weights=None, alpha=1, adain=False, swap5=False, ss_alpha=1) -> uint8 HxWx3
 
 `checkpoints` / `vgg_path`: the reference restores TF checkpoints and a .t7 file
 (wct.py:46-58, vgg_normalised.py:16).  Per decoder this class takes either of
@@ -103,6 +104,27 @@ class WCT(object):
         # reference's preprocess does (wct.py:60-64) -- Context.stylize hands them over as float32 images
         return self.sess.stylize(content, style, self.relu_targets, alpha=alpha, adain=adain,
                                  wct_mode=self.wct_mode, swap5=bool(swap5))
+
+    def predict_mix(self, content, styles, weights=None, alpha=1, adain=False, swap5=False, ss_alpha=1):
+        '''Stylize with a weighted mix of several styles (Li et al. 2017, sec. 4.2; the reference's README TODO
+           "Interpolation between styles"): every level applies sum_k lambda_k T(content, style_k), lambda = weights /
+           sum(weights); weights=None means equal weights.  Arrays in [0,255], returns uint8 HxWx3.  One style gives
+           predict(content, style) bit for bit, as do one-hot weights.  swap5 takes one style only (style-swap is not linear).'''
+        from ._lib import mix_weights
+        styles = [np.asarray(s) for s in styles]
+        weights = mix_weights(weights, len(styles))              # ValueError before any GPU call
+        if swap5 and len(styles) > 1:
+            raise ValueError('swap5 takes one style: style-swap is not linear in the style')
+        content = np.asarray(content)
+        if swap5 is True and self.ss_stride != 1:
+            from .utils import swap_filter_fit, center_crop_to
+            should_refit, H, W = swap_filter_fit(content.shape[0], content.shape[1], self.ss_patch_size, self.ss_stride)
+            if should_refit:
+                content = center_crop_to(content, H, W)
+        if swap5:
+            self.sess.set_style_swap(ss_alpha, self.ss_patch_size, self.ss_stride)
+        return self.sess.stylize_mix(content, styles, weights, self.relu_targets, alpha=alpha, adain=adain,
+                                     wct_mode=self.wct_mode, swap5=bool(swap5))
 
     def predict_frames(self, frames, style, alpha=1, swap5=False, ss_alpha=1, adain=False, batch=16):
         '''Stylize same-sized frames [F][H][W][3] with ONE style image (the loop of stylize_video.py:112-121,
