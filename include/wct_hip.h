@@ -112,6 +112,26 @@ int wct_transform_mix(wct_ctx* ctx, const float* content, int Nc, const float* c
 /* adain (ops.py:282-294) with sqrt(var_s) -> sum_k lambda_k sqrt(var_k) and mean_s -> sum_k lambda_k mean_k */
 int wct_adain_mix(wct_ctx* ctx, const float* content, int Nc, const float* const* styles, const int* Ns, int K,
                   const float* weights, int C, float alpha, float epsilon, float* out);
+/* Spatial control -- a label map picks the style of each region (Li et al. 2017, sec. 4.2 and Fig. 7 "spatial control"; the
+ * reference's README TODO "Spatial control/masking"): with K = 1 .. 8 styles and a label in 0 .. K - 1 per content row,
+ *   out[rows of k] = T(content[rows of k], style k, alpha)
+ * with T the single-style transform of the call below it and region k's own statistics (mean, covariance with 1 / (N_k - 1),
+ * cut-off).  A label with fewer than 2 rows passes its rows through unchanged (N_k - 1 = 0); a label with none is skipped.
+ * A label >= K, or K outside 1 .. 8, is WCT_STATUS_ARG.  Every region comes out bit for bit as the single-style call on its
+ * rows alone, so K = 1 gives that call's output, and a region's rows do not depend on the other regions' styles.
+ * wct_transform_masked: wct_np / wct_tf (ops.py:24-140) as wct_transform; labels [Nc]; styles[k] [Ns[k]][C].
+ *   sweeps_out [2K] or NULL: label k's content sweeps at 2k, its style's at 2k + 1 (wct_transform's contract); 0 for a label
+ *   with fewer than 2 rows. */
+int wct_transform_masked(wct_ctx* ctx, const float* content, int Nc, const uint8_t* labels, const float* const* styles,
+                         const int* Ns, int K, int C, float alpha, int mode, float eps, float* out, int* sweeps_out);
+/* adain (ops.py:282-294) per region, with that region's moments and its style's */
+int wct_adain_masked(wct_ctx* ctx, const float* content, int Nc, const uint8_t* labels, const float* const* styles,
+                     const int* Ns, int K, int C, float alpha, float epsilon, float* out);
+/* the device's stable partition of an h x w feature map's rows by label, row (i, j) labelled
+ * mask[min(i * stride, Hm - 1)][min(j * stride, Wm - 1)]: perm_out [h * w] lists the rows of label 0 in order, then those of
+ * label 1, ...; seg_off_out [K + 1] where each label starts (what the masked calls use; a check of their first pass) */
+int wct_mask_compact(wct_ctx* ctx, const uint8_t* mask, int Hm, int Wm, int h, int w, int stride, int K, int* perm_out,
+                     int* seg_off_out);
 /* wct_style_swap (ops.py:145-278): content [hc*wc][C], style [hs*ws][C], out [hc*wc][C]; `alpha` is the
  * reference's ss_alpha; eps < 0 = its default 1e-8.  (hc, wc) must survive the patch/stride round trip
  * (utils.swap_filter_fit, wct.py:84-90) -- always true for stride 1. */
@@ -175,6 +195,15 @@ int wct_stylize(wct_ctx* ctx, const uint8_t* content, int Hc, int Wc,
 int wct_stylize_mix(wct_ctx* ctx, const uint8_t* content, int Hc, int Wc, const uint8_t* const* styles, const int* Hs,
                     const int* Ws, int K, const float* weights, const int* levels, int n_levels, float alpha, unsigned flags,
                     uint8_t* out);
+/* WCT.predict with spatial control at every level (see wct_transform_masked): mask [Hc][Wc] labels 0 .. K - 1, styles[k] an
+ * Hs[k] x Ws[k] image (sizes may differ).  At level l (stride s = 2^(l-1)) feature pixel (i, j) of the h x w map has the label
+ * mask[min(i s, Hc - 1)][min(j s, Wc - 1)] (the clamp: a later level's input, the decode of the level before, can be larger than
+ * the content).  A label with fewer than 2 pixels at a level keeps that level's features.  Honours WCT_FLAG_MODE_NP,
+ * WCT_FLAG_ADAIN, WCT_FLAG_IMAGES_F32 (all K + 1 images), and WCT_FLAG_SWAP5 only at K = 1 (style-swap is not a per-region
+ * affine map: K > 1 is WCT_STATUS_ARG); WCT_FLAG_STYLE_SHARED is WCT_STATUS_ARG.  K = 1 gives wct_stylize's frame bit for bit. */
+int wct_stylize_masked(wct_ctx* ctx, const uint8_t* content, int Hc, int Wc, const uint8_t* mask, const uint8_t* const* styles,
+                       const int* Hs, const int* Ws, int K, const int* levels, int n_levels, float alpha, unsigned flags,
+                       uint8_t* out);
 /* batched, device-resident variant: B independent pairs (same sizes), content [B][Hc][Wc][3],
  * style [B][Hs][Ws][3], out [B][Ho][Wo][3], all device pointers; asynchronous on the ctx
  * stream (call wct_sync).  This is what bench.py times. */

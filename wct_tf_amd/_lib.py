@@ -33,6 +33,10 @@ SIGNATURES = [
     ('wct_transform_mix', C.c_int, [_P, _F, C.c_int, C.POINTER(_F), _I, C.c_int, _F, C.c_int, C.c_float, C.c_int, C.c_float,
                                     _F, _I]),
     ('wct_adain_mix', C.c_int, [_P, _F, C.c_int, C.POINTER(_F), _I, C.c_int, _F, C.c_int, C.c_float, C.c_float, _F]),
+    ('wct_transform_masked', C.c_int, [_P, _F, C.c_int, _U8, C.POINTER(_F), _I, C.c_int, C.c_int, C.c_float, C.c_int,
+                                       C.c_float, _F, _I]),
+    ('wct_adain_masked', C.c_int, [_P, _F, C.c_int, _U8, C.POINTER(_F), _I, C.c_int, C.c_int, C.c_float, C.c_float, _F]),
+    ('wct_mask_compact', C.c_int, [_P, _U8, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _I, _I]),
     ('wct_style_swap', C.c_int, [_P, _F, C.c_int, C.c_int, _F, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_float, _F]),
     ('wct_set_style_swap', C.c_int, [_P, C.c_float, C.c_int, C.c_int]),
     ('wct_eigh', C.c_int, [_P, _F, C.c_int, C.c_int, _F, _F, _I]),
@@ -48,6 +52,8 @@ SIGNATURES = [
                               C.c_float, C.c_uint, _U8]),
     ('wct_stylize_mix', C.c_int, [_P, _U8, C.c_int, C.c_int, C.POINTER(_U8), _I, _I, C.c_int, _F, _I, C.c_int,
                                   C.c_float, C.c_uint, _U8]),
+    ('wct_stylize_masked', C.c_int, [_P, _U8, C.c_int, C.c_int, _U8, C.POINTER(_U8), _I, _I, C.c_int, _I, C.c_int,
+                                     C.c_float, C.c_uint, _U8]),
     ('wct_stylize_batch_dev', C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, _I,
                                         C.c_int, C.c_float, C.c_uint, _P]),
     ('wct_train_step', C.c_int, [_P, C.c_int, _F, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float,
@@ -140,3 +146,20 @@ def mix_weights(weights, k):
     if not w.sum() > 0:
         raise ValueError('style weights sum to 0')
     return np.ascontiguousarray(w, np.float32)
+
+
+def mask_labels(mask, k, shape=None):
+    """A validated label map as contiguous uint8 (spatial control): integer labels 0 .. k - 1 for k = 1 .. MIX_MAX styles, and,
+    given `shape`, exactly that shape -- the rules the library applies (include/wct_hip.h), checked here before any GPU call."""
+    if not 1 <= k <= MIX_MAX:
+        raise ValueError('a mask takes 1 .. %d styles, got %d' % (MIX_MAX, k))
+    m = np.asarray(mask)
+    if shape is not None and m.shape != tuple(shape):
+        raise ValueError('mask of shape %s for content of shape %s' % (m.shape, tuple(shape)))
+    if m.size == 0:
+        raise ValueError('empty mask')
+    if not (np.issubdtype(m.dtype, np.integer) or np.issubdtype(m.dtype, np.bool_)):
+        raise ValueError('mask labels must be integers, got %s' % (m.dtype,))
+    if m.min() < 0 or m.max() >= k:
+        raise ValueError('mask labels must be 0 .. %d for %d styles, got %d .. %d' % (k - 1, k, m.min(), m.max()))
+    return np.ascontiguousarray(m, np.uint8)

@@ -137,6 +137,47 @@ class Context(object):
                                      float(alpha), float(epsilon), fptr(out)))
         return out
 
+    def transform_masked(self, content, styles, labels, alpha, mode, eps=-1.0, return_sweeps=False):
+        """Spatial control (wct_transform_masked): content [Nc][C], styles K x [Ns_k][C] float32, labels [Nc] in 0 .. K-1 ->
+        [Nc][C], the rows of label k transformed with style k alone.  Sweeps [2K]: label k's content at 2k, style at 2k + 1
+        (0: a label with fewer than 2 rows)."""
+        c = f32(content)
+        ss = [f32(s) for s in styles]
+        lab = _lib.mask_labels(labels, len(ss), (c.shape[0],))
+        if c.ndim != 2 or any(s.ndim != 2 or s.shape[1] != c.shape[1] for s in ss):
+            raise ValueError('expected [N][C] feature matrices with equal C')
+        out = np.empty_like(c)
+        ns = (C.c_int * len(ss))(*[s.shape[0] for s in ss])
+        sweeps = (C.c_int * (2 * len(ss)))()
+        self.last_sweeps = sweeps
+        check(self.lib.wct_transform_masked(self.h, fptr(c), c.shape[0], lab.ctypes.data_as(_lib._U8), _lib.ptr_array(ss), ns,
+                                            len(ss), c.shape[1], float(alpha), int(mode), float(eps), fptr(out), sweeps))
+        return (out, list(sweeps)) if return_sweeps else out
+
+    def adain_masked(self, content, styles, labels, alpha, epsilon=1e-5):
+        """AdaIN with spatial control (wct_adain_masked): the rows of label k take region k's moments and style k's."""
+        c = f32(content)
+        ss = [f32(s) for s in styles]
+        lab = _lib.mask_labels(labels, len(ss), (c.shape[0],))
+        if c.ndim != 2 or any(s.ndim != 2 or s.shape[1] != c.shape[1] for s in ss):
+            raise ValueError('expected [N][C] feature matrices with equal C')
+        out = np.empty_like(c)
+        ns = (C.c_int * len(ss))(*[s.shape[0] for s in ss])
+        check(self.lib.wct_adain_masked(self.h, fptr(c), c.shape[0], lab.ctypes.data_as(_lib._U8), _lib.ptr_array(ss), ns,
+                                        len(ss), c.shape[1], float(alpha), float(epsilon), fptr(out)))
+        return out
+
+    def mask_compact(self, mask, h, w, stride, k):
+        """The device's stable partition of an h x w feature map's rows by label (wct_mask_compact) -> (perm [h*w], seg_off [k+1])"""
+        m = _lib.mask_labels(mask, k)
+        if m.ndim != 2:
+            raise ValueError('expected an [H][W] label map')
+        perm = np.empty(h * w, np.int32)
+        seg = np.empty(k + 1, np.int32)
+        check(self.lib.wct_mask_compact(self.h, m.ctypes.data_as(_lib._U8), m.shape[0], m.shape[1], int(h), int(w), int(stride),
+                                        int(k), perm.ctypes.data_as(_lib._I), seg.ctypes.data_as(_lib._I)))
+        return perm, seg
+
     def style_swap(self, content, style, alpha, patch_size=3, stride=1, eps=-1.0):
         """content [hc][wc][C], style [hs][ws][C] float32 -> [hc][wc][C] (ops.py:145-278)"""
         c = f32(content)
@@ -297,6 +338,33 @@ class Context(object):
         ws = (C.c_int * k)(*[s.shape[1] for s in ss])
         check(self.lib.wct_stylize_mix(self.h, c.ctypes.data_as(_lib._U8), c.shape[0], c.shape[1], ptrs, hs, ws, k, fptr(w),
                                        arr, len(lv), float(alpha), flags, out.ctypes.data_as(_lib._U8)))
+        return out
+
+    def stylize_masked(self, content, styles, mask, relu_targets, alpha=1.0, adain=False, wct_mode='tf', swap5=False):
+        """One predict() with spatial control at every level (wct_stylize_masked): `mask` [H][W] labels 0 .. K-1 of the content
+        pixels, `styles` a list of K HxWx3 images (sizes may differ).  Inputs as in stylize: all uint8 go as they are,
+        otherwise every image is `/ 255.` in float64 and handed over as float32 in [0,1]."""
+        content = np.asarray(content)
+        styles = [np.asarray(s) for s in styles]
+        m = _lib.mask_labels(mask, len(styles), content.shape[:2])
+        as_f32 = content.dtype != np.uint8 or any(s.dtype != np.uint8 for s in styles)
+        if as_f32:
+            c = np.ascontiguousarray(np.asarray(content / 255.), np.float32)
+            ss = [np.ascontiguousarray(np.asarray(s / 255.), np.float32) for s in styles]
+        else:
+            c, ss = u8(content), [u8(s) for s in styles]
+        lv = _levels(relu_targets)
+        arr = (C.c_int * len(lv))(*lv)
+        ho, wo = self.output_size(c.shape[0], c.shape[1], lv)
+        out = np.empty((ho, wo, 3), np.uint8)
+        flags = (_lib.FLAG_ADAIN if adain else 0) | (_lib.FLAG_MODE_NP if wct_mode == 'np' else 0) | \
+            (_lib.FLAG_SWAP5 if swap5 else 0) | (_lib.FLAG_IMAGES_F32 if as_f32 else 0)
+        k = len(ss)
+        ptrs = (_lib._U8 * k)(*[s.ctypes.data_as(_lib._U8) for s in ss])
+        hs = (C.c_int * k)(*[s.shape[0] for s in ss])
+        ws = (C.c_int * k)(*[s.shape[1] for s in ss])
+        check(self.lib.wct_stylize_masked(self.h, c.ctypes.data_as(_lib._U8), c.shape[0], c.shape[1], m.ctypes.data_as(_lib._U8),
+                                          ptrs, hs, ws, k, arr, len(lv), float(alpha), flags, out.ctypes.data_as(_lib._U8)))
         return out
 
     # device-resident batch (what bench.py times)

@@ -10,6 +10,7 @@
 #include <stdlib.h>
 #include <vector>
 #include <cmath>
+#include <algorithm>
 
 // ---------------------------------------------------------------------------
 // errors
@@ -71,6 +72,7 @@ struct wct_ctx {
   DevBuf act[2], feat_c, feat_s[6], img_c, img_s, img_t[2], wct_out, wct_ws, stage[4];
   DevBuf usum_c, usum_s[6], umax;     // feature statistics from the tap epilogues (ConvArgs::usum / umax); umax: [7][32][UMAX_SLOTS] words
   DevBuf mix_in, feat_mix[6];      // a style mix: the K style inputs, and their features per level (K maps back to back)
+  DevBuf mask_in;                  // spatial control: the label map (wct_stylize_masked) or the row labels (wct_*_masked)
 
   int* eig_fail = nullptr;         // pinned host memory mapped into the device: [2] eigenproblems that did not converge / had
                                    // non-finite input -- bumped by jacobi_finalize_kernel (then [6 size classes][3] solver
@@ -193,6 +195,7 @@ extern "C" void wct_destroy(wct_ctx* c) {
   for (auto& b : c->usum_s) if (b.p) hipFree(b.p);
   for (auto& b : c->feat_mix) if (b.p) hipFree(b.p);
   if (c->mix_in.p) hipFree(c->mix_in.p);
+  if (c->mask_in.p) hipFree(c->mask_in.p);
   if (c->usum_c.p) hipFree(c->usum_c.p);
   if (c->umax.p) hipFree(c->umax.p);
   for (auto& r : c->recs) { hipEventDestroy(r.a); hipEventDestroy(r.b); }
@@ -688,6 +691,53 @@ static int run_transform_mix(wct_ctx* c, const float* fc, int Nc, const float* c
                         WCT_STAGE_APPLY, c->stream, c->eig_fail_dev);
 }
 
+// Spatial control: refuses K outside 1 .. WCT_MIX_MAX and any label >= K in the n labels
+static int mask_check(const uint8_t* labels, size_t n, int K) {
+  if (K < 1 || K > WCT_MIX_MAX) { wct_set_error("mask: K = %d styles, must be 1 .. %d", K, (int)WCT_MIX_MAX); return WCT_ERR_ARG; }
+  uint8_t top = 0;
+  for (size_t i = 0; i < n; ++i) top = labels[i] > top ? labels[i] : top;
+  if (top >= K) { wct_set_error("mask: label %d with K = %d styles (labels must be 0 .. K - 1)", (int)top, K); return WCT_ERR_ARG; }
+  return WCT_OK;
+}
+
+// nk[k] = the rows of label k in an h x w feature map (MaskGeom's rule), on the host: it sizes the launches, and nothing is read back
+static void mask_counts(const uint8_t* mask, int Hm, int Wm, int h, int w, int stride, int K, int* nk) {
+  for (int k = 0; k < K; ++k) nk[k] = 0;
+  for (int i = 0; i < h; ++i) {
+    const uint8_t* row = mask + (size_t)std::min(i * stride, Hm - 1) * Wm;
+    for (int j = 0; j < w; ++j) ++nk[row[std::min(j * stride, Wm - 1)]];
+  }
+}
+
+// the masked counterpart of run_transform (device pointers; one content of Nc rows labelled by g, K styles); sweeps_dev [2P] or null
+static int run_transform_masked(wct_ctx* c, const float* fc, int Nc, const MaskGeom& g, const int* nk, const float* const* fs,
+                                const int* Ns, int K, int C, float alpha, unsigned flags, float eps, half_t* out16, float* out32,
+                                int* sweeps_dev) {
+  TRY(ensure(c, c->wct_ws, wct_masked_workspace_bytes(C, Nc, nk, Ns, K)));
+  double ns = 0;
+  for (int k = 0; k < K; ++k) ns += nk[k] >= 2 ? Ns[k] : 0;
+  if (flags & WCT_FLAG_ADAIN) {
+    ProfScope ps(c, 7, 0, (4.0 * Nc + 2.0 * ns) * C * 4 + (double)Nc * C * 6);
+    return launch_adain_masked(fc, Nc, g, nk, fs, Ns, K, C, alpha, 1e-5f, out16, out32, c->wct_ws.p, c->wct_ws.cap, c->stream);
+  }
+  const int mode = (flags & WCT_FLAG_MODE_NP) ? WCT_MODE_NP : WCT_MODE_TF;
+  int P = 0;
+  for (int k = 0; k < K; ++k) P += nk[k] >= 2;
+  {
+    ProfScope ps(c, 4, 2.0 * C * C * (Nc + ns), (4.0 * Nc + 2.0 * (Nc + ns)) * C * 4);     // (+ the compaction and gather)
+    TRY(launch_wct_masked(fc, Nc, g, nk, fs, Ns, K, C, alpha, mode, eps, out16, out32, c->wct_ws.p, c->wct_ws.cap, sweeps_dev,
+                          WCT_STAGE_COV, c->stream, c->eig_fail_dev));
+  }
+  {
+    ProfScope ps(c, 5, 0, 0);
+    TRY(launch_wct_masked(fc, Nc, g, nk, fs, Ns, K, C, alpha, mode, eps, out16, out32, c->wct_ws.p, c->wct_ws.cap, sweeps_dev,
+                          WCT_STAGE_EIG, c->stream, c->eig_fail_dev));
+  }
+  ProfScope ps(c, 6, 2.0 * C * C * Nc + 6.0 * C * C * C * P, (double)Nc * C * (4 + (out16 ? 2 : 0) + (out32 ? 4 : 0)));
+  return launch_wct_masked(fc, Nc, g, nk, fs, Ns, K, C, alpha, mode, eps, out16, out32, c->wct_ws.p, c->wct_ws.cap, sweeps_dev,
+                           WCT_STAGE_APPLY, c->stream, c->eig_fail_dev);
+}
+
 // ---------------------------------------------------------------------------
 // op-level host entry points
 // ---------------------------------------------------------------------------
@@ -789,6 +839,80 @@ extern "C" int wct_adain_mix(wct_ctx* c, const float* content, int Nc, const flo
   TRY(launch_adain_mix((float*)dc, Nc, ds, Ns, K, lambda, C, alpha, epsilon, nullptr, (float*)c->stage[2].p,
                        c->wct_ws.p, c->wct_ws.cap, c->stream));
   return fetch(c, out, c->stage[2].p, (size_t)Nc * C * 4);
+}
+
+// the row labels of a masked transform in c->mask_in, and their counts; g: one row of Nc labels
+static int stage_labels(wct_ctx* c, const uint8_t* labels, int Nc, int K, int* nk, MaskGeom* g) {
+  TRY(mask_check(labels, (size_t)Nc, K));
+  mask_counts(labels, 1, Nc, 1, Nc, 1, K, nk);
+  TRY(ensure(c, c->mask_in, (size_t)Nc));
+  HIP_TRY(hipMemcpyAsync(c->mask_in.p, labels, (size_t)Nc, hipMemcpyHostToDevice, c->stream));
+  *g = MaskGeom{(const uint8_t*)c->mask_in.p, 1, Nc, Nc, 1};
+  return WCT_OK;
+}
+
+extern "C" int wct_transform_masked(wct_ctx* c, const float* content, int Nc, const uint8_t* labels, const float* const* styles,
+                                    const int* Ns, int K, int C, float alpha, int mode, float eps, float* out, int* sweeps_out) {
+  ARG_CHECK(c && content && labels && styles && Ns && out && Nc >= 1 && (mode == WCT_NP || mode == WCT_TF));
+  HIP_TRY(hipSetDevice(c->device));
+  int nk[WCT_MIX_MAX];
+  MaskGeom g;
+  TRY(stage_labels(c, labels, Nc, K, nk, &g));
+  TRY(eig_stale(c));
+  void* dc;
+  const float* ds[WCT_MIX_MAX];
+  TRY(stage_in(c, 0, content, (size_t)Nc * C * 4, &dc));
+  TRY(stage_in_mix(c, styles, Ns, K, C, ds));
+  TRY(ensure(c, c->stage[2], (size_t)Nc * C * 4));
+  TRY(ensure(c, c->stage[3], 2 * WCT_MIX_MAX * sizeof(int)));
+  TRY(run_transform_masked(c, (float*)dc, Nc, g, nk, ds, Ns, K, C, alpha, mode == WCT_NP ? WCT_FLAG_MODE_NP : 0, eps,
+                           nullptr, (float*)c->stage[2].p, (int*)c->stage[3].p));
+  TRY(fetch(c, out, c->stage[2].p, (size_t)Nc * C * 4));
+  if (sweeps_out) {
+    int sw[2 * WCT_MIX_MAX];
+    TRY(fetch(c, sw, c->stage[3].p, 2 * WCT_MIX_MAX * sizeof(int)));
+    for (int k = 0, p = 0; k < K; ++k) {               // pair p = the p-th label with >= 2 rows
+      sweeps_out[2 * k] = nk[k] >= 2 ? sw[2 * p] : 0;
+      sweeps_out[2 * k + 1] = nk[k] >= 2 ? sw[2 * p + 1] : 0;
+      p += nk[k] >= 2;
+    }
+  }
+  return eig_status(c);
+}
+
+extern "C" int wct_adain_masked(wct_ctx* c, const float* content, int Nc, const uint8_t* labels, const float* const* styles,
+                                const int* Ns, int K, int C, float alpha, float epsilon, float* out) {
+  ARG_CHECK(c && content && labels && styles && Ns && out && Nc >= 1);
+  HIP_TRY(hipSetDevice(c->device));
+  int nk[WCT_MIX_MAX];
+  MaskGeom g;
+  TRY(stage_labels(c, labels, Nc, K, nk, &g));
+  void* dc;
+  const float* ds[WCT_MIX_MAX];
+  TRY(stage_in(c, 0, content, (size_t)Nc * C * 4, &dc));
+  TRY(stage_in_mix(c, styles, Ns, K, C, ds));
+  TRY(ensure(c, c->stage[2], (size_t)Nc * C * 4));
+  TRY(ensure(c, c->wct_ws, wct_masked_workspace_bytes(C, Nc, nk, Ns, K)));
+  TRY(launch_adain_masked((float*)dc, Nc, g, nk, ds, Ns, K, C, alpha, epsilon, nullptr, (float*)c->stage[2].p,
+                          c->wct_ws.p, c->wct_ws.cap, c->stream));
+  return fetch(c, out, c->stage[2].p, (size_t)Nc * C * 4);
+}
+
+extern "C" int wct_mask_compact(wct_ctx* c, const uint8_t* mask, int Hm, int Wm, int h, int w, int stride, int K, int* perm_out,
+                                int* seg_off_out) {
+  ARG_CHECK(c && mask && perm_out && seg_off_out && Hm >= 1 && Wm >= 1 && h >= 1 && w >= 1 && stride >= 1);
+  TRY(mask_check(mask, (size_t)Hm * Wm, K));
+  HIP_TRY(hipSetDevice(c->device));
+  const int N = h * w;
+  TRY(ensure(c, c->mask_in, (size_t)Hm * Wm));
+  HIP_TRY(hipMemcpyAsync(c->mask_in.p, mask, (size_t)Hm * Wm, hipMemcpyHostToDevice, c->stream));
+  const size_t perm_bytes = ((size_t)N * sizeof(int) + 255) & ~(size_t)255;
+  TRY(ensure(c, c->stage[2], perm_bytes + 256 + mask_compact_workspace_bytes(N)));
+  int* perm = (int*)c->stage[2].p;
+  int* seg_off = (int*)((char*)c->stage[2].p + perm_bytes);
+  TRY(launch_mask_compact(MaskGeom{(const uint8_t*)c->mask_in.p, Hm, Wm, w, stride}, N, K, perm, seg_off, (char*)seg_off + 256, c->stream));
+  TRY(fetch(c, seg_off_out, seg_off, (K + 1) * sizeof(int)));
+  return fetch(c, perm_out, perm, (size_t)N * sizeof(int));
 }
 
 extern "C" int wct_set_style_swap(wct_ctx* c, float ss_alpha, int patch_size, int stride) {
@@ -1155,19 +1279,14 @@ extern "C" int wct_stylize(wct_ctx* c, const uint8_t* content, int Hc, int Wc, c
   return eig_status(c);
 }
 
-// One predict() with a style mix at every level (Li et al. 2017, sec. 4.2): the style encoder runs once per style (sizes may
-// differ), then the content chain of wct_stylize_batch_dev with B = 1 and the mix in the place of the single-style transform.
-extern "C" int wct_stylize_mix(wct_ctx* c, const uint8_t* content, int Hc, int Wc, const uint8_t* const* styles, const int* Hs,
-                               const int* Ws, int K, const float* weights, const int* levels, int n_levels, float alpha,
-                               unsigned flags, uint8_t* out) {
-  ARG_CHECK(c && content && styles && Hs && Ws && out && levels && n_levels >= 1 && n_levels <= 16);
-  float lambda[WCT_MIX_MAX];
-  TRY(mix_weights(weights, K, lambda));
-  if ((flags & WCT_FLAG_SWAP5) && K > 1) {
-    wct_set_error("style mix: WCT_FLAG_SWAP5 needs K = 1 (style-swap is not linear in the style; got K = %d)", K);
-    return WCT_ERR_ARG;
-  }
-  if (flags & WCT_FLAG_STYLE_SHARED) { wct_set_error("style mix: WCT_FLAG_STYLE_SHARED is for wct_stylize_batch_dev"); return WCT_ERR_ARG; }
+// The body of wct_stylize_mix / wct_stylize_masked (their checks done): the style encoder runs once per style (sizes may differ),
+// then the content chain of wct_stylize_batch_dev with B = 1, `level_transform` in the place of the single-style transform.
+// level_transform(i, l, C, h, w, fs, Ns): level i (relu<l>_1, C channels) of the h x w content in c->feat_c -> c->wct_out (fp16);
+// fs[k] / Ns[k]: style k's features of the level.  WCT_FLAG_SWAP5 (K = 1) runs wct_stylize's style-swap at relu5_1 instead.
+template <typename LevelTransform>
+static int stylize_multi(wct_ctx* c, const uint8_t* content, int Hc, int Wc, const uint8_t* const* styles, const int* Hs,
+                         const int* Ws, int K, const int* levels, int n_levels, unsigned flags, uint8_t* out,
+                         LevelTransform&& level_transform) {
   HIP_TRY(hipSetDevice(c->device));
   int deepest = 0;
   for (int i = 0; i < n_levels; ++i) {
@@ -1179,7 +1298,6 @@ extern "C" int wct_stylize_mix(wct_ctx* c, const uint8_t* content, int Hc, int W
   TRY(wct_output_size(Hc, Wc, levels, n_levels, &Ho, &Wo));
   for (int k = 0; k < K; ++k) { ARG_CHECK(styles[k]); TRY(check_min_size("style", Hs[k], Ws[k], deepest)); }
   TRY(eig_stale(c));
-
   // inputs: the content in stage 0, the K styles back to back in mix_in; to fp32 in [0,1] (wct.py:60-64)
   const bool f32in = (flags & WCT_FLAG_IMAGES_F32) != 0;
   const size_t px = f32in ? sizeof(float) : 1;
@@ -1253,15 +1371,14 @@ extern "C" int wct_stylize_mix(wct_ctx* c, const uint8_t* content, int Hc, int W
       fs[k] = (const float*)c->feat_mix[l].p + foff[l][k];
       Ns[k] = hs[k] * ws[k];
     }
-    if (l == 5 && (flags & WCT_FLAG_SWAP5)) {            // K = 1 (checked above): wct_stylize's style-swap at relu5_1
-      ARG_CHECK(h >= c->ss_patch && w >= c->ss_patch && hs[0] >= c->ss_patch && ws[0] >= c->ss_patch);
+    if (l == 5 && (flags & WCT_FLAG_SWAP5)) {            // K = 1 (the callers refuse more): wct_stylize's style-swap at relu5_1
+      ARG_CHECK(K == 1 && h >= c->ss_patch && w >= c->ss_patch && hs[0] >= c->ss_patch && ws[0] >= c->ss_patch);
       TRY(ensure(c, c->wct_ws, style_swap_workspace_bytes(C, h, w, hs[0], ws[0], c->ss_patch, c->ss_stride)));
       ProfScope ps(c, 7, 0, 0);
       TRY(launch_style_swap((float*)c->feat_c.p, h, w, fs[0], hs[0], ws[0], C, c->ss_alpha, c->ss_patch, c->ss_stride, -1.f,
                             (half_t*)c->wct_out.p, nullptr, c->wct_ws.p, c->wct_ws.cap, c->stream, c->eig_fail_dev));
     } else
-      TRY(run_transform_mix(c, (float*)c->feat_c.p, h * w, fs, Ns, K, lambda, C, alpha, flags, -1.f, (half_t*)c->wct_out.p, nullptr,
-                            nullptr, &st));
+      TRY(level_transform(i, l, C, h, w, fs, Ns, &st));
     const int scale = 1 << (l - 1);
     const int H2 = h * scale, W2 = w * scale;
     DevBuf& dst = c->img_t[i & 1];
@@ -1276,6 +1393,58 @@ extern "C" int wct_stylize_mix(wct_ctx* c, const uint8_t* content, int Hc, int W
   }
   TRY(fetch(c, out, c->stage[2].p, (size_t)Ho * Wo * 3));
   return eig_status(c);
+}
+
+// One predict() with a style mix at every level (Li et al. 2017, sec. 4.2): stylize_multi with the mix in the place of the
+// single-style transform.
+extern "C" int wct_stylize_mix(wct_ctx* c, const uint8_t* content, int Hc, int Wc, const uint8_t* const* styles, const int* Hs,
+                               const int* Ws, int K, const float* weights, const int* levels, int n_levels, float alpha,
+                               unsigned flags, uint8_t* out) {
+  ARG_CHECK(c && content && styles && Hs && Ws && out && levels && n_levels >= 1 && n_levels <= 16);
+  float lambda[WCT_MIX_MAX];
+  TRY(mix_weights(weights, K, lambda));
+  if ((flags & WCT_FLAG_SWAP5) && K > 1) {
+    wct_set_error("style mix: WCT_FLAG_SWAP5 needs K = 1 (style-swap is not linear in the style; got K = %d)", K);
+    return WCT_ERR_ARG;
+  }
+  if (flags & WCT_FLAG_STYLE_SHARED) { wct_set_error("style mix: WCT_FLAG_STYLE_SHARED is for wct_stylize_batch_dev"); return WCT_ERR_ARG; }
+  return stylize_multi(c, content, Hc, Wc, styles, Hs, Ws, K, levels, n_levels, flags, out,
+                       [&](int, int, int C, int h, int w, const float* const* fs, const int* Ns, const WctFeatStats* st) {
+                         return run_transform_mix(c, (float*)c->feat_c.p, h * w, fs, Ns, K, lambda, C, alpha, flags, -1.f,
+                                                  (half_t*)c->wct_out.p, nullptr, nullptr, st);
+                       });
+}
+
+// One predict() with spatial control at every level (Li et al. 2017, sec. 4.2, Fig. 7): stylize_multi with the masked transform
+// in the place of the single-style transform.  The labels of every level are counted here, once, before any launch.
+extern "C" int wct_stylize_masked(wct_ctx* c, const uint8_t* content, int Hc, int Wc, const uint8_t* mask, const uint8_t* const* styles,
+                                  const int* Hs, const int* Ws, int K, const int* levels, int n_levels, float alpha, unsigned flags,
+                                  uint8_t* out) {
+  ARG_CHECK(c && content && mask && styles && Hs && Ws && out && levels && n_levels >= 1 && n_levels <= 16 && Hc >= 2 && Wc >= 2);
+  TRY(mask_check(mask, (size_t)Hc * Wc, K));
+  if ((flags & WCT_FLAG_SWAP5) && K > 1) {
+    wct_set_error("mask: WCT_FLAG_SWAP5 needs K = 1 (style-swap is not a per-region affine map; got K = %d)", K);
+    return WCT_ERR_ARG;
+  }
+  if (flags & WCT_FLAG_STYLE_SHARED) { wct_set_error("mask: WCT_FLAG_STYLE_SHARED is for wct_stylize_batch_dev"); return WCT_ERR_ARG; }
+  std::vector<int> nk((size_t)n_levels * WCT_MIX_MAX);
+  int H = Hc, W = Wc;
+  for (int i = 0; i < n_levels; ++i) {                   // the geometry of the content chain (wct_output_size)
+    ARG_CHECK(levels[i] >= 1 && levels[i] <= 5);
+    int h, w;
+    level_dims(H, W, levels[i], &h, &w);
+    mask_counts(mask, Hc, Wc, h, w, 1 << (levels[i] - 1), K, &nk[(size_t)i * WCT_MIX_MAX]);
+    H = h << (levels[i] - 1); W = w << (levels[i] - 1);
+  }
+  HIP_TRY(hipSetDevice(c->device));
+  TRY(ensure(c, c->mask_in, (size_t)Hc * Wc));
+  HIP_TRY(hipMemcpyAsync(c->mask_in.p, mask, (size_t)Hc * Wc, hipMemcpyHostToDevice, c->stream));
+  return stylize_multi(c, content, Hc, Wc, styles, Hs, Ws, K, levels, n_levels, flags, out,
+                       [&](int i, int l, int C, int h, int w, const float* const* fs, const int* Ns, const WctFeatStats*) {
+                         const MaskGeom g = {(const uint8_t*)c->mask_in.p, Hc, Wc, w, 1 << (l - 1)};
+                         return run_transform_masked(c, (float*)c->feat_c.p, h * w, g, &nk[(size_t)i * WCT_MIX_MAX], fs, Ns, K, C,
+                                                     alpha, flags, -1.f, (half_t*)c->wct_out.p, nullptr, nullptr);
+                       });
 }
 
 // ---------------------------------------------------------------------------

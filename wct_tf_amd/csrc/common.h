@@ -215,6 +215,21 @@ int launch_wct_mix(const float* content, int Nc, const float* const* styles, con
 int launch_adain_mix(const float* content, int Nc, const float* const* styles, const int* Ns, int K, const float* lambda, int C,
                      float alpha, float eps, half_t* out16, float* out32, void* workspace, size_t workspace_bytes, hipStream_t s,
                      const struct WctFeatStats* stats = nullptr);
+// Spatial control (Li et al. 2017, sec. 4.2): K <= WCT_MIX_MAX labelled regions of one content, region k transformed with style k
+// alone.  Row r = (i, j) of an h x w feature map has the label mask[min(i * stride, Hm - 1)][min(j * stride, Wm - 1)] of the
+// Hm x Wm label map (the content's, at stride 2^(level - 1)).  nk[k]: the rows of label k, counted by the caller (they size
+// the launches; nothing is read back), summing to Nc.  A label with nk < 2 rows passes its rows through unchanged.
+// sweeps_dev [2P]: pair p = the p-th label with nk >= 2, content 2p, style 2p + 1.
+struct MaskGeom { const uint8_t* mask; int Hm, Wm, w, stride; };
+size_t mask_compact_workspace_bytes(int N);
+// stable partition of the N rows by label: perm [N] (the rows of label 0 in order, then label 1, ...), seg_off [K + 1]
+int launch_mask_compact(const MaskGeom& g, int N, int K, int* perm, int* seg_off, void* workspace, hipStream_t s);
+size_t wct_masked_workspace_bytes(int C, int Nc, const int* nk, const int* Ns, int K);
+int launch_wct_masked(const float* content, int Nc, const MaskGeom& g, const int* nk, const float* const* styles, const int* Ns, int K,
+                      int C, float alpha, int mode, float eps, half_t* out16, float* out32, void* workspace, size_t workspace_bytes,
+                      int* sweeps_dev, int stages, hipStream_t s, int* eig_fail);
+int launch_adain_masked(const float* content, int Nc, const MaskGeom& g, const int* nk, const float* const* styles, const int* Ns, int K,
+                        int C, float alpha, float eps, half_t* out16, float* out32, void* workspace, size_t workspace_bytes, hipStream_t s);
 // Symmetric eigensolver (batched): A [nmat][C][C] is overwritten (diag -> eigenvalues),
 // V [nmat][C][C] gets eigenvectors in columns.  C multiple of 32, 32 <= C <= 1024.
 // sweeps_done_dev[m]: sweeps used (> 0) if matrix m converged, -sweeps if it was still rotating when the sweep

@@ -2172,9 +2172,13 @@ struct ApplyArgs {
   const unsigned* mabs;             // [P] max |M| (float bits)
   half_t* out16; float* out32;      // [P][N][C], either may be null
 };
+// A masked transform (launch_wct_masked): pair p is the segment of label lab[p] -- rows [seg_off[lab], seg_off[lab + 1]) of the
+// label-compacted content x -- and its row r is stored to row perm[r] of out16 / out32 (the scatter back to pixel order)
+struct ApplySegArgs : ApplyArgs { const int* seg_off; const int* perm; int lab[WCT_MIX_MAX]; };
 
-template <int BC, int BP>
-__global__ __launch_bounds__(256, 2) void apply_f16x2_kernel(ApplyArgs p) {
+template <int BC, int BP, typename Args = ApplyArgs>
+__global__ __launch_bounds__(256, 2) void apply_f16x2_kernel(Args p) {
+  constexpr bool SEG = std::is_same<Args, ApplySegArgs>::value;     // (ApplyArgs: not a line of the plain apply changes)
   constexpr int TM = BC / 64, TN = BP / 64;
   constexpr int MI = BC * 4 / 256, XI = BP * 4 / 256;    // 16-B (8 k) pieces per thread and stage
   __shared__ __attribute__((aligned(16))) unsigned char lm[2][BC * 64];   // M hi, lo
@@ -2184,8 +2188,14 @@ __global__ __launch_bounds__(256, 2) void apply_f16x2_kernel(ApplyArgs p) {
   const int wm = wave >> 1, wn = wave & 1;
   const int pair = blockIdx.z;
   const int n0 = blockIdx.x * BP, c0 = blockIdx.y * BC;
-  const int N = p.N, C = p.C;
-  const float* x = p.x + (size_t)pair * N * C;
+  int seg0 = 0, N = p.N;
+  if constexpr (SEG) {
+    seg0 = p.seg_off[p.lab[pair]];
+    N = p.seg_off[p.lab[pair] + 1] - seg0;
+    if (n0 >= N) return;                         // (uniform per block: past the end of its segment)
+  }
+  const int C = p.C;
+  const float* x = p.x + (SEG ? (size_t)seg0 * C : (size_t)pair * N * C);
   const float* M = p.M + (size_t)pair * C * C;
   const float* mean = p.mean + (size_t)pair * 2 * C;
   const float sx = p.xscale[2 * pair];
@@ -2298,11 +2308,18 @@ __global__ __launch_bounds__(256, 2) void apply_f16x2_kernel(ApplyArgs p) {
       const f32x4 z = {0.f, 0.f, 0.f, 0.f};
       bvs[i][rq] = co < C ? *reinterpret_cast<const f32x4*>(bias + co) : z;
     }
+  int dst[TN];                                   // SEG: the scatter rows, fetched before the first store as well
+  if constexpr (SEG)
+#pragma unroll
+    for (int j = 0; j < TN; ++j) {
+      const int n = n0 + (wn * TN + j) * 32 + (lane & 31);
+      dst[j] = p.perm[seg0 + (n < N ? n : 0)];
+    }
 #pragma unroll
   for (int j = 0; j < TN; ++j) {
     const int n = n0 + (wn * TN + j) * 32 + (lane & 31);
     const bool n_ok = n < N;
-    const size_t row = ((size_t)pair * N + (n_ok ? n : 0)) * C;
+    const size_t row = SEG ? (size_t)dst[j] * C : ((size_t)pair * N + (n_ok ? n : 0)) * C;
 #pragma unroll
     for (int i = 0; i < TM; ++i) {
       const int cb = c0 + (wm * TM + i) * 32;
@@ -2497,18 +2514,21 @@ static int launch_spectral_tail(const WctCarve& w, int C, int P, float alpha, in
   return WCT_OK;
 }
 
-// M = alpha (Tcs . Tw) + (1 - alpha) I for P pairs, then the apply out = (x - mc) M^T + bias
+// M = alpha (Tcs . Tw) + (1 - alpha) I, max |M| -> mabs for P pairs: the blend in the product's epilogue
+static int launch_blend(const WctCarve& w, int C, int P, float alpha, int shared_style, hipStream_t s) {
+  const size_t cc = (size_t)C * C;
+  GemmArgs g = {};
+  g.A = w.Tcs; g.lda = C; g.a_kmajor = 0; g.B = w.Tw; g.ldb = C; g.b_kmajor = 1; g.sA = shared_style ? 0 : 2 * cc; g.sB = 2 * cc;
+  g.M = C; g.N = C; g.K = C; g.ksplit = C; g.out32 = w.M; g.ldo = C; g.s_out = cc;
+  g.blend = 1; g.alpha = alpha; g.mabs = w.mabs;
+  return launch_gemm(g, 1, P, s);
+}
+
+// the blend product for P pairs, then the apply out = (x - mc) M^T + bias
 static int launch_blend_apply(const WctCarve& w, const float* content, int Nc, int C, int P, float alpha, int shared_style,
                               half_t* out16, float* out32, hipStream_t s) {
   int rc;
-  const size_t cc = (size_t)C * C;
-  {
-    GemmArgs g = {};   // M = alpha (Tcs . Tw) + (1 - alpha) I, max |M| -> mabs: the blend in the product's epilogue
-    g.A = w.Tcs; g.lda = C; g.a_kmajor = 0; g.B = w.Tw; g.ldb = C; g.b_kmajor = 1; g.sA = shared_style ? 0 : 2 * cc; g.sB = 2 * cc;
-    g.M = C; g.N = C; g.K = C; g.ksplit = C; g.out32 = w.M; g.ldo = C; g.s_out = cc;
-    g.blend = 1; g.alpha = alpha; g.mabs = w.mabs;
-    if ((rc = launch_gemm(g, 1, P, s))) return rc;
-  }
+  if ((rc = launch_blend(w, C, P, alpha, shared_style, s))) return rc;
   {  // out[n][j] = sum_k (x[n][k]-mc[k]) M[j][k] + bias[j]
     ApplyArgs a;
     a.x = content; a.N = Nc; a.C = C; a.mean = w.mean; a.M = w.M; a.bias = w.bias;
@@ -2802,6 +2822,334 @@ int launch_adain_mix(const float* content, int Nc, const float* const* styles, c
                      (const float*)w.mix, (const float*)(w.mix + C));
   HIP_TRY(hipGetLastError());
   return WCT_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Spatial control (Li et al. 2017, sec. 4.2 and Fig. 7): a label map splits the content into K regions, and region k is
+// transformed with style k alone -- out[rows of k] = T(content[rows of k], style k, alpha) with region k's own mean, covariance
+// (1 / (N_k - 1)) and cut-off.  The rows of a level are partitioned by label, stably (perm lists the rows of label 0 in pixel
+// order, then those of label 1, ...; label k starts at seg_off[k]), and gathered into one [N][C] buffer.  Every label with
+// N_k >= 2 rows is one (content, style) pair of the slot layout: pair p = the p-th such label, slot 2p its gathered rows, slot
+// 2p + 1 its style, each with the slab / K-slice layout launch_wct gives (N_k, Ns_k).  The batched solver's results do not
+// depend on the batch, so region k comes out bit for bit as launch_wct(rows of k, style k).  The apply reads the gathered
+// rows and scatters them back to pixel order (apply_f16x2_kernel<ApplySegArgs>); the rows of a label with a single pixel are
+// copied through unchanged (N_k - 1 = 0: no covariance).
+// ---------------------------------------------------------------------------
+constexpr int MASK_ROWS = 2048;                  // rows per block of the two compaction passes (8 per thread)
+
+__device__ __forceinline__ int mask_label(const MaskGeom& g, int r) {
+  const int i = r / g.w, j = r - i * g.w;
+  return g.mask[(size_t)min(i * g.stride, g.Hm - 1) * g.Wm + min(j * g.stride, g.Wm - 1)];
+}
+
+// pass 1: counts[b][k] = rows of label k in block b's MASK_ROWS rows (wave64 ballots; no atomics, so the order is fixed)
+__global__ __launch_bounds__(256) void mask_count_kernel(MaskGeom g, int N, int K, int* counts) {
+  __shared__ int wc[4][WCT_MIX_MAX];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int cnt[WCT_MIX_MAX];
+#pragma unroll
+  for (int k = 0; k < WCT_MIX_MAX; ++k) cnt[k] = 0;
+  const int base = blockIdx.x * MASK_ROWS;
+  for (int it = 0; it < MASK_ROWS / 256; ++it) {
+    const int r = base + it * 256 + threadIdx.x;
+    const int lab = r < N ? mask_label(g, r) : -1;
+#pragma unroll
+    for (int k = 0; k < WCT_MIX_MAX; ++k)
+      if (k < K) cnt[k] += __popcll(__ballot(lab == k));
+  }
+  if (lane == 0)
+    for (int k = 0; k < K; ++k) wc[wave][k] = cnt[k];
+  __syncthreads();
+  const int k = threadIdx.x;
+  if (k < K) counts[blockIdx.x * WCT_MIX_MAX + k] = wc[0][k] + wc[1][k] + wc[2][k] + wc[3][k];
+}
+
+// pass 2 (one block): blk_off[b][k] = where block b's rows of label k start in perm; seg_off[k] = where label k starts
+__global__ __launch_bounds__(256) void mask_scan_kernel(const int* counts, int nblk, int K, int* blk_off, int* seg_off) {
+  __shared__ int part[256];
+  __shared__ int start;
+  const int t = threadIdx.x;
+  const int per = (nblk + 255) / 256, b0 = min(t * per, nblk), b1 = min(b0 + per, nblk);
+  if (t == 0) start = 0;
+  __syncthreads();
+  for (int k = 0; k < K; ++k) {
+    int sum = 0;
+    for (int b = b0; b < b1; ++b) sum += counts[b * WCT_MIX_MAX + k];
+    part[t] = sum;
+    __syncthreads();
+    for (int d = 1; d < 256; d <<= 1) {          // inclusive scan over the 256 block ranges
+      const int v = t >= d ? part[t - d] : 0;
+      __syncthreads();
+      part[t] += v;
+      __syncthreads();
+    }
+    int run = start + part[t] - sum;
+    for (int b = b0; b < b1; ++b) {
+      blk_off[b * WCT_MIX_MAX + k] = run;
+      run += counts[b * WCT_MIX_MAX + k];
+    }
+    __syncthreads();
+    if (t == 0) { seg_off[k] = start; start += part[255]; }
+    __syncthreads();
+  }
+  if (t == 0) seg_off[K] = start;
+}
+
+// pass 3: perm[blk_off[b][k] + rank] = r, rank = the row's place among block b's rows of its label (row order: iteration,
+// wave, lane -- a stable partition)
+__global__ __launch_bounds__(256) void mask_rank_kernel(MaskGeom g, int N, int K, const int* blk_off, int* perm) {
+  __shared__ int off[WCT_MIX_MAX];
+  __shared__ int wc[4][WCT_MIX_MAX];
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  if (t < K) off[t] = blk_off[blockIdx.x * WCT_MIX_MAX + t];
+  const unsigned long long below = (1ull << lane) - 1ull;
+  const int base = blockIdx.x * MASK_ROWS;
+  for (int it = 0; it < MASK_ROWS / 256; ++it) {
+    const int r = base + it * 256 + t;
+    const int lab = r < N ? mask_label(g, r) : -1;
+    unsigned long long mine = 0;
+#pragma unroll
+    for (int k = 0; k < WCT_MIX_MAX; ++k)
+      if (k < K) {
+        const unsigned long long b = __ballot(lab == k);
+        if (lab == k) mine = b;
+        if (lane == 0) wc[wave][k] = __popcll(b);
+      }
+    __syncthreads();
+    if (lab >= 0 && lab < K) {
+      int pos = off[lab] + __popcll(mine & below);
+      for (int v = 0; v < wave; ++v) pos += wc[v][lab];
+      perm[pos] = r;
+    }
+    __syncthreads();
+    if (t < K) off[t] += wc[0][t] + wc[1][t] + wc[2][t] + wc[3][t];
+    __syncthreads();
+  }
+}
+
+// xg[r] = x[perm[r]] for the rows of the K segments, 16-B accesses
+__global__ __launch_bounds__(256) void mask_gather_kernel(const float* x, const int* perm, const int* seg_off, int K, int C, float* xg) {
+  const int cq = C / 4;
+  const size_t n4 = (size_t)seg_off[K] * cq;
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
+    const int r = (int)(i / cq), c = (int)(i % cq) * 4;
+    *reinterpret_cast<f32x4*>(xg + (size_t)r * C + c) = *reinterpret_cast<const f32x4*>(x + (size_t)perm[r] * C + c);
+  }
+}
+
+// the rows of the labels in `labs` (bit k: label k, a single pixel) pass through unchanged: x[perm[r]] -> out16 / out32 row perm[r]
+__global__ __launch_bounds__(256) void mask_passthrough_kernel(const float* x, const int* seg_off, const int* perm, unsigned labs,
+                                                               int C, half_t* out16, float* out32) {
+  const int k = blockIdx.x;
+  if (!((labs >> k) & 1u)) return;
+  for (int r = seg_off[k]; r < seg_off[k + 1]; ++r) {
+    const size_t row = (size_t)perm[r] * C;
+    for (int c = threadIdx.x; c < C; c += blockDim.x) {
+      const float v = x[row + c];
+      if (out32) out32[row + c] = v;
+      if (out16) out16[row + c] = (half_t)v;
+    }
+  }
+}
+
+static int mask_nblk(int N) { return cdiv(N, MASK_ROWS); }
+
+size_t mask_compact_workspace_bytes(int N) { return 2 * align_up((size_t)mask_nblk(N) * WCT_MIX_MAX * sizeof(int)); }
+
+int launch_mask_compact(const MaskGeom& g, int N, int K, int* perm, int* seg_off, void* workspace, hipStream_t s) {
+  ARG_CHECK(g.mask && g.Hm >= 1 && g.Wm >= 1 && g.w >= 1 && g.stride >= 1 && N >= 1 && K >= 1 && K <= WCT_MIX_MAX && perm && seg_off);
+  const int nblk = mask_nblk(N);
+  int* counts = (int*)workspace;
+  int* blk_off = (int*)((char*)workspace + align_up((size_t)nblk * WCT_MIX_MAX * sizeof(int)));
+  hipLaunchKernelGGL(mask_count_kernel, dim3(nblk), dim3(256), 0, s, g, N, K, counts);
+  hipLaunchKernelGGL(mask_scan_kernel, dim3(1), dim3(256), 0, s, (const int*)counts, nblk, K, blk_off, seg_off);
+  hipLaunchKernelGGL(mask_rank_kernel, dim3(nblk), dim3(256), 0, s, g, N, K, (const int*)blk_off, perm);
+  HIP_TRY(hipGetLastError());
+  return WCT_OK;
+}
+
+// the slot layout of a masked level: pairs = the labels with nk >= 2 rows, in label order
+struct MaskCarve {
+  WctCarve w; MixLayout L;
+  int P, lab[WCT_MIX_MAX], row0[WCT_MIX_MAX], nmax; unsigned single;   // row0: where label k starts (host counts)
+  float* xg; int *perm, *seg_off; void* compact_ws;
+  size_t total;
+};
+
+static MaskCarve carve_masked(void* base, int C, int Nc, const int* nk, const int* Ns, int K) {
+  MaskCarve m;
+  m.P = 0; m.nmax = 0; m.single = 0;
+  MixLayout& L = m.L;
+  L.nslab_max = L.nsplit_max = L.Nsmax = 0;
+  int row = 0;
+  for (int k = 0; k < K; ++k) {
+    m.row0[k] = row;
+    row += nk[k];
+    if (nk[k] == 1) m.single |= 1u << k;
+    if (nk[k] < 2) continue;
+    const int p = m.P++;
+    m.lab[p] = k;
+    m.nmax = std::max(m.nmax, nk[k]);
+    const int Nmax = std::max(nk[k], Ns[k]);
+    for (int side = 0; side < 2; ++side) {       // (as carve() lays out the single pair (nk[k], Ns[k]))
+      L.nslab[2 * p + side] = wct_nslab(Nmax);
+      cov_split(C, Nmax, 1, &L.nsplit[2 * p + side], &L.ksplit[2 * p + side]);
+    }
+    L.nslab_max = std::max(L.nslab_max, L.nslab[2 * p]);
+    L.nsplit_max = std::max(L.nsplit_max, L.nsplit[2 * p]);
+    L.Nsmax = std::max(L.Nsmax, Ns[k]);
+  }
+  m.w = carve(base, C, 2, 2, std::max(m.P, 1), std::max(L.nslab_max, 1), std::max(L.nsplit_max, 1));
+  size_t off = m.w.total;
+  char* b = reinterpret_cast<char*>(base);
+  auto take = [&](size_t bytes) { void* q = b ? b + off : nullptr; off += align_up(bytes); return q; };
+  m.xg = (float*)take((size_t)Nc * C * sizeof(float));
+  m.perm = (int*)take((size_t)Nc * sizeof(int));
+  m.seg_off = (int*)take((WCT_MIX_MAX + 1) * sizeof(int));
+  m.compact_ws = take(mask_compact_workspace_bytes(Nc));
+  m.total = off;
+  return m;
+}
+
+size_t wct_masked_workspace_bytes(int C, int Nc, const int* nk, const int* Ns, int K) {
+  return carve_masked(nullptr, C < 32 ? 32 : C, Nc, nk, Ns, K).total;
+}
+
+static bool masked_args_ok(int Nc, const int* nk, const float* const* styles, const int* Ns, int K, int nmin) {
+  if (!nk || !styles || !Ns || K < 1 || K > WCT_MIX_MAX || Nc < 1) return false;
+  long long sum = 0;
+  for (int k = 0; k < K; ++k) {
+    if (nk[k] < 0 || (nk[k] >= 2 && (!styles[k] || Ns[k] < nmin))) return false;
+    sum += nk[k];
+  }
+  return sum == Nc;                              // every row has a label < K (the caller counted them)
+}
+
+// compaction and gather of a masked level (the first stage of both masked transforms)
+static int launch_mask_gather(const float* content, const MaskGeom& g, int Nc, int K, int C, const MaskCarve& m, hipStream_t s) {
+  int rc;
+  if ((rc = launch_mask_compact(g, Nc, K, m.perm, m.seg_off, m.compact_ws, s))) return rc;
+  const size_t n4 = (size_t)Nc * C / 4;
+  hipLaunchKernelGGL(mask_gather_kernel, dim3((unsigned)std::min<size_t>((n4 + 255) / 256, 2048)), dim3(256), 0, s, content,
+                     (const int*)m.perm, (const int*)m.seg_off, K, C, m.xg);
+  HIP_TRY(hipGetLastError());
+  return WCT_OK;
+}
+
+static int launch_mask_passthrough(const float* content, int C, const MaskCarve& m, int K, half_t* out16, float* out32, hipStream_t s) {
+  if (!m.single) return WCT_OK;
+  hipLaunchKernelGGL(mask_passthrough_kernel, dim3(K), dim3(256), 0, s, content, (const int*)m.seg_off, (const int*)m.perm, m.single,
+                     C, out16, out32);
+  HIP_TRY(hipGetLastError());
+  return WCT_OK;
+}
+
+int launch_wct_masked(const float* content, int Nc, const MaskGeom& g, const int* nk, const float* const* styles, const int* Ns, int K,
+                      int C, float alpha, int mode, float eps_in, half_t* out16, float* out32, void* workspace, size_t workspace_bytes,
+                      int* sweeps_dev, int stages, hipStream_t s, int* eig_fail) {
+  ARG_CHECK(C % 32 == 0 && C >= 32 && C <= 1024 && content && masked_args_ok(Nc, nk, styles, Ns, K, 2));
+  ARG_CHECK(mode == WCT_MODE_NP || mode == WCT_MODE_TF);
+  ARG_CHECK((size_t)Nc * C * 4 < ((size_t)1 << 31));
+  for (int k = 0; k < K; ++k) ARG_CHECK(nk[k] < 2 || (size_t)Ns[k] * C * 4 < ((size_t)1 << 31));
+  MaskCarve m = carve_masked(workspace, C, Nc, nk, Ns, K);
+  ARG_CHECK(workspace_bytes >= m.total);
+  const WctCarve& w = m.w;
+  const MixLayout& L = m.L;
+  int rc;
+  if (stages & WCT_STAGE_COV) {
+    const float eps_user = eps_in >= 0.f ? eps_in : (mode == WCT_MODE_TF ? 1e-8f : 1e-5f);   // (as launch_wct)
+    const float eps = mode == WCT_MODE_TF ? eps_user : 0.f;
+    if ((rc = launch_mask_gather(content, g, Nc, K, C, m, s))) return rc;
+    for (int p = 0; p < m.P; ++p) {
+      const int k = m.lab[p], mc = 2 * p, ms = 2 * p + 1;
+      const float* xk = m.xg + (size_t)m.row0[k] * C;
+      if ((rc = launch_slot_means(xk, nk[k], C, mc, L.nslab[mc], w, false, s))) return rc;
+      if ((rc = launch_slot_cov(xk, nk[k], C, mc, L.nsplit[mc], L.ksplit[mc], eps, w, s))) return rc;
+      if ((rc = launch_slot_means(styles[k], Ns[k], C, ms, L.nslab[ms], w, false, s))) return rc;
+      if ((rc = launch_slot_cov(styles[k], Ns[k], C, ms, L.nsplit[ms], L.ksplit[ms], eps, w, s))) return rc;
+    }
+  }
+  if ((stages & WCT_STAGE_EIG) && m.P > 0) {
+    JacobiGroup G;
+    if ((rc = jacobi_make_group(&G, w.A, w.V, C, 2 * m.P, w.jacobi_ws, w.jacobi_bytes, sweeps_dev, eig_fail, s))) return rc;
+    G.shared_style = 0; G.tol_fn = JACOBI_TOL_FN_WCT; G.u_f16 = 1;
+    if ((rc = jacobi_dispatch(G, C))) return rc;
+  }
+  if (!(stages & WCT_STAGE_APPLY)) return WCT_OK;
+  if (m.P > 0) {
+    if ((rc = launch_spectral_tail(w, C, m.P, alpha, mode, eps_in, 0, m.P, s))) return rc;
+    if ((rc = launch_blend(w, C, m.P, alpha, 0, s))) return rc;
+    ApplySegArgs a;
+    a.x = m.xg; a.N = 0; a.C = C; a.mean = w.mean; a.M = w.M; a.bias = w.bias;
+    a.xscale = w.scale; a.mabs = w.mabs; a.out16 = out16; a.out32 = out32;
+    a.seg_off = m.seg_off; a.perm = m.perm;
+    for (int p = 0; p < WCT_MIX_MAX; ++p) a.lab[p] = p < m.P ? m.lab[p] : 0;
+    if (C >= 128) hipLaunchKernelGGL((apply_f16x2_kernel<128, 128, ApplySegArgs>), dim3(cdiv(m.nmax, 128), cdiv(C, 128), m.P), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((apply_f16x2_kernel<64, 128, ApplySegArgs>), dim3(cdiv(m.nmax, 128), cdiv(C, 64), m.P), dim3(256), 0, s, a);
+    HIP_TRY(hipGetLastError());
+  }
+  return launch_mask_passthrough(content, C, m, K, out16, out32, s);
+}
+
+// AdaIN of the segments: as adain_apply_kernel (same expression, so the same bits) on pair p = label lab[p], rows read from the
+// gathered buffer and stored to their pixel rows
+struct SegLabels { int lab[WCT_MIX_MAX]; };
+__global__ void adain_seg_apply_kernel(const float* xg, const int* seg_off, const int* perm, SegLabels sl, int C, const float* mean,
+                                       const float* var, float alpha, float eps, half_t* out16, float* out32) {
+  const int pair = blockIdx.y, lab = sl.lab[pair];
+  const int cq = C / 4;
+  const int r0 = seg_off[lab];
+  const size_t n4 = (size_t)(seg_off[lab + 1] - r0) * cq;
+  const float* mp = mean + (size_t)pair * 2 * C;
+  const float* vp = var + (size_t)pair * 2 * C;
+  const float* ms = mp + C;
+  const float* vs = vp + C;
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
+    const int r = (int)(i / cq), c = (int)(i % cq) * 4;
+    const f32x4 v = *reinterpret_cast<const f32x4*>(xg + (size_t)(r0 + r) * C + c);
+    f32x4 o;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float inv = 1.f / sqrtf(vp[c + j] + eps);
+      const float sd = sqrtf(vs[c + j]);
+      const float y = (v[j] - mp[c + j]) * inv * sd + ms[c + j];
+      o[j] = alpha * y + (1.f - alpha) * v[j];
+    }
+    const size_t dst = (size_t)perm[r0 + r] * C + c;
+    if (out32) *reinterpret_cast<f32x4*>(out32 + dst) = o;
+    if (out16) {
+      half4 h;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) h[j] = (half_t)o[j];
+      *reinterpret_cast<half4*>(out16 + dst) = h;
+    }
+  }
+}
+
+int launch_adain_masked(const float* content, int Nc, const MaskGeom& g, const int* nk, const float* const* styles, const int* Ns, int K,
+                        int C, float alpha, float eps, half_t* out16, float* out32, void* workspace, size_t workspace_bytes, hipStream_t s) {
+  ARG_CHECK(C % 4 == 0 && C <= 1024 && content && masked_args_ok(Nc, nk, styles, Ns, K, 1));
+  MaskCarve m = carve_masked(workspace, C < 32 ? 32 : C, Nc, nk, Ns, K);
+  ARG_CHECK(workspace_bytes >= m.total);
+  const WctCarve& w = m.w;
+  int rc;
+  if ((rc = launch_mask_gather(content, g, Nc, K, C, m, s))) return rc;
+  SegLabels sl = {};
+  for (int p = 0; p < m.P; ++p) {
+    const int k = m.lab[p];
+    sl.lab[p] = k;
+    if ((rc = launch_slot_means(m.xg + (size_t)m.row0[k] * C, nk[k], C, 2 * p, m.L.nslab[2 * p], w, true, s))) return rc;
+    if ((rc = launch_slot_means(styles[k], Ns[k], C, 2 * p + 1, m.L.nslab[2 * p + 1], w, true, s))) return rc;
+  }
+  if (m.P > 0) {
+    const size_t n4 = (size_t)m.nmax * C / 4;
+    size_t blocks = (n4 + 255) / 256;
+    if (blocks > 2048) blocks = 2048;
+    hipLaunchKernelGGL(adain_seg_apply_kernel, dim3((unsigned)blocks, m.P), dim3(256), 0, s, (const float*)m.xg, (const int*)m.seg_off,
+                       (const int*)m.perm, sl, C, (const float*)w.mean, (const float*)w.var, alpha, eps, out16, out32);
+    HIP_TRY(hipGetLastError());
+  }
+  return launch_mask_passthrough(content, C, m, K, out16, out32, s);
 }
 
 // ---------------------------------------------------------------------------

@@ -3,7 +3,9 @@ MI355X path.  Flag names, defaults and the output naming `{content}_{style}{ext}
 takes TF checkpoint directories or .npz files (see wct.py), `--vgg-path` the .t7 or a .npz, and
 `--synthetic-weights SEED` stands in when neither exists.  Under torchrun each rank takes a shard of the content
 files (rank_shard); `--gpus N` without a launcher starts the N ranks itself.  `--interp-styles a b [--interp-weights wa wb]`
-stylizes with a weighted mix of the styles (Li et al. 2017, sec. 4.2; the reference's README TODO)."""
+stylizes with a weighted mix of the styles (Li et al. 2017, sec. 4.2; the reference's README TODO).
+`--mask-path M --mask-styles s0 s1 ...` stylizes each region of a grey label map with its own style (the same section,
+spatial control): grey value v is label v * K // 256 of K styles."""
 import argparse
 import os
 import time
@@ -42,6 +44,13 @@ _FLAGS = [
                                      'content, named {content}_{style1}+{style2}+...; not with --style-path / -r')),
     (('--interp-weights',), dict(nargs='+', type=float, default=None, metavar='W',
                                  help='one weight >= 0 per --interp-styles image, normalised to sum 1 (default: equal)')),
+    (('--mask-path',), dict(default=None, metavar='PATH',
+                            help='spatial control (Li et al. 2017, sec. 4.2): an 8-bit grey label map, resized (nearest) to each '
+                                 'content; grey v picks --mask-styles image v * K // 256.  One output per content, named '
+                                 '{content}_mask_{style0}+{style1}+...')),
+    (('--mask-styles',), dict(nargs='+', default=None, metavar='PATH',
+                              help='the K style images of --mask-path, label 0 first; not with --style-path / -r / '
+                                   '--interp-styles / --concat')),
     (('--gpus',), dict(type=int, default=0, metavar='N',
                        help='shard the content files over N GPUs of this node, one process per GPU: started here when no '
                             'launcher did (0: whatever the launcher set, else one GPU)')),
@@ -145,10 +154,65 @@ def stylize_mix_pair(model, content, styles, args):
     return out
 
 
+def check_mask_args(parser, args):
+    """--mask-path / --mask-styles: the argument errors of spatial control (parser.error exits)."""
+    if args.mask_path is None and args.mask_styles is None:
+        return
+    if args.mask_path is None or args.mask_styles is None:
+        parser.error('--mask-path and --mask-styles go together')
+    if args.style_path is not None or args.random > 0:
+        parser.error('--mask-styles replaces --style-path and -r/--random: give one or the other')
+    if args.interp_styles is not None:
+        parser.error('--mask-path does not combine with --interp-styles')
+    if args.concat:
+        parser.error('--concat takes one style: not with --mask-path')
+    if args.swap5 and len(args.mask_styles) > 1:
+        parser.error('--swap5 takes one style: style-swap is not a per-region affine map')
+    if len(args.mask_styles) > 8:
+        parser.error('--mask-styles takes at most 8 styles')
+
+
+def mask_name(content_path, style_paths):
+    """output file of a masked stylization: {content}_mask_{style0}+{style1}+...{ext of the content}"""
+    return '%s_mask_%s%s' % (_stem(content_path), '+'.join(_stem(p) for p in style_paths), os.path.splitext(content_path)[1])
+
+
+def load_mask(path):
+    """the label map file as 8-bit grey [H][W]"""
+    from PIL import Image
+    with Image.open(path) as im:
+        return np.array(im.convert('L'))
+
+
+def mask_labels(grey, k, shape_hw):
+    """labels [h][w] of a grey map for k styles: resized (nearest) to shape_hw, then grey v -> v * k // 256 (black: style 0,
+    white: style k - 1; k equal bands of grey)"""
+    from PIL import Image
+    h, w = (int(v) for v in shape_hw[:2])
+    g = np.asarray(grey, np.uint8)
+    if g.shape != (h, w):
+        g = np.array(Image.fromarray(g).resize((w, h), Image.NEAREST))
+    return np.uint8(g.astype(np.int32) * k // 256)
+
+
+def stylize_mask_pair(model, content, grey, styles, args):
+    """one output of spatial control: stylize_pair with a style per region -- CORAL per style (--keep-colors), and `--passes`
+    masked predictions, the mask resized to each pass's input (a pass's output can be larger than its input)"""
+    if args.keep_colors:
+        from .ops import preserve_colors_np
+        styles = [preserve_colors_np(s, content, ctx=model.sess) for s in styles]
+    out = content
+    for _ in range(max(1, args.passes)):
+        out = model.predict_masked(out, styles, mask_labels(grey, len(styles), out.shape[:2]), args.alpha, args.adain,
+                                   args.swap5, args.ss_alpha)
+    return out
+
+
 def main(argv=None):
     parser = build_parser()
     args = parser.parse_args(argv)
     check_interp_args(parser, args)
+    check_mask_args(parser, args)
     if args.synthetic_weights is None and not args.checkpoints:
         parser.error('--checkpoints is required (stylize.py:17) unless --synthetic-weights SEED is given')
     if args.gpus > 0:
@@ -180,6 +244,19 @@ def main(argv=None):
                 content = utils.resize_to(content, args.content_size)
             target = os.path.join(args.out_path, interp_name(cpath, args.interp_styles))
             utils.save_img(target, stylize_mix_pair(model, content, mix, args))
+            written += 1
+            print('%d: wrote %s' % (written, target))
+        print('%d outputs in %.1f s' % (written, time.time() - t0))
+        return written
+    if args.mask_path is not None:
+        grey = load_mask(args.mask_path)
+        regions = [load_style(p, args) for p in args.mask_styles]
+        for cpath in contents:
+            content = utils.get_img(cpath)
+            if args.content_size > 0:
+                content = utils.resize_to(content, args.content_size)
+            target = os.path.join(args.out_path, mask_name(cpath, args.mask_styles))
+            utils.save_img(target, stylize_mask_pair(model, content, grey, regions, args))
             written += 1
             print('%d: wrote %s' % (written, target))
         print('%d outputs in %.1f s' % (written, time.time() - t0))

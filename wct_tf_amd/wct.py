@@ -3,6 +3,7 @@
     WCT(checkpoints, relu_targets, vgg_path, device='/gpu:0', ss_patch_size=3, ss_stride=1)
     WCT.predict(content, style, alpha=1, swap5=False, ss_alpha=1, adain=False) -> uint8 HxWx3
     WCT.predict_mix(content, styles, weights=None, alpha=1, adain=False, swap5=False, ss_alpha=1) -> uint8 HxWx3
+    WCT.predict_masked(content, styles, mask, alpha=1, adain=False, swap5=False, ss_alpha=1) -> uint8 HxWx3
 
 `checkpoints` / `vgg_path`: the reference restores TF checkpoints and a .t7 file
 (wct.py:46-58, vgg_normalised.py:16).  Per decoder this class takes either of
@@ -125,6 +126,29 @@ class WCT(object):
             self.sess.set_style_swap(ss_alpha, self.ss_patch_size, self.ss_stride)
         return self.sess.stylize_mix(content, styles, weights, self.relu_targets, alpha=alpha, adain=adain,
                                      wct_mode=self.wct_mode, swap5=bool(swap5))
+
+    def predict_masked(self, content, styles, mask, alpha=1, adain=False, swap5=False, ss_alpha=1):
+        '''Stylize each region of a label map with its own style (Li et al. 2017, sec. 4.2, Fig. 7; the reference's README TODO
+           "Spatial control/masking"): `mask` [H][W] holds a label 0 .. K-1 per content pixel, `styles` K images (sizes may
+           differ), and at every level the pixels of label k are transformed with style k alone, with their own statistics
+           (a label with fewer than 2 pixels at a level keeps that level's features).  Arrays in [0,255], returns uint8 HxWx3.
+           One style with an all-zero mask gives predict(content, style) bit for bit.  swap5 takes one style only.'''
+        from ._lib import mask_labels
+        styles = [np.asarray(s) for s in styles]
+        content = np.asarray(content)
+        mask = mask_labels(mask, len(styles), content.shape[:2])        # ValueError before any GPU call
+        if swap5 and len(styles) > 1:
+            raise ValueError('swap5 takes one style: style-swap is not a per-region affine map')
+        if swap5 is True and self.ss_stride != 1:
+            from .utils import swap_filter_fit, center_crop_to, _centre_window
+            should_refit, H, W = swap_filter_fit(content.shape[0], content.shape[1], self.ss_patch_size, self.ss_stride)
+            if should_refit:                                       # (a crop, never a resize: H, W fit inside the content)
+                content = center_crop_to(content, H, W)
+                mask = np.ascontiguousarray(_centre_window(mask, H, W))
+        if swap5:
+            self.sess.set_style_swap(ss_alpha, self.ss_patch_size, self.ss_stride)
+        return self.sess.stylize_masked(content, styles, mask, self.relu_targets, alpha=alpha, adain=adain,
+                                        wct_mode=self.wct_mode, swap5=bool(swap5))
 
     def predict_frames(self, frames, style, alpha=1, swap5=False, ss_alpha=1, adain=False, batch=16):
         '''Stylize same-sized frames [F][H][W][3] with ONE style image (the loop of stylize_video.py:112-121,
