@@ -25,6 +25,24 @@ def _levels(relu_targets):
     return out
 
 
+def _feature_args(content, styles, validate):
+    """A content [Nc][C] and K styles [Ns_k][C] as float32, the caller's own validate(content, K) (its result is returned), the
+    shape check, and the style row counts as a C int array."""
+    c = f32(content)
+    ss = [f32(s) for s in styles]
+    v = validate(c, len(ss))
+    if c.ndim != 2 or any(s.ndim != 2 or s.shape[1] != c.shape[1] for s in ss):
+        raise ValueError('expected [N][C] feature matrices with equal C')
+    return c, ss, v, (C.c_int * len(ss))(*[s.shape[0] for s in ss])
+
+
+def _image_arrays(images):
+    """Pointers, heights and widths of K images as C arrays."""
+    k = len(images)
+    return ((_lib._U8 * k)(*[s.ctypes.data_as(_lib._U8) for s in images]), (C.c_int * k)(*[s.shape[0] for s in images]),
+            (C.c_int * k)(*[s.shape[1] for s in images]))
+
+
 class Context(object):
     def __init__(self, device=0):
         self.lib = _lib.load()
@@ -111,13 +129,8 @@ class Context(object):
     def transform_mix(self, content, styles, weights, alpha, mode, eps=-1.0, return_sweeps=False):
         """Style mix (wct_transform_mix): content [Nc][C], styles K x [Ns_k][C] float32, weights [K] (None: equal) ->
         sum_k lambda_k transform(content, styles[k]) [Nc][C], lambda = weights / sum(weights).  Sweeps: content, then style k."""
-        c = f32(content)
-        ss = [f32(s) for s in styles]
-        w = _lib.mix_weights(weights, len(ss))
-        if c.ndim != 2 or any(s.ndim != 2 or s.shape[1] != c.shape[1] for s in ss):
-            raise ValueError('expected [N][C] feature matrices with equal C')
+        c, ss, w, ns = _feature_args(content, styles, lambda c, k: _lib.mix_weights(weights, k))
         out = np.empty_like(c)
-        ns = (C.c_int * len(ss))(*[s.shape[0] for s in ss])
         sweeps = (C.c_int * (1 + len(ss)))()
         self.last_sweeps = sweeps
         check(self.lib.wct_transform_mix(self.h, fptr(c), c.shape[0], _lib.ptr_array(ss), ns, len(ss), fptr(w), c.shape[1],
@@ -126,13 +139,8 @@ class Context(object):
 
     def adain_mix(self, content, styles, weights, alpha, epsilon=1e-5):
         """AdaIN with a style mix (wct_adain_mix): the style's deviation and mean are the lambda-weighted ones."""
-        c = f32(content)
-        ss = [f32(s) for s in styles]
-        w = _lib.mix_weights(weights, len(ss))
-        if c.ndim != 2 or any(s.ndim != 2 or s.shape[1] != c.shape[1] for s in ss):
-            raise ValueError('expected [N][C] feature matrices with equal C')
+        c, ss, w, ns = _feature_args(content, styles, lambda c, k: _lib.mix_weights(weights, k))
         out = np.empty_like(c)
-        ns = (C.c_int * len(ss))(*[s.shape[0] for s in ss])
         check(self.lib.wct_adain_mix(self.h, fptr(c), c.shape[0], _lib.ptr_array(ss), ns, len(ss), fptr(w), c.shape[1],
                                      float(alpha), float(epsilon), fptr(out)))
         return out
@@ -141,13 +149,8 @@ class Context(object):
         """Spatial control (wct_transform_masked): content [Nc][C], styles K x [Ns_k][C] float32, labels [Nc] in 0 .. K-1 ->
         [Nc][C], the rows of label k transformed with style k alone.  Sweeps [2K]: label k's content at 2k, style at 2k + 1
         (0: a label with fewer than 2 rows)."""
-        c = f32(content)
-        ss = [f32(s) for s in styles]
-        lab = _lib.mask_labels(labels, len(ss), (c.shape[0],))
-        if c.ndim != 2 or any(s.ndim != 2 or s.shape[1] != c.shape[1] for s in ss):
-            raise ValueError('expected [N][C] feature matrices with equal C')
+        c, ss, lab, ns = _feature_args(content, styles, lambda c, k: _lib.mask_labels(labels, k, (c.shape[0],)))
         out = np.empty_like(c)
-        ns = (C.c_int * len(ss))(*[s.shape[0] for s in ss])
         sweeps = (C.c_int * (2 * len(ss)))()
         self.last_sweeps = sweeps
         check(self.lib.wct_transform_masked(self.h, fptr(c), c.shape[0], lab.ctypes.data_as(_lib._U8), _lib.ptr_array(ss), ns,
@@ -156,13 +159,8 @@ class Context(object):
 
     def adain_masked(self, content, styles, labels, alpha, epsilon=1e-5):
         """AdaIN with spatial control (wct_adain_masked): the rows of label k take region k's moments and style k's."""
-        c = f32(content)
-        ss = [f32(s) for s in styles]
-        lab = _lib.mask_labels(labels, len(ss), (c.shape[0],))
-        if c.ndim != 2 or any(s.ndim != 2 or s.shape[1] != c.shape[1] for s in ss):
-            raise ValueError('expected [N][C] feature matrices with equal C')
+        c, ss, lab, ns = _feature_args(content, styles, lambda c, k: _lib.mask_labels(labels, k, (c.shape[0],)))
         out = np.empty_like(c)
-        ns = (C.c_int * len(ss))(*[s.shape[0] for s in ss])
         check(self.lib.wct_adain_masked(self.h, fptr(c), c.shape[0], lab.ctypes.data_as(_lib._U8), _lib.ptr_array(ss), ns,
                                         len(ss), c.shape[1], float(alpha), float(epsilon), fptr(out)))
         return out
@@ -295,31 +293,19 @@ class Context(object):
         runs on the device); anything else is preprocessed exactly as the reference does -- `image / 255.` in float64
         (wct.py:60-64), cast to the float32 the graph's placeholders hold (model.py:43-44) -- and handed over as float32
         images in [0,1] (WCT_FLAG_IMAGES_F32): a float image is NOT rounded to integer levels."""
-        content, style = np.asarray(content), np.asarray(style)
-        as_f32 = content.dtype != np.uint8 or style.dtype != np.uint8
-        if as_f32:
-            c = np.ascontiguousarray(np.asarray(content / 255.), np.float32)
-            s = np.ascontiguousarray(np.asarray(style / 255.), np.float32)
-        else:
-            c, s = u8(content), u8(style)
-        lv = _levels(relu_targets)
-        arr = (C.c_int * len(lv))(*lv)
-        ho, wo = self.output_size(c.shape[0], c.shape[1], lv)
-        out = np.empty((ho, wo, 3), np.uint8)
-        flags = (_lib.FLAG_ADAIN if adain else 0) | (_lib.FLAG_MODE_NP if wct_mode == 'np' else 0) | \
-            (_lib.FLAG_SWAP5 if swap5 else 0) | (_lib.FLAG_IMAGES_F32 if as_f32 else 0)
+        c, (s,), _, arr, out, flags = self._stylize_args(content, [style], None, relu_targets, adain, wct_mode, swap5)
         check(self.lib.wct_stylize(self.h, c.ctypes.data_as(_lib._U8), c.shape[0], c.shape[1],
-                                   s.ctypes.data_as(_lib._U8), s.shape[0], s.shape[1], arr, len(lv),
+                                   s.ctypes.data_as(_lib._U8), s.shape[0], s.shape[1], arr, len(arr),
                                    float(alpha), flags, out.ctypes.data_as(_lib._U8)))
         return out
 
-    def stylize_mix(self, content, styles, weights, relu_targets, alpha=1.0, adain=False, wct_mode='tf', swap5=False):
-        """One predict() with a style mix at every level (wct_stylize_mix): `styles` is a list of K HxWx3 images (sizes may
-        differ), `weights` [K] (None: equal).  Inputs as in stylize: all uint8 go as they are, otherwise every image is
-        `/ 255.` in float64 and handed over as float32 in [0,1]."""
+    def _stylize_args(self, content, styles, validate, relu_targets, adain, wct_mode, swap5):
+        """The common arguments of the stylize calls: the caller's own validate(content, K) first (None: none; its result is
+        returned), then the images -- all uint8 go as they are, otherwise every image is `/ 255.` in float64 and handed over as
+        float32 in [0,1] -- the levels as a C int array, the output image and the flag word."""
         content = np.asarray(content)
         styles = [np.asarray(s) for s in styles]
-        w = _lib.mix_weights(weights, len(styles))
+        v = validate(content, len(styles)) if validate else None
         as_f32 = content.dtype != np.uint8 or any(s.dtype != np.uint8 for s in styles)
         if as_f32:
             c = np.ascontiguousarray(np.asarray(content / 255.), np.float32)
@@ -327,44 +313,31 @@ class Context(object):
         else:
             c, ss = u8(content), [u8(s) for s in styles]
         lv = _levels(relu_targets)
-        arr = (C.c_int * len(lv))(*lv)
         ho, wo = self.output_size(c.shape[0], c.shape[1], lv)
-        out = np.empty((ho, wo, 3), np.uint8)
         flags = (_lib.FLAG_ADAIN if adain else 0) | (_lib.FLAG_MODE_NP if wct_mode == 'np' else 0) | \
             (_lib.FLAG_SWAP5 if swap5 else 0) | (_lib.FLAG_IMAGES_F32 if as_f32 else 0)
-        k = len(ss)
-        ptrs = (_lib._U8 * k)(*[s.ctypes.data_as(_lib._U8) for s in ss])
-        hs = (C.c_int * k)(*[s.shape[0] for s in ss])
-        ws = (C.c_int * k)(*[s.shape[1] for s in ss])
-        check(self.lib.wct_stylize_mix(self.h, c.ctypes.data_as(_lib._U8), c.shape[0], c.shape[1], ptrs, hs, ws, k, fptr(w),
-                                       arr, len(lv), float(alpha), flags, out.ctypes.data_as(_lib._U8)))
+        return c, ss, v, (C.c_int * len(lv))(*lv), np.empty((ho, wo, 3), np.uint8), flags
+
+    def stylize_mix(self, content, styles, weights, relu_targets, alpha=1.0, adain=False, wct_mode='tf', swap5=False):
+        """One predict() with a style mix at every level (wct_stylize_mix): `styles` is a list of K HxWx3 images (sizes may
+        differ), `weights` [K] (None: equal).  Inputs as in stylize: all uint8 go as they are, otherwise every image is
+        `/ 255.` in float64 and handed over as float32 in [0,1]."""
+        c, ss, w, arr, out, flags = self._stylize_args(content, styles, lambda c, k: _lib.mix_weights(weights, k), relu_targets,
+                                                       adain, wct_mode, swap5)
+        ptrs, hs, ws = _image_arrays(ss)
+        check(self.lib.wct_stylize_mix(self.h, c.ctypes.data_as(_lib._U8), c.shape[0], c.shape[1], ptrs, hs, ws, len(ss), fptr(w),
+                                       arr, len(arr), float(alpha), flags, out.ctypes.data_as(_lib._U8)))
         return out
 
     def stylize_masked(self, content, styles, mask, relu_targets, alpha=1.0, adain=False, wct_mode='tf', swap5=False):
         """One predict() with spatial control at every level (wct_stylize_masked): `mask` [H][W] labels 0 .. K-1 of the content
         pixels, `styles` a list of K HxWx3 images (sizes may differ).  Inputs as in stylize: all uint8 go as they are,
         otherwise every image is `/ 255.` in float64 and handed over as float32 in [0,1]."""
-        content = np.asarray(content)
-        styles = [np.asarray(s) for s in styles]
-        m = _lib.mask_labels(mask, len(styles), content.shape[:2])
-        as_f32 = content.dtype != np.uint8 or any(s.dtype != np.uint8 for s in styles)
-        if as_f32:
-            c = np.ascontiguousarray(np.asarray(content / 255.), np.float32)
-            ss = [np.ascontiguousarray(np.asarray(s / 255.), np.float32) for s in styles]
-        else:
-            c, ss = u8(content), [u8(s) for s in styles]
-        lv = _levels(relu_targets)
-        arr = (C.c_int * len(lv))(*lv)
-        ho, wo = self.output_size(c.shape[0], c.shape[1], lv)
-        out = np.empty((ho, wo, 3), np.uint8)
-        flags = (_lib.FLAG_ADAIN if adain else 0) | (_lib.FLAG_MODE_NP if wct_mode == 'np' else 0) | \
-            (_lib.FLAG_SWAP5 if swap5 else 0) | (_lib.FLAG_IMAGES_F32 if as_f32 else 0)
-        k = len(ss)
-        ptrs = (_lib._U8 * k)(*[s.ctypes.data_as(_lib._U8) for s in ss])
-        hs = (C.c_int * k)(*[s.shape[0] for s in ss])
-        ws = (C.c_int * k)(*[s.shape[1] for s in ss])
+        c, ss, m, arr, out, flags = self._stylize_args(content, styles, lambda c, k: _lib.mask_labels(mask, k, c.shape[:2]),
+                                                       relu_targets, adain, wct_mode, swap5)
+        ptrs, hs, ws = _image_arrays(ss)
         check(self.lib.wct_stylize_masked(self.h, c.ctypes.data_as(_lib._U8), c.shape[0], c.shape[1], m.ctypes.data_as(_lib._U8),
-                                          ptrs, hs, ws, k, arr, len(lv), float(alpha), flags, out.ctypes.data_as(_lib._U8)))
+                                          ptrs, hs, ws, len(ss), arr, len(arr), float(alpha), flags, out.ctypes.data_as(_lib._U8)))
         return out
 
     # device-resident batch (what bench.py times)

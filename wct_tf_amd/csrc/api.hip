@@ -621,27 +621,43 @@ static int run_decoder(wct_ctx* c, int level, const half_t* feat16, int B, int h
   return WCT_OK;
 }
 
+// what the stages of a transform are charged in their profile classes: covariance (4), apply (6), or the one AdaIN launch (7)
+struct StageCost { double cov_flops, cov_bytes, apply_flops, apply_bytes, adain_bytes; };
+
+// One transform by a variant's launcher, launch(mode, stages): AdaIN (stages = 0) in one launch, or the covariance, eigensolve
+// and apply stages, each timed in its class
+template <typename Launch>
+static int run_stages(wct_ctx* c, size_t ws_bytes, unsigned flags, const StageCost& cost, Launch&& launch) {
+  TRY(ensure(c, c->wct_ws, ws_bytes));
+  if (flags & WCT_FLAG_ADAIN) {
+    ProfScope ps(c, 7, 0, cost.adain_bytes);
+    return launch(0, 0);
+  }
+  const int mode = (flags & WCT_FLAG_MODE_NP) ? WCT_MODE_NP : WCT_MODE_TF;
+  {
+    ProfScope ps(c, 4, cost.cov_flops, cost.cov_bytes);
+    TRY(launch(mode, WCT_STAGE_COV));
+  }
+  {
+    ProfScope ps(c, 5, 0, 0);
+    TRY(launch(mode, WCT_STAGE_EIG));
+  }
+  ProfScope ps(c, 6, cost.apply_flops, cost.apply_bytes);
+  return launch(mode, WCT_STAGE_APPLY);
+}
+
 static int run_transform(wct_ctx* c, const float* fc, int Nc, const float* fs, int Ns, int C, int P,
                          float alpha, unsigned flags, float eps, half_t* out16, float* out32, int* sweeps_dev,
                          const WctFeatStats* st = nullptr) {
   const int shared = (flags & WCT_FLAG_STYLE_SHARED) ? 1 : 0;
-  const size_t ws = wct_workspace_bytes(C, Nc, Ns, P);
-  TRY(ensure(c, c->wct_ws, ws));
-  if (flags & WCT_FLAG_ADAIN) {
-    ProfScope ps(c, 7, 0, (double)P * (2.0 * Nc + 2.0 * Ns) * C * 4 + (double)P * Nc * C * 6);
-    return launch_adain(fc, Nc, fs, Ns, C, P, alpha, 1e-5f, out16, out32, c->wct_ws.p, c->wct_ws.cap, c->stream, shared, st);
-  }
-  const int mode = (flags & WCT_FLAG_MODE_NP) ? WCT_MODE_NP : WCT_MODE_TF;
-  {
-    ProfScope ps(c, 4, (double)P * 2.0 * C * C * ((double)Nc + Ns), (double)P * 2.0 * ((double)Nc + Ns) * C * 4);
-    TRY(launch_wct(fc, Nc, fs, Ns, C, P, alpha, mode, eps, out16, out32, c->wct_ws.p, c->wct_ws.cap, sweeps_dev, WCT_STAGE_COV, c->stream, shared, c->eig_fail_dev, st));
-  }
-  {
-    ProfScope ps(c, 5, 0, 0);
-    TRY(launch_wct(fc, Nc, fs, Ns, C, P, alpha, mode, eps, out16, out32, c->wct_ws.p, c->wct_ws.cap, sweeps_dev, WCT_STAGE_EIG, c->stream, shared, c->eig_fail_dev));
-  }
-  ProfScope ps(c, 6, (double)P * (2.0 * C * C * Nc + 6.0 * C * C * C), (double)P * Nc * C * (4 + (out16 ? 2 : 0) + (out32 ? 4 : 0)));
-  return launch_wct(fc, Nc, fs, Ns, C, P, alpha, mode, eps, out16, out32, c->wct_ws.p, c->wct_ws.cap, sweeps_dev, WCT_STAGE_APPLY, c->stream, shared, c->eig_fail_dev);
+  const StageCost cost = {(double)P * 2.0 * C * C * ((double)Nc + Ns), (double)P * 2.0 * ((double)Nc + Ns) * C * 4,
+                          (double)P * (2.0 * C * C * Nc + 6.0 * C * C * C), (double)P * Nc * C * (4 + (out16 ? 2 : 0) + (out32 ? 4 : 0)),
+                          (double)P * (2.0 * Nc + 2.0 * Ns) * C * 4 + (double)P * Nc * C * 6};
+  return run_stages(c, wct_workspace_bytes(C, Nc, Ns, P), flags, cost, [&](int mode, int stages) {
+    if (!stages) return launch_adain(fc, Nc, fs, Ns, C, P, alpha, 1e-5f, out16, out32, c->wct_ws.p, c->wct_ws.cap, c->stream, shared, st);
+    return launch_wct(fc, Nc, fs, Ns, C, P, alpha, mode, eps, out16, out32, c->wct_ws.p, c->wct_ws.cap, sweeps_dev, stages, c->stream,
+                      shared, c->eig_fail_dev, st);
+  });
 }
 
 // lambda[k] = weights[k] / sum(weights) (Li et al. 2017, sec. 4.2); refuses K outside 1 .. WCT_MIX_MAX and weights that are
@@ -666,29 +682,16 @@ static int mix_weights(const float* weights, int K, float* lambda) {
 static int run_transform_mix(wct_ctx* c, const float* fc, int Nc, const float* const* fs, const int* Ns, int K, const float* lambda,
                              int C, float alpha, unsigned flags, float eps, half_t* out16, float* out32, int* sweeps_dev,
                              const WctFeatStats* st = nullptr) {
-  TRY(ensure(c, c->wct_ws, wct_mix_workspace_bytes(C, Nc, Ns, K, lambda)));
   double ns = 0;
   for (int k = 0; k < K; ++k) ns += Ns[k];
-  if (flags & WCT_FLAG_ADAIN) {
-    ProfScope ps(c, 7, 0, (2.0 * Nc + 2.0 * ns) * C * 4 + (double)Nc * C * 6);
-    return launch_adain_mix(fc, Nc, fs, Ns, K, lambda, C, alpha, 1e-5f, out16, out32, c->wct_ws.p, c->wct_ws.cap, c->stream, st);
-  }
-  const int mode = (flags & WCT_FLAG_MODE_NP) ? WCT_MODE_NP : WCT_MODE_TF;
-  {
-    ProfScope ps(c, 4, 2.0 * C * C * (Nc + ns), 2.0 * (Nc + ns) * C * 4);
-    TRY(launch_wct_mix(fc, Nc, fs, Ns, K, lambda, C, alpha, mode, eps, out16, out32, c->wct_ws.p, c->wct_ws.cap, sweeps_dev,
-                       WCT_STAGE_COV, c->stream, c->eig_fail_dev, st));
-  }
-  {
-    ProfScope ps(c, 5, 0, 0);
-    TRY(launch_wct_mix(fc, Nc, fs, Ns, K, lambda, C, alpha, mode, eps, out16, out32, c->wct_ws.p, c->wct_ws.cap, sweeps_dev,
-                       WCT_STAGE_EIG, c->stream, c->eig_fail_dev));
-  }
   // (the mix of the K colouring matrices is timed with the tail it belongs to)
-  ProfScope ps(c, 6, 2.0 * C * C * Nc + 6.0 * C * C * C * (K + 1) + 2.0 * C * C * K,
-               (double)Nc * C * (4 + (out16 ? 2 : 0) + (out32 ? 4 : 0)));
-  return launch_wct_mix(fc, Nc, fs, Ns, K, lambda, C, alpha, mode, eps, out16, out32, c->wct_ws.p, c->wct_ws.cap, sweeps_dev,
-                        WCT_STAGE_APPLY, c->stream, c->eig_fail_dev);
+  const StageCost cost = {2.0 * C * C * (Nc + ns), 2.0 * (Nc + ns) * C * 4, 2.0 * C * C * Nc + 6.0 * C * C * C * (K + 1) + 2.0 * C * C * K,
+                          (double)Nc * C * (4 + (out16 ? 2 : 0) + (out32 ? 4 : 0)), (2.0 * Nc + 2.0 * ns) * C * 4 + (double)Nc * C * 6};
+  return run_stages(c, wct_mix_workspace_bytes(C, Nc, Ns, K, lambda), flags, cost, [&](int mode, int stages) {
+    if (!stages) return launch_adain_mix(fc, Nc, fs, Ns, K, lambda, C, alpha, 1e-5f, out16, out32, c->wct_ws.p, c->wct_ws.cap, c->stream, st);
+    return launch_wct_mix(fc, Nc, fs, Ns, K, lambda, C, alpha, mode, eps, out16, out32, c->wct_ws.p, c->wct_ws.cap, sweeps_dev, stages,
+                          c->stream, c->eig_fail_dev, st);
+  });
 }
 
 // Spatial control: refuses K outside 1 .. WCT_MIX_MAX and any label >= K in the n labels
@@ -713,29 +716,17 @@ static void mask_counts(const uint8_t* mask, int Hm, int Wm, int h, int w, int s
 static int run_transform_masked(wct_ctx* c, const float* fc, int Nc, const MaskGeom& g, const int* nk, const float* const* fs,
                                 const int* Ns, int K, int C, float alpha, unsigned flags, float eps, half_t* out16, float* out32,
                                 int* sweeps_dev) {
-  TRY(ensure(c, c->wct_ws, wct_masked_workspace_bytes(C, Nc, nk, Ns, K)));
   double ns = 0;
-  for (int k = 0; k < K; ++k) ns += nk[k] >= 2 ? Ns[k] : 0;
-  if (flags & WCT_FLAG_ADAIN) {
-    ProfScope ps(c, 7, 0, (4.0 * Nc + 2.0 * ns) * C * 4 + (double)Nc * C * 6);
-    return launch_adain_masked(fc, Nc, g, nk, fs, Ns, K, C, alpha, 1e-5f, out16, out32, c->wct_ws.p, c->wct_ws.cap, c->stream);
-  }
-  const int mode = (flags & WCT_FLAG_MODE_NP) ? WCT_MODE_NP : WCT_MODE_TF;
   int P = 0;
-  for (int k = 0; k < K; ++k) P += nk[k] >= 2;
-  {
-    ProfScope ps(c, 4, 2.0 * C * C * (Nc + ns), (4.0 * Nc + 2.0 * (Nc + ns)) * C * 4);     // (+ the compaction and gather)
-    TRY(launch_wct_masked(fc, Nc, g, nk, fs, Ns, K, C, alpha, mode, eps, out16, out32, c->wct_ws.p, c->wct_ws.cap, sweeps_dev,
-                          WCT_STAGE_COV, c->stream, c->eig_fail_dev));
-  }
-  {
-    ProfScope ps(c, 5, 0, 0);
-    TRY(launch_wct_masked(fc, Nc, g, nk, fs, Ns, K, C, alpha, mode, eps, out16, out32, c->wct_ws.p, c->wct_ws.cap, sweeps_dev,
-                          WCT_STAGE_EIG, c->stream, c->eig_fail_dev));
-  }
-  ProfScope ps(c, 6, 2.0 * C * C * Nc + 6.0 * C * C * C * P, (double)Nc * C * (4 + (out16 ? 2 : 0) + (out32 ? 4 : 0)));
-  return launch_wct_masked(fc, Nc, g, nk, fs, Ns, K, C, alpha, mode, eps, out16, out32, c->wct_ws.p, c->wct_ws.cap, sweeps_dev,
-                           WCT_STAGE_APPLY, c->stream, c->eig_fail_dev);
+  for (int k = 0; k < K; ++k) { ns += nk[k] >= 2 ? Ns[k] : 0; P += nk[k] >= 2; }
+  // (the covariance stage is charged the compaction and gather as well)
+  const StageCost cost = {2.0 * C * C * (Nc + ns), (4.0 * Nc + 2.0 * (Nc + ns)) * C * 4, 2.0 * C * C * Nc + 6.0 * C * C * C * P,
+                          (double)Nc * C * (4 + (out16 ? 2 : 0) + (out32 ? 4 : 0)), (4.0 * Nc + 2.0 * ns) * C * 4 + (double)Nc * C * 6};
+  return run_stages(c, wct_masked_workspace_bytes(C, Nc, nk, Ns, K), flags, cost, [&](int mode, int stages) {
+    if (!stages) return launch_adain_masked(fc, Nc, g, nk, fs, Ns, K, C, alpha, 1e-5f, out16, out32, c->wct_ws.p, c->wct_ws.cap, c->stream);
+    return launch_wct_masked(fc, Nc, g, nk, fs, Ns, K, C, alpha, mode, eps, out16, out32, c->wct_ws.p, c->wct_ws.cap, sweeps_dev, stages,
+                             c->stream, c->eig_fail_dev);
+  });
 }
 
 // ---------------------------------------------------------------------------
@@ -784,8 +775,11 @@ extern "C" int wct_adain(wct_ctx* c, const float* content, int Nc, const float* 
   return fetch(c, out, c->stage[2].p, (size_t)Nc * C * 4);
 }
 
-// the K host feature maps [Ns[k]][C] back to back in c->mix_in; dev[k] points at map k
-static int stage_in_mix(wct_ctx* c, const float* const* styles, const int* Ns, int K, int C, const float* dev[]) {
+// the inputs of a one-content, K-style op: the content [Nc][C] in stage 0 (*dc), the K host feature maps [Ns[k]][C] back to back
+// in c->mix_in (ds[k] points at map k); room for the output in stage 2 and the sweeps in stage 3
+static int stage_in_multi(wct_ctx* c, const float* content, int Nc, const float* const* styles, const int* Ns, int K, int C,
+                          void** dc, const float* ds[]) {
+  TRY(stage_in(c, 0, content, (size_t)Nc * C * 4, dc));
   size_t total = 0;
   for (int k = 0; k < K; ++k) { ARG_CHECK(styles[k] && Ns[k] >= 1); total += (size_t)Ns[k] * C * 4; }
   TRY(ensure(c, c->mix_in, total));
@@ -793,10 +787,11 @@ static int stage_in_mix(wct_ctx* c, const float* const* styles, const int* Ns, i
   for (int k = 0; k < K; ++k) {
     char* d = (char*)c->mix_in.p + off;
     HIP_TRY(hipMemcpyAsync(d, styles[k], (size_t)Ns[k] * C * 4, hipMemcpyHostToDevice, c->stream));
-    dev[k] = (const float*)d;
+    ds[k] = (const float*)d;
     off += (size_t)Ns[k] * C * 4;
   }
-  return WCT_OK;
+  TRY(ensure(c, c->stage[2], (size_t)Nc * C * 4));
+  return ensure(c, c->stage[3], 2 * WCT_MIX_MAX * sizeof(int));
 }
 
 extern "C" int wct_transform_mix(wct_ctx* c, const float* content, int Nc, const float* const* styles, const int* Ns, int K,
@@ -808,10 +803,7 @@ extern "C" int wct_transform_mix(wct_ctx* c, const float* content, int Nc, const
   TRY(eig_stale(c));
   void* dc;
   const float* ds[WCT_MIX_MAX];
-  TRY(stage_in(c, 0, content, (size_t)Nc * C * 4, &dc));
-  TRY(stage_in_mix(c, styles, Ns, K, C, ds));
-  TRY(ensure(c, c->stage[2], (size_t)Nc * C * 4));
-  TRY(ensure(c, c->stage[3], 2 * WCT_MIX_MAX * sizeof(int)));
+  TRY(stage_in_multi(c, content, Nc, styles, Ns, K, C, &dc, ds));
   TRY(run_transform_mix(c, (float*)dc, Nc, ds, Ns, K, lambda, C, alpha, mode == WCT_NP ? WCT_FLAG_MODE_NP : 0, eps,
                         nullptr, (float*)c->stage[2].p, (int*)c->stage[3].p));
   TRY(fetch(c, out, c->stage[2].p, (size_t)Nc * C * 4));
@@ -832,9 +824,7 @@ extern "C" int wct_adain_mix(wct_ctx* c, const float* content, int Nc, const flo
   HIP_TRY(hipSetDevice(c->device));
   void* dc;
   const float* ds[WCT_MIX_MAX];
-  TRY(stage_in(c, 0, content, (size_t)Nc * C * 4, &dc));
-  TRY(stage_in_mix(c, styles, Ns, K, C, ds));
-  TRY(ensure(c, c->stage[2], (size_t)Nc * C * 4));
+  TRY(stage_in_multi(c, content, Nc, styles, Ns, K, C, &dc, ds));
   TRY(ensure(c, c->wct_ws, wct_mix_workspace_bytes(C, Nc, Ns, K, lambda)));
   TRY(launch_adain_mix((float*)dc, Nc, ds, Ns, K, lambda, C, alpha, epsilon, nullptr, (float*)c->stage[2].p,
                        c->wct_ws.p, c->wct_ws.cap, c->stream));
@@ -861,10 +851,7 @@ extern "C" int wct_transform_masked(wct_ctx* c, const float* content, int Nc, co
   TRY(eig_stale(c));
   void* dc;
   const float* ds[WCT_MIX_MAX];
-  TRY(stage_in(c, 0, content, (size_t)Nc * C * 4, &dc));
-  TRY(stage_in_mix(c, styles, Ns, K, C, ds));
-  TRY(ensure(c, c->stage[2], (size_t)Nc * C * 4));
-  TRY(ensure(c, c->stage[3], 2 * WCT_MIX_MAX * sizeof(int)));
+  TRY(stage_in_multi(c, content, Nc, styles, Ns, K, C, &dc, ds));
   TRY(run_transform_masked(c, (float*)dc, Nc, g, nk, ds, Ns, K, C, alpha, mode == WCT_NP ? WCT_FLAG_MODE_NP : 0, eps,
                            nullptr, (float*)c->stage[2].p, (int*)c->stage[3].p));
   TRY(fetch(c, out, c->stage[2].p, (size_t)Nc * C * 4));
@@ -889,9 +876,7 @@ extern "C" int wct_adain_masked(wct_ctx* c, const float* content, int Nc, const 
   TRY(stage_labels(c, labels, Nc, K, nk, &g));
   void* dc;
   const float* ds[WCT_MIX_MAX];
-  TRY(stage_in(c, 0, content, (size_t)Nc * C * 4, &dc));
-  TRY(stage_in_mix(c, styles, Ns, K, C, ds));
-  TRY(ensure(c, c->stage[2], (size_t)Nc * C * 4));
+  TRY(stage_in_multi(c, content, Nc, styles, Ns, K, C, &dc, ds));
   TRY(ensure(c, c->wct_ws, wct_masked_workspace_bytes(C, Nc, nk, Ns, K)));
   TRY(launch_adain_masked((float*)dc, Nc, g, nk, ds, Ns, K, C, alpha, epsilon, nullptr, (float*)c->stage[2].p,
                           c->wct_ws.p, c->wct_ws.cap, c->stream));
@@ -1155,42 +1140,113 @@ extern "C" int wct_output_size(int Hc, int Wc, const int* levels, int n_levels, 
   return WCT_OK;
 }
 
+// The checks of a stylize call before any launch: the levels and their decoders, the output size (*Ho, *Wo), K styles
+// large enough for the deepest level (*deepest)
+static int stylize_checks(wct_ctx* c, int Hc, int Wc, const uint8_t* const* styles, const int* Hs, const int* Ws, int K,
+                          const int* levels, int n_levels, int* deepest, int* Ho, int* Wo) {
+  *deepest = 0;
+  for (int i = 0; i < n_levels; ++i) {
+    ARG_CHECK(levels[i] >= 1 && levels[i] <= 5);
+    if (levels[i] > *deepest) *deepest = levels[i];
+    if (!c->dec[levels[i]].loaded) { wct_set_error("decoder weights for relu%d_1 not set", levels[i]); return WCT_ERR_STATE; }
+  }
+  TRY(wct_output_size(Hc, Wc, levels, n_levels, Ho, Wo));
+  for (int k = 0; k < K; ++k) { ARG_CHECK(styles[k]); TRY(check_min_size("style", Hs[k], Ws[k], *deepest)); }
+  return WCT_OK;
+}
+
+// the content (nc samples) and style (ns) images as fp32 in [0,1] (wct.py:60-64): uint8 ones converted into img_c / img_s
+static int images_f32(wct_ctx* c, unsigned flags, const void* content, size_t nc, const void* style, size_t ns, const float** img_c,
+                      const float** img_s) {
+  *img_c = (const float*)content; *img_s = (const float*)style;
+  if (flags & WCT_FLAG_IMAGES_F32) return WCT_OK;
+  TRY(ensure(c, c->img_c, nc * 4));
+  TRY(ensure(c, c->img_s, ns * 4));
+  ProfScope ps(c, 7, 0, (double)(nc + ns) * 5);
+  TRY(launch_u8_to_f32((const uint8_t*)content, (float*)c->img_c.p, nc, c->stream));
+  TRY(launch_u8_to_f32((const uint8_t*)style, (float*)c->img_s.p, ns, c->stream));
+  *img_c = (const float*)c->img_c.p; *img_s = (const float*)c->img_s.p;
+  return WCT_OK;
+}
+
+// The per-channel sums and the largest value of every tap come out of the epilogue that writes it (16-pixel unit sums,
+// ConvArgs::usum): the transform's statistics pass then reads 1/16 of the feature bytes.  Needs a feature width that is
+// a multiple of 16; other widths (and WCT_FUSE_STATS=0) take the sums from the stored features -- the same bits.
+static bool fuse_stats() {
+  static const int on = getenv("WCT_FUSE_STATS") ? atoi(getenv("WCT_FUSE_STATS")) : 1;
+  return on != 0;
+}
+
+// The content chain of a stylize call (model.py:77-101) on B contents img_c [B][Hc][Wc][3] fp32: per level the encoder pass with
+// a tap (and its unit sums, umax row 0 -- its first umax_clear bytes cleared from level clear_from on), the transform, and the
+// decoder into the ping-pong images; then the uint8 frames into out (wct.py:66-68).
+// style_at(l, b, &hs, &ws): pair b's style features of relu<l>_1, hs x ws.  transform(i, l, C, h, w, st): level i (relu<l>_1,
+// C channels) of the h x w contents in c->feat_c -> c->wct_out (fp16), st the content's unit sums.  WCT_FLAG_SWAP5 runs the
+// style-swap at relu5_1 instead.
+template <typename StyleAt, typename Transform>
+static int stylize_levels(wct_ctx* c, const float* img_c, int B, int Hc, int Wc, const int* levels, int n_levels, unsigned flags,
+                          size_t umax_clear, int clear_from, StyleAt&& style_at, Transform&& transform, uint8_t* out) {
+  unsigned* const umax_c = (unsigned*)c->umax.p;
+  const float* cur = img_c;
+  int H = Hc, W = Wc;
+  for (int i = 0; i < n_levels; ++i) {
+    const int l = levels[i], C = LEVEL_C[l];
+    int h, w;
+    level_dims(H, W, l, &h, &w);
+    TRY(ensure(c, c->feat_c, (size_t)B * h * w * C * 4));
+    float* ctaps[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    ctaps[l] = (float*)c->feat_c.p;
+    float* us_c[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    unsigned* um_c[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    if (fuse_stats() && w % 16 == 0) {
+      TRY(ensure(c, c->usum_c, (size_t)B * h * (w / 16) * C * 4));
+      us_c[l] = (float*)c->usum_c.p; um_c[l] = umax_c;
+      if (i >= clear_from) HIP_TRY(hipMemsetAsync(umax_c, 0, umax_clear, c->stream));
+    }
+    WctFeatStats st = {};
+    st.u[0] = us_c[l]; st.umax[0] = um_c[l];
+    // level i>0 encodes clip(previous decoded, 0, 1) (model.py:86): the clamp is in the conv1_1 loader
+    TRY(run_encoder(c, cur, B, H, W, i > 0, l, ctaps, us_c, um_c));
+    TRY(ensure(c, c->wct_out, (size_t)B * h * w * C * 2));
+    if (l == 5 && (flags & WCT_FLAG_SWAP5)) {
+      // tf.case priority at relu5_1: swap5 > adain > wct (model.py:148-154); pairs one at a time
+      int hs, ws;
+      style_at(l, 0, &hs, &ws);
+      ARG_CHECK(h >= c->ss_patch && w >= c->ss_patch && hs >= c->ss_patch && ws >= c->ss_patch);
+      TRY(ensure(c, c->wct_ws, style_swap_workspace_bytes(C, h, w, hs, ws, c->ss_patch, c->ss_stride)));
+      ProfScope ps(c, 7, 0, 0);
+      for (int b = 0; b < B; ++b)
+        TRY(launch_style_swap((float*)c->feat_c.p + (size_t)b * h * w * C, h, w, style_at(l, b, &hs, &ws), hs, ws, C, c->ss_alpha,
+                              c->ss_patch, c->ss_stride, -1.f, (half_t*)c->wct_out.p + (size_t)b * h * w * C, nullptr,
+                              c->wct_ws.p, c->wct_ws.cap, c->stream, c->eig_fail_dev));
+    } else
+      TRY(transform(i, l, C, h, w, st));
+    const int scale = 1 << (l - 1);
+    const int H2 = h * scale, W2 = w * scale;
+    DevBuf& dst = c->img_t[i & 1];
+    TRY(ensure(c, dst, (size_t)B * H2 * W2 * 3 * 4));
+    TRY(run_decoder(c, l, (half_t*)c->wct_out.p, B, h, w, (float*)dst.p));
+    cur = (float*)dst.p; H = H2; W = W2;
+  }
+  ProfScope ps(c, 7, 0, (double)B * H * W * 3 * 5);
+  return launch_f32_to_u8(cur, out, (size_t)B * H * W * 3, c->stream);
+}
+
 extern "C" int wct_stylize_batch_dev(wct_ctx* c, const uint8_t* content, int Hc, int Wc, const uint8_t* style,
                                      int Hs, int Ws, int B, const int* levels, int n_levels, float alpha,
                                      unsigned flags, uint8_t* out) {
   ARG_CHECK(c && content && style && out && levels && n_levels >= 1 && n_levels <= 16 && B >= 1 && B <= 32);
   HIP_TRY(hipSetDevice(c->device));
-  int deepest = 0;
-  for (int i = 0; i < n_levels; ++i) {
-    ARG_CHECK(levels[i] >= 1 && levels[i] <= 5);
-    if (levels[i] > deepest) deepest = levels[i];
-    if (!c->dec[levels[i]].loaded) { wct_set_error("decoder weights for relu%d_1 not set", levels[i]); return WCT_ERR_STATE; }
-  }
-  int Ho, Wo;
-  TRY(wct_output_size(Hc, Wc, levels, n_levels, &Ho, &Wo));
-  TRY(check_min_size("style", Hs, Ws, deepest));
+  int deepest, Ho, Wo;
+  TRY(stylize_checks(c, Hc, Wc, &style, &Hs, &Ws, 1, levels, n_levels, &deepest, &Ho, &Wo));
 
   // WCT_FLAG_STYLE_SHARED: `style` is ONE image for all B pairs (a video with a fixed style); its encoder pass,
   // statistics and eigensystems are computed once per call instead of once per pair
   const int shared = (flags & WCT_FLAG_STYLE_SHARED) ? 1 : 0;
   const int Bs = shared ? 1 : B;
-  // images to fp32 in [0,1] (wct.py:60-64)
-  const size_t nc = (size_t)B * Hc * Wc * 3, ns = (size_t)Bs * Hs * Ws * 3;
-  const float* img_c = reinterpret_cast<const float*>(content);
-  const float* img_s = reinterpret_cast<const float*>(style);
-  if (!(flags & WCT_FLAG_IMAGES_F32)) {
-    TRY(ensure(c, c->img_c, nc * 4));
-    TRY(ensure(c, c->img_s, ns * 4));
-    ProfScope ps(c, 7, 0, (double)(nc + ns) * 5);
-    TRY(launch_u8_to_f32(content, (float*)c->img_c.p, nc, c->stream));
-    TRY(launch_u8_to_f32(style, (float*)c->img_s.p, ns, c->stream));
-    img_c = (const float*)c->img_c.p; img_s = (const float*)c->img_s.p;
-  }
-  // The per-channel sums and the largest value of every tap come out of the epilogue that writes it (16-pixel unit sums,
-  // ConvArgs::usum): the transform's statistics pass then reads 1/16 of the feature bytes.  Needs a feature width that is
-  // a multiple of 16; other widths (and WCT_FUSE_STATS=0) take the sums from the stored features -- the same bits.
-  static const int fuse_stats = getenv("WCT_FUSE_STATS") ? atoi(getenv("WCT_FUSE_STATS")) : 1;
-  const bool want_stats = fuse_stats != 0;
+  const float *img_c, *img_s;
+  TRY(images_f32(c, flags, content, (size_t)B * Hc * Wc * 3, style, (size_t)Bs * Hs * Ws * 3, &img_c, &img_s));
+  const bool want_stats = fuse_stats();
   constexpr size_t UROW = 32 * UMAX_SLOTS;                           // words per row: 32 images
   TRY(ensure(c, c->umax, 7 * UROW * sizeof(unsigned)));
   unsigned* const umax_c = (unsigned*)c->umax.p;                    // row 0: content (per level), rows 1..5: style levels
@@ -1212,53 +1268,19 @@ extern "C" int wct_stylize_batch_dev(wct_ctx* c, const uint8_t* content, int Hc,
   }
   TRY(run_encoder(c, img_s, Bs, Hs, Ws, 0, deepest, taps, us_s, um_s));
 
-  const float* cur = img_c;
-  int H = Hc, W = Wc;
-  for (int i = 0; i < n_levels; ++i) {
-    const int l = levels[i], C = LEVEL_C[l];
-    int h, w, hs, ws;
-    level_dims(H, W, l, &h, &w);
-    level_dims(Hs, Ws, l, &hs, &ws);
-    TRY(ensure(c, c->feat_c, (size_t)B * h * w * C * 4));
-    float* ctaps[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    ctaps[l] = (float*)c->feat_c.p;
-    float* us_c[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    unsigned* um_c[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    if (want_stats && w % 16 == 0) {
-      TRY(ensure(c, c->usum_c, (size_t)B * h * (w / 16) * C * 4));
-      us_c[l] = (float*)c->usum_c.p; um_c[l] = umax_c;
-      if (i > 0) HIP_TRY(hipMemsetAsync(umax_c, 0, UROW * sizeof(unsigned), c->stream));
-    }
-    WctFeatStats st;
-    st.u[0] = us_c[l]; st.umax[0] = um_c[l]; st.u[1] = us_s[l]; st.umax[1] = um_s[l];
-    // level i>0 encodes clip(previous decoded, 0, 1) (model.py:86): the clamp is in the conv1_1 loader
-    TRY(run_encoder(c, cur, B, H, W, i > 0, l, ctaps, us_c, um_c));
-    TRY(ensure(c, c->wct_out, (size_t)B * h * w * C * 2));
-    if (l == 5 && (flags & WCT_FLAG_SWAP5)) {
-      // tf.case priority at relu5_1: swap5 > adain > wct (model.py:148-154); pairs one at a time
-      ARG_CHECK(h >= c->ss_patch && w >= c->ss_patch && hs >= c->ss_patch && ws >= c->ss_patch);
-      TRY(ensure(c, c->wct_ws, style_swap_workspace_bytes(C, h, w, hs, ws, c->ss_patch, c->ss_stride)));
-      ProfScope ps(c, 7, 0, 0);
-      for (int b = 0; b < B; ++b)
-        TRY(launch_style_swap((float*)c->feat_c.p + (size_t)b * h * w * C, h, w,
-                              (float*)c->feat_s[l].p + (size_t)(shared ? 0 : b) * hs * ws * C, hs, ws, C, c->ss_alpha, c->ss_patch,
-                              c->ss_stride, -1.f, (half_t*)c->wct_out.p + (size_t)b * h * w * C, nullptr,
-                              c->wct_ws.p, c->wct_ws.cap, c->stream, c->eig_fail_dev));
-    } else
-    TRY(run_transform(c, (float*)c->feat_c.p, h * w, (float*)c->feat_s[l].p, hs * ws, C, B, alpha, flags, -1.f,
-                      (half_t*)c->wct_out.p, nullptr, nullptr, &st));
-    const int scale = 1 << (l - 1);
-    const int H2 = h * scale, W2 = w * scale;
-    DevBuf& dst = c->img_t[i & 1];
-    TRY(ensure(c, dst, (size_t)B * H2 * W2 * 3 * 4));
-    TRY(run_decoder(c, l, (half_t*)c->wct_out.p, B, h, w, (float*)dst.p));
-    cur = (float*)dst.p; H = H2; W = W2;
-  }
-  {
-    ProfScope ps(c, 7, 0, (double)B * H * W * 3 * 5);
-    TRY(launch_f32_to_u8(cur, out, (size_t)B * H * W * 3, c->stream));     // wct.py:66-68
-  }
-  return WCT_OK;
+  // the content chain; its umax row was cleared with the others for level 0
+  auto style_at = [&](int l, int b, int* hs, int* ws) {
+    level_dims(Hs, Ws, l, hs, ws);
+    return (const float*)c->feat_s[l].p + (size_t)(shared ? 0 : b) * *hs * *ws * LEVEL_C[l];
+  };
+  return stylize_levels(c, img_c, B, Hc, Wc, levels, n_levels, flags, UROW * sizeof(unsigned), 1, style_at,
+                        [&](int, int l, int C, int h, int w, WctFeatStats st) {
+                          int hs, ws;
+                          const float* fs = style_at(l, 0, &hs, &ws);
+                          st.u[1] = us_s[l]; st.umax[1] = um_s[l];
+                          return run_transform(c, (float*)c->feat_c.p, h * w, fs, hs * ws, C, B, alpha, flags, -1.f,
+                                               (half_t*)c->wct_out.p, nullptr, nullptr, &st);
+                        }, out);
 }
 
 extern "C" int wct_stylize(wct_ctx* c, const uint8_t* content, int Hc, int Wc, const uint8_t* style, int Hs, int Ws,
@@ -1280,27 +1302,19 @@ extern "C" int wct_stylize(wct_ctx* c, const uint8_t* content, int Hc, int Wc, c
 }
 
 // The body of wct_stylize_mix / wct_stylize_masked (their checks done): the style encoder runs once per style (sizes may differ),
-// then the content chain of wct_stylize_batch_dev with B = 1, `level_transform` in the place of the single-style transform.
-// level_transform(i, l, C, h, w, fs, Ns): level i (relu<l>_1, C channels) of the h x w content in c->feat_c -> c->wct_out (fp16);
-// fs[k] / Ns[k]: style k's features of the level.  WCT_FLAG_SWAP5 (K = 1) runs wct_stylize's style-swap at relu5_1 instead.
+// then the content chain with B = 1, `level_transform` in the place of the single-style transform.
+// level_transform(i, l, C, h, w, fs, Ns, st): stylize_levels' transform, fs[k] / Ns[k] style k's features of the level.
+// WCT_FLAG_SWAP5 (K = 1) runs wct_stylize's style-swap at relu5_1 instead.
 template <typename LevelTransform>
 static int stylize_multi(wct_ctx* c, const uint8_t* content, int Hc, int Wc, const uint8_t* const* styles, const int* Hs,
                          const int* Ws, int K, const int* levels, int n_levels, unsigned flags, uint8_t* out,
                          LevelTransform&& level_transform) {
   HIP_TRY(hipSetDevice(c->device));
-  int deepest = 0;
-  for (int i = 0; i < n_levels; ++i) {
-    ARG_CHECK(levels[i] >= 1 && levels[i] <= 5);
-    if (levels[i] > deepest) deepest = levels[i];
-    if (!c->dec[levels[i]].loaded) { wct_set_error("decoder weights for relu%d_1 not set", levels[i]); return WCT_ERR_STATE; }
-  }
-  int Ho, Wo;
-  TRY(wct_output_size(Hc, Wc, levels, n_levels, &Ho, &Wo));
-  for (int k = 0; k < K; ++k) { ARG_CHECK(styles[k]); TRY(check_min_size("style", Hs[k], Ws[k], deepest)); }
+  int deepest, Ho, Wo;
+  TRY(stylize_checks(c, Hc, Wc, styles, Hs, Ws, K, levels, n_levels, &deepest, &Ho, &Wo));
   TRY(eig_stale(c));
-  // inputs: the content in stage 0, the K styles back to back in mix_in; to fp32 in [0,1] (wct.py:60-64)
-  const bool f32in = (flags & WCT_FLAG_IMAGES_F32) != 0;
-  const size_t px = f32in ? sizeof(float) : 1;
+  // inputs: the content in stage 0, the K styles back to back in mix_in
+  const size_t px = (flags & WCT_FLAG_IMAGES_F32) ? sizeof(float) : 1;
   size_t ns_tot = 0, soff[WCT_MIX_MAX];
   for (int k = 0; k < K; ++k) { soff[k] = ns_tot; ns_tot += (size_t)Hs[k] * Ws[k] * 3; }
   const size_t nc = (size_t)Hc * Wc * 3;
@@ -1309,16 +1323,8 @@ static int stylize_multi(wct_ctx* c, const uint8_t* content, int Hc, int Wc, con
   TRY(ensure(c, c->mix_in, ns_tot * px));
   for (int k = 0; k < K; ++k)
     HIP_TRY(hipMemcpyAsync((char*)c->mix_in.p + soff[k] * px, styles[k], (size_t)Hs[k] * Ws[k] * 3 * px, hipMemcpyHostToDevice, c->stream));
-  const float* img_c = (const float*)dc;
-  const float* img_s = (const float*)c->mix_in.p;
-  if (!f32in) {
-    TRY(ensure(c, c->img_c, nc * 4));
-    TRY(ensure(c, c->img_s, ns_tot * 4));
-    ProfScope ps(c, 7, 0, (double)(nc + ns_tot) * 5);
-    TRY(launch_u8_to_f32((const uint8_t*)dc, (float*)c->img_c.p, nc, c->stream));
-    TRY(launch_u8_to_f32((const uint8_t*)c->mix_in.p, (float*)c->img_s.p, ns_tot, c->stream));
-    img_c = (const float*)c->img_c.p; img_s = (const float*)c->img_s.p;
-  }
+  const float *img_c, *img_s;
+  TRY(images_f32(c, flags, dc, nc, c->mix_in.p, ns_tot, &img_c, &img_s));
 
   // one style pass per style, a tap per requested level (model.py:69-75); style k's map of level l at feat_mix[l] + foff[l][k]
   // (statistics from the stored features: the same bits as the epilogue's unit sums, colsum_kernel)
@@ -1340,57 +1346,24 @@ static int stylize_multi(wct_ctx* c, const uint8_t* content, int Hc, int Wc, con
     TRY(run_encoder(c, img_s + soff[k], 1, Hs[k], Ws[k], 0, deepest, taps));
   }
 
-  // the content chain (wct_stylize_batch_dev, B = 1)
-  static const int fuse_stats = getenv("WCT_FUSE_STATS") ? atoi(getenv("WCT_FUSE_STATS")) : 1;
+  // the content chain, B = 1: pair k is style k (the style-swap takes K = 1); its umax row is cleared at every level
   TRY(ensure(c, c->umax, 32 * UMAX_SLOTS * sizeof(unsigned)));
-  unsigned* const umax_c = (unsigned*)c->umax.p;
-  const float* cur = img_c;
-  int H = Hc, W = Wc;
-  for (int i = 0; i < n_levels; ++i) {
-    const int l = levels[i], C = LEVEL_C[l];
-    int h, w;
-    level_dims(H, W, l, &h, &w);
-    TRY(ensure(c, c->feat_c, (size_t)h * w * C * 4));
-    float* ctaps[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    ctaps[l] = (float*)c->feat_c.p;
-    float* us_c[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    unsigned* um_c[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    if (fuse_stats && w % 16 == 0) {
-      TRY(ensure(c, c->usum_c, (size_t)h * (w / 16) * C * 4));
-      us_c[l] = (float*)c->usum_c.p; um_c[l] = umax_c;
-      HIP_TRY(hipMemsetAsync(umax_c, 0, UMAX_SLOTS * sizeof(unsigned), c->stream));
-    }
-    WctFeatStats st = {};
-    st.u[0] = us_c[l]; st.umax[0] = um_c[l];
-    TRY(run_encoder(c, cur, 1, H, W, i > 0, l, ctaps, us_c, um_c));     // level i > 0 encodes clip(previous decoded) (model.py:86)
-    TRY(ensure(c, c->wct_out, (size_t)h * w * C * 2));
-    const float* fs[WCT_MIX_MAX];
-    int Ns[WCT_MIX_MAX], hs[WCT_MIX_MAX], ws[WCT_MIX_MAX];
-    for (int k = 0; k < K; ++k) {
-      level_dims(Hs[k], Ws[k], l, &hs[k], &ws[k]);
-      fs[k] = (const float*)c->feat_mix[l].p + foff[l][k];
-      Ns[k] = hs[k] * ws[k];
-    }
-    if (l == 5 && (flags & WCT_FLAG_SWAP5)) {            // K = 1 (the callers refuse more): wct_stylize's style-swap at relu5_1
-      ARG_CHECK(K == 1 && h >= c->ss_patch && w >= c->ss_patch && hs[0] >= c->ss_patch && ws[0] >= c->ss_patch);
-      TRY(ensure(c, c->wct_ws, style_swap_workspace_bytes(C, h, w, hs[0], ws[0], c->ss_patch, c->ss_stride)));
-      ProfScope ps(c, 7, 0, 0);
-      TRY(launch_style_swap((float*)c->feat_c.p, h, w, fs[0], hs[0], ws[0], C, c->ss_alpha, c->ss_patch, c->ss_stride, -1.f,
-                            (half_t*)c->wct_out.p, nullptr, c->wct_ws.p, c->wct_ws.cap, c->stream, c->eig_fail_dev));
-    } else
-      TRY(level_transform(i, l, C, h, w, fs, Ns, &st));
-    const int scale = 1 << (l - 1);
-    const int H2 = h * scale, W2 = w * scale;
-    DevBuf& dst = c->img_t[i & 1];
-    TRY(ensure(c, dst, (size_t)H2 * W2 * 3 * 4));
-    TRY(run_decoder(c, l, (half_t*)c->wct_out.p, 1, h, w, (float*)dst.p));
-    cur = (float*)dst.p; H = H2; W = W2;
-  }
   TRY(ensure(c, c->stage[2], (size_t)Ho * Wo * 3));
-  {
-    ProfScope ps(c, 7, 0, (double)H * W * 3 * 5);
-    TRY(launch_f32_to_u8(cur, (uint8_t*)c->stage[2].p, (size_t)H * W * 3, c->stream));     // wct.py:66-68
-  }
+  auto style_at = [&](int l, int k, int* hs, int* ws) {
+    level_dims(Hs[k], Ws[k], l, hs, ws);
+    return (const float*)c->feat_mix[l].p + foff[l][k];
+  };
+  TRY(stylize_levels(c, img_c, 1, Hc, Wc, levels, n_levels, flags, UMAX_SLOTS * sizeof(unsigned), 0, style_at,
+                     [&](int i, int l, int C, int h, int w, const WctFeatStats& st) {
+                       const float* fs[WCT_MIX_MAX];
+                       int Ns[WCT_MIX_MAX];
+                       for (int k = 0; k < K; ++k) {
+                         int hs, ws;
+                         fs[k] = style_at(l, k, &hs, &ws);
+                         Ns[k] = hs * ws;
+                       }
+                       return level_transform(i, l, C, h, w, fs, Ns, &st);
+                     }, (uint8_t*)c->stage[2].p));
   TRY(fetch(c, out, c->stage[2].p, (size_t)Ho * Wo * 3));
   return eig_status(c);
 }

@@ -2380,15 +2380,23 @@ static void cov_split(int C, int Nmax, int P, int* nsplit, int* ksplit) {
   *nsplit = cdiv(Nmax, ks);
 }
 
-// nslab_max / nsplit_max > 0: size the per-matrix partial buffers for that many slabs / K-slices (a style mix, whose matrices
-// each keep the layout of their own (content, style) pair -- launch_wct_mix)
-static WctCarve carve(void* base, int C, int Nc, int Ns, int P, int nslab_max = 0, int nsplit_max = 0) {
-  WctCarve w;
+// the slab count and K-slices of ONE (content, style) pair of Nc and Ns rows: independent of P, as a pair's result must not
+// depend on its batch
+struct PairLayout { int nslab, nsplit, ksplit; };
+
+static PairLayout pair_layout(int C, int Nc, int Ns) {
+  PairLayout L;
   const int Nmax = Nc > Ns ? Nc : Ns;
-  w.nslab = wct_nslab(Nmax);
-  cov_split(C, Nmax, 1, &w.nsplit, &w.ksplit);   // independent of P: a pair's result must not depend on its batch
-  if (nslab_max > 0) w.nslab = nslab_max;
-  if (nsplit_max > 0) w.nsplit = nsplit_max;
+  L.nslab = wct_nslab(Nmax);
+  cov_split(C, Nmax, 1, &L.nsplit, &L.ksplit);
+  return L;
+}
+
+// P pairs whose per-matrix partial buffers hold lay.nslab slabs / lay.nsplit K-slices (the largest layout of the call: a slot
+// plan's matrices each keep the layout of their own pair -- SlotPlan)
+static WctCarve carve(void* base, int C, int P, const PairLayout& lay) {
+  WctCarve w;
+  w.nslab = lay.nslab; w.nsplit = lay.nsplit; w.ksplit = lay.ksplit;
   size_t off = 0;
   char* b = reinterpret_cast<char*>(base);
   auto take = [&](size_t bytes) { void* p = b ? b + off : nullptr; off += align_up(bytes); return p; };
@@ -2422,7 +2430,29 @@ static WctCarve carve(void* base, int C, int Nc, int Ns, int P, int nslab_max = 
 }
 
 size_t wct_workspace_bytes(int C, int Nc, int Ns, int P) {
-  return carve(nullptr, C < 32 ? 32 : C, Nc, Ns, P).total;
+  const int Cw = C < 32 ? 32 : C;
+  return carve(nullptr, Cw, P, pair_layout(Cw, Nc, Ns)).total;
+}
+
+// eps_in < 0 selects the reference defaults: 1e-8 on the covariance diagonal for wct_tf (ops.py:24,45,50); wct_np adds none
+// there (its 1e-5 sits inside the spectral gains, ops.py:92,114,127 -- launch_spectral_tail)
+static float cov_eps(int mode, float eps_in) {
+  return mode == WCT_MODE_TF ? (eps_in >= 0.f ? eps_in : 1e-8f) : 0.f;
+}
+
+// the eigensolve stage of a transform: the 2P matrices of w in one batched solve, minus those the skip mode drops
+static int launch_eig_stage(const WctCarve& w, int C, int P, int skip, int u_f16, int* sweeps_dev, int* eig_fail, hipStream_t s) {
+  JacobiGroup G;
+  int rc;
+  if ((rc = jacobi_make_group(&G, w.A, w.V, C, 2 * P, w.jacobi_ws, w.jacobi_bytes, sweeps_dev, eig_fail, s))) return rc;
+  G.shared_style = skip; G.tol_fn = JACOBI_TOL_FN_WCT; G.u_f16 = u_f16;
+  return jacobi_dispatch(G, C);
+}
+
+// blocks of a grid-stride pass over N rows of C channels, 4 channels a thread (the AdaIN applies, the mask gather)
+static unsigned rows_grid(size_t N, int C) {
+  const size_t blocks = (N * C / 4 + 255) / 256;
+  return (unsigned)(blocks > 2048 ? 2048 : blocks);
 }
 
 static int launch_means(const float* content, int Nc, const float* style, int Ns, int C, int P,
@@ -2547,7 +2577,7 @@ int launch_wct(const float* content, int Nc, const float* style, int Ns, int C, 
   ARG_CHECK(mode == WCT_MODE_NP || mode == WCT_MODE_TF);
   // the covariance kernel addresses one feature map through a buffer resource with 32-bit byte offsets
   ARG_CHECK((size_t)Nc * C * 4 < ((size_t)1 << 31) && (size_t)Ns * C * 4 < ((size_t)1 << 31));
-  WctCarve w = carve(workspace, C, Nc, Ns, P);
+  WctCarve w = carve(workspace, C, P, pair_layout(C, Nc, Ns));
   ARG_CHECK(workspace_bytes >= w.total);
   int rc;
   if (stages & WCT_STAGE_COV) {
@@ -2565,21 +2595,13 @@ int launch_wct(const float* content, int Nc, const float* style, int Ns, int C, 
     else hipLaunchKernelGGL((cov_f16x2_kernel<64>), grid, dim3(256), 0, s, ca);
     HIP_TRY(hipGetLastError());
   }
-  // eps_in < 0 selects the reference defaults: 1e-8 on the covariance diagonal for wct_tf
-  // (ops.py:24,45,50), 1e-5 inside the spectral gains for wct_np (ops.py:92,114,127)
-  const float eps_user = eps_in >= 0.f ? eps_in : (mode == WCT_MODE_TF ? 1e-8f : 1e-5f);
-  const float eps = mode == WCT_MODE_TF ? eps_user : 0.f;
-  hipLaunchKernelGGL(cov_finish_kernel, dim3(cdiv(C, 64), cdiv(C, 64), 2 * P), dim3(256), 0, s,
-                     w.cov_partial, w.scale, w.A, C, w.nsplit, BT, 1.f / (float)(Nc - 1), 1.f / (float)(Ns - 1), eps, shared_style, w.A0);
+  hipLaunchKernelGGL(cov_finish_kernel, dim3(cdiv(C, 64), cdiv(C, 64), 2 * P), dim3(256), 0, s, w.cov_partial, w.scale, w.A, C,
+                     w.nsplit, BT, 1.f / (float)(Nc - 1), 1.f / (float)(Ns - 1), cov_eps(mode, eps_in), shared_style, w.A0);
   HIP_TRY(hipGetLastError());
   }
-  if (stages & WCT_STAGE_EIG) {
-    JacobiGroup G;
-    if ((rc = jacobi_make_group(&G, w.A, w.V, C, 2 * P, w.jacobi_ws, w.jacobi_bytes, sweeps_dev, eig_fail, s))) return rc;
-    G.shared_style = shared_style; G.tol_fn = JACOBI_TOL_FN_WCT;
-    G.u_f16 = (stages & WCT_STAGE_EIG_FP32UPDATE) ? 0 : 1;
-    if ((rc = jacobi_dispatch(G, C))) return rc;
-  }
+  if ((stages & WCT_STAGE_EIG) &&
+      (rc = launch_eig_stage(w, C, P, shared_style, (stages & WCT_STAGE_EIG_FP32UPDATE) ? 0 : 1, sweeps_dev, eig_fail, s)))
+    return rc;
   if (!(stages & WCT_STAGE_APPLY)) return WCT_OK;
 
   if ((rc = launch_spectral_tail(w, C, P, alpha, mode, eps_in, shared_style, P, s))) return rc;
@@ -2589,46 +2611,63 @@ int launch_wct(const float* content, int Nc, const float* style, int Ns, int C, 
 // ---------------------------------------------------------------------------
 // Style mix (Li et al. 2017, sec. 4.2): mix(fc) = sum_k lambda_k T(fc, fs_k, alpha), sum_k lambda_k = 1.  T is affine in the
 // colouring side, so the mix is ONE transform with Tcs_mix = sum_k lambda_k Tcs_k and bias_mix = sum_k lambda_k bias_k.
-// Slot layout: the P = K pair layout of carve(), matrix 0 the content, matrix 2k + 1 style k; the content slots 2k (k >= 1) are
-// skipped everywhere (WCT_SKIP_MIX), so the content's statistics, covariance, eigensystem and whitening run once, and the K + 1
-// live matrices share one batched eigensolve.  Every matrix keeps the slab / K-slice layout it has in the single-pair
+// Slot layout (mix_plan): the P = K pair layout of carve(), matrix 0 the content, matrix 2k + 1 style k; the content slots 2k
+// (k >= 1) are skipped everywhere (WCT_SKIP_MIX), so the content's statistics, covariance, eigensystem and whitening run once, and
+// the K + 1 live matrices share one batched eigensolve.  Every matrix keeps the slab / K-slice layout it has in the single-pair
 // transform of its own (content, style) pair -- style k that of (content, style k), the content that of (content, style
 // ref), ref = the style of the largest weight -- so each of them comes out bit for bit as launch_wct computes it: K = 1, and
 // one-hot weights, give launch_wct's output exactly (the mix below starts from 0 and 0 + 1 x = x).
 // ---------------------------------------------------------------------------
-struct MixLayout { int nslab[2 * WCT_MIX_MAX], nsplit[2 * WCT_MIX_MAX], ksplit[2 * WCT_MIX_MAX], nslab_max, nsplit_max, Nsmax; };
+// The slot plan of a per-slot transform (a style mix, spatial control): 2P matrix slots in the pair layout of carve(), each
+// slot's statistics and covariance launched on its own rows with the layout of its own single-pair transform (pair_layout).
+struct SlotPlan {
+  int P, skip, nwhite;                         // pairs; the skip mode (WCT_SKIP_MIX or 0); pairs whose whitening side is live
+  struct Slot { const float* x; int n; PairLayout lay; } slot[2 * WCT_MIX_MAX];   // rows (null while only sizing the
+                                                                                 // workspace), their count (0: skipped), layout
+  const float* u0; const unsigned* umax0;      // slot 0's unit sums from a conv epilogue, or null
+  WctCarve w;
+  size_t total;
+};
 
-static void mix_layout(int C, int Nc, const int* Ns, int K, const float* lambda, MixLayout* L) {
-  int ref = 0;
-  for (int k = 1; k < K; ++k) if (lambda[k] > lambda[ref]) ref = k;
-  L->nslab_max = L->nsplit_max = L->Nsmax = 0;
-  for (int m = 0; m < 2 * K; ++m) {
-    if (m > 0 && (m & 1) == 0) { L->nslab[m] = L->nsplit[m] = L->ksplit[m] = 0; continue; }   // skipped content slots
-    const int ns = Ns[m == 0 ? ref : m >> 1];
-    const int Nmax = Nc > ns ? Nc : ns;
-    L->nslab[m] = wct_nslab(Nmax);
-    cov_split(C, Nmax, 1, &L->nsplit[m], &L->ksplit[m]);
-    L->nslab_max = std::max(L->nslab_max, L->nslab[m]);
-    L->nsplit_max = std::max(L->nsplit_max, L->nsplit[m]);
-    L->Nsmax = std::max(L->Nsmax, ns);
-  }
+// the workspace of a plan: partial buffers for the largest layout of its live slots (at least one pair)
+static void plan_carve(SlotPlan* sp, void* base, int C) {
+  PairLayout mx = {1, 1, 0};
+  for (int m = 0; m < 2 * sp->P; ++m)
+    if (sp->slot[m].n) { mx.nslab = std::max(mx.nslab, sp->slot[m].lay.nslab); mx.nsplit = std::max(mx.nsplit, sp->slot[m].lay.nsplit); }
+  sp->w = carve(base, C, std::max(sp->P, 1), mx);
+  sp->total = sp->w.total;
 }
 
-static WctCarve carve_mix(void* base, int C, int Nc, const int* Ns, int K, const float* lambda, MixLayout* L) {
-  mix_layout(C, Nc, Ns, K, lambda, L);
-  return carve(base, C, Nc, L->Nsmax, K, L->nslab_max, L->nsplit_max);
+// the covariance kernel addresses one feature map through a buffer resource with 32-bit byte offsets
+static bool plan_fits(const SlotPlan& sp, int C) {
+  for (int m = 0; m < 2 * sp.P; ++m)
+    if ((size_t)sp.slot[m].n * C * 4 >= ((size_t)1 << 31)) return false;
+  return true;
+}
+
+// The plan of a style mix (see above).  C: the channels (AdaIN takes C < 32; its workspace is laid out as for 32).  styles may
+// be null (the workspace size alone).  False for arguments no mix takes.
+static bool mix_plan(SlotPlan* sp, void* base, int C, const float* content, int Nc, const float* const* styles, const int* Ns,
+                     int K, const float* lambda, int nmin, const WctFeatStats* stats) {
+  if (!Ns || !lambda || K < 1 || K > WCT_MIX_MAX) return false;
+  int ref = 0;
+  for (int k = 0; k < K; ++k) {
+    if ((styles && !styles[k]) || Ns[k] < nmin || !(lambda[k] >= 0.f && lambda[k] <= 1.f)) return false;
+    if (lambda[k] > lambda[ref]) ref = k;
+  }
+  const int Cw = std::max(C, 32);
+  *sp = SlotPlan{};
+  sp->P = K; sp->skip = WCT_SKIP_MIX; sp->nwhite = 1;
+  if (stats) { sp->u0 = stats->u[0]; sp->umax0 = stats->umax[0]; }
+  sp->slot[0] = {content, Nc, pair_layout(Cw, Nc, Ns[ref])};
+  for (int k = 0; k < K; ++k) sp->slot[2 * k + 1] = {styles ? styles[k] : nullptr, Ns[k], pair_layout(Cw, Nc, Ns[k])};
+  plan_carve(sp, base, Cw);
+  return true;
 }
 
 size_t wct_mix_workspace_bytes(int C, int Nc, const int* Ns, int K, const float* lambda) {
-  MixLayout L;
-  return carve_mix(nullptr, C < 32 ? 32 : C, Nc, Ns, K, lambda, &L).total;
-}
-
-static bool mix_args_ok(const float* const* styles, const int* Ns, int K, const float* lambda, int nmin) {
-  if (!styles || !Ns || !lambda || K < 1 || K > WCT_MIX_MAX) return false;
-  for (int k = 0; k < K; ++k)
-    if (!styles[k] || Ns[k] < nmin || !(lambda[k] >= 0.f && lambda[k] <= 1.f)) return false;
-  return true;
+  SlotPlan sp;
+  return mix_plan(&sp, nullptr, C, nullptr, Nc, nullptr, Ns, K, lambda, 1, nullptr) ? sp.total : 0;
 }
 
 // first statistics pass (means, the fp16 scale; with_var: the variances) of ONE matrix, slot `m` of the workspace, with its own
@@ -2671,6 +2710,19 @@ static int launch_slot_cov(const float* x, int N, int C, int m, int nsplit, int 
   return WCT_OK;
 }
 
+// the statistics stage of a plan, slot by slot in index order (the skipped slots left out): means and the fp16 scale, with_var
+// the variances, with_cov the covariance (eps on its diagonal) into A and A0
+static int launch_plan_stats(const SlotPlan& sp, int C, bool with_var, bool with_cov, float eps, hipStream_t s) {
+  int rc;
+  for (int m = 0; m < 2 * sp.P; ++m) {
+    const SlotPlan::Slot& t = sp.slot[m];
+    if (!t.n) continue;
+    if ((rc = launch_slot_means(t.x, t.n, C, m, t.lay.nslab, sp.w, with_var, s, m ? nullptr : sp.u0, m ? nullptr : sp.umax0))) return rc;
+    if (with_cov && (rc = launch_slot_cov(t.x, t.n, C, m, t.lay.nsplit, t.lay.ksplit, eps, sp.w, s))) return rc;
+  }
+  return WCT_OK;
+}
+
 struct MixWeights { float lambda[WCT_MIX_MAX]; int K; };
 
 // Tcs_mix = sum_k lambda_k Tcs_k (Tcs_k = matrix 2k + 1 of Tw) into matrix 1, bias_mix = sum_k lambda_k bias_k into bias[0]:
@@ -2697,34 +2749,18 @@ __global__ __launch_bounds__(256) void wct_mix_kernel(float* Tw, float* bias, in
 int launch_wct_mix(const float* content, int Nc, const float* const* styles, const int* Ns, int K, const float* lambda, int C,
                    float alpha, int mode, float eps_in, half_t* out16, float* out32, void* workspace, size_t workspace_bytes,
                    int* sweeps_dev, int stages, hipStream_t s, int* eig_fail, const WctFeatStats* stats) {
-  ARG_CHECK(C % 32 == 0 && C >= 32 && C <= 1024 && Nc >= 2 && content && mix_args_ok(styles, Ns, K, lambda, 2));
+  SlotPlan sp;
+  ARG_CHECK(C % 32 == 0 && C >= 32 && C <= 1024 && Nc >= 2 && content && styles &&
+            mix_plan(&sp, workspace, C, content, Nc, styles, Ns, K, lambda, 2, stats));
   ARG_CHECK(mode == WCT_MODE_NP || mode == WCT_MODE_TF);
-  ARG_CHECK((size_t)Nc * C * 4 < ((size_t)1 << 31));
-  for (int k = 0; k < K; ++k) ARG_CHECK((size_t)Ns[k] * C * 4 < ((size_t)1 << 31));
-  MixLayout L;
-  WctCarve w = carve_mix(workspace, C, Nc, Ns, K, lambda, &L);
-  ARG_CHECK(workspace_bytes >= w.total);
+  ARG_CHECK(plan_fits(sp, C));
+  ARG_CHECK(workspace_bytes >= sp.total);
+  const WctCarve& w = sp.w;
   int rc;
-  if (stages & WCT_STAGE_COV) {
-    const float eps_user = eps_in >= 0.f ? eps_in : (mode == WCT_MODE_TF ? 1e-8f : 1e-5f);   // (as launch_wct)
-    const float eps = mode == WCT_MODE_TF ? eps_user : 0.f;
-    const WctFeatStats* fs = stats && stats->umax[0] ? stats : nullptr;
-    if ((rc = launch_slot_means(content, Nc, C, 0, L.nslab[0], w, false, s, fs ? fs->u[0] : nullptr, fs ? fs->umax[0] : nullptr))) return rc;
-    if ((rc = launch_slot_cov(content, Nc, C, 0, L.nsplit[0], L.ksplit[0], eps, w, s))) return rc;
-    for (int k = 0; k < K; ++k) {
-      const int m = 2 * k + 1;
-      if ((rc = launch_slot_means(styles[k], Ns[k], C, m, L.nslab[m], w, false, s))) return rc;
-      if ((rc = launch_slot_cov(styles[k], Ns[k], C, m, L.nsplit[m], L.ksplit[m], eps, w, s))) return rc;
-    }
-  }
-  if (stages & WCT_STAGE_EIG) {
-    JacobiGroup G;
-    if ((rc = jacobi_make_group(&G, w.A, w.V, C, 2 * K, w.jacobi_ws, w.jacobi_bytes, sweeps_dev, eig_fail, s))) return rc;
-    G.shared_style = WCT_SKIP_MIX; G.tol_fn = JACOBI_TOL_FN_WCT; G.u_f16 = 1;
-    if ((rc = jacobi_dispatch(G, C))) return rc;
-  }
+  if ((stages & WCT_STAGE_COV) && (rc = launch_plan_stats(sp, C, false, true, cov_eps(mode, eps_in), s))) return rc;
+  if ((stages & WCT_STAGE_EIG) && (rc = launch_eig_stage(w, C, sp.P, sp.skip, 1, sweeps_dev, eig_fail, s))) return rc;
   if (!(stages & WCT_STAGE_APPLY)) return WCT_OK;
-  if ((rc = launch_spectral_tail(w, C, K, alpha, mode, eps_in, WCT_SKIP_MIX, 1, s))) return rc;
+  if ((rc = launch_spectral_tail(w, C, sp.P, alpha, mode, eps_in, sp.skip, sp.nwhite, s))) return rc;
   MixWeights mw = {};
   mw.K = K;
   for (int k = 0; k < K; ++k) mw.lambda[k] = lambda[k];
@@ -2774,14 +2810,13 @@ int launch_adain(const float* content, int Nc, const float* style, int Ns, int C
                  half_t* out16, float* out32, void* workspace, size_t workspace_bytes, hipStream_t s, int shared_style,
                  const WctFeatStats* stats) {
   ARG_CHECK(C % 4 == 0 && C <= 1024 && Nc >= 1 && Ns >= 1 && P >= 1 && P <= 32);
-  WctCarve w = carve(workspace, C < 32 ? 32 : C, Nc, Ns, P);
+  const int Cw = C < 32 ? 32 : C;
+  WctCarve w = carve(workspace, Cw, P, pair_layout(Cw, Nc, Ns));
   ARG_CHECK(workspace_bytes >= w.total);
   int rc;
   if ((rc = launch_means(content, Nc, style, Ns, C, P, w, true, shared_style, s, stats))) return rc;
   const size_t n4 = (size_t)Nc * C / 4;
-  size_t blocks = (n4 + 255) / 256;
-  if (blocks > 2048) blocks = 2048;
-  hipLaunchKernelGGL(adain_apply_kernel, dim3((unsigned)blocks, P), dim3(256), 0, s, content, n4, C, w.mean, w.var, alpha, eps, out16, out32, shared_style);
+  hipLaunchKernelGGL(adain_apply_kernel, dim3(rows_grid(Nc, C), P), dim3(256), 0, s, content, n4, C, w.mean, w.var, alpha, eps, out16, out32, shared_style);
   HIP_TRY(hipGetLastError());
   return WCT_OK;
 }
@@ -2802,23 +2837,18 @@ __global__ void adain_mix_moments_kernel(const float* mean, const float* var, fl
 int launch_adain_mix(const float* content, int Nc, const float* const* styles, const int* Ns, int K, const float* lambda, int C,
                      float alpha, float eps, half_t* out16, float* out32, void* workspace, size_t workspace_bytes, hipStream_t s,
                      const WctFeatStats* stats) {
-  ARG_CHECK(C % 4 == 0 && C <= 1024 && Nc >= 1 && content && mix_args_ok(styles, Ns, K, lambda, 1));
-  MixLayout L;
-  WctCarve w = carve_mix(workspace, C < 32 ? 32 : C, Nc, Ns, K, lambda, &L);
-  ARG_CHECK(workspace_bytes >= w.total);
+  SlotPlan sp;
+  ARG_CHECK(C % 4 == 0 && C <= 1024 && Nc >= 1 && content && styles && mix_plan(&sp, workspace, C, content, Nc, styles, Ns, K, lambda, 1, stats));
+  ARG_CHECK(workspace_bytes >= sp.total);
+  const WctCarve& w = sp.w;
   int rc;
-  const WctFeatStats* fs = stats && stats->umax[0] ? stats : nullptr;
-  if ((rc = launch_slot_means(content, Nc, C, 0, L.nslab[0], w, true, s, fs ? fs->u[0] : nullptr, fs ? fs->umax[0] : nullptr))) return rc;
-  for (int k = 0; k < K; ++k)
-    if ((rc = launch_slot_means(styles[k], Ns[k], C, 2 * k + 1, L.nslab[2 * k + 1], w, true, s))) return rc;
+  if ((rc = launch_plan_stats(sp, C, true, false, 0.f, s))) return rc;
   MixWeights mw = {};
   mw.K = K;
   for (int k = 0; k < K; ++k) mw.lambda[k] = lambda[k];
   hipLaunchKernelGGL(adain_mix_moments_kernel, dim3(cdiv(C, 256)), dim3(256), 0, s, w.mean, w.var, w.mix, C, mw);
   const size_t n4 = (size_t)Nc * C / 4;
-  size_t blocks = (n4 + 255) / 256;
-  if (blocks > 2048) blocks = 2048;
-  hipLaunchKernelGGL(adain_apply_kernel, dim3((unsigned)blocks, 1), dim3(256), 0, s, content, n4, C, w.mean, w.var, alpha, eps, out16, out32, 0,
+  hipLaunchKernelGGL(adain_apply_kernel, dim3(rows_grid(Nc, C), 1), dim3(256), 0, s, content, n4, C, w.mean, w.var, alpha, eps, out16, out32, 0,
                      (const float*)w.mix, (const float*)(w.mix + C));
   HIP_TRY(hipGetLastError());
   return WCT_OK;
@@ -2968,75 +2998,69 @@ int launch_mask_compact(const MaskGeom& g, int N, int K, int* perm, int* seg_off
   return WCT_OK;
 }
 
-// the slot layout of a masked level: pairs = the labels with nk >= 2 rows, in label order
-struct MaskCarve {
-  WctCarve w; MixLayout L;
-  int P, lab[WCT_MIX_MAX], row0[WCT_MIX_MAX], nmax; unsigned single;   // row0: where label k starts (host counts)
+// The slot plan of a masked level: pair p = the p-th label with nk >= 2 rows, slot 2p its rows of the gathered buffer, slot
+// 2p + 1 its style, both with the layout of the single pair (nk[k], Ns[k]).  C as in mix_plan; styles may be null (the
+// workspace size alone).  False for arguments no masked transform takes.
+struct MaskPlan : SlotPlan {
+  int lab[WCT_MIX_MAX], nmax; unsigned single;   // the label of pair p; the most rows of a pair; bit k: label k has 1 row
   float* xg; int *perm, *seg_off; void* compact_ws;
-  size_t total;
 };
 
-static MaskCarve carve_masked(void* base, int C, int Nc, const int* nk, const int* Ns, int K) {
-  MaskCarve m;
-  m.P = 0; m.nmax = 0; m.single = 0;
-  MixLayout& L = m.L;
-  L.nslab_max = L.nsplit_max = L.Nsmax = 0;
-  int row = 0;
+static bool mask_plan(MaskPlan* m, void* base, int C, int Nc, const int* nk, const float* const* styles, const int* Ns, int K,
+                      int nmin) {
+  if (!nk || !Ns || K < 1 || K > WCT_MIX_MAX || Nc < 1) return false;
+  long long sum = 0;
   for (int k = 0; k < K; ++k) {
-    m.row0[k] = row;
-    row += nk[k];
-    if (nk[k] == 1) m.single |= 1u << k;
-    if (nk[k] < 2) continue;
-    const int p = m.P++;
-    m.lab[p] = k;
-    m.nmax = std::max(m.nmax, nk[k]);
-    const int Nmax = std::max(nk[k], Ns[k]);
-    for (int side = 0; side < 2; ++side) {       // (as carve() lays out the single pair (nk[k], Ns[k]))
-      L.nslab[2 * p + side] = wct_nslab(Nmax);
-      cov_split(C, Nmax, 1, &L.nsplit[2 * p + side], &L.ksplit[2 * p + side]);
-    }
-    L.nslab_max = std::max(L.nslab_max, L.nslab[2 * p]);
-    L.nsplit_max = std::max(L.nsplit_max, L.nsplit[2 * p]);
-    L.Nsmax = std::max(L.Nsmax, Ns[k]);
+    if (nk[k] < 0 || (nk[k] >= 2 && ((styles && !styles[k]) || Ns[k] < nmin))) return false;
+    sum += nk[k];
   }
-  m.w = carve(base, C, 2, 2, std::max(m.P, 1), std::max(L.nslab_max, 1), std::max(L.nsplit_max, 1));
-  size_t off = m.w.total;
+  if (sum != Nc) return false;                   // every row has a label < K (the caller counted them)
+  const int Cw = std::max(C, 32);
+  *m = MaskPlan{};
+  int row0[WCT_MIX_MAX], row = 0;                // where label k starts (host counts)
+  for (int k = 0; k < K; ++k) {
+    row0[k] = row;
+    row += nk[k];
+    if (nk[k] == 1) m->single |= 1u << k;
+    if (nk[k] < 2) continue;
+    const int p = m->P++;
+    m->lab[p] = k;
+    m->nmax = std::max(m->nmax, nk[k]);
+    const PairLayout lay = pair_layout(Cw, nk[k], Ns[k]);
+    m->slot[2 * p] = {nullptr, nk[k], lay};
+    m->slot[2 * p + 1] = {styles ? styles[k] : nullptr, Ns[k], lay};
+  }
+  m->nwhite = m->P;
+  plan_carve(m, base, Cw);
+  size_t off = m->total;
   char* b = reinterpret_cast<char*>(base);
   auto take = [&](size_t bytes) { void* q = b ? b + off : nullptr; off += align_up(bytes); return q; };
-  m.xg = (float*)take((size_t)Nc * C * sizeof(float));
-  m.perm = (int*)take((size_t)Nc * sizeof(int));
-  m.seg_off = (int*)take((WCT_MIX_MAX + 1) * sizeof(int));
-  m.compact_ws = take(mask_compact_workspace_bytes(Nc));
-  m.total = off;
-  return m;
+  m->xg = (float*)take((size_t)Nc * Cw * sizeof(float));
+  m->perm = (int*)take((size_t)Nc * sizeof(int));
+  m->seg_off = (int*)take((WCT_MIX_MAX + 1) * sizeof(int));
+  m->compact_ws = take(mask_compact_workspace_bytes(Nc));
+  m->total = off;
+  if (m->xg)
+    for (int p = 0; p < m->P; ++p) m->slot[2 * p].x = m->xg + (size_t)row0[m->lab[p]] * C;
+  return true;
 }
 
 size_t wct_masked_workspace_bytes(int C, int Nc, const int* nk, const int* Ns, int K) {
-  return carve_masked(nullptr, C < 32 ? 32 : C, Nc, nk, Ns, K).total;
-}
-
-static bool masked_args_ok(int Nc, const int* nk, const float* const* styles, const int* Ns, int K, int nmin) {
-  if (!nk || !styles || !Ns || K < 1 || K > WCT_MIX_MAX || Nc < 1) return false;
-  long long sum = 0;
-  for (int k = 0; k < K; ++k) {
-    if (nk[k] < 0 || (nk[k] >= 2 && (!styles[k] || Ns[k] < nmin))) return false;
-    sum += nk[k];
-  }
-  return sum == Nc;                              // every row has a label < K (the caller counted them)
+  MaskPlan m;
+  return mask_plan(&m, nullptr, C, Nc, nk, nullptr, Ns, K, 1) ? m.total : 0;
 }
 
 // compaction and gather of a masked level (the first stage of both masked transforms)
-static int launch_mask_gather(const float* content, const MaskGeom& g, int Nc, int K, int C, const MaskCarve& m, hipStream_t s) {
+static int launch_mask_gather(const float* content, const MaskGeom& g, int Nc, int K, int C, const MaskPlan& m, hipStream_t s) {
   int rc;
   if ((rc = launch_mask_compact(g, Nc, K, m.perm, m.seg_off, m.compact_ws, s))) return rc;
-  const size_t n4 = (size_t)Nc * C / 4;
-  hipLaunchKernelGGL(mask_gather_kernel, dim3((unsigned)std::min<size_t>((n4 + 255) / 256, 2048)), dim3(256), 0, s, content,
-                     (const int*)m.perm, (const int*)m.seg_off, K, C, m.xg);
+  hipLaunchKernelGGL(mask_gather_kernel, dim3(rows_grid(Nc, C)), dim3(256), 0, s, content, (const int*)m.perm, (const int*)m.seg_off, K, C,
+                     m.xg);
   HIP_TRY(hipGetLastError());
   return WCT_OK;
 }
 
-static int launch_mask_passthrough(const float* content, int C, const MaskCarve& m, int K, half_t* out16, float* out32, hipStream_t s) {
+static int launch_mask_passthrough(const float* content, int C, const MaskPlan& m, int K, half_t* out16, float* out32, hipStream_t s) {
   if (!m.single) return WCT_OK;
   hipLaunchKernelGGL(mask_passthrough_kernel, dim3(K), dim3(256), 0, s, content, (const int*)m.seg_off, (const int*)m.perm, m.single,
                      C, out16, out32);
@@ -3047,43 +3071,27 @@ static int launch_mask_passthrough(const float* content, int C, const MaskCarve&
 int launch_wct_masked(const float* content, int Nc, const MaskGeom& g, const int* nk, const float* const* styles, const int* Ns, int K,
                       int C, float alpha, int mode, float eps_in, half_t* out16, float* out32, void* workspace, size_t workspace_bytes,
                       int* sweeps_dev, int stages, hipStream_t s, int* eig_fail) {
-  ARG_CHECK(C % 32 == 0 && C >= 32 && C <= 1024 && content && masked_args_ok(Nc, nk, styles, Ns, K, 2));
+  MaskPlan m;
+  ARG_CHECK(C % 32 == 0 && C >= 32 && C <= 1024 && content && styles && mask_plan(&m, workspace, C, Nc, nk, styles, Ns, K, 2));
   ARG_CHECK(mode == WCT_MODE_NP || mode == WCT_MODE_TF);
-  ARG_CHECK((size_t)Nc * C * 4 < ((size_t)1 << 31));
-  for (int k = 0; k < K; ++k) ARG_CHECK(nk[k] < 2 || (size_t)Ns[k] * C * 4 < ((size_t)1 << 31));
-  MaskCarve m = carve_masked(workspace, C, Nc, nk, Ns, K);
+  ARG_CHECK((size_t)Nc * C * 4 < ((size_t)1 << 31) && plan_fits(m, C));
   ARG_CHECK(workspace_bytes >= m.total);
   const WctCarve& w = m.w;
-  const MixLayout& L = m.L;
   int rc;
   if (stages & WCT_STAGE_COV) {
-    const float eps_user = eps_in >= 0.f ? eps_in : (mode == WCT_MODE_TF ? 1e-8f : 1e-5f);   // (as launch_wct)
-    const float eps = mode == WCT_MODE_TF ? eps_user : 0.f;
     if ((rc = launch_mask_gather(content, g, Nc, K, C, m, s))) return rc;
-    for (int p = 0; p < m.P; ++p) {
-      const int k = m.lab[p], mc = 2 * p, ms = 2 * p + 1;
-      const float* xk = m.xg + (size_t)m.row0[k] * C;
-      if ((rc = launch_slot_means(xk, nk[k], C, mc, L.nslab[mc], w, false, s))) return rc;
-      if ((rc = launch_slot_cov(xk, nk[k], C, mc, L.nsplit[mc], L.ksplit[mc], eps, w, s))) return rc;
-      if ((rc = launch_slot_means(styles[k], Ns[k], C, ms, L.nslab[ms], w, false, s))) return rc;
-      if ((rc = launch_slot_cov(styles[k], Ns[k], C, ms, L.nsplit[ms], L.ksplit[ms], eps, w, s))) return rc;
-    }
+    if ((rc = launch_plan_stats(m, C, false, true, cov_eps(mode, eps_in), s))) return rc;
   }
-  if ((stages & WCT_STAGE_EIG) && m.P > 0) {
-    JacobiGroup G;
-    if ((rc = jacobi_make_group(&G, w.A, w.V, C, 2 * m.P, w.jacobi_ws, w.jacobi_bytes, sweeps_dev, eig_fail, s))) return rc;
-    G.shared_style = 0; G.tol_fn = JACOBI_TOL_FN_WCT; G.u_f16 = 1;
-    if ((rc = jacobi_dispatch(G, C))) return rc;
-  }
+  if ((stages & WCT_STAGE_EIG) && m.P > 0 && (rc = launch_eig_stage(w, C, m.P, m.skip, 1, sweeps_dev, eig_fail, s))) return rc;
   if (!(stages & WCT_STAGE_APPLY)) return WCT_OK;
   if (m.P > 0) {
-    if ((rc = launch_spectral_tail(w, C, m.P, alpha, mode, eps_in, 0, m.P, s))) return rc;
+    if ((rc = launch_spectral_tail(w, C, m.P, alpha, mode, eps_in, m.skip, m.nwhite, s))) return rc;
     if ((rc = launch_blend(w, C, m.P, alpha, 0, s))) return rc;
     ApplySegArgs a;
     a.x = m.xg; a.N = 0; a.C = C; a.mean = w.mean; a.M = w.M; a.bias = w.bias;
     a.xscale = w.scale; a.mabs = w.mabs; a.out16 = out16; a.out32 = out32;
     a.seg_off = m.seg_off; a.perm = m.perm;
-    for (int p = 0; p < WCT_MIX_MAX; ++p) a.lab[p] = p < m.P ? m.lab[p] : 0;
+    for (int p = 0; p < WCT_MIX_MAX; ++p) a.lab[p] = m.lab[p];           // (0 past the pairs)
     if (C >= 128) hipLaunchKernelGGL((apply_f16x2_kernel<128, 128, ApplySegArgs>), dim3(cdiv(m.nmax, 128), cdiv(C, 128), m.P), dim3(256), 0, s, a);
     else hipLaunchKernelGGL((apply_f16x2_kernel<64, 128, ApplySegArgs>), dim3(cdiv(m.nmax, 128), cdiv(C, 64), m.P), dim3(256), 0, s, a);
     HIP_TRY(hipGetLastError());
@@ -3128,24 +3136,17 @@ __global__ void adain_seg_apply_kernel(const float* xg, const int* seg_off, cons
 
 int launch_adain_masked(const float* content, int Nc, const MaskGeom& g, const int* nk, const float* const* styles, const int* Ns, int K,
                         int C, float alpha, float eps, half_t* out16, float* out32, void* workspace, size_t workspace_bytes, hipStream_t s) {
-  ARG_CHECK(C % 4 == 0 && C <= 1024 && content && masked_args_ok(Nc, nk, styles, Ns, K, 1));
-  MaskCarve m = carve_masked(workspace, C < 32 ? 32 : C, Nc, nk, Ns, K);
+  MaskPlan m;
+  ARG_CHECK(C % 4 == 0 && C <= 1024 && content && styles && mask_plan(&m, workspace, C, Nc, nk, styles, Ns, K, 1));
   ARG_CHECK(workspace_bytes >= m.total);
   const WctCarve& w = m.w;
   int rc;
   if ((rc = launch_mask_gather(content, g, Nc, K, C, m, s))) return rc;
-  SegLabels sl = {};
-  for (int p = 0; p < m.P; ++p) {
-    const int k = m.lab[p];
-    sl.lab[p] = k;
-    if ((rc = launch_slot_means(m.xg + (size_t)m.row0[k] * C, nk[k], C, 2 * p, m.L.nslab[2 * p], w, true, s))) return rc;
-    if ((rc = launch_slot_means(styles[k], Ns[k], C, 2 * p + 1, m.L.nslab[2 * p + 1], w, true, s))) return rc;
-  }
+  if ((rc = launch_plan_stats(m, C, true, false, 0.f, s))) return rc;
   if (m.P > 0) {
-    const size_t n4 = (size_t)m.nmax * C / 4;
-    size_t blocks = (n4 + 255) / 256;
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(adain_seg_apply_kernel, dim3((unsigned)blocks, m.P), dim3(256), 0, s, (const float*)m.xg, (const int*)m.seg_off,
+    SegLabels sl;
+    for (int p = 0; p < WCT_MIX_MAX; ++p) sl.lab[p] = m.lab[p];
+    hipLaunchKernelGGL(adain_seg_apply_kernel, dim3(rows_grid(m.nmax, C), m.P), dim3(256), 0, s, (const float*)m.xg, (const int*)m.seg_off,
                        (const int*)m.perm, sl, C, (const float*)w.mean, (const float*)w.var, alpha, eps, out16, out32);
     HIP_TRY(hipGetLastError());
   }
@@ -3304,7 +3305,7 @@ int launch_style_swap(const float* content, int hc, int wc, const float* style, 
   const int Nc = hc * wc, Ns = hs * ws, Mo = ho * wo, Pn = rows * cols, K = patch * patch * C;
   const size_t wct_bytes = align_up(wct_workspace_bytes(C, Nc, Ns, 1));
   ARG_CHECK(workspace_bytes >= style_swap_workspace_bytes(C, hc, wc, hs, ws, patch, stride));
-  WctCarve w = carve(workspace, C, Nc, Ns, 1);
+  WctCarve w = carve(workspace, C, 1, pair_layout(C, Nc, Ns));
   SwapCarve sw = swap_carve((char*)workspace + wct_bytes, C, hc, wc, hs, ws, patch, stride);
   int rc;
   // statistics, covariances (+eps I), eigendecompositions: the same stages as wct_tf

@@ -87,20 +87,26 @@ class WCT(object):
     def postprocess(image):
         return np.uint8(np.clip(image, 0, 1) * 255)
 
+    def _swap5_setup(self, content, mask, swap5, ss_alpha):
+        '''With swap5: the style-swap settings, and the content (and the mask, if any) center-cropped so that the swap's
+           filter fits when ss_stride > 1 (a crop, never a resize: H, W fit inside the content).  -> (content, mask)'''
+        if swap5 is True and self.ss_stride != 1:
+            from .utils import swap_filter_fit, center_crop_to, _centre_window
+            should_refit, H, W = swap_filter_fit(content.shape[0], content.shape[1], self.ss_patch_size, self.ss_stride)
+            if should_refit:
+                content = center_crop_to(content, H, W)
+                if mask is not None:
+                    mask = np.ascontiguousarray(_centre_window(mask, H, W))
+        if swap5:
+            self.sess.set_style_swap(ss_alpha, self.ss_patch_size, self.ss_stride)
+        return content, mask
+
     def predict(self, content, style, alpha=1, swap5=False, ss_alpha=1, adain=False):
         '''Stylize a single content/style pair; arrays in [0,255], returns uint8 HxWx3.
            The /255 preprocess and the clip*255 postprocess run inside the library
            (fused at the ends of the kernel chain).'''
-        content = np.asarray(content)
+        content, _ = self._swap5_setup(np.asarray(content), None, swap5, ss_alpha)
         style = np.asarray(style)
-        # If doing style swap and stride > 1 the content might need to be resized for the filter to fit
-        if swap5 is True and self.ss_stride != 1:
-            from .utils import swap_filter_fit, center_crop_to
-            should_refit, H, W = swap_filter_fit(content.shape[0], content.shape[1], self.ss_patch_size, self.ss_stride)
-            if should_refit:
-                content = center_crop_to(content, H, W)
-        if swap5:
-            self.sess.set_style_swap(ss_alpha, self.ss_patch_size, self.ss_stride)
         # uint8 arrays take the fused /255 on the device; float arrays are divided by 255 WITHOUT rounding, as the
         # reference's preprocess does (wct.py:60-64) -- Context.stylize hands them over as float32 images
         return self.sess.stylize(content, style, self.relu_targets, alpha=alpha, adain=adain,
@@ -116,14 +122,7 @@ class WCT(object):
         weights = mix_weights(weights, len(styles))              # ValueError before any GPU call
         if swap5 and len(styles) > 1:
             raise ValueError('swap5 takes one style: style-swap is not linear in the style')
-        content = np.asarray(content)
-        if swap5 is True and self.ss_stride != 1:
-            from .utils import swap_filter_fit, center_crop_to
-            should_refit, H, W = swap_filter_fit(content.shape[0], content.shape[1], self.ss_patch_size, self.ss_stride)
-            if should_refit:
-                content = center_crop_to(content, H, W)
-        if swap5:
-            self.sess.set_style_swap(ss_alpha, self.ss_patch_size, self.ss_stride)
+        content, _ = self._swap5_setup(np.asarray(content), None, swap5, ss_alpha)
         return self.sess.stylize_mix(content, styles, weights, self.relu_targets, alpha=alpha, adain=adain,
                                      wct_mode=self.wct_mode, swap5=bool(swap5))
 
@@ -139,14 +138,7 @@ class WCT(object):
         mask = mask_labels(mask, len(styles), content.shape[:2])        # ValueError before any GPU call
         if swap5 and len(styles) > 1:
             raise ValueError('swap5 takes one style: style-swap is not a per-region affine map')
-        if swap5 is True and self.ss_stride != 1:
-            from .utils import swap_filter_fit, center_crop_to, _centre_window
-            should_refit, H, W = swap_filter_fit(content.shape[0], content.shape[1], self.ss_patch_size, self.ss_stride)
-            if should_refit:                                       # (a crop, never a resize: H, W fit inside the content)
-                content = center_crop_to(content, H, W)
-                mask = np.ascontiguousarray(_centre_window(mask, H, W))
-        if swap5:
-            self.sess.set_style_swap(ss_alpha, self.ss_patch_size, self.ss_stride)
+        content, mask = self._swap5_setup(content, mask, swap5, ss_alpha)
         return self.sess.stylize_masked(content, styles, mask, self.relu_targets, alpha=alpha, adain=adain,
                                         wct_mode=self.wct_mode, swap5=bool(swap5))
 
