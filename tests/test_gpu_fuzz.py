@@ -131,7 +131,7 @@ def _wct_case(ctx, c, hc, wc, hs, ws, alpha, mode, log_scale, seed):
     # reference's float32 landed 9.5e-5 .. 4.6e-4 from the exact outcome and this path 1.06e-3 .. 2.36e-3.  Cause: the solver
     # tracks the rotated matrix D + E and the eigenvectors V separately (fp32 tile updates; 22-bit products), so V^T A0 V = D + E
     # held only to ~1e-6 ||A||, and the spectral functions' completion took that inconsistency for signal; a kept noise direction
-    # has a gain of up to 316.  FIX (csrc/wct.hip refresh_needed): for a matrix with a kept eigenvalue 4 decades below its
+    # has a gain of up to 316.  FIX (csrc/stats_gemm.hip refresh_needed): for a matrix with a kept eigenvalue 4 decades below its
     # largest the rotated matrix is RECOMPUTED, E' = V^T A0 V, before the spectral functions -- f(A0) = V f(V^T A0 V) V^T is then
     # exact for orthogonal V.  After it the same cases read 3.5e-5 (was 2.36e-3; reference 4.6e-4), 6.1e-7 (5.2e-4; 4.4e-5),
     # 4.1e-6 (7.2e-4; 1.3e-4): the stated budget holds again -- 1e-3, or 4x what the reference's arithmetic loses on the input.

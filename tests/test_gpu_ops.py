@@ -42,7 +42,7 @@ def test_eigh_matches_lapack(ctx, c):
     mats = np.stack([_graded_spd(rng, c, 3.0), _graded_spd(rng, c, 1.0, rank=c // 3)])
     evals, evecs, sweeps = ctx.eigh(mats, return_sweeps=True)
     print('C=%d sweeps=%s' % (c, sweeps))
-    assert max(sweeps) <= 14                  # two inside the budget of 16 (csrc/wct.hip JACOBI_MAX_SWEEPS)
+    assert max(sweeps) <= 14                  # two inside the budget of 16 (csrc/eigh.hip JACOBI_MAX_SWEEPS)
     for a, lam, v in zip(mats, evals, evecs):
         a64 = a.astype(np.float64)
         ref = np.linalg.eigvalsh(a64)
@@ -170,7 +170,7 @@ def test_wct_rank_deficient_features_whose_rounding_noise_is_above_the_cutoff(ct
     noise of ~1e-7 ||cov||, which from a feature scale of ~10 on is ABOVE the reference's absolute 1e-5 cut-off (ops.py:68-69 /
     112,125).  The exact outcome (the oracle in float64) drops them; the reference's float32 evaluation keeps them with gains of
     order one and lands 1e-4 .. 2e-3 from the exact outcome.  Round 6 found this path off by 0.14 .. 11.5 at scale 1e3 (the
-    completion of the spectral functions summed over noise pairs with squared cosines of order one -- csrc/wct.hip
+    completion of the spectral functions summed over noise pairs with squared cosines of order one -- csrc/spectral.hip
     pair_resolved / spectral_cut, profiles/r06_noise_block.txt).  Bound: 1e-3, or four times what the reference's float32 loses."""
     c, hc, wc, hs, ws = 256, 12, 7, 13, 6
     fn = oracle.wct_np if mode == 'np' else oracle.wct_tf

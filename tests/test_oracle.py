@@ -296,7 +296,7 @@ def test_wct_style_swap_properties():
 
 
 def test_refresh_model_tracked_rotated_matrix_is_the_error_recomputed_one_is_not():
-    """The experiment behind the eigen-stage's refresh (csrc/wct.hip refresh_needed), kept as a regression test of
+    """The experiment behind the eigen-stage's refresh (csrc/stats_gemm.hip refresh_needed), kept as a regression test of
     the ARGUMENT: a NumPy model of the solver (cyclic Jacobi in float32, eigenvectors rounded to 22 bits like the split-fp16
     products, first-order completion of the spectral functions) on a rank-deficient covariance (C = 96, N = 4) whose rounding-noise
     eigenvalues the reference's absolute cut-off keeps.  With the TRACKED rotated matrix the transform is 3e-3 from the nearest

@@ -1,4 +1,4 @@
-"""NumPy model of the DATA ROUTING of the look-ahead block-Jacobi launches (round 3, csrc/wct.hip jacobi_fused_kernel):
+"""NumPy model of the DATA ROUTING of the look-ahead block-Jacobi launches (round 3, csrc/eigh.hip jacobi_fused_kernel):
 
   launch L_s = { D(s): pair problems of outer step s,  U(s-1): tile update of outer step s-1 }
 

@@ -6,7 +6,7 @@ sys.path.insert(0, ROOT)
 from wct_tf_amd import build
 src = [os.path.join(ROOT, 'wct_tf_amd', 'csrc', s) for s in build.SOURCES]
 print('# hipcc %s -Rpass-analysis=kernel-resource-usage  (the flags of wct_tf_amd/build.py)' % ' '.join(build.FLAGS))
-print('%-8s %5s %5s %8s %7s %7s %5s %8s  %s' % ('file', 'VGPR', 'AGPR', 'scratch', 'vspill', 'sspill', 'occ', 'LDS', 'kernel'))
+print('%-10s %5s %5s %8s %7s %7s %5s %8s  %s' % ('file', 'VGPR', 'AGPR', 'scratch', 'vspill', 'sspill', 'occ', 'LDS', 'kernel'))
 worst = 0
 for f in src:
     out = subprocess.run([os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')] + build.FLAGS + build.FILE_FLAGS.get(os.path.basename(f), []) +
@@ -30,6 +30,6 @@ for f in src:
         name = re.sub(r'\(.*', '', name.replace('(anonymous namespace)::', '')).replace('void ', '')
         sc = int(r.get('ScratchSize [bytes/lane]', '0'))
         worst = max(worst, sc)
-        print('%-8s %5s %5s %8d %7s %7s %5s %8s  %s' % (os.path.basename(f)[:8], r['VGPRs'], r.get('AGPRs', '0'), sc, r.get('VGPRs Spill', '0'), r.get('SGPRs Spill', '0'),
+        print('%-10s %5s %5s %8d %7s %7s %5s %8s  %s' % (os.path.basename(f)[:-4][:10], r['VGPRs'], r.get('AGPRs', '0'), sc, r.get('VGPRs Spill', '0'), r.get('SGPRs Spill', '0'),
                                                      r.get('Occupancy [waves/SIMD]', '?'), r.get('LDS Size [bytes/block]', '0'), name))
 print('# largest scratch size of any kernel: %d bytes per lane' % worst)

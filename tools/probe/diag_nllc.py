@@ -1,6 +1,6 @@
 """NumPy model of the fuzz sweep's failing N << C case (C = 96, N = 4, scale 10): cyclic Jacobi in fp32 with V in fp32 or rounded to 22 bits, first-order
 completion of the spectral functions on (a) the TRACKED rotated matrix, (b) the rotated matrix recomputed from V and the untouched covariance.  Round 5: the
-experiment behind refresh_needed (csrc/wct.hip).  Result: profiles/r05_parity_holes.txt."""
+experiment behind refresh_needed (csrc/stats_gemm.hip).  Result: profiles/r05_parity_holes.txt."""
 import numpy as np, sys
 import os
 ROOT=os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

@@ -3,18 +3,23 @@ import hashlib
 import os
 import subprocess
 import sys
+from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIB = os.path.join(HERE, 'libwct_hip.so')
-SOURCES = ['api.hip', 'conv.hip', 'conv_wino.hip', 'wct.hip', 'coral.hip', 'train.hip']
+# the whiten-colour transform is one unit per stage (csrc/wct_stages.h is what they share)
+WCT_UNITS = ['stats_gemm.hip', 'eigh.hip', 'spectral.hip', 'wct.hip', 'mask.hip', 'style_swap.hip']
+SOURCES = ['api.hip', 'conv.hip', 'conv_wino.hip', 'coral.hip', 'train.hip'] + WCT_UNITS
 
 
 STAMP = LIB + '.src.sha256'
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wno-unused-value', '-Wno-unused-result']
-# per-file additions.  wct.hip: the SLP vectoriser packs the eigensolver's rotation arithmetic into v_pk_fma_f32 pairs at the
-# price of ~20 v_mov per rotation set for operand assembly (measured: Jacobi 25.2 -> 23.8 ms per 32-pair step without it)
-FILE_FLAGS = {'wct.hip': ['-fno-slp-vectorize']}
+# per-file additions.  eigh.hip: the SLP vectoriser packs the eigensolver's rotation arithmetic into v_pk_fma_f32 pairs at the
+# price of ~20 v_mov per rotation set for operand assembly (measured: Jacobi 25.2 -> 23.8 ms per 32-pair step without it).  Only
+# the eigensolver is known to need the flag; the other transform units carry it because they were built with it while they were
+# one file with the solver, and nobody has measured them without it.
+FILE_FLAGS = {u: ['-fno-slp-vectorize'] for u in WCT_UNITS}
 
 
 def source_digest():
@@ -40,14 +45,16 @@ def build(force=False, verbose=True):
     if not force and not needs_build():
         return LIB
     hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
-    objs = []
-    for src in SOURCES:
-        obj = os.path.join(CSRC, src.replace('.hip', '.o'))
+    objs = [os.path.join(CSRC, src.replace('.hip', '.o')) for src in SOURCES]
+
+    def compile_unit(src, obj):
         cmd = [hipcc] + FLAGS + FILE_FLAGS.get(src, []) + ['-c', os.path.join(CSRC, src), '-o', obj]
         if verbose:
             print(' '.join(cmd), flush=True)
         subprocess.check_call(cmd)
-        objs.append(obj)
+
+    with ThreadPoolExecutor(min(16, len(SOURCES))) as pool:     # (a fixed bound, never the CPU count of the machine)
+        list(pool.map(compile_unit, SOURCES, objs))
     cmd = [hipcc, '--offload-arch=gfx950', '-shared', '-fPIC', '-o', LIB] + objs
     if verbose:
         print(' '.join(cmd), flush=True)

@@ -144,7 +144,7 @@ int launch_f32_to_u8(const float* x, uint8_t* y, size_t n, hipStream_t s);      
 int launch_f32_to_f16(const float* x, half_t* y, size_t n, hipStream_t s);
 int launch_f16_to_f32(const half_t* x, float* y, size_t n, hipStream_t s);
 
-// ---- wct.hip --------------------------------------------------------------
+// ---- the whiten-colour transform: stats_gemm.hip, eigh.hip, spectral.hip, wct.hip, mask.hip, style_swap.hip ----
 // generic fp32 GEMM on v_mfma_f32_32x32x2_f32:  D[m][n] = sum_k A(m,k) B(k,n)
 // A element (m,k): a_kmajor ? A[k*lda+m] : A[m*lda+k];  B element (k,n): b_kmajor ? B[k*ldb+n] : B[n*ldb+k]
 struct GemmArgs {
@@ -171,7 +171,7 @@ struct GemmArgs {
   // blend and the block merges max |M| into mabs[batch] (bit patterns of non-negative floats; zeroed by an earlier kernel)
   int blend; float alpha; unsigned* mabs;
   // refresh products (round 5, launch_wct): run for the batches whose matrix needs it, a no-op for the others.  mask_diag: the
-  // [nbatch][M][M] matrices whose DIAGONAL decides (refresh_needed, csrc/wct.hip); every block of a batch evaluates it the same way
+  // [nbatch][M][M] matrices whose DIAGONAL decides (refresh_needed, csrc/stats_gemm.hip); every block of a batch evaluates it the same way
   // and block (0, 0) stores it in mask_out[batch].  mask_in: a mask stored by an earlier launch.
   const float* mask_diag; size_t s_mask; int* mask_out; const int* mask_in;
 };

@@ -1,8 +1,8 @@
-// Device-side pieces of the batched block-Jacobi eigensolver (K5) that are shared by the kernels of wct.hip and by the
+// Device-side pieces of the batched block-Jacobi eigensolver (K5) that are shared by the kernels of eigh.hip and by the
 // CPU lane-emulation test (tests/emul): the solver's state words, the pairing schedule, the rotation, the generic
 // LDS-image rotation sets, the argument block of the look-ahead launches and the round-4 register-resident pair problem
 // (namespace r4).  Device code only: nothing here touches the HIP runtime API.  The includer provides the vector typedefs
-// of common.h (wct.hip includes that first; the emulation brings its own prelude, tests/emul/hip_emul.h).
+// of common.h (eigh.hip includes that first; the emulation brings its own prelude, tests/emul/hip_emul.h).
 #pragma once
 #include <type_traits>
 #include <utility>

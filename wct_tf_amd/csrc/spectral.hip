@@ -1,0 +1,453 @@
+// K6 of the whiten-colour transform (the stage list: wct.hip): the spectral functions of the solved covariances, one matrix
+// at a time (style-swap) and for all matrices of a level in merged launches (the transforms), and the refresh before them.
+#include "wct_stages.h"
+
+// ---------------------------------------------------------------------------
+// K6: spectral functions with the reference cut-off
+// ---------------------------------------------------------------------------
+// First-order completion of the matrix function (Daleckii-Krein): the sweeps stop with A = D + E, E a small
+// off-diagonal residual (|e_pq| up to ~tol sqrt(d_p d_q)), and V^T A0 V = D + E holds to round-off, so
+//   f(A0) = V f(D + E) V^T = V (f(D) + F o E) V^T + O(|E|^2),  F_pq = (f(d_p) - f(d_q)) / (d_p - d_q).
+// Using G = f(D) + F o E instead of f(D) squares the error the residual leaves in the transform (measured on the
+// level features of a 512x512 frame: 2.7e-3 -> see DESIGN) and lets the sweeps stop a whole sweep earlier.
+// f is the reference's spectral function INCLUDING its cut-off (ops.py:68-77 / 112-127): f(l) = 0 for l <= 1e-5,
+// else l^-1/2 | l^1/2 (wct_tf), (l + eps)^-1/2 | (l + eps)^1/2 (wct_np).  The divided differences of l^+-1/2 have
+// closed forms without cancellation: -1 / (sa sb (sa + sb)) and 1 / (sa + sb) with sa = sqrt(a), sb = sqrt(b);
+// across the cut-off (one eigenvalue kept, one dropped) F_pq = f(d_kept) / (d_kept - d_dropped).
+// `kind`: 0 whitening gain l^-1/2, 1 colouring gain l^1/2.   G [nmat][C][C], matrix m of A / G at stride `stride`.
+// Round 6: the expansion is one in the squared cosines e^2 / (d_p d_q), and it is only used where it converges.  The sweeps may
+// stop with pairs that are NOT resolved: the rounding-noise diagonals of a rank-deficient covariance (N < C pixels) never settle
+// against each other (the lenient rule of jacobi_check_end lets such a matrix go), and when the feature scale puts that noise
+// above the 1e-5 cut-off -- 1e-7 ||cov|| ~ 1 at features of ~1e3 -- those diagonals are KEPT, with squared cosines of order one
+// and more among them.  The second divided differences then grow like f(a) e^2 / (2 d_a d_b) per term: measured on
+// C = 256, 84 / 78 pixels, features ~1e3 (tools/probe/r06_fuzz_case.py, profiles/r06_noise_block.txt) the transform was off by
+// 0.14 .. 11.5 (six seeds of six).  A pair with e^2 > d_p d_q / 4 takes no part in either order of the completion: f of its two
+// diagonals stands alone (0.02 .. 0.15 on the same six; the rest is spectral_cut's, below).  On a matrix that met the stop test
+// no pair is near that bound (the test bounds the mean over the rows of a row's SUM of squared cosines by 1.6e-3), so every
+// converged result keeps its bits.
+__device__ __forceinline__ bool pair_resolved(float dp, float dq, float e) { return e * e <= 0.25f * dp * dq; }
+
+// The cut-off of ONE matrix (round 6).  The reference drops eigenvalues <= 1e-5 (ops.py:68-69 / 112,125).  A covariance is positive
+// semi-definite in exact arithmetic, so a NEGATIVE diagonal of the rotated matrix is rounding noise and nothing else, and the most
+// negative one, -r, measures the noise of this evaluation on this matrix (N < C pixels: C - N + 1 directions of exact zeros come
+// out as a cluster symmetric around 0, radius r ~ 1.5e-7 ||cov||).  A positive diagonal no larger than 2 r is the same noise: it is
+// dropped like the exact zero it stands for -- cut = max(1e-5, 2 r).  Below a feature scale of ~10 (r < 5e-6) this is the
+// reference's cut-off unchanged; above it the noise directions, which the absolute 1e-5 would keep with gains (d + eps)^-1/2
+// that dwarf the signal's, no longer enter.  Why it is needed (profiles/r06_noise_block.txt: C = 256, 84 / 78 pixels, features
+// ~1e3, six seeds; error of the transform against the float64 oracle, the reference's own float32 evaluation 1.3e-4 .. 7e-4):
+// diagonal gains only 3.5e-3 .. 1.9e-2, with the first-order completion 5e-2 .. 1.3, with the second-order one 0.35 .. 16.
+// The kept count stays inside the band the parity tests accept as the reference's (tests/test_gpu_fuzz.py: eigenvalues within
+// 2e-6 + 1e-6 ||cov|| of 1e-5 may fall on either side in float32).  Block-wide (256 threads), `red`: 4 floats of LDS.
+constexpr float SPECTRAL_NOISE_CUT = 2.f;
+__device__ __forceinline__ float spectral_cut(const float* Am, int C, int tid, float* red) {
+  float mn = 0.f;
+  for (int i = tid; i < C; i += 256) mn = fminf(mn, Am[(size_t)i * C + i]);
+  for (int o = 32; o > 0; o >>= 1) mn = fminf(mn, __shfl_xor(mn, o, 64));
+  if ((tid & 63) == 0) red[tid >> 6] = mn;
+  __syncthreads();
+  mn = fminf(fminf(red[0], red[1]), fminf(red[2], red[3]));
+  return fmaxf(1e-5f, -SPECTRAL_NOISE_CUT * mn);
+}
+
+__device__ __forceinline__ float spectral_entry(float dp, float dq, float e, bool diag, int kind, float shift, float cut) {
+  const bool kp = dp > cut, kq = dq > cut;
+  if (diag) return kp ? (kind == 0 ? 1.f / sqrtf(dp + shift) : sqrtf(dp + shift)) : 0.f;
+  if (!kp && !kq) return 0.f;
+  if (kp && kq) {
+    if (!pair_resolved(dp, dq, e)) return 0.f;
+    const float sa = sqrtf(dp + shift), sb = sqrtf(dq + shift);
+    return kind == 0 ? -e / (sa * sb * (sa + sb)) : e / (sa + sb);
+  }
+  const float dk = kp ? dp : dq, dd = kp ? dq : dp;
+  const float fk = kind == 0 ? 1.f / sqrtf(dk + shift) : sqrtf(dk + shift);
+  // across the cut-off f jumps, and the first-order term e f_k / (d_k - d_d) is only the expansion of
+  // (f_k - 0) sin(theta) cos(theta) for a small rotation angle theta ~ e / gap: it can never exceed f_k / 2.  A residual
+  // that is not small against the gap (two eigenvalues within a per cent of 1e-5) is clamped to that bound
+  return e * fk / fmaxf(dk - dd, 2.f * fabsf(e));
+}
+
+// The three elementwise passes over a matrix in 64 x 64 TILES (round 4).  Written element by element (round 3) every
+// output read two diagonal entries (a gather with stride C + 1: one cache line per thread) and the mirrored entry
+// (a column walk), ~1.4 ms per 32-pair step for three kernels that move 100 MB each.  A block now parks the two
+// diagonal segments of its tile and the MIRROR tile in LDS (rows loaded coalesced, read transposed), so every global
+// access is a coalesced 16-byte row piece.  Per element the arithmetic is what it was, in the same order.
+struct SpectralTile {
+  float dp[64], dq[64];          // diagonal entries of the tile's rows / columns
+  float mt[64][65];              // mirror tile: mt[c][r] = A[q0 + c][p0 + r]
+};
+__device__ __forceinline__ void spectral_tile_load(SpectralTile& t, const float* Am, int C, int p0, int q0, int tid) {
+  if (tid < 64) t.dp[tid] = p0 + tid < C ? Am[(size_t)(p0 + tid) * C + p0 + tid] : 0.f;
+  else if (tid < 128) t.dq[tid - 64] = q0 + tid - 64 < C ? Am[(size_t)(q0 + tid - 64) * C + q0 + tid - 64] : 0.f;
+  const int ty = tid >> 4, tx = tid & 15;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int r = q0 + ty * 4 + i, c = p0 + tx * 4;
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    if (r < C && c < C) v = *reinterpret_cast<const f32x4*>(Am + (size_t)r * C + c);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) t.mt[ty * 4 + i][tx * 4 + j] = v[j];
+  }
+}
+
+// grid (C / 64, C / 64, nbatch): tile rows p0 = 64 blockIdx.y, columns q0 = 64 blockIdx.x
+__global__ __launch_bounds__(256) void spectral_matrix_kernel(const float* A, float* G, int C, size_t stride, int kind, float shift, int correct) {
+  __shared__ SpectralTile t;
+  const int m = blockIdx.z, p0 = blockIdx.y * 64, q0 = blockIdx.x * 64, tid = threadIdx.x;
+  __shared__ float cutred[4];
+  const float* Am = A + m * stride;
+  float* Gm = G + m * stride;
+  const float cut = spectral_cut(Am, C, tid, cutred);
+  spectral_tile_load(t, Am, C, p0, q0, tid);
+  __syncthreads();
+  const int ty = tid >> 4, tx = tid & 15;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int pl = ty * 4 + i, p = p0 + pl, q = q0 + tx * 4;
+    if (p >= C || q >= C) continue;
+    const f32x4 a = *reinterpret_cast<const f32x4*>(Am + (size_t)p * C + q);
+    f32x4 g;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      // the two triangles agree to round-off; their mean keeps G exactly symmetric
+      const float e = correct ? 0.5f * (a[j] + t.mt[tx * 4 + j][pl]) : 0.f;
+      g[j] = spectral_entry(t.dp[pl], t.dq[tx * 4 + j], e, p == q + j, kind, shift, cut);
+    }
+    *reinterpret_cast<f32x4*>(Gm + (size_t)p * C + q) = g;
+  }
+}
+
+// Second-order term of the same expansion (round 3):  (L2)_pq = sum_k f[d_p, d_k, d_q] E_pk E_kq  with the second divided
+// differences of the spectral functions, which have closed forms without cancellation (sa = sqrt(a + shift) ...):
+//   l^+1/2:  f[a,b,c] = -1 / ((sa+sb)(sb+sc)(sa+sc))
+//   l^-1/2:  f[a,b,c] = (sa+sb+sc) / (sa sb sc (sa+sb)(sb+sc)(sa+sc))
+// and both SEPARATE into matrix products of elementwise-scaled copies of E:  with N_pk = E_pk / (s_p + s_k),
+// R_pk = E_pk / s_k, P_pk = N_pk / s_k,
+//   l^+1/2:  L2 = -(N N) o 1/(s_p + s_q)
+//   l^-1/2:  L2 = ( sym(R N) + (s_p + s_q)/2 (P N) ) o 1/(s_p s_q (s_p + s_q))      (P N = N diag(1/s) N is symmetric)
+// (checked against an exact eigendecomposition in NumPy: the error of f(D + E) drops from ~r^2 to ~r^3).  Only the block
+// of kept eigenvalues takes part: a dropped direction's couplings are bounded by sqrt(1e-5 d_p) tol and enter squared.
+// It lets the sweeps stop one sweep earlier for the same transform error (profiles/r03_eig_calibration.txt).
+__global__ __launch_bounds__(256) void spectral_prep2_kernel(const float* A, float* N, float* R, float* Pm, int C, size_t stride, int kind, float shift) {
+  __shared__ SpectralTile t;
+  const int m = blockIdx.z, p0 = blockIdx.y * 64, q0 = blockIdx.x * 64, tid = threadIdx.x;
+  const size_t cc = (size_t)C * C;
+  __shared__ float cutred[4];
+  const float* Am = A + m * stride;
+  const float cut = spectral_cut(Am, C, tid, cutred);
+  spectral_tile_load(t, Am, C, p0, q0, tid);
+  __syncthreads();
+  const int ty = tid >> 4, tx = tid & 15;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int pl = ty * 4 + i, p = p0 + pl, k0 = q0 + tx * 4;
+    if (p >= C || k0 >= C) continue;
+    const f32x4 a = *reinterpret_cast<const f32x4*>(Am + (size_t)p * C + k0);
+    const float dp = t.dp[pl];
+    f32x4 n4 = {0.f, 0.f, 0.f, 0.f}, r4 = n4, p4 = n4;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float dk = t.dq[tx * 4 + j];
+      const float e = 0.5f * (a[j] + t.mt[tx * 4 + j][pl]);
+      if (p != k0 + j && dp > cut && dk > cut && pair_resolved(dp, dk, e)) {
+        const float sp = sqrtf(dp + shift), sk = sqrtf(dk + shift);
+        n4[j] = e / (sp + sk);
+        r4[j] = e / sk;
+        p4[j] = n4[j] / sk;
+      }
+    }
+    const size_t o = m * cc + (size_t)p * C + k0;
+    *reinterpret_cast<f32x4*>(N + o) = n4;
+    if (kind == 0) { *reinterpret_cast<f32x4*>(R + o) = r4; *reinterpret_cast<f32x4*>(Pm + o) = p4; }
+  }
+}
+
+__global__ __launch_bounds__(256) void spectral_add2_kernel(const float* A, float* G, const float* X1, const float* X2, int C, size_t stride, int kind, float shift) {
+  __shared__ float dps[64], dqs[64];
+  __shared__ float x1t[64][65], x2t[64][65];       // mirror tiles of X1 (kind 0 only), X2
+  const int m = blockIdx.z, p0 = blockIdx.y * 64, q0 = blockIdx.x * 64, tid = threadIdx.x;
+  const size_t cc = (size_t)C * C;
+  const float* Am = A + m * stride;
+  float* Gm = G + m * stride;
+  // a matrix with an eigenvalue within half a decade of the cut-off keeps the first-order completion and the old stop
+  // threshold (jacobi_resid_kernel weighs its residual accordingly): around the cut-off sit the noise directions of
+  // rank-deficient covariances, whose mutual couplings never become small, and a second-order sum over them is noise
+  int near = 0;
+  for (int i = tid; i < C; i += 256) {
+    const float d = fabsf(Am[(size_t)i * C + i]);
+    near |= (d > 3.3e-6f) & (d < 3e-5f);
+  }
+  if (__syncthreads_or(near)) return;
+  __shared__ float cutred[4];
+  const float cut = spectral_cut(Am, C, tid, cutred);
+  if (tid < 64) dps[tid] = p0 + tid < C ? Am[(size_t)(p0 + tid) * C + p0 + tid] : 0.f;
+  else if (tid < 128) dqs[tid - 64] = q0 + tid - 64 < C ? Am[(size_t)(q0 + tid - 64) * C + q0 + tid - 64] : 0.f;
+  const int ty = tid >> 4, tx = tid & 15;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int r = q0 + ty * 4 + i, c = p0 + tx * 4;
+    f32x4 v1 = {0.f, 0.f, 0.f, 0.f}, v2 = v1;
+    if (r < C && c < C) {
+      v2 = *reinterpret_cast<const f32x4*>(X2 + m * cc + (size_t)r * C + c);
+      if (kind == 0) v1 = *reinterpret_cast<const f32x4*>(X1 + m * cc + (size_t)r * C + c);
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { x2t[ty * 4 + i][tx * 4 + j] = v2[j]; x1t[ty * 4 + i][tx * 4 + j] = v1[j]; }
+  }
+  __syncthreads();
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int pl = ty * 4 + i, p = p0 + pl, q = q0 + tx * 4;
+    if (p >= C || q >= C) continue;
+    const size_t o = (size_t)p * C + q;
+    const f32x4 x2 = *reinterpret_cast<const f32x4*>(X2 + m * cc + o);
+    f32x4 x1 = {0.f, 0.f, 0.f, 0.f};
+    if (kind == 0) x1 = *reinterpret_cast<const f32x4*>(X1 + m * cc + o);
+    f32x4 g = *reinterpret_cast<const f32x4*>(Gm + o);
+    const float dp = dps[pl];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float dq = dqs[tx * 4 + j];
+      if (!(dp > cut && dq > cut)) continue;
+      const float sp = sqrtf(dp + shift), sq = sqrtf(dq + shift);
+      float l2;
+      if (kind == 1) l2 = -0.5f * (x2[j] + x2t[tx * 4 + j][pl]) / (sp + sq);
+      else l2 = (0.5f * (x1[j] + x1t[tx * 4 + j][pl]) + 0.25f * (sp + sq) * (x2[j] + x2t[tx * 4 + j][pl])) / (sp * sq * (sp + sq));
+      g[j] += l2;
+    }
+    *reinterpret_cast<f32x4*>(Gm + o) = g;
+  }
+}
+
+// ---- round 5: the transform tail in MERGED launches.  Until round 4 every level ran the chain spectral_matrix -> prep2 ->
+// products -> add2 -> V G -> (V G) V^T twice, content side then style side (13 launches), then T = Tcs Tw, a memset, the blend
+// and the apply: 17 launches per level, most of them a few microseconds of work on half the matrices.  Here one launch of each
+// kind covers all 2P matrices of the level (matrix m = 2 pair + side; kind = m & 1: 0 whitening, 1 colouring), the first-order
+// matrix and the second-order operands come out of ONE pass over the tile, the blend rides on the epilogue of T = Tcs Tw
+// (gemm_f32_kernel), and the pass that opens the chain also clears mabs and writes the bias vector: 8 launches per level.
+// The per-element arithmetic exists TWICE and must be kept in step by hand (sharing it as inlined tile bodies was tried when
+// the units were split: hipcc then schedules the two _all kernels differently, so the copies stayed).  What to compare, as text:
+//   * spectral_open_all_kernel's tile loop = spectral_matrix_kernel's (e, spectral_entry) + spectral_prep2_kernel's (the
+//     condition under `second`, n4 / r4 / p4), with em for e, a.shift for shift, a.correct for correct;
+//   * spectral_add2_all_kernel from `int near = 0;` to its end = spectral_add2_kernel from the same line, with a.shift for
+//     shift and X1 / X2 already offset to the matrix (X1 at pair * cc there, m * cc here);
+//   * spectral_cut, spectral_entry, pair_resolved and spectral_tile_load are shared already.
+// tests/test_gpu_ops.py (style-swap against the oracle) and the transform tests cover one copy each, not their agreement.
+struct SpecAllArgs {
+  const float* A;            // [2P][C][C] rotated covariances (diagonal = eigenvalues, off-diagonal = residual)
+  float* G;                  // [2P][C][C]
+  float *N, *R, *Pm;         // N [2P][C][C]; R, Pm [P][C][C] (whitening side only)
+  const float *X1, *X2;      // add2: X1 [P][C][C], X2 [2P][C][C]
+  int C; float shift; int correct, second, shared_style;
+  unsigned* mabs; const float* mean; float* bias; float alpha; int mode;     // per-pair housekeeping of the opening pass
+};
+
+__global__ __launch_bounds__(256) void spectral_open_all_kernel(SpecAllArgs a) {
+  __shared__ SpectralTile t;
+  const int m = blockIdx.z, p0 = blockIdx.y * 64, q0 = blockIdx.x * 64, tid = threadIdx.x;
+  const int C = a.C, kind = m & 1, pair = m >> 1;
+  const size_t cc = (size_t)C * C;
+  if (kind == 0 && blockIdx.x == 0 && blockIdx.y == 0) {
+    // what blend_matrix_kernel did besides the blend: bias = alpha ms (+ (1 - alpha) mc in tf mode); and mabs starts at 0
+    if (tid == 0) a.mabs[pair] = 0u;
+    const float* mp = a.mean + (size_t)(a.shared_style == WCT_SKIP_MIX ? 0 : pair) * 2 * C;     // (a mix: the one content)
+    const float* ms = a.mean + (size_t)(a.shared_style == 1 ? 0 : pair) * 2 * C + C;
+    for (int i = tid; i < C; i += 256) {
+      float b = a.alpha * ms[i];
+      if (a.mode == WCT_MODE_TF) b += (1.f - a.alpha) * mp[i];
+      a.bias[pair * C + i] = b;
+    }
+  }
+  if (skip_style_mat(m, a.shared_style)) return;
+  __shared__ float cutred[4];
+  const float* Am = a.A + m * cc;
+  const float cut = spectral_cut(Am, C, tid, cutred);
+  spectral_tile_load(t, Am, C, p0, q0, tid);
+  __syncthreads();
+  const int ty = tid >> 4, tx = tid & 15;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int pl = ty * 4 + i, p = p0 + pl, q = q0 + tx * 4;
+    if (p >= C || q >= C) continue;
+    const f32x4 av = *reinterpret_cast<const f32x4*>(Am + (size_t)p * C + q);
+    const float dp = t.dp[pl];
+    f32x4 g, n4 = {0.f, 0.f, 0.f, 0.f}, r4 = n4, p4 = n4;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float dk = t.dq[tx * 4 + j];
+      const float em = 0.5f * (av[j] + t.mt[tx * 4 + j][pl]);      // the two triangles agree to round-off; their mean keeps G symmetric
+      g[j] = spectral_entry(dp, dk, a.correct ? em : 0.f, p == q + j, kind, a.shift, cut);
+      if (a.second && p != q + j && dp > cut && dk > cut && pair_resolved(dp, dk, em)) {
+        const float sp = sqrtf(dp + a.shift), sk = sqrtf(dk + a.shift);
+        n4[j] = em / (sp + sk);
+        r4[j] = em / sk;
+        p4[j] = n4[j] / sk;
+      }
+    }
+    const size_t o = (size_t)p * C + q;
+    *reinterpret_cast<f32x4*>(a.G + m * cc + o) = g;
+    if (a.second) {
+      *reinterpret_cast<f32x4*>(a.N + m * cc + o) = n4;
+      if (kind == 0) { *reinterpret_cast<f32x4*>(a.R + pair * cc + o) = r4; *reinterpret_cast<f32x4*>(a.Pm + pair * cc + o) = p4; }
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void spectral_add2_all_kernel(SpecAllArgs a) {
+  __shared__ float dps[64], dqs[64];
+  __shared__ float x1t[64][65], x2t[64][65];       // mirror tiles of X1 (kind 0 only), X2
+  const int m = blockIdx.z, p0 = blockIdx.y * 64, q0 = blockIdx.x * 64, tid = threadIdx.x;
+  if (skip_style_mat(m, a.shared_style)) return;
+  const int C = a.C, kind = m & 1;
+  const size_t cc = (size_t)C * C;
+  const float* Am = a.A + m * cc;
+  float* Gm = a.G + m * cc;
+  const float* X2 = a.X2 + m * cc;
+  const float* X1 = a.X1 + (size_t)(m >> 1) * cc;
+  int near = 0;                                     // (see spectral_add2_kernel)
+  for (int i = tid; i < C; i += 256) {
+    const float d = fabsf(Am[(size_t)i * C + i]);
+    near |= (d > 3.3e-6f) & (d < 3e-5f);
+  }
+  if (__syncthreads_or(near)) return;
+  __shared__ float cutred[4];
+  const float cut = spectral_cut(Am, C, tid, cutred);
+  if (tid < 64) dps[tid] = p0 + tid < C ? Am[(size_t)(p0 + tid) * C + p0 + tid] : 0.f;
+  else if (tid < 128) dqs[tid - 64] = q0 + tid - 64 < C ? Am[(size_t)(q0 + tid - 64) * C + q0 + tid - 64] : 0.f;
+  const int ty = tid >> 4, tx = tid & 15;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int r = q0 + ty * 4 + i, c = p0 + tx * 4;
+    f32x4 v1 = {0.f, 0.f, 0.f, 0.f}, v2 = v1;
+    if (r < C && c < C) {
+      v2 = *reinterpret_cast<const f32x4*>(X2 + (size_t)r * C + c);
+      if (kind == 0) v1 = *reinterpret_cast<const f32x4*>(X1 + (size_t)r * C + c);
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { x2t[ty * 4 + i][tx * 4 + j] = v2[j]; x1t[ty * 4 + i][tx * 4 + j] = v1[j]; }
+  }
+  __syncthreads();
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int pl = ty * 4 + i, p = p0 + pl, q = q0 + tx * 4;
+    if (p >= C || q >= C) continue;
+    const size_t o = (size_t)p * C + q;
+    const f32x4 x2 = *reinterpret_cast<const f32x4*>(X2 + o);
+    f32x4 x1 = {0.f, 0.f, 0.f, 0.f};
+    if (kind == 0) x1 = *reinterpret_cast<const f32x4*>(X1 + o);
+    f32x4 g = *reinterpret_cast<const f32x4*>(Gm + o);
+    const float dp = dps[pl];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float dq = dqs[tx * 4 + j];
+      if (!(dp > cut && dq > cut)) continue;
+      const float sp = sqrtf(dp + a.shift), sq = sqrtf(dq + a.shift);
+      float l2;
+      if (kind == 1) l2 = -0.5f * (x2[j] + x2t[tx * 4 + j][pl]) / (sp + sq);
+      else l2 = (0.5f * (x1[j] + x1t[tx * 4 + j][pl]) + 0.25f * (sp + sq) * (x2[j] + x2t[tx * 4 + j][pl])) / (sp * sq * (sp + sq));
+      g[j] += l2;
+    }
+    *reinterpret_cast<f32x4*>(Gm + o) = g;
+  }
+}
+
+// out[b] = V[b] G[b] V[b]^T for nbatch matrices (strides in elements); X: scratch of the same shape as G
+// scratch2: 5 * nbatch * C * C floats for the second-order completion (or null: first order at most)
+int launch_spectral_function(const float* A, const float* V, float* G, float* X, float* out, int C, int nbatch,
+                                    size_t stride, size_t out_stride, int kind, float shift, hipStream_t s, float* scratch2) {
+  const size_t cc = (size_t)C * C;
+  const dim3 tiles(cdiv(C, 64), cdiv(C, 64), nbatch);
+  hipLaunchKernelGGL(spectral_matrix_kernel, tiles, dim3(256), 0, s, A, G, C, stride, kind, shift, EIG_CORRECT);
+  HIP_TRY(hipGetLastError());
+  if (scratch2 && EIG_CORRECT >= 2) {
+    float* N = scratch2; float* R = N + nbatch * cc; float* Pm = R + nbatch * cc; float* X1 = Pm + nbatch * cc; float* X2 = X1 + nbatch * cc;
+    hipLaunchKernelGGL(spectral_prep2_kernel, tiles, dim3(256), 0, s, A, N, R, Pm, C, stride, kind, shift);
+    HIP_TRY(hipGetLastError());
+    GemmArgs a = {};   // X2 = (kind 1: N, kind 0: P) N
+    a.A = kind == 1 ? N : Pm; a.lda = C; a.a_kmajor = 0; a.B = N; a.ldb = C; a.b_kmajor = 1; a.sA = a.sB = cc;
+    a.M = C; a.N = C; a.K = C; a.ksplit = C; a.out32 = X2; a.ldo = C; a.s_out = cc;
+    int rc2 = launch_gemm(a, 1, nbatch, s);
+    if (rc2) return rc2;
+    if (kind == 0) {
+      a.A = R; a.out32 = X1;   // X1 = R N
+      if ((rc2 = launch_gemm(a, 1, nbatch, s))) return rc2;
+    }
+    hipLaunchKernelGGL(spectral_add2_kernel, tiles, dim3(256), 0, s, A, G, X1, X2, C, stride, kind, shift);
+    HIP_TRY(hipGetLastError());
+  }
+  GemmArgs g = {};   // X = V G
+  g.A = V; g.lda = C; g.a_kmajor = 0; g.B = G; g.ldb = C; g.b_kmajor = 1; g.sA = g.sB = stride;
+  g.M = C; g.N = C; g.K = C; g.ksplit = C; g.out32 = X; g.ldo = C; g.s_out = stride;
+  int rc = launch_gemm(g, 1, nbatch, s);
+  if (rc) return rc;
+  GemmArgs h = {};   // out = X V^T
+  h.A = X; h.lda = C; h.a_kmajor = 0; h.B = V; h.ldb = C; h.b_kmajor = 0; h.sA = h.sB = stride;
+  h.M = C; h.N = C; h.K = C; h.ksplit = C; h.out32 = out; h.ldo = C; h.s_out = out_stride;
+  return launch_gemm(h, 1, nbatch, s);
+}
+
+// refresh (see refresh_needed): X = A0 V, then A <- V^T X, for the matrices whose kept spectrum reaches 4 decades below their
+// norm; the others' blocks exit at once.  Before ANY spectral function of the tracked (A, V): launch_wct's apply stage and the
+// three of launch_style_swap (relu5_1, C = 512: every input of 352 x 352 or smaller has N < C -- the rank-deficient case).
+// always: every matrix, whatever its spectrum (measured for style-swap when the solver's tile update moved to split fp16: the
+// 3 of 900 patch matches that flipped on the 32 x 32 test case flipped with the rotated matrix recomputed as well -- it is V, not
+// the tracked matrix, that carries the difference; the switch stays for experiments).
+int launch_refresh(const WctCarve& w, int C, int P, int shared_style, hipStream_t s, bool always) {
+  const size_t cc = (size_t)C * C;
+  int rc;
+  GemmArgs r1 = {};
+  r1.A = w.A0; r1.lda = C; r1.a_kmajor = 0; r1.B = w.V; r1.ldb = C; r1.b_kmajor = 1; r1.sA = r1.sB = cc; r1.skip_shared = shared_style;
+  r1.M = C; r1.N = C; r1.K = C; r1.ksplit = C; r1.out32 = w.X; r1.ldo = C; r1.s_out = cc;
+  if (!always) { r1.mask_diag = w.A; r1.s_mask = cc; r1.mask_out = w.refresh; }
+  if ((rc = launch_gemm(r1, 1, 2 * P, s))) return rc;
+  GemmArgs r2 = {};
+  r2.A = w.V; r2.lda = C; r2.a_kmajor = 1; r2.B = w.X; r2.ldb = C; r2.b_kmajor = 1; r2.sA = r2.sB = cc; r2.skip_shared = shared_style;
+  r2.M = C; r2.N = C; r2.K = C; r2.ksplit = C; r2.out32 = w.A; r2.ldo = C; r2.s_out = cc;
+  if (!always) r2.mask_in = w.refresh;
+  rc = launch_gemm(r2, 1, 2 * P, s);
+  return rc;
+}
+
+// The spectral tail of a level, all 2P matrices in merged launches: Tw / Tcs [m] = V f(A) V^T (whitening for the even matrices,
+// colouring for the odd ones), plus the bias vectors and cleared mabs words of the opening pass.  nwhite: the pairs whose
+// whitening side is live (P; 1 for a style mix, whose content is matrix 0 alone).
+int launch_spectral_tail(const WctCarve& w, int C, int P, float alpha, int mode, float eps_in, int shared_style, int nwhite,
+                                hipStream_t s) {
+  int rc;
+  const size_t cc = (size_t)C * C;
+  // Tw = Vc f_c(Ac) Vc^T, Tcs = Vs f_s(As) Vs^T with the first- and second-order completion of f on the residual
+  // off-diagonals; the wct_np semantics shift the kept eigenvalues by eps inside the gains (ops.py:114,127), wct_tf does not.
+  // One launch of each kind over all 2P matrices of the level (see spectral_open_all_kernel).
+  const float shift = mode == WCT_MODE_NP ? (eps_in >= 0.f ? eps_in : 1e-5f) : 0.f;
+  const int second = EIG_CORRECT >= 2;
+  const dim3 tiles(cdiv(C, 64), cdiv(C, 64), 2 * P);
+  if ((rc = launch_refresh(w, C, P, shared_style, s))) return rc;
+  SpecAllArgs sa = {};
+  sa.A = w.A; sa.G = w.G; sa.C = C; sa.shift = shift; sa.correct = EIG_CORRECT; sa.second = second; sa.shared_style = shared_style;
+  sa.N = w.S2; float* X2 = sa.N + 2 * P * cc; sa.R = X2 + 2 * P * cc; sa.Pm = sa.R + P * cc; float* X1 = sa.Pm + P * cc;
+  sa.X1 = X1; sa.X2 = X2;
+  sa.mabs = w.mabs; sa.mean = w.mean; sa.bias = w.bias; sa.alpha = alpha; sa.mode = mode;
+  hipLaunchKernelGGL(spectral_open_all_kernel, tiles, dim3(256), 0, s, sa);
+  HIP_TRY(hipGetLastError());
+  if (second) {
+    GemmArgs a = {};   // X2[m] = (colouring: N[m], whitening: Pm[pair]) . N[m]
+    a.A = sa.Pm; a.sA = cc; a.A_odd = sa.N + cc; a.sA_odd = 2 * cc; a.lda = C; a.a_kmajor = 0;
+    a.B = sa.N; a.ldb = C; a.b_kmajor = 1; a.sB = cc; a.skip_shared = shared_style;
+    a.M = C; a.N = C; a.K = C; a.ksplit = C; a.out32 = X2; a.ldo = C; a.s_out = cc;
+    if ((rc = launch_gemm(a, 1, 2 * P, s))) return rc;
+    GemmArgs b = {};   // X1[pair] = R[pair] . N[2 pair]   (whitening side only)
+    b.A = sa.R; b.sA = cc; b.lda = C; b.a_kmajor = 0; b.B = sa.N; b.ldb = C; b.b_kmajor = 1; b.sB = 2 * cc;
+    b.M = C; b.N = C; b.K = C; b.ksplit = C; b.out32 = X1; b.ldo = C; b.s_out = cc;
+    if ((rc = launch_gemm(b, 1, nwhite, s))) return rc;
+    hipLaunchKernelGGL(spectral_add2_all_kernel, tiles, dim3(256), 0, s, sa);
+    HIP_TRY(hipGetLastError());
+  }
+  GemmArgs g = {};   // X[m] = V[m] G[m]
+  g.A = w.V; g.lda = C; g.a_kmajor = 0; g.B = w.G; g.ldb = C; g.b_kmajor = 1; g.sA = g.sB = cc; g.skip_shared = shared_style;
+  g.M = C; g.N = C; g.K = C; g.ksplit = C; g.out32 = w.X; g.ldo = C; g.s_out = cc;
+  if ((rc = launch_gemm(g, 1, 2 * P, s))) return rc;
+  GemmArgs h = {};   // Tw / Tcs [m] = X[m] V[m]^T
+  h.A = w.X; h.lda = C; h.a_kmajor = 0; h.B = w.V; h.ldb = C; h.b_kmajor = 0; h.sA = h.sB = cc; h.skip_shared = shared_style;
+  h.M = C; h.N = C; h.K = C; h.ksplit = C; h.out32 = w.Tw; h.ldo = C; h.s_out = cc;
+  if ((rc = launch_gemm(h, 1, 2 * P, s))) return rc;
+  return WCT_OK;
+}

@@ -422,7 +422,7 @@ int launch_conv_first_dgrad(const float* g, const float* wf, float* gp, int B, i
 // ---------------------------------------------------------------------------
 // Split-operand GEMM for the backward pass: D[m][n] = sum_k A(m,k) B(k,n) / (sa sb) on v_mfma_f32_32x32x16_f16.
 // fp32 operands are scaled by a power of two and split into fp16 hi + lo at staging (22 significand bits, as in
-// the covariance / apply kernels of wct.hip); an operand whose values are exact fp16 numbers (saved activations)
+// the covariance / apply kernels of stats_gemm.hip / wct.hip); an operand whose values are exact fp16 numbers (saved activations)
 // skips its lo half.  A(m,k) = AKM ? A[k*lda+m] : A[m*lda+k];  B(k,n) = BKM ? B[k*ldb+n] : B[n*ldb+k].
 // Block = 128 x BN tile, 256 threads = 2x2 waves, K-stage 32, split-K over blockIdx.z (partials reduced in a fixed
 // order by the caller).  The data gradient runs <0,1> (rows of the im2col'ed gradient x transposed weights), the

@@ -1,0 +1,102 @@
+// What the translation units of the whiten-colour transform share among themselves -- stats_gemm.hip (K3, the GEMM, K4),
+// eigh.hip (K5), spectral.hip (K6), wct.hip (K7, the carve, the plans, the transforms), mask.hip, style_swap.hip.  Private to
+// those units: api.hip sees common.h alone.  Every kernel lives in ONE unit, behind the launcher declared here.
+#pragma once
+#include "common.h"
+
+// ---- the matrices of a batch: matrix m = 2 * pair + side (0 content, 1 style) ----------------------------------------------
+// With a shared style (one style image for every pair of the batch: video; shared_style == 1) only pair 0's style matrix
+// (matrix 1) is computed; the style matrices of the other pairs are skipped and their consumers read pair 0's.
+// A style mix (launch_wct_mix; shared_style == WCT_SKIP_MIX) is the mirror image: K styles share ONE content, matrix 0;
+// the content slots 2k of the pairs k >= 1 are skipped.
+constexpr int WCT_SKIP_MIX = 2;
+__device__ __host__ __forceinline__ bool skip_style_mat(int mat, int shared_style) {
+  return shared_style == WCT_SKIP_MIX ? ((mat & 1) == 0 && mat > 0) : (shared_style && (mat & 1) && mat > 1);
+}
+
+// 0: spectral functions of the diagonal only, 1: + first-order completion, 2 (the product): + second-order completion
+constexpr int EIG_CORRECT = 2;
+// residual at which the WCT path stops sweeping.  Calibrated on the level features of a 512x512 frame
+// (profiles/r02_eig_calibration.txt): with r2 the strict measure at the stop, the transform error is ~0.55 sqrt(r2)
+// without the first-order completion and ~0.8 r2 (+ ~3e-5 from the other stages) with it, so 1.5e-2 bounds the
+// completed transform's error by ~1.8e-4 -- five times inside the 1e-3 budget.  0 without the completion.
+constexpr float JACOBI_TOL_FN = 1.5e-2f;
+constexpr float JACOBI_TOL_FN2 = 4e-2f;            // with the second-order completion (profiles/r03_eig_calibration.txt: the transform error
+                                                   // at 4e-2 with it, 3.1e-5 .. 1.3e-4, is what 1.5e-2 gave without it, one sweep later)
+constexpr float JACOBI_TOL_FN_WCT = EIG_CORRECT >= 2 ? JACOBI_TOL_FN2 : (EIG_CORRECT ? JACOBI_TOL_FN : 0.f);   // the one in use
+
+// ---- workspace carving (P independent content/style pairs per call; wct.hip) ----------------------------------------------
+static inline size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
+
+struct WctCarve {
+  float *mean, *var, *stat_partial, *absmax, *scale, *cov_partial, *A, *A0, *V, *d, *G, *X, *S2, *Tw, *Tcs, *T, *M, *bias, *mix;
+  unsigned* mabs; int* refresh;
+  void* jacobi_ws; size_t jacobi_bytes;
+  int nslab, nsplit, ksplit;
+  size_t total;
+};
+
+// the slab count and K-slices of ONE (content, style) pair of Nc and Ns rows: independent of P, as a pair's result must not
+// depend on its batch
+struct PairLayout { int nslab, nsplit, ksplit; };
+PairLayout pair_layout(int C, int Nc, int Ns);
+// P pairs whose per-matrix partial buffers hold lay.nslab slabs / lay.nsplit K-slices
+WctCarve carve(void* base, int C, int P, const PairLayout& lay);
+
+// eps_in < 0 selects the reference defaults: 1e-8 on the covariance diagonal for wct_tf (ops.py:24,45,50); wct_np adds none
+// there (its 1e-5 sits inside the spectral gains, ops.py:92,114,127 -- launch_spectral_tail)
+static inline float cov_eps(int mode, float eps_in) {
+  return mode == WCT_MODE_TF ? (eps_in >= 0.f ? eps_in : 1e-8f) : 0.f;
+}
+
+// blocks of a grid-stride pass over N rows of C channels, 4 channels a thread (the AdaIN applies, the mask gather)
+static inline unsigned rows_grid(size_t N, int C) {
+  const size_t blocks = (N * C / 4 + 255) / 256;
+  return (unsigned)(blocks > 2048 ? 2048 : blocks);
+}
+
+// The slot plan of a per-slot transform (a style mix, spatial control): 2P matrix slots in the pair layout of carve(), each
+// slot's statistics and covariance launched on its own rows with the layout of its own single-pair transform (pair_layout).
+struct SlotPlan {
+  int P, skip, nwhite;                         // pairs; the skip mode (WCT_SKIP_MIX or 0); pairs whose whitening side is live
+  struct Slot { const float* x; int n; PairLayout lay; } slot[2 * WCT_MIX_MAX];   // rows (null while only sizing the
+                                                                                 // workspace), their count (0: skipped), layout
+  const float* u0; const unsigned* umax0;      // slot 0's unit sums from a conv epilogue, or null
+  WctCarve w;
+  size_t total;
+};
+void plan_carve(SlotPlan* sp, void* base, int C);    // the workspace of a plan (wct.hip)
+bool plan_fits(const SlotPlan& sp, int C);           // every slot within the covariance kernel's 32-bit byte offsets
+
+// ---- K7 apply (wct.hip) ------------------------------------------------------------------------------------------------------
+struct ApplyArgs {
+  const float* x; int N; int C;     // content features [P][N][C]
+  const float* mean;                // [2P][C]: content mean of pair p at 2p
+  const float* M; const float* bias;  // [P][C][C], [P][C]
+  const float* xscale;              // [2P]: content scale of pair p at 2p
+  const unsigned* mabs;             // [P] max |M| (float bits)
+  half_t* out16; float* out32;      // [P][N][C], either may be null
+};
+// A masked transform (launch_wct_masked): pair p is the segment of label lab[p] -- rows [seg_off[lab], seg_off[lab + 1]) of the
+// label-compacted content x -- and its row r is stored to row perm[r] of out16 / out32 (the scatter back to pixel order)
+struct ApplySegArgs : ApplyArgs { const int* seg_off; const int* perm; int lab[WCT_MIX_MAX]; };
+
+// ---- stage launchers, by the unit that holds their kernels -----------------------------------------------------------------
+// stats_gemm.hip: means and the fp16 scale (with_var: the variances) of the 2P matrices; their covariances into w.A and w.A0
+// (eps on the diagonal); both for the live slots of a plan, each with its own layout
+int launch_means(const float* content, int Nc, const float* style, int Ns, int C, int P, const WctCarve& w, bool with_var,
+                 int shared_style, hipStream_t s, const WctFeatStats* fs = nullptr);
+int launch_cov(const float* content, int Nc, const float* style, int Ns, int C, int P, const WctCarve& w, float eps, int shared_style,
+               hipStream_t s);
+int launch_plan_stats(const SlotPlan& sp, int C, bool with_var, bool with_cov, float eps, hipStream_t s);
+// eigh.hip: the 2P matrices of w in one batched solve
+int launch_eig_stage(const WctCarve& w, int C, int P, int skip, int u_f16, int* sweeps_dev, int* eig_fail, hipStream_t s);
+// spectral.hip: the refresh of the rotated matrices, the merged spectral tail of a level, one spectral function (style-swap)
+int launch_refresh(const WctCarve& w, int C, int P, int shared_style, hipStream_t s, bool always = false);
+int launch_spectral_tail(const WctCarve& w, int C, int P, float alpha, int mode, float eps_in, int shared_style, int nwhite, hipStream_t s);
+int launch_spectral_function(const float* A, const float* V, float* G, float* X, float* out, int C, int nbatch, size_t stride,
+                             size_t out_stride, int kind, float shift, hipStream_t s, float* scratch2 = nullptr);
+// wct.hip: the blend product M = alpha Tcs Tw + (1 - alpha) I of P pairs; the apply of a masked transform's P segments (the
+// longest has nmax rows)
+int launch_blend(const WctCarve& w, int C, int P, float alpha, int shared_style, hipStream_t s);
+int launch_apply_seg(const ApplySegArgs& a, int nmax, int P, hipStream_t s);
