@@ -212,6 +212,46 @@ int wct_stylize_batch_dev(wct_ctx* ctx, const uint8_t* content_dev, int Hc, int 
                           const int* levels, int n_levels, float alpha, unsigned flags,
                           uint8_t* out_dev);
 
+/* ---- prepared styles: the style side once, any number of contents -------------------------
+ * Every call above takes a style IMAGE and redoes the whole style side from it -- the style encoder pass, the style statistics
+ * and covariance of every level, the style eigendecompositions and colouring matrices -- as the reference does: predict() feeds
+ * the style through the graph once per call (wct.py:70-106), and stylize_video.py calls it once per frame of a video whose style
+ * never changes (stylize_video.py:88-121).  A wct_style is that style side, computed once and owned by the ctx.
+ *
+ * wct_style_prepare: style is an Hs x Ws x 3 host image (uint8, or float32 in [0,1] with WCT_FLAG_IMAGES_F32); levels is the SET
+ *   of relu levels the handle serves (order and repeats do not matter).  Blocking.  The handle keeps the image on the device
+ *   and, per level, a small cache of states -- colouring matrix and style mean (WCT), mean and variance (AdaIN) -- keyed by what
+ *   their bits depend on: the partial-sum layout of the (content, style) pair (it follows the LARGER of the two feature maps)
+ *   and the mode (wct_tf, wct_np, AdaIN).  This call fills the entries for a content as large as the style, in the mode that
+ *   WCT_FLAG_ADAIN / WCT_FLAG_MODE_NP name; a stylize call that needs another key computes it from the kept image in front of its
+ *   content chain, keeps it (4 keys per level, oldest out) and reuses it afterwards.  So one handle serves any content size,
+ *   either mode, AdaIN and every alpha (alpha enters in the blend and the bias only, which are not part of a state).
+ *   If a style eigensolve does not converge: WCT_STATUS_NOCONV and no handle (*out = NULL); a state computed later inside a
+ *   stylize call is checked the same way before it is kept, and that call then returns WCT_STATUS_NOCONV without a frame.
+ * wct_style_free: waits for the ctx stream, then releases the handle; NULL, a freed or a foreign handle is a no-op.
+ *   wct_destroy frees what is left.
+ * wct_stylize_prepared           = wct_stylize's frame, bit for bit, for the same images, levels, alpha and flags;
+ * wct_stylize_prepared_batch_dev = wct_stylize_batch_dev with WCT_FLAG_STYLE_SHARED, bit for bit (asynchronous like it, except
+ *   that a call which has to compute a new state blocks while it does);
+ * wct_stylize_prepared_mix       = wct_stylize_mix, bit for bit (so K = 1 and one-hot weights give wct_stylize's frame): new
+ *   weights for the same K handles cost one content side, one mix of K cached matrices and one apply.
+ * flags: WCT_FLAG_MODE_NP, WCT_FLAG_ADAIN, and WCT_FLAG_IMAGES_F32 for the CONTENT (the style is what it was when prepared).
+ *   WCT_FLAG_SWAP5 is WCT_STATUS_ARG (style-swap needs the style's relu5_1 map and patches, not its moments), and so is
+ *   WCT_FLAG_STYLE_SHARED, as in the mix / masked calls.  The levels of a call (any order, repeats allowed) must all be in the
+ *   handle's set, else WCT_STATUS_ARG.  A handle that is not live in THIS ctx -- freed, or another context's -- is
+ *   WCT_STATUS_STATE; it is recognised by its address and never dereferenced.  A refusal leaves the ctx usable. */
+typedef struct wct_style wct_style;
+int  wct_style_prepare(wct_ctx* ctx, const uint8_t* style, int Hs, int Ws, const int* levels, int n_levels, unsigned flags,
+                       wct_style** out);
+void wct_style_free(wct_ctx* ctx, wct_style* style);
+int  wct_stylize_prepared(wct_ctx* ctx, const uint8_t* content, int Hc, int Wc, const wct_style* style, const int* levels,
+                          int n_levels, float alpha, unsigned flags, uint8_t* out);
+int  wct_stylize_prepared_batch_dev(wct_ctx* ctx, const uint8_t* content_dev, int Hc, int Wc, int B, const wct_style* style,
+                                    const int* levels, int n_levels, float alpha, unsigned flags, uint8_t* out_dev);
+int  wct_stylize_prepared_mix(wct_ctx* ctx, const uint8_t* content, int Hc, int Wc, const wct_style* const* styles, int K,
+                              const float* weights, const int* levels, int n_levels, float alpha, unsigned flags,
+                              uint8_t* out);
+
 /* ---- decoder training (model.py:123-223, train.py:129-196) ---------------------------
  * One optimiser step of the decoder for relu<level>_1 (the encoder is frozen, model.py:202):
  *   F = enc(x); D = dec(F); F' = enc(D);

@@ -56,6 +56,11 @@ SIGNATURES = [
                                      C.c_float, C.c_uint, _U8]),
     ('wct_stylize_batch_dev', C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, _I,
                                         C.c_int, C.c_float, C.c_uint, _P]),
+    ('wct_style_prepare', C.c_int, [_P, _U8, C.c_int, C.c_int, _I, C.c_int, C.c_uint, _PP]),
+    ('wct_style_free', None, [_P, _P]),
+    ('wct_stylize_prepared', C.c_int, [_P, _U8, C.c_int, C.c_int, _P, _I, C.c_int, C.c_float, C.c_uint, _U8]),
+    ('wct_stylize_prepared_batch_dev', C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _I, C.c_int, C.c_float, C.c_uint, _P]),
+    ('wct_stylize_prepared_mix', C.c_int, [_P, _U8, C.c_int, C.c_int, _PP, C.c_int, _F, _I, C.c_int, C.c_float, C.c_uint, _U8]),
     ('wct_train_step', C.c_int, [_P, C.c_int, _F, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float,
                                  C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, _F]),
     ('wct_get_decoder_layer', C.c_int, [_P, C.c_int, C.c_int, _F, _F, _F, _F]),

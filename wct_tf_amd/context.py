@@ -43,6 +43,64 @@ def _image_arrays(images):
             (C.c_int * k)(*[s.shape[1] for s in images]))
 
 
+class PreparedStyle(object):
+    """A style whose style side -- encoder pass, statistics, covariances, eigendecompositions, colouring matrices -- is kept on
+    the device (wct_style, include/wct_hip.h): Context.prepare_style makes one, the stylize_prepared* calls take it in the place
+    of a style image and give the image-based call's frame bit for bit.  Owned by its context (closing the context closes it);
+    close() or a `with` block releases it earlier.  `image` is the style as it was handed in."""
+
+    def __init__(self, ctx, handle, image, levels):
+        self.ctx, self.h, self.image, self.levels = ctx, handle, image, frozenset(levels)
+
+    @property
+    def closed(self):
+        return self.h is None or self.ctx is None or not getattr(self.ctx, 'h', None)
+
+    def close(self):
+        if not self.closed:
+            self.ctx.lib.wct_style_free(self.ctx.h, self.h)
+        self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def check_prepared(ctx, styles, relu_targets, swap5=False):
+    """The refusals of a call that takes prepared styles, raised before any library call: swap5, a closed handle, a handle of
+    another context, levels the handle was not prepared for."""
+    if swap5:
+        raise ValueError('swap5 takes a style image: style-swap needs the style\'s relu5_1 patches, which a prepared style does not hold')
+    lv = _levels(relu_targets)
+    for s in styles:
+        if not isinstance(s, PreparedStyle):
+            raise TypeError('expected a PreparedStyle, got %s' % type(s).__name__)
+        if s.closed:
+            raise ValueError('the prepared style is closed')
+        if s.ctx is not ctx:
+            raise ValueError('the prepared style belongs to another context')
+        if not set(lv) <= s.levels:
+            raise ValueError('the prepared style serves relu levels %s, not %s' % (sorted(s.levels), sorted(set(lv))))
+    return lv
+
+
+def split_styles(styles):
+    """(handles, images) of a list of styles: one of the two is empty, a list that mixes PreparedStyle objects and images is a
+    ValueError."""
+    handles = [s for s in styles if isinstance(s, PreparedStyle)]
+    if handles and len(handles) != len(styles):
+        raise ValueError('give either style images or prepared styles, not a mix of both')
+    return handles, ([] if handles else list(styles))
+
+
 class Context(object):
     def __init__(self, device=0):
         self.lib = _lib.load()
@@ -317,6 +375,77 @@ class Context(object):
         flags = (_lib.FLAG_ADAIN if adain else 0) | (_lib.FLAG_MODE_NP if wct_mode == 'np' else 0) | \
             (_lib.FLAG_SWAP5 if swap5 else 0) | (_lib.FLAG_IMAGES_F32 if as_f32 else 0)
         return c, ss, v, (C.c_int * len(lv))(*lv), np.empty((ho, wo, 3), np.uint8), flags
+
+    # ---- prepared styles -----------------------------------------------------
+    def prepare_style(self, style, relu_targets, adain=False, wct_mode='tf'):
+        """The style side of `style` (HxWx3 in [0,255]) for the levels `relu_targets`, kept on the device -> PreparedStyle.
+        uint8 goes as it is, anything else `/ 255.` in float64 and handed over as float32, exactly as Context.stylize does with
+        its style.  adain / wct_mode only pick what is computed up front: a handle serves either mode and AdaIN."""
+        img = np.asarray(style)
+        if img.ndim != 3 or img.shape[2] != 3:
+            raise ValueError('expected an HxWx3 style image, got shape %s' % (img.shape,))
+        as_f32 = img.dtype != np.uint8
+        s = np.ascontiguousarray(np.asarray(img / 255.), np.float32) if as_f32 else u8(img)
+        lv = sorted(set(_levels(relu_targets)))
+        flags = (_lib.FLAG_ADAIN if adain else 0) | (_lib.FLAG_MODE_NP if wct_mode == 'np' else 0) | (_lib.FLAG_IMAGES_F32 if as_f32 else 0)
+        h = C.c_void_p()
+        check(self.lib.wct_style_prepare(self.h, s.ctypes.data_as(_lib._U8), s.shape[0], s.shape[1], (C.c_int * len(lv))(*lv), len(lv),
+                                         flags, C.byref(h)))
+        return PreparedStyle(self, h, img, lv)
+
+    def _prepared_args(self, content, relu_targets, adain, wct_mode):
+        """content, levels, output and flags of a call with prepared styles (the content as in stylize)"""
+        content = np.asarray(content)
+        as_f32 = content.dtype != np.uint8
+        c = np.ascontiguousarray(np.asarray(content / 255.), np.float32) if as_f32 else u8(content)
+        lv = _levels(relu_targets)
+        ho, wo = self.output_size(c.shape[0], c.shape[1], lv)
+        flags = (_lib.FLAG_ADAIN if adain else 0) | (_lib.FLAG_MODE_NP if wct_mode == 'np' else 0) | (_lib.FLAG_IMAGES_F32 if as_f32 else 0)
+        return c, (C.c_int * len(lv))(*lv), np.empty((ho, wo, 3), np.uint8), flags
+
+    def stylize_prepared(self, content, style, relu_targets, alpha=1.0, adain=False, wct_mode='tf'):
+        """stylize() with a PreparedStyle in the place of the style image: the same frame, bit for bit."""
+        check_prepared(self, [style], relu_targets)
+        c, arr, out, flags = self._prepared_args(content, relu_targets, adain, wct_mode)
+        check(self.lib.wct_stylize_prepared(self.h, c.ctypes.data_as(_lib._U8), c.shape[0], c.shape[1], style.h, arr, len(arr),
+                                            float(alpha), flags, out.ctypes.data_as(_lib._U8)))
+        return out
+
+    def stylize_prepared_mix(self, content, styles, weights, relu_targets, alpha=1.0, adain=False, wct_mode='tf'):
+        """stylize_mix() with K PreparedStyle objects in the place of the K images: the same frame, bit for bit."""
+        w = _lib.mix_weights(weights, len(styles))
+        check_prepared(self, styles, relu_targets)
+        c, arr, out, flags = self._prepared_args(content, relu_targets, adain, wct_mode)
+        hs = (C.c_void_p * len(styles))(*[s.h.value for s in styles])
+        check(self.lib.wct_stylize_prepared_mix(self.h, c.ctypes.data_as(_lib._U8), c.shape[0], c.shape[1], hs, len(styles), fptr(w),
+                                                arr, len(arr), float(alpha), flags, out.ctypes.data_as(_lib._U8)))
+        return out
+
+    def stylize_prepared_batch_dev(self, content_dev, hc, wc, batch, style, relu_targets, alpha, out_dev, adain=False, wct_mode='tf'):
+        """stylize_batch_dev(shared_style=True) with a PreparedStyle: B contents resident in HBM, asynchronous."""
+        lv = check_prepared(self, [style], relu_targets)
+        flags = (_lib.FLAG_ADAIN if adain else 0) | (_lib.FLAG_MODE_NP if wct_mode == 'np' else 0)
+        check(self.lib.wct_stylize_prepared_batch_dev(self.h, content_dev, hc, wc, batch, style.h, (C.c_int * len(lv))(*lv), len(lv),
+                                                      float(alpha), flags, out_dev))
+
+    def stylize_prepared_batch(self, contents_u8, style, relu_targets, alpha=1.0, adain=False, wct_mode='tf'):
+        """stylize_batch() with a PreparedStyle: contents [B][H][W][3] uint8 (B <= 32) -> [B][Ho][Wo][3] uint8."""
+        check_prepared(self, [style], relu_targets)
+        c = u8(contents_u8)
+        assert c.ndim == 4 and c.shape[3] == 3
+        B, hc, wc = c.shape[:3]
+        ho, wo = self.output_size(hc, wc, relu_targets)
+        out = np.empty((B, ho, wo, 3), np.uint8)
+        dc, do = self.dev_alloc(c.nbytes), self.dev_alloc(out.nbytes)
+        try:
+            self.h2d(dc, c)
+            self.stylize_prepared_batch_dev(dc, hc, wc, B, style, relu_targets, alpha, do, adain=adain, wct_mode=wct_mode)
+            self.sync()
+            self.d2h(out, do)
+        finally:
+            for p in (dc, do):
+                self.dev_free(p)
+        return out
 
     def stylize_mix(self, content, styles, weights, relu_targets, alpha=1.0, adain=False, wct_mode='tf', swap5=False):
         """One predict() with a style mix at every level (wct_stylize_mix): `styles` is a list of K HxWx3 images (sizes may

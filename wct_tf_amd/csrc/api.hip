@@ -58,6 +58,23 @@ struct Decoder {
 struct ProfRec { hipEvent_t a, b; int cls; double flops, bytes; };
 constexpr int WCT_EIG_WORDS = 2 + 6 * 3;
 
+// A prepared style (wct_style_prepare): the style image on the device and, per level, a small cache of STATES -- the style side
+// of that level (common.h: WctStyleRef) for one key.  The bits of a state depend on the partial-sum layout of the (content,
+// style) pair it serves and on the mode, so a handle cannot hold one state per level: a call that needs a key the cache does
+// not hold computes it from the image in front of its content chain (style_fill) and keeps it, oldest out.
+constexpr int STYLE_CACHE_KEYS = 4;                  // states per level and handle
+struct StyleState {
+  WctStyleKey key; int kind;                         // kind 0: wct_tf, 1: wct_np, 2: AdaIN
+  float* buf;                                        // wct_style_state_floats(C)
+  unsigned long long stamp;                          // the call that used it last (wct_ctx::style_clock)
+};
+struct wct_style {
+  int Hs = 0, Ws = 0;
+  unsigned level_set = 0;                            // bit l: relu<l>_1 is served
+  float* img = nullptr;                              // [Hs][Ws][3] fp32 in [0,1]
+  std::vector<StyleState> cache[6];
+};
+
 struct wct_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -73,6 +90,8 @@ struct wct_ctx {
   DevBuf usum_c, usum_s[6], umax;     // feature statistics from the tap epilogues (ConvArgs::usum / umax); umax: [7][32][UMAX_SLOTS] words
   DevBuf mix_in, feat_mix[6];      // a style mix: the K style inputs, and their features per level (K maps back to back)
   DevBuf mask_in;                  // spatial control: the label map (wct_stylize_masked) or the row labels (wct_*_masked)
+  std::vector<wct_style*> styles;  // the live prepared styles of this context (wct_style_prepare .. wct_style_free)
+  unsigned long long style_clock = 0;   // one tick per call that takes prepared styles
 
   int* eig_fail = nullptr;         // pinned host memory mapped into the device: [2] eigenproblems that did not converge / had
                                    // non-finite input -- bumped by jacobi_finalize_kernel (then [6 size classes][3] solver
@@ -177,10 +196,20 @@ static void free_decoder(Decoder& d) {
   d = Decoder();
 }
 
+static void free_style(wct_style* st) {
+  if (!st) return;
+  for (auto& lv : st->cache)
+    for (auto& e : lv) if (e.buf) hipFree(e.buf);
+  if (st->img) hipFree(st->img);
+  delete st;
+}
+
 extern "C" void wct_destroy(wct_ctx* c) {
   if (!c) return;
   hipSetDevice(c->device);
   hipStreamSynchronize(c->stream);
+  for (wct_style* st : c->styles) free_style(st);
+  c->styles.clear();
   if (c->first_w) hipFree(c->first_w);
   if (c->first_b) hipFree(c->first_b);
   if (c->first_w32) hipFree(c->first_w32);
@@ -648,15 +677,15 @@ static int run_stages(wct_ctx* c, size_t ws_bytes, unsigned flags, const StageCo
 
 static int run_transform(wct_ctx* c, const float* fc, int Nc, const float* fs, int Ns, int C, int P,
                          float alpha, unsigned flags, float eps, half_t* out16, float* out32, int* sweeps_dev,
-                         const WctFeatStats* st = nullptr) {
+                         const WctFeatStats* st = nullptr, const WctStyleRef* prep = nullptr /* a prepared style: fs may be null */) {
   const int shared = (flags & WCT_FLAG_STYLE_SHARED) ? 1 : 0;
   const StageCost cost = {(double)P * 2.0 * C * C * ((double)Nc + Ns), (double)P * 2.0 * ((double)Nc + Ns) * C * 4,
                           (double)P * (2.0 * C * C * Nc + 6.0 * C * C * C), (double)P * Nc * C * (4 + (out16 ? 2 : 0) + (out32 ? 4 : 0)),
                           (double)P * (2.0 * Nc + 2.0 * Ns) * C * 4 + (double)P * Nc * C * 6};
   return run_stages(c, wct_workspace_bytes(C, Nc, Ns, P), flags, cost, [&](int mode, int stages) {
-    if (!stages) return launch_adain(fc, Nc, fs, Ns, C, P, alpha, 1e-5f, out16, out32, c->wct_ws.p, c->wct_ws.cap, c->stream, shared, st);
+    if (!stages) return launch_adain(fc, Nc, fs, Ns, C, P, alpha, 1e-5f, out16, out32, c->wct_ws.p, c->wct_ws.cap, c->stream, shared, st, prep);
     return launch_wct(fc, Nc, fs, Ns, C, P, alpha, mode, eps, out16, out32, c->wct_ws.p, c->wct_ws.cap, sweeps_dev, stages, c->stream,
-                      shared, c->eig_fail_dev, st);
+                      shared, c->eig_fail_dev, st, prep);
   });
 }
 
@@ -681,16 +710,16 @@ static int mix_weights(const float* weights, int K, float* lambda) {
 // the style-mix counterpart of run_transform (device pointers; one content, K styles); sweeps_dev [2K] or null
 static int run_transform_mix(wct_ctx* c, const float* fc, int Nc, const float* const* fs, const int* Ns, int K, const float* lambda,
                              int C, float alpha, unsigned flags, float eps, half_t* out16, float* out32, int* sweeps_dev,
-                             const WctFeatStats* st = nullptr) {
+                             const WctFeatStats* st = nullptr, const WctStyleRef* prep = nullptr /* K prepared styles: fs may be null */) {
   double ns = 0;
   for (int k = 0; k < K; ++k) ns += Ns[k];
   // (the mix of the K colouring matrices is timed with the tail it belongs to)
   const StageCost cost = {2.0 * C * C * (Nc + ns), 2.0 * (Nc + ns) * C * 4, 2.0 * C * C * Nc + 6.0 * C * C * C * (K + 1) + 2.0 * C * C * K,
                           (double)Nc * C * (4 + (out16 ? 2 : 0) + (out32 ? 4 : 0)), (2.0 * Nc + 2.0 * ns) * C * 4 + (double)Nc * C * 6};
   return run_stages(c, wct_mix_workspace_bytes(C, Nc, Ns, K, lambda), flags, cost, [&](int mode, int stages) {
-    if (!stages) return launch_adain_mix(fc, Nc, fs, Ns, K, lambda, C, alpha, 1e-5f, out16, out32, c->wct_ws.p, c->wct_ws.cap, c->stream, st);
+    if (!stages) return launch_adain_mix(fc, Nc, fs, Ns, K, lambda, C, alpha, 1e-5f, out16, out32, c->wct_ws.p, c->wct_ws.cap, c->stream, st, prep);
     return launch_wct_mix(fc, Nc, fs, Ns, K, lambda, C, alpha, mode, eps, out16, out32, c->wct_ws.p, c->wct_ws.cap, sweeps_dev, stages,
-                          c->stream, c->eig_fail_dev, st);
+                          c->stream, c->eig_fail_dev, st, prep);
   });
 }
 
@@ -1418,6 +1447,252 @@ extern "C" int wct_stylize_masked(wct_ctx* c, const uint8_t* content, int Hc, in
                          return run_transform_masked(c, (float*)c->feat_c.p, h * w, g, &nk[(size_t)i * WCT_MIX_MAX], fs, Ns, K, C,
                                                      alpha, flags, -1.f, (half_t*)c->wct_out.p, nullptr, nullptr);
                        });
+}
+
+// ---------------------------------------------------------------------------
+// prepared styles: the style side once, any number of contents (wct.py:70-106 / stylize_video.py:88-121 with a fixed style)
+// ---------------------------------------------------------------------------
+static int style_live(const wct_ctx* c, const wct_style* st) {
+  if (st && std::find(c->styles.begin(), c->styles.end(), st) != c->styles.end()) return WCT_OK;
+  wct_set_error("prepared style %p is not a live handle of this context (freed, or prepared by another context)", (const void*)st);
+  return WCT_ERR_STATE;
+}
+
+static StyleState* state_find(wct_style* st, int level, const WctStyleKey& key, int kind) {
+  for (auto& e : st->cache[level])
+    if (e.kind == kind && e.key.nslab == key.nslab && e.key.nsplit == key.nsplit && e.key.ksplit == key.ksplit) return &e;
+  return nullptr;
+}
+
+struct StyleNeed { int level; WctStyleKey key; int kind; };
+
+// Computes the states `needs` of a handle (none of them cached) on the ctx stream: ONE encoder pass of the style with a tap per
+// level needed, then launch_style_state per state.  Blocking, and the eigensolves are checked before a state is kept: on
+// WCT_ERR_NOCONV (or any error) none of them stays in the cache.
+static int style_fill(wct_ctx* c, wct_style* st, const std::vector<StyleNeed>& needs) {
+  if (needs.empty()) return WCT_OK;
+  HIP_TRY(hipStreamSynchronize(c->stream));               // (a state evicted below may belong to frames still in flight)
+  int deepest = 0;
+  float* taps[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  for (const StyleNeed& n : needs) {
+    int h, w;
+    level_dims(st->Hs, st->Ws, n.level, &h, &w);
+    TRY(ensure(c, c->feat_s[n.level], (size_t)h * w * LEVEL_C[n.level] * 4));
+    taps[n.level] = (float*)c->feat_s[n.level].p;
+    deepest = std::max(deepest, n.level);
+  }
+  TRY(run_encoder(c, st->img, 1, st->Hs, st->Ws, 0, deepest, taps));
+  std::vector<float*> fresh;
+  int rc = WCT_OK;
+  for (const StyleNeed& n : needs) {
+    const int C = LEVEL_C[n.level];
+    int h, w;
+    level_dims(st->Hs, st->Ws, n.level, &h, &w);
+    auto& lv = st->cache[n.level];
+    float* buf = nullptr;
+    if ((int)lv.size() >= STYLE_CACHE_KEYS) {            // the oldest state that this call does not use makes room
+      int old = -1;
+      for (int i = 0; i < (int)lv.size(); ++i)
+        if (lv[i].stamp != c->style_clock && (old < 0 || lv[i].stamp < lv[old].stamp)) old = i;
+      if (old >= 0) { buf = lv[old].buf; lv.erase(lv.begin() + old); }
+    }
+    if (!buf && hipMalloc((void**)&buf, wct_style_state_floats(C) * sizeof(float)) != hipSuccess) {
+      wct_set_error("hipMalloc failed (prepared style state, relu%d_1)", n.level);
+      rc = WCT_ERR_NOMEM;
+      break;
+    }
+    lv.push_back(StyleState{n.key, n.kind, buf, c->style_clock});
+    fresh.push_back(buf);
+    if (hipMemsetAsync(buf, 0, wct_style_state_floats(C) * sizeof(float), c->stream) != hipSuccess) { wct_set_error("hipMemsetAsync failed"); rc = WCT_ERR_HIP; break; }
+    if ((rc = ensure(c, c->wct_ws, wct_style_workspace_bytes(C, h * w, n.key)))) break;
+    ProfScope ps(c, n.kind == 2 ? 7 : 5, 0, 0);
+    if ((rc = launch_style_state(taps[n.level], h * w, C, n.key, n.kind == 2, n.kind == 1 ? WCT_MODE_NP : WCT_MODE_TF, -1.f, c->wct_ws.p,
+                                 c->wct_ws.cap, c->eig_fail_dev, c->stream, buf)))
+      break;
+  }
+  if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) { wct_set_error("hipStreamSynchronize failed (prepared style)"); rc = WCT_ERR_HIP; }
+  if (!rc) rc = eig_status(c);
+  if (rc) {                                               // keep nothing of a failed fill
+    hipStreamSynchronize(c->stream);
+    for (auto& lv : st->cache)
+      for (size_t i = lv.size(); i-- > 0;)
+        if (std::find(fresh.begin(), fresh.end(), lv[i].buf) != fresh.end()) { hipFree(lv[i].buf); lv.erase(lv.begin() + i); }
+  }
+  return rc;
+}
+
+static int style_kind(unsigned flags) { return (flags & WCT_FLAG_ADAIN) ? 2 : ((flags & WCT_FLAG_MODE_NP) ? 1 : 0); }
+
+static int style_flags_ok(unsigned flags) {
+  if (flags & WCT_FLAG_SWAP5) {
+    wct_set_error("prepared style: WCT_FLAG_SWAP5 needs the style's relu5_1 map and patches, which a handle does not hold");
+    return WCT_ERR_ARG;
+  }
+  if (flags & WCT_FLAG_STYLE_SHARED) { wct_set_error("prepared style: WCT_FLAG_STYLE_SHARED is for wct_stylize_batch_dev"); return WCT_ERR_ARG; }
+  return WCT_OK;
+}
+
+extern "C" int wct_style_prepare(wct_ctx* c, const uint8_t* style, int Hs, int Ws, const int* levels, int n_levels, unsigned flags,
+                                 wct_style** out) {
+  ARG_CHECK(c && style && levels && out && n_levels >= 1 && n_levels <= 16 && Hs >= 2 && Ws >= 2);
+  *out = nullptr;
+  TRY(style_flags_ok(flags));
+  unsigned set = 0;
+  int deepest = 0;
+  for (int i = 0; i < n_levels; ++i) {
+    ARG_CHECK(levels[i] >= 1 && levels[i] <= 5);
+    set |= 1u << levels[i];
+    deepest = std::max(deepest, levels[i]);
+  }
+  TRY(check_min_size("style", Hs, Ws, deepest));
+  if (!c->enc_loaded) { wct_set_error("encoder weights not set (wct_set_encoder)"); return WCT_ERR_STATE; }
+  HIP_TRY(hipSetDevice(c->device));
+  TRY(eig_stale(c));
+  struct Guard { wct_style* st; ~Guard() { free_style(st); } } g = {new wct_style()};
+  wct_style* st = g.st;
+  st->Hs = Hs; st->Ws = Ws; st->level_set = set;
+  const size_t n = (size_t)Hs * Ws * 3;
+  HIP_TRY(hipMalloc((void**)&st->img, n * sizeof(float)));
+  void* ds;
+  TRY(stage_in(c, 1, style, n * ((flags & WCT_FLAG_IMAGES_F32) ? sizeof(float) : 1), &ds));
+  if (flags & WCT_FLAG_IMAGES_F32) HIP_TRY(hipMemcpyAsync(st->img, ds, n * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+  else TRY(launch_u8_to_f32((const uint8_t*)ds, st->img, n, c->stream));
+  // the states of "a content as large as the style", in the mode the flags name; every other key on first use
+  ++c->style_clock;
+  std::vector<StyleNeed> needs;
+  for (int l = 1; l <= 5; ++l) {
+    if (!(set & (1u << l))) continue;
+    int h, w;
+    level_dims(Hs, Ws, l, &h, &w);
+    needs.push_back(StyleNeed{l, wct_style_key(LEVEL_C[l], h * w, h * w), style_kind(flags)});
+  }
+  TRY(style_fill(c, st, needs));
+  c->styles.push_back(st);
+  g.st = nullptr;
+  *out = st;
+  return WCT_OK;
+}
+
+extern "C" void wct_style_free(wct_ctx* c, wct_style* st) {
+  if (!c || !st) return;
+  auto it = std::find(c->styles.begin(), c->styles.end(), st);
+  if (it == c->styles.end()) return;                      // not ours, or freed already
+  hipSetDevice(c->device);
+  hipStreamSynchronize(c->stream);                        // frames in flight may still read its states
+  c->styles.erase(it);
+  free_style(st);
+}
+
+// The body of the wct_stylize_prepared* calls (their pointer and flag checks done): B contents [B][Hc][Wc][3] on the device, K
+// handles; lambda null: one style for all B (K = 1), else the mix weights of K styles (B = 1).  Asynchronous unless a handle
+// has to compute a state (style_fill), which happens before anything of the content chain is enqueued.
+static int stylize_prepared_dev(wct_ctx* c, const void* content, int Hc, int Wc, int B, const wct_style* const* styles, int K,
+                                const float* lambda, const int* levels, int n_levels, float alpha, unsigned flags, uint8_t* out) {
+  HIP_TRY(hipSetDevice(c->device));
+  for (int k = 0; k < K; ++k) TRY(style_live(c, styles[k]));
+  for (int i = 0; i < n_levels; ++i) {
+    ARG_CHECK(levels[i] >= 1 && levels[i] <= 5);
+    for (int k = 0; k < K; ++k)
+      if (!(styles[k]->level_set & (1u << levels[i]))) {
+        wct_set_error("prepared style %d was not prepared for relu%d_1", k, levels[i]);
+        return WCT_ERR_ARG;
+      }
+    if (!c->dec[levels[i]].loaded) { wct_set_error("decoder weights for relu%d_1 not set", levels[i]); return WCT_ERR_STATE; }
+  }
+  int Ho, Wo;
+  TRY(wct_output_size(Hc, Wc, levels, n_levels, &Ho, &Wo));
+
+  // the states of every level, before any launch of the content chain: style k serves the layout of (content, style k)
+  const int kind = style_kind(flags);
+  ++c->style_clock;
+  std::vector<WctStyleRef> refs(n_levels);
+  std::vector<int> ns((size_t)n_levels * WCT_MIX_MAX);
+  for (int k = 0; k < K; ++k) {
+    wct_style* st = const_cast<wct_style*>(styles[k]);
+    std::vector<StyleNeed> all, missing;
+    int H = Hc, W = Wc;
+    for (int i = 0; i < n_levels; ++i) {
+      const int l = levels[i];
+      int h, w, hs, ws;
+      level_dims(H, W, l, &h, &w);
+      level_dims(st->Hs, st->Ws, l, &hs, &ws);
+      ns[(size_t)i * WCT_MIX_MAX + k] = hs * ws;
+      const StyleNeed n = {l, wct_style_key(LEVEL_C[l], h * w, hs * ws), kind};
+      all.push_back(n);
+      StyleState* e = state_find(st, l, n.key, kind);
+      if (e) e->stamp = c->style_clock;
+      else if (std::none_of(missing.begin(), missing.end(), [&](const StyleNeed& m) {
+                 return m.level == l && m.key.nslab == n.key.nslab && m.key.nsplit == n.key.nsplit && m.key.ksplit == n.key.ksplit; }))
+        missing.push_back(n);
+      H = h << (l - 1); W = w << (l - 1);
+    }
+    TRY(style_fill(c, st, missing));
+    for (int i = 0; i < n_levels; ++i) {
+      StyleState* e = state_find(st, all[i].level, all[i].key, kind);
+      if (!e) { wct_set_error("prepared style %d: the state of relu%d_1 is gone", k, all[i].level); return WCT_ERR_STATE; }
+      refs[i].state[k] = e->buf;
+    }
+  }
+
+  const float* img_c = (const float*)content;
+  const size_t nc = (size_t)B * Hc * Wc * 3;
+  if (!(flags & WCT_FLAG_IMAGES_F32)) {
+    TRY(ensure(c, c->img_c, nc * 4));
+    ProfScope ps(c, 7, 0, (double)nc * 5);
+    TRY(launch_u8_to_f32((const uint8_t*)content, (float*)c->img_c.p, nc, c->stream));
+    img_c = (const float*)c->img_c.p;
+  }
+  constexpr size_t UROW = 32 * UMAX_SLOTS;                           // (the content's row of wct_stylize_batch_dev)
+  TRY(ensure(c, c->umax, 7 * UROW * sizeof(unsigned)));
+  if (fuse_stats()) HIP_TRY(hipMemsetAsync(c->umax.p, 0, UROW * sizeof(unsigned), c->stream));
+  auto no_style = [](int, int, int* hs, int* ws) { *hs = *ws = 0; return (const float*)nullptr; };     // (style-swap alone asks)
+  return stylize_levels(c, img_c, B, Hc, Wc, levels, n_levels, flags, UROW * sizeof(unsigned), 1, no_style,
+                        [&](int i, int, int C, int h, int w, const WctFeatStats& st) {
+                          const int* Ns = &ns[(size_t)i * WCT_MIX_MAX];
+                          if (!lambda)
+                            return run_transform(c, (float*)c->feat_c.p, h * w, nullptr, Ns[0], C, B, alpha, flags, -1.f,
+                                                 (half_t*)c->wct_out.p, nullptr, nullptr, &st, &refs[i]);
+                          return run_transform_mix(c, (float*)c->feat_c.p, h * w, nullptr, Ns, K, lambda, C, alpha, flags, -1.f,
+                                                   (half_t*)c->wct_out.p, nullptr, nullptr, &st, &refs[i]);
+                        }, out);
+}
+
+// host content in, host frame out, around stylize_prepared_dev (B = 1)
+static int stylize_prepared_host(wct_ctx* c, const uint8_t* content, int Hc, int Wc, const wct_style* const* styles, int K,
+                                 const float* lambda, const int* levels, int n_levels, float alpha, unsigned flags, uint8_t* out) {
+  HIP_TRY(hipSetDevice(c->device));
+  TRY(eig_stale(c));
+  int Ho, Wo;
+  TRY(wct_output_size(Hc, Wc, levels, n_levels, &Ho, &Wo));
+  void* dc;
+  TRY(stage_in(c, 0, content, (size_t)Hc * Wc * 3 * ((flags & WCT_FLAG_IMAGES_F32) ? sizeof(float) : 1), &dc));
+  TRY(ensure(c, c->stage[2], (size_t)Ho * Wo * 3));
+  TRY(stylize_prepared_dev(c, dc, Hc, Wc, 1, styles, K, lambda, levels, n_levels, alpha, flags, (uint8_t*)c->stage[2].p));
+  TRY(fetch(c, out, c->stage[2].p, (size_t)Ho * Wo * 3));
+  return eig_status(c);
+}
+
+extern "C" int wct_stylize_prepared(wct_ctx* c, const uint8_t* content, int Hc, int Wc, const wct_style* style, const int* levels,
+                                    int n_levels, float alpha, unsigned flags, uint8_t* out) {
+  ARG_CHECK(c && content && out && levels && n_levels >= 1 && n_levels <= 16);
+  TRY(style_flags_ok(flags));
+  return stylize_prepared_host(c, content, Hc, Wc, &style, 1, nullptr, levels, n_levels, alpha, flags, out);
+}
+
+extern "C" int wct_stylize_prepared_batch_dev(wct_ctx* c, const uint8_t* content, int Hc, int Wc, int B, const wct_style* style,
+                                              const int* levels, int n_levels, float alpha, unsigned flags, uint8_t* out) {
+  ARG_CHECK(c && content && out && levels && n_levels >= 1 && n_levels <= 16 && B >= 1 && B <= 32);
+  TRY(style_flags_ok(flags));
+  return stylize_prepared_dev(c, content, Hc, Wc, B, &style, 1, nullptr, levels, n_levels, alpha, flags, out);
+}
+
+extern "C" int wct_stylize_prepared_mix(wct_ctx* c, const uint8_t* content, int Hc, int Wc, const wct_style* const* styles, int K,
+                                        const float* weights, const int* levels, int n_levels, float alpha, unsigned flags, uint8_t* out) {
+  ARG_CHECK(c && content && styles && out && levels && n_levels >= 1 && n_levels <= 16);
+  float lambda[WCT_MIX_MAX];
+  TRY(mix_weights(weights, K, lambda));
+  TRY(style_flags_ok(flags));
+  return stylize_prepared_host(c, content, Hc, Wc, styles, K, lambda, levels, n_levels, alpha, flags, out);
 }
 
 // ---------------------------------------------------------------------------

@@ -166,7 +166,7 @@ struct GemmArgs {
   const float* A_odd;     // if set: A of an odd batch b is A_odd + (b >> 1) * sA_odd, that of an even one A + (b >> 1) * sA
   size_t sA_odd;
   int skip_shared;        // batches b with skip_style_mat(b, skip_shared) have nothing to do (1: one style for all pairs,
-                          // WCT_FLAG_STYLE_SHARED; 2: one content for a style mix, launch_wct_mix)
+                          // WCT_FLAG_STYLE_SHARED; 2: one content for a style mix, launch_wct_mix; 3 .. 5: prepared styles)
   // blend epilogue (T = Tcs Tw -> M = alpha T + (1 - alpha) I, ops.py:83 folded into the apply matrix): the store carries the
   // blend and the block merges max |M| into mabs[batch] (bit patterns of non-negative floats; zeroed by an earlier kernel)
   int blend; float alpha; unsigned* mabs;
@@ -185,6 +185,19 @@ enum { WCT_MODE_NP = 0, WCT_MODE_TF = 1 };
 // whose u is null is summed from the features themselves (same bits either way, colsum_kernel).
 struct WctFeatStats { const float* u[2]; const unsigned* umax[2]; };
 
+// Prepared styles (wct.hip): a STATE is the style side of one level for one layout and mode -- [mean C][var C][Tcs C x C] floats
+// (var for AdaIN, Tcs for WCT).  Its bits depend on the slab count and K-slices of the (content, style) pair it serves: the key.
+struct WctStyleKey { int nslab, nsplit, ksplit; };
+WctStyleKey wct_style_key(int C, int Nc, int Ns);
+size_t wct_style_state_floats(int C);
+size_t wct_style_workspace_bytes(int C, int Ns, const WctStyleKey& key);
+// the state of `style` [Ns][C] under `key`: launch_wct's style side alone (adain: launch_adain's), bit for bit
+int launch_style_state(const float* style, int Ns, int C, const WctStyleKey& key, int adain, int mode, float eps, void* workspace,
+                       size_t workspace_bytes, int* eig_fail, hipStream_t s, float* state);
+// the states a transform takes in place of its style features (`prep` below): state[0], or state[k] for style k of a mix.  The
+// style pointers may then be null; Ns still names the styles' rows (the content's layout depends on them).
+struct WctStyleRef { const float* state[8]; };
+
 // P independent whiten-colour transforms on `s`:  out = blend(T (x - mc) + ms)
 // content [P][Nc][C], style [P][Ns][C]; out16/out32 [P][Nc][C] (either may be null).
 size_t wct_workspace_bytes(int C, int Nc, int Ns, int P);
@@ -195,14 +208,15 @@ int launch_wct(const float* content, int Nc, const float* style, int Ns, int C, 
                                    eigensystem are computed once */,
                int* eig_fail /* device-visible status words: [2] (not converged, non-finite), bumped by the eigensolver,
                                 then [6 size classes][3] solver statistics; or null */,
-               const struct WctFeatStats* stats = nullptr /* unit sums / maxima a conv epilogue left beside the features */);
+               const struct WctFeatStats* stats = nullptr /* unit sums / maxima a conv epilogue left beside the features */,
+               const struct WctStyleRef* prep = nullptr /* one prepared style for all P pairs (shared_style is ignored) */);
 // WCT_STAGE_EIG_FP32UPDATE (with WCT_STAGE_EIG): the eigensolver's tile updates on fp32 MFMA instead of split fp16 -- style-swap, whose
 // patch matching is an argmax over the whitened features (csrc/jacobi_dev.h r4::fused_u)
 enum { WCT_STAGE_COV = 1, WCT_STAGE_EIG = 2, WCT_STAGE_APPLY = 4, WCT_STAGE_ALL = 7, WCT_STAGE_EIG_FP32UPDATE = 8 };
 int launch_adain(const float* content, int Nc, const float* style, int Ns, int C, int P,
                  float alpha, float eps, half_t* out16, float* out32,
                  void* workspace, size_t workspace_bytes, hipStream_t s, int shared_style,
-                 const struct WctFeatStats* stats = nullptr);
+                 const struct WctFeatStats* stats = nullptr, const struct WctStyleRef* prep = nullptr);
 // Style mix (Li et al. 2017, sec. 4.2): out = sum_k lambda[k] T(content, styles[k]) for K <= WCT_MIX_MAX styles of any sizes
 // Ns[k]; lambda[k] in [0, 1] summing to 1 (normalised by the caller).  One content whitening, K colourings mixed before ONE
 // blend product and apply.  sweeps_dev [2K]: slot 2k + 1 style k, slot 0 the content (the even slots k >= 1 read 0).  stats:
@@ -211,10 +225,11 @@ enum { WCT_MIX_MAX = 8 };
 size_t wct_mix_workspace_bytes(int C, int Nc, const int* Ns, int K, const float* lambda);
 int launch_wct_mix(const float* content, int Nc, const float* const* styles, const int* Ns, int K, const float* lambda, int C,
                    float alpha, int mode, float eps, half_t* out16, float* out32, void* workspace, size_t workspace_bytes,
-                   int* sweeps_dev, int stages, hipStream_t s, int* eig_fail, const struct WctFeatStats* stats = nullptr);
+                   int* sweeps_dev, int stages, hipStream_t s, int* eig_fail, const struct WctFeatStats* stats = nullptr,
+                   const struct WctStyleRef* prep = nullptr);
 int launch_adain_mix(const float* content, int Nc, const float* const* styles, const int* Ns, int K, const float* lambda, int C,
                      float alpha, float eps, half_t* out16, float* out32, void* workspace, size_t workspace_bytes, hipStream_t s,
-                     const struct WctFeatStats* stats = nullptr);
+                     const struct WctFeatStats* stats = nullptr, const struct WctStyleRef* prep = nullptr);
 // Spatial control (Li et al. 2017, sec. 4.2): K <= WCT_MIX_MAX labelled regions of one content, region k transformed with style k
 // alone.  Row r = (i, j) of an h x w feature map has the label mask[min(i * stride, Hm - 1)][min(j * stride, Wm - 1)] of the
 // Hm x Wm label map (the content's, at stride 2^(level - 1)).  nk[k]: the rows of label k, counted by the caller (they size

@@ -249,8 +249,8 @@ __global__ __launch_bounds__(256) void spectral_open_all_kernel(SpecAllArgs a) {
   if (kind == 0 && blockIdx.x == 0 && blockIdx.y == 0) {
     // what blend_matrix_kernel did besides the blend: bias = alpha ms (+ (1 - alpha) mc in tf mode); and mabs starts at 0
     if (tid == 0) a.mabs[pair] = 0u;
-    const float* mp = a.mean + (size_t)(a.shared_style == WCT_SKIP_MIX ? 0 : pair) * 2 * C;     // (a mix: the one content)
-    const float* ms = a.mean + (size_t)(a.shared_style == 1 ? 0 : pair) * 2 * C + C;
+    const float* mp = a.mean + (size_t)(one_content(a.shared_style) ? 0 : pair) * 2 * C;     // (a mix: the one content)
+    const float* ms = a.mean + (size_t)(one_style(a.shared_style) ? 0 : pair) * 2 * C + C;
     for (int i = tid; i < C; i += 256) {
       float b = a.alpha * ms[i];
       if (a.mode == WCT_MODE_TF) b += (1.f - a.alpha) * mp[i];
@@ -437,7 +437,7 @@ int launch_spectral_tail(const WctCarve& w, int C, int P, float alpha, int mode,
     GemmArgs b = {};   // X1[pair] = R[pair] . N[2 pair]   (whitening side only)
     b.A = sa.R; b.sA = cc; b.lda = C; b.a_kmajor = 0; b.B = sa.N; b.ldb = C; b.b_kmajor = 1; b.sB = 2 * cc;
     b.M = C; b.N = C; b.K = C; b.ksplit = C; b.out32 = X1; b.ldo = C; b.s_out = cc;
-    if ((rc = launch_gemm(b, 1, nwhite, s))) return rc;
+    if (nwhite > 0 && (rc = launch_gemm(b, 1, nwhite, s))) return rc;
     hipLaunchKernelGGL(spectral_add2_all_kernel, tiles, dim3(256), 0, s, sa);
     HIP_TRY(hipGetLastError());
   }

@@ -306,10 +306,85 @@ static int launch_blend_apply(const WctCarve& w, const float* content, int Nc, i
   return WCT_OK;
 }
 
+// ---------------------------------------------------------------------------
+// Prepared styles (wct_style, api.hip).  The colouring side of a level is content-independent up to the layout of its partial
+// sums: the colouring matrix Tcs [C][C] and the style mean [C] (WCT), the mean and the variance (AdaIN).  A STATE holds them --
+// [mean C][var C][Tcs C x C] floats -- for ONE layout and mode (WctStyleKey).  launch_style_state fills one from a style's features
+// with the content slot dead (WCT_SKIP_CONTENT): the statistics, covariance, eigensolve and spectral tail of launch_wct on
+// matrix 1 alone, so the state holds launch_wct's own bits.  A transform with `prep` set runs the content side alone
+// (WCT_SKIP_STYLE; a mix: WCT_SKIP_MIX_STYLE) and style_load_kernel copies state k into the style slot 2k + 1 in front of the
+// consumers, which read it as they read a computed one -- not a line of them changes.
+// ---------------------------------------------------------------------------
+WctStyleKey wct_style_key(int C, int Nc, int Ns) {
+  const PairLayout L = pair_layout(std::max(C, 32), Nc, Ns);
+  return WctStyleKey{L.nslab, L.nsplit, L.ksplit};
+}
+size_t wct_style_state_floats(int C) { return (size_t)2 * C + (size_t)C * C; }
+
+// grid (blocks, K): state k -> mean / var slot 2k + 1 and, with_T, Tw matrix 2k + 1 (C % 4 == 0: no float4 straddles a part)
+__global__ __launch_bounds__(256) void style_load_kernel(WctStyleRef r, float* mean, float* var, float* Tw, int C, int with_T) {
+  const int k = blockIdx.y;
+  const float* src = r.state[k];
+  const size_t cc = (size_t)C * C, n = (size_t)2 * C + (with_T ? cc : 0), slot = (size_t)(2 * k + 1);
+  for (size_t i = (blockIdx.x * (size_t)blockDim.x + threadIdx.x) * 4; i < n; i += (size_t)gridDim.x * blockDim.x * 4) {
+    const f32x4 v = *reinterpret_cast<const f32x4*>(src + i);
+    float* dst = i < (size_t)C ? mean + slot * C + i : (i < (size_t)2 * C ? var + slot * C + (i - C) : Tw + slot * cc + (i - 2 * C));
+    *reinterpret_cast<f32x4*>(dst) = v;
+  }
+}
+
+static int launch_style_load(const WctStyleRef& r, int K, const WctCarve& w, int C, bool with_T, hipStream_t s) {
+  for (int k = 0; k < K; ++k) ARG_CHECK(r.state[k] != nullptr);
+  const size_t n4 = ((size_t)2 * C + (with_T ? (size_t)C * C : 0)) / 4;
+  hipLaunchKernelGGL(style_load_kernel, dim3((unsigned)std::min<size_t>((n4 + 255) / 256, 256), K), dim3(256), 0, s, r, w.mean, w.var, w.Tw,
+                     C, with_T ? 1 : 0);
+  HIP_TRY(hipGetLastError());
+  return WCT_OK;
+}
+
+// the plan of a state: one pair, the style in slot 1 with the layout of the key, the content slot dead
+static void style_plan(SlotPlan* sp, void* base, int C, const float* style, int Ns, const WctStyleKey& key) {
+  *sp = SlotPlan{};
+  sp->P = 1; sp->skip = WCT_SKIP_CONTENT; sp->nwhite = 0;
+  sp->slot[1] = {style, Ns, PairLayout{key.nslab, key.nsplit, key.ksplit}};
+  plan_carve(sp, base, C);
+}
+
+size_t wct_style_workspace_bytes(int C, int Ns, const WctStyleKey& key) {
+  SlotPlan sp;
+  style_plan(&sp, nullptr, C, nullptr, Ns, key);
+  return sp.total;
+}
+
+int launch_style_state(const float* style, int Ns, int C, const WctStyleKey& key, int adain, int mode, float eps_in, void* workspace,
+                       size_t workspace_bytes, int* eig_fail, hipStream_t s, float* state) {
+  ARG_CHECK(style && state && C % 32 == 0 && C >= 32 && C <= 1024 && Ns >= (adain ? 1 : 2) && (size_t)Ns * C * 4 < ((size_t)1 << 31));
+  ARG_CHECK(adain || mode == WCT_MODE_NP || mode == WCT_MODE_TF);
+  ARG_CHECK(key.nslab >= 1 && key.nslab <= 256 && key.nsplit >= 1 && key.ksplit >= 256 && key.ksplit % 32 == 0 &&
+            (long long)key.nsplit * key.ksplit >= Ns);
+  SlotPlan sp;
+  style_plan(&sp, workspace, C, style, Ns, key);
+  ARG_CHECK(workspace_bytes >= sp.total);
+  const WctCarve& w = sp.w;
+  int rc;
+  if (adain) {
+    if ((rc = launch_plan_stats(sp, C, true, false, 0.f, s))) return rc;
+    HIP_TRY(hipMemcpyAsync(state + C, w.var + C, (size_t)C * sizeof(float), hipMemcpyDeviceToDevice, s));
+  } else {
+    if ((rc = launch_plan_stats(sp, C, false, true, cov_eps(mode, eps_in), s))) return rc;
+    if ((rc = launch_eig_stage(w, C, sp.P, sp.skip, 1, nullptr, eig_fail, s))) return rc;
+    if ((rc = launch_spectral_tail(w, C, sp.P, 1.f, mode, eps_in, sp.skip, sp.nwhite, s))) return rc;
+    HIP_TRY(hipMemcpyAsync(state + 2 * C, w.Tw + (size_t)C * C, (size_t)C * C * sizeof(float), hipMemcpyDeviceToDevice, s));
+  }
+  HIP_TRY(hipMemcpyAsync(state, w.mean + C, (size_t)C * sizeof(float), hipMemcpyDeviceToDevice, s));
+  return WCT_OK;
+}
+
 int launch_wct(const float* content, int Nc, const float* style, int Ns, int C, int P, float alpha, int mode, float eps_in,
                half_t* out16, float* out32, void* workspace, size_t workspace_bytes, int* sweeps_dev,
-               int stages, hipStream_t s, int shared_style, int* eig_fail, const WctFeatStats* stats) {
+               int stages, hipStream_t s, int shared_style, int* eig_fail, const WctFeatStats* stats, const WctStyleRef* prep) {
   ARG_CHECK(C % 32 == 0 && C >= 32 && C <= 1024 && Nc >= 2 && Ns >= 2 && P >= 1 && P <= 32);
+  if (prep) shared_style = WCT_SKIP_STYLE;       // (the style rows are not read: `style` may be null)
   ARG_CHECK(mode == WCT_MODE_NP || mode == WCT_MODE_TF);
   // the covariance kernel addresses one feature map through a buffer resource with 32-bit byte offsets
   ARG_CHECK((size_t)Nc * C * 4 < ((size_t)1 << 31) && (size_t)Ns * C * 4 < ((size_t)1 << 31));
@@ -325,6 +400,7 @@ int launch_wct(const float* content, int Nc, const float* style, int Ns, int C, 
     return rc;
   if (!(stages & WCT_STAGE_APPLY)) return WCT_OK;
 
+  if (prep && (rc = launch_style_load(*prep, 1, w, C, true, s))) return rc;
   if ((rc = launch_spectral_tail(w, C, P, alpha, mode, eps_in, shared_style, P, s))) return rc;
   return launch_blend_apply(w, content, Nc, C, P, alpha, shared_style, out16, out32, s);
 }
@@ -358,7 +434,7 @@ bool plan_fits(const SlotPlan& sp, int C) {
 // The plan of a style mix (see above).  C: the channels (AdaIN takes C < 32; its workspace is laid out as for 32).  styles may
 // be null (the workspace size alone).  False for arguments no mix takes.
 static bool mix_plan(SlotPlan* sp, void* base, int C, const float* content, int Nc, const float* const* styles, const int* Ns,
-                     int K, const float* lambda, int nmin, const WctFeatStats* stats) {
+                     int K, const float* lambda, int nmin, const WctFeatStats* stats, bool prepared = false) {
   if (!Ns || !lambda || K < 1 || K > WCT_MIX_MAX) return false;
   int ref = 0;
   for (int k = 0; k < K; ++k) {
@@ -371,12 +447,16 @@ static bool mix_plan(SlotPlan* sp, void* base, int C, const float* content, int 
   if (stats) { sp->u0 = stats->u[0]; sp->umax0 = stats->umax[0]; }
   sp->slot[0] = {content, Nc, pair_layout(Cw, Nc, Ns[ref])};
   for (int k = 0; k < K; ++k) sp->slot[2 * k + 1] = {styles ? styles[k] : nullptr, Ns[k], pair_layout(Cw, Nc, Ns[k])};
+  if (prepared) {                                // the K style slots take prepared states: the content alone is live
+    sp->skip = WCT_SKIP_MIX_STYLE;
+    for (int k = 0; k < K; ++k) sp->slot[2 * k + 1].n = 0;
+  }
   plan_carve(sp, base, Cw);
   return true;
 }
 
 size_t wct_mix_workspace_bytes(int C, int Nc, const int* Ns, int K, const float* lambda) {
-  SlotPlan sp;
+  SlotPlan sp;     // (a prepared mix needs no more: its style slots are dead)
   return mix_plan(&sp, nullptr, C, nullptr, Nc, nullptr, Ns, K, lambda, 1, nullptr) ? sp.total : 0;
 }
 
@@ -405,10 +485,10 @@ __global__ __launch_bounds__(256) void wct_mix_kernel(float* Tw, float* bias, in
 
 int launch_wct_mix(const float* content, int Nc, const float* const* styles, const int* Ns, int K, const float* lambda, int C,
                    float alpha, int mode, float eps_in, half_t* out16, float* out32, void* workspace, size_t workspace_bytes,
-                   int* sweeps_dev, int stages, hipStream_t s, int* eig_fail, const WctFeatStats* stats) {
+                   int* sweeps_dev, int stages, hipStream_t s, int* eig_fail, const WctFeatStats* stats, const WctStyleRef* prep) {
   SlotPlan sp;
-  ARG_CHECK(C % 32 == 0 && C >= 32 && C <= 1024 && Nc >= 2 && content && styles &&
-            mix_plan(&sp, workspace, C, content, Nc, styles, Ns, K, lambda, 2, stats));
+  ARG_CHECK(C % 32 == 0 && C >= 32 && C <= 1024 && Nc >= 2 && content && (styles || prep) &&
+            mix_plan(&sp, workspace, C, content, Nc, prep ? nullptr : styles, Ns, K, lambda, 2, stats, prep != nullptr));
   ARG_CHECK(mode == WCT_MODE_NP || mode == WCT_MODE_TF);
   ARG_CHECK(plan_fits(sp, C));
   ARG_CHECK(workspace_bytes >= sp.total);
@@ -417,6 +497,7 @@ int launch_wct_mix(const float* content, int Nc, const float* const* styles, con
   if ((stages & WCT_STAGE_COV) && (rc = launch_plan_stats(sp, C, false, true, cov_eps(mode, eps_in), s))) return rc;
   if ((stages & WCT_STAGE_EIG) && (rc = launch_eig_stage(w, C, sp.P, sp.skip, 1, sweeps_dev, eig_fail, s))) return rc;
   if (!(stages & WCT_STAGE_APPLY)) return WCT_OK;
+  if (prep && (rc = launch_style_load(*prep, K, w, C, true, s))) return rc;
   if ((rc = launch_spectral_tail(w, C, sp.P, alpha, mode, eps_in, sp.skip, sp.nwhite, s))) return rc;
   MixWeights mw = {};
   mw.K = K;
@@ -465,13 +546,15 @@ __global__ void adain_apply_kernel(const float* x, size_t n4_per_pair, int C, co
 
 int launch_adain(const float* content, int Nc, const float* style, int Ns, int C, int P, float alpha, float eps,
                  half_t* out16, float* out32, void* workspace, size_t workspace_bytes, hipStream_t s, int shared_style,
-                 const WctFeatStats* stats) {
+                 const WctFeatStats* stats, const WctStyleRef* prep) {
   ARG_CHECK(C % 4 == 0 && C <= 1024 && Nc >= 1 && Ns >= 1 && P >= 1 && P <= 32);
+  if (prep) shared_style = WCT_SKIP_STYLE;
   const int Cw = C < 32 ? 32 : C;
   WctCarve w = carve(workspace, Cw, P, pair_layout(Cw, Nc, Ns));
   ARG_CHECK(workspace_bytes >= w.total);
   int rc;
   if ((rc = launch_means(content, Nc, style, Ns, C, P, w, true, shared_style, s, stats))) return rc;
+  if (prep && (rc = launch_style_load(*prep, 1, w, C, false, s))) return rc;
   const size_t n4 = (size_t)Nc * C / 4;
   hipLaunchKernelGGL(adain_apply_kernel, dim3(rows_grid(Nc, C), P), dim3(256), 0, s, content, n4, C, w.mean, w.var, alpha, eps, out16, out32, shared_style);
   HIP_TRY(hipGetLastError());
@@ -493,13 +576,16 @@ __global__ void adain_mix_moments_kernel(const float* mean, const float* var, fl
 
 int launch_adain_mix(const float* content, int Nc, const float* const* styles, const int* Ns, int K, const float* lambda, int C,
                      float alpha, float eps, half_t* out16, float* out32, void* workspace, size_t workspace_bytes, hipStream_t s,
-                     const WctFeatStats* stats) {
+                     const WctFeatStats* stats, const WctStyleRef* prep) {
   SlotPlan sp;
-  ARG_CHECK(C % 4 == 0 && C <= 1024 && Nc >= 1 && content && styles && mix_plan(&sp, workspace, C, content, Nc, styles, Ns, K, lambda, 1, stats));
+  ARG_CHECK(C % 4 == 0 && C <= 1024 && Nc >= 1 && content && (styles || prep) &&
+            mix_plan(&sp, workspace, C, content, Nc, prep ? nullptr : styles, Ns, K, lambda, 1, stats, prep != nullptr));
+  ARG_CHECK(!prep || C >= 32);
   ARG_CHECK(workspace_bytes >= sp.total);
   const WctCarve& w = sp.w;
   int rc;
   if ((rc = launch_plan_stats(sp, C, true, false, 0.f, s))) return rc;
+  if (prep && (rc = launch_style_load(*prep, K, w, C, false, s))) return rc;
   MixWeights mw = {};
   mw.K = K;
   for (int k = 0; k < K; ++k) mw.lambda[k] = lambda[k];

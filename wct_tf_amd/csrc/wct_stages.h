@@ -10,9 +10,19 @@
 // A style mix (launch_wct_mix; shared_style == WCT_SKIP_MIX) is the mirror image: K styles share ONE content, matrix 0;
 // the content slots 2k of the pairs k >= 1 are skipped.
 constexpr int WCT_SKIP_MIX = 2;
+// Prepared styles (wct_style, api.hip): the style side of a call comes out of a handle's cached state, copied into the style
+// slots by style_load_kernel (wct.hip), so EVERY style matrix is dead -- WCT_SKIP_STYLE (P contents, one state in slot 1, read
+// like a shared style) and WCT_SKIP_MIX_STYLE (a mix of K states: matrix 0 alone is live).  WCT_SKIP_CONTENT is the mirror image
+// that fills a state: one style in slot 1, the content slot dead, no whitening side.
+constexpr int WCT_SKIP_STYLE = 3, WCT_SKIP_CONTENT = 4, WCT_SKIP_MIX_STYLE = 5;
 __device__ __host__ __forceinline__ bool skip_style_mat(int mat, int shared_style) {
+  if (shared_style >= WCT_SKIP_STYLE)
+    return shared_style == WCT_SKIP_STYLE ? (mat & 1) != 0 : (shared_style == WCT_SKIP_CONTENT ? (mat & 1) == 0 : mat > 0);
   return shared_style == WCT_SKIP_MIX ? ((mat & 1) == 0 && mat > 0) : (shared_style && (mat & 1) && mat > 1);
 }
+// which pair's slots hold the content / style moments a pair's consumers read: pair 0's for all where one is shared
+__device__ __host__ __forceinline__ bool one_content(int shared_style) { return shared_style == WCT_SKIP_MIX || shared_style == WCT_SKIP_MIX_STYLE; }
+__device__ __host__ __forceinline__ bool one_style(int shared_style) { return shared_style == 1 || shared_style == WCT_SKIP_STYLE; }
 
 // 0: spectral functions of the diagonal only, 1: + first-order completion, 2 (the product): + second-order completion
 constexpr int EIG_CORRECT = 2;
@@ -58,7 +68,7 @@ static inline unsigned rows_grid(size_t N, int C) {
 // The slot plan of a per-slot transform (a style mix, spatial control): 2P matrix slots in the pair layout of carve(), each
 // slot's statistics and covariance launched on its own rows with the layout of its own single-pair transform (pair_layout).
 struct SlotPlan {
-  int P, skip, nwhite;                         // pairs; the skip mode (WCT_SKIP_MIX or 0); pairs whose whitening side is live
+  int P, skip, nwhite;                         // pairs; the skip mode (0 or a WCT_SKIP_*); pairs whose whitening side is live
   struct Slot { const float* x; int n; PairLayout lay; } slot[2 * WCT_MIX_MAX];   // rows (null while only sizing the
                                                                                  // workspace), their count (0: skipped), layout
   const float* u0; const unsigned* umax0;      // slot 0's unit sums from a conv epilogue, or null

@@ -99,14 +99,24 @@ def load_style(path, args):
     return img
 
 
-def stylize_pair(model, content, style, args):
-    """one output image: optional CORAL, `--passes` predictions, optional `--concat` (stylize.py:85-110)"""
+MAX_PREPARED = 64        # prepared styles alive at once in the --style-path loop (each keeps its image and states on the device)
+
+
+def can_prepare(args):
+    """may the styles of this run be prepared once (WCT.prepare_style) instead of once per content?  Not with --keep-colors
+    (CORAL makes the style depend on the content) or --swap5 (style-swap needs the style's patches)."""
+    return not args.keep_colors and not args.swap5
+
+
+def stylize_pair(model, content, style, args, prepared=None):
+    """one output image: optional CORAL, `--passes` predictions, optional `--concat` (stylize.py:85-110).  prepared: the
+    PreparedStyle of `style` (can_prepare), or None"""
     if args.keep_colors:
         from .ops import preserve_colors_np
         style = preserve_colors_np(style, content, ctx=model.sess)
     out = content
     for _ in range(max(1, args.passes)):
-        out = model.predict(out, style, args.alpha, args.swap5, args.ss_alpha, args.adain)
+        out = model.predict(out, style if prepared is None else prepared, args.alpha, args.swap5, args.ss_alpha, args.adain)
     if args.concat:
         side = out.shape[0]
         out = np.hstack([utils._imresize(style, (side, side)), out])
@@ -139,15 +149,16 @@ def interp_name(content_path, style_paths):
     return '%s_%s%s' % (_stem(content_path), '+'.join(_stem(p) for p in style_paths), os.path.splitext(content_path)[1])
 
 
-def stylize_mix_pair(model, content, styles, args):
+def stylize_mix_pair(model, content, styles, args, prepared=None):
     """one output of a style mix: stylize_pair with every style taking part -- CORAL per style (--keep-colors), `--passes`
-    mixes, and --concat with the K styles to the left of the result"""
+    mixes, and --concat with the K styles to the left of the result.  prepared: the PreparedStyle objects of `styles`, or None"""
     if args.keep_colors:
         from .ops import preserve_colors_np
         styles = [preserve_colors_np(s, content, ctx=model.sess) for s in styles]
     out = content
     for _ in range(max(1, args.passes)):
-        out = model.predict_mix(out, styles, args.interp_weights, args.alpha, args.adain, args.swap5, args.ss_alpha)
+        out = model.predict_mix(out, styles if prepared is None else prepared, args.interp_weights, args.alpha, args.adain, args.swap5,
+                                args.ss_alpha)
     if args.concat:
         side = out.shape[0]
         out = np.hstack([utils._imresize(s, (side, side)) for s in styles] + [out])
@@ -238,12 +249,13 @@ def main(argv=None):
     written = 0
     if args.interp_styles is not None:
         mix = [load_style(p, args) for p in args.interp_styles]
+        prepared = [model.prepare_style(s, adain=args.adain) for s in mix] if can_prepare(args) and contents else None
         for cpath in contents:
             content = utils.get_img(cpath)
             if args.content_size > 0:
                 content = utils.resize_to(content, args.content_size)
             target = os.path.join(args.out_path, interp_name(cpath, args.interp_styles))
-            utils.save_img(target, stylize_mix_pair(model, content, mix, args))
+            utils.save_img(target, stylize_mix_pair(model, content, mix, args, prepared))
             written += 1
             print('%d: wrote %s' % (written, target))
         print('%d outputs in %.1f s' % (written, time.time() - t0))
@@ -264,12 +276,21 @@ def main(argv=None):
     styles = _listing(args.style_path)
     if os.path.isdir(args.style_path) and args.random > 0:
         styles = list(np.random.choice(styles, args.random))
+    # every style once, not once per content: the whole style side of every further pair (the first MAX_PREPARED styles of a
+    # large folder; the others go as images, as before)
+    loaded, n_prepared = {}, 0
     for cpath in contents:
         content = utils.get_img(cpath)
         if args.content_size > 0:
             content = utils.resize_to(content, args.content_size)
         for spath in styles:
-            result = stylize_pair(model, content, load_style(spath, args), args)
+            if spath not in loaded:
+                style = load_style(spath, args)
+                prepare = can_prepare(args) and len(contents) > 1 and n_prepared < MAX_PREPARED
+                loaded[spath] = (style, model.prepare_style(style, adain=args.adain) if prepare else None)
+                n_prepared += prepare
+            style, prepared = loaded[spath]
+            result = stylize_pair(model, content, style, args, prepared)
             target = os.path.join(args.out_path, '%s_%s%s' % (_stem(cpath), _stem(spath), os.path.splitext(cpath)[1]))
             utils.save_img(target, result)
             written += 1

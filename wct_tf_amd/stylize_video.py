@@ -84,7 +84,15 @@ def stylize_frames(wct_model, frame_files, style_img, args):
             img = resize_to(img, args.content_size)
         return img
 
+    # the style is the same for every frame: its style side runs once (WCT.prepare_style), not once per batch -- the frames
+    # are bit-identical.  Not with --keep-colors (the style differs per frame) or --swap5 (style-swap needs the style's patches).
+    prepared = None
+    if not args.keep_colors and not args.swap5:
+        prepared = wct_model.prepare_style(np.uint8(np.clip(style_img, 0, 255)) if style_img.dtype != np.uint8 else style_img,
+                                           adain=args.adain)
+
     def run(frames, style):
+        style = prepared if prepared is not None else style
         out = wct_model.predict_frames(frames, style, args.alpha, args.swap5, args.ss_alpha, args.adain, batch=args.batch)
         for _ in range(args.passes - 1):                      # later passes: plain WCT, as stylize_video.py:124-126
             out = wct_model.predict_frames(out, style, args.alpha, adain=args.adain, batch=args.batch)
@@ -120,6 +128,8 @@ def stylize_frames(wct_model, frame_files, style_img, args):
             if args.concat:                                   # stylize_video.py:129-132
                 o = np.hstack([_imresize(s, (o.shape[0], o.shape[0])), o])
             yield f, o
+    if prepared is not None:
+        prepared.close()
 
 
 def main(argv=None):

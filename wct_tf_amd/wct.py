@@ -4,6 +4,7 @@
     WCT.predict(content, style, alpha=1, swap5=False, ss_alpha=1, adain=False) -> uint8 HxWx3
     WCT.predict_mix(content, styles, weights=None, alpha=1, adain=False, swap5=False, ss_alpha=1) -> uint8 HxWx3
     WCT.predict_masked(content, styles, mask, alpha=1, adain=False, swap5=False, ss_alpha=1) -> uint8 HxWx3
+    WCT.prepare_style(style) -> PreparedStyle, which predict / predict_frames / predict_mix take in the place of a style image
 
 `checkpoints` / `vgg_path`: the reference restores TF checkpoints and a .t7 file
 (wct.py:46-58, vgg_normalised.py:16).  Per decoder this class takes either of
@@ -18,7 +19,7 @@ import re
 
 import numpy as np
 
-from .context import Context
+from .context import Context, PreparedStyle, check_prepared, split_styles
 from .model import WCTModel
 from .weights import load_weights
 
@@ -101,10 +102,23 @@ class WCT(object):
             self.sess.set_style_swap(ss_alpha, self.ss_patch_size, self.ss_stride)
         return content, mask
 
+    def prepare_style(self, style, adain=False):
+        '''Run the style side of `style` (array in [0,255]) once, for this model's relu_targets, and keep it on the device: the
+           PreparedStyle goes wherever predict, predict_frames and predict_mix take a style image and gives the same frames bit
+           for bit, without the style encoder pass, the style statistics and the style eigendecompositions of every call.  One
+           handle serves every content size and alpha, AdaIN included (`adain` only picks what is computed up front; another
+           content size is computed on first use and kept).  Not for swap5 or predict_masked.  Close it, or the model's context,
+           to release it.'''
+        return self.sess.prepare_style(style, self.relu_targets, adain=adain, wct_mode=self.wct_mode)
+
     def predict(self, content, style, alpha=1, swap5=False, ss_alpha=1, adain=False):
         '''Stylize a single content/style pair; arrays in [0,255], returns uint8 HxWx3.
            The /255 preprocess and the clip*255 postprocess run inside the library
-           (fused at the ends of the kernel chain).'''
+           (fused at the ends of the kernel chain).  `style` may be a PreparedStyle (prepare_style).'''
+        if isinstance(style, PreparedStyle):
+            check_prepared(self.sess, [style], self.relu_targets, swap5)          # ValueError before any GPU call
+            return self.sess.stylize_prepared(np.asarray(content), style, self.relu_targets, alpha=alpha, adain=adain,
+                                              wct_mode=self.wct_mode)
         content, _ = self._swap5_setup(np.asarray(content), None, swap5, ss_alpha)
         style = np.asarray(style)
         # uint8 arrays take the fused /255 on the device; float arrays are divided by 255 WITHOUT rounding, as the
@@ -118,6 +132,12 @@ class WCT(object):
            sum(weights); weights=None means equal weights.  Arrays in [0,255], returns uint8 HxWx3.  One style gives
            predict(content, style) bit for bit, as do one-hot weights.  swap5 takes one style only (style-swap is not linear).'''
         from ._lib import mix_weights
+        handles, styles = split_styles(list(styles))             # ValueError: images and prepared styles in one list
+        if handles:
+            weights = mix_weights(weights, len(handles))
+            check_prepared(self.sess, handles, self.relu_targets, swap5)
+            return self.sess.stylize_prepared_mix(np.asarray(content), handles, weights, self.relu_targets, alpha=alpha,
+                                                  adain=adain, wct_mode=self.wct_mode)
         styles = [np.asarray(s) for s in styles]
         weights = mix_weights(weights, len(styles))              # ValueError before any GPU call
         if swap5 and len(styles) > 1:
@@ -133,6 +153,8 @@ class WCT(object):
            (a label with fewer than 2 pixels at a level keeps that level's features).  Arrays in [0,255], returns uint8 HxWx3.
            One style with an all-zero mask gives predict(content, style) bit for bit.  swap5 takes one style only.'''
         from ._lib import mask_labels
+        if any(isinstance(s, PreparedStyle) for s in styles):
+            raise TypeError('predict_masked takes style images: spatial control with prepared styles is not implemented')
         styles = [np.asarray(s) for s in styles]
         content = np.asarray(content)
         mask = mask_labels(mask, len(styles), content.shape[:2])        # ValueError before any GPU call
@@ -146,8 +168,18 @@ class WCT(object):
         '''Stylize same-sized frames [F][H][W][3] with ONE style image (the loop of stylize_video.py:112-121,
            which calls predict() once per frame and so re-runs the style encoder, the style statistics and the
            style eigendecompositions every frame).  Here the style side runs once per batch of `batch` frames;
-           every frame equals predict(frame, style) bit for bit.  Returns uint8 [F][Ho][Wo][3].'''
+           every frame equals predict(frame, style) bit for bit.  Returns uint8 [F][Ho][Wo][3].
+           With a PreparedStyle (prepare_style) the style side does not run at all; the frames are the same.'''
         frames = np.asarray(frames)
+        if isinstance(style, PreparedStyle):
+            check_prepared(self.sess, [style], self.relu_targets, swap5)          # ValueError before any GPU call
+            assert frames.ndim == 4
+            if frames.dtype != np.uint8:
+                frames = np.uint8(np.clip(frames, 0, 255))
+            batch = max(1, min(32, int(batch)))
+            return np.concatenate([self.sess.stylize_prepared_batch(frames[i:i + batch], style, self.relu_targets, alpha=alpha,
+                                                                    adain=adain, wct_mode=self.wct_mode)
+                                   for i in range(0, len(frames), batch)], axis=0)
         style = np.asarray(style)
         assert frames.ndim == 4 and style.ndim == 3
         if frames.dtype != np.uint8:
