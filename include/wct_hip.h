@@ -132,6 +132,11 @@ int wct_adain_masked(wct_ctx* ctx, const float* content, int Nc, const uint8_t* 
  * label 1, ...; seg_off_out [K + 1] where each label starts (what the masked calls use; a check of their first pass) */
 int wct_mask_compact(wct_ctx* ctx, const uint8_t* mask, int Hm, int Wm, int h, int w, int stride, int K, int* perm_out,
                      int* seg_off_out);
+/* the same for B <= 32 label maps masks [B][Hm][Wm] in ONE launch of each pass (the frame is a grid axis; what the masked batch
+ * call uses): perm_out [B][h * w], seg_off_out [B][K + 1], frame f's being what wct_mask_compact gives for masks[f] alone.  Like
+ * wct_mask_compact this is a check of the masked calls' first pass (tests/test_gpu_mask_video.py), not a call to build on */
+int wct_mask_compact_batch(wct_ctx* ctx, const uint8_t* masks, int B, int Hm, int Wm, int h, int w, int stride, int K,
+                           int* perm_out, int* seg_off_out);
 /* wct_style_swap (ops.py:145-278): content [hc*wc][C], style [hs*ws][C], out [hc*wc][C]; `alpha` is the
  * reference's ss_alpha; eps < 0 = its default 1e-8.  (hc, wc) must survive the patch/stride round trip
  * (utils.swap_filter_fit, wct.py:84-90) -- always true for stride 1. */
@@ -251,6 +256,31 @@ int  wct_stylize_prepared_batch_dev(wct_ctx* ctx, const uint8_t* content_dev, in
 int  wct_stylize_prepared_mix(wct_ctx* ctx, const uint8_t* content, int Hc, int Wc, const wct_style* const* styles, int K,
                               const float* weights, const int* levels, int n_levels, float alpha, unsigned flags,
                               uint8_t* out);
+/* Spatial control on prepared styles, and on a batch of frames with one label map each (a video with a segmentation per frame).
+ * wct_stylize_prepared_masked = wct_stylize_masked's frame, bit for bit, for the same content, mask, levels, alpha and flags and
+ *   the images the K handles were prepared from: host pointers, blocking, like wct_stylize_prepared.  It is the B = 1 case of
+ * wct_stylize_prepared_masked_batch_dev: content_dev [B][Hc][Wc][3] and out_dev [B][Ho][Wo][3] are DEVICE pointers, masks_host
+ *   [B][Hc][Wc] is on the HOST (the labels of every level and frame are counted there before any launch -- the counts size the
+ *   launches and the slot layout, nothing is read back -- and the B maps are then uploaded once, by a copy enqueued on the ctx
+ *   stream: keep masks_host valid until wct_sync), B = 1 .. 32, the K handles are shared by all frames.  Asynchronous on the ctx
+ *   stream like wct_stylize_prepared_batch_dev; it blocks only while it computes a style state it does not hold.  Frame f is wct_stylize_prepared_masked(content f, mask f), bit for bit -- so also
+ *   wct_stylize_masked's.  Per level the live (frame, region) pairs run in groups of at most 32 (one batched eigensolve each; the
+ *   style slots are dead); a matrix's eigensystem does not depend on its batch, so the grouping does not show in the frames.
+ * Per frame the semantics are wct_stylize_masked's: feature pixel (i, j) at stride s has the label mask[min(i s, Hc - 1)][min(j s,
+ *   Wc - 1)], a label with fewer than 2 pixels at a level keeps that level's features, a label with none is skipped.
+ * States: region k of frame f takes handle k's state under the key of (N_fk rows, style k) -- the key follows the LARGER of the
+ *   region and the style map, so regions no larger than the style all share the state made by wct_style_prepare, and larger
+ *   regions of different sizes need one state each.  A state that the running call uses is never evicted: a level's cache then
+ *   holds more than 4 keys -- as many as the most demanding call needed, at most B per handle and level -- and keeps that size.
+ * flags: WCT_FLAG_MODE_NP, WCT_FLAG_ADAIN, and WCT_FLAG_IMAGES_F32 for the content.  WCT_FLAG_SWAP5 and WCT_FLAG_STYLE_SHARED are
+ *   WCT_STATUS_ARG; so are K outside 1 .. 8, a label >= K, and a level outside a handle's set.  A handle that is not live in this
+ *   ctx is WCT_STATUS_STATE and never dereferenced.  A refusal leaves the ctx usable. */
+int  wct_stylize_prepared_masked(wct_ctx* ctx, const uint8_t* content, int Hc, int Wc, const uint8_t* mask,
+                                 const wct_style* const* styles, int K, const int* levels, int n_levels, float alpha,
+                                 unsigned flags, uint8_t* out);
+int  wct_stylize_prepared_masked_batch_dev(wct_ctx* ctx, const uint8_t* content_dev, int Hc, int Wc, int B,
+                                           const uint8_t* masks_host, const wct_style* const* styles, int K, const int* levels,
+                                           int n_levels, float alpha, unsigned flags, uint8_t* out_dev);
 
 /* ---- decoder training (model.py:123-223, train.py:129-196) ---------------------------
  * One optimiser step of the decoder for relu<level>_1 (the encoder is frozen, model.py:202):

@@ -37,6 +37,7 @@ SIGNATURES = [
                                        C.c_float, _F, _I]),
     ('wct_adain_masked', C.c_int, [_P, _F, C.c_int, _U8, C.POINTER(_F), _I, C.c_int, C.c_int, C.c_float, C.c_float, _F]),
     ('wct_mask_compact', C.c_int, [_P, _U8, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _I, _I]),
+    ('wct_mask_compact_batch', C.c_int, [_P, _U8, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _I, _I]),
     ('wct_style_swap', C.c_int, [_P, _F, C.c_int, C.c_int, _F, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_float, _F]),
     ('wct_set_style_swap', C.c_int, [_P, C.c_float, C.c_int, C.c_int]),
     ('wct_eigh', C.c_int, [_P, _F, C.c_int, C.c_int, _F, _F, _I]),
@@ -61,6 +62,9 @@ SIGNATURES = [
     ('wct_stylize_prepared', C.c_int, [_P, _U8, C.c_int, C.c_int, _P, _I, C.c_int, C.c_float, C.c_uint, _U8]),
     ('wct_stylize_prepared_batch_dev', C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _I, C.c_int, C.c_float, C.c_uint, _P]),
     ('wct_stylize_prepared_mix', C.c_int, [_P, _U8, C.c_int, C.c_int, _PP, C.c_int, _F, _I, C.c_int, C.c_float, C.c_uint, _U8]),
+    ('wct_stylize_prepared_masked', C.c_int, [_P, _U8, C.c_int, C.c_int, _U8, _PP, C.c_int, _I, C.c_int, C.c_float, C.c_uint, _U8]),
+    ('wct_stylize_prepared_masked_batch_dev', C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _U8, _PP, C.c_int, _I, C.c_int, C.c_float,
+                                                        C.c_uint, _P]),
     ('wct_train_step', C.c_int, [_P, C.c_int, _F, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float,
                                  C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, _F]),
     ('wct_get_decoder_layer', C.c_int, [_P, C.c_int, C.c_int, _F, _F, _F, _F]),
@@ -94,6 +98,7 @@ class WCTNotConverged(WCTHipError):
 
 STATUS_NOCONV = -5
 MIX_MAX = 8                  # styles per mix (WCT_MIX_MAX)
+BATCH_MAX = 32               # frames per batch call
 
 
 def load():
@@ -168,3 +173,19 @@ def mask_labels(mask, k, shape=None):
     if m.min() < 0 or m.max() >= k:
         raise ValueError('mask labels must be 0 .. %d for %d styles, got %d .. %d' % (k - 1, k, m.min(), m.max()))
     return np.ascontiguousarray(m, np.uint8)
+
+
+def mask_labels_frames(masks, k, n_frames, shape):
+    """The label maps of `n_frames` frames of `shape` (H, W) as contiguous uint8 [F][H][W]: `masks` is [F][H][W] (one map per
+    frame; the count must equal the frame count), or one [H][W] map used for every frame.  Each map is checked by mask_labels."""
+    if not 1 <= k <= MIX_MAX:
+        raise ValueError('a mask takes 1 .. %d styles, got %d' % (MIX_MAX, k))
+    shape = tuple(shape)
+    if isinstance(masks, np.ndarray) and masks.ndim == 2:
+        return np.ascontiguousarray(np.broadcast_to(mask_labels(masks, k, shape), (n_frames,) + shape))
+    if len(masks) != n_frames:
+        raise ValueError('%d masks for %d frames' % (len(masks), n_frames))
+    out = np.empty((n_frames,) + shape, np.uint8)
+    for f in range(n_frames):
+        out[f] = mask_labels(masks[f], k, shape)
+    return out

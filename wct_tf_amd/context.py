@@ -76,7 +76,8 @@ class PreparedStyle(object):
 
 def check_prepared(ctx, styles, relu_targets, swap5=False):
     """The refusals of a call that takes prepared styles, raised before any library call: swap5, a closed handle, a handle of
-    another context, levels the handle was not prepared for."""
+    another context, levels the handle was not prepared for, and -- last -- an object whose `h` is not the wct_style pointer
+    prepare_style stores (TypeError: the library takes addresses, and a made-up one must never reach it)."""
     if swap5:
         raise ValueError('swap5 takes a style image: style-swap needs the style\'s relu5_1 patches, which a prepared style does not hold')
     lv = _levels(relu_targets)
@@ -89,6 +90,9 @@ def check_prepared(ctx, styles, relu_targets, swap5=False):
             raise ValueError('the prepared style belongs to another context')
         if not set(lv) <= s.levels:
             raise ValueError('the prepared style serves relu levels %s, not %s' % (sorted(s.levels), sorted(set(lv))))
+    for s in styles:
+        if not isinstance(s.h, C.c_void_p):
+            raise TypeError('the prepared style holds %s, not a wct_style pointer' % type(s.h).__name__)
     return lv
 
 
@@ -124,6 +128,7 @@ class Context(object):
 
     def sync(self):
         check(self.lib.wct_sync(self.h))
+        self._masks_in_flight = []               # (stylize_prepared_masked_batch_dev: every upload has run)
 
     def stream_handle(self):
         """The context's hipStream_t as an integer (torch.cuda.ExternalStream(handle) wraps it)."""
@@ -232,6 +237,18 @@ class Context(object):
         seg = np.empty(k + 1, np.int32)
         check(self.lib.wct_mask_compact(self.h, m.ctypes.data_as(_lib._U8), m.shape[0], m.shape[1], int(h), int(w), int(stride),
                                         int(k), perm.ctypes.data_as(_lib._I), seg.ctypes.data_as(_lib._I)))
+        return perm, seg
+
+    def mask_compact_batch(self, masks, h, w, stride, k):
+        """mask_compact for B label maps [B][H][W] in one launch of each pass (wct_mask_compact_batch) -> (perm [B][h*w],
+        seg_off [B][k+1])"""
+        m = _lib.mask_labels(masks, k)
+        if m.ndim != 3:
+            raise ValueError('expected [B][H][W] label maps')
+        perm = np.empty((m.shape[0], h * w), np.int32)
+        seg = np.empty((m.shape[0], k + 1), np.int32)
+        check(self.lib.wct_mask_compact_batch(self.h, m.ctypes.data_as(_lib._U8), m.shape[0], m.shape[1], m.shape[2], int(h), int(w),
+                                              int(stride), int(k), perm.ctypes.data_as(_lib._I), seg.ctypes.data_as(_lib._I)))
         return perm, seg
 
     def style_swap(self, content, style, alpha, patch_size=3, stride=1, eps=-1.0):
@@ -440,6 +457,59 @@ class Context(object):
         try:
             self.h2d(dc, c)
             self.stylize_prepared_batch_dev(dc, hc, wc, B, style, relu_targets, alpha, do, adain=adain, wct_mode=wct_mode)
+            self.sync()
+            self.d2h(out, do)
+        finally:
+            for p in (dc, do):
+                self.dev_free(p)
+        return out
+
+    def stylize_prepared_masked(self, content, styles, mask, relu_targets, alpha=1.0, adain=False, wct_mode='tf'):
+        """stylize_masked() with K PreparedStyle objects in the place of the K images: the same frame, bit for bit."""
+        c0 = np.asarray(content)
+        m = _lib.mask_labels(mask, len(styles), c0.shape[:2])
+        check_prepared(self, styles, relu_targets)
+        c, arr, out, flags = self._prepared_args(c0, relu_targets, adain, wct_mode)
+        hs = (C.c_void_p * len(styles))(*[s.h.value for s in styles])
+        check(self.lib.wct_stylize_prepared_masked(self.h, c.ctypes.data_as(_lib._U8), c.shape[0], c.shape[1],
+                                                   m.ctypes.data_as(_lib._U8), hs, len(styles), arr, len(arr), float(alpha), flags,
+                                                   out.ctypes.data_as(_lib._U8)))
+        return out
+
+    def stylize_prepared_masked_batch_dev(self, content_dev, hc, wc, batch, masks, styles, relu_targets, alpha, out_dev,
+                                          adain=False, wct_mode='tf'):
+        """Spatial control of B uint8 frames resident in HBM, one label map per frame: `masks` [B][hc][wc] (or one [hc][wc] map
+        for all) is a HOST array, the K PreparedStyle objects are shared by all frames.  Asynchronous; frame f is
+        stylize_prepared_masked(frame f, masks[f])."""
+        if not 1 <= int(batch) <= _lib.BATCH_MAX:
+            raise ValueError('a batch takes 1 .. %d frames, got %d' % (_lib.BATCH_MAX, batch))
+        m = _lib.mask_labels_frames(masks, len(styles), int(batch), (hc, wc))
+        lv = check_prepared(self, styles, relu_targets)
+        flags = (_lib.FLAG_ADAIN if adain else 0) | (_lib.FLAG_MODE_NP if wct_mode == 'np' else 0)
+        hs = (C.c_void_p * len(styles))(*[s.h.value for s in styles])
+        # the upload is enqueued on the stream: the maps stay alive until sync() (include/wct_hip.h)
+        self._masks_in_flight = getattr(self, '_masks_in_flight', []) + [m]
+        check(self.lib.wct_stylize_prepared_masked_batch_dev(self.h, content_dev, hc, wc, int(batch), m.ctypes.data_as(_lib._U8), hs,
+                                                             len(styles), (C.c_int * len(lv))(*lv), len(lv), float(alpha), flags,
+                                                             out_dev))
+
+    def stylize_prepared_masked_batch(self, contents_u8, styles, masks, relu_targets, alpha=1.0, adain=False, wct_mode='tf'):
+        """Host arrays in, host array out: contents [B][H][W][3] uint8 (B <= 32), masks [B][H][W] (or one [H][W] map for all),
+        K PreparedStyle objects -> [B][Ho][Wo][3] uint8."""
+        c = u8(contents_u8)
+        if c.ndim != 4 or c.shape[3] != 3:
+            raise ValueError('expected [B][H][W][3] frames, got shape %s' % (c.shape,))
+        B, hc, wc = c.shape[:3]
+        if not 1 <= B <= _lib.BATCH_MAX:
+            raise ValueError('a batch takes 1 .. %d frames, got %d' % (_lib.BATCH_MAX, B))
+        m = _lib.mask_labels_frames(masks, len(styles), B, (hc, wc))
+        check_prepared(self, styles, relu_targets)
+        ho, wo = self.output_size(hc, wc, relu_targets)
+        out = np.empty((B, ho, wo, 3), np.uint8)
+        dc, do = self.dev_alloc(c.nbytes), self.dev_alloc(out.nbytes)
+        try:
+            self.h2d(dc, c)
+            self.stylize_prepared_masked_batch_dev(dc, hc, wc, B, m, styles, relu_targets, alpha, do, adain=adain, wct_mode=wct_mode)
             self.sync()
             self.d2h(out, do)
         finally:

@@ -929,6 +929,28 @@ extern "C" int wct_mask_compact(wct_ctx* c, const uint8_t* mask, int Hm, int Wm,
   return fetch(c, perm_out, perm, (size_t)N * sizeof(int));
 }
 
+extern "C" int wct_mask_compact_batch(wct_ctx* c, const uint8_t* masks, int B, int Hm, int Wm, int h, int w, int stride, int K,
+                                      int* perm_out, int* seg_off_out) {
+  ARG_CHECK(c && masks && perm_out && seg_off_out && B >= 1 && B <= 32 && Hm >= 1 && Wm >= 1 && h >= 1 && w >= 1 && stride >= 1);
+  TRY(mask_check(masks, (size_t)B * Hm * Wm, K));
+  HIP_TRY(hipSetDevice(c->device));
+  const int N = h * w;
+  TRY(ensure(c, c->mask_in, (size_t)B * Hm * Wm));
+  HIP_TRY(hipMemcpyAsync(c->mask_in.p, masks, (size_t)B * Hm * Wm, hipMemcpyHostToDevice, c->stream));
+  const size_t perm_bytes = ((size_t)B * N * sizeof(int) + 255) & ~(size_t)255;
+  const size_t seg_bytes = ((size_t)B * (WCT_MIX_MAX + 1) * sizeof(int) + 255) & ~(size_t)255;
+  TRY(ensure(c, c->stage[2], perm_bytes + seg_bytes + mask_compact_workspace_bytes(N, B)));
+  int* perm = (int*)c->stage[2].p;
+  int* seg_off = (int*)((char*)c->stage[2].p + perm_bytes);
+  TRY(launch_mask_compact_batch(MaskGeom{(const uint8_t*)c->mask_in.p, Hm, Wm, w, stride}, N, K, B, perm, seg_off, (char*)seg_off + seg_bytes,
+                                c->stream));
+  std::vector<int> seg((size_t)B * (WCT_MIX_MAX + 1));
+  TRY(fetch(c, seg.data(), seg_off, seg.size() * sizeof(int)));
+  for (int f = 0; f < B; ++f)
+    for (int k = 0; k <= K; ++k) seg_off_out[f * (K + 1) + k] = seg[(size_t)f * (WCT_MIX_MAX + 1) + k];
+  return fetch(c, perm_out, perm, (size_t)B * N * sizeof(int));
+}
+
 extern "C" int wct_set_style_swap(wct_ctx* c, float ss_alpha, int patch_size, int stride) {
   ARG_CHECK(c && patch_size >= 1 && stride >= 1);
   c->ss_alpha = ss_alpha; c->ss_patch = patch_size; c->ss_stride = stride;
@@ -1693,6 +1715,168 @@ extern "C" int wct_stylize_prepared_mix(wct_ctx* c, const uint8_t* content, int 
   TRY(mix_weights(weights, K, lambda));
   TRY(style_flags_ok(flags));
   return stylize_prepared_host(c, content, Hc, Wc, styles, K, lambda, levels, n_levels, alpha, flags, out);
+}
+
+// Spatial control of B frames on prepared styles: one label map per frame (on the HOST: every level's labels are counted here,
+// before any launch, and size the launches), K handles shared by all frames.  The level transform runs the frames in GROUPS of at
+// most WCT_PLAN_PAIRS = 32 live (frame, region) pairs -- one batched eigensolve of 64 slots, the style slots dead -- through
+// launch_wct_masked_batch; a matrix's eigensystem does not depend on its batch, so the grouping does not show in the frames.
+// Pair (f, k) takes handle k's state under wct_style_key(C, N_fk, Ns_k); the missing ones are filled in front of the content
+// chain (style_fill), and a state the running call uses is never evicted (its stamp is the call's), so a level's cache holds
+// as many keys as the call with the most distinct region sizes needed (at least STYLE_CACHE_KEYS, at most B per label).
+static int stylize_prepared_masked_dev(wct_ctx* c, const void* content, int Hc, int Wc, int B, const uint8_t* masks,
+                                       const wct_style* const* styles, int K, const int* levels, int n_levels, float alpha,
+                                       unsigned flags, uint8_t* out) {
+  HIP_TRY(hipSetDevice(c->device));
+  if (K < 1 || K > WCT_MIX_MAX) { wct_set_error("mask: K = %d styles, must be 1 .. %d", K, (int)WCT_MIX_MAX); return WCT_ERR_ARG; }
+  for (int k = 0; k < K; ++k) TRY(style_live(c, styles[k]));
+  TRY(mask_check(masks, (size_t)B * Hc * Wc, K));
+  for (int i = 0; i < n_levels; ++i) {
+    ARG_CHECK(levels[i] >= 1 && levels[i] <= 5);
+    for (int k = 0; k < K; ++k)
+      if (!(styles[k]->level_set & (1u << levels[i]))) {
+        wct_set_error("prepared style %d was not prepared for relu%d_1", k, levels[i]);
+        return WCT_ERR_ARG;
+      }
+    if (!c->dec[levels[i]].loaded) { wct_set_error("decoder weights for relu%d_1 not set", levels[i]); return WCT_ERR_STATE; }
+  }
+  int Ho, Wo;
+  TRY(wct_output_size(Hc, Wc, levels, n_levels, &Ho, &Wo));
+
+  // the labels of every level and frame, counted on the host: nk [level][frame][WCT_MIX_MAX]
+  const size_t fstride = (size_t)B * WCT_MIX_MAX;
+  std::vector<int> nk((size_t)n_levels * fstride), ns((size_t)n_levels * WCT_MIX_MAX);
+  {
+    int H = Hc, W = Wc;
+    for (int i = 0; i < n_levels; ++i) {
+      const int l = levels[i];
+      int h, w;
+      level_dims(H, W, l, &h, &w);
+      for (int f = 0; f < B; ++f)
+        mask_counts(masks + (size_t)f * Hc * Wc, Hc, Wc, h, w, 1 << (l - 1), K, &nk[i * fstride + (size_t)f * WCT_MIX_MAX]);
+      for (int k = 0; k < K; ++k) {
+        int hs, ws;
+        level_dims(styles[k]->Hs, styles[k]->Ws, l, &hs, &ws);
+        ns[(size_t)i * WCT_MIX_MAX + k] = hs * ws;
+      }
+      H = h << (l - 1); W = w << (l - 1);
+    }
+  }
+
+  // the states of every live (level, frame, region), before any launch of the content chain
+  const int kind = style_kind(flags);
+  ++c->style_clock;
+  auto same_key = [](const WctStyleKey& a, const WctStyleKey& b) { return a.nslab == b.nslab && a.nsplit == b.nsplit && a.ksplit == b.ksplit; };
+  auto key_of = [&](int i, int f, int k) {
+    return wct_style_key(LEVEL_C[levels[i]], nk[i * fstride + (size_t)f * WCT_MIX_MAX + k], ns[(size_t)i * WCT_MIX_MAX + k]);
+  };
+  for (int k = 0; k < K; ++k) {
+    wct_style* st = const_cast<wct_style*>(styles[k]);
+    std::vector<StyleNeed> missing;
+    for (int i = 0; i < n_levels; ++i)
+      for (int f = 0; f < B; ++f) {
+        if (nk[i * fstride + (size_t)f * WCT_MIX_MAX + k] < 2) continue;
+        const StyleNeed n = {levels[i], key_of(i, f, k), kind};
+        StyleState* e = state_find(st, n.level, n.key, kind);
+        if (e) e->stamp = c->style_clock;
+        else if (std::none_of(missing.begin(), missing.end(), [&](const StyleNeed& m) { return m.level == n.level && same_key(m.key, n.key); }))
+          missing.push_back(n);
+      }
+    TRY(style_fill(c, st, missing));
+  }
+  std::vector<const float*> states((size_t)n_levels * fstride, nullptr);
+  for (int i = 0; i < n_levels; ++i)
+    for (int f = 0; f < B; ++f)
+      for (int k = 0; k < K; ++k) {
+        if (nk[i * fstride + (size_t)f * WCT_MIX_MAX + k] < 2) continue;
+        StyleState* e = state_find(const_cast<wct_style*>(styles[k]), levels[i], key_of(i, f, k), kind);
+        if (!e) { wct_set_error("prepared style %d: the state of relu%d_1 is gone", k, levels[i]); return WCT_ERR_STATE; }
+        states[i * fstride + (size_t)f * WCT_MIX_MAX + k] = e->buf;
+      }
+
+  TRY(ensure(c, c->mask_in, (size_t)B * Hc * Wc));
+  HIP_TRY(hipMemcpyAsync(c->mask_in.p, masks, (size_t)B * Hc * Wc, hipMemcpyHostToDevice, c->stream));
+  const float* img_c = (const float*)content;
+  const size_t nc = (size_t)B * Hc * Wc * 3;
+  if (!(flags & WCT_FLAG_IMAGES_F32)) {
+    TRY(ensure(c, c->img_c, nc * 4));
+    ProfScope ps(c, 7, 0, (double)nc * 5);
+    TRY(launch_u8_to_f32((const uint8_t*)content, (float*)c->img_c.p, nc, c->stream));
+    img_c = (const float*)c->img_c.p;
+  }
+  constexpr size_t UROW = 32 * UMAX_SLOTS;
+  TRY(ensure(c, c->umax, 7 * UROW * sizeof(unsigned)));
+  if (fuse_stats()) HIP_TRY(hipMemsetAsync(c->umax.p, 0, UROW * sizeof(unsigned), c->stream));
+  auto no_style = [](int, int, int* hs, int* ws) { *hs = *ws = 0; return (const float*)nullptr; };
+  return stylize_levels(c, img_c, B, Hc, Wc, levels, n_levels, flags, UROW * sizeof(unsigned), 1, no_style,
+                        [&](int i, int l, int C, int h, int w, const WctFeatStats&) {
+                          const int Nc = h * w;
+                          const int* Ns = &ns[(size_t)i * WCT_MIX_MAX];
+                          for (int f0 = 0; f0 < B;) {                  // a group: frames f0 .. f1 - 1, at most WCT_PLAN_PAIRS pairs
+                            const int* gnk = &nk[i * fstride + (size_t)f0 * WCT_MIX_MAX];
+                            int f1 = f0 + 1;
+                            while (f1 < B && wct_masked_batch_pairs(f1 + 1 - f0, gnk, K) <= 32) ++f1;
+                            const int G = f1 - f0;
+                            WctStyleSlots slots = {};
+                            int P = 0;
+                            for (int f = f0; f < f1; ++f)
+                              for (int k = 0; k < K; ++k)
+                                if (nk[i * fstride + (size_t)f * WCT_MIX_MAX + k] >= 2)
+                                  slots.state[P++] = states[i * fstride + (size_t)f * WCT_MIX_MAX + k];
+                            const MaskGeom g = {(const uint8_t*)c->mask_in.p + (size_t)f0 * Hc * Wc, Hc, Wc, w, 1 << (l - 1)};
+                            const float* fc = (const float*)c->feat_c.p + (size_t)f0 * Nc * C;
+                            half_t* o16 = (half_t*)c->wct_out.p + (size_t)f0 * Nc * C;
+                            const double rows = (double)G * Nc;
+                            // (the covariance stage is charged the compaction and gather as well; no style rows are read)
+                            const StageCost cost = {2.0 * C * C * rows, 6.0 * rows * C * 4, 2.0 * C * C * rows + 6.0 * C * C * C * P,
+                                                    rows * C * (4 + 2), 4.0 * rows * C * 4 + rows * C * 6};
+                            TRY(run_stages(c, wct_masked_batch_workspace_bytes(C, Nc, G, gnk, Ns, K), flags, cost, [&](int mode, int stages) {
+                              if (!stages)
+                                return launch_adain_masked_batch(fc, Nc, G, g, gnk, Ns, K, slots, C, alpha, 1e-5f, o16, nullptr, c->wct_ws.p,
+                                                                 c->wct_ws.cap, c->stream);
+                              return launch_wct_masked_batch(fc, Nc, G, g, gnk, Ns, K, slots, C, alpha, mode, -1.f, o16, nullptr, c->wct_ws.p,
+                                                             c->wct_ws.cap, stages, c->stream, c->eig_fail_dev);
+                            }));
+                            f0 = f1;
+                          }
+                          return (int)WCT_OK;
+                        }, out);
+}
+
+static int prepared_masked_flags_ok(unsigned flags) {
+  if (flags & WCT_FLAG_SWAP5) {
+    wct_set_error("mask: WCT_FLAG_SWAP5 needs the style's relu5_1 map and patches, which a handle does not hold (and style-swap is "
+                  "not a per-region affine map)");
+    return WCT_ERR_ARG;
+  }
+  if (flags & WCT_FLAG_STYLE_SHARED) { wct_set_error("mask: WCT_FLAG_STYLE_SHARED is for wct_stylize_batch_dev"); return WCT_ERR_ARG; }
+  return WCT_OK;
+}
+
+extern "C" int wct_stylize_prepared_masked_batch_dev(wct_ctx* c, const uint8_t* content, int Hc, int Wc, int B, const uint8_t* masks,
+                                                     const wct_style* const* styles, int K, const int* levels, int n_levels,
+                                                     float alpha, unsigned flags, uint8_t* out) {
+  ARG_CHECK(c && content && masks && styles && out && levels && n_levels >= 1 && n_levels <= 16 && B >= 1 && B <= 32 && Hc >= 2 && Wc >= 2);
+  TRY(prepared_masked_flags_ok(flags));
+  return stylize_prepared_masked_dev(c, content, Hc, Wc, B, masks, styles, K, levels, n_levels, alpha, flags, out);
+}
+
+// host content in, host frame out: the B = 1 case of the batch call
+extern "C" int wct_stylize_prepared_masked(wct_ctx* c, const uint8_t* content, int Hc, int Wc, const uint8_t* mask,
+                                           const wct_style* const* styles, int K, const int* levels, int n_levels, float alpha,
+                                           unsigned flags, uint8_t* out) {
+  ARG_CHECK(c && content && mask && styles && out && levels && n_levels >= 1 && n_levels <= 16 && Hc >= 2 && Wc >= 2);
+  TRY(prepared_masked_flags_ok(flags));
+  HIP_TRY(hipSetDevice(c->device));
+  TRY(eig_stale(c));
+  int Ho, Wo;
+  TRY(wct_output_size(Hc, Wc, levels, n_levels, &Ho, &Wo));
+  void* dc;
+  TRY(stage_in(c, 0, content, (size_t)Hc * Wc * 3 * ((flags & WCT_FLAG_IMAGES_F32) ? sizeof(float) : 1), &dc));
+  TRY(ensure(c, c->stage[2], (size_t)Ho * Wo * 3));
+  TRY(stylize_prepared_masked_dev(c, dc, Hc, Wc, 1, mask, styles, K, levels, n_levels, alpha, flags, (uint8_t*)c->stage[2].p));
+  TRY(fetch(c, out, c->stage[2].p, (size_t)Ho * Wo * 3));
+  return eig_status(c);
 }
 
 // ---------------------------------------------------------------------------

@@ -197,6 +197,8 @@ int launch_style_state(const float* style, int Ns, int C, const WctStyleKey& key
 // the states a transform takes in place of its style features (`prep` below): state[0], or state[k] for style k of a mix.  The
 // style pointers may then be null; Ns still names the styles' rows (the content's layout depends on them).
 struct WctStyleRef { const float* state[8]; };
+// the states of a masked batch (launch_wct_masked_batch): state[p] serves pair p = the p-th (frame, label) with >= 2 rows
+struct WctStyleSlots { const float* state[32]; };
 
 // P independent whiten-colour transforms on `s`:  out = blend(T (x - mc) + ms)
 // content [P][Nc][C], style [P][Ns][C]; out16/out32 [P][Nc][C] (either may be null).
@@ -236,7 +238,7 @@ int launch_adain_mix(const float* content, int Nc, const float* const* styles, c
 // the launches; nothing is read back), summing to Nc.  A label with nk < 2 rows passes its rows through unchanged.
 // sweeps_dev [2P]: pair p = the p-th label with nk >= 2, content 2p, style 2p + 1.
 struct MaskGeom { const uint8_t* mask; int Hm, Wm, w, stride; };
-size_t mask_compact_workspace_bytes(int N);
+size_t mask_compact_workspace_bytes(int N, int G = 1);
 // stable partition of the N rows by label: perm [N] (the rows of label 0 in order, then label 1, ...), seg_off [K + 1]
 int launch_mask_compact(const MaskGeom& g, int N, int K, int* perm, int* seg_off, void* workspace, hipStream_t s);
 size_t wct_masked_workspace_bytes(int C, int Nc, const int* nk, const int* Ns, int K);
@@ -245,6 +247,20 @@ int launch_wct_masked(const float* content, int Nc, const MaskGeom& g, const int
                       int* sweeps_dev, int stages, hipStream_t s, int* eig_fail);
 int launch_adain_masked(const float* content, int Nc, const MaskGeom& g, const int* nk, const float* const* styles, const int* Ns, int K,
                         int C, float alpha, float eps, half_t* out16, float* out32, void* workspace, size_t workspace_bytes, hipStream_t s);
+// Spatial control of G <= 32 frames on prepared styles, one launch of every stage for all of them: content and out16 / out32
+// [G][Nc][C], g.mask [G][Hm][Wm] (one label map per frame), nk [G][WCT_MIX_MAX] the rows of every label of every frame.  The
+// live (frame, label) pairs -- nk >= 2, in frame-major order, at most 32 of them -- take the content side alone; pair p's style
+// side is states.state[p], the state of style k under wct_style_key(C, nk, Ns[k]).  Frame f comes out as launch_wct_masked /
+// launch_adain_masked give it alone, bit for bit.
+size_t wct_masked_batch_workspace_bytes(int C, int Nc, int G, const int* nk, const int* Ns, int K);
+int wct_masked_batch_pairs(int G, const int* nk, int K);
+int launch_mask_compact_batch(const MaskGeom& g, int N, int K, int G, int* perm, int* seg_off, void* workspace, hipStream_t s);
+int launch_wct_masked_batch(const float* content, int Nc, int G, const MaskGeom& g, const int* nk, const int* Ns, int K,
+                            const WctStyleSlots& states, int C, float alpha, int mode, float eps, half_t* out16, float* out32,
+                            void* workspace, size_t workspace_bytes, int stages, hipStream_t s, int* eig_fail);
+int launch_adain_masked_batch(const float* content, int Nc, int G, const MaskGeom& g, const int* nk, const int* Ns, int K,
+                              const WctStyleSlots& states, int C, float alpha, float eps, half_t* out16, float* out32,
+                              void* workspace, size_t workspace_bytes, hipStream_t s);
 // Symmetric eigensolver (batched): A [nmat][C][C] is overwritten (diag -> eigenvalues),
 // V [nmat][C][C] gets eigenvectors in columns.  C multiple of 32, 32 <= C <= 1024.
 // sweeps_done_dev[m]: sweeps used (> 0) if matrix m converged, -sweeps if it was still rotating when the sweep

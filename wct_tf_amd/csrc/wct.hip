@@ -30,7 +30,8 @@
 
 template <int BC, int BP, typename Args = ApplyArgs>
 __global__ __launch_bounds__(256, 2) void apply_f16x2_kernel(Args p) {
-  constexpr bool SEG = std::is_same<Args, ApplySegArgs>::value;     // (ApplyArgs: not a line of the plain apply changes)
+  constexpr bool SEGB = std::is_same<Args, ApplySegBatchArgs>::value;   // a masked batch: per-frame seg_off / perm / rows
+  constexpr bool SEG = std::is_same<Args, ApplySegArgs>::value || SEGB;  // (ApplyArgs: not a line of the plain apply changes)
   constexpr int TM = BC / 64, TN = BP / 64;
   constexpr int MI = BC * 4 / 256, XI = BP * 4 / 256;    // 16-B (8 k) pieces per thread and stage
   __shared__ __attribute__((aligned(16))) unsigned char lm[2][BC * 64];   // M hi, lo
@@ -41,7 +42,15 @@ __global__ __launch_bounds__(256, 2) void apply_f16x2_kernel(Args p) {
   const int pair = blockIdx.z;
   const int n0 = blockIdx.x * BP, c0 = blockIdx.y * BC;
   int seg0 = 0, N = p.N;
-  if constexpr (SEG) {
+  [[maybe_unused]] int row0 = 0;                 // SEGB: the first row of the pair's frame in x, perm and the outputs
+  if constexpr (SEGB) {
+    const int f = seg_frame(p.fl[pair]), lab = seg_label(p.fl[pair]);
+    const int first = p.seg_off[f * (WCT_MIX_MAX + 1) + lab];
+    N = p.seg_off[f * (WCT_MIX_MAX + 1) + lab + 1] - first;
+    if (n0 >= N) return;
+    row0 = f * p.N;
+    seg0 = row0 + first;
+  } else if constexpr (SEG) {
     seg0 = p.seg_off[p.lab[pair]];
     N = p.seg_off[p.lab[pair] + 1] - seg0;
     if (n0 >= N) return;                         // (uniform per block: past the end of its segment)
@@ -166,6 +175,7 @@ __global__ __launch_bounds__(256, 2) void apply_f16x2_kernel(Args p) {
     for (int j = 0; j < TN; ++j) {
       const int n = n0 + (wn * TN + j) * 32 + (lane & 31);
       dst[j] = p.perm[seg0 + (n < N ? n : 0)];
+      if constexpr (SEGB) dst[j] += row0;
     }
 #pragma unroll
   for (int j = 0; j < TN; ++j) {
@@ -208,6 +218,14 @@ int launch_apply_seg(const ApplySegArgs& a, int nmax, int P, hipStream_t s) {
   const int C = a.C;
   if (C >= 128) hipLaunchKernelGGL((apply_f16x2_kernel<128, 128, ApplySegArgs>), dim3(cdiv(nmax, 128), cdiv(C, 128), P), dim3(256), 0, s, a);
   else hipLaunchKernelGGL((apply_f16x2_kernel<64, 128, ApplySegArgs>), dim3(cdiv(nmax, 128), cdiv(C, 64), P), dim3(256), 0, s, a);
+  HIP_TRY(hipGetLastError());
+  return WCT_OK;
+}
+
+int launch_apply_seg_batch(const ApplySegBatchArgs& a, int nmax, int P, hipStream_t s) {
+  const int C = a.C;
+  if (C >= 128) hipLaunchKernelGGL((apply_f16x2_kernel<128, 128, ApplySegBatchArgs>), dim3(cdiv(nmax, 128), cdiv(C, 128), P), dim3(256), 0, s, a);
+  else hipLaunchKernelGGL((apply_f16x2_kernel<64, 128, ApplySegBatchArgs>), dim3(cdiv(nmax, 128), cdiv(C, 64), P), dim3(256), 0, s, a);
   HIP_TRY(hipGetLastError());
   return WCT_OK;
 }
@@ -321,8 +339,10 @@ WctStyleKey wct_style_key(int C, int Nc, int Ns) {
 }
 size_t wct_style_state_floats(int C) { return (size_t)2 * C + (size_t)C * C; }
 
-// grid (blocks, K): state k -> mean / var slot 2k + 1 and, with_T, Tw matrix 2k + 1 (C % 4 == 0: no float4 straddles a part)
-__global__ __launch_bounds__(256) void style_load_kernel(WctStyleRef r, float* mean, float* var, float* Tw, int C, int with_T) {
+// grid (blocks, K): state k -> mean / var slot 2k + 1 and, with_T, Tw matrix 2k + 1 (C % 4 == 0: no float4 straddles a part).
+// Ref: WctStyleRef (the K styles of a call), or WctStyleSlots (a masked batch: the state of every (frame, region) pair)
+template <typename Ref>
+__global__ __launch_bounds__(256) void style_load_kernel(Ref r, float* mean, float* var, float* Tw, int C, int with_T) {
   const int k = blockIdx.y;
   const float* src = r.state[k];
   const size_t cc = (size_t)C * C, n = (size_t)2 * C + (with_T ? cc : 0), slot = (size_t)(2 * k + 1);
@@ -336,8 +356,18 @@ __global__ __launch_bounds__(256) void style_load_kernel(WctStyleRef r, float* m
 static int launch_style_load(const WctStyleRef& r, int K, const WctCarve& w, int C, bool with_T, hipStream_t s) {
   for (int k = 0; k < K; ++k) ARG_CHECK(r.state[k] != nullptr);
   const size_t n4 = ((size_t)2 * C + (with_T ? (size_t)C * C : 0)) / 4;
-  hipLaunchKernelGGL(style_load_kernel, dim3((unsigned)std::min<size_t>((n4 + 255) / 256, 256), K), dim3(256), 0, s, r, w.mean, w.var, w.Tw,
-                     C, with_T ? 1 : 0);
+  hipLaunchKernelGGL(style_load_kernel<WctStyleRef>, dim3((unsigned)std::min<size_t>((n4 + 255) / 256, 256), K), dim3(256), 0, s, r, w.mean,
+                     w.var, w.Tw, C, with_T ? 1 : 0);
+  HIP_TRY(hipGetLastError());
+  return WCT_OK;
+}
+
+int launch_style_load_slots(const WctStyleSlots& r, int P, const WctCarve& w, int C, bool with_T, hipStream_t s) {
+  ARG_CHECK(P >= 1 && P <= WCT_PLAN_PAIRS);
+  for (int p = 0; p < P; ++p) ARG_CHECK(r.state[p] != nullptr);
+  const size_t n4 = ((size_t)2 * C + (with_T ? (size_t)C * C : 0)) / 4;
+  hipLaunchKernelGGL(style_load_kernel<WctStyleSlots>, dim3((unsigned)std::min<size_t>((n4 + 255) / 256, 256), P), dim3(256), 0, s, r, w.mean,
+                     w.var, w.Tw, C, with_T ? 1 : 0);
   HIP_TRY(hipGetLastError());
   return WCT_OK;
 }

@@ -15,9 +15,14 @@ constexpr int WCT_SKIP_MIX = 2;
 // like a shared style) and WCT_SKIP_MIX_STYLE (a mix of K states: matrix 0 alone is live).  WCT_SKIP_CONTENT is the mirror image
 // that fills a state: one style in slot 1, the content slot dead, no whitening side.
 constexpr int WCT_SKIP_STYLE = 3, WCT_SKIP_CONTENT = 4, WCT_SKIP_MIX_STYLE = 5;
+// WCT_SKIP_STYLES: the batched masked transform on prepared styles (mask.hip) -- every style matrix dead as under
+// WCT_SKIP_STYLE, but each pair reads the state in its OWN style slot (neither one_style nor one_content)
+constexpr int WCT_SKIP_STYLES = 6;
 __device__ __host__ __forceinline__ bool skip_style_mat(int mat, int shared_style) {
   if (shared_style >= WCT_SKIP_STYLE)
-    return shared_style == WCT_SKIP_STYLE ? (mat & 1) != 0 : (shared_style == WCT_SKIP_CONTENT ? (mat & 1) == 0 : mat > 0);
+    return shared_style == WCT_SKIP_STYLE ? (mat & 1) != 0
+                                          : (shared_style == WCT_SKIP_CONTENT ? (mat & 1) == 0
+                                                                              : (shared_style == WCT_SKIP_MIX_STYLE ? mat > 0 : (mat & 1) != 0));
   return shared_style == WCT_SKIP_MIX ? ((mat & 1) == 0 && mat > 0) : (shared_style && (mat & 1) && mat > 1);
 }
 // which pair's slots hold the content / style moments a pair's consumers read: pair 0's for all where one is shared
@@ -67,10 +72,13 @@ static inline unsigned rows_grid(size_t N, int C) {
 
 // The slot plan of a per-slot transform (a style mix, spatial control): 2P matrix slots in the pair layout of carve(), each
 // slot's statistics and covariance launched on its own rows with the layout of its own single-pair transform (pair_layout).
+// A mix or a masked frame has at most WCT_MIX_MAX pairs; the (frame, region) pairs of a masked batch fill one batched
+// eigensolve of 64 matrices: WCT_PLAN_PAIRS.
+constexpr int WCT_PLAN_PAIRS = 32;
 struct SlotPlan {
   int P, skip, nwhite;                         // pairs; the skip mode (0 or a WCT_SKIP_*); pairs whose whitening side is live
-  struct Slot { const float* x; int n; PairLayout lay; } slot[2 * WCT_MIX_MAX];   // rows (null while only sizing the
-                                                                                 // workspace), their count (0: skipped), layout
+  struct Slot { const float* x; int n; PairLayout lay; } slot[2 * WCT_PLAN_PAIRS];   // rows (null while only sizing the
+                                                                                    // workspace), their count (0: skipped), layout
   const float* u0; const unsigned* umax0;      // slot 0's unit sums from a conv epilogue, or null
   WctCarve w;
   size_t total;
@@ -90,6 +98,11 @@ struct ApplyArgs {
 // A masked transform (launch_wct_masked): pair p is the segment of label lab[p] -- rows [seg_off[lab], seg_off[lab + 1]) of the
 // label-compacted content x -- and its row r is stored to row perm[r] of out16 / out32 (the scatter back to pixel order)
 struct ApplySegArgs : ApplyArgs { const int* seg_off; const int* perm; int lab[WCT_MIX_MAX]; };
+// The segments of a masked BATCH (launch_wct_masked_batch): x, out16 / out32 hold G frames of N rows, seg_off [G][WCT_MIX_MAX + 1]
+// and perm [G][N] are per frame, and pair p is the segment of label fl[p] & 7 of frame fl[p] >> 3
+struct ApplySegBatchArgs : ApplyArgs { const int* seg_off; const int* perm; unsigned char fl[WCT_PLAN_PAIRS]; };
+__device__ __host__ __forceinline__ int seg_frame(unsigned char fl) { return fl >> 3; }
+__device__ __host__ __forceinline__ int seg_label(unsigned char fl) { return fl & 7; }
 
 // ---- stage launchers, by the unit that holds their kernels -----------------------------------------------------------------
 // stats_gemm.hip: means and the fp16 scale (with_var: the variances) of the 2P matrices; their covariances into w.A and w.A0
@@ -110,3 +123,6 @@ int launch_spectral_function(const float* A, const float* V, float* G, float* X,
 // longest has nmax rows)
 int launch_blend(const WctCarve& w, int C, int P, float alpha, int shared_style, hipStream_t s);
 int launch_apply_seg(const ApplySegArgs& a, int nmax, int P, hipStream_t s);
+int launch_apply_seg_batch(const ApplySegBatchArgs& a, int nmax, int P, hipStream_t s);
+// wct.hip: state p of `r` into the style slot 2p + 1 of w (mean, var and, with_T, the colouring matrix), P <= WCT_PLAN_PAIRS
+int launch_style_load_slots(const WctStyleSlots& r, int P, const WctCarve& w, int C, bool with_T, hipStream_t s);

@@ -206,16 +206,17 @@ def mask_labels(grey, k, shape_hw):
     return np.uint8(g.astype(np.int32) * k // 256)
 
 
-def stylize_mask_pair(model, content, grey, styles, args):
+def stylize_mask_pair(model, content, grey, styles, args, prepared=None):
     """one output of spatial control: stylize_pair with a style per region -- CORAL per style (--keep-colors), and `--passes`
-    masked predictions, the mask resized to each pass's input (a pass's output can be larger than its input)"""
+    masked predictions, the mask resized to each pass's input (a pass's output can be larger than its input).  prepared: the
+    PreparedStyle objects of `styles` (can_prepare), or None"""
     if args.keep_colors:
         from .ops import preserve_colors_np
         styles = [preserve_colors_np(s, content, ctx=model.sess) for s in styles]
     out = content
     for _ in range(max(1, args.passes)):
-        out = model.predict_masked(out, styles, mask_labels(grey, len(styles), out.shape[:2]), args.alpha, args.adain,
-                                   args.swap5, args.ss_alpha)
+        out = model.predict_masked(out, styles if prepared is None else prepared, mask_labels(grey, len(styles), out.shape[:2]),
+                                   args.alpha, args.adain, args.swap5, args.ss_alpha)
     return out
 
 
@@ -263,14 +264,18 @@ def main(argv=None):
     if args.mask_path is not None:
         grey = load_mask(args.mask_path)
         regions = [load_style(p, args) for p in args.mask_styles]
+        # every style once for a folder of contents, not once per content (not with --keep-colors or --swap5: can_prepare)
+        prepared = [model.prepare_style(s, adain=args.adain) for s in regions] if can_prepare(args) and len(contents) > 1 else None
         for cpath in contents:
             content = utils.get_img(cpath)
             if args.content_size > 0:
                 content = utils.resize_to(content, args.content_size)
             target = os.path.join(args.out_path, mask_name(cpath, args.mask_styles))
-            utils.save_img(target, stylize_mask_pair(model, content, grey, regions, args))
+            utils.save_img(target, stylize_mask_pair(model, content, grey, regions, args, prepared))
             written += 1
             print('%d: wrote %s' % (written, target))
+        for h in prepared or []:
+            h.close()
         print('%d outputs in %.1f s' % (written, time.time() - t0))
         return written
     styles = _listing(args.style_path)

@@ -37,7 +37,7 @@ _FLAGS = [
     (('--vgg-path',), dict(default='models/vgg_normalised.t7', help='encoder weights: vgg_normalised.t7 or .npz (stylize.py:19 default)')),
     (('--in-path',), dict(required=True, help='a video file (needs ffmpeg on PATH) or a directory of frames')),
     (('--out-path',), dict(required=True, help='folder the results are written to')),
-    (('--style-path',), dict(required=True, help='style image, or a folder of them (one output per style)')),
+    (('--style-path',), dict(default=None, help='style image, or a folder of them (one output per style)')),
     (('--tmp-dir',), dict(dest='tmp_dir', default=TMP_DIR, help='scratch folder for extracted / stylized frames')),
     (('--keep-tmp',), dict(action='store_true', default=False, help='leave the scratch folder in place')),
     (('--keep-colors',), dict(action='store_true', default=False, help='CORAL: give the style the colours of each frame first')),
@@ -57,6 +57,14 @@ _FLAGS = [
     (('--fps',), dict(type=int, default=30, help='frame rate of the re-encoded video (reference: 30)')),
     (('--synthetic-weights',), dict(type=int, default=None, metavar='SEED', help='seeded synthetic weights instead of files')),
     (('--wct-mode',), dict(choices=['tf', 'np'], default='tf', help='wct_tf (the graph) or wct_np semantics')),
+    (('--mask-path',), dict(default=None, metavar='PATH',
+                            help='spatial control: one grey label map for all frames, or a directory with one map per frame '
+                                 '(matched to the frames in sorted order; the counts must agree).  Grey v picks --mask-styles image '
+                                 'v * K // 256; maps are resized (nearest) to the frame.  One output folder, '
+                                 '{video}_mask_{style0}+{style1}+...')),
+    (('--mask-styles',), dict(nargs='+', default=None, metavar='PATH',
+                              help='the K style images of --mask-path, label 0 first; replaces --style-path; not with '
+                                   '--keep-colors, --swap5 or --concat')),
 ]
 
 
@@ -74,6 +82,78 @@ def natural_key(path):
 
 def list_frames(in_dir):
     return sorted(get_files(in_dir), key=natural_key)
+
+
+def check_mask_args(parser, args):
+    """--mask-path / --mask-styles: the argument errors of a masked video (parser.error exits)."""
+    if args.mask_path is None and args.mask_styles is None:
+        if args.style_path is None:
+            parser.error('--style-path is required (or --mask-path with --mask-styles)')
+        return
+    if args.mask_path is None or args.mask_styles is None:
+        parser.error('--mask-path and --mask-styles go together')
+    if args.style_path is not None:
+        parser.error('--mask-styles replaces --style-path: give one or the other')
+    if args.keep_colors or args.swap5 or args.concat:
+        parser.error('--mask-path does not combine with --keep-colors, --swap5 or --concat')
+    if len(args.mask_styles) > 8:
+        parser.error('--mask-styles takes at most 8 styles')
+
+
+def match_masks(mask_path, frame_files):
+    """the label map file of every frame: `mask_path` is one file for all frames, or a directory whose maps are matched to the
+    frames in sorted order (natural_key) -- the counts must agree (ValueError, before any GPU work)"""
+    if not os.path.isdir(mask_path):
+        return [mask_path] * len(frame_files)
+    maps = sorted(get_files(mask_path), key=natural_key)
+    if len(maps) != len(frame_files):
+        raise ValueError('%d label maps in %s for %d frames' % (len(maps), mask_path, len(frame_files)))
+    return maps
+
+
+def stylize_frames_masked(wct_model, frame_files, mask_files, styles, args):
+    """Yield (frame_file, stylized uint8 image) in order, every frame stylized under its own label map: consecutive same-sized
+    frames go through WCT.predict_frames_masked in batches, the K styles prepared once for the whole video.  Later --passes use
+    the masked call too, the maps resized to each pass's input."""
+    from .stylize import load_mask, mask_labels
+    k = len(styles)
+    prepared = [wct_model.prepare_style(np.uint8(np.clip(s, 0, 255)) if s.dtype != np.uint8 else s, adain=args.adain) for s in styles]
+    greys = {}
+
+    def grey_of(path):
+        if path not in greys:
+            if len(greys) > 64:
+                greys.clear()
+            greys[path] = load_mask(path)
+        return greys[path]
+
+    def load(f):
+        img = get_img(f)
+        if args.content_size > 0:
+            img = resize_to(img, args.content_size)
+        return img
+
+    try:
+        i = 0
+        while i < len(frame_files):
+            first = load(frame_files[i])
+            j, group = i + 1, [first]
+            while j < len(frame_files) and len(group) < args.batch:
+                nxt = load(frame_files[j])
+                if nxt.shape != first.shape:
+                    break
+                group.append(nxt)
+                j += 1
+            out = np.stack(group)
+            for _ in range(max(1, args.passes)):
+                masks = np.stack([mask_labels(grey_of(m), k, out.shape[1:3]) for m in mask_files[i:j]])
+                out = wct_model.predict_frames_masked(out, prepared, masks, args.alpha, args.adain, batch=args.batch)
+            for f, o in zip(frame_files[i:j], out):
+                yield f, o
+            i = j
+    finally:
+        for h in prepared:
+            h.close()
 
 
 def stylize_frames(wct_model, frame_files, style_img, args):
@@ -135,16 +215,10 @@ def stylize_frames(wct_model, frame_files, style_img, args):
 def main(argv=None):
     parser = build_parser()
     args = parser.parse_args(argv)
+    check_mask_args(parser, args)
     if args.synthetic_weights is None and not args.checkpoints:
         parser.error('--checkpoints is required (stylize.py:17) unless --synthetic-weights SEED is given')
     start = time.time()
-    weights = None
-    if args.synthetic_weights is not None:
-        from .weights import synthetic_weights
-        weights = synthetic_weights(args.synthetic_weights, relu_targets=args.relu_targets)
-    wct_model = WCT(checkpoints=args.checkpoints, relu_targets=args.relu_targets, vgg_path=args.vgg_path,
-                    device=args.device, ss_patch_size=args.ss_patch_size, ss_stride=args.ss_stride,
-                    weights=weights, wct_mode=args.wct_mode)
     if args.keep_colors and args.swap5:
         raise SystemExit('--keep-colors with --swap5 is not batched here: use stylize.py per frame')
 
@@ -158,22 +232,39 @@ def main(argv=None):
         os.makedirs(in_dir, exist_ok=True)
         subprocess.check_call([ffmpeg, '-i', args.in_path, '%s/frame_%%d.png' % in_dir])
     frame_files = list_frames(in_dir)
-    style_files = get_files(args.style_path) if os.path.isdir(args.style_path) else [args.style_path]
+    masked = args.mask_path is not None
+    mask_files = match_masks(args.mask_path, frame_files) if masked else None      # (the count check: before any GPU work)
+    weights = None
+    if args.synthetic_weights is not None:
+        from .weights import synthetic_weights
+        weights = synthetic_weights(args.synthetic_weights, relu_targets=args.relu_targets)
+    wct_model = WCT(checkpoints=args.checkpoints, relu_targets=args.relu_targets, vgg_path=args.vgg_path,
+                    device=args.device, ss_patch_size=args.ss_patch_size, ss_stride=args.ss_stride,
+                    weights=weights, wct_mode=args.wct_mode)
+    style_files = [None] if masked else (get_files(args.style_path) if os.path.isdir(args.style_path) else [args.style_path])
     os.makedirs(args.out_path, exist_ok=True)
+
+    def load_style(path):
+        img = get_img(path)
+        if args.style_size > 0:
+            img = resize_to(img, args.style_size)
+        if args.crop_size > 0:
+            img = center_crop(img, args.crop_size)
+        return img
 
     content_prefix, content_ext = os.path.splitext(os.path.basename(os.path.normpath(args.in_path)))
     count = 0
     for style_fullpath in style_files:
-        style_img = get_img(style_fullpath)
-        if args.style_size > 0:
-            style_img = resize_to(style_img, args.style_size)
-        if args.crop_size > 0:
-            style_img = center_crop(style_img, args.crop_size)
-        style_prefix = os.path.splitext(os.path.basename(style_fullpath))[0]
+        if masked:
+            style_prefix = 'mask_' + '+'.join(os.path.splitext(os.path.basename(p))[0] for p in args.mask_styles)
+            results = stylize_frames_masked(wct_model, frame_files, mask_files, [load_style(p) for p in args.mask_styles], args)
+        else:
+            style_prefix = os.path.splitext(os.path.basename(style_fullpath))[0]
+            results = stylize_frames(wct_model, frame_files, load_style(style_fullpath), args)
         out_dir = os.path.join(args.tmp_dir, 'sytlized') if is_video else \
             os.path.join(args.out_path, '{}_{}'.format(content_prefix, style_prefix))
         os.makedirs(out_dir, exist_ok=True)
-        for f, stylized in stylize_frames(wct_model, frame_files, style_img, args):
+        for f, stylized in results:
             out_f = os.path.join(out_dir, os.path.basename(f))
             save_img(out_f, stylized)
             count += 1

@@ -104,11 +104,11 @@ class WCT(object):
 
     def prepare_style(self, style, adain=False):
         '''Run the style side of `style` (array in [0,255]) once, for this model's relu_targets, and keep it on the device: the
-           PreparedStyle goes wherever predict, predict_frames and predict_mix take a style image and gives the same frames bit
-           for bit, without the style encoder pass, the style statistics and the style eigendecompositions of every call.  One
-           handle serves every content size and alpha, AdaIN included (`adain` only picks what is computed up front; another
-           content size is computed on first use and kept).  Not for swap5 or predict_masked.  Close it, or the model's context,
-           to release it.'''
+           PreparedStyle goes wherever predict, predict_frames, predict_mix, predict_masked and predict_frames_masked take a
+           style image and gives the same frames bit for bit, without the style encoder pass, the style statistics and the style
+           eigendecompositions of every call.  One handle serves every content size and alpha, AdaIN included (`adain` only
+           picks what is computed up front; another content -- or region -- size is computed on first use and kept).  Not for
+           swap5.  Close it, or the model's context, to release it.'''
         return self.sess.prepare_style(style, self.relu_targets, adain=adain, wct_mode=self.wct_mode)
 
     def predict(self, content, style, alpha=1, swap5=False, ss_alpha=1, adain=False):
@@ -151,18 +151,51 @@ class WCT(object):
            "Spatial control/masking"): `mask` [H][W] holds a label 0 .. K-1 per content pixel, `styles` K images (sizes may
            differ), and at every level the pixels of label k are transformed with style k alone, with their own statistics
            (a label with fewer than 2 pixels at a level keeps that level's features).  Arrays in [0,255], returns uint8 HxWx3.
-           One style with an all-zero mask gives predict(content, style) bit for bit.  swap5 takes one style only.'''
+           One style with an all-zero mask gives predict(content, style) bit for bit.  swap5 takes one style only.
+           `styles` may be K PreparedStyle objects (prepare_style) instead: the same frame, without the K style sides; the
+           entries are all handles or all images (a mixed list is a ValueError), and swap5 takes images.'''
         from ._lib import mask_labels
-        if any(isinstance(s, PreparedStyle) for s in styles):
-            raise TypeError('predict_masked takes style images: spatial control with prepared styles is not implemented')
-        styles = [np.asarray(s) for s in styles]
+        handles, styles = split_styles(list(styles))             # ValueError: images and prepared styles in one list
         content = np.asarray(content)
+        if handles:
+            mask = mask_labels(mask, len(handles), content.shape[:2])
+            check_prepared(self.sess, handles, self.relu_targets, swap5)
+            return self.sess.stylize_prepared_masked(content, handles, mask, self.relu_targets, alpha=alpha, adain=adain,
+                                                     wct_mode=self.wct_mode)
+        styles = [np.asarray(s) for s in styles]
         mask = mask_labels(mask, len(styles), content.shape[:2])        # ValueError before any GPU call
         if swap5 and len(styles) > 1:
             raise ValueError('swap5 takes one style: style-swap is not a per-region affine map')
         content, mask = self._swap5_setup(content, mask, swap5, ss_alpha)
         return self.sess.stylize_masked(content, styles, mask, self.relu_targets, alpha=alpha, adain=adain,
                                         wct_mode=self.wct_mode, swap5=bool(swap5))
+
+    def predict_frames_masked(self, frames, styles, masks, alpha=1, adain=False, batch=16):
+        '''Spatial control of a video: same-sized frames [F][H][W][3], a label map per frame `masks` [F][H][W] (or one [H][W] map
+           used for every frame), `styles` K images -- prepared once here -- or K PreparedStyle objects.  Frame f equals
+           predict_masked(frames[f], styles, masks[f]) bit for bit; the frames go through the device in batches of `batch`
+           (<= 32), the regions of a batch sharing every launch and the eigensolves.  Returns uint8 [F][Ho][Wo][3].'''
+        from ._lib import mask_labels_frames
+        frames = np.asarray(frames)
+        if frames.ndim != 4 or frames.shape[3] != 3:
+            raise ValueError('expected [F][H][W][3] frames, got shape %s' % (frames.shape,))
+        handles, images = split_styles(list(styles))             # ValueError: images and prepared styles in one list
+        k = len(handles) or len(images)
+        masks = mask_labels_frames(masks, k, len(frames), frames.shape[1:3])    # ValueError before any GPU call
+        if handles:
+            check_prepared(self.sess, handles, self.relu_targets)
+        if frames.dtype != np.uint8:
+            frames = np.uint8(np.clip(frames, 0, 255))
+        own = [] if handles else [self.prepare_style(np.asarray(s), adain=adain) for s in images]
+        try:
+            batch = max(1, min(32, int(batch)))
+            return np.concatenate([self.sess.stylize_prepared_masked_batch(frames[i:i + batch], handles or own, masks[i:i + batch],
+                                                                           self.relu_targets, alpha=alpha, adain=adain,
+                                                                           wct_mode=self.wct_mode)
+                                   for i in range(0, len(frames), batch)], axis=0)
+        finally:
+            for h in own:
+                h.close()
 
     def predict_frames(self, frames, style, alpha=1, swap5=False, ss_alpha=1, adain=False, batch=16):
         '''Stylize same-sized frames [F][H][W][3] with ONE style image (the loop of stylize_video.py:112-121,
