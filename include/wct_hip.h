@@ -282,6 +282,43 @@ int  wct_stylize_prepared_masked_batch_dev(wct_ctx* ctx, const uint8_t* content_
                                            const uint8_t* masks_host, const wct_style* const* styles, int K, const int* levels,
                                            int n_levels, float alpha, unsigned flags, uint8_t* out_dev);
 
+/* ---- video warm start: solve each frame from the previous frame's basis --------------------
+ * stylize_video.py:112-135 calls predict() once per frame, and every call decomposes the frame's content covariances from
+ * scratch although consecutive frames have almost the same ones.  A wct_warm holds, per relu level of its set, one C x C fp32
+ * basis -- the eigenvectors of the content covariance of the LAST frame of the previous call, re-orthonormalised by one
+ * Newton-Schulz step -- and a valid bit.  A call that takes a state with a valid basis V0 rotates every content covariance of
+ * the level into it (A' = V0^T A V0, fp32), runs the same batched solver on A' from the identity, and composes V = V0 V'; all
+ * the rest of the transform is unchanged.  Such frames are NOT bit-identical to the cold ones (they meet the same tolerances).
+ *   - an invalid level (a fresh state, after wct_warm_reset, after a failure) solves cold: today's frames bit for bit;
+ *   - all B frames of a batched call start from the same stored basis ("the previous frame" is the last frame of the previous
+ *     call); given the same state a frame does not depend on the other frames of its call, and runs are bit-reproducible;
+ *   - after the call the state holds the basis of frame B - 1 for every level.  The content size may change between calls; the
+ *     set of levels of a stylize call must be the state's set, else WCT_STATUS_ARG;
+ *   - a call whose eigensolves end in WCT_STATUS_NOCONV (from the call itself if it blocks, from wct_sync or the next blocking
+ *     call after wct_stylize_prepared_batch_dev_warm) leaves every level of the state invalid: the next call is cold;
+ *   - WCT_FLAG_ADAIN (no eigensolve) and WCT_FLAG_SWAP5 (not on handles) are WCT_STATUS_ARG.  A state that is not live in THIS
+ *     ctx -- freed, or another context's -- is WCT_STATUS_STATE; it is recognised by its address and never dereferenced.  A
+ *     refusal leaves the ctx usable.  wct_warm_free of NULL, a freed or a foreign state is a no-op; wct_destroy frees what is left.
+ * wct_warm_basis: *valid and, if V_host is not NULL and the level is valid, its C x C basis (eigenvectors in columns, row-major).
+ * wct_stylize_prepared_warm / wct_stylize_prepared_batch_dev_warm: wct_stylize_prepared / wct_stylize_prepared_batch_dev with a
+ *   state (replacing the per-frame loop of stylize_video.py:112-135).
+ * wct_transform_warm: the op-level twin of wct_transform (replacing the decompositions stylize_video.py:112-135 repeats per
+ *   frame, ops.py:53-55,110,123) -- flags: WCT_FLAG_MODE_NP or 0 (wct_tf), eps the reference defaults; relu<level>_1 must be in
+ *   the state's set and have C channels, else WCT_STATUS_ARG.  Only the content solve is warm; sweeps_out as in wct_transform.
+ * The masked and the mix calls take no state. */
+typedef struct wct_warm wct_warm;
+int  wct_warm_create(wct_ctx* ctx, const int* levels, int n_levels, wct_warm** out);
+void wct_warm_free(wct_ctx* ctx, wct_warm* warm);
+int  wct_warm_reset(wct_ctx* ctx, wct_warm* warm);                      /* all levels invalid */
+int  wct_warm_basis(wct_ctx* ctx, const wct_warm* warm, int level, int* valid, float* V_host /* C*C or NULL */);
+int  wct_stylize_prepared_warm(wct_ctx* ctx, const uint8_t* content, int Hc, int Wc, const wct_style* style, const int* levels,
+                               int n_levels, float alpha, unsigned flags, wct_warm* warm, uint8_t* out);
+int  wct_stylize_prepared_batch_dev_warm(wct_ctx* ctx, const uint8_t* content_dev, int Hc, int Wc, int B, const wct_style* style,
+                                         const int* levels, int n_levels, float alpha, unsigned flags, wct_warm* warm,
+                                         uint8_t* out_dev);
+int  wct_transform_warm(wct_ctx* ctx, const float* content, int Nc, const float* style, int Ns, int C, float alpha,
+                        unsigned flags, wct_warm* warm, int level, float* out, int* sweeps_out);
+
 /* ---- decoder training (model.py:123-223, train.py:129-196) ---------------------------
  * One optimiser step of the decoder for relu<level>_1 (the encoder is frozen, model.py:202):
  *   F = enc(x); D = dec(F); F' = enc(D);

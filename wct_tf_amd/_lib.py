@@ -65,6 +65,13 @@ SIGNATURES = [
     ('wct_stylize_prepared_masked', C.c_int, [_P, _U8, C.c_int, C.c_int, _U8, _PP, C.c_int, _I, C.c_int, C.c_float, C.c_uint, _U8]),
     ('wct_stylize_prepared_masked_batch_dev', C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _U8, _PP, C.c_int, _I, C.c_int, C.c_float,
                                                         C.c_uint, _P]),
+    ('wct_warm_create', C.c_int, [_P, _I, C.c_int, _PP]),
+    ('wct_warm_free', None, [_P, _P]),
+    ('wct_warm_reset', C.c_int, [_P, _P]),
+    ('wct_warm_basis', C.c_int, [_P, _P, C.c_int, _I, _F]),
+    ('wct_stylize_prepared_warm', C.c_int, [_P, _U8, C.c_int, C.c_int, _P, _I, C.c_int, C.c_float, C.c_uint, _P, _U8]),
+    ('wct_stylize_prepared_batch_dev_warm', C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _I, C.c_int, C.c_float, C.c_uint, _P, _P]),
+    ('wct_transform_warm', C.c_int, [_P, _F, C.c_int, _F, C.c_int, C.c_int, C.c_float, C.c_uint, _P, C.c_int, _F, _I]),
     ('wct_train_step', C.c_int, [_P, C.c_int, _F, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float,
                                  C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, _F]),
     ('wct_get_decoder_layer', C.c_int, [_P, C.c_int, C.c_int, _F, _F, _F, _F]),

@@ -9,7 +9,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIB = os.path.join(HERE, 'libwct_hip.so')
 # the whiten-colour transform is one unit per stage (csrc/wct_stages.h is what they share)
-WCT_UNITS = ['stats_gemm.hip', 'eigh.hip', 'spectral.hip', 'wct.hip', 'mask.hip', 'style_swap.hip']
+WCT_UNITS = ['stats_gemm.hip', 'eigh.hip', 'spectral.hip', 'wct.hip', 'mask.hip', 'style_swap.hip', 'warm.hip']
 SOURCES = ['api.hip', 'conv.hip', 'conv_wino.hip', 'coral.hip', 'train.hip'] + WCT_UNITS
 
 

@@ -96,6 +96,86 @@ def check_prepared(ctx, styles, relu_targets, swap5=False):
     return lv
 
 
+class WarmState(object):
+    """A video warm start (wct_warm, include/wct_hip.h): per relu level the eigenvector basis of the last frame a call stylized
+    with it, from which the content eigensolves of the next call start.  Context.warm_state makes one; the stylize_prepared*
+    calls and Context.transform take it as `warm=`.  A fresh state, and one after reset(), solves cold -- today's frames bit for
+    bit; warm frames meet the same tolerances but are not bit-identical to cold ones.  Owned by its context; close() or a
+    `with` block releases it earlier."""
+
+    def __init__(self, ctx, handle, levels):
+        self.ctx, self.h, self.levels = ctx, handle, frozenset(levels)
+
+    @property
+    def closed(self):
+        return self.h is None or self.ctx is None or not getattr(self.ctx, 'h', None)
+
+    def close(self):
+        if not self.closed:
+            self.ctx.lib.wct_warm_free(self.ctx.h, self.h)
+        self.h = None
+
+    def _live(self):
+        if self.closed:
+            raise ValueError('the warm state is closed')
+
+    def reset(self):
+        """Every level invalid: the next call solves cold."""
+        self._live()
+        check(self.ctx.lib.wct_warm_reset(self.ctx.h, self.h))
+
+    def _basis(self, level, want):
+        self._live()
+        lv = _levels([level])[0]
+        if lv not in self.levels:
+            raise ValueError('the warm state serves relu levels %s, not %d' % (sorted(self.levels), lv))
+        valid = C.c_int()
+        v = np.empty((_LEVEL_C[lv], _LEVEL_C[lv]), np.float32) if want else None
+        check(self.ctx.lib.wct_warm_basis(self.ctx.h, self.h, lv, C.byref(valid), fptr(v) if want else None))
+        return bool(valid.value), v
+
+    def valid(self, level):
+        """Does `level` ('relu3_1' or 3) hold a basis?"""
+        return self._basis(level, False)[0]
+
+    def basis(self, level):
+        """The stored C x C basis of `level` (eigenvectors in columns), or None while the level is invalid."""
+        ok, v = self._basis(level, True)
+        return v if ok else None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def check_warm(ctx, warm, relu_targets, adain=False, swap5=False, level_set=True):
+    """The refusals of a call that takes a warm state, raised before any library call: AdaIN (no eigensolve) and swap5, an object
+    that is not a WarmState, a closed one, another context's, and a call whose levels are not the state's."""
+    if not isinstance(warm, WarmState):
+        raise TypeError('expected a WarmState, got %s' % type(warm).__name__)
+    if adain:
+        raise ValueError('a warm state starts eigensolves: AdaIN has none')
+    if swap5:
+        raise ValueError('a warm state goes with a prepared style, which does not serve swap5')
+    if warm.closed:
+        raise ValueError('the warm state is closed')
+    if warm.ctx is not ctx:
+        raise ValueError('the warm state belongs to another context')
+    lv = set(_levels(relu_targets))
+    if (lv != warm.levels) if level_set else not lv <= warm.levels:
+        raise ValueError('the warm state serves relu levels %s, not %s' % (sorted(warm.levels), sorted(lv)))
+    if not isinstance(warm.h, C.c_void_p):
+        raise TypeError('the warm state holds %s, not a wct_warm pointer' % type(warm.h).__name__)
+
+
 def split_styles(styles):
     """(handles, images) of a list of styles: one of the two is empty, a list that mixes PreparedStyle objects and images is a
     ValueError."""
@@ -168,8 +248,9 @@ class Context(object):
             self.set_decoder(relu, layers)
 
     # ---- op level ----------------------------------------------------------
-    def transform(self, content, style, alpha, mode, eps=-1.0, return_sweeps=False):
-        """content [Nc][C], style [Ns][C] float32 -> [Nc][C]"""
+    def transform(self, content, style, alpha, mode, eps=-1.0, return_sweeps=False, warm=None, level=None):
+        """content [Nc][C], style [Ns][C] float32 -> [Nc][C].  warm (a WarmState) with level: the content eigensolve starts from
+        the state's basis of that level (wct_transform_warm; the reference eps only)."""
         c = f32(content)
         s = f32(style)
         if c.ndim != 2 or s.ndim != 2 or c.shape[1] != s.shape[1]:
@@ -177,6 +258,16 @@ class Context(object):
         out = np.empty_like(c)
         sweeps = (C.c_int * 2)()
         self.last_sweeps = sweeps            # negative entries: that eigensolve failed (the call raises WCTNotConverged)
+        if warm is not None:
+            if level is None:
+                raise ValueError('transform(warm=...) needs the level whose basis it starts from')
+            if eps >= 0:
+                raise ValueError('transform(warm=...) takes the reference eps only')
+            check_warm(self, warm, [level], level_set=False)
+            check(self.lib.wct_transform_warm(self.h, fptr(c), c.shape[0], fptr(s), s.shape[0], c.shape[1], float(alpha),
+                                              _lib.FLAG_MODE_NP if int(mode) == _lib.WCT_NP else 0, warm.h, _levels([level])[0],
+                                              fptr(out), sweeps))
+            return (out, list(sweeps)) if return_sweeps else out
         check(self.lib.wct_transform(self.h, fptr(c), c.shape[0], fptr(s), s.shape[0], c.shape[1],
                                      float(alpha), int(mode), float(eps), fptr(out), sweeps))
         return (out, list(sweeps)) if return_sweeps else out
@@ -420,10 +511,24 @@ class Context(object):
         flags = (_lib.FLAG_ADAIN if adain else 0) | (_lib.FLAG_MODE_NP if wct_mode == 'np' else 0) | (_lib.FLAG_IMAGES_F32 if as_f32 else 0)
         return c, (C.c_int * len(lv))(*lv), np.empty((ho, wo, 3), np.uint8), flags
 
-    def stylize_prepared(self, content, style, relu_targets, alpha=1.0, adain=False, wct_mode='tf'):
-        """stylize() with a PreparedStyle in the place of the style image: the same frame, bit for bit."""
+    def warm_state(self, relu_targets):
+        """A WarmState for the levels `relu_targets` (wct_warm_create): every level invalid until a call has used it."""
+        lv = sorted(set(_levels(relu_targets)))
+        h = C.c_void_p()
+        check(self.lib.wct_warm_create(self.h, (C.c_int * len(lv))(*lv), len(lv), C.byref(h)))
+        return WarmState(self, h, lv)
+
+    def stylize_prepared(self, content, style, relu_targets, alpha=1.0, adain=False, wct_mode='tf', warm=None):
+        """stylize() with a PreparedStyle in the place of the style image: the same frame, bit for bit.  warm (a WarmState):
+        the content eigensolves start from the state's bases, which then take this frame's."""
         check_prepared(self, [style], relu_targets)
+        if warm is not None:
+            check_warm(self, warm, relu_targets, adain)
         c, arr, out, flags = self._prepared_args(content, relu_targets, adain, wct_mode)
+        if warm is not None:
+            check(self.lib.wct_stylize_prepared_warm(self.h, c.ctypes.data_as(_lib._U8), c.shape[0], c.shape[1], style.h, arr,
+                                                     len(arr), float(alpha), flags, warm.h, out.ctypes.data_as(_lib._U8)))
+            return out
         check(self.lib.wct_stylize_prepared(self.h, c.ctypes.data_as(_lib._U8), c.shape[0], c.shape[1], style.h, arr, len(arr),
                                             float(alpha), flags, out.ctypes.data_as(_lib._U8)))
         return out
@@ -438,16 +543,26 @@ class Context(object):
                                                 arr, len(arr), float(alpha), flags, out.ctypes.data_as(_lib._U8)))
         return out
 
-    def stylize_prepared_batch_dev(self, content_dev, hc, wc, batch, style, relu_targets, alpha, out_dev, adain=False, wct_mode='tf'):
-        """stylize_batch_dev(shared_style=True) with a PreparedStyle: B contents resident in HBM, asynchronous."""
+    def stylize_prepared_batch_dev(self, content_dev, hc, wc, batch, style, relu_targets, alpha, out_dev, adain=False, wct_mode='tf',
+                                   warm=None):
+        """stylize_batch_dev(shared_style=True) with a PreparedStyle: B contents resident in HBM, asynchronous.  warm (a
+        WarmState): all B frames start from the state's bases, which then take those of frame B - 1."""
         lv = check_prepared(self, [style], relu_targets)
         flags = (_lib.FLAG_ADAIN if adain else 0) | (_lib.FLAG_MODE_NP if wct_mode == 'np' else 0)
+        if warm is not None:
+            check_warm(self, warm, relu_targets, adain)
+            check(self.lib.wct_stylize_prepared_batch_dev_warm(self.h, content_dev, hc, wc, batch, style.h, (C.c_int * len(lv))(*lv),
+                                                               len(lv), float(alpha), flags, warm.h, out_dev))
+            return
         check(self.lib.wct_stylize_prepared_batch_dev(self.h, content_dev, hc, wc, batch, style.h, (C.c_int * len(lv))(*lv), len(lv),
                                                       float(alpha), flags, out_dev))
 
-    def stylize_prepared_batch(self, contents_u8, style, relu_targets, alpha=1.0, adain=False, wct_mode='tf'):
-        """stylize_batch() with a PreparedStyle: contents [B][H][W][3] uint8 (B <= 32) -> [B][Ho][Wo][3] uint8."""
+    def stylize_prepared_batch(self, contents_u8, style, relu_targets, alpha=1.0, adain=False, wct_mode='tf', warm=None):
+        """stylize_batch() with a PreparedStyle: contents [B][H][W][3] uint8 (B <= 32) -> [B][Ho][Wo][3] uint8.  warm: as in
+        stylize_prepared_batch_dev."""
         check_prepared(self, [style], relu_targets)
+        if warm is not None:
+            check_warm(self, warm, relu_targets, adain)
         c = u8(contents_u8)
         assert c.ndim == 4 and c.shape[3] == 3
         B, hc, wc = c.shape[:3]
@@ -456,7 +571,7 @@ class Context(object):
         dc, do = self.dev_alloc(c.nbytes), self.dev_alloc(out.nbytes)
         try:
             self.h2d(dc, c)
-            self.stylize_prepared_batch_dev(dc, hc, wc, B, style, relu_targets, alpha, do, adain=adain, wct_mode=wct_mode)
+            self.stylize_prepared_batch_dev(dc, hc, wc, B, style, relu_targets, alpha, do, adain=adain, wct_mode=wct_mode, warm=warm)
             self.sync()
             self.d2h(out, do)
         finally:

@@ -75,6 +75,14 @@ struct wct_style {
   std::vector<StyleState> cache[6];
 };
 
+// A warm state (wct_warm_create): per level of its set the C x C basis the content eigensolves of a call start from -- the
+// re-orthonormalised eigenvectors of the last frame of the previous call -- and whether it holds one yet
+struct wct_warm {
+  unsigned level_set = 0;                            // bit l: relu<l>_1 is served
+  float* basis[6] = {nullptr};
+  bool valid[6] = {false};
+};
+
 struct wct_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -92,6 +100,8 @@ struct wct_ctx {
   DevBuf mask_in;                  // spatial control: the label map (wct_stylize_masked) or the row labels (wct_*_masked)
   std::vector<wct_style*> styles;  // the live prepared styles of this context (wct_style_prepare .. wct_style_free)
   unsigned long long style_clock = 0;   // one tick per call that takes prepared styles
+  std::vector<wct_warm*> warms;    // the live warm states of this context (wct_warm_create .. wct_warm_free)
+  std::vector<wct_warm*> warm_used;// those that took a basis from solves whose status nobody has read yet (eig_status)
 
   int* eig_fail = nullptr;         // pinned host memory mapped into the device: [2] eigenproblems that did not converge / had
                                    // non-finite input -- bumped by jacobi_finalize_kernel (then [6 size classes][3] solver
@@ -196,6 +206,12 @@ static void free_decoder(Decoder& d) {
   d = Decoder();
 }
 
+static void free_warm(wct_warm* wm) {
+  if (!wm) return;
+  for (float* b : wm->basis) if (b) hipFree(b);
+  delete wm;
+}
+
 static void free_style(wct_style* st) {
   if (!st) return;
   for (auto& lv : st->cache)
@@ -210,6 +226,8 @@ extern "C" void wct_destroy(wct_ctx* c) {
   hipStreamSynchronize(c->stream);
   for (wct_style* st : c->styles) free_style(st);
   c->styles.clear();
+  for (wct_warm* wm : c->warms) free_warm(wm);
+  c->warms.clear();
   if (c->first_w) hipFree(c->first_w);
   if (c->first_b) hipFree(c->first_b);
   if (c->first_w32) hipFree(c->first_w32);
@@ -236,8 +254,17 @@ extern "C" void wct_destroy(wct_ctx* c) {
 
 // After a stream sync: did any eigensolve since the last check fail?  The frames / features of the call are still
 // written (best effort, like LAPACK's "did not converge" info > 0), but the status is loud: WCT_STATUS_NOCONV.
+// the solves behind the bases that the warm states in c->warm_used took have been judged: a failure leaves those states cold
+static void warm_settle(wct_ctx* c, bool failed) {
+  if (failed)
+    for (wct_warm* wm : c->warm_used)
+      for (bool& v : wm->valid) v = false;
+  c->warm_used.clear();
+}
+
 static int eig_status(wct_ctx* c) {
   const int n_open = c->eig_fail[0], n_nan = c->eig_fail[1];
+  warm_settle(c, n_open || n_nan);
   if (!n_open && !n_nan) return WCT_OK;
   c->eig_fail[0] = c->eig_fail[1] = 0;
   wct_set_error("eigensolver: %d covariance matri%s still rotating after the sweep budget, %d with non-finite entries "
@@ -251,6 +278,7 @@ static int eig_status(wct_ctx* c) {
 static int eig_stale(wct_ctx* c) {
   HIP_TRY(hipStreamSynchronize(c->stream));
   const int n_open = c->eig_fail[0], n_nan = c->eig_fail[1];
+  warm_settle(c, n_open || n_nan);
   if (!n_open && !n_nan) return WCT_OK;
   c->eig_fail[0] = c->eig_fail[1] = 0;
   wct_set_error("eigensolver failures of an EARLIER asynchronous wct_stylize_batch_dev call that was not followed by wct_sync "
@@ -677,7 +705,8 @@ static int run_stages(wct_ctx* c, size_t ws_bytes, unsigned flags, const StageCo
 
 static int run_transform(wct_ctx* c, const float* fc, int Nc, const float* fs, int Ns, int C, int P,
                          float alpha, unsigned flags, float eps, half_t* out16, float* out32, int* sweeps_dev,
-                         const WctFeatStats* st = nullptr, const WctStyleRef* prep = nullptr /* a prepared style: fs may be null */) {
+                         const WctFeatStats* st = nullptr, const WctStyleRef* prep = nullptr /* a prepared style: fs may be null */,
+                         const WctWarmRef* warm = nullptr /* a warm state's basis for this level */) {
   const int shared = (flags & WCT_FLAG_STYLE_SHARED) ? 1 : 0;
   const StageCost cost = {(double)P * 2.0 * C * C * ((double)Nc + Ns), (double)P * 2.0 * ((double)Nc + Ns) * C * 4,
                           (double)P * (2.0 * C * C * Nc + 6.0 * C * C * C), (double)P * Nc * C * (4 + (out16 ? 2 : 0) + (out32 ? 4 : 0)),
@@ -685,7 +714,7 @@ static int run_transform(wct_ctx* c, const float* fc, int Nc, const float* fs, i
   return run_stages(c, wct_workspace_bytes(C, Nc, Ns, P), flags, cost, [&](int mode, int stages) {
     if (!stages) return launch_adain(fc, Nc, fs, Ns, C, P, alpha, 1e-5f, out16, out32, c->wct_ws.p, c->wct_ws.cap, c->stream, shared, st, prep);
     return launch_wct(fc, Nc, fs, Ns, C, P, alpha, mode, eps, out16, out32, c->wct_ws.p, c->wct_ws.cap, sweeps_dev, stages, c->stream,
-                      shared, c->eig_fail_dev, st, prep);
+                      shared, c->eig_fail_dev, st, prep, warm);
   });
 }
 
@@ -1608,10 +1637,22 @@ extern "C" void wct_style_free(wct_ctx* c, wct_style* st) {
 // The body of the wct_stylize_prepared* calls (their pointer and flag checks done): B contents [B][Hc][Wc][3] on the device, K
 // handles; lambda null: one style for all B (K = 1), else the mix weights of K styles (B = 1).  Asynchronous unless a handle
 // has to compute a state (style_fill), which happens before anything of the content chain is enqueued.
+static int warm_live(const wct_ctx* c, const wct_warm* wm);
 static int stylize_prepared_dev(wct_ctx* c, const void* content, int Hc, int Wc, int B, const wct_style* const* styles, int K,
-                                const float* lambda, const int* levels, int n_levels, float alpha, unsigned flags, uint8_t* out) {
+                                const float* lambda, const int* levels, int n_levels, float alpha, unsigned flags, uint8_t* out,
+                                wct_warm* warm = nullptr /* with one style (lambda null): start the content solves from it */) {
   HIP_TRY(hipSetDevice(c->device));
   for (int k = 0; k < K; ++k) TRY(style_live(c, styles[k]));
+  if (warm) {
+    TRY(warm_live(c, warm));
+    if (flags & WCT_FLAG_ADAIN) { wct_set_error("warm start: WCT_FLAG_ADAIN has no eigensolve to start"); return WCT_ERR_ARG; }
+    unsigned set = 0;
+    for (int i = 0; i < n_levels; ++i) { ARG_CHECK(levels[i] >= 1 && levels[i] <= 5); set |= 1u << levels[i]; }
+    if (set != warm->level_set) {
+      wct_set_error("warm start: the levels of the call (set 0x%x) are not the levels the state was created for (0x%x)", set, warm->level_set);
+      return WCT_ERR_ARG;
+    }
+  }
   for (int i = 0; i < n_levels; ++i) {
     ARG_CHECK(levels[i] >= 1 && levels[i] <= 5);
     for (int k = 0; k < K; ++k)
@@ -1668,9 +1709,17 @@ static int stylize_prepared_dev(wct_ctx* c, const void* content, int Hc, int Wc,
   TRY(ensure(c, c->umax, 7 * UROW * sizeof(unsigned)));
   if (fuse_stats()) HIP_TRY(hipMemsetAsync(c->umax.p, 0, UROW * sizeof(unsigned), c->stream));
   auto no_style = [](int, int, int* hs, int* ws) { *hs = *ws = 0; return (const float*)nullptr; };     // (style-swap alone asks)
+  if (warm && std::find(c->warm_used.begin(), c->warm_used.end(), warm) == c->warm_used.end()) c->warm_used.push_back(warm);
   return stylize_levels(c, img_c, B, Hc, Wc, levels, n_levels, flags, UROW * sizeof(unsigned), 1, no_style,
-                        [&](int i, int, int C, int h, int w, const WctFeatStats& st) {
+                        [&](int i, int l, int C, int h, int w, const WctFeatStats& st) {
                           const int* Ns = &ns[(size_t)i * WCT_MIX_MAX];
+                          if (!lambda && warm) {
+                            const WctWarmRef wr = {warm->basis[l], warm->valid[l] ? 1 : 0};
+                            TRY(run_transform(c, (float*)c->feat_c.p, h * w, nullptr, Ns[0], C, B, alpha, flags, -1.f,
+                                              (half_t*)c->wct_out.p, nullptr, nullptr, &st, &refs[i], &wr));
+                            warm->valid[l] = true;              // (the basis of frame B - 1 is enqueued)
+                            return (int)WCT_OK;
+                          }
                           if (!lambda)
                             return run_transform(c, (float*)c->feat_c.p, h * w, nullptr, Ns[0], C, B, alpha, flags, -1.f,
                                                  (half_t*)c->wct_out.p, nullptr, nullptr, &st, &refs[i]);
@@ -1681,7 +1730,8 @@ static int stylize_prepared_dev(wct_ctx* c, const void* content, int Hc, int Wc,
 
 // host content in, host frame out, around stylize_prepared_dev (B = 1)
 static int stylize_prepared_host(wct_ctx* c, const uint8_t* content, int Hc, int Wc, const wct_style* const* styles, int K,
-                                 const float* lambda, const int* levels, int n_levels, float alpha, unsigned flags, uint8_t* out) {
+                                 const float* lambda, const int* levels, int n_levels, float alpha, unsigned flags, uint8_t* out,
+                                 wct_warm* warm = nullptr) {
   HIP_TRY(hipSetDevice(c->device));
   TRY(eig_stale(c));
   int Ho, Wo;
@@ -1689,7 +1739,7 @@ static int stylize_prepared_host(wct_ctx* c, const uint8_t* content, int Hc, int
   void* dc;
   TRY(stage_in(c, 0, content, (size_t)Hc * Wc * 3 * ((flags & WCT_FLAG_IMAGES_F32) ? sizeof(float) : 1), &dc));
   TRY(ensure(c, c->stage[2], (size_t)Ho * Wo * 3));
-  TRY(stylize_prepared_dev(c, dc, Hc, Wc, 1, styles, K, lambda, levels, n_levels, alpha, flags, (uint8_t*)c->stage[2].p));
+  TRY(stylize_prepared_dev(c, dc, Hc, Wc, 1, styles, K, lambda, levels, n_levels, alpha, flags, (uint8_t*)c->stage[2].p, warm));
   TRY(fetch(c, out, c->stage[2].p, (size_t)Ho * Wo * 3));
   return eig_status(c);
 }
@@ -1715,6 +1765,121 @@ extern "C" int wct_stylize_prepared_mix(wct_ctx* c, const uint8_t* content, int 
   TRY(mix_weights(weights, K, lambda));
   TRY(style_flags_ok(flags));
   return stylize_prepared_host(c, content, Hc, Wc, styles, K, lambda, levels, n_levels, alpha, flags, out);
+}
+
+// ---------------------------------------------------------------------------
+// video warm start (stylize_video.py:112-135 calls predict() per frame and solves every content covariance from scratch): the
+// content eigensolves of a call start from the eigenvectors of the previous call's last frame (csrc/warm.hip)
+// ---------------------------------------------------------------------------
+static int warm_live(const wct_ctx* c, const wct_warm* wm) {
+  if (wm && std::find(c->warms.begin(), c->warms.end(), wm) != c->warms.end()) return WCT_OK;
+  wct_set_error("warm state %p is not a live state of this context (freed, or created by another context)", (const void*)wm);
+  return WCT_ERR_STATE;
+}
+
+extern "C" int wct_warm_create(wct_ctx* c, const int* levels, int n_levels, wct_warm** out) {
+  ARG_CHECK(c && levels && out && n_levels >= 1 && n_levels <= 16);
+  *out = nullptr;
+  for (int i = 0; i < n_levels; ++i) ARG_CHECK(levels[i] >= 1 && levels[i] <= 5);
+  HIP_TRY(hipSetDevice(c->device));
+  struct Guard { wct_warm* wm; ~Guard() { free_warm(wm); } } g = {new wct_warm()};
+  for (int i = 0; i < n_levels; ++i) {
+    const int l = levels[i];
+    if (g.wm->basis[l]) continue;
+    g.wm->level_set |= 1u << l;
+    if (hipMalloc((void**)&g.wm->basis[l], (size_t)LEVEL_C[l] * LEVEL_C[l] * sizeof(float)) != hipSuccess) {
+      wct_set_error("hipMalloc failed (warm state, relu%d_1)", l);
+      return WCT_ERR_NOMEM;
+    }
+  }
+  c->warms.push_back(g.wm);
+  *out = g.wm;
+  g.wm = nullptr;
+  return WCT_OK;
+}
+
+extern "C" void wct_warm_free(wct_ctx* c, wct_warm* wm) {
+  if (!c || !wm) return;
+  auto it = std::find(c->warms.begin(), c->warms.end(), wm);
+  if (it == c->warms.end()) return;                       // not ours, or freed already
+  hipSetDevice(c->device);
+  hipStreamSynchronize(c->stream);                        // frames in flight may still read its bases
+  c->warms.erase(it);
+  c->warm_used.erase(std::remove(c->warm_used.begin(), c->warm_used.end(), wm), c->warm_used.end());
+  free_warm(wm);
+}
+
+extern "C" int wct_warm_reset(wct_ctx* c, wct_warm* wm) {
+  ARG_CHECK(c != nullptr);
+  TRY(warm_live(c, wm));
+  for (bool& v : wm->valid) v = false;
+  return WCT_OK;
+}
+
+extern "C" int wct_warm_basis(wct_ctx* c, const wct_warm* wm, int level, int* valid, float* V_host) {
+  ARG_CHECK(c && valid);
+  TRY(warm_live(c, wm));
+  if (level < 1 || level > 5 || !(wm->level_set & (1u << level))) {
+    wct_set_error("warm state: relu%d_1 is not in the state's level set", level);
+    return WCT_ERR_ARG;
+  }
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  *valid = wm->valid[level] ? 1 : 0;
+  if (V_host && wm->valid[level]) TRY(fetch(c, V_host, wm->basis[level], (size_t)LEVEL_C[level] * LEVEL_C[level] * sizeof(float)));
+  return WCT_OK;
+}
+
+extern "C" int wct_stylize_prepared_warm(wct_ctx* c, const uint8_t* content, int Hc, int Wc, const wct_style* style, const int* levels,
+                                         int n_levels, float alpha, unsigned flags, wct_warm* warm, uint8_t* out) {
+  ARG_CHECK(c && content && out && levels && n_levels >= 1 && n_levels <= 16);
+  TRY(style_flags_ok(flags));
+  TRY(warm_live(c, warm));
+  return stylize_prepared_host(c, content, Hc, Wc, &style, 1, nullptr, levels, n_levels, alpha, flags, out, warm);
+}
+
+extern "C" int wct_stylize_prepared_batch_dev_warm(wct_ctx* c, const uint8_t* content, int Hc, int Wc, int B, const wct_style* style,
+                                                   const int* levels, int n_levels, float alpha, unsigned flags, wct_warm* warm,
+                                                   uint8_t* out) {
+  ARG_CHECK(c && content && out && levels && n_levels >= 1 && n_levels <= 16 && B >= 1 && B <= 32);
+  TRY(style_flags_ok(flags));
+  TRY(warm_live(c, warm));
+  return stylize_prepared_dev(c, content, Hc, Wc, B, &style, 1, nullptr, levels, n_levels, alpha, flags, out, warm);
+}
+
+// the op-level twin of wct_transform: one (content, style) pair of feature matrices, the content solve started from the
+// state's basis of `level`
+extern "C" int wct_transform_warm(wct_ctx* c, const float* content, int Nc, const float* style, int Ns, int C, float alpha,
+                                  unsigned flags, wct_warm* warm, int level, float* out, int* sweeps_out) {
+  ARG_CHECK(c && content && style && out);
+  TRY(warm_live(c, warm));
+  if (flags & (WCT_FLAG_ADAIN | WCT_FLAG_SWAP5 | WCT_FLAG_STYLE_SHARED | WCT_FLAG_IMAGES_F32)) {
+    wct_set_error("wct_transform_warm: the flags take WCT_FLAG_MODE_NP alone (AdaIN has no eigensolve, style-swap no warm start)");
+    return WCT_ERR_ARG;
+  }
+  if (level < 1 || level > 5 || !(warm->level_set & (1u << level))) {
+    wct_set_error("warm state: relu%d_1 is not in the state's level set", level);
+    return WCT_ERR_ARG;
+  }
+  if (C != LEVEL_C[level]) {
+    wct_set_error("warm state: relu%d_1 has %d channels, the features have %d", level, LEVEL_C[level], C);
+    return WCT_ERR_ARG;
+  }
+  HIP_TRY(hipSetDevice(c->device));
+  TRY(eig_stale(c));
+  void *dc, *ds;
+  TRY(stage_in(c, 0, content, (size_t)Nc * C * 4, &dc));
+  TRY(stage_in(c, 1, style, (size_t)Ns * C * 4, &ds));
+  TRY(ensure(c, c->stage[2], (size_t)Nc * C * 4));
+  TRY(ensure(c, c->stage[3], 256));
+  c->warm_used.push_back(warm);
+  const WctWarmRef wr = {warm->basis[level], warm->valid[level] ? 1 : 0};
+  TRY(run_transform(c, (float*)dc, Nc, (float*)ds, Ns, C, 1, alpha, flags, -1.f, nullptr, (float*)c->stage[2].p, (int*)c->stage[3].p,
+                    nullptr, nullptr, &wr));
+  warm->valid[level] = true;
+  TRY(fetch(c, out, c->stage[2].p, (size_t)Nc * C * 4));
+  if (sweeps_out) TRY(fetch(c, sweeps_out, c->stage[3].p, 2 * sizeof(int)));
+  return eig_status(c);
 }
 
 // Spatial control of B frames on prepared styles: one label map per frame (on the HOST: every level's labels are counted here,

@@ -200,6 +200,10 @@ struct WctStyleRef { const float* state[8]; };
 // the states of a masked batch (launch_wct_masked_batch): state[p] serves pair p = the p-th (frame, label) with >= 2 rows
 struct WctStyleSlots { const float* state[32]; };
 
+// Video warm start (warm.hip): the C x C basis a level's content eigensolves start from when `valid`, and which takes the
+// re-orthonormalised eigenvectors of the call's LAST content matrix either way
+struct WctWarmRef { float* basis; int valid; };
+
 // P independent whiten-colour transforms on `s`:  out = blend(T (x - mc) + ms)
 // content [P][Nc][C], style [P][Ns][C]; out16/out32 [P][Nc][C] (either may be null).
 size_t wct_workspace_bytes(int C, int Nc, int Ns, int P);
@@ -211,7 +215,9 @@ int launch_wct(const float* content, int Nc, const float* style, int Ns, int C, 
                int* eig_fail /* device-visible status words: [2] (not converged, non-finite), bumped by the eigensolver,
                                 then [6 size classes][3] solver statistics; or null */,
                const struct WctFeatStats* stats = nullptr /* unit sums / maxima a conv epilogue left beside the features */,
-               const struct WctStyleRef* prep = nullptr /* one prepared style for all P pairs (shared_style is ignored) */);
+               const struct WctStyleRef* prep = nullptr /* one prepared style for all P pairs (shared_style is ignored) */,
+               const struct WctWarmRef* warm = nullptr /* start the P content eigensolves from a stored basis (plain pairs or a
+                                                          prepared style only) */);
 // WCT_STAGE_EIG_FP32UPDATE (with WCT_STAGE_EIG): the eigensolver's tile updates on fp32 MFMA instead of split fp16 -- style-swap, whose
 // patch matching is an argmax over the whitened features (csrc/jacobi_dev.h r4::fused_u)
 enum { WCT_STAGE_COV = 1, WCT_STAGE_EIG = 2, WCT_STAGE_APPLY = 4, WCT_STAGE_ALL = 7, WCT_STAGE_EIG_FP32UPDATE = 8 };

@@ -961,6 +961,8 @@ struct JacobiGroup {
   float tol_fn;                // > 0: also stop on the measured residual (callers that complete f(A) to first order)
   int* fail;                   // device view of the caller's failure words [2], or null
   int* stats;                  // device view of the caller's statistics slot [3] for matrices of this size class, or null
+  int check_from = 2;          // the host reads the done-flags after sweep check_from and every later one.  2: matrices solved from
+                               // the identity are never done earlier; a warm solve (launch_eig_stage) sets 0
 };
 
 // per host thread (= per ctx user) and device: pinned copies of the convergence flags, the event behind them, and the V pass's
@@ -1127,7 +1129,7 @@ static int jacobi_run_fused(JacobiGroup& G, int C) {
       if ((rc = jacobi_segment_end(G, C, half, nblk - 1))) return rc;
     }
     jacobi_measure(G, C, JacobiCheckArgs{0, JACOBI_CONV_TOL, G.tol_fn, G.cur, G.segs, max_sweeps - 3, JACOBI_ROW_K});
-    if (host && sweep >= 2 && sweep + 1 < max_sweeps) {
+    if (host && sweep >= G.check_from && sweep + 1 < max_sweeps) {
       HIP_TRY(hipEventRecord(host->ev, G.stream));      // (behind the sweep's jacobi_check_kernel, which stored the flags)
       pending = true;
     }
@@ -1191,10 +1193,10 @@ int launch_jacobi_eigh(float* A, float* V, int C, int nmat, void* workspace, siz
 }
 
 // the eigensolve stage of a transform: the 2P matrices of w in one batched solve, minus those the skip mode drops
-int launch_eig_stage(const WctCarve& w, int C, int P, int skip, int u_f16, int* sweeps_dev, int* eig_fail, hipStream_t s) {
+int launch_eig_stage(const WctCarve& w, int C, int P, int skip, int u_f16, int* sweeps_dev, int* eig_fail, hipStream_t s, int check_from) {
   JacobiGroup G;
   int rc;
   if ((rc = jacobi_make_group(&G, w.A, w.V, C, 2 * P, w.jacobi_ws, w.jacobi_bytes, sweeps_dev, eig_fail, s))) return rc;
-  G.shared_style = skip; G.tol_fn = JACOBI_TOL_FN_WCT; G.u_f16 = u_f16;
+  G.shared_style = skip; G.tol_fn = JACOBI_TOL_FN_WCT; G.u_f16 = u_f16; G.check_from = check_from;
   return jacobi_dispatch(G, C);
 }

@@ -412,8 +412,10 @@ int launch_style_state(const float* style, int Ns, int C, const WctStyleKey& key
 
 int launch_wct(const float* content, int Nc, const float* style, int Ns, int C, int P, float alpha, int mode, float eps_in,
                half_t* out16, float* out32, void* workspace, size_t workspace_bytes, int* sweeps_dev,
-               int stages, hipStream_t s, int shared_style, int* eig_fail, const WctFeatStats* stats, const WctStyleRef* prep) {
+               int stages, hipStream_t s, int shared_style, int* eig_fail, const WctFeatStats* stats, const WctStyleRef* prep,
+               const WctWarmRef* warm) {
   ARG_CHECK(C % 32 == 0 && C >= 32 && C <= 1024 && Nc >= 2 && Ns >= 2 && P >= 1 && P <= 32);
+  ARG_CHECK(!warm || (warm->basis && (shared_style == 0 || prep)));
   if (prep) shared_style = WCT_SKIP_STYLE;       // (the style rows are not read: `style` may be null)
   ARG_CHECK(mode == WCT_MODE_NP || mode == WCT_MODE_TF);
   // the covariance kernel addresses one feature map through a buffer resource with 32-bit byte offsets
@@ -425,9 +427,16 @@ int launch_wct(const float* content, int Nc, const float* style, int Ns, int C, 
     if ((rc = launch_means(content, Nc, style, Ns, C, P, w, false, shared_style, s, stats))) return rc;
     if ((rc = launch_cov(content, Nc, style, Ns, C, P, w, cov_eps(mode, eps_in), shared_style, s))) return rc;
   }
-  if ((stages & WCT_STAGE_EIG) &&
-      (rc = launch_eig_stage(w, C, P, shared_style, (stages & WCT_STAGE_EIG_FP32UPDATE) ? 0 : 1, sweeps_dev, eig_fail, s)))
-    return rc;
+  if (stages & WCT_STAGE_EIG) {
+    // a warm start (warm.hip): the content matrices rotated into the stored basis, the same solve on them, the bases composed --
+    // and the last content's eigenvectors, re-orthonormalised, kept for the next call (after a cold solve as well)
+    const bool rotate = warm && warm->valid;
+    if (rotate && (rc = launch_warm_rotate(w, C, P, warm->basis, s))) return rc;
+    if ((rc = launch_eig_stage(w, C, P, shared_style, (stages & WCT_STAGE_EIG_FP32UPDATE) ? 0 : 1, sweeps_dev, eig_fail, s, rotate ? 0 : 2)))
+      return rc;
+    if (rotate && (rc = launch_warm_compose(w, C, P, warm->basis, s))) return rc;
+    if (warm && (rc = launch_warm_store(w.V + (size_t)2 * (P - 1) * C * C, w.X, warm->basis, C, s))) return rc;
+  }
   if (!(stages & WCT_STAGE_APPLY)) return WCT_OK;
 
   if (prep && (rc = launch_style_load(*prep, 1, w, C, true, s))) return rc;

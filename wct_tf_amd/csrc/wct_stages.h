@@ -113,7 +113,9 @@ int launch_cov(const float* content, int Nc, const float* style, int Ns, int C, 
                hipStream_t s);
 int launch_plan_stats(const SlotPlan& sp, int C, bool with_var, bool with_cov, float eps, hipStream_t s);
 // eigh.hip: the 2P matrices of w in one batched solve
-int launch_eig_stage(const WctCarve& w, int C, int P, int skip, int u_f16, int* sweeps_dev, int* eig_fail, hipStream_t s);
+// (check_from: the first sweep after which the host looks at the done-flags -- JacobiGroup::check_from; a warm solve passes 0)
+int launch_eig_stage(const WctCarve& w, int C, int P, int skip, int u_f16, int* sweeps_dev, int* eig_fail, hipStream_t s,
+                     int check_from = 2);
 // spectral.hip: the refresh of the rotated matrices, the merged spectral tail of a level, one spectral function (style-swap)
 int launch_refresh(const WctCarve& w, int C, int P, int shared_style, hipStream_t s, bool always = false);
 int launch_spectral_tail(const WctCarve& w, int C, int P, float alpha, int mode, float eps_in, int shared_style, int nwhite, hipStream_t s);
@@ -124,5 +126,10 @@ int launch_spectral_function(const float* A, const float* V, float* G, float* X,
 int launch_blend(const WctCarve& w, int C, int P, float alpha, int shared_style, hipStream_t s);
 int launch_apply_seg(const ApplySegArgs& a, int nmax, int P, hipStream_t s);
 int launch_apply_seg_batch(const ApplySegBatchArgs& a, int nmax, int P, hipStream_t s);
+// warm.hip (video warm start): A' = V0^T A V0 of the P content matrices of w in place (w.X scratch); V = V0 V' of the same in place
+// (w.X scratch); basis = V (3 I - V^T V) / 2 of one C x C matrix (scratch: C x C floats)
+int launch_warm_rotate(const WctCarve& w, int C, int P, const float* V0, hipStream_t s);
+int launch_warm_compose(const WctCarve& w, int C, int P, const float* V0, hipStream_t s);
+int launch_warm_store(const float* V, float* scratch, float* basis, int C, hipStream_t s);
 // wct.hip: state p of `r` into the style slot 2p + 1 of w (mean, var and, with_T, the colouring matrix), P <= WCT_PLAN_PAIRS
 int launch_style_load_slots(const WctStyleSlots& r, int P, const WctCarve& w, int C, bool with_T, hipStream_t s);

@@ -62,6 +62,11 @@ _FLAGS = [
                                  '(matched to the frames in sorted order; the counts must agree).  Grey v picks --mask-styles image '
                                  'v * K // 256; maps are resized (nearest) to the frame.  One output folder, '
                                  '{video}_mask_{style0}+{style1}+...')),
+    (('--warm-start',), dict(action='store_true',
+                             help='start the content eigensolves of every batch from the last frame of the batch before it (one '
+                                  'state for the whole video; frames within tolerance of the cold ones, not bit-identical).  Needs '
+                                  'the prepared-style path: not with --keep-colors, --swap5, --adain or --mask-path.  Later --passes '
+                                  'run cold')),
     (('--mask-styles',), dict(nargs='+', default=None, metavar='PATH',
                               help='the K style images of --mask-path, label 0 first; replaces --style-path; not with '
                                    '--keep-colors, --swap5 or --concat')),
@@ -98,6 +103,16 @@ def check_mask_args(parser, args):
         parser.error('--mask-path does not combine with --keep-colors, --swap5 or --concat')
     if len(args.mask_styles) > 8:
         parser.error('--mask-styles takes at most 8 styles')
+
+
+def check_warm_args(parser, args):
+    """--warm-start: the combinations it refuses (parser.error exits)"""
+    if not args.warm_start:
+        return
+    for flag, on in (('--keep-colors', args.keep_colors), ('--swap5', args.swap5), ('--adain', args.adain),
+                     ('--mask-path', args.mask_path is not None)):
+        if on:
+            parser.error('--warm-start does not combine with %s' % flag)
 
 
 def match_masks(mask_path, frame_files):
@@ -171,9 +186,12 @@ def stylize_frames(wct_model, frame_files, style_img, args):
         prepared = wct_model.prepare_style(np.uint8(np.clip(style_img, 0, 255)) if style_img.dtype != np.uint8 else style_img,
                                            adain=args.adain)
 
+    # --warm-start: one state for the whole video, kept across frame-size groups (a covariance is C x C whatever the frame size)
+    warm = wct_model.warm_state() if getattr(args, 'warm_start', False) else None
+
     def run(frames, style):
         style = prepared if prepared is not None else style
-        out = wct_model.predict_frames(frames, style, args.alpha, args.swap5, args.ss_alpha, args.adain, batch=args.batch)
+        out = wct_model.predict_frames(frames, style, args.alpha, args.swap5, args.ss_alpha, args.adain, batch=args.batch, warm=warm)
         for _ in range(args.passes - 1):                      # later passes: plain WCT, as stylize_video.py:124-126
             out = wct_model.predict_frames(out, style, args.alpha, adain=args.adain, batch=args.batch)
         return out
@@ -208,6 +226,8 @@ def stylize_frames(wct_model, frame_files, style_img, args):
             if args.concat:                                   # stylize_video.py:129-132
                 o = np.hstack([_imresize(s, (o.shape[0], o.shape[0])), o])
             yield f, o
+    if warm is not None:
+        warm.close()
     if prepared is not None:
         prepared.close()
 
@@ -216,6 +236,7 @@ def main(argv=None):
     parser = build_parser()
     args = parser.parse_args(argv)
     check_mask_args(parser, args)
+    check_warm_args(parser, args)
     if args.synthetic_weights is None and not args.checkpoints:
         parser.error('--checkpoints is required (stylize.py:17) unless --synthetic-weights SEED is given')
     start = time.time()

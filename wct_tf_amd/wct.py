@@ -19,7 +19,7 @@ import re
 
 import numpy as np
 
-from .context import Context, PreparedStyle, check_prepared, split_styles
+from .context import Context, PreparedStyle, check_prepared, check_warm, split_styles
 from .model import WCTModel
 from .weights import load_weights
 
@@ -111,14 +111,28 @@ class WCT(object):
            swap5.  Close it, or the model's context, to release it.'''
         return self.sess.prepare_style(style, self.relu_targets, adain=adain, wct_mode=self.wct_mode)
 
-    def predict(self, content, style, alpha=1, swap5=False, ss_alpha=1, adain=False):
+    def warm_state(self):
+        '''A WarmState for this model's relu_targets: hand it to predict / predict_frames (with a PreparedStyle) as `warm=` and
+           the content eigensolves of a call start from the bases the previous call left in it.  For the frames of ONE video, in
+           order: the frames meet the tolerances of cold ones but are not bit-identical to them.'''
+        return self.sess.warm_state(self.relu_targets)
+
+    def _check_warm(self, warm, style, swap5, adain):
+        if not isinstance(style, PreparedStyle):
+            raise ValueError('a warm state goes with a PreparedStyle (prepare_style), not a style image')
+        check_warm(self.sess, warm, self.relu_targets, adain, swap5)
+
+    def predict(self, content, style, alpha=1, swap5=False, ss_alpha=1, adain=False, warm=None):
         '''Stylize a single content/style pair; arrays in [0,255], returns uint8 HxWx3.
            The /255 preprocess and the clip*255 postprocess run inside the library
-           (fused at the ends of the kernel chain).  `style` may be a PreparedStyle (prepare_style).'''
+           (fused at the ends of the kernel chain).  `style` may be a PreparedStyle (prepare_style); with one, `warm` may be a
+           WarmState (warm_state).'''
+        if warm is not None:
+            self._check_warm(warm, style, swap5, adain)                           # ValueError before any GPU call
         if isinstance(style, PreparedStyle):
             check_prepared(self.sess, [style], self.relu_targets, swap5)          # ValueError before any GPU call
             return self.sess.stylize_prepared(np.asarray(content), style, self.relu_targets, alpha=alpha, adain=adain,
-                                              wct_mode=self.wct_mode)
+                                              wct_mode=self.wct_mode, warm=warm)
         content, _ = self._swap5_setup(np.asarray(content), None, swap5, ss_alpha)
         style = np.asarray(style)
         # uint8 arrays take the fused /255 on the device; float arrays are divided by 255 WITHOUT rounding, as the
@@ -197,13 +211,17 @@ class WCT(object):
             for h in own:
                 h.close()
 
-    def predict_frames(self, frames, style, alpha=1, swap5=False, ss_alpha=1, adain=False, batch=16):
+    def predict_frames(self, frames, style, alpha=1, swap5=False, ss_alpha=1, adain=False, batch=16, warm=None):
         '''Stylize same-sized frames [F][H][W][3] with ONE style image (the loop of stylize_video.py:112-121,
            which calls predict() once per frame and so re-runs the style encoder, the style statistics and the
            style eigendecompositions every frame).  Here the style side runs once per batch of `batch` frames;
            every frame equals predict(frame, style) bit for bit.  Returns uint8 [F][Ho][Wo][3].
-           With a PreparedStyle (prepare_style) the style side does not run at all; the frames are the same.'''
+           With a PreparedStyle (prepare_style) the style side does not run at all; the frames are the same.
+           With a PreparedStyle and `warm` (a WarmState) every batch starts its content eigensolves from the last frame of the
+           batch before it (the state's, for the first): frames within tolerance of the cold ones, not bit-identical.'''
         frames = np.asarray(frames)
+        if warm is not None:
+            self._check_warm(warm, style, swap5, adain)                           # ValueError before any GPU call
         if isinstance(style, PreparedStyle):
             check_prepared(self.sess, [style], self.relu_targets, swap5)          # ValueError before any GPU call
             assert frames.ndim == 4
@@ -211,7 +229,7 @@ class WCT(object):
                 frames = np.uint8(np.clip(frames, 0, 255))
             batch = max(1, min(32, int(batch)))
             return np.concatenate([self.sess.stylize_prepared_batch(frames[i:i + batch], style, self.relu_targets, alpha=alpha,
-                                                                    adain=adain, wct_mode=self.wct_mode)
+                                                                    adain=adain, wct_mode=self.wct_mode, warm=warm)
                                    for i in range(0, len(frames), batch)], axis=0)
         style = np.asarray(style)
         assert frames.ndim == 4 and style.ndim == 3
