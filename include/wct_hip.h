@@ -51,9 +51,13 @@ enum wct_flags {
   WCT_FLAG_STYLE_SHARED = 8, /* wct_stylize_batch_dev only: `style` is ONE image shared by all B pairs (stylize_video.py
                               keeps one style for every frame but re-runs it per frame, stylize_video.py:88-106);
                               the style pass, statistics and eigensystems run once per call, results are identical */
-  WCT_FLAG_IMAGES_F32 = 16  /* content / style point at float32 images already in [0,1] (WCT.preprocess applied by the
+  WCT_FLAG_IMAGES_F32 = 16, /* content / style point at float32 images already in [0,1] (WCT.preprocess applied by the
                               caller: a FLOAT input of predict() is divided by 255 without rounding, wct.py:60-64)
                               instead of uint8 ones; the output stays uint8 */
+  WCT_FLAG_CONTENT_COLORS = 32 /* luminance-only colour preservation: every frame keeps its stylized luminance and takes the
+                              colours of its content (see wct_content_colors).  Honoured by every wct_stylize* call, with
+                              any of the flags above; the frame equals wct_content_colors(the unflagged frame, the content)
+                              bit for bit.  Without the flag nothing changes */
 };
 
 /* ---- lifecycle: replaces WCT.__init__'s tf.Session setup (wct.py:29-44) ---- */
@@ -183,6 +187,25 @@ int wct_coral_apply(wct_ctx* ctx, const uint8_t* src, int H, int W, const double
                     const double src_mean[3], const double src_std[3],
                     const double tgt_mean[3], const double tgt_std[3],
                     uint8_t* out_u8, double* out_f64);
+/* Luminance-only colour preservation (Gatys et al. 2016, "Preserving Color in Neural Artistic Style Transfer", luminance-only
+ * transfer in its post-hoc form; jcjohnson/neural-style's -original_colors).  The reference's own answer to the same need is
+ * CORAL on the style (utils.py:87-90, above), which makes the style depend on the content; this one touches the finished frame
+ * only, so it goes with every stylize call.  Integers only -- stylized s [Ho][Wo][3], content c [Hc][Wc][3], Ho >= Hc, Wo >= Wc:
+ *   p      = c[min(y, Hc - 1)][min(x, Wc - 1)]        (the clamp of the label maps: a frame can be larger than its content)
+ *   Y(q)   = 77 q.R + 150 q.G + 29 q.B                 (BT.601 x 256; the weights sum to 256)
+ *   d      = Y(s[y][x]) - Y(p)
+ *   out.ch = clamp((256 p.ch + d + 128) >> 8, 0, 255)  for ch in R, G, B; >> is arithmetic (floor)
+ * i.e. Y from s, U and V from p, for any luma-weighted YUV.  s == c gives c; a grey content gives a grey frame.
+ * WCT_FLAG_CONTENT_COLORS is this rule fused into the last launch of a stylize call: s is the decoded frame under the call's
+ * output rule uint8(clip(x, 0, 1) * 255.f) (truncating), c the content bytes as given -- with WCT_FLAG_IMAGES_F32 the float
+ * content under that same output rule.  Hence  stylize(flag) == wct_content_colors(stylize(no flag), content)  bit for bit.
+ * wct_content_colors: host pointers, blocking.  wct_content_colors_batch_dev: device pointers, B = 1 .. 32 frames
+ *   [B][Ho][Wo][3] and contents [B][Hc][Wc][3], asynchronous on the ctx stream; out_dev may be stylized_dev (in place).
+ * Ho < Hc, Wo < Wc, a null pointer or B outside 1 .. 32 is WCT_STATUS_ARG and leaves the ctx usable. */
+int wct_content_colors(wct_ctx* ctx, const uint8_t* stylized, int Ho, int Wo, const uint8_t* content, int Hc, int Wc,
+                       uint8_t* out);
+int wct_content_colors_batch_dev(wct_ctx* ctx, const uint8_t* stylized_dev, int Ho, int Wo, const uint8_t* content_dev, int Hc,
+                                 int Wc, int B, uint8_t* out_dev);
 
 /* ---- the hot path: WCT.predict (wct.py:70-106) -------------------------------------
  * levels: relu levels in pipeline order, e.g. {5,4,3,2,1}.  Output size: wct_output_size. */

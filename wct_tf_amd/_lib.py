@@ -48,6 +48,8 @@ SIGNATURES = [
     ('wct_decode', C.c_int, [_P, _F, C.c_int, C.c_int, C.c_int, _F]),
     ('wct_coral_stats', C.c_int, [_P, _U8, C.c_int, C.c_int, _D]),
     ('wct_coral_apply', C.c_int, [_P, _U8, C.c_int, C.c_int, _D, _D, _D, _D, _D, _U8, _D]),
+    ('wct_content_colors', C.c_int, [_P, _U8, C.c_int, C.c_int, _U8, C.c_int, C.c_int, _U8]),
+    ('wct_content_colors_batch_dev', C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P]),
     ('wct_output_size', C.c_int, [C.c_int, C.c_int, _I, C.c_int, _I, _I]),
     ('wct_stylize', C.c_int, [_P, _U8, C.c_int, C.c_int, _U8, C.c_int, C.c_int, _I, C.c_int,
                               C.c_float, C.c_uint, _U8]),
@@ -88,7 +90,7 @@ SIGNATURES = [
 ]
 
 WCT_NP, WCT_TF = 0, 1
-FLAG_ADAIN, FLAG_MODE_NP, FLAG_SWAP5, FLAG_STYLE_SHARED, FLAG_IMAGES_F32 = 1, 2, 4, 8, 16
+FLAG_ADAIN, FLAG_MODE_NP, FLAG_SWAP5, FLAG_STYLE_SHARED, FLAG_IMAGES_F32, FLAG_CONTENT_COLORS = 1, 2, 4, 8, 16, 32
 PROF_CLASSES = ['conv3x3', 'conv_first', 'conv_last', 'pool', 'wct_cov', 'jacobi', 'wct_apply', 'other', 'conv12', 'conv_wino', 'conv_tail']
 
 _lib = None

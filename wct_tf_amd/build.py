@@ -10,7 +10,7 @@ CSRC = os.path.join(HERE, 'csrc')
 LIB = os.path.join(HERE, 'libwct_hip.so')
 # the whiten-colour transform is one unit per stage (csrc/wct_stages.h is what they share)
 WCT_UNITS = ['stats_gemm.hip', 'eigh.hip', 'spectral.hip', 'wct.hip', 'mask.hip', 'style_swap.hip', 'warm.hip']
-SOURCES = ['api.hip', 'conv.hip', 'conv_wino.hip', 'coral.hip', 'train.hip'] + WCT_UNITS
+SOURCES = ['api.hip', 'conv.hip', 'conv_wino.hip', 'coral.hip', 'colors.hip', 'train.hip'] + WCT_UNITS
 
 
 STAMP = LIB + '.src.sha256'

@@ -36,6 +36,20 @@ def _feature_args(content, styles, validate):
     return c, ss, v, (C.c_int * len(ss))(*[s.shape[0] for s in ss])
 
 
+def _color_images(stylized, content, ndim):
+    """The refusals of content_colors, before any library call: uint8 arrays [...][H][W][3] of `ndim` dimensions, the stylized
+    frame at least as large as the content.  -> both as contiguous uint8"""
+    s, c = np.asarray(stylized), np.asarray(content)
+    for name, a in (('stylized', s), ('content', c)):
+        if a.dtype != np.uint8:
+            raise ValueError('content_colors takes uint8 images, the %s one is %s' % (name, a.dtype))
+        if a.ndim != ndim or a.shape[-1] != 3 or a.size == 0:
+            raise ValueError('content_colors takes %s images, the %s one has shape %s' % ('[B][H][W][3]' if ndim == 4 else 'HxWx3', name, a.shape))
+    if s.shape[-3] < c.shape[-3] or s.shape[-2] < c.shape[-2]:
+        raise ValueError('the stylized frame %dx%d is smaller than its content %dx%d' % (s.shape[-3], s.shape[-2], c.shape[-3], c.shape[-2]))
+    return u8(s), u8(c)
+
+
 def _image_arrays(images):
     """Pointers, heights and widths of K images as C arrays."""
     k = len(images)
@@ -446,6 +460,39 @@ class Context(object):
             out64.ctypes.data_as(_lib._D) if want_f64 else None))
         return out8, out64
 
+    def content_colors(self, stylized_u8, content_u8):
+        """Luminance-only colour preservation (wct_content_colors): stylized [Ho][Wo][3] and content [Hc][Wc][3] uint8, Ho >= Hc
+        and Wo >= Wc -> uint8 [Ho][Wo][3], the luminance of `stylized` on the colours of `content` (pixel (y, x) takes content
+        pixel (min(y, Hc - 1), min(x, Wc - 1)))."""
+        s, c = _color_images(stylized_u8, content_u8, 3)
+        out = np.empty_like(s)
+        check(self.lib.wct_content_colors(self.h, s.ctypes.data_as(_lib._U8), s.shape[0], s.shape[1], c.ctypes.data_as(_lib._U8),
+                                          c.shape[0], c.shape[1], out.ctypes.data_as(_lib._U8)))
+        return out
+
+    def content_colors_batch_dev(self, stylized_dev, ho, wo, content_dev, hc, wc, batch, out_dev):
+        """content_colors for B frames resident in HBM (wct_content_colors_batch_dev): asynchronous; out_dev may be stylized_dev."""
+        check(self.lib.wct_content_colors_batch_dev(self.h, stylized_dev, int(ho), int(wo), content_dev, int(hc), int(wc), int(batch),
+                                                    out_dev))
+
+    def content_colors_batch(self, stylized_u8, contents_u8):
+        """Host arrays in, host array out: stylized [B][Ho][Wo][3] and contents [B][Hc][Wc][3] uint8 (B <= 32) -> [B][Ho][Wo][3]."""
+        s, c = _color_images(stylized_u8, contents_u8, 4)
+        if s.shape[0] != c.shape[0] or not 1 <= s.shape[0] <= _lib.BATCH_MAX:
+            raise ValueError('a batch takes 1 .. %d frames and as many contents, got %d and %d' % (_lib.BATCH_MAX, s.shape[0], c.shape[0]))
+        out = np.empty_like(s)
+        ds, dc = self.dev_alloc(s.nbytes), self.dev_alloc(c.nbytes)
+        try:
+            self.h2d(ds, s)
+            self.h2d(dc, c)
+            self.content_colors_batch_dev(ds, s.shape[1], s.shape[2], dc, c.shape[1], c.shape[2], s.shape[0], ds)     # in place
+            self.sync()
+            self.d2h(out, ds)
+        finally:
+            for p in (ds, dc):
+                self.dev_free(p)
+        return out
+
     # ---- the hot path ------------------------------------------------------
     def output_size(self, hc, wc, relu_targets):
         lv = _levels(relu_targets)
@@ -454,18 +501,20 @@ class Context(object):
         check(self.lib.wct_output_size(hc, wc, arr, len(lv), C.byref(ho), C.byref(wo)))
         return ho.value, wo.value
 
-    def stylize(self, content, style, relu_targets, alpha=1.0, adain=False, wct_mode='tf', swap5=False):
+    def stylize(self, content, style, relu_targets, alpha=1.0, adain=False, wct_mode='tf', swap5=False, content_colors=False):
         """One predict(): HxWx3 images in [0,255] in, uint8 out.  uint8 inputs go to the library as they are (the /255
         runs on the device); anything else is preprocessed exactly as the reference does -- `image / 255.` in float64
         (wct.py:60-64), cast to the float32 the graph's placeholders hold (model.py:43-44) -- and handed over as float32
-        images in [0,1] (WCT_FLAG_IMAGES_F32): a float image is NOT rounded to integer levels."""
-        c, (s,), _, arr, out, flags = self._stylize_args(content, [style], None, relu_targets, adain, wct_mode, swap5)
+        images in [0,1] (WCT_FLAG_IMAGES_F32): a float image is NOT rounded to integer levels.
+        content_colors (here and in every stylize* method): the frame keeps its luminance and takes the colours of its content
+        (WCT_FLAG_CONTENT_COLORS) -- content_colors(the plain frame, content) bit for bit, fused into the last launch."""
+        c, (s,), _, arr, out, flags = self._stylize_args(content, [style], None, relu_targets, adain, wct_mode, swap5, content_colors)
         check(self.lib.wct_stylize(self.h, c.ctypes.data_as(_lib._U8), c.shape[0], c.shape[1],
                                    s.ctypes.data_as(_lib._U8), s.shape[0], s.shape[1], arr, len(arr),
                                    float(alpha), flags, out.ctypes.data_as(_lib._U8)))
         return out
 
-    def _stylize_args(self, content, styles, validate, relu_targets, adain, wct_mode, swap5):
+    def _stylize_args(self, content, styles, validate, relu_targets, adain, wct_mode, swap5, content_colors=False):
         """The common arguments of the stylize calls: the caller's own validate(content, K) first (None: none; its result is
         returned), then the images -- all uint8 go as they are, otherwise every image is `/ 255.` in float64 and handed over as
         float32 in [0,1] -- the levels as a C int array, the output image and the flag word."""
@@ -481,7 +530,8 @@ class Context(object):
         lv = _levels(relu_targets)
         ho, wo = self.output_size(c.shape[0], c.shape[1], lv)
         flags = (_lib.FLAG_ADAIN if adain else 0) | (_lib.FLAG_MODE_NP if wct_mode == 'np' else 0) | \
-            (_lib.FLAG_SWAP5 if swap5 else 0) | (_lib.FLAG_IMAGES_F32 if as_f32 else 0)
+            (_lib.FLAG_SWAP5 if swap5 else 0) | (_lib.FLAG_IMAGES_F32 if as_f32 else 0) | \
+            (_lib.FLAG_CONTENT_COLORS if content_colors else 0)
         return c, ss, v, (C.c_int * len(lv))(*lv), np.empty((ho, wo, 3), np.uint8), flags
 
     # ---- prepared styles -----------------------------------------------------
@@ -501,14 +551,15 @@ class Context(object):
                                          flags, C.byref(h)))
         return PreparedStyle(self, h, img, lv)
 
-    def _prepared_args(self, content, relu_targets, adain, wct_mode):
+    def _prepared_args(self, content, relu_targets, adain, wct_mode, content_colors=False):
         """content, levels, output and flags of a call with prepared styles (the content as in stylize)"""
         content = np.asarray(content)
         as_f32 = content.dtype != np.uint8
         c = np.ascontiguousarray(np.asarray(content / 255.), np.float32) if as_f32 else u8(content)
         lv = _levels(relu_targets)
         ho, wo = self.output_size(c.shape[0], c.shape[1], lv)
-        flags = (_lib.FLAG_ADAIN if adain else 0) | (_lib.FLAG_MODE_NP if wct_mode == 'np' else 0) | (_lib.FLAG_IMAGES_F32 if as_f32 else 0)
+        flags = (_lib.FLAG_ADAIN if adain else 0) | (_lib.FLAG_MODE_NP if wct_mode == 'np' else 0) | \
+            (_lib.FLAG_IMAGES_F32 if as_f32 else 0) | (_lib.FLAG_CONTENT_COLORS if content_colors else 0)
         return c, (C.c_int * len(lv))(*lv), np.empty((ho, wo, 3), np.uint8), flags
 
     def warm_state(self, relu_targets):
@@ -518,13 +569,13 @@ class Context(object):
         check(self.lib.wct_warm_create(self.h, (C.c_int * len(lv))(*lv), len(lv), C.byref(h)))
         return WarmState(self, h, lv)
 
-    def stylize_prepared(self, content, style, relu_targets, alpha=1.0, adain=False, wct_mode='tf', warm=None):
+    def stylize_prepared(self, content, style, relu_targets, alpha=1.0, adain=False, wct_mode='tf', warm=None, content_colors=False):
         """stylize() with a PreparedStyle in the place of the style image: the same frame, bit for bit.  warm (a WarmState):
         the content eigensolves start from the state's bases, which then take this frame's."""
         check_prepared(self, [style], relu_targets)
         if warm is not None:
             check_warm(self, warm, relu_targets, adain)
-        c, arr, out, flags = self._prepared_args(content, relu_targets, adain, wct_mode)
+        c, arr, out, flags = self._prepared_args(content, relu_targets, adain, wct_mode, content_colors)
         if warm is not None:
             check(self.lib.wct_stylize_prepared_warm(self.h, c.ctypes.data_as(_lib._U8), c.shape[0], c.shape[1], style.h, arr,
                                                      len(arr), float(alpha), flags, warm.h, out.ctypes.data_as(_lib._U8)))
@@ -533,22 +584,23 @@ class Context(object):
                                             float(alpha), flags, out.ctypes.data_as(_lib._U8)))
         return out
 
-    def stylize_prepared_mix(self, content, styles, weights, relu_targets, alpha=1.0, adain=False, wct_mode='tf'):
+    def stylize_prepared_mix(self, content, styles, weights, relu_targets, alpha=1.0, adain=False, wct_mode='tf', content_colors=False):
         """stylize_mix() with K PreparedStyle objects in the place of the K images: the same frame, bit for bit."""
         w = _lib.mix_weights(weights, len(styles))
         check_prepared(self, styles, relu_targets)
-        c, arr, out, flags = self._prepared_args(content, relu_targets, adain, wct_mode)
+        c, arr, out, flags = self._prepared_args(content, relu_targets, adain, wct_mode, content_colors)
         hs = (C.c_void_p * len(styles))(*[s.h.value for s in styles])
         check(self.lib.wct_stylize_prepared_mix(self.h, c.ctypes.data_as(_lib._U8), c.shape[0], c.shape[1], hs, len(styles), fptr(w),
                                                 arr, len(arr), float(alpha), flags, out.ctypes.data_as(_lib._U8)))
         return out
 
     def stylize_prepared_batch_dev(self, content_dev, hc, wc, batch, style, relu_targets, alpha, out_dev, adain=False, wct_mode='tf',
-                                   warm=None):
+                                   warm=None, content_colors=False):
         """stylize_batch_dev(shared_style=True) with a PreparedStyle: B contents resident in HBM, asynchronous.  warm (a
         WarmState): all B frames start from the state's bases, which then take those of frame B - 1."""
         lv = check_prepared(self, [style], relu_targets)
-        flags = (_lib.FLAG_ADAIN if adain else 0) | (_lib.FLAG_MODE_NP if wct_mode == 'np' else 0)
+        flags = (_lib.FLAG_ADAIN if adain else 0) | (_lib.FLAG_MODE_NP if wct_mode == 'np' else 0) | \
+            (_lib.FLAG_CONTENT_COLORS if content_colors else 0)
         if warm is not None:
             check_warm(self, warm, relu_targets, adain)
             check(self.lib.wct_stylize_prepared_batch_dev_warm(self.h, content_dev, hc, wc, batch, style.h, (C.c_int * len(lv))(*lv),
@@ -557,7 +609,8 @@ class Context(object):
         check(self.lib.wct_stylize_prepared_batch_dev(self.h, content_dev, hc, wc, batch, style.h, (C.c_int * len(lv))(*lv), len(lv),
                                                       float(alpha), flags, out_dev))
 
-    def stylize_prepared_batch(self, contents_u8, style, relu_targets, alpha=1.0, adain=False, wct_mode='tf', warm=None):
+    def stylize_prepared_batch(self, contents_u8, style, relu_targets, alpha=1.0, adain=False, wct_mode='tf', warm=None,
+                               content_colors=False):
         """stylize_batch() with a PreparedStyle: contents [B][H][W][3] uint8 (B <= 32) -> [B][Ho][Wo][3] uint8.  warm: as in
         stylize_prepared_batch_dev."""
         check_prepared(self, [style], relu_targets)
@@ -571,7 +624,8 @@ class Context(object):
         dc, do = self.dev_alloc(c.nbytes), self.dev_alloc(out.nbytes)
         try:
             self.h2d(dc, c)
-            self.stylize_prepared_batch_dev(dc, hc, wc, B, style, relu_targets, alpha, do, adain=adain, wct_mode=wct_mode, warm=warm)
+            self.stylize_prepared_batch_dev(dc, hc, wc, B, style, relu_targets, alpha, do, adain=adain, wct_mode=wct_mode, warm=warm,
+                                            content_colors=content_colors)
             self.sync()
             self.d2h(out, do)
         finally:
@@ -579,12 +633,12 @@ class Context(object):
                 self.dev_free(p)
         return out
 
-    def stylize_prepared_masked(self, content, styles, mask, relu_targets, alpha=1.0, adain=False, wct_mode='tf'):
+    def stylize_prepared_masked(self, content, styles, mask, relu_targets, alpha=1.0, adain=False, wct_mode='tf', content_colors=False):
         """stylize_masked() with K PreparedStyle objects in the place of the K images: the same frame, bit for bit."""
         c0 = np.asarray(content)
         m = _lib.mask_labels(mask, len(styles), c0.shape[:2])
         check_prepared(self, styles, relu_targets)
-        c, arr, out, flags = self._prepared_args(c0, relu_targets, adain, wct_mode)
+        c, arr, out, flags = self._prepared_args(c0, relu_targets, adain, wct_mode, content_colors)
         hs = (C.c_void_p * len(styles))(*[s.h.value for s in styles])
         check(self.lib.wct_stylize_prepared_masked(self.h, c.ctypes.data_as(_lib._U8), c.shape[0], c.shape[1],
                                                    m.ctypes.data_as(_lib._U8), hs, len(styles), arr, len(arr), float(alpha), flags,
@@ -592,7 +646,7 @@ class Context(object):
         return out
 
     def stylize_prepared_masked_batch_dev(self, content_dev, hc, wc, batch, masks, styles, relu_targets, alpha, out_dev,
-                                          adain=False, wct_mode='tf'):
+                                          adain=False, wct_mode='tf', content_colors=False):
         """Spatial control of B uint8 frames resident in HBM, one label map per frame: `masks` [B][hc][wc] (or one [hc][wc] map
         for all) is a HOST array, the K PreparedStyle objects are shared by all frames.  Asynchronous; frame f is
         stylize_prepared_masked(frame f, masks[f])."""
@@ -600,7 +654,8 @@ class Context(object):
             raise ValueError('a batch takes 1 .. %d frames, got %d' % (_lib.BATCH_MAX, batch))
         m = _lib.mask_labels_frames(masks, len(styles), int(batch), (hc, wc))
         lv = check_prepared(self, styles, relu_targets)
-        flags = (_lib.FLAG_ADAIN if adain else 0) | (_lib.FLAG_MODE_NP if wct_mode == 'np' else 0)
+        flags = (_lib.FLAG_ADAIN if adain else 0) | (_lib.FLAG_MODE_NP if wct_mode == 'np' else 0) | \
+            (_lib.FLAG_CONTENT_COLORS if content_colors else 0)
         hs = (C.c_void_p * len(styles))(*[s.h.value for s in styles])
         # the upload is enqueued on the stream: the maps stay alive until sync() (include/wct_hip.h)
         self._masks_in_flight = getattr(self, '_masks_in_flight', []) + [m]
@@ -608,7 +663,8 @@ class Context(object):
                                                              len(styles), (C.c_int * len(lv))(*lv), len(lv), float(alpha), flags,
                                                              out_dev))
 
-    def stylize_prepared_masked_batch(self, contents_u8, styles, masks, relu_targets, alpha=1.0, adain=False, wct_mode='tf'):
+    def stylize_prepared_masked_batch(self, contents_u8, styles, masks, relu_targets, alpha=1.0, adain=False, wct_mode='tf',
+                                      content_colors=False):
         """Host arrays in, host array out: contents [B][H][W][3] uint8 (B <= 32), masks [B][H][W] (or one [H][W] map for all),
         K PreparedStyle objects -> [B][Ho][Wo][3] uint8."""
         c = u8(contents_u8)
@@ -624,7 +680,8 @@ class Context(object):
         dc, do = self.dev_alloc(c.nbytes), self.dev_alloc(out.nbytes)
         try:
             self.h2d(dc, c)
-            self.stylize_prepared_masked_batch_dev(dc, hc, wc, B, m, styles, relu_targets, alpha, do, adain=adain, wct_mode=wct_mode)
+            self.stylize_prepared_masked_batch_dev(dc, hc, wc, B, m, styles, relu_targets, alpha, do, adain=adain, wct_mode=wct_mode,
+                                                   content_colors=content_colors)
             self.sync()
             self.d2h(out, do)
         finally:
@@ -632,23 +689,25 @@ class Context(object):
                 self.dev_free(p)
         return out
 
-    def stylize_mix(self, content, styles, weights, relu_targets, alpha=1.0, adain=False, wct_mode='tf', swap5=False):
+    def stylize_mix(self, content, styles, weights, relu_targets, alpha=1.0, adain=False, wct_mode='tf', swap5=False,
+                    content_colors=False):
         """One predict() with a style mix at every level (wct_stylize_mix): `styles` is a list of K HxWx3 images (sizes may
         differ), `weights` [K] (None: equal).  Inputs as in stylize: all uint8 go as they are, otherwise every image is
         `/ 255.` in float64 and handed over as float32 in [0,1]."""
         c, ss, w, arr, out, flags = self._stylize_args(content, styles, lambda c, k: _lib.mix_weights(weights, k), relu_targets,
-                                                       adain, wct_mode, swap5)
+                                                       adain, wct_mode, swap5, content_colors)
         ptrs, hs, ws = _image_arrays(ss)
         check(self.lib.wct_stylize_mix(self.h, c.ctypes.data_as(_lib._U8), c.shape[0], c.shape[1], ptrs, hs, ws, len(ss), fptr(w),
                                        arr, len(arr), float(alpha), flags, out.ctypes.data_as(_lib._U8)))
         return out
 
-    def stylize_masked(self, content, styles, mask, relu_targets, alpha=1.0, adain=False, wct_mode='tf', swap5=False):
+    def stylize_masked(self, content, styles, mask, relu_targets, alpha=1.0, adain=False, wct_mode='tf', swap5=False,
+                       content_colors=False):
         """One predict() with spatial control at every level (wct_stylize_masked): `mask` [H][W] labels 0 .. K-1 of the content
         pixels, `styles` a list of K HxWx3 images (sizes may differ).  Inputs as in stylize: all uint8 go as they are,
         otherwise every image is `/ 255.` in float64 and handed over as float32 in [0,1]."""
         c, ss, m, arr, out, flags = self._stylize_args(content, styles, lambda c, k: _lib.mask_labels(mask, k, c.shape[:2]),
-                                                       relu_targets, adain, wct_mode, swap5)
+                                                       relu_targets, adain, wct_mode, swap5, content_colors)
         ptrs, hs, ws = _image_arrays(ss)
         check(self.lib.wct_stylize_masked(self.h, c.ctypes.data_as(_lib._U8), c.shape[0], c.shape[1], m.ctypes.data_as(_lib._U8),
                                           ptrs, hs, ws, len(ss), arr, len(arr), float(alpha), flags, out.ctypes.data_as(_lib._U8)))
@@ -672,18 +731,20 @@ class Context(object):
         check(self.lib.wct_d2h(self.h, arr.ctypes.data_as(C.c_void_p), src, arr.nbytes))
 
     def stylize_batch_dev(self, content_dev, hc, wc, style_dev, hs, ws, batch, relu_targets, alpha, out_dev,
-                          adain=False, wct_mode='tf', swap5=False, shared_style=False):
+                          adain=False, wct_mode='tf', swap5=False, shared_style=False, content_colors=False):
         """B pairs resident in HBM.  shared_style: style_dev holds ONE image used for every pair (fixed-style
         video): its encoder pass, statistics and eigensystems run once per call; the frames are bit-identical
         to the ones a replicated style produces."""
         lv = _levels(relu_targets)
         arr = (C.c_int * len(lv))(*lv)
         flags = (_lib.FLAG_ADAIN if adain else 0) | (_lib.FLAG_MODE_NP if wct_mode == 'np' else 0) | \
-            (_lib.FLAG_SWAP5 if swap5 else 0) | (_lib.FLAG_STYLE_SHARED if shared_style else 0)
+            (_lib.FLAG_SWAP5 if swap5 else 0) | (_lib.FLAG_STYLE_SHARED if shared_style else 0) | \
+            (_lib.FLAG_CONTENT_COLORS if content_colors else 0)
         check(self.lib.wct_stylize_batch_dev(self.h, content_dev, hc, wc, style_dev, hs, ws, batch, arr, len(lv),
                                              float(alpha), flags, out_dev))
 
-    def stylize_batch(self, contents_u8, style_u8, relu_targets, alpha=1.0, adain=False, wct_mode='tf', swap5=False):
+    def stylize_batch(self, contents_u8, style_u8, relu_targets, alpha=1.0, adain=False, wct_mode='tf', swap5=False,
+                      content_colors=False):
         """Host arrays in, host array out: contents [B][H][W][3] uint8 (B <= 32); style either one image
         [Hs][Ws][3] shared by all frames or [B][Hs][Ws][3].  Returns [B][Ho][Wo][3] uint8."""
         c = u8(contents_u8)
@@ -700,7 +761,7 @@ class Context(object):
             self.h2d(dc, c)
             self.h2d(ds, s)
             self.stylize_batch_dev(dc, hc, wc, ds, hs, ws, B, relu_targets, alpha, do, adain=adain,
-                                   wct_mode=wct_mode, swap5=swap5, shared_style=shared)
+                                   wct_mode=wct_mode, swap5=swap5, shared_style=shared, content_colors=content_colors)
             self.sync()
             self.d2h(out, do)
         finally:

@@ -1203,6 +1203,38 @@ extern "C" int wct_coral_apply(wct_ctx* c, const uint8_t* src, int H, int W, con
   return WCT_OK;
 }
 
+// Luminance-only colour preservation, op level (csrc/colors.hip): the refusals both calls share
+static int content_colors_checks(const void* stylized, int Ho, int Wo, const void* content, int Hc, int Wc, int B, const void* out) {
+  if (!stylized || !content || !out) { wct_set_error("content colours: null image pointer"); return WCT_ERR_ARG; }
+  if (B < 1 || B > 32) { wct_set_error("content colours: B = %d frames, must be 1 .. 32", B); return WCT_ERR_ARG; }
+  if (Hc < 1 || Wc < 1 || Ho < Hc || Wo < Wc) {
+    wct_set_error("content colours: a %dx%d stylized frame for a %dx%d content (the frame is never the smaller one)", Ho, Wo, Hc, Wc);
+    return WCT_ERR_ARG;
+  }
+  return WCT_OK;
+}
+
+extern "C" int wct_content_colors_batch_dev(wct_ctx* c, const uint8_t* stylized, int Ho, int Wo, const uint8_t* content, int Hc,
+                                            int Wc, int B, uint8_t* out) {
+  ARG_CHECK(c != nullptr);
+  TRY(content_colors_checks(stylized, Ho, Wo, content, Hc, Wc, B, out));
+  HIP_TRY(hipSetDevice(c->device));
+  ProfScope ps(c, 7, 0, (double)B * Ho * Wo * 3 * 2 + (double)B * Hc * Wc * 3);
+  return launch_content_colors_u8(stylized, content, B, Ho, Wo, Hc, Wc, out, c->stream);
+}
+
+extern "C" int wct_content_colors(wct_ctx* c, const uint8_t* stylized, int Ho, int Wo, const uint8_t* content, int Hc, int Wc,
+                                  uint8_t* out) {
+  ARG_CHECK(c != nullptr);
+  TRY(content_colors_checks(stylized, Ho, Wo, content, Hc, Wc, 1, out));
+  HIP_TRY(hipSetDevice(c->device));
+  void *ds, *dc;
+  TRY(stage_in(c, 0, stylized, (size_t)Ho * Wo * 3, &ds));
+  TRY(stage_in(c, 1, content, (size_t)Hc * Wc * 3, &dc));
+  TRY(wct_content_colors_batch_dev(c, (uint8_t*)ds, Ho, Wo, (uint8_t*)dc, Hc, Wc, 1, (uint8_t*)ds));    // (in place)
+  return fetch(c, out, ds, (size_t)Ho * Wo * 3);
+}
+
 // ---------------------------------------------------------------------------
 // the hot path
 // ---------------------------------------------------------------------------
@@ -1262,10 +1294,12 @@ static bool fuse_stats() {
 // decoder into the ping-pong images; then the uint8 frames into out (wct.py:66-68).
 // style_at(l, b, &hs, &ws): pair b's style features of relu<l>_1, hs x ws.  transform(i, l, C, h, w, st): level i (relu<l>_1,
 // C channels) of the h x w contents in c->feat_c -> c->wct_out (fp16), st the content's unit sums.  WCT_FLAG_SWAP5 runs the
-// style-swap at relu5_1 instead.
+// style-swap at relu5_1 instead.  WCT_FLAG_CONTENT_COLORS: the last launch puts the frames' luminance on the colours of
+// content_raw, the contents as the caller gave them ([B][Hc][Wc][3] on the device: uint8, or fp32 with WCT_FLAG_IMAGES_F32).
 template <typename StyleAt, typename Transform>
-static int stylize_levels(wct_ctx* c, const float* img_c, int B, int Hc, int Wc, const int* levels, int n_levels, unsigned flags,
-                          size_t umax_clear, int clear_from, StyleAt&& style_at, Transform&& transform, uint8_t* out) {
+static int stylize_levels(wct_ctx* c, const float* img_c, const void* content_raw, int B, int Hc, int Wc, const int* levels,
+                          int n_levels, unsigned flags, size_t umax_clear, int clear_from, StyleAt&& style_at,
+                          Transform&& transform, uint8_t* out) {
   unsigned* const umax_c = (unsigned*)c->umax.p;
   const float* cur = img_c;
   int H = Hc, W = Wc;
@@ -1307,6 +1341,11 @@ static int stylize_levels(wct_ctx* c, const float* img_c, int B, int Hc, int Wc,
     TRY(ensure(c, dst, (size_t)B * H2 * W2 * 3 * 4));
     TRY(run_decoder(c, l, (half_t*)c->wct_out.p, B, h, w, (float*)dst.p));
     cur = (float*)dst.p; H = H2; W = W2;
+  }
+  if (flags & WCT_FLAG_CONTENT_COLORS) {
+    const int f32 = (flags & WCT_FLAG_IMAGES_F32) ? 1 : 0;
+    ProfScope ps(c, 7, 0, (double)B * H * W * 3 * 5 + (double)B * Hc * Wc * 3 * (f32 ? 4 : 1));
+    return launch_content_colors_f32(cur, content_raw, f32, B, H, W, Hc, Wc, out, c->stream);
   }
   ProfScope ps(c, 7, 0, (double)B * H * W * 3 * 5);
   return launch_f32_to_u8(cur, out, (size_t)B * H * W * 3, c->stream);
@@ -1353,7 +1392,7 @@ extern "C" int wct_stylize_batch_dev(wct_ctx* c, const uint8_t* content, int Hc,
     level_dims(Hs, Ws, l, hs, ws);
     return (const float*)c->feat_s[l].p + (size_t)(shared ? 0 : b) * *hs * *ws * LEVEL_C[l];
   };
-  return stylize_levels(c, img_c, B, Hc, Wc, levels, n_levels, flags, UROW * sizeof(unsigned), 1, style_at,
+  return stylize_levels(c, img_c, content, B, Hc, Wc, levels, n_levels, flags, UROW * sizeof(unsigned), 1, style_at,
                         [&](int, int l, int C, int h, int w, WctFeatStats st) {
                           int hs, ws;
                           const float* fs = style_at(l, 0, &hs, &ws);
@@ -1433,7 +1472,7 @@ static int stylize_multi(wct_ctx* c, const uint8_t* content, int Hc, int Wc, con
     level_dims(Hs[k], Ws[k], l, hs, ws);
     return (const float*)c->feat_mix[l].p + foff[l][k];
   };
-  TRY(stylize_levels(c, img_c, 1, Hc, Wc, levels, n_levels, flags, UMAX_SLOTS * sizeof(unsigned), 0, style_at,
+  TRY(stylize_levels(c, img_c, dc, 1, Hc, Wc, levels, n_levels, flags, UMAX_SLOTS * sizeof(unsigned), 0, style_at,
                      [&](int i, int l, int C, int h, int w, const WctFeatStats& st) {
                        const float* fs[WCT_MIX_MAX];
                        int Ns[WCT_MIX_MAX];
@@ -1710,7 +1749,7 @@ static int stylize_prepared_dev(wct_ctx* c, const void* content, int Hc, int Wc,
   if (fuse_stats()) HIP_TRY(hipMemsetAsync(c->umax.p, 0, UROW * sizeof(unsigned), c->stream));
   auto no_style = [](int, int, int* hs, int* ws) { *hs = *ws = 0; return (const float*)nullptr; };     // (style-swap alone asks)
   if (warm && std::find(c->warm_used.begin(), c->warm_used.end(), warm) == c->warm_used.end()) c->warm_used.push_back(warm);
-  return stylize_levels(c, img_c, B, Hc, Wc, levels, n_levels, flags, UROW * sizeof(unsigned), 1, no_style,
+  return stylize_levels(c, img_c, content, B, Hc, Wc, levels, n_levels, flags, UROW * sizeof(unsigned), 1, no_style,
                         [&](int i, int l, int C, int h, int w, const WctFeatStats& st) {
                           const int* Ns = &ns[(size_t)i * WCT_MIX_MAX];
                           if (!lambda && warm) {
@@ -1853,7 +1892,7 @@ extern "C" int wct_transform_warm(wct_ctx* c, const float* content, int Nc, cons
                                   unsigned flags, wct_warm* warm, int level, float* out, int* sweeps_out) {
   ARG_CHECK(c && content && style && out);
   TRY(warm_live(c, warm));
-  if (flags & (WCT_FLAG_ADAIN | WCT_FLAG_SWAP5 | WCT_FLAG_STYLE_SHARED | WCT_FLAG_IMAGES_F32)) {
+  if (flags & (WCT_FLAG_ADAIN | WCT_FLAG_SWAP5 | WCT_FLAG_STYLE_SHARED | WCT_FLAG_IMAGES_F32 | WCT_FLAG_CONTENT_COLORS)) {
     wct_set_error("wct_transform_warm: the flags take WCT_FLAG_MODE_NP alone (AdaIN has no eigensolve, style-swap no warm start)");
     return WCT_ERR_ARG;
   }
@@ -1973,7 +2012,7 @@ static int stylize_prepared_masked_dev(wct_ctx* c, const void* content, int Hc, 
   TRY(ensure(c, c->umax, 7 * UROW * sizeof(unsigned)));
   if (fuse_stats()) HIP_TRY(hipMemsetAsync(c->umax.p, 0, UROW * sizeof(unsigned), c->stream));
   auto no_style = [](int, int, int* hs, int* ws) { *hs = *ws = 0; return (const float*)nullptr; };
-  return stylize_levels(c, img_c, B, Hc, Wc, levels, n_levels, flags, UROW * sizeof(unsigned), 1, no_style,
+  return stylize_levels(c, img_c, content, B, Hc, Wc, levels, n_levels, flags, UROW * sizeof(unsigned), 1, no_style,
                         [&](int i, int l, int C, int h, int w, const WctFeatStats&) {
                           const int Nc = h * w;
                           const int* Ns = &ns[(size_t)i * WCT_MIX_MAX];

@@ -316,3 +316,13 @@ int launch_coral_stats(const uint8_t* img, size_t npix, unsigned long long* part
                        unsigned long long* out9, hipStream_t s);
 int launch_coral_apply(const uint8_t* src, size_t npix, const CoralApplyArgs& a, uint8_t* out_u8,
                        double* out_f64, hipStream_t s);
+
+// ---- colors.hip -----------------------------------------------------------
+// Luminance-only colour preservation (colors_rule.h): out [B][Ho][Wo][3] = the luminance of the stylized frame on the colours of
+// content [B][Hc][Wc][3], content pixel (min(y, Hc - 1), min(x, Wc - 1)); Ho >= Hc, Wo >= Wc.
+// _f32: the chain's last launch -- frame is the fp32 decode (quantised as launch_f32_to_u8 does), content uint8 or, with
+// content_f32, fp32 in [0,1] (quantised the same way).  _u8: both uint8; out may be stylized.
+int launch_content_colors_f32(const float* frame, const void* content, int content_f32, int B, int Ho, int Wo, int Hc, int Wc,
+                              uint8_t* out, hipStream_t s);
+int launch_content_colors_u8(const uint8_t* stylized, const uint8_t* content, int B, int Ho, int Wo, int Hc, int Wc, uint8_t* out,
+                             hipStream_t s);

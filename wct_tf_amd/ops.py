@@ -6,6 +6,8 @@ on libwct_hip.so.  Same names, argument meaning and array conventions:
   adain(content_features, style_features, alpha, epsilon=1e-5)   ops.py:282
   coral_numpy(source, target)                   coral.py:13 (float64)
   preserve_colors_np(style_rgb, content_rgb)    utils.py:87
+and, without a counterpart in the reference,
+  content_colors_np(stylized_rgb, content_rgb)  luminance-only colour preservation (Gatys et al. 2016), applied to a result
 """
 import numpy as np
 
@@ -109,3 +111,12 @@ def coral_numpy(source, target, ctx=None):
 def preserve_colors_np(style_rgb, content_rgb, ctx=None):
     ctx = ctx or default_context()
     return _coral(style_rgb, content_rgb, ctx, False, True)[0]
+
+
+def content_colors_np(stylized_rgb, content_rgb, ctx=None):
+    """The other way to keep a content's colours (Gatys et al. 2016, luminance-only transfer, post hoc): uint8 HxWx3 images, the
+    stylized one at least as large as the content -> uint8, the luminance of `stylized_rgb` on the colours of `content_rgb`
+    (the integer rule of include/wct_hip.h, wct_content_colors).  preserve_colors_np recolours the STYLE before stylizing; this
+    recolours the RESULT, so the style side does not depend on the content."""
+    ctx = ctx or default_context()
+    return ctx.content_colors(stylized_rgb, content_rgb)

@@ -5,7 +5,10 @@ takes TF checkpoint directories or .npz files (see wct.py), `--vgg-path` the .t7
 files (rank_shard); `--gpus N` without a launcher starts the N ranks itself.  `--interp-styles a b [--interp-weights wa wb]`
 stylizes with a weighted mix of the styles (Li et al. 2017, sec. 4.2; the reference's README TODO).
 `--mask-path M --mask-styles s0 s1 ...` stylizes each region of a grey label map with its own style (the same section,
-spatial control): grey value v is label v * K // 256 of K styles."""
+spatial control): grey value v is label v * K // 256 of K styles.
+`--content-colors` keeps every content's colours by luminance-only transfer (Gatys et al. 2016): the result takes its own
+luminance and the content's chrominance.  Unlike `--keep-colors` (CORAL on the style) it leaves the style alone, so it goes
+with prepared styles and every other option."""
 import argparse
 import os
 import time
@@ -24,6 +27,10 @@ _FLAGS = [
     (('--style-path',), dict(dest='style_path', help='style image, or a folder of them')),
     (('--out-path',), dict(dest='out_path', help='folder the results are written to')),
     (('--keep-colors',), dict(action='store_true', default=False, help='CORAL: give the style the colours of the content first')),
+    (('--content-colors',), dict(action='store_true', default=False,
+                                 help='luminance-only colour preservation: the result keeps its luminance and takes the colours of '
+                                      'the content (the alternative to --keep-colors: not with it).  Fused into the last launch; '
+                                      'with --passes > 1 applied once at the end, against the original content')),
     (('--device',), dict(default='/gpu:0', help='e.g. /gpu:0')),
     (('--style-size',), dict(type=int, default=0, help='short side of the style image (0: as is)')),
     (('--crop-size',), dict(type=int, default=0, help='centre-crop the style image to a square of this side (0: no)')),
@@ -108,15 +115,39 @@ def can_prepare(args):
     return not args.keep_colors and not args.swap5
 
 
+def check_color_args(parser, args):
+    """--content-colors: the combinations it refuses (parser.error exits)"""
+    if not args.content_colors:
+        return
+    if args.keep_colors:
+        parser.error('--content-colors and --keep-colors are alternatives: give one')
+    if args.passes > 1 and args.swap5 and args.ss_stride != 1:
+        parser.error('--content-colors with --passes > 1 needs --ss-stride 1 (a larger stride crops the content of every pass)')
+
+
+def run_passes(model, content, args, predict):
+    """`--passes` predictions from `content`, predict(image, content_colors) -> image.  --content-colors is fused into the
+    prediction of a single pass; several passes run plain (a later pass sees a stylized input, not the content) and the
+    stand-alone op then runs once, against the original content -- at one pass the two routes give the same bits."""
+    n = max(1, args.passes)
+    colors = getattr(args, 'content_colors', False)
+    out = content
+    for _ in range(n):
+        out = predict(out, colors and n == 1)
+    if colors and n > 1:
+        from .ops import content_colors_np
+        out = content_colors_np(out, content, ctx=model.sess)
+    return out
+
+
 def stylize_pair(model, content, style, args, prepared=None):
     """one output image: optional CORAL, `--passes` predictions, optional `--concat` (stylize.py:85-110).  prepared: the
     PreparedStyle of `style` (can_prepare), or None"""
     if args.keep_colors:
         from .ops import preserve_colors_np
         style = preserve_colors_np(style, content, ctx=model.sess)
-    out = content
-    for _ in range(max(1, args.passes)):
-        out = model.predict(out, style if prepared is None else prepared, args.alpha, args.swap5, args.ss_alpha, args.adain)
+    out = run_passes(model, content, args, lambda img, colors: model.predict(
+        img, style if prepared is None else prepared, args.alpha, args.swap5, args.ss_alpha, args.adain, content_colors=colors))
     if args.concat:
         side = out.shape[0]
         out = np.hstack([utils._imresize(style, (side, side)), out])
@@ -155,10 +186,9 @@ def stylize_mix_pair(model, content, styles, args, prepared=None):
     if args.keep_colors:
         from .ops import preserve_colors_np
         styles = [preserve_colors_np(s, content, ctx=model.sess) for s in styles]
-    out = content
-    for _ in range(max(1, args.passes)):
-        out = model.predict_mix(out, styles if prepared is None else prepared, args.interp_weights, args.alpha, args.adain, args.swap5,
-                                args.ss_alpha)
+    out = run_passes(model, content, args, lambda img, colors: model.predict_mix(
+        img, styles if prepared is None else prepared, args.interp_weights, args.alpha, args.adain, args.swap5, args.ss_alpha,
+        content_colors=colors))
     if args.concat:
         side = out.shape[0]
         out = np.hstack([utils._imresize(s, (side, side)) for s in styles] + [out])
@@ -213,11 +243,9 @@ def stylize_mask_pair(model, content, grey, styles, args, prepared=None):
     if args.keep_colors:
         from .ops import preserve_colors_np
         styles = [preserve_colors_np(s, content, ctx=model.sess) for s in styles]
-    out = content
-    for _ in range(max(1, args.passes)):
-        out = model.predict_masked(out, styles if prepared is None else prepared, mask_labels(grey, len(styles), out.shape[:2]),
-                                   args.alpha, args.adain, args.swap5, args.ss_alpha)
-    return out
+    return run_passes(model, content, args, lambda img, colors: model.predict_masked(
+        img, styles if prepared is None else prepared, mask_labels(grey, len(styles), img.shape[:2]), args.alpha, args.adain,
+        args.swap5, args.ss_alpha, content_colors=colors))
 
 
 def main(argv=None):
@@ -225,6 +253,7 @@ def main(argv=None):
     args = parser.parse_args(argv)
     check_interp_args(parser, args)
     check_mask_args(parser, args)
+    check_color_args(parser, args)
     if args.synthetic_weights is None and not args.checkpoints:
         parser.error('--checkpoints is required (stylize.py:17) unless --synthetic-weights SEED is given')
     if args.gpus > 0:

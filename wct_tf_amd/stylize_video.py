@@ -10,7 +10,9 @@ MI355X path.  Same flags.  Differences, all forced by the environment or by the 
   through `WCT.predict_frames` in batches that share ONE style: the style side runs once per batch
   (WCT_FLAG_STYLE_SHARED) and every frame is bit-identical to `predict(frame, style)`.  With
   `--keep-colors` the style image is CORAL-matched to every frame (stylize_video.py:116-119) and therefore
-  differs per frame: those frames go through the per-pair batch instead.
+  differs per frame: those frames go through the per-pair batch instead.  `--content-colors` keeps the frames' colours the
+  other way (luminance-only transfer, applied to the result): the style stays shared, so it goes with the prepared style,
+  `--mask-path` and `--warm-start`.
 """
 from __future__ import division, print_function
 
@@ -41,6 +43,10 @@ _FLAGS = [
     (('--tmp-dir',), dict(dest='tmp_dir', default=TMP_DIR, help='scratch folder for extracted / stylized frames')),
     (('--keep-tmp',), dict(action='store_true', default=False, help='leave the scratch folder in place')),
     (('--keep-colors',), dict(action='store_true', default=False, help='CORAL: give the style the colours of each frame first')),
+    (('--content-colors',), dict(action='store_true', default=False,
+                                 help='luminance-only colour preservation: every frame keeps its luminance and takes the colours '
+                                      'of its input frame (the alternative to --keep-colors: not with it).  Fused into the last '
+                                      'launch; with --passes > 1 applied once at the end, against the input frames')),
     (('--style-size',), dict(type=int, default=0, help='short side of the style image (0: as is)')),
     (('--crop-size',), dict(type=int, default=0, help='centre-crop the style image to a square of this side (0: no)')),
     (('--content-size',), dict(type=int, default=0, help='short side of every frame (0: as is)')),
@@ -115,6 +121,22 @@ def check_warm_args(parser, args):
             parser.error('--warm-start does not combine with %s' % flag)
 
 
+def check_color_args(parser, args):
+    """--content-colors: the combinations it refuses (parser.error exits)"""
+    if not args.content_colors:
+        return
+    if args.keep_colors:
+        parser.error('--content-colors and --keep-colors are alternatives: give one')
+    if args.passes > 1 and args.swap5 and args.ss_stride != 1:
+        parser.error('--content-colors with --passes > 1 needs --ss-stride 1 (a larger stride crops the frames of every pass)')
+
+
+def content_colors_frames(wct_model, stylized, frames):
+    """the stand-alone op on a group of frames (after --passes > 1): the luminance of `stylized` on the colours of `frames`"""
+    return np.concatenate([wct_model.sess.content_colors_batch(stylized[i:i + 32], frames[i:i + 32])
+                           for i in range(0, len(frames), 32)], axis=0)
+
+
 def match_masks(mask_path, frame_files):
     """the label map file of every frame: `mask_path` is one file for all frames, or a directory whose maps are matched to the
     frames in sorted order (natural_key) -- the counts must agree (ValueError, before any GPU work)"""
@@ -159,10 +181,15 @@ def stylize_frames_masked(wct_model, frame_files, mask_files, styles, args):
                     break
                 group.append(nxt)
                 j += 1
-            out = np.stack(group)
-            for _ in range(max(1, args.passes)):
+            frames = out = np.stack(group)
+            # --content-colors: fused into a single pass; after several plain passes the op runs once, against the input frames
+            colors, n = getattr(args, 'content_colors', False), max(1, args.passes)
+            for _ in range(n):
                 masks = np.stack([mask_labels(grey_of(m), k, out.shape[1:3]) for m in mask_files[i:j]])
-                out = wct_model.predict_frames_masked(out, prepared, masks, args.alpha, args.adain, batch=args.batch)
+                out = wct_model.predict_frames_masked(out, prepared, masks, args.alpha, args.adain, batch=args.batch,
+                                                      content_colors=colors and n == 1)
+            if colors and n > 1:
+                out = content_colors_frames(wct_model, out, frames)
             for f, o in zip(frame_files[i:j], out):
                 yield f, o
             i = j
@@ -189,11 +216,17 @@ def stylize_frames(wct_model, frame_files, style_img, args):
     # --warm-start: one state for the whole video, kept across frame-size groups (a covariance is C x C whatever the frame size)
     warm = wct_model.warm_state() if getattr(args, 'warm_start', False) else None
 
+    # --content-colors: fused into a single pass; after several plain passes the op runs once, against the input frames
+    colors = getattr(args, 'content_colors', False)
+
     def run(frames, style):
         style = prepared if prepared is not None else style
-        out = wct_model.predict_frames(frames, style, args.alpha, args.swap5, args.ss_alpha, args.adain, batch=args.batch, warm=warm)
+        out = wct_model.predict_frames(frames, style, args.alpha, args.swap5, args.ss_alpha, args.adain, batch=args.batch, warm=warm,
+                                       content_colors=colors and args.passes <= 1)
         for _ in range(args.passes - 1):                      # later passes: plain WCT, as stylize_video.py:124-126
             out = wct_model.predict_frames(out, style, args.alpha, adain=args.adain, batch=args.batch)
+        if colors and args.passes > 1:
+            out = content_colors_frames(wct_model, out, frames)
         return out
 
     i = 0
@@ -237,6 +270,7 @@ def main(argv=None):
     args = parser.parse_args(argv)
     check_mask_args(parser, args)
     check_warm_args(parser, args)
+    check_color_args(parser, args)
     if args.synthetic_weights is None and not args.checkpoints:
         parser.error('--checkpoints is required (stylize.py:17) unless --synthetic-weights SEED is given')
     start = time.time()

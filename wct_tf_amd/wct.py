@@ -5,6 +5,7 @@
     WCT.predict_mix(content, styles, weights=None, alpha=1, adain=False, swap5=False, ss_alpha=1) -> uint8 HxWx3
     WCT.predict_masked(content, styles, mask, alpha=1, adain=False, swap5=False, ss_alpha=1) -> uint8 HxWx3
     WCT.prepare_style(style) -> PreparedStyle, which predict / predict_frames / predict_mix take in the place of a style image
+    every predict* takes content_colors=True: the frame keeps its luminance and takes the colours of its content
 
 `checkpoints` / `vgg_path`: the reference restores TF checkpoints and a .t7 file
 (wct.py:46-58, vgg_normalised.py:16).  Per decoder this class takes either of
@@ -122,25 +123,27 @@ class WCT(object):
             raise ValueError('a warm state goes with a PreparedStyle (prepare_style), not a style image')
         check_warm(self.sess, warm, self.relu_targets, adain, swap5)
 
-    def predict(self, content, style, alpha=1, swap5=False, ss_alpha=1, adain=False, warm=None):
+    def predict(self, content, style, alpha=1, swap5=False, ss_alpha=1, adain=False, warm=None, content_colors=False):
         '''Stylize a single content/style pair; arrays in [0,255], returns uint8 HxWx3.
            The /255 preprocess and the clip*255 postprocess run inside the library
            (fused at the ends of the kernel chain).  `style` may be a PreparedStyle (prepare_style); with one, `warm` may be a
-           WarmState (warm_state).'''
+           WarmState (warm_state).  content_colors (here and in every predict*): luminance-only colour preservation (Gatys et
+           al. 2016; WCT_FLAG_CONTENT_COLORS) -- the frame keeps its stylized luminance and takes the colours of `content`, in
+           the last launch of the call; it equals ops.content_colors_np(the plain frame, content) bit for bit.'''
         if warm is not None:
             self._check_warm(warm, style, swap5, adain)                           # ValueError before any GPU call
         if isinstance(style, PreparedStyle):
             check_prepared(self.sess, [style], self.relu_targets, swap5)          # ValueError before any GPU call
             return self.sess.stylize_prepared(np.asarray(content), style, self.relu_targets, alpha=alpha, adain=adain,
-                                              wct_mode=self.wct_mode, warm=warm)
+                                              wct_mode=self.wct_mode, warm=warm, content_colors=content_colors)
         content, _ = self._swap5_setup(np.asarray(content), None, swap5, ss_alpha)
         style = np.asarray(style)
         # uint8 arrays take the fused /255 on the device; float arrays are divided by 255 WITHOUT rounding, as the
         # reference's preprocess does (wct.py:60-64) -- Context.stylize hands them over as float32 images
         return self.sess.stylize(content, style, self.relu_targets, alpha=alpha, adain=adain,
-                                 wct_mode=self.wct_mode, swap5=bool(swap5))
+                                 wct_mode=self.wct_mode, swap5=bool(swap5), content_colors=content_colors)
 
-    def predict_mix(self, content, styles, weights=None, alpha=1, adain=False, swap5=False, ss_alpha=1):
+    def predict_mix(self, content, styles, weights=None, alpha=1, adain=False, swap5=False, ss_alpha=1, content_colors=False):
         '''Stylize with a weighted mix of several styles (Li et al. 2017, sec. 4.2; the reference's README TODO
            "Interpolation between styles"): every level applies sum_k lambda_k T(content, style_k), lambda = weights /
            sum(weights); weights=None means equal weights.  Arrays in [0,255], returns uint8 HxWx3.  One style gives
@@ -151,16 +154,16 @@ class WCT(object):
             weights = mix_weights(weights, len(handles))
             check_prepared(self.sess, handles, self.relu_targets, swap5)
             return self.sess.stylize_prepared_mix(np.asarray(content), handles, weights, self.relu_targets, alpha=alpha,
-                                                  adain=adain, wct_mode=self.wct_mode)
+                                                  adain=adain, wct_mode=self.wct_mode, content_colors=content_colors)
         styles = [np.asarray(s) for s in styles]
         weights = mix_weights(weights, len(styles))              # ValueError before any GPU call
         if swap5 and len(styles) > 1:
             raise ValueError('swap5 takes one style: style-swap is not linear in the style')
         content, _ = self._swap5_setup(np.asarray(content), None, swap5, ss_alpha)
         return self.sess.stylize_mix(content, styles, weights, self.relu_targets, alpha=alpha, adain=adain,
-                                     wct_mode=self.wct_mode, swap5=bool(swap5))
+                                     wct_mode=self.wct_mode, swap5=bool(swap5), content_colors=content_colors)
 
-    def predict_masked(self, content, styles, mask, alpha=1, adain=False, swap5=False, ss_alpha=1):
+    def predict_masked(self, content, styles, mask, alpha=1, adain=False, swap5=False, ss_alpha=1, content_colors=False):
         '''Stylize each region of a label map with its own style (Li et al. 2017, sec. 4.2, Fig. 7; the reference's README TODO
            "Spatial control/masking"): `mask` [H][W] holds a label 0 .. K-1 per content pixel, `styles` K images (sizes may
            differ), and at every level the pixels of label k are transformed with style k alone, with their own statistics
@@ -175,16 +178,16 @@ class WCT(object):
             mask = mask_labels(mask, len(handles), content.shape[:2])
             check_prepared(self.sess, handles, self.relu_targets, swap5)
             return self.sess.stylize_prepared_masked(content, handles, mask, self.relu_targets, alpha=alpha, adain=adain,
-                                                     wct_mode=self.wct_mode)
+                                                     wct_mode=self.wct_mode, content_colors=content_colors)
         styles = [np.asarray(s) for s in styles]
         mask = mask_labels(mask, len(styles), content.shape[:2])        # ValueError before any GPU call
         if swap5 and len(styles) > 1:
             raise ValueError('swap5 takes one style: style-swap is not a per-region affine map')
         content, mask = self._swap5_setup(content, mask, swap5, ss_alpha)
         return self.sess.stylize_masked(content, styles, mask, self.relu_targets, alpha=alpha, adain=adain,
-                                        wct_mode=self.wct_mode, swap5=bool(swap5))
+                                        wct_mode=self.wct_mode, swap5=bool(swap5), content_colors=content_colors)
 
-    def predict_frames_masked(self, frames, styles, masks, alpha=1, adain=False, batch=16):
+    def predict_frames_masked(self, frames, styles, masks, alpha=1, adain=False, batch=16, content_colors=False):
         '''Spatial control of a video: same-sized frames [F][H][W][3], a label map per frame `masks` [F][H][W] (or one [H][W] map
            used for every frame), `styles` K images -- prepared once here -- or K PreparedStyle objects.  Frame f equals
            predict_masked(frames[f], styles, masks[f]) bit for bit; the frames go through the device in batches of `batch`
@@ -205,13 +208,14 @@ class WCT(object):
             batch = max(1, min(32, int(batch)))
             return np.concatenate([self.sess.stylize_prepared_masked_batch(frames[i:i + batch], handles or own, masks[i:i + batch],
                                                                            self.relu_targets, alpha=alpha, adain=adain,
-                                                                           wct_mode=self.wct_mode)
+                                                                           wct_mode=self.wct_mode, content_colors=content_colors)
                                    for i in range(0, len(frames), batch)], axis=0)
         finally:
             for h in own:
                 h.close()
 
-    def predict_frames(self, frames, style, alpha=1, swap5=False, ss_alpha=1, adain=False, batch=16, warm=None):
+    def predict_frames(self, frames, style, alpha=1, swap5=False, ss_alpha=1, adain=False, batch=16, warm=None,
+                       content_colors=False):
         '''Stylize same-sized frames [F][H][W][3] with ONE style image (the loop of stylize_video.py:112-121,
            which calls predict() once per frame and so re-runs the style encoder, the style statistics and the
            style eigendecompositions every frame).  Here the style side runs once per batch of `batch` frames;
@@ -229,7 +233,8 @@ class WCT(object):
                 frames = np.uint8(np.clip(frames, 0, 255))
             batch = max(1, min(32, int(batch)))
             return np.concatenate([self.sess.stylize_prepared_batch(frames[i:i + batch], style, self.relu_targets, alpha=alpha,
-                                                                    adain=adain, wct_mode=self.wct_mode, warm=warm)
+                                                                    adain=adain, wct_mode=self.wct_mode, warm=warm,
+                                                                    content_colors=content_colors)
                                    for i in range(0, len(frames), batch)], axis=0)
         style = np.asarray(style)
         assert frames.ndim == 4 and style.ndim == 3
@@ -246,6 +251,6 @@ class WCT(object):
             self.sess.set_style_swap(ss_alpha, self.ss_patch_size, self.ss_stride)
         batch = max(1, min(32, int(batch)))
         outs = [self.sess.stylize_batch(frames[i:i + batch], style, self.relu_targets, alpha=alpha, adain=adain,
-                                        wct_mode=self.wct_mode, swap5=bool(swap5))
+                                        wct_mode=self.wct_mode, swap5=bool(swap5), content_colors=content_colors)
                 for i in range(0, len(frames), batch)]
         return np.concatenate(outs, axis=0)
