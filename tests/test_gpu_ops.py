@@ -420,11 +420,12 @@ def _h(x):
     (37, 29, 128, 64, True, False),      # ragged edges
     (16, 16, 512, 512, True, False),     # deep K
     (20, 12, 256, 128, False, True),     # upsample folded into the loader, no ReLU
-    (128, 128, 64, 64, True, False),     # 16x16 tile, BN=64
-    (96, 96, 128, 128, True, False),     # 16x16 tile, BN=128
+    (128, 128, 64, 64, True, False),     # several tile rows and columns (64 tiles of 16x16 are under the 256 of <16,64,4,1>: the 8-row tile)
+    (96, 96, 128, 128, True, False),     # ... at 128 channels (36 tiles: the 8-row tile, two 64-channel blocks)
     (4, 4, 64, 64, True, True),
-    (360, 376, 64, 64, True, False),     # tall 32x16 tile config, ragged edge
-    (184, 180, 64, 64, False, True),     # same with the upsample folded in, no ReLU
+    (360, 376, 64, 64, True, False),     # 24 x 23 = 552 tiles of 16x16, ragged edge (24 x 12 = 288 tall 32x16 tiles are under the 512
+                                         # the policy asks for: tests/test_gpu_pointwise.py runs the tall tile, on a batch)
+    (184, 180, 64, 64, False, True),     # the 16x16 tile on 368 x 360 with the upsample folded in, no ReLU
 ])
 def test_conv3x3(ctx, h, w, cin, cout, relu, up):
     rng = np.random.default_rng(h * 1000 + cin)
