@@ -90,7 +90,7 @@ _WINO_BT = np.array([[1, 0, -1, 0], [0, 1, 1, 0], [0, -1, 1, 0], [0, 1, 0, -1]],
 
 
 def wino_layer(cin, cout):
-    """The layers the MI355X path runs on its reduced-FLOP kernel (csrc/api.hip::wino_layer; tap layers excepted there)."""
+    """The layers the MI355X path runs on its reduced-FLOP kernel (csrc/api_weights.hip::wino_layer; tap layers excepted there)."""
     return cin >= 256 and cout >= 256
 
 

@@ -43,6 +43,35 @@ def test_errors_cross_the_abi_as_status_codes(lib):
     assert lib.wct_output_size(64, 64, bad, 1, C.byref(ho), C.byref(wo)) == -2
 
 
+def _chain_model(h, w, levels):
+    """The frame size of a content chain -- per level ceil-halve l - 1 times, shift back -- or the level whose map is under 2x2."""
+    for l in levels:
+        fh, fw = h, w
+        for _ in range(l - 1):
+            fh, fw = (fh + 1) // 2, (fw + 1) // 2
+        if fh < 2 or fw < 2:
+            return l
+        h, w = fh << (l - 1), fw << (l - 1)
+    return h, w
+
+
+@pytest.mark.parametrize('levels', [[1], [2], [3], [4], [5], [5, 4, 3, 2, 1], [1, 5], [3, 3], [2, 4, 1]], ids=str)
+def test_output_size_walks_the_content_chain(lib, levels):
+    """wct_output_size against the pooling rule written out, for every content of 2..40 pixels a side: the frame size, and the
+    refusal (status -2, naming the level) exactly when a level's feature map would be smaller than 2x2."""
+    import ctypes as C
+    lv = (C.c_int * len(levels))(*levels)
+    ho, wo = C.c_int(), C.c_int()
+    for h in range(2, 41):
+        for w in range(2, 41):
+            want = _chain_model(h, w, levels)
+            rc = lib.wct_output_size(h, w, lv, len(levels), C.byref(ho), C.byref(wo))
+            if isinstance(want, tuple):
+                assert rc == 0 and (ho.value, wo.value) == want, (h, w, levels)
+            else:
+                assert rc == -2 and b'too small for relu%d_1' % want in lib.wct_last_error(), (h, w, levels)
+
+
 def test_no_gpu_means_loud_failure_not_fallback(lib):
     import torch
     if torch.cuda.is_available():

@@ -195,16 +195,19 @@ def test_abi_refusals_leave_the_context_usable(small_ctx):
     out = np.zeros((64, 64, 3), np.uint8)
     u8p = lambda a: a.ctypes.data_as(_lib._U8)
 
-    def call(k, mask, flags=0):
+    def call(k, mask, flags=0, lv=lv):
         ptrs = (_lib._U8 * max(k, 1))(*[u8p(a) for a in img[:max(k, 1)]])
         hs = (C.c_int * max(k, 1))(*([64] * max(k, 1)))
         m = np.ascontiguousarray(mask, np.uint8)
-        return lib.wct_stylize_masked(small_ctx.h, u8p(c), 64, 64, u8p(m), ptrs, hs, hs, k, lv, 3, C.c_float(0.7), flags, u8p(out))
+        return lib.wct_stylize_masked(small_ctx.h, u8p(c), 64, 64, u8p(m), ptrs, hs, hs, k, lv, len(lv), C.c_float(0.7), flags, u8p(out))
 
     zero = np.zeros((64, 64), np.uint8)
     for k, mask, flags in ((2, zero + 2, 0), (9, zero, 0), (0, zero, 0), (2, zero, _lib.FLAG_SWAP5), (2, zero, 8)):
         assert call(k, mask, flags) == -2, (k, flags)
         assert lib.wct_last_error()
+    # two faults in one call: a level out of range is refused before the decoder that is not loaded (relu4_1) is noticed
+    assert call(1, zero, lv=(C.c_int * 2)(4, 7)) == -2 and b'invalid argument' in lib.wct_last_error()
+    assert call(1, zero, lv=(C.c_int * 2)(4, 1)) == -3 and b'relu4_1' in lib.wct_last_error()
     fs = [_lib.f32(np.ones((16, 64))) for _ in range(9)]
     ns = (C.c_int * 9)(*([16] * 9))
     o = np.zeros((16, 64), np.float32)

@@ -542,6 +542,51 @@ def test_pipeline_reports_failed_eigensolves_at_sync(ctx, weights):
     assert np.array_equal(ctx.stylize(c, s, targets, alpha=0.8), good)
 
 
+def test_stale_failures_are_reported_by_the_next_blocking_call(ctx, weights):
+    """Failures that an asynchronous wct_stylize_batch_dev left behind, and that no wct_sync read, are reported by the next
+    blocking call before it starts: WCT_STATUS_NOCONV named as EARLIER work, the caller's output untouched.  The call after
+    that one runs as if nothing had happened -- with a style image and with a prepared style alike."""
+    import ctypes as C
+    from wct_tf_amd import _lib
+    targets = ['relu3_1', 'relu1_1']
+    lv = (C.c_int * 2)(3, 1)
+    c, s = synthetic_image(1000, 64, 64), synthetic_image(2000, 64, 64)
+    good = ctx.stylize(c, s, targets, alpha=0.8)
+    style = ctx.prepare_style(s, targets)
+    cs, ss = np.stack([c, c]), np.stack([s, s])
+    dc, ds, do = ctx.dev_alloc(cs.nbytes), ctx.dev_alloc(ss.nbytes), ctx.dev_alloc(cs.nbytes)
+    ctx.h2d(dc, cs); ctx.h2d(ds, ss)
+    u8p = lambda a: a.ctypes.data_as(_lib._U8)
+
+    def leave_failures_behind():
+        os.environ['WCT_JACOBI_MAX_SWEEPS'] = '1'
+        try:
+            ctx.stylize_batch_dev(dc, 64, 64, ds, 64, 64, 2, targets, 0.8, do)    # enqueues; nobody syncs
+        finally:
+            del os.environ['WCT_JACOBI_MAX_SWEEPS']
+
+    def refused(rc, out):
+        err = ctx.lib.wct_last_error()
+        print(rc, err)
+        assert rc == -5 and b'EARLIER' in err and b'was not started' in err
+        assert (out == 77).all()
+
+    try:
+        leave_failures_behind()
+        out = np.full((64, 64, 3), 77, np.uint8)
+        refused(ctx.lib.wct_stylize(ctx.h, u8p(c), 64, 64, u8p(s), 64, 64, lv, 2, 0.8, 0, u8p(out)), out)
+        assert np.array_equal(ctx.stylize(c, s, targets, alpha=0.8), good)
+        leave_failures_behind()
+        refused(ctx.lib.wct_stylize_prepared(ctx.h, u8p(c), 64, 64, style.h, lv, 2, 0.8, 0, u8p(out)), out)
+        assert np.array_equal(ctx.stylize(c, s, targets, alpha=0.8), good)
+        assert np.array_equal(ctx.stylize_prepared(c, style, targets, alpha=0.8), good)
+    finally:
+        ctx.sync()
+        style.close()
+        for p in (dc, ds, do):
+            ctx.dev_free(p)
+
+
 def test_stream_handle_orders_foreign_work(ctx, weights):
     """wct_get_stream: a caller's own stream can be ordered behind wct_stylize_batch_dev with events alone (what the
     multi-GPU bench does with the RCCL gather) -- no host sync between the library's kernels and the foreign copy."""

@@ -25,6 +25,13 @@ def _levels(relu_targets):
     return out
 
 
+def _flags(adain=False, wct_mode='tf', swap5=False, images_f32=False, shared_style=False, content_colors=False):
+    """The flag word of a stylize call (WCT_FLAG_*, include/wct_hip.h)."""
+    return (_lib.FLAG_ADAIN if adain else 0) | (_lib.FLAG_MODE_NP if wct_mode == 'np' else 0) | \
+        (_lib.FLAG_SWAP5 if swap5 else 0) | (_lib.FLAG_IMAGES_F32 if images_f32 else 0) | \
+        (_lib.FLAG_STYLE_SHARED if shared_style else 0) | (_lib.FLAG_CONTENT_COLORS if content_colors else 0)
+
+
 def _feature_args(content, styles, validate):
     """A content [Nc][C] and K styles [Ns_k][C] as float32, the caller's own validate(content, K) (its result is returned), the
     shape check, and the style row counts as a C int array."""
@@ -480,18 +487,8 @@ class Context(object):
         s, c = _color_images(stylized_u8, contents_u8, 4)
         if s.shape[0] != c.shape[0] or not 1 <= s.shape[0] <= _lib.BATCH_MAX:
             raise ValueError('a batch takes 1 .. %d frames and as many contents, got %d and %d' % (_lib.BATCH_MAX, s.shape[0], c.shape[0]))
-        out = np.empty_like(s)
-        ds, dc = self.dev_alloc(s.nbytes), self.dev_alloc(c.nbytes)
-        try:
-            self.h2d(ds, s)
-            self.h2d(dc, c)
-            self.content_colors_batch_dev(ds, s.shape[1], s.shape[2], dc, c.shape[1], c.shape[2], s.shape[0], ds)     # in place
-            self.sync()
-            self.d2h(out, ds)
-        finally:
-            for p in (ds, dc):
-                self.dev_free(p)
-        return out
+        return self._host_batch([s, c], np.empty_like(s), in_place=True, enqueue=lambda ds, dc: self.content_colors_batch_dev(
+            ds, s.shape[1], s.shape[2], dc, c.shape[1], c.shape[2], s.shape[0], ds))
 
     # ---- the hot path ------------------------------------------------------
     def output_size(self, hc, wc, relu_targets):
@@ -529,9 +526,7 @@ class Context(object):
             c, ss = u8(content), [u8(s) for s in styles]
         lv = _levels(relu_targets)
         ho, wo = self.output_size(c.shape[0], c.shape[1], lv)
-        flags = (_lib.FLAG_ADAIN if adain else 0) | (_lib.FLAG_MODE_NP if wct_mode == 'np' else 0) | \
-            (_lib.FLAG_SWAP5 if swap5 else 0) | (_lib.FLAG_IMAGES_F32 if as_f32 else 0) | \
-            (_lib.FLAG_CONTENT_COLORS if content_colors else 0)
+        flags = _flags(adain, wct_mode, swap5, images_f32=as_f32, content_colors=content_colors)
         return c, ss, v, (C.c_int * len(lv))(*lv), np.empty((ho, wo, 3), np.uint8), flags
 
     # ---- prepared styles -----------------------------------------------------
@@ -545,7 +540,7 @@ class Context(object):
         as_f32 = img.dtype != np.uint8
         s = np.ascontiguousarray(np.asarray(img / 255.), np.float32) if as_f32 else u8(img)
         lv = sorted(set(_levels(relu_targets)))
-        flags = (_lib.FLAG_ADAIN if adain else 0) | (_lib.FLAG_MODE_NP if wct_mode == 'np' else 0) | (_lib.FLAG_IMAGES_F32 if as_f32 else 0)
+        flags = _flags(adain, wct_mode, images_f32=as_f32)
         h = C.c_void_p()
         check(self.lib.wct_style_prepare(self.h, s.ctypes.data_as(_lib._U8), s.shape[0], s.shape[1], (C.c_int * len(lv))(*lv), len(lv),
                                          flags, C.byref(h)))
@@ -558,8 +553,7 @@ class Context(object):
         c = np.ascontiguousarray(np.asarray(content / 255.), np.float32) if as_f32 else u8(content)
         lv = _levels(relu_targets)
         ho, wo = self.output_size(c.shape[0], c.shape[1], lv)
-        flags = (_lib.FLAG_ADAIN if adain else 0) | (_lib.FLAG_MODE_NP if wct_mode == 'np' else 0) | \
-            (_lib.FLAG_IMAGES_F32 if as_f32 else 0) | (_lib.FLAG_CONTENT_COLORS if content_colors else 0)
+        flags = _flags(adain, wct_mode, images_f32=as_f32, content_colors=content_colors)
         return c, (C.c_int * len(lv))(*lv), np.empty((ho, wo, 3), np.uint8), flags
 
     def warm_state(self, relu_targets):
@@ -599,8 +593,7 @@ class Context(object):
         """stylize_batch_dev(shared_style=True) with a PreparedStyle: B contents resident in HBM, asynchronous.  warm (a
         WarmState): all B frames start from the state's bases, which then take those of frame B - 1."""
         lv = check_prepared(self, [style], relu_targets)
-        flags = (_lib.FLAG_ADAIN if adain else 0) | (_lib.FLAG_MODE_NP if wct_mode == 'np' else 0) | \
-            (_lib.FLAG_CONTENT_COLORS if content_colors else 0)
+        flags = _flags(adain, wct_mode, content_colors=content_colors)
         if warm is not None:
             check_warm(self, warm, relu_targets, adain)
             check(self.lib.wct_stylize_prepared_batch_dev_warm(self.h, content_dev, hc, wc, batch, style.h, (C.c_int * len(lv))(*lv),
@@ -621,17 +614,8 @@ class Context(object):
         B, hc, wc = c.shape[:3]
         ho, wo = self.output_size(hc, wc, relu_targets)
         out = np.empty((B, ho, wo, 3), np.uint8)
-        dc, do = self.dev_alloc(c.nbytes), self.dev_alloc(out.nbytes)
-        try:
-            self.h2d(dc, c)
-            self.stylize_prepared_batch_dev(dc, hc, wc, B, style, relu_targets, alpha, do, adain=adain, wct_mode=wct_mode, warm=warm,
-                                            content_colors=content_colors)
-            self.sync()
-            self.d2h(out, do)
-        finally:
-            for p in (dc, do):
-                self.dev_free(p)
-        return out
+        return self._host_batch([c], out, lambda dc, do: self.stylize_prepared_batch_dev(
+            dc, hc, wc, B, style, relu_targets, alpha, do, adain=adain, wct_mode=wct_mode, warm=warm, content_colors=content_colors))
 
     def stylize_prepared_masked(self, content, styles, mask, relu_targets, alpha=1.0, adain=False, wct_mode='tf', content_colors=False):
         """stylize_masked() with K PreparedStyle objects in the place of the K images: the same frame, bit for bit."""
@@ -654,8 +638,7 @@ class Context(object):
             raise ValueError('a batch takes 1 .. %d frames, got %d' % (_lib.BATCH_MAX, batch))
         m = _lib.mask_labels_frames(masks, len(styles), int(batch), (hc, wc))
         lv = check_prepared(self, styles, relu_targets)
-        flags = (_lib.FLAG_ADAIN if adain else 0) | (_lib.FLAG_MODE_NP if wct_mode == 'np' else 0) | \
-            (_lib.FLAG_CONTENT_COLORS if content_colors else 0)
+        flags = _flags(adain, wct_mode, content_colors=content_colors)
         hs = (C.c_void_p * len(styles))(*[s.h.value for s in styles])
         # the upload is enqueued on the stream: the maps stay alive until sync() (include/wct_hip.h)
         self._masks_in_flight = getattr(self, '_masks_in_flight', []) + [m]
@@ -677,17 +660,8 @@ class Context(object):
         check_prepared(self, styles, relu_targets)
         ho, wo = self.output_size(hc, wc, relu_targets)
         out = np.empty((B, ho, wo, 3), np.uint8)
-        dc, do = self.dev_alloc(c.nbytes), self.dev_alloc(out.nbytes)
-        try:
-            self.h2d(dc, c)
-            self.stylize_prepared_masked_batch_dev(dc, hc, wc, B, m, styles, relu_targets, alpha, do, adain=adain, wct_mode=wct_mode,
-                                                   content_colors=content_colors)
-            self.sync()
-            self.d2h(out, do)
-        finally:
-            for p in (dc, do):
-                self.dev_free(p)
-        return out
+        return self._host_batch([c], out, lambda dc, do: self.stylize_prepared_masked_batch_dev(
+            dc, hc, wc, B, m, styles, relu_targets, alpha, do, adain=adain, wct_mode=wct_mode, content_colors=content_colors))
 
     def stylize_mix(self, content, styles, weights, relu_targets, alpha=1.0, adain=False, wct_mode='tf', swap5=False,
                     content_colors=False):
@@ -730,6 +704,25 @@ class Context(object):
         assert arr.flags['C_CONTIGUOUS']
         check(self.lib.wct_d2h(self.h, arr.ctypes.data_as(C.c_void_p), src, arr.nbytes))
 
+    def _host_batch(self, inputs, out, enqueue, in_place=False):
+        """The round trip of a host batch: a device buffer per input array and one for `out` (in_place: `out` comes back in the
+        first input's buffer), h2d, enqueue(*buffers), sync(), d2h -> out.  The buffers are freed whatever happens."""
+        bufs = []
+        try:
+            for a in inputs:
+                bufs.append(self.dev_alloc(a.nbytes))
+            if not in_place:
+                bufs.append(self.dev_alloc(out.nbytes))
+            for p, a in zip(bufs, inputs):
+                self.h2d(p, a)
+            enqueue(*bufs)
+            self.sync()
+            self.d2h(out, bufs[0] if in_place else bufs[-1])
+        finally:
+            for p in bufs:
+                self.dev_free(p)
+        return out
+
     def stylize_batch_dev(self, content_dev, hc, wc, style_dev, hs, ws, batch, relu_targets, alpha, out_dev,
                           adain=False, wct_mode='tf', swap5=False, shared_style=False, content_colors=False):
         """B pairs resident in HBM.  shared_style: style_dev holds ONE image used for every pair (fixed-style
@@ -737,9 +730,7 @@ class Context(object):
         to the ones a replicated style produces."""
         lv = _levels(relu_targets)
         arr = (C.c_int * len(lv))(*lv)
-        flags = (_lib.FLAG_ADAIN if adain else 0) | (_lib.FLAG_MODE_NP if wct_mode == 'np' else 0) | \
-            (_lib.FLAG_SWAP5 if swap5 else 0) | (_lib.FLAG_STYLE_SHARED if shared_style else 0) | \
-            (_lib.FLAG_CONTENT_COLORS if content_colors else 0)
+        flags = _flags(adain, wct_mode, swap5, shared_style=shared_style, content_colors=content_colors)
         check(self.lib.wct_stylize_batch_dev(self.h, content_dev, hc, wc, style_dev, hs, ws, batch, arr, len(lv),
                                              float(alpha), flags, out_dev))
 
@@ -756,18 +747,9 @@ class Context(object):
         hs, ws = s.shape[-3], s.shape[-2]
         ho, wo = self.output_size(hc, wc, relu_targets)
         out = np.empty((B, ho, wo, 3), np.uint8)
-        dc, ds, do = self.dev_alloc(c.nbytes), self.dev_alloc(s.nbytes), self.dev_alloc(out.nbytes)
-        try:
-            self.h2d(dc, c)
-            self.h2d(ds, s)
-            self.stylize_batch_dev(dc, hc, wc, ds, hs, ws, B, relu_targets, alpha, do, adain=adain,
-                                   wct_mode=wct_mode, swap5=swap5, shared_style=shared, content_colors=content_colors)
-            self.sync()
-            self.d2h(out, do)
-        finally:
-            for p in (dc, ds, do):
-                self.dev_free(p)
-        return out
+        return self._host_batch([c, s], out, lambda dc, ds, do: self.stylize_batch_dev(
+            dc, hc, wc, ds, hs, ws, B, relu_targets, alpha, do, adain=adain, wct_mode=wct_mode, swap5=swap5, shared_style=shared,
+            content_colors=content_colors))
 
     # ---- decoder training (model.py:123-223) --------------------------------
     def train_step(self, relu_target, images01, step, learning_rate=1e-4, feature_weight=1.0, pixel_weight=1.0,

@@ -1,0 +1,212 @@
+// What the units behind the C ABI of libwct_hip.so (include/wct_hip.h) share: the context and what hangs off it, and the
+// host-side drivers that one unit (api_*.hip; DESIGN.md section 4 says which holds what) defines and another calls.  Internal:
+// not installed, not part of include/.
+#pragma once
+#include "common.h"
+#include "../../include/wct_hip.h"
+
+#include <stdio.h>
+#include <string.h>
+#include <stdlib.h>
+#include <memory>
+#include <vector>
+#include <cmath>
+#include <algorithm>
+
+// a device buffer that grows on demand (ensure) and releases its memory with its owner
+struct DevBuf {
+  void* p = nullptr;
+  size_t cap = 0;
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  ~DevBuf() { if (p) hipFree(p); }
+};
+
+struct ConvLayer {
+  half_t* w = nullptr;   // [cout][9][cin]
+  float* b = nullptr;
+  half_t* ww = nullptr;  // the filters transformed for conv_wino.hip (ConvArgs::w_wino), or null: the direct kernel only
+  int cin = 0, cout = 0;
+};
+
+struct PlanStep { char kind; int cin, cout, relu; };   // 'C' or 'U'
+
+struct Decoder {
+  bool loaded = false;
+  std::vector<PlanStep> plan;
+  std::vector<ConvLayer> convs;    // every conv but the last
+  half_t* last_w = nullptr;        // MFMA A-fragments of the 64->3 conv (see ConvLastArgs::wfrag)
+  float* last_b = nullptr;
+  // training (wct_train_step): fp32 master copies (HWIO), Adam moments and the last step's gradients, one entry
+  // per conv of the plan (the output conv last)
+  std::vector<float*> w32, b32, mw, vw, mb, vb, gw, gb;
+  std::vector<int> cin, cout;
+  float* grad_arena = nullptr;     // gw / gb point into ONE contiguous buffer: a single all-reduce covers a decoder
+  size_t grad_count = 0;
+};
+
+struct ProfRec { hipEvent_t a, b; int cls; double flops, bytes; };
+constexpr int WCT_EIG_WORDS = 2 + 6 * 3;
+
+// A prepared style (wct_style_prepare): the style image on the device and, per level, a small cache of STATES -- the style side
+// of that level (common.h: WctStyleRef) for one key.  The bits of a state depend on the partial-sum layout of the (content,
+// style) pair it serves and on the mode, so a handle cannot hold one state per level: a call that needs a key the cache does
+// not hold computes it from the image in front of its content chain (style_fill) and keeps it, oldest out.
+constexpr int STYLE_CACHE_KEYS = 4;                  // states per level and handle
+struct StyleState {
+  WctStyleKey key; int kind;                         // kind 0: wct_tf, 1: wct_np, 2: AdaIN
+  float* buf;                                        // wct_style_state_floats(C)
+  unsigned long long stamp;                          // the call that used it last (wct_ctx::style_clock)
+};
+struct wct_style {
+  int Hs = 0, Ws = 0;
+  unsigned level_set = 0;                            // bit l: relu<l>_1 is served
+  float* img = nullptr;                              // [Hs][Ws][3] fp32 in [0,1]
+  std::vector<StyleState> cache[6];
+  ~wct_style() {
+    for (auto& lv : cache)
+      for (auto& e : lv) if (e.buf) hipFree(e.buf);
+    if (img) hipFree(img);
+  }
+};
+
+// A warm state (wct_warm_create): per level of its set the C x C basis the content eigensolves of a call start from -- the
+// re-orthonormalised eigenvectors of the last frame of the previous call -- and whether it holds one yet
+struct wct_warm {
+  unsigned level_set = 0;                            // bit l: relu<l>_1 is served
+  float* basis[6] = {nullptr};
+  bool valid[6] = {false};
+  ~wct_warm() { for (float* b : basis) if (b) hipFree(b); }
+};
+
+struct wct_ctx {
+  int device = 0;
+  hipStream_t stream = nullptr;
+  bool enc_loaded = false;
+  half_t* first_w = nullptr;       // folded conv1_1 as fp16 hi/lo MFMA fragments (ConvFirstArgs::wfrag)
+  float* first_b = nullptr;
+  ConvLayer enc[12];               // conv1_2 .. conv5_1
+  float* first_w32 = nullptr;      // folded conv1_1 weights fp32 [27][64] (data gradient of the feature loss)
+  float* enc_wt[12] = {nullptr};   // encoder weights transposed [(tap, cout)][cin] fp32 (B operand of the dgrad GEMM)
+  DevBuf train_ws;
+  Decoder dec[6];
+  DevBuf act[2], feat_c, feat_s[6], img_c, img_s, img_t[2], wct_out, wct_ws, stage[4];
+  DevBuf usum_c, usum_s[6], umax;     // feature statistics from the tap epilogues (ConvArgs::usum / umax); umax: [7][32][UMAX_SLOTS] words
+  DevBuf mix_in, feat_mix[6];      // a style mix: the K style inputs, and their features per level (K maps back to back)
+  DevBuf mask_in;                  // spatial control: the label map (wct_stylize_masked) or the row labels (wct_*_masked)
+  std::vector<wct_style*> styles;  // the live prepared styles of this context (wct_style_prepare .. wct_style_free)
+  unsigned long long style_clock = 0;   // one tick per call that takes prepared styles
+  std::vector<wct_warm*> warms;    // the live warm states of this context (wct_warm_create .. wct_warm_free)
+  std::vector<wct_warm*> warm_used;// those that took a basis from solves whose status nobody has read yet (eig_status)
+
+  int* eig_fail = nullptr;         // pinned host memory mapped into the device: [2] eigenproblems that did not converge / had
+                                   // non-finite input -- bumped by jacobi_finalize_kernel (then [6 size classes][3] solver
+  int* eig_fail_dev = nullptr;     // statistics: matrices, sweeps, max sweeps)
+  float ss_alpha = 0.6f;           // style-swap settings (stylize.py:34-37 defaults)
+  int ss_patch = 3, ss_stride = 1;
+  bool prof = false;
+  bool no_wino = false;            // the training forward keeps every layer on the direct kernel (its backward assumes it)
+  std::vector<ProfRec> recs;
+  std::vector<std::pair<hipEvent_t, hipEvent_t>> free_events;
+  double prof_ms[WCT_PROF_CLASSES] = {0};
+  long long prof_n[WCT_PROF_CLASSES] = {0};
+  double prof_flops[WCT_PROF_CLASSES] = {0};
+  double prof_bytes[WCT_PROF_CLASSES] = {0};
+};
+
+inline constexpr int LEVEL_C[6] = {0, 64, 128, 256, 512, 512};
+inline constexpr int ENC_CIN[12] = {64, 64, 128, 128, 256, 256, 256, 256, 512, 512, 512, 512};
+inline constexpr int ENC_COUT[12] = {64, 128, 128, 256, 256, 256, 256, 512, 512, 512, 512, 512};
+// enc[i] (conv1_2 .. conv5_1): the level whose relu*_1 it produces (0 = none), and whether a 'same' max-pool follows it
+// (conv1_2, conv2_2, conv3_4, conv4_4 -- their outputs feed nothing but the pool)
+inline constexpr int ENC_TAP[12] = {0, 2, 0, 3, 0, 0, 0, 4, 0, 0, 0, 5};
+inline constexpr int ENC_POOL_AFTER[12] = {1, 0, 1, 0, 0, 0, 1, 0, 0, 0, 1, 0};
+
+#define TRY(expr) do { int _rc = (expr); if (_rc) return _rc; } while (0)
+
+struct ProfScope {
+  wct_ctx* c; ProfRec r; bool on;
+  ProfScope(wct_ctx* ctx, int cls, double flops, double bytes) : c(ctx), on(ctx->prof) {
+    if (!on) return;
+    if (c->free_events.empty()) {
+      hipEventCreate(&r.a); hipEventCreate(&r.b);
+    } else {
+      r.a = c->free_events.back().first; r.b = c->free_events.back().second;
+      c->free_events.pop_back();
+    }
+    r.cls = cls; r.flops = flops; r.bytes = bytes;
+    hipEventRecord(r.a, c->stream);
+  }
+  ~ProfScope() {
+    if (!on) return;
+    hipEventRecord(r.b, c->stream);
+    c->recs.push_back(r);
+  }
+};
+
+// what the stages of a transform are charged in their profile classes: covariance (4), apply (6), or the one AdaIN launch (7)
+struct StageCost { double cov_flops, cov_bytes, apply_flops, apply_bytes, adain_bytes; };
+
+// ---- api_ctx.hip ----------------------------------------------------------
+int ensure(wct_ctx* c, DevBuf& b, size_t bytes);                                    // b holds at least `bytes` (may sync and reallocate)
+int stage_in(wct_ctx* c, int slot, const void* host, size_t bytes, void** dev);     // host -> c->stage[slot], enqueued
+int fetch(wct_ctx* c, void* host, const void* dev, size_t bytes);                   // device -> host, then a stream sync
+int eig_status(wct_ctx* c);    // after a stream sync: did an eigensolve of this call fail?
+int eig_stale(wct_ctx* c);     // at the start of a blocking call: failures that earlier asynchronous work left unread
+void free_layer(ConvLayer& l);
+void free_decoder(Decoder& d);
+
+// ---- api_weights.hip ------------------------------------------------------
+int upload(wct_ctx* c, const void* host, size_t bytes, void** dev);                 // hipMalloc + copy, blocking
+int pack_conv(wct_ctx* c, const float* w_hwio, const float* b, int cin, int cout, ConvLayer* out);
+
+// ---- api_drivers.hip (device pointers, batch B) ---------------------------
+// One transform by a variant's launcher, launch(mode, stages): AdaIN (stages = 0) in one launch, or the covariance, eigensolve
+// and apply stages, each timed in its class
+template <typename Launch>
+static int run_stages(wct_ctx* c, size_t ws_bytes, unsigned flags, const StageCost& cost, Launch&& launch) {
+  TRY(ensure(c, c->wct_ws, ws_bytes));
+  if (flags & WCT_FLAG_ADAIN) {
+    ProfScope ps(c, 7, 0, cost.adain_bytes);
+    return launch(0, 0);
+  }
+  const int mode = (flags & WCT_FLAG_MODE_NP) ? WCT_MODE_NP : WCT_MODE_TF;
+  {
+    ProfScope ps(c, 4, cost.cov_flops, cost.cov_bytes);
+    TRY(launch(mode, WCT_STAGE_COV));
+  }
+  {
+    ProfScope ps(c, 5, 0, 0);
+    TRY(launch(mode, WCT_STAGE_EIG));
+  }
+  ProfScope ps(c, 6, cost.apply_flops, cost.apply_bytes);
+  return launch(mode, WCT_STAGE_APPLY);
+}
+void level_dims(int H, int W, int level, int* h, int* w);
+int check_min_size(const char* what, int H, int W, int level);
+// The geometry of a content chain: level i (relu<l>_1, C channels) sees H x W, its feature map is h x w, and the next level
+// sees the decoder's h << (l - 1) by w << (l - 1) -- ceil pooling then x2 upsampling; the frames are Ho x Wo
+struct ChainLevel { int l, C, H, W, h, w; };
+struct Chain { std::vector<ChainLevel> lv; int Ho, Wo; };
+int chain_geometry(int Hc, int Wc, const int* levels, int n_levels, Chain* out);
+int run_conv(wct_ctx* c, const ConvLayer& l, const half_t* x, half_t* y16, float* y32, int B, int H, int W, int upsample, int relu,
+             int pool = 0, float* usum = nullptr, unsigned* umax = nullptr, bool tap_layer = false);
+int run_encoder(wct_ctx* c, const float* img, int B, int H, int W, int clamp01, int deepest, float* const taps32[6],
+                float* const* usum = nullptr, unsigned* const* umax = nullptr);
+int run_decoder(wct_ctx* c, int level, const half_t* feat16, int B, int h, int w, float* img_out);
+int run_transform(wct_ctx* c, const float* fc, int Nc, const float* fs, int Ns, int C, int P, float alpha, unsigned flags, float eps,
+                  half_t* out16, float* out32, int* sweeps_dev, const WctFeatStats* st = nullptr,
+                  const WctStyleRef* prep = nullptr /* a prepared style: fs may be null */,
+                  const WctWarmRef* warm = nullptr /* a warm state's basis for this level */);
+int mix_weights(const float* weights, int K, float* lambda);
+int run_transform_mix(wct_ctx* c, const float* fc, int Nc, const float* const* fs, const int* Ns, int K, const float* lambda, int C,
+                      float alpha, unsigned flags, float eps, half_t* out16, float* out32, int* sweeps_dev,
+                      const WctFeatStats* st = nullptr, const WctStyleRef* prep = nullptr /* K prepared styles: fs may be null */);
+int mask_check(const uint8_t* labels, size_t n, int K);
+void mask_counts(const uint8_t* mask, int Hm, int Wm, int h, int w, int stride, int K, int* nk);
+int run_transform_masked(wct_ctx* c, const float* fc, int Nc, const MaskGeom& g, const int* nk, const float* const* fs, const int* Ns,
+                         int K, int C, float alpha, unsigned flags, float eps, half_t* out16, float* out32, int* sweeps_dev);
+
+// ---- api_stylize.hip ------------------------------------------------------
+int warm_live(const wct_ctx* c, const wct_warm* wm);     // WCT_ERR_STATE unless wm is a live warm state of c

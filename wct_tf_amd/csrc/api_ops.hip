@@ -1,0 +1,469 @@
+// The op-level entry points: host arrays in, host arrays out, one operation of the path each (the tests and the CPU oracle
+// compare them one by one).
+#include "api.h"
+
+// One (content, style) pair of feature matrices through run_transform.  warm (with its level): the content solve starts from the
+// state's basis of that level, which then takes this pair's.
+static int transform_pair(wct_ctx* c, const float* content, int Nc, const float* style, int Ns, int C, float alpha, unsigned flags,
+                          float eps, wct_warm* warm, int level, float* out, int* sweeps_out) {
+  HIP_TRY(hipSetDevice(c->device));
+  TRY(eig_stale(c));
+  void *dc, *ds;
+  TRY(stage_in(c, 0, content, (size_t)Nc * C * 4, &dc));
+  TRY(stage_in(c, 1, style, (size_t)Ns * C * 4, &ds));
+  TRY(ensure(c, c->stage[2], (size_t)Nc * C * 4));
+  TRY(ensure(c, c->stage[3], 256));
+  WctWarmRef wr = {};
+  if (warm) {
+    c->warm_used.push_back(warm);
+    wr = {warm->basis[level], warm->valid[level] ? 1 : 0};
+  }
+  TRY(run_transform(c, (float*)dc, Nc, (float*)ds, Ns, C, 1, alpha, flags, eps, nullptr, (float*)c->stage[2].p, (int*)c->stage[3].p,
+                    nullptr, nullptr, warm ? &wr : nullptr));
+  if (warm) warm->valid[level] = true;
+  TRY(fetch(c, out, c->stage[2].p, (size_t)Nc * C * 4));
+  if (sweeps_out) TRY(fetch(c, sweeps_out, c->stage[3].p, 2 * sizeof(int)));
+  return eig_status(c);
+}
+
+extern "C" int wct_transform(wct_ctx* c, const float* content, int Nc, const float* style, int Ns, int C,
+                             float alpha, int mode, float eps, float* out, int* sweeps_out) {
+  ARG_CHECK(c && content && style && out && (mode == WCT_NP || mode == WCT_TF));
+  return transform_pair(c, content, Nc, style, Ns, C, alpha, mode == WCT_NP ? WCT_FLAG_MODE_NP : 0, eps, nullptr, 0, out, sweeps_out);
+}
+
+// the warm twin of wct_transform: the content solve started from the state's basis of `level`
+extern "C" int wct_transform_warm(wct_ctx* c, const float* content, int Nc, const float* style, int Ns, int C, float alpha,
+                                  unsigned flags, wct_warm* warm, int level, float* out, int* sweeps_out) {
+  ARG_CHECK(c && content && style && out);
+  TRY(warm_live(c, warm));
+  if (flags & (WCT_FLAG_ADAIN | WCT_FLAG_SWAP5 | WCT_FLAG_STYLE_SHARED | WCT_FLAG_IMAGES_F32 | WCT_FLAG_CONTENT_COLORS)) {
+    wct_set_error("wct_transform_warm: the flags take WCT_FLAG_MODE_NP alone (AdaIN has no eigensolve, style-swap no warm start)");
+    return WCT_ERR_ARG;
+  }
+  if (level < 1 || level > 5 || !(warm->level_set & (1u << level))) {
+    wct_set_error("warm state: relu%d_1 is not in the state's level set", level);
+    return WCT_ERR_ARG;
+  }
+  if (C != LEVEL_C[level]) {
+    wct_set_error("warm state: relu%d_1 has %d channels, the features have %d", level, LEVEL_C[level], C);
+    return WCT_ERR_ARG;
+  }
+  return transform_pair(c, content, Nc, style, Ns, C, alpha, flags, -1.f, warm, level, out, sweeps_out);
+}
+
+extern "C" int wct_adain(wct_ctx* c, const float* content, int Nc, const float* style, int Ns, int C,
+                         float alpha, float epsilon, float* out) {
+  ARG_CHECK(c && content && style && out);
+  HIP_TRY(hipSetDevice(c->device));
+  void *dc, *ds;
+  TRY(stage_in(c, 0, content, (size_t)Nc * C * 4, &dc));
+  TRY(stage_in(c, 1, style, (size_t)Ns * C * 4, &ds));
+  TRY(ensure(c, c->stage[2], (size_t)Nc * C * 4));
+  TRY(ensure(c, c->wct_ws, wct_workspace_bytes(C, Nc, Ns, 1)));
+  TRY(launch_adain((float*)dc, Nc, (float*)ds, Ns, C, 1, alpha, epsilon, nullptr, (float*)c->stage[2].p,
+                   c->wct_ws.p, c->wct_ws.cap, c->stream, 0));
+  return fetch(c, out, c->stage[2].p, (size_t)Nc * C * 4);
+}
+
+// the inputs of a one-content, K-style op: the content [Nc][C] in stage 0 (*dc), the K host feature maps [Ns[k]][C] back to back
+// in c->mix_in (ds[k] points at map k); room for the output in stage 2 and the sweeps in stage 3
+static int stage_in_multi(wct_ctx* c, const float* content, int Nc, const float* const* styles, const int* Ns, int K, int C,
+                          void** dc, const float* ds[]) {
+  TRY(stage_in(c, 0, content, (size_t)Nc * C * 4, dc));
+  size_t total = 0;
+  for (int k = 0; k < K; ++k) { ARG_CHECK(styles[k] && Ns[k] >= 1); total += (size_t)Ns[k] * C * 4; }
+  TRY(ensure(c, c->mix_in, total));
+  size_t off = 0;
+  for (int k = 0; k < K; ++k) {
+    char* d = (char*)c->mix_in.p + off;
+    HIP_TRY(hipMemcpyAsync(d, styles[k], (size_t)Ns[k] * C * 4, hipMemcpyHostToDevice, c->stream));
+    ds[k] = (const float*)d;
+    off += (size_t)Ns[k] * C * 4;
+  }
+  TRY(ensure(c, c->stage[2], (size_t)Nc * C * 4));
+  return ensure(c, c->stage[3], 2 * WCT_MIX_MAX * sizeof(int));
+}
+
+extern "C" int wct_transform_mix(wct_ctx* c, const float* content, int Nc, const float* const* styles, const int* Ns, int K,
+                                 const float* weights, int C, float alpha, int mode, float eps, float* out, int* sweeps_out) {
+  ARG_CHECK(c && content && styles && Ns && out && (mode == WCT_NP || mode == WCT_TF));
+  float lambda[WCT_MIX_MAX];
+  TRY(mix_weights(weights, K, lambda));
+  HIP_TRY(hipSetDevice(c->device));
+  TRY(eig_stale(c));
+  void* dc;
+  const float* ds[WCT_MIX_MAX];
+  TRY(stage_in_multi(c, content, Nc, styles, Ns, K, C, &dc, ds));
+  TRY(run_transform_mix(c, (float*)dc, Nc, ds, Ns, K, lambda, C, alpha, mode == WCT_NP ? WCT_FLAG_MODE_NP : 0, eps,
+                        nullptr, (float*)c->stage[2].p, (int*)c->stage[3].p));
+  TRY(fetch(c, out, c->stage[2].p, (size_t)Nc * C * 4));
+  if (sweeps_out) {
+    int sw[2 * WCT_MIX_MAX];
+    TRY(fetch(c, sw, c->stage[3].p, 2 * K * sizeof(int)));
+    sweeps_out[0] = sw[0];                                     // the content, then style k at slot 2k + 1
+    for (int k = 0; k < K; ++k) sweeps_out[1 + k] = sw[2 * k + 1];
+  }
+  return eig_status(c);
+}
+
+extern "C" int wct_adain_mix(wct_ctx* c, const float* content, int Nc, const float* const* styles, const int* Ns, int K,
+                             const float* weights, int C, float alpha, float epsilon, float* out) {
+  ARG_CHECK(c && content && styles && Ns && out);
+  float lambda[WCT_MIX_MAX];
+  TRY(mix_weights(weights, K, lambda));
+  HIP_TRY(hipSetDevice(c->device));
+  void* dc;
+  const float* ds[WCT_MIX_MAX];
+  TRY(stage_in_multi(c, content, Nc, styles, Ns, K, C, &dc, ds));
+  TRY(ensure(c, c->wct_ws, wct_mix_workspace_bytes(C, Nc, Ns, K, lambda)));
+  TRY(launch_adain_mix((float*)dc, Nc, ds, Ns, K, lambda, C, alpha, epsilon, nullptr, (float*)c->stage[2].p,
+                       c->wct_ws.p, c->wct_ws.cap, c->stream));
+  return fetch(c, out, c->stage[2].p, (size_t)Nc * C * 4);
+}
+
+// the row labels of a masked transform in c->mask_in, and their counts; g: one row of Nc labels
+static int stage_labels(wct_ctx* c, const uint8_t* labels, int Nc, int K, int* nk, MaskGeom* g) {
+  TRY(mask_check(labels, (size_t)Nc, K));
+  mask_counts(labels, 1, Nc, 1, Nc, 1, K, nk);
+  TRY(ensure(c, c->mask_in, (size_t)Nc));
+  HIP_TRY(hipMemcpyAsync(c->mask_in.p, labels, (size_t)Nc, hipMemcpyHostToDevice, c->stream));
+  *g = MaskGeom{(const uint8_t*)c->mask_in.p, 1, Nc, Nc, 1};
+  return WCT_OK;
+}
+
+extern "C" int wct_transform_masked(wct_ctx* c, const float* content, int Nc, const uint8_t* labels, const float* const* styles,
+                                    const int* Ns, int K, int C, float alpha, int mode, float eps, float* out, int* sweeps_out) {
+  ARG_CHECK(c && content && labels && styles && Ns && out && Nc >= 1 && (mode == WCT_NP || mode == WCT_TF));
+  HIP_TRY(hipSetDevice(c->device));
+  int nk[WCT_MIX_MAX];
+  MaskGeom g;
+  TRY(stage_labels(c, labels, Nc, K, nk, &g));
+  TRY(eig_stale(c));
+  void* dc;
+  const float* ds[WCT_MIX_MAX];
+  TRY(stage_in_multi(c, content, Nc, styles, Ns, K, C, &dc, ds));
+  TRY(run_transform_masked(c, (float*)dc, Nc, g, nk, ds, Ns, K, C, alpha, mode == WCT_NP ? WCT_FLAG_MODE_NP : 0, eps,
+                           nullptr, (float*)c->stage[2].p, (int*)c->stage[3].p));
+  TRY(fetch(c, out, c->stage[2].p, (size_t)Nc * C * 4));
+  if (sweeps_out) {
+    int sw[2 * WCT_MIX_MAX];
+    TRY(fetch(c, sw, c->stage[3].p, 2 * WCT_MIX_MAX * sizeof(int)));
+    for (int k = 0, p = 0; k < K; ++k) {               // pair p = the p-th label with >= 2 rows
+      sweeps_out[2 * k] = nk[k] >= 2 ? sw[2 * p] : 0;
+      sweeps_out[2 * k + 1] = nk[k] >= 2 ? sw[2 * p + 1] : 0;
+      p += nk[k] >= 2;
+    }
+  }
+  return eig_status(c);
+}
+
+extern "C" int wct_adain_masked(wct_ctx* c, const float* content, int Nc, const uint8_t* labels, const float* const* styles,
+                                const int* Ns, int K, int C, float alpha, float epsilon, float* out) {
+  ARG_CHECK(c && content && labels && styles && Ns && out && Nc >= 1);
+  HIP_TRY(hipSetDevice(c->device));
+  int nk[WCT_MIX_MAX];
+  MaskGeom g;
+  TRY(stage_labels(c, labels, Nc, K, nk, &g));
+  void* dc;
+  const float* ds[WCT_MIX_MAX];
+  TRY(stage_in_multi(c, content, Nc, styles, Ns, K, C, &dc, ds));
+  TRY(ensure(c, c->wct_ws, wct_masked_workspace_bytes(C, Nc, nk, Ns, K)));
+  TRY(launch_adain_masked((float*)dc, Nc, g, nk, ds, Ns, K, C, alpha, epsilon, nullptr, (float*)c->stage[2].p,
+                          c->wct_ws.p, c->wct_ws.cap, c->stream));
+  return fetch(c, out, c->stage[2].p, (size_t)Nc * C * 4);
+}
+
+extern "C" int wct_mask_compact(wct_ctx* c, const uint8_t* mask, int Hm, int Wm, int h, int w, int stride, int K, int* perm_out,
+                                int* seg_off_out) {
+  ARG_CHECK(c && mask && perm_out && seg_off_out && Hm >= 1 && Wm >= 1 && h >= 1 && w >= 1 && stride >= 1);
+  TRY(mask_check(mask, (size_t)Hm * Wm, K));
+  HIP_TRY(hipSetDevice(c->device));
+  const int N = h * w;
+  TRY(ensure(c, c->mask_in, (size_t)Hm * Wm));
+  HIP_TRY(hipMemcpyAsync(c->mask_in.p, mask, (size_t)Hm * Wm, hipMemcpyHostToDevice, c->stream));
+  const size_t perm_bytes = ((size_t)N * sizeof(int) + 255) & ~(size_t)255;
+  TRY(ensure(c, c->stage[2], perm_bytes + 256 + mask_compact_workspace_bytes(N)));
+  int* perm = (int*)c->stage[2].p;
+  int* seg_off = (int*)((char*)c->stage[2].p + perm_bytes);
+  TRY(launch_mask_compact(MaskGeom{(const uint8_t*)c->mask_in.p, Hm, Wm, w, stride}, N, K, perm, seg_off, (char*)seg_off + 256, c->stream));
+  TRY(fetch(c, seg_off_out, seg_off, (K + 1) * sizeof(int)));
+  return fetch(c, perm_out, perm, (size_t)N * sizeof(int));
+}
+
+extern "C" int wct_mask_compact_batch(wct_ctx* c, const uint8_t* masks, int B, int Hm, int Wm, int h, int w, int stride, int K,
+                                      int* perm_out, int* seg_off_out) {
+  ARG_CHECK(c && masks && perm_out && seg_off_out && B >= 1 && B <= 32 && Hm >= 1 && Wm >= 1 && h >= 1 && w >= 1 && stride >= 1);
+  TRY(mask_check(masks, (size_t)B * Hm * Wm, K));
+  HIP_TRY(hipSetDevice(c->device));
+  const int N = h * w;
+  TRY(ensure(c, c->mask_in, (size_t)B * Hm * Wm));
+  HIP_TRY(hipMemcpyAsync(c->mask_in.p, masks, (size_t)B * Hm * Wm, hipMemcpyHostToDevice, c->stream));
+  const size_t perm_bytes = ((size_t)B * N * sizeof(int) + 255) & ~(size_t)255;
+  const size_t seg_bytes = ((size_t)B * (WCT_MIX_MAX + 1) * sizeof(int) + 255) & ~(size_t)255;
+  TRY(ensure(c, c->stage[2], perm_bytes + seg_bytes + mask_compact_workspace_bytes(N, B)));
+  int* perm = (int*)c->stage[2].p;
+  int* seg_off = (int*)((char*)c->stage[2].p + perm_bytes);
+  TRY(launch_mask_compact_batch(MaskGeom{(const uint8_t*)c->mask_in.p, Hm, Wm, w, stride}, N, K, B, perm, seg_off, (char*)seg_off + seg_bytes,
+                                c->stream));
+  std::vector<int> seg((size_t)B * (WCT_MIX_MAX + 1));
+  TRY(fetch(c, seg.data(), seg_off, seg.size() * sizeof(int)));
+  for (int f = 0; f < B; ++f)
+    for (int k = 0; k <= K; ++k) seg_off_out[f * (K + 1) + k] = seg[(size_t)f * (WCT_MIX_MAX + 1) + k];
+  return fetch(c, perm_out, perm, (size_t)B * N * sizeof(int));
+}
+
+extern "C" int wct_set_style_swap(wct_ctx* c, float ss_alpha, int patch_size, int stride) {
+  ARG_CHECK(c && patch_size >= 1 && stride >= 1);
+  c->ss_alpha = ss_alpha; c->ss_patch = patch_size; c->ss_stride = stride;
+  return WCT_OK;
+}
+
+extern "C" int wct_style_swap(wct_ctx* c, const float* content, int hc, int wc, const float* style, int hs, int ws,
+                              int C, float alpha, int patch_size, int stride, float eps, float* out) {
+  ARG_CHECK(c && content && style && out && hc > 0 && wc > 0 && hs > 0 && ws > 0);
+  HIP_TRY(hipSetDevice(c->device));
+  TRY(eig_stale(c));
+  void *dc, *ds;
+  TRY(stage_in(c, 0, content, (size_t)hc * wc * C * 4, &dc));
+  TRY(stage_in(c, 1, style, (size_t)hs * ws * C * 4, &ds));
+  TRY(ensure(c, c->stage[2], (size_t)hc * wc * C * 4));
+  ARG_CHECK(patch_size >= 1 && stride >= 1 && hc >= patch_size && wc >= patch_size && hs >= patch_size && ws >= patch_size);
+  TRY(ensure(c, c->wct_ws, style_swap_workspace_bytes(C, hc, wc, hs, ws, patch_size, stride)));
+  TRY(launch_style_swap((float*)dc, hc, wc, (float*)ds, hs, ws, C, alpha, patch_size, stride, eps, nullptr,
+                        (float*)c->stage[2].p, c->wct_ws.p, c->wct_ws.cap, c->stream, c->eig_fail_dev));
+  TRY(fetch(c, out, c->stage[2].p, (size_t)hc * wc * C * 4));
+  return eig_status(c);
+}
+
+__global__ void extract_diag_kernel(const float* A, float* d, int C) {
+  const int m = blockIdx.y, k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k < C) d[m * C + k] = A[(size_t)m * C * C + (size_t)k * C + k];
+}
+
+// wct_eigh's input contract: the UPPER triangle is authoritative.  The solver reads an element from whichever triangle is
+// contiguous for the kernel at hand, so the staged copy is mirrored first (a C caller may pass upper-only data or a matrix
+// that is symmetric only to round-off -- ADVICE r4).  In tiles: coalesced rows in, transposed through LDS out.
+__global__ __launch_bounds__(256) void mirror_upper_kernel(float* A, int C) {
+  __shared__ float t[32][33];
+  const int bi = blockIdx.x, bj = blockIdx.y;
+  if (bj < bi) return;                                     // tile (bi, bj) of the upper triangle -> tile (bj, bi)
+  float* Am = A + (size_t)blockIdx.z * C * C;
+  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;  // 32 x 8
+  for (int r = ty; r < 32; r += 8) {
+    const int i = bi * 32 + r, j = bj * 32 + tx;
+    t[r][tx] = (i < C && j < C) ? Am[(size_t)i * C + j] : 0.f;
+  }
+  __syncthreads();
+  for (int r = ty; r < 32; r += 8) {
+    const int i = bj * 32 + r, j = bi * 32 + tx;           // element (i, j) of the lower side = upper (j, i)
+    if (i < C && j < C && i > j) Am[(size_t)i * C + j] = t[tx][r];
+  }
+}
+
+extern "C" int wct_eigh(wct_ctx* c, const float* A, int C, int nmat, float* evals, float* evecs, int* sweeps_out) {
+  ARG_CHECK(c && A && evals && evecs && nmat >= 1 && nmat <= 64);
+  HIP_TRY(hipSetDevice(c->device));
+  TRY(eig_stale(c));
+  const size_t mb = (size_t)nmat * C * C * 4;
+  void* dA;
+  TRY(stage_in(c, 0, A, mb, &dA));
+  hipLaunchKernelGGL(mirror_upper_kernel, dim3(cdiv(C, 32), cdiv(C, 32), nmat), dim3(256), 0, c->stream, (float*)dA, C);
+  TRY(ensure(c, c->stage[1], mb));
+  TRY(ensure(c, c->stage[2], (size_t)nmat * C * 4 + 1024));
+  TRY(ensure(c, c->wct_ws, jacobi_workspace_bytes(C, nmat)));
+  int* sw = (int*)((char*)c->stage[2].p + (size_t)nmat * C * 4);
+  {
+    ProfScope ps(c, 5, 0, 0);
+    TRY(launch_jacobi_eigh((float*)dA, (float*)c->stage[1].p, C, nmat, c->wct_ws.p, c->wct_ws.cap, sw, c->eig_fail_dev, c->stream));
+  }
+  hipLaunchKernelGGL(extract_diag_kernel, dim3(cdiv(C, 256), nmat), dim3(256), 0, c->stream, (float*)dA, (float*)c->stage[2].p, C);
+  TRY(fetch(c, evals, c->stage[2].p, (size_t)nmat * C * 4));
+  TRY(fetch(c, evecs, c->stage[1].p, mb));
+  if (sweeps_out) TRY(fetch(c, sweeps_out, sw, nmat * sizeof(int)));
+  return eig_status(c);
+}
+
+extern "C" int wct_conv3x3(wct_ctx* c, const float* x, int H, int W, int Cin, const float* w_hwio, const float* bias,
+                           int Cout, int relu, int upsample, float* y) {
+  ARG_CHECK(c && x && w_hwio && bias && y);
+  HIP_TRY(hipSetDevice(c->device));
+  const int Ho = upsample ? 2 * H : H, Wo = upsample ? 2 * W : W;
+  ConvLayer l;
+  TRY(pack_conv(c, w_hwio, bias, Cin, Cout, &l));
+  void* dx;
+  int rc = stage_in(c, 0, x, (size_t)H * W * Cin * 4, &dx);
+  if (!rc) rc = ensure(c, c->stage[1], (size_t)H * W * Cin * 2);
+  if (!rc) rc = ensure(c, c->stage[2], (size_t)Ho * Wo * Cout * 4);
+  if (!rc) rc = launch_f32_to_f16((float*)dx, (half_t*)c->stage[1].p, (size_t)H * W * Cin, c->stream);
+  if (!rc) rc = run_conv(c, l, (half_t*)c->stage[1].p, nullptr, (float*)c->stage[2].p, 1, Ho, Wo, upsample, relu);
+  if (!rc) rc = fetch(c, y, c->stage[2].p, (size_t)Ho * Wo * Cout * 4);
+  hipStreamSynchronize(c->stream);
+  free_layer(l);
+  return rc;
+}
+
+// One layer as the PIPELINE runs it: fp16 activations in, fp16 out (returned as fp32), optionally with the fused 2x2 'same'
+// max-pool.  algo 0: the pipeline's choice for this layer shape, 1: the direct kernel, 2: the reduced-FLOP kernel (conv_wino.hip;
+// an error if the shape is not one it takes).  x: [B][H][W][Cin] fp32 (rounded to fp16 on the device like wct_conv3x3).
+extern "C" int wct_conv3x3_f16(wct_ctx* c, const float* x, int B, int H, int W, int Cin, const float* w_hwio, const float* bias,
+                               int Cout, int relu, int upsample, int pool, int algo, float* y) {
+  ARG_CHECK(c && x && w_hwio && bias && y && B >= 1 && algo >= 0 && algo <= 2);
+  HIP_TRY(hipSetDevice(c->device));
+  const int Hc = upsample ? 2 * H : H, Wc = upsample ? 2 * W : W;
+  const int Ho = pool ? (Hc + 1) / 2 : Hc, Wo = pool ? (Wc + 1) / 2 : Wc;
+  ConvLayer l;
+  TRY(pack_conv(c, w_hwio, bias, Cin, Cout, &l));
+  int rc = WCT_OK;
+  if (algo == 2 && !l.ww) {
+    // a shape the policy leaves on the direct kernel: pack its Winograd fragments on the device for this call
+    float* w32 = nullptr;
+    rc = upload(c, w_hwio, (size_t)9 * Cin * Cout * sizeof(float), (void**)&w32);
+    if (!rc && hipMalloc((void**)&l.ww, (size_t)Cout * 12 * Cin * sizeof(half_t)) != hipSuccess) { wct_set_error("hipMalloc failed"); rc = WCT_ERR_NOMEM; }
+    if (!rc) rc = launch_pack_conv_wino_frag(w32, l.ww, Cin, Cout, c->stream);
+    hipStreamSynchronize(c->stream);
+    if (w32) hipFree(w32);
+  }
+  const bool keep = c->no_wino;
+  c->no_wino = algo == 1;
+  void* dx;
+  const size_t nin = (size_t)B * H * W * Cin, nout = (size_t)B * Ho * Wo * Cout;
+  if (!rc) rc = stage_in(c, 0, x, nin * 4, &dx);
+  if (!rc) rc = ensure(c, c->stage[1], nin * 2);
+  if (!rc) rc = ensure(c, c->stage[2], nout * 2);
+  if (!rc) rc = ensure(c, c->stage[3], nout * 4);
+  if (!rc) rc = launch_f32_to_f16((float*)dx, (half_t*)c->stage[1].p, nin, c->stream);
+  if (!rc) {
+    ConvArgs a;
+    a.x = (half_t*)c->stage[1].p; a.w = l.w; a.bias = l.b; a.y16 = (half_t*)c->stage[2].p; a.y32 = nullptr; a.usum = nullptr; a.umax = nullptr;
+    a.B = B; a.H = Hc; a.W = Wc; a.Cin = Cin; a.Cout = Cout; a.upsample = upsample; a.relu = relu; a.pool = pool;
+    a.w_wino = c->no_wino ? nullptr : l.ww;
+    if (algo == 2 && !conv3x3_wino_takes(a)) { wct_set_error("wct_conv3x3_f16: algo 2 does not take this layer"); rc = WCT_ERR_ARG; }
+    if (!rc) {
+      const double px = (double)B * Hc * Wc;
+      ProfScope ps(c, 0, 2.0 * px * 9 * Cin * Cout, (double)nin * 2 + (double)nout * 2 + 9.0 * Cin * Cout * 2);
+      rc = launch_conv3x3(a, c->stream);
+    }
+  }
+  c->no_wino = keep;
+  if (!rc) rc = launch_f16_to_f32((half_t*)c->stage[2].p, (float*)c->stage[3].p, nout, c->stream);
+  if (!rc) rc = fetch(c, y, c->stage[3].p, nout * 4);
+  hipStreamSynchronize(c->stream);
+  free_layer(l);
+  return rc;
+}
+
+extern "C" int wct_maxpool(wct_ctx* c, const float* x, int H, int W, int C, float* y) {
+  ARG_CHECK(c && x && y && C % 8 == 0);
+  HIP_TRY(hipSetDevice(c->device));
+  const int Ho = (H + 1) / 2, Wo = (W + 1) / 2;
+  void* dx;
+  TRY(stage_in(c, 0, x, (size_t)H * W * C * 4, &dx));
+  TRY(ensure(c, c->stage[1], (size_t)H * W * C * 2));
+  TRY(ensure(c, c->stage[2], (size_t)Ho * Wo * C * 2));
+  TRY(ensure(c, c->stage[3], (size_t)Ho * Wo * C * 4));
+  TRY(launch_f32_to_f16((float*)dx, (half_t*)c->stage[1].p, (size_t)H * W * C, c->stream));
+  TRY(launch_maxpool2x2((half_t*)c->stage[1].p, (half_t*)c->stage[2].p, 1, H, W, C, c->stream));
+  TRY(launch_f16_to_f32((half_t*)c->stage[2].p, (float*)c->stage[3].p, (size_t)Ho * Wo * C, c->stream));
+  return fetch(c, y, c->stage[3].p, (size_t)Ho * Wo * C * 4);
+}
+
+extern "C" int wct_encode(wct_ctx* c, const float* img01, int H, int W, int level, float* feat) {
+  ARG_CHECK(c && img01 && feat && level >= 1 && level <= 5);
+  HIP_TRY(hipSetDevice(c->device));
+  TRY(check_min_size("image", H, W, level));
+  int h, w;
+  level_dims(H, W, level, &h, &w);
+  void* dimg;
+  TRY(stage_in(c, 0, img01, (size_t)H * W * 3 * 4, &dimg));
+  const size_t fb = (size_t)h * w * LEVEL_C[level] * 4;
+  TRY(ensure(c, c->feat_c, fb));
+  float* taps[6] = {};
+  taps[level] = (float*)c->feat_c.p;
+  TRY(run_encoder(c, (float*)dimg, 1, H, W, 0, level, taps));
+  return fetch(c, feat, c->feat_c.p, fb);
+}
+
+extern "C" int wct_decode(wct_ctx* c, const float* feat, int h, int w, int level, float* img) {
+  ARG_CHECK(c && feat && img && level >= 1 && level <= 5);
+  HIP_TRY(hipSetDevice(c->device));
+  const int C = LEVEL_C[level], scale = 1 << (level - 1);
+  void* df;
+  TRY(stage_in(c, 0, feat, (size_t)h * w * C * 4, &df));
+  TRY(ensure(c, c->wct_out, (size_t)h * w * C * 2));
+  TRY(launch_f32_to_f16((float*)df, (half_t*)c->wct_out.p, (size_t)h * w * C, c->stream));
+  const size_t ib = (size_t)h * scale * w * scale * 3 * 4;
+  TRY(ensure(c, c->img_t[0], ib));
+  TRY(run_decoder(c, level, (half_t*)c->wct_out.p, 1, h, w, (float*)c->img_t[0].p));
+  return fetch(c, img, c->img_t[0].p, ib);
+}
+
+extern "C" int wct_coral_stats(wct_ctx* c, const uint8_t* img, int H, int W, double sums[9]) {
+  ARG_CHECK(c && img && sums && H > 0 && W > 0);
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t npix = (size_t)H * W;
+  void* dimg;
+  TRY(stage_in(c, 0, img, npix * 3, &dimg));
+  int nblocks = (int)((npix + 255) / 256);
+  if (nblocks > 1024) nblocks = 1024;
+  TRY(ensure(c, c->stage[1], (size_t)(nblocks + 1) * 9 * sizeof(unsigned long long)));
+  unsigned long long* partial = (unsigned long long*)c->stage[1].p;
+  unsigned long long* out9 = partial + (size_t)nblocks * 9;
+  TRY(launch_coral_stats((uint8_t*)dimg, npix, partial, nblocks, out9, c->stream));
+  unsigned long long host9[9];
+  TRY(fetch(c, host9, out9, sizeof(host9)));
+  for (int k = 0; k < 9; ++k) sums[k] = (double)host9[k];     // exact: < 2^53
+  return WCT_OK;
+}
+
+extern "C" int wct_coral_apply(wct_ctx* c, const uint8_t* src, int H, int W, const double M[9],
+                               const double src_mean[3], const double src_std[3], const double tgt_mean[3],
+                               const double tgt_std[3], uint8_t* out_u8, double* out_f64) {
+  ARG_CHECK(c && src && M && src_mean && src_std && tgt_mean && tgt_std && (out_u8 || out_f64) && H > 0 && W > 0);
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t npix = (size_t)H * W;
+  CoralApplyArgs a;
+  for (int i = 0; i < 9; ++i) a.M[i] = M[i];
+  for (int i = 0; i < 3; ++i) { a.src_mean[i] = src_mean[i]; a.src_std[i] = src_std[i]; a.tgt_mean[i] = tgt_mean[i]; a.tgt_std[i] = tgt_std[i]; }
+  void* dsrc;
+  TRY(stage_in(c, 0, src, npix * 3, &dsrc));
+  if (out_u8) TRY(ensure(c, c->stage[1], npix * 3));
+  if (out_f64) TRY(ensure(c, c->stage[2], npix * 3 * sizeof(double)));
+  TRY(launch_coral_apply((uint8_t*)dsrc, npix, a, out_u8 ? (uint8_t*)c->stage[1].p : nullptr,
+                         out_f64 ? (double*)c->stage[2].p : nullptr, c->stream));
+  if (out_u8) TRY(fetch(c, out_u8, c->stage[1].p, npix * 3));
+  if (out_f64) TRY(fetch(c, out_f64, c->stage[2].p, npix * 3 * sizeof(double)));
+  return WCT_OK;
+}
+
+// Luminance-only colour preservation, op level (csrc/colors.hip): the refusals both calls share
+static int content_colors_checks(const void* stylized, int Ho, int Wo, const void* content, int Hc, int Wc, int B, const void* out) {
+  if (!stylized || !content || !out) { wct_set_error("content colours: null image pointer"); return WCT_ERR_ARG; }
+  if (B < 1 || B > 32) { wct_set_error("content colours: B = %d frames, must be 1 .. 32", B); return WCT_ERR_ARG; }
+  if (Hc < 1 || Wc < 1 || Ho < Hc || Wo < Wc) {
+    wct_set_error("content colours: a %dx%d stylized frame for a %dx%d content (the frame is never the smaller one)", Ho, Wo, Hc, Wc);
+    return WCT_ERR_ARG;
+  }
+  return WCT_OK;
+}
+
+extern "C" int wct_content_colors_batch_dev(wct_ctx* c, const uint8_t* stylized, int Ho, int Wo, const uint8_t* content, int Hc,
+                                            int Wc, int B, uint8_t* out) {
+  ARG_CHECK(c != nullptr);
+  TRY(content_colors_checks(stylized, Ho, Wo, content, Hc, Wc, B, out));
+  HIP_TRY(hipSetDevice(c->device));
+  ProfScope ps(c, 7, 0, (double)B * Ho * Wo * 3 * 2 + (double)B * Hc * Wc * 3);
+  return launch_content_colors_u8(stylized, content, B, Ho, Wo, Hc, Wc, out, c->stream);
+}
+
+extern "C" int wct_content_colors(wct_ctx* c, const uint8_t* stylized, int Ho, int Wo, const uint8_t* content, int Hc, int Wc,
+                                  uint8_t* out) {
+  ARG_CHECK(c != nullptr);
+  TRY(content_colors_checks(stylized, Ho, Wo, content, Hc, Wc, 1, out));
+  HIP_TRY(hipSetDevice(c->device));
+  void *ds, *dc;
+  TRY(stage_in(c, 0, stylized, (size_t)Ho * Wo * 3, &ds));
+  TRY(stage_in(c, 1, content, (size_t)Hc * Wc * 3, &dc));
+  TRY(wct_content_colors_batch_dev(c, (uint8_t*)ds, Ho, Wo, (uint8_t*)dc, Hc, Wc, 1, (uint8_t*)ds));    // (in place)
+  return fetch(c, out, ds, (size_t)Ho * Wo * 3);
+}

@@ -1,0 +1,776 @@
+// The stylize entry points: one predict() (wct.py:70-106) as a chain of launches on the context's stream -- with style images,
+// with prepared styles, with a warm start, and with spatial control of a video on prepared styles.
+#include "api.h"
+
+extern "C" int wct_output_size(int Hc, int Wc, const int* levels, int n_levels, int* Ho, int* Wo) {
+  ARG_CHECK(Ho && Wo);
+  Chain chain;
+  TRY(chain_geometry(Hc, Wc, levels, n_levels, &chain));
+  *Ho = chain.Ho; *Wo = chain.Wo;
+  return WCT_OK;
+}
+
+// The level check of every stylize driver: each level in range, served by all K handles (none with style images), its decoder loaded
+static int check_levels(const wct_ctx* c, const int* levels, int n_levels, const wct_style* const* handles = nullptr, int K = 0) {
+  for (int i = 0; i < n_levels; ++i) {
+    ARG_CHECK(levels[i] >= 1 && levels[i] <= 5);
+    for (int k = 0; k < K; ++k)
+      if (!(handles[k]->level_set & (1u << levels[i]))) {
+        wct_set_error("prepared style %d was not prepared for relu%d_1", k, levels[i]);
+        return WCT_ERR_ARG;
+      }
+    if (!c->dec[levels[i]].loaded) { wct_set_error("decoder weights for relu%d_1 not set", levels[i]); return WCT_ERR_STATE; }
+  }
+  return WCT_OK;
+}
+
+// The checks of a stylize call with style images before any launch: the levels and their decoders, the content chain (*chain), K
+// styles large enough for the deepest level (*deepest)
+static int stylize_checks(wct_ctx* c, int Hc, int Wc, const uint8_t* const* styles, const int* Hs, const int* Ws, int K,
+                          const int* levels, int n_levels, int* deepest, Chain* chain) {
+  TRY(check_levels(c, levels, n_levels));
+  TRY(chain_geometry(Hc, Wc, levels, n_levels, chain));
+  *deepest = *std::max_element(levels, levels + n_levels);
+  for (int k = 0; k < K; ++k) { ARG_CHECK(styles[k]); TRY(check_min_size("style", Hs[k], Ws[k], *deepest)); }
+  return WCT_OK;
+}
+
+static size_t sample_bytes(unsigned flags) { return (flags & WCT_FLAG_IMAGES_F32) ? sizeof(float) : 1; }   // per colour sample of the inputs
+
+// the content (nc samples) and style (ns) images as fp32 in [0,1] (wct.py:60-64): uint8 ones converted into img_c / img_s
+static int images_f32(wct_ctx* c, unsigned flags, const void* content, size_t nc, const void* style, size_t ns, const float** img_c,
+                      const float** img_s) {
+  *img_c = (const float*)content; *img_s = (const float*)style;
+  if (flags & WCT_FLAG_IMAGES_F32) return WCT_OK;
+  TRY(ensure(c, c->img_c, nc * 4));
+  TRY(ensure(c, c->img_s, ns * 4));
+  ProfScope ps(c, 7, 0, (double)(nc + ns) * 5);
+  TRY(launch_u8_to_f32((const uint8_t*)content, (float*)c->img_c.p, nc, c->stream));
+  TRY(launch_u8_to_f32((const uint8_t*)style, (float*)c->img_s.p, ns, c->stream));
+  *img_c = (const float*)c->img_c.p; *img_s = (const float*)c->img_s.p;
+  return WCT_OK;
+}
+
+// The per-channel sums and the largest value of every tap come out of the epilogue that writes it (16-pixel unit sums,
+// ConvArgs::usum): the transform's statistics pass then reads 1/16 of the feature bytes.  Needs a feature width that is
+// a multiple of 16; other widths (and WCT_FUSE_STATS=0) take the sums from the stored features -- the same bits.
+constexpr size_t UROW = 32 * UMAX_SLOTS;       // words per row of c->umax: 32 images
+static bool fuse_stats() {
+  static const int on = getenv("WCT_FUSE_STATS") ? atoi(getenv("WCT_FUSE_STATS")) : 1;
+  return on != 0;
+}
+
+// The content chain of a stylize call (model.py:77-101) on B contents img_c [B][Hc][Wc][3] fp32: per level of `chain` the encoder
+// pass with a tap (and its unit sums, umax row 0 -- its first umax_clear bytes cleared from level clear_from on), the transform, and
+// the decoder into the ping-pong images; then the uint8 frames into out (wct.py:66-68).
+// style_at(l, b, &hs, &ws): pair b's style features of relu<l>_1, hs x ws.  transform(i, g, st): level i (g: relu<g.l>_1, g.C
+// channels) of the g.h x g.w contents in c->feat_c -> c->wct_out (fp16), st the content's unit sums.  WCT_FLAG_SWAP5 runs the
+// style-swap at relu5_1 instead.  WCT_FLAG_CONTENT_COLORS: the last launch puts the frames' luminance on the colours of
+// content_raw, the contents as the caller gave them ([B][Hc][Wc][3] on the device: uint8, or fp32 with WCT_FLAG_IMAGES_F32).
+template <typename StyleAt, typename Transform>
+static int stylize_levels(wct_ctx* c, const float* img_c, const void* content_raw, int B, const Chain& chain, unsigned flags,
+                          size_t umax_clear, int clear_from, StyleAt&& style_at, Transform&& transform, uint8_t* out) {
+  unsigned* const umax_c = (unsigned*)c->umax.p;
+  const float* cur = img_c;
+  for (int i = 0; i < (int)chain.lv.size(); ++i) {
+    const ChainLevel& g = chain.lv[i];
+    const int l = g.l, C = g.C, h = g.h, w = g.w;
+    TRY(ensure(c, c->feat_c, (size_t)B * h * w * C * 4));
+    float* ctaps[6] = {};
+    ctaps[l] = (float*)c->feat_c.p;
+    float* us_c[6] = {};
+    unsigned* um_c[6] = {};
+    if (fuse_stats() && w % 16 == 0) {
+      TRY(ensure(c, c->usum_c, (size_t)B * h * (w / 16) * C * 4));
+      us_c[l] = (float*)c->usum_c.p; um_c[l] = umax_c;
+      if (i >= clear_from) HIP_TRY(hipMemsetAsync(umax_c, 0, umax_clear, c->stream));
+    }
+    WctFeatStats st = {};
+    st.u[0] = us_c[l]; st.umax[0] = um_c[l];
+    // level i>0 encodes clip(previous decoded, 0, 1) (model.py:86): the clamp is in the conv1_1 loader
+    TRY(run_encoder(c, cur, B, g.H, g.W, i > 0, l, ctaps, us_c, um_c));
+    TRY(ensure(c, c->wct_out, (size_t)B * h * w * C * 2));
+    if (l == 5 && (flags & WCT_FLAG_SWAP5)) {
+      // tf.case priority at relu5_1: swap5 > adain > wct (model.py:148-154); pairs one at a time
+      int hs, ws;
+      style_at(l, 0, &hs, &ws);
+      ARG_CHECK(h >= c->ss_patch && w >= c->ss_patch && hs >= c->ss_patch && ws >= c->ss_patch);
+      TRY(ensure(c, c->wct_ws, style_swap_workspace_bytes(C, h, w, hs, ws, c->ss_patch, c->ss_stride)));
+      ProfScope ps(c, 7, 0, 0);
+      for (int b = 0; b < B; ++b)
+        TRY(launch_style_swap((float*)c->feat_c.p + (size_t)b * h * w * C, h, w, style_at(l, b, &hs, &ws), hs, ws, C, c->ss_alpha,
+                              c->ss_patch, c->ss_stride, -1.f, (half_t*)c->wct_out.p + (size_t)b * h * w * C, nullptr,
+                              c->wct_ws.p, c->wct_ws.cap, c->stream, c->eig_fail_dev));
+    } else
+      TRY(transform(i, g, st));
+    DevBuf& dst = c->img_t[i & 1];                     // the decoder's h << (l - 1) by w << (l - 1) image: the next level's input
+    TRY(ensure(c, dst, (size_t)B * (h << (l - 1)) * (w << (l - 1)) * 3 * 4));
+    TRY(run_decoder(c, l, (half_t*)c->wct_out.p, B, h, w, (float*)dst.p));
+    cur = (float*)dst.p;
+  }
+  const int H = chain.Ho, W = chain.Wo, Hc = chain.lv[0].H, Wc = chain.lv[0].W;
+  if (flags & WCT_FLAG_CONTENT_COLORS) {
+    const int f32 = (flags & WCT_FLAG_IMAGES_F32) ? 1 : 0;
+    ProfScope ps(c, 7, 0, (double)B * H * W * 3 * 5 + (double)B * Hc * Wc * 3 * (f32 ? 4 : 1));
+    return launch_content_colors_f32(cur, content_raw, f32, B, H, W, Hc, Wc, out, c->stream);
+  }
+  ProfScope ps(c, 7, 0, (double)B * H * W * 3 * 5);
+  return launch_f32_to_u8(cur, out, (size_t)B * H * W * 3, c->stream);
+}
+
+// Host frame in, host frame out, around a device driver (B = 1): failures that earlier asynchronous work left are reported first,
+// the content goes through stage 0 and the frame comes back through stage 2.  enqueue(content_dev, out_dev) is the driver's call.
+template <typename Enqueue>
+static int host_frame(wct_ctx* c, const uint8_t* content, int Hc, int Wc, const int* levels, int n_levels, unsigned flags,
+                      uint8_t* out, Enqueue&& enqueue) {
+  HIP_TRY(hipSetDevice(c->device));
+  TRY(eig_stale(c));
+  int Ho, Wo;
+  TRY(wct_output_size(Hc, Wc, levels, n_levels, &Ho, &Wo));
+  void* dc;
+  TRY(stage_in(c, 0, content, (size_t)Hc * Wc * 3 * sample_bytes(flags), &dc));
+  TRY(ensure(c, c->stage[2], (size_t)Ho * Wo * 3));
+  TRY(enqueue(dc, (uint8_t*)c->stage[2].p));
+  TRY(fetch(c, out, c->stage[2].p, (size_t)Ho * Wo * 3));
+  return eig_status(c);
+}
+
+extern "C" int wct_stylize_batch_dev(wct_ctx* c, const uint8_t* content, int Hc, int Wc, const uint8_t* style,
+                                     int Hs, int Ws, int B, const int* levels, int n_levels, float alpha,
+                                     unsigned flags, uint8_t* out) {
+  ARG_CHECK(c && content && style && out && levels && n_levels >= 1 && n_levels <= 16 && B >= 1 && B <= 32);
+  HIP_TRY(hipSetDevice(c->device));
+  int deepest;
+  Chain chain;
+  TRY(stylize_checks(c, Hc, Wc, &style, &Hs, &Ws, 1, levels, n_levels, &deepest, &chain));
+
+  // WCT_FLAG_STYLE_SHARED: `style` is ONE image for all B pairs (a video with a fixed style); its encoder pass,
+  // statistics and eigensystems are computed once per call instead of once per pair
+  const int shared = (flags & WCT_FLAG_STYLE_SHARED) ? 1 : 0;
+  const int Bs = shared ? 1 : B;
+  const float *img_c, *img_s;
+  TRY(images_f32(c, flags, content, (size_t)B * Hc * Wc * 3, style, (size_t)Bs * Hs * Ws * 3, &img_c, &img_s));
+  const bool want_stats = fuse_stats();
+  TRY(ensure(c, c->umax, 7 * UROW * sizeof(unsigned)));
+  unsigned* const umax_c = (unsigned*)c->umax.p;                    // row 0: content (per level), rows 1..5: style levels
+  if (want_stats) HIP_TRY(hipMemsetAsync(c->umax.p, 0, 7 * UROW * sizeof(unsigned), c->stream));
+  // ONE style pass with a tap per requested level (model.py:69-75)
+  float* taps[6] = {};
+  float* us_s[6] = {};
+  unsigned* um_s[6] = {};
+  for (int i = 0; i < n_levels; ++i) {
+    const int l = levels[i];
+    int h, w;
+    level_dims(Hs, Ws, l, &h, &w);
+    TRY(ensure(c, c->feat_s[l], (size_t)Bs * h * w * LEVEL_C[l] * 4));
+    taps[l] = (float*)c->feat_s[l].p;
+    if (want_stats && w % 16 == 0) {
+      TRY(ensure(c, c->usum_s[l], (size_t)Bs * h * (w / 16) * LEVEL_C[l] * 4));
+      us_s[l] = (float*)c->usum_s[l].p; um_s[l] = umax_c + UROW * l;
+    }
+  }
+  TRY(run_encoder(c, img_s, Bs, Hs, Ws, 0, deepest, taps, us_s, um_s));
+
+  // the content chain; its umax row was cleared with the others for level 0
+  auto style_at = [&](int l, int b, int* hs, int* ws) {
+    level_dims(Hs, Ws, l, hs, ws);
+    return (const float*)c->feat_s[l].p + (size_t)(shared ? 0 : b) * *hs * *ws * LEVEL_C[l];
+  };
+  return stylize_levels(c, img_c, content, B, chain, flags, UROW * sizeof(unsigned), 1, style_at,
+                        [&](int, const ChainLevel& g, WctFeatStats st) {
+                          int hs, ws;
+                          const float* fs = style_at(g.l, 0, &hs, &ws);
+                          st.u[1] = us_s[g.l]; st.umax[1] = um_s[g.l];
+                          return run_transform(c, (float*)c->feat_c.p, g.h * g.w, fs, hs * ws, g.C, B, alpha, flags, -1.f,
+                                               (half_t*)c->wct_out.p, nullptr, nullptr, &st);
+                        }, out);
+}
+
+extern "C" int wct_stylize(wct_ctx* c, const uint8_t* content, int Hc, int Wc, const uint8_t* style, int Hs, int Ws,
+                           const int* levels, int n_levels, float alpha, unsigned flags, uint8_t* out) {
+  ARG_CHECK(c && content && style && out);
+  return host_frame(c, content, Hc, Wc, levels, n_levels, flags, out, [&](void* dc, uint8_t* frame) {
+    void* ds;
+    TRY(stage_in(c, 1, style, (size_t)Hs * Ws * 3 * sample_bytes(flags), &ds));
+    return wct_stylize_batch_dev(c, (uint8_t*)dc, Hc, Wc, (uint8_t*)ds, Hs, Ws, 1, levels, n_levels, alpha, flags, frame);
+  });
+}
+
+// The body of wct_stylize_mix / wct_stylize_masked (their checks done): the style encoder runs once per style (sizes may differ),
+// then the content chain with B = 1, `level_transform` in the place of the single-style transform.
+// level_transform(g, fs, Ns, st): stylize_levels' transform of level g, fs[k] / Ns[k] style k's features of the level.
+// (Not through host_frame: its checks come before the report of stale failures.)
+// WCT_FLAG_SWAP5 (K = 1) runs wct_stylize's style-swap at relu5_1 instead.
+template <typename LevelTransform>
+static int stylize_multi(wct_ctx* c, const uint8_t* content, int Hc, int Wc, const uint8_t* const* styles, const int* Hs,
+                         const int* Ws, int K, const int* levels, int n_levels, unsigned flags, uint8_t* out,
+                         LevelTransform&& level_transform) {
+  HIP_TRY(hipSetDevice(c->device));
+  int deepest;
+  Chain chain;
+  TRY(stylize_checks(c, Hc, Wc, styles, Hs, Ws, K, levels, n_levels, &deepest, &chain));
+  TRY(eig_stale(c));
+  // inputs: the content in stage 0, the K styles back to back in mix_in
+  const size_t px = sample_bytes(flags);
+  size_t ns_tot = 0, soff[WCT_MIX_MAX];
+  for (int k = 0; k < K; ++k) { soff[k] = ns_tot; ns_tot += (size_t)Hs[k] * Ws[k] * 3; }
+  const size_t nc = (size_t)Hc * Wc * 3;
+  void* dc;
+  TRY(stage_in(c, 0, content, nc * px, &dc));
+  TRY(ensure(c, c->mix_in, ns_tot * px));
+  for (int k = 0; k < K; ++k)
+    HIP_TRY(hipMemcpyAsync((char*)c->mix_in.p + soff[k] * px, styles[k], (size_t)Hs[k] * Ws[k] * 3 * px, hipMemcpyHostToDevice, c->stream));
+  const float *img_c, *img_s;
+  TRY(images_f32(c, flags, dc, nc, c->mix_in.p, ns_tot, &img_c, &img_s));
+
+  // one style pass per style, a tap per requested level (model.py:69-75); style k's map of level l at feat_mix[l] + foff[l][k]
+  // (statistics from the stored features: the same bits as the epilogue's unit sums, colsum_kernel)
+  size_t foff[6][WCT_MIX_MAX];
+  for (int i = 0; i < n_levels; ++i) {
+    const int l = levels[i];
+    size_t tot = 0;
+    for (int k = 0; k < K; ++k) {
+      int h, w;
+      level_dims(Hs[k], Ws[k], l, &h, &w);
+      foff[l][k] = tot;
+      tot += (size_t)h * w * LEVEL_C[l];
+    }
+    TRY(ensure(c, c->feat_mix[l], tot * 4));
+  }
+  for (int k = 0; k < K; ++k) {
+    float* taps[6] = {};
+    for (int i = 0; i < n_levels; ++i) taps[levels[i]] = (float*)c->feat_mix[levels[i]].p + foff[levels[i]][k];
+    TRY(run_encoder(c, img_s + soff[k], 1, Hs[k], Ws[k], 0, deepest, taps));
+  }
+
+  // the content chain, B = 1: pair k is style k (the style-swap takes K = 1); its umax row is cleared at every level
+  TRY(ensure(c, c->umax, 32 * UMAX_SLOTS * sizeof(unsigned)));
+  const size_t frame_bytes = (size_t)chain.Ho * chain.Wo * 3;
+  TRY(ensure(c, c->stage[2], frame_bytes));
+  auto style_at = [&](int l, int k, int* hs, int* ws) {
+    level_dims(Hs[k], Ws[k], l, hs, ws);
+    return (const float*)c->feat_mix[l].p + foff[l][k];
+  };
+  TRY(stylize_levels(c, img_c, dc, 1, chain, flags, UMAX_SLOTS * sizeof(unsigned), 0, style_at,
+                     [&](int, const ChainLevel& g, const WctFeatStats& st) {
+                       const float* fs[WCT_MIX_MAX];
+                       int Ns[WCT_MIX_MAX];
+                       for (int k = 0; k < K; ++k) {
+                         int hs, ws;
+                         fs[k] = style_at(g.l, k, &hs, &ws);
+                         Ns[k] = hs * ws;
+                       }
+                       return level_transform(g, fs, Ns, &st);
+                     }, (uint8_t*)c->stage[2].p));
+  TRY(fetch(c, out, c->stage[2].p, frame_bytes));
+  return eig_status(c);
+}
+
+// One predict() with a style mix at every level (Li et al. 2017, sec. 4.2): stylize_multi with the mix in the place of the
+// single-style transform.
+extern "C" int wct_stylize_mix(wct_ctx* c, const uint8_t* content, int Hc, int Wc, const uint8_t* const* styles, const int* Hs,
+                               const int* Ws, int K, const float* weights, const int* levels, int n_levels, float alpha,
+                               unsigned flags, uint8_t* out) {
+  ARG_CHECK(c && content && styles && Hs && Ws && out && levels && n_levels >= 1 && n_levels <= 16);
+  float lambda[WCT_MIX_MAX];
+  TRY(mix_weights(weights, K, lambda));
+  if ((flags & WCT_FLAG_SWAP5) && K > 1) {
+    wct_set_error("style mix: WCT_FLAG_SWAP5 needs K = 1 (style-swap is not linear in the style; got K = %d)", K);
+    return WCT_ERR_ARG;
+  }
+  if (flags & WCT_FLAG_STYLE_SHARED) { wct_set_error("style mix: WCT_FLAG_STYLE_SHARED is for wct_stylize_batch_dev"); return WCT_ERR_ARG; }
+  return stylize_multi(c, content, Hc, Wc, styles, Hs, Ws, K, levels, n_levels, flags, out,
+                       [&](const ChainLevel& g, const float* const* fs, const int* Ns, const WctFeatStats* st) {
+                         return run_transform_mix(c, (float*)c->feat_c.p, g.h * g.w, fs, Ns, K, lambda, g.C, alpha, flags, -1.f,
+                                                  (half_t*)c->wct_out.p, nullptr, nullptr, st);
+                       });
+}
+
+// One predict() with spatial control at every level (Li et al. 2017, sec. 4.2, Fig. 7): stylize_multi with the masked transform
+// in the place of the single-style transform.  The labels of a level are counted on the host (they size its launches; nothing is
+// read back) when the chain, whose geometry says which pixels they are, reaches the level.
+extern "C" int wct_stylize_masked(wct_ctx* c, const uint8_t* content, int Hc, int Wc, const uint8_t* mask, const uint8_t* const* styles,
+                                  const int* Hs, const int* Ws, int K, const int* levels, int n_levels, float alpha, unsigned flags,
+                                  uint8_t* out) {
+  ARG_CHECK(c && content && mask && styles && Hs && Ws && out && levels && n_levels >= 1 && n_levels <= 16 && Hc >= 2 && Wc >= 2);
+  TRY(mask_check(mask, (size_t)Hc * Wc, K));
+  if ((flags & WCT_FLAG_SWAP5) && K > 1) {
+    wct_set_error("mask: WCT_FLAG_SWAP5 needs K = 1 (style-swap is not a per-region affine map; got K = %d)", K);
+    return WCT_ERR_ARG;
+  }
+  if (flags & WCT_FLAG_STYLE_SHARED) { wct_set_error("mask: WCT_FLAG_STYLE_SHARED is for wct_stylize_batch_dev"); return WCT_ERR_ARG; }
+  for (int i = 0; i < n_levels; ++i) ARG_CHECK(levels[i] >= 1 && levels[i] <= 5);    // (before anything is enqueued)
+  HIP_TRY(hipSetDevice(c->device));
+  TRY(ensure(c, c->mask_in, (size_t)Hc * Wc));
+  HIP_TRY(hipMemcpyAsync(c->mask_in.p, mask, (size_t)Hc * Wc, hipMemcpyHostToDevice, c->stream));
+  return stylize_multi(c, content, Hc, Wc, styles, Hs, Ws, K, levels, n_levels, flags, out,
+                       [&](const ChainLevel& g, const float* const* fs, const int* Ns, const WctFeatStats*) {
+                         int nk[WCT_MIX_MAX];
+                         mask_counts(mask, Hc, Wc, g.h, g.w, 1 << (g.l - 1), K, nk);
+                         const MaskGeom mg = {(const uint8_t*)c->mask_in.p, Hc, Wc, g.w, 1 << (g.l - 1)};
+                         return run_transform_masked(c, (float*)c->feat_c.p, g.h * g.w, mg, nk, fs, Ns, K, g.C, alpha, flags, -1.f,
+                                                     (half_t*)c->wct_out.p, nullptr, nullptr);
+                       });
+}
+
+// ---------------------------------------------------------------------------
+// video warm start (stylize_video.py:112-135 calls predict() per frame and solves every content covariance from scratch): the
+// content eigensolves of a call start from the eigenvectors of the previous call's last frame (csrc/warm.hip)
+// ---------------------------------------------------------------------------
+int warm_live(const wct_ctx* c, const wct_warm* wm) {
+  if (wm && std::find(c->warms.begin(), c->warms.end(), wm) != c->warms.end()) return WCT_OK;
+  wct_set_error("warm state %p is not a live state of this context (freed, or created by another context)", (const void*)wm);
+  return WCT_ERR_STATE;
+}
+
+extern "C" int wct_warm_create(wct_ctx* c, const int* levels, int n_levels, wct_warm** out) {
+  ARG_CHECK(c && levels && out && n_levels >= 1 && n_levels <= 16);
+  *out = nullptr;
+  for (int i = 0; i < n_levels; ++i) ARG_CHECK(levels[i] >= 1 && levels[i] <= 5);
+  HIP_TRY(hipSetDevice(c->device));
+  std::unique_ptr<wct_warm> wm(new wct_warm());
+  for (int i = 0; i < n_levels; ++i) {
+    const int l = levels[i];
+    if (wm->basis[l]) continue;
+    wm->level_set |= 1u << l;
+    if (hipMalloc((void**)&wm->basis[l], (size_t)LEVEL_C[l] * LEVEL_C[l] * sizeof(float)) != hipSuccess) {
+      wct_set_error("hipMalloc failed (warm state, relu%d_1)", l);
+      return WCT_ERR_NOMEM;
+    }
+  }
+  c->warms.push_back(wm.get());
+  *out = wm.release();
+  return WCT_OK;
+}
+
+extern "C" void wct_warm_free(wct_ctx* c, wct_warm* wm) {
+  if (!c || !wm) return;
+  auto it = std::find(c->warms.begin(), c->warms.end(), wm);
+  if (it == c->warms.end()) return;                       // not ours, or freed already
+  hipSetDevice(c->device);
+  hipStreamSynchronize(c->stream);                        // frames in flight may still read its bases
+  c->warms.erase(it);
+  c->warm_used.erase(std::remove(c->warm_used.begin(), c->warm_used.end(), wm), c->warm_used.end());
+  delete wm;
+}
+
+extern "C" int wct_warm_reset(wct_ctx* c, wct_warm* wm) {
+  ARG_CHECK(c != nullptr);
+  TRY(warm_live(c, wm));
+  for (bool& v : wm->valid) v = false;
+  return WCT_OK;
+}
+
+extern "C" int wct_warm_basis(wct_ctx* c, const wct_warm* wm, int level, int* valid, float* V_host) {
+  ARG_CHECK(c && valid);
+  TRY(warm_live(c, wm));
+  if (level < 1 || level > 5 || !(wm->level_set & (1u << level))) {
+    wct_set_error("warm state: relu%d_1 is not in the state's level set", level);
+    return WCT_ERR_ARG;
+  }
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  *valid = wm->valid[level] ? 1 : 0;
+  if (V_host && wm->valid[level]) TRY(fetch(c, V_host, wm->basis[level], (size_t)LEVEL_C[level] * LEVEL_C[level] * sizeof(float)));
+  return WCT_OK;
+}
+
+// ---------------------------------------------------------------------------
+// prepared styles: the style side once, any number of contents (wct.py:70-106 / stylize_video.py:88-121 with a fixed style)
+// ---------------------------------------------------------------------------
+static int style_live(const wct_ctx* c, const wct_style* st) {
+  if (st && std::find(c->styles.begin(), c->styles.end(), st) != c->styles.end()) return WCT_OK;
+  wct_set_error("prepared style %p is not a live handle of this context (freed, or prepared by another context)", (const void*)st);
+  return WCT_ERR_STATE;
+}
+
+static bool same_key(const WctStyleKey& a, const WctStyleKey& b) { return a.nslab == b.nslab && a.nsplit == b.nsplit && a.ksplit == b.ksplit; }
+
+static StyleState* state_find(wct_style* st, int level, const WctStyleKey& key, int kind) {
+  for (auto& e : st->cache[level])
+    if (e.kind == kind && same_key(e.key, key)) return &e;
+  return nullptr;
+}
+
+struct StyleNeed { int level; WctStyleKey key; };
+
+// Computes the states `needs` of a handle for one kind (none of them cached) on the ctx stream: ONE encoder pass of the style with a tap per
+// level needed, then launch_style_state per state.  Blocking, and the eigensolves are checked before a state is kept: on
+// WCT_ERR_NOCONV (or any error) none of them stays in the cache.
+static int style_fill(wct_ctx* c, wct_style* st, int kind, const std::vector<StyleNeed>& needs) {
+  if (needs.empty()) return WCT_OK;
+  HIP_TRY(hipStreamSynchronize(c->stream));               // (a state evicted below may belong to frames still in flight)
+  int deepest = 0;
+  float* taps[6] = {};
+  for (const StyleNeed& n : needs) {
+    int h, w;
+    level_dims(st->Hs, st->Ws, n.level, &h, &w);
+    TRY(ensure(c, c->feat_s[n.level], (size_t)h * w * LEVEL_C[n.level] * 4));
+    taps[n.level] = (float*)c->feat_s[n.level].p;
+    deepest = std::max(deepest, n.level);
+  }
+  TRY(run_encoder(c, st->img, 1, st->Hs, st->Ws, 0, deepest, taps));
+  std::vector<float*> fresh;
+  int rc = WCT_OK;
+  for (const StyleNeed& n : needs) {
+    const int C = LEVEL_C[n.level];
+    int h, w;
+    level_dims(st->Hs, st->Ws, n.level, &h, &w);
+    auto& lv = st->cache[n.level];
+    float* buf = nullptr;
+    if ((int)lv.size() >= STYLE_CACHE_KEYS) {            // the oldest state that this call does not use makes room
+      int old = -1;
+      for (int i = 0; i < (int)lv.size(); ++i)
+        if (lv[i].stamp != c->style_clock && (old < 0 || lv[i].stamp < lv[old].stamp)) old = i;
+      if (old >= 0) { buf = lv[old].buf; lv.erase(lv.begin() + old); }
+    }
+    if (!buf && hipMalloc((void**)&buf, wct_style_state_floats(C) * sizeof(float)) != hipSuccess) {
+      wct_set_error("hipMalloc failed (prepared style state, relu%d_1)", n.level);
+      rc = WCT_ERR_NOMEM;
+      break;
+    }
+    lv.push_back(StyleState{n.key, kind, buf, c->style_clock});
+    fresh.push_back(buf);
+    if (hipMemsetAsync(buf, 0, wct_style_state_floats(C) * sizeof(float), c->stream) != hipSuccess) { wct_set_error("hipMemsetAsync failed"); rc = WCT_ERR_HIP; break; }
+    if ((rc = ensure(c, c->wct_ws, wct_style_workspace_bytes(C, h * w, n.key)))) break;
+    ProfScope ps(c, kind == 2 ? 7 : 5, 0, 0);
+    if ((rc = launch_style_state(taps[n.level], h * w, C, n.key, kind == 2, kind == 1 ? WCT_MODE_NP : WCT_MODE_TF, -1.f, c->wct_ws.p,
+                                 c->wct_ws.cap, c->eig_fail_dev, c->stream, buf)))
+      break;
+  }
+  if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) { wct_set_error("hipStreamSynchronize failed (prepared style)"); rc = WCT_ERR_HIP; }
+  if (!rc) rc = eig_status(c);
+  if (rc) {                                               // keep nothing of a failed fill
+    hipStreamSynchronize(c->stream);
+    for (auto& lv : st->cache)
+      for (size_t i = lv.size(); i-- > 0;)
+        if (std::find(fresh.begin(), fresh.end(), lv[i].buf) != fresh.end()) { hipFree(lv[i].buf); lv.erase(lv.begin() + i); }
+  }
+  return rc;
+}
+
+// The states `needs` of handle k of the running call (duplicates allowed), one buffer per need in *bufs: the cached ones are stamped
+// with the call -- a state the running call uses is never evicted --, the distinct missing ones computed by ONE style_fill
+static int style_states(wct_ctx* c, int k, wct_style* st, int kind, const std::vector<StyleNeed>& needs, std::vector<const float*>* bufs) {
+  std::vector<StyleNeed> missing;
+  for (const StyleNeed& n : needs) {
+    StyleState* e = state_find(st, n.level, n.key, kind);
+    if (e) e->stamp = c->style_clock;
+    else if (std::none_of(missing.begin(), missing.end(), [&](const StyleNeed& m) { return m.level == n.level && same_key(m.key, n.key); }))
+      missing.push_back(n);
+  }
+  TRY(style_fill(c, st, kind, missing));
+  bufs->clear();
+  for (const StyleNeed& n : needs) {
+    StyleState* e = state_find(st, n.level, n.key, kind);
+    if (!e) { wct_set_error("prepared style %d: the state of relu%d_1 is gone", k, n.level); return WCT_ERR_STATE; }
+    bufs->push_back(e->buf);
+  }
+  return WCT_OK;
+}
+
+static int style_kind(unsigned flags) { return (flags & WCT_FLAG_ADAIN) ? 2 : ((flags & WCT_FLAG_MODE_NP) ? 1 : 0); }
+
+static int style_flags_ok(unsigned flags) {
+  if (flags & WCT_FLAG_SWAP5) {
+    wct_set_error("prepared style: WCT_FLAG_SWAP5 needs the style's relu5_1 map and patches, which a handle does not hold");
+    return WCT_ERR_ARG;
+  }
+  if (flags & WCT_FLAG_STYLE_SHARED) { wct_set_error("prepared style: WCT_FLAG_STYLE_SHARED is for wct_stylize_batch_dev"); return WCT_ERR_ARG; }
+  return WCT_OK;
+}
+
+extern "C" int wct_style_prepare(wct_ctx* c, const uint8_t* style, int Hs, int Ws, const int* levels, int n_levels, unsigned flags,
+                                 wct_style** out) {
+  ARG_CHECK(c && style && levels && out && n_levels >= 1 && n_levels <= 16 && Hs >= 2 && Ws >= 2);
+  *out = nullptr;
+  TRY(style_flags_ok(flags));
+  unsigned set = 0;
+  int deepest = 0;
+  for (int i = 0; i < n_levels; ++i) {
+    ARG_CHECK(levels[i] >= 1 && levels[i] <= 5);
+    set |= 1u << levels[i];
+    deepest = std::max(deepest, levels[i]);
+  }
+  TRY(check_min_size("style", Hs, Ws, deepest));
+  if (!c->enc_loaded) { wct_set_error("encoder weights not set (wct_set_encoder)"); return WCT_ERR_STATE; }
+  HIP_TRY(hipSetDevice(c->device));
+  TRY(eig_stale(c));
+  std::unique_ptr<wct_style> owner(new wct_style());
+  wct_style* st = owner.get();
+  st->Hs = Hs; st->Ws = Ws; st->level_set = set;
+  const size_t n = (size_t)Hs * Ws * 3;
+  HIP_TRY(hipMalloc((void**)&st->img, n * sizeof(float)));
+  void* ds;
+  TRY(stage_in(c, 1, style, n * sample_bytes(flags), &ds));
+  if (flags & WCT_FLAG_IMAGES_F32) HIP_TRY(hipMemcpyAsync(st->img, ds, n * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+  else TRY(launch_u8_to_f32((const uint8_t*)ds, st->img, n, c->stream));
+  // the states of "a content as large as the style", in the mode the flags name; every other key on first use
+  ++c->style_clock;
+  std::vector<StyleNeed> needs;
+  for (int l = 1; l <= 5; ++l) {
+    if (!(set & (1u << l))) continue;
+    int h, w;
+    level_dims(Hs, Ws, l, &h, &w);
+    needs.push_back(StyleNeed{l, wct_style_key(LEVEL_C[l], h * w, h * w)});
+  }
+  TRY(style_fill(c, st, style_kind(flags), needs));
+  c->styles.push_back(st);
+  *out = owner.release();
+  return WCT_OK;
+}
+
+extern "C" void wct_style_free(wct_ctx* c, wct_style* st) {
+  if (!c || !st) return;
+  auto it = std::find(c->styles.begin(), c->styles.end(), st);
+  if (it == c->styles.end()) return;                      // not ours, or freed already
+  hipSetDevice(c->device);
+  hipStreamSynchronize(c->stream);                        // frames in flight may still read its states
+  c->styles.erase(it);
+  delete st;
+}
+
+// The prelude of a content chain on prepared styles: the nc colour samples of the contents as fp32 in [0,1] (*img_c: uint8 ones
+// converted into c->img_c), and c->umax with the content's row cleared (the row of wct_stylize_batch_dev)
+static int content_prelude(wct_ctx* c, unsigned flags, const void* content, size_t nc, const float** img_c) {
+  *img_c = (const float*)content;
+  if (!(flags & WCT_FLAG_IMAGES_F32)) {
+    TRY(ensure(c, c->img_c, nc * 4));
+    ProfScope ps(c, 7, 0, (double)nc * 5);
+    TRY(launch_u8_to_f32((const uint8_t*)content, (float*)c->img_c.p, nc, c->stream));
+    *img_c = (const float*)c->img_c.p;
+  }
+  TRY(ensure(c, c->umax, 7 * UROW * sizeof(unsigned)));
+  if (fuse_stats()) HIP_TRY(hipMemsetAsync(c->umax.p, 0, UROW * sizeof(unsigned), c->stream));
+  return WCT_OK;
+}
+
+// stylize_levels' style_at of a chain on handles: no style features (style-swap alone asks for them)
+static const float* no_style_at(int, int, int* hs, int* ws) { *hs = *ws = 0; return nullptr; }
+
+// The body of the wct_stylize_prepared* calls (their pointer and flag checks done): B contents [B][Hc][Wc][3] on the device, K
+// handles; lambda null: one style for all B (K = 1), else the mix weights of K styles (B = 1).  Asynchronous unless a handle
+// has to compute a state (style_fill), which happens before anything of the content chain is enqueued.
+static int stylize_prepared_dev(wct_ctx* c, const void* content, int Hc, int Wc, int B, const wct_style* const* styles, int K,
+                                const float* lambda, const int* levels, int n_levels, float alpha, unsigned flags, uint8_t* out,
+                                wct_warm* warm = nullptr /* with one style (lambda null): start the content solves from it */) {
+  HIP_TRY(hipSetDevice(c->device));
+  for (int k = 0; k < K; ++k) TRY(style_live(c, styles[k]));
+  if (warm) {
+    TRY(warm_live(c, warm));
+    if (flags & WCT_FLAG_ADAIN) { wct_set_error("warm start: WCT_FLAG_ADAIN has no eigensolve to start"); return WCT_ERR_ARG; }
+    unsigned set = 0;
+    for (int i = 0; i < n_levels; ++i) { ARG_CHECK(levels[i] >= 1 && levels[i] <= 5); set |= 1u << levels[i]; }
+    if (set != warm->level_set) {
+      wct_set_error("warm start: the levels of the call (set 0x%x) are not the levels the state was created for (0x%x)", set, warm->level_set);
+      return WCT_ERR_ARG;
+    }
+  }
+  TRY(check_levels(c, levels, n_levels, styles, K));
+  Chain chain;
+  TRY(chain_geometry(Hc, Wc, levels, n_levels, &chain));
+
+  // the states of every level, before any launch of the content chain: style k serves the layout of (content, style k)
+  const int kind = style_kind(flags);
+  ++c->style_clock;
+  std::vector<WctStyleRef> refs(n_levels);
+  std::vector<int> ns((size_t)n_levels * WCT_MIX_MAX);
+  for (int k = 0; k < K; ++k) {
+    wct_style* st = const_cast<wct_style*>(styles[k]);
+    std::vector<StyleNeed> needs;
+    for (int i = 0; i < n_levels; ++i) {
+      const ChainLevel& g = chain.lv[i];
+      int hs, ws;
+      level_dims(st->Hs, st->Ws, g.l, &hs, &ws);
+      ns[(size_t)i * WCT_MIX_MAX + k] = hs * ws;
+      needs.push_back(StyleNeed{g.l, wct_style_key(g.C, g.h * g.w, hs * ws)});
+    }
+    std::vector<const float*> bufs;
+    TRY(style_states(c, k, st, kind, needs, &bufs));
+    for (int i = 0; i < n_levels; ++i) refs[i].state[k] = bufs[i];
+  }
+
+  const float* img_c;
+  TRY(content_prelude(c, flags, content, (size_t)B * Hc * Wc * 3, &img_c));
+  if (warm && std::find(c->warm_used.begin(), c->warm_used.end(), warm) == c->warm_used.end()) c->warm_used.push_back(warm);
+  return stylize_levels(c, img_c, content, B, chain, flags, UROW * sizeof(unsigned), 1, no_style_at,
+                        [&](int i, const ChainLevel& g, const WctFeatStats& st) {
+                          const int* Ns = &ns[(size_t)i * WCT_MIX_MAX];
+                          if (lambda)
+                            return run_transform_mix(c, (float*)c->feat_c.p, g.h * g.w, nullptr, Ns, K, lambda, g.C, alpha, flags, -1.f,
+                                                     (half_t*)c->wct_out.p, nullptr, nullptr, &st, &refs[i]);
+                          WctWarmRef wr = {};
+                          if (warm) wr = {warm->basis[g.l], warm->valid[g.l] ? 1 : 0};
+                          TRY(run_transform(c, (float*)c->feat_c.p, g.h * g.w, nullptr, Ns[0], g.C, B, alpha, flags, -1.f,
+                                            (half_t*)c->wct_out.p, nullptr, nullptr, &st, &refs[i], warm ? &wr : nullptr));
+                          if (warm) warm->valid[g.l] = true;     // (the basis of frame B - 1 is enqueued)
+                          return (int)WCT_OK;
+                        }, out);
+}
+
+// host content in, host frame out, around stylize_prepared_dev (B = 1)
+static int stylize_prepared_host(wct_ctx* c, const uint8_t* content, int Hc, int Wc, const wct_style* const* styles, int K,
+                                 const float* lambda, const int* levels, int n_levels, float alpha, unsigned flags, uint8_t* out,
+                                 wct_warm* warm = nullptr) {
+  return host_frame(c, content, Hc, Wc, levels, n_levels, flags, out, [&](void* dc, uint8_t* frame) {
+    return stylize_prepared_dev(c, dc, Hc, Wc, 1, styles, K, lambda, levels, n_levels, alpha, flags, frame, warm);
+  });
+}
+
+extern "C" int wct_stylize_prepared(wct_ctx* c, const uint8_t* content, int Hc, int Wc, const wct_style* style, const int* levels,
+                                    int n_levels, float alpha, unsigned flags, uint8_t* out) {
+  ARG_CHECK(c && content && out && levels && n_levels >= 1 && n_levels <= 16);
+  TRY(style_flags_ok(flags));
+  return stylize_prepared_host(c, content, Hc, Wc, &style, 1, nullptr, levels, n_levels, alpha, flags, out);
+}
+
+extern "C" int wct_stylize_prepared_batch_dev(wct_ctx* c, const uint8_t* content, int Hc, int Wc, int B, const wct_style* style,
+                                              const int* levels, int n_levels, float alpha, unsigned flags, uint8_t* out) {
+  ARG_CHECK(c && content && out && levels && n_levels >= 1 && n_levels <= 16 && B >= 1 && B <= 32);
+  TRY(style_flags_ok(flags));
+  return stylize_prepared_dev(c, content, Hc, Wc, B, &style, 1, nullptr, levels, n_levels, alpha, flags, out);
+}
+
+extern "C" int wct_stylize_prepared_mix(wct_ctx* c, const uint8_t* content, int Hc, int Wc, const wct_style* const* styles, int K,
+                                        const float* weights, const int* levels, int n_levels, float alpha, unsigned flags, uint8_t* out) {
+  ARG_CHECK(c && content && styles && out && levels && n_levels >= 1 && n_levels <= 16);
+  float lambda[WCT_MIX_MAX];
+  TRY(mix_weights(weights, K, lambda));
+  TRY(style_flags_ok(flags));
+  return stylize_prepared_host(c, content, Hc, Wc, styles, K, lambda, levels, n_levels, alpha, flags, out);
+}
+
+extern "C" int wct_stylize_prepared_warm(wct_ctx* c, const uint8_t* content, int Hc, int Wc, const wct_style* style, const int* levels,
+                                         int n_levels, float alpha, unsigned flags, wct_warm* warm, uint8_t* out) {
+  ARG_CHECK(c && content && out && levels && n_levels >= 1 && n_levels <= 16);
+  TRY(style_flags_ok(flags));
+  TRY(warm_live(c, warm));
+  return stylize_prepared_host(c, content, Hc, Wc, &style, 1, nullptr, levels, n_levels, alpha, flags, out, warm);
+}
+
+extern "C" int wct_stylize_prepared_batch_dev_warm(wct_ctx* c, const uint8_t* content, int Hc, int Wc, int B, const wct_style* style,
+                                                   const int* levels, int n_levels, float alpha, unsigned flags, wct_warm* warm,
+                                                   uint8_t* out) {
+  ARG_CHECK(c && content && out && levels && n_levels >= 1 && n_levels <= 16 && B >= 1 && B <= 32);
+  TRY(style_flags_ok(flags));
+  TRY(warm_live(c, warm));
+  return stylize_prepared_dev(c, content, Hc, Wc, B, &style, 1, nullptr, levels, n_levels, alpha, flags, out, warm);
+}
+
+// Spatial control of B frames on prepared styles: one label map per frame (on the HOST: every level's labels are counted here,
+// before any launch, and size the launches), K handles shared by all frames.  The level transform runs the frames in GROUPS of at
+// most WCT_PLAN_PAIRS = 32 live (frame, region) pairs -- one batched eigensolve of 64 slots, the style slots dead -- through
+// launch_wct_masked_batch; a matrix's eigensystem does not depend on its batch, so the grouping does not show in the frames.
+// Pair (f, k) takes handle k's state under wct_style_key(C, N_fk, Ns_k); the missing ones are filled in front of the content
+// chain (style_fill), and a state the running call uses is never evicted (its stamp is the call's), so a level's cache holds
+// as many keys as the call with the most distinct region sizes needed (at least STYLE_CACHE_KEYS, at most B per label).
+static int stylize_prepared_masked_dev(wct_ctx* c, const void* content, int Hc, int Wc, int B, const uint8_t* masks,
+                                       const wct_style* const* styles, int K, const int* levels, int n_levels, float alpha,
+                                       unsigned flags, uint8_t* out) {
+  HIP_TRY(hipSetDevice(c->device));
+  if (K < 1 || K > WCT_MIX_MAX) { wct_set_error("mask: K = %d styles, must be 1 .. %d", K, (int)WCT_MIX_MAX); return WCT_ERR_ARG; }
+  for (int k = 0; k < K; ++k) TRY(style_live(c, styles[k]));
+  TRY(mask_check(masks, (size_t)B * Hc * Wc, K));
+  TRY(check_levels(c, levels, n_levels, styles, K));
+  Chain chain;
+  TRY(chain_geometry(Hc, Wc, levels, n_levels, &chain));
+
+  // the labels of every level and frame, counted on the host: nk [level][frame][WCT_MIX_MAX]
+  const size_t fstride = (size_t)B * WCT_MIX_MAX;
+  std::vector<int> nk((size_t)n_levels * fstride), ns((size_t)n_levels * WCT_MIX_MAX);
+  for (int i = 0; i < n_levels; ++i) {
+    const ChainLevel& g = chain.lv[i];
+    for (int f = 0; f < B; ++f)
+      mask_counts(masks + (size_t)f * Hc * Wc, Hc, Wc, g.h, g.w, 1 << (g.l - 1), K, &nk[i * fstride + (size_t)f * WCT_MIX_MAX]);
+    for (int k = 0; k < K; ++k) {
+      int hs, ws;
+      level_dims(styles[k]->Hs, styles[k]->Ws, g.l, &hs, &ws);
+      ns[(size_t)i * WCT_MIX_MAX + k] = hs * ws;
+    }
+  }
+
+  // the states of every live (level, frame, region), before any launch of the content chain
+  const int kind = style_kind(flags);
+  ++c->style_clock;
+  std::vector<const float*> states((size_t)n_levels * fstride, nullptr), bufs;
+  for (int k = 0; k < K; ++k) {
+    std::vector<StyleNeed> needs;
+    std::vector<size_t> slot;                            // need j is the state of pair slot[j]
+    for (int i = 0; i < n_levels; ++i)
+      for (int f = 0; f < B; ++f) {
+        const size_t at = i * fstride + (size_t)f * WCT_MIX_MAX + k;
+        if (nk[at] < 2) continue;
+        needs.push_back(StyleNeed{levels[i], wct_style_key(chain.lv[i].C, nk[at], ns[(size_t)i * WCT_MIX_MAX + k])});
+        slot.push_back(at);
+      }
+    TRY(style_states(c, k, const_cast<wct_style*>(styles[k]), kind, needs, &bufs));
+    for (size_t j = 0; j < slot.size(); ++j) states[slot[j]] = bufs[j];
+  }
+
+  TRY(ensure(c, c->mask_in, (size_t)B * Hc * Wc));
+  HIP_TRY(hipMemcpyAsync(c->mask_in.p, masks, (size_t)B * Hc * Wc, hipMemcpyHostToDevice, c->stream));
+  const float* img_c;
+  TRY(content_prelude(c, flags, content, (size_t)B * Hc * Wc * 3, &img_c));
+  return stylize_levels(c, img_c, content, B, chain, flags, UROW * sizeof(unsigned), 1, no_style_at,
+                        [&](int i, const ChainLevel& lv, const WctFeatStats&) {
+                          const int l = lv.l, C = lv.C, w = lv.w, Nc = lv.h * lv.w;
+                          const int* Ns = &ns[(size_t)i * WCT_MIX_MAX];
+                          for (int f0 = 0; f0 < B;) {                  // a group: frames f0 .. f1 - 1, at most WCT_PLAN_PAIRS pairs
+                            const int* gnk = &nk[i * fstride + (size_t)f0 * WCT_MIX_MAX];
+                            int f1 = f0 + 1;
+                            while (f1 < B && wct_masked_batch_pairs(f1 + 1 - f0, gnk, K) <= 32) ++f1;
+                            const int G = f1 - f0;
+                            WctStyleSlots slots = {};
+                            int P = 0;
+                            for (int f = f0; f < f1; ++f)
+                              for (int k = 0; k < K; ++k)
+                                if (nk[i * fstride + (size_t)f * WCT_MIX_MAX + k] >= 2)
+                                  slots.state[P++] = states[i * fstride + (size_t)f * WCT_MIX_MAX + k];
+                            const MaskGeom g = {(const uint8_t*)c->mask_in.p + (size_t)f0 * Hc * Wc, Hc, Wc, w, 1 << (l - 1)};
+                            const float* fc = (const float*)c->feat_c.p + (size_t)f0 * Nc * C;
+                            half_t* o16 = (half_t*)c->wct_out.p + (size_t)f0 * Nc * C;
+                            const double rows = (double)G * Nc;
+                            // (the covariance stage is charged the compaction and gather as well; no style rows are read)
+                            const StageCost cost = {2.0 * C * C * rows, 6.0 * rows * C * 4, 2.0 * C * C * rows + 6.0 * C * C * C * P,
+                                                    rows * C * (4 + 2), 4.0 * rows * C * 4 + rows * C * 6};
+                            TRY(run_stages(c, wct_masked_batch_workspace_bytes(C, Nc, G, gnk, Ns, K), flags, cost, [&](int mode, int stages) {
+                              if (!stages)
+                                return launch_adain_masked_batch(fc, Nc, G, g, gnk, Ns, K, slots, C, alpha, 1e-5f, o16, nullptr, c->wct_ws.p,
+                                                                 c->wct_ws.cap, c->stream);
+                              return launch_wct_masked_batch(fc, Nc, G, g, gnk, Ns, K, slots, C, alpha, mode, -1.f, o16, nullptr, c->wct_ws.p,
+                                                             c->wct_ws.cap, stages, c->stream, c->eig_fail_dev);
+                            }));
+                            f0 = f1;
+                          }
+                          return (int)WCT_OK;
+                        }, out);
+}
+
+static int prepared_masked_flags_ok(unsigned flags) {
+  if (flags & WCT_FLAG_SWAP5) {
+    wct_set_error("mask: WCT_FLAG_SWAP5 needs the style's relu5_1 map and patches, which a handle does not hold (and style-swap is "
+                  "not a per-region affine map)");
+    return WCT_ERR_ARG;
+  }
+  if (flags & WCT_FLAG_STYLE_SHARED) { wct_set_error("mask: WCT_FLAG_STYLE_SHARED is for wct_stylize_batch_dev"); return WCT_ERR_ARG; }
+  return WCT_OK;
+}
+
+extern "C" int wct_stylize_prepared_masked_batch_dev(wct_ctx* c, const uint8_t* content, int Hc, int Wc, int B, const uint8_t* masks,
+                                                     const wct_style* const* styles, int K, const int* levels, int n_levels,
+                                                     float alpha, unsigned flags, uint8_t* out) {
+  ARG_CHECK(c && content && masks && styles && out && levels && n_levels >= 1 && n_levels <= 16 && B >= 1 && B <= 32 && Hc >= 2 && Wc >= 2);
+  TRY(prepared_masked_flags_ok(flags));
+  return stylize_prepared_masked_dev(c, content, Hc, Wc, B, masks, styles, K, levels, n_levels, alpha, flags, out);
+}
+
+// host content in, host frame out: the B = 1 case of the batch call
+extern "C" int wct_stylize_prepared_masked(wct_ctx* c, const uint8_t* content, int Hc, int Wc, const uint8_t* mask,
+                                           const wct_style* const* styles, int K, const int* levels, int n_levels, float alpha,
+                                           unsigned flags, uint8_t* out) {
+  ARG_CHECK(c && content && mask && styles && out && levels && n_levels >= 1 && n_levels <= 16 && Hc >= 2 && Wc >= 2);
+  TRY(prepared_masked_flags_ok(flags));
+  return host_frame(c, content, Hc, Wc, levels, n_levels, flags, out, [&](void* dc, uint8_t* frame) {
+    return stylize_prepared_masked_dev(c, dc, Hc, Wc, 1, mask, styles, K, levels, n_levels, alpha, flags, frame);
+  });
+}

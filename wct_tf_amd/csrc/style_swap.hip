@@ -3,7 +3,7 @@
 // ---------------------------------------------------------------------------
 // Style-swap at relu5_1 (ops.py:145-278, `--swap5`): whiten content and style, replace every
 // content patch by its best-correlated (un-normalised) style patch, colour with the style.
-// One content/style pair per call; the batch loop is in api.hip.
+// One content/style pair per call; the batch loop is in api_stylize.hip (stylize_levels).
 // ---------------------------------------------------------------------------
 // dst[m][(i*p + j)*C + c] = src[(y*st + i)][(x*st + j)][c],  m = y*wo + x   (tf.extract_image_patches, VALID)
 __global__ void im2col_kernel(const float* src, float* dst, int w, int C, int p, int st, int ho, int wo) {

@@ -304,7 +304,7 @@ int launch_adam(float* w, float* m, float* v, const float* g, size_t n, float lr
 // ---------------------------------------------------------------------------
 // weight re-layouts on the device (after every optimiser step)
 // ---------------------------------------------------------------------------
-// fp32 HWIO -> fp16 MFMA A-fragments [cout/32][tap][cin/16][lane][8]  (the layout of api.hip::pack_conv)
+// fp32 HWIO -> fp16 MFMA A-fragments [cout/32][tap][cin/16][lane][8]  (the layout of api_weights.hip::pack_conv)
 __global__ void pack_conv_frag_kernel(const float* w, half_t* frag, int cin, int cout) {
   const size_t total = (size_t)cout * 9 * cin;
   const int c16 = cin / 16;
@@ -319,7 +319,7 @@ __global__ void pack_conv_frag_kernel(const float* w, half_t* frag, int cin, int
   }
 }
 // fp32 HWIO -> the Winograd fragments of conv_wino.hip, [cout/32][f*3+kx][cin/16][lane][8] of U_f[kx] = sum_ky G[f][ky] g[ky][kx]
-// (api.hip::pack_conv computes the same values on the host: the sum in double, one rounding to fp16)
+// (api_weights.hip::pack_conv computes the same values on the host: the sum in double, one rounding to fp16)
 __global__ void pack_conv_wino_frag_kernel(const float* w, half_t* frag, int cin, int cout) {
   const size_t total = (size_t)cout * 12 * cin;
   const int c16 = cin / 16;

@@ -325,7 +325,7 @@ static int launch_blend_apply(const WctCarve& w, const float* content, int Nc, i
 }
 
 // ---------------------------------------------------------------------------
-// Prepared styles (wct_style, api.hip).  The colouring side of a level is content-independent up to the layout of its partial
+// Prepared styles (wct_style, api.h; the drivers in api_stylize.hip).  The colouring side of a level is content-independent up to the layout of its partial
 // sums: the colouring matrix Tcs [C][C] and the style mean [C] (WCT), the mean and the variance (AdaIN).  A STATE holds them --
 // [mean C][var C][Tcs C x C] floats -- for ONE layout and mode (WctStyleKey).  launch_style_state fills one from a style's features
 // with the content slot dead (WCT_SKIP_CONTENT): the statistics, covariance, eigensolve and spectral tail of launch_wct on

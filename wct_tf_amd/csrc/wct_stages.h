@@ -1,6 +1,6 @@
 // What the translation units of the whiten-colour transform share among themselves -- stats_gemm.hip (K3, the GEMM, K4),
 // eigh.hip (K5), spectral.hip (K6), wct.hip (K7, the carve, the plans, the transforms), mask.hip, style_swap.hip.  Private to
-// those units: api.hip sees common.h alone.  Every kernel lives in ONE unit, behind the launcher declared here.
+// those units: the api_*.hip units see common.h alone.  Every kernel lives in ONE unit, behind the launcher declared here.
 #pragma once
 #include "common.h"
 
@@ -10,7 +10,7 @@
 // A style mix (launch_wct_mix; shared_style == WCT_SKIP_MIX) is the mirror image: K styles share ONE content, matrix 0;
 // the content slots 2k of the pairs k >= 1 are skipped.
 constexpr int WCT_SKIP_MIX = 2;
-// Prepared styles (wct_style, api.hip): the style side of a call comes out of a handle's cached state, copied into the style
+// Prepared styles (wct_style, api.h): the style side of a call comes out of a handle's cached state, copied into the style
 // slots by style_load_kernel (wct.hip), so EVERY style matrix is dead -- WCT_SKIP_STYLE (P contents, one state in slot 1, read
 // like a shared style) and WCT_SKIP_MIX_STYLE (a mix of K states: matrix 0 alone is live).  WCT_SKIP_CONTENT is the mirror image
 // that fills a state: one style in slot 1, the content slot dead, no whitening side.
