@@ -342,6 +342,52 @@ int  wct_stylize_prepared_batch_dev_warm(wct_ctx* ctx, const uint8_t* content_de
 int  wct_transform_warm(wct_ctx* ctx, const float* content, int Nc, const float* style, int Ns, int C, float alpha,
                         unsigned flags, wct_warm* warm, int level, float* out, int* sweeps_out);
 
+/* ---- texture synthesis: seeded noise on the device, the passes chained there ------------------
+ * Li et al. 2017, sec. 4.3: a noise image goes through the multi-level pipeline a few times and comes out as a sample of the
+ * style's texture; other noise images give other samples, a style mix gives interpolated textures.  The reference ships it as
+ * webcam.py --noise (webcam.py:191-192: the frame is replaced by np.random.randint(0, 256, shape, np.uint8)) and as the
+ * commented-out recipe of stylize.py:95-97 (the same noise under gaussian_filter(sigma=0.5)).  Here the noise is a RULE, integers
+ * only, so that the device, a host program and NumPy agree bit for bit (all arithmetic mod 2^32):
+ *   fmix(h):  h ^= h >> 16;  h *= 0x85EBCA6B;  h ^= h >> 13;  h *= 0xC2B2AE35;  h ^= h >> 16      (murmur3's finaliser)
+ *   key = fmix(seed ^ (sample * 0x9E3779B9))          sample: the index of the image -- one independent image per sample
+ *   n   = (y * W + x) * 3 + ch                        the byte's index in its [H][W][3] image
+ *   raw = fmix(fmix(n ^ key) + key) >> 24             one uniform byte
+ * smooth = 0 (webcam.py:192) gives raw.  smooth != 0 is the recipe of stylize.py:95-97 restated in integers, over the two spatial
+ * axes only (the reference's call would also blur across R, G and B, an accident of handing it an [H][W][3] array): the 3-tap
+ * weights w = 27 202 27 (sigma = 0.5 to 8 bits; they sum to 256, the taps at +-2 round to 0) along y and along x,
+ *   out = (sum_dy sum_dx w[dy] w[dx] raw(sym(y + dy, H), sym(x + dx, W), ch) + 32768) >> 16,   sym(-1, n) = 0, sym(n, n) = n - 1
+ * (scipy's mode='reflect', NumPy's 'symmetric' -- not the tf.pad REFLECT of the convolutions).
+ * wct_texture_noise_batch_dev (webcam.py:191-192, stylize.py:95-97, Li et al. sec. 4.3): out_dev [B][H][W][3] uint8 on the device,
+ *   at any byte address; image b is sample first_sample + b; B = 1 .. 32; one launch, asynchronous on the ctx stream.
+ * wct_texture_noise (the same lines): one image into host memory, blocking.
+ * A null pointer, B outside 1 .. 32, H or W < 1, or B * H * W * 3 >= 2^31 bytes in one call (the kernel's indices are 32-bit: such
+ *   a call is refused, not wrapped) is WCT_STATUS_ARG and leaves the ctx usable. */
+int wct_texture_noise_batch_dev(wct_ctx* ctx, int H, int W, int B, unsigned seed, unsigned first_sample, int smooth,
+                                uint8_t* out_dev);
+int wct_texture_noise(wct_ctx* ctx, int H, int W, unsigned seed, unsigned sample, int smooth, uint8_t* out_host);
+/* wct_texture_size (webcam.py:191-192, stylize.py:95-97, Li et al. sec. 4.3): the frame size of a texture from H x W noise --
+ *   wct_output_size applied `passes` times (passes = 1 .. 16).  The first pass can grow the frame; later passes keep its size.
+ * wct_texture_prepared_batch_dev (the same lines; replaces the host loop "noise, then --passes predictions" of those recipes):
+ *   the noise of samples first_sample .. first_sample + B - 1 (B = 1 .. 32) is made in ctx scratch, then `passes` (1 .. 16) runs
+ *   of wct_stylize_prepared_batch_dev's body follow, each on the frames of the one before it; the frames between two passes live
+ *   in two ctx-owned uint8 buffers that alternate, and nothing goes to the host.  out_dev [B][Ho][Wo][3] (wct_texture_size)
+ *   holds the last pass.  Sample f equals `passes` chained wct_stylize_prepared_batch_dev calls on wct_texture_noise(.., sample
+ *   f), bit for bit, whatever B and first_sample it came with.  Asynchronous on the ctx stream: the style states of every
+ *   geometry the passes meet (at most two: the noise size and the size after pass 1) are asked for before the first launch, so
+ *   the call blocks only there, as the prepared calls do; WCT_STATUS_NOCONV surfaces as on wct_stylize_prepared_batch_dev.
+ * wct_texture_prepared (the same lines): the B = 1 case, the frame into host memory, blocking like wct_stylize_prepared.
+ * flags: WCT_FLAG_MODE_NP and WCT_FLAG_ADAIN.  WCT_STATUS_ARG: WCT_FLAG_SWAP5, WCT_FLAG_STYLE_SHARED, WCT_FLAG_IMAGES_F32,
+ *   WCT_FLAG_CONTENT_COLORS (there is no content whose colours could be kept), B outside 1 .. 32, passes outside 1 .. 16, H or W
+ *   below the minimum of the deepest level, a level outside the handle's set, a null pointer.  A handle that is not live in this
+ *   ctx is WCT_STATUS_STATE and never dereferenced.  A refusal leaves the ctx usable. */
+int wct_texture_size(int H, int W, const int* levels, int n_levels, int passes, int* Ho, int* Wo);
+int wct_texture_prepared_batch_dev(wct_ctx* ctx, int H, int W, int B, unsigned seed, unsigned first_sample, int smooth,
+                                   const wct_style* style, const int* levels, int n_levels, int passes, float alpha,
+                                   unsigned flags, uint8_t* out_dev);
+int wct_texture_prepared(wct_ctx* ctx, int H, int W, unsigned seed, unsigned sample, int smooth,
+                         const wct_style* style, const int* levels, int n_levels, int passes, float alpha,
+                         unsigned flags, uint8_t* out_host);
+
 /* ---- decoder training (model.py:123-223, train.py:129-196) ---------------------------
  * One optimiser step of the decoder for relu<level>_1 (the encoder is frozen, model.py:202):
  *   F = enc(x); D = dec(F); F' = enc(D);

@@ -74,6 +74,13 @@ SIGNATURES = [
     ('wct_stylize_prepared_warm', C.c_int, [_P, _U8, C.c_int, C.c_int, _P, _I, C.c_int, C.c_float, C.c_uint, _P, _U8]),
     ('wct_stylize_prepared_batch_dev_warm', C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _I, C.c_int, C.c_float, C.c_uint, _P, _P]),
     ('wct_transform_warm', C.c_int, [_P, _F, C.c_int, _F, C.c_int, C.c_int, C.c_float, C.c_uint, _P, C.c_int, _F, _I]),
+    ('wct_texture_noise_batch_dev', C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_uint, C.c_uint, C.c_int, _P]),
+    ('wct_texture_noise', C.c_int, [_P, C.c_int, C.c_int, C.c_uint, C.c_uint, C.c_int, _U8]),
+    ('wct_texture_size', C.c_int, [C.c_int, C.c_int, _I, C.c_int, C.c_int, _I, _I]),
+    ('wct_texture_prepared_batch_dev', C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_uint, C.c_uint, C.c_int, _P, _I, C.c_int, C.c_int,
+                                                 C.c_float, C.c_uint, _P]),
+    ('wct_texture_prepared', C.c_int, [_P, C.c_int, C.c_int, C.c_uint, C.c_uint, C.c_int, _P, _I, C.c_int, C.c_int, C.c_float,
+                                       C.c_uint, _U8]),
     ('wct_train_step', C.c_int, [_P, C.c_int, _F, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float,
                                  C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, _F]),
     ('wct_get_decoder_layer', C.c_int, [_P, C.c_int, C.c_int, _F, _F, _F, _F]),
@@ -108,6 +115,7 @@ class WCTNotConverged(WCTHipError):
 STATUS_NOCONV = -5
 MIX_MAX = 8                  # styles per mix (WCT_MIX_MAX)
 BATCH_MAX = 32               # frames per batch call
+PASSES_MAX = 16              # passes of one texture call (wct_texture_prepared*)
 
 
 def load():

@@ -57,6 +57,25 @@ def _color_images(stylized, content, ndim):
     return u8(s), u8(c)
 
 
+def check_texture(size, passes=1, batch=1, seed=0, first_sample=0):
+    """The refusals of a texture call, before any library call: a size (H, W) of two positive integers, 1 .. PASSES_MAX passes,
+    1 .. BATCH_MAX samples per call, seed and sample indices that are uint32.  -> (H, W)"""
+    try:
+        h, w = (int(v) for v in size)
+    except (TypeError, ValueError):
+        raise ValueError('a texture size is (H, W), got %r' % (size,))
+    if h < 1 or w < 1:
+        raise ValueError('an empty texture size %dx%d' % (h, w))
+    if not 1 <= int(passes) <= _lib.PASSES_MAX:
+        raise ValueError('a texture takes 1 .. %d passes, got %d' % (_lib.PASSES_MAX, passes))
+    if not 1 <= int(batch) <= _lib.BATCH_MAX:
+        raise ValueError('a batch takes 1 .. %d samples, got %d' % (_lib.BATCH_MAX, batch))
+    if not 0 <= int(seed) < 1 << 32 or not 0 <= int(first_sample) or not int(first_sample) + int(batch) <= 1 << 32:
+        raise ValueError('seed and sample indices are uint32, got seed %d, samples %d .. %d' %
+                         (seed, first_sample, int(first_sample) + int(batch) - 1))
+    return h, w
+
+
 def _image_arrays(images):
     """Pointers, heights and widths of K images as C arrays."""
     k = len(images)
@@ -489,6 +508,60 @@ class Context(object):
             raise ValueError('a batch takes 1 .. %d frames and as many contents, got %d and %d' % (_lib.BATCH_MAX, s.shape[0], c.shape[0]))
         return self._host_batch([s, c], np.empty_like(s), in_place=True, enqueue=lambda ds, dc: self.content_colors_batch_dev(
             ds, s.shape[1], s.shape[2], dc, c.shape[1], c.shape[2], s.shape[0], ds))
+
+    # ---- texture synthesis: seeded noise on the device, the passes chained there -----
+    def texture_noise(self, h, w, seed, sample=0, smooth=False):
+        """The noise image `sample` of `seed` (wct_texture_noise; the integer rule of include/wct_hip.h) -> uint8 [h][w][3].
+        smooth: the rule's 27 202 27 filter along y and x (stylize.py:95-97); off is webcam.py:192's plain noise."""
+        h, w = check_texture((h, w), seed=seed, first_sample=sample)
+        out = np.empty((h, w, 3), np.uint8)
+        check(self.lib.wct_texture_noise(self.h, h, w, int(seed), int(sample), int(bool(smooth)), out.ctypes.data_as(_lib._U8)))
+        return out
+
+    def texture_noise_batch_dev(self, h, w, batch, seed, first_sample, smooth, out_dev):
+        """`batch` noise images [batch][h][w][3] into device memory at any byte address (wct_texture_noise_batch_dev): image b is
+        sample first_sample + b.  One launch, asynchronous."""
+        h, w = check_texture((h, w), batch=batch, seed=seed, first_sample=first_sample)
+        check(self.lib.wct_texture_noise_batch_dev(self.h, h, w, int(batch), int(seed), int(first_sample), int(bool(smooth)), out_dev))
+
+    def texture_size(self, h, w, relu_targets, passes=1):
+        """The frame size of a texture from h x w noise after `passes` passes (wct_texture_size)."""
+        lv = _levels(relu_targets)
+        ho, wo = C.c_int(), C.c_int()
+        check(self.lib.wct_texture_size(int(h), int(w), (C.c_int * len(lv))(*lv), len(lv), int(passes), C.byref(ho), C.byref(wo)))
+        return ho.value, wo.value
+
+    def texture_prepared_batch_dev(self, h, w, batch, seed, first_sample, style, relu_targets, passes, alpha, out_dev, adain=False,
+                                   wct_mode='tf', smooth=False):
+        """Texture samples first_sample .. first_sample + batch - 1 of `seed` on a PreparedStyle, into device memory
+        [batch][Ho][Wo][3] (texture_size): the noise is made on the device and the `passes` passes feed each other there
+        (wct_texture_prepared_batch_dev).  Asynchronous."""
+        h, w = check_texture((h, w), passes, batch, seed, first_sample)
+        lv = check_prepared(self, [style], relu_targets)
+        check(self.lib.wct_texture_prepared_batch_dev(self.h, h, w, int(batch), int(seed), int(first_sample), int(bool(smooth)), style.h,
+                                                      (C.c_int * len(lv))(*lv), len(lv), int(passes), float(alpha),
+                                                      _flags(adain, wct_mode), out_dev))
+
+    def texture_prepared_batch(self, h, w, batch, seed, first_sample, style, relu_targets, passes=3, alpha=1.0, adain=False,
+                               wct_mode='tf', smooth=False):
+        """texture_prepared_batch_dev with the frames brought to the host -> uint8 [batch][Ho][Wo][3].  Sample f equals the noise
+        texture_noise(h, w, seed, first_sample + f) through `passes` chained stylize_prepared_batch calls, bit for bit."""
+        h, w = check_texture((h, w), passes, batch, seed, first_sample)
+        check_prepared(self, [style], relu_targets)
+        ho, wo = self.texture_size(h, w, relu_targets, passes)
+        out = np.empty((int(batch), ho, wo, 3), np.uint8)
+        return self._host_batch([], out, lambda do: self.texture_prepared_batch_dev(
+            h, w, batch, seed, first_sample, style, relu_targets, passes, alpha, do, adain=adain, wct_mode=wct_mode, smooth=smooth))
+
+    def texture_prepared(self, h, w, seed, sample, style, relu_targets, passes=3, alpha=1.0, adain=False, wct_mode='tf', smooth=False):
+        """One texture sample -> uint8 [Ho][Wo][3] (wct_texture_prepared, blocking): texture_prepared_batch with one sample."""
+        h, w = check_texture((h, w), passes, 1, seed, sample)
+        lv = check_prepared(self, [style], relu_targets)
+        ho, wo = self.texture_size(h, w, relu_targets, passes)
+        out = np.empty((ho, wo, 3), np.uint8)
+        check(self.lib.wct_texture_prepared(self.h, h, w, int(seed), int(sample), int(bool(smooth)), style.h, (C.c_int * len(lv))(*lv),
+                                            len(lv), int(passes), float(alpha), _flags(adain, wct_mode), out.ctypes.data_as(_lib._U8)))
+        return out
 
     # ---- the hot path ------------------------------------------------------
     def output_size(self, hc, wc, relu_targets):

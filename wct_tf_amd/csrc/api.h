@@ -95,6 +95,7 @@ struct wct_ctx {
   DevBuf usum_c, usum_s[6], umax;     // feature statistics from the tap epilogues (ConvArgs::usum / umax); umax: [7][32][UMAX_SLOTS] words
   DevBuf mix_in, feat_mix[6];      // a style mix: the K style inputs, and their features per level (K maps back to back)
   DevBuf mask_in;                  // spatial control: the label map (wct_stylize_masked) or the row labels (wct_*_masked)
+  DevBuf tex_noise, tex[2];        // texture synthesis: the noise images, and the uint8 frames between two passes (alternating)
   std::vector<wct_style*> styles;  // the live prepared styles of this context (wct_style_prepare .. wct_style_free)
   unsigned long long style_clock = 0;   // one tick per call that takes prepared styles
   std::vector<wct_warm*> warms;    // the live warm states of this context (wct_warm_create .. wct_warm_free)

@@ -467,3 +467,33 @@ extern "C" int wct_content_colors(wct_ctx* c, const uint8_t* stylized, int Ho, i
   TRY(wct_content_colors_batch_dev(c, (uint8_t*)ds, Ho, Wo, (uint8_t*)dc, Hc, Wc, 1, (uint8_t*)ds));    // (in place)
   return fetch(c, out, ds, (size_t)Ho * Wo * 3);
 }
+
+// Seeded noise images for texture synthesis, op level (csrc/noise.hip): the refusals both calls share
+static int texture_noise_checks(int H, int W, int B, const void* out) {
+  if (!out) { wct_set_error("texture noise: null output pointer"); return WCT_ERR_ARG; }
+  if (B < 1 || B > 32) { wct_set_error("texture noise: B = %d images, must be 1 .. 32", B); return WCT_ERR_ARG; }
+  if (H < 1 || W < 1) { wct_set_error("texture noise: an empty %dx%d image", H, W); return WCT_ERR_ARG; }
+  return WCT_OK;
+}
+
+extern "C" int wct_texture_noise_batch_dev(wct_ctx* c, int H, int W, int B, unsigned seed, unsigned first_sample, int smooth,
+                                           uint8_t* out) {
+  ARG_CHECK(c != nullptr);
+  TRY(texture_noise_checks(H, W, B, out));
+  HIP_TRY(hipSetDevice(c->device));
+  ProfScope ps(c, 7, 0, (double)B * H * W * 3);
+  return launch_texture_noise(out, B, H, W, seed, first_sample, smooth, c->stream);
+}
+
+extern "C" int wct_texture_noise(wct_ctx* c, int H, int W, unsigned seed, unsigned sample, int smooth, uint8_t* out) {
+  ARG_CHECK(c != nullptr);
+  TRY(texture_noise_checks(H, W, 1, out));
+  HIP_TRY(hipSetDevice(c->device));
+  if ((unsigned long long)H * (unsigned long long)W * 3ull >= (1ull << 31)) {              // (before the staging buffer is sized)
+    wct_set_error("texture noise: a %dx%dx3 image passes 2^31 bytes", H, W);
+    return WCT_ERR_ARG;
+  }
+  TRY(ensure(c, c->stage[0], (size_t)H * W * 3));
+  TRY(wct_texture_noise_batch_dev(c, H, W, 1, seed, sample, smooth, (uint8_t*)c->stage[0].p));
+  return fetch(c, out, c->stage[0].p, (size_t)H * W * 3);
+}

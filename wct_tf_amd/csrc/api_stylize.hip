@@ -548,6 +548,31 @@ static int content_prelude(wct_ctx* c, unsigned flags, const void* content, size
 // stylize_levels' style_at of a chain on handles: no style features (style-swap alone asks for them)
 static const float* no_style_at(int, int, int* hs, int* ws) { *hs = *ws = 0; return nullptr; }
 
+// The states of K live handles for every level of `chain`, stamped with the running call (c->style_clock; the missing ones are
+// computed, which blocks): style k serves the layout of (content, style k).  refs[i].state[k] is the state of level i, and
+// ns[i * WCT_MIX_MAX + k] the rows of style k's feature map there.
+static int chain_states(wct_ctx* c, const Chain& chain, const wct_style* const* styles, int K, int kind, std::vector<WctStyleRef>* refs,
+                        std::vector<int>* ns) {
+  const int n_levels = (int)chain.lv.size();
+  refs->assign(n_levels, WctStyleRef{});
+  ns->assign((size_t)n_levels * WCT_MIX_MAX, 0);
+  for (int k = 0; k < K; ++k) {
+    wct_style* st = const_cast<wct_style*>(styles[k]);
+    std::vector<StyleNeed> needs;
+    for (int i = 0; i < n_levels; ++i) {
+      const ChainLevel& g = chain.lv[i];
+      int hs, ws;
+      level_dims(st->Hs, st->Ws, g.l, &hs, &ws);
+      (*ns)[(size_t)i * WCT_MIX_MAX + k] = hs * ws;
+      needs.push_back(StyleNeed{g.l, wct_style_key(g.C, g.h * g.w, hs * ws)});
+    }
+    std::vector<const float*> bufs;
+    TRY(style_states(c, k, st, kind, needs, &bufs));
+    for (int i = 0; i < n_levels; ++i) (*refs)[i].state[k] = bufs[i];
+  }
+  return WCT_OK;
+}
+
 // The body of the wct_stylize_prepared* calls (their pointer and flag checks done): B contents [B][Hc][Wc][3] on the device, K
 // handles; lambda null: one style for all B (K = 1), else the mix weights of K styles (B = 1).  Asynchronous unless a handle
 // has to compute a state (style_fill), which happens before anything of the content chain is enqueued.
@@ -570,25 +595,11 @@ static int stylize_prepared_dev(wct_ctx* c, const void* content, int Hc, int Wc,
   Chain chain;
   TRY(chain_geometry(Hc, Wc, levels, n_levels, &chain));
 
-  // the states of every level, before any launch of the content chain: style k serves the layout of (content, style k)
-  const int kind = style_kind(flags);
+  // the states of every level, before any launch of the content chain
   ++c->style_clock;
-  std::vector<WctStyleRef> refs(n_levels);
-  std::vector<int> ns((size_t)n_levels * WCT_MIX_MAX);
-  for (int k = 0; k < K; ++k) {
-    wct_style* st = const_cast<wct_style*>(styles[k]);
-    std::vector<StyleNeed> needs;
-    for (int i = 0; i < n_levels; ++i) {
-      const ChainLevel& g = chain.lv[i];
-      int hs, ws;
-      level_dims(st->Hs, st->Ws, g.l, &hs, &ws);
-      ns[(size_t)i * WCT_MIX_MAX + k] = hs * ws;
-      needs.push_back(StyleNeed{g.l, wct_style_key(g.C, g.h * g.w, hs * ws)});
-    }
-    std::vector<const float*> bufs;
-    TRY(style_states(c, k, st, kind, needs, &bufs));
-    for (int i = 0; i < n_levels; ++i) refs[i].state[k] = bufs[i];
-  }
+  std::vector<WctStyleRef> refs;
+  std::vector<int> ns;
+  TRY(chain_states(c, chain, styles, K, style_kind(flags), &refs, &ns));
 
   const float* img_c;
   TRY(content_prelude(c, flags, content, (size_t)B * Hc * Wc * 3, &img_c));
@@ -655,6 +666,81 @@ extern "C" int wct_stylize_prepared_batch_dev_warm(wct_ctx* c, const uint8_t* co
   TRY(style_flags_ok(flags));
   TRY(warm_live(c, warm));
   return stylize_prepared_dev(c, content, Hc, Wc, B, &style, 1, nullptr, levels, n_levels, alpha, flags, out, warm);
+}
+
+// ---------------------------------------------------------------------------
+// texture synthesis (Li et al. 2017, sec. 4.3; webcam.py:191-192 --noise, stylize.py:95-97): seeded noise made on the device,
+// then `passes` runs of the prepared chain, each on the frames of the one before it
+// ---------------------------------------------------------------------------
+extern "C" int wct_texture_size(int H, int W, const int* levels, int n_levels, int passes, int* Ho, int* Wo) {
+  ARG_CHECK(Ho && Wo && passes >= 1 && passes <= 16);
+  for (int p = 0; p < passes; ++p) TRY(wct_output_size(H, W, levels, n_levels, &H, &W));
+  *Ho = H; *Wo = W;
+  return WCT_OK;
+}
+
+static int texture_flags_ok(unsigned flags) {
+  TRY(style_flags_ok(flags));
+  if (flags & WCT_FLAG_IMAGES_F32) { wct_set_error("texture: WCT_FLAG_IMAGES_F32 describes input images, and a texture has none"); return WCT_ERR_ARG; }
+  if (flags & WCT_FLAG_CONTENT_COLORS) { wct_set_error("texture: WCT_FLAG_CONTENT_COLORS needs a content whose colours could be kept"); return WCT_ERR_ARG; }
+  return WCT_OK;
+}
+
+extern "C" int wct_texture_prepared_batch_dev(wct_ctx* c, int H, int W, int B, unsigned seed, unsigned first_sample, int smooth,
+                                              const wct_style* style, const int* levels, int n_levels, int passes, float alpha,
+                                              unsigned flags, uint8_t* out) {
+  ARG_CHECK(c && out && levels && n_levels >= 1 && n_levels <= 16 && B >= 1 && B <= 32 && passes >= 1 && passes <= 16);
+  TRY(texture_flags_ok(flags));
+  HIP_TRY(hipSetDevice(c->device));
+  TRY(style_live(c, style));
+  TRY(check_levels(c, levels, n_levels, &style, 1));
+  const unsigned long long px = (unsigned long long)(H > 0 ? H : 0) * (unsigned long long)(W > 0 ? W : 0);
+  if (px >= (1ull << 31) || px * 3ull * B >= (1ull << 31)) {               // (launch_texture_noise's bound, before its buffer is sized)
+    wct_set_error("texture: the noise of %d images of %dx%dx3 passes 2^31 bytes in one call", B, H, W);
+    return WCT_ERR_ARG;
+  }
+  // the two geometries the passes meet: the noise size, and the frame size of pass 1, which every later pass keeps (the deepest
+  // level leaves a multiple of its stride, and no level changes such a size)
+  Chain first, rest;
+  TRY(chain_geometry(H, W, levels, n_levels, &first));
+  TRY(chain_geometry(first.Ho, first.Wo, levels, n_levels, &rest));
+  // their style states, before the first launch of the chain (one tick: neither geometry evicts the other's), and every buffer
+  // of the call's own -- what may block is over when the noise is enqueued
+  ++c->style_clock;
+  std::vector<WctStyleRef> refs;
+  std::vector<int> ns;
+  TRY(chain_states(c, first, &style, 1, style_kind(flags), &refs, &ns));
+  if (passes > 1) TRY(chain_states(c, rest, &style, 1, style_kind(flags), &refs, &ns));
+  const size_t frames = (size_t)B * first.Ho * first.Wo * 3;
+  TRY(ensure(c, c->tex_noise, (size_t)B * H * W * 3));
+  for (int i = 0; i < 2 && i < passes - 1; ++i) TRY(ensure(c, c->tex[i], frames));
+  {
+    ProfScope ps(c, 7, 0, (double)B * H * W * 3);
+    TRY(launch_texture_noise((uint8_t*)c->tex_noise.p, B, H, W, seed, first_sample, smooth, c->stream));
+  }
+  const uint8_t* in = (const uint8_t*)c->tex_noise.p;
+  for (int p = 0; p < passes; ++p) {
+    uint8_t* dst = p == passes - 1 ? out : (uint8_t*)c->tex[p & 1].p;
+    TRY(stylize_prepared_dev(c, in, p ? first.Ho : H, p ? first.Wo : W, B, &style, 1, nullptr, levels, n_levels, alpha, flags, dst));
+    in = dst;
+  }
+  return WCT_OK;
+}
+
+// host frame out: the B = 1 case of the batch call, blocking
+extern "C" int wct_texture_prepared(wct_ctx* c, int H, int W, unsigned seed, unsigned sample, int smooth, const wct_style* style,
+                                    const int* levels, int n_levels, int passes, float alpha, unsigned flags, uint8_t* out) {
+  ARG_CHECK(c && out && levels && n_levels >= 1 && n_levels <= 16 && passes >= 1 && passes <= 16);
+  TRY(texture_flags_ok(flags));
+  HIP_TRY(hipSetDevice(c->device));
+  TRY(eig_stale(c));
+  int Ho, Wo;
+  TRY(wct_texture_size(H, W, levels, n_levels, passes, &Ho, &Wo));
+  TRY(ensure(c, c->stage[2], (size_t)Ho * Wo * 3));
+  TRY(wct_texture_prepared_batch_dev(c, H, W, 1, seed, sample, smooth, style, levels, n_levels, passes, alpha, flags,
+                                     (uint8_t*)c->stage[2].p));
+  TRY(fetch(c, out, c->stage[2].p, (size_t)Ho * Wo * 3));
+  return eig_status(c);
 }
 
 // Spatial control of B frames on prepared styles: one label map per frame (on the HOST: every level's labels are counted here,

@@ -326,3 +326,8 @@ int launch_content_colors_f32(const float* frame, const void* content, int conte
                               uint8_t* out, hipStream_t s);
 int launch_content_colors_u8(const uint8_t* stylized, const uint8_t* content, int B, int Ho, int Wo, int Hc, int Wc, uint8_t* out,
                              hipStream_t s);
+
+// ---- noise.hip ------------------------------------------------------------
+// Seeded noise for texture synthesis (noise_rule.h): out [B][H][W][3] uint8 on the device, image b = sample first_sample + b of
+// `seed`; smooth: the rule's 27 202 27 filter along y and x.  One launch; any base address; B * H * W * 3 >= 2^31 is WCT_ERR_ARG.
+int launch_texture_noise(uint8_t* out, int B, int H, int W, unsigned seed, unsigned first_sample, int smooth, hipStream_t s);

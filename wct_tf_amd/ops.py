@@ -8,6 +8,7 @@ on libwct_hip.so.  Same names, argument meaning and array conventions:
   preserve_colors_np(style_rgb, content_rgb)    utils.py:87
 and, without a counterpart in the reference,
   content_colors_np(stylized_rgb, content_rgb)  luminance-only colour preservation (Gatys et al. 2016), applied to a result
+  texture_noise_np(h, w, seed, sample=0, smooth=False)   the seeded noise image a texture starts from (webcam.py:191-192 --noise)
 """
 import numpy as np
 
@@ -120,3 +121,12 @@ def content_colors_np(stylized_rgb, content_rgb, ctx=None):
     recolours the RESULT, so the style side does not depend on the content."""
     ctx = ctx or default_context()
     return ctx.content_colors(stylized_rgb, content_rgb)
+
+
+def texture_noise_np(h, w, seed, sample=0, smooth=False, ctx=None):
+    """The noise image that texture synthesis starts from (Li et al. 2017, sec. 4.3) -> uint8 [h][w][3].  The reference draws it
+    with `np.random.randint(0, 256, shape, np.uint8)` (webcam.py:191-192); here it is the seeded integer rule of include/wct_hip.h
+    (wct_texture_noise), made on the device: the same (seed, sample) gives the same bytes anywhere, and every sample of a seed is
+    an independent image.  smooth: the 27 202 27 filter along y and x, the gaussian_filter(sigma=0.5) of stylize.py:95-97."""
+    ctx = ctx or default_context()
+    return ctx.texture_noise(h, w, seed, sample, smooth)

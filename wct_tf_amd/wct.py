@@ -6,6 +6,7 @@
     WCT.predict_masked(content, styles, mask, alpha=1, adain=False, swap5=False, ss_alpha=1) -> uint8 HxWx3
     WCT.prepare_style(style) -> PreparedStyle, which predict / predict_frames / predict_mix take in the place of a style image
     every predict* takes content_colors=True: the frame keeps its luminance and takes the colours of its content
+    WCT.synthesize(style, size, seeds=1, seed=0, passes=3) -> uint8 [n][Ho][Wo][3], textures of the style from seeded noise
 
 `checkpoints` / `vgg_path`: the reference restores TF checkpoints and a .t7 file
 (wct.py:46-58, vgg_normalised.py:16).  Per decoder this class takes either of
@@ -20,7 +21,7 @@ import re
 
 import numpy as np
 
-from .context import Context, PreparedStyle, check_prepared, check_warm, split_styles
+from .context import Context, PreparedStyle, check_prepared, check_texture, check_warm, split_styles
 from .model import WCTModel
 from .weights import load_weights
 
@@ -30,6 +31,38 @@ def _device_index(device):
         return device
     m = re.search(r'(\d+)\s*$', str(device))        # '/gpu:0' -> 0
     return int(m.group(1)) if m else 0
+
+
+def texture_plan(style, size, seeds=1, seed=0, passes=3, batch=16, weights=None, swap5=False):
+    """The arguments of WCT.synthesize, checked without a GPU (ValueError): -> (h, w, samples, runs, batch).  `samples` are the
+    sample indices in the order asked for; `runs` cuts them into (first_sample, count) pieces of consecutive indices, at most
+    `batch` (clamped to 1 .. 32) each -- one device call per piece."""
+    if swap5:
+        raise ValueError('a texture takes no swap5: style-swap matches patches of a content, and noise has none worth matching')
+    mix = isinstance(style, (list, tuple))
+    if weights is not None and not mix:
+        raise ValueError('weights go with a list of styles (texture interpolation), got one style')
+    if mix:
+        from ._lib import mix_weights
+        mix_weights(weights, len(style))
+    batch = max(1, min(32, int(batch)))
+    if isinstance(seeds, (int, np.integer)):
+        if seeds < 1:
+            raise ValueError('seeds is a count >= 1 or a list of sample indices, got %d' % seeds)
+        samples = list(range(int(seeds)))
+    else:
+        samples = [int(v) for v in seeds]
+        if not samples:
+            raise ValueError('an empty list of sample indices')
+    h, w = check_texture(size, passes, 1, seed, min(samples))
+    check_texture(size, passes, 1, seed, max(samples))
+    runs = []
+    for v in samples:
+        if runs and runs[-1][0] + runs[-1][1] == v and runs[-1][1] < batch:
+            runs[-1][1] += 1
+        else:
+            runs.append([v, 1])
+    return h, w, samples, [tuple(r) for r in runs], batch
 
 
 class WCT(object):
@@ -254,3 +287,47 @@ class WCT(object):
                                         wct_mode=self.wct_mode, swap5=bool(swap5), content_colors=content_colors)
                 for i in range(0, len(frames), batch)]
         return np.concatenate(outs, axis=0)
+
+    def synthesize(self, style, size, seeds=1, seed=0, passes=3, alpha=1, adain=False, smooth=False, batch=16, weights=None,
+                   swap5=False):
+        '''Texture synthesis (Li et al. 2017, sec. 4.3; the reference's webcam.py --noise and the recipe of stylize.py:95-97): seeded
+           noise images of `size` (H, W) go through the pipeline `passes` times and come out as samples of the style's texture.
+           `style` is an image (array in [0,255]: prepared here and closed afterwards) or a PreparedStyle.  `seeds` is a count n
+           -- samples 0 .. n-1 of `seed` -- or a list of sample indices; every (seed, sample) is its own noise image
+           (ops.texture_noise_np gives it), so a sample does not depend on which others were asked for with it.  `smooth`: the
+           noise under the 27 202 27 filter of stylize.py:95-97.  Returns uint8 [n][Ho][Wo][3]; the first pass can grow the frame
+           (Context.texture_size).  The noise is made on the device and the passes feed each other there, for up to `batch`
+           (<= 32) consecutive sample indices per call; each sample equals predict_frames repeated `passes` times on its noise,
+           bit for bit.
+           Texture interpolation (Fig. 9 of the paper): `style` is a LIST of images or of PreparedStyle objects and `weights` the
+           mix weights (None: equal).  Each sample then takes its noise from texture_noise_np and `passes` x predict_mix on the
+           handles -- one sample at a time, through the host between passes, because the mix path is single-frame.  Batched
+           mixes, masks and warm states are not part of this call.'''
+        h, w, samples, runs, batch = texture_plan(style, size, seeds, seed, passes, batch, weights, swap5)   # ValueError, no GPU call
+        if isinstance(style, (list, tuple)):
+            from .ops import texture_noise_np
+            handles, images = split_styles(list(style))
+            if handles:
+                check_prepared(self.sess, handles, self.relu_targets)
+            own = [] if handles else [self.prepare_style(np.asarray(s), adain=adain) for s in images]
+            try:
+                outs = []
+                for v in samples:
+                    img = texture_noise_np(h, w, seed, v, smooth, ctx=self.sess)
+                    for _ in range(passes):
+                        img = self.predict_mix(img, handles or own, weights, alpha=alpha, adain=adain)
+                    outs.append(img)
+                return np.stack(outs)
+            finally:
+                for hd in own:
+                    hd.close()
+        if isinstance(style, PreparedStyle):
+            check_prepared(self.sess, [style], self.relu_targets)
+        handle = style if isinstance(style, PreparedStyle) else self.prepare_style(np.asarray(style), adain=adain)
+        try:
+            return np.concatenate([self.sess.texture_prepared_batch(h, w, n, seed, first, handle, self.relu_targets, passes=passes,
+                                                                    alpha=alpha, adain=adain, wct_mode=self.wct_mode, smooth=smooth)
+                                   for first, n in runs], axis=0)
+        finally:
+            if handle is not style:
+                handle.close()
