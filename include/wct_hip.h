@@ -388,6 +388,62 @@ int wct_texture_prepared(wct_ctx* ctx, int H, int W, unsigned seed, unsigned sam
                          const wct_style* style, const int* levels, int n_levels, int passes, float alpha,
                          unsigned flags, uint8_t* out_host);
 
+/* ---- banded stylization: contents past the limits of one launch ---------------------------
+ * predict() runs every layer over the whole image (wct.py:70-106, model.py:77-101), and so do the calls above: each layer is one
+ * launch, and the kernels address one image's activations with 32-bit byte offsets.  A content whose largest map passes 2^31
+ * bytes is WCT_STATUS_ARG there: H W >= 2^31 / 256 = 8 388 608 pixels with relu1_1 among the levels (its fp32 tap), 16.7 MP
+ * without (the 64-channel fp16 maps).  The calls below run such a content in pieces on the same kernels, exactly:
+ *   bands:  band k owns the image rows [k band_rows, (k + 1) band_rows) of a level's input (band_rows a multiple of 16).  The
+ *     encoder runs on the band and a halo of real rows (16, 16, 16, 48, 96 image rows for relu1_1 .. relu5_1: what the layer
+ *     list needs, rounded up to 16), the decoder on the band's feature rows and 2, 2, 3, 4, 5 feature rows on either side (its
+ *     first row moved down to an even one); an edge that is the image's gets the image's own reflect pad.  The interiors are
+ *     copied into the full map, so every value has the operands, in the order, of the whole pass: the same bits.
+ *   chunks: the transform's content side needs a mean and a covariance, which pool exactly over chunks of whole feature rows:
+ *     N = sum n_k, m = sum n_k m_k / N, Cov = [sum (n_k - 1) S_k + sum n_k (m_k - m)(m_k - m)^T] / (N - 1), in double, in chunk
+ *     order, rounded to fp32 once, wct_tf's diagonal eps added after it (csrc/pool_rule.h).  The eigensolve, the colouring and
+ *     the blend run once on the pooled statistics; the apply runs per chunk with the fp16 scale that covers every chunk.
+ *     stat_rows = 0: the fewest equal chunks that fit -- ONE when the map fits, and one chunk is the whole-image transform
+ *     itself, bit for bit; stat_rows > 0: that many feature rows per chunk.  The chunks depend on the map and stat_rows alone,
+ *     never on band_rows, so frames do not depend on band_rows.  At most 4096 chunks per map.
+ * wct_band_rows (reference: none; wct.py:70-106 has no size limit of its own): *band_rows = 0 when the whole-image calls take
+ *   this content with these levels, else the automatic band height -- the largest multiple of 16 up to 2048 at which every band
+ *   of every level fits.  Too wide for a band of 16 rows: WCT_STATUS_ARG, the width limit in the message.  Pure host code.
+ * wct_band_plan (the same lines): the bands of ONE level on an H x W input, band k in rows[6 k ..]: the encoder span [0], [1]
+ *   and the interior [2], [3] in image rows, the decoder span [4], [5] in feature rows; the band's interior feature rows are
+ *   [rows[2] / s, rows[3] / s), s = 2^(level - 1), the last band's running to the map's end.  band_rows = 0: the automatic
+ *   height (one band when the whole-image call runs).  *n_bands is always set; more than max_bands is WCT_STATUS_ARG unless
+ *   max_bands = 0 (a query of the count).  Pure host code.
+ * wct_encode_banded / wct_decode_banded (model.py:135-139 / model.py:245-304): the banded twins of wct_encode / wct_decode --
+ *   host pointers, blocking; equal to the twin bit for bit wherever it runs, and running beyond its limit.  band_rows = 0:
+ *   automatic.  Like wct_mask_compact they are checks of the stylize call's stages, not calls to build on.
+ * wct_transform_chunked (ops.py:24-140): wct_transform with the content statistics pooled over chunks of chunk_rows rows (a
+ *   single left-over row joins the chunk before it; chunk_rows = 1 is WCT_STATUS_ARG).  chunk_rows = 0 or >= Nc: one chunk,
+ *   wct_transform's output bit for bit.  Groups of 32 chunks share the launches' workspace; any number up to 4096 works.
+ * wct_stylize_prepared_banded_dev (wct.py:70-106): one content [Hc][Wc][3] on the device on a prepared style, the frame
+ *   [Ho][Wo][3] (wct_output_size) on the device; asynchronous the way wct_stylize_prepared_batch_dev is (a call that computes a
+ *   new state or grows a buffer blocks while it does), WCT_STATUS_NOCONV surfacing as there.  band_rows = 0: automatic (one band
+ *   per level when the whole-image call runs).  With stat_rows = 0 and maps that fit, the frame is wct_stylize_prepared's bit
+ *   for bit.  wct_stylize_prepared_banded: host pointers, blocking, like wct_stylize_prepared.
+ *   The style state is the handle's under the key of the WHOLE map -- the layout of (h w content rows, the style's rows), the
+ *   key the whole-image call uses --, whatever the chunks.
+ *   flags: WCT_FLAG_MODE_NP, WCT_FLAG_IMAGES_F32, WCT_FLAG_CONTENT_COLORS (its launch indexes with size_t: any frame size).
+ *   WCT_STATUS_ARG: WCT_FLAG_ADAIN, WCT_FLAG_SWAP5, WCT_FLAG_STYLE_SHARED, a band_rows that is not a multiple of 16 or whose
+ *   bands pass the launch limit, a stat_rows whose chunks do, a level outside the handle's set.  A handle that is not live is
+ *   WCT_STATUS_STATE, a failed allocation WCT_STATUS_NOMEM.  A refusal leaves the ctx usable.
+ * Out of scope: AdaIN, style-swap, style mixes, masks, warm states and batches on large contents; and large STYLE images --
+ *   wct_style_prepare keeps its limit (the same pooling would serve it). */
+int wct_band_rows(int Hc, int Wc, const int* levels, int n_levels, int* band_rows);
+int wct_band_plan(int H, int W, int level, int band_rows, int max_bands, int* n_bands, int* rows /* [max_bands][6] */);
+int wct_encode_banded(wct_ctx* ctx, const float* img01, int H, int W, int level, int band_rows, float* feat);
+int wct_decode_banded(wct_ctx* ctx, const float* feat, int h, int w, int level, int band_rows, float* img);
+int wct_transform_chunked(wct_ctx* ctx, const float* content, int Nc, const float* style, int Ns, int C, float alpha, int mode,
+                          float eps, int chunk_rows, float* out, int* sweeps_out);
+int wct_stylize_prepared_banded_dev(wct_ctx* ctx, const uint8_t* content_dev, int Hc, int Wc, const wct_style* style,
+                                    const int* levels, int n_levels, float alpha, unsigned flags, int band_rows, int stat_rows,
+                                    uint8_t* out_dev);
+int wct_stylize_prepared_banded(wct_ctx* ctx, const uint8_t* content, int Hc, int Wc, const wct_style* style, const int* levels,
+                                int n_levels, float alpha, unsigned flags, int band_rows, int stat_rows, uint8_t* out);
+
 /* ---- decoder training (model.py:123-223, train.py:129-196) ---------------------------
  * One optimiser step of the decoder for relu<level>_1 (the encoder is frozen, model.py:202):
  *   F = enc(x); D = dec(F); F' = enc(D);

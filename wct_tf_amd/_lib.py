@@ -81,6 +81,13 @@ SIGNATURES = [
                                                  C.c_float, C.c_uint, _P]),
     ('wct_texture_prepared', C.c_int, [_P, C.c_int, C.c_int, C.c_uint, C.c_uint, C.c_int, _P, _I, C.c_int, C.c_int, C.c_float,
                                        C.c_uint, _U8]),
+    ('wct_band_rows', C.c_int, [C.c_int, C.c_int, _I, C.c_int, _I]),
+    ('wct_band_plan', C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _I, _I]),
+    ('wct_encode_banded', C.c_int, [_P, _F, C.c_int, C.c_int, C.c_int, C.c_int, _F]),
+    ('wct_decode_banded', C.c_int, [_P, _F, C.c_int, C.c_int, C.c_int, C.c_int, _F]),
+    ('wct_transform_chunked', C.c_int, [_P, _F, C.c_int, _F, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float, C.c_int, _F, _I]),
+    ('wct_stylize_prepared_banded_dev', C.c_int, [_P, _P, C.c_int, C.c_int, _P, _I, C.c_int, C.c_float, C.c_uint, C.c_int, C.c_int, _P]),
+    ('wct_stylize_prepared_banded', C.c_int, [_P, _U8, C.c_int, C.c_int, _P, _I, C.c_int, C.c_float, C.c_uint, C.c_int, C.c_int, _U8]),
     ('wct_train_step', C.c_int, [_P, C.c_int, _F, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float,
                                  C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, _F]),
     ('wct_get_decoder_layer', C.c_int, [_P, C.c_int, C.c_int, _F, _F, _F, _F]),

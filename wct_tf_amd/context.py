@@ -216,6 +216,36 @@ def check_warm(ctx, warm, relu_targets, adain=False, swap5=False, level_set=True
         raise TypeError('the warm state holds %s, not a wct_warm pointer' % type(warm.h).__name__)
 
 
+def check_band_rows(band_rows):
+    """band_rows as the banded calls take it: an int, 0 (automatic) or a positive multiple of 16 -- checked before any GPU call"""
+    if isinstance(band_rows, bool) or not isinstance(band_rows, (int, np.integer)):
+        raise ValueError('band_rows must be an int, got %r' % (band_rows,))
+    if band_rows < 0 or band_rows % 16:
+        raise ValueError('band_rows must be 0 (automatic) or a positive multiple of 16, got %d' % band_rows)
+    return int(band_rows)
+
+
+def band_rows(hc, wc, relu_targets):
+    """wct_band_rows: 0 when the whole-image calls take an hc x wc content with the levels `relu_targets`, else the automatic
+    band height of the banded call.  Host code only: no context, no GPU."""
+    lv = _levels(relu_targets)
+    out = C.c_int()
+    check(_lib.load().wct_band_rows(int(hc), int(wc), (C.c_int * len(lv))(*lv), len(lv), C.byref(out)))
+    return out.value
+
+
+def band_plan(h, w, relu_target, band_rows=0):
+    """wct_band_plan: the bands of one level on an h x w input as an int array [n_bands][6] -- the encoder span and the interior
+    in image rows, the decoder span in feature rows.  Host code only."""
+    level = _levels([relu_target])[0]
+    lib = _lib.load()
+    n = C.c_int()
+    check(lib.wct_band_plan(int(h), int(w), level, int(band_rows), 0, C.byref(n), None))
+    rows = np.zeros((n.value, 6), np.int32)
+    check(lib.wct_band_plan(int(h), int(w), level, int(band_rows), n.value, C.byref(n), rows.ctypes.data_as(_lib._I)))
+    return rows
+
+
 def split_styles(styles):
     """(handles, images) of a list of styles: one of the two is empty, a list that mixes PreparedStyle objects and images is a
     ValueError."""
@@ -467,6 +497,42 @@ class Context(object):
         check(self.lib.wct_decode(self.h, fptr(f), h, w, level, fptr(img)))
         return img
 
+    def encode_banded(self, img01, relu_target, band_rows=0):
+        """encode() band by band (wct_encode_banded; band_rows 0: automatic): the same map, bit for bit, and maps past its limit"""
+        level = _levels([relu_target])[0]
+        x = f32(img01)
+        h, w, _ = x.shape
+        hh, ww = h, w
+        for _ in range(level - 1):
+            hh, ww = (hh + 1) // 2, (ww + 1) // 2
+        feat = np.empty((hh, ww, _LEVEL_C[level]), np.float32)
+        check(self.lib.wct_encode_banded(self.h, fptr(x), h, w, level, int(band_rows), fptr(feat)))
+        return feat
+
+    def decode_banded(self, feat, relu_target, band_rows=0):
+        """decode() band by band (wct_decode_banded; band_rows 0: automatic): the same image, bit for bit"""
+        level = _levels([relu_target])[0]
+        f = f32(feat)
+        h, w, _ = f.shape
+        s = 1 << (level - 1)
+        img = np.empty((h * s, w * s, 3), np.float32)
+        check(self.lib.wct_decode_banded(self.h, fptr(f), h, w, level, int(band_rows), fptr(img)))
+        return img
+
+    def transform_chunked(self, content, style, alpha, mode, chunk_rows, eps=-1.0, return_sweeps=False):
+        """transform() with the content statistics pooled over chunks of chunk_rows rows (wct_transform_chunked); 0, or at
+        least the content's rows: one chunk, transform()'s output bit for bit"""
+        c = f32(content)
+        s = f32(style)
+        if c.ndim != 2 or s.ndim != 2 or c.shape[1] != s.shape[1]:
+            raise ValueError('expected [N][C] feature matrices with equal C')
+        out = np.empty_like(c)
+        sweeps = (C.c_int * 2)()
+        self.last_sweeps = sweeps
+        check(self.lib.wct_transform_chunked(self.h, fptr(c), c.shape[0], fptr(s), s.shape[0], c.shape[1], float(alpha), int(mode),
+                                             float(eps), int(chunk_rows), fptr(out), sweeps))
+        return (out, list(sweeps)) if return_sweeps else out
+
     def coral_stats(self, img_u8):
         a = u8(img_u8)
         sums = (C.c_double * 9)()
@@ -649,6 +715,28 @@ class Context(object):
             return out
         check(self.lib.wct_stylize_prepared(self.h, c.ctypes.data_as(_lib._U8), c.shape[0], c.shape[1], style.h, arr, len(arr),
                                             float(alpha), flags, out.ctypes.data_as(_lib._U8)))
+        return out
+
+    def band_rows(self, hc, wc, relu_targets):
+        """0 when the whole-image calls take an hc x wc content with these levels, else the automatic band height (band_rows)"""
+        return band_rows(hc, wc, relu_targets)
+
+    def band_plan(self, h, w, relu_target, band_rows=0):
+        """The bands of one level on an h x w input (band_plan)"""
+        return band_plan(h, w, relu_target, band_rows)
+
+    def stylize_prepared_banded(self, content, style, relu_targets, alpha=1.0, wct_mode='tf', band_rows=0, stat_rows=0,
+                                content_colors=False):
+        """stylize_prepared() in bands of band_rows image rows (a multiple of 16; 0: automatic) with the content statistics
+        pooled over chunks of stat_rows feature rows (0: the fewest that fit): contents of any size.  Where stylize_prepared()
+        runs, stat_rows = 0 gives its frame bit for bit.  WCT only: no AdaIN, warm state, mix or mask."""
+        check_prepared(self, [style], relu_targets)
+        check_band_rows(band_rows)
+        if int(stat_rows) < 0:
+            raise ValueError('stat_rows must be >= 0, got %r' % (stat_rows,))
+        c, arr, out, flags = self._prepared_args(content, relu_targets, False, wct_mode, content_colors)
+        check(self.lib.wct_stylize_prepared_banded(self.h, c.ctypes.data_as(_lib._U8), c.shape[0], c.shape[1], style.h, arr, len(arr),
+                                                   float(alpha), flags, int(band_rows), int(stat_rows), out.ctypes.data_as(_lib._U8)))
         return out
 
     def stylize_prepared_mix(self, content, styles, weights, relu_targets, alpha=1.0, adain=False, wct_mode='tf', content_colors=False):

@@ -96,6 +96,8 @@ struct wct_ctx {
   DevBuf mix_in, feat_mix[6];      // a style mix: the K style inputs, and their features per level (K maps back to back)
   DevBuf mask_in;                  // spatial control: the label map (wct_stylize_masked) or the row labels (wct_*_masked)
   DevBuf tex_noise, tex[2];        // texture synthesis: the noise images, and the uint8 frames between two passes (alternating)
+  DevBuf band_f, band_g, band_img; // banded stylization: a level's full fp32 feature map and its fp16 transform (either may pass
+                                   // 2^31 bytes: every launch sees a slice), and the decoded image of one band with its halo
   std::vector<wct_style*> styles;  // the live prepared styles of this context (wct_style_prepare .. wct_style_free)
   unsigned long long style_clock = 0;   // one tick per call that takes prepared styles
   std::vector<wct_warm*> warms;    // the live warm states of this context (wct_warm_create .. wct_warm_free)
@@ -208,6 +210,20 @@ int mask_check(const uint8_t* labels, size_t n, int K);
 void mask_counts(const uint8_t* mask, int Hm, int Wm, int h, int w, int stride, int K, int* nk);
 int run_transform_masked(wct_ctx* c, const float* fc, int Nc, const MaskGeom& g, const int* nk, const float* const* fs, const int* Ns,
                          int K, int C, float alpha, unsigned flags, float eps, half_t* out16, float* out32, int* sweeps_dev);
+
+// ---- banded.hip (B = 1: a level in bands of rows and chunks of feature rows, every launch inside the 2^31-byte limits) ----
+// the automatic band height of a chain (0: the whole-image call takes every level of it); a caller's band height checked
+int band_rows_for(const Chain& chain, int* band_rows);
+int band_rows_check(const Chain& chain, int band_rows);
+// run_encoder to relu<level>_1 of img [H][W][3] band by band into the full map F [h][w][C] fp32; run_decoder of the full map
+// G [h][w][C] fp16 band by band into img_out [h << (l - 1)][w << (l - 1)][3]: the whole pass's bits
+int run_encoder_banded(wct_ctx* c, const float* img, int H, int W, int clamp01, int level, int band_rows, float* F);
+int run_decoder_banded(wct_ctx* c, int level, const half_t* G, int h, int w, int band_rows, float* img_out);
+// the chunks of an h x w map (rows: feature rows per chunk, K: how many), and run_transform over K chunks of n_full rows of
+// fc [Nc][C] (the last chunk: what is left) with the content statistics pooled; K = 1 is run_transform itself
+int chunk_rule(int h, int w, int C, int stat_rows, int* rows, int* K);
+int run_transform_chunked(wct_ctx* c, const float* fc, size_t Nc, int n_full, int K, const float* fs, int Ns, int C, float alpha,
+                          unsigned flags, float eps, half_t* out16, float* out32, int* sweeps_dev, const WctStyleRef* prep = nullptr);
 
 // ---- api_stylize.hip ------------------------------------------------------
 int warm_live(const wct_ctx* c, const wct_warm* wm);     // WCT_ERR_STATE unless wm is a live warm state of c

@@ -32,6 +32,30 @@ extern "C" int wct_transform(wct_ctx* c, const float* content, int Nc, const flo
   return transform_pair(c, content, Nc, style, Ns, C, alpha, mode == WCT_NP ? WCT_FLAG_MODE_NP : 0, eps, nullptr, 0, out, sweeps_out);
 }
 
+// wct_transform with the content statistics pooled over chunks of chunk_rows rows (the last chunk: what is left, a single
+// left-over row joins the chunk before it); one chunk is wct_transform itself
+extern "C" int wct_transform_chunked(wct_ctx* c, const float* content, int Nc, const float* style, int Ns, int C, float alpha, int mode,
+                                     float eps, int chunk_rows, float* out, int* sweeps_out) {
+  ARG_CHECK(c && content && style && out && (mode == WCT_NP || mode == WCT_TF) && chunk_rows >= 0 && Nc >= 2);
+  const unsigned flags = mode == WCT_NP ? WCT_FLAG_MODE_NP : 0;
+  if (chunk_rows == 0 || chunk_rows >= Nc) return transform_pair(c, content, Nc, style, Ns, C, alpha, flags, eps, nullptr, 0, out, sweeps_out);
+  if (chunk_rows < 2) { wct_set_error("chunk_rows = %d: a chunk needs at least 2 rows for a covariance", chunk_rows); return WCT_ERR_ARG; }
+  int K = (Nc + chunk_rows - 1) / chunk_rows;
+  if (Nc - (K - 1) * chunk_rows < 2) --K;
+  HIP_TRY(hipSetDevice(c->device));
+  TRY(eig_stale(c));
+  void *dc, *ds;
+  TRY(stage_in(c, 0, content, (size_t)Nc * C * 4, &dc));
+  TRY(stage_in(c, 1, style, (size_t)Ns * C * 4, &ds));
+  TRY(ensure(c, c->stage[2], (size_t)Nc * C * 4));
+  TRY(ensure(c, c->stage[3], 256));
+  TRY(run_transform_chunked(c, (float*)dc, (size_t)Nc, chunk_rows, K, (float*)ds, Ns, C, alpha, flags, eps, nullptr, (float*)c->stage[2].p,
+                            (int*)c->stage[3].p));
+  TRY(fetch(c, out, c->stage[2].p, (size_t)Nc * C * 4));
+  if (sweeps_out) TRY(fetch(c, sweeps_out, c->stage[3].p, 2 * sizeof(int)));
+  return eig_status(c);
+}
+
 // the warm twin of wct_transform: the content solve started from the state's basis of `level`
 extern "C" int wct_transform_warm(wct_ctx* c, const float* content, int Nc, const float* style, int Ns, int C, float alpha,
                                   unsigned flags, wct_warm* warm, int level, float* out, int* sweeps_out) {
@@ -395,6 +419,46 @@ extern "C" int wct_decode(wct_ctx* c, const float* feat, int h, int w, int level
   const size_t ib = (size_t)h * scale * w * scale * 3 * 4;
   TRY(ensure(c, c->img_t[0], ib));
   TRY(run_decoder(c, level, (half_t*)c->wct_out.p, 1, h, w, (float*)c->img_t[0].p));
+  return fetch(c, img, c->img_t[0].p, ib);
+}
+
+// The band height of a banded twin: the caller's, checked, or (0) the automatic one -- one band where the whole-image call runs
+static int twin_band_rows(int H, int W, int level, int* band_rows) {
+  Chain chain;
+  TRY(chain_geometry(H, W, &level, 1, &chain));
+  if (*band_rows) return band_rows_check(chain, *band_rows);
+  TRY(band_rows_for(chain, band_rows));
+  if (!*band_rows) *band_rows = (H + 15) / 16 * 16;
+  return WCT_OK;
+}
+
+extern "C" int wct_encode_banded(wct_ctx* c, const float* img01, int H, int W, int level, int band_rows, float* feat) {
+  ARG_CHECK(c && img01 && feat && level >= 1 && level <= 5 && band_rows >= 0);
+  HIP_TRY(hipSetDevice(c->device));
+  TRY(twin_band_rows(H, W, level, &band_rows));
+  int h, w;
+  level_dims(H, W, level, &h, &w);
+  void* dimg;
+  TRY(stage_in(c, 0, img01, (size_t)H * W * 3 * 4, &dimg));
+  const size_t fb = (size_t)h * w * LEVEL_C[level] * 4;
+  TRY(ensure(c, c->band_f, fb));
+  TRY(run_encoder_banded(c, (float*)dimg, H, W, 0, level, band_rows, (float*)c->band_f.p));
+  return fetch(c, feat, c->band_f.p, fb);
+}
+
+extern "C" int wct_decode_banded(wct_ctx* c, const float* feat, int h, int w, int level, int band_rows, float* img) {
+  ARG_CHECK(c && feat && img && level >= 1 && level <= 5 && band_rows >= 0 && h >= 2 && w >= 2 && h <= (1 << 26) && w <= (1 << 26));
+  HIP_TRY(hipSetDevice(c->device));
+  const int C = LEVEL_C[level], scale = 1 << (level - 1);
+  TRY(twin_band_rows(h * scale, w * scale, level, &band_rows));
+  void* df;
+  const size_t n = (size_t)h * w * C;
+  TRY(stage_in(c, 0, feat, n * 4, &df));
+  TRY(ensure(c, c->band_g, n * 2));
+  TRY(launch_f32_to_f16((float*)df, (half_t*)c->band_g.p, n, c->stream));
+  const size_t ib = (size_t)h * scale * w * scale * 3 * 4;
+  TRY(ensure(c, c->img_t[0], ib));
+  TRY(run_decoder_banded(c, level, (half_t*)c->band_g.p, h, w, band_rows, (float*)c->img_t[0].p));
   return fetch(c, img, c->img_t[0].p, ib);
 }
 

@@ -669,6 +669,80 @@ extern "C" int wct_stylize_prepared_batch_dev_warm(wct_ctx* c, const uint8_t* co
 }
 
 // ---------------------------------------------------------------------------
+// banded stylization (banded.hip): one content of any size on a prepared style -- every level encoded and decoded in bands of
+// rows, its content statistics pooled over chunks of feature rows.  wct.py:70-106 runs each level over the whole image, as the
+// calls above do; where they run, this one gives their frame.
+// ---------------------------------------------------------------------------
+static int banded_flags_ok(unsigned flags) {
+  if (flags & WCT_FLAG_ADAIN) { wct_set_error("banded: WCT_FLAG_ADAIN is not served on this path (whiten-colour transforms only)"); return WCT_ERR_ARG; }
+  return style_flags_ok(flags);
+}
+
+static int stylize_prepared_banded_dev(wct_ctx* c, const void* content, int Hc, int Wc, const wct_style* style, const int* levels,
+                                       int n_levels, float alpha, unsigned flags, int band_rows, int stat_rows, uint8_t* out) {
+  HIP_TRY(hipSetDevice(c->device));
+  TRY(style_live(c, style));
+  TRY(check_levels(c, levels, n_levels, &style, 1));
+  Chain chain;
+  TRY(chain_geometry(Hc, Wc, levels, n_levels, &chain));
+  if (band_rows) TRY(band_rows_check(chain, band_rows));
+  else {
+    TRY(band_rows_for(chain, &band_rows));
+    if (!band_rows)                                       // the whole-image call takes this content: one band per level
+      for (const ChainLevel& g : chain.lv) band_rows = std::max(band_rows, (g.H + 15) / 16 * 16);
+  }
+  const int n = (int)chain.lv.size();
+  std::vector<int> crows(n), cK(n);
+  for (int i = 0; i < n; ++i) TRY(chunk_rule(chain.lv[i].h, chain.lv[i].w, chain.lv[i].C, stat_rows, &crows[i], &cK[i]));
+
+  // the states of every level (the key of the whole-image call: the layout of the whole map against the style), before any launch
+  ++c->style_clock;
+  std::vector<WctStyleRef> refs;
+  std::vector<int> ns;
+  TRY(chain_states(c, chain, &style, 1, style_kind(flags), &refs, &ns));
+
+  const float* cur;
+  TRY(content_prelude(c, flags, content, (size_t)Hc * Wc * 3, &cur));
+  for (int i = 0; i < n; ++i) {
+    const ChainLevel& g = chain.lv[i];
+    const size_t px = (size_t)g.h * g.w;
+    TRY(ensure(c, c->band_f, px * g.C * 4));
+    TRY(ensure(c, c->band_g, px * g.C * 2));
+    DevBuf& dst = c->img_t[i & 1];
+    TRY(ensure(c, dst, (size_t)(g.h << (g.l - 1)) * (g.w << (g.l - 1)) * 3 * 4));
+    TRY(run_encoder_banded(c, cur, g.H, g.W, i > 0, g.l, band_rows, (float*)c->band_f.p));
+    TRY(run_transform_chunked(c, (float*)c->band_f.p, px, crows[i] * g.w, cK[i], nullptr, ns[(size_t)i * WCT_MIX_MAX], g.C, alpha, flags,
+                              -1.f, (half_t*)c->band_g.p, nullptr, nullptr, &refs[i]));
+    TRY(run_decoder_banded(c, g.l, (half_t*)c->band_g.p, g.h, g.w, band_rows, (float*)dst.p));
+    cur = (float*)dst.p;
+  }
+  const int H = chain.Ho, W = chain.Wo;
+  if (flags & WCT_FLAG_CONTENT_COLORS) {
+    const int f32 = (flags & WCT_FLAG_IMAGES_F32) ? 1 : 0;
+    ProfScope ps(c, 7, 0, (double)H * W * 3 * 5 + (double)Hc * Wc * 3 * (f32 ? 4 : 1));
+    return launch_content_colors_f32(cur, content, f32, 1, H, W, Hc, Wc, out, c->stream);
+  }
+  ProfScope ps(c, 7, 0, (double)H * W * 3 * 5);
+  return launch_f32_to_u8(cur, out, (size_t)H * W * 3, c->stream);
+}
+
+extern "C" int wct_stylize_prepared_banded_dev(wct_ctx* c, const uint8_t* content, int Hc, int Wc, const wct_style* style, const int* levels,
+                                               int n_levels, float alpha, unsigned flags, int band_rows, int stat_rows, uint8_t* out) {
+  ARG_CHECK(c && content && out && levels && n_levels >= 1 && n_levels <= 16 && band_rows >= 0 && stat_rows >= 0);
+  TRY(banded_flags_ok(flags));
+  return stylize_prepared_banded_dev(c, content, Hc, Wc, style, levels, n_levels, alpha, flags, band_rows, stat_rows, out);
+}
+
+extern "C" int wct_stylize_prepared_banded(wct_ctx* c, const uint8_t* content, int Hc, int Wc, const wct_style* style, const int* levels,
+                                           int n_levels, float alpha, unsigned flags, int band_rows, int stat_rows, uint8_t* out) {
+  ARG_CHECK(c && content && out && levels && n_levels >= 1 && n_levels <= 16 && band_rows >= 0 && stat_rows >= 0);
+  TRY(banded_flags_ok(flags));
+  return host_frame(c, content, Hc, Wc, levels, n_levels, flags, out, [&](void* dc, uint8_t* frame) {
+    return stylize_prepared_banded_dev(c, dc, Hc, Wc, style, levels, n_levels, alpha, flags, band_rows, stat_rows, frame);
+  });
+}
+
+// ---------------------------------------------------------------------------
 // texture synthesis (Li et al. 2017, sec. 4.3; webcam.py:191-192 --noise, stylize.py:95-97): seeded noise made on the device,
 // then `passes` runs of the prepared chain, each on the frames of the one before it
 // ---------------------------------------------------------------------------

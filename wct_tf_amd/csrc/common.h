@@ -39,6 +39,12 @@ void wct_set_error(const char* fmt, ...);
 
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 
+// The conv kernels address one image's activations, and the transform one feature map, with 32-bit byte offsets: a map of `elems`
+// elements of `bytes` each fits one launch below 2^31 bytes.  The one bound behind the size check of every launcher and behind
+// the routing of the banded path (banded.hip), which cuts what does not fit into pieces that do.
+constexpr size_t WCT_LAUNCH_BYTES = (size_t)1 << 31;
+static inline bool launch_map_fits(size_t elems, size_t bytes) { return elems * bytes < WCT_LAUNCH_BYTES; }
+
 // Environment variables: the library reads four TEST hooks and nothing else, all safe by construction (a library whose
 // contract is bit-reproducible output must not change its numerics on a stray variable): WCT_JACOBI_MAX_SWEEPS can only
 // LOWER the sweep budget (clamped to the compiled one; the solve then fails loudly, never silently); WCT_FUSE_STATS=0 and

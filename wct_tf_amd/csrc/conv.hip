@@ -554,8 +554,8 @@ int launch_conv3x3(const ConvArgs& a, hipStream_t s) {
   ARG_CHECK(a.Cin % 64 == 0 && a.Cout % 64 == 0 && a.H > 1 && a.W > 1 && a.B > 0);
   ARG_CHECK(!a.upsample || (a.H % 2 == 0 && a.W % 2 == 0));
   // one image's activations are addressed with 32-bit byte offsets (buffer loads)
-  ARG_CHECK((size_t)a.H * a.W * a.Cin * 2 < ((size_t)1 << 31));
-  ARG_CHECK((size_t)a.H * a.W * a.Cout * (a.y32 ? 4 : 2) < ((size_t)1 << 31));     // per-image output buffers (epilogue)
+  ARG_CHECK(launch_map_fits((size_t)a.H * a.W * a.Cin, 2));
+  ARG_CHECK(launch_map_fits((size_t)a.H * a.W * a.Cout, a.y32 ? 4 : 2));     // per-image output buffers (epilogue)
   ARG_CHECK(!a.usum || (a.y32 && a.umax && a.relu && a.W % 16 == 0));
   ARG_CHECK(!a.pool || (a.relu && !a.y32));            // the fused pool relies on post-ReLU values (>= 0) at ragged edges
   // the reduced-FLOP kernel, where the caller packed its filters for it (api_weights.hip: the wide layers) and the epilogue is one it has

@@ -408,8 +408,8 @@ bool conv3x3_wino_takes(const ConvArgs& a) {
 int launch_conv3x3_wino(const ConvArgs& a, hipStream_t s) {
   ARG_CHECK(conv3x3_wino_takes(a) && a.H > 1 && a.W > 1 && a.B > 0);
   ARG_CHECK(!a.upsample || (a.H % 2 == 0 && a.W % 2 == 0));
-  ARG_CHECK((size_t)a.H * a.W * a.Cin * 2 < ((size_t)1 << 31));
-  ARG_CHECK((size_t)a.H * a.W * a.Cout * 2 < ((size_t)1 << 31));
+  ARG_CHECK(launch_map_fits((size_t)a.H * a.W * a.Cin, 2));
+  ARG_CHECK(launch_map_fits((size_t)a.H * a.W * a.Cout, 2));
   const long px16 = (long)cdiv(a.W, TW) * cdiv(a.H, 16) * a.B;
   // one 256-pixel x 128-channel block per CU with the interleaved schedule where that fills the chip; below, blocks of 8 rows at
   // two per CU (the second block covers the first one's prologue and epilogue)

@@ -247,7 +247,7 @@ int launch_wct_masked(const float* content, int Nc, const MaskGeom& g, const int
   MaskPlan m;
   ARG_CHECK(C % 32 == 0 && C >= 32 && C <= 1024 && content && styles && mask_plan(&m, workspace, C, Nc, nk, styles, Ns, K, 2));
   ARG_CHECK(mode == WCT_MODE_NP || mode == WCT_MODE_TF);
-  ARG_CHECK((size_t)Nc * C * 4 < ((size_t)1 << 31) && plan_fits(m, C));
+  ARG_CHECK(launch_map_fits((size_t)Nc * C, 4) && plan_fits(m, C));
   ARG_CHECK(workspace_bytes >= m.total);
   const WctCarve& w = m.w;
   int rc;
@@ -431,7 +431,7 @@ int launch_wct_masked_batch(const float* content, int Nc, int G, const MaskGeom&
   MaskBatchPlan m;
   ARG_CHECK(C % 32 == 0 && C >= 32 && C <= 1024 && content && mask_batch_plan(&m, workspace, C, Nc, G, nk, Ns, K, 2));
   ARG_CHECK(mode == WCT_MODE_NP || mode == WCT_MODE_TF);
-  ARG_CHECK((size_t)Nc * C * 4 < ((size_t)1 << 31) && plan_fits(m, C));
+  ARG_CHECK(launch_map_fits((size_t)Nc * C, 4) && plan_fits(m, C));
   ARG_CHECK((size_t)G * Nc < ((size_t)1 << 31));                        // (row indices are ints)
   ARG_CHECK(workspace_bytes >= m.total);
   const WctCarve& w = m.w;

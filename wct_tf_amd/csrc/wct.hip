@@ -308,20 +308,24 @@ int launch_blend(const WctCarve& w, int C, int P, float alpha, int shared_style,
   return launch_gemm(g, 1, P, s);
 }
 
-// the blend product for P pairs, then the apply out = (x - mc) M^T + bias
+// the apply out = (x - mc) M^T + bias of P pairs of Nc rows, on the mean, scale, M, bias and mabs of w:
+// out[n][j] = sum_k (x[n][k]-mc[k]) M[j][k] + bias[j]
+int launch_apply(const WctCarve& w, const float* content, int Nc, int C, int P, half_t* out16, float* out32, hipStream_t s) {
+  ApplyArgs a;
+  a.x = content; a.N = Nc; a.C = C; a.mean = w.mean; a.M = w.M; a.bias = w.bias;
+  a.xscale = w.scale; a.mabs = w.mabs; a.out16 = out16; a.out32 = out32;
+  if (C >= 128) hipLaunchKernelGGL((apply_f16x2_kernel<128, 128>), dim3(cdiv(Nc, 128), cdiv(C, 128), P), dim3(256), 0, s, a);
+  else hipLaunchKernelGGL((apply_f16x2_kernel<64, 128>), dim3(cdiv(Nc, 128), cdiv(C, 64), P), dim3(256), 0, s, a);
+  HIP_TRY(hipGetLastError());
+  return WCT_OK;
+}
+
+// the blend product for P pairs, then the apply
 static int launch_blend_apply(const WctCarve& w, const float* content, int Nc, int C, int P, float alpha, int shared_style,
                               half_t* out16, float* out32, hipStream_t s) {
   int rc;
   if ((rc = launch_blend(w, C, P, alpha, shared_style, s))) return rc;
-  {  // out[n][j] = sum_k (x[n][k]-mc[k]) M[j][k] + bias[j]
-    ApplyArgs a;
-    a.x = content; a.N = Nc; a.C = C; a.mean = w.mean; a.M = w.M; a.bias = w.bias;
-    a.xscale = w.scale; a.mabs = w.mabs; a.out16 = out16; a.out32 = out32;
-    if (C >= 128) hipLaunchKernelGGL((apply_f16x2_kernel<128, 128>), dim3(cdiv(Nc, 128), cdiv(C, 128), P), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((apply_f16x2_kernel<64, 128>), dim3(cdiv(Nc, 128), cdiv(C, 64), P), dim3(256), 0, s, a);
-  }
-  HIP_TRY(hipGetLastError());
-  return WCT_OK;
+  return launch_apply(w, content, Nc, C, P, out16, out32, s);
 }
 
 // ---------------------------------------------------------------------------
@@ -388,7 +392,7 @@ size_t wct_style_workspace_bytes(int C, int Ns, const WctStyleKey& key) {
 
 int launch_style_state(const float* style, int Ns, int C, const WctStyleKey& key, int adain, int mode, float eps_in, void* workspace,
                        size_t workspace_bytes, int* eig_fail, hipStream_t s, float* state) {
-  ARG_CHECK(style && state && C % 32 == 0 && C >= 32 && C <= 1024 && Ns >= (adain ? 1 : 2) && (size_t)Ns * C * 4 < ((size_t)1 << 31));
+  ARG_CHECK(style && state && C % 32 == 0 && C >= 32 && C <= 1024 && Ns >= (adain ? 1 : 2) && launch_map_fits((size_t)Ns * C, 4));
   ARG_CHECK(adain || mode == WCT_MODE_NP || mode == WCT_MODE_TF);
   ARG_CHECK(key.nslab >= 1 && key.nslab <= 256 && key.nsplit >= 1 && key.ksplit >= 256 && key.ksplit % 32 == 0 &&
             (long long)key.nsplit * key.ksplit >= Ns);
@@ -419,7 +423,7 @@ int launch_wct(const float* content, int Nc, const float* style, int Ns, int C, 
   if (prep) shared_style = WCT_SKIP_STYLE;       // (the style rows are not read: `style` may be null)
   ARG_CHECK(mode == WCT_MODE_NP || mode == WCT_MODE_TF);
   // the covariance kernel addresses one feature map through a buffer resource with 32-bit byte offsets
-  ARG_CHECK((size_t)Nc * C * 4 < ((size_t)1 << 31) && (size_t)Ns * C * 4 < ((size_t)1 << 31));
+  ARG_CHECK(launch_map_fits((size_t)Nc * C, 4) && launch_map_fits((size_t)Ns * C, 4));
   WctCarve w = carve(workspace, C, P, pair_layout(C, Nc, Ns));
   ARG_CHECK(workspace_bytes >= w.total);
   int rc;
@@ -466,7 +470,7 @@ void plan_carve(SlotPlan* sp, void* base, int C) {
 // the covariance kernel addresses one feature map through a buffer resource with 32-bit byte offsets
 bool plan_fits(const SlotPlan& sp, int C) {
   for (int m = 0; m < 2 * sp.P; ++m)
-    if ((size_t)sp.slot[m].n * C * 4 >= ((size_t)1 << 31)) return false;
+    if (!launch_map_fits((size_t)sp.slot[m].n * C, 4)) return false;
   return true;
 }
 

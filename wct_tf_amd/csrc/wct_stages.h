@@ -121,9 +121,11 @@ int launch_refresh(const WctCarve& w, int C, int P, int shared_style, hipStream_
 int launch_spectral_tail(const WctCarve& w, int C, int P, float alpha, int mode, float eps_in, int shared_style, int nwhite, hipStream_t s);
 int launch_spectral_function(const float* A, const float* V, float* G, float* X, float* out, int C, int nbatch, size_t stride,
                              size_t out_stride, int kind, float shift, hipStream_t s, float* scratch2 = nullptr);
-// wct.hip: the blend product M = alpha Tcs Tw + (1 - alpha) I of P pairs; the apply of a masked transform's P segments (the
+// wct.hip: the blend product M = alpha Tcs Tw + (1 - alpha) I of P pairs; the apply of P pairs of Nc rows on the matrices of w
+// (any number of calls on one set of matrices: the chunks of a banded map); the apply of a masked transform's P segments (the
 // longest has nmax rows)
 int launch_blend(const WctCarve& w, int C, int P, float alpha, int shared_style, hipStream_t s);
+int launch_apply(const WctCarve& w, const float* content, int Nc, int C, int P, half_t* out16, float* out32, hipStream_t s);
 int launch_apply_seg(const ApplySegArgs& a, int nmax, int P, hipStream_t s);
 int launch_apply_seg_batch(const ApplySegBatchArgs& a, int nmax, int P, hipStream_t s);
 // warm.hip (video warm start): A' = V0^T A V0 of the P content matrices of w in place (w.X scratch); V = V0 V' of the same in place

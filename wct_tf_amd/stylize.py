@@ -58,6 +58,10 @@ _FLAGS = [
     (('--mask-styles',), dict(nargs='+', default=None, metavar='PATH',
                               help='the K style images of --mask-path, label 0 first; not with --style-path / -r / '
                                    '--interp-styles / --concat')),
+    (('--band-rows',), dict(type=int, default=0, metavar='N',
+                            help='image rows per band (a multiple of 16) of the banded call, which takes contents of any size; 0: '
+                                 'only for a content past the limit of one launch (8.4 MP with relu1_1, 16.7 MP without), at the '
+                                 'automatic height.  Not with --adain, --swap5, --interp-styles or --mask-path')),
     (('--gpus',), dict(type=int, default=0, metavar='N',
                        help='shard the content files over N GPUs of this node, one process per GPU: started here when no '
                             'launcher did (0: whatever the launcher set, else one GPU)')),
@@ -125,6 +129,33 @@ def check_color_args(parser, args):
         parser.error('--content-colors with --passes > 1 needs --ss-stride 1 (a larger stride crops the content of every pass)')
 
 
+def _unbanded(args):
+    """the options of this run that the banded call does not serve"""
+    on = [('--adain', args.adain), ('--swap5', args.swap5), ('--interp-styles', args.interp_styles is not None),
+          ('--mask-path', args.mask_path is not None)]
+    return [name for name, v in on if v]
+
+
+def check_band_args(parser, args):
+    """--band-rows: 0 or a positive multiple of 16, and none of the options the banded call does not serve (parser.error exits)"""
+    if args.band_rows < 0 or args.band_rows % 16:
+        parser.error('--band-rows must be 0 (automatic, only when needed) or a positive multiple of 16, got %d' % args.band_rows)
+    if args.band_rows and _unbanded(args):
+        parser.error('--band-rows does not combine with %s: the banded call takes whiten-colour transforms on one style'
+                     % ' / '.join(_unbanded(args)))
+
+
+def check_content_fits(parser, args, content, path):
+    """A content past the limit of one launch runs in bands, which some options do not: a clear error, not the library's refusal"""
+    if not _unbanded(args):
+        return
+    from .context import band_rows
+    need = band_rows(content.shape[0], content.shape[1], args.relu_targets)
+    if need:
+        parser.error('%s is %dx%d: past the limit of one launch (a map of 2^31 bytes), it runs in bands (--band-rows, here %d), '
+                     'which %s does not; try --content-size' % (path, content.shape[0], content.shape[1], need, ' / '.join(_unbanded(args))))
+
+
 def run_passes(model, content, args, predict):
     """`--passes` predictions from `content`, predict(image, content_colors) -> image.  --content-colors is fused into the
     prediction of a single pass; several passes run plain (a later pass sees a stylized input, not the content) and the
@@ -147,7 +178,8 @@ def stylize_pair(model, content, style, args, prepared=None):
         from .ops import preserve_colors_np
         style = preserve_colors_np(style, content, ctx=model.sess)
     out = run_passes(model, content, args, lambda img, colors: model.predict(
-        img, style if prepared is None else prepared, args.alpha, args.swap5, args.ss_alpha, args.adain, content_colors=colors))
+        img, style if prepared is None else prepared, args.alpha, args.swap5, args.ss_alpha, args.adain, content_colors=colors,
+        band_rows=getattr(args, 'band_rows', 0) or None))
     if args.concat:
         side = out.shape[0]
         out = np.hstack([utils._imresize(style, (side, side)), out])
@@ -254,6 +286,7 @@ def main(argv=None):
     check_interp_args(parser, args)
     check_mask_args(parser, args)
     check_color_args(parser, args)
+    check_band_args(parser, args)
     if args.synthetic_weights is None and not args.checkpoints:
         parser.error('--checkpoints is required (stylize.py:17) unless --synthetic-weights SEED is given')
     if args.gpus > 0:
@@ -284,6 +317,7 @@ def main(argv=None):
             content = utils.get_img(cpath)
             if args.content_size > 0:
                 content = utils.resize_to(content, args.content_size)
+            check_content_fits(parser, args, content, cpath)
             target = os.path.join(args.out_path, interp_name(cpath, args.interp_styles))
             utils.save_img(target, stylize_mix_pair(model, content, mix, args, prepared))
             written += 1
@@ -299,6 +333,7 @@ def main(argv=None):
             content = utils.get_img(cpath)
             if args.content_size > 0:
                 content = utils.resize_to(content, args.content_size)
+            check_content_fits(parser, args, content, cpath)
             target = os.path.join(args.out_path, mask_name(cpath, args.mask_styles))
             utils.save_img(target, stylize_mask_pair(model, content, grey, regions, args, prepared))
             written += 1
@@ -317,6 +352,7 @@ def main(argv=None):
         content = utils.get_img(cpath)
         if args.content_size > 0:
             content = utils.resize_to(content, args.content_size)
+        check_content_fits(parser, args, content, cpath)
         for spath in styles:
             if spath not in loaded:
                 style = load_style(spath, args)

@@ -156,13 +156,53 @@ class WCT(object):
             raise ValueError('a warm state goes with a PreparedStyle (prepare_style), not a style image')
         check_warm(self.sess, warm, self.relu_targets, adain, swap5)
 
-    def predict(self, content, style, alpha=1, swap5=False, ss_alpha=1, adain=False, warm=None, content_colors=False):
+    def _band_route(self, content, band_rows, swap5, adain, warm):
+        '''The band height a predict() goes to the banded call with, or None for the whole-image call.  band_rows None: banded
+           only when the whole-image call refuses this content (wct_band_rows), at the automatic height; an int forces banding
+           (0: the automatic height).  ValueError before any GPU call for what large contents do not take.'''
+        from .context import band_rows as auto_band_rows, check_band_rows
+        shape = np.shape(content)
+        if len(shape) != 3:
+            return None                                      # (the whole-image call reports the shape)
+        if band_rows is None:
+            need = auto_band_rows(shape[0], shape[1], self.relu_targets)
+            if need == 0:
+                return None
+            rows = need
+        else:
+            rows = check_band_rows(band_rows)
+            need = 0
+        for name, on in (('adain', adain), ('swap5', swap5), ('warm', warm is not None)):
+            if on:
+                if need:
+                    raise ValueError('%s is not served on a %dx%d content: it passes the limit of one launch (a map of 2^31 bytes) '
+                                     'and runs in bands (band_rows=%d), which take whiten-colour transforms on one style only'
+                                     % (name, shape[0], shape[1], need))
+                raise ValueError('%s is not served with band_rows: the banded call takes whiten-colour transforms on one style only'
+                                 % name)
+        return rows
+
+    def predict(self, content, style, alpha=1, swap5=False, ss_alpha=1, adain=False, warm=None, content_colors=False,
+                band_rows=None):
         '''Stylize a single content/style pair; arrays in [0,255], returns uint8 HxWx3.
            The /255 preprocess and the clip*255 postprocess run inside the library
            (fused at the ends of the kernel chain).  `style` may be a PreparedStyle (prepare_style); with one, `warm` may be a
            WarmState (warm_state).  content_colors (here and in every predict*): luminance-only colour preservation (Gatys et
            al. 2016; WCT_FLAG_CONTENT_COLORS) -- the frame keeps its stylized luminance and takes the colours of `content`, in
-           the last launch of the call; it equals ops.content_colors_np(the plain frame, content) bit for bit.'''
+           the last launch of the call; it equals ops.content_colors_np(the plain frame, content) bit for bit.
+           band_rows: None sends a content to the banded call (Context.stylize_prepared_banded) only when it passes the limit of
+           the whole-image call -- 8.4 MP with relu1_1 among the targets, 16.7 MP without --, an int forces it (a multiple of 16
+           image rows per band; 0: the automatic height).  A style image is then prepared, used and closed.  adain, swap5 and
+           warm are not served there: ValueError.'''
+        rows = self._band_route(content, band_rows, swap5, adain, warm)           # ValueError before any GPU call
+        if rows is not None:
+            if isinstance(style, PreparedStyle):
+                check_prepared(self.sess, [style], self.relu_targets)
+                return self.sess.stylize_prepared_banded(np.asarray(content), style, self.relu_targets, alpha=alpha,
+                                                         wct_mode=self.wct_mode, band_rows=rows, content_colors=content_colors)
+            with self.prepare_style(np.asarray(style)) as handle:
+                return self.sess.stylize_prepared_banded(np.asarray(content), handle, self.relu_targets, alpha=alpha,
+                                                         wct_mode=self.wct_mode, band_rows=rows, content_colors=content_colors)
         if warm is not None:
             self._check_warm(warm, style, swap5, adain)                           # ValueError before any GPU call
         if isinstance(style, PreparedStyle):
