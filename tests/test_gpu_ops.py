@@ -458,7 +458,8 @@ def test_conv3x3_reduced_flop_kernel(ctx, h, w, cin, cout, relu, up, pool, batch
     """csrc/conv_wino.hip (Winograd F(2,3) along y, direct along x) against (a) the restatement with ITS roundings
     (fp16 filters U = G g, fp16 transformed rows, fp16 output): what is left is accumulation order and fp16 rounding flips;
     (b) the fp32 oracle: the per-layer gate of 1.5e-3 (measured on the CPU first, profiles/r06_winograd_error.txt);
-    (c) the direct kernel through the same entry point, whose bits must be the round-5 path's."""
+    (c) the direct kernel through the same entry point, whose bits must be the round-5 path's.
+    Every case here selects the <8,64,2,2> tile shape; test_gpu_pointwise.py::test_wino_conv holds <16,128,1,4,IL> and <8,128,1,4> too."""
     rng = np.random.default_rng(h * 1000 + cin + 7 * pool)
     x = np.maximum(rng.standard_normal((batch, h, w, cin)), 0).astype(np.float32)
     wt = (rng.standard_normal((3, 3, cin, cout)) * np.sqrt(2.0 / (9 * cin))).astype(np.float32)

@@ -9,7 +9,7 @@ import pytest
 
 import oracle
 import pointwise as pw
-from conftest import rel_err
+from conftest import max_rel, rel_err
 
 
 @pytest.fixture(scope='module')
@@ -89,7 +89,188 @@ def test_the_two_float64_convolutions_agree():
     assert np.array_equal(pw._conv64(pw.h16(x), pw.h16(wt), bias, False), pw._conv64(pw.h16(x), pw.h16(wt), bias, False, torch_from=0))
 
 
+def test_direct_reference_where_cin_differs_from_cout():
+    """The direct kernel's added cases (Cin != Cout, the folded upsample, the fp32 epilogue of the tap layers): each is listed
+    under the tile configuration the policy picks, and the float32 oracle sits within half of tau_direct(Cin)."""
+    for ci, co, b, h, w, up, pools, cfg in pw.DIRECT_MIXED_CASES:
+        s = 2 if up else 1
+        assert pw.tile_config(co, b, h * s, w * s) == cfg
+        x, wt, bias = pw.layer_inputs(ci, co, b, h, w)
+        x = x[[0, b - 1]] if b > 4 else x
+        want, sm = pw.conv_ref(pw.h16(x), pw.h16(wt), bias, relu=True, up=up)
+        f32 = np.stack([oracle.conv3x3_reflect(oracle.upsample2x_nearest(pw.h16(xi)) if up else pw.h16(xi), pw.h16(wt), bias, True) for xi in x])
+        assert (want[:, -1] == 0).any() and (want[:, :, -1] == 0).any()
+        for pool in ((False, True) if pools else (False,)):
+            g = np.stack([oracle.maxpool2x2_same(f) for f in f32]) if pool else f32
+            r, at = pw.judge(g, want, sm, pw.tau_direct(ci), pool=pool)
+            r16, at16 = pw.judge(pw.h16(g), want, sm, pw.tau_direct(ci), pool=pool, fp16_out=True)
+            print('direct %d->%d %dx%dx%d up=%d pool=%d: float32 oracle %.3f at %s, rounded to fp16 %.3f at %s' % (ci, co, b, h, w, up, pool, r, at, r16, at16))
+            assert r <= 0.5 and r16 <= 1.0, (ci, co, b, h, w, up, pool, r, r16)
+    for ci, co, h, w, relu, cfg in pw.TAP_CASES:
+        assert pw.tile_config(co, 1, h, w) == cfg
+        x, wt, bias = pw.layer_inputs(ci, co, 1, h, w)
+        want, sm = pw.conv_ref(pw.h16(x[0]), pw.h16(wt), bias, relu=relu)
+        r, at = pw.judge(oracle.conv3x3_reflect(pw.h16(x[0]), pw.h16(wt), bias, relu), want, sm, pw.tau_direct(ci))
+        print('tap %d->%d %dx%d relu=%d: float32 oracle %.3f at %s' % (ci, co, h, w, relu, r, at))
+        assert r <= 0.5 and ((want < 0).any() or relu)
+    assert {c[7] for c in pw.DIRECT_MIXED_CASES} == {'8,64,2,2', '16,128,2,2'}
+
+
+# ---- the reduced-FLOP kernel: policy, coverage, reference, emulation -----------------------------------------------------------
+
+def test_wino_cases_select_their_tile_shape_and_cover_every_edge():
+    """Every case is listed under the shape launch_conv3x3_wino picks for it, and each of the three shapes occurs with an odd
+    H, a last tile column one pixel wide, the upsample, the no-ReLU epilogue, filters from both packers (the device's for
+    Cin < 256, the host's from 256) and more than one channel block."""
+    for ci, co, b, h, w, up, norelu, cfg in pw.WINO_CASES:
+        s = 2 if up else 1
+        assert pw.wino_config(co, b, h * s, w * s) == cfg, (ci, co, b, h, w, up)
+        assert ci % 64 == 0 and co % 64 == 0 and h * s > 1 and w * s > 1
+    for cfg, bn in (('IL16', 128), ('8x128', 128), ('8x64', 64)):
+        cases = [c for c in pw.WINO_CASES if c[7] == cfg]
+        assert any(c[3] % 2 == 1 and not c[5] for c in cases), cfg
+        assert any(c[4] % 16 == 1 and not c[5] for c in cases), cfg
+        assert any(c[5] for c in cases) and any(c[6] for c in cases), cfg
+        assert any(c[0] in (64, 128) for c in cases) and any(c[0] >= 256 and c[1] >= 256 for c in cases), cfg
+        assert any(c[1] // bn > 1 for c in cases), cfg
+    # the shared images of the two 17x33 cases
+    a, b = pw.layer_inputs(256, 256, 32, 17, 33), pw.layer_inputs(256, 256, 16, 17, 33)
+    assert np.array_equal(a[0][:16], b[0]) and np.array_equal(a[1], b[1]) and np.array_equal(a[2], b[2])
+    # a single image of every case selects <8,64,2,2>: the GPU test's batch == single check crosses the shapes for IL16 and 8x128
+    assert all(pw.wino_config(c[1], 1, c[3] * (2 if c[5] else 1), c[4] * (2 if c[5] else 1)) == '8x64' for c in pw.WINO_CASES)
+
+
+@pytest.mark.parametrize('case', pw.WINO_CASES, ids=pw.wino_case_id)
+def test_wino_reference_and_emulation_within_the_bounds(case):
+    """The Winograd form with exact U, T IS the layer (1e-13 of s); an fp32-accumulating emulation of the kernel's order sits
+    within half of A before the fp16 store (against tau_wino s_A alone, and so against the whole bound), within A after it (the
+    rounding term is the whole of the store's error), and within half of B before / B after the store; unpooled and pooled."""
+    ci, co, b, h, w, up, norelu, cfg = case
+    x, wt, bias = pw.layer_inputs(ci, co, b, h, w)
+    x = x[[0, b - 1]] if b > 4 else x
+    (pa, sa), (pb, sb) = pw.wino_ref(x, wt, bias, relu=False, up=up)
+    assert (np.abs(pw.wino_exact(x, wt, bias, up) - pb) <= 1e-13 * sb).all()
+    pre = np.stack([pw.wino_emulate(xi, wt, bias, relu=False, up=up) for xi in x])
+    ta, tb = pw.tau_wino(ci), pw.tau_wino_b(ci)
+    for relu in ((True, False) if norelu else (True,)):
+        act = (lambda v: np.maximum(v, 0)) if relu else (lambda v: v)
+        wa, wb, em = act(pa), act(pb), act(pre)
+        if relu:
+            assert (wa == 0).mean() > 0.2 and (wa[:, -1] == 0).any() and (wa[:, :, -1] == 0).any()
+        for pool in ((False, True) if relu else (False,)):
+            g = pw.pool_same(em) if pool else em
+            r0, at0 = pw.judge(g, wa, sa, ta, pool=pool)
+            r1, _ = pw.judge(g, wa, sa, ta, pool=pool, fp16_out=True)
+            r2, at2 = pw.judge(pw.h16(g), wa, sa, ta, pool=pool, fp16_out=True)
+            rb0, atb0 = pw.judge(g, wb, sb, tb, pool=pool)
+            rb1, atb1 = pw.judge(pw.h16(g), wb, sb, tb, pool=pool, fp16_out=True)
+            print('wino %s relu=%d pool=%d: A before the store %.4f (%.4f of tau s alone, at %s), after %.3f at %s; B before %.3f at %s, after %.3f at %s'
+                  % (pw.wino_case_id(case), relu, pool, r1, r0, at0, r2, at2, rb0, atb0, rb1, atb1))
+            assert r0 <= 0.5 and r1 <= 0.5 and r2 <= 1.0 and rb0 <= 0.5 and rb1 <= 1.0, (case, relu, pool, r0, r1, r2, rb0, rb1)
+
+
+@pytest.mark.parametrize('case', pw.WINO_SUBNORMAL_CASES, ids=pw.wino_case_id)
+def test_wino_subnormal_rows_are_kept(case):
+    """Activations scaled by 2^-15: the emulation (which keeps fp16 subnormals, as the kernel's denormal mode does) stays inside
+    A and B with the absolute term of a subnormal store; the same emulation with the subnormals of T flushed to zero does not."""
+    ci, co, b, h, w, up, norelu, cfg = case
+    assert pw.wino_config(co, b, h, w) == cfg
+    x, wt, bias = pw.subnormal_inputs(case)
+    x = x[[0, b - 1]] if b > 4 else x
+    x16 = pw.h16(x)
+    assert 0.3 < ((np.abs(x16) < 2.0 ** -14) & (x16 != 0)).mean() < 0.7          # (half of the inputs are exact zeros after the ReLU; nearly all the rest are subnormal)
+    (wa, sa), (wb, sb) = pw.wino_ref(x, wt, bias, relu=True)
+    em = np.stack([pw.wino_emulate(xi, wt, bias) for xi in x])
+    r0, _ = pw.judge(em, wa, sa, pw.tau_wino(ci))
+    r1, at1 = pw.judge(pw.h16(em), wa, sa, pw.tau_wino(ci), a=pw.A16_SUBNORMAL, fp16_out=True)
+    rb, atb = pw.judge(pw.h16(em), wb, sb, pw.tau_wino_b(ci), a=pw.A16_SUBNORMAL, fp16_out=True)
+    bad = pw.h16(np.stack([pw.wino_emulate(xi, wt, bias, defect='flush') for xi in x]))
+    rf, atf = pw.judge(bad, wa, sa, pw.tau_wino(ci), a=pw.A16_SUBNORMAL, fp16_out=True)
+    rfb, _ = pw.judge(bad, wb, sb, pw.tau_wino_b(ci), a=pw.A16_SUBNORMAL, fp16_out=True)
+    print('wino subnormal %s: A before the store %.4f, after %.3f at %s, B %.3f at %s; T flushed: A %.3g at %s, B %.3g, rel_err %.2e'
+          % (pw.wino_case_id(case), r0, r1, at1, rb, atb, rf, atf, rfb, rel_err(bad, pw.h16(em))))
+    assert r0 <= 0.5 and r1 <= 1.0 and rb <= 0.5
+    assert rf > 1 and rfb > 1
+
+
+def test_wino_restatement_equals_the_oracles():
+    """wino_ref's pair A, rounded to fp16, is oracle/net_oracle.py::conv3x3_reflect_wino_f16 (float64 sums) up to the sum order."""
+    x, wt, bias = pw.layer_inputs(64, 192, 1, 5, 18)
+    (wa, sa), _ = pw.wino_ref(x[0], wt, bias, relu=True)
+    got = oracle.conv3x3_reflect_wino_f16(x[0], wt, bias, relu=True)
+    assert pw.judge(got, wa, sa, 1e-13, fp16_out=True)[0] <= 1.0
+
+
 # ---- injected defects ---------------------------------------------------------------------------------------------------
+
+def _wino_defect(name, case, defect, mask_of, pool=False, **kw):
+    """Plant `defect` in the emulation of image 0 of `case`, print the whole-map figures and the judge's, and hold the judge to
+    > 1 inside the mask (a boolean map over the output's rows and columns) and <= 1 outside it, against A and against B."""
+    ci, co, b, h, w, up, norelu, cfg = case
+    x, wt, bias = pw.layer_inputs(ci, co, b, h, w)
+    (wa, sa), (wb, sb) = pw.wino_ref(x[0], wt, bias, relu=True, up=up)
+    good = pw.h16(pw.wino_emulate(x[0], wt, bias, up=up))
+    bad = pw.h16(pw.wino_emulate(x[0], wt, bias, up=up, defect=defect, **kw))
+    if pool:
+        good, bad = pw.pool_same(good), pw.pool_same(bad)
+    mask = mask_of(np.zeros(good.shape[:2], bool))
+    assert np.array_equal(good[~mask], bad[~mask]) and not np.array_equal(good[mask], bad[mask])
+    ra = pw.ratios(bad, wa, sa, pw.tau_wino(ci), pool=pool, fp16_out=True)
+    rb = pw.ratios(bad, wb, sb, pw.tau_wino_b(ci), pool=pool, fp16_out=True)
+    at = tuple(int(i) for i in np.unravel_index(int(np.argmax(ra)), ra.shape))
+    print('wino defect %s, %s: A worst %.3g at %s (%.0f %% of the masked elements > 1), elsewhere %.3f; B worst %.3g, elsewhere %.3f; rel_err %.2e, max_rel %.2e'
+          % (name, pw.wino_case_id(case), ra.max(), at, 100 * (ra[mask] > 1).mean(), ra[~mask].max(), rb[mask].max(), rb[~mask].max(),
+             rel_err(bad, good), max_rel(bad, good)))
+    assert ra[mask].max() > 1 and mask[at[:2]] and ra[~mask].max() <= 1
+    assert rb[mask].max() > 1 and rb[~mask].max() <= 1
+    assert pw.ratios(good, wa, sa, pw.tau_wino(ci), pool=pool, fp16_out=True).max() <= 1
+    return ra, mask
+
+
+def _rows_cols(rows=(), cols=()):
+    def mark(m):
+        for r in rows:
+            m[r] = True
+        for c in cols:
+            m[:, c] = True
+        return m
+    return mark
+
+
+WINO_17x33, WINO_UP, WINO_DEEP = pw.WINO_CASES[1], pw.WINO_CASES[2], pw.WINO_CASES[3]
+
+
+def test_wino_defect_1_odd_last_row_pooled_against_its_dropped_partner():
+    """17 rows: pooled row 8 has image row 16 alone; the kernel computes that row's partner y(17) from clamped input rows and
+    must keep it out of the pool.  Here it gets in."""
+    assert WINO_17x33[3:5] == (17, 33)
+    _wino_defect('1 (partner row pooled)', WINO_17x33, 'partner', _rows_cols(rows=[8]), pool=True)
+
+
+def test_wino_defect_2_right_halo_column_clamped():
+    """W = 33: the third tile column holds one pixel, whose right neighbour is the reflection, image column 31; clamped, it is
+    column 32 itself.  Only the last output column may differ."""
+    ra, mask = _wino_defect('2 (right halo clamped)', WINO_17x33, 'clamp_right', _rows_cols(cols=[32]))
+    assert (ra[:, 32].max(axis=1) > 1).all()              # every pixel of the column is named
+
+
+def test_wino_defect_3_upsample_index_halved_before_the_reflection():
+    """9x9 -> 18x18: padded index -1 is upsampled pixel 1 = source pixel 0, and 18 is 16 = source 8; halved first they become
+    source -1 -> 1 and 9 -> 7.  The outermost output ring differs (row 0 through T0 only, row 17 through T3 only)."""
+    assert WINO_UP[5] and WINO_UP[3:5] == (9, 9)
+    _wino_defect('3 (halved before reflected)', WINO_UP, 'halve_first', _rows_cols(rows=[0, 17], cols=[0, 17]))
+
+
+def test_wino_defect_4_one_frequency_with_the_wrong_sign_in_one_tile():
+    """M2 enters the odd output rows of ONE tile with + instead of -: the 16-row tile (0, 1) of 18x31 and the 8-row tile (1, 1)."""
+    def odd_rows(r0, r1, c0, c1):
+        def mark(m):
+            m[r0 + 1:r1:2, c0:c1] = True
+            return m
+        return mark
+    _wino_defect('4 (sign of M2, 16-row tile)', WINO_DEEP, 'sign', odd_rows(0, 16, 16, 31), tile=(0, 1, 16))
+    _wino_defect('4 (sign of M2, 8-row tile)', WINO_DEEP, 'sign', odd_rows(8, 16, 16, 31), tile=(1, 1, 8))
+
 
 def _edge_padded_right(x, w_hwio, b):
     """The layer with the RIGHT border padded by edge replication instead of reflection (float64)."""
