@@ -165,26 +165,34 @@ int upload(wct_ctx* c, const void* host, size_t bytes, void** dev);             
 int pack_conv(wct_ctx* c, const float* w_hwio, const float* b, int cin, int cout, ConvLayer* out);
 
 // ---- api_drivers.hip (device pointers, batch B) ---------------------------
-// One transform by a variant's launcher, launch(mode, stages): AdaIN (stages = 0) in one launch, or the covariance, eigensolve
-// and apply stages, each timed in its class
+// the call block of a launcher on the context's workspace, stream and status words; the caller adds alpha, eps, the outputs
+// and the sweeps (all zero here)
+static inline WctCall ctx_call(wct_ctx* c, int mode, int stages) {
+  WctCall r = {};
+  r.mode = mode; r.stages = stages; r.workspace = c->wct_ws.p; r.workspace_bytes = c->wct_ws.cap;
+  r.eig_fail = c->eig_fail_dev; r.stream = c->stream;
+  return r;
+}
+// One transform by a variant's launcher, launch(ctx_call of the stage): AdaIN (stages = 0) in one launch, or the covariance,
+// eigensolve and apply stages, each timed in its class
 template <typename Launch>
 static int run_stages(wct_ctx* c, size_t ws_bytes, unsigned flags, const StageCost& cost, Launch&& launch) {
   TRY(ensure(c, c->wct_ws, ws_bytes));
   if (flags & WCT_FLAG_ADAIN) {
     ProfScope ps(c, 7, 0, cost.adain_bytes);
-    return launch(0, 0);
+    return launch(ctx_call(c, 0, 0));
   }
   const int mode = (flags & WCT_FLAG_MODE_NP) ? WCT_MODE_NP : WCT_MODE_TF;
   {
     ProfScope ps(c, 4, cost.cov_flops, cost.cov_bytes);
-    TRY(launch(mode, WCT_STAGE_COV));
+    TRY(launch(ctx_call(c, mode, WCT_STAGE_COV)));
   }
   {
     ProfScope ps(c, 5, 0, 0);
-    TRY(launch(mode, WCT_STAGE_EIG));
+    TRY(launch(ctx_call(c, mode, WCT_STAGE_EIG)));
   }
   ProfScope ps(c, 6, cost.apply_flops, cost.apply_bytes);
-  return launch(mode, WCT_STAGE_APPLY);
+  return launch(ctx_call(c, mode, WCT_STAGE_APPLY));
 }
 void level_dims(int H, int W, int level, int* h, int* w);
 int check_min_size(const char* what, int H, int W, int level);

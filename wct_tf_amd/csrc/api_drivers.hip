@@ -140,14 +140,14 @@ int run_decoder(wct_ctx* c, int level, const half_t* feat16, int B, int h, int w
 
 int run_transform(wct_ctx* c, const float* fc, int Nc, const float* fs, int Ns, int C, int P, float alpha, unsigned flags, float eps,
                   half_t* out16, float* out32, int* sweeps_dev, const WctFeatStats* st, const WctStyleRef* prep, const WctWarmRef* warm) {
-  const int shared = (flags & WCT_FLAG_STYLE_SHARED) ? 1 : 0;
+  const WctSkip skip = (flags & WCT_FLAG_STYLE_SHARED) ? WCT_SKIP_SHARED_STYLE : WCT_SKIP_NONE;
   const StageCost cost = {(double)P * 2.0 * C * C * ((double)Nc + Ns), (double)P * 2.0 * ((double)Nc + Ns) * C * 4,
                           (double)P * (2.0 * C * C * Nc + 6.0 * C * C * C), (double)P * Nc * C * (4 + (out16 ? 2 : 0) + (out32 ? 4 : 0)),
                           (double)P * (2.0 * Nc + 2.0 * Ns) * C * 4 + (double)P * Nc * C * 6};
-  return run_stages(c, wct_workspace_bytes(C, Nc, Ns, P), flags, cost, [&](int mode, int stages) {
-    if (!stages) return launch_adain(fc, Nc, fs, Ns, C, P, alpha, 1e-5f, out16, out32, c->wct_ws.p, c->wct_ws.cap, c->stream, shared, st, prep);
-    return launch_wct(fc, Nc, fs, Ns, C, P, alpha, mode, eps, out16, out32, c->wct_ws.p, c->wct_ws.cap, sweeps_dev, stages, c->stream,
-                      shared, c->eig_fail_dev, st, prep, warm);
+  return run_stages(c, wct_workspace_bytes(C, Nc, Ns, P), flags, cost, [&](WctCall r) {
+    r.alpha = alpha; r.eps = r.stages ? eps : 1e-5f; r.out16 = out16; r.out32 = out32; r.sweeps_dev = sweeps_dev;
+    if (!r.stages) return launch_adain(fc, Nc, fs, Ns, C, P, skip, r, st, prep);
+    return launch_wct(fc, Nc, fs, Ns, C, P, skip, r, st, prep, warm);
   });
 }
 
@@ -178,10 +178,10 @@ int run_transform_mix(wct_ctx* c, const float* fc, int Nc, const float* const* f
   // (the mix of the K colouring matrices is timed with the tail it belongs to)
   const StageCost cost = {2.0 * C * C * (Nc + ns), 2.0 * (Nc + ns) * C * 4, 2.0 * C * C * Nc + 6.0 * C * C * C * (K + 1) + 2.0 * C * C * K,
                           (double)Nc * C * (4 + (out16 ? 2 : 0) + (out32 ? 4 : 0)), (2.0 * Nc + 2.0 * ns) * C * 4 + (double)Nc * C * 6};
-  return run_stages(c, wct_mix_workspace_bytes(C, Nc, Ns, K, lambda), flags, cost, [&](int mode, int stages) {
-    if (!stages) return launch_adain_mix(fc, Nc, fs, Ns, K, lambda, C, alpha, 1e-5f, out16, out32, c->wct_ws.p, c->wct_ws.cap, c->stream, st, prep);
-    return launch_wct_mix(fc, Nc, fs, Ns, K, lambda, C, alpha, mode, eps, out16, out32, c->wct_ws.p, c->wct_ws.cap, sweeps_dev, stages,
-                          c->stream, c->eig_fail_dev, st, prep);
+  return run_stages(c, wct_mix_workspace_bytes(C, Nc, Ns, K, lambda), flags, cost, [&](WctCall r) {
+    r.alpha = alpha; r.eps = r.stages ? eps : 1e-5f; r.out16 = out16; r.out32 = out32; r.sweeps_dev = sweeps_dev;
+    if (!r.stages) return launch_adain_mix(fc, Nc, fs, Ns, K, lambda, C, r, st, prep);
+    return launch_wct_mix(fc, Nc, fs, Ns, K, lambda, C, r, st, prep);
   });
 }
 
@@ -212,9 +212,9 @@ int run_transform_masked(wct_ctx* c, const float* fc, int Nc, const MaskGeom& g,
   // (the covariance stage is charged the compaction and gather as well)
   const StageCost cost = {2.0 * C * C * (Nc + ns), (4.0 * Nc + 2.0 * (Nc + ns)) * C * 4, 2.0 * C * C * Nc + 6.0 * C * C * C * P,
                           (double)Nc * C * (4 + (out16 ? 2 : 0) + (out32 ? 4 : 0)), (4.0 * Nc + 2.0 * ns) * C * 4 + (double)Nc * C * 6};
-  return run_stages(c, wct_masked_workspace_bytes(C, Nc, nk, Ns, K), flags, cost, [&](int mode, int stages) {
-    if (!stages) return launch_adain_masked(fc, Nc, g, nk, fs, Ns, K, C, alpha, 1e-5f, out16, out32, c->wct_ws.p, c->wct_ws.cap, c->stream);
-    return launch_wct_masked(fc, Nc, g, nk, fs, Ns, K, C, alpha, mode, eps, out16, out32, c->wct_ws.p, c->wct_ws.cap, sweeps_dev, stages,
-                             c->stream, c->eig_fail_dev);
+  return run_stages(c, wct_masked_workspace_bytes(C, Nc, nk, Ns, K), flags, cost, [&](WctCall r) {
+    r.alpha = alpha; r.eps = r.stages ? eps : 1e-5f; r.out16 = out16; r.out32 = out32; r.sweeps_dev = sweeps_dev;
+    if (!r.stages) return launch_adain_masked(fc, Nc, g, nk, fs, Ns, K, C, r);
+    return launch_wct_masked(fc, Nc, g, nk, fs, Ns, K, C, r);
   });
 }

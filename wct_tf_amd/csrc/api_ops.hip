@@ -76,6 +76,13 @@ extern "C" int wct_transform_warm(wct_ctx* c, const float* content, int Nc, cons
   return transform_pair(c, content, Nc, style, Ns, C, alpha, flags, -1.f, warm, level, out, sweeps_out);
 }
 
+// the call block of the AdaIN ops: fp32 into stage 2
+static WctCall adain_call(wct_ctx* c, float alpha, float epsilon) {
+  WctCall r = ctx_call(c, 0, 0);
+  r.alpha = alpha; r.eps = epsilon; r.out32 = (float*)c->stage[2].p;
+  return r;
+}
+
 extern "C" int wct_adain(wct_ctx* c, const float* content, int Nc, const float* style, int Ns, int C,
                          float alpha, float epsilon, float* out) {
   ARG_CHECK(c && content && style && out);
@@ -85,8 +92,7 @@ extern "C" int wct_adain(wct_ctx* c, const float* content, int Nc, const float* 
   TRY(stage_in(c, 1, style, (size_t)Ns * C * 4, &ds));
   TRY(ensure(c, c->stage[2], (size_t)Nc * C * 4));
   TRY(ensure(c, c->wct_ws, wct_workspace_bytes(C, Nc, Ns, 1)));
-  TRY(launch_adain((float*)dc, Nc, (float*)ds, Ns, C, 1, alpha, epsilon, nullptr, (float*)c->stage[2].p,
-                   c->wct_ws.p, c->wct_ws.cap, c->stream, 0));
+  TRY(launch_adain((float*)dc, Nc, (float*)ds, Ns, C, 1, WCT_SKIP_NONE, adain_call(c, alpha, epsilon), nullptr, nullptr));
   return fetch(c, out, c->stage[2].p, (size_t)Nc * C * 4);
 }
 
@@ -141,8 +147,7 @@ extern "C" int wct_adain_mix(wct_ctx* c, const float* content, int Nc, const flo
   const float* ds[WCT_MIX_MAX];
   TRY(stage_in_multi(c, content, Nc, styles, Ns, K, C, &dc, ds));
   TRY(ensure(c, c->wct_ws, wct_mix_workspace_bytes(C, Nc, Ns, K, lambda)));
-  TRY(launch_adain_mix((float*)dc, Nc, ds, Ns, K, lambda, C, alpha, epsilon, nullptr, (float*)c->stage[2].p,
-                       c->wct_ws.p, c->wct_ws.cap, c->stream));
+  TRY(launch_adain_mix((float*)dc, Nc, ds, Ns, K, lambda, C, adain_call(c, alpha, epsilon), nullptr, nullptr));
   return fetch(c, out, c->stage[2].p, (size_t)Nc * C * 4);
 }
 
@@ -193,8 +198,7 @@ extern "C" int wct_adain_masked(wct_ctx* c, const float* content, int Nc, const 
   const float* ds[WCT_MIX_MAX];
   TRY(stage_in_multi(c, content, Nc, styles, Ns, K, C, &dc, ds));
   TRY(ensure(c, c->wct_ws, wct_masked_workspace_bytes(C, Nc, nk, Ns, K)));
-  TRY(launch_adain_masked((float*)dc, Nc, g, nk, ds, Ns, K, C, alpha, epsilon, nullptr, (float*)c->stage[2].p,
-                          c->wct_ws.p, c->wct_ws.cap, c->stream));
+  TRY(launch_adain_masked((float*)dc, Nc, g, nk, ds, Ns, K, C, adain_call(c, alpha, epsilon)));
   return fetch(c, out, c->stage[2].p, (size_t)Nc * C * 4);
 }
 

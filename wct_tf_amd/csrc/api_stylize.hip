@@ -434,9 +434,9 @@ static int style_fill(wct_ctx* c, wct_style* st, int kind, const std::vector<Sty
     if (hipMemsetAsync(buf, 0, wct_style_state_floats(C) * sizeof(float), c->stream) != hipSuccess) { wct_set_error("hipMemsetAsync failed"); rc = WCT_ERR_HIP; break; }
     if ((rc = ensure(c, c->wct_ws, wct_style_workspace_bytes(C, h * w, n.key)))) break;
     ProfScope ps(c, kind == 2 ? 7 : 5, 0, 0);
-    if ((rc = launch_style_state(taps[n.level], h * w, C, n.key, kind == 2, kind == 1 ? WCT_MODE_NP : WCT_MODE_TF, -1.f, c->wct_ws.p,
-                                 c->wct_ws.cap, c->eig_fail_dev, c->stream, buf)))
-      break;
+    WctCall r = ctx_call(c, kind == 1 ? WCT_MODE_NP : WCT_MODE_TF, WCT_STAGE_ALL);
+    r.eps = -1.f;
+    if ((rc = launch_style_state(taps[n.level], h * w, C, n.key, kind == 2, r, buf))) break;
   }
   if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) { wct_set_error("hipStreamSynchronize failed (prepared style)"); rc = WCT_ERR_HIP; }
   if (!rc) rc = eig_status(c);
@@ -893,12 +893,10 @@ static int stylize_prepared_masked_dev(wct_ctx* c, const void* content, int Hc, 
                             // (the covariance stage is charged the compaction and gather as well; no style rows are read)
                             const StageCost cost = {2.0 * C * C * rows, 6.0 * rows * C * 4, 2.0 * C * C * rows + 6.0 * C * C * C * P,
                                                     rows * C * (4 + 2), 4.0 * rows * C * 4 + rows * C * 6};
-                            TRY(run_stages(c, wct_masked_batch_workspace_bytes(C, Nc, G, gnk, Ns, K), flags, cost, [&](int mode, int stages) {
-                              if (!stages)
-                                return launch_adain_masked_batch(fc, Nc, G, g, gnk, Ns, K, slots, C, alpha, 1e-5f, o16, nullptr, c->wct_ws.p,
-                                                                 c->wct_ws.cap, c->stream);
-                              return launch_wct_masked_batch(fc, Nc, G, g, gnk, Ns, K, slots, C, alpha, mode, -1.f, o16, nullptr, c->wct_ws.p,
-                                                             c->wct_ws.cap, stages, c->stream, c->eig_fail_dev);
+                            TRY(run_stages(c, wct_masked_batch_workspace_bytes(C, Nc, G, gnk, Ns, K), flags, cost, [&](WctCall r) {
+                              r.alpha = alpha; r.eps = r.stages ? -1.f : 1e-5f; r.out16 = o16;
+                              if (!r.stages) return launch_adain_masked_batch(fc, Nc, G, g, gnk, Ns, K, C, r, slots);
+                              return launch_wct_masked_batch(fc, Nc, G, g, gnk, Ns, K, C, r, slots);
                             }));
                             f0 = f1;
                           }

@@ -264,7 +264,7 @@ static void chunked_plan(ChunkedPlan* cp, void* base, int C, int n_full, int n_l
   char* b = (char*)base;
   size_t off = 0;
   cp->tail = SlotPlan{};
-  cp->tail.P = 1; cp->tail.skip = prepared ? WCT_SKIP_STYLE : 0; cp->tail.nwhite = 1;
+  cp->tail.P = 1; cp->tail.skip = prepared ? WCT_SKIP_STYLE : WCT_SKIP_NONE; cp->tail.nwhite = 1;
   if (!prepared) cp->tail.slot[1] = {style, Ns, pair_layout(C, Nc, Ns)};
   plan_carve(&cp->tail, b, C);
   off += align_up(cp->tail.total);
@@ -287,19 +287,19 @@ static void chunked_plan(ChunkedPlan* cp, void* base, int C, int n_full, int n_l
 
 // K >= 2 chunks of content [Nc][C] (Nc = n_full (K - 1) + n_last rows, any size) against one style -- `style` [Ns][C], or a
 // prepared state -- in the stages of launch_wct
-static int launch_wct_chunked(const float* content, int n_full, int n_last, int K, const float* style, int Ns, int C,
-                              float alpha, int mode, float eps_in, half_t* out16, float* out32, void* workspace, size_t workspace_bytes,
-                              int* sweeps_dev, int stages, hipStream_t s, int* eig_fail, const WctStyleRef* prep) {
+static int launch_wct_chunked(const float* content, int n_full, int n_last, int K, const float* style, int Ns, int C, const WctCall& r,
+                              const WctStyleRef* prep) {
+  const int mode = r.mode, stages = r.stages; hipStream_t s = r.stream;
   ARG_CHECK(C % 32 == 0 && C >= 32 && C <= 512 && K >= 2 && K <= CHUNKS_MAX && n_full >= 2 && n_last >= 2 && Ns >= 2 && (style || prep));
   ARG_CHECK(mode == WCT_MODE_NP || mode == WCT_MODE_TF);
   ChunkedPlan cp;
-  chunked_plan(&cp, workspace, C, n_full, n_last, K, style, Ns, prep != nullptr);
-  ARG_CHECK(workspace_bytes >= cp.total);
+  chunked_plan(&cp, r.workspace, C, n_full, n_last, K, style, Ns, prep != nullptr);
+  ARG_CHECK(r.workspace_bytes >= cp.total);
   ARG_CHECK(launch_map_fits((size_t)std::max(n_full, n_last) * C, 4) && plan_fits(cp.tail, C));
   const WctCarve& w = cp.tail.w;
   int rc;
   if (stages & WCT_STAGE_COV) {
-    if (!prep && (rc = launch_plan_stats(cp.tail, C, false, true, cov_eps(mode, eps_in), s))) return rc;
+    if (!prep && (rc = launch_plan_stats(cp.tail, C, false, true, cov_eps(mode, r.eps), s))) return rc;
     hipLaunchKernelGGL(chunk_rows_kernel, dim3(cdiv(K, 256)), dim3(256), 0, s, cp.n, K, n_full, n_last);
     HIP_TRY(hipGetLastError());
     for (int k0 = 0; k0 < K; k0 += WCT_PLAN_PAIRS) {
@@ -318,21 +318,22 @@ static int launch_wct_chunked(const float* content, int n_full, int n_last, int 
       HIP_TRY(hipMemcpyAsync(cp.scales + k0, gp.w.scale, (size_t)G * sizeof(float), hipMemcpyDeviceToDevice, s));
     }
     hipLaunchKernelGGL(pool_finish_kernel, dim3(C), dim3(C), 0, s, (const double*)cp.acc, (const float*)cp.means, (const float*)cp.scales,
-                       (const int*)cp.n, K, C, cov_eps(mode, eps_in), w.mean, w.A, w.A0, w.scale);
+                       (const int*)cp.n, K, C, cov_eps(mode, r.eps), w.mean, w.A, w.A0, w.scale);
     HIP_TRY(hipGetLastError());
   }
-  if ((stages & WCT_STAGE_EIG) && (rc = launch_eig_stage(w, C, 1, cp.tail.skip, 1, sweeps_dev, eig_fail, s))) return rc;
+  if ((stages & WCT_STAGE_EIG) && (rc = launch_eig_stage(w, C, 1, cp.tail.skip, 1, r.sweeps_dev, r.eig_fail, s))) return rc;
   if (!(stages & WCT_STAGE_APPLY)) return WCT_OK;
   if (prep) {
     WctStyleSlots slots = {};
     slots.state[0] = prep->state[0];
     if ((rc = launch_style_load_slots(slots, 1, w, C, true, s))) return rc;
   }
-  if ((rc = launch_spectral_tail(w, C, 1, alpha, mode, eps_in, cp.tail.skip, 1, s))) return rc;
-  if ((rc = launch_blend(w, C, 1, alpha, cp.tail.skip, s))) return rc;
+  if ((rc = launch_spectral_tail(w, C, 1, r.alpha, mode, r.eps, cp.tail.skip, 1, s))) return rc;
+  if ((rc = launch_blend(w, C, 1, r.alpha, cp.tail.skip, s))) return rc;
   for (int k = 0; k < K; ++k) {
     const size_t at = (size_t)k * n_full * C;
-    if ((rc = launch_apply(w, content + at, k == K - 1 ? n_last : n_full, C, 1, out16 ? out16 + at : nullptr, out32 ? out32 + at : nullptr, s))) return rc;
+    if ((rc = launch_apply(w, content + at, k == K - 1 ? n_last : n_full, C, 1, r.out16 ? r.out16 + at : nullptr, r.out32 ? r.out32 + at : nullptr, s)))
+      return rc;
   }
   return WCT_OK;
 }
@@ -351,8 +352,8 @@ int run_transform_chunked(wct_ctx* c, const float* fc, size_t Nc, int n_full, in
   const double rows = (double)Nc;
   const StageCost cost = {2.0 * C * C * (rows + (prep ? 0 : Ns)), 2.0 * (rows + (prep ? 0 : Ns)) * C * 4, 2.0 * C * C * rows + 6.0 * C * C * C,
                           rows * C * (4 + (out16 ? 2 : 0) + (out32 ? 4 : 0)), 0};
-  return run_stages(c, cp.total, flags, cost, [&](int mode, int stages) {
-    return launch_wct_chunked(fc, n_full, n_last, K, fs, Ns, C, alpha, mode, eps, out16, out32, c->wct_ws.p, c->wct_ws.cap,
-                              sweeps_dev, stages, c->stream, c->eig_fail_dev, prep);
+  return run_stages(c, cp.total, flags, cost, [&](WctCall r) {
+    r.alpha = alpha; r.eps = eps; r.out16 = out16; r.out32 = out32; r.sweeps_dev = sweeps_dev;
+    return launch_wct_chunked(fc, n_full, n_last, K, fs, Ns, C, r, prep);
   });
 }

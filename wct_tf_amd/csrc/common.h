@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
+#include "skip_rule.h"
 
 typedef _Float16 half_t;
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
@@ -171,8 +172,7 @@ struct GemmArgs {
   // round 5 (the transform tail in merged launches over the 2P matrices of a level, batch b = matrix 2 * pair + side):
   const float* A_odd;     // if set: A of an odd batch b is A_odd + (b >> 1) * sA_odd, that of an even one A + (b >> 1) * sA
   size_t sA_odd;
-  int skip_shared;        // batches b with skip_style_mat(b, skip_shared) have nothing to do (1: one style for all pairs,
-                          // WCT_FLAG_STYLE_SHARED; 2: one content for a style mix, launch_wct_mix; 3 .. 5: prepared styles)
+  WctSkip skip;           // batches b with skip_style_mat(b, skip) have nothing to do (skip_rule.h; WCT_SKIP_NONE: a plain batch)
   // blend epilogue (T = Tcs Tw -> M = alpha T + (1 - alpha) I, ops.py:83 folded into the apply matrix): the store carries the
   // blend and the block merges max |M| into mabs[batch] (bit patterns of non-negative floats; zeroed by an earlier kernel)
   int blend; float alpha; unsigned* mabs;
@@ -197,9 +197,6 @@ struct WctStyleKey { int nslab, nsplit, ksplit; };
 WctStyleKey wct_style_key(int C, int Nc, int Ns);
 size_t wct_style_state_floats(int C);
 size_t wct_style_workspace_bytes(int C, int Ns, const WctStyleKey& key);
-// the state of `style` [Ns][C] under `key`: launch_wct's style side alone (adain: launch_adain's), bit for bit
-int launch_style_state(const float* style, int Ns, int C, const WctStyleKey& key, int adain, int mode, float eps, void* workspace,
-                       size_t workspace_bytes, int* eig_fail, hipStream_t s, float* state);
 // the states a transform takes in place of its style features (`prep` below): state[0], or state[k] for style k of a mix.  The
 // style pointers may then be null; Ns still names the styles' rows (the content's layout depends on them).
 struct WctStyleRef { const float* state[8]; };
@@ -210,27 +207,36 @@ struct WctStyleSlots { const float* state[32]; };
 // re-orthonormalised eigenvectors of the call's LAST content matrix either way
 struct WctWarmRef { float* basis; int valid; };
 
-// P independent whiten-colour transforms on `s`:  out = blend(T (x - mc) + ms)
-// content [P][Nc][C], style [P][Ns][C]; out16/out32 [P][Nc][C] (either may be null).
-size_t wct_workspace_bytes(int C, int Nc, int Ns, int P);
-int launch_wct(const float* content, int Nc, const float* style, int Ns, int C, int P,
-               float alpha, int mode, float eps /* <0: reference default */, half_t* out16, float* out32,
-               void* workspace, size_t workspace_bytes, int* sweeps_dev, int stages, hipStream_t s,
-               int shared_style /* style holds ONE feature map used by all P pairs: its statistics and
-                                   eigensystem are computed once */,
-               int* eig_fail /* device-visible status words: [2] (not converged, non-finite), bumped by the eigensolver,
-                                then [6 size classes][3] solver statistics; or null */,
-               const struct WctFeatStats* stats = nullptr /* unit sums / maxima a conv epilogue left beside the features */,
-               const struct WctStyleRef* prep = nullptr /* one prepared style for all P pairs (shared_style is ignored) */,
-               const struct WctWarmRef* warm = nullptr /* start the P content eigensolves from a stored basis (plain pairs or a
-                                                          prepared style only) */);
+// The call block of a transform launcher: what every one of them takes besides its features and their geometry.  The drivers
+// (api.h: run_stages) fill workspace, stream, eig_fail, mode and stages from the context, their callers the rest.
+struct WctCall {
+  float alpha; int mode;    // mode: WCT_MODE_NP / WCT_MODE_TF (unused by the AdaIN launchers, as are stages and sweeps_dev)
+  float eps;                // < 0: the reference default; the AdaIN launchers: AdaIN's epsilon
+  half_t* out16; float* out32;   // the outputs, either may be null
+  void* workspace; size_t workspace_bytes;
+  int* sweeps_dev;          // device: the sweeps of every solved matrix, or null
+  int stages;               // WCT_STAGE_* of this call
+  int* eig_fail;            // device-visible status words: [2] (not converged, non-finite), bumped by the eigensolver, then
+                            // [6 size classes][3] solver statistics; or null
+  hipStream_t stream;
+};
 // WCT_STAGE_EIG_FP32UPDATE (with WCT_STAGE_EIG): the eigensolver's tile updates on fp32 MFMA instead of split fp16 -- style-swap, whose
 // patch matching is an argmax over the whitened features (csrc/jacobi_dev.h r4::fused_u)
 enum { WCT_STAGE_COV = 1, WCT_STAGE_EIG = 2, WCT_STAGE_APPLY = 4, WCT_STAGE_ALL = 7, WCT_STAGE_EIG_FP32UPDATE = 8 };
-int launch_adain(const float* content, int Nc, const float* style, int Ns, int C, int P,
-                 float alpha, float eps, half_t* out16, float* out32,
-                 void* workspace, size_t workspace_bytes, hipStream_t s, int shared_style,
-                 const struct WctFeatStats* stats = nullptr, const struct WctStyleRef* prep = nullptr);
+
+// the state of `style` [Ns][C] under `key`: launch_wct's style side alone (adain: launch_adain's), bit for bit
+int launch_style_state(const float* style, int Ns, int C, const WctStyleKey& key, int adain, const WctCall& r, float* state);
+
+// P independent whiten-colour transforms:  out = blend(T (x - mc) + ms); content [P][Nc][C], style [P][Ns][C]; out16/out32 [P][Nc][C].
+// skip: WCT_SKIP_NONE, or WCT_SKIP_SHARED_STYLE -- style holds ONE feature map used by all P pairs, its statistics and eigensystem
+// are computed once.  stats: unit sums / maxima a conv epilogue left beside the features.  prep: one prepared style for all P pairs
+// (skip is then ignored; style may be null).  warm: start the P content eigensolves from a stored basis (plain pairs or a prepared
+// style only).  Each of the three may be null.
+size_t wct_workspace_bytes(int C, int Nc, int Ns, int P);
+int launch_wct(const float* content, int Nc, const float* style, int Ns, int C, int P, WctSkip skip, const WctCall& r,
+               const WctFeatStats* stats, const WctStyleRef* prep, const WctWarmRef* warm);
+int launch_adain(const float* content, int Nc, const float* style, int Ns, int C, int P, WctSkip skip, const WctCall& r,
+                 const WctFeatStats* stats, const WctStyleRef* prep);
 // Style mix (Li et al. 2017, sec. 4.2): out = sum_k lambda[k] T(content, styles[k]) for K <= WCT_MIX_MAX styles of any sizes
 // Ns[k]; lambda[k] in [0, 1] summing to 1 (normalised by the caller).  One content whitening, K colourings mixed before ONE
 // blend product and apply.  sweeps_dev [2K]: slot 2k + 1 style k, slot 0 the content (the even slots k >= 1 read 0).  stats:
@@ -238,12 +244,9 @@ int launch_adain(const float* content, int Nc, const float* style, int Ns, int C
 enum { WCT_MIX_MAX = 8 };
 size_t wct_mix_workspace_bytes(int C, int Nc, const int* Ns, int K, const float* lambda);
 int launch_wct_mix(const float* content, int Nc, const float* const* styles, const int* Ns, int K, const float* lambda, int C,
-                   float alpha, int mode, float eps, half_t* out16, float* out32, void* workspace, size_t workspace_bytes,
-                   int* sweeps_dev, int stages, hipStream_t s, int* eig_fail, const struct WctFeatStats* stats = nullptr,
-                   const struct WctStyleRef* prep = nullptr);
+                   const WctCall& r, const WctFeatStats* stats, const WctStyleRef* prep);
 int launch_adain_mix(const float* content, int Nc, const float* const* styles, const int* Ns, int K, const float* lambda, int C,
-                     float alpha, float eps, half_t* out16, float* out32, void* workspace, size_t workspace_bytes, hipStream_t s,
-                     const struct WctFeatStats* stats = nullptr, const struct WctStyleRef* prep = nullptr);
+                     const WctCall& r, const WctFeatStats* stats, const WctStyleRef* prep);
 // Spatial control (Li et al. 2017, sec. 4.2): K <= WCT_MIX_MAX labelled regions of one content, region k transformed with style k
 // alone.  Row r = (i, j) of an h x w feature map has the label mask[min(i * stride, Hm - 1)][min(j * stride, Wm - 1)] of the
 // Hm x Wm label map (the content's, at stride 2^(level - 1)).  nk[k]: the rows of label k, counted by the caller (they size
@@ -255,28 +258,25 @@ size_t mask_compact_workspace_bytes(int N, int G = 1);
 int launch_mask_compact(const MaskGeom& g, int N, int K, int* perm, int* seg_off, void* workspace, hipStream_t s);
 size_t wct_masked_workspace_bytes(int C, int Nc, const int* nk, const int* Ns, int K);
 int launch_wct_masked(const float* content, int Nc, const MaskGeom& g, const int* nk, const float* const* styles, const int* Ns, int K,
-                      int C, float alpha, int mode, float eps, half_t* out16, float* out32, void* workspace, size_t workspace_bytes,
-                      int* sweeps_dev, int stages, hipStream_t s, int* eig_fail);
+                      int C, const WctCall& r);
 int launch_adain_masked(const float* content, int Nc, const MaskGeom& g, const int* nk, const float* const* styles, const int* Ns, int K,
-                        int C, float alpha, float eps, half_t* out16, float* out32, void* workspace, size_t workspace_bytes, hipStream_t s);
+                        int C, const WctCall& r);
 // Spatial control of G <= 32 frames on prepared styles, one launch of every stage for all of them: content and out16 / out32
 // [G][Nc][C], g.mask [G][Hm][Wm] (one label map per frame), nk [G][WCT_MIX_MAX] the rows of every label of every frame.  The
 // live (frame, label) pairs -- nk >= 2, in frame-major order, at most 32 of them -- take the content side alone; pair p's style
 // side is states.state[p], the state of style k under wct_style_key(C, nk, Ns[k]).  Frame f comes out as launch_wct_masked /
-// launch_adain_masked give it alone, bit for bit.
+// launch_adain_masked give it alone, bit for bit.  (sweeps_dev is not served.)
 size_t wct_masked_batch_workspace_bytes(int C, int Nc, int G, const int* nk, const int* Ns, int K);
 int wct_masked_batch_pairs(int G, const int* nk, int K);
 int launch_mask_compact_batch(const MaskGeom& g, int N, int K, int G, int* perm, int* seg_off, void* workspace, hipStream_t s);
-int launch_wct_masked_batch(const float* content, int Nc, int G, const MaskGeom& g, const int* nk, const int* Ns, int K,
-                            const WctStyleSlots& states, int C, float alpha, int mode, float eps, half_t* out16, float* out32,
-                            void* workspace, size_t workspace_bytes, int stages, hipStream_t s, int* eig_fail);
-int launch_adain_masked_batch(const float* content, int Nc, int G, const MaskGeom& g, const int* nk, const int* Ns, int K,
-                              const WctStyleSlots& states, int C, float alpha, float eps, half_t* out16, float* out32,
-                              void* workspace, size_t workspace_bytes, hipStream_t s);
+int launch_wct_masked_batch(const float* content, int Nc, int G, const MaskGeom& g, const int* nk, const int* Ns, int K, int C,
+                            const WctCall& r, const WctStyleSlots& states);
+int launch_adain_masked_batch(const float* content, int Nc, int G, const MaskGeom& g, const int* nk, const int* Ns, int K, int C,
+                              const WctCall& r, const WctStyleSlots& states);
 // Symmetric eigensolver (batched): A [nmat][C][C] is overwritten (diag -> eigenvalues),
 // V [nmat][C][C] gets eigenvectors in columns.  C multiple of 32, 32 <= C <= 1024.
 // sweeps_done_dev[m]: sweeps used (> 0) if matrix m converged, -sweeps if it was still rotating when the sweep
-// budget ran out, <= -1000 for non-finite input; eig_fail as in launch_wct.
+// budget ran out, <= -1000 for non-finite input; eig_fail as in WctCall.
 int launch_jacobi_eigh(float* A, float* V, int C, int nmat, void* workspace,
                        size_t workspace_bytes, int* sweeps_done_dev, int* eig_fail, hipStream_t s);
 size_t jacobi_workspace_bytes(int C, int nmat);

@@ -643,27 +643,27 @@ __global__ __launch_bounds__(256) void jacobi_gather_kernel(float* A, const floa
 
 constexpr int JACOBI_ROWSUM_MAX = 1024;                // words of row sums per matrix (C <= 1024; see JACOBI_ROW_K below)
 // mat0 = index of the first matrix in the 2P batch (0: a solve takes the whole batch); skipped style matrices start out `done`
-__global__ __launch_bounds__(256) void jacobi_init_kernel(const float* A, float* V, JacobiState* st, int C, int mat0, int shared_style, unsigned* rowsum) {
+__global__ __launch_bounds__(256) void jacobi_init_kernel(const float* A, float* V, JacobiState* st, int C, int mat0, int skip, unsigned* rowsum) {
   __shared__ float red[4];
   const int m = blockIdx.y;
-  const bool skip = skip_style_mat(mat0 + m, shared_style);
+  const bool dead = skip_style_mat(mat0 + m, skip);
   const size_t cc = (size_t)C * C;
-  if (!skip)
+  if (!dead)
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < cc; i += (size_t)gridDim.x * blockDim.x)
       V[(size_t)m * cc + i] = (i / C == i % C) ? 1.f : 0.f;
   if (blockIdx.x == 0) {
     for (int i = threadIdx.x; i < C; i += 256) rowsum[(size_t)m * JACOBI_ROWSUM_MAX + i] = 0u;      // (jacobi_resid_kernel adds, jacobi_check_kernel clears)
     float mx = 0.f;                          // NaN diagonals drop out of fmaxf; the pair kernels flag them
-    if (!skip) for (int i = threadIdx.x; i < C; i += 256) mx = fmaxf(mx, fabsf(A[(size_t)m * cc + (size_t)i * C + i]));
+    if (!dead) for (int i = threadIdx.x; i < C; i += 256) mx = fmaxf(mx, fabsf(A[(size_t)m * cc + (size_t)i * C + i]));
     for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mx;
     __syncthreads();
     if (threadIdx.x == 0) {
       mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
       JacobiState z;
-      z.offmax = 0u; z.done = skip ? 1 : 0; z.sweeps = 0; z.offsig = 0u;
+      z.offmax = 0u; z.done = dead ? 1 : 0; z.sweeps = 0; z.offsig = 0u;
       z.floor = JACOBI_SIG_FLOOR * fminf(mx, 3.0e38f); z.last_sig = 0u; z.dmax = 0u; z.r2 = -1.f; z.r2l = -1.f; z.pad = 0;
-      z.seg_stop = skip ? 0 : 0x7fffffff; z.pad2 = 0;
+      z.seg_stop = dead ? 0 : 0x7fffffff; z.pad2 = 0;
       st[m] = z;
     }
   }
@@ -957,7 +957,7 @@ struct JacobiGroup {
   int vstrip;                                // V is updated per segment by jacobi_vstrip_kernel on the side stream `vs`
   hipStream_t vs; hipEvent_t ev_seg, ev_v[2];// main -> side (segment enqueued), side -> main (log buffer free again)
   bool v_busy[2];
-  int shared_style;            // position in a WCT batch (skip_style_mat); 0 for a plain batch
+  WctSkip skip;                // position in a WCT batch (skip_style_mat); WCT_SKIP_NONE for a plain batch
   float tol_fn;                // > 0: also stop on the measured residual (callers that complete f(A) to first order)
   int* fail;                   // device view of the caller's failure words [2], or null
   int* stats;                  // device view of the caller's statistics slot [3] for matrices of this size class, or null
@@ -1101,7 +1101,7 @@ static int jacobi_run_fused(JacobiGroup& G, int C) {
   G.vstrip = host && M2 == 64 && (nblk == 8 || nblk == 16) && G.nmat >= JACOBI_VSTRIP_MIN;
   if (G.vstrip) { G.vs = host->vs; G.ev_seg = host->ev_seg; G.ev_v[0] = host->ev_v[0]; G.ev_v[1] = host->ev_v[1]; }
   G.done_host = host ? host->flags_dev : nullptr;
-  hipLaunchKernelGGL(jacobi_init_kernel, dim3(64, G.nmat), dim3(256), 0, G.stream, G.A, G.V, G.st, C, 0, G.shared_style,
+  hipLaunchKernelGGL(jacobi_init_kernel, dim3(64, G.nmat), dim3(256), 0, G.stream, G.A, G.V, G.st, C, 0, (int)G.skip,
                      reinterpret_cast<unsigned*>(G.resid + (size_t)G.nmat * JACOBI_RESID_MAXTILES * JACOBI_RESID_STRIDE));
   HIP_TRY(hipGetLastError());
   bool pending = false;
@@ -1170,7 +1170,7 @@ static int jacobi_make_group(JacobiGroup* G, float* A, float* V, int C, int nmat
   G->resid = reinterpret_cast<float*>(reinterpret_cast<char*>(G->st) + (((size_t)nmat * sizeof(JacobiState) + 255) / 256) * 256);
   G->tol_fn = 0.f;
   G->stream = s; G->sweeps_out = sweeps_out; G->fail = eig_fail; G->stats = jacobi_stats_slot(eig_fail, C);
-  G->shared_style = 0;
+  G->skip = WCT_SKIP_NONE;
   return WCT_OK;
 }
 
@@ -1193,10 +1193,10 @@ int launch_jacobi_eigh(float* A, float* V, int C, int nmat, void* workspace, siz
 }
 
 // the eigensolve stage of a transform: the 2P matrices of w in one batched solve, minus those the skip mode drops
-int launch_eig_stage(const WctCarve& w, int C, int P, int skip, int u_f16, int* sweeps_dev, int* eig_fail, hipStream_t s, int check_from) {
+int launch_eig_stage(const WctCarve& w, int C, int P, WctSkip skip, int u_f16, int* sweeps_dev, int* eig_fail, hipStream_t s, int check_from) {
   JacobiGroup G;
   int rc;
   if ((rc = jacobi_make_group(&G, w.A, w.V, C, 2 * P, w.jacobi_ws, w.jacobi_bytes, sweeps_dev, eig_fail, s))) return rc;
-  G.shared_style = skip; G.tol_fn = JACOBI_TOL_FN_WCT; G.u_f16 = u_f16; G.check_from = check_from;
+  G.skip = skip; G.tol_fn = JACOBI_TOL_FN_WCT; G.u_f16 = u_f16; G.check_from = check_from;
   return jacobi_dispatch(G, C);
 }

@@ -173,9 +173,24 @@ int launch_mask_compact(const MaskGeom& g, int N, int K, int* perm, int* seg_off
 // 2p + 1 its style, both with the layout of the single pair (nk[k], Ns[k]).  C as in mix_plan; styles may be null (the
 // workspace size alone).  False for arguments no masked transform takes.
 struct MaskPlan : SlotPlan {
-  int lab[WCT_MIX_MAX], nmax; unsigned single;   // the label of pair p; the most rows of a pair; bit k: label k has 1 row
+  int lab[WCT_MIX_MAX], nmax;                    // the label of pair p; the most rows of a pair
+  SingleLabels single; bool any_single;          // frame 0, bit k: label k has 1 row
   float* xg; int *perm, *seg_off; void* compact_ws;
 };
+
+// what a masked plan of G frames lays out behind its transform workspace: the gathered rows, the partition, the compaction's scratch
+template <typename Plan>
+static void mask_carve(Plan* m, void* base, int Cw, int Nc, int G) {
+  plan_carve(m, base, Cw);
+  size_t off = m->total;
+  char* b = reinterpret_cast<char*>(base);
+  auto take = [&](size_t bytes) { void* q = b ? b + off : nullptr; off += align_up(bytes); return q; };
+  m->xg = (float*)take((size_t)G * Nc * Cw * sizeof(float));
+  m->perm = (int*)take((size_t)G * Nc * sizeof(int));
+  m->seg_off = (int*)take((size_t)G * SEG_STRIDE * sizeof(int));
+  m->compact_ws = take(mask_compact_workspace_bytes(Nc, G));
+  m->total = off;
+}
 
 static bool mask_plan(MaskPlan* m, void* base, int C, int Nc, const int* nk, const float* const* styles, const int* Ns, int K,
                       int nmin) {
@@ -192,7 +207,7 @@ static bool mask_plan(MaskPlan* m, void* base, int C, int Nc, const int* nk, con
   for (int k = 0; k < K; ++k) {
     row0[k] = row;
     row += nk[k];
-    if (nk[k] == 1) m->single |= 1u << k;
+    if (nk[k] == 1) { m->single.frame[0] |= (unsigned char)(1u << k); m->any_single = true; }
     if (nk[k] < 2) continue;
     const int p = m->P++;
     m->lab[p] = k;
@@ -202,15 +217,7 @@ static bool mask_plan(MaskPlan* m, void* base, int C, int Nc, const int* nk, con
     m->slot[2 * p + 1] = {styles ? styles[k] : nullptr, Ns[k], lay};
   }
   m->nwhite = m->P;
-  plan_carve(m, base, Cw);
-  size_t off = m->total;
-  char* b = reinterpret_cast<char*>(base);
-  auto take = [&](size_t bytes) { void* q = b ? b + off : nullptr; off += align_up(bytes); return q; };
-  m->xg = (float*)take((size_t)Nc * Cw * sizeof(float));
-  m->perm = (int*)take((size_t)Nc * sizeof(int));
-  m->seg_off = (int*)take((WCT_MIX_MAX + 1) * sizeof(int));
-  m->compact_ws = take(mask_compact_workspace_bytes(Nc));
-  m->total = off;
+  mask_carve(m, base, Cw, Nc, 1);
   if (m->xg)
     for (int p = 0; p < m->P; ++p) m->slot[2 * p].x = m->xg + (size_t)row0[m->lab[p]] * C;
   return true;
@@ -221,53 +228,52 @@ size_t wct_masked_workspace_bytes(int C, int Nc, const int* nk, const int* Ns, i
   return mask_plan(&m, nullptr, C, Nc, nk, nullptr, Ns, K, 1) ? m.total : 0;
 }
 
-// compaction and gather of a masked level (the first stage of both masked transforms)
-static int launch_mask_gather(const float* content, const MaskGeom& g, int Nc, int K, int C, const MaskPlan& m, hipStream_t s) {
+// compaction and gather of the G frames of a masked level (the first stage of every masked transform)
+template <typename Plan>
+static int launch_mask_gather(const float* content, const MaskGeom& g, int Nc, int K, int C, const Plan& m, int G, hipStream_t s) {
   int rc;
-  if ((rc = launch_mask_compact(g, Nc, K, m.perm, m.seg_off, m.compact_ws, s))) return rc;
-  hipLaunchKernelGGL(mask_gather_kernel, dim3(rows_grid(Nc, C)), dim3(256), 0, s, content, (const int*)m.perm, (const int*)m.seg_off, K, C,
+  if ((rc = launch_mask_compact_batch(g, Nc, K, G, m.perm, m.seg_off, m.compact_ws, s))) return rc;
+  hipLaunchKernelGGL(mask_gather_kernel, dim3(rows_grid(Nc, C), G), dim3(256), 0, s, content, (const int*)m.perm, (const int*)m.seg_off, K, C,
                      Nc, m.xg);
   HIP_TRY(hipGetLastError());
   return WCT_OK;
 }
 
-static int launch_mask_passthrough(const float* content, int Nc, int C, const MaskPlan& m, int K, half_t* out16, float* out32, hipStream_t s) {
-  if (!m.single) return WCT_OK;
-  SingleLabels labs = {};
-  labs.frame[0] = (unsigned char)m.single;
-  hipLaunchKernelGGL(mask_passthrough_kernel, dim3(K), dim3(256), 0, s, content, (const int*)m.seg_off, (const int*)m.perm, labs,
+// the single-pixel labels of the G frames of a masked plan pass through
+template <typename Plan>
+static int launch_mask_passthrough(const float* content, int Nc, int C, const Plan& m, int G, int K, half_t* out16, float* out32, hipStream_t s) {
+  if (!m.any_single) return WCT_OK;
+  hipLaunchKernelGGL(mask_passthrough_kernel, dim3(K, G), dim3(256), 0, s, content, (const int*)m.seg_off, (const int*)m.perm, m.single,
                      C, Nc, out16, out32);
   HIP_TRY(hipGetLastError());
   return WCT_OK;
 }
 
 int launch_wct_masked(const float* content, int Nc, const MaskGeom& g, const int* nk, const float* const* styles, const int* Ns, int K,
-                      int C, float alpha, int mode, float eps_in, half_t* out16, float* out32, void* workspace, size_t workspace_bytes,
-                      int* sweeps_dev, int stages, hipStream_t s, int* eig_fail) {
+                      int C, const WctCall& r) {
+  const int mode = r.mode, stages = r.stages; hipStream_t s = r.stream;
   MaskPlan m;
-  ARG_CHECK(C % 32 == 0 && C >= 32 && C <= 1024 && content && styles && mask_plan(&m, workspace, C, Nc, nk, styles, Ns, K, 2));
+  ARG_CHECK(C % 32 == 0 && C >= 32 && C <= 1024 && content && styles && mask_plan(&m, r.workspace, C, Nc, nk, styles, Ns, K, 2));
   ARG_CHECK(mode == WCT_MODE_NP || mode == WCT_MODE_TF);
   ARG_CHECK(launch_map_fits((size_t)Nc * C, 4) && plan_fits(m, C));
-  ARG_CHECK(workspace_bytes >= m.total);
+  ARG_CHECK(r.workspace_bytes >= m.total);
   const WctCarve& w = m.w;
   int rc;
   if (stages & WCT_STAGE_COV) {
-    if ((rc = launch_mask_gather(content, g, Nc, K, C, m, s))) return rc;
-    if ((rc = launch_plan_stats(m, C, false, true, cov_eps(mode, eps_in), s))) return rc;
+    if ((rc = launch_mask_gather(content, g, Nc, K, C, m, 1, s))) return rc;
+    if ((rc = launch_plan_stats(m, C, false, true, cov_eps(mode, r.eps), s))) return rc;
   }
-  if ((stages & WCT_STAGE_EIG) && m.P > 0 && (rc = launch_eig_stage(w, C, m.P, m.skip, 1, sweeps_dev, eig_fail, s))) return rc;
+  if ((stages & WCT_STAGE_EIG) && m.P > 0 && (rc = launch_eig_stage(w, C, m.P, m.skip, 1, r.sweeps_dev, r.eig_fail, s))) return rc;
   if (!(stages & WCT_STAGE_APPLY)) return WCT_OK;
   if (m.P > 0) {
-    if ((rc = launch_spectral_tail(w, C, m.P, alpha, mode, eps_in, m.skip, m.nwhite, s))) return rc;
-    if ((rc = launch_blend(w, C, m.P, alpha, 0, s))) return rc;
-    ApplySegArgs a;
-    a.x = m.xg; a.N = 0; a.C = C; a.mean = w.mean; a.M = w.M; a.bias = w.bias;
-    a.xscale = w.scale; a.mabs = w.mabs; a.out16 = out16; a.out32 = out32;
+    if ((rc = launch_spectral_tail(w, C, m.P, r.alpha, mode, r.eps, m.skip, m.nwhite, s))) return rc;
+    if ((rc = launch_blend(w, C, m.P, r.alpha, m.skip, s))) return rc;
+    ApplySegArgs a = apply_args<ApplySegArgs>(w, m.xg, 0, C, r.out16, r.out32);
     a.seg_off = m.seg_off; a.perm = m.perm;
     for (int p = 0; p < WCT_MIX_MAX; ++p) a.lab[p] = m.lab[p];           // (0 past the pairs)
-    if ((rc = launch_apply_seg(a, m.nmax, m.P, s))) return rc;
+    if ((rc = launch_apply_args(a, m.nmax, m.P, s))) return rc;
   }
-  return launch_mask_passthrough(content, Nc, C, m, K, out16, out32, s);
+  return launch_mask_passthrough(content, Nc, C, m, 1, K, r.out16, r.out32, s);
 }
 
 // AdaIN of the segments: as adain_apply_kernel (same expression, so the same bits) on pair p = label lab[p], rows read from the
@@ -319,22 +325,23 @@ __global__ void adain_seg_apply_kernel(const float* xg, const int* seg_off, cons
 }
 
 int launch_adain_masked(const float* content, int Nc, const MaskGeom& g, const int* nk, const float* const* styles, const int* Ns, int K,
-                        int C, float alpha, float eps, half_t* out16, float* out32, void* workspace, size_t workspace_bytes, hipStream_t s) {
+                        int C, const WctCall& r) {
+  hipStream_t s = r.stream;
   MaskPlan m;
-  ARG_CHECK(C % 4 == 0 && C <= 1024 && content && styles && mask_plan(&m, workspace, C, Nc, nk, styles, Ns, K, 1));
-  ARG_CHECK(workspace_bytes >= m.total);
+  ARG_CHECK(C % 4 == 0 && C <= 1024 && content && styles && mask_plan(&m, r.workspace, C, Nc, nk, styles, Ns, K, 1));
+  ARG_CHECK(r.workspace_bytes >= m.total);
   const WctCarve& w = m.w;
   int rc;
-  if ((rc = launch_mask_gather(content, g, Nc, K, C, m, s))) return rc;
+  if ((rc = launch_mask_gather(content, g, Nc, K, C, m, 1, s))) return rc;
   if ((rc = launch_plan_stats(m, C, true, false, 0.f, s))) return rc;
   if (m.P > 0) {
     SegLabels sl;
     for (int p = 0; p < WCT_MIX_MAX; ++p) sl.lab[p] = m.lab[p];
     hipLaunchKernelGGL(adain_seg_apply_kernel<SegLabels>, dim3(rows_grid(m.nmax, C), m.P), dim3(256), 0, s, (const float*)m.xg, (const int*)m.seg_off,
-                       (const int*)m.perm, sl, C, (const float*)w.mean, (const float*)w.var, alpha, eps, out16, out32);
+                       (const int*)m.perm, sl, C, (const float*)w.mean, (const float*)w.var, r.alpha, r.eps, r.out16, r.out32);
     HIP_TRY(hipGetLastError());
   }
-  return launch_mask_passthrough(content, Nc, C, m, K, out16, out32, s);
+  return launch_mask_passthrough(content, Nc, C, m, 1, K, r.out16, r.out32, s);
 }
 
 // ---------------------------------------------------------------------------
@@ -388,15 +395,7 @@ static bool mask_batch_plan(MaskBatchPlan* m, void* base, int C, int Nc, int G, 
   }
   m->skip = WCT_SKIP_STYLES;
   m->nwhite = m->P;
-  plan_carve(m, base, Cw);
-  size_t off = m->total;
-  char* b = reinterpret_cast<char*>(base);
-  auto take = [&](size_t bytes) { void* q = b ? b + off : nullptr; off += align_up(bytes); return q; };
-  m->xg = (float*)take((size_t)G * Nc * Cw * sizeof(float));
-  m->perm = (int*)take((size_t)G * Nc * sizeof(int));
-  m->seg_off = (int*)take((size_t)G * SEG_STRIDE * sizeof(int));
-  m->compact_ws = take(mask_compact_workspace_bytes(Nc, G));
-  m->total = off;
+  mask_carve(m, base, Cw, Nc, G);
   if (m->xg)
     for (int p = 0; p < m->P; ++p) m->slot[2 * p].x = m->xg + ((size_t)seg_frame(m->fl[p]) * Nc + row0[p]) * C;
   return true;
@@ -407,65 +406,45 @@ size_t wct_masked_batch_workspace_bytes(int C, int Nc, int G, const int* nk, con
   return mask_batch_plan(&m, nullptr, C, Nc, G, nk, Ns, K, 1) ? m.total : 0;
 }
 
-static int launch_mask_batch_gather(const float* content, const MaskGeom& g, int Nc, int K, int C, const MaskBatchPlan& m, hipStream_t s) {
-  int rc;
-  if ((rc = launch_mask_compact_batch(g, Nc, K, m.G, m.perm, m.seg_off, m.compact_ws, s))) return rc;
-  hipLaunchKernelGGL(mask_gather_kernel, dim3(rows_grid(Nc, C), m.G), dim3(256), 0, s, content, (const int*)m.perm, (const int*)m.seg_off, K, C,
-                     Nc, m.xg);
-  HIP_TRY(hipGetLastError());
-  return WCT_OK;
-}
-
-static int launch_mask_batch_passthrough(const float* content, int Nc, int C, const MaskBatchPlan& m, int K, half_t* out16, float* out32,
-                                         hipStream_t s) {
-  if (!m.any_single) return WCT_OK;
-  hipLaunchKernelGGL(mask_passthrough_kernel, dim3(K, m.G), dim3(256), 0, s, content, (const int*)m.seg_off, (const int*)m.perm, m.single,
-                     C, Nc, out16, out32);
-  HIP_TRY(hipGetLastError());
-  return WCT_OK;
-}
-
-int launch_wct_masked_batch(const float* content, int Nc, int G, const MaskGeom& g, const int* nk, const int* Ns, int K,
-                            const WctStyleSlots& states, int C, float alpha, int mode, float eps_in, half_t* out16, float* out32,
-                            void* workspace, size_t workspace_bytes, int stages, hipStream_t s, int* eig_fail) {
+int launch_wct_masked_batch(const float* content, int Nc, int G, const MaskGeom& g, const int* nk, const int* Ns, int K, int C,
+                            const WctCall& r, const WctStyleSlots& states) {
+  const int mode = r.mode, stages = r.stages; hipStream_t s = r.stream;
   MaskBatchPlan m;
-  ARG_CHECK(C % 32 == 0 && C >= 32 && C <= 1024 && content && mask_batch_plan(&m, workspace, C, Nc, G, nk, Ns, K, 2));
+  ARG_CHECK(C % 32 == 0 && C >= 32 && C <= 1024 && content && mask_batch_plan(&m, r.workspace, C, Nc, G, nk, Ns, K, 2));
   ARG_CHECK(mode == WCT_MODE_NP || mode == WCT_MODE_TF);
   ARG_CHECK(launch_map_fits((size_t)Nc * C, 4) && plan_fits(m, C));
   ARG_CHECK((size_t)G * Nc < ((size_t)1 << 31));                        // (row indices are ints)
-  ARG_CHECK(workspace_bytes >= m.total);
+  ARG_CHECK(r.workspace_bytes >= m.total);
   const WctCarve& w = m.w;
   int rc;
   if (stages & WCT_STAGE_COV) {
-    if ((rc = launch_mask_batch_gather(content, g, Nc, K, C, m, s))) return rc;
-    if ((rc = launch_plan_stats(m, C, false, true, cov_eps(mode, eps_in), s))) return rc;
+    if ((rc = launch_mask_gather(content, g, Nc, K, C, m, m.G, s))) return rc;
+    if ((rc = launch_plan_stats(m, C, false, true, cov_eps(mode, r.eps), s))) return rc;
   }
-  if ((stages & WCT_STAGE_EIG) && m.P > 0 && (rc = launch_eig_stage(w, C, m.P, m.skip, 1, nullptr, eig_fail, s))) return rc;
+  if ((stages & WCT_STAGE_EIG) && m.P > 0 && (rc = launch_eig_stage(w, C, m.P, m.skip, 1, nullptr, r.eig_fail, s))) return rc;
   if (!(stages & WCT_STAGE_APPLY)) return WCT_OK;
   if (m.P > 0) {
     if ((rc = launch_style_load_slots(states, m.P, w, C, true, s))) return rc;
-    if ((rc = launch_spectral_tail(w, C, m.P, alpha, mode, eps_in, m.skip, m.nwhite, s))) return rc;
-    if ((rc = launch_blend(w, C, m.P, alpha, 0, s))) return rc;
-    ApplySegBatchArgs a;
-    a.x = m.xg; a.N = Nc; a.C = C; a.mean = w.mean; a.M = w.M; a.bias = w.bias;
-    a.xscale = w.scale; a.mabs = w.mabs; a.out16 = out16; a.out32 = out32;
+    if ((rc = launch_spectral_tail(w, C, m.P, r.alpha, mode, r.eps, m.skip, m.nwhite, s))) return rc;
+    if ((rc = launch_blend(w, C, m.P, r.alpha, m.skip, s))) return rc;
+    ApplySegBatchArgs a = apply_args<ApplySegBatchArgs>(w, m.xg, Nc, C, r.out16, r.out32);
     a.seg_off = m.seg_off; a.perm = m.perm;
     for (int p = 0; p < WCT_PLAN_PAIRS; ++p) a.fl[p] = m.fl[p];          // (0 past the pairs)
-    if ((rc = launch_apply_seg_batch(a, m.nmax, m.P, s))) return rc;
+    if ((rc = launch_apply_args(a, m.nmax, m.P, s))) return rc;
   }
-  return launch_mask_batch_passthrough(content, Nc, C, m, K, out16, out32, s);
+  return launch_mask_passthrough(content, Nc, C, m, m.G, K, r.out16, r.out32, s);
 }
 
-int launch_adain_masked_batch(const float* content, int Nc, int G, const MaskGeom& g, const int* nk, const int* Ns, int K,
-                              const WctStyleSlots& states, int C, float alpha, float eps, half_t* out16, float* out32,
-                              void* workspace, size_t workspace_bytes, hipStream_t s) {
+int launch_adain_masked_batch(const float* content, int Nc, int G, const MaskGeom& g, const int* nk, const int* Ns, int K, int C,
+                              const WctCall& r, const WctStyleSlots& states) {
+  hipStream_t s = r.stream;
   MaskBatchPlan m;
-  ARG_CHECK(C % 32 == 0 && C <= 1024 && content && mask_batch_plan(&m, workspace, C, Nc, G, nk, Ns, K, 1));
+  ARG_CHECK(C % 32 == 0 && C <= 1024 && content && mask_batch_plan(&m, r.workspace, C, Nc, G, nk, Ns, K, 1));
   ARG_CHECK((size_t)G * Nc < ((size_t)1 << 31));
-  ARG_CHECK(workspace_bytes >= m.total);
+  ARG_CHECK(r.workspace_bytes >= m.total);
   const WctCarve& w = m.w;
   int rc;
-  if ((rc = launch_mask_batch_gather(content, g, Nc, K, C, m, s))) return rc;
+  if ((rc = launch_mask_gather(content, g, Nc, K, C, m, m.G, s))) return rc;
   if ((rc = launch_plan_stats(m, C, true, false, 0.f, s))) return rc;
   if (m.P > 0) {
     if ((rc = launch_style_load_slots(states, m.P, w, C, false, s))) return rc;
@@ -473,8 +452,9 @@ int launch_adain_masked_batch(const float* content, int Nc, int G, const MaskGeo
     for (int p = 0; p < WCT_PLAN_PAIRS; ++p) sl.fl[p] = m.fl[p];
     sl.N = Nc;
     hipLaunchKernelGGL(adain_seg_apply_kernel<SegBatchLabels>, dim3(rows_grid(m.nmax, C), m.P), dim3(256), 0, s, (const float*)m.xg,
-                       (const int*)m.seg_off, (const int*)m.perm, sl, C, (const float*)w.mean, (const float*)w.var, alpha, eps, out16, out32);
+                       (const int*)m.seg_off, (const int*)m.perm, sl, C, (const float*)w.mean, (const float*)w.var, r.alpha, r.eps, r.out16,
+                       r.out32);
     HIP_TRY(hipGetLastError());
   }
-  return launch_mask_batch_passthrough(content, Nc, C, m, K, out16, out32, s);
+  return launch_mask_passthrough(content, Nc, C, m, m.G, K, r.out16, r.out32, s);
 }

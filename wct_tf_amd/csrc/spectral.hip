@@ -237,7 +237,7 @@ struct SpecAllArgs {
   float* G;                  // [2P][C][C]
   float *N, *R, *Pm;         // N [2P][C][C]; R, Pm [P][C][C] (whitening side only)
   const float *X1, *X2;      // add2: X1 [P][C][C], X2 [2P][C][C]
-  int C; float shift; int correct, second, shared_style;
+  int C; float shift; int correct, second; WctSkip skip;
   unsigned* mabs; const float* mean; float* bias; float alpha; int mode;     // per-pair housekeeping of the opening pass
 };
 
@@ -249,15 +249,15 @@ __global__ __launch_bounds__(256) void spectral_open_all_kernel(SpecAllArgs a) {
   if (kind == 0 && blockIdx.x == 0 && blockIdx.y == 0) {
     // what blend_matrix_kernel did besides the blend: bias = alpha ms (+ (1 - alpha) mc in tf mode); and mabs starts at 0
     if (tid == 0) a.mabs[pair] = 0u;
-    const float* mp = a.mean + (size_t)(one_content(a.shared_style) ? 0 : pair) * 2 * C;     // (a mix: the one content)
-    const float* ms = a.mean + (size_t)(one_style(a.shared_style) ? 0 : pair) * 2 * C + C;
+    const float* mp = a.mean + (size_t)(one_content(a.skip) ? 0 : pair) * 2 * C;     // (a mix: the one content)
+    const float* ms = a.mean + (size_t)(one_style(a.skip) ? 0 : pair) * 2 * C + C;
     for (int i = tid; i < C; i += 256) {
       float b = a.alpha * ms[i];
       if (a.mode == WCT_MODE_TF) b += (1.f - a.alpha) * mp[i];
       a.bias[pair * C + i] = b;
     }
   }
-  if (skip_style_mat(m, a.shared_style)) return;
+  if (skip_style_mat(m, a.skip)) return;
   __shared__ float cutred[4];
   const float* Am = a.A + m * cc;
   const float cut = spectral_cut(Am, C, tid, cutred);
@@ -296,7 +296,7 @@ __global__ __launch_bounds__(256) void spectral_add2_all_kernel(SpecAllArgs a) {
   __shared__ float dps[64], dqs[64];
   __shared__ float x1t[64][65], x2t[64][65];       // mirror tiles of X1 (kind 0 only), X2
   const int m = blockIdx.z, p0 = blockIdx.y * 64, q0 = blockIdx.x * 64, tid = threadIdx.x;
-  if (skip_style_mat(m, a.shared_style)) return;
+  if (skip_style_mat(m, a.skip)) return;
   const int C = a.C, kind = m & 1;
   const size_t cc = (size_t)C * C;
   const float* Am = a.A + m * cc;
@@ -391,16 +391,16 @@ int launch_spectral_function(const float* A, const float* V, float* G, float* X,
 // always: every matrix, whatever its spectrum (measured for style-swap when the solver's tile update moved to split fp16: the
 // 3 of 900 patch matches that flipped on the 32 x 32 test case flipped with the rotated matrix recomputed as well -- it is V, not
 // the tracked matrix, that carries the difference; the switch stays for experiments).
-int launch_refresh(const WctCarve& w, int C, int P, int shared_style, hipStream_t s, bool always) {
+int launch_refresh(const WctCarve& w, int C, int P, WctSkip skip, hipStream_t s, bool always) {
   const size_t cc = (size_t)C * C;
   int rc;
   GemmArgs r1 = {};
-  r1.A = w.A0; r1.lda = C; r1.a_kmajor = 0; r1.B = w.V; r1.ldb = C; r1.b_kmajor = 1; r1.sA = r1.sB = cc; r1.skip_shared = shared_style;
+  r1.A = w.A0; r1.lda = C; r1.a_kmajor = 0; r1.B = w.V; r1.ldb = C; r1.b_kmajor = 1; r1.sA = r1.sB = cc; r1.skip = skip;
   r1.M = C; r1.N = C; r1.K = C; r1.ksplit = C; r1.out32 = w.X; r1.ldo = C; r1.s_out = cc;
   if (!always) { r1.mask_diag = w.A; r1.s_mask = cc; r1.mask_out = w.refresh; }
   if ((rc = launch_gemm(r1, 1, 2 * P, s))) return rc;
   GemmArgs r2 = {};
-  r2.A = w.V; r2.lda = C; r2.a_kmajor = 1; r2.B = w.X; r2.ldb = C; r2.b_kmajor = 1; r2.sA = r2.sB = cc; r2.skip_shared = shared_style;
+  r2.A = w.V; r2.lda = C; r2.a_kmajor = 1; r2.B = w.X; r2.ldb = C; r2.b_kmajor = 1; r2.sA = r2.sB = cc; r2.skip = skip;
   r2.M = C; r2.N = C; r2.K = C; r2.ksplit = C; r2.out32 = w.A; r2.ldo = C; r2.s_out = cc;
   if (!always) r2.mask_in = w.refresh;
   rc = launch_gemm(r2, 1, 2 * P, s);
@@ -410,7 +410,7 @@ int launch_refresh(const WctCarve& w, int C, int P, int shared_style, hipStream_
 // The spectral tail of a level, all 2P matrices in merged launches: Tw / Tcs [m] = V f(A) V^T (whitening for the even matrices,
 // colouring for the odd ones), plus the bias vectors and cleared mabs words of the opening pass.  nwhite: the pairs whose
 // whitening side is live (P; 1 for a style mix, whose content is matrix 0 alone).
-int launch_spectral_tail(const WctCarve& w, int C, int P, float alpha, int mode, float eps_in, int shared_style, int nwhite,
+int launch_spectral_tail(const WctCarve& w, int C, int P, float alpha, int mode, float eps_in, WctSkip skip, int nwhite,
                                 hipStream_t s) {
   int rc;
   const size_t cc = (size_t)C * C;
@@ -420,9 +420,9 @@ int launch_spectral_tail(const WctCarve& w, int C, int P, float alpha, int mode,
   const float shift = mode == WCT_MODE_NP ? (eps_in >= 0.f ? eps_in : 1e-5f) : 0.f;
   const int second = EIG_CORRECT >= 2;
   const dim3 tiles(cdiv(C, 64), cdiv(C, 64), 2 * P);
-  if ((rc = launch_refresh(w, C, P, shared_style, s))) return rc;
+  if ((rc = launch_refresh(w, C, P, skip, s))) return rc;
   SpecAllArgs sa = {};
-  sa.A = w.A; sa.G = w.G; sa.C = C; sa.shift = shift; sa.correct = EIG_CORRECT; sa.second = second; sa.shared_style = shared_style;
+  sa.A = w.A; sa.G = w.G; sa.C = C; sa.shift = shift; sa.correct = EIG_CORRECT; sa.second = second; sa.skip = skip;
   sa.N = w.S2; float* X2 = sa.N + 2 * P * cc; sa.R = X2 + 2 * P * cc; sa.Pm = sa.R + P * cc; float* X1 = sa.Pm + P * cc;
   sa.X1 = X1; sa.X2 = X2;
   sa.mabs = w.mabs; sa.mean = w.mean; sa.bias = w.bias; sa.alpha = alpha; sa.mode = mode;
@@ -431,7 +431,7 @@ int launch_spectral_tail(const WctCarve& w, int C, int P, float alpha, int mode,
   if (second) {
     GemmArgs a = {};   // X2[m] = (colouring: N[m], whitening: Pm[pair]) . N[m]
     a.A = sa.Pm; a.sA = cc; a.A_odd = sa.N + cc; a.sA_odd = 2 * cc; a.lda = C; a.a_kmajor = 0;
-    a.B = sa.N; a.ldb = C; a.b_kmajor = 1; a.sB = cc; a.skip_shared = shared_style;
+    a.B = sa.N; a.ldb = C; a.b_kmajor = 1; a.sB = cc; a.skip = skip;
     a.M = C; a.N = C; a.K = C; a.ksplit = C; a.out32 = X2; a.ldo = C; a.s_out = cc;
     if ((rc = launch_gemm(a, 1, 2 * P, s))) return rc;
     GemmArgs b = {};   // X1[pair] = R[pair] . N[2 pair]   (whitening side only)
@@ -442,11 +442,11 @@ int launch_spectral_tail(const WctCarve& w, int C, int P, float alpha, int mode,
     HIP_TRY(hipGetLastError());
   }
   GemmArgs g = {};   // X[m] = V[m] G[m]
-  g.A = w.V; g.lda = C; g.a_kmajor = 0; g.B = w.G; g.ldb = C; g.b_kmajor = 1; g.sA = g.sB = cc; g.skip_shared = shared_style;
+  g.A = w.V; g.lda = C; g.a_kmajor = 0; g.B = w.G; g.ldb = C; g.b_kmajor = 1; g.sA = g.sB = cc; g.skip = skip;
   g.M = C; g.N = C; g.K = C; g.ksplit = C; g.out32 = w.X; g.ldo = C; g.s_out = cc;
   if ((rc = launch_gemm(g, 1, 2 * P, s))) return rc;
   GemmArgs h = {};   // Tw / Tcs [m] = X[m] V[m]^T
-  h.A = w.X; h.lda = C; h.a_kmajor = 0; h.B = w.V; h.ldb = C; h.b_kmajor = 0; h.sA = h.sB = cc; h.skip_shared = shared_style;
+  h.A = w.X; h.lda = C; h.a_kmajor = 0; h.B = w.V; h.ldb = C; h.b_kmajor = 0; h.sA = h.sB = cc; h.skip = skip;
   h.M = C; h.N = C; h.K = C; h.ksplit = C; h.out32 = w.Tw; h.ldo = C; h.s_out = cc;
   if ((rc = launch_gemm(h, 1, 2 * P, s))) return rc;
   return WCT_OK;

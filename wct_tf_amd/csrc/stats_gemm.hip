@@ -19,7 +19,7 @@ struct StatArgs {
   float* partial;        // [2P][nslab][C]
   float* absmax;         // [2P][nslab] max |x| of the slab (first pass only) or null
   int C, nslab;
-  int shared_style;
+  WctSkip skip;
 };
 
 // First pass (mean == null): the sum runs over UNITS of 16 consecutive rows, each added up in the fixed tree of
@@ -30,7 +30,7 @@ struct StatArgs {
 __global__ __launch_bounds__(256) void colsum_kernel(StatArgs p) {
   __shared__ f32x4 red[256];
   const int mat = blockIdx.y, slab = blockIdx.x;
-  if (skip_style_mat(mat, p.shared_style)) return;
+  if (skip_style_mat(mat, p.skip)) return;
   const int b = mat & 1, pair = mat >> 1;
   const int C = p.C, cq = C / 4;
   const int nrp = 256 / cq;                  // rows / units handled in parallel (C <= 1024)
@@ -101,10 +101,10 @@ __global__ __launch_bounds__(256) void colsum_kernel(StatArgs p) {
 // colsum_finish_kernel (round 5; it was a launch of its own, cov_scale_kernel)
 // out[m][c] = sum_slab partial / denom_side; with absmax / scale given, block 0 of a matrix also does cov_scale_kernel's job
 // (round 5: one launch less per level)
-__global__ void colsum_finish_kernel(const float* partial, float* out, int C, int nslab, float d0, float d1, int shared_style,
+__global__ void colsum_finish_kernel(const float* partial, float* out, int C, int nslab, float d0, float d1, int skip,
                                      const float* absmax = nullptr, float* scale = nullptr) {
   const int mat = blockIdx.y;
-  if (skip_style_mat(mat, shared_style)) return;
+  if (skip_style_mat(mat, skip)) return;
   if (scale && blockIdx.x == 0 && threadIdx.x < 64) {
     float m = 0.f;
     for (int i = threadIdx.x; i < nslab; i += 64) m = fmaxf(m, absmax[(size_t)mat * nslab + i]);
@@ -232,7 +232,7 @@ __global__ __launch_bounds__(256, 4) void gemm_f32_kernel(GemmArgs p) {
   const int wm = wave >> 1, wn = wave & 1;
   const int m0 = blockIdx.y * BM, n0 = blockIdx.x * BN;
   const int batch = blockIdx.z / p.nsplit, split = blockIdx.z % p.nsplit;
-  if (p.skip_shared && skip_style_mat(batch, p.skip_shared)) return;
+  if (p.skip != WCT_SKIP_NONE && skip_style_mat(batch, p.skip)) return;
   if (p.mask_in && !p.mask_in[batch]) return;
   if (p.mask_diag) {                             // (uniform per block)
     const bool need = refresh_needed(p.mask_diag + batch * p.s_mask, p.M, tid);
@@ -369,7 +369,7 @@ struct CovArgs {
   const float* scale;    // [2P]
   float* partial;        // [2P][nsplit][C][C]
   int C, ksplit, nsplit, ntile;   // ntile = tiles per side
-  int shared_style;
+  WctSkip skip;
 };
 
 template <int BT>
@@ -387,7 +387,7 @@ __global__ __launch_bounds__(256, 2) void cov_f16x2_kernel(CovArgs p) {
   const bool diag = ti == tj;
   const int m0 = ti * BT, n0 = tj * BT;
   const int mat = blockIdx.z, split = blockIdx.y;
-  if (skip_style_mat(mat, p.shared_style)) return;
+  if (skip_style_mat(mat, p.skip)) return;
   const int side = mat & 1, pair = mat >> 1;
   const int N = p.n[side], C = p.C;
   const float* x = p.x[side] + (size_t)pair * N * C;
@@ -518,10 +518,10 @@ __global__ __launch_bounds__(256, 2) void cov_f16x2_kernel(CovArgs p) {
 //  them in LDS; element by element the lower triangle walked columns of every partial.  Same sums in the same order.)
 // grid (C / 64, C / 64, 2P)
 __global__ __launch_bounds__(256) void cov_finish_kernel(const float* partial, const float* scale, float* cov, int C, int nsplit, int BT,
-                                                         float inv0, float inv1, float eps, int shared_style, float* cov0 = nullptr) {
+                                                         float inv0, float inv1, float eps, int skip, float* cov0 = nullptr) {
   __shared__ float tt[64][65];
   const int mat = blockIdx.z;             // 2*pair + side
-  if (skip_style_mat(mat, shared_style)) return;
+  if (skip_style_mat(mat, skip)) return;
   const size_t cc = (size_t)C * C;
   const int r0 = blockIdx.y * 64, c0 = blockIdx.x * 64, tid = threadIdx.x, ty = tid >> 4, tx = tid & 15;
   const bool mirror = r0 / BT > c0 / BT;  // (uniform: BT is a multiple of 64)
@@ -561,86 +561,81 @@ __global__ __launch_bounds__(256) void cov_finish_kernel(const float* partial, c
   }
 }
 
-int launch_means(const float* content, int Nc, const float* style, int Ns, int C, int P,
-                        const WctCarve& w, bool with_var, int shared_style, hipStream_t s, const WctFeatStats* fs) {
-  StatArgs sa;
-  sa.x[0] = content; sa.x[1] = style; sa.n[0] = Nc; sa.n[1] = Ns;
-  for (int b = 0; b < 2; ++b) {
-    sa.u[b] = fs && fs->umax[b] ? fs->u[b] : nullptr;
-    sa.umax[b] = sa.u[b] ? fs->umax[b] : nullptr;
-  }
-  sa.mean = nullptr; sa.partial = w.stat_partial; sa.absmax = w.absmax; sa.C = C; sa.nslab = w.nslab; sa.shared_style = shared_style;
-  hipLaunchKernelGGL(colsum_kernel, dim3(w.nslab, 2 * P), dim3(256), 0, s, sa);
-  hipLaunchKernelGGL(colsum_finish_kernel, dim3(cdiv(C, 256), 2 * P), dim3(256), 0, s, w.stat_partial, w.mean, C, w.nslab, (float)Nc, (float)Ns, shared_style,
-                     (const float*)w.absmax, w.scale);
-  if (with_var) {
-    sa.mean = w.mean; sa.absmax = nullptr;
-    hipLaunchKernelGGL(colsum_kernel, dim3(w.nslab, 2 * P), dim3(256), 0, s, sa);
-    hipLaunchKernelGGL(colsum_finish_kernel, dim3(cdiv(C, 256), 2 * P), dim3(256), 0, s, w.stat_partial, w.var, C, w.nslab, (float)Nc, (float)Ns, shared_style,
+// The statistics passes over the nmat matrices of a grid -- the 2P matrices of a batch (launch_means), or one slot of a plan on
+// a one-matrix grid, pointed at the slot (launch_slot_means): sa with its inputs, partial / absmax buffers and skip mode set;
+// the means and the fp16 scale into mean / scale and, var given, the variances; d0 / d1: the rows of an even / odd matrix
+static int stat_passes(StatArgs sa, int nmat, float* mean, float* var, float* scale, float d0, float d1, hipStream_t s) {
+  const int C = sa.C;
+  sa.mean = nullptr;
+  hipLaunchKernelGGL(colsum_kernel, dim3(sa.nslab, nmat), dim3(256), 0, s, sa);
+  hipLaunchKernelGGL(colsum_finish_kernel, dim3(cdiv(C, 256), nmat), dim3(256), 0, s, sa.partial, mean, C, sa.nslab, d0, d1, (int)sa.skip,
+                     (const float*)sa.absmax, scale);
+  if (var) {
+    sa.mean = mean; sa.absmax = nullptr;
+    hipLaunchKernelGGL(colsum_kernel, dim3(sa.nslab, nmat), dim3(256), 0, s, sa);
+    hipLaunchKernelGGL(colsum_finish_kernel, dim3(cdiv(C, 256), nmat), dim3(256), 0, s, sa.partial, var, C, sa.nslab, d0, d1, (int)sa.skip,
                        (const float*)nullptr, (float*)nullptr);
   }
   HIP_TRY(hipGetLastError());
   return WCT_OK;
 }
 
-int launch_cov(const float* content, int Nc, const float* style, int Ns, int C, int P, const WctCarve& w, float eps, int shared_style,
-               hipStream_t s) {
-  // covariance partials: matrix 2p+side, side 0 = content, 1 = style; slices past a side's N write zeros
-  const int BT = C >= 128 ? 128 : 64;
-  {
-    CovArgs ca;
-    ca.x[0] = content; ca.x[1] = style; ca.n[0] = Nc; ca.n[1] = Ns;
-    ca.mean = w.mean; ca.scale = w.scale; ca.partial = w.cov_partial;
-    ca.C = C; ca.ksplit = w.ksplit; ca.nsplit = w.nsplit; ca.ntile = cdiv(C, BT); ca.shared_style = shared_style;
-    dim3 grid(ca.ntile * (ca.ntile + 1) / 2, w.nsplit, 2 * P);
-    if (BT == 128) hipLaunchKernelGGL((cov_f16x2_kernel<128>), grid, dim3(256), 0, s, ca);
-    else hipLaunchKernelGGL((cov_f16x2_kernel<64>), grid, dim3(256), 0, s, ca);
-    HIP_TRY(hipGetLastError());
+int launch_means(const float* content, int Nc, const float* style, int Ns, int C, int P, const WctCarve& w, bool with_var, WctSkip skip,
+                 hipStream_t s, const WctFeatStats* fs) {
+  StatArgs sa;
+  sa.x[0] = content; sa.x[1] = style; sa.n[0] = Nc; sa.n[1] = Ns;
+  for (int b = 0; b < 2; ++b) {
+    sa.u[b] = fs && fs->umax[b] ? fs->u[b] : nullptr;
+    sa.umax[b] = sa.u[b] ? fs->umax[b] : nullptr;
   }
-  hipLaunchKernelGGL(cov_finish_kernel, dim3(cdiv(C, 64), cdiv(C, 64), 2 * P), dim3(256), 0, s, w.cov_partial, w.scale, w.A, C,
-                     w.nsplit, BT, 1.f / (float)(Nc - 1), 1.f / (float)(Ns - 1), eps, shared_style, w.A0);
+  sa.partial = w.stat_partial; sa.absmax = w.absmax; sa.C = C; sa.nslab = w.nslab; sa.skip = skip;
+  return stat_passes(sa, 2 * P, w.mean, with_var ? w.var : nullptr, w.scale, (float)Nc, (float)Ns, s);
+}
+
+// The covariance passes over the nmat matrices of a grid, as stat_passes: the partials of ca (matrix 2p + side, side 0 =
+// content, 1 = style; slices past a side's N write zeros), then their sum into A and A0 with eps on the diagonal; inv0 / inv1:
+// 1 / (rows - 1) of an even / odd matrix
+static int cov_passes(CovArgs ca, int nmat, float* A, float* A0, float inv0, float inv1, float eps, hipStream_t s) {
+  const int C = ca.C, BT = C >= 128 ? 128 : 64;
+  ca.ntile = cdiv(C, BT);
+  dim3 grid(ca.ntile * (ca.ntile + 1) / 2, ca.nsplit, nmat);
+  if (BT == 128) hipLaunchKernelGGL((cov_f16x2_kernel<128>), grid, dim3(256), 0, s, ca);
+  else hipLaunchKernelGGL((cov_f16x2_kernel<64>), grid, dim3(256), 0, s, ca);
+  hipLaunchKernelGGL(cov_finish_kernel, dim3(cdiv(C, 64), cdiv(C, 64), nmat), dim3(256), 0, s, ca.partial, ca.scale, A, C, ca.nsplit, BT,
+                     inv0, inv1, eps, (int)ca.skip, A0);
   HIP_TRY(hipGetLastError());
   return WCT_OK;
 }
 
+int launch_cov(const float* content, int Nc, const float* style, int Ns, int C, int P, const WctCarve& w, float eps, WctSkip skip,
+               hipStream_t s) {
+  CovArgs ca;
+  ca.x[0] = content; ca.x[1] = style; ca.n[0] = Nc; ca.n[1] = Ns;
+  ca.mean = w.mean; ca.scale = w.scale; ca.partial = w.cov_partial;
+  ca.C = C; ca.ksplit = w.ksplit; ca.nsplit = w.nsplit; ca.skip = skip;
+  return cov_passes(ca, 2 * P, w.A, w.A0, 1.f / (float)(Nc - 1), 1.f / (float)(Ns - 1), eps, s);
+}
+
 // first statistics pass (means, the fp16 scale; with_var: the variances) of ONE matrix, slot `m` of the workspace, with its own
-// slab count: the kernels of launch_means on a one-matrix grid (side 0), pointed at the slot
+// slab count; u / umax: its unit sums from a conv epilogue, or null
 static int launch_slot_means(const float* x, int N, int C, int m, int nslab, const WctCarve& w, bool with_var, hipStream_t s,
-                             const float* u = nullptr, const unsigned* umax = nullptr) {
+                             const float* u, const unsigned* umax) {
   StatArgs sa = {};
   sa.x[0] = sa.x[1] = x; sa.n[0] = sa.n[1] = N;
   sa.u[0] = umax ? u : nullptr; sa.umax[0] = sa.u[0] ? umax : nullptr;
-  float* partial = w.stat_partial + (size_t)m * w.nslab * C;
-  float* absmax = w.absmax + (size_t)m * w.nslab;
-  sa.mean = nullptr; sa.partial = partial; sa.absmax = absmax; sa.C = C; sa.nslab = nslab; sa.shared_style = 0;
-  hipLaunchKernelGGL(colsum_kernel, dim3(nslab, 1), dim3(256), 0, s, sa);
-  hipLaunchKernelGGL(colsum_finish_kernel, dim3(cdiv(C, 256), 1), dim3(256), 0, s, partial, w.mean + (size_t)m * C, C, nslab, (float)N,
-                     (float)N, 0, (const float*)absmax, w.scale + m);
-  if (with_var) {
-    sa.mean = w.mean + (size_t)m * C; sa.absmax = nullptr;
-    hipLaunchKernelGGL(colsum_kernel, dim3(nslab, 1), dim3(256), 0, s, sa);
-    hipLaunchKernelGGL(colsum_finish_kernel, dim3(cdiv(C, 256), 1), dim3(256), 0, s, partial, w.var + (size_t)m * C, C, nslab, (float)N,
-                       (float)N, 0, (const float*)nullptr, (float*)nullptr);
-  }
-  HIP_TRY(hipGetLastError());
-  return WCT_OK;
+  sa.partial = w.stat_partial + (size_t)m * w.nslab * C; sa.absmax = w.absmax + (size_t)m * w.nslab;
+  sa.C = C; sa.nslab = nslab; sa.skip = WCT_SKIP_NONE;
+  return stat_passes(sa, 1, w.mean + (size_t)m * C, with_var ? w.var + (size_t)m * C : nullptr, w.scale + m, (float)N, (float)N, s);
 }
 
 // covariance of ONE matrix into slot m (A and A0), K-slices of its own layout
 static int launch_slot_cov(const float* x, int N, int C, int m, int nsplit, int ksplit, float eps, const WctCarve& w, hipStream_t s) {
-  const int BT = C >= 128 ? 128 : 64;
   const size_t cc = (size_t)C * C;
   CovArgs ca;
   ca.x[0] = ca.x[1] = x; ca.n[0] = ca.n[1] = N;
   ca.mean = w.mean + (size_t)m * C; ca.scale = w.scale + m; ca.partial = w.cov_partial + (size_t)m * w.nsplit * cc;
-  ca.C = C; ca.ksplit = ksplit; ca.nsplit = nsplit; ca.ntile = cdiv(C, BT); ca.shared_style = 0;
-  dim3 grid(ca.ntile * (ca.ntile + 1) / 2, nsplit, 1);
-  if (BT == 128) hipLaunchKernelGGL((cov_f16x2_kernel<128>), grid, dim3(256), 0, s, ca);
-  else hipLaunchKernelGGL((cov_f16x2_kernel<64>), grid, dim3(256), 0, s, ca);
-  hipLaunchKernelGGL(cov_finish_kernel, dim3(cdiv(C, 64), cdiv(C, 64), 1), dim3(256), 0, s,
-                     ca.partial, ca.scale, w.A + m * cc, C, nsplit, BT, 1.f / (float)(N - 1), 1.f / (float)(N - 1), eps, 0, w.A0 + m * cc);
-  HIP_TRY(hipGetLastError());
-  return WCT_OK;
+  ca.C = C; ca.ksplit = ksplit; ca.nsplit = nsplit; ca.skip = WCT_SKIP_NONE;
+  return cov_passes(ca, 1, w.A + m * cc, w.A0 + m * cc, 1.f / (float)(N - 1), 1.f / (float)(N - 1), eps, s);
 }
 
 // the statistics stage of a plan, slot by slot in index order (the skipped slots left out): means and the fp16 scale, with_var

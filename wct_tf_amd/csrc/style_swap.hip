@@ -156,12 +156,14 @@ int launch_style_swap(const float* content, int hc, int wc, const float* style, 
   SwapCarve sw = swap_carve((char*)workspace + wct_bytes, C, hc, wc, hs, ws, patch, stride);
   int rc;
   // statistics, covariances (+eps I), eigendecompositions: the same stages as wct_tf
-  if ((rc = launch_wct(content, Nc, style, Ns, C, 1, alpha, WCT_MODE_TF, eps, nullptr, nullptr, workspace, wct_bytes,
-                       nullptr, WCT_STAGE_COV | WCT_STAGE_EIG | WCT_STAGE_EIG_FP32UPDATE, s, 0, eig_fail))) return rc;
+  WctCall r = {};
+  r.alpha = alpha; r.mode = WCT_MODE_TF; r.eps = eps; r.workspace = workspace; r.workspace_bytes = wct_bytes;
+  r.stages = WCT_STAGE_COV | WCT_STAGE_EIG | WCT_STAGE_EIG_FP32UPDATE; r.eig_fail = eig_fail; r.stream = s;
+  if ((rc = launch_wct(content, Nc, style, Ns, C, 1, WCT_SKIP_NONE, r, nullptr, nullptr, nullptr))) return rc;
   const size_t cc = (size_t)C * C;
   // content whitening, style whitening, style colouring: S^-1/2 | S^1/2 over the kept singular values, no eps in the
   // gains (ops.py:187-189,197-198,208-209), with the first-order completion on the solver's residual
-  if ((rc = launch_refresh(w, C, 1, 0, s))) return rc;
+  if ((rc = launch_refresh(w, C, 1, WCT_SKIP_NONE, s))) return rc;
   if ((rc = launch_spectral_function(w.A, w.V, w.G, w.X, w.Tw, C, 1, 2 * cc, cc, 0, 0.f, s, w.S2))) return rc;
   if ((rc = launch_spectral_function(w.A + cc, w.V + cc, w.G + cc, w.X + cc, w.Tcs, C, 1, 2 * cc, cc, 0, 0.f, s, w.S2))) return rc;
   if ((rc = launch_spectral_function(w.A + cc, w.V + cc, w.G + cc, w.X + cc, w.T, C, 1, 2 * cc, cc, 1, 0.f, s, w.S2))) return rc;

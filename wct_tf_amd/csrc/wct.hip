@@ -214,21 +214,17 @@ __global__ __launch_bounds__(256, 2) void apply_f16x2_kernel(Args p) {
   }
 }
 
-int launch_apply_seg(const ApplySegArgs& a, int nmax, int P, hipStream_t s) {
+// P pairs of at most nmax rows each: the plain apply, a masked transform's segments, a masked batch's
+template <typename Args>
+int launch_apply_args(const Args& a, int nmax, int P, hipStream_t s) {
   const int C = a.C;
-  if (C >= 128) hipLaunchKernelGGL((apply_f16x2_kernel<128, 128, ApplySegArgs>), dim3(cdiv(nmax, 128), cdiv(C, 128), P), dim3(256), 0, s, a);
-  else hipLaunchKernelGGL((apply_f16x2_kernel<64, 128, ApplySegArgs>), dim3(cdiv(nmax, 128), cdiv(C, 64), P), dim3(256), 0, s, a);
+  if (C >= 128) hipLaunchKernelGGL((apply_f16x2_kernel<128, 128, Args>), dim3(cdiv(nmax, 128), cdiv(C, 128), P), dim3(256), 0, s, a);
+  else hipLaunchKernelGGL((apply_f16x2_kernel<64, 128, Args>), dim3(cdiv(nmax, 128), cdiv(C, 64), P), dim3(256), 0, s, a);
   HIP_TRY(hipGetLastError());
   return WCT_OK;
 }
-
-int launch_apply_seg_batch(const ApplySegBatchArgs& a, int nmax, int P, hipStream_t s) {
-  const int C = a.C;
-  if (C >= 128) hipLaunchKernelGGL((apply_f16x2_kernel<128, 128, ApplySegBatchArgs>), dim3(cdiv(nmax, 128), cdiv(C, 128), P), dim3(256), 0, s, a);
-  else hipLaunchKernelGGL((apply_f16x2_kernel<64, 128, ApplySegBatchArgs>), dim3(cdiv(nmax, 128), cdiv(C, 64), P), dim3(256), 0, s, a);
-  HIP_TRY(hipGetLastError());
-  return WCT_OK;
-}
+template int launch_apply_args<ApplySegArgs>(const ApplySegArgs&, int, int, hipStream_t);
+template int launch_apply_args<ApplySegBatchArgs>(const ApplySegBatchArgs&, int, int, hipStream_t);
 
 // ---------------------------------------------------------------------------
 // workspace carving (P independent content/style pairs per call)
@@ -299,10 +295,10 @@ size_t wct_workspace_bytes(int C, int Nc, int Ns, int P) {
 }
 
 // M = alpha (Tcs . Tw) + (1 - alpha) I, max |M| -> mabs for P pairs: the blend in the product's epilogue
-int launch_blend(const WctCarve& w, int C, int P, float alpha, int shared_style, hipStream_t s) {
+int launch_blend(const WctCarve& w, int C, int P, float alpha, WctSkip skip, hipStream_t s) {
   const size_t cc = (size_t)C * C;
   GemmArgs g = {};
-  g.A = w.Tcs; g.lda = C; g.a_kmajor = 0; g.B = w.Tw; g.ldb = C; g.b_kmajor = 1; g.sA = shared_style ? 0 : 2 * cc; g.sB = 2 * cc;
+  g.A = w.Tcs; g.lda = C; g.a_kmajor = 0; g.B = w.Tw; g.ldb = C; g.b_kmajor = 1; g.sA = one_style(skip) ? 0 : 2 * cc; g.sB = 2 * cc;
   g.M = C; g.N = C; g.K = C; g.ksplit = C; g.out32 = w.M; g.ldo = C; g.s_out = cc;
   g.blend = 1; g.alpha = alpha; g.mabs = w.mabs;
   return launch_gemm(g, 1, P, s);
@@ -311,21 +307,14 @@ int launch_blend(const WctCarve& w, int C, int P, float alpha, int shared_style,
 // the apply out = (x - mc) M^T + bias of P pairs of Nc rows, on the mean, scale, M, bias and mabs of w:
 // out[n][j] = sum_k (x[n][k]-mc[k]) M[j][k] + bias[j]
 int launch_apply(const WctCarve& w, const float* content, int Nc, int C, int P, half_t* out16, float* out32, hipStream_t s) {
-  ApplyArgs a;
-  a.x = content; a.N = Nc; a.C = C; a.mean = w.mean; a.M = w.M; a.bias = w.bias;
-  a.xscale = w.scale; a.mabs = w.mabs; a.out16 = out16; a.out32 = out32;
-  if (C >= 128) hipLaunchKernelGGL((apply_f16x2_kernel<128, 128>), dim3(cdiv(Nc, 128), cdiv(C, 128), P), dim3(256), 0, s, a);
-  else hipLaunchKernelGGL((apply_f16x2_kernel<64, 128>), dim3(cdiv(Nc, 128), cdiv(C, 64), P), dim3(256), 0, s, a);
-  HIP_TRY(hipGetLastError());
-  return WCT_OK;
+  return launch_apply_args(apply_args<ApplyArgs>(w, content, Nc, C, out16, out32), Nc, P, s);
 }
 
 // the blend product for P pairs, then the apply
-static int launch_blend_apply(const WctCarve& w, const float* content, int Nc, int C, int P, float alpha, int shared_style,
-                              half_t* out16, float* out32, hipStream_t s) {
+static int launch_blend_apply(const WctCarve& w, const float* content, int Nc, int C, int P, WctSkip skip, const WctCall& r) {
   int rc;
-  if ((rc = launch_blend(w, C, P, alpha, shared_style, s))) return rc;
-  return launch_apply(w, content, Nc, C, P, out16, out32, s);
+  if ((rc = launch_blend(w, C, P, r.alpha, skip, r.stream))) return rc;
+  return launch_apply(w, content, Nc, C, P, r.out16, r.out32, r.stream);
 }
 
 // ---------------------------------------------------------------------------
@@ -357,23 +346,19 @@ __global__ __launch_bounds__(256) void style_load_kernel(Ref r, float* mean, flo
   }
 }
 
-static int launch_style_load(const WctStyleRef& r, int K, const WctCarve& w, int C, bool with_T, hipStream_t s) {
+template <typename Ref>
+static int launch_style_load(const Ref& r, int K, const WctCarve& w, int C, bool with_T, hipStream_t s) {
   for (int k = 0; k < K; ++k) ARG_CHECK(r.state[k] != nullptr);
   const size_t n4 = ((size_t)2 * C + (with_T ? (size_t)C * C : 0)) / 4;
-  hipLaunchKernelGGL(style_load_kernel<WctStyleRef>, dim3((unsigned)std::min<size_t>((n4 + 255) / 256, 256), K), dim3(256), 0, s, r, w.mean,
-                     w.var, w.Tw, C, with_T ? 1 : 0);
+  hipLaunchKernelGGL(style_load_kernel<Ref>, dim3((unsigned)std::min<size_t>((n4 + 255) / 256, 256), K), dim3(256), 0, s, r, w.mean, w.var,
+                     w.Tw, C, with_T ? 1 : 0);
   HIP_TRY(hipGetLastError());
   return WCT_OK;
 }
 
 int launch_style_load_slots(const WctStyleSlots& r, int P, const WctCarve& w, int C, bool with_T, hipStream_t s) {
   ARG_CHECK(P >= 1 && P <= WCT_PLAN_PAIRS);
-  for (int p = 0; p < P; ++p) ARG_CHECK(r.state[p] != nullptr);
-  const size_t n4 = ((size_t)2 * C + (with_T ? (size_t)C * C : 0)) / 4;
-  hipLaunchKernelGGL(style_load_kernel<WctStyleSlots>, dim3((unsigned)std::min<size_t>((n4 + 255) / 256, 256), P), dim3(256), 0, s, r, w.mean,
-                     w.var, w.Tw, C, with_T ? 1 : 0);
-  HIP_TRY(hipGetLastError());
-  return WCT_OK;
+  return launch_style_load(r, P, w, C, with_T, s);
 }
 
 // the plan of a state: one pair, the style in slot 1 with the layout of the key, the content slot dead
@@ -390,53 +375,53 @@ size_t wct_style_workspace_bytes(int C, int Ns, const WctStyleKey& key) {
   return sp.total;
 }
 
-int launch_style_state(const float* style, int Ns, int C, const WctStyleKey& key, int adain, int mode, float eps_in, void* workspace,
-                       size_t workspace_bytes, int* eig_fail, hipStream_t s, float* state) {
+int launch_style_state(const float* style, int Ns, int C, const WctStyleKey& key, int adain, const WctCall& r, float* state) {
+  const int mode = r.mode; hipStream_t s = r.stream;
   ARG_CHECK(style && state && C % 32 == 0 && C >= 32 && C <= 1024 && Ns >= (adain ? 1 : 2) && launch_map_fits((size_t)Ns * C, 4));
   ARG_CHECK(adain || mode == WCT_MODE_NP || mode == WCT_MODE_TF);
   ARG_CHECK(key.nslab >= 1 && key.nslab <= 256 && key.nsplit >= 1 && key.ksplit >= 256 && key.ksplit % 32 == 0 &&
             (long long)key.nsplit * key.ksplit >= Ns);
   SlotPlan sp;
-  style_plan(&sp, workspace, C, style, Ns, key);
-  ARG_CHECK(workspace_bytes >= sp.total);
+  style_plan(&sp, r.workspace, C, style, Ns, key);
+  ARG_CHECK(r.workspace_bytes >= sp.total);
   const WctCarve& w = sp.w;
   int rc;
   if (adain) {
     if ((rc = launch_plan_stats(sp, C, true, false, 0.f, s))) return rc;
     HIP_TRY(hipMemcpyAsync(state + C, w.var + C, (size_t)C * sizeof(float), hipMemcpyDeviceToDevice, s));
   } else {
-    if ((rc = launch_plan_stats(sp, C, false, true, cov_eps(mode, eps_in), s))) return rc;
-    if ((rc = launch_eig_stage(w, C, sp.P, sp.skip, 1, nullptr, eig_fail, s))) return rc;
-    if ((rc = launch_spectral_tail(w, C, sp.P, 1.f, mode, eps_in, sp.skip, sp.nwhite, s))) return rc;
+    if ((rc = launch_plan_stats(sp, C, false, true, cov_eps(mode, r.eps), s))) return rc;
+    if ((rc = launch_eig_stage(w, C, sp.P, sp.skip, 1, nullptr, r.eig_fail, s))) return rc;
+    if ((rc = launch_spectral_tail(w, C, sp.P, 1.f, mode, r.eps, sp.skip, sp.nwhite, s))) return rc;
     HIP_TRY(hipMemcpyAsync(state + 2 * C, w.Tw + (size_t)C * C, (size_t)C * C * sizeof(float), hipMemcpyDeviceToDevice, s));
   }
   HIP_TRY(hipMemcpyAsync(state, w.mean + C, (size_t)C * sizeof(float), hipMemcpyDeviceToDevice, s));
   return WCT_OK;
 }
 
-int launch_wct(const float* content, int Nc, const float* style, int Ns, int C, int P, float alpha, int mode, float eps_in,
-               half_t* out16, float* out32, void* workspace, size_t workspace_bytes, int* sweeps_dev,
-               int stages, hipStream_t s, int shared_style, int* eig_fail, const WctFeatStats* stats, const WctStyleRef* prep,
-               const WctWarmRef* warm) {
+int launch_wct(const float* content, int Nc, const float* style, int Ns, int C, int P, WctSkip skip, const WctCall& r,
+               const WctFeatStats* stats, const WctStyleRef* prep, const WctWarmRef* warm) {
+  const int mode = r.mode, stages = r.stages; hipStream_t s = r.stream;
   ARG_CHECK(C % 32 == 0 && C >= 32 && C <= 1024 && Nc >= 2 && Ns >= 2 && P >= 1 && P <= 32);
-  ARG_CHECK(!warm || (warm->basis && (shared_style == 0 || prep)));
-  if (prep) shared_style = WCT_SKIP_STYLE;       // (the style rows are not read: `style` may be null)
+  ARG_CHECK(skip == WCT_SKIP_NONE || skip == WCT_SKIP_SHARED_STYLE);
+  ARG_CHECK(!warm || (warm->basis && (skip == WCT_SKIP_NONE || prep)));
+  if (prep) skip = WCT_SKIP_STYLE;               // (the style rows are not read: `style` may be null)
   ARG_CHECK(mode == WCT_MODE_NP || mode == WCT_MODE_TF);
   // the covariance kernel addresses one feature map through a buffer resource with 32-bit byte offsets
   ARG_CHECK(launch_map_fits((size_t)Nc * C, 4) && launch_map_fits((size_t)Ns * C, 4));
-  WctCarve w = carve(workspace, C, P, pair_layout(C, Nc, Ns));
-  ARG_CHECK(workspace_bytes >= w.total);
+  WctCarve w = carve(r.workspace, C, P, pair_layout(C, Nc, Ns));
+  ARG_CHECK(r.workspace_bytes >= w.total);
   int rc;
   if (stages & WCT_STAGE_COV) {
-    if ((rc = launch_means(content, Nc, style, Ns, C, P, w, false, shared_style, s, stats))) return rc;
-    if ((rc = launch_cov(content, Nc, style, Ns, C, P, w, cov_eps(mode, eps_in), shared_style, s))) return rc;
+    if ((rc = launch_means(content, Nc, style, Ns, C, P, w, false, skip, s, stats))) return rc;
+    if ((rc = launch_cov(content, Nc, style, Ns, C, P, w, cov_eps(mode, r.eps), skip, s))) return rc;
   }
   if (stages & WCT_STAGE_EIG) {
     // a warm start (warm.hip): the content matrices rotated into the stored basis, the same solve on them, the bases composed --
     // and the last content's eigenvectors, re-orthonormalised, kept for the next call (after a cold solve as well)
     const bool rotate = warm && warm->valid;
     if (rotate && (rc = launch_warm_rotate(w, C, P, warm->basis, s))) return rc;
-    if ((rc = launch_eig_stage(w, C, P, shared_style, (stages & WCT_STAGE_EIG_FP32UPDATE) ? 0 : 1, sweeps_dev, eig_fail, s, rotate ? 0 : 2)))
+    if ((rc = launch_eig_stage(w, C, P, skip, (stages & WCT_STAGE_EIG_FP32UPDATE) ? 0 : 1, r.sweeps_dev, r.eig_fail, s, rotate ? 0 : 2)))
       return rc;
     if (rotate && (rc = launch_warm_compose(w, C, P, warm->basis, s))) return rc;
     if (warm && (rc = launch_warm_store(w.V + (size_t)2 * (P - 1) * C * C, w.X, warm->basis, C, s))) return rc;
@@ -444,8 +429,8 @@ int launch_wct(const float* content, int Nc, const float* style, int Ns, int C, 
   if (!(stages & WCT_STAGE_APPLY)) return WCT_OK;
 
   if (prep && (rc = launch_style_load(*prep, 1, w, C, true, s))) return rc;
-  if ((rc = launch_spectral_tail(w, C, P, alpha, mode, eps_in, shared_style, P, s))) return rc;
-  return launch_blend_apply(w, content, Nc, C, P, alpha, shared_style, out16, out32, s);
+  if ((rc = launch_spectral_tail(w, C, P, r.alpha, mode, r.eps, skip, P, s))) return rc;
+  return launch_blend_apply(w, content, Nc, C, P, skip, r);
 }
 
 // ---------------------------------------------------------------------------
@@ -527,28 +512,28 @@ __global__ __launch_bounds__(256) void wct_mix_kernel(float* Tw, float* bias, in
 }
 
 int launch_wct_mix(const float* content, int Nc, const float* const* styles, const int* Ns, int K, const float* lambda, int C,
-                   float alpha, int mode, float eps_in, half_t* out16, float* out32, void* workspace, size_t workspace_bytes,
-                   int* sweeps_dev, int stages, hipStream_t s, int* eig_fail, const WctFeatStats* stats, const WctStyleRef* prep) {
+                   const WctCall& r, const WctFeatStats* stats, const WctStyleRef* prep) {
+  const int mode = r.mode, stages = r.stages; hipStream_t s = r.stream;
   SlotPlan sp;
   ARG_CHECK(C % 32 == 0 && C >= 32 && C <= 1024 && Nc >= 2 && content && (styles || prep) &&
-            mix_plan(&sp, workspace, C, content, Nc, prep ? nullptr : styles, Ns, K, lambda, 2, stats, prep != nullptr));
+            mix_plan(&sp, r.workspace, C, content, Nc, prep ? nullptr : styles, Ns, K, lambda, 2, stats, prep != nullptr));
   ARG_CHECK(mode == WCT_MODE_NP || mode == WCT_MODE_TF);
   ARG_CHECK(plan_fits(sp, C));
-  ARG_CHECK(workspace_bytes >= sp.total);
+  ARG_CHECK(r.workspace_bytes >= sp.total);
   const WctCarve& w = sp.w;
   int rc;
-  if ((stages & WCT_STAGE_COV) && (rc = launch_plan_stats(sp, C, false, true, cov_eps(mode, eps_in), s))) return rc;
-  if ((stages & WCT_STAGE_EIG) && (rc = launch_eig_stage(w, C, sp.P, sp.skip, 1, sweeps_dev, eig_fail, s))) return rc;
+  if ((stages & WCT_STAGE_COV) && (rc = launch_plan_stats(sp, C, false, true, cov_eps(mode, r.eps), s))) return rc;
+  if ((stages & WCT_STAGE_EIG) && (rc = launch_eig_stage(w, C, sp.P, sp.skip, 1, r.sweeps_dev, r.eig_fail, s))) return rc;
   if (!(stages & WCT_STAGE_APPLY)) return WCT_OK;
   if (prep && (rc = launch_style_load(*prep, K, w, C, true, s))) return rc;
-  if ((rc = launch_spectral_tail(w, C, sp.P, alpha, mode, eps_in, sp.skip, sp.nwhite, s))) return rc;
+  if ((rc = launch_spectral_tail(w, C, sp.P, r.alpha, mode, r.eps, sp.skip, sp.nwhite, s))) return rc;
   MixWeights mw = {};
   mw.K = K;
   for (int k = 0; k < K; ++k) mw.lambda[k] = lambda[k];
   const size_t n4 = (size_t)C * C / 4;
   hipLaunchKernelGGL(wct_mix_kernel, dim3((unsigned)std::min<size_t>((n4 + 255) / 256, 1024)), dim3(256), 0, s, w.Tw, w.bias, C, mw);
   HIP_TRY(hipGetLastError());
-  return launch_blend_apply(w, content, Nc, C, 1, alpha, 0, out16, out32, s);
+  return launch_blend_apply(w, content, Nc, C, 1, WCT_SKIP_NONE, r);      // (the mixed colouring sits in pair 0's own slot)
 }
 
 // ---------------------------------------------------------------------------
@@ -557,14 +542,14 @@ int launch_wct_mix(const float* content, int Nc, const float* const* styles, con
 // mix_mu / mix_sd (or null): the style moments as a mean and a STANDARD DEVIATION (a style mix, launch_adain_mix: squaring the
 // mixed deviation to hand it over as a variance would not round-trip through sqrtf)
 __global__ void adain_apply_kernel(const float* x, size_t n4_per_pair, int C, const float* mean, const float* var,
-                                   float alpha, float eps, half_t* out16, float* out32, int shared_style,
+                                   float alpha, float eps, half_t* out16, float* out32, int style_of_pair0,
                                    const float* mix_mu = nullptr, const float* mix_sd = nullptr) {
   const int pair = blockIdx.y;
   const int cq = C / 4;
   const float* mp = mean + (size_t)pair * 2 * C;
   const float* vp = var + (size_t)pair * 2 * C;
-  const float* ms = mix_mu ? mix_mu : mean + (size_t)(shared_style ? 0 : pair) * 2 * C + C;   // style moments
-  const float* vs = var + (size_t)(shared_style ? 0 : pair) * 2 * C + C;
+  const float* ms = mix_mu ? mix_mu : mean + (size_t)(style_of_pair0 ? 0 : pair) * 2 * C + C;   // style moments
+  const float* vs = var + (size_t)(style_of_pair0 ? 0 : pair) * 2 * C + C;
   const size_t base = (size_t)pair * n4_per_pair;
   for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n4_per_pair; i += (size_t)gridDim.x * blockDim.x) {
     const int c = (int)(i % cq) * 4;
@@ -587,19 +572,21 @@ __global__ void adain_apply_kernel(const float* x, size_t n4_per_pair, int C, co
   }
 }
 
-int launch_adain(const float* content, int Nc, const float* style, int Ns, int C, int P, float alpha, float eps,
-                 half_t* out16, float* out32, void* workspace, size_t workspace_bytes, hipStream_t s, int shared_style,
+int launch_adain(const float* content, int Nc, const float* style, int Ns, int C, int P, WctSkip skip, const WctCall& r,
                  const WctFeatStats* stats, const WctStyleRef* prep) {
+  hipStream_t s = r.stream;
   ARG_CHECK(C % 4 == 0 && C <= 1024 && Nc >= 1 && Ns >= 1 && P >= 1 && P <= 32);
-  if (prep) shared_style = WCT_SKIP_STYLE;
+  ARG_CHECK(skip == WCT_SKIP_NONE || skip == WCT_SKIP_SHARED_STYLE);
+  if (prep) skip = WCT_SKIP_STYLE;
   const int Cw = C < 32 ? 32 : C;
-  WctCarve w = carve(workspace, Cw, P, pair_layout(Cw, Nc, Ns));
-  ARG_CHECK(workspace_bytes >= w.total);
+  WctCarve w = carve(r.workspace, Cw, P, pair_layout(Cw, Nc, Ns));
+  ARG_CHECK(r.workspace_bytes >= w.total);
   int rc;
-  if ((rc = launch_means(content, Nc, style, Ns, C, P, w, true, shared_style, s, stats))) return rc;
+  if ((rc = launch_means(content, Nc, style, Ns, C, P, w, true, skip, s, stats))) return rc;
   if (prep && (rc = launch_style_load(*prep, 1, w, C, false, s))) return rc;
   const size_t n4 = (size_t)Nc * C / 4;
-  hipLaunchKernelGGL(adain_apply_kernel, dim3(rows_grid(Nc, C), P), dim3(256), 0, s, content, n4, C, w.mean, w.var, alpha, eps, out16, out32, shared_style);
+  hipLaunchKernelGGL(adain_apply_kernel, dim3(rows_grid(Nc, C), P), dim3(256), 0, s, content, n4, C, w.mean, w.var, r.alpha, r.eps, r.out16, r.out32,
+                     one_style(skip) ? 1 : 0);
   HIP_TRY(hipGetLastError());
   return WCT_OK;
 }
@@ -618,13 +605,13 @@ __global__ void adain_mix_moments_kernel(const float* mean, const float* var, fl
 }
 
 int launch_adain_mix(const float* content, int Nc, const float* const* styles, const int* Ns, int K, const float* lambda, int C,
-                     float alpha, float eps, half_t* out16, float* out32, void* workspace, size_t workspace_bytes, hipStream_t s,
-                     const WctFeatStats* stats, const WctStyleRef* prep) {
+                     const WctCall& r, const WctFeatStats* stats, const WctStyleRef* prep) {
+  hipStream_t s = r.stream;
   SlotPlan sp;
   ARG_CHECK(C % 4 == 0 && C <= 1024 && Nc >= 1 && content && (styles || prep) &&
-            mix_plan(&sp, workspace, C, content, Nc, prep ? nullptr : styles, Ns, K, lambda, 1, stats, prep != nullptr));
+            mix_plan(&sp, r.workspace, C, content, Nc, prep ? nullptr : styles, Ns, K, lambda, 1, stats, prep != nullptr));
   ARG_CHECK(!prep || C >= 32);
-  ARG_CHECK(workspace_bytes >= sp.total);
+  ARG_CHECK(r.workspace_bytes >= sp.total);
   const WctCarve& w = sp.w;
   int rc;
   if ((rc = launch_plan_stats(sp, C, true, false, 0.f, s))) return rc;
@@ -634,8 +621,8 @@ int launch_adain_mix(const float* content, int Nc, const float* const* styles, c
   for (int k = 0; k < K; ++k) mw.lambda[k] = lambda[k];
   hipLaunchKernelGGL(adain_mix_moments_kernel, dim3(cdiv(C, 256)), dim3(256), 0, s, w.mean, w.var, w.mix, C, mw);
   const size_t n4 = (size_t)Nc * C / 4;
-  hipLaunchKernelGGL(adain_apply_kernel, dim3(rows_grid(Nc, C), 1), dim3(256), 0, s, content, n4, C, w.mean, w.var, alpha, eps, out16, out32, 0,
-                     (const float*)w.mix, (const float*)(w.mix + C));
+  hipLaunchKernelGGL(adain_apply_kernel, dim3(rows_grid(Nc, C), 1), dim3(256), 0, s, content, n4, C, w.mean, w.var, r.alpha, r.eps, r.out16,
+                     r.out32, 0, (const float*)w.mix, (const float*)(w.mix + C));
   HIP_TRY(hipGetLastError());
   return WCT_OK;
 }

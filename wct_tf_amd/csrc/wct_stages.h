@@ -4,30 +4,7 @@
 #pragma once
 #include "common.h"
 
-// ---- the matrices of a batch: matrix m = 2 * pair + side (0 content, 1 style) ----------------------------------------------
-// With a shared style (one style image for every pair of the batch: video; shared_style == 1) only pair 0's style matrix
-// (matrix 1) is computed; the style matrices of the other pairs are skipped and their consumers read pair 0's.
-// A style mix (launch_wct_mix; shared_style == WCT_SKIP_MIX) is the mirror image: K styles share ONE content, matrix 0;
-// the content slots 2k of the pairs k >= 1 are skipped.
-constexpr int WCT_SKIP_MIX = 2;
-// Prepared styles (wct_style, api.h): the style side of a call comes out of a handle's cached state, copied into the style
-// slots by style_load_kernel (wct.hip), so EVERY style matrix is dead -- WCT_SKIP_STYLE (P contents, one state in slot 1, read
-// like a shared style) and WCT_SKIP_MIX_STYLE (a mix of K states: matrix 0 alone is live).  WCT_SKIP_CONTENT is the mirror image
-// that fills a state: one style in slot 1, the content slot dead, no whitening side.
-constexpr int WCT_SKIP_STYLE = 3, WCT_SKIP_CONTENT = 4, WCT_SKIP_MIX_STYLE = 5;
-// WCT_SKIP_STYLES: the batched masked transform on prepared styles (mask.hip) -- every style matrix dead as under
-// WCT_SKIP_STYLE, but each pair reads the state in its OWN style slot (neither one_style nor one_content)
-constexpr int WCT_SKIP_STYLES = 6;
-__device__ __host__ __forceinline__ bool skip_style_mat(int mat, int shared_style) {
-  if (shared_style >= WCT_SKIP_STYLE)
-    return shared_style == WCT_SKIP_STYLE ? (mat & 1) != 0
-                                          : (shared_style == WCT_SKIP_CONTENT ? (mat & 1) == 0
-                                                                              : (shared_style == WCT_SKIP_MIX_STYLE ? mat > 0 : (mat & 1) != 0));
-  return shared_style == WCT_SKIP_MIX ? ((mat & 1) == 0 && mat > 0) : (shared_style && (mat & 1) && mat > 1);
-}
-// which pair's slots hold the content / style moments a pair's consumers read: pair 0's for all where one is shared
-__device__ __host__ __forceinline__ bool one_content(int shared_style) { return shared_style == WCT_SKIP_MIX || shared_style == WCT_SKIP_MIX_STYLE; }
-__device__ __host__ __forceinline__ bool one_style(int shared_style) { return shared_style == 1 || shared_style == WCT_SKIP_STYLE; }
+// (the matrices of a batch, and the skip mode that says which of them are dead: skip_rule.h, through common.h)
 
 // 0: spectral functions of the diagonal only, 1: + first-order completion, 2 (the product): + second-order completion
 constexpr int EIG_CORRECT = 2;
@@ -76,7 +53,7 @@ static inline unsigned rows_grid(size_t N, int C) {
 // eigensolve of 64 matrices: WCT_PLAN_PAIRS.
 constexpr int WCT_PLAN_PAIRS = 32;
 struct SlotPlan {
-  int P, skip, nwhite;                         // pairs; the skip mode (0 or a WCT_SKIP_*); pairs whose whitening side is live
+  int P; WctSkip skip; int nwhite;             // pairs; the skip mode; pairs whose whitening side is live
   struct Slot { const float* x; int n; PairLayout lay; } slot[2 * WCT_PLAN_PAIRS];   // rows (null while only sizing the
                                                                                     // workspace), their count (0: skipped), layout
   const float* u0; const unsigned* umax0;      // slot 0's unit sums from a conv epilogue, or null
@@ -101,6 +78,14 @@ struct ApplySegArgs : ApplyArgs { const int* seg_off; const int* perm; int lab[W
 // The segments of a masked BATCH (launch_wct_masked_batch): x, out16 / out32 hold G frames of N rows, seg_off [G][WCT_MIX_MAX + 1]
 // and perm [G][N] are per frame, and pair p is the segment of label fl[p] & 7 of frame fl[p] >> 3
 struct ApplySegBatchArgs : ApplyArgs { const int* seg_off; const int* perm; unsigned char fl[WCT_PLAN_PAIRS]; };
+// the ApplyArgs part of any of the three: x [N rows a pair, or a masked transform's gathered rows] against the matrices of w
+template <typename Args>
+static inline Args apply_args(const WctCarve& w, const float* x, int N, int C, half_t* out16, float* out32) {
+  Args a;
+  a.x = x; a.N = N; a.C = C; a.mean = w.mean; a.M = w.M; a.bias = w.bias;
+  a.xscale = w.scale; a.mabs = w.mabs; a.out16 = out16; a.out32 = out32;
+  return a;
+}
 __device__ __host__ __forceinline__ int seg_frame(unsigned char fl) { return fl >> 3; }
 __device__ __host__ __forceinline__ int seg_label(unsigned char fl) { return fl & 7; }
 
@@ -108,26 +93,25 @@ __device__ __host__ __forceinline__ int seg_label(unsigned char fl) { return fl 
 // stats_gemm.hip: means and the fp16 scale (with_var: the variances) of the 2P matrices; their covariances into w.A and w.A0
 // (eps on the diagonal); both for the live slots of a plan, each with its own layout
 int launch_means(const float* content, int Nc, const float* style, int Ns, int C, int P, const WctCarve& w, bool with_var,
-                 int shared_style, hipStream_t s, const WctFeatStats* fs = nullptr);
-int launch_cov(const float* content, int Nc, const float* style, int Ns, int C, int P, const WctCarve& w, float eps, int shared_style,
+                 WctSkip skip, hipStream_t s, const WctFeatStats* fs);
+int launch_cov(const float* content, int Nc, const float* style, int Ns, int C, int P, const WctCarve& w, float eps, WctSkip skip,
                hipStream_t s);
 int launch_plan_stats(const SlotPlan& sp, int C, bool with_var, bool with_cov, float eps, hipStream_t s);
 // eigh.hip: the 2P matrices of w in one batched solve
 // (check_from: the first sweep after which the host looks at the done-flags -- JacobiGroup::check_from; a warm solve passes 0)
-int launch_eig_stage(const WctCarve& w, int C, int P, int skip, int u_f16, int* sweeps_dev, int* eig_fail, hipStream_t s,
+int launch_eig_stage(const WctCarve& w, int C, int P, WctSkip skip, int u_f16, int* sweeps_dev, int* eig_fail, hipStream_t s,
                      int check_from = 2);
 // spectral.hip: the refresh of the rotated matrices, the merged spectral tail of a level, one spectral function (style-swap)
-int launch_refresh(const WctCarve& w, int C, int P, int shared_style, hipStream_t s, bool always = false);
-int launch_spectral_tail(const WctCarve& w, int C, int P, float alpha, int mode, float eps_in, int shared_style, int nwhite, hipStream_t s);
+int launch_refresh(const WctCarve& w, int C, int P, WctSkip skip, hipStream_t s, bool always = false);
+int launch_spectral_tail(const WctCarve& w, int C, int P, float alpha, int mode, float eps_in, WctSkip skip, int nwhite, hipStream_t s);
 int launch_spectral_function(const float* A, const float* V, float* G, float* X, float* out, int C, int nbatch, size_t stride,
                              size_t out_stride, int kind, float shift, hipStream_t s, float* scratch2 = nullptr);
 // wct.hip: the blend product M = alpha Tcs Tw + (1 - alpha) I of P pairs; the apply of P pairs of Nc rows on the matrices of w
 // (any number of calls on one set of matrices: the chunks of a banded map); the apply of a masked transform's P segments (the
-// longest has nmax rows)
-int launch_blend(const WctCarve& w, int C, int P, float alpha, int shared_style, hipStream_t s);
+// longest has nmax rows), whose argument blocks start from apply_args
+int launch_blend(const WctCarve& w, int C, int P, float alpha, WctSkip skip, hipStream_t s);
 int launch_apply(const WctCarve& w, const float* content, int Nc, int C, int P, half_t* out16, float* out32, hipStream_t s);
-int launch_apply_seg(const ApplySegArgs& a, int nmax, int P, hipStream_t s);
-int launch_apply_seg_batch(const ApplySegBatchArgs& a, int nmax, int P, hipStream_t s);
+template <typename Args> int launch_apply_args(const Args& a, int nmax, int P, hipStream_t s);   // (ApplySegArgs, ApplySegBatchArgs)
 // warm.hip (video warm start): A' = V0^T A V0 of the P content matrices of w in place (w.X scratch); V = V0 V' of the same in place
 // (w.X scratch); basis = V (3 I - V^T V) / 2 of one C x C matrix (scratch: C x C floats)
 int launch_warm_rotate(const WctCarve& w, int C, int P, const float* V0, hipStream_t s);
