@@ -70,7 +70,8 @@ extern "C" int wct_train_step(wct_ctx* c, int level, const float* images, int B,
   HIP_TRY(hipSetDevice(c->device));
   if (!c->enc_loaded) { wct_set_error("encoder weights not set (wct_set_encoder)"); return WCT_ERR_STATE; }
   // every forward layer of a training step on the direct kernel: the backward pass differentiates THAT arithmetic (fp16-rounded
-  // operands, exact products), and the gradient tests hold it to 1e-4
+  // operands, exact products); tests/test_gpu_backward.py rebuilds the saved state layer by layer with that kernel and holds every
+  // gradient element to a derived bound, tests/test_gpu_train.py holds the whole chain to 1e-3 .. 1e-2 against autograd
   struct DirectOnly { wct_ctx* c; DirectOnly(wct_ctx* x) : c(x) { c->no_wino = true; } ~DirectOnly() { c->no_wino = false; } } direct_only(c);
   Decoder& d = c->dec[level];
   if (!d.loaded) { wct_set_error("decoder weights for relu%d_1 not set (wct_set_decoder)", level); return WCT_ERR_STATE; }
