@@ -206,6 +206,29 @@ int wct_content_colors(wct_ctx* ctx, const uint8_t* stylized, int Ho, int Wo, co
                        uint8_t* out);
 int wct_content_colors_batch_dev(wct_ctx* ctx, const uint8_t* stylized_dev, int Ho, int Wo, const uint8_t* content_dev, int Hc,
                                  int Wc, int B, uint8_t* out_dev);
+/* On-device resize (the reference's resize_to, utils.py:55-67, behind --content-size, stylize_video.py:29; webcam.py:163,189
+ * resizes every frame by --scale): img [H][W][3] uint8 -> [h][w][3] uint8, the bytes of Pillow's Image.resize((w, h), Image.BILINEAR).
+ * Pillow's 8-bit resampler is an integer rule.  Per axis (`in` the input length, `out` the output length; everything up to the
+ * integer taps is IEEE double, evaluated in exactly this order, without fused multiply-adds):
+ *   scale = in / out;  fs = max(scale, 1.0);  support = fs;  ksize = (int)ceil(support) * 2 + 1
+ *   for xx in 0 .. out-1:
+ *     center = (xx + 0.5) * scale
+ *     xmin = max((int)(center - support + 0.5), 0)                        (int): truncation
+ *     n    = min((int)(center + support + 0.5), in) - xmin
+ *     w[x] = tri((x + xmin - center + 0.5) * (1.0 / fs)),  x in 0 .. n-1,   tri(t) = |t| < 1 ? 1 - |t| : 0
+ *     ww = sum w[x] in order;  if ww != 0: w[x] /= ww
+ *     k[x] = (int)(0.5 + w[x] * 4194304.0)                                (22 bits; bilinear taps are never negative)
+ *   byte = clamp((2097152 + sum_x k[x] * src[xmin + x]) >> 22, 0, 255)    int32 throughout
+ * The image is resized along x first, into a uint8 intermediate of H x w (it stays on the chip), which is then resized along y.
+ * An axis whose length does not change reproduces its bytes; h == H and w == W is a copy.
+ * wct_resize: host pointers, blocking.  wct_resize_batch_dev: device pointers, B = 1 .. 32 frames [B][H][W][3] ->
+ *   [B][h][w][3] in one launch, asynchronous on the ctx stream, no workspace; out_dev must not overlap in_dev.  The tap tables
+ *   of the last geometry (H, W, h, w) stay in the ctx: a call with another geometry waits for the stream while it replaces them.
+ * A null pointer, a size < 1, B outside 1 .. 32, input or output bytes >= 2^31 in one call (every index is a 32-bit one), an
+ * overlap, or a vertical reduction so strong that the input rows one output row taps do not fit the kernel's 16 KB of LDS at
+ * min(w, 64) columns (H / h above about 42 at w >= 64) is WCT_STATUS_ARG and leaves the ctx usable. */
+int wct_resize(wct_ctx* ctx, const uint8_t* img, int H, int W, int h, int w, uint8_t* out);
+int wct_resize_batch_dev(wct_ctx* ctx, const uint8_t* in_dev, int H, int W, int B, int h, int w, uint8_t* out_dev);
 
 /* ---- the hot path: WCT.predict (wct.py:70-106) -------------------------------------
  * levels: relu levels in pipeline order, e.g. {5,4,3,2,1}.  Output size: wct_output_size. */

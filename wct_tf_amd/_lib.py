@@ -50,6 +50,8 @@ SIGNATURES = [
     ('wct_coral_apply', C.c_int, [_P, _U8, C.c_int, C.c_int, _D, _D, _D, _D, _D, _U8, _D]),
     ('wct_content_colors', C.c_int, [_P, _U8, C.c_int, C.c_int, _U8, C.c_int, C.c_int, _U8]),
     ('wct_content_colors_batch_dev', C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P]),
+    ('wct_resize', C.c_int, [_P, _U8, C.c_int, C.c_int, C.c_int, C.c_int, _U8]),
+    ('wct_resize_batch_dev', C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     ('wct_output_size', C.c_int, [C.c_int, C.c_int, _I, C.c_int, _I, _I]),
     ('wct_stylize', C.c_int, [_P, _U8, C.c_int, C.c_int, _U8, C.c_int, C.c_int, _I, C.c_int,
                               C.c_float, C.c_uint, _U8]),

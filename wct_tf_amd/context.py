@@ -76,6 +76,27 @@ def check_texture(size, passes=1, batch=1, seed=0, first_sample=0):
     return h, w
 
 
+def check_resize(size, frames=None, ndim=4):
+    """The refusals of a resize, before any library call: a target size (h, w) of two positive integers and, given `frames`, a
+    non-empty uint8 array [B][H][W][3] (ndim 4; B <= BATCH_MAX) or HxWx3 (ndim 3).  -> (h, w), or (h, w, frames contiguous)"""
+    try:
+        h, w = (int(v) for v in size)
+    except (TypeError, ValueError):
+        raise ValueError('a resize target is (h, w), got %r' % (size,))
+    if h < 1 or w < 1:
+        raise ValueError('an empty resize target %dx%d' % (h, w))
+    if frames is None:
+        return h, w
+    a = np.asarray(frames)
+    if a.dtype != np.uint8:
+        raise ValueError('resize takes uint8 images, got %s' % a.dtype)
+    if a.ndim != ndim or a.shape[-1] != 3 or a.size == 0:
+        raise ValueError('resize takes %s images, got shape %s' % ('[B][H][W][3]' if ndim == 4 else 'HxWx3', a.shape))
+    if ndim == 4 and not 1 <= a.shape[0] <= _lib.BATCH_MAX:
+        raise ValueError('a batch takes 1 .. %d frames, got %d' % (_lib.BATCH_MAX, a.shape[0]))
+    return h, w, u8(a)
+
+
 def _image_arrays(images):
     """Pointers, heights and widths of K images as C arrays."""
     k = len(images)
@@ -575,6 +596,29 @@ class Context(object):
         return self._host_batch([s, c], np.empty_like(s), in_place=True, enqueue=lambda ds, dc: self.content_colors_batch_dev(
             ds, s.shape[1], s.shape[2], dc, c.shape[1], c.shape[2], s.shape[0], ds))
 
+    # ---- on-device resize: Pillow's bilinear bytes ------------------------------------------
+    def resize(self, img_u8, size):
+        """img [H][W][3] uint8 -> uint8 [h][w][3] for size = (h, w) (wct_resize; the integer rule of include/wct_hip.h): the bytes
+        of Image.fromarray(img).resize((w, h), Image.BILINEAR), i.e. of utils._imresize."""
+        h, w, a = check_resize(size, img_u8, ndim=3)
+        out = np.empty((h, w, 3), np.uint8)
+        check(self.lib.wct_resize(self.h, a.ctypes.data_as(_lib._U8), a.shape[0], a.shape[1], h, w, out.ctypes.data_as(_lib._U8)))
+        return out
+
+    def resize_batch_dev(self, in_dev, hi, wi, batch, size, out_dev):
+        """`batch` frames [batch][hi][wi][3] resident in HBM -> [batch][h][w][3] at out_dev (wct_resize_batch_dev): one launch,
+        asynchronous; out_dev must not overlap in_dev."""
+        h, w = check_resize(size)
+        if not 1 <= int(batch) <= _lib.BATCH_MAX:
+            raise ValueError('a batch takes 1 .. %d frames, got %d' % (_lib.BATCH_MAX, batch))
+        check(self.lib.wct_resize_batch_dev(self.h, in_dev, int(hi), int(wi), int(batch), h, w, out_dev))
+
+    def resize_batch(self, frames_u8, size):
+        """Host arrays in, host array out: frames [B][H][W][3] uint8 (B <= 32) -> [B][h][w][3]; frame f is resize(frames[f], size)."""
+        h, w, a = check_resize(size, frames_u8)
+        out = np.empty((a.shape[0], h, w, 3), np.uint8)
+        return self._host_batch([a], out, lambda di, do: self.resize_batch_dev(di, a.shape[1], a.shape[2], a.shape[0], (h, w), do))
+
     # ---- texture synthesis: seeded noise on the device, the passes chained there -----
     def texture_noise(self, h, w, seed, sample=0, smooth=False):
         """The noise image `sample` of `seed` (wct_texture_noise; the integer rule of include/wct_hip.h) -> uint8 [h][w][3].
@@ -764,19 +808,27 @@ class Context(object):
                                                       float(alpha), flags, out_dev))
 
     def stylize_prepared_batch(self, contents_u8, style, relu_targets, alpha=1.0, adain=False, wct_mode='tf', warm=None,
-                               content_colors=False):
+                               content_colors=False, resize=None):
         """stylize_batch() with a PreparedStyle: contents [B][H][W][3] uint8 (B <= 32) -> [B][Ho][Wo][3] uint8.  warm: as in
-        stylize_prepared_batch_dev."""
+        stylize_prepared_batch_dev.  resize (h, w): the contents are raw frames, resized on the device (resize_batch_dev) into
+        the content buffer the call -- and content_colors -- reads: the frames of the call on utils._imresize(frame, (h, w))."""
         check_prepared(self, [style], relu_targets)
         if warm is not None:
             check_warm(self, warm, relu_targets, adain)
-        c = u8(contents_u8)
-        assert c.ndim == 4 and c.shape[3] == 3
-        B, hc, wc = c.shape[:3]
+        if resize is not None:
+            hc, wc, c = check_resize(resize, contents_u8)
+        else:
+            c = u8(contents_u8)
+            assert c.ndim == 4 and c.shape[3] == 3
+            hc, wc = c.shape[1:3]
+        B = c.shape[0]
         ho, wo = self.output_size(hc, wc, relu_targets)
         out = np.empty((B, ho, wo, 3), np.uint8)
-        return self._host_batch([c], out, lambda dc, do: self.stylize_prepared_batch_dev(
-            dc, hc, wc, B, style, relu_targets, alpha, do, adain=adain, wct_mode=wct_mode, warm=warm, content_colors=content_colors))
+        enqueue = lambda dc, do: self.stylize_prepared_batch_dev(
+            dc, hc, wc, B, style, relu_targets, alpha, do, adain=adain, wct_mode=wct_mode, warm=warm, content_colors=content_colors)
+        if resize is not None:
+            return self._host_batch_resized(c, (hc, wc), [], out, enqueue)
+        return self._host_batch([c], out, enqueue)
 
     def stylize_prepared_masked(self, content, styles, mask, relu_targets, alpha=1.0, adain=False, wct_mode='tf', content_colors=False):
         """stylize_masked() with K PreparedStyle objects in the place of the K images: the same frame, bit for bit."""
@@ -808,21 +860,29 @@ class Context(object):
                                                              out_dev))
 
     def stylize_prepared_masked_batch(self, contents_u8, styles, masks, relu_targets, alpha=1.0, adain=False, wct_mode='tf',
-                                      content_colors=False):
+                                      content_colors=False, resize=None):
         """Host arrays in, host array out: contents [B][H][W][3] uint8 (B <= 32), masks [B][H][W] (or one [H][W] map for all),
-        K PreparedStyle objects -> [B][Ho][Wo][3] uint8."""
-        c = u8(contents_u8)
-        if c.ndim != 4 or c.shape[3] != 3:
-            raise ValueError('expected [B][H][W][3] frames, got shape %s' % (c.shape,))
-        B, hc, wc = c.shape[:3]
+        K PreparedStyle objects -> [B][Ho][Wo][3] uint8.  resize (h, w): as in stylize_prepared_batch; the label maps are given
+        at the resized size."""
+        if resize is not None:
+            hc, wc, c = check_resize(resize, contents_u8)
+        else:
+            c = u8(contents_u8)
+            if c.ndim != 4 or c.shape[3] != 3:
+                raise ValueError('expected [B][H][W][3] frames, got shape %s' % (c.shape,))
+            hc, wc = c.shape[1:3]
+        B = c.shape[0]
         if not 1 <= B <= _lib.BATCH_MAX:
             raise ValueError('a batch takes 1 .. %d frames, got %d' % (_lib.BATCH_MAX, B))
         m = _lib.mask_labels_frames(masks, len(styles), B, (hc, wc))
         check_prepared(self, styles, relu_targets)
         ho, wo = self.output_size(hc, wc, relu_targets)
         out = np.empty((B, ho, wo, 3), np.uint8)
-        return self._host_batch([c], out, lambda dc, do: self.stylize_prepared_masked_batch_dev(
-            dc, hc, wc, B, m, styles, relu_targets, alpha, do, adain=adain, wct_mode=wct_mode, content_colors=content_colors))
+        enqueue = lambda dc, do: self.stylize_prepared_masked_batch_dev(
+            dc, hc, wc, B, m, styles, relu_targets, alpha, do, adain=adain, wct_mode=wct_mode, content_colors=content_colors)
+        if resize is not None:
+            return self._host_batch_resized(c, (hc, wc), [], out, enqueue)
+        return self._host_batch([c], out, enqueue)
 
     def stylize_mix(self, content, styles, weights, relu_targets, alpha=1.0, adain=False, wct_mode='tf', swap5=False,
                     content_colors=False):
@@ -884,6 +944,27 @@ class Context(object):
                 self.dev_free(p)
         return out
 
+    def _host_batch_resized(self, raw, size, inputs, out, enqueue):
+        """_host_batch for raw frames that are resized on the way in: `raw` [B][H][W][3] uint8 goes up as it is, is resized into a
+        device content buffer [B][h][w][3] (resize_batch_dev), and enqueue(content buffer, *buffers of `inputs`, out buffer)
+        follows on the same stream; one sync(), d2h -> out.  The buffers are freed whatever happens."""
+        h, w = size
+        B, hi, wi = raw.shape[:3]
+        bufs = []
+        try:
+            for n in [raw.nbytes, B * h * w * 3] + [a.nbytes for a in inputs] + [out.nbytes]:
+                bufs.append(self.dev_alloc(n))
+            for p, a in zip([bufs[0]] + bufs[2:], [raw] + list(inputs)):
+                self.h2d(p, a)
+            self.resize_batch_dev(bufs[0], hi, wi, B, (h, w), bufs[1])
+            enqueue(*bufs[1:])
+            self.sync()
+            self.d2h(out, bufs[-1])
+        finally:
+            for p in bufs:
+                self.dev_free(p)
+        return out
+
     def stylize_batch_dev(self, content_dev, hc, wc, style_dev, hs, ws, batch, relu_targets, alpha, out_dev,
                           adain=False, wct_mode='tf', swap5=False, shared_style=False, content_colors=False):
         """B pairs resident in HBM.  shared_style: style_dev holds ONE image used for every pair (fixed-style
@@ -896,21 +977,29 @@ class Context(object):
                                              float(alpha), flags, out_dev))
 
     def stylize_batch(self, contents_u8, style_u8, relu_targets, alpha=1.0, adain=False, wct_mode='tf', swap5=False,
-                      content_colors=False):
+                      content_colors=False, resize=None):
         """Host arrays in, host array out: contents [B][H][W][3] uint8 (B <= 32); style either one image
-        [Hs][Ws][3] shared by all frames or [B][Hs][Ws][3].  Returns [B][Ho][Wo][3] uint8."""
-        c = u8(contents_u8)
+        [Hs][Ws][3] shared by all frames or [B][Hs][Ws][3].  Returns [B][Ho][Wo][3] uint8.  resize (h, w): as in
+        stylize_prepared_batch (the contents only; the style goes as it is)."""
         s = u8(style_u8)
+        if resize is not None:
+            hc, wc, c = check_resize(resize, contents_u8)
+        else:
+            c = u8(contents_u8)
+            hc, wc = c.shape[1:3]
         assert c.ndim == 4 and c.shape[3] == 3 and s.ndim in (3, 4) and s.shape[-1] == 3
         shared = s.ndim == 3
         assert shared or s.shape[0] == c.shape[0]
-        B, hc, wc = c.shape[:3]
+        B = c.shape[0]
         hs, ws = s.shape[-3], s.shape[-2]
         ho, wo = self.output_size(hc, wc, relu_targets)
         out = np.empty((B, ho, wo, 3), np.uint8)
-        return self._host_batch([c, s], out, lambda dc, ds, do: self.stylize_batch_dev(
+        enqueue = lambda dc, ds, do: self.stylize_batch_dev(
             dc, hc, wc, ds, hs, ws, B, relu_targets, alpha, do, adain=adain, wct_mode=wct_mode, swap5=swap5, shared_style=shared,
-            content_colors=content_colors))
+            content_colors=content_colors)
+        if resize is not None:
+            return self._host_batch_resized(c, (hc, wc), [s], out, enqueue)
+        return self._host_batch([c, s], out, enqueue)
 
     # ---- decoder training (model.py:123-223) --------------------------------
     def train_step(self, relu_target, images01, step, learning_rate=1e-4, feature_weight=1.0, pixel_weight=1.0,

@@ -98,6 +98,9 @@ struct wct_ctx {
   DevBuf tex_noise, tex[2];        // texture synthesis: the noise images, and the uint8 frames between two passes (alternating)
   DevBuf band_f, band_g, band_img; // banded stylization: a level's full fp32 feature map and its fp16 transform (either may pass
                                    // 2^31 bytes: every launch sees a slice), and the decoded image of one band with its halo
+  DevBuf resize_tab;               // on-device resize: the tap and bounds tables of the last geometry (resize_geom; H = 0: none yet),
+  std::vector<int> resize_host;    // and the host copy they were uploaded from
+  ResizeGeom resize_geom = {};
   std::vector<wct_style*> styles;  // the live prepared styles of this context (wct_style_prepare .. wct_style_free)
   unsigned long long style_clock = 0;   // one tick per call that takes prepared styles
   std::vector<wct_warm*> warms;    // the live warm states of this context (wct_warm_create .. wct_warm_free)

@@ -565,3 +565,55 @@ extern "C" int wct_texture_noise(wct_ctx* c, int H, int W, unsigned seed, unsign
   TRY(wct_texture_noise_batch_dev(c, H, W, 1, seed, sample, smooth, (uint8_t*)c->stage[0].p));
   return fetch(c, out, c->stage[0].p, (size_t)H * W * 3);
 }
+
+// On-device resize, op level (csrc/resize.hip): the refusals both calls share
+static int resize_checks(const void* in, int H, int W, int B, int h, int w, const void* out) {
+  if (!in || !out) { wct_set_error("resize: null image pointer"); return WCT_ERR_ARG; }
+  if (B < 1 || B > 32) { wct_set_error("resize: B = %d frames, must be 1 .. 32", B); return WCT_ERR_ARG; }
+  if (H < 1 || W < 1 || h < 1 || w < 1) { wct_set_error("resize: an empty image, %dx%d to %dx%d", H, W, h, w); return WCT_ERR_ARG; }
+  return resize_check_bytes(B, H, W, h, w);
+}
+
+// The tables of (H, W, h, w) in c->resize_tab: built and uploaded when the geometry is not the last call's.  Only then does the
+// call wait for the stream (the tables that earlier launches still read are about to be replaced).
+static int resize_tables(wct_ctx* c, int H, int W, int h, int w) {
+  const ResizeGeom& g = c->resize_geom;
+  if (g.H == H && g.W == W && g.h == h && g.w == w) return WCT_OK;
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  c->resize_geom = ResizeGeom{};
+  const size_t n = resize_table_ints(H, W, h, w);
+  c->resize_host.resize(n);
+  ResizeGeom plan;
+  TRY(resize_plan(H, W, h, w, &plan, c->resize_host.data()));
+  TRY(ensure(c, c->resize_tab, n * sizeof(int)));
+  HIP_TRY(hipMemcpyAsync(c->resize_tab.p, c->resize_host.data(), n * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  c->resize_geom = plan;
+  return WCT_OK;
+}
+
+extern "C" int wct_resize_batch_dev(wct_ctx* c, const uint8_t* in, int H, int W, int B, int h, int w, uint8_t* out) {
+  ARG_CHECK(c != nullptr);
+  TRY(resize_checks(in, H, W, B, h, w, out));
+  const size_t nin = (size_t)B * H * W * 3, nout = (size_t)B * h * w * 3;
+  if (in < out + nout && out < in + nin) { wct_set_error("resize: the output overlaps the input"); return WCT_ERR_ARG; }
+  HIP_TRY(hipSetDevice(c->device));
+  ProfScope ps(c, 7, 0, (double)nin + (double)nout);
+  if (h == H && w == W) {                                    // a copy
+    HIP_TRY(hipMemcpyAsync(out, in, nin, hipMemcpyDeviceToDevice, c->stream));
+    return WCT_OK;
+  }
+  TRY(resize_tables(c, H, W, h, w));
+  return launch_resize(in, out, B, c->resize_geom, (const int*)c->resize_tab.p, c->stream);
+}
+
+extern "C" int wct_resize(wct_ctx* c, const uint8_t* img, int H, int W, int h, int w, uint8_t* out) {
+  ARG_CHECK(c != nullptr);
+  TRY(resize_checks(img, H, W, 1, h, w, out));               // (before the staging buffers are sized)
+  HIP_TRY(hipSetDevice(c->device));
+  if (h != H || w != W) TRY(resize_tables(c, H, W, h, w));   // (the plan's refusal: before the image is read)
+  void* din;
+  TRY(stage_in(c, 0, img, (size_t)H * W * 3, &din));
+  TRY(ensure(c, c->stage[1], (size_t)h * w * 3));
+  TRY(wct_resize_batch_dev(c, (uint8_t*)din, H, W, 1, h, w, (uint8_t*)c->stage[1].p));
+  return fetch(c, out, c->stage[1].p, (size_t)h * w * 3);
+}

@@ -337,3 +337,14 @@ int launch_content_colors_u8(const uint8_t* stylized, const uint8_t* content, in
 // Seeded noise for texture synthesis (noise_rule.h): out [B][H][W][3] uint8 on the device, image b = sample first_sample + b of
 // `seed`; smooth: the rule's 27 202 27 filter along y and x.  One launch; any base address; B * H * W * 3 >= 2^31 is WCT_ERR_ARG.
 int launch_texture_noise(uint8_t* out, int B, int H, int W, unsigned seed, unsigned first_sample, int smooth, hipStream_t s);
+
+// ---- resize.hip -----------------------------------------------------------
+// Bilinear resize by Pillow's 8-bit rule (resize_rule.h): in [B][H][W][3] -> out [B][h][w][3] uint8 on the device, one launch, no
+// workspace.  A geometry's plan is host work: resize_plan fills `tabs` (resize_table_ints int32 words: the bounds and taps of both
+// axes) and picks the tile height `th`; the caller keeps the tables on the device.  WCT_ERR_ARG: input or output bytes >= 2^31
+// (resize_check_bytes, launch_resize), a vertical reduction whose taps of one output row do not fit the kernel's LDS (resize_plan).
+struct ResizeGeom { int H, W, h, w, ksx, ksy, th; };
+int resize_check_bytes(int B, int H, int W, int h, int w);
+size_t resize_table_ints(int H, int W, int h, int w);
+int resize_plan(int H, int W, int h, int w, ResizeGeom* g, int* tabs);
+int launch_resize(const uint8_t* in, uint8_t* out, int B, const ResizeGeom& g, const int* tabs_dev, hipStream_t s);

@@ -13,6 +13,8 @@ MI355X path.  Same flags.  Differences, all forced by the environment or by the 
   differs per frame: those frames go through the per-pair batch instead.  `--content-colors` keeps the frames' colours the
   other way (luminance-only transfer, applied to the result): the style stays shared, so it goes with the prepared style,
   `--mask-path` and `--warm-start`.
+* `--device-resize` (opt-in) applies `--content-size` on the device: the frames go up raw and are resized there, on the stream
+  of the call that stylizes them, to the bytes Pillow's bilinear resize gives on the host -- the same frames come out.
 """
 from __future__ import division, print_function
 
@@ -26,7 +28,7 @@ import time
 
 import numpy as np
 
-from .utils import get_files, get_img, save_img, resize_to, center_crop, _imresize
+from .utils import get_files, get_img, save_img, resize_to, resize_shape, center_crop, _imresize
 from .wct import WCT
 
 TMP_DIR = '_____fns_frames_%s/' % random.randint(0, 99999)
@@ -73,6 +75,11 @@ _FLAGS = [
                                   'state for the whole video; frames within tolerance of the cold ones, not bit-identical).  Needs '
                                   'the prepared-style path: not with --keep-colors, --swap5, --adain or --mask-path.  Later --passes '
                                   'run cold')),
+    (('--device-resize',), dict(action='store_true', default=False,
+                                help='apply --content-size on the device: frames are uploaded raw and resized there (the bytes of '
+                                     'the host resize); consecutive frames of one raw size are batched.  Needs --content-size > 0; not '
+                                     'with --keep-colors, with --content-colors --passes > 1, or with --swap5 --ss-stride > 1 (each '
+                                     'needs the resized frames on the host).  --style-size, --concat and label maps stay on the host')),
     (('--mask-styles',), dict(nargs='+', default=None, metavar='PATH',
                               help='the K style images of --mask-path, label 0 first; replaces --style-path; not with '
                                    '--keep-colors, --swap5 or --concat')),
@@ -131,6 +138,28 @@ def check_color_args(parser, args):
         parser.error('--content-colors with --passes > 1 needs --ss-stride 1 (a larger stride crops the frames of every pass)')
 
 
+def check_resize_args(parser, args):
+    """--device-resize: the combinations it refuses (parser.error exits)"""
+    if not args.device_resize:
+        return
+    if args.content_size <= 0:
+        parser.error('--device-resize applies --content-size: give --content-size > 0')
+    if args.keep_colors:
+        parser.error('--device-resize does not combine with --keep-colors (per-frame CORAL needs the resized frame on the host)')
+    if args.content_colors and args.passes > 1:
+        parser.error('--device-resize with --content-colors needs --passes 1 (the stand-alone colour op needs the resized frames '
+                     'on the host)')
+    if args.swap5 and args.ss_stride != 1:
+        parser.error('--device-resize with --swap5 needs --ss-stride 1 (a larger stride crops the resized frames on the host)')
+
+
+def device_size(args, group):
+    """--device-resize: the size --content-size gives the raw frames of `group` (resize= of the predict_frames calls), else None"""
+    if not getattr(args, 'device_resize', False):
+        return None
+    return resize_shape(group[0].shape[0], group[0].shape[1], args.content_size)
+
+
 def content_colors_frames(wct_model, stylized, frames):
     """the stand-alone op on a group of frames (after --passes > 1): the luminance of `stylized` on the colours of `frames`"""
     return np.concatenate([wct_model.sess.content_colors_batch(stylized[i:i + 32], frames[i:i + 32])
@@ -166,7 +195,7 @@ def stylize_frames_masked(wct_model, frame_files, mask_files, styles, args):
 
     def load(f):
         img = get_img(f)
-        if args.content_size > 0:
+        if args.content_size > 0 and not getattr(args, 'device_resize', False):
             img = resize_to(img, args.content_size)
         return img
 
@@ -184,10 +213,12 @@ def stylize_frames_masked(wct_model, frame_files, mask_files, styles, args):
             frames = out = np.stack(group)
             # --content-colors: fused into a single pass; after several plain passes the op runs once, against the input frames
             colors, n = getattr(args, 'content_colors', False), max(1, args.passes)
+            size = device_size(args, group)                       # --device-resize: pass 1 takes the raw frames
             for _ in range(n):
-                masks = np.stack([mask_labels(grey_of(m), k, out.shape[1:3]) for m in mask_files[i:j]])
+                masks = np.stack([mask_labels(grey_of(m), k, size or out.shape[1:3]) for m in mask_files[i:j]])
                 out = wct_model.predict_frames_masked(out, prepared, masks, args.alpha, args.adain, batch=args.batch,
-                                                      content_colors=colors and n == 1)
+                                                      content_colors=colors and n == 1, resize=size)
+                size = None
             if colors and n > 1:
                 out = content_colors_frames(wct_model, out, frames)
             for f, o in zip(frame_files[i:j], out):
@@ -202,7 +233,7 @@ def stylize_frames(wct_model, frame_files, style_img, args):
     """Yield (frame_file, stylized uint8 image) in order; consecutive same-sized frames are batched."""
     def load(f):
         img = get_img(f)
-        if args.content_size > 0:
+        if args.content_size > 0 and not getattr(args, 'device_resize', False):
             img = resize_to(img, args.content_size)
         return img
 
@@ -222,7 +253,7 @@ def stylize_frames(wct_model, frame_files, style_img, args):
     def run(frames, style):
         style = prepared if prepared is not None else style
         out = wct_model.predict_frames(frames, style, args.alpha, args.swap5, args.ss_alpha, args.adain, batch=args.batch, warm=warm,
-                                       content_colors=colors and args.passes <= 1)
+                                       content_colors=colors and args.passes <= 1, resize=device_size(args, frames))
         for _ in range(args.passes - 1):                      # later passes: plain WCT, as stylize_video.py:124-126
             out = wct_model.predict_frames(out, style, args.alpha, adain=args.adain, batch=args.batch)
         if colors and args.passes > 1:
@@ -271,6 +302,7 @@ def main(argv=None):
     check_mask_args(parser, args)
     check_warm_args(parser, args)
     check_color_args(parser, args)
+    check_resize_args(parser, args)
     if args.synthetic_weights is None and not args.checkpoints:
         parser.error('--checkpoints is required (stylize.py:17) unless --synthetic-weights SEED is given')
     start = time.time()

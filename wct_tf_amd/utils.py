@@ -42,6 +42,14 @@ def resize_to(img, resize=512):
     return _imresize(img, (round(h * scale), resize))
 
 
+def resize_shape(h, w, short_side=512):
+    """the (h, w) that resize_to gives an h x w image: the same arithmetic, the same round"""
+    scale = short_side / min(h, w)
+    if h < w:
+        return short_side, round(w * scale)
+    return round(h * scale), short_side
+
+
 def center_crop(img, size=256):
     """square centre crop; an image with a side below `size` is scaled up first (utils.py:27-38)"""
     if min(img.shape[:2]) < size:

@@ -21,7 +21,7 @@ import re
 
 import numpy as np
 
-from .context import Context, PreparedStyle, check_prepared, check_texture, check_warm, split_styles
+from .context import Context, PreparedStyle, check_prepared, check_resize, check_texture, check_warm, split_styles
 from .model import WCTModel
 from .weights import load_weights
 
@@ -260,18 +260,21 @@ class WCT(object):
         return self.sess.stylize_masked(content, styles, mask, self.relu_targets, alpha=alpha, adain=adain,
                                         wct_mode=self.wct_mode, swap5=bool(swap5), content_colors=content_colors)
 
-    def predict_frames_masked(self, frames, styles, masks, alpha=1, adain=False, batch=16, content_colors=False):
+    def predict_frames_masked(self, frames, styles, masks, alpha=1, adain=False, batch=16, content_colors=False, resize=None):
         '''Spatial control of a video: same-sized frames [F][H][W][3], a label map per frame `masks` [F][H][W] (or one [H][W] map
            used for every frame), `styles` K images -- prepared once here -- or K PreparedStyle objects.  Frame f equals
            predict_masked(frames[f], styles, masks[f]) bit for bit; the frames go through the device in batches of `batch`
-           (<= 32), the regions of a batch sharing every launch and the eigensolves.  Returns uint8 [F][Ho][Wo][3].'''
+           (<= 32), the regions of a batch sharing every launch and the eigensolves.  Returns uint8 [F][Ho][Wo][3].
+           resize (h, w): as in predict_frames; the label maps are given at the resized size.'''
         from ._lib import mask_labels_frames
         frames = np.asarray(frames)
         if frames.ndim != 4 or frames.shape[3] != 3:
             raise ValueError('expected [F][H][W][3] frames, got shape %s' % (frames.shape,))
+        if resize is not None:
+            resize = check_resize(resize)                        # ValueError before any GPU call
         handles, images = split_styles(list(styles))             # ValueError: images and prepared styles in one list
         k = len(handles) or len(images)
-        masks = mask_labels_frames(masks, k, len(frames), frames.shape[1:3])    # ValueError before any GPU call
+        masks = mask_labels_frames(masks, k, len(frames), resize or frames.shape[1:3])    # ValueError before any GPU call
         if handles:
             check_prepared(self.sess, handles, self.relu_targets)
         if frames.dtype != np.uint8:
@@ -281,24 +284,31 @@ class WCT(object):
             batch = max(1, min(32, int(batch)))
             return np.concatenate([self.sess.stylize_prepared_masked_batch(frames[i:i + batch], handles or own, masks[i:i + batch],
                                                                            self.relu_targets, alpha=alpha, adain=adain,
-                                                                           wct_mode=self.wct_mode, content_colors=content_colors)
+                                                                           wct_mode=self.wct_mode, content_colors=content_colors,
+                                                                           resize=resize)
                                    for i in range(0, len(frames), batch)], axis=0)
         finally:
             for h in own:
                 h.close()
 
     def predict_frames(self, frames, style, alpha=1, swap5=False, ss_alpha=1, adain=False, batch=16, warm=None,
-                       content_colors=False):
+                       content_colors=False, resize=None):
         '''Stylize same-sized frames [F][H][W][3] with ONE style image (the loop of stylize_video.py:112-121,
            which calls predict() once per frame and so re-runs the style encoder, the style statistics and the
            style eigendecompositions every frame).  Here the style side runs once per batch of `batch` frames;
            every frame equals predict(frame, style) bit for bit.  Returns uint8 [F][Ho][Wo][3].
            With a PreparedStyle (prepare_style) the style side does not run at all; the frames are the same.
            With a PreparedStyle and `warm` (a WarmState) every batch starts its content eigensolves from the last frame of the
-           batch before it (the state's, for the first): frames within tolerance of the cold ones, not bit-identical.'''
+           batch before it (the state's, for the first): frames within tolerance of the cold ones, not bit-identical.
+           resize (h, w): the frames are raw and are resized to h x w on the device, in front of the call and on its stream
+           (Context.resize_batch_dev: Pillow's bilinear bytes) -- predict_frames on utils._imresize(frame, (h, w)), bit for bit.'''
         frames = np.asarray(frames)
         if warm is not None:
             self._check_warm(warm, style, swap5, adain)                           # ValueError before any GPU call
+        if resize is not None:
+            resize = check_resize(resize)                                         # ValueError before any GPU call
+            if swap5 is True and self.ss_stride != 1:
+                raise ValueError('resize with swap5 needs ss_stride 1: a larger stride crops the resized frames on the host')
         if isinstance(style, PreparedStyle):
             check_prepared(self.sess, [style], self.relu_targets, swap5)          # ValueError before any GPU call
             assert frames.ndim == 4
@@ -307,7 +317,7 @@ class WCT(object):
             batch = max(1, min(32, int(batch)))
             return np.concatenate([self.sess.stylize_prepared_batch(frames[i:i + batch], style, self.relu_targets, alpha=alpha,
                                                                     adain=adain, wct_mode=self.wct_mode, warm=warm,
-                                                                    content_colors=content_colors)
+                                                                    content_colors=content_colors, resize=resize)
                                    for i in range(0, len(frames), batch)], axis=0)
         style = np.asarray(style)
         assert frames.ndim == 4 and style.ndim == 3
@@ -324,7 +334,7 @@ class WCT(object):
             self.sess.set_style_swap(ss_alpha, self.ss_patch_size, self.ss_stride)
         batch = max(1, min(32, int(batch)))
         outs = [self.sess.stylize_batch(frames[i:i + batch], style, self.relu_targets, alpha=alpha, adain=adain,
-                                        wct_mode=self.wct_mode, swap5=bool(swap5), content_colors=content_colors)
+                                        wct_mode=self.wct_mode, swap5=bool(swap5), content_colors=content_colors, resize=resize)
                 for i in range(0, len(frames), batch)]
         return np.concatenate(outs, axis=0)
 
