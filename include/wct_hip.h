@@ -467,6 +467,61 @@ int wct_stylize_prepared_banded_dev(wct_ctx* ctx, const uint8_t* content_dev, in
 int wct_stylize_prepared_banded(wct_ctx* ctx, const uint8_t* content, int Hc, int Wc, const wct_style* style, const int* levels,
                                 int n_levels, float alpha, unsigned flags, int band_rows, int stat_rows, uint8_t* out);
 
+/* ---- seamless textures: periodic synthesis on wrap-around halos ---------------------------
+ * Every conv of the encoder and the decoders reflect-pads its input (model.py:135-139, 245-304), so the left edge of a frame
+ * knows nothing of its right edge and a synthesized texture cannot be repeated without a seam.  The calls below run the same
+ * network on a torus, on the unchanged kernels: before each encoder and each decoder of the chain the map is extended, on the
+ * device, by a halo of its own pixels taken modulo its size; the kernels run on the extended map; the interior is kept; the
+ * transform runs on the interior alone (its statistics are those of one period).  A halo as wide as a level's receptive field
+ * makes the interior exactly the periodic network's output (the argument of the banded calls, with another halo source):
+ *   encoder of relu1_1 .. relu5_1: 16, 16, 16, 48, 96 image pixels on all four sides;
+ *   decoder: 2, 2, 4, 4, 6 feature pixels on top and left (even, so that the interior starts on an upsampled pair and a Winograd
+ *     row pair), 2, 2, 3, 4, 5 on bottom and right.
+ * Size rule: H and W multiples of 2^(l_max - 1), l_max the deepest level of the chain (ceil-mode pooling of an odd size is not
+ *   periodic) -- else WCT_STATUS_ARG, the multiple in the message; the minimum size of any content applies; frames have the
+ *   size of the tile.  A tile whose padded maps pass the limit of one launch (2^31 bytes) is WCT_STATUS_ARG.
+ * wct_wrap_halo (reference: none): the halo of a level -- *enc, *dec_before, *dec_after.  wct_wrap_check: the size rule and the
+ *   launch limits of an H x W tile for these levels.  Both pure host code.
+ * wct_wrap_pad_batch_dev (reference: none; np.pad(mode='wrap')): in_dev [B][H][W][C] fp32 -> out_dev
+ *   [B][top + H + bottom][left + W + right][C], out(y, x) = in((y - top) mod H, (x - left) mod W), the modulo non-negative (a halo
+ *   may be several periods wide).  C a multiple of 4 moves 16-byte groups (both pointers 16-byte aligned), any other C floats.
+ *   B = 1 .. 32; one launch, asynchronous.  wct_wrap_pad: B = 1, host pointers, blocking.  Checks of the kernel, like
+ *   wct_mask_compact; a padded map of 2^31 bytes is WCT_STATUS_ARG.
+ * wct_encode_wrap / wct_decode_wrap (model.py:135-139 / 245-304 on a torus): wct_encode / wct_decode of the periodically extended
+ *   map, the interior returned -- bit for bit what wct_encode / wct_decode give on the map padded by the halo on the host.  Host
+ *   pointers, blocking.  img01 [H][W][3] -> feat [H / s][W / s][C]; feat [h][w][C] -> img [h s][w s][3], s = 2^(level - 1).
+ * wct_stylize_prepared_wrap_batch_dev (wct.py:70-106 on a torus): B = 1 .. 32 tiles [B][Hc][Wc][3] on the device on a prepared
+ *   style, frames [B][Hc][Wc][3]; per level: pad, encode, crop the tap, transform under the state key of the unpadded map (no
+ *   fused epilogue statistics), pad, decode, crop.  A periodic content gives a periodic frame; frame f does not depend on B.
+ *   Asynchronous the way wct_stylize_prepared_batch_dev is (states and buffers first).  wct_stylize_prepared_wrap: B = 1, host
+ *   pointers, blocking.  flags: WCT_FLAG_MODE_NP, WCT_FLAG_ADAIN, WCT_FLAG_IMAGES_F32.
+ * wct_texture_prepared_wrap_batch_dev / wct_texture_prepared_wrap (Li et al. sec. 4.3): wct_texture_prepared_batch_dev /
+ *   wct_texture_prepared with the wrap chain in the place of the plain one: the same noise, `passes` wrap runs chained in device
+ *   memory, tiles [B][H][W][3].  Sample f equals `passes` chained wct_stylize_prepared_wrap_batch_dev calls on
+ *   wct_texture_noise(.., sample f) bit for bit.  flags: WCT_FLAG_MODE_NP, WCT_FLAG_ADAIN.
+ * WCT_STATUS_ARG, each with a message: WCT_FLAG_CONTENT_COLORS, WCT_FLAG_SWAP5, WCT_FLAG_STYLE_SHARED, a size that breaks the
+ *   size rule or the launch limit, a level outside the handle's set, B outside 1 .. 32, a null pointer.  A handle that is not
+ *   live is WCT_STATUS_STATE.  A refusal leaves the ctx usable.
+ * Out of scope: tileable mixes, masks, warm states, style-swap and content colours; wrap combined with bands (tiles past the
+ *   launch limit); sizes that are not multiples of the deepest stride. */
+int wct_wrap_halo(int level, int* enc, int* dec_before, int* dec_after);
+int wct_wrap_check(int H, int W, const int* levels, int n_levels);
+int wct_wrap_pad_batch_dev(wct_ctx* ctx, const float* in_dev, int B, int H, int W, int C, int top, int bottom, int left, int right,
+                           float* out_dev);
+int wct_wrap_pad(wct_ctx* ctx, const float* x, int H, int W, int C, int top, int bottom, int left, int right, float* y);
+int wct_encode_wrap(wct_ctx* ctx, const float* img01, int H, int W, int level, float* feat);
+int wct_decode_wrap(wct_ctx* ctx, const float* feat, int h, int w, int level, float* img);
+int wct_stylize_prepared_wrap_batch_dev(wct_ctx* ctx, const uint8_t* content_dev, int Hc, int Wc, int B, const wct_style* style,
+                                        const int* levels, int n_levels, float alpha, unsigned flags, uint8_t* out_dev);
+int wct_stylize_prepared_wrap(wct_ctx* ctx, const uint8_t* content, int Hc, int Wc, const wct_style* style, const int* levels,
+                              int n_levels, float alpha, unsigned flags, uint8_t* out);
+int wct_texture_prepared_wrap_batch_dev(wct_ctx* ctx, int H, int W, int B, unsigned seed, unsigned first_sample, int smooth,
+                                        const wct_style* style, const int* levels, int n_levels, int passes, float alpha,
+                                        unsigned flags, uint8_t* out_dev);
+int wct_texture_prepared_wrap(wct_ctx* ctx, int H, int W, unsigned seed, unsigned sample, int smooth,
+                              const wct_style* style, const int* levels, int n_levels, int passes, float alpha,
+                              unsigned flags, uint8_t* out_host);
+
 /* ---- decoder training (model.py:123-223, train.py:129-196) ---------------------------
  * One optimiser step of the decoder for relu<level>_1 (the encoder is frozen, model.py:202):
  *   F = enc(x); D = dec(F); F' = enc(D);

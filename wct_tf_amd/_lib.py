@@ -90,6 +90,18 @@ SIGNATURES = [
     ('wct_transform_chunked', C.c_int, [_P, _F, C.c_int, _F, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float, C.c_int, _F, _I]),
     ('wct_stylize_prepared_banded_dev', C.c_int, [_P, _P, C.c_int, C.c_int, _P, _I, C.c_int, C.c_float, C.c_uint, C.c_int, C.c_int, _P]),
     ('wct_stylize_prepared_banded', C.c_int, [_P, _U8, C.c_int, C.c_int, _P, _I, C.c_int, C.c_float, C.c_uint, C.c_int, C.c_int, _U8]),
+    ('wct_wrap_halo', C.c_int, [C.c_int, _I, _I, _I]),
+    ('wct_wrap_check', C.c_int, [C.c_int, C.c_int, _I, C.c_int]),
+    ('wct_wrap_pad_batch_dev', C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+    ('wct_wrap_pad', C.c_int, [_P, _F, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _F]),
+    ('wct_encode_wrap', C.c_int, [_P, _F, C.c_int, C.c_int, C.c_int, _F]),
+    ('wct_decode_wrap', C.c_int, [_P, _F, C.c_int, C.c_int, C.c_int, _F]),
+    ('wct_stylize_prepared_wrap_batch_dev', C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _I, C.c_int, C.c_float, C.c_uint, _P]),
+    ('wct_stylize_prepared_wrap', C.c_int, [_P, _U8, C.c_int, C.c_int, _P, _I, C.c_int, C.c_float, C.c_uint, _U8]),
+    ('wct_texture_prepared_wrap_batch_dev', C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_uint, C.c_uint, C.c_int, _P, _I, C.c_int,
+                                                      C.c_int, C.c_float, C.c_uint, _P]),
+    ('wct_texture_prepared_wrap', C.c_int, [_P, C.c_int, C.c_int, C.c_uint, C.c_uint, C.c_int, _P, _I, C.c_int, C.c_int, C.c_float,
+                                            C.c_uint, _U8]),
     ('wct_train_step', C.c_int, [_P, C.c_int, _F, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float,
                                  C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, _F]),
     ('wct_get_decoder_layer', C.c_int, [_P, C.c_int, C.c_int, _F, _F, _F, _F]),

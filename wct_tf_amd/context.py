@@ -267,6 +267,26 @@ def band_plan(h, w, relu_target, band_rows=0):
     return rows
 
 
+def wrap_halo(relu_target):
+    """wct_wrap_halo: the wrap-around halo of one level as (enc, dec_before, dec_after) -- image pixels on every side of the
+    encoder's input, feature pixels in front of and behind the decoder's.  Host code only: no context, no GPU."""
+    level = _levels([relu_target])[0]
+    e, d0, d1 = C.c_int(), C.c_int(), C.c_int()
+    check(_lib.load().wct_wrap_halo(level, C.byref(e), C.byref(d0), C.byref(d1)))
+    return e.value, d0.value, d1.value
+
+
+def check_wrap(h, w, relu_targets):
+    """The size rule of the wrap calls, before any GPU call (wct_wrap_check, host code only): h and w multiples of the deepest
+    level's stride, the tile large enough for that level, its padded maps inside one launch -- else ValueError with the
+    library's message.  -> (h, w)"""
+    lv = _levels(relu_targets)
+    lib = _lib.load()
+    if lib.wct_wrap_check(int(h), int(w), (C.c_int * len(lv))(*lv), len(lv)) != 0:
+        raise ValueError(lib.wct_last_error().decode())
+    return int(h), int(w)
+
+
 def split_styles(styles):
     """(handles, images) of a list of styles: one of the two is empty, a list that mixes PreparedStyle objects and images is a
     ValueError."""
@@ -540,6 +560,53 @@ class Context(object):
         check(self.lib.wct_decode_banded(self.h, fptr(f), h, w, level, int(band_rows), fptr(img)))
         return img
 
+    # ---- wrap-around halos: the periodic network on the unchanged kernels ------------------------
+    def wrap_halo(self, relu_target):
+        """The wrap-around halo of one level as (enc, dec_before, dec_after) (wrap_halo)"""
+        return wrap_halo(relu_target)
+
+    def wrap_pad_batch_dev(self, in_dev, batch, h, w, c, pads, out_dev):
+        """`batch` fp32 maps [batch][h][w][c] resident in HBM extended periodically by pads = (top, bottom, left, right) into out_dev
+        (wct_wrap_pad_batch_dev): one launch, asynchronous."""
+        t, b, l, r = (int(v) for v in pads)
+        check(self.lib.wct_wrap_pad_batch_dev(self.h, in_dev, int(batch), int(h), int(w), int(c), t, b, l, r, out_dev))
+
+    def wrap_pad(self, x, pads):
+        """x [H][W][C] fp32 -> np.pad(x, ((top, bottom), (left, right), (0, 0)), mode='wrap') for pads = (top, bottom, left,
+        right), on the device (wct_wrap_pad): the kernel of the wrap calls alone."""
+        a = f32(x)
+        if a.ndim != 3 or a.size == 0:
+            raise ValueError('wrap_pad takes an HxWxC map, got shape %s' % (a.shape,))
+        t, b, l, r = (int(v) for v in pads)
+        if min(t, b, l, r) < 0:
+            raise ValueError('pads must be >= 0, got %r' % (pads,))
+        h, w, c = a.shape
+        y = np.empty((t + h + b, l + w + r, c), np.float32)
+        check(self.lib.wct_wrap_pad(self.h, fptr(a), h, w, c, t, b, l, r, fptr(y)))
+        return y
+
+    def encode_wrap(self, img01, relu_target):
+        """encode() on a torus (wct_encode_wrap): the map of the image extended periodically by the level's halo, its interior
+        kept -- encode(np.pad(img01, halo, mode='wrap')) cropped, bit for bit.  H and W multiples of the level's stride."""
+        level = _levels([relu_target])[0]
+        x = f32(img01)
+        h, w, _ = x.shape
+        check_wrap(h, w, [level])
+        s = 1 << (level - 1)
+        feat = np.empty((h // s, w // s, _LEVEL_C[level]), np.float32)
+        check(self.lib.wct_encode_wrap(self.h, fptr(x), h, w, level, fptr(feat)))
+        return feat
+
+    def decode_wrap(self, feat, relu_target):
+        """decode() on a torus (wct_decode_wrap): the image of the map extended periodically by the level's halo, its interior kept"""
+        level = _levels([relu_target])[0]
+        f = f32(feat)
+        h, w, _ = f.shape
+        s = 1 << (level - 1)
+        img = np.empty((h * s, w * s, 3), np.float32)
+        check(self.lib.wct_decode_wrap(self.h, fptr(f), h, w, level, fptr(img)))
+        return img
+
     def transform_chunked(self, content, style, alpha, mode, chunk_rows, eps=-1.0, return_sweeps=False):
         """transform() with the content statistics pooled over chunks of chunk_rows rows (wct_transform_chunked); 0, or at
         least the content's rows: one chunk, transform()'s output bit for bit"""
@@ -671,6 +738,39 @@ class Context(object):
         out = np.empty((ho, wo, 3), np.uint8)
         check(self.lib.wct_texture_prepared(self.h, h, w, int(seed), int(sample), int(bool(smooth)), style.h, (C.c_int * len(lv))(*lv),
                                             len(lv), int(passes), float(alpha), _flags(adain, wct_mode), out.ctypes.data_as(_lib._U8)))
+        return out
+
+    def texture_prepared_wrap_batch_dev(self, h, w, batch, seed, first_sample, style, relu_targets, passes, alpha, out_dev, adain=False,
+                                        wct_mode='tf', smooth=False):
+        """texture_prepared_batch_dev on a torus (wct_texture_prepared_wrap_batch_dev): seamless tiles [batch][h][w][3] into device
+        memory -- the same noise, `passes` runs of the wrap chain.  h and w multiples of the deepest level's stride.  Asynchronous."""
+        h, w = check_texture((h, w), passes, batch, seed, first_sample)
+        lv = check_prepared(self, [style], relu_targets)
+        check_wrap(h, w, lv)
+        check(self.lib.wct_texture_prepared_wrap_batch_dev(self.h, h, w, int(batch), int(seed), int(first_sample), int(bool(smooth)),
+                                                           style.h, (C.c_int * len(lv))(*lv), len(lv), int(passes), float(alpha),
+                                                           _flags(adain, wct_mode), out_dev))
+
+    def texture_prepared_wrap_batch(self, h, w, batch, seed, first_sample, style, relu_targets, passes=3, alpha=1.0, adain=False,
+                                    wct_mode='tf', smooth=False):
+        """texture_prepared_wrap_batch_dev with the tiles brought to the host -> uint8 [batch][h][w][3].  Sample f equals the noise
+        texture_noise(h, w, seed, first_sample + f) through `passes` chained stylize_prepared_wrap_batch calls, bit for bit."""
+        h, w = check_texture((h, w), passes, batch, seed, first_sample)
+        check_wrap(h, w, check_prepared(self, [style], relu_targets))
+        out = np.empty((int(batch), h, w, 3), np.uint8)
+        return self._host_batch([], out, lambda do: self.texture_prepared_wrap_batch_dev(
+            h, w, batch, seed, first_sample, style, relu_targets, passes, alpha, do, adain=adain, wct_mode=wct_mode, smooth=smooth))
+
+    def texture_prepared_wrap(self, h, w, seed, sample, style, relu_targets, passes=3, alpha=1.0, adain=False, wct_mode='tf',
+                              smooth=False):
+        """One seamless tile -> uint8 [h][w][3] (wct_texture_prepared_wrap, blocking): texture_prepared_wrap_batch with one sample."""
+        h, w = check_texture((h, w), passes, 1, seed, sample)
+        lv = check_prepared(self, [style], relu_targets)
+        check_wrap(h, w, lv)
+        out = np.empty((h, w, 3), np.uint8)
+        check(self.lib.wct_texture_prepared_wrap(self.h, h, w, int(seed), int(sample), int(bool(smooth)), style.h,
+                                                 (C.c_int * len(lv))(*lv), len(lv), int(passes), float(alpha), _flags(adain, wct_mode),
+                                                 out.ctypes.data_as(_lib._U8)))
         return out
 
     # ---- the hot path ------------------------------------------------------
@@ -829,6 +929,35 @@ class Context(object):
         if resize is not None:
             return self._host_batch_resized(c, (hc, wc), [], out, enqueue)
         return self._host_batch([c], out, enqueue)
+
+    def stylize_prepared_wrap_batch_dev(self, content_dev, hc, wc, batch, style, relu_targets, alpha, out_dev, adain=False, wct_mode='tf'):
+        """stylize_prepared_batch_dev on a torus (wct_stylize_prepared_wrap_batch_dev): every encoder and decoder of the chain sees
+        its input extended periodically, so a periodic content gives a periodic frame [batch][hc][wc][3].  Asynchronous."""
+        lv = check_prepared(self, [style], relu_targets)
+        check_wrap(hc, wc, lv)
+        check(self.lib.wct_stylize_prepared_wrap_batch_dev(self.h, content_dev, int(hc), int(wc), int(batch), style.h,
+                                                           (C.c_int * len(lv))(*lv), len(lv), float(alpha), _flags(adain, wct_mode), out_dev))
+
+    def stylize_prepared_wrap_batch(self, frames, style, relu_targets, alpha=1.0, adain=False, wct_mode='tf'):
+        """stylize_prepared_wrap_batch_dev with host arrays: frames [B][H][W][3] uint8 (B <= 32; H and W multiples of the deepest
+        level's stride) -> [B][H][W][3] uint8.  No mix, mask, warm state, style-swap or content colours on this path."""
+        lv = check_prepared(self, [style], relu_targets)
+        c = np.asarray(frames)
+        if c.dtype != np.uint8 or c.ndim != 4 or c.shape[3] != 3 or not 1 <= c.shape[0] <= _lib.BATCH_MAX:
+            raise ValueError('expected 1 .. %d uint8 frames [B][H][W][3], got %s of shape %s' % (_lib.BATCH_MAX, c.dtype, c.shape))
+        c = u8(c)
+        hc, wc = check_wrap(c.shape[1], c.shape[2], lv)
+        return self._host_batch([c], np.empty_like(c), lambda dc, do: self.stylize_prepared_wrap_batch_dev(
+            dc, hc, wc, c.shape[0], style, relu_targets, alpha, do, adain=adain, wct_mode=wct_mode))
+
+    def stylize_prepared_wrap(self, content, style, relu_targets, alpha=1.0, adain=False, wct_mode='tf'):
+        """One tile through wct_stylize_prepared_wrap (blocking): content HxWx3 in [0,255] as in stylize_prepared -> uint8 HxWx3"""
+        lv = check_prepared(self, [style], relu_targets)
+        check_wrap(np.shape(content)[0], np.shape(content)[1], lv)
+        c, arr, out, flags = self._prepared_args(content, relu_targets, adain, wct_mode)
+        check(self.lib.wct_stylize_prepared_wrap(self.h, c.ctypes.data_as(_lib._U8), c.shape[0], c.shape[1], style.h, arr, len(arr),
+                                                 float(alpha), flags, out.ctypes.data_as(_lib._U8)))
+        return out
 
     def stylize_prepared_masked(self, content, styles, mask, relu_targets, alpha=1.0, adain=False, wct_mode='tf', content_colors=False):
         """stylize_masked() with K PreparedStyle objects in the place of the K images: the same frame, bit for bit."""

@@ -98,6 +98,8 @@ struct wct_ctx {
   DevBuf tex_noise, tex[2];        // texture synthesis: the noise images, and the uint8 frames between two passes (alternating)
   DevBuf band_f, band_g, band_img; // banded stylization: a level's full fp32 feature map and its fp16 transform (either may pass
                                    // 2^31 bytes: every launch sees a slice), and the decoded image of one band with its halo
+  DevBuf wrap_img, wrap_g, wrap_f; // periodic synthesis (wrap.hip): a level's image with its wrap-around halo (then the decoded image
+                                   // with its halo), the fp16 transform with its halo, and the tap cropped to the tile
   DevBuf resize_tab;               // on-device resize: the tap and bounds tables of the last geometry (resize_geom; H = 0: none yet),
   std::vector<int> resize_host;    // and the host copy they were uploaded from
   ResizeGeom resize_geom = {};
@@ -235,6 +237,20 @@ int run_decoder_banded(wct_ctx* c, int level, const half_t* G, int h, int w, int
 int chunk_rule(int h, int w, int C, int stat_rows, int* rows, int* K);
 int run_transform_chunked(wct_ctx* c, const float* fc, size_t Nc, int n_full, int K, const float* fs, int Ns, int C, float alpha,
                           unsigned flags, float eps, half_t* out16, float* out32, int* sweeps_dev, const WctStyleRef* prep = nullptr);
+
+// the wrap plan (periodic synthesis): the halo of a level -- image pixels around the encoder's input, feature pixels in front of
+// and behind the decoder's --, and the checks of a tile H x W for a chain (its geometry into *chain): the size rule, the launch limits
+void wrap_halo(int level, int* enc, int* dec_before, int* dec_after);
+int wrap_chain_check(int H, int W, const int* levels, int n_levels, Chain* chain);
+
+// (banded.hip as well: the wrap drivers)  run_encoder to relu<level>_1 of B tiles img [B][H][W][3] (H, W multiples of 2^(level - 1)) extended periodically by the level's
+// halo, the interior of the tap into tap [B][h][w][C] fp32 (c->wrap_img and c->feat_c hold the padded maps); run_decoder of B maps
+// G [B][h][w][C] fp16 extended the same way, the interior of the image into img_out [B][h << (l - 1)][w << (l - 1)][3]
+int run_encoder_wrap(wct_ctx* c, const float* img, int B, int H, int W, int clamp01, int level, float* tap);
+int run_decoder_wrap(wct_ctx* c, int level, const half_t* G, int B, int h, int w, float* img_out);
+// what the two need in c->wrap_img / c->feat_c and c->wrap_g / c->wrap_img, ensured here: a driver calls them before its first launch
+int wrap_encoder_buffers(wct_ctx* c, int B, int H, int W, int level);
+int wrap_decoder_buffers(wct_ctx* c, int B, int h, int w, int level);
 
 // ---- api_stylize.hip ------------------------------------------------------
 int warm_live(const wct_ctx* c, const wct_warm* wm);     // WCT_ERR_STATE unless wm is a live warm state of c

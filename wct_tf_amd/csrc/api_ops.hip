@@ -466,6 +466,66 @@ extern "C" int wct_decode_banded(wct_ctx* c, const float* feat, int h, int w, in
   return fetch(c, img, c->img_t[0].p, ib);
 }
 
+// Wrap-around halos, op level (csrc/wrap.hip; the plan and the drivers in banded.hip)
+extern "C" int wct_wrap_pad_batch_dev(wct_ctx* c, const float* in, int B, int H, int W, int C, int top, int bottom, int left, int right,
+                                      float* out) {
+  ARG_CHECK(c != nullptr);
+  if (!in || !out) { wct_set_error("wrap pad: null map pointer"); return WCT_ERR_ARG; }
+  if (B < 1 || B > 32) { wct_set_error("wrap pad: B = %d maps, must be 1 .. 32", B); return WCT_ERR_ARG; }
+  if (H < 1 || W < 1 || C < 1 || top < 0 || bottom < 0 || left < 0 || right < 0) {
+    wct_set_error("wrap pad: a %dx%dx%d map with pads %d %d %d %d (sizes >= 1, pads >= 0)", H, W, C, top, bottom, left, right);
+    return WCT_ERR_ARG;
+  }
+  HIP_TRY(hipSetDevice(c->device));
+  ProfScope ps(c, 7, 0, 2.0 * B * ((double)top + H + bottom) * ((double)left + W + right) * C * 4);
+  return launch_wrap_pad(in, out, B, H, W, C, 4, top, bottom, left, right, c->stream);
+}
+
+extern "C" int wct_wrap_pad(wct_ctx* c, const float* x, int H, int W, int C, int top, int bottom, int left, int right, float* y) {
+  ARG_CHECK(c && x && y && H >= 1 && W >= 1 && C >= 1 && top >= 0 && bottom >= 0 && left >= 0 && right >= 0);
+  HIP_TRY(hipSetDevice(c->device));
+  const unsigned long long out_elems = ((unsigned long long)top + H + bottom) * ((unsigned long long)left + W + right) * (unsigned long long)C;
+  if (out_elems >= (1ull << 29)) {                           // (launch_wrap_pad's bound, before the staging buffers are sized)
+    wct_set_error("wrap pad: the padded %dx%dx%d map passes 2^31 bytes in one launch", H, W, C);
+    return WCT_ERR_ARG;
+  }
+  void* dx;
+  TRY(stage_in(c, 0, x, (size_t)H * W * C * 4, &dx));
+  TRY(ensure(c, c->stage[1], (size_t)out_elems * 4));
+  TRY(wct_wrap_pad_batch_dev(c, (const float*)dx, 1, H, W, C, top, bottom, left, right, (float*)c->stage[1].p));
+  return fetch(c, y, c->stage[1].p, (size_t)out_elems * 4);
+}
+
+extern "C" int wct_encode_wrap(wct_ctx* c, const float* img01, int H, int W, int level, float* feat) {
+  ARG_CHECK(c && img01 && feat && level >= 1 && level <= 5);
+  HIP_TRY(hipSetDevice(c->device));
+  Chain chain;
+  TRY(wrap_chain_check(H, W, &level, 1, &chain));
+  void* dimg;
+  TRY(stage_in(c, 0, img01, (size_t)H * W * 3 * 4, &dimg));
+  const size_t fb = (size_t)chain.lv[0].h * chain.lv[0].w * LEVEL_C[level] * 4;
+  TRY(ensure(c, c->wrap_f, fb));
+  TRY(run_encoder_wrap(c, (const float*)dimg, 1, H, W, 0, level, (float*)c->wrap_f.p));
+  return fetch(c, feat, c->wrap_f.p, fb);
+}
+
+extern "C" int wct_decode_wrap(wct_ctx* c, const float* feat, int h, int w, int level, float* img) {
+  ARG_CHECK(c && feat && img && level >= 1 && level <= 5 && h >= 1 && w >= 1 && h <= (1 << 26) && w <= (1 << 26));
+  HIP_TRY(hipSetDevice(c->device));
+  const int C = LEVEL_C[level], scale = 1 << (level - 1);
+  Chain chain;
+  TRY(wrap_chain_check(h * scale, w * scale, &level, 1, &chain));
+  void* df;
+  const size_t n = (size_t)h * w * C;
+  TRY(stage_in(c, 0, feat, n * 4, &df));
+  TRY(ensure(c, c->wct_out, n * 2));
+  TRY(launch_f32_to_f16((float*)df, (half_t*)c->wct_out.p, n, c->stream));
+  const size_t ib = (size_t)h * scale * w * scale * 3 * 4;
+  TRY(ensure(c, c->img_t[0], ib));
+  TRY(run_decoder_wrap(c, level, (const half_t*)c->wct_out.p, 1, h, w, (float*)c->img_t[0].p));
+  return fetch(c, img, c->img_t[0].p, ib);
+}
+
 extern "C" int wct_coral_stats(wct_ctx* c, const uint8_t* img, int H, int W, double sums[9]) {
   ARG_CHECK(c && img && sums && H > 0 && W > 0);
   HIP_TRY(hipSetDevice(c->device));

@@ -817,6 +817,121 @@ extern "C" int wct_texture_prepared(wct_ctx* c, int H, int W, unsigned seed, uns
   return eig_status(c);
 }
 
+// ---------------------------------------------------------------------------
+// periodic (tileable) stylization and synthesis: every encoder and decoder of the chain runs on the map extended by a halo of its
+// own pixels modulo its size (wrap.hip; the halos and the argument in banded.hip), the transform on the tile alone.  The
+// reference reflect-pads every conv (model.py:135-139, 245-304) and so cannot make a tile; this is that network on a torus.
+// ---------------------------------------------------------------------------
+static int wrap_flags_ok(unsigned flags) {
+  if (flags & WCT_FLAG_CONTENT_COLORS) {
+    wct_set_error("wrap: WCT_FLAG_CONTENT_COLORS is not served on the periodic path");
+    return WCT_ERR_ARG;
+  }
+  if (flags & WCT_FLAG_SWAP5) { wct_set_error("wrap: WCT_FLAG_SWAP5 (style-swap) is not served on the periodic path"); return WCT_ERR_ARG; }
+  return style_flags_ok(flags);
+}
+
+// The body of the wrap calls (their pointer and flag checks done): B tiles [B][Hc][Wc][3] on the device (uint8, or fp32 with
+// WCT_FLAG_IMAGES_F32), frames of the same size.  Asynchronous unless the handle has to compute a state or a buffer grows, both of
+// which happen before the first launch.
+static int stylize_prepared_wrap_dev(wct_ctx* c, const void* content, int Hc, int Wc, int B, const wct_style* style, const int* levels,
+                                     int n_levels, float alpha, unsigned flags, uint8_t* out) {
+  HIP_TRY(hipSetDevice(c->device));
+  TRY(style_live(c, style));
+  TRY(check_levels(c, levels, n_levels, &style, 1));
+  Chain chain;
+  TRY(wrap_chain_check(Hc, Wc, levels, n_levels, &chain));
+
+  // the states of every level under the key of the unpadded map (the transform never sees the halo), and every buffer of the call
+  ++c->style_clock;
+  std::vector<WctStyleRef> refs;
+  std::vector<int> ns;
+  TRY(chain_states(c, chain, &style, 1, style_kind(flags), &refs, &ns));
+  for (const ChainLevel& g : chain.lv) {
+    TRY(wrap_encoder_buffers(c, B, g.H, g.W, g.l));
+    TRY(wrap_decoder_buffers(c, B, g.h, g.w, g.l));
+    TRY(ensure(c, c->wrap_f, (size_t)B * g.h * g.w * g.C * 4));
+    TRY(ensure(c, c->wct_out, (size_t)B * g.h * g.w * g.C * 2));
+  }
+  for (int i = 0; i < 2 && i < (int)chain.lv.size(); ++i) TRY(ensure(c, c->img_t[i], (size_t)B * Hc * Wc * 3 * 4));
+
+  const float* cur;
+  TRY(content_prelude(c, flags, content, (size_t)B * Hc * Wc * 3, &cur));
+  for (int i = 0; i < (int)chain.lv.size(); ++i) {
+    const ChainLevel& g = chain.lv[i];
+    // level i>0 encodes clip(previous decoded, 0, 1) (model.py:86): the clamp is in the conv1_1 loader, as in stylize_levels
+    TRY(run_encoder_wrap(c, cur, B, g.H, g.W, i > 0, g.l, (float*)c->wrap_f.p));
+    TRY(run_transform(c, (float*)c->wrap_f.p, g.h * g.w, nullptr, ns[(size_t)i * WCT_MIX_MAX], g.C, B, alpha, flags, -1.f,
+                      (half_t*)c->wct_out.p, nullptr, nullptr, nullptr, &refs[i]));
+    float* dst = (float*)c->img_t[i & 1].p;
+    TRY(run_decoder_wrap(c, g.l, (half_t*)c->wct_out.p, B, g.h, g.w, dst));
+    cur = dst;
+  }
+  ProfScope ps(c, 7, 0, (double)B * Hc * Wc * 3 * 5);
+  return launch_f32_to_u8(cur, out, (size_t)B * Hc * Wc * 3, c->stream);
+}
+
+extern "C" int wct_stylize_prepared_wrap_batch_dev(wct_ctx* c, const uint8_t* content, int Hc, int Wc, int B, const wct_style* style,
+                                                   const int* levels, int n_levels, float alpha, unsigned flags, uint8_t* out) {
+  ARG_CHECK(c && content && out && levels && n_levels >= 1 && n_levels <= 16 && B >= 1 && B <= 32);
+  TRY(wrap_flags_ok(flags));
+  return stylize_prepared_wrap_dev(c, content, Hc, Wc, B, style, levels, n_levels, alpha, flags, out);
+}
+
+extern "C" int wct_stylize_prepared_wrap(wct_ctx* c, const uint8_t* content, int Hc, int Wc, const wct_style* style, const int* levels,
+                                         int n_levels, float alpha, unsigned flags, uint8_t* out) {
+  ARG_CHECK(c && content && out && levels && n_levels >= 1 && n_levels <= 16);
+  TRY(wrap_flags_ok(flags));
+  Chain chain;
+  TRY(wrap_chain_check(Hc, Wc, levels, n_levels, &chain));    // (the size rule, before the content is staged)
+  return host_frame(c, content, Hc, Wc, levels, n_levels, flags, out, [&](void* dc, uint8_t* frame) {
+    return stylize_prepared_wrap_dev(c, dc, Hc, Wc, 1, style, levels, n_levels, alpha, flags, frame);
+  });
+}
+
+// seamless textures: the noise of wct_texture_prepared_batch_dev, then `passes` runs of the wrap chain, each on the frames of the
+// one before it; the tile keeps its size through every pass
+extern "C" int wct_texture_prepared_wrap_batch_dev(wct_ctx* c, int H, int W, int B, unsigned seed, unsigned first_sample, int smooth,
+                                                   const wct_style* style, const int* levels, int n_levels, int passes, float alpha,
+                                                   unsigned flags, uint8_t* out) {
+  ARG_CHECK(c && out && levels && n_levels >= 1 && n_levels <= 16 && B >= 1 && B <= 32 && passes >= 1 && passes <= 16);
+  TRY(texture_flags_ok(flags));
+  HIP_TRY(hipSetDevice(c->device));
+  TRY(style_live(c, style));
+  TRY(check_levels(c, levels, n_levels, &style, 1));
+  Chain chain;
+  TRY(wrap_chain_check(H, W, levels, n_levels, &chain));      // (its launch limits keep B * H * W * 3 far below 2^31)
+  const size_t frames = (size_t)B * H * W * 3;
+  TRY(ensure(c, c->tex_noise, frames));
+  for (int i = 0; i < 2 && i < passes - 1; ++i) TRY(ensure(c, c->tex[i], frames));
+  {
+    ProfScope ps(c, 7, 0, (double)frames);
+    TRY(launch_texture_noise((uint8_t*)c->tex_noise.p, B, H, W, seed, first_sample, smooth, c->stream));
+  }
+  const uint8_t* in = (const uint8_t*)c->tex_noise.p;
+  for (int p = 0; p < passes; ++p) {
+    uint8_t* dst = p == passes - 1 ? out : (uint8_t*)c->tex[p & 1].p;
+    TRY(stylize_prepared_wrap_dev(c, in, H, W, B, style, levels, n_levels, alpha, flags, dst));
+    in = dst;
+  }
+  return WCT_OK;
+}
+
+extern "C" int wct_texture_prepared_wrap(wct_ctx* c, int H, int W, unsigned seed, unsigned sample, int smooth, const wct_style* style,
+                                         const int* levels, int n_levels, int passes, float alpha, unsigned flags, uint8_t* out) {
+  ARG_CHECK(c && out && levels && n_levels >= 1 && n_levels <= 16 && passes >= 1 && passes <= 16);
+  TRY(texture_flags_ok(flags));
+  Chain chain;
+  TRY(wrap_chain_check(H, W, levels, n_levels, &chain));
+  HIP_TRY(hipSetDevice(c->device));
+  TRY(eig_stale(c));
+  TRY(ensure(c, c->stage[2], (size_t)H * W * 3));
+  TRY(wct_texture_prepared_wrap_batch_dev(c, H, W, 1, seed, sample, smooth, style, levels, n_levels, passes, alpha, flags,
+                                          (uint8_t*)c->stage[2].p));
+  TRY(fetch(c, out, c->stage[2].p, (size_t)H * W * 3));
+  return eig_status(c);
+}
+
 // Spatial control of B frames on prepared styles: one label map per frame (on the HOST: every level's labels are counted here,
 // before any launch, and size the launches), K handles shared by all frames.  The level transform runs the frames in GROUPS of at
 // most WCT_PLAN_PAIRS = 32 live (frame, region) pairs -- one batched eigensolve of 64 slots, the style slots dead -- through

@@ -6,6 +6,8 @@
 //   (pool_rule.h); the eigensolve, the spectral tail and the blend then run once, the apply per chunk.
 // This unit holds the band plan, the pooling kernels and the band / chunk drivers; the entry points are in api_ops.hip
 // (wct_encode_banded, wct_decode_banded, wct_transform_chunked) and api_stylize.hip (wct_stylize_prepared_banded*).
+// It also holds the wrap plan and the wrap drivers of periodic synthesis (wrap.hip's kernels): the same halo tables and the same
+// argument, the halo filled with the tile's own pixels modulo its size.
 #include "api.h"
 #include "wct_stages.h"
 #include "pool_rule.h"
@@ -141,6 +143,55 @@ extern "C" int wct_band_plan(int H, int W, int level, int band_rows, int max_ban
 }
 
 // ---------------------------------------------------------------------------
+// the wrap plan: the same halos around a TILE, filled with the tile's own pixels modulo its size (wrap.hip) -- every layer then
+// sees a torus, and the interior of the pass is the periodic network's output
+// ---------------------------------------------------------------------------
+// Encoder: BAND_RE image pixels on all four sides.  Decoder: BAND_RD feature pixels behind the tile, and BAND_RD rounded up to
+// even in front of it, where a band moves its first row down to an even one.  tests/test_wrap_cpu.py checks both on the oracle.
+void wrap_halo(int level, int* enc, int* dec_before, int* dec_after) {
+  *enc = BAND_RE[level];
+  *dec_before = (BAND_RD[level] + 1) & ~1;
+  *dec_after = BAND_RD[level];
+}
+
+extern "C" int wct_wrap_halo(int level, int* enc, int* dec_before, int* dec_after) {
+  ARG_CHECK(enc && dec_before && dec_after && level >= 1 && level <= 5);
+  wrap_halo(level, enc, dec_before, dec_after);
+  return WCT_OK;
+}
+
+// The tile of a wrap chain: every side a multiple of the deepest level's stride (ceil-mode pooling of an odd size is not
+// periodic), large enough for that level, and every padded map of every level inside the limits of one launch
+int wrap_chain_check(int H, int W, const int* levels, int n_levels, Chain* chain) {
+  ARG_CHECK(levels && n_levels >= 1);
+  int deepest = 0;
+  for (int i = 0; i < n_levels; ++i) { ARG_CHECK(levels[i] >= 1 && levels[i] <= 5); deepest = std::max(deepest, levels[i]); }
+  const int m = 1 << (deepest - 1);
+  if (H < 1 || W < 1 || H % m || W % m) {
+    wct_set_error("wrap: a %dx%d tile with relu%d_1 in the chain: both sides must be multiples of %d (ceil-mode pooling of an odd "
+                  "size is not periodic)", H, W, deepest, m);
+    return WCT_ERR_ARG;
+  }
+  TRY(chain_geometry(H, W, levels, n_levels, chain));
+  for (const ChainLevel& g : chain->lv) {
+    int Re, d0, d1;
+    wrap_halo(g.l, &Re, &d0, &d1);
+    const long long Hp = (long long)g.H + 2 * Re, Wp = (long long)g.W + 2 * Re;
+    if (Hp > 0x7fffffff || Wp > 0x7fffffff || !enc_fits(Hp, Wp, g.l) || !launch_map_fits((size_t)g.h * g.w * g.C, 4) ||
+        !dec_fits((long long)g.h + d0 + d1, (long long)g.w + d0 + d1, g.l)) {
+      wct_set_error("wrap: a %dx%d tile with its halo of relu%d_1 (%lldx%lld) passes 2^31 bytes in one launch", g.H, g.W, g.l, Hp, Wp);
+      return WCT_ERR_ARG;
+    }
+  }
+  return WCT_OK;
+}
+
+extern "C" int wct_wrap_check(int H, int W, const int* levels, int n_levels) {
+  Chain chain;
+  return wrap_chain_check(H, W, levels, n_levels, &chain);
+}
+
+// ---------------------------------------------------------------------------
 // the band drivers: slices of the full maps through run_encoder / run_decoder, interiors copied device to device
 // ---------------------------------------------------------------------------
 static int copy_rows(wct_ctx* c, void* dst, const void* src, size_t bytes) {
@@ -187,6 +238,61 @@ int run_decoder_banded(wct_ctx* c, int level, const half_t* G, int h, int w, int
                   (size_t)(b.f1 - b.f0) * s * row * 4));
   }
   return WCT_OK;
+}
+
+// ---------------------------------------------------------------------------
+// the wrap drivers: B tiles with their wrap-around halos through run_encoder / run_decoder, the interiors cropped out
+// ---------------------------------------------------------------------------
+int wrap_encoder_buffers(wct_ctx* c, int B, int H, int W, int level) {
+  ARG_CHECK(level >= 1 && level <= 5 && B >= 1 && H >= 1 && W >= 1);
+  const int Re = BAND_RE[level];
+  const size_t Hp = (size_t)H + 2 * Re, Wp = (size_t)W + 2 * Re;
+  TRY(ensure(c, c->wrap_img, (size_t)B * Hp * Wp * 3 * 4));
+  return ensure(c, c->feat_c, (size_t)B * (Hp >> (level - 1)) * (Wp >> (level - 1)) * LEVEL_C[level] * 4);
+}
+
+int wrap_decoder_buffers(wct_ctx* c, int B, int h, int w, int level) {
+  ARG_CHECK(level >= 1 && level <= 5 && B >= 1 && h >= 1 && w >= 1);
+  int Re, d0, d1;
+  wrap_halo(level, &Re, &d0, &d1);
+  const size_t hp = (size_t)h + d0 + d1, wp = (size_t)w + d0 + d1;
+  TRY(ensure(c, c->wrap_g, (size_t)B * hp * wp * LEVEL_C[level] * 2));
+  return ensure(c, c->wrap_img, (size_t)B * (hp << (level - 1)) * (wp << (level - 1)) * 3 * 4);
+}
+
+int run_encoder_wrap(wct_ctx* c, const float* img, int B, int H, int W, int clamp01, int level, float* tap) {
+  ARG_CHECK(level >= 1 && level <= 5);
+  const int s = 1 << (level - 1), C = LEVEL_C[level], Re = BAND_RE[level];
+  ARG_CHECK(H >= s && W >= s && H % s == 0 && W % s == 0);
+  const int Hp = H + 2 * Re, Wp = W + 2 * Re;
+  ARG_CHECK(enc_fits(Hp, Wp, level));
+  TRY(wrap_encoder_buffers(c, B, H, W, level));
+  {
+    ProfScope ps(c, 7, 0, 2.0 * B * Hp * Wp * 3 * 4);
+    TRY(launch_wrap_pad(img, c->wrap_img.p, B, H, W, 3, 4, Re, Re, Re, Re, c->stream));
+  }
+  float* taps[6] = {};
+  taps[level] = (float*)c->feat_c.p;
+  TRY(run_encoder(c, (const float*)c->wrap_img.p, B, Hp, Wp, clamp01, level, taps));
+  ProfScope ps(c, 7, 0, 2.0 * B * (H / s) * (W / s) * C * 4);
+  return launch_wrap_crop(c->feat_c.p, tap, B, Hp / s, Wp / s, C, 4, Re / s, Re / s, H / s, W / s, c->stream);
+}
+
+int run_decoder_wrap(wct_ctx* c, int level, const half_t* G, int B, int h, int w, float* img_out) {
+  ARG_CHECK(level >= 1 && level <= 5 && h >= 1 && w >= 1);
+  const int s = 1 << (level - 1), C = LEVEL_C[level];
+  int Re, d0, d1;
+  wrap_halo(level, &Re, &d0, &d1);
+  const int hp = h + d0 + d1, wp = w + d0 + d1;
+  ARG_CHECK(dec_fits(hp, wp, level));
+  TRY(wrap_decoder_buffers(c, B, h, w, level));
+  {
+    ProfScope ps(c, 7, 0, 2.0 * B * hp * wp * C * 2);
+    TRY(launch_wrap_pad(G, c->wrap_g.p, B, h, w, C, 2, d0, d1, d0, d1, c->stream));
+  }
+  TRY(run_decoder(c, level, (const half_t*)c->wrap_g.p, B, hp, wp, (float*)c->wrap_img.p));
+  ProfScope ps(c, 7, 0, 2.0 * B * h * s * w * s * 3 * 4);
+  return launch_wrap_crop(c->wrap_img.p, img_out, B, hp * s, wp * s, 3, 4, d0 * s, d0 * s, h * s, w * s, c->stream);
 }
 
 // ---------------------------------------------------------------------------

@@ -338,6 +338,13 @@ int launch_content_colors_u8(const uint8_t* stylized, const uint8_t* content, in
 // `seed`; smooth: the rule's 27 202 27 filter along y and x.  One launch; any base address; B * H * W * 3 >= 2^31 is WCT_ERR_ARG.
 int launch_texture_noise(uint8_t* out, int B, int H, int W, unsigned seed, unsigned first_sample, int smooth, hipStream_t s);
 
+// ---- wrap.hip -------------------------------------------------------------
+// Periodic extension and its inverse, B maps of E elements of elem_bytes (4: fp32, any E; 2: fp16, E a multiple of 8) per pixel:
+// out [B][t + H + b][l + W + r][E] with out(y, x) = in((y - t) mod H, (x - l) mod W), and out [B][h][w][E] = the interior of
+// in [B][Hp][Wp][E] at (t, l).  A padded map of 2^31 bytes or more is WCT_ERR_ARG with a message.
+int launch_wrap_pad(const void* in, void* out, int B, int H, int W, int E, int elem_bytes, int t, int b, int l, int r, hipStream_t s);
+int launch_wrap_crop(const void* in, void* out, int B, int Hp, int Wp, int E, int elem_bytes, int t, int l, int h, int w, hipStream_t s);
+
 // ---- resize.hip -----------------------------------------------------------
 // Bilinear resize by Pillow's 8-bit rule (resize_rule.h): in [B][H][W][3] -> out [B][h][w][3] uint8 on the device, one launch, no
 // workspace.  A geometry's plan is host work: resize_plan fills `tabs` (resize_table_ints int32 words: the bounds and taps of both

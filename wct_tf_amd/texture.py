@@ -4,7 +4,9 @@ the pipeline `--passes` times and comes out as a sample of the style's texture. 
 independent noise images of `--seed`; the noise is made on the device and the passes feed each other there, `--batch` samples
 per call.  `--style-path` is a file, or a folder (one set of textures per style).  `--interp-styles a b [--interp-weights wa wb]`
 in its place interpolates between textures (Fig. 9 of the paper).  Outputs: `{out}/{style}_texture_s{seed}_{sample}.png`, and
-`{out}/{a}+{b}_texture_s{seed}_{sample}.png` for a mix.  The model flags are those of `wct_tf_amd.stylize`."""
+`{out}/{a}+{b}_texture_s{seed}_{sample}.png` for a mix.  `--tile` makes the textures seamless (every pass on a torus: the
+outputs repeat without a seam; `--size` in multiples of the deepest level's stride), `--tile-preview N` also writes
+`{name}_tiled.png`, the tile repeated N x N.  The model flags are those of `wct_tf_amd.stylize`."""
 import argparse
 import os
 import time
@@ -30,6 +32,11 @@ _NEW = [
                                 help='interpolate between the textures of these style images, in the place of --style-path')),
     (('--interp-weights',), dict(nargs='+', type=float, default=None, metavar='W',
                                  help='one weight >= 0 per --interp-styles image, normalised to sum 1 (default: equal)')),
+    (('--tile',), dict(action='store_true', default=False,
+                       help='seamless textures: every pass runs on a torus, so an output repeats without a seam (--size must be '
+                            'multiples of the deepest level\'s stride; not with --interp-styles)')),
+    (('--tile-preview',), dict(type=int, default=None, metavar='N',
+                               help='with --tile: also write {name}_tiled.png, the tile repeated N x N')),
 ]
 
 
@@ -62,6 +69,13 @@ def check_texture_args(parser, args):
                 parser.error('--interp-weights must be finite and >= 0')
             if not sum(args.interp_weights) > 0:
                 parser.error('--interp-weights sum to 0')
+    if args.tile_preview is not None:
+        if not args.tile:
+            parser.error('--tile-preview needs --tile')
+        if args.tile_preview < 1:
+            parser.error('--tile-preview must be >= 1, got %d' % args.tile_preview)
+    if args.tile and args.interp_styles is not None:
+        parser.error('--tile takes one style: --interp-styles runs on the single-frame mix path, which has no periodic form')
     if not 1 <= args.passes <= 16:
         parser.error('--passes must be 1 .. 16, got %d' % args.passes)
     if not 1 <= args.batch <= 32:
@@ -103,12 +117,17 @@ def main(argv=None):
     written = 0
     for paths, style, mix_weights in jobs:
         out = model.synthesize(style, args.size, seeds=args.samples, seed=args.seed, passes=args.passes, alpha=args.alpha,
-                               adain=args.adain, smooth=args.noise_smooth, batch=args.batch, weights=mix_weights)
+                               adain=args.adain, smooth=args.noise_smooth, batch=args.batch, weights=mix_weights, tile=args.tile)
         for sample, img in enumerate(out):
             target = os.path.join(args.out_path, texture_name(paths, args.seed, sample))
             utils.save_img(target, img)
             written += 1
             print('%d: wrote %s' % (written, target))
+            if args.tile_preview is not None:
+                preview = target[:-len('.png')] + '_tiled.png'
+                utils.save_img(preview, np.tile(img, (args.tile_preview, args.tile_preview, 1)))
+                written += 1
+                print('%d: wrote %s' % (written, preview))
     print('%d outputs in %.1f s' % (written, time.time() - t0))
     return written
 

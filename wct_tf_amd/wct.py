@@ -7,6 +7,7 @@
     WCT.prepare_style(style) -> PreparedStyle, which predict / predict_frames / predict_mix take in the place of a style image
     every predict* takes content_colors=True: the frame keeps its luminance and takes the colours of its content
     WCT.synthesize(style, size, seeds=1, seed=0, passes=3) -> uint8 [n][Ho][Wo][3], textures of the style from seeded noise
+    predict_frames(wrap=True) / synthesize(tile=True): the network on a torus -- tileable frames, seamless textures
 
 `checkpoints` / `vgg_path`: the reference restores TF checkpoints and a .t7 file
 (wct.py:46-58, vgg_normalised.py:16).  Per decoder this class takes either of
@@ -21,7 +22,7 @@ import re
 
 import numpy as np
 
-from .context import Context, PreparedStyle, check_prepared, check_resize, check_texture, check_warm, split_styles
+from .context import Context, PreparedStyle, check_prepared, check_resize, check_texture, check_warm, check_wrap, split_styles
 from .model import WCTModel
 from .weights import load_weights
 
@@ -292,7 +293,7 @@ class WCT(object):
                 h.close()
 
     def predict_frames(self, frames, style, alpha=1, swap5=False, ss_alpha=1, adain=False, batch=16, warm=None,
-                       content_colors=False, resize=None):
+                       content_colors=False, resize=None, wrap=False):
         '''Stylize same-sized frames [F][H][W][3] with ONE style image (the loop of stylize_video.py:112-121,
            which calls predict() once per frame and so re-runs the style encoder, the style statistics and the
            style eigendecompositions every frame).  Here the style side runs once per batch of `batch` frames;
@@ -301,8 +302,28 @@ class WCT(object):
            With a PreparedStyle and `warm` (a WarmState) every batch starts its content eigensolves from the last frame of the
            batch before it (the state's, for the first): frames within tolerance of the cold ones, not bit-identical.
            resize (h, w): the frames are raw and are resized to h x w on the device, in front of the call and on its stream
-           (Context.resize_batch_dev: Pillow's bilinear bytes) -- predict_frames on utils._imresize(frame, (h, w)), bit for bit.'''
+           (Context.resize_batch_dev: Pillow's bilinear bytes) -- predict_frames on utils._imresize(frame, (h, w)), bit for bit.
+           wrap: the network on a torus (Context.stylize_prepared_wrap_batch) -- every conv sees the frame continued periodically,
+           so a tileable frame stays tileable.  Prepared styles only; H and W multiples of the deepest level's stride; no swap5,
+           warm, content_colors or resize (ValueError before any GPU call).  Frames keep their size.'''
         frames = np.asarray(frames)
+        if wrap:
+            if not isinstance(style, PreparedStyle):
+                raise ValueError('wrap takes a PreparedStyle (prepare_style), not a style image')
+            for name, on in (('swap5', swap5), ('warm', warm is not None), ('content_colors', content_colors),
+                             ('resize', resize is not None)):
+                if on:
+                    raise ValueError('%s is not served with wrap: the periodic path takes one prepared style, WCT or AdaIN' % name)
+            if frames.ndim != 4 or frames.shape[3] != 3:
+                raise ValueError('expected [F][H][W][3] frames, got shape %s' % (frames.shape,))
+            check_wrap(frames.shape[1], frames.shape[2], self.relu_targets)
+            check_prepared(self.sess, [style], self.relu_targets)
+            if frames.dtype != np.uint8:
+                frames = np.uint8(np.clip(frames, 0, 255))
+            batch = max(1, min(32, int(batch)))
+            return np.concatenate([self.sess.stylize_prepared_wrap_batch(frames[i:i + batch], style, self.relu_targets, alpha=alpha,
+                                                                         adain=adain, wct_mode=self.wct_mode)
+                                   for i in range(0, len(frames), batch)], axis=0)
         if warm is not None:
             self._check_warm(warm, style, swap5, adain)                           # ValueError before any GPU call
         if resize is not None:
@@ -339,7 +360,7 @@ class WCT(object):
         return np.concatenate(outs, axis=0)
 
     def synthesize(self, style, size, seeds=1, seed=0, passes=3, alpha=1, adain=False, smooth=False, batch=16, weights=None,
-                   swap5=False):
+                   swap5=False, tile=False):
         '''Texture synthesis (Li et al. 2017, sec. 4.3; the reference's webcam.py --noise and the recipe of stylize.py:95-97): seeded
            noise images of `size` (H, W) go through the pipeline `passes` times and come out as samples of the style's texture.
            `style` is an image (array in [0,255]: prepared here and closed afterwards) or a PreparedStyle.  `seeds` is a count n
@@ -352,8 +373,16 @@ class WCT(object):
            Texture interpolation (Fig. 9 of the paper): `style` is a LIST of images or of PreparedStyle objects and `weights` the
            mix weights (None: equal).  Each sample then takes its noise from texture_noise_np and `passes` x predict_mix on the
            handles -- one sample at a time, through the host between passes, because the mix path is single-frame.  Batched
-           mixes, masks and warm states are not part of this call.'''
+           mixes, masks and warm states are not part of this call.
+           tile: seamless textures (Context.texture_prepared_wrap_batch) -- every pass runs on a torus, so a sample can be
+           repeated in both directions without a seam.  One style only (a list is a ValueError: the mix path is single-frame);
+           H and W multiples of the deepest level's stride; the samples keep the noise's size.'''
         h, w, samples, runs, batch = texture_plan(style, size, seeds, seed, passes, batch, weights, swap5)   # ValueError, no GPU call
+        if tile:
+            if isinstance(style, (list, tuple)):
+                raise ValueError('tile takes one style: texture interpolation runs on the single-frame mix path, which has no '
+                                 'periodic form')
+            check_wrap(h, w, self.relu_targets)                                                             # ValueError, no GPU call
         if isinstance(style, (list, tuple)):
             from .ops import texture_noise_np
             handles, images = split_styles(list(style))
@@ -374,9 +403,10 @@ class WCT(object):
         if isinstance(style, PreparedStyle):
             check_prepared(self.sess, [style], self.relu_targets)
         handle = style if isinstance(style, PreparedStyle) else self.prepare_style(np.asarray(style), adain=adain)
+        call = self.sess.texture_prepared_wrap_batch if tile else self.sess.texture_prepared_batch
         try:
-            return np.concatenate([self.sess.texture_prepared_batch(h, w, n, seed, first, handle, self.relu_targets, passes=passes,
-                                                                    alpha=alpha, adain=adain, wct_mode=self.wct_mode, smooth=smooth)
+            return np.concatenate([call(h, w, n, seed, first, handle, self.relu_targets, passes=passes, alpha=alpha, adain=adain,
+                                        wct_mode=self.wct_mode, smooth=smooth)
                                    for first, n in runs], axis=0)
         finally:
             if handle is not style:
