@@ -153,7 +153,16 @@ int wct_set_style_swap(wct_ctx* ctx, float ss_alpha, int patch_size, int stride)
  * A [nmat][C][C] in; evals [nmat][C], evecs [nmat][C][C] (columns) out.  The UPPER triangle of A (a[i][j],
  * i <= j) is authoritative: the entry point mirrors it into the lower one on its staged copy before the
  * solve (the solver reads an element from whichever triangle is contiguous for the kernel at hand), so a
- * matrix that is symmetric only to round-off, or upper-only data, is solved as that symmetric matrix. */
+ * matrix that is symmetric only to round-off, or upper-only data, is solved as that symmetric matrix; the
+ * lower triangle may hold anything (NaN included) and the caller's array is not written.  evals is not
+ * sorted: column j of evecs belongs to evals[j], and eigenpair j is the one that grew out of coordinate j,
+ * so a matrix that is already diagonal comes back exact and in place: evals = its diagonal, evecs = I.
+ * Accepted: C a multiple of 32 with 32 <= C <= 1024, 1 <= nmat <= 64, ctx / A / evals / evecs non-null.
+ * Anything else returns WCT_ERR_ARG ("invalid argument") from the first line of the call: a refused call
+ * reads no host memory, stages and launches nothing, and leaves the context as it was.
+ * Batch guarantee: the evals, evecs and sweeps of a matrix are, bit for bit, those of the same matrix solved
+ * alone (nmat = 1) -- they depend neither on nmat, nor on the matrix' position in the batch, nor on what its
+ * neighbours are (a neighbour that fails, by running out of sweeps or on non-finite input, included). */
 int wct_eigh(wct_ctx* ctx, const float* A, int C, int nmat, float* evals, float* evecs,
              int* sweeps_out /* [nmat] or NULL; same contract as wct_transform's */);
 /* Conv2DReflect (ops.py:17-19): x [H][W][Cin] fp32, w HWIO, y [Ho][Wo][Cout] fp32;

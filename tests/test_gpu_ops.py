@@ -12,6 +12,7 @@ import pytest
 
 import oracle
 from conftest import GOLDEN, rel_err, max_rel, check_against_size_digest
+from eig_cases import graded_spd as _graded_spd
 from wct_tf_amd import _lib
 from wct_tf_amd.weights import synthetic_features, synthetic_weights, synthetic_image
 
@@ -26,14 +27,6 @@ def ctx():
     c = Context(0)
     yield c
     c.close()
-
-
-def _graded_spd(rng, c, decades, rank=None):
-    k = rank or c
-    g = rng.standard_normal((4 * c, k)) @ rng.standard_normal((k, c)) / np.sqrt(k)
-    scales = 10.0 ** rng.uniform(-decades / 2, decades / 2, c)
-    g = g * scales
-    return (g.T @ g / (4 * c - 1)).astype(np.float32)
 
 
 @pytest.mark.parametrize('c', [32, 64, 128, 256, 512])

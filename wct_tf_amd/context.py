@@ -465,13 +465,18 @@ class Context(object):
     def set_style_swap(self, ss_alpha=0.6, patch_size=3, stride=1):
         check(self.lib.wct_set_style_swap(self.h, float(ss_alpha), int(patch_size), int(stride)))
 
-    def eigh(self, mats, return_sweeps=False):
+    def eigh(self, mats, return_sweeps=False, symmetrize=True):
+        """mats [n][C][C] (or [C][C]) -> (evals [n][C], evecs [n][C][C]) through wct_eigh.  symmetrize=False hands the float32
+        array to the ABI as given (what a C caller does)."""
         a = f32(mats)
         if a.ndim == 2:
             a = a[None]
-        # wct_eigh wants a matrix that is symmetric to the bit (include/wct_hip.h); (a + a^T) / 2 is, and leaves a symmetric
-        # input unchanged
-        a = np.ascontiguousarray(0.5 * (a + a.transpose(0, 2, 1)), np.float32)
+        # wct_eigh takes the UPPER triangle as authoritative and mirrors it into the lower one on its staged copy
+        # (include/wct_hip.h), so it needs no symmetric input.  The default solves (a + a^T) / 2, the matrix a NumPy caller
+        # means by a nearly symmetric `a`; it leaves a symmetric input unchanged.
+        if symmetrize:
+            a = 0.5 * (a + a.transpose(0, 2, 1))
+        a = np.ascontiguousarray(a, np.float32)
         n, c, _ = a.shape
         evals = np.empty((n, c), np.float32)
         evecs = np.empty((n, c, c), np.float32)

@@ -290,7 +290,8 @@ __global__ __launch_bounds__(256) void mirror_upper_kernel(float* A, int C) {
 }
 
 extern "C" int wct_eigh(wct_ctx* c, const float* A, int C, int nmat, float* evals, float* evecs, int* sweeps_out) {
-  ARG_CHECK(c && A && evals && evecs && nmat >= 1 && nmat <= 64);
+  // the order check is jacobi_make_group's, made here before anything is sized by C: a refused call stages and launches nothing
+  ARG_CHECK(c && A && evals && evecs && nmat >= 1 && nmat <= 64 && C % 32 == 0 && C >= 32 && C <= 1024);
   HIP_TRY(hipSetDevice(c->device));
   TRY(eig_stale(c));
   const size_t mb = (size_t)nmat * C * C * 4;

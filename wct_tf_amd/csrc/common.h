@@ -274,7 +274,8 @@ int launch_wct_masked_batch(const float* content, int Nc, int G, const MaskGeom&
 int launch_adain_masked_batch(const float* content, int Nc, int G, const MaskGeom& g, const int* nk, const int* Ns, int K, int C,
                               const WctCall& r, const WctStyleSlots& states);
 // Symmetric eigensolver (batched): A [nmat][C][C] is overwritten (diag -> eigenvalues),
-// V [nmat][C][C] gets eigenvectors in columns.  C multiple of 32, 32 <= C <= 1024.
+// V [nmat][C][C] gets eigenvectors in columns, unsorted: eigenpair j is the one that grew out of coordinate j
+// (jacobi_unexchange_kernel).  C multiple of 32, 32 <= C <= 1024.
 // sweeps_done_dev[m]: sweeps used (> 0) if matrix m converged, -sweeps if it was still rotating when the sweep
 // budget ran out, <= -1000 for non-finite input; eig_fail as in WctCall.
 int launch_jacobi_eigh(float* A, float* V, int C, int nmat, void* workspace,

@@ -1174,14 +1174,38 @@ static int jacobi_make_group(JacobiGroup* G, float* A, float* V, int C, int nmat
   return WCT_OK;
 }
 
+// measured (16 matrices): 64-wide pairs win from C = 256 up (half the tile traffic), 32-wide below
+static bool jacobi_wide_pairs(int C) { return C % 64 == 0 && C >= 256; }
+
 static int jacobi_dispatch(JacobiGroup& G, int C) {
-  // measured (16 matrices): 64-wide pairs win from C = 256 up (half the tile traffic), 32-wide below
   // (the round-2 two-launch steps -- separate pair-problem and tile-update kernels -- were deleted in round 4: the
   //  look-ahead launches have been the only path since round 3)
-  const bool m64 = C % 64 == 0 && C >= 256;
+  const bool m64 = jacobi_wide_pairs(C);
   const int rc = m64 ? jacobi_run_fused<64>(G, C) : jacobi_run_fused<32>(G, C);
   const int noted = launch_rc_take();  // a launch one of the train's void helpers saw refused (named there); cleared on every exit
   return rc ? rc : noted;
+}
+
+// Eigenpair j of a plain solve is the one that grew out of coordinate j.  The 32-wide path keeps that by construction; on the
+// 64-wide path every sweep's intra step (r4::intra_wave: odd-even transposition WITH EXCHANGE) leaves the 32 columns of each
+// block in reverse order, so after an odd number of sweeps column b * 32 + j of V (and diagonal entry b * 32 + j of A) belongs to
+// coordinate b * 32 + 31 - j -- a matrix that was diagonal to begin with came back with a permutation for V.  This puts the
+// columns and the eigenvalues back (a pure exchange: no value changes; only the diagonal of A is an output, its off-diagonal
+// residue is left).  Per matrix, from its own sweep count alone.  The transform's solves (launch_eig_stage) build V f(D) V^T,
+// which has no order, and keep theirs.  grid (C / 32 column blocks, C / 16 row groups, matrices), 16 x 16 threads.
+__global__ __launch_bounds__(256) void jacobi_unexchange_kernel(float* A, float* V, const JacobiState* st, int C) {
+  const int m = blockIdx.z;
+  if (!(st[m].sweeps & 1)) return;
+  const size_t cc = (size_t)C * C;
+  const int j = threadIdx.x & 15, lo = blockIdx.x * 32 + j, hi = blockIdx.x * 32 + 31 - j;
+  float* row = V + m * cc + (size_t)(blockIdx.y * 16 + (threadIdx.x >> 4)) * C;
+  const float a = row[lo], b = row[hi];
+  row[lo] = b; row[hi] = a;
+  if (blockIdx.y == 0 && threadIdx.x < 16) {
+    float* Am = A + m * cc;
+    const float da = Am[(size_t)lo * C + lo], db = Am[(size_t)hi * C + hi];
+    Am[(size_t)lo * C + lo] = db; Am[(size_t)hi * C + hi] = da;
+  }
 }
 
 int launch_jacobi_eigh(float* A, float* V, int C, int nmat, void* workspace, size_t workspace_bytes,
@@ -1189,7 +1213,12 @@ int launch_jacobi_eigh(float* A, float* V, int C, int nmat, void* workspace, siz
   JacobiGroup G;
   int rc = jacobi_make_group(&G, A, V, C, nmat, workspace, workspace_bytes, sweeps_done_dev, eig_fail, s);
   if (rc) return rc;
-  return jacobi_dispatch(G, C);
+  if ((rc = jacobi_dispatch(G, C))) return rc;
+  if (jacobi_wide_pairs(C)) {
+    hipLaunchKernelGGL(jacobi_unexchange_kernel, dim3(C / 32, C / 16, nmat), dim3(256), 0, s, A, V, G.st, C);
+    HIP_TRY(hipGetLastError());
+  }
+  return WCT_OK;
 }
 
 // the eigensolve stage of a transform: the 2P matrices of w in one batched solve, minus those the skip mode drops
