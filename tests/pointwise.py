@@ -332,7 +332,7 @@ def wino_config(cout, b, h, w):
     """launch_conv3x3_wino's choice (restated from csrc/conv_wino.hip); h, w after the upsample."""
     tx = -(-w // 16)
     if cout % 128 == 0 and tx * -(-h // 16) * b * (cout // 128) >= 256:
-        return 'IL16'                  # <16,128,1,4,IL=true>
+        return 'IL16'                  # conv3x3_wino_walk_kernel<16,128,1,4>
     if cout % 128 == 0 and tx * -(-h // 8) * b * (cout // 128) >= 256:
         return '8x128'                 # <8,128,1,4>
     return '8x64'                      # <8,64,2,2>

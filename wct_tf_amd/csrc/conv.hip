@@ -13,23 +13,11 @@
 // so every lane ends up holding 4 consecutive output channels of one pixel and
 // the epilogue stores 8 B (fp16) / 16 B (fp32) per lane.
 #include "common.h"
+#include "conv_tile.h"          // TW, PITCH, BK, u32x4, h2, reflect_idx: shared with conv_wino.hip
 
 // ---------------------------------------------------------------------------
 // generic 3x3 conv, Cin % 32 == 0, Cout % BN == 0
 // ---------------------------------------------------------------------------
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-constexpr int TW = 16;          // tile width in pixels (one MFMA B-fragment = 2 rows x 16)
-constexpr int PITCH = 20;       // patch row pitch in pixels (18 used; multiple of 4 keeps the swizzle aligned)
-constexpr int BK = 32;          // input channels per K-chunk
-
-__device__ __forceinline__ int reflect_idx(int i, int n) {
-  // 1-px REFLECT padding (edge not repeated): -1 -> 1, n -> n-2
-  if (i < 0) i = -i;
-  if (i >= n) i = 2 * n - 2 - i;
-  // ragged tiles can run further out; clamp (those lanes are masked at the store)
-  i = i < 0 ? 0 : i;
-  return i >= n ? n - 1 : i;
-}
 
 // epilogue shared by the conv kernels: bias, ReLU, (2x2 max-pool), store
 // acc register r of a 32x32 tile holds channel (r&3) + 8*(r>>2) + 4*(lane>>5) of pixel lane&31 (= tile row
@@ -52,7 +40,6 @@ __device__ __forceinline__ int reflect_idx(int i, int n) {
 template <int MT, int NT, bool POOL, bool OUT32>
 __device__ __forceinline__ void conv_epilogue_t(const ConvArgs& p, f32x16 (&acc)[NT][MT], int b, int y0, int x0, int n0,
                                                 int wm, int wn, int lane, const unsigned char* bias_lds) {
-  typedef _Float16 h2 __attribute__((ext_vector_type(2)));
   constexpr int OOB = (int)0x80000000u;      // beyond num_records of every per-image buffer (< 2^31 bytes, checked at launch)
   const int frag_px = lane & 15;
   const int frag_py = (lane & 31) >> 4;
