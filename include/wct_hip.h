@@ -374,6 +374,42 @@ int  wct_stylize_prepared_batch_dev_warm(wct_ctx* ctx, const uint8_t* content_de
 int  wct_transform_warm(wct_ctx* ctx, const float* content, int Nc, const float* style, int Ns, int C, float alpha,
                         unsigned flags, wct_warm* warm, int level, float* out, int* sweeps_out);
 
+/* ---- strength maps: a per-pixel style strength, blended in the apply ----------------------------
+ * Li et al. 2017, sec. 4.2 gives one alpha per call; a strength map lets it vary over the image (keep a face untouched, fade the
+ * style in from one side, feather the edge between "stylized" and "kept").  A map is a uint8 image smap[Hc][Wc] of the content's
+ * size: 255 means the call's alpha, 0 keeps the content features.  At a level of stride s = 2^(level - 1), feature pixel (i, j)
+ * reads v = smap[min(i s, Hc - 1)][min(j s, Wc - 1)] (the rule of the label maps), and its row leaves the transform as
+ *   a = alpha * (float(v) / 255.f);   out = a * y + (1.f - a) * x            (float32, each operation rounded once, none fused)
+ * with x the row's content features and y its transform at alpha = 1 (wct_tf, wct_np or AdaIN): ops.py:83,133,293 with alpha
+ * replaced by a.  The statistics, covariance, eigensystem and colouring matrix of a level are those of the plain call over the
+ * whole map; the map enters only the blend.  So v = 0 gives x bit for bit, and v = 255 with alpha = 1 the plain alpha = 1 row.
+ * wct_transform_strength / wct_adain_strength: one level, host pointers -- wct_transform / wct_adain on content [Nc][C], the rows
+ *   of an h x w feature map (Nc = h w, else WCT_STATUS_ARG), with smap [Hm][Wm] sampled at `stride`; sweeps_out as in wct_transform.
+ * wct_stylize_prepared_strength: wct_stylize_prepared with a map [Hc][Wc]; host pointers, blocking.  It is the B = 1 case of
+ * wct_stylize_prepared_strength_batch_dev: content_dev [B][Hc][Wc][3], smaps_dev [B][Hc][Wc] and out_dev [B][Ho][Wo][3] are
+ *   DEVICE pointers, B = 1 .. 32, one map per frame.  Nothing of a map is read on the host, so the call is asynchronous on the ctx
+ *   stream like wct_stylize_prepared_batch_dev (it blocks only while it computes a style state it does not hold).  Frame f is
+ *   wct_stylize_prepared_strength(content f, map f), bit for bit.  ..._warm: the same with a warm state, as
+ *   wct_stylize_prepared_batch_dev_warm (the levels of the call must be the state's set; no WCT_FLAG_ADAIN).
+ * flags: WCT_FLAG_MODE_NP, WCT_FLAG_ADAIN, WCT_FLAG_IMAGES_F32 for the content, WCT_FLAG_CONTENT_COLORS (on the frame: it does not
+ *   meet the map).  WCT_STATUS_ARG, with a message: WCT_FLAG_SWAP5, WCT_FLAG_STYLE_SHARED, a NULL map, B outside 1 .. 32, a level
+ *   outside the handle's set, and a content past the limit of one launch (the banded call takes no map).  A handle that is not
+ *   live in this ctx is WCT_STATUS_STATE and never dereferenced.  A refusal leaves the ctx usable.
+ * Mixes, label maps, style-swap, tiles and textures take no strength map. */
+int  wct_transform_strength(wct_ctx* ctx, const float* content, int Nc, int h, int w, const uint8_t* smap, int Hm, int Wm,
+                            int stride, const float* style, int Ns, int C, float alpha, int mode, float eps, float* out,
+                            int* sweeps_out /* [2] or NULL */);
+int  wct_adain_strength(wct_ctx* ctx, const float* content, int Nc, int h, int w, const uint8_t* smap, int Hm, int Wm, int stride,
+                        const float* style, int Ns, int C, float alpha, float epsilon, float* out);
+int  wct_stylize_prepared_strength(wct_ctx* ctx, const uint8_t* content, int Hc, int Wc, const uint8_t* smap, const wct_style* style,
+                                   const int* levels, int n_levels, float alpha, unsigned flags, uint8_t* out);
+int  wct_stylize_prepared_strength_batch_dev(wct_ctx* ctx, const uint8_t* content_dev, int Hc, int Wc, int B,
+                                             const uint8_t* smaps_dev /* [B][Hc][Wc] */, const wct_style* style, const int* levels,
+                                             int n_levels, float alpha, unsigned flags, uint8_t* out_dev);
+int  wct_stylize_prepared_strength_batch_dev_warm(wct_ctx* ctx, const uint8_t* content_dev, int Hc, int Wc, int B,
+                                                  const uint8_t* smaps_dev, const wct_style* style, const int* levels, int n_levels,
+                                                  float alpha, unsigned flags, wct_warm* warm, uint8_t* out_dev);
+
 /* ---- texture synthesis: seeded noise on the device, the passes chained there ------------------
  * Li et al. 2017, sec. 4.3: a noise image goes through the multi-level pipeline a few times and comes out as a sample of the
  * style's texture; other noise images give other samples, a style mix gives interpolated textures.  The reference ships it as

@@ -76,6 +76,14 @@ SIGNATURES = [
     ('wct_stylize_prepared_warm', C.c_int, [_P, _U8, C.c_int, C.c_int, _P, _I, C.c_int, C.c_float, C.c_uint, _P, _U8]),
     ('wct_stylize_prepared_batch_dev_warm', C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _I, C.c_int, C.c_float, C.c_uint, _P, _P]),
     ('wct_transform_warm', C.c_int, [_P, _F, C.c_int, _F, C.c_int, C.c_int, C.c_float, C.c_uint, _P, C.c_int, _F, _I]),
+    ('wct_transform_strength', C.c_int, [_P, _F, C.c_int, C.c_int, C.c_int, _U8, C.c_int, C.c_int, C.c_int, _F, C.c_int, C.c_int, C.c_float,
+                                         C.c_int, C.c_float, _F, _I]),
+    ('wct_adain_strength', C.c_int, [_P, _F, C.c_int, C.c_int, C.c_int, _U8, C.c_int, C.c_int, C.c_int, _F, C.c_int, C.c_int, C.c_float,
+                                     C.c_float, _F]),
+    ('wct_stylize_prepared_strength', C.c_int, [_P, _U8, C.c_int, C.c_int, _U8, _P, _I, C.c_int, C.c_float, C.c_uint, _U8]),
+    ('wct_stylize_prepared_strength_batch_dev', C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _I, C.c_int, C.c_float, C.c_uint, _P]),
+    ('wct_stylize_prepared_strength_batch_dev_warm', C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _I, C.c_int, C.c_float, C.c_uint,
+                                                               _P, _P]),
     ('wct_texture_noise_batch_dev', C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_uint, C.c_uint, C.c_int, _P]),
     ('wct_texture_noise', C.c_int, [_P, C.c_int, C.c_int, C.c_uint, C.c_uint, C.c_int, _U8]),
     ('wct_texture_size', C.c_int, [C.c_int, C.c_int, _I, C.c_int, C.c_int, _I, _I]),
@@ -211,6 +219,31 @@ def mask_labels(mask, k, shape=None):
     if m.min() < 0 or m.max() >= k:
         raise ValueError('mask labels must be 0 .. %d for %d styles, got %d .. %d' % (k - 1, k, m.min(), m.max()))
     return np.ascontiguousarray(m, np.uint8)
+
+
+def strength_map(smap, shape):
+    """A validated strength map as contiguous uint8: a uint8 array of exactly `shape` (H, W) -- 255 is the call's alpha, 0 keeps the
+    content -- checked here before any GPU call."""
+    m = np.asarray(smap)
+    if m.dtype != np.uint8:
+        raise ValueError('a strength map is uint8 (255: the full alpha, 0: keep the content), got %s' % (m.dtype,))
+    if m.shape != tuple(shape) or m.size == 0:
+        raise ValueError('strength map of shape %s for content of shape %s' % (m.shape, tuple(shape)))
+    return np.ascontiguousarray(m)
+
+
+def strength_maps_frames(smaps, n_frames, shape):
+    """The strength maps of `n_frames` frames of `shape` (H, W) as contiguous uint8 [F][H][W]: `smaps` is [F][H][W] (one map per
+    frame; the count must equal the frame count), or one [H][W] map used for every frame.  Each map is checked by strength_map."""
+    shape = tuple(shape)
+    if isinstance(smaps, np.ndarray) and smaps.ndim == 2:
+        return np.ascontiguousarray(np.broadcast_to(strength_map(smaps, shape), (n_frames,) + shape))
+    if len(smaps) != n_frames:
+        raise ValueError('%d strength maps for %d frames' % (len(smaps), n_frames))
+    out = np.empty((n_frames,) + shape, np.uint8)
+    for f in range(n_frames):
+        out[f] = strength_map(smaps[f], shape)
+    return out
 
 
 def mask_labels_frames(masks, k, n_frames, shape):

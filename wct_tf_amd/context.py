@@ -391,6 +391,44 @@ class Context(object):
                                  float(alpha), float(epsilon), fptr(out)))
         return out
 
+    @staticmethod
+    def _strength_level(content, smap, h, w, stride):
+        """The arguments of a one-level strength call, checked before any GPU call: content [h*w][C] float32, smap [Hm][Wm] uint8."""
+        c = f32(content)
+        m = np.asarray(smap)
+        if m.ndim != 2:
+            raise ValueError('expected an [H][W] strength map, got shape %s' % (m.shape,))
+        m = _lib.strength_map(m, m.shape)
+        if c.ndim != 2 or int(h) < 1 or int(w) < 1 or int(stride) < 1 or c.shape[0] != int(h) * int(w):
+            raise ValueError('content of shape %s is not the [h*w][C] rows of a %dx%d feature map' % (c.shape, h, w))
+        return c, m
+
+    def transform_strength(self, content, style, smap, h, w, stride, alpha, mode, eps=-1.0, return_sweeps=False):
+        """transform() with a strength map (wct_transform_strength): content [h*w][C] the rows of an h x w feature map, smap
+        [Hm][Wm] uint8 sampled at `stride` -- row (i, j) takes a = alpha * smap[min(i stride, Hm-1)][min(j stride, Wm-1)] / 255 and
+        leaves as a * transform(content, style, 1.0)[row] + (1 - a) * content[row], in float32."""
+        c, m = self._strength_level(content, smap, h, w, stride)
+        s = f32(style)
+        if s.ndim != 2 or c.shape[1] != s.shape[1]:
+            raise ValueError('expected [N][C] feature matrices with equal C')
+        out = np.empty_like(c)
+        sweeps = (C.c_int * 2)()
+        self.last_sweeps = sweeps
+        check(self.lib.wct_transform_strength(self.h, fptr(c), c.shape[0], int(h), int(w), m.ctypes.data_as(_lib._U8), m.shape[0],
+                                              m.shape[1], int(stride), fptr(s), s.shape[0], c.shape[1], float(alpha), int(mode),
+                                              float(eps), fptr(out), sweeps))
+        return (out, list(sweeps)) if return_sweeps else out
+
+    def adain_strength(self, content, style, smap, h, w, stride, alpha, epsilon=1e-5):
+        """adain() with a strength map (wct_adain_strength): as transform_strength."""
+        c, m = self._strength_level(content, smap, h, w, stride)
+        s = f32(style)
+        out = np.empty_like(c)
+        check(self.lib.wct_adain_strength(self.h, fptr(c), c.shape[0], int(h), int(w), m.ctypes.data_as(_lib._U8), m.shape[0],
+                                          m.shape[1], int(stride), fptr(s), s.shape[0], c.shape[1], float(alpha), float(epsilon),
+                                          fptr(out)))
+        return out
+
     def transform_mix(self, content, styles, weights, alpha, mode, eps=-1.0, return_sweeps=False):
         """Style mix (wct_transform_mix): content [Nc][C], styles K x [Ns_k][C] float32, weights [K] (None: equal) ->
         sum_k lambda_k transform(content, styles[k]) [Nc][C], lambda = weights / sum(weights).  Sweeps: content, then style k."""
@@ -934,6 +972,63 @@ class Context(object):
         if resize is not None:
             return self._host_batch_resized(c, (hc, wc), [], out, enqueue)
         return self._host_batch([c], out, enqueue)
+
+    def stylize_prepared_strength(self, content, style, smap, relu_targets, alpha=1.0, adain=False, wct_mode='tf', content_colors=False):
+        """stylize_prepared() with a strength map (wct_stylize_prepared_strength): smap [H][W] uint8 of the content's size, 255 the
+        call's alpha, 0 "keep the content features"; every level samples it at its own stride.  An all-255 map gives
+        stylize_prepared's frame at alpha = 1 bit for bit."""
+        c0 = np.asarray(content)
+        m = _lib.strength_map(smap, c0.shape[:2])
+        check_prepared(self, [style], relu_targets)
+        c, arr, out, flags = self._prepared_args(c0, relu_targets, adain, wct_mode, content_colors)
+        check(self.lib.wct_stylize_prepared_strength(self.h, c.ctypes.data_as(_lib._U8), c.shape[0], c.shape[1],
+                                                     m.ctypes.data_as(_lib._U8), style.h, arr, len(arr), float(alpha), flags,
+                                                     out.ctypes.data_as(_lib._U8)))
+        return out
+
+    def stylize_prepared_strength_batch_dev(self, content_dev, hc, wc, batch, smaps_dev, style, relu_targets, alpha, out_dev,
+                                            adain=False, wct_mode='tf', warm=None, content_colors=False):
+        """stylize_prepared_batch_dev with one strength map per frame, smaps_dev [B][hc][wc] uint8 resident in HBM.  Asynchronous:
+        nothing of the maps is read on the host.  Frame f is stylize_prepared_strength(frame f, map f)."""
+        if not 1 <= int(batch) <= _lib.BATCH_MAX:
+            raise ValueError('a batch takes 1 .. %d frames, got %d' % (_lib.BATCH_MAX, batch))
+        lv = check_prepared(self, [style], relu_targets)
+        flags = _flags(adain, wct_mode, content_colors=content_colors)
+        arr = (C.c_int * len(lv))(*lv)
+        if warm is not None:
+            check_warm(self, warm, relu_targets, adain)
+            check(self.lib.wct_stylize_prepared_strength_batch_dev_warm(self.h, content_dev, hc, wc, int(batch), smaps_dev, style.h, arr,
+                                                                        len(lv), float(alpha), flags, warm.h, out_dev))
+            return
+        check(self.lib.wct_stylize_prepared_strength_batch_dev(self.h, content_dev, hc, wc, int(batch), smaps_dev, style.h, arr, len(lv),
+                                                               float(alpha), flags, out_dev))
+
+    def stylize_prepared_strength_batch(self, contents_u8, style, smaps, relu_targets, alpha=1.0, adain=False, wct_mode='tf', warm=None,
+                                        content_colors=False, resize=None):
+        """Host arrays in, host array out: contents [B][H][W][3] uint8 (B <= 32), smaps [B][H][W] uint8 (or one [H][W] map for
+        all) -> [B][Ho][Wo][3] uint8.  warm and resize (h, w): as in stylize_prepared_batch; the maps are given at the resized
+        size."""
+        if resize is not None:
+            hc, wc, c = check_resize(resize, contents_u8)
+        else:
+            c = u8(contents_u8)
+            if c.ndim != 4 or c.shape[3] != 3:
+                raise ValueError('expected [B][H][W][3] frames, got shape %s' % (c.shape,))
+            hc, wc = c.shape[1:3]
+        B = c.shape[0]
+        if not 1 <= B <= _lib.BATCH_MAX:
+            raise ValueError('a batch takes 1 .. %d frames, got %d' % (_lib.BATCH_MAX, B))
+        m = _lib.strength_maps_frames(smaps, B, (hc, wc))
+        check_prepared(self, [style], relu_targets)
+        if warm is not None:
+            check_warm(self, warm, relu_targets, adain)
+        ho, wo = self.output_size(hc, wc, relu_targets)
+        out = np.empty((B, ho, wo, 3), np.uint8)
+        enqueue = lambda dc, dm, do: self.stylize_prepared_strength_batch_dev(
+            dc, hc, wc, B, dm, style, relu_targets, alpha, do, adain=adain, wct_mode=wct_mode, warm=warm, content_colors=content_colors)
+        if resize is not None:
+            return self._host_batch_resized(c, (hc, wc), [m], out, enqueue)
+        return self._host_batch([c, m], out, enqueue)
 
     def stylize_prepared_wrap_batch_dev(self, content_dev, hc, wc, batch, style, relu_targets, alpha, out_dev, adain=False, wct_mode='tf'):
         """stylize_prepared_batch_dev on a torus (wct_stylize_prepared_wrap_batch_dev): every encoder and decoder of the chain sees

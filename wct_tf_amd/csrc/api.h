@@ -94,7 +94,8 @@ struct wct_ctx {
   DevBuf act[2], feat_c, feat_s[6], img_c, img_s, img_t[2], wct_out, wct_ws, stage[4];
   DevBuf usum_c, usum_s[6], umax;     // feature statistics from the tap epilogues (ConvArgs::usum / umax); umax: [7][32][UMAX_SLOTS] words
   DevBuf mix_in, feat_mix[6];      // a style mix: the K style inputs, and their features per level (K maps back to back)
-  DevBuf mask_in;                  // spatial control: the label map (wct_stylize_masked) or the row labels (wct_*_masked)
+  DevBuf mask_in;                  // spatial control: the label map (wct_stylize_masked) or the row labels (wct_*_masked); the
+                                   // strength map of wct_transform_strength, wct_adain_strength and wct_stylize_prepared_strength
   DevBuf tex_noise, tex[2];        // texture synthesis: the noise images, and the uint8 frames between two passes (alternating)
   DevBuf band_f, band_g, band_img; // banded stylization: a level's full fp32 feature map and its fp16 transform (either may pass
                                    // 2^31 bytes: every launch sees a slice), and the decoded image of one band with its halo
@@ -214,7 +215,8 @@ int run_decoder(wct_ctx* c, int level, const half_t* feat16, int B, int h, int w
 int run_transform(wct_ctx* c, const float* fc, int Nc, const float* fs, int Ns, int C, int P, float alpha, unsigned flags, float eps,
                   half_t* out16, float* out32, int* sweeps_dev, const WctFeatStats* st = nullptr,
                   const WctStyleRef* prep = nullptr /* a prepared style: fs may be null */,
-                  const WctWarmRef* warm = nullptr /* a warm state's basis for this level */);
+                  const WctWarmRef* warm = nullptr /* a warm state's basis for this level */,
+                  const WctStrength* sm = nullptr /* a strength map per pair: the blend moves into the apply's rows */);
 int mix_weights(const float* weights, int K, float* lambda);
 int run_transform_mix(wct_ctx* c, const float* fc, int Nc, const float* const* fs, const int* Ns, int K, const float* lambda, int C,
                       float alpha, unsigned flags, float eps, half_t* out16, float* out32, int* sweeps_dev,

@@ -139,15 +139,18 @@ int run_decoder(wct_ctx* c, int level, const half_t* feat16, int B, int h, int w
 }
 
 int run_transform(wct_ctx* c, const float* fc, int Nc, const float* fs, int Ns, int C, int P, float alpha, unsigned flags, float eps,
-                  half_t* out16, float* out32, int* sweeps_dev, const WctFeatStats* st, const WctStyleRef* prep, const WctWarmRef* warm) {
+                  half_t* out16, float* out32, int* sweeps_dev, const WctFeatStats* st, const WctStyleRef* prep, const WctWarmRef* warm,
+                  const WctStrength* sm) {
   const WctSkip skip = (flags & WCT_FLAG_STYLE_SHARED) ? WCT_SKIP_SHARED_STYLE : WCT_SKIP_NONE;
+  // (a strength map: the apply's epilogue reads the fp32 features once more, and one byte per pixel)
   const StageCost cost = {(double)P * 2.0 * C * C * ((double)Nc + Ns), (double)P * 2.0 * ((double)Nc + Ns) * C * 4,
-                          (double)P * (2.0 * C * C * Nc + 6.0 * C * C * C), (double)P * Nc * C * (4 + (out16 ? 2 : 0) + (out32 ? 4 : 0)),
-                          (double)P * (2.0 * Nc + 2.0 * Ns) * C * 4 + (double)P * Nc * C * 6};
+                          (double)P * (2.0 * C * C * Nc + 6.0 * C * C * C),
+                          (double)P * Nc * C * (4 + (out16 ? 2 : 0) + (out32 ? 4 : 0) + (sm ? 4 : 0)) + (sm ? (double)P * Nc : 0.0),
+                          (double)P * (2.0 * Nc + 2.0 * Ns) * C * 4 + (double)P * Nc * C * 6 + (sm ? (double)P * Nc : 0.0)};
   return run_stages(c, wct_workspace_bytes(C, Nc, Ns, P), flags, cost, [&](WctCall r) {
     r.alpha = alpha; r.eps = r.stages ? eps : 1e-5f; r.out16 = out16; r.out32 = out32; r.sweeps_dev = sweeps_dev;
-    if (!r.stages) return launch_adain(fc, Nc, fs, Ns, C, P, skip, r, st, prep);
-    return launch_wct(fc, Nc, fs, Ns, C, P, skip, r, st, prep, warm);
+    if (!r.stages) return launch_adain(fc, Nc, fs, Ns, C, P, skip, r, st, prep, sm);
+    return launch_wct(fc, Nc, fs, Ns, C, P, skip, r, st, prep, warm, sm);
   });
 }
 

@@ -2,10 +2,23 @@
 // compare them one by one).
 #include "api.h"
 
+// The strength map of one h x w feature map of Nc rows (host, Hm x Wm) into c->mask_in, enqueued; *sm: its device form
+static int stage_strength(wct_ctx* c, const uint8_t* smap, int Hm, int Wm, int Nc, int h, int w, int stride, WctStrength* sm) {
+  if (!smap) { wct_set_error("strength map: no map"); return WCT_ERR_ARG; }
+  if (Hm < 1 || Wm < 1 || h < 1 || w < 1 || stride < 1 || (long long)h * w != Nc) {
+    wct_set_error("strength map: a %dx%d map at stride %d for %d rows as %dx%d feature pixels", Hm, Wm, stride, Nc, h, w);
+    return WCT_ERR_ARG;
+  }
+  TRY(ensure(c, c->mask_in, (size_t)Hm * Wm));
+  HIP_TRY(hipMemcpyAsync(c->mask_in.p, smap, (size_t)Hm * Wm, hipMemcpyHostToDevice, c->stream));
+  *sm = WctStrength{(const uint8_t*)c->mask_in.p, Hm, Wm, w, stride};
+  return WCT_OK;
+}
+
 // One (content, style) pair of feature matrices through run_transform.  warm (with its level): the content solve starts from the
-// state's basis of that level, which then takes this pair's.
+// state's basis of that level, which then takes this pair's.  sm: a strength map on the device (stage_strength).
 static int transform_pair(wct_ctx* c, const float* content, int Nc, const float* style, int Ns, int C, float alpha, unsigned flags,
-                          float eps, wct_warm* warm, int level, float* out, int* sweeps_out) {
+                          float eps, wct_warm* warm, int level, float* out, int* sweeps_out, const WctStrength* sm = nullptr) {
   HIP_TRY(hipSetDevice(c->device));
   TRY(eig_stale(c));
   void *dc, *ds;
@@ -19,7 +32,7 @@ static int transform_pair(wct_ctx* c, const float* content, int Nc, const float*
     wr = {warm->basis[level], warm->valid[level] ? 1 : 0};
   }
   TRY(run_transform(c, (float*)dc, Nc, (float*)ds, Ns, C, 1, alpha, flags, eps, nullptr, (float*)c->stage[2].p, (int*)c->stage[3].p,
-                    nullptr, nullptr, warm ? &wr : nullptr));
+                    nullptr, nullptr, warm ? &wr : nullptr, sm));
   if (warm) warm->valid[level] = true;
   TRY(fetch(c, out, c->stage[2].p, (size_t)Nc * C * 4));
   if (sweeps_out) TRY(fetch(c, sweeps_out, c->stage[3].p, 2 * sizeof(int)));
@@ -30,6 +43,16 @@ extern "C" int wct_transform(wct_ctx* c, const float* content, int Nc, const flo
                              float alpha, int mode, float eps, float* out, int* sweeps_out) {
   ARG_CHECK(c && content && style && out && (mode == WCT_NP || mode == WCT_TF));
   return transform_pair(c, content, Nc, style, Ns, C, alpha, mode == WCT_NP ? WCT_FLAG_MODE_NP : 0, eps, nullptr, 0, out, sweeps_out);
+}
+
+extern "C" int wct_transform_strength(wct_ctx* c, const float* content, int Nc, int h, int w, const uint8_t* smap, int Hm, int Wm,
+                                      int stride, const float* style, int Ns, int C, float alpha, int mode, float eps, float* out,
+                                      int* sweeps_out) {
+  ARG_CHECK(c && content && style && out && (mode == WCT_NP || mode == WCT_TF));
+  HIP_TRY(hipSetDevice(c->device));
+  WctStrength sm;
+  TRY(stage_strength(c, smap, Hm, Wm, Nc, h, w, stride, &sm));
+  return transform_pair(c, content, Nc, style, Ns, C, alpha, mode == WCT_NP ? WCT_FLAG_MODE_NP : 0, eps, nullptr, 0, out, sweeps_out, &sm);
 }
 
 // wct_transform with the content statistics pooled over chunks of chunk_rows rows (the last chunk: what is left, a single
@@ -93,6 +116,21 @@ extern "C" int wct_adain(wct_ctx* c, const float* content, int Nc, const float* 
   TRY(ensure(c, c->stage[2], (size_t)Nc * C * 4));
   TRY(ensure(c, c->wct_ws, wct_workspace_bytes(C, Nc, Ns, 1)));
   TRY(launch_adain((float*)dc, Nc, (float*)ds, Ns, C, 1, WCT_SKIP_NONE, adain_call(c, alpha, epsilon), nullptr, nullptr));
+  return fetch(c, out, c->stage[2].p, (size_t)Nc * C * 4);
+}
+
+extern "C" int wct_adain_strength(wct_ctx* c, const float* content, int Nc, int h, int w, const uint8_t* smap, int Hm, int Wm, int stride,
+                                  const float* style, int Ns, int C, float alpha, float epsilon, float* out) {
+  ARG_CHECK(c && content && style && out);
+  HIP_TRY(hipSetDevice(c->device));
+  WctStrength sm;
+  TRY(stage_strength(c, smap, Hm, Wm, Nc, h, w, stride, &sm));
+  void *dc, *ds;
+  TRY(stage_in(c, 0, content, (size_t)Nc * C * 4, &dc));
+  TRY(stage_in(c, 1, style, (size_t)Ns * C * 4, &ds));
+  TRY(ensure(c, c->stage[2], (size_t)Nc * C * 4));
+  TRY(ensure(c, c->wct_ws, wct_workspace_bytes(C, Nc, Ns, 1)));
+  TRY(launch_adain((float*)dc, Nc, (float*)ds, Ns, C, 1, WCT_SKIP_NONE, adain_call(c, alpha, epsilon), nullptr, nullptr, &sm));
   return fetch(c, out, c->stage[2].p, (size_t)Nc * C * 4);
 }
 

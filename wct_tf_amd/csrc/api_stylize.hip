@@ -576,9 +576,11 @@ static int chain_states(wct_ctx* c, const Chain& chain, const wct_style* const* 
 // The body of the wct_stylize_prepared* calls (their pointer and flag checks done): B contents [B][Hc][Wc][3] on the device, K
 // handles; lambda null: one style for all B (K = 1), else the mix weights of K styles (B = 1).  Asynchronous unless a handle
 // has to compute a state (style_fill), which happens before anything of the content chain is enqueued.
+// smaps (one style): B strength maps [B][Hc][Wc] on the device, sampled by every level at its own stride.
 static int stylize_prepared_dev(wct_ctx* c, const void* content, int Hc, int Wc, int B, const wct_style* const* styles, int K,
                                 const float* lambda, const int* levels, int n_levels, float alpha, unsigned flags, uint8_t* out,
-                                wct_warm* warm = nullptr /* with one style (lambda null): start the content solves from it */) {
+                                wct_warm* warm = nullptr /* with one style (lambda null): start the content solves from it */,
+                                const uint8_t* smaps = nullptr) {
   HIP_TRY(hipSetDevice(c->device));
   for (int k = 0; k < K; ++k) TRY(style_live(c, styles[k]));
   if (warm) {
@@ -612,8 +614,10 @@ static int stylize_prepared_dev(wct_ctx* c, const void* content, int Hc, int Wc,
                                                      (half_t*)c->wct_out.p, nullptr, nullptr, &st, &refs[i]);
                           WctWarmRef wr = {};
                           if (warm) wr = {warm->basis[g.l], warm->valid[g.l] ? 1 : 0};
+                          const WctStrength sm = {smaps, Hc, Wc, g.w, 1 << (g.l - 1)};
                           TRY(run_transform(c, (float*)c->feat_c.p, g.h * g.w, nullptr, Ns[0], g.C, B, alpha, flags, -1.f,
-                                            (half_t*)c->wct_out.p, nullptr, nullptr, &st, &refs[i], warm ? &wr : nullptr));
+                                            (half_t*)c->wct_out.p, nullptr, nullptr, &st, &refs[i], warm ? &wr : nullptr,
+                                            smaps ? &sm : nullptr));
                           if (warm) warm->valid[g.l] = true;     // (the basis of frame B - 1 is enqueued)
                           return (int)WCT_OK;
                         }, out);
@@ -666,6 +670,61 @@ extern "C" int wct_stylize_prepared_batch_dev_warm(wct_ctx* c, const uint8_t* co
   TRY(style_flags_ok(flags));
   TRY(warm_live(c, warm));
   return stylize_prepared_dev(c, content, Hc, Wc, B, &style, 1, nullptr, levels, n_levels, alpha, flags, out, warm);
+}
+
+// ---------------------------------------------------------------------------
+// strength maps (strength_rule.h): the prepared-style calls with a per-pixel style strength -- the chain, the statistics and the
+// matrices of every level are the plain call's, the blend of every feature row takes the strength of its pixel
+// ---------------------------------------------------------------------------
+// the refusals of a strength call before anything is staged: the flags of a prepared style, a map, a content whole-image calls take
+static int strength_checks(const uint8_t* smaps, int Hc, int Wc, const int* levels, int n_levels, unsigned flags) {
+  TRY(style_flags_ok(flags));
+  if (!smaps) { wct_set_error("strength map: no map"); return WCT_ERR_ARG; }
+  Chain chain;
+  TRY(chain_geometry(Hc, Wc, levels, n_levels, &chain));
+  int band_rows;
+  TRY(band_rows_for(chain, &band_rows));
+  if (band_rows) {
+    wct_set_error("strength map: a %dx%d content passes the limit of one launch at these levels, and the banded call takes no map", Hc, Wc);
+    return WCT_ERR_ARG;
+  }
+  return WCT_OK;
+}
+
+extern "C" int wct_stylize_prepared_strength(wct_ctx* c, const uint8_t* content, int Hc, int Wc, const uint8_t* smap, const wct_style* style,
+                                             const int* levels, int n_levels, float alpha, unsigned flags, uint8_t* out) {
+  ARG_CHECK(c && content && out && levels && n_levels >= 1 && n_levels <= 16);
+  TRY(strength_checks(smap, Hc, Wc, levels, n_levels, flags));
+  TRY(style_live(c, style));
+  return host_frame(c, content, Hc, Wc, levels, n_levels, flags, out, [&](void* dc, uint8_t* frame) {
+    TRY(ensure(c, c->mask_in, (size_t)Hc * Wc));
+    HIP_TRY(hipMemcpyAsync(c->mask_in.p, smap, (size_t)Hc * Wc, hipMemcpyHostToDevice, c->stream));
+    return stylize_prepared_dev(c, dc, Hc, Wc, 1, &style, 1, nullptr, levels, n_levels, alpha, flags, frame, nullptr,
+                                (const uint8_t*)c->mask_in.p);
+  });
+}
+
+// the body of the two batch calls: B maps on the device, asynchronous like wct_stylize_prepared_batch_dev
+static int strength_batch_dev(wct_ctx* c, const uint8_t* content, int Hc, int Wc, int B, const uint8_t* smaps, const wct_style* style,
+                              const int* levels, int n_levels, float alpha, unsigned flags, wct_warm* warm, uint8_t* out) {
+  ARG_CHECK(c && content && out && levels && n_levels >= 1 && n_levels <= 16);
+  if (B < 1 || B > 32) { wct_set_error("strength map: a batch of %d frames, must be 1 .. 32", B); return WCT_ERR_ARG; }
+  TRY(strength_checks(smaps, Hc, Wc, levels, n_levels, flags));
+  return stylize_prepared_dev(c, content, Hc, Wc, B, &style, 1, nullptr, levels, n_levels, alpha, flags, out, warm, smaps);
+}
+
+extern "C" int wct_stylize_prepared_strength_batch_dev(wct_ctx* c, const uint8_t* content, int Hc, int Wc, int B, const uint8_t* smaps,
+                                                       const wct_style* style, const int* levels, int n_levels, float alpha,
+                                                       unsigned flags, uint8_t* out) {
+  return strength_batch_dev(c, content, Hc, Wc, B, smaps, style, levels, n_levels, alpha, flags, nullptr, out);
+}
+
+extern "C" int wct_stylize_prepared_strength_batch_dev_warm(wct_ctx* c, const uint8_t* content, int Hc, int Wc, int B, const uint8_t* smaps,
+                                                            const wct_style* style, const int* levels, int n_levels, float alpha,
+                                                            unsigned flags, wct_warm* warm, uint8_t* out) {
+  ARG_CHECK(c != nullptr);
+  TRY(warm_live(c, warm));
+  return strength_batch_dev(c, content, Hc, Wc, B, smaps, style, levels, n_levels, alpha, flags, warm, out);
 }
 
 // ---------------------------------------------------------------------------

@@ -207,6 +207,12 @@ struct WctStyleSlots { const float* state[32]; };
 // re-orthonormalised eigenvectors of the call's LAST content matrix either way
 struct WctWarmRef { float* basis; int valid; };
 
+// Strength maps (strength_rule.h): smap [P][Hm][Wm] uint8 on the device, one map per pair; row n of a pair's N = h x w feature map
+// is pixel (n / w, n % w) and reads smap[min(i stride, Hm - 1)][min(j stride, Wm - 1)] -- 255 is the call's alpha, 0 keeps the
+// content features.  The statistics, covariance, eigensystem and matrices of the level are the plain call's: only the blend moves
+// from the matrix M (alpha = 1 here) to the rows the apply stores.
+struct WctStrength { const uint8_t* smap; int Hm, Wm, w, stride; };
+
 // The call block of a transform launcher: what every one of them takes besides its features and their geometry.  The drivers
 // (api.h: run_stages) fill workspace, stream, eig_fail, mode and stages from the context, their callers the rest.
 struct WctCall {
@@ -231,12 +237,12 @@ int launch_style_state(const float* style, int Ns, int C, const WctStyleKey& key
 // skip: WCT_SKIP_NONE, or WCT_SKIP_SHARED_STYLE -- style holds ONE feature map used by all P pairs, its statistics and eigensystem
 // are computed once.  stats: unit sums / maxima a conv epilogue left beside the features.  prep: one prepared style for all P pairs
 // (skip is then ignored; style may be null).  warm: start the P content eigensolves from a stored basis (plain pairs or a prepared
-// style only).  Each of the three may be null.
+// style only).  sm: a strength map per pair (Nc a multiple of sm->w).  Each of the four may be null.
 size_t wct_workspace_bytes(int C, int Nc, int Ns, int P);
 int launch_wct(const float* content, int Nc, const float* style, int Ns, int C, int P, WctSkip skip, const WctCall& r,
-               const WctFeatStats* stats, const WctStyleRef* prep, const WctWarmRef* warm);
+               const WctFeatStats* stats, const WctStyleRef* prep, const WctWarmRef* warm, const WctStrength* sm = nullptr);
 int launch_adain(const float* content, int Nc, const float* style, int Ns, int C, int P, WctSkip skip, const WctCall& r,
-                 const WctFeatStats* stats, const WctStyleRef* prep);
+                 const WctFeatStats* stats, const WctStyleRef* prep, const WctStrength* sm = nullptr);
 // Style mix (Li et al. 2017, sec. 4.2): out = sum_k lambda[k] T(content, styles[k]) for K <= WCT_MIX_MAX styles of any sizes
 // Ns[k]; lambda[k] in [0, 1] summing to 1 (normalised by the caller).  One content whitening, K colourings mixed before ONE
 // blend product and apply.  sweeps_dev [2K]: slot 2k + 1 style k, slot 0 the content (the even slots k >= 1 read 0).  stats:

@@ -14,6 +14,7 @@
 // style mix, AdaIN); spatial control is mask.hip, style-swap style_swap.hip.  What the units share: wct_stages.h.
 #include "wct_stages.h"
 #include "jacobi_dev.h"   // JacobiState alone: carve() sizes the solver's state words
+#include "strength_rule.h"
 #include <algorithm>
 #include <type_traits>
 
@@ -32,6 +33,7 @@ template <int BC, int BP, typename Args = ApplyArgs>
 __global__ __launch_bounds__(256, 2) void apply_f16x2_kernel(Args p) {
   constexpr bool SEGB = std::is_same<Args, ApplySegBatchArgs>::value;   // a masked batch: per-frame seg_off / perm / rows
   constexpr bool SEG = std::is_same<Args, ApplySegArgs>::value || SEGB;  // (ApplyArgs: not a line of the plain apply changes)
+  constexpr bool MAP = std::is_same<Args, ApplyMapArgs>::value;          // a strength map: M is the alpha = 1 matrix, the blend per row
   constexpr int TM = BC / 64, TN = BP / 64;
   constexpr int MI = BC * 4 / 256, XI = BP * 4 / 256;    // 16-B (8 k) pieces per thread and stage
   __shared__ __attribute__((aligned(16))) unsigned char lm[2][BC * 64];   // M hi, lo
@@ -177,6 +179,25 @@ __global__ __launch_bounds__(256, 2) void apply_f16x2_kernel(Args p) {
       dst[j] = p.perm[seg0 + (n < N ? n : 0)];
       if constexpr (SEGB) dst[j] += row0;
     }
+  // MAP: the strength a of this lane's pixels and their content features, in the epilogue's own layout (4 consecutive channels of
+  // one pixel), fetched before the first store as well
+  [[maybe_unused]] float amap[TN];
+  [[maybe_unused]] f32x4 xv[TN][TM][4];
+  if constexpr (MAP)
+#pragma unroll
+    for (int j = 0; j < TN; ++j) {
+      const int n = n0 + (wn * TN + j) * 32 + (lane & 31), nc = n < N ? n : 0;
+      const uint8_t* sm = p.smap + (size_t)pair * p.Hm * p.Wm;
+      amap[j] = wct_strength_a(p.alpha, sm[wct_strength_index(nc / p.w, nc % p.w, p.stride, p.Hm, p.Wm)]);
+#pragma unroll
+      for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int rq = 0; rq < 4; ++rq) {
+          const int co = c0 + (wm * TM + i) * 32 + 8 * rq + 4 * kgrp;
+          const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+          xv[j][i][rq] = co < C ? *reinterpret_cast<const f32x4*>(x + (size_t)nc * C + co) : z;
+        }
+    }
 #pragma unroll
   for (int j = 0; j < TN; ++j) {
     const int n = n0 + (wn * TN + j) * 32 + (lane & 31);
@@ -193,6 +214,9 @@ __global__ __launch_bounds__(256, 2) void apply_f16x2_kernel(Args p) {
         f32x4 v;
 #pragma unroll
         for (int q = 0; q < 4; ++q) v[q] = acc[i][j][rq * 4 + q] * inv + bv[q];
+        if constexpr (MAP)
+#pragma unroll
+          for (int q = 0; q < 4; ++q) v[q] = wct_strength_blend(amap[j], v[q], xv[j][i][rq][q]);
         if (p.out32 && n_ok && co < C) *reinterpret_cast<f32x4*>(p.out32 + row + co) = v;
         typedef _Float16 h2 __attribute__((ext_vector_type(2)));
         h2 lo = {(half_t)v[0], (half_t)v[1]}, hi = {(half_t)v[2], (half_t)v[3]};
@@ -225,6 +249,7 @@ int launch_apply_args(const Args& a, int nmax, int P, hipStream_t s) {
 }
 template int launch_apply_args<ApplySegArgs>(const ApplySegArgs&, int, int, hipStream_t);
 template int launch_apply_args<ApplySegBatchArgs>(const ApplySegBatchArgs&, int, int, hipStream_t);
+template int launch_apply_args<ApplyMapArgs>(const ApplyMapArgs&, int, int, hipStream_t);
 
 // ---------------------------------------------------------------------------
 // workspace carving (P independent content/style pairs per call)
@@ -308,6 +333,22 @@ int launch_blend(const WctCarve& w, int C, int P, float alpha, WctSkip skip, hip
 // out[n][j] = sum_k (x[n][k]-mc[k]) M[j][k] + bias[j]
 int launch_apply(const WctCarve& w, const float* content, int Nc, int C, int P, half_t* out16, float* out32, hipStream_t s) {
   return launch_apply_args(apply_args<ApplyArgs>(w, content, Nc, C, out16, out32), Nc, P, s);
+}
+
+// a strength map's geometry against the rows it serves
+static bool strength_ok(const WctStrength& sm, int Nc) {
+  return sm.smap && sm.Hm >= 1 && sm.Wm >= 1 && sm.w >= 1 && sm.stride >= 1 && Nc % sm.w == 0;
+}
+
+// the blend product at alpha = 1 for P pairs -- the plain alpha = 1 call's M, bias and mabs --, then the apply that blends every
+// row with its content features by the strength of its pixel
+static int launch_blend_apply_map(const WctCarve& w, const float* content, int Nc, int C, int P, WctSkip skip, const WctCall& r,
+                                  const WctStrength& sm) {
+  int rc;
+  if ((rc = launch_blend(w, C, P, 1.f, skip, r.stream))) return rc;
+  ApplyMapArgs a = apply_args<ApplyMapArgs>(w, content, Nc, C, r.out16, r.out32);
+  a.smap = sm.smap; a.Hm = sm.Hm; a.Wm = sm.Wm; a.w = sm.w; a.stride = sm.stride; a.alpha = r.alpha;
+  return launch_apply_args(a, Nc, P, r.stream);
 }
 
 // the blend product for P pairs, then the apply
@@ -400,9 +441,10 @@ int launch_style_state(const float* style, int Ns, int C, const WctStyleKey& key
 }
 
 int launch_wct(const float* content, int Nc, const float* style, int Ns, int C, int P, WctSkip skip, const WctCall& r,
-               const WctFeatStats* stats, const WctStyleRef* prep, const WctWarmRef* warm) {
+               const WctFeatStats* stats, const WctStyleRef* prep, const WctWarmRef* warm, const WctStrength* sm) {
   const int mode = r.mode, stages = r.stages; hipStream_t s = r.stream;
   ARG_CHECK(C % 32 == 0 && C >= 32 && C <= 1024 && Nc >= 2 && Ns >= 2 && P >= 1 && P <= 32);
+  ARG_CHECK(!sm || strength_ok(*sm, Nc));
   ARG_CHECK(skip == WCT_SKIP_NONE || skip == WCT_SKIP_SHARED_STYLE);
   ARG_CHECK(!warm || (warm->basis && (skip == WCT_SKIP_NONE || prep)));
   if (prep) skip = WCT_SKIP_STYLE;               // (the style rows are not read: `style` may be null)
@@ -429,7 +471,8 @@ int launch_wct(const float* content, int Nc, const float* style, int Ns, int C, 
   if (!(stages & WCT_STAGE_APPLY)) return WCT_OK;
 
   if (prep && (rc = launch_style_load(*prep, 1, w, C, true, s))) return rc;
-  if ((rc = launch_spectral_tail(w, C, P, r.alpha, mode, r.eps, skip, P, s))) return rc;
+  if ((rc = launch_spectral_tail(w, C, P, sm ? 1.f : r.alpha, mode, r.eps, skip, P, s))) return rc;
+  if (sm) return launch_blend_apply_map(w, content, Nc, C, P, skip, r, *sm);
   return launch_blend_apply(w, content, Nc, C, P, skip, r);
 }
 
@@ -572,10 +615,45 @@ __global__ void adain_apply_kernel(const float* x, size_t n4_per_pair, int C, co
   }
 }
 
+// adain_apply_kernel with a strength map: y is its expression (so the bits of its alpha = 1 output), the blend strength_rule.h's
+// with the strength of the row's pixel; one row of C channels per C / 4 consecutive threads, as there
+__global__ void adain_apply_map_kernel(const float* x, size_t n4_per_pair, int C, const float* mean, const float* var, float eps,
+                                       half_t* out16, float* out32, int style_of_pair0, WctStrength m, float alpha) {
+  const int pair = blockIdx.y;
+  const int cq = C / 4;
+  const float* mp = mean + (size_t)pair * 2 * C;
+  const float* vp = var + (size_t)pair * 2 * C;
+  const float* ms = mean + (size_t)(style_of_pair0 ? 0 : pair) * 2 * C + C;
+  const float* vs = var + (size_t)(style_of_pair0 ? 0 : pair) * 2 * C + C;
+  const uint8_t* sm = m.smap + (size_t)pair * m.Hm * m.Wm;
+  const size_t base = (size_t)pair * n4_per_pair;
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n4_per_pair; i += (size_t)gridDim.x * blockDim.x) {
+    const int c = (int)(i % cq) * 4, n = (int)(i / cq);
+    const float a = wct_strength_a(alpha, sm[wct_strength_index(n / m.w, n % m.w, m.stride, m.Hm, m.Wm)]);
+    f32x4 v = *reinterpret_cast<const f32x4*>(x + (base + i) * 4);
+    f32x4 o;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float inv = 1.f / sqrtf(vp[c + j] + eps);
+      const float sd = sqrtf(vs[c + j]);
+      const float y = (v[j] - mp[c + j]) * inv * sd + ms[c + j];
+      o[j] = wct_strength_blend(a, y, v[j]);
+    }
+    if (out32) *reinterpret_cast<f32x4*>(out32 + (base + i) * 4) = o;
+    if (out16) {
+      half4 h;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) h[j] = (half_t)o[j];
+      *reinterpret_cast<half4*>(out16 + (base + i) * 4) = h;
+    }
+  }
+}
+
 int launch_adain(const float* content, int Nc, const float* style, int Ns, int C, int P, WctSkip skip, const WctCall& r,
-                 const WctFeatStats* stats, const WctStyleRef* prep) {
+                 const WctFeatStats* stats, const WctStyleRef* prep, const WctStrength* sm) {
   hipStream_t s = r.stream;
   ARG_CHECK(C % 4 == 0 && C <= 1024 && Nc >= 1 && Ns >= 1 && P >= 1 && P <= 32);
+  ARG_CHECK(!sm || strength_ok(*sm, Nc));
   ARG_CHECK(skip == WCT_SKIP_NONE || skip == WCT_SKIP_SHARED_STYLE);
   if (prep) skip = WCT_SKIP_STYLE;
   const int Cw = C < 32 ? 32 : C;
@@ -585,6 +663,10 @@ int launch_adain(const float* content, int Nc, const float* style, int Ns, int C
   if ((rc = launch_means(content, Nc, style, Ns, C, P, w, true, skip, s, stats))) return rc;
   if (prep && (rc = launch_style_load(*prep, 1, w, C, false, s))) return rc;
   const size_t n4 = (size_t)Nc * C / 4;
+  if (sm)
+    hipLaunchKernelGGL(adain_apply_map_kernel, dim3(rows_grid(Nc, C), P), dim3(256), 0, s, content, n4, C, w.mean, w.var, r.eps, r.out16,
+                       r.out32, one_style(skip) ? 1 : 0, *sm, r.alpha);
+  else
   hipLaunchKernelGGL(adain_apply_kernel, dim3(rows_grid(Nc, C), P), dim3(256), 0, s, content, n4, C, w.mean, w.var, r.alpha, r.eps, r.out16, r.out32,
                      one_style(skip) ? 1 : 0);
   HIP_TRY(hipGetLastError());

@@ -78,7 +78,10 @@ struct ApplySegArgs : ApplyArgs { const int* seg_off; const int* perm; int lab[W
 // The segments of a masked BATCH (launch_wct_masked_batch): x, out16 / out32 hold G frames of N rows, seg_off [G][WCT_MIX_MAX + 1]
 // and perm [G][N] are per frame, and pair p is the segment of label fl[p] & 7 of frame fl[p] >> 3
 struct ApplySegBatchArgs : ApplyArgs { const int* seg_off; const int* perm; unsigned char fl[WCT_PLAN_PAIRS]; };
-// the ApplyArgs part of any of the three: x [N rows a pair, or a masked transform's gathered rows] against the matrices of w
+// A strength map (launch_wct with a WctStrength): M, bias and mabs are the alpha = 1 call's, and row r of pair p
+// leaves as strength_rule.h blends it with x -- a = alpha * smap[p][pixel of r] / 255 (the map addressing of WctStrength)
+struct ApplyMapArgs : ApplyArgs { const uint8_t* smap; int Hm, Wm, w, stride; float alpha; };
+// the ApplyArgs part of any of the four: x [N rows a pair, or a masked transform's gathered rows] against the matrices of w
 template <typename Args>
 static inline Args apply_args(const WctCarve& w, const float* x, int N, int C, half_t* out16, float* out32) {
   Args a;
@@ -111,7 +114,7 @@ int launch_spectral_function(const float* A, const float* V, float* G, float* X,
 // longest has nmax rows), whose argument blocks start from apply_args
 int launch_blend(const WctCarve& w, int C, int P, float alpha, WctSkip skip, hipStream_t s);
 int launch_apply(const WctCarve& w, const float* content, int Nc, int C, int P, half_t* out16, float* out32, hipStream_t s);
-template <typename Args> int launch_apply_args(const Args& a, int nmax, int P, hipStream_t s);   // (ApplySegArgs, ApplySegBatchArgs)
+template <typename Args> int launch_apply_args(const Args& a, int nmax, int P, hipStream_t s);   // (ApplySegArgs, ApplySegBatchArgs, ApplyMapArgs)
 // warm.hip (video warm start): A' = V0^T A V0 of the P content matrices of w in place (w.X scratch); V = V0 V' of the same in place
 // (w.X scratch); basis = V (3 I - V^T V) / 2 of one C x C matrix (scratch: C x C floats)
 int launch_warm_rotate(const WctCarve& w, int C, int P, const float* V0, hipStream_t s);

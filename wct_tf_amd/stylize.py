@@ -58,6 +58,10 @@ _FLAGS = [
     (('--mask-styles',), dict(nargs='+', default=None, metavar='PATH',
                               help='the K style images of --mask-path, label 0 first; not with --style-path / -r / '
                                    '--interp-styles / --concat')),
+    (('--alpha-map',), dict(default=None, metavar='PATH',
+                            help='a strength map: an 8-bit grey image, resized (bilinear) to each content; white takes --alpha, '
+                                 'black keeps the content, greys in between.  With --style-path; not with --swap5, '
+                                 '--interp-styles, --mask-path, --keep-colors, --passes > 1 or --band-rows')),
     (('--band-rows',), dict(type=int, default=0, metavar='N',
                             help='image rows per band (a multiple of 16) of the banded call, which takes contents of any size; 0: '
                                  'only for a content past the limit of one launch (8.4 MP with relu1_1, 16.7 MP without), at the '
@@ -132,7 +136,7 @@ def check_color_args(parser, args):
 def _unbanded(args):
     """the options of this run that the banded call does not serve"""
     on = [('--adain', args.adain), ('--swap5', args.swap5), ('--interp-styles', args.interp_styles is not None),
-          ('--mask-path', args.mask_path is not None)]
+          ('--mask-path', args.mask_path is not None), ('--alpha-map', getattr(args, 'alpha_map', None) is not None)]
     return [name for name, v in on if v]
 
 
@@ -171,15 +175,48 @@ def run_passes(model, content, args, predict):
     return out
 
 
-def stylize_pair(model, content, style, args, prepared=None):
+def check_alpha_map_args(parser, args):
+    """--alpha-map: what a strength map does not combine with (parser.error exits)"""
+    if args.alpha_map is None:
+        return
+    on = [('--swap5', args.swap5), ('--interp-styles', args.interp_styles is not None), ('--mask-path', args.mask_path is not None),
+          ('--keep-colors', args.keep_colors), ('--passes > 1', args.passes > 1), ('--band-rows', getattr(args, 'band_rows', 0) != 0)]
+    bad = [name for name, v in on if v]
+    if bad:
+        parser.error('--alpha-map does not combine with %s: a strength map goes with one style, WCT or AdaIN, in one pass on the '
+                     'whole image' % ' / '.join(bad))
+
+
+def load_alpha_map(path):
+    """the strength map file as 8-bit grey [H][W]"""
+    from PIL import Image
+    with Image.open(path) as im:
+        return np.array(im.convert('L'))
+
+
+def strength_map(grey, shape_hw):
+    """the strength map [h][w] of a grey image: resized with Pillow's bilinear filter to shape_hw"""
+    from PIL import Image
+    h, w = (int(v) for v in shape_hw[:2])
+    g = np.asarray(grey, np.uint8)
+    if g.shape != (h, w):
+        g = np.array(Image.fromarray(g).resize((w, h), Image.BILINEAR))
+    return np.ascontiguousarray(g)
+
+
+def stylize_pair(model, content, style, args, prepared=None, alpha_grey=None):
     """one output image: optional CORAL, `--passes` predictions, optional `--concat` (stylize.py:85-110).  prepared: the
-    PreparedStyle of `style` (can_prepare), or None"""
+    PreparedStyle of `style` (can_prepare), or None.  alpha_grey: the grey image of --alpha-map, or None"""
     if args.keep_colors:
         from .ops import preserve_colors_np
         style = preserve_colors_np(style, content, ctx=model.sess)
-    out = run_passes(model, content, args, lambda img, colors: model.predict(
-        img, style if prepared is None else prepared, args.alpha, args.swap5, args.ss_alpha, args.adain, content_colors=colors,
-        band_rows=getattr(args, 'band_rows', 0) or None))
+    if alpha_grey is not None:             # (one pass, no swap5, no bands: check_alpha_map_args)
+        out = model.predict(content, style if prepared is None else prepared, args.alpha, adain=args.adain,
+                            content_colors=getattr(args, 'content_colors', False), strength=strength_map(alpha_grey, content.shape[:2]))
+    else:
+        out = run_passes(model, content, args, lambda img, colors: model.predict(
+            img, style if prepared is None else prepared, args.alpha, args.swap5, args.ss_alpha, args.adain, content_colors=colors,
+            band_rows=getattr(args, 'band_rows', 0) or None))
     if args.concat:
         side = out.shape[0]
         out = np.hstack([utils._imresize(style, (side, side)), out])
@@ -287,6 +324,7 @@ def main(argv=None):
     check_mask_args(parser, args)
     check_color_args(parser, args)
     check_band_args(parser, args)
+    check_alpha_map_args(parser, args)
     if args.synthetic_weights is None and not args.checkpoints:
         parser.error('--checkpoints is required (stylize.py:17) unless --synthetic-weights SEED is given')
     if args.gpus > 0:
@@ -348,6 +386,7 @@ def main(argv=None):
     # every style once, not once per content: the whole style side of every further pair (the first MAX_PREPARED styles of a
     # large folder; the others go as images, as before)
     loaded, n_prepared = {}, 0
+    alpha_grey = load_alpha_map(args.alpha_map) if args.alpha_map is not None else None
     for cpath in contents:
         content = utils.get_img(cpath)
         if args.content_size > 0:
@@ -360,7 +399,7 @@ def main(argv=None):
                 loaded[spath] = (style, model.prepare_style(style, adain=args.adain) if prepare else None)
                 n_prepared += prepare
             style, prepared = loaded[spath]
-            result = stylize_pair(model, content, style, args, prepared)
+            result = stylize_pair(model, content, style, args, prepared, alpha_grey)
             target = os.path.join(args.out_path, '%s_%s%s' % (_stem(cpath), _stem(spath), os.path.splitext(cpath)[1]))
             utils.save_img(target, result)
             written += 1

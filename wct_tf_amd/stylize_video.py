@@ -83,6 +83,11 @@ _FLAGS = [
     (('--mask-styles',), dict(nargs='+', default=None, metavar='PATH',
                               help='the K style images of --mask-path, label 0 first; replaces --style-path; not with '
                                    '--keep-colors, --swap5 or --concat')),
+    (('--alpha-map',), dict(default=None, metavar='PATH',
+                            help='a strength map: one 8-bit grey image for all frames, or a directory with one map per frame '
+                                 '(matched to the frames in sorted order; the counts must agree), resized (bilinear) to the frame; '
+                                 'white takes --alpha, black keeps the frame, greys in between.  With --style-path; not with '
+                                 '--swap5, --mask-path, --keep-colors or --passes > 1')),
 ]
 
 
@@ -116,6 +121,18 @@ def check_mask_args(parser, args):
         parser.error('--mask-path does not combine with --keep-colors, --swap5 or --concat')
     if len(args.mask_styles) > 8:
         parser.error('--mask-styles takes at most 8 styles')
+
+
+def check_alpha_map_args(parser, args):
+    """--alpha-map: what a strength map does not combine with (parser.error exits)"""
+    if args.alpha_map is None:
+        return
+    on = [('--swap5', args.swap5), ('--mask-path', args.mask_path is not None), ('--keep-colors', args.keep_colors),
+          ('--passes > 1', args.passes > 1)]
+    bad = [name for name, v in on if v]
+    if bad:
+        parser.error('--alpha-map does not combine with %s: a strength map goes with one style, WCT or AdaIN, in one pass'
+                     % ' / '.join(bad))
 
 
 def check_warm_args(parser, args):
@@ -166,14 +183,14 @@ def content_colors_frames(wct_model, stylized, frames):
                            for i in range(0, len(frames), 32)], axis=0)
 
 
-def match_masks(mask_path, frame_files):
-    """the label map file of every frame: `mask_path` is one file for all frames, or a directory whose maps are matched to the
-    frames in sorted order (natural_key) -- the counts must agree (ValueError, before any GPU work)"""
+def match_masks(mask_path, frame_files, what='label maps'):
+    """the label map (or strength map) file of every frame: `mask_path` is one file for all frames, or a directory whose maps are
+    matched to the frames in sorted order (natural_key) -- the counts must agree (ValueError, before any GPU work)"""
     if not os.path.isdir(mask_path):
         return [mask_path] * len(frame_files)
     maps = sorted(get_files(mask_path), key=natural_key)
     if len(maps) != len(frame_files):
-        raise ValueError('%d label maps in %s for %d frames' % (len(maps), mask_path, len(frame_files)))
+        raise ValueError('%d %s in %s for %d frames' % (len(maps), what, mask_path, len(frame_files)))
     return maps
 
 
@@ -229,8 +246,17 @@ def stylize_frames_masked(wct_model, frame_files, mask_files, styles, args):
             h.close()
 
 
-def stylize_frames(wct_model, frame_files, style_img, args):
-    """Yield (frame_file, stylized uint8 image) in order; consecutive same-sized frames are batched."""
+def stylize_frames(wct_model, frame_files, style_img, args, alpha_files=None):
+    """Yield (frame_file, stylized uint8 image) in order; consecutive same-sized frames are batched.  alpha_files: the strength map
+    file of every frame (--alpha-map), or None."""
+    from .stylize import load_alpha_map, strength_map
+    alpha_of = dict(zip(frame_files, alpha_files)) if alpha_files is not None else {}
+
+    def strengths_of(files, shape_hw):
+        """the strength maps [B][h][w] of the frames `files`, resized to the frames' (resized) size"""
+        greys = {p: load_alpha_map(p) for p in {alpha_of[f] for f in files}}
+        return np.stack([strength_map(greys[alpha_of[f]], shape_hw) for f in files])
+
     def load(f):
         img = get_img(f)
         if args.content_size > 0 and not getattr(args, 'device_resize', False):
@@ -250,10 +276,12 @@ def stylize_frames(wct_model, frame_files, style_img, args):
     # --content-colors: fused into a single pass; after several plain passes the op runs once, against the input frames
     colors = getattr(args, 'content_colors', False)
 
-    def run(frames, style):
+    def run(frames, style, files):
         style = prepared if prepared is not None else style
+        size = device_size(args, frames)
+        maps = strengths_of(files, size or frames.shape[1:3]) if alpha_files is not None else None     # (one pass: check_alpha_map_args)
         out = wct_model.predict_frames(frames, style, args.alpha, args.swap5, args.ss_alpha, args.adain, batch=args.batch, warm=warm,
-                                       content_colors=colors and args.passes <= 1, resize=device_size(args, frames))
+                                       content_colors=colors and args.passes <= 1, resize=size, strengths=maps)
         for _ in range(args.passes - 1):                      # later passes: plain WCT, as stylize_video.py:124-126
             out = wct_model.predict_frames(out, style, args.alpha, adain=args.adain, batch=args.batch)
         if colors and args.passes > 1:
@@ -284,7 +312,7 @@ def stylize_frames(wct_model, frame_files, style_img, args):
                                                     adain=args.adain, wct_mode=wct_model.wct_mode)
             style_per_frame = list(styles)
         else:
-            outs = run(frames, style_img)
+            outs = run(frames, style_img, group_files)
             style_per_frame = [style_img] * len(group)
         for f, o, s in zip(group_files, outs, style_per_frame):
             if args.concat:                                   # stylize_video.py:129-132
@@ -303,6 +331,7 @@ def main(argv=None):
     check_warm_args(parser, args)
     check_color_args(parser, args)
     check_resize_args(parser, args)
+    check_alpha_map_args(parser, args)
     if args.synthetic_weights is None and not args.checkpoints:
         parser.error('--checkpoints is required (stylize.py:17) unless --synthetic-weights SEED is given')
     start = time.time()
@@ -321,6 +350,7 @@ def main(argv=None):
     frame_files = list_frames(in_dir)
     masked = args.mask_path is not None
     mask_files = match_masks(args.mask_path, frame_files) if masked else None      # (the count check: before any GPU work)
+    alpha_files = match_masks(args.alpha_map, frame_files, 'strength maps') if args.alpha_map is not None else None
     weights = None
     if args.synthetic_weights is not None:
         from .weights import synthetic_weights
@@ -347,7 +377,7 @@ def main(argv=None):
             results = stylize_frames_masked(wct_model, frame_files, mask_files, [load_style(p) for p in args.mask_styles], args)
         else:
             style_prefix = os.path.splitext(os.path.basename(style_fullpath))[0]
-            results = stylize_frames(wct_model, frame_files, load_style(style_fullpath), args)
+            results = stylize_frames(wct_model, frame_files, load_style(style_fullpath), args, alpha_files)
         out_dir = os.path.join(args.tmp_dir, 'sytlized') if is_video else \
             os.path.join(args.out_path, '{}_{}'.format(content_prefix, style_prefix))
         os.makedirs(out_dir, exist_ok=True)

@@ -183,8 +183,19 @@ class WCT(object):
                                  % name)
         return rows
 
+    def _strength_refusals(self, shape, swap5, band_rows, wrap=False):
+        """What a strength map does not go with, as a ValueError before any GPU call: swap5, wrap, bands -- asked for, or needed by
+        a content of `shape` (H, W) past the limit of one launch."""
+        from .context import band_rows as auto_band_rows
+        for name, on in (('swap5', swap5), ('wrap', wrap), ('band_rows', band_rows is not None)):
+            if on:
+                raise ValueError('%s is not served with a strength map: it goes with one style, WCT or AdaIN, on the whole image' % name)
+        if auto_band_rows(shape[0], shape[1], self.relu_targets):
+            raise ValueError('a strength map is not served on a %dx%d content: it passes the limit of one launch and runs in bands, '
+                             'which take no map' % (shape[0], shape[1]))
+
     def predict(self, content, style, alpha=1, swap5=False, ss_alpha=1, adain=False, warm=None, content_colors=False,
-                band_rows=None):
+                band_rows=None, strength=None):
         '''Stylize a single content/style pair; arrays in [0,255], returns uint8 HxWx3.
            The /255 preprocess and the clip*255 postprocess run inside the library
            (fused at the ends of the kernel chain).  `style` may be a PreparedStyle (prepare_style); with one, `warm` may be a
@@ -194,7 +205,26 @@ class WCT(object):
            band_rows: None sends a content to the banded call (Context.stylize_prepared_banded) only when it passes the limit of
            the whole-image call -- 8.4 MP with relu1_1 among the targets, 16.7 MP without --, an int forces it (a multiple of 16
            image rows per band; 0: the automatic height).  A style image is then prepared, used and closed.  adain, swap5 and
-           warm are not served there: ValueError.'''
+           warm are not served there: ValueError.
+           strength: a uint8 map [H][W] of the content's size (Context.stylize_prepared_strength) -- 255 the call's alpha, 0 "keep
+           the content features", every level sampling it at its own stride; a style image is prepared for the call.  No swap5,
+           warm or bands with it: ValueError.'''
+        if strength is not None:
+            from ._lib import strength_map
+            content = np.asarray(content)
+            if content.ndim != 3 or content.shape[2] != 3:
+                raise ValueError('expected an HxWx3 content, got shape %s' % (content.shape,))
+            strength = strength_map(strength, content.shape[:2])                  # ValueError before any GPU call
+            self._strength_refusals(content.shape, swap5, band_rows)
+            if warm is not None:
+                raise ValueError('warm is not served with predict(strength=...): predict_frames(strengths=...) takes a warm state')
+            if isinstance(style, PreparedStyle):
+                check_prepared(self.sess, [style], self.relu_targets)
+                return self.sess.stylize_prepared_strength(content, style, strength, self.relu_targets, alpha=alpha, adain=adain,
+                                                           wct_mode=self.wct_mode, content_colors=content_colors)
+            with self.prepare_style(np.asarray(style), adain=adain) as handle:
+                return self.sess.stylize_prepared_strength(content, handle, strength, self.relu_targets, alpha=alpha, adain=adain,
+                                                           wct_mode=self.wct_mode, content_colors=content_colors)
         rows = self._band_route(content, band_rows, swap5, adain, warm)           # ValueError before any GPU call
         if rows is not None:
             if isinstance(style, PreparedStyle):
@@ -293,7 +323,7 @@ class WCT(object):
                 h.close()
 
     def predict_frames(self, frames, style, alpha=1, swap5=False, ss_alpha=1, adain=False, batch=16, warm=None,
-                       content_colors=False, resize=None, wrap=False):
+                       content_colors=False, resize=None, wrap=False, strengths=None):
         '''Stylize same-sized frames [F][H][W][3] with ONE style image (the loop of stylize_video.py:112-121,
            which calls predict() once per frame and so re-runs the style encoder, the style statistics and the
            style eigendecompositions every frame).  Here the style side runs once per batch of `batch` frames;
@@ -305,8 +335,36 @@ class WCT(object):
            (Context.resize_batch_dev: Pillow's bilinear bytes) -- predict_frames on utils._imresize(frame, (h, w)), bit for bit.
            wrap: the network on a torus (Context.stylize_prepared_wrap_batch) -- every conv sees the frame continued periodically,
            so a tileable frame stays tileable.  Prepared styles only; H and W multiples of the deepest level's stride; no swap5,
-           warm, content_colors or resize (ValueError before any GPU call).  Frames keep their size.'''
+           warm, content_colors or resize (ValueError before any GPU call).  Frames keep their size.
+           strengths: a strength map per frame, uint8 [F][H][W] (or one [H][W] map for all frames), at the resized size with
+           resize -- frame f equals predict(frames[f], style, strength=strengths[f]) bit for bit (cold).  A style image is prepared
+           once here; warm then needs a PreparedStyle as always.  No swap5 or wrap with it: ValueError.'''
         frames = np.asarray(frames)
+        if strengths is not None:
+            from ._lib import strength_maps_frames
+            if frames.ndim != 4 or frames.shape[3] != 3:
+                raise ValueError('expected [F][H][W][3] frames, got shape %s' % (frames.shape,))
+            if resize is not None:
+                resize = check_resize(resize)                                     # ValueError before any GPU call
+            shape = resize or frames.shape[1:3]
+            strengths = strength_maps_frames(strengths, len(frames), shape)       # ValueError before any GPU call
+            self._strength_refusals(shape, swap5, None, wrap)
+            if warm is not None:
+                self._check_warm(warm, style, swap5, adain)
+            if isinstance(style, PreparedStyle):
+                check_prepared(self.sess, [style], self.relu_targets)
+            if frames.dtype != np.uint8:
+                frames = np.uint8(np.clip(frames, 0, 255))
+            own = None if isinstance(style, PreparedStyle) else self.prepare_style(np.asarray(style), adain=adain)
+            try:
+                batch = max(1, min(32, int(batch)))
+                return np.concatenate([self.sess.stylize_prepared_strength_batch(
+                    frames[i:i + batch], own or style, strengths[i:i + batch], self.relu_targets, alpha=alpha, adain=adain,
+                    wct_mode=self.wct_mode, warm=warm, content_colors=content_colors, resize=resize)
+                    for i in range(0, len(frames), batch)], axis=0)
+            finally:
+                if own is not None:
+                    own.close()
         if wrap:
             if not isinstance(style, PreparedStyle):
                 raise ValueError('wrap takes a PreparedStyle (prepare_style), not a style image')
