@@ -54,10 +54,16 @@ enum wct_flags {
   WCT_FLAG_IMAGES_F32 = 16, /* content / style point at float32 images already in [0,1] (WCT.preprocess applied by the
                               caller: a FLOAT input of predict() is divided by 255 without rounding, wct.py:60-64)
                               instead of uint8 ones; the output stays uint8 */
-  WCT_FLAG_CONTENT_COLORS = 32 /* luminance-only colour preservation: every frame keeps its stylized luminance and takes the
+  WCT_FLAG_CONTENT_COLORS = 32, /* luminance-only colour preservation: every frame keeps its stylized luminance and takes the
                               colours of its content (see wct_content_colors).  Honoured by every wct_stylize* call, with
                               any of the flags above; the frame equals wct_content_colors(the unflagged frame, the content)
                               bit for bit.  Without the flag nothing changes */
+  WCT_FLAG_GUIDED = 64     /* guided smoothing, the photo mode: every frame is filtered with its content as guide (see
+                              wct_guided_filter), radius and eps_q from wct_set_guided.  Honoured by every wct_stylize* call that
+                              ends in the whole-image chain, with any of the flags above; the frame equals wct_guided_filter(the
+                              unflagged frame, the content) bit for bit, and with WCT_FLAG_CONTENT_COLORS as well
+                              wct_content_colors(that, the content): the colour op runs last.  The banded, texture and wrap
+                              calls refuse it (WCT_STATUS_ARG, a message that names it) */
 };
 
 /* ---- lifecycle: replaces WCT.__init__'s tf.Session setup (wct.py:29-44) ---- */
@@ -215,6 +221,31 @@ int wct_content_colors(wct_ctx* ctx, const uint8_t* stylized, int Ho, int Wo, co
                        uint8_t* out);
 int wct_content_colors_batch_dev(wct_ctx* ctx, const uint8_t* stylized_dev, int Ho, int Wo, const uint8_t* content_dev, int Hc,
                                  int Wc, int B, uint8_t* out_dev);
+/* Guided smoothing (He, Sun, Tang, "Guided Image Filtering", ECCV 2010; the smoothing step of the fast variant of Li et al. 2018,
+ * "A Closed-form Solution to Photorealistic Image Stylization"): the stylized frame filtered with the grey content as guide --
+ * the frame keeps an edge wherever the content has one and is averaged wherever the content is flat.  Integers only (the rule
+ * and its bounds: csrc/guided_rule.h) -- stylized s [Ho][Wo][3], content c [Hc][Wc][3], Ho >= Hc, Wo >= Wc, radius r in 1 .. 64,
+ * eps_q in 1 .. 65025 (grey levels squared: round(eps * 65025) of the usual [0,1]^2 eps, at least 1):
+ *   rdiv(a, b) = floor((2a + b) / (2b))                                  (nearest, halves up, a true floor for negative a)
+ *   I(y, x)    = (77 p.R + 150 p.G + 29 p.B + 128) >> 8, p = c[min(y, Hc - 1)][min(x, Wc - 1)]    (the clamp of wct_content_colors)
+ *   window     = rows max(0, y - r) .. min(Ho - 1, y + r) x the same in x, n pixels (the border-normalised box of He et al.)
+ *   pass 1, per channel: SI, SII, Sp, SIp = the window sums of I, I^2, s.ch, I s.ch
+ *              a_q = rdiv((n SIp - SI Sp) 2^12, n SII - SI^2 + eps_q n^2),  b_q = rdiv(Sp 2^12 - a_q SI, n)
+ *   pass 2:    out.ch = clamp(rdiv(I sum a_q + sum b_q, n 2^12), 0, 255), the sums over the same window
+ * A constant frame comes back exactly; the result stays within 0.54 of the float64 filter with the same guide and box.
+ * wct_guided_filter: host pointers, blocking.  wct_guided_filter_batch_dev: device pointers, B = 1 .. 32 frames [B][Ho][Wo][3]
+ *   and contents [B][Hc][Wc][3], two launches, asynchronous on the ctx stream; out_dev may be stylized_dev (in place).  The
+ *   24 B per pixel between the passes live in a workspace of the ctx.
+ * wct_set_guided: the radius and eps_q of WCT_FLAG_GUIDED (initially 8 and 650).  With WCT_FLAG_IMAGES_F32 the float content is
+ *   taken under the output rule uint8(clip(x, 0, 1) * 255.f), as the colour op takes it.
+ * Ho < Hc, Wo < Wc, a null pointer, B outside 1 .. 32, a radius or eps_q out of range, or B * Ho * Wo * 3 >= 2^31 is
+ * WCT_STATUS_ARG and leaves the ctx (and the flag's settings) as they were.
+ * Not served: a colour (3-channel) guide, the subsampled "fast guided filter", the banded / texture / wrap calls, radii above 64. */
+int wct_guided_filter(wct_ctx* ctx, const uint8_t* stylized, int Ho, int Wo, const uint8_t* content, int Hc, int Wc, int radius,
+                      int eps_q, uint8_t* out);
+int wct_guided_filter_batch_dev(wct_ctx* ctx, const uint8_t* stylized_dev, int Ho, int Wo, const uint8_t* content_dev, int Hc, int Wc,
+                                int B, int radius, int eps_q, uint8_t* out_dev);
+int wct_set_guided(wct_ctx* ctx, int radius, int eps_q);
 /* On-device resize (the reference's resize_to, utils.py:55-67, behind --content-size, stylize_video.py:29; webcam.py:163,189
  * resizes every frame by --scale): img [H][W][3] uint8 -> [h][w][3] uint8, the bytes of Pillow's Image.resize((w, h), Image.BILINEAR).
  * Pillow's 8-bit resampler is an integer rule.  Per axis (`in` the input length, `out` the output length; everything up to the

@@ -50,6 +50,9 @@ SIGNATURES = [
     ('wct_coral_apply', C.c_int, [_P, _U8, C.c_int, C.c_int, _D, _D, _D, _D, _D, _U8, _D]),
     ('wct_content_colors', C.c_int, [_P, _U8, C.c_int, C.c_int, _U8, C.c_int, C.c_int, _U8]),
     ('wct_content_colors_batch_dev', C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P]),
+    ('wct_guided_filter', C.c_int, [_P, _U8, C.c_int, C.c_int, _U8, C.c_int, C.c_int, C.c_int, C.c_int, _U8]),
+    ('wct_guided_filter_batch_dev', C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+    ('wct_set_guided', C.c_int, [_P, C.c_int, C.c_int]),
     ('wct_resize', C.c_int, [_P, _U8, C.c_int, C.c_int, C.c_int, C.c_int, _U8]),
     ('wct_resize_batch_dev', C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     ('wct_output_size', C.c_int, [C.c_int, C.c_int, _I, C.c_int, _I, _I]),
@@ -127,6 +130,15 @@ SIGNATURES = [
 
 WCT_NP, WCT_TF = 0, 1
 FLAG_ADAIN, FLAG_MODE_NP, FLAG_SWAP5, FLAG_STYLE_SHARED, FLAG_IMAGES_F32, FLAG_CONTENT_COLORS = 1, 2, 4, 8, 16, 32
+FLAG_GUIDED = 64
+GUIDED_MAX_RADIUS, GUIDED_MAX_EPS = 64, 65025      # csrc/guided_rule.h
+
+
+def guided_eps_q(eps):
+    """eps of the usual [0,1]^2 convention of a guided filter in grey levels squared: round(eps * 255^2), at least 1"""
+    return max(1, int(round(float(eps) * 65025)))
+
+
 PROF_CLASSES = ['conv3x3', 'conv_first', 'conv_last', 'pool', 'wct_cov', 'jacobi', 'wct_apply', 'other', 'conv12', 'conv_wino', 'conv_tail']
 
 _lib = None

@@ -25,11 +25,12 @@ def _levels(relu_targets):
     return out
 
 
-def _flags(adain=False, wct_mode='tf', swap5=False, images_f32=False, shared_style=False, content_colors=False):
+def _flags(adain=False, wct_mode='tf', swap5=False, images_f32=False, shared_style=False, content_colors=False, guided=False):
     """The flag word of a stylize call (WCT_FLAG_*, include/wct_hip.h)."""
     return (_lib.FLAG_ADAIN if adain else 0) | (_lib.FLAG_MODE_NP if wct_mode == 'np' else 0) | \
         (_lib.FLAG_SWAP5 if swap5 else 0) | (_lib.FLAG_IMAGES_F32 if images_f32 else 0) | \
-        (_lib.FLAG_STYLE_SHARED if shared_style else 0) | (_lib.FLAG_CONTENT_COLORS if content_colors else 0)
+        (_lib.FLAG_STYLE_SHARED if shared_style else 0) | (_lib.FLAG_CONTENT_COLORS if content_colors else 0) | \
+        (_lib.FLAG_GUIDED if guided else 0)
 
 
 def _feature_args(content, styles, validate):
@@ -55,6 +56,31 @@ def _color_images(stylized, content, ndim):
     if s.shape[-3] < c.shape[-3] or s.shape[-2] < c.shape[-2]:
         raise ValueError('the stylized frame %dx%d is smaller than its content %dx%d' % (s.shape[-3], s.shape[-2], c.shape[-3], c.shape[-2]))
     return u8(s), u8(c)
+
+
+def check_guided(guided):
+    """The refusals of guided=(radius, eps_q), before any library call: two integers, the radius 1 .. 64 and eps_q 1 .. 65025 (grey
+    levels squared; _lib.guided_eps_q converts an eps of the [0,1]^2 convention).  -> (radius, eps_q)"""
+    try:
+        r, e = guided
+        if int(r) != r or int(e) != e:
+            raise TypeError
+        r, e = int(r), int(e)
+    except (TypeError, ValueError):
+        raise ValueError('guided is (radius, eps_q), two integers, got %r' % (guided,))
+    if not 1 <= r <= _lib.GUIDED_MAX_RADIUS:
+        raise ValueError('the guided radius must be 1 .. %d, got %d' % (_lib.GUIDED_MAX_RADIUS, r))
+    if not 1 <= e <= _lib.GUIDED_MAX_EPS:
+        raise ValueError('the guided eps_q must be 1 .. %d (grey levels squared), got %d' % (_lib.GUIDED_MAX_EPS, e))
+    return r, e
+
+
+def _guided_images(stylized, content, ndim):
+    """The refusals of guided_filter's images, before any library call (those of content_colors) -> both as contiguous uint8"""
+    try:
+        return _color_images(stylized, content, ndim)
+    except ValueError as e:
+        raise ValueError(str(e).replace('content_colors', 'guided_filter'))
 
 
 def check_texture(size, passes=1, batch=1, seed=0, first_sample=0):
@@ -706,6 +732,46 @@ class Context(object):
         return self._host_batch([s, c], np.empty_like(s), in_place=True, enqueue=lambda ds, dc: self.content_colors_batch_dev(
             ds, s.shape[1], s.shape[2], dc, c.shape[1], c.shape[2], s.shape[0], ds))
 
+    # ---- guided smoothing: the photo mode ---------------------------------------------------
+    def set_guided(self, radius, eps_q):
+        """The radius and eps_q that WCT_FLAG_GUIDED filters with (wct_set_guided)"""
+        r, e = check_guided((radius, eps_q))
+        check(self.lib.wct_set_guided(self.h, r, e))
+
+    def _set_guided(self, guided):
+        """guided=(radius, eps_q) of a stylize call: None -> False; else the settings go to the library -> True (the flag)"""
+        if guided is None:
+            return False
+        self.set_guided(*check_guided(guided))
+        return True
+
+    def guided_filter(self, stylized_u8, content_u8, radius, eps_q):
+        """Guided smoothing (wct_guided_filter; He, Sun, Tang, "Guided Image Filtering"): stylized [Ho][Wo][3] and content
+        [Hc][Wc][3] uint8, Ho >= Hc and Wo >= Wc -> uint8 [Ho][Wo][3], `stylized` filtered with the grey of `content` as guide
+        (pixel (y, x) takes content pixel (min(y, Hc - 1), min(x, Wc - 1))) over a (2 radius + 1)^2 box; eps_q in grey levels
+        squared.  The integer rule of include/wct_hip.h."""
+        s, c = _guided_images(stylized_u8, content_u8, 3)
+        r, e = check_guided((radius, eps_q))
+        out = np.empty_like(s)
+        check(self.lib.wct_guided_filter(self.h, s.ctypes.data_as(_lib._U8), s.shape[0], s.shape[1], c.ctypes.data_as(_lib._U8),
+                                         c.shape[0], c.shape[1], r, e, out.ctypes.data_as(_lib._U8)))
+        return out
+
+    def guided_filter_batch_dev(self, stylized_dev, ho, wo, content_dev, hc, wc, batch, radius, eps_q, out_dev):
+        """guided_filter for B frames resident in HBM (wct_guided_filter_batch_dev): asynchronous; out_dev may be stylized_dev."""
+        r, e = check_guided((radius, eps_q))
+        check(self.lib.wct_guided_filter_batch_dev(self.h, stylized_dev, int(ho), int(wo), content_dev, int(hc), int(wc), int(batch),
+                                                   r, e, out_dev))
+
+    def guided_filter_batch(self, stylized_u8, contents_u8, radius, eps_q):
+        """Host arrays in, host array out: stylized [B][Ho][Wo][3] and contents [B][Hc][Wc][3] uint8 (B <= 32) -> [B][Ho][Wo][3]."""
+        s, c = _guided_images(stylized_u8, contents_u8, 4)
+        r, e = check_guided((radius, eps_q))
+        if s.shape[0] != c.shape[0] or not 1 <= s.shape[0] <= _lib.BATCH_MAX:
+            raise ValueError('a batch takes 1 .. %d frames and as many contents, got %d and %d' % (_lib.BATCH_MAX, s.shape[0], c.shape[0]))
+        return self._host_batch([s, c], np.empty_like(s), in_place=True, enqueue=lambda ds, dc: self.guided_filter_batch_dev(
+            ds, s.shape[1], s.shape[2], dc, c.shape[1], c.shape[2], s.shape[0], r, e, ds))
+
     # ---- on-device resize: Pillow's bilinear bytes ------------------------------------------
     def resize(self, img_u8, size):
         """img [H][W][3] uint8 -> uint8 [h][w][3] for size = (h, w) (wct_resize; the integer rule of include/wct_hip.h): the bytes
@@ -824,23 +890,24 @@ class Context(object):
         check(self.lib.wct_output_size(hc, wc, arr, len(lv), C.byref(ho), C.byref(wo)))
         return ho.value, wo.value
 
-    def stylize(self, content, style, relu_targets, alpha=1.0, adain=False, wct_mode='tf', swap5=False, content_colors=False):
+    def stylize(self, content, style, relu_targets, alpha=1.0, adain=False, wct_mode='tf', swap5=False, content_colors=False, guided=None):
         """One predict(): HxWx3 images in [0,255] in, uint8 out.  uint8 inputs go to the library as they are (the /255
         runs on the device); anything else is preprocessed exactly as the reference does -- `image / 255.` in float64
         (wct.py:60-64), cast to the float32 the graph's placeholders hold (model.py:43-44) -- and handed over as float32
         images in [0,1] (WCT_FLAG_IMAGES_F32): a float image is NOT rounded to integer levels.
         content_colors (here and in every stylize* method): the frame keeps its luminance and takes the colours of its content
         (WCT_FLAG_CONTENT_COLORS) -- content_colors(the plain frame, content) bit for bit, fused into the last launch."""
-        c, (s,), _, arr, out, flags = self._stylize_args(content, [style], None, relu_targets, adain, wct_mode, swap5, content_colors)
+        c, (s,), _, arr, out, flags = self._stylize_args(content, [style], None, relu_targets, adain, wct_mode, swap5, content_colors, guided)
         check(self.lib.wct_stylize(self.h, c.ctypes.data_as(_lib._U8), c.shape[0], c.shape[1],
                                    s.ctypes.data_as(_lib._U8), s.shape[0], s.shape[1], arr, len(arr),
                                    float(alpha), flags, out.ctypes.data_as(_lib._U8)))
         return out
 
-    def _stylize_args(self, content, styles, validate, relu_targets, adain, wct_mode, swap5, content_colors=False):
+    def _stylize_args(self, content, styles, validate, relu_targets, adain, wct_mode, swap5, content_colors=False, guided=None):
         """The common arguments of the stylize calls: the caller's own validate(content, K) first (None: none; its result is
         returned), then the images -- all uint8 go as they are, otherwise every image is `/ 255.` in float64 and handed over as
         float32 in [0,1] -- the levels as a C int array, the output image and the flag word."""
+        guided = None if guided is None else check_guided(guided)              # ValueError before any library call
         content = np.asarray(content)
         styles = [np.asarray(s) for s in styles]
         v = validate(content, len(styles)) if validate else None
@@ -852,7 +919,7 @@ class Context(object):
             c, ss = u8(content), [u8(s) for s in styles]
         lv = _levels(relu_targets)
         ho, wo = self.output_size(c.shape[0], c.shape[1], lv)
-        flags = _flags(adain, wct_mode, swap5, images_f32=as_f32, content_colors=content_colors)
+        flags = _flags(adain, wct_mode, swap5, images_f32=as_f32, content_colors=content_colors, guided=self._set_guided(guided))
         return c, ss, v, (C.c_int * len(lv))(*lv), np.empty((ho, wo, 3), np.uint8), flags
 
     # ---- prepared styles -----------------------------------------------------
@@ -872,14 +939,15 @@ class Context(object):
                                          flags, C.byref(h)))
         return PreparedStyle(self, h, img, lv)
 
-    def _prepared_args(self, content, relu_targets, adain, wct_mode, content_colors=False):
+    def _prepared_args(self, content, relu_targets, adain, wct_mode, content_colors=False, guided=None):
         """content, levels, output and flags of a call with prepared styles (the content as in stylize)"""
+        guided = None if guided is None else check_guided(guided)              # ValueError before any library call
         content = np.asarray(content)
         as_f32 = content.dtype != np.uint8
         c = np.ascontiguousarray(np.asarray(content / 255.), np.float32) if as_f32 else u8(content)
         lv = _levels(relu_targets)
         ho, wo = self.output_size(c.shape[0], c.shape[1], lv)
-        flags = _flags(adain, wct_mode, images_f32=as_f32, content_colors=content_colors)
+        flags = _flags(adain, wct_mode, images_f32=as_f32, content_colors=content_colors, guided=self._set_guided(guided))
         return c, (C.c_int * len(lv))(*lv), np.empty((ho, wo, 3), np.uint8), flags
 
     def warm_state(self, relu_targets):
@@ -889,13 +957,13 @@ class Context(object):
         check(self.lib.wct_warm_create(self.h, (C.c_int * len(lv))(*lv), len(lv), C.byref(h)))
         return WarmState(self, h, lv)
 
-    def stylize_prepared(self, content, style, relu_targets, alpha=1.0, adain=False, wct_mode='tf', warm=None, content_colors=False):
+    def stylize_prepared(self, content, style, relu_targets, alpha=1.0, adain=False, wct_mode='tf', warm=None, content_colors=False, guided=None):
         """stylize() with a PreparedStyle in the place of the style image: the same frame, bit for bit.  warm (a WarmState):
         the content eigensolves start from the state's bases, which then take this frame's."""
         check_prepared(self, [style], relu_targets)
         if warm is not None:
             check_warm(self, warm, relu_targets, adain)
-        c, arr, out, flags = self._prepared_args(content, relu_targets, adain, wct_mode, content_colors)
+        c, arr, out, flags = self._prepared_args(content, relu_targets, adain, wct_mode, content_colors, guided)
         if warm is not None:
             check(self.lib.wct_stylize_prepared_warm(self.h, c.ctypes.data_as(_lib._U8), c.shape[0], c.shape[1], style.h, arr,
                                                      len(arr), float(alpha), flags, warm.h, out.ctypes.data_as(_lib._U8)))
@@ -926,22 +994,22 @@ class Context(object):
                                                    float(alpha), flags, int(band_rows), int(stat_rows), out.ctypes.data_as(_lib._U8)))
         return out
 
-    def stylize_prepared_mix(self, content, styles, weights, relu_targets, alpha=1.0, adain=False, wct_mode='tf', content_colors=False):
+    def stylize_prepared_mix(self, content, styles, weights, relu_targets, alpha=1.0, adain=False, wct_mode='tf', content_colors=False, guided=None):
         """stylize_mix() with K PreparedStyle objects in the place of the K images: the same frame, bit for bit."""
         w = _lib.mix_weights(weights, len(styles))
         check_prepared(self, styles, relu_targets)
-        c, arr, out, flags = self._prepared_args(content, relu_targets, adain, wct_mode, content_colors)
+        c, arr, out, flags = self._prepared_args(content, relu_targets, adain, wct_mode, content_colors, guided)
         hs = (C.c_void_p * len(styles))(*[s.h.value for s in styles])
         check(self.lib.wct_stylize_prepared_mix(self.h, c.ctypes.data_as(_lib._U8), c.shape[0], c.shape[1], hs, len(styles), fptr(w),
                                                 arr, len(arr), float(alpha), flags, out.ctypes.data_as(_lib._U8)))
         return out
 
     def stylize_prepared_batch_dev(self, content_dev, hc, wc, batch, style, relu_targets, alpha, out_dev, adain=False, wct_mode='tf',
-                                   warm=None, content_colors=False):
+                                   warm=None, content_colors=False, guided=None):
         """stylize_batch_dev(shared_style=True) with a PreparedStyle: B contents resident in HBM, asynchronous.  warm (a
         WarmState): all B frames start from the state's bases, which then take those of frame B - 1."""
         lv = check_prepared(self, [style], relu_targets)
-        flags = _flags(adain, wct_mode, content_colors=content_colors)
+        flags = _flags(adain, wct_mode, content_colors=content_colors, guided=self._set_guided(guided))
         if warm is not None:
             check_warm(self, warm, relu_targets, adain)
             check(self.lib.wct_stylize_prepared_batch_dev_warm(self.h, content_dev, hc, wc, batch, style.h, (C.c_int * len(lv))(*lv),
@@ -951,7 +1019,7 @@ class Context(object):
                                                       float(alpha), flags, out_dev))
 
     def stylize_prepared_batch(self, contents_u8, style, relu_targets, alpha=1.0, adain=False, wct_mode='tf', warm=None,
-                               content_colors=False, resize=None):
+                               content_colors=False, guided=None, resize=None):
         """stylize_batch() with a PreparedStyle: contents [B][H][W][3] uint8 (B <= 32) -> [B][Ho][Wo][3] uint8.  warm: as in
         stylize_prepared_batch_dev.  resize (h, w): the contents are raw frames, resized on the device (resize_batch_dev) into
         the content buffer the call -- and content_colors -- reads: the frames of the call on utils._imresize(frame, (h, w))."""
@@ -968,32 +1036,32 @@ class Context(object):
         ho, wo = self.output_size(hc, wc, relu_targets)
         out = np.empty((B, ho, wo, 3), np.uint8)
         enqueue = lambda dc, do: self.stylize_prepared_batch_dev(
-            dc, hc, wc, B, style, relu_targets, alpha, do, adain=adain, wct_mode=wct_mode, warm=warm, content_colors=content_colors)
+            dc, hc, wc, B, style, relu_targets, alpha, do, adain=adain, wct_mode=wct_mode, warm=warm, content_colors=content_colors, guided=guided)
         if resize is not None:
             return self._host_batch_resized(c, (hc, wc), [], out, enqueue)
         return self._host_batch([c], out, enqueue)
 
-    def stylize_prepared_strength(self, content, style, smap, relu_targets, alpha=1.0, adain=False, wct_mode='tf', content_colors=False):
+    def stylize_prepared_strength(self, content, style, smap, relu_targets, alpha=1.0, adain=False, wct_mode='tf', content_colors=False, guided=None):
         """stylize_prepared() with a strength map (wct_stylize_prepared_strength): smap [H][W] uint8 of the content's size, 255 the
         call's alpha, 0 "keep the content features"; every level samples it at its own stride.  An all-255 map gives
         stylize_prepared's frame at alpha = 1 bit for bit."""
         c0 = np.asarray(content)
         m = _lib.strength_map(smap, c0.shape[:2])
         check_prepared(self, [style], relu_targets)
-        c, arr, out, flags = self._prepared_args(c0, relu_targets, adain, wct_mode, content_colors)
+        c, arr, out, flags = self._prepared_args(c0, relu_targets, adain, wct_mode, content_colors, guided)
         check(self.lib.wct_stylize_prepared_strength(self.h, c.ctypes.data_as(_lib._U8), c.shape[0], c.shape[1],
                                                      m.ctypes.data_as(_lib._U8), style.h, arr, len(arr), float(alpha), flags,
                                                      out.ctypes.data_as(_lib._U8)))
         return out
 
     def stylize_prepared_strength_batch_dev(self, content_dev, hc, wc, batch, smaps_dev, style, relu_targets, alpha, out_dev,
-                                            adain=False, wct_mode='tf', warm=None, content_colors=False):
+                                            adain=False, wct_mode='tf', warm=None, content_colors=False, guided=None):
         """stylize_prepared_batch_dev with one strength map per frame, smaps_dev [B][hc][wc] uint8 resident in HBM.  Asynchronous:
         nothing of the maps is read on the host.  Frame f is stylize_prepared_strength(frame f, map f)."""
         if not 1 <= int(batch) <= _lib.BATCH_MAX:
             raise ValueError('a batch takes 1 .. %d frames, got %d' % (_lib.BATCH_MAX, batch))
         lv = check_prepared(self, [style], relu_targets)
-        flags = _flags(adain, wct_mode, content_colors=content_colors)
+        flags = _flags(adain, wct_mode, content_colors=content_colors, guided=self._set_guided(guided))
         arr = (C.c_int * len(lv))(*lv)
         if warm is not None:
             check_warm(self, warm, relu_targets, adain)
@@ -1004,7 +1072,7 @@ class Context(object):
                                                                float(alpha), flags, out_dev))
 
     def stylize_prepared_strength_batch(self, contents_u8, style, smaps, relu_targets, alpha=1.0, adain=False, wct_mode='tf', warm=None,
-                                        content_colors=False, resize=None):
+                                        content_colors=False, guided=None, resize=None):
         """Host arrays in, host array out: contents [B][H][W][3] uint8 (B <= 32), smaps [B][H][W] uint8 (or one [H][W] map for
         all) -> [B][Ho][Wo][3] uint8.  warm and resize (h, w): as in stylize_prepared_batch; the maps are given at the resized
         size."""
@@ -1025,7 +1093,7 @@ class Context(object):
         ho, wo = self.output_size(hc, wc, relu_targets)
         out = np.empty((B, ho, wo, 3), np.uint8)
         enqueue = lambda dc, dm, do: self.stylize_prepared_strength_batch_dev(
-            dc, hc, wc, B, dm, style, relu_targets, alpha, do, adain=adain, wct_mode=wct_mode, warm=warm, content_colors=content_colors)
+            dc, hc, wc, B, dm, style, relu_targets, alpha, do, adain=adain, wct_mode=wct_mode, warm=warm, content_colors=content_colors, guided=guided)
         if resize is not None:
             return self._host_batch_resized(c, (hc, wc), [m], out, enqueue)
         return self._host_batch([c, m], out, enqueue)
@@ -1059,12 +1127,12 @@ class Context(object):
                                                  float(alpha), flags, out.ctypes.data_as(_lib._U8)))
         return out
 
-    def stylize_prepared_masked(self, content, styles, mask, relu_targets, alpha=1.0, adain=False, wct_mode='tf', content_colors=False):
+    def stylize_prepared_masked(self, content, styles, mask, relu_targets, alpha=1.0, adain=False, wct_mode='tf', content_colors=False, guided=None):
         """stylize_masked() with K PreparedStyle objects in the place of the K images: the same frame, bit for bit."""
         c0 = np.asarray(content)
         m = _lib.mask_labels(mask, len(styles), c0.shape[:2])
         check_prepared(self, styles, relu_targets)
-        c, arr, out, flags = self._prepared_args(c0, relu_targets, adain, wct_mode, content_colors)
+        c, arr, out, flags = self._prepared_args(c0, relu_targets, adain, wct_mode, content_colors, guided)
         hs = (C.c_void_p * len(styles))(*[s.h.value for s in styles])
         check(self.lib.wct_stylize_prepared_masked(self.h, c.ctypes.data_as(_lib._U8), c.shape[0], c.shape[1],
                                                    m.ctypes.data_as(_lib._U8), hs, len(styles), arr, len(arr), float(alpha), flags,
@@ -1072,7 +1140,7 @@ class Context(object):
         return out
 
     def stylize_prepared_masked_batch_dev(self, content_dev, hc, wc, batch, masks, styles, relu_targets, alpha, out_dev,
-                                          adain=False, wct_mode='tf', content_colors=False):
+                                          adain=False, wct_mode='tf', content_colors=False, guided=None):
         """Spatial control of B uint8 frames resident in HBM, one label map per frame: `masks` [B][hc][wc] (or one [hc][wc] map
         for all) is a HOST array, the K PreparedStyle objects are shared by all frames.  Asynchronous; frame f is
         stylize_prepared_masked(frame f, masks[f])."""
@@ -1080,7 +1148,7 @@ class Context(object):
             raise ValueError('a batch takes 1 .. %d frames, got %d' % (_lib.BATCH_MAX, batch))
         m = _lib.mask_labels_frames(masks, len(styles), int(batch), (hc, wc))
         lv = check_prepared(self, styles, relu_targets)
-        flags = _flags(adain, wct_mode, content_colors=content_colors)
+        flags = _flags(adain, wct_mode, content_colors=content_colors, guided=self._set_guided(guided))
         hs = (C.c_void_p * len(styles))(*[s.h.value for s in styles])
         # the upload is enqueued on the stream: the maps stay alive until sync() (include/wct_hip.h)
         self._masks_in_flight = getattr(self, '_masks_in_flight', []) + [m]
@@ -1089,7 +1157,7 @@ class Context(object):
                                                              out_dev))
 
     def stylize_prepared_masked_batch(self, contents_u8, styles, masks, relu_targets, alpha=1.0, adain=False, wct_mode='tf',
-                                      content_colors=False, resize=None):
+                                      content_colors=False, guided=None, resize=None):
         """Host arrays in, host array out: contents [B][H][W][3] uint8 (B <= 32), masks [B][H][W] (or one [H][W] map for all),
         K PreparedStyle objects -> [B][Ho][Wo][3] uint8.  resize (h, w): as in stylize_prepared_batch; the label maps are given
         at the resized size."""
@@ -1108,30 +1176,30 @@ class Context(object):
         ho, wo = self.output_size(hc, wc, relu_targets)
         out = np.empty((B, ho, wo, 3), np.uint8)
         enqueue = lambda dc, do: self.stylize_prepared_masked_batch_dev(
-            dc, hc, wc, B, m, styles, relu_targets, alpha, do, adain=adain, wct_mode=wct_mode, content_colors=content_colors)
+            dc, hc, wc, B, m, styles, relu_targets, alpha, do, adain=adain, wct_mode=wct_mode, content_colors=content_colors, guided=guided)
         if resize is not None:
             return self._host_batch_resized(c, (hc, wc), [], out, enqueue)
         return self._host_batch([c], out, enqueue)
 
     def stylize_mix(self, content, styles, weights, relu_targets, alpha=1.0, adain=False, wct_mode='tf', swap5=False,
-                    content_colors=False):
+                    content_colors=False, guided=None):
         """One predict() with a style mix at every level (wct_stylize_mix): `styles` is a list of K HxWx3 images (sizes may
         differ), `weights` [K] (None: equal).  Inputs as in stylize: all uint8 go as they are, otherwise every image is
         `/ 255.` in float64 and handed over as float32 in [0,1]."""
         c, ss, w, arr, out, flags = self._stylize_args(content, styles, lambda c, k: _lib.mix_weights(weights, k), relu_targets,
-                                                       adain, wct_mode, swap5, content_colors)
+                                                       adain, wct_mode, swap5, content_colors, guided)
         ptrs, hs, ws = _image_arrays(ss)
         check(self.lib.wct_stylize_mix(self.h, c.ctypes.data_as(_lib._U8), c.shape[0], c.shape[1], ptrs, hs, ws, len(ss), fptr(w),
                                        arr, len(arr), float(alpha), flags, out.ctypes.data_as(_lib._U8)))
         return out
 
     def stylize_masked(self, content, styles, mask, relu_targets, alpha=1.0, adain=False, wct_mode='tf', swap5=False,
-                       content_colors=False):
+                       content_colors=False, guided=None):
         """One predict() with spatial control at every level (wct_stylize_masked): `mask` [H][W] labels 0 .. K-1 of the content
         pixels, `styles` a list of K HxWx3 images (sizes may differ).  Inputs as in stylize: all uint8 go as they are,
         otherwise every image is `/ 255.` in float64 and handed over as float32 in [0,1]."""
         c, ss, m, arr, out, flags = self._stylize_args(content, styles, lambda c, k: _lib.mask_labels(mask, k, c.shape[:2]),
-                                                       relu_targets, adain, wct_mode, swap5, content_colors)
+                                                       relu_targets, adain, wct_mode, swap5, content_colors, guided)
         ptrs, hs, ws = _image_arrays(ss)
         check(self.lib.wct_stylize_masked(self.h, c.ctypes.data_as(_lib._U8), c.shape[0], c.shape[1], m.ctypes.data_as(_lib._U8),
                                           ptrs, hs, ws, len(ss), arr, len(arr), float(alpha), flags, out.ctypes.data_as(_lib._U8)))
@@ -1195,18 +1263,18 @@ class Context(object):
         return out
 
     def stylize_batch_dev(self, content_dev, hc, wc, style_dev, hs, ws, batch, relu_targets, alpha, out_dev,
-                          adain=False, wct_mode='tf', swap5=False, shared_style=False, content_colors=False):
+                          adain=False, wct_mode='tf', swap5=False, shared_style=False, content_colors=False, guided=None):
         """B pairs resident in HBM.  shared_style: style_dev holds ONE image used for every pair (fixed-style
         video): its encoder pass, statistics and eigensystems run once per call; the frames are bit-identical
         to the ones a replicated style produces."""
         lv = _levels(relu_targets)
         arr = (C.c_int * len(lv))(*lv)
-        flags = _flags(adain, wct_mode, swap5, shared_style=shared_style, content_colors=content_colors)
+        flags = _flags(adain, wct_mode, swap5, shared_style=shared_style, content_colors=content_colors, guided=self._set_guided(guided))
         check(self.lib.wct_stylize_batch_dev(self.h, content_dev, hc, wc, style_dev, hs, ws, batch, arr, len(lv),
                                              float(alpha), flags, out_dev))
 
     def stylize_batch(self, contents_u8, style_u8, relu_targets, alpha=1.0, adain=False, wct_mode='tf', swap5=False,
-                      content_colors=False, resize=None):
+                      content_colors=False, guided=None, resize=None):
         """Host arrays in, host array out: contents [B][H][W][3] uint8 (B <= 32); style either one image
         [Hs][Ws][3] shared by all frames or [B][Hs][Ws][3].  Returns [B][Ho][Wo][3] uint8.  resize (h, w): as in
         stylize_prepared_batch (the contents only; the style goes as it is)."""
@@ -1225,7 +1293,7 @@ class Context(object):
         out = np.empty((B, ho, wo, 3), np.uint8)
         enqueue = lambda dc, ds, do: self.stylize_batch_dev(
             dc, hc, wc, ds, hs, ws, B, relu_targets, alpha, do, adain=adain, wct_mode=wct_mode, swap5=swap5, shared_style=shared,
-            content_colors=content_colors)
+            content_colors=content_colors, guided=guided)
         if resize is not None:
             return self._host_batch_resized(c, (hc, wc), [s], out, enqueue)
         return self._host_batch([c, s], out, enqueue)

@@ -67,6 +67,8 @@ static bool fuse_stats() {
 // channels) of the g.h x g.w contents in c->feat_c -> c->wct_out (fp16), st the content's unit sums.  WCT_FLAG_SWAP5 runs the
 // style-swap at relu5_1 instead.  WCT_FLAG_CONTENT_COLORS: the last launch puts the frames' luminance on the colours of
 // content_raw, the contents as the caller gave them ([B][Hc][Wc][3] on the device: uint8, or fp32 with WCT_FLAG_IMAGES_F32).
+// WCT_FLAG_GUIDED: the uint8 frames are then filtered in place with content_raw as guide (guided.hip, the context's radius and
+// eps_q), and the colour op, if flagged too, runs after that as the stand-alone uint8 kernel.
 template <typename StyleAt, typename Transform>
 static int stylize_levels(wct_ctx* c, const float* img_c, const void* content_raw, int B, const Chain& chain, unsigned flags,
                           size_t umax_clear, int clear_from, StyleAt&& style_at, Transform&& transform, uint8_t* out) {
@@ -109,8 +111,19 @@ static int stylize_levels(wct_ctx* c, const float* img_c, const void* content_ra
     cur = (float*)dst.p;
   }
   const int H = chain.Ho, W = chain.Wo, Hc = chain.lv[0].H, Wc = chain.lv[0].W;
+  const int f32 = (flags & WCT_FLAG_IMAGES_F32) ? 1 : 0;
+  if (flags & WCT_FLAG_GUIDED) {
+    // the frames by the chain's own rule, filtered in place against the content; the colour op, if asked for, runs last on them
+    {
+      ProfScope ps(c, 7, 0, (double)B * H * W * 3 * 5);
+      TRY(launch_f32_to_u8(cur, out, (size_t)B * H * W * 3, c->stream));
+    }
+    TRY(run_guided_filter(c, out, content_raw, f32, B, H, W, Hc, Wc, c->guided_radius, c->guided_eps, out));
+    if (!(flags & WCT_FLAG_CONTENT_COLORS)) return WCT_OK;
+    ProfScope ps(c, 7, 0, (double)B * H * W * 3 * 2 + (double)B * Hc * Wc * 3 * (f32 ? 4 : 1));
+    return launch_content_colors_u8_any(out, content_raw, f32, B, H, W, Hc, Wc, out, c->stream);
+  }
   if (flags & WCT_FLAG_CONTENT_COLORS) {
-    const int f32 = (flags & WCT_FLAG_IMAGES_F32) ? 1 : 0;
     ProfScope ps(c, 7, 0, (double)B * H * W * 3 * 5 + (double)B * Hc * Wc * 3 * (f32 ? 4 : 1));
     return launch_content_colors_f32(cur, content_raw, f32, B, H, W, Hc, Wc, out, c->stream);
   }
@@ -734,6 +747,7 @@ extern "C" int wct_stylize_prepared_strength_batch_dev_warm(wct_ctx* c, const ui
 // ---------------------------------------------------------------------------
 static int banded_flags_ok(unsigned flags) {
   if (flags & WCT_FLAG_ADAIN) { wct_set_error("banded: WCT_FLAG_ADAIN is not served on this path (whiten-colour transforms only)"); return WCT_ERR_ARG; }
+  if (flags & WCT_FLAG_GUIDED) { wct_set_error("banded: WCT_FLAG_GUIDED is not served on this path (filter the frame with wct_guided_filter)"); return WCT_ERR_ARG; }
   return style_flags_ok(flags);
 }
 
@@ -816,6 +830,7 @@ static int texture_flags_ok(unsigned flags) {
   TRY(style_flags_ok(flags));
   if (flags & WCT_FLAG_IMAGES_F32) { wct_set_error("texture: WCT_FLAG_IMAGES_F32 describes input images, and a texture has none"); return WCT_ERR_ARG; }
   if (flags & WCT_FLAG_CONTENT_COLORS) { wct_set_error("texture: WCT_FLAG_CONTENT_COLORS needs a content whose colours could be kept"); return WCT_ERR_ARG; }
+  if (flags & WCT_FLAG_GUIDED) { wct_set_error("texture: WCT_FLAG_GUIDED needs a content to guide the filter, and a texture has none"); return WCT_ERR_ARG; }
   return WCT_OK;
 }
 
@@ -887,6 +902,7 @@ static int wrap_flags_ok(unsigned flags) {
     return WCT_ERR_ARG;
   }
   if (flags & WCT_FLAG_SWAP5) { wct_set_error("wrap: WCT_FLAG_SWAP5 (style-swap) is not served on the periodic path"); return WCT_ERR_ARG; }
+  if (flags & WCT_FLAG_GUIDED) { wct_set_error("wrap: WCT_FLAG_GUIDED is not served on the periodic path (its window stops at the border)"); return WCT_ERR_ARG; }
   return style_flags_ok(flags);
 }
 

@@ -3,6 +3,7 @@
 //                last launch in the place of f32_to_u8_kernel (WCT_FLAG_CONTENT_COLORS); both inputs are quantised by that
 //                kernel's rule first, so the frame equals the stand-alone op on the unflagged frame, bit for bit
 //   stand-alone: uint8 stylized + uint8 content -> uint8, in place if asked (a lane reads its pixels before it writes them)
+//                (behind the guided filter of a stylize call the content is the call's: uint8, or fp32 quantised as above)
 // Output pixel (y, x) takes content pixel (min(y, Hc - 1), min(x, Wc - 1)): the clamp of the label maps (a frame can be larger
 // than its content, wct_output_size).  HBM-bound byte streams: a lane owns PX = 4 consecutive pixels of one row = 12 samples
 // = three 16-byte loads of the fp32 frame (three dwords of a uint8 one) and three dword stores, when the rows keep that
@@ -121,4 +122,10 @@ int launch_content_colors_f32(const float* frame, const void* content, int conte
 int launch_content_colors_u8(const uint8_t* stylized, const uint8_t* content, int B, int Ho, int Wo, int Hc, int Wc, uint8_t* out,
                              hipStream_t s) {
   return launch(stylized, content, out, B, Ho, Wo, Hc, Wc, s);
+}
+
+int launch_content_colors_u8_any(const uint8_t* stylized, const void* content, int content_f32, int B, int Ho, int Wo, int Hc, int Wc,
+                                 uint8_t* out, hipStream_t s) {
+  if (content_f32) return launch(stylized, (const float*)content, out, B, Ho, Wo, Hc, Wc, s);
+  return launch(stylized, (const uint8_t*)content, out, B, Ho, Wo, Hc, Wc, s);
 }

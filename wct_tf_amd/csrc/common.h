@@ -339,6 +339,21 @@ int launch_content_colors_f32(const float* frame, const void* content, int conte
                               uint8_t* out, hipStream_t s);
 int launch_content_colors_u8(const uint8_t* stylized, const uint8_t* content, int B, int Ho, int Wo, int Hc, int Wc, uint8_t* out,
                              hipStream_t s);
+// _u8_any: _u8 with the content of a stylize call (content_f32: fp32 in [0,1], quantised as above) -- the colour op behind the
+// guided filter, on frames that are uint8 already
+int launch_content_colors_u8_any(const uint8_t* stylized, const void* content, int content_f32, int B, int Ho, int Wo, int Hc, int Wc,
+                                 uint8_t* out, hipStream_t s);
+
+// ---- guided.hip -----------------------------------------------------------
+// Guided smoothing (guided_rule.h): out [B][Ho][Wo][3] = the stylized frames filtered with the grey of content [B][Hc][Wc][3]
+// (uint8, or with content_f32 fp32 in [0,1] quantised as launch_f32_to_u8 does) as guide, content pixel (min(y, Hc - 1),
+// min(x, Wc - 1)).  Two launches; workspace: guided_workspace_bytes(B, Ho, Wo) bytes on the device; out may be stylized; any base
+// address.  guided_check: B outside 1 .. 32, Ho < Hc or Wo < Wc, a radius outside 1 .. 64, eps_q outside 1 .. 65025, or
+// B * Ho * Wo * 3 >= 2^31 is WCT_ERR_ARG with a message.
+int guided_check(int B, int Ho, int Wo, int Hc, int Wc, int radius, int eps_q);
+size_t guided_workspace_bytes(int B, int Ho, int Wo);
+int launch_guided_filter(const uint8_t* stylized, const void* content, int content_f32, int B, int Ho, int Wo, int Hc, int Wc, int radius,
+                         int eps_q, void* workspace, uint8_t* out, hipStream_t s);
 
 // ---- noise.hip ------------------------------------------------------------
 // Seeded noise for texture synthesis (noise_rule.h): out [B][H][W][3] uint8 on the device, image b = sample first_sample + b of

@@ -8,6 +8,7 @@ on libwct_hip.so.  Same names, argument meaning and array conventions:
   preserve_colors_np(style_rgb, content_rgb)    utils.py:87
 and, without a counterpart in the reference,
   content_colors_np(stylized_rgb, content_rgb)  luminance-only colour preservation (Gatys et al. 2016), applied to a result
+  guided_filter_np(stylized_rgb, content_rgb, radius, eps_q)   guided smoothing of a result with its content as guide (He et al.)
   texture_noise_np(h, w, seed, sample=0, smooth=False)   the seeded noise image a texture starts from (webcam.py:191-192 --noise)
 """
 import numpy as np
@@ -121,6 +122,15 @@ def content_colors_np(stylized_rgb, content_rgb, ctx=None):
     recolours the RESULT, so the style side does not depend on the content."""
     ctx = ctx or default_context()
     return ctx.content_colors(stylized_rgb, content_rgb)
+
+
+def guided_filter_np(stylized, content, radius, eps_q, ctx=None):
+    """Guided smoothing of a result (He, Sun, Tang, "Guided Image Filtering"; the post-step of Li et al. 2018's fast photorealistic
+    variant): uint8 HxWx3 images, the stylized one at least as large as the content -> uint8, `stylized` filtered over a
+    (2 radius + 1)^2 box with the grey of `content` as guide (the integer rule of include/wct_hip.h, wct_guided_filter).  radius
+    1 .. 64; eps_q 1 .. 65025 in grey levels squared (_lib.guided_eps_q(eps) for an eps of the [0,1]^2 convention)."""
+    ctx = ctx or default_context()
+    return ctx.guided_filter(stylized, content, radius, eps_q)
 
 
 def texture_noise_np(h, w, seed, sample=0, smooth=False, ctx=None):

@@ -8,7 +8,10 @@ stylizes with a weighted mix of the styles (Li et al. 2017, sec. 4.2; the refere
 spatial control): grey value v is label v * K // 256 of K styles.
 `--content-colors` keeps every content's colours by luminance-only transfer (Gatys et al. 2016): the result takes its own
 luminance and the content's chrominance.  Unlike `--keep-colors` (CORAL on the style) it leaves the style alone, so it goes
-with prepared styles and every other option."""
+with prepared styles and every other option.
+`--guided-radius R [--guided-eps E]` is the photo mode: the result is smoothed by a guided filter with the content as guide (He
+et al., "Guided Image Filtering"; the post-step of Li et al. 2018's fast photorealistic variant) -- edges where the content has
+them, averages where it is flat.  Not in bands."""
 import argparse
 import os
 import time
@@ -31,6 +34,12 @@ _FLAGS = [
                                  help='luminance-only colour preservation: the result keeps its luminance and takes the colours of '
                                       'the content (the alternative to --keep-colors: not with it).  Fused into the last launch; '
                                       'with --passes > 1 applied once at the end, against the original content')),
+    (('--guided-radius',), dict(type=int, default=0, metavar='R',
+                                help='guided smoothing, the photo mode: filter the result over a (2R + 1)^2 box with the content as '
+                                     'guide (1 .. 64; 0: off).  With --passes > 1 applied once at the end, against the original '
+                                     'content; before --content-colors.  Not with --band-rows')),
+    (('--guided-eps',), dict(type=float, default=0.01, metavar='E',
+                             help='the regulariser of --guided-radius for images in [0,1] (> 0): smaller keeps more edges')),
     (('--device',), dict(default='/gpu:0', help='e.g. /gpu:0')),
     (('--style-size',), dict(type=int, default=0, help='short side of the style image (0: as is)')),
     (('--crop-size',), dict(type=int, default=0, help='centre-crop the style image to a square of this side (0: no)')),
@@ -133,10 +142,29 @@ def check_color_args(parser, args):
         parser.error('--content-colors with --passes > 1 needs --ss-stride 1 (a larger stride crops the content of every pass)')
 
 
+def check_guided_args(parser, args):
+    """--guided-radius / --guided-eps: their ranges (parser.error exits)"""
+    from ._lib import GUIDED_MAX_RADIUS
+    if not 0 <= args.guided_radius <= GUIDED_MAX_RADIUS:
+        parser.error('--guided-radius must be 0 (off) .. %d, got %d' % (GUIDED_MAX_RADIUS, args.guided_radius))
+    if not (np.isfinite(args.guided_eps) and args.guided_eps > 0):
+        parser.error('--guided-eps must be > 0, got %r' % (args.guided_eps,))
+    if args.guided_radius and args.passes > 1 and args.swap5 and args.ss_stride != 1:
+        parser.error('--guided-radius with --passes > 1 needs --ss-stride 1 (a larger stride crops the content of every pass)')
+
+
+def guided_of(args):
+    """(radius, eps_q) of --guided-radius / --guided-eps, eps in grey levels squared and at most 65025; None: off"""
+    from ._lib import guided_eps_q, GUIDED_MAX_EPS
+    r = getattr(args, 'guided_radius', 0)
+    return (r, min(GUIDED_MAX_EPS, guided_eps_q(getattr(args, 'guided_eps', 0.01)))) if r else None
+
+
 def _unbanded(args):
     """the options of this run that the banded call does not serve"""
     on = [('--adain', args.adain), ('--swap5', args.swap5), ('--interp-styles', args.interp_styles is not None),
-          ('--mask-path', args.mask_path is not None), ('--alpha-map', getattr(args, 'alpha_map', None) is not None)]
+          ('--mask-path', args.mask_path is not None), ('--alpha-map', getattr(args, 'alpha_map', None) is not None),
+          ('--guided-radius', getattr(args, 'guided_radius', 0) != 0)]
     return [name for name, v in on if v]
 
 
@@ -163,12 +191,18 @@ def check_content_fits(parser, args, content, path):
 def run_passes(model, content, args, predict):
     """`--passes` predictions from `content`, predict(image, content_colors) -> image.  --content-colors is fused into the
     prediction of a single pass; several passes run plain (a later pass sees a stylized input, not the content) and the
-    stand-alone op then runs once, against the original content -- at one pass the two routes give the same bits."""
+    stand-alone op then runs once, against the original content -- at one pass the two routes give the same bits.
+    --guided-radius is treated the same way, and runs before the colour op; only then is predict called with a third argument,
+    predict(image, content_colors, guided): (radius, eps_q) for the single pass, None for each of several."""
     n = max(1, args.passes)
     colors = getattr(args, 'content_colors', False)
+    guided = guided_of(args)
     out = content
     for _ in range(n):
-        out = predict(out, colors and n == 1)
+        out = predict(out, colors and n == 1, guided if n == 1 else None) if guided else predict(out, colors and n == 1)
+    if guided and n > 1:
+        from .ops import guided_filter_np
+        out = guided_filter_np(out, content, guided[0], guided[1], ctx=model.sess)
     if colors and n > 1:
         from .ops import content_colors_np
         out = content_colors_np(out, content, ctx=model.sess)
@@ -212,11 +246,12 @@ def stylize_pair(model, content, style, args, prepared=None, alpha_grey=None):
         style = preserve_colors_np(style, content, ctx=model.sess)
     if alpha_grey is not None:             # (one pass, no swap5, no bands: check_alpha_map_args)
         out = model.predict(content, style if prepared is None else prepared, args.alpha, adain=args.adain,
-                            content_colors=getattr(args, 'content_colors', False), strength=strength_map(alpha_grey, content.shape[:2]))
+                            content_colors=getattr(args, 'content_colors', False), strength=strength_map(alpha_grey, content.shape[:2]),
+                            guided=guided_of(args))
     else:
-        out = run_passes(model, content, args, lambda img, colors: model.predict(
+        out = run_passes(model, content, args, lambda img, colors, guided=None: model.predict(
             img, style if prepared is None else prepared, args.alpha, args.swap5, args.ss_alpha, args.adain, content_colors=colors,
-            band_rows=getattr(args, 'band_rows', 0) or None))
+            band_rows=getattr(args, 'band_rows', 0) or None, guided=guided))
     if args.concat:
         side = out.shape[0]
         out = np.hstack([utils._imresize(style, (side, side)), out])
@@ -255,9 +290,9 @@ def stylize_mix_pair(model, content, styles, args, prepared=None):
     if args.keep_colors:
         from .ops import preserve_colors_np
         styles = [preserve_colors_np(s, content, ctx=model.sess) for s in styles]
-    out = run_passes(model, content, args, lambda img, colors: model.predict_mix(
+    out = run_passes(model, content, args, lambda img, colors, guided=None: model.predict_mix(
         img, styles if prepared is None else prepared, args.interp_weights, args.alpha, args.adain, args.swap5, args.ss_alpha,
-        content_colors=colors))
+        content_colors=colors, guided=guided))
     if args.concat:
         side = out.shape[0]
         out = np.hstack([utils._imresize(s, (side, side)) for s in styles] + [out])
@@ -312,9 +347,9 @@ def stylize_mask_pair(model, content, grey, styles, args, prepared=None):
     if args.keep_colors:
         from .ops import preserve_colors_np
         styles = [preserve_colors_np(s, content, ctx=model.sess) for s in styles]
-    return run_passes(model, content, args, lambda img, colors: model.predict_masked(
+    return run_passes(model, content, args, lambda img, colors, guided=None: model.predict_masked(
         img, styles if prepared is None else prepared, mask_labels(grey, len(styles), img.shape[:2]), args.alpha, args.adain,
-        args.swap5, args.ss_alpha, content_colors=colors))
+        args.swap5, args.ss_alpha, content_colors=colors, guided=guided))
 
 
 def main(argv=None):
@@ -323,6 +358,7 @@ def main(argv=None):
     check_interp_args(parser, args)
     check_mask_args(parser, args)
     check_color_args(parser, args)
+    check_guided_args(parser, args)
     check_band_args(parser, args)
     check_alpha_map_args(parser, args)
     if args.synthetic_weights is None and not args.checkpoints:

@@ -13,6 +13,9 @@ MI355X path.  Same flags.  Differences, all forced by the environment or by the 
   differs per frame: those frames go through the per-pair batch instead.  `--content-colors` keeps the frames' colours the
   other way (luminance-only transfer, applied to the result): the style stays shared, so it goes with the prepared style,
   `--mask-path` and `--warm-start`.
+* `--guided-radius R [--guided-eps E]` (the photo mode) smooths every stylized frame with a guided filter whose guide is the input
+  frame (He et al., "Guided Image Filtering"): edges where the frame has them, averages where it is flat.  It runs at the end of the
+  batched call, before `--content-colors`, and goes with every other option.
 * `--device-resize` (opt-in) applies `--content-size` on the device: the frames go up raw and are resized there, on the stream
   of the call that stylizes them, to the bytes Pillow's bilinear resize gives on the host -- the same frames come out.
 """
@@ -49,6 +52,12 @@ _FLAGS = [
                                  help='luminance-only colour preservation: every frame keeps its luminance and takes the colours '
                                       'of its input frame (the alternative to --keep-colors: not with it).  Fused into the last '
                                       'launch; with --passes > 1 applied once at the end, against the input frames')),
+    (('--guided-radius',), dict(type=int, default=0, metavar='R',
+                                help='guided smoothing, the photo mode: filter every frame over a (2R + 1)^2 box with its input frame '
+                                     'as guide (1 .. 64; 0: off).  With --passes > 1 applied once at the end, against the input '
+                                     'frames; before --content-colors')),
+    (('--guided-eps',), dict(type=float, default=0.01, metavar='E',
+                             help='the regulariser of --guided-radius for images in [0,1] (> 0): smaller keeps more edges')),
     (('--style-size',), dict(type=int, default=0, help='short side of the style image (0: as is)')),
     (('--crop-size',), dict(type=int, default=0, help='centre-crop the style image to a square of this side (0: no)')),
     (('--content-size',), dict(type=int, default=0, help='short side of every frame (0: as is)')),
@@ -155,6 +164,15 @@ def check_color_args(parser, args):
         parser.error('--content-colors with --passes > 1 needs --ss-stride 1 (a larger stride crops the frames of every pass)')
 
 
+def check_guided_args(parser, args):
+    """--guided-radius / --guided-eps: their ranges, and the combinations they refuse (parser.error exits)"""
+    from .stylize import check_guided_args as check
+    check(parser, args)
+    if args.guided_radius and getattr(args, 'device_resize', False) and args.passes > 1:
+        parser.error('--device-resize with --guided-radius needs --passes 1 (the stand-alone filter needs the resized frames on '
+                     'the host)')
+
+
 def check_resize_args(parser, args):
     """--device-resize: the combinations it refuses (parser.error exits)"""
     if not args.device_resize:
@@ -183,6 +201,12 @@ def content_colors_frames(wct_model, stylized, frames):
                            for i in range(0, len(frames), 32)], axis=0)
 
 
+def guided_frames(wct_model, stylized, frames, guided):
+    """the stand-alone filter on a group of frames (after --passes > 1): `stylized` smoothed with `frames` as guides"""
+    return np.concatenate([wct_model.sess.guided_filter_batch(stylized[i:i + 32], frames[i:i + 32], guided[0], guided[1])
+                           for i in range(0, len(frames), 32)], axis=0)
+
+
 def match_masks(mask_path, frame_files, what='label maps'):
     """the label map (or strength map) file of every frame: `mask_path` is one file for all frames, or a directory whose maps are
     matched to the frames in sorted order (natural_key) -- the counts must agree (ValueError, before any GPU work)"""
@@ -198,7 +222,7 @@ def stylize_frames_masked(wct_model, frame_files, mask_files, styles, args):
     """Yield (frame_file, stylized uint8 image) in order, every frame stylized under its own label map: consecutive same-sized
     frames go through WCT.predict_frames_masked in batches, the K styles prepared once for the whole video.  Later --passes use
     the masked call too, the maps resized to each pass's input."""
-    from .stylize import load_mask, mask_labels
+    from .stylize import load_mask, mask_labels, guided_of
     k = len(styles)
     prepared = [wct_model.prepare_style(np.uint8(np.clip(s, 0, 255)) if s.dtype != np.uint8 else s, adain=args.adain) for s in styles]
     greys = {}
@@ -230,12 +254,16 @@ def stylize_frames_masked(wct_model, frame_files, mask_files, styles, args):
             frames = out = np.stack(group)
             # --content-colors: fused into a single pass; after several plain passes the op runs once, against the input frames
             colors, n = getattr(args, 'content_colors', False), max(1, args.passes)
+            guided = guided_of(args)                               # --guided-radius: the same, in front of the colour op
             size = device_size(args, group)                       # --device-resize: pass 1 takes the raw frames
             for _ in range(n):
                 masks = np.stack([mask_labels(grey_of(m), k, size or out.shape[1:3]) for m in mask_files[i:j]])
                 out = wct_model.predict_frames_masked(out, prepared, masks, args.alpha, args.adain, batch=args.batch,
-                                                      content_colors=colors and n == 1, resize=size)
+                                                      content_colors=colors and n == 1, resize=size,
+                                                      guided=guided if n == 1 else None)
                 size = None
+            if guided and n > 1:
+                out = guided_frames(wct_model, out, frames, guided)
             if colors and n > 1:
                 out = content_colors_frames(wct_model, out, frames)
             for f, o in zip(frame_files[i:j], out):
@@ -249,7 +277,7 @@ def stylize_frames_masked(wct_model, frame_files, mask_files, styles, args):
 def stylize_frames(wct_model, frame_files, style_img, args, alpha_files=None):
     """Yield (frame_file, stylized uint8 image) in order; consecutive same-sized frames are batched.  alpha_files: the strength map
     file of every frame (--alpha-map), or None."""
-    from .stylize import load_alpha_map, strength_map
+    from .stylize import load_alpha_map, strength_map, guided_of
     alpha_of = dict(zip(frame_files, alpha_files)) if alpha_files is not None else {}
 
     def strengths_of(files, shape_hw):
@@ -275,15 +303,19 @@ def stylize_frames(wct_model, frame_files, style_img, args, alpha_files=None):
 
     # --content-colors: fused into a single pass; after several plain passes the op runs once, against the input frames
     colors = getattr(args, 'content_colors', False)
+    guided = guided_of(args)                                      # --guided-radius: the same, in front of the colour op
 
     def run(frames, style, files):
         style = prepared if prepared is not None else style
         size = device_size(args, frames)
         maps = strengths_of(files, size or frames.shape[1:3]) if alpha_files is not None else None     # (one pass: check_alpha_map_args)
         out = wct_model.predict_frames(frames, style, args.alpha, args.swap5, args.ss_alpha, args.adain, batch=args.batch, warm=warm,
-                                       content_colors=colors and args.passes <= 1, resize=size, strengths=maps)
+                                       content_colors=colors and args.passes <= 1, resize=size, strengths=maps,
+                                       guided=guided if args.passes <= 1 else None)
         for _ in range(args.passes - 1):                      # later passes: plain WCT, as stylize_video.py:124-126
             out = wct_model.predict_frames(out, style, args.alpha, adain=args.adain, batch=args.batch)
+        if guided and args.passes > 1:
+            out = guided_frames(wct_model, out, frames, guided)
         if colors and args.passes > 1:
             out = content_colors_frames(wct_model, out, frames)
         return out
@@ -306,10 +338,13 @@ def stylize_frames(wct_model, frame_files, style_img, args, alpha_files=None):
             from .ops import preserve_colors_np
             styles = np.stack([preserve_colors_np(style_img, f, ctx=wct_model.sess) for f in group])
             outs = wct_model.sess.stylize_batch(frames, styles, wct_model.relu_targets, alpha=args.alpha,
-                                                adain=args.adain, wct_mode=wct_model.wct_mode)
+                                                adain=args.adain, wct_mode=wct_model.wct_mode,
+                                                guided=guided if args.passes <= 1 else None)
             for _ in range(args.passes - 1):
                 outs = wct_model.sess.stylize_batch(outs, styles, wct_model.relu_targets, alpha=args.alpha,
                                                     adain=args.adain, wct_mode=wct_model.wct_mode)
+            if guided and args.passes > 1:
+                outs = guided_frames(wct_model, outs, frames, guided)
             style_per_frame = list(styles)
         else:
             outs = run(frames, style_img, group_files)
@@ -330,6 +365,7 @@ def main(argv=None):
     check_mask_args(parser, args)
     check_warm_args(parser, args)
     check_color_args(parser, args)
+    check_guided_args(parser, args)
     check_resize_args(parser, args)
     check_alpha_map_args(parser, args)
     if args.synthetic_weights is None and not args.checkpoints:

@@ -194,8 +194,14 @@ class WCT(object):
             raise ValueError('a strength map is not served on a %dx%d content: it passes the limit of one launch and runs in bands, '
                              'which take no map' % (shape[0], shape[1]))
 
+    @staticmethod
+    def _check_guided(guided):
+        '''guided=(radius, eps_q) of a predict* call, checked: None stays None'''
+        from .context import check_guided
+        return None if guided is None else check_guided(guided)
+
     def predict(self, content, style, alpha=1, swap5=False, ss_alpha=1, adain=False, warm=None, content_colors=False,
-                band_rows=None, strength=None):
+                band_rows=None, strength=None, guided=None):
         '''Stylize a single content/style pair; arrays in [0,255], returns uint8 HxWx3.
            The /255 preprocess and the clip*255 postprocess run inside the library
            (fused at the ends of the kernel chain).  `style` may be a PreparedStyle (prepare_style); with one, `warm` may be a
@@ -208,7 +214,13 @@ class WCT(object):
            warm are not served there: ValueError.
            strength: a uint8 map [H][W] of the content's size (Context.stylize_prepared_strength) -- 255 the call's alpha, 0 "keep
            the content features", every level sampling it at its own stride; a style image is prepared for the call.  No swap5,
-           warm or bands with it: ValueError.'''
+           warm or bands with it: ValueError.
+           guided (here and in predict_frames, predict_mix, predict_masked, predict_frames_masked): (radius, eps_q) -- guided
+           smoothing, the photo mode (He et al., "Guided Image Filtering"; WCT_FLAG_GUIDED): the frame is filtered over a
+           (2 radius + 1)^2 box with the grey of `content` as guide, eps_q in grey levels squared (_lib.guided_eps_q(eps)); it
+           equals ops.guided_filter_np(the plain frame, content, radius, eps_q) bit for bit, and with content_colors the colour op
+           runs after it.  Not served in bands, with wrap or for textures: ValueError.'''
+        guided = self._check_guided(guided)                                       # ValueError before any GPU call
         if strength is not None:
             from ._lib import strength_map
             content = np.asarray(content)
@@ -221,12 +233,14 @@ class WCT(object):
             if isinstance(style, PreparedStyle):
                 check_prepared(self.sess, [style], self.relu_targets)
                 return self.sess.stylize_prepared_strength(content, style, strength, self.relu_targets, alpha=alpha, adain=adain,
-                                                           wct_mode=self.wct_mode, content_colors=content_colors)
+                                                           wct_mode=self.wct_mode, content_colors=content_colors, guided=guided)
             with self.prepare_style(np.asarray(style), adain=adain) as handle:
                 return self.sess.stylize_prepared_strength(content, handle, strength, self.relu_targets, alpha=alpha, adain=adain,
-                                                           wct_mode=self.wct_mode, content_colors=content_colors)
+                                                           wct_mode=self.wct_mode, content_colors=content_colors, guided=guided)
         rows = self._band_route(content, band_rows, swap5, adain, warm)           # ValueError before any GPU call
         if rows is not None:
+            if guided is not None:
+                raise ValueError('guided is not served in bands: filter the frame with ops.guided_filter_np')
             if isinstance(style, PreparedStyle):
                 check_prepared(self.sess, [style], self.relu_targets)
                 return self.sess.stylize_prepared_banded(np.asarray(content), style, self.relu_targets, alpha=alpha,
@@ -239,35 +253,38 @@ class WCT(object):
         if isinstance(style, PreparedStyle):
             check_prepared(self.sess, [style], self.relu_targets, swap5)          # ValueError before any GPU call
             return self.sess.stylize_prepared(np.asarray(content), style, self.relu_targets, alpha=alpha, adain=adain,
-                                              wct_mode=self.wct_mode, warm=warm, content_colors=content_colors)
+                                              wct_mode=self.wct_mode, warm=warm, content_colors=content_colors, guided=guided)
         content, _ = self._swap5_setup(np.asarray(content), None, swap5, ss_alpha)
         style = np.asarray(style)
         # uint8 arrays take the fused /255 on the device; float arrays are divided by 255 WITHOUT rounding, as the
         # reference's preprocess does (wct.py:60-64) -- Context.stylize hands them over as float32 images
         return self.sess.stylize(content, style, self.relu_targets, alpha=alpha, adain=adain,
-                                 wct_mode=self.wct_mode, swap5=bool(swap5), content_colors=content_colors)
+                                 wct_mode=self.wct_mode, swap5=bool(swap5), content_colors=content_colors, guided=guided)
 
-    def predict_mix(self, content, styles, weights=None, alpha=1, adain=False, swap5=False, ss_alpha=1, content_colors=False):
+    def predict_mix(self, content, styles, weights=None, alpha=1, adain=False, swap5=False, ss_alpha=1, content_colors=False,
+                    guided=None):
         '''Stylize with a weighted mix of several styles (Li et al. 2017, sec. 4.2; the reference's README TODO
            "Interpolation between styles"): every level applies sum_k lambda_k T(content, style_k), lambda = weights /
            sum(weights); weights=None means equal weights.  Arrays in [0,255], returns uint8 HxWx3.  One style gives
            predict(content, style) bit for bit, as do one-hot weights.  swap5 takes one style only (style-swap is not linear).'''
         from ._lib import mix_weights
+        guided = self._check_guided(guided)
         handles, styles = split_styles(list(styles))             # ValueError: images and prepared styles in one list
         if handles:
             weights = mix_weights(weights, len(handles))
             check_prepared(self.sess, handles, self.relu_targets, swap5)
             return self.sess.stylize_prepared_mix(np.asarray(content), handles, weights, self.relu_targets, alpha=alpha,
-                                                  adain=adain, wct_mode=self.wct_mode, content_colors=content_colors)
+                                                  adain=adain, wct_mode=self.wct_mode, content_colors=content_colors, guided=guided)
         styles = [np.asarray(s) for s in styles]
         weights = mix_weights(weights, len(styles))              # ValueError before any GPU call
         if swap5 and len(styles) > 1:
             raise ValueError('swap5 takes one style: style-swap is not linear in the style')
         content, _ = self._swap5_setup(np.asarray(content), None, swap5, ss_alpha)
         return self.sess.stylize_mix(content, styles, weights, self.relu_targets, alpha=alpha, adain=adain,
-                                     wct_mode=self.wct_mode, swap5=bool(swap5), content_colors=content_colors)
+                                     wct_mode=self.wct_mode, swap5=bool(swap5), content_colors=content_colors, guided=guided)
 
-    def predict_masked(self, content, styles, mask, alpha=1, adain=False, swap5=False, ss_alpha=1, content_colors=False):
+    def predict_masked(self, content, styles, mask, alpha=1, adain=False, swap5=False, ss_alpha=1, content_colors=False,
+                       guided=None):
         '''Stylize each region of a label map with its own style (Li et al. 2017, sec. 4.2, Fig. 7; the reference's README TODO
            "Spatial control/masking"): `mask` [H][W] holds a label 0 .. K-1 per content pixel, `styles` K images (sizes may
            differ), and at every level the pixels of label k are transformed with style k alone, with their own statistics
@@ -276,28 +293,31 @@ class WCT(object):
            `styles` may be K PreparedStyle objects (prepare_style) instead: the same frame, without the K style sides; the
            entries are all handles or all images (a mixed list is a ValueError), and swap5 takes images.'''
         from ._lib import mask_labels
+        guided = self._check_guided(guided)
         handles, styles = split_styles(list(styles))             # ValueError: images and prepared styles in one list
         content = np.asarray(content)
         if handles:
             mask = mask_labels(mask, len(handles), content.shape[:2])
             check_prepared(self.sess, handles, self.relu_targets, swap5)
             return self.sess.stylize_prepared_masked(content, handles, mask, self.relu_targets, alpha=alpha, adain=adain,
-                                                     wct_mode=self.wct_mode, content_colors=content_colors)
+                                                     wct_mode=self.wct_mode, content_colors=content_colors, guided=guided)
         styles = [np.asarray(s) for s in styles]
         mask = mask_labels(mask, len(styles), content.shape[:2])        # ValueError before any GPU call
         if swap5 and len(styles) > 1:
             raise ValueError('swap5 takes one style: style-swap is not a per-region affine map')
         content, mask = self._swap5_setup(content, mask, swap5, ss_alpha)
         return self.sess.stylize_masked(content, styles, mask, self.relu_targets, alpha=alpha, adain=adain,
-                                        wct_mode=self.wct_mode, swap5=bool(swap5), content_colors=content_colors)
+                                        wct_mode=self.wct_mode, swap5=bool(swap5), content_colors=content_colors, guided=guided)
 
-    def predict_frames_masked(self, frames, styles, masks, alpha=1, adain=False, batch=16, content_colors=False, resize=None):
+    def predict_frames_masked(self, frames, styles, masks, alpha=1, adain=False, batch=16, content_colors=False, resize=None,
+                              guided=None):
         '''Spatial control of a video: same-sized frames [F][H][W][3], a label map per frame `masks` [F][H][W] (or one [H][W] map
            used for every frame), `styles` K images -- prepared once here -- or K PreparedStyle objects.  Frame f equals
            predict_masked(frames[f], styles, masks[f]) bit for bit; the frames go through the device in batches of `batch`
            (<= 32), the regions of a batch sharing every launch and the eigensolves.  Returns uint8 [F][Ho][Wo][3].
            resize (h, w): as in predict_frames; the label maps are given at the resized size.'''
         from ._lib import mask_labels_frames
+        guided = self._check_guided(guided)
         frames = np.asarray(frames)
         if frames.ndim != 4 or frames.shape[3] != 3:
             raise ValueError('expected [F][H][W][3] frames, got shape %s' % (frames.shape,))
@@ -315,7 +335,7 @@ class WCT(object):
             batch = max(1, min(32, int(batch)))
             return np.concatenate([self.sess.stylize_prepared_masked_batch(frames[i:i + batch], handles or own, masks[i:i + batch],
                                                                            self.relu_targets, alpha=alpha, adain=adain,
-                                                                           wct_mode=self.wct_mode, content_colors=content_colors,
+                                                                           wct_mode=self.wct_mode, content_colors=content_colors, guided=guided,
                                                                            resize=resize)
                                    for i in range(0, len(frames), batch)], axis=0)
         finally:
@@ -323,7 +343,7 @@ class WCT(object):
                 h.close()
 
     def predict_frames(self, frames, style, alpha=1, swap5=False, ss_alpha=1, adain=False, batch=16, warm=None,
-                       content_colors=False, resize=None, wrap=False, strengths=None):
+                       content_colors=False, resize=None, wrap=False, strengths=None, guided=None):
         '''Stylize same-sized frames [F][H][W][3] with ONE style image (the loop of stylize_video.py:112-121,
            which calls predict() once per frame and so re-runs the style encoder, the style statistics and the
            style eigendecompositions every frame).  Here the style side runs once per batch of `batch` frames;
@@ -339,6 +359,7 @@ class WCT(object):
            strengths: a strength map per frame, uint8 [F][H][W] (or one [H][W] map for all frames), at the resized size with
            resize -- frame f equals predict(frames[f], style, strength=strengths[f]) bit for bit (cold).  A style image is prepared
            once here; warm then needs a PreparedStyle as always.  No swap5 or wrap with it: ValueError.'''
+        guided = self._check_guided(guided)                                       # ValueError before any GPU call
         frames = np.asarray(frames)
         if strengths is not None:
             from ._lib import strength_maps_frames
@@ -360,7 +381,7 @@ class WCT(object):
                 batch = max(1, min(32, int(batch)))
                 return np.concatenate([self.sess.stylize_prepared_strength_batch(
                     frames[i:i + batch], own or style, strengths[i:i + batch], self.relu_targets, alpha=alpha, adain=adain,
-                    wct_mode=self.wct_mode, warm=warm, content_colors=content_colors, resize=resize)
+                    wct_mode=self.wct_mode, warm=warm, content_colors=content_colors, guided=guided, resize=resize)
                     for i in range(0, len(frames), batch)], axis=0)
             finally:
                 if own is not None:
@@ -369,7 +390,7 @@ class WCT(object):
             if not isinstance(style, PreparedStyle):
                 raise ValueError('wrap takes a PreparedStyle (prepare_style), not a style image')
             for name, on in (('swap5', swap5), ('warm', warm is not None), ('content_colors', content_colors),
-                             ('resize', resize is not None)):
+                             ('resize', resize is not None), ('guided', guided is not None)):
                 if on:
                     raise ValueError('%s is not served with wrap: the periodic path takes one prepared style, WCT or AdaIN' % name)
             if frames.ndim != 4 or frames.shape[3] != 3:
@@ -396,7 +417,7 @@ class WCT(object):
             batch = max(1, min(32, int(batch)))
             return np.concatenate([self.sess.stylize_prepared_batch(frames[i:i + batch], style, self.relu_targets, alpha=alpha,
                                                                     adain=adain, wct_mode=self.wct_mode, warm=warm,
-                                                                    content_colors=content_colors, resize=resize)
+                                                                    content_colors=content_colors, guided=guided, resize=resize)
                                    for i in range(0, len(frames), batch)], axis=0)
         style = np.asarray(style)
         assert frames.ndim == 4 and style.ndim == 3
@@ -413,7 +434,7 @@ class WCT(object):
             self.sess.set_style_swap(ss_alpha, self.ss_patch_size, self.ss_stride)
         batch = max(1, min(32, int(batch)))
         outs = [self.sess.stylize_batch(frames[i:i + batch], style, self.relu_targets, alpha=alpha, adain=adain,
-                                        wct_mode=self.wct_mode, swap5=bool(swap5), content_colors=content_colors, resize=resize)
+                                        wct_mode=self.wct_mode, swap5=bool(swap5), content_colors=content_colors, guided=guided, resize=resize)
                 for i in range(0, len(frames), batch)]
         return np.concatenate(outs, axis=0)
 
