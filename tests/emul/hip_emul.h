@@ -1,4 +1,4 @@
-// Lane-by-lane CPU emulation of the HIP device facilities the eigensolver's pair-problem code (csrc/jacobi_dev.h) uses:
+// Lane-by-lane CPU emulation of the HIP device facilities the eigensolver's pair-problem code (csrc/jacobi_pair64.h) uses:
 // a workgroup is NT host threads, a wave 64 consecutive ones; __syncthreads is a pthread barrier, cross-lane operations
 // (DPP row rotate, __shfl, readfirstlane) and the MFMAs exchange their operands through a per-wave array between two
 // wave barriers.  Test infrastructure only (tests/test_jacobi_emul.py): lets the kernel SOURCE run here, where there is no GPU.

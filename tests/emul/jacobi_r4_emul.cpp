@@ -1,4 +1,4 @@
-// The round-4 pair-problem code (wct_tf_amd/csrc/jacobi_dev.h, namespace r4) executed lane by lane on the CPU
+// The 64-wide pair-problem code (wct_tf_amd/csrc/jacobi_pair64.h, namespace pair64) executed lane by lane on the CPU
 // (hip_emul.h) and checked against plain sequential arithmetic in double precision:
 //   1. cross step, first mode: S image and rotation matrix of every pair problem == the 32 rotation sets applied to the
 //      full 64 x 64 matrices one after the other (the routing of tools/jacobi_patch_proto.py, now on the kernel source);
@@ -12,7 +12,7 @@
 namespace emul { thread_local Idx tidx; thread_local Idx bidx; thread_local Block* blk; }
 #include <stdio.h>
 #include <stdlib.h>
-#include "../../wct_tf_amd/csrc/jacobi_dev.h"
+#include "../../wct_tf_amd/csrc/jacobi_pair64.h"
 
 static int failures = 0;
 static void check(const char* what, double err, double tol) {
@@ -20,7 +20,7 @@ static void check(const char* what, double err, double tol) {
   if (!(err <= tol)) ++failures;
 }
 
-constexpr int M2 = 64, B = 32, FR = M2 * M2;
+constexpr int M2 = pair64::M2, B = pair64::B, FR = pair64::FR;
 
 // host view of the pairing schedule (block_pair)
 static void pair_blocks(int g, int step, int nblk, int& bi, int& bj) { block_pair(g, step, nblk, bi, bj); }
@@ -84,7 +84,7 @@ static void reference_cross(const double* S0, double* S, double* Q) {
   }
 }
 
-// the intra step's ordering (r4::intra_wave): odd-even transposition with exchange on the positions of each 32-wide block -- even
+// the intra step's ordering (pair64::intra_wave): odd-even transposition with exchange on the positions of each 32-wide block -- even
 // sets rotate the position pairs (0,1)(2,3).., odd sets (1,2)..(29,30); position p takes s x_p + c x_q, position q takes c x_p - s x_q
 static double ref_offmax_intra = 0;
 static int intra_pairs_seen = 0;
@@ -154,19 +154,19 @@ struct Solver {
     return a;
   }
   void run_d(const JacobiFusedArgs& a) {
-    const size_t bytes = r4::lds_bytes<M2, 0>(1, 0, a.first, a.step_d);
+    const size_t bytes = pair64::lds_bytes(1, 0, a.first, a.step_d);
     for (int g = 0; g < npair; ++g) {
       arm(bytes);
-      emul::run_block(r4::Lay<0>::NTD, g, [&](int) { r4::fused_d<M2, 0>(a, 0, g, lds.data()); });
+      emul::run_block(pair64::NT, g, [&](int) { pair64::fused_d(a, 0, g, lds.data()); });
       guard_ok(bytes, "fused_d");
     }
   }
   void run_u(const JacobiFusedArgs& a, bool with_v) {
     const int ntask = npair * (npair - 1) / 2 + npair + (with_v ? npair * npair : 0);
-    const size_t bytes = r4::lds_bytes<M2, 0>(0, 1, 0, 0);
+    const size_t bytes = pair64::lds_bytes(0, 1, 0, 0);
     for (int task = 0; task < ntask; ++task) {
       arm(bytes);
-      emul::run_block(r4::NT, task, [&](int) { r4::fused_u<M2>(a, 0, task, lds.data()); });
+      emul::run_block(pair64::NT, task, [&](int) { pair64::fused_u(a, 0, task, lds.data()); });
       guard_ok(bytes, "fused_u");
     }
   }

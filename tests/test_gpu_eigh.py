@@ -131,7 +131,7 @@ def test_eigh_pool_solved_alone(solo, c):
 def test_eigh_trivial_matrices_come_back_in_place(solo, c):
     """identity, diagonal and zero come back exact and in place: evals == diag(A) position by position, V == I.
 
-    On the 64-wide block pairs (C = 256, 384, 512 here) the intra step of a sweep (csrc/jacobi_dev.h r4 intra_wave) orders its
+    On the 64-wide block pairs (C = 256, 384, 512 here) the intra step of a sweep (csrc/jacobi_pair64.h intra_wave) orders its
     pairs by odd-even transposition WITH EXCHANGE and leaves the 32 columns of every block in reverse order: until
     jacobi_unexchange_kernel (csrc/eigh.hip) these matrices, done after one sweep, came back with V the permutation that reverses
     each block of 32 columns and evals permuted alike (exact, but not in place)."""

@@ -1,4 +1,4 @@
-"""The round-4 pair-problem kernel source (wct_tf_amd/csrc/jacobi_dev.h, namespace r4: the 64 x 64 pair problem resident
+"""The 64-wide pair-problem kernel source (wct_tf_amd/csrc/jacobi_pair64.h, namespace pair64: the 64 x 64 pair problem resident
 in registers, the 256-thread tile update, the look-ahead assembly) compiled for the HOST and executed lane by lane
 (tests/emul/hip_emul.h: 256 threads per workgroup, pthread barriers, emulated DPP / shuffles / MFMA) against plain
 sequential arithmetic in double precision.  There is no GPU in the build container: this is how the kernel's data routing

@@ -1,11 +1,14 @@
 #!/usr/bin/env python3
-"""Per-kernel ISA comparison of two builds of the library:  kernel_isa_diff.py <dirA> <dirB>
+"""Per-kernel ISA comparison of two builds of the library:  kernel_isa_diff.py [--rename OLD_SYMBOL=NEW_SYMBOL]... <dirA> <dirB>
 
 Each directory holds the `*-hip-amdgcn-amd-amdhsa-gfx950.s` files of one build: every unit of csrc/ compiled with the flags of
 wct_tf_amd/build.py plus --save-temps, from inside the directory.  A kernel is the text from its `_Z...:` label to
-`.Lfunc_end`, comments stripped and the `.LBB<n>_` label numbers normalised.  Exit status 0 iff both builds have the same set
+`.Lfunc_end` (instructions and kernel descriptor), comments stripped, the `.LBB<n>_` label numbers normalised and the closing
+switch back to the text section written as `.text` whether or not the kernel is an instance of a template.  Exit status 0 iff both builds have the same set
 of kernel symbols, every symbol is emitted by exactly one unit of its build, and every kernel's instruction text is identical.
-Under a kernel that differs: its line counts and the opcodes whose counts differ."""
+Under a kernel that differs: its line counts and the opcodes whose counts differ.
+--rename (repeatable): a kernel of build A whose mangled name changed (template arguments dropped, say) is compared under its new
+name: OLD_SYMBOL becomes NEW_SYMBOL as build A's symbol and wherever its text names it, before the comparison."""
 import collections
 import glob
 import os
@@ -30,6 +33,9 @@ def kernels(d):
                     cur = None
                     continue
                 s = re.sub(r'\.LBB\d+_', '.LBB_', line.split(';')[0].rstrip())
+                # the way back to the text section behind the kernel descriptor: `.section .text.<symbol>,...,comdat` for an
+                # instance of a template, plain `.text` for a kernel that is none -- where the code lies, not what it is
+                s = re.sub(r'^\s*\.section\s+\.text\.\S+,comdat$', '\t.text', s)
                 if s.strip():
                     cur.append(s)
     return out
@@ -47,8 +53,28 @@ def opcodes(lines):
     return h
 
 
+def renamed(ks, renames):
+    """ks with every OLD symbol of renames [(OLD, NEW), ...] called NEW, as a key and wherever a kernel's text names it"""
+    for old, new in renames:
+        out = {}
+        for k, es in ks.items():      # (a NEW that the build has already: both entries under it, reported as MULTIPLE)
+            out.setdefault(new if k == old else k, []).extend((unit, [s.replace(old, new) for s in lines]) for unit, lines in es)
+        ks = out
+    return ks
+
+
 def main():
-    a, b = kernels(sys.argv[1]), kernels(sys.argv[2])
+    args, renames = [], []
+    argv = sys.argv[1:]
+    while argv:
+        x = argv.pop(0)
+        if x == '--rename':
+            renames.append(tuple(argv.pop(0).split('=', 1)))
+        elif x.startswith('--rename='):
+            renames.append(tuple(x[len('--rename='):].split('=', 1)))
+        else:
+            args.append(x)
+    a, b = renamed(kernels(args[0]), renames), kernels(args[1])
     bad = 0
     print('%-8s %-10s %-10s %6s  kernel' % ('status', 'unit A', 'unit B', 'lines'))
     for k in sorted(set(a) | set(b)):

@@ -17,7 +17,7 @@ SOURCES = API_UNITS + ['conv.hip', 'conv_wino.hip', 'coral.hip', 'colors.hip', '
 
 STAMP = LIB + '.src.sha256'
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wno-unused-value', '-Wno-unused-result']
-# per-file additions.  eigh.hip: the SLP vectoriser packs the eigensolver's rotation arithmetic into v_pk_fma_f32 pairs at the
+# per-file additions.  eigh.hip (with its jacobi_*.h): the SLP vectoriser packs the eigensolver's rotation arithmetic into v_pk_fma_f32 pairs at the
 # price of ~20 v_mov per rotation set for operand assembly (measured: Jacobi 25.2 -> 23.8 ms per 32-pair step without it).  Only
 # the eigensolver is known to need the flag; the other transform units carry it because they were built with it while they were
 # one file with the solver, and nobody has measured them without it.

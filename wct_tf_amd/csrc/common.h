@@ -227,7 +227,7 @@ struct WctCall {
   hipStream_t stream;
 };
 // WCT_STAGE_EIG_FP32UPDATE (with WCT_STAGE_EIG): the eigensolver's tile updates on fp32 MFMA instead of split fp16 -- style-swap, whose
-// patch matching is an argmax over the whitened features (csrc/jacobi_dev.h r4::fused_u)
+// patch matching is an argmax over the whitened features (csrc/jacobi_pair64.h fused_u)
 enum { WCT_STAGE_COV = 1, WCT_STAGE_EIG = 2, WCT_STAGE_APPLY = 4, WCT_STAGE_ALL = 7, WCT_STAGE_EIG_FP32UPDATE = 8 };
 
 // the state of `style` [Ns][C] under `key`: launch_wct's style side alone (adain: launch_adain's), bit for bit

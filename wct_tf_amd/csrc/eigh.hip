@@ -1,8 +1,18 @@
-// K5 of the whiten-colour transform (the stage list: wct.hip): the batched symmetric eigensolver -- its kernels on top of
-// jacobi_dev.h, the host driver of a solve (segments, look-ahead launches, the V pass) and the transform's eigensolve stage.
+// K5 of the whiten-colour transform (the stage list: wct.hip): the batched symmetric eigensolver -- two-sided block Jacobi.
+//   Column blocks of B = M2/2 are paired round-robin (jacobi_dev.h); each pair's M2 x M2 diagonal problem gets one cyclic
+//   Jacobi step -- the D part --, then every M2 x M2 tile of A (and of the eigenvector matrix V) is updated as Qg^T A_gh Qh
+//   on the MFMA pipe -- the U part.  ONE launch per outer step carries { D(s), U(s-1) } (the look-ahead launches:
+//   jacobi_pair32.h), C/B steps per sweep.  A per-matrix `done` flag turns later launches into no-ops.
+//   Two kernels: jacobi_fused_kernel for the 32-wide block pairs, pair problems as LDS images (jacobi_pair32.h), and
+//   jacobi_fused4_kernel for the 64-wide ones, pair problems resident in registers (jacobi_pair64.h); jacobi_wide_pairs
+//   chooses.  With many matrices the 64-wide path takes V out of the tile update: jacobi_vstrip_kernel applies a whole launch
+//   segment's rotations to V held in registers, on a side stream.
+// This unit: those kernels, the residual measurement and the checks, the host driver of a solve (segments, look-ahead
+// launches, the V pass) and the transform's eigensolve stage.
 #include "wct_stages.h"
 #include <stdlib.h>
-#include <algorithm>
+#include "jacobi_pair32.h"
+#include "jacobi_pair64.h"
 
 // A launcher that returns void (the per-launch helpers of the eigensolver's trains) notes a refused launch here, with the kernel's
 // name, the moment it happens; the train's driver returns it (launch_rc_take) instead of a generic failure at a later sync.
@@ -11,467 +21,51 @@ static thread_local int launch_rc_sticky = WCT_OK;
     wct_set_error("launch of %s refused: %s (%s:%d)", what, hipGetErrorString(e_), __FILE__, __LINE__); launch_rc_sticky = WCT_ERR_HIP; } } while (0)
 static inline int launch_rc_take() { const int r = launch_rc_sticky; launch_rc_sticky = WCT_OK; return r; }
 
-// ---------------------------------------------------------------------------
-// K5: batched symmetric eigensolver -- two-sided block Jacobi.
-//   Column blocks of B = M2/2 are paired round-robin; each pair's M2 x M2 diagonal
-//   problem gets one cyclic Jacobi sweep in LDS (jacobi_diag_kernel), then every
-//   M2 x M2 tile of A (and of the eigenvector matrix V) is updated as Qg^T A_gh Qh on
-//   fp32 MFMA (jacobi_update_kernel).  Two launches per step, C/B-1 steps per sweep.
-//   A per-matrix `done` flag turns later launches into no-ops.
-// ---------------------------------------------------------------------------
-#include "jacobi_dev.h"
-
-// The cross sweep with ONE wave carrying the rotation parameters ("pivot wave"), the default since round 2.
-// In jacobi_cross_sets every thread derives rotation(l) itself (~35 instructions with three transcendentals on a
-// dependent chain, 32x redundant) and the owners mirror the pivots into the D/O arrays.  Here:
-//   * threads are numbered along the diagonals of the (k, l) grid: k = t % NP, d = t / NP, l = k + d + 1 (mod NP), so the
-//     NP threads (k, k+1) that own S[p_k][q_k'] -- the element pair k annihilates in the NEXT set -- are the first NP
-//     lanes of wave 0;
-//   * those lanes keep pair k's pivot block (pp, qq, pq) in registers: pp and qq follow in closed form from the
-//     rotation they computed for this set (c^2 pp - 2cs pq + s^2 qq, ...), the q diagonal of pair k+1 arrives by one
-//     lane shuffle, pq is their own freshly rotated element; they derive the next rotation and publish (c, s) in a
-//     ping-pong LDS array; every other wave reads (c_l, s_l), (c_k, s_k) -- two 8-byte loads -- and only rotates;
-//   * within a set every element of the {S, Q} image is read and written by exactly one thread, so the image is
-//     updated in place (one image instead of two); with PITCH = N the 8-byte accesses of a diagonal are conflict-free.
-// Per set a bulk wave issues ~45 instructions instead of ~100, and the dependent chain of a set is the pivot wave's.
-template <int N>
-__device__ __forceinline__ void jacobi_cross_sets_pw(unsigned char* sq, unsigned char* csb, int t, float floor_m, float& my_off, float& my_sig) {
-  constexpr int NP = N / 2, ROWB = N * 8;                            // bytes per image row
-  constexpr int CSB = NP * 8, DUMMY = 2 * CSB;                       // csb layout: CS[2][NP] float2 (c, s), dummy float2
-  const int k = t & (NP - 1), d = t / NP;
-  const int l = (k + d + 1) & (NP - 1);
-  const bool pwave = __builtin_amdgcn_readfirstlane(t >> 6) == 0;    // wave-uniform: the wave holding the lanes (k, k+1)
-  const bool piv = d == 0;
-  const int nb_lane = (t & 63 & ~(NP - 1)) | ((k + 1) & (NP - 1));   // lane of pair k+1
-  float ppk = 0.f, qqk = 0.f, pqk = 0.f, ck = 1.f, sk = 0.f;         // pair k's pivot block and rotation (pivot wave only)
-  if (pwave) {
-    __builtin_amdgcn_s_setprio(2);                                   // the chain of a set runs through this wave
-    const f32x2* SQ = reinterpret_cast<const f32x2*>(sq);
-    ppk = SQ[k * N + k][0]; qqk = SQ[(NP + k) * N + NP + k][0]; pqk = SQ[k * N + NP + k][0];   // set 0 pairs k with NP + k
-    float off, sig;
-    jacobi_rotation(ppk, qqk, pqk, floor_m, ck, sk, off, sig);
-    if (piv) { my_off = fmaxf(my_off, off); my_sig = fmaxf(my_sig, sig); }
-    f32x2 r; r[0] = ck; r[1] = sk;
-    *reinterpret_cast<f32x2*>(csb + (piv ? k * 8 : DUMMY)) = r;
-  }
-  __syncthreads();
-  const int row_pk = k * ROWB, col_pl = l * 8;
-  const int a_pp = row_pk + col_pl;
-  int qk = NP + k, ql = NP + l;                                      // q index of set s: NP + ((j + s) & (NP - 1))
-  const int cs_l = l * 8, cs_k = k * 8;
-  const int cs_w0 = piv ? k * 8 : DUMMY, cs_w1 = piv ? CSB + k * 8 : DUMMY;   // the dummy slot absorbs the lanes that own no pair
-  auto ld2 = [&](const unsigned char* base, int off) { return *reinterpret_cast<const f32x2*>(base + off); };
-  auto body = [&](auto CURC) {
-    constexpr int CUR = decltype(CURC)::value, NX = CUR ^ 1;
-    const f32x2 rl = ld2(csb + CUR * CSB, cs_l), rk = ld2(csb + CUR * CSB, cs_k);
-    const int qlb = ql * 8, qkb = qk * ROWB;
-    const int a_pq = row_pk + qlb, a_qp = qkb + col_pl, a_qq = qkb + qlb;
-    const f32x2 app = ld2(sq, a_pp), apq = ld2(sq, a_pq), aqp = ld2(sq, a_qp), aqq = ld2(sq, a_qq);
-    const float cl = rl[0], sl = rl[1], ckk = rk[0], skk = rk[1];
-    // columns (pair l) on the {S, Q} pairs as packed operations -- the same (c_l, s_l) acts on both halves of a
-    // float2, so v_pk_mul / v_pk_fma take the scalars broadcast and need no operand assembly --, then rows (pair k) on
-    // the S halves alone.  (Written element by element the same arithmetic came out of hipcc as 12 packed operations
-    // fed by ~30 v_mov: the set loop is VALU-issue bound, ablation in profiles/r03_jacobi_set_ablation.txt.)
-    const f32x2 ypp = cl * app - sl * apq, ypq = sl * app + cl * apq;
-    const f32x2 yqp = cl * aqp - sl * aqq, yqq = sl * aqp + cl * aqq;
-    f32x2 npp = ypp, npq = ypq, nqp = yqp, nqq = yqq;
-    npp[0] = ckk * ypp[0] - skk * yqp[0];  npq[0] = ckk * ypq[0] - skk * yqq[0];
-    nqp[0] = skk * ypp[0] + ckk * yqp[0];  nqq[0] = skk * ypq[0] + ckk * yqq[0];
-    if (pwave) {
-      // pair k after this set's rotation (closed form from registers), the next set's partner diagonal from the
-      // lane of pair k+1 -- a DPP wave shift (lane i reads lane i+1), the wrap-around lane NP-1 <- 0 patched with a
-      // v_readlane: no LDS round trip on the chain (round 2 used ds_bpermute here) --, the next pivot element from
-      // this thread's own block
-      const float c2 = ck * ck, s2 = sk * sk, cs2 = 2.f * ck * sk;
-      const float ppn = c2 * ppk - cs2 * pqk + s2 * qqk;
-      const float qqn = s2 * ppk + cs2 * pqk + c2 * qqk;
-      const int qqn_i = __builtin_bit_cast(int, qqn);
-      const int shl = __builtin_amdgcn_update_dpp(qqn_i, qqn_i, 0x130 /* wave_shl:1 */, 0xF, 0xF, false);
-      const int first = __builtin_amdgcn_readlane(qqn_i, 0);
-      const float qq_next = __builtin_bit_cast(float, k == NP - 1 ? first : shl);
-      ppk = ppn; qqk = qq_next; pqk = npq[0];
-      const bool rot = jacobi_rotation_cs(ppk, qqk, pqk, ck, sk);
-      f32x2 r; r[0] = ck; r[1] = sk;
-      *reinterpret_cast<f32x2*>(csb + (NX ? cs_w1 : cs_w0)) = r;
-      float off, sig;
-      jacobi_rotation_stats(ppk, qqk, pqk, floor_m, rot, off, sig);
-      if (piv) { my_off = fmaxf(my_off, off); my_sig = fmaxf(my_sig, sig); }
-    }
-    *reinterpret_cast<f32x2*>(sq + a_pp) = npp;  *reinterpret_cast<f32x2*>(sq + a_pq) = npq;
-    *reinterpret_cast<f32x2*>(sq + a_qp) = nqp;  *reinterpret_cast<f32x2*>(sq + a_qq) = nqq;
-    qk = NP | ((qk + 1) & (NP - 1));
-    ql = NP | ((ql + 1) & (NP - 1));
-    __syncthreads();
-  };
-#pragma unroll 1
-  for (int s = 0; s < NP; s += 2) {
-    body(std::integral_constant<int, 0>{});
-    body(std::integral_constant<int, 1>{});
-  }
-}
-
-template <int M2>
-static size_t jacobi_diag_lds(int step, bool pw) {
-  if (pw && step >= 0) return (size_t)M2 * M2 * sizeof(f32x2) + (size_t)(M2 + 2) * sizeof(f32x2);   // image, CS[2][M2/2], dummy
-  return (size_t)2 * M2 * (M2 + 1) * sizeof(f32x2) + 4 * M2 * sizeof(float);                         // images, D[2][M2], O[2][M2/2], dummy[M2]
-}
-
-// ---------------------------------------------------------------------------
-// K5, look-ahead launches (round 3).  The serial chain of a solve used to be  D(s) -> U(s) -> D(s+1) -> ...  (pair
-// problems, then the tile update that needs their rotations, then the next pair problems that need the updated
-// tiles): two dependent launches per outer step, the latency-bound pair kernel idle while the tile update runs and
-// vice versa.  Here ONE launch carries  { D(s), U(s-1) }:
-//   * D(s) does not wait for U(s-1).  Its 2B x 2B pair problem (blocks bi, bj) is assembled from the rotated images
-//     D(s-1) left behind (Sbuf: they ARE the diagonal tiles after U(s-1)) and ONE off-diagonal B x B block it
-//     computes itself -- crit = Q_g1[:, h1]^T . P_old[tile g1, g2] . Q_g2[:, h2], with (g1, h1) / (g2, h2) the pair and
-//     half that held bi / bj at step s-1 -- from the matrix state BEFORE U(s-1) and the rotations of step s-1;
-//   * U(s-1) reads P_old and writes every tile into the other buffer P_new (off-diagonal tiles g < h computed and
-//     mirrored, diagonal tiles copied from Sbuf), so D(s) can read P_old while it runs; V is updated in place.
-// Both parts use the whole block (M2/2)^2 threads = (M2/16)^2 waves, one 16x16 output tile of v_mfma_f32_16x16x4_f32
-// per wave.  The chain of a solve becomes D -> D -> D ...; the tile updates run beside it.
-// Data routing checked against the plain sequence in tools/jacobi_lookahead_proto.py.
-// ---------------------------------------------------------------------------
-
-template <int M2>
-static size_t jacobi_fused_lds(int has_d, int has_u, int first, int step_d) {
-  constexpr int B = M2 / 2;
-  size_t need = 0;
-  if (has_d) {
-    if (step_d < 0) need = jacobi_diag_lds<M2>(-1, true);                               // intra sets: two images
-    else {
-      need = jacobi_diag_lds<M2>(0, true);
-      if (!first) need = std::max(need, (size_t)(M2 * (M2 + 1) + 2 * M2 * (B + 1) + B * (M2 + 1)) * sizeof(float));
-    }
-  }
-  if (has_u) need = std::max(need, (size_t)3 * M2 * (M2 + 1) * sizeof(float));
-  return need;
-}
-
-template <int M2>
-__device__ __forceinline__ void jacobi_fused_d(const JacobiFusedArgs& p, int m, int g, float* jsm) {
-  constexpr int B = M2 / 2, NT = B * B, KB = 1, NW = M2 / 16;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int C = p.C, nblk = C / B, npair = nblk / 2;
-  f32x2* SQ = reinterpret_cast<f32x2*>(jsm);
-  int bi, bj;
-  block_pair(g, p.step_d, nblk, bi, bj);
-  // the matrix' state words (done, floor) are read AFTER the block's data loads have been issued: a done matrix costs a few
-  // wasted loads, a live one no longer waits a memory round trip before it requests anything (round 3 phase stamps)
-  float floor_m = 0.f;
-  float my_off = 0.f, my_sig = 0.f, my_dm = 0.f;
-  bool finite = true;
-  float* Qo = p.Qw + ((size_t)m * npair + g) * (M2 * M2);
-  float* So = p.Sw + ((size_t)m * npair + g) * (M2 * M2);
-  if (p.first) {
-    if (p.st[m].done) return;
-    floor_m = p.st[m].floor;
-    const float* Am = p.Pr + (size_t)m * C * C;
-    const int PITCH = p.step_d >= 0 ? M2 : M2 + 1;
-    for (int e = tid; e < M2 * M2; e += NT) {
-      const int r = e / M2, c = e % M2;
-      f32x2 v;
-      v[0] = Am[(size_t)pair_index<B>(r, bi, bj) * C + pair_index<B>(c, bi, bj)];
-      v[1] = r == c ? 1.f : 0.f;
-      finite &= fabsf(v[0]) <= 3.0e38f;
-      if (r == c) my_dm = fmaxf(my_dm, fabsf(v[0]));
-      SQ[r * PITCH + c] = v;
-    }
-    __syncthreads();
-  } else {
-    // ---- look-ahead assembly (cross steps only: a segment never starts behind an intra step)
-    int g1, h1, g2, h2;
-    block_locate(bi, p.step_u, nblk, g1, h1);
-    block_locate(bj, p.step_u, nblk, g2, h2);
-    const float* S1 = p.Sr + ((size_t)m * npair + g1) * (M2 * M2);
-    const float* S2 = p.Sr + ((size_t)m * npair + g2) * (M2 * M2);
-    const bool same = g1 == g2;
-    // this thread's four image elements that come out of the previous images (requested before the staging loads)
-    float sv[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int e = tid + i * NT, r = e / M2, c = e % M2;
-      const bool rlo = r < B, clo = c < B;
-      const float* src = rlo ? S1 : S2;
-      const int rr = (rlo ? h1 : h2) * B + (rlo ? r : r - B);
-      const int cc = (clo ? h1 : h2) * B + (clo ? c : c - B);
-      sv[i] = (rlo == clo || same) ? src[rr * M2 + cc] : 0.f;
-    }
-    float* Xs = jsm;                                // [M2][M2 + 1]  tile (g1, g2) of the state before U(step_u)
-    float* Q1s = Xs + M2 * (M2 + 1);                // [M2][B + 1]   columns h1 of Q_g1
-    float* Q2s = Q1s + M2 * (B + 1);                // [M2][B + 1]   columns h2 of Q_g2
-    float* Ws = Q2s + M2 * (B + 1);                 // [B][M2 + 1]   Q_g1[:, h1]^T X
-    f32x4 xv = {0.f, 0.f, 0.f, 0.f}, qv = {0.f, 0.f, 0.f, 0.f};
-    const int se = tid * 4, sr = se / M2, sc = se % M2;
-    float* Qdst = nullptr;
-    if (!same) {
-      int b1i, b1j, b2i, b2j;
-      block_pair(g1, p.step_u, nblk, b1i, b1j);
-      block_pair(g2, p.step_u, nblk, b2i, b2j);
-      const float* Pm = p.Pr + (size_t)m * C * C;
-      xv = *reinterpret_cast<const f32x4*>(Pm + (size_t)pair_index<B>(sr, b1i, b1j) * C + pair_index<B>(sc, b2i, b2j));
-      // Q columns: M2 x B floats per side = NT / 2 float4 (the fragments mt of that half); first half of the block
-      // fetches Q_g1, second half Q_g2
-      const bool one = tid < NT / 2;
-      const int t2 = one ? tid : tid - NT / 2;
-      const int f = (one ? h1 : h2) * (NT / 2) + t2;
-      int qr, qc;
-      qfrag_rc<M2>(f, qr, qc);
-      qc -= (one ? h1 : h2) * B;
-      qv = *reinterpret_cast<const f32x4*>(p.Qr + ((size_t)m * npair + (one ? g1 : g2)) * (M2 * M2) + (size_t)f * 4);
-      Qdst = (one ? Q1s : Q2s) + qr * (B + 1) + qc;
-    }
-    if (p.st[m].done) return;        // (block-uniform)
-    floor_m = p.st[m].floor;
-    f32x4 crit = {0.f, 0.f, 0.f, 0.f};
-    if (!same) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) { Xs[sr * (M2 + 1) + sc + j] = xv[j]; Qdst[j * (B + 1)] = qv[j]; }
-      __syncthreads();
-      const int li = lane & 15, lq = lane >> 4;
-      if (wave < (B / 16) * NW) {                   // W = Q_g1[:, h1]^T X   (B x M2)
-        const int tr = wave / NW, tj = wave % NW;
-        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll 4
-        for (int kk = 0; kk < M2; kk += 4)
-          acc = __builtin_amdgcn_mfma_f32_16x16x4f32(Q1s[(kk + lq) * (B + 1) + 16 * tr + li], Xs[(kk + lq) * (M2 + 1) + 16 * tj + li], acc, 0, 0, 0);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) Ws[(16 * tr + 4 * lq + r) * (M2 + 1) + 16 * tj + li] = acc[r];
-      }
-      __syncthreads();
-      if (wave < (B / 16) * (B / 16)) {             // crit = W Q_g2[:, h2]   (B x B)
-        const int tr = wave / (B / 16), tc = wave % (B / 16);
-#pragma unroll 4
-        for (int kk = 0; kk < M2; kk += 4)
-          crit = __builtin_amdgcn_mfma_f32_16x16x4f32(Ws[(16 * tr + li) * (M2 + 1) + kk + lq], Q2s[(kk + lq) * (B + 1) + 16 * tc + li], crit, 0, 0, 0);
-      }
-      __syncthreads();                              // the staging area becomes the image
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int e = tid + i * NT, r = e / M2, c = e % M2;
-      if ((r < B) == (c < B) || same) {
-        f32x2 v; v[0] = sv[i]; v[1] = r == c ? 1.f : 0.f;
-        SQ[e] = v;
-        finite &= fabsf(sv[i]) <= 3.0e38f;
-        if (r == c) my_dm = fmaxf(my_dm, fabsf(sv[i]));
-      }
-    }
-    if (!same && wave < (B / 16) * (B / 16)) {
-      const int tr = wave / (B / 16), tc = wave % (B / 16), li = lane & 15, lq = lane >> 4;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int row = 16 * tr + 4 * lq + r, col = B + 16 * tc + li;
-        f32x2 v; v[0] = crit[r]; v[1] = 0.f;
-        SQ[row * M2 + col] = v;
-        SQ[col * M2 + row] = v;
-        finite &= fabsf(crit[r]) <= 3.0e38f;
-      }
-    }
-    __syncthreads();
-  }
-  if (p.step_d >= 0) {
-    jacobi_cross_sets_pw<M2>(reinterpret_cast<unsigned char*>(SQ), reinterpret_cast<unsigned char*>(jsm + 2 * M2 * M2), tid, floor_m, my_off, my_sig);
-    for (int e = tid; e < M2 * M2; e += NT) So[e] = SQ[e][0];
-    int qr, qc;
-    qfrag_rc<M2>(tid, qr, qc);                      // NT float4 = one tile, fragment order
-    f32x4 q;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) q[j] = SQ[(qr + j) * M2 + qc][1];
-    *reinterpret_cast<f32x4*>(Qo + (size_t)tid * 4) = q;
-    {  // fp16 hi / lo fragment unit `tid`
-      constexpr int NCH = M2 / 32;
-      const int l16 = tid & 63, part = (tid >> 6) & 1, cc = (tid >> 7) % NCH, mt = (tid >> 7) / NCH;
-      float x[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) x[j] = SQ[qfrag16_k<M2>(cc, l16 >> 4, j) * M2 + 16 * mt + (l16 & 15)][1];
-      half8 hi, lo;
-      split_f16x8(x, hi, lo);
-      *reinterpret_cast<half8*>(p.Qw16 + ((size_t)m * npair + g) * (2 * M2 * M2) + (size_t)tid * 8) = part ? lo : hi;
-    }
-  } else {
-    constexpr int PITCH = M2 + 1;
-    float* DO = jsm + 4 * M2 * PITCH;
-    const int cur = jacobi_sets<SWEEP_INTRA, M2, KB>(SQ, DO, tid, floor_m, my_off, my_sig);
-    for (int e = tid; e < M2 * M2; e += NT) So[e] = SQ[cur * M2 * PITCH + (e / M2) * PITCH + (e % M2)][0];
-    int qr, qc;
-    qfrag_rc<M2>(tid, qr, qc);
-    f32x4 q;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) q[j] = SQ[cur * M2 * PITCH + (qr + j) * PITCH + qc][1];
-    *reinterpret_cast<f32x4*>(Qo + (size_t)tid * 4) = q;
-    {
-      constexpr int NCH = M2 / 32;
-      const int l16 = tid & 63, part = (tid >> 6) & 1, cc = (tid >> 7) % NCH, mt = (tid >> 7) / NCH;
-      float x[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) x[j] = SQ[cur * M2 * PITCH + qfrag16_k<M2>(cc, l16 >> 4, j) * PITCH + 16 * mt + (l16 & 15)][1];
-      half8 hi, lo;
-      split_f16x8(x, hi, lo);
-      *reinterpret_cast<half8*>(p.Qw16 + ((size_t)m * npair + g) * (2 * M2 * M2) + (size_t)tid * 8) = part ? lo : hi;
-    }
-  }
-  if (!finite) my_off = __builtin_inff();
-  for (int o = 32; o > 0; o >>= 1) {
-    my_off = fmaxf(my_off, __shfl_xor(my_off, o, 64));
-    my_sig = fmaxf(my_sig, __shfl_xor(my_sig, o, 64));
-    my_dm = fmaxf(my_dm, __shfl_xor(my_dm, o, 64));
-  }
-  if ((tid & 63) == 0) {
-    if (my_off > 0.f) atomicMax(&p.st[m].offmax, __float_as_uint(my_off));
-    if (my_sig > 0.f) atomicMax(&p.st[m].offsig, __float_as_uint(my_sig));
-    if (my_dm > 0.f && my_dm < 3.0e38f) atomicMax(&p.st[m].dmax, __float_as_uint(my_dm));
-  }
-}
-
-// tasks of one matrix: [off-diagonal tiles g < h][diagonal tile copies][V tiles (row block, column pair)]
-template <int M2>
-__device__ __forceinline__ void jacobi_fused_u(const JacobiFusedArgs& p, int m, int task, float* jsm) {
-  constexpr int B = M2 / 2, PITCH = M2 + 1, NW = M2 / 16;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int C = p.C, nblk = C / B, npair = nblk / 2;
-  const int n_off = npair * (npair - 1) / 2;
-  const size_t cc = (size_t)C * C;
-  const int e4 = tid * 4, lr = e4 / M2, lc = e4 % M2;     // this thread's float4 of a staged tile
-  if (task >= n_off && task < n_off + npair) {            // diagonal tile g: the image D(step_u) left behind
-    const int g = task - n_off;
-    int gi, gj;
-    block_pair(g, p.step_u, nblk, gi, gj);
-    const f32x4 v = *reinterpret_cast<const f32x4*>(p.Sr + ((size_t)m * npair + g) * (M2 * M2) + e4);
-    *reinterpret_cast<f32x4*>(p.Pw + m * cc + (size_t)pair_index<B>(lr, gi, gj) * C + pair_index<B>(lc, gi, gj)) = v;
-    return;
-  }
-  const bool is_v = task >= n_off;               // (V tasks exist only in launches with_v)
-  int g, h;
-  if (is_v) { const int t = task - n_off - npair; g = t / npair; h = t % npair; }       // g = M2-row block of V
-  else { int t = task; g = 0; while (t >= npair - 1 - g) { t -= npair - 1 - g; ++g; } h = g + 1 + t; }
-  int hi, hj, gi = 0, gj = 0;
-  block_pair(h, p.step_u, nblk, hi, hj);
-  if (!is_v) block_pair(g, p.step_u, nblk, gi, gj);
-  float* Xs = jsm;
-  float* Qhs = Xs + M2 * PITCH;
-  float* Qgs = Qhs + M2 * PITCH;
-  {
-    const float* X = is_v ? p.V + m * cc : p.Pr + m * cc;
-    const int gr = is_v ? g * M2 + lr : pair_index<B>(lr, gi, gj);
-    const f32x4 xv = *reinterpret_cast<const f32x4*>(X + (size_t)gr * C + pair_index<B>(lc, hi, hj));
-    const f32x4 hv = *reinterpret_cast<const f32x4*>(p.Qr + ((size_t)m * npair + h) * (M2 * M2) + e4);
-    f32x4 gv = {0.f, 0.f, 0.f, 0.f};
-    if (!is_v) gv = *reinterpret_cast<const f32x4*>(p.Qr + ((size_t)m * npair + g) * (M2 * M2) + e4);
-    int qr, qc;
-    qfrag_rc<M2>(tid, qr, qc);                      // the rotations arrive in fragment order
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      Xs[lr * PITCH + lc + j] = xv[j];
-      Qhs[(qr + j) * PITCH + qc] = hv[j];
-      if (!is_v) Qgs[(qr + j) * PITCH + qc] = gv[j];
-    }
-  }
-  __syncthreads();
-  const int ti = wave / NW, tj = wave % NW, li = lane & 15, lq = lane >> 4;
-  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-  if (is_v) {
-    // (V Qh)^T = Qh^T V^T tile (column tile tj, rows 16 ti ..) exactly as jacobi_vstrip_kernel computes it -- the same
-    // split-fp16 operands, k-slots and order of the MFMAs -- so V comes out bit-identical whichever kernel updates it
-    constexpr int NCH = M2 / 32;
-    const half_t* q16 = p.Qr16 + ((size_t)m * npair + h) * (2 * M2 * M2);
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-      float x[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) x[j] = Xs[(16 * ti + li) * PITCH + qfrag16_k<M2>(c, lq, j)];
-      half8 bh, bl;
-      split_f16x8(x, bh, bl);
-      const half8 ah = *reinterpret_cast<const half8*>(q16 + ((size_t)((tj * NCH + c) * 2 + 0) * 64 + lane) * 8);
-      const half8 al = *reinterpret_cast<const half8*>(q16 + ((size_t)((tj * NCH + c) * 2 + 1) * 64 + lane) * 8);
-      acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, bh, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bl, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bh, acc, 0, 0, 0);
-    }
-  } else {
-#pragma unroll 4
-    for (int kk = 0; kk < M2; kk += 4)      // T = X Qh
-      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(Xs[(16 * ti + li) * PITCH + kk + lq], Qhs[(kk + lq) * PITCH + 16 * tj + li], acc, 0, 0, 0);
-  }
-  if (!is_v) {
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < 4; ++r) Xs[(16 * ti + 4 * lq + r) * PITCH + 16 * tj + li] = acc[r];
-    __syncthreads();
-    acc = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll 4
-    for (int kk = 0; kk < M2; kk += 4)      // Y = Qg^T T
-      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(Qgs[(kk + lq) * PITCH + 16 * ti + li], Xs[(kk + lq) * PITCH + 16 * tj + li], acc, 0, 0, 0);
-    float* Pw = p.Pw + m * cc;
-    const int col = pair_index<B>(16 * tj + li, hi, hj);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) Pw[(size_t)pair_index<B>(16 * ti + 4 * lq + r, gi, gj) * C + col] = acc[r];
-    // mirror tile (h, g): this lane's four rows are four consecutive columns there
-    *reinterpret_cast<f32x4*>(Pw + (size_t)col * C + pair_index<B>(16 * ti + 4 * lq, gi, gj)) = acc;
-  } else {
-    // lane (n, q), register r = (V Qh)[row 16 ti + n][column 16 tj + 4 q + r]: four consecutive columns
-    float* Vm = p.V + m * cc;
-    *reinterpret_cast<f32x4*>(Vm + (size_t)(g * M2 + 16 * ti + li) * C + pair_index<B>(16 * tj + 4 * lq, hi, hj)) = acc;
-  }
-}
-
-// grid: [nmat * npair pair problems (if has_d)] [ntask * nmat update tasks, task-major (if has_u)]
-template <int M2>
-__global__ __launch_bounds__((M2 / 2) * (M2 / 2), M2 == 64 ? 8 : 2) void jacobi_fused_kernel(JacobiFusedArgs p) {
+// grid: [nmat * npair pair problems (if has_d)] [ntask * nmat update tasks, task-major (if has_u)]; pair32::NT = 256 threads
+__global__ __launch_bounds__(256, 2) void jacobi_fused_kernel(JacobiFusedArgs p) {
   extern __shared__ __attribute__((aligned(16))) float jsm[];
-  constexpr int B = M2 / 2;
-  const int npair = p.C / B / 2;
+  const int npair = p.C / pair32::B / 2;
   const int n_d = p.has_d ? p.nmat * npair : 0;
   int b = blockIdx.x;
   if (b < n_d) {
     const int m = b / npair, g = b % npair;
-    jacobi_fused_d<M2>(p, m, g, jsm);               // (checks the matrix' done flag itself, after issuing its loads)
+    pair32::fused_d(p, m, g, jsm);                  // (checks the matrix' done flag itself, after issuing its loads)
   } else {
     b -= n_d;
     const int task = b / p.nmat, m = b % p.nmat;
     if (p.st[m].done) return;
-    jacobi_fused_u<M2>(p, m, task, jsm);
+    pair32::fused_u(p, m, task, jsm);
   }
 }
 
-namespace r4 {
-template <int M2, int LAY>
-static size_t fused_lds(int has_d, int has_u, int first, int step_d) {
-  static_assert(lds_bytes<64, 0>(1, 1, 0, 0) * 4 <= 160 * 1024, "four blocks of a {D, U} launch per CU");
-  return lds_bytes<M2, LAY>(has_d, has_u, first, step_d);
-}
-}  // namespace r4
-
-
-// grid: [nmat * npair pair problems (if has_d)] [ntask * nmat update tasks, task-major (if has_u)]; 256 threads
-template <int M2, int LAY>
-__global__ __launch_bounds__(r4::Lay<LAY>::NTD, 4) void jacobi_fused4_kernel(JacobiFusedArgs p) {
+// the same grid; pair64::NT = 256 threads
+__global__ __launch_bounds__(256, 4) void jacobi_fused4_kernel(JacobiFusedArgs p) {
   extern __shared__ __attribute__((aligned(16))) float jsm[];
-  constexpr int B = M2 / 2;
-  const int npair = p.C / B / 2;
+  const int npair = p.C / pair64::B / 2;
   const int n_d = p.has_d ? p.nmat * npair : 0;
   int b = blockIdx.x;
   if (b < n_d) {
     const int m = b / npair, g = b % npair;
-    r4::fused_d<M2, LAY>(p, m, g, jsm);
+    pair64::fused_d(p, m, g, jsm);
   } else {
     b -= n_d;
     const int task = b / p.nmat, m = b % p.nmat;
     if (p.st[m].done) return;
-    r4::fused_u<M2>(p, m, task, jsm);
+    pair64::fused_u(p, m, task, jsm);
   }
 }
+static_assert(pair32::NT == 256 && pair64::NT == 256, "the launch bounds above");
 
 // ---------------------------------------------------------------------------
-// V <- V Q for all the rotations of one launch segment, with V resident in REGISTERS (round 3).
+// V <- V Q for all the rotations of one launch segment, with V resident in REGISTERS (the V pass; 64-wide block pairs).
 // Updating V inside the tile update streams the whole of V through the chip at every outer step (64 % of the update's
 // traffic: 4 MB per 512-channel matrix and step), although nothing in the solver reads V.  Here a wave owns 16 rows of V
 // -- C/16 tiles of 16x16 held as MFMA accumulators, C/4 registers per lane -- and applies the rotation matrices of all
-// the steps of a segment (the Q log the pair problems wrote) without V leaving the registers:
-//   (V Q_h)^T = Q_h^T V^T is computed tile by tile with v_mfma_f32_16x16x4_f32; a 16x16 tile of V^T in the C/D layout
-//   (lane (n, q), register r  <->  V[row n][tile column 4 q + r]) is ALREADY the B operand of the k-step that covers the
-//   columns {4 q + r : q = 0..3}, so the old tiles feed the MFMAs straight from the accumulator registers, the results
-//   arrive in the same layout, and the only operand that is loaded is Q (fragment order: one 16-byte LDS read per
-//   four MFMAs; the tile of a pair is staged once per block, double-buffered).
+// the steps of a segment (the fp16 log the pair problems wrote) without V leaving the registers:
+//   (V Q_h)^T = Q_h^T V^T is computed tile by tile on split fp16 (see qfrag16_k, jacobi_dev.h); two 16x16 tiles of V^T in the
+//   C/D layout (lane (n, q), register r  <->  V[row n][tile column 4 q + r]) are ALREADY the B operand of a K-chunk, so the
+//   old tiles feed the MFMAs straight from the accumulator registers (split into hi + lo on the way), the results arrive
+//   in the same layout, and the only operand that is loaded is Q (fragment order: one 16-byte LDS read per fragment).
 // Register indices must be static: the strip is kept in POSITION order of the round-robin pairing (pair g = positions g
 // and NBLK-1-g; the intra step pairs positions 2g, 2g+1, natural order = the order of step 0); advancing one outer step
 // moves position pos+1 to pos (pos >= 1) and position 1 to NBLK-1 -- a static register rotation.
@@ -479,36 +73,36 @@ __global__ __launch_bounds__(r4::Lay<LAY>::NTD, 4) void jacobi_fused4_kernel(Jac
 // the next segment's pair problems (MFMA pipe and registers here, LDS and VALU there).
 // ---------------------------------------------------------------------------
 struct VStripArgs {
-  float* V; const half_t* Qlog;     // Qlog: [slot][nmat][npair][2*M2*M2] fp16 hi/lo fragments (qfrag16), slot = step - step_begin
+  float* V; const half_t* Qlog;     // Qlog: [slot][nmat][npair][2*M2*M2] fp16 hi/lo fragments (qfrag16_k), slot = step - step_begin
   const JacobiState* st;
   int C, nmat, step_begin, step_end, seg;
   int mat_major; // grid (nmat, strips) instead of (strips, nmat): see vstrip_launch
 };
 
-// Round 5: the rotation log reaches the block by LDS-DMA into a RING of VS_RING tiles (buffer_load_dwordx4 ... lds, 1 KiB per wave
-// instruction, no registers), VS_RING - 1 tiles ahead of the one in use.  Until round 4 a tile was requested four pairs ahead into
-// 64 VGPRs and parked in a two-tile LDS buffer: with ~2 us per access (the log streams from HBM: 64 MB per segment at 64 matrices)
-// and ~0.2 us of MFMA work per tile a block waited nine tenths of its life, and while it waits it holds a whole CU (414 registers
-// per lane: no pair-problem or update wave fits beside it) -- the V pass cost the solve a quarter of its time at batch 32 although
-// it runs on its own stream.  Protocol per tile q: s_waitcnt vmcnt((VS_RING - 2) x NDMA) retires this wave's share of tile q (the
-// counter is in order), the barrier makes it everybody's and retires slot (q - 1) % VS_RING, whose refill (tile q + VS_RING - 1)
-// is issued at once.  Past the end of the segment the refills re-fetch the last tile into slots nobody reads: the outstanding
-// count stays constant and so does the wait.
-// Round 5, last change: a block of the pass used to hold its CU alone (128 KB of ring, 398 registers per lane), and the launch that
-// opens the next segment waited for it (per-launch trace: 86-117 us for that launch against 25-35 alone).  With a ring of FIVE tiles
-// (80 KB) and the fragments of a tile requested one K-chunk ahead instead of all sixteen at once (364 registers) two pair-problem /
-// update blocks fit beside it on every CU: eigensolver 12.05 -> 11.55 ms per 32-pair step, 8.44 -> 7.9 at 16 pairs, frames identical
+// The rotation log reaches the block by LDS-DMA into a RING of VS_RING tiles (buffer_load_dwordx4 ... lds, 1 KiB per wave
+// instruction, no registers), VS_RING - 1 tiles ahead of the one in use: an access takes ~2 us (the log streams from HBM: 64 MB
+// per segment at 64 matrices) against ~0.2 us of MFMA work per tile, and while a block waits it holds its registers.  Protocol per
+// tile q: s_waitcnt vmcnt((VS_RING - 2) x NDMA) retires this wave's share of tile q (the counter is in order), the barrier makes it
+// everybody's and retires slot (q - 1) % VS_RING, whose refill (tile q + VS_RING - 1) is issued at once.  Past the end of the
+// segment the refills re-fetch the last tile into slots nobody reads: the outstanding count stays constant and so does the wait.
+// FIVE tiles (80 KB), and the fragments of a tile requested one K-chunk ahead instead of all sixteen at once (364 registers per
+// lane against 398): two pair-problem / update blocks fit beside a block of the pass on every CU, and the launch that opens the
+// next segment does not wait for it (per-launch trace: 86-117 us for that launch behind a pass that held its CU alone, 25-35
+// without): eigensolver 12.05 -> 11.55 ms per 32-pair step, 8.44 -> 7.9 at 16 pairs, frames identical
 // (profiles/r05_vstrip_coresident.txt: rings of 4 / 5 / 6 / 7 / 8 tiles = 11.86 / 11.55 / 11.60 / 11.78 / 11.88).
-constexpr int VS_RING = 5;
-template <int M2, int W>
-constexpr size_t vstrip_lds_bytes() { return (size_t)VS_RING * M2 * M2 * sizeof(float); }
+// Four waves a block, one per SIMD: 224 VGPRs + 72 AGPRs, no scratch (profiles/r06_vstrip_w4.txt).
+constexpr int VS_RING = 5, VS_WAVES = 4;
+constexpr size_t VS_LDS_BYTES = (size_t)VS_RING * pair64::FR * sizeof(float);   // a tile of fp16 hi / lo fragments = FR * 4 bytes
+static_assert(VS_LDS_BYTES == 81920, "the ring of the V pass");
 
-template <int M2, int NBLK, int W>
-__global__ __launch_bounds__(W * 64) void jacobi_vstrip_kernel(VStripArgs p) {
-  constexpr int B = M2 / 2, TB = B / 16, NCH = M2 / 32, NPAIR = NBLK / 2, FR = M2 * M2, C = NBLK * B;
+// NBLK = C / 32 column blocks: 8 and 16 (C = 256 and 512)
+template <int NBLK>
+__global__ __launch_bounds__(256) void jacobi_vstrip_kernel(VStripArgs p) {
+  constexpr int M2 = pair64::M2, B = pair64::B, NCH = pair64::NCH, FR = pair64::FR, W = VS_WAVES;
+  constexpr int TB = B / 16, NPAIR = NBLK / 2, C = NBLK * B;
   constexpr int TILE_BYTES = FR * 4;                       // fp16 hi / lo fragments of one rotation matrix
   constexpr int NDMA = TILE_BYTES / 1024 / W;              // 1-KiB DMA pieces per wave and tile
-  constexpr bool FRAGS_AHEAD = W <= 4;                     // one wave per SIMD: registers to hold a tile's 16 fragments at once
+  static_assert(W * 64 == 256, "the launch bound above");
   static_assert(NDMA >= 1 && NDMA * W * 1024 == TILE_BYTES, "a tile is a whole number of 1-KiB pieces per wave");
   extern __shared__ __attribute__((aligned(16))) unsigned char vs_ring[];
   const int m = p.mat_major ? blockIdx.x : blockIdx.y;
@@ -568,7 +162,7 @@ __global__ __launch_bounds__(W * 64) void jacobi_vstrip_kernel(VStripArgs p) {
     _Pragma("unroll") for (int mt = 0; mt < 2 * TB; ++mt)                                                            \
       _Pragma("unroll") for (int part = 0; part < 2; ++part)                                                         \
         fa[0][mt][part] = *reinterpret_cast<const half8*>(qb + (((mt * NCH + 0) * 2 + part) * 64 + lane) * 8);       \
-    if (FRAGS_AHEAD) __builtin_amdgcn_sched_barrier(0);   /* (two waves per SIMD: 256 registers -- let the compiler read just in time) */ \
+    __builtin_amdgcn_sched_barrier(0);                     /* (the order written here, not the scheduler's) */                        \
     half8 bh[NCH], bl[NCH];                                                                                          \
     _Pragma("unroll") for (int c = 0; c < NCH; ++c) {                                                                \
       /* tiles 2c, 2c+1 of the pair's 2 TB tiles: positions pa (tiles 0..TB-1) and pb (TB..2TB-1) */                 \
@@ -577,7 +171,7 @@ __global__ __launch_bounds__(W * 64) void jacobi_vstrip_kernel(VStripArgs p) {
       const float xx[8] = {x0[0], x0[1], x0[2], x0[3], x1[0], x1[1], x1[2], x1[3]};                                  \
       split_f16x8(xx, bh[c], bl[c]);                                                                                 \
     }                                                                                                                \
-    if (FRAGS_AHEAD) __builtin_amdgcn_sched_barrier(0);                                                              \
+    __builtin_amdgcn_sched_barrier(0);                                                                               \
     _Pragma("unroll") for (int c = 0; c < NCH; ++c) {                                                                \
       if (c + 1 < NCH) {                                   /* the next chunk's fragments under this chunk's MFMAs */ \
         _Pragma("unroll") for (int mt = 0; mt < 2 * TB; ++mt)                                                        \
@@ -587,9 +181,9 @@ __global__ __launch_bounds__(W * 64) void jacobi_vstrip_kernel(VStripArgs p) {
       _Pragma("unroll") for (int mt = 0; mt < 2 * TB; ++mt) out[mt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fa[c][mt][1], bh[c], out[mt], 0, 0, 0); \
       _Pragma("unroll") for (int mt = 0; mt < 2 * TB; ++mt) out[mt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fa[c][mt][0], bl[c], out[mt], 0, 0, 0); \
       _Pragma("unroll") for (int mt = 0; mt < 2 * TB; ++mt) out[mt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fa[c][mt][0], bh[c], out[mt], 0, 0, 0); \
-      if (FRAGS_AHEAD) __builtin_amdgcn_sched_barrier(0);                                                            \
+      __builtin_amdgcn_sched_barrier(0);                                                                             \
     }                                                                                                                \
-    if (FRAGS_AHEAD) __builtin_amdgcn_sched_barrier(0);                                                              \
+    __builtin_amdgcn_sched_barrier(0);                                                                               \
     _Pragma("unroll") for (int t = 0; t < TB; ++t) { v[(pa) * TB + t] = out[t]; v[(pb) * TB + t] = out[TB + t]; }    \
     ++q;                                                                                                             \
   }
@@ -997,7 +591,7 @@ static JacobiHost* jacobi_host() {
 // launch { D(step_d) writing log slot step_d - seg_begin, U(step_u) reading slot step_u - seg_begin }
 template <int M2>
 static void jacobi_fused_launch(JacobiGroup& G, int C, int seg_begin, bool has_d, int step_d, bool has_u, int step_u, bool first) {
-  constexpr int B = M2 / 2, NT = B * B;
+  constexpr int B = M2 / 2;
   const int npair = C / B / 2;
   const int ntask = npair * (npair - 1) / 2 + npair + (G.vstrip ? 0 : npair * npair);
   const size_t slot = (size_t)G.nmat * npair * M2 * M2;
@@ -1009,14 +603,14 @@ static void jacobi_fused_launch(JacobiGroup& G, int C, int seg_begin, bool has_d
   a.st = G.st; a.C = C; a.nmat = G.nmat; a.step_d = step_d; a.step_u = step_u;
   a.has_d = has_d; a.has_u = has_u; a.first = first; a.with_v = !G.vstrip; a.u_f16 = G.u_f16;
   const unsigned grid = (has_d ? G.nmat * npair : 0) + (has_u ? G.nmat * ntask : 0);
-  // round 4 (M2 = 64): pair problems resident in registers, strips over 4 waves (namespace r4, csrc/jacobi_dev.h; against an
-  // 8-wave layout and the round-3 kernel, eigensolver ms per step at batch 32 / 8 / 1: 14.4 / 7.6 / 6.0 vs 16.2 / 7.7 / 6.1 and
-  // 17.1 / 8.0 / 6.4 -- profiles/r04_jacobi_ab.txt); the 32-wide block pairs of C <= 128 keep the round-3 kernel
+  // M2 = 64: pair problems resident in registers, strips over 4 waves (jacobi_pair64.h; against an 8-wave layout and the LDS
+  // images of the 32-wide kernel at this width, eigensolver ms per step at batch 32 / 8 / 1: 14.4 / 7.6 / 6.0 vs 16.2 / 7.7 / 6.1
+  // and 17.1 / 8.0 / 6.4 -- profiles/r04_jacobi_ab.txt); the 32-wide block pairs keep the LDS images
   if constexpr (M2 == 64) {
-    hipLaunchKernelGGL((jacobi_fused4_kernel<M2, 0>), dim3(grid), dim3(r4::Lay<0>::NTD), (r4::fused_lds<M2, 0>(has_d, has_u, first, step_d)), G.stream, a);
+    hipLaunchKernelGGL(jacobi_fused4_kernel, dim3(grid), dim3(pair64::NT), pair64::lds_bytes(has_d, has_u, first, step_d), G.stream, a);
     LAUNCH_NOTE("jacobi_fused4_kernel");
   } else {
-    hipLaunchKernelGGL((jacobi_fused_kernel<M2>), dim3(grid), dim3(NT), jacobi_fused_lds<M2>(has_d, has_u, first, step_d), G.stream, a);
+    hipLaunchKernelGGL(jacobi_fused_kernel, dim3(grid), dim3(pair32::NT), pair32::lds_bytes(has_d, has_u, first, step_d), G.stream, a);
     LAUNCH_NOTE("jacobi_fused_kernel");
   }
   if (has_d) G.par ^= 1;
@@ -1033,16 +627,17 @@ static void vstrip_launch(const JacobiGroup& G, int C, int step_begin, int step_
   // and every one of the 8 L2s fetched every log from HBM.  With the MATRIX index running fastest (and a multiple of 8 matrices)
   // the strips of matrix m all run on XCD m % 8 and share its L2.
   a.mat_major = G.nmat % 8 == 0;
-#define VSTRIP_CASE(m2, nb, w) \
+  constexpr int W = VS_WAVES;
+#define VSTRIP_CASE(nb) \
   if (nblk == nb) {                                                                                                  \
-    const size_t vs_lds = (vstrip_lds_bytes<m2, w>());                                                               \
-    /* (every launch: cheap, idempotent, no per-device flag to race on -- ADVICE r5; a refusal is reported here) */   \
-    if (vs_lds > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(&jacobi_vstrip_kernel<m2, nb, w>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)vs_lds) != hipSuccess) \
+    /* the ring is above the 64 KiB a kernel gets unasked (every launch: cheap, idempotent, no per-device flag to race on; a  \
+       refusal is reported here) */                                                                                  \
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&jacobi_vstrip_kernel<nb>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)VS_LDS_BYTES) != hipSuccess) \
       LAUNCH_NOTE("jacobi_vstrip_kernel (hipFuncSetAttribute: dynamic LDS above 64 KiB)");                            \
-    hipLaunchKernelGGL((jacobi_vstrip_kernel<m2, nb, w>), a.mat_major ? dim3(G.nmat, C / 16 / w) : dim3(C / 16 / w, G.nmat), dim3(w * 64), vs_lds, s, a); \
+    hipLaunchKernelGGL(jacobi_vstrip_kernel<nb>, a.mat_major ? dim3(G.nmat, C / 16 / W) : dim3(C / 16 / W, G.nmat), dim3(W * 64), VS_LDS_BYTES, s, a); \
     LAUNCH_NOTE("jacobi_vstrip_kernel");                                                                             \
   }
-  VSTRIP_CASE(64, 16, 4) VSTRIP_CASE(64, 8, 4)
+  VSTRIP_CASE(16) VSTRIP_CASE(8)
 #undef VSTRIP_CASE
 }
 
@@ -1178,8 +773,6 @@ static int jacobi_make_group(JacobiGroup* G, float* A, float* V, int C, int nmat
 static bool jacobi_wide_pairs(int C) { return C % 64 == 0 && C >= 256; }
 
 static int jacobi_dispatch(JacobiGroup& G, int C) {
-  // (the round-2 two-launch steps -- separate pair-problem and tile-update kernels -- were deleted in round 4: the
-  //  look-ahead launches have been the only path since round 3)
   const bool m64 = jacobi_wide_pairs(C);
   const int rc = m64 ? jacobi_run_fused<64>(G, C) : jacobi_run_fused<32>(G, C);
   const int noted = launch_rc_take();  // a launch one of the train's void helpers saw refused (named there); cleared on every exit
@@ -1187,7 +780,7 @@ static int jacobi_dispatch(JacobiGroup& G, int C) {
 }
 
 // Eigenpair j of a plain solve is the one that grew out of coordinate j.  The 32-wide path keeps that by construction; on the
-// 64-wide path every sweep's intra step (r4::intra_wave: odd-even transposition WITH EXCHANGE) leaves the 32 columns of each
+// 64-wide path every sweep's intra step (pair64::intra_wave: odd-even transposition WITH EXCHANGE) leaves the 32 columns of each
 // block in reverse order, so after an odd number of sweeps column b * 32 + j of V (and diagonal entry b * 32 + j of A) belongs to
 // coordinate b * 32 + 31 - j -- a matrix that was diagonal to begin with came back with a permutation for V.  This puts the
 // columns and the eigenvalues back (a pure exchange: no value changes; only the diagonal of A is an output, its off-diagonal

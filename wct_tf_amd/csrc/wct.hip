@@ -13,7 +13,7 @@
 // eigh.hip, K6 in spectral.hip; this file holds K7, the workspace carve, the slot plans and the transforms themselves (launch_wct, the
 // style mix, AdaIN); spatial control is mask.hip, style-swap style_swap.hip.  What the units share: wct_stages.h.
 #include "wct_stages.h"
-#include "jacobi_dev.h"   // JacobiState alone: carve() sizes the solver's state words
+#include "jacobi_dev.h"   // (JacobiState: carve() sizes the solver's state words)
 #include "strength_rule.h"
 #include <algorithm>
 #include <type_traits>
