@@ -266,7 +266,7 @@ __global__ __launch_bounds__(256) void jacobi_init_kernel(const float* A, float*
 // State of a matrix AFTER a sweep, measured on the matrix itself: means of squared cosines e^2 / (d_p d_q) of the
 // off-diagonal residual E.  A squared cosine is at once the relative perturbation E still causes in the smaller
 // eigenvalue of the pair (what decides on which side of the reference's 1e-5 cut-off it falls, and how accurate its
-// gain is) and the size of the first-order term F o E of a spectral function against f(D) (spectral_matrix_kernel).
+// gain is) and the size of the first-order term F o E of a spectral function against f(D) (spectral_open_all_kernel).
 //   STRICT (decides when to stop; what the reference's spectral functions need): both diagonals above the cut-off:
 //     the squared cosine; one above, one below: the squared angle e^2 / big^2 plus the contamination of the dropped
 //     direction, 0.01 e^2 / (big 1e-5) (it has to stay below the cut-off); both below: nothing (both are dropped).

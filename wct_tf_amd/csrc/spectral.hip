@@ -1,5 +1,5 @@
-// K6 of the whiten-colour transform (the stage list: wct.hip): the spectral functions of the solved covariances, one matrix
-// at a time (style-swap) and for all matrices of a level in merged launches (the transforms), and the refresh before them.
+// K6 of the whiten-colour transform (the stage list: wct.hip): the spectral functions of the solved covariances, for all
+// matrices of a level in merged launches (the transforms and style-swap alike), and the refresh before them.
 #include "wct_stages.h"
 
 // ---------------------------------------------------------------------------
@@ -14,7 +14,7 @@
 // else l^-1/2 | l^1/2 (wct_tf), (l + eps)^-1/2 | (l + eps)^1/2 (wct_np).  The divided differences of l^+-1/2 have
 // closed forms without cancellation: -1 / (sa sb (sa + sb)) and 1 / (sa + sb) with sa = sqrt(a), sb = sqrt(b);
 // across the cut-off (one eigenvalue kept, one dropped) F_pq = f(d_kept) / (d_kept - d_dropped).
-// `kind`: 0 whitening gain l^-1/2, 1 colouring gain l^1/2.   G [nmat][C][C], matrix m of A / G at stride `stride`.
+// `kind`: 0 whitening gain l^-1/2, 1 colouring gain l^1/2.   G [nmat][C][C], as A.
 // Round 6: the expansion is one in the squared cosines e^2 / (d_p d_q), and it is only used where it converges.  The sweeps may
 // stop with pairs that are NOT resolved: the rounding-noise diagonals of a rank-deficient covariance (N < C pixels) never settle
 // against each other (the lenient rule of jacobi_check_end lets such a matrix go), and when the feature scale puts that noise
@@ -66,7 +66,7 @@ __device__ __forceinline__ float spectral_entry(float dp, float dq, float e, boo
   return e * fk / fmaxf(dk - dd, 2.f * fabsf(e));
 }
 
-// The three elementwise passes over a matrix in 64 x 64 TILES (round 4).  Written element by element (round 3) every
+// The elementwise passes over a matrix in 64 x 64 TILES (round 4).  Written element by element (round 3) every
 // output read two diagonal entries (a gather with stride C + 1: one cache line per thread) and the mirrored entry
 // (a column walk), ~1.4 ms per 32-pair step for three kernels that move 100 MB each.  A block now parks the two
 // diagonal segments of its tile and the MIRROR tile in LDS (rows loaded coalesced, read transposed), so every global
@@ -75,7 +75,11 @@ struct SpectralTile {
   float dp[64], dq[64];          // diagonal entries of the tile's rows / columns
   float mt[64][65];              // mirror tile: mt[c][r] = A[q0 + c][p0 + r]
 };
-__device__ __forceinline__ void spectral_tile_load(SpectralTile& t, const float* Am, int C, int p0, int q0, int tid) {
+// (`used`: spectral_open_all_kernel is the only caller left, and hipcc's link-time passes then specialise this function on that
+// kernel's tile BEFORE they inline it -- measured: equivalent instructions, the two diagonal stores arranged differently, but
+// not the kernel text that tools/kernel_isa_diff.py pins.  Kept whole, it is inlined as it always was; the price is an
+// uncalled copy of it in the code object.)
+__attribute__((used)) __device__ __forceinline__ void spectral_tile_load(SpectralTile& t, const float* Am, int C, int p0, int q0, int tid) {
   if (tid < 64) t.dp[tid] = p0 + tid < C ? Am[(size_t)(p0 + tid) * C + p0 + tid] : 0.f;
   else if (tid < 128) t.dq[tid - 64] = q0 + tid - 64 < C ? Am[(size_t)(q0 + tid - 64) * C + q0 + tid - 64] : 0.f;
   const int ty = tid >> 4, tx = tid & 15;
@@ -89,32 +93,21 @@ __device__ __forceinline__ void spectral_tile_load(SpectralTile& t, const float*
   }
 }
 
-// grid (C / 64, C / 64, nbatch): tile rows p0 = 64 blockIdx.y, columns q0 = 64 blockIdx.x
-__global__ __launch_bounds__(256) void spectral_matrix_kernel(const float* A, float* G, int C, size_t stride, int kind, float shift, int correct) {
-  __shared__ SpectralTile t;
-  const int m = blockIdx.z, p0 = blockIdx.y * 64, q0 = blockIdx.x * 64, tid = threadIdx.x;
-  __shared__ float cutred[4];
-  const float* Am = A + m * stride;
-  float* Gm = G + m * stride;
-  const float cut = spectral_cut(Am, C, tid, cutred);
-  spectral_tile_load(t, Am, C, p0, q0, tid);
-  __syncthreads();
-  const int ty = tid >> 4, tx = tid & 15;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int pl = ty * 4 + i, p = p0 + pl, q = q0 + tx * 4;
-    if (p >= C || q >= C) continue;
-    const f32x4 a = *reinterpret_cast<const f32x4*>(Am + (size_t)p * C + q);
-    f32x4 g;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      // the two triangles agree to round-off; their mean keeps G exactly symmetric
-      const float e = correct ? 0.5f * (a[j] + t.mt[tx * 4 + j][pl]) : 0.f;
-      g[j] = spectral_entry(t.dp[pl], t.dq[tx * 4 + j], e, p == q + j, kind, shift, cut);
-    }
-    *reinterpret_cast<f32x4*>(Gm + (size_t)p * C + q) = g;
-  }
-}
+// ---- round 5: the transform tail in MERGED launches.  Until round 4 every level ran the chain spectral_matrix -> prep2 ->
+// products -> add2 -> V G -> (V G) V^T twice, content side then style side (13 launches), then T = Tcs Tw, a memset, the blend
+// and the apply: 17 launches per level, most of them a few microseconds of work on half the matrices.  Here one launch of each
+// kind covers all 2P matrices of the level (matrix m = 2 pair + side; kind = m & 1: 0 whitening, 1 colouring), the first-order
+// matrix and the second-order operands come out of ONE pass over the tile, the blend rides on the epilogue of T = Tcs Tw
+// (gemm_f32_kernel), and the pass that opens the chain also clears mabs and writes the bias vector: 8 launches per level.
+// These two kernels hold the only copy of the per-element arithmetic: style-swap's three functions run through them too.
+struct SpecAllArgs {
+  const float* A;            // [2P][C][C] rotated covariances (diagonal = eigenvalues, off-diagonal = residual)
+  float* G;                  // [2P][C][C]
+  float *N, *R, *Pm;         // N [2P][C][C]; R, Pm [P][C][C] (whitening side only)
+  const float *X1, *X2;      // add2: X1 [P][C][C], X2 [2P][C][C]
+  int C; float shift; int correct, second; WctSkip skip;
+  unsigned* mabs; const float* mean; float* bias; float alpha; int mode;     // per-pair housekeeping of the opening pass
+};
 
 // Second-order term of the same expansion (round 3):  (L2)_pq = sum_k f[d_p, d_k, d_q] E_pk E_kq  with the second divided
 // differences of the spectral functions, which have closed forms without cancellation (sa = sqrt(a + shift) ...):
@@ -127,120 +120,7 @@ __global__ __launch_bounds__(256) void spectral_matrix_kernel(const float* A, fl
 // (checked against an exact eigendecomposition in NumPy: the error of f(D + E) drops from ~r^2 to ~r^3).  Only the block
 // of kept eigenvalues takes part: a dropped direction's couplings are bounded by sqrt(1e-5 d_p) tol and enter squared.
 // It lets the sweeps stop one sweep earlier for the same transform error (profiles/r03_eig_calibration.txt).
-__global__ __launch_bounds__(256) void spectral_prep2_kernel(const float* A, float* N, float* R, float* Pm, int C, size_t stride, int kind, float shift) {
-  __shared__ SpectralTile t;
-  const int m = blockIdx.z, p0 = blockIdx.y * 64, q0 = blockIdx.x * 64, tid = threadIdx.x;
-  const size_t cc = (size_t)C * C;
-  __shared__ float cutred[4];
-  const float* Am = A + m * stride;
-  const float cut = spectral_cut(Am, C, tid, cutred);
-  spectral_tile_load(t, Am, C, p0, q0, tid);
-  __syncthreads();
-  const int ty = tid >> 4, tx = tid & 15;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int pl = ty * 4 + i, p = p0 + pl, k0 = q0 + tx * 4;
-    if (p >= C || k0 >= C) continue;
-    const f32x4 a = *reinterpret_cast<const f32x4*>(Am + (size_t)p * C + k0);
-    const float dp = t.dp[pl];
-    f32x4 n4 = {0.f, 0.f, 0.f, 0.f}, r4 = n4, p4 = n4;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const float dk = t.dq[tx * 4 + j];
-      const float e = 0.5f * (a[j] + t.mt[tx * 4 + j][pl]);
-      if (p != k0 + j && dp > cut && dk > cut && pair_resolved(dp, dk, e)) {
-        const float sp = sqrtf(dp + shift), sk = sqrtf(dk + shift);
-        n4[j] = e / (sp + sk);
-        r4[j] = e / sk;
-        p4[j] = n4[j] / sk;
-      }
-    }
-    const size_t o = m * cc + (size_t)p * C + k0;
-    *reinterpret_cast<f32x4*>(N + o) = n4;
-    if (kind == 0) { *reinterpret_cast<f32x4*>(R + o) = r4; *reinterpret_cast<f32x4*>(Pm + o) = p4; }
-  }
-}
-
-__global__ __launch_bounds__(256) void spectral_add2_kernel(const float* A, float* G, const float* X1, const float* X2, int C, size_t stride, int kind, float shift) {
-  __shared__ float dps[64], dqs[64];
-  __shared__ float x1t[64][65], x2t[64][65];       // mirror tiles of X1 (kind 0 only), X2
-  const int m = blockIdx.z, p0 = blockIdx.y * 64, q0 = blockIdx.x * 64, tid = threadIdx.x;
-  const size_t cc = (size_t)C * C;
-  const float* Am = A + m * stride;
-  float* Gm = G + m * stride;
-  // a matrix with an eigenvalue within half a decade of the cut-off keeps the first-order completion and the old stop
-  // threshold (jacobi_resid_kernel weighs its residual accordingly): around the cut-off sit the noise directions of
-  // rank-deficient covariances, whose mutual couplings never become small, and a second-order sum over them is noise
-  int near = 0;
-  for (int i = tid; i < C; i += 256) {
-    const float d = fabsf(Am[(size_t)i * C + i]);
-    near |= (d > 3.3e-6f) & (d < 3e-5f);
-  }
-  if (__syncthreads_or(near)) return;
-  __shared__ float cutred[4];
-  const float cut = spectral_cut(Am, C, tid, cutred);
-  if (tid < 64) dps[tid] = p0 + tid < C ? Am[(size_t)(p0 + tid) * C + p0 + tid] : 0.f;
-  else if (tid < 128) dqs[tid - 64] = q0 + tid - 64 < C ? Am[(size_t)(q0 + tid - 64) * C + q0 + tid - 64] : 0.f;
-  const int ty = tid >> 4, tx = tid & 15;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int r = q0 + ty * 4 + i, c = p0 + tx * 4;
-    f32x4 v1 = {0.f, 0.f, 0.f, 0.f}, v2 = v1;
-    if (r < C && c < C) {
-      v2 = *reinterpret_cast<const f32x4*>(X2 + m * cc + (size_t)r * C + c);
-      if (kind == 0) v1 = *reinterpret_cast<const f32x4*>(X1 + m * cc + (size_t)r * C + c);
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) { x2t[ty * 4 + i][tx * 4 + j] = v2[j]; x1t[ty * 4 + i][tx * 4 + j] = v1[j]; }
-  }
-  __syncthreads();
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int pl = ty * 4 + i, p = p0 + pl, q = q0 + tx * 4;
-    if (p >= C || q >= C) continue;
-    const size_t o = (size_t)p * C + q;
-    const f32x4 x2 = *reinterpret_cast<const f32x4*>(X2 + m * cc + o);
-    f32x4 x1 = {0.f, 0.f, 0.f, 0.f};
-    if (kind == 0) x1 = *reinterpret_cast<const f32x4*>(X1 + m * cc + o);
-    f32x4 g = *reinterpret_cast<const f32x4*>(Gm + o);
-    const float dp = dps[pl];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const float dq = dqs[tx * 4 + j];
-      if (!(dp > cut && dq > cut)) continue;
-      const float sp = sqrtf(dp + shift), sq = sqrtf(dq + shift);
-      float l2;
-      if (kind == 1) l2 = -0.5f * (x2[j] + x2t[tx * 4 + j][pl]) / (sp + sq);
-      else l2 = (0.5f * (x1[j] + x1t[tx * 4 + j][pl]) + 0.25f * (sp + sq) * (x2[j] + x2t[tx * 4 + j][pl])) / (sp * sq * (sp + sq));
-      g[j] += l2;
-    }
-    *reinterpret_cast<f32x4*>(Gm + o) = g;
-  }
-}
-
-// ---- round 5: the transform tail in MERGED launches.  Until round 4 every level ran the chain spectral_matrix -> prep2 ->
-// products -> add2 -> V G -> (V G) V^T twice, content side then style side (13 launches), then T = Tcs Tw, a memset, the blend
-// and the apply: 17 launches per level, most of them a few microseconds of work on half the matrices.  Here one launch of each
-// kind covers all 2P matrices of the level (matrix m = 2 pair + side; kind = m & 1: 0 whitening, 1 colouring), the first-order
-// matrix and the second-order operands come out of ONE pass over the tile, the blend rides on the epilogue of T = Tcs Tw
-// (gemm_f32_kernel), and the pass that opens the chain also clears mabs and writes the bias vector: 8 launches per level.
-// The per-element arithmetic exists TWICE and must be kept in step by hand (sharing it as inlined tile bodies was tried when
-// the units were split: hipcc then schedules the two _all kernels differently, so the copies stayed).  What to compare, as text:
-//   * spectral_open_all_kernel's tile loop = spectral_matrix_kernel's (e, spectral_entry) + spectral_prep2_kernel's (the
-//     condition under `second`, n4 / r4 / p4), with em for e, a.shift for shift, a.correct for correct;
-//   * spectral_add2_all_kernel from `int near = 0;` to its end = spectral_add2_kernel from the same line, with a.shift for
-//     shift and X1 / X2 already offset to the matrix (X1 at pair * cc there, m * cc here);
-//   * spectral_cut, spectral_entry, pair_resolved and spectral_tile_load are shared already.
-// tests/test_gpu_ops.py (style-swap against the oracle) and the transform tests cover one copy each, not their agreement.
-struct SpecAllArgs {
-  const float* A;            // [2P][C][C] rotated covariances (diagonal = eigenvalues, off-diagonal = residual)
-  float* G;                  // [2P][C][C]
-  float *N, *R, *Pm;         // N [2P][C][C]; R, Pm [P][C][C] (whitening side only)
-  const float *X1, *X2;      // add2: X1 [P][C][C], X2 [2P][C][C]
-  int C; float shift; int correct, second; WctSkip skip;
-  unsigned* mabs; const float* mean; float* bias; float alpha; int mode;     // per-pair housekeeping of the opening pass
-};
-
+// grid (C / 64, C / 64, 2P): tile rows p0 = 64 blockIdx.y, columns q0 = 64 blockIdx.x
 __global__ __launch_bounds__(256) void spectral_open_all_kernel(SpecAllArgs a) {
   __shared__ SpectralTile t;
   const int m = blockIdx.z, p0 = blockIdx.y * 64, q0 = blockIdx.x * 64, tid = threadIdx.x;
@@ -303,7 +183,10 @@ __global__ __launch_bounds__(256) void spectral_add2_all_kernel(SpecAllArgs a) {
   float* Gm = a.G + m * cc;
   const float* X2 = a.X2 + m * cc;
   const float* X1 = a.X1 + (size_t)(m >> 1) * cc;
-  int near = 0;                                     // (see spectral_add2_kernel)
+  // a matrix with an eigenvalue within half a decade of the cut-off keeps the first-order completion and the old stop
+  // threshold (jacobi_resid_kernel weighs its residual accordingly): around the cut-off sit the noise directions of
+  // rank-deficient covariances, whose mutual couplings never become small, and a second-order sum over them is noise
+  int near = 0;
   for (int i = tid; i < C; i += 256) {
     const float d = fabsf(Am[(size_t)i * C + i]);
     near |= (d > 3.3e-6f) & (d < 3e-5f);
@@ -350,68 +233,36 @@ __global__ __launch_bounds__(256) void spectral_add2_all_kernel(SpecAllArgs a) {
   }
 }
 
-// out[b] = V[b] G[b] V[b]^T for nbatch matrices (strides in elements); X: scratch of the same shape as G
-// scratch2: 5 * nbatch * C * C floats for the second-order completion (or null: first order at most)
-int launch_spectral_function(const float* A, const float* V, float* G, float* X, float* out, int C, int nbatch,
-                                    size_t stride, size_t out_stride, int kind, float shift, hipStream_t s, float* scratch2) {
-  const size_t cc = (size_t)C * C;
-  const dim3 tiles(cdiv(C, 64), cdiv(C, 64), nbatch);
-  hipLaunchKernelGGL(spectral_matrix_kernel, tiles, dim3(256), 0, s, A, G, C, stride, kind, shift, EIG_CORRECT);
-  HIP_TRY(hipGetLastError());
-  if (scratch2 && EIG_CORRECT >= 2) {
-    float* N = scratch2; float* R = N + nbatch * cc; float* Pm = R + nbatch * cc; float* X1 = Pm + nbatch * cc; float* X2 = X1 + nbatch * cc;
-    hipLaunchKernelGGL(spectral_prep2_kernel, tiles, dim3(256), 0, s, A, N, R, Pm, C, stride, kind, shift);
-    HIP_TRY(hipGetLastError());
-    GemmArgs a = {};   // X2 = (kind 1: N, kind 0: P) N
-    a.A = kind == 1 ? N : Pm; a.lda = C; a.a_kmajor = 0; a.B = N; a.ldb = C; a.b_kmajor = 1; a.sA = a.sB = cc;
-    a.M = C; a.N = C; a.K = C; a.ksplit = C; a.out32 = X2; a.ldo = C; a.s_out = cc;
-    int rc2 = launch_gemm(a, 1, nbatch, s);
-    if (rc2) return rc2;
-    if (kind == 0) {
-      a.A = R; a.out32 = X1;   // X1 = R N
-      if ((rc2 = launch_gemm(a, 1, nbatch, s))) return rc2;
-    }
-    hipLaunchKernelGGL(spectral_add2_kernel, tiles, dim3(256), 0, s, A, G, X1, X2, C, stride, kind, shift);
-    HIP_TRY(hipGetLastError());
-  }
-  GemmArgs g = {};   // X = V G
-  g.A = V; g.lda = C; g.a_kmajor = 0; g.B = G; g.ldb = C; g.b_kmajor = 1; g.sA = g.sB = stride;
-  g.M = C; g.N = C; g.K = C; g.ksplit = C; g.out32 = X; g.ldo = C; g.s_out = stride;
-  int rc = launch_gemm(g, 1, nbatch, s);
-  if (rc) return rc;
-  GemmArgs h = {};   // out = X V^T
-  h.A = X; h.lda = C; h.a_kmajor = 0; h.B = V; h.ldb = C; h.b_kmajor = 0; h.sA = h.sB = stride;
-  h.M = C; h.N = C; h.K = C; h.ksplit = C; h.out32 = out; h.ldo = C; h.s_out = out_stride;
-  return launch_gemm(h, 1, nbatch, s);
+// what the C x C products over the matrices of a level have in common; the operands, their layouts and the output are the caller's
+static GemmArgs level_product(int C, WctSkip skip) {
+  GemmArgs g = {};
+  g.lda = g.ldb = g.ldo = C; g.M = g.N = g.K = g.ksplit = C; g.sA = g.sB = g.s_out = (size_t)C * C; g.skip = skip;
+  return g;
 }
 
 // refresh (see refresh_needed): X = A0 V, then A <- V^T X, for the matrices whose kept spectrum reaches 4 decades below their
 // norm; the others' blocks exit at once.  Before ANY spectral function of the tracked (A, V): launch_wct's apply stage and the
 // three of launch_style_swap (relu5_1, C = 512: every input of 352 x 352 or smaller has N < C -- the rank-deficient case).
-// always: every matrix, whatever its spectrum (measured for style-swap when the solver's tile update moved to split fp16: the
-// 3 of 900 patch matches that flipped on the 32 x 32 test case flipped with the rotated matrix recomputed as well -- it is V, not
-// the tracked matrix, that carries the difference; the switch stays for experiments).
-int launch_refresh(const WctCarve& w, int C, int P, WctSkip skip, hipStream_t s, bool always) {
-  const size_t cc = (size_t)C * C;
+// Refreshing EVERY matrix, whatever its spectrum, was measured for style-swap when the solver's tile update moved to split fp16:
+// the 3 of 900 patch matches that flipped on the 32 x 32 test case flipped with the rotated matrix recomputed as well -- it is V,
+// not the tracked matrix, that carries the difference.
+static int launch_refresh(const WctCarve& w, int C, int P, WctSkip skip, hipStream_t s) {
   int rc;
-  GemmArgs r1 = {};
-  r1.A = w.A0; r1.lda = C; r1.a_kmajor = 0; r1.B = w.V; r1.ldb = C; r1.b_kmajor = 1; r1.sA = r1.sB = cc; r1.skip = skip;
-  r1.M = C; r1.N = C; r1.K = C; r1.ksplit = C; r1.out32 = w.X; r1.ldo = C; r1.s_out = cc;
-  if (!always) { r1.mask_diag = w.A; r1.s_mask = cc; r1.mask_out = w.refresh; }
+  GemmArgs r1 = level_product(C, skip);
+  r1.A = w.A0; r1.a_kmajor = 0; r1.B = w.V; r1.b_kmajor = 1; r1.out32 = w.X;
+  r1.mask_diag = w.A; r1.s_mask = (size_t)C * C; r1.mask_out = w.refresh;
   if ((rc = launch_gemm(r1, 1, 2 * P, s))) return rc;
-  GemmArgs r2 = {};
-  r2.A = w.V; r2.lda = C; r2.a_kmajor = 1; r2.B = w.X; r2.ldb = C; r2.b_kmajor = 1; r2.sA = r2.sB = cc; r2.skip = skip;
-  r2.M = C; r2.N = C; r2.K = C; r2.ksplit = C; r2.out32 = w.A; r2.ldo = C; r2.s_out = cc;
-  if (!always) r2.mask_in = w.refresh;
-  rc = launch_gemm(r2, 1, 2 * P, s);
-  return rc;
+  GemmArgs r2 = level_product(C, skip);
+  r2.A = w.V; r2.a_kmajor = 1; r2.B = w.X; r2.b_kmajor = 1; r2.out32 = w.A; r2.mask_in = w.refresh;
+  return launch_gemm(r2, 1, 2 * P, s);
 }
 
 // The spectral tail of a level, all 2P matrices in merged launches: Tw / Tcs [m] = V f(A) V^T (whitening for the even matrices,
 // colouring for the odd ones), plus the bias vectors and cleared mabs words of the opening pass.  nwhite: the pairs whose
-// whitening side is live (P; 1 for a style mix, whose content is matrix 0 alone).
-int launch_spectral_tail(const WctCarve& w, int C, int P, float alpha, int mode, float eps_in, WctSkip skip, int nwhite,
-                                hipStream_t s) {
+// whitening side is live (P; 1 for a style mix, whose content is matrix 0 alone).  This is the tail behind its refresh: on
+// its own for a second run over matrices that have had theirs (style-swap's style whitening).
+int launch_spectral_tail_refreshed(const WctCarve& w, int C, int P, float alpha, int mode, float eps_in, WctSkip skip, int nwhite,
+                                   hipStream_t s) {
   int rc;
   const size_t cc = (size_t)C * C;
   // Tw = Vc f_c(Ac) Vc^T, Tcs = Vs f_s(As) Vs^T with the first- and second-order completion of f on the residual
@@ -420,7 +271,6 @@ int launch_spectral_tail(const WctCarve& w, int C, int P, float alpha, int mode,
   const float shift = mode == WCT_MODE_NP ? (eps_in >= 0.f ? eps_in : 1e-5f) : 0.f;
   const int second = EIG_CORRECT >= 2;
   const dim3 tiles(cdiv(C, 64), cdiv(C, 64), 2 * P);
-  if ((rc = launch_refresh(w, C, P, skip, s))) return rc;
   SpecAllArgs sa = {};
   sa.A = w.A; sa.G = w.G; sa.C = C; sa.shift = shift; sa.correct = EIG_CORRECT; sa.second = second; sa.skip = skip;
   sa.N = w.S2; float* X2 = sa.N + 2 * P * cc; sa.R = X2 + 2 * P * cc; sa.Pm = sa.R + P * cc; float* X1 = sa.Pm + P * cc;
@@ -429,25 +279,25 @@ int launch_spectral_tail(const WctCarve& w, int C, int P, float alpha, int mode,
   hipLaunchKernelGGL(spectral_open_all_kernel, tiles, dim3(256), 0, s, sa);
   HIP_TRY(hipGetLastError());
   if (second) {
-    GemmArgs a = {};   // X2[m] = (colouring: N[m], whitening: Pm[pair]) . N[m]
-    a.A = sa.Pm; a.sA = cc; a.A_odd = sa.N + cc; a.sA_odd = 2 * cc; a.lda = C; a.a_kmajor = 0;
-    a.B = sa.N; a.ldb = C; a.b_kmajor = 1; a.sB = cc; a.skip = skip;
-    a.M = C; a.N = C; a.K = C; a.ksplit = C; a.out32 = X2; a.ldo = C; a.s_out = cc;
+    GemmArgs a = level_product(C, skip);   // X2[m] = (colouring: N[m], whitening: Pm[pair]) . N[m]
+    a.A = sa.Pm; a.A_odd = sa.N + cc; a.sA_odd = 2 * cc; a.a_kmajor = 0; a.B = sa.N; a.b_kmajor = 1; a.out32 = X2;
     if ((rc = launch_gemm(a, 1, 2 * P, s))) return rc;
-    GemmArgs b = {};   // X1[pair] = R[pair] . N[2 pair]   (whitening side only)
-    b.A = sa.R; b.sA = cc; b.lda = C; b.a_kmajor = 0; b.B = sa.N; b.ldb = C; b.b_kmajor = 1; b.sB = 2 * cc;
-    b.M = C; b.N = C; b.K = C; b.ksplit = C; b.out32 = X1; b.ldo = C; b.s_out = cc;
+    GemmArgs b = level_product(C, WCT_SKIP_NONE);   // X1[pair] = R[pair] . N[2 pair]   (whitening side only)
+    b.A = sa.R; b.a_kmajor = 0; b.B = sa.N; b.b_kmajor = 1; b.sB = 2 * cc; b.out32 = X1;
     if (nwhite > 0 && (rc = launch_gemm(b, 1, nwhite, s))) return rc;
     hipLaunchKernelGGL(spectral_add2_all_kernel, tiles, dim3(256), 0, s, sa);
     HIP_TRY(hipGetLastError());
   }
-  GemmArgs g = {};   // X[m] = V[m] G[m]
-  g.A = w.V; g.lda = C; g.a_kmajor = 0; g.B = w.G; g.ldb = C; g.b_kmajor = 1; g.sA = g.sB = cc; g.skip = skip;
-  g.M = C; g.N = C; g.K = C; g.ksplit = C; g.out32 = w.X; g.ldo = C; g.s_out = cc;
+  GemmArgs g = level_product(C, skip);   // X[m] = V[m] G[m]
+  g.A = w.V; g.a_kmajor = 0; g.B = w.G; g.b_kmajor = 1; g.out32 = w.X;
   if ((rc = launch_gemm(g, 1, 2 * P, s))) return rc;
-  GemmArgs h = {};   // Tw / Tcs [m] = X[m] V[m]^T
-  h.A = w.X; h.lda = C; h.a_kmajor = 0; h.B = w.V; h.ldb = C; h.b_kmajor = 0; h.sA = h.sB = cc; h.skip = skip;
-  h.M = C; h.N = C; h.K = C; h.ksplit = C; h.out32 = w.Tw; h.ldo = C; h.s_out = cc;
-  if ((rc = launch_gemm(h, 1, 2 * P, s))) return rc;
-  return WCT_OK;
+  GemmArgs h = level_product(C, skip);   // Tw / Tcs [m] = X[m] V[m]^T
+  h.A = w.X; h.a_kmajor = 0; h.B = w.V; h.b_kmajor = 0; h.out32 = w.Tw;
+  return launch_gemm(h, 1, 2 * P, s);
+}
+
+int launch_spectral_tail(const WctCarve& w, int C, int P, float alpha, int mode, float eps_in, WctSkip skip, int nwhite,
+                         hipStream_t s) {
+  const int rc = launch_refresh(w, C, P, skip, s);
+  return rc ? rc : launch_spectral_tail_refreshed(w, C, P, alpha, mode, eps_in, skip, nwhite, s);
 }

@@ -208,7 +208,7 @@ __device__ __forceinline__ bool refresh_needed(const float* Am, int C, int tid) 
   for (int i = tid; i < C; i += 256) {
     const float d = Am[(size_t)i * C + i];
     dmax = fmaxf(dmax, fabsf(d));
-    // kept, or within half a decade below the cut-off (the `near` band of spectral_add2_kernel: its side of the cut-off is not settled)
+    // kept, or within half a decade below the cut-off (the `near` band of spectral_add2_all_kernel: its side of the cut-off is not settled)
     if (d > 3.3e-6f) dmin = fminf(dmin, d);
   }
   for (int o = 32; o > 0; o >>= 1) { dmax = fmaxf(dmax, __shfl_xor(dmax, o, 64)); dmin = fminf(dmin, __shfl_xor(dmin, o, 64)); }

@@ -162,11 +162,13 @@ int launch_style_swap(const float* content, int hc, int wc, const float* style, 
   if ((rc = launch_wct(content, Nc, style, Ns, C, 1, WCT_SKIP_NONE, r, nullptr, nullptr, nullptr))) return rc;
   const size_t cc = (size_t)C * C;
   // content whitening, style whitening, style colouring: S^-1/2 | S^1/2 over the kept singular values, no eps in the
-  // gains (ops.py:187-189,197-198,208-209), with the first-order completion on the solver's residual
-  if ((rc = launch_refresh(w, C, 1, WCT_SKIP_NONE, s))) return rc;
-  if ((rc = launch_spectral_function(w.A, w.V, w.G, w.X, w.Tw, C, 1, 2 * cc, cc, 0, 0.f, s, w.S2))) return rc;
-  if ((rc = launch_spectral_function(w.A + cc, w.V + cc, w.G + cc, w.X + cc, w.Tcs, C, 1, 2 * cc, cc, 0, 0.f, s, w.S2))) return rc;
-  if ((rc = launch_spectral_function(w.A + cc, w.V + cc, w.G + cc, w.X + cc, w.T, C, 1, 2 * cc, cc, 1, 0.f, s, w.S2))) return rc;
+  // gains (ops.py:187-189,197-198,208-209), with the completion on the solver's residual: wct_tf's own tail over the pair
+  // (content whitening into w.Tw, style colouring into w.Tcs), then the tail once more on a view of the carve in which the
+  // style is matrix 0, the whitening side, with the (empty) odd side dead: style whitening into w.T
+  if ((rc = launch_spectral_tail(w, C, 1, alpha, WCT_MODE_TF, eps, WCT_SKIP_NONE, 1, s))) return rc;
+  WctCarve v = w;
+  v.A += cc; v.V += cc; v.G += cc; v.X += cc; v.Tw = w.T;
+  if ((rc = launch_spectral_tail_refreshed(v, C, 1, alpha, WCT_MODE_TF, eps, WCT_SKIP_STYLE, 1, s))) return rc;
   auto apply = [&](const float* X, int N, const float* mean, const float* T, float* out) {   // out = (X - mean) T^T
     GemmArgs g = {};
     g.A = X; g.lda = C; g.a_kmajor = 0; g.a_sub_k = mean; g.B = T; g.ldb = C; g.b_kmajor = 0;
@@ -174,7 +176,7 @@ int launch_style_swap(const float* content, int hc, int wc, const float* style, 
     return launch_gemm(g, 1, 1, s);
   };
   if ((rc = apply(content, Nc, w.mean, w.Tw, sw.Wc))) return rc;
-  if ((rc = apply(style, Ns, w.mean + C, w.Tcs, sw.Ws))) return rc;
+  if ((rc = apply(style, Ns, w.mean + C, w.T, sw.Ws))) return rc;
   hipLaunchKernelGGL(im2col_kernel, dim3(ew_grid((size_t)Mo * K / 4)), dim3(256), 0, s, sw.Wc, sw.Ac, wc, C, patch, stride, ho, wo);
   hipLaunchKernelGGL(im2col_kernel, dim3(ew_grid((size_t)Pn * K / 4)), dim3(256), 0, s, sw.Ws, sw.Bs, ws, C, patch, stride, rows, cols);
   hipLaunchKernelGGL(patch_axis_inv_norm_kernel, dim3(cdiv(K / 4, 64)), dim3(64), 0, s, sw.Bs, sw.inv, Pn, K);
@@ -192,7 +194,7 @@ int launch_style_swap(const float* content, int hc, int wc, const float* style, 
   HIP_TRY(hipGetLastError());
   {  // col = ss . Tcol^T
     GemmArgs g = {};
-    g.A = sw.ss; g.lda = C; g.a_kmajor = 0; g.B = w.T; g.ldb = C; g.b_kmajor = 0;
+    g.A = sw.ss; g.lda = C; g.a_kmajor = 0; g.B = w.Tcs; g.ldb = C; g.b_kmajor = 0;
     g.M = Nc; g.N = C; g.K = C; g.ksplit = C; g.out32 = sw.col; g.ldo = C;
     if ((rc = launch_gemm(g, 1, 1, s))) return rc;
   }

@@ -301,7 +301,7 @@ WctCarve carve(void* base, int C, int P, const PairLayout& lay) {
   w.X = (float*)take(2 * P * cc);
   w.S2 = (float*)take(7 * P * cc);          // second-order operands of a level, all matrices at once: N [2P], X2 [2P], R, Pm, X1 [P]
   w.Tw = (float*)take(2 * P * cc);          // [2P][C][C] interleaved: whitening matrix of pair p at 2p, colouring matrix at 2p + 1
-  w.Tcs = w.Tw + (size_t)C * C;             // (style-swap path: one pair, Tw and Tcs side by side)
+  w.Tcs = w.Tw + (size_t)C * C;             // (pair 0's colouring matrix.  Style-swap, one pair: the style's whitening matrix in T)
   w.T = (float*)take(P * cc);
   w.M = (float*)take(P * cc);
   w.bias = (float*)take((size_t)P * C * sizeof(float));

@@ -104,11 +104,11 @@ int launch_plan_stats(const SlotPlan& sp, int C, bool with_var, bool with_cov, f
 // (check_from: the first sweep after which the host looks at the done-flags -- JacobiGroup::check_from; a warm solve passes 0)
 int launch_eig_stage(const WctCarve& w, int C, int P, WctSkip skip, int u_f16, int* sweeps_dev, int* eig_fail, hipStream_t s,
                      int check_from = 2);
-// spectral.hip: the refresh of the rotated matrices, the merged spectral tail of a level, one spectral function (style-swap)
-int launch_refresh(const WctCarve& w, int C, int P, WctSkip skip, hipStream_t s, bool always = false);
+// spectral.hip: the merged spectral tail of a level, which begins with the refresh of the rotated matrices; the tail alone, for
+// matrices that have had their refresh (style-swap's second run)
 int launch_spectral_tail(const WctCarve& w, int C, int P, float alpha, int mode, float eps_in, WctSkip skip, int nwhite, hipStream_t s);
-int launch_spectral_function(const float* A, const float* V, float* G, float* X, float* out, int C, int nbatch, size_t stride,
-                             size_t out_stride, int kind, float shift, hipStream_t s, float* scratch2 = nullptr);
+int launch_spectral_tail_refreshed(const WctCarve& w, int C, int P, float alpha, int mode, float eps_in, WctSkip skip, int nwhite,
+                                   hipStream_t s);
 // wct.hip: the blend product M = alpha Tcs Tw + (1 - alpha) I of P pairs; the apply of P pairs of Nc rows on the matrices of w
 // (any number of calls on one set of matrices: the chunks of a banded map); the apply of a masked transform's P segments (the
 // longest has nmax rows), whose argument blocks start from apply_args
