@@ -368,6 +368,44 @@ int  wct_stylize_prepared_masked_batch_dev(wct_ctx* ctx, const uint8_t* content_
                                            const uint8_t* masks_host, const wct_style* const* styles, int K, const int* levels,
                                            int n_levels, float alpha, unsigned flags, uint8_t* out_dev);
 
+/* ---- style regions: a prepared style from a labelled part of its image --------------------
+ * Spatial control gives every region of the CONTENT its own style, but each of those styles is a whole image.  Semantic matching
+ * (sky from the sky of a painting; the label-matched transfer of Li et al. 2018) needs the other half: the style statistics of a
+ * level from a selected part of the style image.  A style Hs x Ws x 3 comes with a uint8 label map [Hs][Ws] on the host.
+ * Semantics (the content side's rule): at relu<l>_1, stride s = 2^(l - 1), feature pixel (i, j) of the style's h x w map has the
+ *   label map[min(i s, Hs - 1)][min(j s, Ws - 1)]; the region of a label is the feature rows with that label, in pixel order; the
+ *   style side of the level is what a whole-image handle computes, from those n rows alone: mean, covariance with 1 / (n - 1), the
+ *   per-matrix cut-off, the colouring matrix, mean and variance for AdaIN.  The encoder always sees the whole image: only the rows
+ *   that enter the statistics are selected (on the device: one compaction of the level's labels, then a gather of n C floats).
+ *   A region needs at least 2 rows at EVERY level of the handle, for WCT and AdaIN alike.
+ * wct_style_prepare_region: wct_style_prepare for the rows of `label` (0 .. 7; other values of the map just are not selected).
+ *   The handle keeps the image AND the map on the device, and the rows of every level counted on the host; it is an ordinary
+ *   wct_style -- every call that takes handles takes it, with no change on the content side -- whose state keys follow (content
+ *   rows, region rows) instead of (content rows, h w).  A map that labels every pixel `label` gives wct_style_prepare's handle,
+ *   bit for bit.  A region with fewer than 2 rows at a served level is WCT_STATUS_ARG (the message names the level and the count)
+ *   and no handle.
+ * wct_style_prepare_regions: K = 1 .. 8 regions of one image, labels 0 .. K - 1 (a label >= K in the map: WCT_STATUS_ARG): one
+ *   upload, ONE encoder pass and ONE compaction per level for all K; the states are then filled region by region.  out[k] is the
+ *   handle wct_style_prepare_region(label k) gives, bit for bit, or NULL (status OK) for a label with fewer than 2 rows at some
+ *   level, which cannot carry a style.  The handles share the image and the map by reference count: each is freed by
+ *   wct_style_free on its own, and refilled on a new key by its own encoder pass.  On an error no handle is made.
+ * wct_style_rows: the rows a handle's statistics use at a level of its set (h w for a whole-image handle).
+ * wct_transform_region / wct_adain_region = wct_transform / wct_adain on the rows of `label` of a style feature map hs x ws x C,
+ *   labels [hs ws] one per row, selected on the device by the same launches: bit for bit wct_transform(content, style[labels ==
+ *   label]).  Fewer than 2 rows: WCT_STATUS_ARG.
+ * Refused with WCT_STATUS_ARG and a message, the ctx usable afterwards: a NULL map, WCT_FLAG_SWAP5, WCT_FLAG_STYLE_SHARED, K
+ *   outside 1 .. 8, a label outside 0 .. 7, and a style past the limit of one launch, as for wct_style_prepare.  Not served: soft
+ *   or weighted style regions, style-swap from a region, banded style images. */
+int  wct_style_prepare_region(wct_ctx* ctx, const uint8_t* style, int Hs, int Ws, const uint8_t* map, int label, const int* levels,
+                              int n_levels, unsigned flags, wct_style** out);
+int  wct_style_prepare_regions(wct_ctx* ctx, const uint8_t* style, int Hs, int Ws, const uint8_t* map, int K, const int* levels,
+                               int n_levels, unsigned flags, wct_style** out /* [K] */);
+int  wct_style_rows(wct_ctx* ctx, const wct_style* style, int level, int* n);
+int  wct_transform_region(wct_ctx* ctx, const float* content, int Nc, const float* style, int hs, int ws, int C,
+                          const uint8_t* labels, int label, float alpha, int mode, float eps, float* out, int* sweeps_out);
+int  wct_adain_region(wct_ctx* ctx, const float* content, int Nc, const float* style, int hs, int ws, int C, const uint8_t* labels,
+                      int label, float alpha, float epsilon, float* out);
+
 /* ---- video warm start: solve each frame from the previous frame's basis --------------------
  * stylize_video.py:112-135 calls predict() once per frame, and every call decomposes the frame's content covariances from
  * scratch although consecutive frames have almost the same ones.  A wct_warm holds, per relu level of its set, one C x C fp32

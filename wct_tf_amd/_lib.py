@@ -72,6 +72,12 @@ SIGNATURES = [
     ('wct_stylize_prepared_masked', C.c_int, [_P, _U8, C.c_int, C.c_int, _U8, _PP, C.c_int, _I, C.c_int, C.c_float, C.c_uint, _U8]),
     ('wct_stylize_prepared_masked_batch_dev', C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _U8, _PP, C.c_int, _I, C.c_int, C.c_float,
                                                         C.c_uint, _P]),
+    ('wct_style_prepare_region', C.c_int, [_P, _U8, C.c_int, C.c_int, _U8, C.c_int, _I, C.c_int, C.c_uint, _PP]),
+    ('wct_style_prepare_regions', C.c_int, [_P, _U8, C.c_int, C.c_int, _U8, C.c_int, _I, C.c_int, C.c_uint, _PP]),
+    ('wct_style_rows', C.c_int, [_P, _P, C.c_int, _I]),
+    ('wct_transform_region', C.c_int, [_P, _F, C.c_int, _F, C.c_int, C.c_int, C.c_int, _U8, C.c_int, C.c_float, C.c_int, C.c_float,
+                                       _F, _I]),
+    ('wct_adain_region', C.c_int, [_P, _F, C.c_int, _F, C.c_int, C.c_int, C.c_int, _U8, C.c_int, C.c_float, C.c_float, _F]),
     ('wct_warm_create', C.c_int, [_P, _I, C.c_int, _PP]),
     ('wct_warm_free', None, [_P, _P]),
     ('wct_warm_reset', C.c_int, [_P, _P]),
@@ -230,6 +236,25 @@ def mask_labels(mask, k, shape=None):
         raise ValueError('mask labels must be integers, got %s' % (m.dtype,))
     if m.min() < 0 or m.max() >= k:
         raise ValueError('mask labels must be 0 .. %d for %d styles, got %d .. %d' % (k - 1, k, m.min(), m.max()))
+    return np.ascontiguousarray(m, np.uint8)
+
+
+def style_region_map(label_map, shape, k=None, label=None):
+    """The label map of a style image of `shape` (H, W) as contiguous uint8 (style regions, include/wct_hip.h): an integer
+    array of exactly that shape with values 0 .. 255 -- and, given k, labels 0 .. k - 1 for k = 1 .. MIX_MAX regions; given
+    `label`, a label 0 .. MIX_MAX - 1.  The rules the library applies, checked here before any GPU call."""
+    if k is not None and not 1 <= int(k) <= MIX_MAX:
+        raise ValueError('style regions: 1 .. %d regions, got %d' % (MIX_MAX, k))
+    if label is not None and not 0 <= int(label) < MIX_MAX:
+        raise ValueError('a style region takes a label 0 .. %d, got %d' % (MIX_MAX - 1, label))
+    m = np.asarray(label_map)
+    if not (np.issubdtype(m.dtype, np.integer) or np.issubdtype(m.dtype, np.bool_)):
+        raise ValueError('style region labels must be integers, got %s' % (m.dtype,))
+    if m.shape != tuple(shape) or m.size == 0:
+        raise ValueError('style label map of shape %s for a style of shape %s' % (m.shape, tuple(shape)))
+    top = 255 if k is None else int(k) - 1
+    if m.min() < 0 or m.max() > top:
+        raise ValueError('style region labels must be 0 .. %d, got %d .. %d' % (top, m.min(), m.max()))
     return np.ascontiguousarray(m, np.uint8)
 
 

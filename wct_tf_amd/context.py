@@ -134,10 +134,19 @@ class PreparedStyle(object):
     """A style whose style side -- encoder pass, statistics, covariances, eigendecompositions, colouring matrices -- is kept on
     the device (wct_style, include/wct_hip.h): Context.prepare_style makes one, the stylize_prepared* calls take it in the place
     of a style image and give the image-based call's frame bit for bit.  Owned by its context (closing the context closes it);
-    close() or a `with` block releases it earlier.  `image` is the style as it was handed in."""
+    close() or a `with` block releases it earlier.  `image` is the style as it was handed in.  `region` is None, or the
+    (label_map, label) of a style region: the statistics of every level come from the feature rows of that label alone."""
 
-    def __init__(self, ctx, handle, image, levels):
-        self.ctx, self.h, self.image, self.levels = ctx, handle, image, frozenset(levels)
+    def __init__(self, ctx, handle, image, levels, region=None):
+        self.ctx, self.h, self.image, self.levels, self.region = ctx, handle, image, frozenset(levels), region
+
+    def rows(self, relu_target):
+        """the feature rows the statistics of `relu_target` use (wct_style_rows): h * w of the style's map, or the region's"""
+        if self.closed:
+            raise ValueError('the prepared style is closed')
+        n = C.c_int()
+        check(self.ctx.lib.wct_style_rows(self.ctx.h, self.h, _levels([relu_target])[0], C.byref(n)))
+        return n.value
 
     @property
     def closed(self):
@@ -313,6 +322,20 @@ def check_wrap(h, w, relu_targets):
     return int(h), int(w)
 
 
+def region_rows(label_map, label, relu_target):
+    """The feature rows a style region has at `relu_target`, by the library's rule (include/wct_hip.h): feature pixel (i, j) of the
+    ceil-pooled h x w map has the label label_map[min(i s, H - 1)][min(j s, W - 1)], s = 2^(level - 1).  No GPU call."""
+    m = np.asarray(label_map)
+    l = _levels([relu_target])[0]
+    h, w = m.shape
+    for _ in range(l - 1):
+        h, w = (h + 1) // 2, (w + 1) // 2
+    s = 1 << (l - 1)
+    rows = np.minimum(np.arange(h) * s, m.shape[0] - 1)
+    cols = np.minimum(np.arange(w) * s, m.shape[1] - 1)
+    return int(np.count_nonzero(m[np.ix_(rows, cols)] == label))
+
+
 def split_styles(styles):
     """(handles, images) of a list of styles: one of the two is empty, a list that mixes PreparedStyle objects and images is a
     ValueError."""
@@ -415,6 +438,34 @@ class Context(object):
         out = np.empty_like(c)
         check(self.lib.wct_adain(self.h, fptr(c), c.shape[0], fptr(s), s.shape[0], c.shape[1],
                                  float(alpha), float(epsilon), fptr(out)))
+        return out
+
+    @staticmethod
+    def _region_level(content, style, labels, label):
+        """The arguments of a one-level region call, checked before any GPU call: content [Nc][C], style [hs][ws][C] float32,
+        labels [hs][ws] integers, label 0 .. 7."""
+        c, s = f32(content), f32(style)
+        if c.ndim != 2 or s.ndim != 3 or c.shape[1] != s.shape[2]:
+            raise ValueError('expected content [N][C] and a style feature map [hs][ws][C] with equal C')
+        return c, s, _lib.style_region_map(labels, s.shape[:2], label=label)
+
+    def transform_region(self, content, style, labels, label, alpha, mode, eps=-1.0, return_sweeps=False):
+        """transform() on a style region (wct_transform_region): style [hs][ws][C] a feature map, labels [hs][ws] -- the style
+        rows are those of `label`, selected on the device: transform(content, style[labels == label]) bit for bit."""
+        c, s, m = self._region_level(content, style, labels, label)
+        out = np.empty_like(c)
+        sweeps = (C.c_int * 2)()
+        self.last_sweeps = sweeps
+        check(self.lib.wct_transform_region(self.h, fptr(c), c.shape[0], fptr(s), s.shape[0], s.shape[1], c.shape[1],
+                                            m.ctypes.data_as(_lib._U8), int(label), float(alpha), int(mode), float(eps), fptr(out), sweeps))
+        return (out, list(sweeps)) if return_sweeps else out
+
+    def adain_region(self, content, style, labels, label, alpha, epsilon=1e-5):
+        """adain() on a style region (wct_adain_region): as transform_region."""
+        c, s, m = self._region_level(content, style, labels, label)
+        out = np.empty_like(c)
+        check(self.lib.wct_adain_region(self.h, fptr(c), c.shape[0], fptr(s), s.shape[0], s.shape[1], c.shape[1],
+                                        m.ctypes.data_as(_lib._U8), int(label), float(alpha), float(epsilon), fptr(out)))
         return out
 
     @staticmethod
@@ -923,21 +974,49 @@ class Context(object):
         return c, ss, v, (C.c_int * len(lv))(*lv), np.empty((ho, wo, 3), np.uint8), flags
 
     # ---- prepared styles -----------------------------------------------------
-    def prepare_style(self, style, relu_targets, adain=False, wct_mode='tf'):
-        """The style side of `style` (HxWx3 in [0,255]) for the levels `relu_targets`, kept on the device -> PreparedStyle.
-        uint8 goes as it is, anything else `/ 255.` in float64 and handed over as float32, exactly as Context.stylize does with
-        its style.  adain / wct_mode only pick what is computed up front: a handle serves either mode and AdaIN."""
+    @staticmethod
+    def _style_image(style):
+        """a style image as prepare_style hands it over: -> (the array as given, its device form, images_f32)"""
         img = np.asarray(style)
         if img.ndim != 3 or img.shape[2] != 3:
             raise ValueError('expected an HxWx3 style image, got shape %s' % (img.shape,))
         as_f32 = img.dtype != np.uint8
-        s = np.ascontiguousarray(np.asarray(img / 255.), np.float32) if as_f32 else u8(img)
+        return img, (np.ascontiguousarray(np.asarray(img / 255.), np.float32) if as_f32 else u8(img)), as_f32
+
+    def prepare_style(self, style, relu_targets, adain=False, wct_mode='tf', region=None):
+        """The style side of `style` (HxWx3 in [0,255]) for the levels `relu_targets`, kept on the device -> PreparedStyle.
+        uint8 goes as it is, anything else `/ 255.` in float64 and handed over as float32, exactly as Context.stylize does with
+        its style.  adain / wct_mode only pick what is computed up front: a handle serves either mode and AdaIN.
+        region=(label_map, label): a style region (wct_style_prepare_region) -- label_map [H][W] integers of the style's size,
+        and the statistics of every level come from the feature rows of `label` (0 .. 7) alone; the encoder still sees the
+        whole image.  A region with fewer than 2 rows at a level is refused by the library."""
+        img, s, as_f32 = self._style_image(style)
         lv = sorted(set(_levels(relu_targets)))
         flags = _flags(adain, wct_mode, images_f32=as_f32)
         h = C.c_void_p()
+        if region is not None:
+            label_map, label = region
+            m = _lib.style_region_map(label_map, img.shape[:2], label=label)   # ValueError before any library call
+            check(self.lib.wct_style_prepare_region(self.h, s.ctypes.data_as(_lib._U8), s.shape[0], s.shape[1], m.ctypes.data_as(_lib._U8),
+                                                    int(label), (C.c_int * len(lv))(*lv), len(lv), flags, C.byref(h)))
+            return PreparedStyle(self, h, img, lv, region=(m, int(label)))
         check(self.lib.wct_style_prepare(self.h, s.ctypes.data_as(_lib._U8), s.shape[0], s.shape[1], (C.c_int * len(lv))(*lv), len(lv),
                                          flags, C.byref(h)))
         return PreparedStyle(self, h, img, lv)
+
+    def prepare_style_regions(self, style, label_map, k, relu_targets, adain=False, wct_mode='tf'):
+        """The k regions of ONE style image as prepared styles (wct_style_prepare_regions): label_map [H][W] integers 0 .. k - 1 of
+        the style's size -> a list of k entries, entry j the PreparedStyle prepare_style(style, region=(label_map, j)) gives, bit
+        for bit -- from one upload, one encoder pass and one partition per level for all of them -- or None for a label with
+        fewer than 2 feature rows at some level, which cannot carry a style."""
+        img, s, as_f32 = self._style_image(style)
+        m = _lib.style_region_map(label_map, img.shape[:2], k=k)               # ValueError before any library call
+        lv = sorted(set(_levels(relu_targets)))
+        flags = _flags(adain, wct_mode, images_f32=as_f32)
+        hs = (C.c_void_p * int(k))()
+        check(self.lib.wct_style_prepare_regions(self.h, s.ctypes.data_as(_lib._U8), s.shape[0], s.shape[1], m.ctypes.data_as(_lib._U8),
+                                                 int(k), (C.c_int * len(lv))(*lv), len(lv), flags, hs))
+        return [PreparedStyle(self, C.c_void_p(hs[j]), img, lv, region=(m, j)) if hs[j] else None for j in range(int(k))]
 
     def _prepared_args(self, content, relu_targets, adain, wct_mode, content_colors=False, guided=None):
         """content, levels, output and flags of a call with prepared styles (the content as in stylize)"""

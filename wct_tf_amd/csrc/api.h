@@ -59,15 +59,27 @@ struct StyleState {
   float* buf;                                        // wct_style_state_floats(C)
   unsigned long long stamp;                          // the call that used it last (wct_ctx::style_clock)
 };
+// what a handle is refilled from: the style image and, for a style region (wct_style_prepare_region*), its label map.  The sibling
+// handles of one wct_style_prepare_regions call share one (by reference count: each is freed on its own).
+struct StyleSource {
+  float* img = nullptr;                              // [Hs][Ws][3] fp32 in [0,1]
+  uint8_t* map = nullptr;                            // [Hs][Ws] labels, or null: a whole-image handle
+  StyleSource() = default;
+  StyleSource(const StyleSource&) = delete;
+  StyleSource& operator=(const StyleSource&) = delete;
+  ~StyleSource() { if (img) hipFree(img); if (map) hipFree(map); }
+};
 struct wct_style {
   int Hs = 0, Ws = 0;
   unsigned level_set = 0;                            // bit l: relu<l>_1 is served
-  float* img = nullptr;                              // [Hs][Ws][3] fp32 in [0,1]
+  std::shared_ptr<StyleSource> src;
+  int label = -1;                                    // >= 0: a style region -- the rows of this label of src->map alone
+  int rows[6] = {0};                                 // per served level: the rows its statistics use (a region: counted on the host;
+                                                     // else h * w).  Every style key and style workspace is formed from these.
   std::vector<StyleState> cache[6];
   ~wct_style() {
     for (auto& lv : cache)
       for (auto& e : lv) if (e.buf) hipFree(e.buf);
-    if (img) hipFree(img);
   }
 };
 
@@ -96,6 +108,7 @@ struct wct_ctx {
   DevBuf mix_in, feat_mix[6];      // a style mix: the K style inputs, and their features per level (K maps back to back)
   DevBuf mask_in;                  // spatial control: the label map (wct_stylize_masked) or the row labels (wct_*_masked); the
                                    // strength map of wct_transform_strength, wct_adain_strength and wct_stylize_prepared_strength
+  DevBuf region_ws;                // style regions: a level's partition (perm, seg_off), the compaction's scratch and the gathered rows
   DevBuf tex_noise, tex[2];        // texture synthesis: the noise images, and the uint8 frames between two passes (alternating)
   DevBuf band_f, band_g, band_img; // banded stylization: a level's full fp32 feature map and its fp16 transform (either may pass
                                    // 2^31 bytes: every launch sees a slice), and the decoded image of one band with its halo

@@ -15,15 +15,44 @@ static int stage_strength(wct_ctx* c, const uint8_t* smap, int Hm, int Wm, int N
   return WCT_OK;
 }
 
+// A style region at op level: the hs x ws x C style map into stage 1 and its row labels into c->mask_in, then the rows of `label`
+// selected on the device (mask.hip: the compaction of the prepared-style fill, and its segment gather) into c->region_ws.
+// *rows: the n selected rows, in pixel order.  Fewer than 2 rows are refused, for WCT and AdaIN alike.
+static int stage_region(wct_ctx* c, const float* style, int hs, int ws, int C, const uint8_t* labels, int label, const float** rows, int* n) {
+  if (!labels) { wct_set_error("style region: no label map"); return WCT_ERR_ARG; }
+  if (label < 0 || label >= WCT_MIX_MAX) { wct_set_error("style region: label %d, must be 0 .. %d", label, (int)WCT_MIX_MAX - 1); return WCT_ERR_ARG; }
+  ARG_CHECK(hs >= 1 && ws >= 1 && C >= 4 && C % 4 == 0 && (long long)hs * ws < (1ll << 31));
+  const int N = hs * ws;
+  int cnt = 0;
+  for (int i = 0; i < N; ++i) cnt += labels[i] == label;
+  if (cnt < 2) { wct_set_error("style region: label %d has %d rows of the %dx%d style map (a region needs at least 2)", label, cnt, hs, ws); return WCT_ERR_ARG; }
+  HIP_TRY(hipSetDevice(c->device));
+  TRY(ensure(c, c->mask_in, (size_t)N));
+  HIP_TRY(hipMemcpyAsync(c->mask_in.p, labels, (size_t)N, hipMemcpyHostToDevice, c->stream));
+  void* ds;
+  TRY(stage_in(c, 1, style, (size_t)N * C * 4, &ds));
+  auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  const size_t perm_b = up((size_t)N * sizeof(int)), seg_b = up((WCT_MIX_MAX + 1) * sizeof(int)), cws_b = up(mask_compact_workspace_bytes(N));
+  TRY(ensure(c, c->region_ws, perm_b + seg_b + cws_b + (size_t)cnt * C * 4));
+  char* base = (char*)c->region_ws.p;
+  int *perm = (int*)base, *seg_off = (int*)(base + perm_b);
+  float* out = (float*)(base + perm_b + seg_b + cws_b);
+  TRY(launch_mask_compact(MaskGeom{(const uint8_t*)c->mask_in.p, hs, ws, ws, 1}, N, label + 1, perm, seg_off, base + perm_b + seg_b, c->stream));
+  TRY(launch_mask_gather_segment((const float*)ds, perm, seg_off, label, cnt, C, out, c->stream));
+  *rows = out; *n = cnt;
+  return WCT_OK;
+}
+
 // One (content, style) pair of feature matrices through run_transform.  warm (with its level): the content solve starts from the
 // state's basis of that level, which then takes this pair's.  sm: a strength map on the device (stage_strength).
 static int transform_pair(wct_ctx* c, const float* content, int Nc, const float* style, int Ns, int C, float alpha, unsigned flags,
-                          float eps, wct_warm* warm, int level, float* out, int* sweeps_out, const WctStrength* sm = nullptr) {
+                          float eps, wct_warm* warm, int level, float* out, int* sweeps_out, const WctStrength* sm = nullptr,
+                          const float* style_dev = nullptr /* the style rows on the device already (stage_region): `style` is unused */) {
   HIP_TRY(hipSetDevice(c->device));
   TRY(eig_stale(c));
-  void *dc, *ds;
+  void *dc, *ds = (void*)style_dev;
   TRY(stage_in(c, 0, content, (size_t)Nc * C * 4, &dc));
-  TRY(stage_in(c, 1, style, (size_t)Ns * C * 4, &ds));
+  if (!style_dev) TRY(stage_in(c, 1, style, (size_t)Ns * C * 4, &ds));
   TRY(ensure(c, c->stage[2], (size_t)Nc * C * 4));
   TRY(ensure(c, c->stage[3], 256));
   WctWarmRef wr = {};
@@ -43,6 +72,17 @@ extern "C" int wct_transform(wct_ctx* c, const float* content, int Nc, const flo
                              float alpha, int mode, float eps, float* out, int* sweeps_out) {
   ARG_CHECK(c && content && style && out && (mode == WCT_NP || mode == WCT_TF));
   return transform_pair(c, content, Nc, style, Ns, C, alpha, mode == WCT_NP ? WCT_FLAG_MODE_NP : 0, eps, nullptr, 0, out, sweeps_out);
+}
+
+// wct_transform with the style rows selected on the device: the rows of `label` of the hs x ws style map
+extern "C" int wct_transform_region(wct_ctx* c, const float* content, int Nc, const float* style, int hs, int ws, int C,
+                                    const uint8_t* labels, int label, float alpha, int mode, float eps, float* out, int* sweeps_out) {
+  ARG_CHECK(c && content && style && out && (mode == WCT_NP || mode == WCT_TF));
+  const float* rows;
+  int n;
+  TRY(stage_region(c, style, hs, ws, C, labels, label, &rows, &n));
+  return transform_pair(c, content, Nc, nullptr, n, C, alpha, mode == WCT_NP ? WCT_FLAG_MODE_NP : 0, eps, nullptr, 0, out, sweeps_out,
+                        nullptr, rows);
 }
 
 extern "C" int wct_transform_strength(wct_ctx* c, const float* content, int Nc, int h, int w, const uint8_t* smap, int Hm, int Wm,
@@ -116,6 +156,21 @@ extern "C" int wct_adain(wct_ctx* c, const float* content, int Nc, const float* 
   TRY(ensure(c, c->stage[2], (size_t)Nc * C * 4));
   TRY(ensure(c, c->wct_ws, wct_workspace_bytes(C, Nc, Ns, 1)));
   TRY(launch_adain((float*)dc, Nc, (float*)ds, Ns, C, 1, WCT_SKIP_NONE, adain_call(c, alpha, epsilon), nullptr, nullptr));
+  return fetch(c, out, c->stage[2].p, (size_t)Nc * C * 4);
+}
+
+// wct_adain with the style rows selected on the device (wct_transform_region's rule, its < 2 rows refusal included)
+extern "C" int wct_adain_region(wct_ctx* c, const float* content, int Nc, const float* style, int hs, int ws, int C, const uint8_t* labels,
+                                int label, float alpha, float epsilon, float* out) {
+  ARG_CHECK(c && content && style && out);
+  const float* rows;
+  int n;
+  TRY(stage_region(c, style, hs, ws, C, labels, label, &rows, &n));
+  void* dc;
+  TRY(stage_in(c, 0, content, (size_t)Nc * C * 4, &dc));
+  TRY(ensure(c, c->stage[2], (size_t)Nc * C * 4));
+  TRY(ensure(c, c->wct_ws, wct_workspace_bytes(C, Nc, n, 1)));
+  TRY(launch_adain((float*)dc, Nc, rows, n, C, 1, WCT_SKIP_NONE, adain_call(c, alpha, epsilon), nullptr, nullptr));
   return fetch(c, out, c->stage[2].p, (size_t)Nc * C * 4);
 }
 

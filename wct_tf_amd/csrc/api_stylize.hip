@@ -407,57 +407,126 @@ static StyleState* state_find(wct_style* st, int level, const WctStyleKey& key, 
 
 struct StyleNeed { int level; WctStyleKey key; };
 
-// Computes the states `needs` of a handle for one kind (none of them cached) on the ctx stream: ONE encoder pass of the style with a tap per
-// level needed, then launch_style_state per state.  Blocking, and the eigensolves are checked before a state is kept: on
-// WCT_ERR_NOCONV (or any error) none of them stays in the cache.
-static int style_fill(wct_ctx* c, wct_style* st, int kind, const std::vector<StyleNeed>& needs) {
-  if (needs.empty()) return WCT_OK;
-  HIP_TRY(hipStreamSynchronize(c->stream));               // (a state evicted below may belong to frames still in flight)
-  int deepest = 0;
-  float* taps[6] = {};
-  for (const StyleNeed& n : needs) {
-    int h, w;
-    level_dims(st->Hs, st->Ws, n.level, &h, &w);
-    TRY(ensure(c, c->feat_s[n.level], (size_t)h * w * LEVEL_C[n.level] * 4));
-    taps[n.level] = (float*)c->feat_s[n.level].p;
-    deepest = std::max(deepest, n.level);
+// the rows a handle's statistics use at a level: what every style key and style workspace is formed from (a whole-image handle:
+// h * w of the style's feature map; a style region: the rows of its label, counted when it was prepared)
+static int style_rows(const wct_style* st, int level) { return st->rows[level]; }
+
+// the rows of `label` in the h x w feature map of a level (MaskGeom's rule at `stride`), counted on the host
+static int region_count(const uint8_t* map, int Hm, int Wm, int h, int w, int stride, int label) {
+  int n = 0;
+  for (int i = 0; i < h; ++i) {
+    const uint8_t* row = map + (size_t)std::min(i * stride, Hm - 1) * Wm;
+    for (int j = 0; j < w; ++j) n += row[std::min(j * stride, Wm - 1)] == label;
   }
-  TRY(run_encoder(c, st->img, 1, st->Hs, st->Ws, 0, deepest, taps));
+  return n;
+}
+
+// Computes the states needs[g] of the G handles of `group` for one kind (none of them cached) on the ctx stream.  The handles share
+// their source -- one handle, or the siblings of wct_style_prepare_regions --, so there is ONE encoder pass of the style with a tap
+// per level needed and, for style regions, ONE compaction of each level's labels (mask.hip); then per state the rows of the
+// handle's label are gathered (n_k * C floats) in front of launch_style_state.  A whole-image handle takes the tap itself: the
+// launches it always took.  Blocking, and the eigensolves are checked before a state is kept: on WCT_ERR_NOCONV (or any error)
+// none of them stays in a cache.
+static int style_fill(wct_ctx* c, wct_style* const* group, int G, int kind, const std::vector<StyleNeed>* needs) {
+  bool any = false;
+  for (int g = 0; g < G; ++g) any = any || !needs[g].empty();
+  if (!any) return WCT_OK;
+  HIP_TRY(hipStreamSynchronize(c->stream));               // (a state evicted below may belong to frames still in flight)
+  const wct_style* st0 = group[0];
+  const bool region = st0->label >= 0;
+  int deepest = 0, labels = 0;
+  size_t row_floats = 0;
+  float* taps[6] = {};
+  for (int g = 0; g < G; ++g)
+    for (const StyleNeed& n : needs[g]) {
+      int h, w;
+      level_dims(st0->Hs, st0->Ws, n.level, &h, &w);
+      TRY(ensure(c, c->feat_s[n.level], (size_t)h * w * LEVEL_C[n.level] * 4));
+      taps[n.level] = (float*)c->feat_s[n.level].p;
+      deepest = std::max(deepest, n.level);
+      labels = std::max(labels, group[g]->label + 1);
+      row_floats = std::max(row_floats, (size_t)style_rows(group[g], n.level) * LEVEL_C[n.level]);
+    }
+  // a region's scratch in c->region_ws: per level needed its partition (perm, seg_off), then the compaction's counts and the rows
+  int *perm[6] = {}, *seg_off[6] = {};
+  void* compact_ws = nullptr;
+  float* rows = nullptr;
+  if (region) {
+    size_t off = 0, poff[6] = {}, soff[6] = {}, cbytes = 0;
+    auto take = [&](size_t bytes) { const size_t at = off; off += (bytes + 255) & ~(size_t)255; return at; };
+    for (int l = 1; l <= 5; ++l) {
+      if (!taps[l]) continue;
+      int h, w;
+      level_dims(st0->Hs, st0->Ws, l, &h, &w);
+      poff[l] = take((size_t)h * w * sizeof(int));
+      soff[l] = take((WCT_MIX_MAX + 1) * sizeof(int));
+      cbytes = std::max(cbytes, mask_compact_workspace_bytes(h * w));
+    }
+    const size_t coff = take(cbytes), roff = take(row_floats * sizeof(float));
+    TRY(ensure(c, c->region_ws, off));
+    char* base = (char*)c->region_ws.p;
+    for (int l = 1; l <= 5; ++l)
+      if (taps[l]) { perm[l] = (int*)(base + poff[l]); seg_off[l] = (int*)(base + soff[l]); }
+    compact_ws = base + coff;
+    rows = (float*)(base + roff);
+  }
+  TRY(run_encoder(c, st0->src->img, 1, st0->Hs, st0->Ws, 0, deepest, taps));
+  if (region)
+    for (int l = 1; l <= 5; ++l) {
+      if (!taps[l]) continue;
+      int h, w;
+      level_dims(st0->Hs, st0->Ws, l, &h, &w);
+      ProfScope ps(c, 7, 0, (double)h * w * 2);
+      TRY(launch_mask_compact(MaskGeom{st0->src->map, st0->Hs, st0->Ws, w, 1 << (l - 1)}, h * w, labels, perm[l], seg_off[l], compact_ws,
+                              c->stream));
+    }
   std::vector<float*> fresh;
   int rc = WCT_OK;
-  for (const StyleNeed& n : needs) {
-    const int C = LEVEL_C[n.level];
-    int h, w;
-    level_dims(st->Hs, st->Ws, n.level, &h, &w);
-    auto& lv = st->cache[n.level];
-    float* buf = nullptr;
-    if ((int)lv.size() >= STYLE_CACHE_KEYS) {            // the oldest state that this call does not use makes room
-      int old = -1;
-      for (int i = 0; i < (int)lv.size(); ++i)
-        if (lv[i].stamp != c->style_clock && (old < 0 || lv[i].stamp < lv[old].stamp)) old = i;
-      if (old >= 0) { buf = lv[old].buf; lv.erase(lv.begin() + old); }
+  for (int g = 0; g < G && !rc; ++g) {
+    wct_style* st = group[g];
+    int gathered = 0;                                     // the level whose rows of this handle `rows` holds
+    for (const StyleNeed& n : needs[g]) {
+      const int C = LEVEL_C[n.level], Ns = style_rows(st, n.level);
+      auto& lv = st->cache[n.level];
+      float* buf = nullptr;
+      if ((int)lv.size() >= STYLE_CACHE_KEYS) {            // the oldest state that this call does not use makes room
+        int old = -1;
+        for (int i = 0; i < (int)lv.size(); ++i)
+          if (lv[i].stamp != c->style_clock && (old < 0 || lv[i].stamp < lv[old].stamp)) old = i;
+        if (old >= 0) { buf = lv[old].buf; lv.erase(lv.begin() + old); }
+      }
+      if (!buf && hipMalloc((void**)&buf, wct_style_state_floats(C) * sizeof(float)) != hipSuccess) {
+        wct_set_error("hipMalloc failed (prepared style state, relu%d_1)", n.level);
+        rc = WCT_ERR_NOMEM;
+        break;
+      }
+      lv.push_back(StyleState{n.key, kind, buf, c->style_clock});
+      fresh.push_back(buf);
+      if (hipMemsetAsync(buf, 0, wct_style_state_floats(C) * sizeof(float), c->stream) != hipSuccess) { wct_set_error("hipMemsetAsync failed"); rc = WCT_ERR_HIP; break; }
+      const float* feat = taps[n.level];
+      if (region) {
+        if (gathered != n.level) {
+          ProfScope ps(c, 7, 0, (double)Ns * C * 8);
+          if ((rc = launch_mask_gather_segment(taps[n.level], perm[n.level], seg_off[n.level], st->label, Ns, C, rows, c->stream))) break;
+          gathered = n.level;
+        }
+        feat = rows;
+      }
+      if ((rc = ensure(c, c->wct_ws, wct_style_workspace_bytes(C, Ns, n.key)))) break;
+      ProfScope ps(c, kind == 2 ? 7 : 5, 0, 0);
+      WctCall r = ctx_call(c, kind == 1 ? WCT_MODE_NP : WCT_MODE_TF, WCT_STAGE_ALL);
+      r.eps = -1.f;
+      if ((rc = launch_style_state(feat, Ns, C, n.key, kind == 2, r, buf))) break;
     }
-    if (!buf && hipMalloc((void**)&buf, wct_style_state_floats(C) * sizeof(float)) != hipSuccess) {
-      wct_set_error("hipMalloc failed (prepared style state, relu%d_1)", n.level);
-      rc = WCT_ERR_NOMEM;
-      break;
-    }
-    lv.push_back(StyleState{n.key, kind, buf, c->style_clock});
-    fresh.push_back(buf);
-    if (hipMemsetAsync(buf, 0, wct_style_state_floats(C) * sizeof(float), c->stream) != hipSuccess) { wct_set_error("hipMemsetAsync failed"); rc = WCT_ERR_HIP; break; }
-    if ((rc = ensure(c, c->wct_ws, wct_style_workspace_bytes(C, h * w, n.key)))) break;
-    ProfScope ps(c, kind == 2 ? 7 : 5, 0, 0);
-    WctCall r = ctx_call(c, kind == 1 ? WCT_MODE_NP : WCT_MODE_TF, WCT_STAGE_ALL);
-    r.eps = -1.f;
-    if ((rc = launch_style_state(taps[n.level], h * w, C, n.key, kind == 2, r, buf))) break;
   }
   if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) { wct_set_error("hipStreamSynchronize failed (prepared style)"); rc = WCT_ERR_HIP; }
   if (!rc) rc = eig_status(c);
   if (rc) {                                               // keep nothing of a failed fill
     hipStreamSynchronize(c->stream);
-    for (auto& lv : st->cache)
-      for (size_t i = lv.size(); i-- > 0;)
-        if (std::find(fresh.begin(), fresh.end(), lv[i].buf) != fresh.end()) { hipFree(lv[i].buf); lv.erase(lv.begin() + i); }
+    for (int g = 0; g < G; ++g)
+      for (auto& lv : group[g]->cache)
+        for (size_t i = lv.size(); i-- > 0;)
+          if (std::find(fresh.begin(), fresh.end(), lv[i].buf) != fresh.end()) { hipFree(lv[i].buf); lv.erase(lv.begin() + i); }
   }
   return rc;
 }
@@ -472,7 +541,7 @@ static int style_states(wct_ctx* c, int k, wct_style* st, int kind, const std::v
     else if (std::none_of(missing.begin(), missing.end(), [&](const StyleNeed& m) { return m.level == n.level && same_key(m.key, n.key); }))
       missing.push_back(n);
   }
-  TRY(style_fill(c, st, kind, missing));
+  TRY(style_fill(c, &st, 1, kind, &missing));
   bufs->clear();
   for (const StyleNeed& n : needs) {
     StyleState* e = state_find(st, n.level, n.key, kind);
@@ -493,43 +562,162 @@ static int style_flags_ok(unsigned flags) {
   return WCT_OK;
 }
 
-extern "C" int wct_style_prepare(wct_ctx* c, const uint8_t* style, int Hs, int Ws, const int* levels, int n_levels, unsigned flags,
-                                 wct_style** out) {
-  ARG_CHECK(c && style && levels && out && n_levels >= 1 && n_levels <= 16 && Hs >= 2 && Ws >= 2);
-  *out = nullptr;
+// The checks of the wct_style_prepare* calls before anything is staged (their pointers checked by the caller): the flags, the
+// levels (*set, *deepest), the size of the style, the encoder; then stale failures are reported
+static int prepare_checks(wct_ctx* c, int Hs, int Ws, const int* levels, int n_levels, unsigned flags, unsigned* set, int* deepest) {
   TRY(style_flags_ok(flags));
-  unsigned set = 0;
-  int deepest = 0;
+  *set = 0; *deepest = 0;
   for (int i = 0; i < n_levels; ++i) {
     ARG_CHECK(levels[i] >= 1 && levels[i] <= 5);
-    set |= 1u << levels[i];
-    deepest = std::max(deepest, levels[i]);
+    *set |= 1u << levels[i];
+    *deepest = std::max(*deepest, levels[i]);
   }
-  TRY(check_min_size("style", Hs, Ws, deepest));
+  TRY(check_min_size("style", Hs, Ws, *deepest));
   if (!c->enc_loaded) { wct_set_error("encoder weights not set (wct_set_encoder)"); return WCT_ERR_STATE; }
   HIP_TRY(hipSetDevice(c->device));
-  TRY(eig_stale(c));
-  std::unique_ptr<wct_style> owner(new wct_style());
-  wct_style* st = owner.get();
-  st->Hs = Hs; st->Ws = Ws; st->level_set = set;
+  return eig_stale(c);
+}
+
+// the source of a handle on the device: the host image (uint8, or fp32 with WCT_FLAG_IMAGES_F32) as fp32, and the label map if any
+static int source_upload(wct_ctx* c, const uint8_t* style, int Hs, int Ws, const uint8_t* map, unsigned flags,
+                         std::shared_ptr<StyleSource>* out) {
+  auto src = std::make_shared<StyleSource>();
   const size_t n = (size_t)Hs * Ws * 3;
-  HIP_TRY(hipMalloc((void**)&st->img, n * sizeof(float)));
+  HIP_TRY(hipMalloc((void**)&src->img, n * sizeof(float)));
   void* ds;
   TRY(stage_in(c, 1, style, n * sample_bytes(flags), &ds));
-  if (flags & WCT_FLAG_IMAGES_F32) HIP_TRY(hipMemcpyAsync(st->img, ds, n * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
-  else TRY(launch_u8_to_f32((const uint8_t*)ds, st->img, n, c->stream));
-  // the states of "a content as large as the style", in the mode the flags name; every other key on first use
-  ++c->style_clock;
-  std::vector<StyleNeed> needs;
+  if (flags & WCT_FLAG_IMAGES_F32) HIP_TRY(hipMemcpyAsync(src->img, ds, n * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+  else TRY(launch_u8_to_f32((const uint8_t*)ds, src->img, n, c->stream));
+  if (map) {
+    HIP_TRY(hipMalloc((void**)&src->map, (size_t)Hs * Ws));
+    HIP_TRY(hipMemcpyAsync(src->map, map, (size_t)Hs * Ws, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));             // (the caller's map may go once the call returns)
+  }
+  *out = std::move(src);
+  return WCT_OK;
+}
+
+// a handle of `set` on src (label < 0: the whole image; else the rows of `label` of the host map) with its rows per level counted;
+// *small: the first served level at which a region has fewer than 2 rows (0: none), its count in *small_rows
+static std::unique_ptr<wct_style> new_handle(const std::shared_ptr<StyleSource>& src, int Hs, int Ws, unsigned set, const uint8_t* map,
+                                             int label, int* small, int* small_rows) {
+  std::unique_ptr<wct_style> st(new wct_style());
+  st->Hs = Hs; st->Ws = Ws; st->level_set = set; st->src = src; st->label = label;
+  *small = 0;
   for (int l = 1; l <= 5; ++l) {
     if (!(set & (1u << l))) continue;
     int h, w;
     level_dims(Hs, Ws, l, &h, &w);
-    needs.push_back(StyleNeed{l, wct_style_key(LEVEL_C[l], h * w, h * w)});
+    st->rows[l] = label < 0 ? h * w : region_count(map, Hs, Ws, h, w, 1 << (l - 1), label);
+    if (st->rows[l] < 2 && !*small) { *small = l; *small_rows = st->rows[l]; }
   }
-  TRY(style_fill(c, st, style_kind(flags), needs));
+  return st;
+}
+
+// the states a handle is prepared with: those of "a content as large as the style", every other key on first use
+static std::vector<StyleNeed> prepare_needs(const wct_style* st) {
+  std::vector<StyleNeed> needs;
+  for (int l = 1; l <= 5; ++l) {
+    if (!(st->level_set & (1u << l))) continue;
+    int h, w;
+    level_dims(st->Hs, st->Ws, l, &h, &w);
+    needs.push_back(StyleNeed{l, wct_style_key(LEVEL_C[l], h * w, style_rows(st, l))});
+  }
+  return needs;
+}
+
+// wct_style_prepare (map null) and wct_style_prepare_region
+static int style_prepare(wct_ctx* c, const uint8_t* style, int Hs, int Ws, const uint8_t* map, int label, const int* levels, int n_levels,
+                         unsigned flags, wct_style** out) {
+  unsigned set;
+  int deepest, small, small_rows;
+  TRY(prepare_checks(c, Hs, Ws, levels, n_levels, flags, &set, &deepest));
+  std::shared_ptr<StyleSource> src;
+  if (map) {                                              // (counted before anything is staged: a refusal costs no upload)
+    std::unique_ptr<wct_style> probe = new_handle(src, Hs, Ws, set, map, label, &small, &small_rows);
+    if (small) {
+      wct_set_error("style region: label %d has %d rows at relu%d_1 of the %dx%d style (a region needs at least 2 at every level)", label,
+                    small_rows, small, Hs, Ws);
+      return WCT_ERR_ARG;
+    }
+  }
+  TRY(source_upload(c, style, Hs, Ws, map, flags, &src));
+  std::unique_ptr<wct_style> owner = new_handle(src, Hs, Ws, set, map, map ? label : -1, &small, &small_rows);
+  wct_style* st = owner.get();
+  ++c->style_clock;
+  const std::vector<StyleNeed> needs = prepare_needs(st);
+  TRY(style_fill(c, &st, 1, style_kind(flags), &needs));
   c->styles.push_back(st);
   *out = owner.release();
+  return WCT_OK;
+}
+
+extern "C" int wct_style_prepare(wct_ctx* c, const uint8_t* style, int Hs, int Ws, const int* levels, int n_levels, unsigned flags,
+                                 wct_style** out) {
+  ARG_CHECK(c && style && levels && out && n_levels >= 1 && n_levels <= 16 && Hs >= 2 && Ws >= 2);
+  *out = nullptr;
+  return style_prepare(c, style, Hs, Ws, nullptr, -1, levels, n_levels, flags, out);
+}
+
+static int region_map_ok(const uint8_t* map) {
+  if (map) return WCT_OK;
+  wct_set_error("style region: no label map");
+  return WCT_ERR_ARG;
+}
+
+extern "C" int wct_style_prepare_region(wct_ctx* c, const uint8_t* style, int Hs, int Ws, const uint8_t* map, int label, const int* levels,
+                                        int n_levels, unsigned flags, wct_style** out) {
+  ARG_CHECK(c && style && levels && out && n_levels >= 1 && n_levels <= 16 && Hs >= 2 && Ws >= 2);
+  *out = nullptr;
+  TRY(region_map_ok(map));
+  if (label < 0 || label >= WCT_MIX_MAX) { wct_set_error("style region: label %d, must be 0 .. %d", label, (int)WCT_MIX_MAX - 1); return WCT_ERR_ARG; }
+  return style_prepare(c, style, Hs, Ws, map, label, levels, n_levels, flags, out);
+}
+
+extern "C" int wct_style_prepare_regions(wct_ctx* c, const uint8_t* style, int Hs, int Ws, const uint8_t* map, int K, const int* levels,
+                                         int n_levels, unsigned flags, wct_style** out) {
+  ARG_CHECK(c && style && levels && out && n_levels >= 1 && n_levels <= 16 && Hs >= 2 && Ws >= 2);
+  if (K < 1 || K > WCT_MIX_MAX) { wct_set_error("style regions: K = %d regions, must be 1 .. %d", K, (int)WCT_MIX_MAX); return WCT_ERR_ARG; }
+  for (int k = 0; k < K; ++k) out[k] = nullptr;
+  TRY(region_map_ok(map));
+  TRY(mask_check(map, (size_t)Hs * Ws, K));
+  unsigned set;
+  int deepest;
+  TRY(prepare_checks(c, Hs, Ws, levels, n_levels, flags, &set, &deepest));
+  std::shared_ptr<StyleSource> src;
+  TRY(source_upload(c, style, Hs, Ws, map, flags, &src));
+  // a handle per region that can carry a style (>= 2 rows at every level); ONE fill for all of them
+  std::vector<std::unique_ptr<wct_style>> owners;
+  std::vector<wct_style*> group;
+  std::vector<std::vector<StyleNeed>> needs;
+  std::vector<int> label;
+  for (int k = 0; k < K; ++k) {
+    int small, small_rows;
+    std::unique_ptr<wct_style> st = new_handle(src, Hs, Ws, set, map, k, &small, &small_rows);
+    if (small) continue;
+    needs.push_back(prepare_needs(st.get()));
+    group.push_back(st.get());
+    label.push_back(k);
+    owners.push_back(std::move(st));
+  }
+  if (group.empty()) return WCT_OK;
+  ++c->style_clock;
+  TRY(style_fill(c, group.data(), (int)group.size(), style_kind(flags), needs.data()));
+  for (size_t g = 0; g < group.size(); ++g) {
+    c->styles.push_back(group[g]);
+    out[label[g]] = owners[g].release();
+  }
+  return WCT_OK;
+}
+
+extern "C" int wct_style_rows(wct_ctx* c, const wct_style* st, int level, int* n) {
+  ARG_CHECK(c && n);
+  TRY(style_live(c, st));
+  if (level < 1 || level > 5 || !(st->level_set & (1u << level))) {
+    wct_set_error("prepared style: relu%d_1 is not in the handle's level set", level);
+    return WCT_ERR_ARG;
+  }
+  *n = style_rows(st, level);
   return WCT_OK;
 }
 
@@ -563,7 +751,7 @@ static const float* no_style_at(int, int, int* hs, int* ws) { *hs = *ws = 0; ret
 
 // The states of K live handles for every level of `chain`, stamped with the running call (c->style_clock; the missing ones are
 // computed, which blocks): style k serves the layout of (content, style k).  refs[i].state[k] is the state of level i, and
-// ns[i * WCT_MIX_MAX + k] the rows of style k's feature map there.
+// ns[i * WCT_MIX_MAX + k] the rows of style k there (style_rows).
 static int chain_states(wct_ctx* c, const Chain& chain, const wct_style* const* styles, int K, int kind, std::vector<WctStyleRef>* refs,
                         std::vector<int>* ns) {
   const int n_levels = (int)chain.lv.size();
@@ -574,10 +762,9 @@ static int chain_states(wct_ctx* c, const Chain& chain, const wct_style* const* 
     std::vector<StyleNeed> needs;
     for (int i = 0; i < n_levels; ++i) {
       const ChainLevel& g = chain.lv[i];
-      int hs, ws;
-      level_dims(st->Hs, st->Ws, g.l, &hs, &ws);
-      (*ns)[(size_t)i * WCT_MIX_MAX + k] = hs * ws;
-      needs.push_back(StyleNeed{g.l, wct_style_key(g.C, g.h * g.w, hs * ws)});
+      const int rows = style_rows(st, g.l);
+      (*ns)[(size_t)i * WCT_MIX_MAX + k] = rows;
+      needs.push_back(StyleNeed{g.l, wct_style_key(g.C, g.h * g.w, rows)});
     }
     std::vector<const float*> bufs;
     TRY(style_states(c, k, st, kind, needs, &bufs));
@@ -1032,11 +1219,7 @@ static int stylize_prepared_masked_dev(wct_ctx* c, const void* content, int Hc, 
     const ChainLevel& g = chain.lv[i];
     for (int f = 0; f < B; ++f)
       mask_counts(masks + (size_t)f * Hc * Wc, Hc, Wc, g.h, g.w, 1 << (g.l - 1), K, &nk[i * fstride + (size_t)f * WCT_MIX_MAX]);
-    for (int k = 0; k < K; ++k) {
-      int hs, ws;
-      level_dims(styles[k]->Hs, styles[k]->Ws, g.l, &hs, &ws);
-      ns[(size_t)i * WCT_MIX_MAX + k] = hs * ws;
-    }
+    for (int k = 0; k < K; ++k) ns[(size_t)i * WCT_MIX_MAX + k] = style_rows(styles[k], g.l);
   }
 
   // the states of every live (level, frame, region), before any launch of the content chain

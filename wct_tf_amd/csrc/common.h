@@ -262,6 +262,8 @@ struct MaskGeom { const uint8_t* mask; int Hm, Wm, w, stride; };
 size_t mask_compact_workspace_bytes(int N, int G = 1);
 // stable partition of the N rows by label: perm [N] (the rows of label 0 in order, then label 1, ...), seg_off [K + 1]
 int launch_mask_compact(const MaskGeom& g, int N, int K, int* perm, int* seg_off, void* workspace, hipStream_t s);
+// a style region: the nk (host-counted) rows of label k of x [N][C] into xg [nk][C] in pixel order, from a compaction with K > k labels
+int launch_mask_gather_segment(const float* x, const int* perm, const int* seg_off, int k, int nk, int C, float* xg, hipStream_t s);
 size_t wct_masked_workspace_bytes(int C, int Nc, const int* nk, const int* Ns, int K);
 int launch_wct_masked(const float* content, int Nc, const MaskGeom& g, const int* nk, const float* const* styles, const int* Ns, int K,
                       int C, const WctCall& r);

@@ -130,6 +130,18 @@ __global__ __launch_bounds__(256) void mask_gather_kernel(const float* x, const 
   }
 }
 
+// xg[r] = x[perm[seg_off[k] + r]] for the rows of segment k ALONE, packed from row 0 of xg (a style region: n_k * C floats move,
+// not the whole map), 16-B accesses
+__global__ __launch_bounds__(256) void mask_gather_segment_kernel(const float* x, const int* perm, const int* seg_off, int k, int C, float* xg) {
+  const int cq = C / 4;
+  const int r0 = seg_off[k];
+  const size_t n4 = (size_t)(seg_off[k + 1] - r0) * cq;
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
+    const int r = (int)(i / cq), c = (int)(i % cq) * 4;
+    *reinterpret_cast<f32x4*>(xg + (size_t)r * C + c) = *reinterpret_cast<const f32x4*>(x + (size_t)perm[r0 + r] * C + c);
+  }
+}
+
 // the rows of the labels in `labs` (byte f, bit k: label k of frame f, a single pixel) pass through unchanged: x[perm[r]] -> out16 /
 // out32 row perm[r] of the frame
 struct SingleLabels { unsigned char frame[WCT_PLAN_PAIRS]; };
@@ -167,6 +179,15 @@ int launch_mask_compact_batch(const MaskGeom& g, int N, int K, int G, int* perm,
 
 int launch_mask_compact(const MaskGeom& g, int N, int K, int* perm, int* seg_off, void* workspace, hipStream_t s) {
   return launch_mask_compact_batch(g, N, K, 1, perm, seg_off, workspace, s);
+}
+
+// A style region: the nk rows of label k of x [N][C] (perm / seg_off: a compaction of the map with K > k labels) into xg [nk][C],
+// in pixel order.  nk is the caller's host count (it sizes the grid; the kernel reads the segment's bounds from seg_off).
+int launch_mask_gather_segment(const float* x, const int* perm, const int* seg_off, int k, int nk, int C, float* xg, hipStream_t s) {
+  ARG_CHECK(x && perm && seg_off && xg && k >= 0 && k < WCT_MIX_MAX && nk >= 1 && C >= 4 && C % 4 == 0);
+  hipLaunchKernelGGL(mask_gather_segment_kernel, dim3(rows_grid(nk, C)), dim3(256), 0, s, x, perm, seg_off, k, C, xg);
+  HIP_TRY(hipGetLastError());
+  return WCT_OK;
 }
 
 // The slot plan of a masked level: pair p = the p-th label with nk >= 2 rows, slot 2p its rows of the gathered buffer, slot

@@ -6,6 +6,7 @@ files (rank_shard); `--gpus N` without a launcher starts the N ranks itself.  `-
 stylizes with a weighted mix of the styles (Li et al. 2017, sec. 4.2; the reference's README TODO).
 `--mask-path M --mask-styles s0 s1 ...` stylizes each region of a grey label map with its own style (the same section,
 spatial control): grey value v is label v * K // 256 of K styles.
+`--style-masks m0 m1 ...` adds style regions: content region k takes its style from the pixels of style k labelled k.
 `--content-colors` keeps every content's colours by luminance-only transfer (Gatys et al. 2016): the result takes its own
 luminance and the content's chrominance.  Unlike `--keep-colors` (CORAL on the style) it leaves the style alone, so it goes
 with prepared styles and every other option.
@@ -67,6 +68,11 @@ _FLAGS = [
     (('--mask-styles',), dict(nargs='+', default=None, metavar='PATH',
                               help='the K style images of --mask-path, label 0 first; not with --style-path / -r / '
                                    '--interp-styles / --concat')),
+    (('--style-masks',), dict(nargs='+', default=None, metavar='PATH',
+                              help='style regions: one 8-bit grey label map per --mask-styles image (resized, nearest, to it; read '
+                                   'as --mask-path is: grey v is label v * K // 256), or - for the whole image.  Content region k then '
+                                   'takes its style from the pixels of style k labelled k.  The same image and map for several k '
+                                   '(one photo, one segmentation) is prepared once.  Not with --keep-colors or --swap5')),
     (('--alpha-map',), dict(default=None, metavar='PATH',
                             help='a strength map: an 8-bit grey image, resized (bilinear) to each content; white takes --alpha, '
                                  'black keeps the content, greys in between.  With --style-path; not with --swap5, '
@@ -317,6 +323,55 @@ def check_mask_args(parser, args):
         parser.error('--mask-styles takes at most 8 styles')
 
 
+def check_style_mask_args(parser, args):
+    """--style-masks: the argument errors of style regions (parser.error exits)."""
+    if getattr(args, 'style_masks', None) is None:
+        return
+    if args.mask_styles is None:
+        parser.error('--style-masks needs --mask-styles (and --mask-path): one label map per style of a masked run')
+    if len(args.style_masks) != len(args.mask_styles):
+        parser.error('--style-masks has %d maps for %d --mask-styles (one per style; - for the whole image)'
+                     % (len(args.style_masks), len(args.mask_styles)))
+    if args.keep_colors:
+        parser.error('--style-masks does not combine with --keep-colors (CORAL makes the style depend on the content)')
+    if args.swap5:
+        parser.error('--style-masks does not combine with --swap5 (style-swap needs the patches of a style image)')
+
+
+def prepare_style_regions(model, style_paths, styles, mask_paths, args):
+    """The K prepared styles of a run with --style-masks: style k from label k of its map (- : the whole image).  Entries with the
+    same image file and the same map file are prepared together, once (WCT.prepare_style_regions).  A region too small to carry a
+    style -- fewer than 2 feature pixels at some relu target -- falls back to its whole image, with one line on stderr."""
+    import sys
+    from .context import region_rows
+    if args.keep_colors or args.swap5:
+        raise ValueError('style regions do not combine with keep_colors (the style depends on the content) or swap5')
+    k = len(styles)
+    labels = [None if m == '-' else mask_labels(load_mask(m), k, styles[j].shape[:2]) for j, m in enumerate(mask_paths)]
+    handles = [None] * k
+    for j in range(k):
+        if handles[j] is not None:
+            continue
+        if labels[j] is not None and min(region_rows(labels[j], j, r) for r in model.relu_targets) < 2:
+            print('style region %d of %s is too small to carry a style: using the whole image' % (j, style_paths[j]), file=sys.stderr)
+            labels[j] = None
+        if labels[j] is None:
+            handles[j] = model.prepare_style(styles[j], adain=args.adain)
+            continue
+        same = [i for i in range(j, k) if (style_paths[i], mask_paths[i]) == (style_paths[j], mask_paths[j])
+                and min(region_rows(labels[j], i, r) for r in model.relu_targets) >= 2]
+        if len(same) > 1:
+            made = model.prepare_style_regions(styles[j], labels[j], k, adain=args.adain)
+            for i, h in enumerate(made):
+                if i in same:
+                    handles[i] = h
+                elif h is not None:
+                    h.close()
+        else:
+            handles[j] = model.prepare_style(styles[j], adain=args.adain, region=(labels[j], j))
+    return handles
+
+
 def mask_name(content_path, style_paths):
     """output file of a masked stylization: {content}_mask_{style0}+{style1}+...{ext of the content}"""
     return '%s_mask_%s%s' % (_stem(content_path), '+'.join(_stem(p) for p in style_paths), os.path.splitext(content_path)[1])
@@ -357,6 +412,7 @@ def main(argv=None):
     args = parser.parse_args(argv)
     check_interp_args(parser, args)
     check_mask_args(parser, args)
+    check_style_mask_args(parser, args)
     check_color_args(parser, args)
     check_guided_args(parser, args)
     check_band_args(parser, args)
@@ -402,7 +458,10 @@ def main(argv=None):
         grey = load_mask(args.mask_path)
         regions = [load_style(p, args) for p in args.mask_styles]
         # every style once for a folder of contents, not once per content (not with --keep-colors or --swap5: can_prepare)
-        prepared = [model.prepare_style(s, adain=args.adain) for s in regions] if can_prepare(args) and len(contents) > 1 else None
+        if args.style_masks is not None:                      # style regions live in handles: prepared even for one content
+            prepared = prepare_style_regions(model, args.mask_styles, regions, args.style_masks, args) if contents else None
+        else:
+            prepared = [model.prepare_style(s, adain=args.adain) for s in regions] if can_prepare(args) and len(contents) > 1 else None
         for cpath in contents:
             content = utils.get_img(cpath)
             if args.content_size > 0:

@@ -92,6 +92,9 @@ _FLAGS = [
     (('--mask-styles',), dict(nargs='+', default=None, metavar='PATH',
                               help='the K style images of --mask-path, label 0 first; replaces --style-path; not with '
                                    '--keep-colors, --swap5 or --concat')),
+    (('--style-masks',), dict(nargs='+', default=None, metavar='PATH',
+                              help='style regions: one 8-bit grey label map per --mask-styles image (read as --mask-path is), or - for '
+                                   'the whole image; frame region k takes its style from the pixels of style k labelled k')),
     (('--alpha-map',), dict(default=None, metavar='PATH',
                             help='a strength map: one 8-bit grey image for all frames, or a directory with one map per frame '
                                  '(matched to the frames in sorted order; the counts must agree), resized (bilinear) to the frame; '
@@ -222,9 +225,13 @@ def stylize_frames_masked(wct_model, frame_files, mask_files, styles, args):
     """Yield (frame_file, stylized uint8 image) in order, every frame stylized under its own label map: consecutive same-sized
     frames go through WCT.predict_frames_masked in batches, the K styles prepared once for the whole video.  Later --passes use
     the masked call too, the maps resized to each pass's input."""
-    from .stylize import load_mask, mask_labels, guided_of
+    from .stylize import load_mask, mask_labels, guided_of, prepare_style_regions
     k = len(styles)
-    prepared = [wct_model.prepare_style(np.uint8(np.clip(s, 0, 255)) if s.dtype != np.uint8 else s, adain=args.adain) for s in styles]
+    styles = [np.uint8(np.clip(s, 0, 255)) if s.dtype != np.uint8 else s for s in styles]
+    if getattr(args, 'style_masks', None) is not None:
+        prepared = prepare_style_regions(wct_model, args.mask_styles, styles, args.style_masks, args)
+    else:
+        prepared = [wct_model.prepare_style(s, adain=args.adain) for s in styles]
     greys = {}
 
     def grey_of(path):
@@ -363,6 +370,8 @@ def main(argv=None):
     parser = build_parser()
     args = parser.parse_args(argv)
     check_mask_args(parser, args)
+    from .stylize import check_style_mask_args
+    check_style_mask_args(parser, args)
     check_warm_args(parser, args)
     check_color_args(parser, args)
     check_guided_args(parser, args)

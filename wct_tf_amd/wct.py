@@ -5,6 +5,8 @@
     WCT.predict_mix(content, styles, weights=None, alpha=1, adain=False, swap5=False, ss_alpha=1) -> uint8 HxWx3
     WCT.predict_masked(content, styles, mask, alpha=1, adain=False, swap5=False, ss_alpha=1) -> uint8 HxWx3
     WCT.prepare_style(style) -> PreparedStyle, which predict / predict_frames / predict_mix take in the place of a style image
+    WCT.prepare_style(style, region=(label_map, label)) / prepare_style_regions(style, label_map, k): a style from a labelled part
+    of its image; predict_masked(..., style_masks=[...]) matches content region k with label k of style k
     every predict* takes content_colors=True: the frame keeps its luminance and takes the colours of its content
     WCT.synthesize(style, size, seeds=1, seed=0, passes=3) -> uint8 [n][Ho][Wo][3], textures of the style from seeded noise
     predict_frames(wrap=True) / synthesize(tile=True): the network on a torus -- tileable frames, seamless textures
@@ -22,7 +24,7 @@ import re
 
 import numpy as np
 
-from .context import Context, PreparedStyle, check_prepared, check_resize, check_texture, check_warm, check_wrap, split_styles
+from .context import Context, PreparedStyle, check_prepared, check_resize, check_texture, check_warm, check_wrap, region_rows, split_styles
 from .model import WCTModel
 from .weights import load_weights
 
@@ -137,14 +139,71 @@ class WCT(object):
             self.sess.set_style_swap(ss_alpha, self.ss_patch_size, self.ss_stride)
         return content, mask
 
-    def prepare_style(self, style, adain=False):
+    def prepare_style(self, style, adain=False, region=None):
         '''Run the style side of `style` (array in [0,255]) once, for this model's relu_targets, and keep it on the device: the
            PreparedStyle goes wherever predict, predict_frames, predict_mix, predict_masked and predict_frames_masked take a
            style image and gives the same frames bit for bit, without the style encoder pass, the style statistics and the style
            eigendecompositions of every call.  One handle serves every content size and alpha, AdaIN included (`adain` only
            picks what is computed up front; another content -- or region -- size is computed on first use and kept).  Not for
-           swap5.  Close it, or the model's context, to release it.'''
-        return self.sess.prepare_style(style, self.relu_targets, adain=adain, wct_mode=self.wct_mode)
+           swap5.  Close it, or the model's context, to release it.
+           region=(label_map, label): a style region -- label_map [H][W] integers of the style's size; the statistics of every
+           level come from the feature pixels of `label` alone (sky from the sky of a painting), the encoder still sees the
+           whole image.  A region needs 2 feature pixels at every relu target.'''
+        return self.sess.prepare_style(style, self.relu_targets, adain=adain, wct_mode=self.wct_mode, region=region)
+
+    def prepare_style_regions(self, style, label_map, k, adain=False):
+        '''The k regions of ONE style image (label_map [H][W], labels 0 .. k - 1) as prepared styles, from one encoder pass: a
+           list of k entries, entry j what prepare_style(style, region=(label_map, j)) gives bit for bit, or None for a region
+           too small to carry a style (fewer than 2 feature pixels at some relu target).'''
+        return self.sess.prepare_style_regions(style, label_map, k, self.relu_targets, adain=adain, wct_mode=self.wct_mode)
+
+    def _region_handles(self, styles, style_masks, swap5, adain):
+        '''The handles of predict_masked / predict_frames_masked with style_masks: style j from label j of style_masks[j] (None:
+           the whole image).  Everything is checked before anything is prepared (ValueError); entries that are the same image
+           and the same map are prepared together (prepare_style_regions).  A region too small to carry a style is a ValueError
+           naming it.  -> the K handles, owned by the caller'''
+        from ._lib import style_region_map
+        k = len(styles)
+        if swap5:
+            raise ValueError('swap5 is not served with style_masks: style-swap needs the patches of a style image, not a region\'s moments')
+        if len(style_masks) != k:
+            raise ValueError('%d style masks for %d styles (one map, or None, per style)' % (len(style_masks), k))
+        if any(isinstance(s, PreparedStyle) for s in styles):
+            raise ValueError('style_masks go with style images: a PreparedStyle already holds its region (prepare_style(region=...))')
+        styles = [np.asarray(s) for s in styles]
+        for j, (s, m) in enumerate(zip(styles, style_masks)):
+            if s.ndim != 3 or s.shape[2] != 3:
+                raise ValueError('expected an HxWx3 style image, got shape %s' % (s.shape,))
+            if m is not None:
+                m = style_region_map(m, s.shape[:2], label=j)
+                for r in self.relu_targets:
+                    if region_rows(m, j, r) < 2:
+                        raise ValueError('style region %d has %d feature pixels at %s: a region needs at least 2 at every relu target'
+                                         % (j, region_rows(m, j, r), r))
+        handles = [None] * k
+        try:
+            for j in range(k):
+                if handles[j] is not None:
+                    continue
+                if style_masks[j] is None:
+                    handles[j] = self.prepare_style(styles[j], adain=adain)
+                    continue
+                same = [i for i in range(j, k) if style_masks[i] is style_masks[j] and styles[i] is styles[j]]
+                if len(same) > 1 and np.asarray(style_masks[j]).max() < k:
+                    made = self.prepare_style_regions(styles[j], style_masks[j], k, adain=adain)
+                    for i, h in enumerate(made):
+                        if i in same:
+                            handles[i] = h
+                        elif h is not None:
+                            h.close()
+                else:
+                    handles[j] = self.prepare_style(styles[j], adain=adain, region=(style_masks[j], j))
+            return handles
+        except Exception:
+            for h in handles:
+                if h is not None:
+                    h.close()
+            raise
 
     def warm_state(self):
         '''A WarmState for this model's relu_targets: hand it to predict / predict_frames (with a PreparedStyle) as `warm=` and
@@ -284,16 +343,30 @@ class WCT(object):
                                      wct_mode=self.wct_mode, swap5=bool(swap5), content_colors=content_colors, guided=guided)
 
     def predict_masked(self, content, styles, mask, alpha=1, adain=False, swap5=False, ss_alpha=1, content_colors=False,
-                       guided=None):
+                       guided=None, style_masks=None):
         '''Stylize each region of a label map with its own style (Li et al. 2017, sec. 4.2, Fig. 7; the reference's README TODO
            "Spatial control/masking"): `mask` [H][W] holds a label 0 .. K-1 per content pixel, `styles` K images (sizes may
            differ), and at every level the pixels of label k are transformed with style k alone, with their own statistics
            (a label with fewer than 2 pixels at a level keeps that level's features).  Arrays in [0,255], returns uint8 HxWx3.
            One style with an all-zero mask gives predict(content, style) bit for bit.  swap5 takes one style only.
            `styles` may be K PreparedStyle objects (prepare_style) instead: the same frame, without the K style sides; the
-           entries are all handles or all images (a mixed list is a ValueError), and swap5 takes images.'''
+           entries are all handles or all images (a mixed list is a ValueError), and swap5 takes images.
+           style_masks: one label map [Hs][Ws] (of style k's size), or None, per style image -- style k is then taken from the
+           pixels of ITS image labelled k (semantic matching: content region k from style region k), prepared here for the call
+           (prepare_style(region=...)).  Not with swap5 or PreparedStyle entries: ValueError.'''
         from ._lib import mask_labels
         guided = self._check_guided(guided)
+        if style_masks is not None:
+            styles = list(styles)
+            content = np.asarray(content)
+            mask = mask_labels(mask, len(styles), content.shape[:2])            # ValueError before any GPU call
+            own = self._region_handles(styles, list(style_masks), swap5, adain)
+            try:
+                return self.sess.stylize_prepared_masked(content, own, mask, self.relu_targets, alpha=alpha, adain=adain,
+                                                         wct_mode=self.wct_mode, content_colors=content_colors, guided=guided)
+            finally:
+                for h in own:
+                    h.close()
         handles, styles = split_styles(list(styles))             # ValueError: images and prepared styles in one list
         content = np.asarray(content)
         if handles:
@@ -310,12 +383,13 @@ class WCT(object):
                                         wct_mode=self.wct_mode, swap5=bool(swap5), content_colors=content_colors, guided=guided)
 
     def predict_frames_masked(self, frames, styles, masks, alpha=1, adain=False, batch=16, content_colors=False, resize=None,
-                              guided=None):
+                              guided=None, style_masks=None):
         '''Spatial control of a video: same-sized frames [F][H][W][3], a label map per frame `masks` [F][H][W] (or one [H][W] map
            used for every frame), `styles` K images -- prepared once here -- or K PreparedStyle objects.  Frame f equals
            predict_masked(frames[f], styles, masks[f]) bit for bit; the frames go through the device in batches of `batch`
            (<= 32), the regions of a batch sharing every launch and the eigensolves.  Returns uint8 [F][Ho][Wo][3].
-           resize (h, w): as in predict_frames; the label maps are given at the resized size.'''
+           resize (h, w): as in predict_frames; the label maps are given at the resized size.
+           style_masks: as in predict_masked -- one label map or None per style image, style k from label k of its map.'''
         from ._lib import mask_labels_frames
         guided = self._check_guided(guided)
         frames = np.asarray(frames)
@@ -330,10 +404,13 @@ class WCT(object):
             check_prepared(self.sess, handles, self.relu_targets)
         if frames.dtype != np.uint8:
             frames = np.uint8(np.clip(frames, 0, 255))
-        own = [] if handles else [self.prepare_style(np.asarray(s), adain=adain) for s in images]
+        if style_masks is not None:
+            own = self._region_handles(list(styles), list(style_masks), False, adain)
+        else:
+            own = [] if handles else [self.prepare_style(np.asarray(s), adain=adain) for s in images]
         try:
             batch = max(1, min(32, int(batch)))
-            return np.concatenate([self.sess.stylize_prepared_masked_batch(frames[i:i + batch], handles or own, masks[i:i + batch],
+            return np.concatenate([self.sess.stylize_prepared_masked_batch(frames[i:i + batch], own or handles, masks[i:i + batch],
                                                                            self.relu_targets, alpha=alpha, adain=adain,
                                                                            wct_mode=self.wct_mode, content_colors=content_colors, guided=guided,
                                                                            resize=resize)
