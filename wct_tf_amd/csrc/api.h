@@ -224,6 +224,10 @@ struct Chain { std::vector<ChainLevel> lv; int Ho, Wo; };
 int chain_geometry(int Hc, int Wc, const int* levels, int n_levels, Chain* out);
 int run_conv(wct_ctx* c, const ConvLayer& l, const half_t* x, half_t* y16, float* y32, int B, int H, int W, int upsample, int relu,
              int pool = 0, float* usum = nullptr, unsigned* umax = nullptr, bool tap_layer = false);
+// run_encoder: taps32[l] the fp32 tap of relu<l>_1 or null; usum[l] / umax[l] the statistics of a tap, taken by the epilogue that
+// writes it.  Level 1 alone also takes usum[1] WITHOUT taps32[1] (a level 1 whose readers compute relu1_1 from the image): the
+// unit sums are then taken and no fp32 map is stored, and conv1_1 stays a launch of its own -- it is NOT moved into conv1_2's
+// loader as it is when neither is given -- which writes the fp16 map for conv1_2 (deepest = 1: nothing at all).
 int run_encoder(wct_ctx* c, const float* img, int B, int H, int W, int clamp01, int deepest, float* const taps32[6],
                 float* const* usum = nullptr, unsigned* const* umax = nullptr);
 int run_decoder(wct_ctx* c, int level, const half_t* feat16, int B, int h, int w, float* img_out);
@@ -231,7 +235,8 @@ int run_transform(wct_ctx* c, const float* fc, int Nc, const float* fs, int Ns, 
                   half_t* out16, float* out32, int* sweeps_dev, const WctFeatStats* st = nullptr,
                   const WctStyleRef* prep = nullptr /* a prepared style: fs may be null */,
                   const WctWarmRef* warm = nullptr /* a warm state's basis for this level */,
-                  const WctStrength* sm = nullptr /* a strength map per pair: the blend moves into the apply's rows */);
+                  const WctStrength* sm = nullptr /* a strength map per pair: the blend moves into the apply's rows */,
+                  const WctImageSrc* src = nullptr /* relu1_1: covariance and apply from the images; fc and fs may be null */);
 int mix_weights(const float* weights, int K, float* lambda);
 int run_transform_mix(wct_ctx* c, const float* fc, int Nc, const float* const* fs, const int* Ns, int K, const float* lambda, int C,
                       float alpha, unsigned flags, float eps, half_t* out16, float* out32, int* sweeps_dev,

@@ -69,15 +69,19 @@ int run_encoder(wct_ctx* c, const float* img, int B, int H, int W, int clamp01, 
   // loader (ConvArgs::img1) -- the 64-channel full-resolution map is neither written nor read, and the bits are the same.
   // (WCT_FUSE_CONV1=0: the two launches; test hook, read once per process)
   static const int fuse_conv1_env = getenv("WCT_FUSE_CONV1") ? atoi(getenv("WCT_FUSE_CONV1")) : 1;
-  const bool fuse_conv1 = fuse_conv1_env && deepest > 1 && !taps32[1];
+  // usum[1] without taps32[1]: the statistics of relu1_1 without the fp32 tap -- a level 1 whose readers compute relu1_1 from the
+  // image themselves (WctImageSrc).  conv1_1 then stays a launch of its own, which takes the unit sums beside the fp16 map it
+  // writes for conv1_2 (deepest = 1: the statistics alone, nothing stored): cheaper than the fused launch and a statistics pass.
+  const bool stats1 = usum && usum[1] && !taps32[1];
+  const bool fuse_conv1 = fuse_conv1_env && deepest > 1 && !taps32[1] && !stats1;
   if (!fuse_conv1) {
     ConvFirstArgs a;
     a.x = img; a.wfrag = c->first_w; a.bias = c->first_b;
     a.y16 = deepest > 1 ? cur : nullptr; a.y32 = taps32[1];
     a.B = B; a.H = H; a.W = W; a.clamp01 = clamp01;
-    a.usum = usum && taps32[1] ? usum[1] : nullptr; a.umax = a.usum ? umax[1] : nullptr;
+    a.usum = usum && (taps32[1] || stats1) ? usum[1] : nullptr; a.umax = a.usum ? umax[1] : nullptr;
     const double px = (double)B * H * W;
-    ProfScope ps(c, 1, 2.0 * px * 27 * 64, px * (12 + 64 * ((a.y16 ? 2 : 0) + (a.y32 ? 4 : 0))));
+    ProfScope ps(c, 1, 2.0 * px * 27 * 64, px * (12 + 64 * ((a.y16 ? 2 : 0) + (a.y32 ? 4 : 0)) + (stats1 ? 64 * 4 / 16.0 : 0)));
     TRY(launch_conv_first(a, c->stream));
   }
   if (deepest == 1) return WCT_OK;
@@ -140,17 +144,22 @@ int run_decoder(wct_ctx* c, int level, const half_t* feat16, int B, int h, int w
 
 int run_transform(wct_ctx* c, const float* fc, int Nc, const float* fs, int Ns, int C, int P, float alpha, unsigned flags, float eps,
                   half_t* out16, float* out32, int* sweeps_dev, const WctFeatStats* st, const WctStyleRef* prep, const WctWarmRef* warm,
-                  const WctStrength* sm) {
+                  const WctStrength* sm, const WctImageSrc* src) {
+  ARG_CHECK(!src || !(flags & WCT_FLAG_ADAIN));
   const WctSkip skip = (flags & WCT_FLAG_STYLE_SHARED) ? WCT_SKIP_SHARED_STYLE : WCT_SKIP_NONE;
   // (a strength map: the apply's epilogue reads the fp32 features once more, and one byte per pixel)
-  const StageCost cost = {(double)P * 2.0 * C * C * ((double)Nc + Ns), (double)P * 2.0 * ((double)Nc + Ns) * C * 4,
-                          (double)P * (2.0 * C * C * Nc + 6.0 * C * C * C),
+  // (src: the covariance and the apply read the images, 12 bytes a row -- the covariance the unit sums as well -- instead of the
+  //  256-byte rows, and add conv1_1's products)
+  const StageCost cost = {(double)P * 2.0 * C * (C + (src ? 27 : 0)) * ((double)Nc + Ns),
+                          (double)P * ((double)Nc + Ns) * (src ? 12 + C * 4 / 16.0 : 2.0 * C * 4),
+                          (double)P * (2.0 * C * (C + (src ? 27 : 0)) * Nc + 6.0 * C * C * C),
+                          src ? (double)P * Nc * (12 + C * ((out16 ? 2 : 0) + (out32 ? 4 : 0))) :
                           (double)P * Nc * C * (4 + (out16 ? 2 : 0) + (out32 ? 4 : 0) + (sm ? 4 : 0)) + (sm ? (double)P * Nc : 0.0),
                           (double)P * (2.0 * Nc + 2.0 * Ns) * C * 4 + (double)P * Nc * C * 6 + (sm ? (double)P * Nc : 0.0)};
   return run_stages(c, wct_workspace_bytes(C, Nc, Ns, P), flags, cost, [&](WctCall r) {
     r.alpha = alpha; r.eps = r.stages ? eps : 1e-5f; r.out16 = out16; r.out32 = out32; r.sweeps_dev = sweeps_dev;
     if (!r.stages) return launch_adain(fc, Nc, fs, Ns, C, P, skip, r, st, prep, sm);
-    return launch_wct(fc, Nc, fs, Ns, C, P, skip, r, st, prep, warm, sm);
+    return launch_wct(fc, Nc, fs, Ns, C, P, skip, r, st, prep, warm, sm, src);
   });
 }
 

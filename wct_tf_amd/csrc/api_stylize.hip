@@ -71,15 +71,21 @@ static bool fuse_stats() {
 // eps_q), and the colour op, if flagged too, runs after that as the stand-alone uint8 kernel.
 template <typename StyleAt, typename Transform>
 static int stylize_levels(wct_ctx* c, const float* img_c, const void* content_raw, int B, const Chain& chain, unsigned flags,
-                          size_t umax_clear, int clear_from, StyleAt&& style_at, Transform&& transform, uint8_t* out) {
+                          size_t umax_clear, int clear_from, StyleAt&& style_at, Transform&& transform, uint8_t* out,
+                          bool l1_img = false) {
   unsigned* const umax_c = (unsigned*)c->umax.p;
   const float* cur = img_c;
   for (int i = 0; i < (int)chain.lv.size(); ++i) {
     const ChainLevel& g = chain.lv[i];
     const int l = g.l, C = g.C, h = g.h, w = g.w;
-    TRY(ensure(c, c->feat_c, (size_t)B * h * w * C * 4));
+    // l1_img (wct_stylize_batch_dev): the transform of relu1_1 computes its rows from the level's input image -- no tap, the
+    // encoder pass leaves the unit sums alone and c->feat_c is not grown for the level
+    const bool from_image = l == 1 && l1_img;
     float* ctaps[6] = {};
-    ctaps[l] = (float*)c->feat_c.p;
+    if (!from_image) {
+      TRY(ensure(c, c->feat_c, (size_t)B * h * w * C * 4));
+      ctaps[l] = (float*)c->feat_c.p;
+    }
     float* us_c[6] = {};
     unsigned* um_c[6] = {};
     if (fuse_stats() && w % 16 == 0) {
@@ -167,6 +173,17 @@ extern "C" int wct_stylize_batch_dev(wct_ctx* c, const uint8_t* content, int Hc,
   TRY(ensure(c, c->umax, 7 * UROW * sizeof(unsigned)));
   unsigned* const umax_c = (unsigned*)c->umax.p;                    // row 0: content (per level), rows 1..5: style levels
   if (want_stats) HIP_TRY(hipMemsetAsync(c->umax.p, 0, 7 * UROW * sizeof(unsigned), c->stream));
+  // relu1_1 from the images: plain WCT with the epilogue statistics on, every width at level 1 a multiple of
+  // 16.  The style's fp32 relu1_1 is then never stored -- its conv1_1 pass takes the unit sums beside the fp16 map conv1_2 reads
+  // (run_encoder: unit sums without a tap) -- and the covariance of both sides is computed from the images.
+  // (WCT_L1_FROM_IMAGE=0: the stored map; test hook, read once per process)
+  static const int l1_env = getenv("WCT_L1_FROM_IMAGE") ? atoi(getenv("WCT_L1_FROM_IMAGE")) : 1;
+  bool l1_img = false;
+  if (l1_env && want_stats && !(flags & WCT_FLAG_ADAIN) && Ws % 16 == 0)
+    for (const ChainLevel& g : chain.lv)
+      if (g.l == 1) l1_img = true;
+  for (const ChainLevel& g : chain.lv)
+    if (g.l == 1 && g.W % 16 != 0) l1_img = false;
   // ONE style pass with a tap per requested level (model.py:69-75)
   float* taps[6] = {};
   float* us_s[6] = {};
@@ -175,8 +192,10 @@ extern "C" int wct_stylize_batch_dev(wct_ctx* c, const uint8_t* content, int Hc,
     const int l = levels[i];
     int h, w;
     level_dims(Hs, Ws, l, &h, &w);
-    TRY(ensure(c, c->feat_s[l], (size_t)Bs * h * w * LEVEL_C[l] * 4));
-    taps[l] = (float*)c->feat_s[l].p;
+    if (!(l == 1 && l1_img)) {
+      TRY(ensure(c, c->feat_s[l], (size_t)Bs * h * w * LEVEL_C[l] * 4));
+      taps[l] = (float*)c->feat_s[l].p;
+    }
     if (want_stats && w % 16 == 0) {
       TRY(ensure(c, c->usum_s[l], (size_t)Bs * h * (w / 16) * LEVEL_C[l] * 4));
       us_s[l] = (float*)c->usum_s[l].p; um_s[l] = umax_c + UROW * l;
@@ -190,13 +209,20 @@ extern "C" int wct_stylize_batch_dev(wct_ctx* c, const uint8_t* content, int Hc,
     return (const float*)c->feat_s[l].p + (size_t)(shared ? 0 : b) * *hs * *ws * LEVEL_C[l];
   };
   return stylize_levels(c, img_c, content, B, chain, flags, UROW * sizeof(unsigned), 1, style_at,
-                        [&](int, const ChainLevel& g, WctFeatStats st) {
+                        [&](int i, const ChainLevel& g, WctFeatStats st) {
                           int hs, ws;
                           const float* fs = style_at(g.l, 0, &hs, &ws);
                           st.u[1] = us_s[g.l]; st.umax[1] = um_s[g.l];
+                          if (g.l == 1 && l1_img) {
+                            // level i encodes the contents (i = 0) or the previous level's decoded images, clamped (stylize_levels)
+                            const float* in = i == 0 ? img_c : (const float*)c->img_t[(i - 1) & 1].p;
+                            const WctImageSrc src = {{{in, g.H, g.W, i > 0}, {img_s, Hs, Ws, 0}}, c->first_w, c->first_b};
+                            return run_transform(c, nullptr, g.h * g.w, nullptr, hs * ws, g.C, B, alpha, flags, -1.f,
+                                                 (half_t*)c->wct_out.p, nullptr, nullptr, &st, nullptr, nullptr, nullptr, &src);
+                          }
                           return run_transform(c, (float*)c->feat_c.p, g.h * g.w, fs, hs * ws, g.C, B, alpha, flags, -1.f,
                                                (half_t*)c->wct_out.p, nullptr, nullptr, &st);
-                        }, out);
+                        }, out, l1_img);
 }
 
 extern "C" int wct_stylize(wct_ctx* c, const uint8_t* content, int Hc, int Wc, const uint8_t* style, int Hs, int Ws,

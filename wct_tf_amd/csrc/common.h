@@ -46,10 +46,11 @@ static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 constexpr size_t WCT_LAUNCH_BYTES = (size_t)1 << 31;
 static inline bool launch_map_fits(size_t elems, size_t bytes) { return elems * bytes < WCT_LAUNCH_BYTES; }
 
-// Environment variables: the library reads four TEST hooks and nothing else, all safe by construction (a library whose
+// Environment variables: the library reads five TEST hooks and nothing else, all safe by construction (a library whose
 // contract is bit-reproducible output must not change its numerics on a stray variable): WCT_JACOBI_MAX_SWEEPS can only
-// LOWER the sweep budget (clamped to the compiled one; the solve then fails loudly, never silently); WCT_FUSE_STATS=0 and
-// WCT_FUSE_CONV1=0 each select a path whose output is bit-identical (asserted by tests/test_gpu_pipeline.py); WCT_WINOGRAD=0
+// LOWER the sweep budget (clamped to the compiled one; the solve then fails loudly, never silently); WCT_FUSE_STATS=0,
+// WCT_FUSE_CONV1=0 and WCT_L1_FROM_IMAGE=0 each select a path whose output is bit-identical (asserted by
+// tests/test_gpu_pipeline.py and tests/test_gpu_level1_image.py); WCT_WINOGRAD=0
 // keeps every 3x3 layer on the direct kernel (the round-5 arithmetic: other roundings, same tolerances).  The A-B switches of
 // the tuning rounds and the variants they selected were removed after round 6.
 
@@ -108,8 +109,8 @@ struct ConvFirstArgs {   // 3 -> 64 with the 1x1 'preprocess' folded in
   float* y32;
   int B, H, W;
   int clamp01;         // clip(x,0,1) at load (model.py:86)
-  float* usum;         // as in ConvArgs (with y32; W % 16 == 0)
-  unsigned* umax;
+  float* usum;         // as in ConvArgs (W % 16 == 0), of the fp32 values whether y32 stores them or not; y16 and y32 both
+  unsigned* umax;      // null: the statistics alone (conv_first_kernel<false>)
 };
 
 // Sums over the 16 lanes of a DPP row (= the 16 pixels of one row of an MFMA pixel tile), the same bits in every
@@ -191,6 +192,14 @@ enum { WCT_MODE_NP = 0, WCT_MODE_TF = 1 };
 // whose u is null is summed from the features themselves (same bits either way, colsum_kernel).
 struct WctFeatStats { const float* u[2]; const unsigned* umax[2]; };
 
+// relu1_1 computed where it is read: the 64-channel map of a side is what conv1_1 makes of an image, so a reader
+// that has the image and conv1_1's parameters needs no stored map.  side[0] content, side[1] style: img [P][H][W][3] fp32 (a shared
+// style: one image), row n of the side's feature matrix is pixel (n / W, n % W); W a multiple of 16 (the unit sums the means come
+// from); wfrag / bias: ConvFirstArgs'.  Given to launch_wct, the covariance of BOTH sides and the apply's content rows are taken
+// from the images (C = 64, the statistics of both sides in `stats`): neither feature pointer is read, both may be null.
+struct WctImageSide { const float* img; int H, W, clamp01; };
+struct WctImageSrc { WctImageSide side[2]; const half_t* wfrag; const float* bias; };
+
 // Prepared styles (wct.hip): a STATE is the style side of one level for one layout and mode -- [mean C][var C][Tcs C x C] floats
 // (var for AdaIN, Tcs for WCT).  Its bits depend on the slab count and K-slices of the (content, style) pair it serves: the key.
 struct WctStyleKey { int nslab, nsplit, ksplit; };
@@ -240,7 +249,8 @@ int launch_style_state(const float* style, int Ns, int C, const WctStyleKey& key
 // style only).  sm: a strength map per pair (Nc a multiple of sm->w).  Each of the four may be null.
 size_t wct_workspace_bytes(int C, int Nc, int Ns, int P);
 int launch_wct(const float* content, int Nc, const float* style, int Ns, int C, int P, WctSkip skip, const WctCall& r,
-               const WctFeatStats* stats, const WctStyleRef* prep, const WctWarmRef* warm, const WctStrength* sm = nullptr);
+               const WctFeatStats* stats, const WctStyleRef* prep, const WctWarmRef* warm, const WctStrength* sm = nullptr,
+               const WctImageSrc* src = nullptr /* relu1_1 from the images (plain pairs or a shared style) */);
 int launch_adain(const float* content, int Nc, const float* style, int Ns, int C, int P, WctSkip skip, const WctCall& r,
                  const WctFeatStats* stats, const WctStyleRef* prep, const WctStrength* sm = nullptr);
 // Style mix (Li et al. 2017, sec. 4.2): out = sum_k lambda[k] T(content, styles[k]) for K <= WCT_MIX_MAX styles of any sizes

@@ -14,6 +14,7 @@
 // the epilogue stores 8 B (fp16) / 16 B (fp32) per lane.
 #include "common.h"
 #include "conv_tile.h"          // TW, PITCH, BK, u32x4, h2, reflect_idx: shared with conv_wino.hip
+#include "conv_first_tile.h"    // conv1_1's tile arithmetic: shared with the kernels that compute relu1_1 where it is read
 
 // ---------------------------------------------------------------------------
 // generic 3x3 conv, Cin % 32 == 0, Cout % BN == 0
@@ -576,7 +577,10 @@ int launch_conv3x3(const ConvArgs& a, hipStream_t s) {
 // per-wave LDS transpose and leave as whole pixel rows (256 B fp32 / 128 B fp16): every store
 // instruction writes 1 KiB of contiguous memory.
 // k = ky*9 + kx*3 + c: a patch row [px][3] holds the 9 values of a ky contiguously.
+// STORE = false: the statistics alone (y16 and y32 both null: usum / umax of a map that its readers compute from the image
+// themselves) -- no transpose, no stores of the map, and no LDS for them.
 // ---------------------------------------------------------------------------
+template <bool STORE>
 __global__ __launch_bounds__(256) void conv_first_kernel(ConvFirstArgs p, int strips_x) {
   // One block walks a strip of CF_TILES horizontally adjacent 16x16 pixel tiles (x 64 channels); wave w owns pixel
   // rows 4w..4w+3 of a tile (two 2x16 MFMA pixel tiles).  The next tile's 18x18x3 halo patch is fetched into
@@ -584,7 +588,7 @@ __global__ __launch_bounds__(256) void conv_first_kernel(ConvFirstArgs p, int st
   // addresses) is paid once per strip.
   constexpr int CF_TILES = 4, PATCH_N = 18 * 18 * 3, PER = (PATCH_N + 255) / 256;
   __shared__ float patch[PATCH_N + 4];         // [972] stays 0: the target of the padded k = 27..31
-  __shared__ __attribute__((aligned(16))) unsigned char tr[4][32 * 256];   // per wave: 32 pixels x 64 ch fp32
+  __shared__ __attribute__((aligned(16))) unsigned char tr[4][STORE ? 32 * 256 : 16];   // per wave: 32 pixels x 64 ch fp32
   typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int sx = blockIdx.x % strips_x, ty = blockIdx.x / strips_x;
@@ -606,8 +610,7 @@ __global__ __launch_bounds__(256) void conv_first_kernel(ConvFirstArgs p, int st
   auto fetch = [&](int x0) {
 #pragma unroll
     for (int i = 0; i < PER; ++i) {
-      float v = xb[((size_t)e_row[i] + reflect_idx(x0 - 1 + e_px[i], p.W)) * 3 + e_c[i]];
-      pre[i] = p.clamp01 ? fminf(fmaxf(v, 0.f), 1.f) : v;
+      pre[i] = conv1_fetch(xb[((size_t)e_row[i] + reflect_idx(x0 - 1 + e_px[i], p.W)) * 3 + e_c[i]], p.clamp01);
     }
   };
   auto park = [&]() {
@@ -618,13 +621,7 @@ __global__ __launch_bounds__(256) void conv_first_kernel(ConvFirstArgs p, int st
   fetch(sx * CF_TILES * 16);
   // weight fragments [cout tile][k-step][hi/lo][lane][8]: 8 coalesced 1-KiB loads, register-resident
   half8 wh[2][2], wl[2][2];
-#pragma unroll
-  for (int t = 0; t < 2; ++t)
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      wh[t][ks] = *reinterpret_cast<const half8*>(p.wfrag + (((t * 2 + ks) * 2 + 0) * 64 + lane) * 8);
-      wl[t][ks] = *reinterpret_cast<const half8*>(p.wfrag + (((t * 2 + ks) * 2 + 1) * 64 + lane) * 8);
-    }
+  conv1_weights(p.wfrag, lane, wh, wl);
   const int frag_px = lane & 15, frag_py = (lane & 31) >> 4, kgrp = lane >> 5;
   // byte address of patch element k of this lane's pixel in tile row pair 0 of the wave (mt adds an immediate)
   int addr[2][8];
@@ -654,28 +651,11 @@ __global__ __launch_bounds__(256) void conv_first_kernel(ConvFirstArgs p, int st
 #pragma unroll
   for (int mt = 0; mt < 2; ++mt) {
     f32x16 acc[2];
-#pragma unroll
-    for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[nt][r] = 0.f;
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      half8 bh, bl;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        // the padded-k slot must not move with mt: its address is absolute
-        const int off = (ks * 16 + kgrp * 8 + j < 27) ? mt * 2 * 54 * 4 : 0;
-        const float v = *reinterpret_cast<const float*>(pb + addr[ks][j] + off);
-        bh[j] = (half_t)v;
-        bl[j] = (half_t)(v - (float)bh[j]);
-      }
-#pragma unroll
-      for (int nt = 0; nt < 2; ++nt) {
-        acc[nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wl[nt][ks], bh, acc[nt], 0, 0, 0);
-        acc[nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh[nt][ks], bl, acc[nt], 0, 0, 0);
-        acc[nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh[nt][ks], bh, acc[nt], 0, 0, 0);
-      }
-    }
+    conv1_tile(wh, wl, [=](int ks, int j) {
+      // the padded-k slot must not move with mt: its address is absolute
+      const int off = (ks * 16 + kgrp * 8 + j < 27) ? mt * 2 * 54 * 4 : 0;
+      return *reinterpret_cast<const float*>(pb + addr[ks][j] + off);
+    }, acc);
     // transpose through LDS: pixel row = 64 fp32 = 16 pieces of 16 B, piece index XOR (pixel & 15)
     const int px = lane & 31;
 #pragma unroll
@@ -684,9 +664,9 @@ __global__ __launch_bounds__(256) void conv_first_kernel(ConvFirstArgs p, int st
       for (int rq = 0; rq < 4; ++rq) {
         f32x4 v;
 #pragma unroll
-        for (int j = 0; j < 4; ++j) v[j] = fmaxf(acc[nt][rq * 4 + j] + bias[nt][rq][j], 0.f);
+        for (int j = 0; j < 4; ++j) v[j] = conv1_act(acc[nt][rq * 4 + j], bias[nt][rq][j]);
         const int piece = nt * 8 + 2 * rq + kgrp;
-        *reinterpret_cast<f32x4*>(wt + (px * 16 + (piece ^ (px & 15))) * 16) = v;
+        if (STORE) *reinterpret_cast<f32x4*>(wt + (px * 16 + (piece ^ (px & 15))) * 16) = v;
         if (p.usum) {                          // uniform; statistics of the fp32 tap as in conv_epilogue_t
           f32x4 t = v;
           unit_row_sum4(t);
@@ -698,6 +678,7 @@ __global__ __launch_bounds__(256) void conv_first_kernel(ConvFirstArgs p, int st
           }
         }
       }
+    if (!STORE) continue;
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     const int oy0 = y0 + wave * 4 + mt * 2;
@@ -739,9 +720,11 @@ __global__ __launch_bounds__(256) void conv_first_kernel(ConvFirstArgs p, int st
 
 int launch_conv_first(const ConvFirstArgs& a, hipStream_t s) {
   ARG_CHECK(a.H > 1 && a.W > 1 && a.B > 0);
-  ARG_CHECK(!a.usum || (a.y32 && a.umax && a.W % 16 == 0));
+  ARG_CHECK(!a.usum || (a.umax && a.W % 16 == 0));     // statistics: of the fp32 values, stored or not
+  ARG_CHECK(a.y16 || a.y32 || a.usum);
   const int strips_x = cdiv(a.W, 64), tiles_y = cdiv(a.H, 16);
-  hipLaunchKernelGGL(conv_first_kernel, dim3(strips_x * tiles_y, a.B), dim3(256), 0, s, a, strips_x);
+  if (a.y16 || a.y32) hipLaunchKernelGGL(conv_first_kernel<true>, dim3(strips_x * tiles_y, a.B), dim3(256), 0, s, a, strips_x);
+  else hipLaunchKernelGGL(conv_first_kernel<false>, dim3(strips_x * tiles_y, a.B), dim3(256), 0, s, a, strips_x);
   HIP_TRY(hipGetLastError());
   return WCT_OK;
 }

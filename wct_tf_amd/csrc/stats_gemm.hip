@@ -3,6 +3,8 @@
 // been: hipcc inlines the small helpers (skip_style_mat, the blockIdx getters) in the order a unit first uses them, and
 // gemm_f32_kernel alone in a unit comes out with other -- equivalent -- branches around skip_style_mat.
 #include "wct_stages.h"
+#include "conv_first_tile.h"    // conv1_1 on one pixel tile (cov_image_kernel)
+#include <type_traits>
 
 // ---------------------------------------------------------------------------
 // K3: per-channel sums over the pixel axis
@@ -561,6 +563,134 @@ __global__ __launch_bounds__(256) void cov_finish_kernel(const float* partial, c
   }
 }
 
+// ---------------------------------------------------------------------------
+// K4 at relu1_1, from the IMAGE: the rows of the level-1 feature matrix are what conv1_1 makes of a 3x3 image patch (27
+// multiply-adds from 12 bytes a pixel), so the block computes them instead of reading 256 bytes a pixel.  Grid (1, nsplit, 2P),
+// the K-slices, skip rule, partial layout and finish of cov_f16x2_kernel<64>; its diagonal tile is the whole 64 x 64 matrix.
+// A block stage is 128 rows: wave w computes relu1_1 of rows k0 + 32 w .. + 31 (pixel (k / W, k % W), patch values straight from
+// the image, reflected as conv_first_kernel reflects them) with conv_first_tile.h's arithmetic, operands swapped so that a lane
+// holds 4 consecutive pixels of one channel, centres, scales and splits them as split_store does and parks them in k-stage w of
+// the [channel][32 k] LDS image (8-byte stores).  Every wave then runs the covariance MFMAs of its 32 x 32 tile over the four
+// k-stages in order: the products and their order are cov_f16x2_kernel<64>'s, so the partials are equal bit for bit.
+// Rows past the slice end get a zero scale (exact zeros), k-stages that start past it are left out.
+// ---------------------------------------------------------------------------
+struct CovImageArgs {
+  WctImageSrc src;
+  const float* mean;     // [2P][64]
+  const float* scale;    // [2P]
+  float* partial;        // [2P][nsplit][64][64]
+  int ksplit, nsplit;
+  WctSkip skip;
+};
+
+__global__ __launch_bounds__(256, 2) void cov_image_kernel(CovImageArgs p) {
+  constexpr int C = 64;
+  __shared__ __attribute__((aligned(16))) unsigned char lds[4][2][C * 64];   // per k-stage: hi, lo
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave >> 1, wn = wave & 1;
+  const int mat = blockIdx.z, split = blockIdx.y;
+  if (skip_style_mat(mat, p.skip)) return;
+  const int side = mat & 1, pair = mat >> 1;
+  const int H = side ? p.src.side[1].H : p.src.side[0].H, W = side ? p.src.side[1].W : p.src.side[0].W;
+  const int clamp01 = side ? p.src.side[1].clamp01 : p.src.side[0].clamp01;
+  const int N = H * W;
+  const float* x = (side ? p.src.side[1].img : p.src.side[0].img) + (size_t)pair * N * 3;
+  const int kbeg = split * p.ksplit;
+  const int kend = min(N, kbeg + p.ksplit);
+  const float sc = p.scale[mat];
+  const int kgrp = lane >> 5, ch = lane & 31;    // this lane's channels: nt * 32 + ch
+
+  half8 wh[2][2], wl[2][2];
+  conv1_weights(p.src.wfrag, lane, wh, wl);
+  float bias[2], mean[2];
+#pragma unroll
+  for (int nt = 0; nt < 2; ++nt) { bias[nt] = p.src.bias[nt * 32 + ch]; mean[nt] = p.mean[mat * C + nt * 32 + ch]; }
+
+  f32x16 acc;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+
+  // the 16 patch values of this lane's pixel at k = ks * 16 + kgrp * 8 + j (k >= 27 reads a valid address and is zeroed when it
+  // is used).  The pixel (py, px) is row kbeg + 32 wave + (lane & 31) of the matrix and moves on by 128 rows a stage; a row
+  // past the image (the last stage of the last slice) reads the last image row: it is scaled by zero.
+  float pre[2][8];
+  int py, px;
+  {
+    const int n = kbeg + wave * 32 + (lane & 31);
+    py = n / W; px = n - py * W;
+  }
+  auto fetch = [&]() {
+    conv1_patch_load(x, min(py, H - 1), px, H, W, kgrp, pre);
+    px += 128;                                   // the next stage's pixel
+    while (px >= W) { px -= W; ++py; }
+  };
+  auto mma_stage = [&](const unsigned char* hi, const unsigned char* lo) {     // cov_f16x2_kernel<64>'s, a diagonal tile
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) {
+      const int chunk = ks * 2 + (lane >> 5);
+      const int ra = wm * 32 + (lane & 31), rb = wn * 32 + (lane & 31);
+      const int offa = (ra * 4 + (chunk ^ ((ra >> 2) & 3))) * 16, offb = (rb * 4 + (chunk ^ ((rb >> 2) & 3))) * 16;
+      const half8 ah = *reinterpret_cast<const half8*>(hi + offa), al = *reinterpret_cast<const half8*>(lo + offa);
+      const half8 bh = *reinterpret_cast<const half8*>(hi + offb), bl = *reinterpret_cast<const half8*>(lo + offb);
+      acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, acc, 0, 0, 0);
+    }
+  };
+
+  // relu1_1 of the k-stage, centred, scaled and split as split_store does, into k-stage `wave` of the LDS image (TAIL: the
+  // stage straddles the slice end; rows past it get a zero scale)
+  auto park = [&](const f32x16 (&f)[2], int ks0, auto tail) {
+#pragma unroll
+    for (int nt = 0; nt < 2; ++nt) {
+      const int c = nt * 32 + ch;
+#pragma unroll
+      for (int rq = 0; rq < 4; ++rq) {
+        half4 h, l;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const float s_in = (!decltype(tail)::value || ks0 + rq * 8 + kgrp * 4 + j < kend) ? sc : 0.f;
+          const float v = (conv1_act(f[nt][rq * 4 + j], bias[nt]) - mean[nt]) * s_in;
+          h[j] = (half_t)v;
+          l[j] = (half_t)(v - (float)h[j]);
+        }
+        const int off = (c * 4 + (rq ^ ((c >> 2) & 3))) * 16 + kgrp * 8;     // k = rq * 8 + kgrp * 4 + j of the k-stage
+        *reinterpret_cast<half4*>(lds[wave][0] + off) = h;
+        *reinterpret_cast<half4*>(lds[wave][1] + off) = l;
+      }
+    }
+  };
+
+  if (kbeg + wave * 32 < kend) fetch();          // (wave-uniform: does this wave's k-stage hold rows of the slice?)
+  for (int k0 = kbeg; k0 < kend; k0 += 128) {
+    const int ks0 = k0 + wave * 32;
+    if (ks0 < kend) {
+      // this stage's values out of the landing registers, the next stage's loads into them: a whole stage ahead of their use
+      float cur[2][8];
+      conv1_patch_values(pre, kgrp, clamp01, cur);
+      if (ks0 + 128 < kend) fetch();
+      f32x16 f[2];
+      conv1_tile<true>(wh, wl, [=](int ks, int j) { return cur[ks][j]; }, f);
+      if (ks0 + 32 <= kend) park(f, ks0, std::false_type());
+      else park(f, ks0, std::true_type());
+    }
+    __syncthreads();
+#pragma unroll
+    for (int st = 0; st < 4; ++st)
+      if (k0 + st * 32 < kend) mma_stage(lds[st][0], lds[st][1]);      // (uniform)
+    __syncthreads();
+  }
+
+  // reg r of the tile = row (r&3)+8*(r>>2)+4*(lane>>5), col lane&31
+  float* out = p.partial + ((size_t)mat * p.nsplit + split) * C * C;
+  const int gn = wn * 32 + (lane & 31);
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int gm = wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+    out[(size_t)gm * C + gn] = acc[r];
+  }
+}
+
 // The statistics passes over the nmat matrices of a grid -- the 2P matrices of a batch (launch_means), or one slot of a plan on
 // a one-matrix grid, pointed at the slot (launch_slot_means): sa with its inputs, partial / absmax buffers and skip mode set;
 // the means and the fp16 scale into mean / scale and, var given, the variances; d0 / d1: the rows of an even / odd matrix
@@ -614,6 +744,22 @@ int launch_cov(const float* content, int Nc, const float* style, int Ns, int C, 
   ca.mean = w.mean; ca.scale = w.scale; ca.partial = w.cov_partial;
   ca.C = C; ca.ksplit = w.ksplit; ca.nsplit = w.nsplit; ca.skip = skip;
   return cov_passes(ca, 2 * P, w.A, w.A0, 1.f / (float)(Nc - 1), 1.f / (float)(Ns - 1), eps, s);
+}
+
+// launch_cov at relu1_1 with both sides' rows computed from their images (cov_image_kernel), the same finish
+int launch_cov_image(const WctImageSrc& src, int P, const WctCarve& w, float eps, WctSkip skip, hipStream_t s) {
+  constexpr int C = 64;
+  for (int b = 0; b < 2; ++b) ARG_CHECK(src.side[b].img && src.side[b].H >= 2 && src.side[b].W >= 16 && src.side[b].W % 16 == 0);
+  ARG_CHECK(src.wfrag && src.bias && w.ksplit % 32 == 0);
+  const int Nc = src.side[0].H * src.side[0].W, Ns = src.side[1].H * src.side[1].W;
+  CovImageArgs ca;
+  ca.src = src; ca.mean = w.mean; ca.scale = w.scale; ca.partial = w.cov_partial;
+  ca.ksplit = w.ksplit; ca.nsplit = w.nsplit; ca.skip = skip;
+  hipLaunchKernelGGL(cov_image_kernel, dim3(1, w.nsplit, 2 * P), dim3(256), 0, s, ca);
+  hipLaunchKernelGGL(cov_finish_kernel, dim3(1, 1, 2 * P), dim3(256), 0, s, ca.partial, ca.scale, w.A, C, ca.nsplit, 64,
+                     1.f / (float)(Nc - 1), 1.f / (float)(Ns - 1), eps, (int)skip, w.A0);
+  HIP_TRY(hipGetLastError());
+  return WCT_OK;
 }
 
 // first statistics pass (means, the fp16 scale; with_var: the variances) of ONE matrix, slot `m` of the workspace, with its own

@@ -15,6 +15,7 @@
 #include "wct_stages.h"
 #include "jacobi_dev.h"   // (JacobiState: carve() sizes the solver's state words)
 #include "strength_rule.h"
+#include "conv_first_tile.h"   // conv1_1 on one pixel tile (apply_image_kernel)
 #include <algorithm>
 #include <type_traits>
 
@@ -252,6 +253,194 @@ template int launch_apply_args<ApplySegBatchArgs>(const ApplySegBatchArgs&, int,
 template int launch_apply_args<ApplyMapArgs>(const ApplyMapArgs&, int, int, hipStream_t);
 
 // ---------------------------------------------------------------------------
+// K7 at relu1_1, from the IMAGE: apply_f16x2_kernel<64, 128, ApplyArgs> with the x operand computed instead of loaded, as a strip
+// kernel.  A block walks APPLY_IMAGE_TILES consecutive tiles of 128 rows: M is fetched, split and parked once (both k-stages),
+// conv1_1's bias and the content mean sit in LDS, and the patch values of the next tile are fetched under the current one.  Per
+// tile, wave w computes relu1_1 of rows 32 w .. + 31 (pixel (n / W, n % W), conv_first_tile.h: 64 channels, in registers) and
+// parks channels 32 s .. + 31 of them, less the mean, scaled and split as split_store does, in the [pixel][32 k] image of
+// k-stage s: the conv's D layout leaves a lane 4 consecutive channels of one pixel, an 8-byte store.  The MFMA order and the
+// epilogue are the plain kernel's, so the output is equal bit for bit.
+// ---------------------------------------------------------------------------
+struct ApplyImageArgs : ApplyArgs { WctImageSide img; const half_t* wfrag; const float* bias1; };
+constexpr int APPLY_IMAGE_TILES = 8;
+
+__global__ __launch_bounds__(256, 2) void apply_image_kernel(ApplyImageArgs p) {
+  constexpr int C = 64, BP = 128, TN = BP / 64;
+  __shared__ __attribute__((aligned(16))) unsigned char lm[2][2][C * 64];    // per k-stage: M hi, lo
+  __shared__ __attribute__((aligned(16))) unsigned char lx[2][2][BP * 64];   // per k-stage: x hi, lo
+  __shared__ __attribute__((aligned(16))) float lbm[2][C];                   // conv1_1's bias, the content mean
+  typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave >> 1, wn = wave & 1;
+  const int pair = blockIdx.z;
+  const int H = p.img.H, W = p.img.W, N = H * W;
+  const int tile0 = blockIdx.x * APPLY_IMAGE_TILES;
+  const int ntile = min(APPLY_IMAGE_TILES, (N + BP - 1) / BP - tile0);
+  const float* x = p.img.img + (size_t)pair * N * 3;
+  const float* M = p.M + (size_t)pair * C * C;
+  const float* mean = p.mean + (size_t)pair * 2 * C;
+  const float sx = p.xscale[2 * pair];
+  float sM = 1.f;
+  {
+    const float m = __uint_as_float(p.mabs[pair]);
+    if (m > 0.f) { int e; frexpf(m, &e); sM = ldexpf(1.f, 14 - e); }
+  }
+  const int kgrp = lane >> 5;
+
+  // once per block: this thread's 16-B piece of M for both k-stages (the plain kernel's staging), the epilogue's bias, the
+  // vectors the x staging reads, conv1_1's weights
+  const int mrow = tid >> 2, mkq = tid & 3;
+  const float* mp = M + (size_t)mrow * C + mkq * 8;
+  const int moff = (mrow * 4 + (mkq ^ ((mrow >> 2) & 3))) * 16;
+  f32x4 rm[2][2];
+#pragma unroll
+  for (int s = 0; s < 2; ++s) {
+    rm[s][0] = *reinterpret_cast<const f32x4*>(mp + s * 32);
+    rm[s][1] = *reinterpret_cast<const f32x4*>(mp + s * 32 + 4);
+  }
+  const float* bias = p.bias + (size_t)pair * C;
+  f32x4 bvs[4];
+#pragma unroll
+  for (int rq = 0; rq < 4; ++rq) bvs[rq] = *reinterpret_cast<const f32x4*>(bias + wm * 32 + 8 * rq + 4 * kgrp);
+  if (tid < C) { lbm[0][tid] = p.bias1[tid]; lbm[1][tid] = mean[tid]; }
+
+  // this lane's pixel: row tile0 * 128 + 32 wave + (lane & 31), then 128 rows on per tile (a row past the end reads the last
+  // image row and is dropped at the store); pre: its 16 patch values, fetched a tile ahead
+  int py, px;
+  {
+    const int n = tile0 * BP + wave * 32 + (lane & 31);
+    py = n / W; px = n - py * W;
+  }
+  float pre[2][8];
+  auto fetch = [&]() {
+    conv1_patch_load(x, min(py, H - 1), px, H, W, kgrp, pre);
+    px += BP;
+    while (px >= W) { px -= W; ++py; }
+  };
+  fetch();
+  half8 wh[2][2], wl[2][2];
+  conv1_weights(p.wfrag, lane, wh, wl);
+#pragma unroll
+  for (int s = 0; s < 2; ++s) {
+    half8 h, l;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const float v = rm[s][j >> 2][j & 3] * sM;
+      h[j] = (half_t)v;
+      l[j] = (half_t)(v - (float)h[j]);
+    }
+    *reinterpret_cast<half8*>(lm[s][0] + moff) = h;
+    *reinterpret_cast<half8*>(lm[s][1] + moff) = l;
+  }
+  __syncthreads();
+
+  const int xrow = wave * 32 + (lane & 31);
+  const float inv = 1.f / (sx * sM);
+  for (int t = 0; t < ntile; ++t) {
+    f32x16 f[2];
+    {
+      float cur[2][8];
+      conv1_patch_values(pre, kgrp, p.img.clamp01, cur);
+      if (t + 1 < ntile) fetch();
+      conv1_tile(wh, wl, [=](int ks, int j) { return cur[ks][j]; }, f);
+    }
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+#pragma unroll
+      for (int rq = 0; rq < 4; ++rq) {           // channels s * 32 + 8 rq + 4 kgrp + j: k = 8 rq + 4 kgrp + j of the stage
+        const int ch = s * 32 + 8 * rq + 4 * kgrp;
+        const f32x4 b1 = *reinterpret_cast<const f32x4*>(&lbm[0][ch]), mc = *reinterpret_cast<const f32x4*>(&lbm[1][ch]);
+        half4 h, l;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const float v = (conv1_act(f[s][rq * 4 + j], b1[j]) - mc[j]) * sx;
+          h[j] = (half_t)v;
+          l[j] = (half_t)(v - (float)h[j]);
+        }
+        const int off = (xrow * 4 + (rq ^ ((xrow >> 2) & 3))) * 16 + kgrp * 8;
+        *reinterpret_cast<half4*>(lx[s][0] + off) = h;
+        *reinterpret_cast<half4*>(lx[s][1] + off) = l;
+      }
+    __syncthreads();
+
+    f32x16 acc[TN];
+#pragma unroll
+    for (int j = 0; j < TN; ++j)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks) {
+        const int chunk = ks * 2 + (lane >> 5);
+        half8 bh[TN], bl[TN];
+        const int r = wm * 32 + (lane & 31);
+        const int offa = (r * 4 + (chunk ^ ((r >> 2) & 3))) * 16;
+        const half8 ah = *reinterpret_cast<const half8*>(lm[s][0] + offa), al = *reinterpret_cast<const half8*>(lm[s][1] + offa);
+#pragma unroll
+        for (int j = 0; j < TN; ++j) {
+          const int rb = (wn * TN + j) * 32 + (lane & 31);
+          const int off = (rb * 4 + (chunk ^ ((rb >> 2) & 3))) * 16;
+          bh[j] = *reinterpret_cast<const half8*>(lx[s][0] + off);
+          bl[j] = *reinterpret_cast<const half8*>(lx[s][1] + off);
+        }
+#pragma unroll
+        for (int j = 0; j < TN; ++j) {
+          acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh[j], acc[j], 0, 0, 0);
+          acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl[j], acc[j], 0, 0, 0);
+          acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh[j], acc[j], 0, 0, 0);
+        }
+      }
+    __syncthreads();                             // the x images are free for the next tile; the stores below need no LDS
+
+    // epilogue, the plain kernel's: reg r of a tile = channel (r&3)+8*(r>>2)+4*(lane>>5), pixel lane&31
+    const int n0 = (tile0 + t) * BP;
+#pragma unroll
+    for (int j = 0; j < TN; ++j) {
+      const int n = n0 + (wn * TN + j) * 32 + (lane & 31);
+      const bool n_ok = n < N;
+      const size_t row = ((size_t)pair * N + (n_ok ? n : 0)) * C;
+      const int cb = wm * 32;
+      unsigned pk[4][2];
+#pragma unroll
+      for (int rq = 0; rq < 4; ++rq) {
+        const int co = cb + 8 * rq + 4 * kgrp;
+        f32x4 v;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) v[q] = acc[j][rq * 4 + q] * inv + bvs[rq][q];
+        if (p.out32 && n_ok) *reinterpret_cast<f32x4*>(p.out32 + row + co) = v;
+        typedef _Float16 h2 __attribute__((ext_vector_type(2)));
+        h2 lo = {(half_t)v[0], (half_t)v[1]}, hi = {(half_t)v[2], (half_t)v[3]};
+        pk[rq][0] = __builtin_bit_cast(unsigned, lo);
+        pk[rq][1] = __builtin_bit_cast(unsigned, hi);
+      }
+      if (p.out16) {
+#pragma unroll
+        for (int m = 0; m < 2; ++m) {
+          auto sxw = __builtin_amdgcn_permlane32_swap(pk[2 * m][0], pk[2 * m + 1][0], false, false);
+          auto syw = __builtin_amdgcn_permlane32_swap(pk[2 * m][1], pk[2 * m + 1][1], false, false);
+          u32x4 o = {sxw[0], syw[0], sxw[1], syw[1]};
+          const int co = cb + 16 * m + 8 * kgrp;
+          if (n_ok) *reinterpret_cast<u32x4*>(p.out16 + row + co) = o;
+        }
+      }
+    }
+  }
+}
+
+// launch_apply at relu1_1 with the content rows computed from the images `img` [P][H][W][3] (N = H * W rows a pair)
+static int launch_apply_image(const WctCarve& w, const WctImageSrc& src, int P, half_t* out16, float* out32, hipStream_t s) {
+  const WctImageSide& im = src.side[0];
+  ARG_CHECK(im.img && im.H >= 2 && im.W >= 2 && src.wfrag && src.bias);
+  ApplyImageArgs a;
+  static_cast<ApplyArgs&>(a) = apply_args<ApplyArgs>(w, nullptr, im.H * im.W, 64, out16, out32);
+  a.img = im; a.wfrag = src.wfrag; a.bias1 = src.bias;
+  hipLaunchKernelGGL(apply_image_kernel, dim3(cdiv(cdiv(a.N, 128), APPLY_IMAGE_TILES), 1, P), dim3(256), 0, s, a);
+  HIP_TRY(hipGetLastError());
+  return WCT_OK;
+}
+
+// ---------------------------------------------------------------------------
 // workspace carving (P independent content/style pairs per call)
 // ---------------------------------------------------------------------------
 static int wct_nslab(int N) { int s = cdiv(N, 64); return s < 1 ? 1 : (s > 256 ? 256 : s); }
@@ -441,9 +630,12 @@ int launch_style_state(const float* style, int Ns, int C, const WctStyleKey& key
 }
 
 int launch_wct(const float* content, int Nc, const float* style, int Ns, int C, int P, WctSkip skip, const WctCall& r,
-               const WctFeatStats* stats, const WctStyleRef* prep, const WctWarmRef* warm, const WctStrength* sm) {
+               const WctFeatStats* stats, const WctStyleRef* prep, const WctWarmRef* warm, const WctStrength* sm, const WctImageSrc* src) {
   const int mode = r.mode, stages = r.stages; hipStream_t s = r.stream;
   ARG_CHECK(C % 32 == 0 && C >= 32 && C <= 1024 && Nc >= 2 && Ns >= 2 && P >= 1 && P <= 32);
+  // covariance and apply from the images: relu1_1 of plain pairs, the means of both sides from the unit sums their conv1_1 pass took
+  ARG_CHECK(!src || (C == 64 && !prep && !warm && !sm && stats && stats->u[0] && stats->umax[0] && stats->u[1] && stats->umax[1] &&
+                     src->side[0].H * src->side[0].W == Nc && src->side[1].H * src->side[1].W == Ns));
   ARG_CHECK(!sm || strength_ok(*sm, Nc));
   ARG_CHECK(skip == WCT_SKIP_NONE || skip == WCT_SKIP_SHARED_STYLE);
   ARG_CHECK(!warm || (warm->basis && (skip == WCT_SKIP_NONE || prep)));
@@ -456,7 +648,9 @@ int launch_wct(const float* content, int Nc, const float* style, int Ns, int C, 
   int rc;
   if (stages & WCT_STAGE_COV) {
     if ((rc = launch_means(content, Nc, style, Ns, C, P, w, false, skip, s, stats))) return rc;
-    if ((rc = launch_cov(content, Nc, style, Ns, C, P, w, cov_eps(mode, r.eps), skip, s))) return rc;
+    if (src) rc = launch_cov_image(*src, P, w, cov_eps(mode, r.eps), skip, s);
+    else rc = launch_cov(content, Nc, style, Ns, C, P, w, cov_eps(mode, r.eps), skip, s);
+    if (rc) return rc;
   }
   if (stages & WCT_STAGE_EIG) {
     // a warm start (warm.hip): the content matrices rotated into the stored basis, the same solve on them, the bases composed --
@@ -473,6 +667,10 @@ int launch_wct(const float* content, int Nc, const float* style, int Ns, int C, 
   if (prep && (rc = launch_style_load(*prep, 1, w, C, true, s))) return rc;
   if ((rc = launch_spectral_tail(w, C, P, sm ? 1.f : r.alpha, mode, r.eps, skip, P, s))) return rc;
   if (sm) return launch_blend_apply_map(w, content, Nc, C, P, skip, r, *sm);
+  if (src) {                                     // the apply computes the content rows from the images as well: `content` is not read
+    if ((rc = launch_blend(w, C, P, r.alpha, skip, s))) return rc;
+    return launch_apply_image(w, *src, P, r.out16, r.out32, s);
+  }
   return launch_blend_apply(w, content, Nc, C, P, skip, r);
 }
 

@@ -100,6 +100,8 @@ int launch_means(const float* content, int Nc, const float* style, int Ns, int C
 int launch_cov(const float* content, int Nc, const float* style, int Ns, int C, int P, const WctCarve& w, float eps, WctSkip skip,
                hipStream_t s);
 int launch_plan_stats(const SlotPlan& sp, int C, bool with_var, bool with_cov, float eps, hipStream_t s);
+// launch_cov at relu1_1 (C = 64), the rows of both sides computed from their images; w laid out for the sides' H * W rows
+int launch_cov_image(const WctImageSrc& src, int P, const WctCarve& w, float eps, WctSkip skip, hipStream_t s);
 // eigh.hip: the 2P matrices of w in one batched solve
 // (check_from: the first sweep after which the host looks at the done-flags -- JacobiGroup::check_from; a warm solve passes 0)
 int launch_eig_stage(const WctCarve& w, int C, int P, WctSkip skip, int u_f16, int* sweeps_dev, int* eig_fail, hipStream_t s,
