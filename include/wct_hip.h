@@ -59,12 +59,16 @@ enum wct_flags {
                               any of the flags above; the frame equals wct_content_colors(the unflagged frame, the content)
                               bit for bit.  Without the flag nothing changes */
   WCT_FLAG_GUIDED = 64     /* guided smoothing, the photo mode: every frame is filtered with its content as guide (see
-                              wct_guided_filter), radius and eps_q from wct_set_guided.  Honoured by every wct_stylize* call that
+                              wct_guided_filter), radius and eps_q from wct_set_guided, the guide from wct_set_guided_guide.  Honoured by every wct_stylize* call that
                               ends in the whole-image chain, with any of the flags above; the frame equals wct_guided_filter(the
                               unflagged frame, the content) bit for bit, and with WCT_FLAG_CONTENT_COLORS as well
                               wct_content_colors(that, the content): the colour op runs last.  The banded, texture and wrap
                               calls refuse it (WCT_STATUS_ARG, a message that names it) */
 };
+
+/* the guide of guided smoothing (wct_guided_filter_guide, wct_set_guided_guide) */
+enum wct_guide { WCT_GUIDE_GREY = 0,   /* the grey of the content: one channel, one division per pixel and channel */
+                 WCT_GUIDE_COLOR = 1   /* its three channels: a 3 x 3 solve per pixel; sees an edge between colours of equal luminance */ };
 
 /* ---- lifecycle: replaces WCT.__init__'s tf.Session setup (wct.py:29-44) ---- */
 int  wct_create(int device, wct_ctx** out);
@@ -240,12 +244,31 @@ int wct_content_colors_batch_dev(wct_ctx* ctx, const uint8_t* stylized_dev, int 
  *   taken under the output rule uint8(clip(x, 0, 1) * 255.f), as the colour op takes it.
  * Ho < Hc, Wo < Wc, a null pointer, B outside 1 .. 32, a radius or eps_q out of range, or B * Ho * Wo * 3 >= 2^31 is
  * WCT_STATUS_ARG and leaves the ctx (and the flag's settings) as they were.
- * Not served: a colour (3-channel) guide, the subsampled "fast guided filter", the banded / texture / wrap calls, radii above 64. */
+ * The colour guide (He et al., eqs. 19-21; the rule, its bounds and its distance from the float64 filter: csrc/guided_color_rule.h).
+ * The grey guide is blind to an edge between two colours of equal luminance and blurs the frame across it; with WCT_GUIDE_COLOR
+ * the guide is the three content bytes I = (p.R, p.G, p.B) of the same clamped pixel, and pass 1 solves a 3 x 3 system (F = 4;
+ * i, j the guide's channels, ch the frame's; U the unit matrix; >> the arithmetic shift):
+ *   pass 1:    the 21 window sums S_i, S_ij (i <= j), S_ch, S_i,ch
+ *              V_ij = rdiv(2^F (n S_ij - S_i S_j), n^2),  M = V + 2^F eps_q U,  c_i,ch = rdiv(2^F (n S_i,ch - S_i S_ch), n^2)
+ *              adj = the adjugate of M,  det = sum_j M_0j adj_0j,  u_i,ch = sum_j adj_ij c_j,ch,  k = max(0, bitlength(det) - 43)
+ *              a_q[i][ch] = rdiv((u_i,ch >> k) 2^12, det >> k),  b_q[ch] = rdiv(S_ch 2^12 - sum_i a_q[i][ch] S_i, n)
+ *   pass 2:    out.ch = clamp(rdiv(sum_i I_i sum a_q[i][ch] + sum b_q[ch], n 2^12), 0, 255)
+ * A constant frame comes back exactly.  48 B per pixel between the passes.
+ * wct_guided_filter_guide, wct_guided_filter_guide_batch_dev: the two calls above with the guide as one more argument;
+ *   WCT_GUIDE_GREY gives their bytes.  wct_set_guided_guide: the guide of WCT_FLAG_GUIDED (initially WCT_GUIDE_GREY); every
+ *   flagged frame equals wct_guided_filter_guide(the unflagged frame, the content, that guide) bit for bit.  A guide that is
+ *   neither value is WCT_STATUS_ARG and keeps the earlier setting.
+ * Not served: the subsampled "fast guided filter", the banded / texture / wrap calls, radii above 64, a guide other than the content. */
 int wct_guided_filter(wct_ctx* ctx, const uint8_t* stylized, int Ho, int Wo, const uint8_t* content, int Hc, int Wc, int radius,
                       int eps_q, uint8_t* out);
 int wct_guided_filter_batch_dev(wct_ctx* ctx, const uint8_t* stylized_dev, int Ho, int Wo, const uint8_t* content_dev, int Hc, int Wc,
                                 int B, int radius, int eps_q, uint8_t* out_dev);
 int wct_set_guided(wct_ctx* ctx, int radius, int eps_q);
+int wct_guided_filter_guide(wct_ctx* ctx, const uint8_t* stylized, int Ho, int Wo, const uint8_t* content, int Hc, int Wc, int radius,
+                            int eps_q, int guide, uint8_t* out);
+int wct_guided_filter_guide_batch_dev(wct_ctx* ctx, const uint8_t* stylized_dev, int Ho, int Wo, const uint8_t* content_dev, int Hc,
+                                      int Wc, int B, int radius, int eps_q, int guide, uint8_t* out_dev);
+int wct_set_guided_guide(wct_ctx* ctx, int guide);
 /* On-device resize (the reference's resize_to, utils.py:55-67, behind --content-size, stylize_video.py:29; webcam.py:163,189
  * resizes every frame by --scale): img [H][W][3] uint8 -> [h][w][3] uint8, the bytes of Pillow's Image.resize((w, h), Image.BILINEAR).
  * Pillow's 8-bit resampler is an integer rule.  Per axis (`in` the input length, `out` the output length; everything up to the

@@ -53,6 +53,9 @@ SIGNATURES = [
     ('wct_guided_filter', C.c_int, [_P, _U8, C.c_int, C.c_int, _U8, C.c_int, C.c_int, C.c_int, C.c_int, _U8]),
     ('wct_guided_filter_batch_dev', C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     ('wct_set_guided', C.c_int, [_P, C.c_int, C.c_int]),
+    ('wct_guided_filter_guide', C.c_int, [_P, _U8, C.c_int, C.c_int, _U8, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _U8]),
+    ('wct_guided_filter_guide_batch_dev', C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+    ('wct_set_guided_guide', C.c_int, [_P, C.c_int]),
     ('wct_resize', C.c_int, [_P, _U8, C.c_int, C.c_int, C.c_int, C.c_int, _U8]),
     ('wct_resize_batch_dev', C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     ('wct_output_size', C.c_int, [C.c_int, C.c_int, _I, C.c_int, _I, _I]),
@@ -138,6 +141,8 @@ WCT_NP, WCT_TF = 0, 1
 FLAG_ADAIN, FLAG_MODE_NP, FLAG_SWAP5, FLAG_STYLE_SHARED, FLAG_IMAGES_F32, FLAG_CONTENT_COLORS = 1, 2, 4, 8, 16, 32
 FLAG_GUIDED = 64
 GUIDED_MAX_RADIUS, GUIDED_MAX_EPS = 64, 65025      # csrc/guided_rule.h
+GUIDE_GREY, GUIDE_COLOR = 0, 1                     # WCT_GUIDE_*: the guide of guided smoothing
+GUIDES = {'grey': GUIDE_GREY, 'color': GUIDE_COLOR}
 
 
 def guided_eps_q(eps):

@@ -58,20 +58,32 @@ def _color_images(stylized, content, ndim):
     return u8(s), u8(c)
 
 
+def check_guide(guide):
+    """The guide of guided smoothing by name, 'grey' or 'color' -> WCT_GUIDE_GREY or WCT_GUIDE_COLOR"""
+    if not isinstance(guide, str) or guide not in _lib.GUIDES:
+        raise ValueError("the guided guide is 'grey' or 'color', got %r" % (guide,))
+    return _lib.GUIDES[guide]
+
+
 def check_guided(guided):
-    """The refusals of guided=(radius, eps_q), before any library call: two integers, the radius 1 .. 64 and eps_q 1 .. 65025 (grey
-    levels squared; _lib.guided_eps_q converts an eps of the [0,1]^2 convention).  -> (radius, eps_q)"""
+    """The refusals of guided=(radius, eps_q) or (radius, eps_q, guide), before any library call: two integers, the radius 1 .. 64
+    and eps_q 1 .. 65025 (grey levels squared; _lib.guided_eps_q converts an eps of the [0,1]^2 convention), and the guide 'grey'
+    (what the two-element form means) or 'color'.  -> (radius, eps_q), or (radius, eps_q, guide) as it was given"""
     try:
-        r, e = guided
+        g = tuple(guided)
+        r, e = g[:2] if len(g) == 3 else g
         if int(r) != r or int(e) != e:
             raise TypeError
         r, e = int(r), int(e)
     except (TypeError, ValueError):
-        raise ValueError('guided is (radius, eps_q), two integers, got %r' % (guided,))
+        raise ValueError("guided is (radius, eps_q), two integers, or (radius, eps_q, 'grey' or 'color'), got %r" % (guided,))
     if not 1 <= r <= _lib.GUIDED_MAX_RADIUS:
         raise ValueError('the guided radius must be 1 .. %d, got %d' % (_lib.GUIDED_MAX_RADIUS, r))
     if not 1 <= e <= _lib.GUIDED_MAX_EPS:
         raise ValueError('the guided eps_q must be 1 .. %d (grey levels squared), got %d' % (_lib.GUIDED_MAX_EPS, e))
+    if len(g) == 3:
+        check_guide(g[2])
+        return r, e, g[2]
     return r, e
 
 
@@ -789,39 +801,51 @@ class Context(object):
         r, e = check_guided((radius, eps_q))
         check(self.lib.wct_set_guided(self.h, r, e))
 
+    def set_guided_guide(self, guide):
+        """The guide that WCT_FLAG_GUIDED filters through, 'grey' (the initial one) or 'color' (wct_set_guided_guide)"""
+        g = check_guide(guide)
+        check(self.lib.wct_set_guided_guide(self.h, g))
+
     def _set_guided(self, guided):
-        """guided=(radius, eps_q) of a stylize call: None -> False; else the settings go to the library -> True (the flag)"""
+        """guided=(radius, eps_q[, guide]) of a stylize call: None -> False; else the settings go to the library -> True (the flag).
+        The two-element form means the grey guide."""
         if guided is None:
             return False
-        self.set_guided(*check_guided(guided))
+        g = check_guided(guided)
+        self.set_guided(g[0], g[1])
+        self.set_guided_guide(g[2] if len(g) == 3 else 'grey')
         return True
 
-    def guided_filter(self, stylized_u8, content_u8, radius, eps_q):
-        """Guided smoothing (wct_guided_filter; He, Sun, Tang, "Guided Image Filtering"): stylized [Ho][Wo][3] and content
-        [Hc][Wc][3] uint8, Ho >= Hc and Wo >= Wc -> uint8 [Ho][Wo][3], `stylized` filtered with the grey of `content` as guide
-        (pixel (y, x) takes content pixel (min(y, Hc - 1), min(x, Wc - 1))) over a (2 radius + 1)^2 box; eps_q in grey levels
-        squared.  The integer rule of include/wct_hip.h."""
+    def guided_filter(self, stylized_u8, content_u8, radius, eps_q, guide='grey'):
+        """Guided smoothing (wct_guided_filter_guide; He, Sun, Tang, "Guided Image Filtering"): stylized [Ho][Wo][3] and content
+        [Hc][Wc][3] uint8, Ho >= Hc and Wo >= Wc -> uint8 [Ho][Wo][3], `stylized` filtered with `content` as guide (pixel (y, x)
+        takes content pixel (min(y, Hc - 1), min(x, Wc - 1))) over a (2 radius + 1)^2 box; eps_q in grey levels squared.  guide:
+        'grey', the grey of the content, or 'color', its three channels (a 3 x 3 solve per pixel, which sees an edge between two
+        colours of equal luminance).  The integer rules of include/wct_hip.h."""
         s, c = _guided_images(stylized_u8, content_u8, 3)
         r, e = check_guided((radius, eps_q))
+        g = check_guide(guide)
         out = np.empty_like(s)
-        check(self.lib.wct_guided_filter(self.h, s.ctypes.data_as(_lib._U8), s.shape[0], s.shape[1], c.ctypes.data_as(_lib._U8),
-                                         c.shape[0], c.shape[1], r, e, out.ctypes.data_as(_lib._U8)))
+        check(self.lib.wct_guided_filter_guide(self.h, s.ctypes.data_as(_lib._U8), s.shape[0], s.shape[1], c.ctypes.data_as(_lib._U8),
+                                               c.shape[0], c.shape[1], r, e, g, out.ctypes.data_as(_lib._U8)))
         return out
 
-    def guided_filter_batch_dev(self, stylized_dev, ho, wo, content_dev, hc, wc, batch, radius, eps_q, out_dev):
-        """guided_filter for B frames resident in HBM (wct_guided_filter_batch_dev): asynchronous; out_dev may be stylized_dev."""
+    def guided_filter_batch_dev(self, stylized_dev, ho, wo, content_dev, hc, wc, batch, radius, eps_q, out_dev, guide='grey'):
+        """guided_filter for B frames resident in HBM (wct_guided_filter_guide_batch_dev): asynchronous; out_dev may be stylized_dev."""
         r, e = check_guided((radius, eps_q))
-        check(self.lib.wct_guided_filter_batch_dev(self.h, stylized_dev, int(ho), int(wo), content_dev, int(hc), int(wc), int(batch),
-                                                   r, e, out_dev))
+        g = check_guide(guide)
+        check(self.lib.wct_guided_filter_guide_batch_dev(self.h, stylized_dev, int(ho), int(wo), content_dev, int(hc), int(wc), int(batch),
+                                                         r, e, g, out_dev))
 
-    def guided_filter_batch(self, stylized_u8, contents_u8, radius, eps_q):
+    def guided_filter_batch(self, stylized_u8, contents_u8, radius, eps_q, guide='grey'):
         """Host arrays in, host array out: stylized [B][Ho][Wo][3] and contents [B][Hc][Wc][3] uint8 (B <= 32) -> [B][Ho][Wo][3]."""
         s, c = _guided_images(stylized_u8, contents_u8, 4)
         r, e = check_guided((radius, eps_q))
+        check_guide(guide)
         if s.shape[0] != c.shape[0] or not 1 <= s.shape[0] <= _lib.BATCH_MAX:
             raise ValueError('a batch takes 1 .. %d frames and as many contents, got %d and %d' % (_lib.BATCH_MAX, s.shape[0], c.shape[0]))
         return self._host_batch([s, c], np.empty_like(s), in_place=True, enqueue=lambda ds, dc: self.guided_filter_batch_dev(
-            ds, s.shape[1], s.shape[2], dc, c.shape[1], c.shape[2], s.shape[0], r, e, ds))
+            ds, s.shape[1], s.shape[2], dc, c.shape[1], c.shape[2], s.shape[0], r, e, ds, guide=guide))
 
     # ---- on-device resize: Pillow's bilinear bytes ------------------------------------------
     def resize(self, img_u8, size):

@@ -117,8 +117,10 @@ struct wct_ctx {
   DevBuf resize_tab;               // on-device resize: the tap and bounds tables of the last geometry (resize_geom; H = 0: none yet),
   std::vector<int> resize_host;    // and the host copy they were uploaded from
   ResizeGeom resize_geom = {};
-  DevBuf guided_ab;                // guided smoothing (guided.hip): the (a_q, b_q) map between its two passes, 24 B per pixel
+  DevBuf guided_ab;                // guided smoothing (guided.hip, guided_color.hip): the coefficient map between the two passes,
+                                   // 24 B per pixel under the grey guide, 48 B under the colour guide
   int guided_radius = 8, guided_eps = 650;   // what WCT_FLAG_GUIDED filters with (wct_set_guided; eps 0.01 of the [0,1]^2 convention)
+  int guided_guide = WCT_GUIDE_GREY;         // ... and through which guide (wct_set_guided_guide)
   std::vector<wct_style*> styles;  // the live prepared styles of this context (wct_style_prepare .. wct_style_free)
   unsigned long long style_clock = 0;   // one tick per call that takes prepared styles
   std::vector<wct_warm*> warms;    // the live warm states of this context (wct_warm_create .. wct_warm_free)
@@ -275,9 +277,10 @@ int wrap_encoder_buffers(wct_ctx* c, int B, int H, int W, int level);
 int wrap_decoder_buffers(wct_ctx* c, int B, int h, int w, int level);
 
 // ---- api_ops.hip ----------------------------------------------------------
-// guided smoothing of B uint8 frames on the device (guided.hip), the (a_q, b_q) map in c->guided_ab (ensured here); out may be stylized
+// guided smoothing of B uint8 frames on the device (guided.hip, or guided_color.hip under WCT_GUIDE_COLOR), the coefficient map in
+// c->guided_ab (ensured here); out may be stylized
 int run_guided_filter(wct_ctx* c, const uint8_t* stylized, const void* content, int content_f32, int B, int Ho, int Wo, int Hc, int Wc,
-                      int radius, int eps_q, uint8_t* out);
+                      int radius, int eps_q, int guide, uint8_t* out);
 
 // ---- api_stylize.hip ------------------------------------------------------
 int warm_live(const wct_ctx* c, const wct_warm* wm);     // WCT_ERR_STATE unless wm is a live warm state of c

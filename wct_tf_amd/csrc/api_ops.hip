@@ -690,44 +690,62 @@ extern "C" int wct_content_colors(wct_ctx* c, const uint8_t* stylized, int Ho, i
   return fetch(c, out, ds, (size_t)Ho * Wo * 3);
 }
 
-// Guided smoothing, op level (csrc/guided.hip).  run_guided_filter: the two launches on B frames resident on the device, their
-// (a_q, b_q) map in the context's workspace; the stylize chain ends in it under WCT_FLAG_GUIDED
+// Guided smoothing, op level (csrc/guided.hip, csrc/guided_color.hip).  run_guided_filter: the two launches on B frames resident on
+// the device, their coefficient map in the context's workspace; the stylize chain ends in it under WCT_FLAG_GUIDED
 int run_guided_filter(wct_ctx* c, const uint8_t* stylized, const void* content, int content_f32, int B, int Ho, int Wo, int Hc, int Wc,
-                      int radius, int eps_q, uint8_t* out) {
-  TRY(guided_check(B, Ho, Wo, Hc, Wc, radius, eps_q));
-  TRY(ensure(c, c->guided_ab, guided_workspace_bytes(B, Ho, Wo)));
+                      int radius, int eps_q, int guide, uint8_t* out) {
+  TRY(guided_check(B, Ho, Wo, Hc, Wc, radius, eps_q, guide));
+  TRY(ensure(c, c->guided_ab, guided_workspace_bytes(B, Ho, Wo, guide)));
   // per pixel: s and c read twice (the entering and the leaving row), the map written once and read twice, the frame written
-  ProfScope ps(c, 7, 0, (double)B * Ho * Wo * (2 * 3 + 2 * 3 * (content_f32 ? 4 : 1) + 3 * 24 + 3 * (content_f32 ? 4 : 1) + 3));
-  return launch_guided_filter(stylized, content, content_f32, B, Ho, Wo, Hc, Wc, radius, eps_q, c->guided_ab.p, out, c->stream);
+  const int map = guide == WCT_GUIDE_COLOR ? 48 : 24;
+  ProfScope ps(c, 7, 0, (double)B * Ho * Wo * (2 * 3 + 2 * 3 * (content_f32 ? 4 : 1) + 3 * map + 3 * (content_f32 ? 4 : 1) + 3));
+  return launch_guided_filter(stylized, content, content_f32, B, Ho, Wo, Hc, Wc, radius, eps_q, guide, c->guided_ab.p, out, c->stream);
 }
 
 extern "C" int wct_set_guided(wct_ctx* c, int radius, int eps_q) {
   ARG_CHECK(c != nullptr);
-  TRY(guided_check(1, 1, 1, 1, 1, radius, eps_q));
+  TRY(guided_check(1, 1, 1, 1, 1, radius, eps_q, WCT_GUIDE_GREY));
   c->guided_radius = radius; c->guided_eps = eps_q;
   return WCT_OK;
 }
 
-extern "C" int wct_guided_filter_batch_dev(wct_ctx* c, const uint8_t* stylized, int Ho, int Wo, const uint8_t* content, int Hc, int Wc,
-                                           int B, int radius, int eps_q, uint8_t* out) {
+extern "C" int wct_set_guided_guide(wct_ctx* c, int guide) {
   ARG_CHECK(c != nullptr);
-  if (!stylized || !content || !out) { wct_set_error("guided filter: null image pointer"); return WCT_ERR_ARG; }
-  TRY(guided_check(B, Ho, Wo, Hc, Wc, radius, eps_q));
-  HIP_TRY(hipSetDevice(c->device));
-  return run_guided_filter(c, stylized, content, 0, B, Ho, Wo, Hc, Wc, radius, eps_q, out);
+  TRY(guided_check(1, 1, 1, 1, 1, 1, 1, guide));
+  c->guided_guide = guide;
+  return WCT_OK;
 }
 
-extern "C" int wct_guided_filter(wct_ctx* c, const uint8_t* stylized, int Ho, int Wo, const uint8_t* content, int Hc, int Wc, int radius,
-                                 int eps_q, uint8_t* out) {
+extern "C" int wct_guided_filter_guide_batch_dev(wct_ctx* c, const uint8_t* stylized, int Ho, int Wo, const uint8_t* content, int Hc,
+                                                 int Wc, int B, int radius, int eps_q, int guide, uint8_t* out) {
   ARG_CHECK(c != nullptr);
   if (!stylized || !content || !out) { wct_set_error("guided filter: null image pointer"); return WCT_ERR_ARG; }
-  TRY(guided_check(1, Ho, Wo, Hc, Wc, radius, eps_q));
+  TRY(guided_check(B, Ho, Wo, Hc, Wc, radius, eps_q, guide));
+  HIP_TRY(hipSetDevice(c->device));
+  return run_guided_filter(c, stylized, content, 0, B, Ho, Wo, Hc, Wc, radius, eps_q, guide, out);
+}
+
+extern "C" int wct_guided_filter_batch_dev(wct_ctx* c, const uint8_t* stylized, int Ho, int Wo, const uint8_t* content, int Hc, int Wc,
+                                           int B, int radius, int eps_q, uint8_t* out) {
+  return wct_guided_filter_guide_batch_dev(c, stylized, Ho, Wo, content, Hc, Wc, B, radius, eps_q, WCT_GUIDE_GREY, out);
+}
+
+extern "C" int wct_guided_filter_guide(wct_ctx* c, const uint8_t* stylized, int Ho, int Wo, const uint8_t* content, int Hc, int Wc,
+                                       int radius, int eps_q, int guide, uint8_t* out) {
+  ARG_CHECK(c != nullptr);
+  if (!stylized || !content || !out) { wct_set_error("guided filter: null image pointer"); return WCT_ERR_ARG; }
+  TRY(guided_check(1, Ho, Wo, Hc, Wc, radius, eps_q, guide));
   HIP_TRY(hipSetDevice(c->device));
   void *ds, *dc;
   TRY(stage_in(c, 0, stylized, (size_t)Ho * Wo * 3, &ds));
   TRY(stage_in(c, 1, content, (size_t)Hc * Wc * 3, &dc));
-  TRY(wct_guided_filter_batch_dev(c, (uint8_t*)ds, Ho, Wo, (uint8_t*)dc, Hc, Wc, 1, radius, eps_q, (uint8_t*)ds));    // (in place)
+  TRY(wct_guided_filter_guide_batch_dev(c, (uint8_t*)ds, Ho, Wo, (uint8_t*)dc, Hc, Wc, 1, radius, eps_q, guide, (uint8_t*)ds));    // (in place)
   return fetch(c, out, ds, (size_t)Ho * Wo * 3);
+}
+
+extern "C" int wct_guided_filter(wct_ctx* c, const uint8_t* stylized, int Ho, int Wo, const uint8_t* content, int Hc, int Wc, int radius,
+                                 int eps_q, uint8_t* out) {
+  return wct_guided_filter_guide(c, stylized, Ho, Wo, content, Hc, Wc, radius, eps_q, WCT_GUIDE_GREY, out);
 }
 
 // Seeded noise images for texture synthesis, op level (csrc/noise.hip): the refusals both calls share

@@ -67,8 +67,8 @@ static bool fuse_stats() {
 // channels) of the g.h x g.w contents in c->feat_c -> c->wct_out (fp16), st the content's unit sums.  WCT_FLAG_SWAP5 runs the
 // style-swap at relu5_1 instead.  WCT_FLAG_CONTENT_COLORS: the last launch puts the frames' luminance on the colours of
 // content_raw, the contents as the caller gave them ([B][Hc][Wc][3] on the device: uint8, or fp32 with WCT_FLAG_IMAGES_F32).
-// WCT_FLAG_GUIDED: the uint8 frames are then filtered in place with content_raw as guide (guided.hip, the context's radius and
-// eps_q), and the colour op, if flagged too, runs after that as the stand-alone uint8 kernel.
+// WCT_FLAG_GUIDED: the uint8 frames are then filtered in place with content_raw as guide (guided.hip or guided_color.hip: the context's radius,
+// eps_q and guide), and the colour op, if flagged too, runs after that as the stand-alone uint8 kernel.
 template <typename StyleAt, typename Transform>
 static int stylize_levels(wct_ctx* c, const float* img_c, const void* content_raw, int B, const Chain& chain, unsigned flags,
                           size_t umax_clear, int clear_from, StyleAt&& style_at, Transform&& transform, uint8_t* out,
@@ -124,7 +124,7 @@ static int stylize_levels(wct_ctx* c, const float* img_c, const void* content_ra
       ProfScope ps(c, 7, 0, (double)B * H * W * 3 * 5);
       TRY(launch_f32_to_u8(cur, out, (size_t)B * H * W * 3, c->stream));
     }
-    TRY(run_guided_filter(c, out, content_raw, f32, B, H, W, Hc, Wc, c->guided_radius, c->guided_eps, out));
+    TRY(run_guided_filter(c, out, content_raw, f32, B, H, W, Hc, Wc, c->guided_radius, c->guided_eps, c->guided_guide, out));
     if (!(flags & WCT_FLAG_CONTENT_COLORS)) return WCT_OK;
     ProfScope ps(c, 7, 0, (double)B * H * W * 3 * 2 + (double)B * Hc * Wc * 3 * (f32 ? 4 : 1));
     return launch_content_colors_u8_any(out, content_raw, f32, B, H, W, Hc, Wc, out, c->stream);

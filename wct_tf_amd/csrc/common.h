@@ -361,11 +361,17 @@ int launch_content_colors_u8_any(const uint8_t* stylized, const void* content, i
 // (uint8, or with content_f32 fp32 in [0,1] quantised as launch_f32_to_u8 does) as guide, content pixel (min(y, Hc - 1),
 // min(x, Wc - 1)).  Two launches; workspace: guided_workspace_bytes(B, Ho, Wo) bytes on the device; out may be stylized; any base
 // address.  guided_check: B outside 1 .. 32, Ho < Hc or Wo < Wc, a radius outside 1 .. 64, eps_q outside 1 .. 65025, or
-// B * Ho * Wo * 3 >= 2^31 is WCT_ERR_ARG with a message.
-int guided_check(int B, int Ho, int Wo, int Hc, int Wc, int radius, int eps_q);
-size_t guided_workspace_bytes(int B, int Ho, int Wo);
+// B * Ho * Wo * 3 >= 2^31, or a guide that is neither of the two, is WCT_ERR_ARG with a message.
+// guide: GUIDE_GREY (the grey of the content, guided_rule.h: 24 B of workspace per pixel) or GUIDE_COLOR (its three channels,
+// guided_color_rule.h: 48 B per pixel, the kernels of guided_color.hip) -- the values of WCT_GUIDE_* of the public header.
+constexpr int GUIDE_GREY = 0, GUIDE_COLOR = 1;
+int guided_check(int B, int Ho, int Wo, int Hc, int Wc, int radius, int eps_q, int guide);
+size_t guided_workspace_bytes(int B, int Ho, int Wo, int guide);
 int launch_guided_filter(const uint8_t* stylized, const void* content, int content_f32, int B, int Ho, int Wo, int Hc, int Wc, int radius,
-                         int eps_q, void* workspace, uint8_t* out, hipStream_t s);
+                         int eps_q, int guide, void* workspace, uint8_t* out, hipStream_t s);
+// ---- guided_color.hip: the two launches of the colour guide; launch_guided_filter has checked the arguments
+int launch_guided_color(const uint8_t* stylized, const void* content, int content_f32, int B, int Ho, int Wo, int Hc, int Wc, int radius,
+                        int eps_q, void* workspace, uint8_t* out, hipStream_t s);
 
 // ---- noise.hip ------------------------------------------------------------
 // Seeded noise for texture synthesis (noise_rule.h): out [B][H][W][3] uint8 on the device, image b = sample first_sample + b of

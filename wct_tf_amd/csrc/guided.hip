@@ -12,60 +12,10 @@
 // sums across the block (a shuffle scan per wave, the wave totals through LDS), and the window sum of column t is
 // P[t + r] - P[t - r - 1].  Pass 1's sums are below 2^31 per window, and its prefixes (256 columns x 129 rows x 65025 < 2^31)
 // are kept mod 2^32; pass 2's are int64.  The nine 64-bit divisions of a pixel are the rule's own (plain C++).
-#include "common.h"
+#include "guided_tile.h"
 #include "guided_rule.h"
 
 namespace {
-constexpr int NT = 256;               // threads of a block = columns of a strip with both halos
-constexpr int NW = NT / 64;           // waves
-constexpr int SEG = 64;               // output rows of a block
-
-__device__ __forceinline__ int sample(const uint8_t* p) { return *p; }
-__device__ __forceinline__ int sample(const float* p) { return wct_quantise_u8(*p); }
-
-// Inclusive prefix sums of K values per thread across the block, into P[k][t].  tot [K][NW] is scratch.  Two barriers; the
-// caller's reads of P and the next call's writes are separated by the first barrier of that call.
-template <typename T, int K>
-__device__ __forceinline__ void block_prefix(T (&v)[K], T (*P)[NT], T (*tot)[NW]) {
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-#pragma unroll
-  for (int k = 0; k < K; ++k) {
-    T x = v[k];
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const T up = __shfl_up(x, d, 64);
-      if (lane >= d) x += up;
-    }
-    v[k] = x;
-    if (lane == 63) tot[k][wave] = x;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < K; ++k) {
-    T base = 0;
-    for (int w = 0; w < wave; ++w) base += tot[k][w];
-    P[k][t] = v[k] + base;
-  }
-  __syncthreads();
-}
-
-// the block's place: strip and row segment of frame b
-struct Place { int b, x, y0, y1; bool col, owner; };
-__device__ __forceinline__ Place place(int H, int W, int r, int strips, int segs) {
-  const int TW = NT - 2 * r, t = threadIdx.x;
-  int id = blockIdx.x;
-  const int strip = id % strips; id /= strips;
-  const int seg = id % segs;
-  Place p;
-  p.b = id / segs;
-  p.x = strip * TW - r + t;
-  p.col = p.x >= 0 && p.x < W;                              // a column of the frame
-  p.owner = p.col && t >= r && t < r + TW;                  // ... that this block writes
-  p.y0 = seg * SEG;
-  p.y1 = p.y0 + SEG < H ? p.y0 + SEG : H;
-  return p;
-}
-
 template <typename CT>
 __global__ __launch_bounds__(NT) void guided_ab_kernel(const uint8_t* s, const CT* c, int32_t* ab, int H, int W, int Hc, int Wc, int r,
                                                        int eps_q, int strips, int segs) {
@@ -161,7 +111,7 @@ int launch(const uint8_t* s, const CT* c, int32_t* ab, int B, int H, int W, int 
 }
 }  // namespace
 
-int guided_check(int B, int Ho, int Wo, int Hc, int Wc, int radius, int eps_q) {
+int guided_check(int B, int Ho, int Wo, int Hc, int Wc, int radius, int eps_q, int guide) {
   if (B < 1 || B > 32) { wct_set_error("guided filter: B = %d frames, must be 1 .. 32", B); return WCT_ERR_ARG; }
   if (Hc < 1 || Wc < 1 || Ho < Hc || Wo < Wc) {
     wct_set_error("guided filter: a %dx%d stylized frame for a %dx%d content (the frame is never the smaller one)", Ho, Wo, Hc, Wc);
@@ -172,6 +122,10 @@ int guided_check(int B, int Ho, int Wo, int Hc, int Wc, int radius, int eps_q) {
                   WCT_GUIDED_MAX_RADIUS, WCT_GUIDED_MAX_EPS);
     return WCT_ERR_ARG;
   }
+  if (guide != GUIDE_GREY && guide != GUIDE_COLOR) {
+    wct_set_error("guided filter: guide %d, must be WCT_GUIDE_GREY (%d) or WCT_GUIDE_COLOR (%d)", guide, GUIDE_GREY, GUIDE_COLOR);
+    return WCT_ERR_ARG;
+  }
   if ((unsigned long long)B * (unsigned long long)Ho * (unsigned long long)Wo * 3ull >= (1ull << 31)) {
     wct_set_error("guided filter: %d frames of %dx%dx3 pass 2^31 bytes in one call", B, Ho, Wo);
     return WCT_ERR_ARG;
@@ -179,13 +133,16 @@ int guided_check(int B, int Ho, int Wo, int Hc, int Wc, int radius, int eps_q) {
   return WCT_OK;
 }
 
-size_t guided_workspace_bytes(int B, int Ho, int Wo) { return (size_t)B * Ho * Wo * 6 * sizeof(int32_t); }
+size_t guided_workspace_bytes(int B, int Ho, int Wo, int guide) {
+  return (size_t)B * Ho * Wo * (guide == GUIDE_COLOR ? 12 : 6) * sizeof(int32_t);
+}
 
 int launch_guided_filter(const uint8_t* stylized, const void* content, int content_f32, int B, int Ho, int Wo, int Hc, int Wc, int radius,
-                         int eps_q, void* workspace, uint8_t* out, hipStream_t s) {
+                         int eps_q, int guide, void* workspace, uint8_t* out, hipStream_t s) {
   ARG_CHECK(stylized && content && workspace && out);
-  int rc = guided_check(B, Ho, Wo, Hc, Wc, radius, eps_q);
+  int rc = guided_check(B, Ho, Wo, Hc, Wc, radius, eps_q, guide);
   if (rc) return rc;
+  if (guide == GUIDE_COLOR) return launch_guided_color(stylized, content, content_f32, B, Ho, Wo, Hc, Wc, radius, eps_q, workspace, out, s);
   if (content_f32) return launch(stylized, (const float*)content, (int32_t*)workspace, B, Ho, Wo, Hc, Wc, radius, eps_q, out, s);
   return launch(stylized, (const uint8_t*)content, (int32_t*)workspace, B, Ho, Wo, Hc, Wc, radius, eps_q, out, s);
 }

@@ -8,7 +8,7 @@ on libwct_hip.so.  Same names, argument meaning and array conventions:
   preserve_colors_np(style_rgb, content_rgb)    utils.py:87
 and, without a counterpart in the reference,
   content_colors_np(stylized_rgb, content_rgb)  luminance-only colour preservation (Gatys et al. 2016), applied to a result
-  guided_filter_np(stylized_rgb, content_rgb, radius, eps_q)   guided smoothing of a result with its content as guide (He et al.)
+  guided_filter_np(stylized_rgb, content_rgb, radius, eps_q, guide)   guided smoothing of a result with its content as guide (He et al.)
   texture_noise_np(h, w, seed, sample=0, smooth=False)   the seeded noise image a texture starts from (webcam.py:191-192 --noise)
 """
 import numpy as np
@@ -124,13 +124,14 @@ def content_colors_np(stylized_rgb, content_rgb, ctx=None):
     return ctx.content_colors(stylized_rgb, content_rgb)
 
 
-def guided_filter_np(stylized, content, radius, eps_q, ctx=None):
+def guided_filter_np(stylized, content, radius, eps_q, guide='grey', ctx=None):
     """Guided smoothing of a result (He, Sun, Tang, "Guided Image Filtering"; the post-step of Li et al. 2018's fast photorealistic
     variant): uint8 HxWx3 images, the stylized one at least as large as the content -> uint8, `stylized` filtered over a
-    (2 radius + 1)^2 box with the grey of `content` as guide (the integer rule of include/wct_hip.h, wct_guided_filter).  radius
+    (2 radius + 1)^2 box with `content` as guide: guide='grey', its grey, or guide='color', its three channels, which also keeps
+    an edge between two colours of equal luminance (the integer rules of include/wct_hip.h, wct_guided_filter_guide).  radius
     1 .. 64; eps_q 1 .. 65025 in grey levels squared (_lib.guided_eps_q(eps) for an eps of the [0,1]^2 convention)."""
     ctx = ctx or default_context()
-    return ctx.guided_filter(stylized, content, radius, eps_q)
+    return ctx.guided_filter(stylized, content, radius, eps_q, guide=guide)
 
 
 def texture_noise_np(h, w, seed, sample=0, smooth=False, ctx=None):

@@ -12,7 +12,9 @@ luminance and the content's chrominance.  Unlike `--keep-colors` (CORAL on the s
 with prepared styles and every other option.
 `--guided-radius R [--guided-eps E]` is the photo mode: the result is smoothed by a guided filter with the content as guide (He
 et al., "Guided Image Filtering"; the post-step of Li et al. 2018's fast photorealistic variant) -- edges where the content has
-them, averages where it is flat.  Not in bands."""
+them, averages where it is flat.  `--guided-guide color` guides it with the content's three channels where the default, `grey`,
+takes their grey: it also keeps an edge between two colours of equal luminance, at about three times the filter's cost.  Not in
+bands."""
 import argparse
 import os
 import time
@@ -41,6 +43,9 @@ _FLAGS = [
                                      'content; before --content-colors.  Not with --band-rows')),
     (('--guided-eps',), dict(type=float, default=0.01, metavar='E',
                              help='the regulariser of --guided-radius for images in [0,1] (> 0): smaller keeps more edges')),
+    (('--guided-guide',), dict(choices=['grey', 'color'], default=None,
+                               help='the guide of --guided-radius: grey (the default), the grey of the content, or color, its three '
+                                    'channels -- keeps edges between colours of equal luminance too.  Needs --guided-radius > 0')),
     (('--device',), dict(default='/gpu:0', help='e.g. /gpu:0')),
     (('--style-size',), dict(type=int, default=0, help='short side of the style image (0: as is)')),
     (('--crop-size',), dict(type=int, default=0, help='centre-crop the style image to a square of this side (0: no)')),
@@ -149,8 +154,10 @@ def check_color_args(parser, args):
 
 
 def check_guided_args(parser, args):
-    """--guided-radius / --guided-eps: their ranges (parser.error exits)"""
+    """--guided-radius / --guided-eps / --guided-guide: their ranges (parser.error exits)"""
     from ._lib import GUIDED_MAX_RADIUS
+    if getattr(args, 'guided_guide', None) is not None and not args.guided_radius > 0:
+        parser.error('--guided-guide needs --guided-radius > 0 (it chooses the guide of that filter)')
     if not 0 <= args.guided_radius <= GUIDED_MAX_RADIUS:
         parser.error('--guided-radius must be 0 (off) .. %d, got %d' % (GUIDED_MAX_RADIUS, args.guided_radius))
     if not (np.isfinite(args.guided_eps) and args.guided_eps > 0):
@@ -160,10 +167,14 @@ def check_guided_args(parser, args):
 
 
 def guided_of(args):
-    """(radius, eps_q) of --guided-radius / --guided-eps, eps in grey levels squared and at most 65025; None: off"""
+    """(radius, eps_q) of --guided-radius / --guided-eps, eps in grey levels squared and at most 65025 -- (radius, eps_q, 'color')
+    with --guided-guide color; None: off"""
     from ._lib import guided_eps_q, GUIDED_MAX_EPS
     r = getattr(args, 'guided_radius', 0)
-    return (r, min(GUIDED_MAX_EPS, guided_eps_q(getattr(args, 'guided_eps', 0.01)))) if r else None
+    if not r:
+        return None
+    g = (r, min(GUIDED_MAX_EPS, guided_eps_q(getattr(args, 'guided_eps', 0.01))))
+    return g + ('color',) if getattr(args, 'guided_guide', None) == 'color' else g
 
 
 def _unbanded(args):
@@ -199,7 +210,7 @@ def run_passes(model, content, args, predict):
     prediction of a single pass; several passes run plain (a later pass sees a stylized input, not the content) and the
     stand-alone op then runs once, against the original content -- at one pass the two routes give the same bits.
     --guided-radius is treated the same way, and runs before the colour op; only then is predict called with a third argument,
-    predict(image, content_colors, guided): (radius, eps_q) for the single pass, None for each of several."""
+    predict(image, content_colors, guided): (radius, eps_q[, 'color']) for the single pass, None for each of several."""
     n = max(1, args.passes)
     colors = getattr(args, 'content_colors', False)
     guided = guided_of(args)
@@ -208,7 +219,7 @@ def run_passes(model, content, args, predict):
         out = predict(out, colors and n == 1, guided if n == 1 else None) if guided else predict(out, colors and n == 1)
     if guided and n > 1:
         from .ops import guided_filter_np
-        out = guided_filter_np(out, content, guided[0], guided[1], ctx=model.sess)
+        out = guided_filter_np(out, content, guided[0], guided[1], ctx=model.sess, **({'guide': guided[2]} if len(guided) > 2 else {}))
     if colors and n > 1:
         from .ops import content_colors_np
         out = content_colors_np(out, content, ctx=model.sess)

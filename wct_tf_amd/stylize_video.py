@@ -15,7 +15,8 @@ MI355X path.  Same flags.  Differences, all forced by the environment or by the 
   `--mask-path` and `--warm-start`.
 * `--guided-radius R [--guided-eps E]` (the photo mode) smooths every stylized frame with a guided filter whose guide is the input
   frame (He et al., "Guided Image Filtering"): edges where the frame has them, averages where it is flat.  It runs at the end of the
-  batched call, before `--content-colors`, and goes with every other option.
+  batched call, before `--content-colors`, and goes with every other option.  `--guided-guide color` guides it with the frame's
+  three channels instead of their grey, which also keeps an edge between two colours of equal luminance.
 * `--device-resize` (opt-in) applies `--content-size` on the device: the frames go up raw and are resized there, on the stream
   of the call that stylizes them, to the bytes Pillow's bilinear resize gives on the host -- the same frames come out.
 """
@@ -58,6 +59,9 @@ _FLAGS = [
                                      'frames; before --content-colors')),
     (('--guided-eps',), dict(type=float, default=0.01, metavar='E',
                              help='the regulariser of --guided-radius for images in [0,1] (> 0): smaller keeps more edges')),
+    (('--guided-guide',), dict(choices=['grey', 'color'], default=None,
+                               help='the guide of --guided-radius: grey (the default), the grey of the input frame, or color, its three '
+                                    'channels -- keeps edges between colours of equal luminance too.  Needs --guided-radius > 0')),
     (('--style-size',), dict(type=int, default=0, help='short side of the style image (0: as is)')),
     (('--crop-size',), dict(type=int, default=0, help='centre-crop the style image to a square of this side (0: no)')),
     (('--content-size',), dict(type=int, default=0, help='short side of every frame (0: as is)')),
@@ -206,7 +210,8 @@ def content_colors_frames(wct_model, stylized, frames):
 
 def guided_frames(wct_model, stylized, frames, guided):
     """the stand-alone filter on a group of frames (after --passes > 1): `stylized` smoothed with `frames` as guides"""
-    return np.concatenate([wct_model.sess.guided_filter_batch(stylized[i:i + 32], frames[i:i + 32], guided[0], guided[1])
+    return np.concatenate([wct_model.sess.guided_filter_batch(stylized[i:i + 32], frames[i:i + 32], guided[0], guided[1],
+                                                              guide=guided[2] if len(guided) > 2 else 'grey')
                            for i in range(0, len(frames), 32)], axis=0)
 
 

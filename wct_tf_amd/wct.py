@@ -255,7 +255,7 @@ class WCT(object):
 
     @staticmethod
     def _check_guided(guided):
-        '''guided=(radius, eps_q) of a predict* call, checked: None stays None'''
+        '''guided=(radius, eps_q) or (radius, eps_q, 'grey' or 'color') of a predict* call, checked: None stays None'''
         from .context import check_guided
         return None if guided is None else check_guided(guided)
 
@@ -278,7 +278,9 @@ class WCT(object):
            smoothing, the photo mode (He et al., "Guided Image Filtering"; WCT_FLAG_GUIDED): the frame is filtered over a
            (2 radius + 1)^2 box with the grey of `content` as guide, eps_q in grey levels squared (_lib.guided_eps_q(eps)); it
            equals ops.guided_filter_np(the plain frame, content, radius, eps_q) bit for bit, and with content_colors the colour op
-           runs after it.  Not served in bands, with wrap or for textures: ValueError.'''
+           runs after it.  (radius, eps_q, 'color') guides with the three channels of `content` (guide='color' of the op), which
+           also keeps an edge between two colours of equal luminance; (radius, eps_q, 'grey') is the two-element form.  Not
+           served in bands, with wrap or for textures: ValueError.'''
         guided = self._check_guided(guided)                                       # ValueError before any GPU call
         if strength is not None:
             from ._lib import strength_map
