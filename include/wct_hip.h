@@ -269,6 +269,34 @@ int wct_guided_filter_guide(wct_ctx* ctx, const uint8_t* stylized, int Ho, int W
 int wct_guided_filter_guide_batch_dev(wct_ctx* ctx, const uint8_t* stylized_dev, int Ho, int Wo, const uint8_t* content_dev, int Hc,
                                       int Wc, int B, int radius, int eps_q, int guide, uint8_t* out_dev);
 int wct_set_guided_guide(wct_ctx* ctx, int guide);
+/* Temporal guided smoothing: the grey-guide filter above with its box extended along time, against the flicker of a video whose
+ * frames were stylized one by one.  Where the content does not change between neighbouring frames the stylized frames are averaged
+ * over them; where it moves, the guide's variance in the window is large and the result follows the guide, as at a spatial edge.
+ * The rule and its bounds: csrc/guided_time_rule.h.  A clip is F frames, s [F][Ho][Wo][3] and c [F][Hc][Wc][3]; T = frames_t is
+ * the number of frames on each side, 0 .. 3; I(f, y, x) is the guide above of content frame f:
+ *   window     = the box above at (y, x) in each frame of max(0, f - T) .. min(F - 1, f + T): cut at the clip's ends as it is cut
+ *                at the image's borders, n = rows x columns x frames of it
+ *   pass 1:    SI, SII, Sp, SIp over that window; a_q, b_q of (f, y, x) by the formulas above with this n
+ *   pass 2:    out.ch(f, y, x) = clamp(rdiv(I(f, y, x) sum a_q + sum b_q, n 2^12), 0, 255), the sums over the same window
+ * T = 0 is wct_guided_filter_batch_dev, bit for bit; a one-frame clip is too, whatever T.  Parameters: those of wct_guided_filter,
+ * 0 <= T <= 3, and (2r + 1)^2 (2T + 1) <= 33025 (= floor(2^31 / 65025): every window sum of pass 1 stays below 2^31), which is
+ * r <= 64 / 51 / 40 / 33 at T = 0 / 1 / 2 / 3 -- wct_guided_time_max_radius(T), 0 for a T outside 0 .. 3.
+ * wct_guided_filter_time: host pointers, blocking, the whole clip, F = 1 .. 32.
+ * wct_guided_filter_time_batch_dev: device pointers, two launches, asynchronous on the ctx stream; F = 1 .. 32 resident frames,
+ *   0 <= f0 < f1 <= F; writes out_dev [f1 - f0][Ho][Wo][3], the filtered frames f0 .. f1 - 1 of THIS clip of F frames.  out_dev may
+ *   be stylized_dev + f0 Ho Wo 3 (in place).  The 24 B per pixel of the F frames live in the workspace of wct_guided_filter.
+ *   A frame depends on the stylized frames up to 2T away (pass 2 reads coefficients T frames away, each made from frames T further):
+ *   a caller that wants the bytes of a longer video gives 2T real frames of halo on each side of [f0, f1), except at the video's
+ *   own ends.  A halo of T frames does not give them.
+ * A null pointer, F outside 1 .. 32, a range that is not 0 <= f0 < f1 <= F, Ho < Hc, Wo < Wc, parameters outside the above, or
+ * F * Ho * Wo * 3 >= 2^31 is WCT_STATUS_ARG with a message and leaves the ctx usable.
+ * Not served: the colour guide along time, T above 3, motion compensation of any kind (a flat region that pans has its stylized
+ * texture averaged along time), WCT_FLAG_GUIDED along time (a frame would need frames that come after it). */
+int wct_guided_filter_time(wct_ctx* ctx, const uint8_t* stylized, int Ho, int Wo, const uint8_t* content, int Hc, int Wc, int F,
+                           int radius, int eps_q, int frames_t, uint8_t* out);
+int wct_guided_filter_time_batch_dev(wct_ctx* ctx, const uint8_t* stylized_dev, int Ho, int Wo, const uint8_t* content_dev, int Hc,
+                                     int Wc, int F, int radius, int eps_q, int frames_t, int f0, int f1, uint8_t* out_dev);
+int wct_guided_time_max_radius(int frames_t);
 /* On-device resize (the reference's resize_to, utils.py:55-67, behind --content-size, stylize_video.py:29; webcam.py:163,189
  * resizes every frame by --scale): img [H][W][3] uint8 -> [h][w][3] uint8, the bytes of Pillow's Image.resize((w, h), Image.BILINEAR).
  * Pillow's 8-bit resampler is an integer rule.  Per axis (`in` the input length, `out` the output length; everything up to the

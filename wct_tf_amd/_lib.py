@@ -56,6 +56,10 @@ SIGNATURES = [
     ('wct_guided_filter_guide', C.c_int, [_P, _U8, C.c_int, C.c_int, _U8, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _U8]),
     ('wct_guided_filter_guide_batch_dev', C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     ('wct_set_guided_guide', C.c_int, [_P, C.c_int]),
+    ('wct_guided_filter_time', C.c_int, [_P, _U8, C.c_int, C.c_int, _U8, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _U8]),
+    ('wct_guided_filter_time_batch_dev', C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                   C.c_int, C.c_int, _P]),
+    ('wct_guided_time_max_radius', C.c_int, [C.c_int]),
     ('wct_resize', C.c_int, [_P, _U8, C.c_int, C.c_int, C.c_int, C.c_int, _U8]),
     ('wct_resize_batch_dev', C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     ('wct_output_size', C.c_int, [C.c_int, C.c_int, _I, C.c_int, _I, _I]),
@@ -143,6 +147,9 @@ FLAG_GUIDED = 64
 GUIDED_MAX_RADIUS, GUIDED_MAX_EPS = 64, 65025      # csrc/guided_rule.h
 GUIDE_GREY, GUIDE_COLOR = 0, 1                     # WCT_GUIDE_*: the guide of guided smoothing
 GUIDES = {'grey': GUIDE_GREY, 'color': GUIDE_COLOR}
+# temporal guided smoothing (csrc/guided_time_rule.h): the largest radius at T = 0 .. 3 frames on each side, from
+# (2r + 1)^2 (2T + 1) <= 33025; wct_guided_time_max_radius(T) returns the same numbers
+GUIDED_TIME_MAX_RADIUS = (64, 51, 40, 33)
 
 
 def guided_eps_q(eps):

@@ -87,6 +87,35 @@ def check_guided(guided):
     return r, e
 
 
+def check_guided_time(radius, eps_q, frames_t):
+    """The refusals of temporal guided smoothing's parameters, before any library call: check_guided's, frames_t an integer
+    0 .. 3 and the radius within the limit for it (_lib.GUIDED_TIME_MAX_RADIUS: (2 radius + 1)^2 (2 frames_t + 1) <= 33025).
+    -> (radius, eps_q, frames_t)"""
+    r, e = check_guided((radius, eps_q))
+    try:
+        if int(frames_t) != frames_t:
+            raise TypeError
+        t = int(frames_t)
+    except (TypeError, ValueError):
+        raise ValueError('guided_frames is an integer 0 .. %d, got %r' % (len(_lib.GUIDED_TIME_MAX_RADIUS) - 1, frames_t))
+    if not 0 <= t < len(_lib.GUIDED_TIME_MAX_RADIUS):
+        raise ValueError('guided_frames must be 0 .. %d frames on each side, got %d' % (len(_lib.GUIDED_TIME_MAX_RADIUS) - 1, t))
+    if r > _lib.GUIDED_TIME_MAX_RADIUS[t]:
+        raise ValueError('the guided radius must be 1 .. %d with guided_frames %d, got %d' % (_lib.GUIDED_TIME_MAX_RADIUS[t], t, r))
+    return r, e, t
+
+
+def _guided_clip(stylized, contents):
+    """The refusals of a clip and its contents, before any library call -> both as contiguous uint8 [F][..][..][3], F >= 1"""
+    try:
+        s, c = _color_images(stylized, contents, 4)
+    except ValueError as e:
+        raise ValueError(str(e).replace('content_colors', 'guided_filter_time'))
+    if s.shape[0] != c.shape[0]:
+        raise ValueError('a clip takes as many contents as frames, got %d and %d' % (s.shape[0], c.shape[0]))
+    return s, c
+
+
 def _guided_images(stylized, content, ndim):
     """The refusals of guided_filter's images, before any library call (those of content_colors) -> both as contiguous uint8"""
     try:
@@ -846,6 +875,63 @@ class Context(object):
             raise ValueError('a batch takes 1 .. %d frames and as many contents, got %d and %d' % (_lib.BATCH_MAX, s.shape[0], c.shape[0]))
         return self._host_batch([s, c], np.empty_like(s), in_place=True, enqueue=lambda ds, dc: self.guided_filter_batch_dev(
             ds, s.shape[1], s.shape[2], dc, c.shape[1], c.shape[2], s.shape[0], r, e, ds, guide=guide))
+
+    # ---- temporal guided smoothing: the filter's box across frames --------------------------
+    def guided_filter_time(self, stylized_u8, contents_u8, radius, eps_q, frames_t):
+        """Temporal guided smoothing of a clip (wct_guided_filter_time): stylized [F][Ho][Wo][3] and contents [F][Hc][Wc][3] uint8,
+        F <= 32 -> uint8 [F][Ho][Wo][3], the grey-guide filter of guided_filter with its box extended over the frames_t (0 .. 3)
+        frames on each side of a frame, cut at the clip's ends.  frames_t = 0 is guided_filter_batch.  The radius is at most
+        64 / 51 / 40 / 33 at frames_t 0 / 1 / 2 / 3.  A longer clip: ops.guided_filter_time_np."""
+        s, c = _guided_clip(stylized_u8, contents_u8)
+        r, e, t = check_guided_time(radius, eps_q, frames_t)
+        if not 1 <= s.shape[0] <= _lib.BATCH_MAX:
+            raise ValueError('a clip takes 1 .. %d frames in one call, got %d (ops.guided_filter_time_np takes any length)'
+                             % (_lib.BATCH_MAX, s.shape[0]))
+        out = np.empty_like(s)
+        check(self.lib.wct_guided_filter_time(self.h, s.ctypes.data_as(_lib._U8), s.shape[1], s.shape[2], c.ctypes.data_as(_lib._U8),
+                                              c.shape[1], c.shape[2], s.shape[0], r, e, t, out.ctypes.data_as(_lib._U8)))
+        return out
+
+    def guided_filter_time_batch_dev(self, stylized_dev, ho, wo, content_dev, hc, wc, frames, radius, eps_q, frames_t, f0, f1, out_dev):
+        """Frames f0 .. f1 - 1 of the clip of `frames` frames resident in HBM, filtered along time as a clip of its own
+        (wct_guided_filter_time_batch_dev) -> out_dev [f1 - f0][ho][wo][3]: asynchronous; out_dev may be the address of frame f0 of
+        stylized_dev.  The bytes of a longer video need 2 frames_t real frames of halo on each side of [f0, f1)."""
+        r, e, t = check_guided_time(radius, eps_q, frames_t)
+        if not (1 <= int(frames) <= _lib.BATCH_MAX and 0 <= int(f0) < int(f1) <= int(frames)):
+            raise ValueError('a clip takes 1 .. %d frames and a range 0 <= f0 < f1 <= frames, got %d frames and [%d, %d)'
+                             % (_lib.BATCH_MAX, frames, f0, f1))
+        check(self.lib.wct_guided_filter_time_batch_dev(self.h, stylized_dev, int(ho), int(wo), content_dev, int(hc), int(wc), int(frames),
+                                                        r, e, t, int(f0), int(f1), out_dev))
+
+    def guided_time_max_radius(self, frames_t):
+        """The largest radius of temporal guided smoothing with frames_t frames on each side (wct_guided_time_max_radius): the
+        entries of _lib.GUIDED_TIME_MAX_RADIUS; 0 for a frames_t outside 0 .. 3"""
+        return int(self.lib.wct_guided_time_max_radius(int(frames_t)))
+
+    def guided_filter_time_clip(self, stylized_u8, contents_u8, radius, eps_q, frames_t):
+        """guided_filter_time for a clip of any length: chunks of at most 32 - 4 frames_t output frames, each uploaded with
+        2 frames_t frames of halo on each side (fewer at the clip's ends) and filtered as a clip of its own -- the whole clip's
+        bytes, since a frame depends on no frame further than 2 frames_t away."""
+        s, c = _guided_clip(stylized_u8, contents_u8)
+        r, e, t = check_guided_time(radius, eps_q, frames_t)
+        n, step, out = s.shape[0], _lib.BATCH_MAX - 4 * t, np.empty_like(s)
+        for f0 in range(0, n, step):
+            f1 = min(n, f0 + step)
+            g0, g1 = max(0, f0 - 2 * t), min(n, f1 + 2 * t)
+            self.guided_filter_time_range(s[g0:g1], c[g0:g1], r, e, t, f0 - g0, f1 - g0, out=out[f0:f1])
+        return out
+
+    def guided_filter_time_range(self, stylized_u8, contents_u8, radius, eps_q, frames_t, f0, f1, out=None):
+        """Host arrays in, host array out: frames f0 .. f1 - 1 of the clip stylized [F][Ho][Wo][3] with contents [F][Hc][Wc][3]
+        (F <= 32), filtered along time as guided_filter_time_batch_dev does -> uint8 [f1 - f0][Ho][Wo][3]"""
+        s, c = _guided_clip(stylized_u8, contents_u8)
+        r, e, t = check_guided_time(radius, eps_q, frames_t)
+        if not (1 <= s.shape[0] <= _lib.BATCH_MAX and 0 <= f0 < f1 <= s.shape[0]):
+            raise ValueError('a clip takes 1 .. %d frames and a range 0 <= f0 < f1 <= frames, got %d frames and [%d, %d)'
+                             % (_lib.BATCH_MAX, s.shape[0], f0, f1))
+        out = np.empty((f1 - f0,) + s.shape[1:], np.uint8) if out is None else out
+        return self._host_batch([s, c], out, enqueue=lambda ds, dc, do: self.guided_filter_time_batch_dev(
+            ds, s.shape[1], s.shape[2], dc, c.shape[1], c.shape[2], s.shape[0], r, e, t, f0, f1, do))
 
     # ---- on-device resize: Pillow's bilinear bytes ------------------------------------------
     def resize(self, img_u8, size):

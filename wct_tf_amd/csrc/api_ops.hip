@@ -748,6 +748,37 @@ extern "C" int wct_guided_filter(wct_ctx* c, const uint8_t* stylized, int Ho, in
   return wct_guided_filter_guide(c, stylized, Ho, Wo, content, Hc, Wc, radius, eps_q, WCT_GUIDE_GREY, out);
 }
 
+// Temporal guided smoothing, op level (csrc/guided_time.hip): frames f0 .. f1 - 1 of a clip of F resident frames, the coefficient
+// map of the whole clip in the workspace of the 2-D op
+extern "C" int wct_guided_filter_time_batch_dev(wct_ctx* c, const uint8_t* stylized, int Ho, int Wo, const uint8_t* content, int Hc,
+                                                int Wc, int F, int radius, int eps_q, int frames_t, int f0, int f1, uint8_t* out) {
+  ARG_CHECK(c != nullptr);
+  if (!stylized || !content || !out) { wct_set_error("guided filter along time: null image pointer"); return WCT_ERR_ARG; }
+  TRY(guided_time_check(F, Ho, Wo, Hc, Wc, radius, eps_q, frames_t, f0, f1));
+  HIP_TRY(hipSetDevice(c->device));
+  TRY(ensure(c, c->guided_ab, guided_workspace_bytes(F, Ho, Wo, GUIDE_GREY)));
+  // per pixel of the n1 frames of pass 1: s and c read twice in each of the up to 2T + 1 frames of the window, the map written;
+  // of the n2 frames of pass 2: the map read twice in each frame of the window, c read, the frame written
+  const int n1 = (f1 + frames_t > F ? F : f1 + frames_t) - (f0 - frames_t < 0 ? 0 : f0 - frames_t), n2 = f1 - f0, win = 2 * frames_t + 1;
+  ProfScope ps(c, 7, 0, (double)Ho * Wo * (n1 * (win * 2 * 6 + 24.0) + n2 * (win * 2 * 24.0 + 3 + 3)));
+  return launch_guided_time(stylized, content, 0, F, Ho, Wo, Hc, Wc, radius, eps_q, frames_t, f0, f1, c->guided_ab.p, out, c->stream);
+}
+
+extern "C" int wct_guided_filter_time(wct_ctx* c, const uint8_t* stylized, int Ho, int Wo, const uint8_t* content, int Hc, int Wc, int F,
+                                      int radius, int eps_q, int frames_t, uint8_t* out) {
+  ARG_CHECK(c != nullptr);
+  if (!stylized || !content || !out) { wct_set_error("guided filter along time: null image pointer"); return WCT_ERR_ARG; }
+  TRY(guided_time_check(F, Ho, Wo, Hc, Wc, radius, eps_q, frames_t, 0, F));                 // (before the staging buffers are sized)
+  HIP_TRY(hipSetDevice(c->device));
+  void *ds, *dc;
+  TRY(stage_in(c, 0, stylized, (size_t)F * Ho * Wo * 3, &ds));
+  TRY(stage_in(c, 1, content, (size_t)F * Hc * Wc * 3, &dc));
+  TRY(wct_guided_filter_time_batch_dev(c, (uint8_t*)ds, Ho, Wo, (uint8_t*)dc, Hc, Wc, F, radius, eps_q, frames_t, 0, F, (uint8_t*)ds));
+  return fetch(c, out, ds, (size_t)F * Ho * Wo * 3);
+}
+
+extern "C" int wct_guided_time_max_radius(int frames_t) { return guided_time_max_radius(frames_t); }
+
 // Seeded noise images for texture synthesis, op level (csrc/noise.hip): the refusals both calls share
 static int texture_noise_checks(int H, int W, int B, const void* out) {
   if (!out) { wct_set_error("texture noise: null output pointer"); return WCT_ERR_ARG; }

@@ -372,6 +372,17 @@ int launch_guided_filter(const uint8_t* stylized, const void* content, int conte
 // ---- guided_color.hip: the two launches of the colour guide; launch_guided_filter has checked the arguments
 int launch_guided_color(const uint8_t* stylized, const void* content, int content_f32, int B, int Ho, int Wo, int Hc, int Wc, int radius,
                         int eps_q, void* workspace, uint8_t* out, hipStream_t s);
+// ---- guided_time.hip ------------------------------------------------------
+// Temporal guided smoothing (guided_time_rule.h): the grey-guide filter with its box extended over frames_t frames on each side,
+// on a clip of F frames [F][Ho][Wo][3] with contents [F][Hc][Wc][3] resident on the device.  out [f1 - f0][Ho][Wo][3] = the
+// filtered frames f0 .. f1 - 1 of that clip; it may be stylized + f0 Ho Wo 3.  Two launches; workspace:
+// guided_workspace_bytes(F, Ho, Wo, GUIDE_GREY) bytes (a frame's coefficients sit at its position in the clip).
+// guided_time_check: F outside 1 .. 32, a range that is not 0 <= f0 < f1 <= F, Ho < Hc or Wo < Wc, parameters outside
+// wct_guided_time_params_ok, or F * Ho * Wo * 3 >= 2^31 is WCT_ERR_ARG with a message.
+int guided_time_check(int F, int Ho, int Wo, int Hc, int Wc, int radius, int eps_q, int frames_t, int f0, int f1);
+int guided_time_max_radius(int frames_t);                  // 64 / 51 / 40 / 33 at 0 .. 3 frames on each side, else 0
+int launch_guided_time(const uint8_t* stylized, const void* content, int content_f32, int F, int Ho, int Wo, int Hc, int Wc, int radius,
+                       int eps_q, int frames_t, int f0, int f1, void* workspace, uint8_t* out, hipStream_t s);
 
 // ---- noise.hip ------------------------------------------------------------
 // Seeded noise for texture synthesis (noise_rule.h): out [B][H][W][3] uint8 on the device, image b = sample first_sample + b of

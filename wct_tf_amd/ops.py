@@ -134,6 +134,18 @@ def guided_filter_np(stylized, content, radius, eps_q, guide='grey', ctx=None):
     return ctx.guided_filter(stylized, content, radius, eps_q, guide=guide)
 
 
+def guided_filter_time_np(stylized, contents, radius, eps_q, frames_t, ctx=None):
+    """Temporal guided smoothing of a stylized clip, against the flicker of frames that were stylized one by one: uint8
+    [F][Ho][Wo][3] frames and [F][Hc][Wc][3] contents of any F -> uint8 [F][Ho][Wo][3], guided_filter_np's grey-guide filter with
+    its box extended over the frames_t (0 .. 3) frames on each side of a frame and cut at the clip's ends (the integer rule of
+    include/wct_hip.h, wct_guided_filter_time).  Where the content stands still the frames are averaged along time; where it
+    moves the result follows the content.  No motion compensation: a flat region that pans is averaged too.  radius 1 ..
+    64 / 51 / 40 / 33 at frames_t 0 / 1 / 2 / 3.  A clip of more than 32 frames goes in chunks of 32 - 4 frames_t frames with
+    halos of 2 frames_t and gives the whole clip's bytes."""
+    ctx = ctx or default_context()
+    return ctx.guided_filter_time_clip(stylized, contents, radius, eps_q, frames_t)
+
+
 def texture_noise_np(h, w, seed, sample=0, smooth=False, ctx=None):
     """The noise image that texture synthesis starts from (Li et al. 2017, sec. 4.3) -> uint8 [h][w][3].  The reference draws it
     with `np.random.randint(0, 256, shape, np.uint8)` (webcam.py:191-192); here it is the seeded integer rule of include/wct_hip.h

@@ -17,6 +17,11 @@ MI355X path.  Same flags.  Differences, all forced by the environment or by the 
   frame (He et al., "Guided Image Filtering"): edges where the frame has them, averages where it is flat.  It runs at the end of the
   batched call, before `--content-colors`, and goes with every other option.  `--guided-guide color` guides it with the frame's
   three channels instead of their grey, which also keeps an edge between two colours of equal luminance.
+* `--guided-frames T` (1 .. 3, with `--guided-radius`) extends that filter's box over the T frames on each side of a frame, against
+  the flicker of frames stylized one by one: where the input stands still the stylized frames are averaged along time, where it
+  moves the result follows the input.  No motion compensation.  A clip is a run of consecutive frames of one size; every frame
+  equals the whole-clip filter on the plain frames of its clip whatever `--batch` is (a sliding buffer of at most 32 + `--batch`
+  frames, never the whole video).  Grey guide only; not with `--swap5`, `--keep-colors` or `--mask-path`.
 * `--device-resize` (opt-in) applies `--content-size` on the device: the frames go up raw and are resized there, on the stream
   of the call that stylizes them, to the bytes Pillow's bilinear resize gives on the host -- the same frames come out.
 """
@@ -62,6 +67,11 @@ _FLAGS = [
     (('--guided-guide',), dict(choices=['grey', 'color'], default=None,
                                help='the guide of --guided-radius: grey (the default), the grey of the input frame, or color, its three '
                                     'channels -- keeps edges between colours of equal luminance too.  Needs --guided-radius > 0')),
+    (('--guided-frames',), dict(type=int, default=0, metavar='T',
+                                help='temporal guided smoothing, against flicker: the box of --guided-radius also covers the T frames '
+                                     'on each side of a frame (0 .. 3; 0: off), within every run of consecutive frames of one size. '
+                                     'The radius is then at most 51 / 40 / 33 at T = 1 / 2 / 3.  Grey guide only; not with --swap5, '
+                                     '--keep-colors or --mask-path')),
     (('--style-size',), dict(type=int, default=0, help='short side of the style image (0: as is)')),
     (('--crop-size',), dict(type=int, default=0, help='centre-crop the style image to a square of this side (0: no)')),
     (('--content-size',), dict(type=int, default=0, help='short side of every frame (0: as is)')),
@@ -178,6 +188,26 @@ def check_guided_args(parser, args):
     if args.guided_radius and getattr(args, 'device_resize', False) and args.passes > 1:
         parser.error('--device-resize with --guided-radius needs --passes 1 (the stand-alone filter needs the resized frames on '
                      'the host)')
+    check_guided_frames_args(parser, args)
+
+
+def check_guided_frames_args(parser, args):
+    """--guided-frames: its range, the radius it allows, and the combinations it refuses (parser.error exits)"""
+    from ._lib import GUIDED_TIME_MAX_RADIUS
+    t = getattr(args, 'guided_frames', 0)
+    if not 0 <= t < len(GUIDED_TIME_MAX_RADIUS):
+        parser.error('--guided-frames must be 0 (off) .. %d frames on each side, got %d' % (len(GUIDED_TIME_MAX_RADIUS) - 1, t))
+    if not t:
+        return
+    if not args.guided_radius:
+        parser.error('--guided-frames needs --guided-radius > 0 (it extends that filter along time)')
+    if args.guided_radius > GUIDED_TIME_MAX_RADIUS[t]:
+        parser.error('--guided-radius must be at most %d with --guided-frames %d, got %d' % (GUIDED_TIME_MAX_RADIUS[t], t, args.guided_radius))
+    if args.guided_guide == 'color':
+        parser.error('--guided-frames goes with the grey guide: --guided-guide color has no form along time')
+    for flag, on in (('--swap5', args.swap5), ('--keep-colors', args.keep_colors), ('--mask-path', args.mask_path is not None)):
+        if on:
+            parser.error('--guided-frames does not combine with %s' % flag)
 
 
 def check_resize_args(parser, args):
@@ -213,6 +243,41 @@ def guided_frames(wct_model, stylized, frames, guided):
     return np.concatenate([wct_model.sess.guided_filter_batch(stylized[i:i + 32], frames[i:i + 32], guided[0], guided[1],
                                                               guide=guided[2] if len(guided) > 2 else 'grey')
                            for i in range(0, len(frames), 32)], axis=0)
+
+
+def smooth_clips(batches, frames_t, op, window=32):
+    """--guided-frames T on a stream of batches: `batches` yields (files, plain frames [B][..], contents [B][..], per-frame extras)
+    in order; a clip is a maximal run of consecutive frames of one size.  Yields the same tuples, the frames filtered along time
+    within their clip -- each equal to the whole-clip op, wherever the batches were cut -- by op(plain [F], contents [F], f0, f1)
+    -> the filtered frames f0 .. f1 - 1 of a resident clip of F <= `window` frames.  A frame depends on no frame further than 2T
+    away, so the buffer holds one chunk of window - 4T frames, 2T frames behind it and what has arrived in front of it (2T are
+    needed, except at the clip's end): never the whole video."""
+    halo, step = 2 * frames_t, window - 4 * frames_t
+    buf, done = [], 0                      # (file, plain, content, extra) from the oldest frame still needed; buf[:done] were yielded
+
+    def flush(final):
+        nonlocal buf, done
+        while True:
+            ready = len(buf) if final else len(buf) - halo          # frames whose look-ahead is there
+            if ready - done < (1 if final else step):
+                return
+            f0, f1 = done, min(ready, done + step)
+            g0, g1 = max(0, f0 - halo), min(len(buf), f1 + halo)
+            outs = op(np.stack([b[1] for b in buf[g0:g1]]), np.stack([b[2] for b in buf[g0:g1]]), f0 - g0, f1 - g0)
+            yield [b[0] for b in buf[f0:f1]], outs, np.stack([b[2] for b in buf[f0:f1]]), [b[3] for b in buf[f0:f1]]
+            drop = max(0, f1 - halo)
+            buf, done = buf[drop:], f1 - drop
+
+    for files, plain, contents, extras in batches:
+        if buf and (plain.shape[1:] != buf[-1][1].shape or contents.shape[1:] != buf[-1][2].shape):
+            for item in flush(True):                                # the clip has ended
+                yield item
+            buf, done = [], 0
+        buf.extend(zip(files, plain, contents, extras))
+        for item in flush(False):
+            yield item
+    for item in flush(True):
+        yield item
 
 
 def match_masks(mask_path, frame_files, what='label maps'):
@@ -316,51 +381,67 @@ def stylize_frames(wct_model, frame_files, style_img, args, alpha_files=None):
     # --content-colors: fused into a single pass; after several plain passes the op runs once, against the input frames
     colors = getattr(args, 'content_colors', False)
     guided = guided_of(args)                                      # --guided-radius: the same, in front of the colour op
+    # --guided-frames T: the batches come out plain (all passes), and the filter along time and then the colour op run on a
+    # sliding buffer of them (smooth_clips), so that a frame does not depend on where the batches were cut
+    frames_t = getattr(args, 'guided_frames', 0)
+    guided_here, colors_here = (None, False) if frames_t else (guided, colors)
 
     def run(frames, style, files):
+        """-> (the stylized frames, their contents at the size the network saw them)"""
         style = prepared if prepared is not None else style
         size = device_size(args, frames)
         maps = strengths_of(files, size or frames.shape[1:3]) if alpha_files is not None else None     # (one pass: check_alpha_map_args)
         out = wct_model.predict_frames(frames, style, args.alpha, args.swap5, args.ss_alpha, args.adain, batch=args.batch, warm=warm,
-                                       content_colors=colors and args.passes <= 1, resize=size, strengths=maps,
-                                       guided=guided if args.passes <= 1 else None)
+                                       content_colors=colors_here and args.passes <= 1, resize=size, strengths=maps,
+                                       guided=guided_here if args.passes <= 1 else None)
         for _ in range(args.passes - 1):                      # later passes: plain WCT, as stylize_video.py:124-126
             out = wct_model.predict_frames(out, style, args.alpha, adain=args.adain, batch=args.batch)
-        if guided and args.passes > 1:
+        if guided_here and args.passes > 1:
             out = guided_frames(wct_model, out, frames, guided)
-        if colors and args.passes > 1:
+        if colors_here and args.passes > 1:
             out = content_colors_frames(wct_model, out, frames)
-        return out
+        if frames_t and size is not None:                     # --device-resize: the filter's guide is the resized frame
+            frames = np.concatenate([wct_model.sess.resize_batch(frames[k:k + 32], size) for k in range(0, len(frames), 32)], axis=0)
+        return out, frames
 
-    i = 0
-    while i < len(frame_files):
-        first = load(frame_files[i])
-        group_files, group = [frame_files[i]], [first]
-        i += 1
-        while i < len(frame_files) and len(group) < args.batch:
-            nxt = load(frame_files[i])
-            if nxt.shape != first.shape:
-                break
-            group_files.append(frame_files[i])
-            group.append(nxt)
+    def batches():
+        """(files, stylized frames, their contents, the style of each) of every batch of consecutive same-sized frames, in order"""
+        i = 0
+        while i < len(frame_files):
+            first = load(frame_files[i])
+            group_files, group = [frame_files[i]], [first]
             i += 1
-        frames = np.stack(group)
-        if args.keep_colors:
-            # the style differs per frame (CORAL towards each frame): per-pair batch
-            from .ops import preserve_colors_np
-            styles = np.stack([preserve_colors_np(style_img, f, ctx=wct_model.sess) for f in group])
-            outs = wct_model.sess.stylize_batch(frames, styles, wct_model.relu_targets, alpha=args.alpha,
-                                                adain=args.adain, wct_mode=wct_model.wct_mode,
-                                                guided=guided if args.passes <= 1 else None)
-            for _ in range(args.passes - 1):
-                outs = wct_model.sess.stylize_batch(outs, styles, wct_model.relu_targets, alpha=args.alpha,
-                                                    adain=args.adain, wct_mode=wct_model.wct_mode)
-            if guided and args.passes > 1:
-                outs = guided_frames(wct_model, outs, frames, guided)
-            style_per_frame = list(styles)
-        else:
-            outs = run(frames, style_img, group_files)
-            style_per_frame = [style_img] * len(group)
+            while i < len(frame_files) and len(group) < args.batch:
+                nxt = load(frame_files[i])
+                if nxt.shape != first.shape:
+                    break
+                group_files.append(frame_files[i])
+                group.append(nxt)
+                i += 1
+            frames = np.stack(group)
+            if args.keep_colors:
+                # the style differs per frame (CORAL towards each frame): per-pair batch
+                from .ops import preserve_colors_np
+                styles = np.stack([preserve_colors_np(style_img, f, ctx=wct_model.sess) for f in group])
+                outs = wct_model.sess.stylize_batch(frames, styles, wct_model.relu_targets, alpha=args.alpha,
+                                                    adain=args.adain, wct_mode=wct_model.wct_mode,
+                                                    guided=guided if args.passes <= 1 else None)
+                for _ in range(args.passes - 1):
+                    outs = wct_model.sess.stylize_batch(outs, styles, wct_model.relu_targets, alpha=args.alpha,
+                                                        adain=args.adain, wct_mode=wct_model.wct_mode)
+                if guided and args.passes > 1:
+                    outs = guided_frames(wct_model, outs, frames, guided)
+                yield group_files, outs, frames, list(styles)
+            else:
+                outs, contents = run(frames, style_img, group_files)
+                yield group_files, outs, contents, [style_img] * len(group)
+
+    def smooth(plain, contents, f0, f1):
+        """frames f0 .. f1 - 1 of a resident clip: the filter along time, then the colour op"""
+        outs = wct_model.sess.guided_filter_time_range(plain, contents, guided[0], guided[1], frames_t, f0, f1)
+        return content_colors_frames(wct_model, outs, contents[f0:f1]) if colors else outs
+
+    for group_files, outs, _, style_per_frame in (smooth_clips(batches(), frames_t, smooth) if frames_t else batches()):
         for f, o, s in zip(group_files, outs, style_per_frame):
             if args.concat:                                   # stylize_video.py:129-132
                 o = np.hstack([_imresize(s, (o.shape[0], o.shape[0])), o])

@@ -421,8 +421,43 @@ class WCT(object):
             for h in own:
                 h.close()
 
+    @staticmethod
+    def _check_guided_frames(guided, guided_frames, swap5, wrap):
+        '''guided_frames of predict_frames, checked before any GPU call -> whether the frames take the temporal route'''
+        from .context import check_guided_time
+        if guided is None:
+            if guided_frames:
+                raise ValueError('guided_frames needs guided=(radius, eps_q): it extends that filter along time')
+            return False
+        t = check_guided_time(guided[0], guided[1], guided_frames)[2]
+        if t == 0:
+            return False
+        if len(guided) == 3 and guided[2] != 'grey':
+            raise ValueError("guided_frames goes with the grey guide: the 'color' guide has no form along time")
+        for name, on in (('swap5', swap5), ('wrap', wrap)):
+            if on:
+                raise ValueError('guided_frames is not served with %s' % name)
+        return True
+
+    def _predict_frames_smoothed(self, frames, style, guided, frames_t, content_colors, resize, kw):
+        '''predict_frames with guided_frames >= 1: the plain frames of the call, filtered along time as one clip against their
+        contents (the resized ones with resize=), then the colour op'''
+        if frames.ndim != 4 or frames.shape[3] != 3:
+            raise ValueError('expected [F][H][W][3] frames, got shape %s' % (frames.shape,))
+        if frames.dtype != np.uint8:
+            frames = np.uint8(np.clip(frames, 0, 255))
+        if resize is not None:
+            resize = check_resize(resize)                                         # ValueError before any GPU call
+        plain = self.predict_frames(frames, style, resize=resize, **kw)
+        contents = frames if resize is None else np.concatenate(
+            [self.sess.resize_batch(frames[i:i + 32], resize) for i in range(0, len(frames), 32)], axis=0)
+        out = self.sess.guided_filter_time_clip(plain, contents, guided[0], guided[1], frames_t)
+        if content_colors:
+            out = np.concatenate([self.sess.content_colors_batch(out[i:i + 32], contents[i:i + 32]) for i in range(0, len(out), 32)], axis=0)
+        return out
+
     def predict_frames(self, frames, style, alpha=1, swap5=False, ss_alpha=1, adain=False, batch=16, warm=None,
-                       content_colors=False, resize=None, wrap=False, strengths=None, guided=None):
+                       content_colors=False, resize=None, wrap=False, strengths=None, guided=None, guided_frames=0):
         '''Stylize same-sized frames [F][H][W][3] with ONE style image (the loop of stylize_video.py:112-121,
            which calls predict() once per frame and so re-runs the style encoder, the style statistics and the
            style eigendecompositions every frame).  Here the style side runs once per batch of `batch` frames;
@@ -437,9 +472,18 @@ class WCT(object):
            warm, content_colors or resize (ValueError before any GPU call).  Frames keep their size.
            strengths: a strength map per frame, uint8 [F][H][W] (or one [H][W] map for all frames), at the resized size with
            resize -- frame f equals predict(frames[f], style, strength=strengths[f]) bit for bit (cold).  A style image is prepared
-           once here; warm then needs a PreparedStyle as always.  No swap5 or wrap with it: ValueError.'''
+           once here; warm then needs a PreparedStyle as always.  No swap5 or wrap with it: ValueError.
+           guided_frames T (0 .. 3; needs guided=(radius, eps_q), the grey guide): temporal guided smoothing against flicker -- the
+           filter's box also covers the T frames on each side of a frame (ops.guided_filter_time_np).  0, the default, is the
+           per-frame filter fused into the batches.  With T >= 1 the batches run plain, then all frames of THIS call are filtered
+           as one clip against their (resized) contents, then the colour op if content_colors: the result equals
+           ops.guided_filter_time_np(predict_frames(frames, ...), contents, radius, eps_q, T), and content_colors_np after it, bit
+           for bit, whatever `batch` is.  The radius is at most 51 / 40 / 33 at T = 1 / 2 / 3.  No swap5 or wrap with it.'''
         guided = self._check_guided(guided)                                       # ValueError before any GPU call
         frames = np.asarray(frames)
+        if self._check_guided_frames(guided, guided_frames, swap5, wrap):
+            return self._predict_frames_smoothed(frames, style, guided, int(guided_frames), content_colors, resize,
+                                                 dict(alpha=alpha, adain=adain, batch=batch, warm=warm, strengths=strengths))
         if strengths is not None:
             from ._lib import strength_maps_frames
             if frames.ndim != 4 or frames.shape[3] != 3:
