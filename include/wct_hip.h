@@ -297,6 +297,42 @@ int wct_guided_filter_time(wct_ctx* ctx, const uint8_t* stylized, int Ho, int Wo
 int wct_guided_filter_time_batch_dev(wct_ctx* ctx, const uint8_t* stylized_dev, int Ho, int Wo, const uint8_t* content_dev, int Hc,
                                      int Wc, int F, int radius, int eps_q, int frames_t, int f0, int f1, uint8_t* out_dev);
 int wct_guided_time_max_radius(int frames_t);
+/* Temporal guided smoothing along camera motion: the filter above with one global integer translation per frame, so that a clip
+ * that pans is averaged along the motion, not across it (with equal windows a textured scene that moves looks like an edge
+ * everywhere along time).  The rule and its bounds: csrc/guided_motion_rule.h.
+ *   positions  pos [F][2] int32 (py, px), host memory; pos[0] is arbitrary, only differences are used.  The scene point at pixel
+ *              (y, x) of frame f is at pixel (y + pos[g][0] - pos[f][0], x + pos[g][1] - pos[f][1]) of frame g.  Every step
+ *              |pos[f + 1] - pos[f]| is at most 16 on both axes.
+ *   window     of (f, y, x): in each frame g of max(0, f - T) .. min(F - 1, f + T) the (2r + 1)^2 box centred at the shifted pixel
+ *              (y + Dy, x + Dx), cut at the image's borders; it may be empty.  ext(c, L, r) = max(0, min(L - 1, c + r) -
+ *              max(0, c - r) + 1);  n = sum over g of ext(y + Dy, H, r) ext(x + Dx, W, r)
+ *   pass 1:    SI, SII, Sp, SIp over that window; a_q, b_q of (f, y, x) by the formulas above with this n
+ *   pass 2:    out.ch(f, y, x) = clamp(rdiv(I(f, y, x) sum a_q + sum b_q, n 2^12), 0, 255), the sums over the same window
+ * Equal positions give wct_guided_filter_time_batch_dev's bytes.  The own frame gives n >= 1 and n <= (2r + 1)^2 (2T + 1): the
+ * parameters, the radius limits and the 2T halo of a longer video are those above.
+ * wct_guided_filter_motion: host pointers, blocking, the whole clip, F = 1 .. 32.
+ * wct_guided_filter_motion_batch_dev: device frames, host positions (read before the call returns), two launches, asynchronous on
+ *   the ctx stream; frames f0 .. f1 - 1 of THIS clip; out_dev may be stylized_dev + f0 Ho Wo 3.
+ * The estimator: for every pair of consecutive contents the step d = (dy, dx), |dy|, |dx| <= range, that minimises the mean absolute
+ * difference of the grey guides I (at content size) over the samples (y, x), both even, inside frame f with (y + dy, x + dx) inside
+ * frame f + 1:  SAD(d) = sum |I_f(y, x) - I_{f+1}(y + dy, x + dx)|, cnt(d) their number; d wins over d' when SAD(d) cnt(d') <
+ * SAD(d') cnt(d) (int64), and at equality the smaller (dy^2 + dx^2, dy, dx) wins: a flat or an unchanged pair gives (0, 0).
+ * pos[0] = (0, 0), pos[f + 1] = pos[f] + d_f.  range is 1 .. 16, Hc and Wc at least 4 range, Hc Wc <= 2^28.  A scene cut yields an
+ * arbitrary step, which the filter treats like any edge.
+ * wct_motion_global: host contents [F][Hc][Wc][3], blocking -> pos_out [F][2] int32, host memory.
+ * wct_motion_global_batch_dev: device contents; three launches on the ctx stream, then it BLOCKS on its 8 F byte result (pos_out
+ *   is host memory).  It uses the workspace of the guided ops: enqueue it before the filter of the same clip, not between its
+ *   passes (a ctx serves one stream, so this is the natural order).
+ * A null pointer, what wct_guided_filter_time refuses, a step above 16, a range outside 1 .. 16, Hc or Wc below 4 range or
+ * Hc Wc > 2^28 is WCT_STATUS_ARG with a message that names it, and leaves the ctx usable.
+ * Not served: per-block or dense motion, sub-pixel shifts, rotation and zoom, the colour guide along time. */
+int wct_motion_global(wct_ctx* ctx, const uint8_t* contents, int Hc, int Wc, int F, int range, int32_t* pos_out);
+int wct_motion_global_batch_dev(wct_ctx* ctx, const uint8_t* content_dev, int Hc, int Wc, int F, int range, int32_t* pos_out);
+int wct_guided_filter_motion(wct_ctx* ctx, const uint8_t* stylized, int Ho, int Wo, const uint8_t* content, int Hc, int Wc, int F,
+                             int radius, int eps_q, int frames_t, const int32_t* pos, uint8_t* out);
+int wct_guided_filter_motion_batch_dev(wct_ctx* ctx, const uint8_t* stylized_dev, int Ho, int Wo, const uint8_t* content_dev, int Hc,
+                                       int Wc, int F, int radius, int eps_q, int frames_t, const int32_t* pos, int f0, int f1,
+                                       uint8_t* out_dev);
 /* On-device resize (the reference's resize_to, utils.py:55-67, behind --content-size, stylize_video.py:29; webcam.py:163,189
  * resizes every frame by --scale): img [H][W][3] uint8 -> [h][w][3] uint8, the bytes of Pillow's Image.resize((w, h), Image.BILINEAR).
  * Pillow's 8-bit resampler is an integer rule.  Per axis (`in` the input length, `out` the output length; everything up to the

@@ -60,6 +60,11 @@ SIGNATURES = [
     ('wct_guided_filter_time_batch_dev', C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                                    C.c_int, C.c_int, _P]),
     ('wct_guided_time_max_radius', C.c_int, [C.c_int]),
+    ('wct_motion_global', C.c_int, [_P, _U8, C.c_int, C.c_int, C.c_int, C.c_int, _I]),
+    ('wct_motion_global_batch_dev', C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _I]),
+    ('wct_guided_filter_motion', C.c_int, [_P, _U8, C.c_int, C.c_int, _U8, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _I, _U8]),
+    ('wct_guided_filter_motion_batch_dev', C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                     _I, C.c_int, C.c_int, _P]),
     ('wct_resize', C.c_int, [_P, _U8, C.c_int, C.c_int, C.c_int, C.c_int, _U8]),
     ('wct_resize_batch_dev', C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     ('wct_output_size', C.c_int, [C.c_int, C.c_int, _I, C.c_int, _I, _I]),
@@ -150,6 +155,9 @@ GUIDES = {'grey': GUIDE_GREY, 'color': GUIDE_COLOR}
 # temporal guided smoothing (csrc/guided_time_rule.h): the largest radius at T = 0 .. 3 frames on each side, from
 # (2r + 1)^2 (2T + 1) <= 33025; wct_guided_time_max_radius(T) returns the same numbers
 GUIDED_TIME_MAX_RADIUS = (64, 51, 40, 33)
+# temporal guided smoothing along motion (csrc/guided_motion_rule.h): the largest step between two frames and the largest search
+# range of the estimator, and the pixels of a content frame it takes
+MOTION_MAX_RANGE, MOTION_MAX_PIXELS = 16, 1 << 28
 
 
 def guided_eps_q(eps):

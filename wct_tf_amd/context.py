@@ -105,6 +105,47 @@ def check_guided_time(radius, eps_q, frames_t):
     return r, e, t
 
 
+def check_guided_motion(positions, frames):
+    """The refusals of positions= of temporal guided smoothing along motion, before any library call: an integer array
+    [frames][2] of (py, px) whose steps between consecutive frames are within _lib.MOTION_MAX_RANGE on both axes
+    -> contiguous int32 [frames][2]"""
+    try:
+        p = np.asarray(positions)
+    except Exception:
+        raise ValueError('positions is an integer array [frames][2] of (py, px), got %r' % (positions,))
+    if not np.issubdtype(p.dtype, np.integer):
+        raise ValueError('positions is an integer array [frames][2] of (py, px), got dtype %s' % p.dtype)
+    if p.ndim != 2 or p.shape != (int(frames), 2):
+        raise ValueError('positions is [frames][2], one (py, px) per frame: expected (%d, 2), got %s' % (frames, p.shape))
+    p = p.astype(np.int64)
+    if np.abs(p).max() >= 1 << 30:
+        raise ValueError('positions must be below 2^30 in size')
+    step = np.abs(np.diff(p, axis=0))
+    if step.size and step.max() > _lib.MOTION_MAX_RANGE:
+        f = int(np.argmax(step.max(1) > _lib.MOTION_MAX_RANGE))
+        raise ValueError('positions: the step from frame %d to %d is %s, must be within %d on both axes'
+                         % (f, f + 1, tuple(int(v) for v in p[f + 1] - p[f]), _lib.MOTION_MAX_RANGE))
+    return np.ascontiguousarray(p, np.int32)
+
+
+def check_motion_search(search, hc, wc):
+    """The refusals of the estimator's search range, before any library call: an integer 1 .. 16, both sides of the content at
+    least 4 search, at most 2^28 pixels -> search"""
+    try:
+        if int(search) != search:
+            raise TypeError
+        r = int(search)
+    except (TypeError, ValueError):
+        raise ValueError('the motion search range is an integer 1 .. %d, got %r' % (_lib.MOTION_MAX_RANGE, search))
+    if not 1 <= r <= _lib.MOTION_MAX_RANGE:
+        raise ValueError('the motion search range must be 1 .. %d, got %d' % (_lib.MOTION_MAX_RANGE, r))
+    if hc < 4 * r or wc < 4 * r:
+        raise ValueError('a motion search range of %d needs contents of at least %d x %d, got %d x %d' % (r, 4 * r, 4 * r, hc, wc))
+    if hc * wc > _lib.MOTION_MAX_PIXELS:
+        raise ValueError('motion estimation takes contents of at most 2^28 pixels, got %d x %d' % (hc, wc))
+    return r
+
+
 def _guided_clip(stylized, contents):
     """The refusals of a clip and its contents, before any library call -> both as contiguous uint8 [F][..][..][3], F >= 1"""
     try:
@@ -877,17 +918,25 @@ class Context(object):
             ds, s.shape[1], s.shape[2], dc, c.shape[1], c.shape[2], s.shape[0], r, e, ds, guide=guide))
 
     # ---- temporal guided smoothing: the filter's box across frames --------------------------
-    def guided_filter_time(self, stylized_u8, contents_u8, radius, eps_q, frames_t):
+    def guided_filter_time(self, stylized_u8, contents_u8, radius, eps_q, frames_t, positions=None):
         """Temporal guided smoothing of a clip (wct_guided_filter_time): stylized [F][Ho][Wo][3] and contents [F][Hc][Wc][3] uint8,
         F <= 32 -> uint8 [F][Ho][Wo][3], the grey-guide filter of guided_filter with its box extended over the frames_t (0 .. 3)
         frames on each side of a frame, cut at the clip's ends.  frames_t = 0 is guided_filter_batch.  The radius is at most
-        64 / 51 / 40 / 33 at frames_t 0 / 1 / 2 / 3.  A longer clip: ops.guided_filter_time_np."""
+        64 / 51 / 40 / 33 at frames_t 0 / 1 / 2 / 3.  A longer clip: ops.guided_filter_time_np.
+        positions: int [F][2] (py, px), one global translation per frame (motion_global estimates them) -- the window in every
+        neighbouring frame is shifted by the difference of the positions (wct_guided_filter_motion); None: no shift."""
         s, c = _guided_clip(stylized_u8, contents_u8)
         r, e, t = check_guided_time(radius, eps_q, frames_t)
+        pos = None if positions is None else check_guided_motion(positions, s.shape[0])
         if not 1 <= s.shape[0] <= _lib.BATCH_MAX:
             raise ValueError('a clip takes 1 .. %d frames in one call, got %d (ops.guided_filter_time_np takes any length)'
                              % (_lib.BATCH_MAX, s.shape[0]))
         out = np.empty_like(s)
+        if pos is not None:
+            check(self.lib.wct_guided_filter_motion(self.h, s.ctypes.data_as(_lib._U8), s.shape[1], s.shape[2], c.ctypes.data_as(_lib._U8),
+                                                    c.shape[1], c.shape[2], s.shape[0], r, e, t, pos.ctypes.data_as(_lib._I),
+                                                    out.ctypes.data_as(_lib._U8)))
+            return out
         check(self.lib.wct_guided_filter_time(self.h, s.ctypes.data_as(_lib._U8), s.shape[1], s.shape[2], c.ctypes.data_as(_lib._U8),
                                               c.shape[1], c.shape[2], s.shape[0], r, e, t, out.ctypes.data_as(_lib._U8)))
         return out
@@ -903,33 +952,82 @@ class Context(object):
         check(self.lib.wct_guided_filter_time_batch_dev(self.h, stylized_dev, int(ho), int(wo), content_dev, int(hc), int(wc), int(frames),
                                                         r, e, t, int(f0), int(f1), out_dev))
 
+    def guided_filter_motion_batch_dev(self, stylized_dev, ho, wo, content_dev, hc, wc, frames, radius, eps_q, frames_t, positions, f0, f1,
+                                       out_dev):
+        """guided_filter_time_batch_dev with positions int [frames][2] (host): the window of every neighbouring frame shifted by
+        the difference of the positions (wct_guided_filter_motion_batch_dev).  Asynchronous; the same aliasing and halo."""
+        r, e, t = check_guided_time(radius, eps_q, frames_t)
+        if not (1 <= int(frames) <= _lib.BATCH_MAX and 0 <= int(f0) < int(f1) <= int(frames)):
+            raise ValueError('a clip takes 1 .. %d frames and a range 0 <= f0 < f1 <= frames, got %d frames and [%d, %d)'
+                             % (_lib.BATCH_MAX, frames, f0, f1))
+        pos = check_guided_motion(positions, frames)
+        check(self.lib.wct_guided_filter_motion_batch_dev(self.h, stylized_dev, int(ho), int(wo), content_dev, int(hc), int(wc), int(frames),
+                                                          r, e, t, pos.ctypes.data_as(_lib._I), int(f0), int(f1), out_dev))
+
+    def motion_global_batch_dev(self, content_dev, hc, wc, frames, search=8):
+        """The positions of `frames` contents resident in HBM (wct_motion_global_batch_dev) -> int32 [frames][2]: three launches,
+        then it blocks on the result."""
+        r = check_motion_search(search, int(hc), int(wc))
+        if not 1 <= int(frames) <= _lib.BATCH_MAX:
+            raise ValueError('motion estimation takes 1 .. %d frames in one call, got %d' % (_lib.BATCH_MAX, frames))
+        pos = np.zeros((int(frames), 2), np.int32)
+        check(self.lib.wct_motion_global_batch_dev(self.h, content_dev, int(hc), int(wc), int(frames), r, pos.ctypes.data_as(_lib._I)))
+        return pos
+
+    def motion_global(self, contents_u8, search=8):
+        """One global integer translation per frame of a clip, from its contents [F][Hc][Wc][3] uint8 of any F (wct_motion_global):
+        for every pair of consecutive frames the step (dy, dx), |dy|, |dx| <= search, with the smallest mean absolute difference of
+        the grey guides over the even pixels (ties: the smallest step), summed up from (0, 0) -> int32 [F][2], what positions= of
+        guided_filter_time takes.  A longer clip goes in chunks of 32 frames that share one frame.  A scene cut yields an
+        arbitrary step."""
+        c = np.ascontiguousarray(contents_u8)
+        if c.dtype != np.uint8 or c.ndim != 4 or c.shape[3] != 3 or c.shape[0] < 1:
+            raise ValueError('motion_global takes uint8 contents [F][H][W][3], got %s %s' % (c.dtype, c.shape))
+        r = check_motion_search(search, c.shape[1], c.shape[2])
+        pos = np.zeros((c.shape[0], 2), np.int32)
+        for f0 in range(0, max(1, c.shape[0] - 1), _lib.BATCH_MAX - 1):
+            part = np.ascontiguousarray(c[f0:f0 + _lib.BATCH_MAX])
+            got = np.zeros((part.shape[0], 2), np.int32)
+            check(self.lib.wct_motion_global(self.h, part.ctypes.data_as(_lib._U8), c.shape[1], c.shape[2], part.shape[0], r,
+                                             got.ctypes.data_as(_lib._I)))
+            pos[f0:f0 + part.shape[0]] = got + pos[f0]
+        return pos
+
     def guided_time_max_radius(self, frames_t):
         """The largest radius of temporal guided smoothing with frames_t frames on each side (wct_guided_time_max_radius): the
         entries of _lib.GUIDED_TIME_MAX_RADIUS; 0 for a frames_t outside 0 .. 3"""
         return int(self.lib.wct_guided_time_max_radius(int(frames_t)))
 
-    def guided_filter_time_clip(self, stylized_u8, contents_u8, radius, eps_q, frames_t):
+    def guided_filter_time_clip(self, stylized_u8, contents_u8, radius, eps_q, frames_t, positions=None):
         """guided_filter_time for a clip of any length: chunks of at most 32 - 4 frames_t output frames, each uploaded with
         2 frames_t frames of halo on each side (fewer at the clip's ends) and filtered as a clip of its own -- the whole clip's
-        bytes, since a frame depends on no frame further than 2 frames_t away."""
+        bytes, since a frame depends on no frame further than 2 frames_t away.  positions [F][2]: sliced with every chunk (only
+        their differences count)."""
         s, c = _guided_clip(stylized_u8, contents_u8)
         r, e, t = check_guided_time(radius, eps_q, frames_t)
+        pos = None if positions is None else check_guided_motion(positions, s.shape[0])
         n, step, out = s.shape[0], _lib.BATCH_MAX - 4 * t, np.empty_like(s)
         for f0 in range(0, n, step):
             f1 = min(n, f0 + step)
             g0, g1 = max(0, f0 - 2 * t), min(n, f1 + 2 * t)
-            self.guided_filter_time_range(s[g0:g1], c[g0:g1], r, e, t, f0 - g0, f1 - g0, out=out[f0:f1])
+            self.guided_filter_time_range(s[g0:g1], c[g0:g1], r, e, t, f0 - g0, f1 - g0, out=out[f0:f1],
+                                          positions=None if pos is None else pos[g0:g1])
         return out
 
-    def guided_filter_time_range(self, stylized_u8, contents_u8, radius, eps_q, frames_t, f0, f1, out=None):
+    def guided_filter_time_range(self, stylized_u8, contents_u8, radius, eps_q, frames_t, f0, f1, out=None, positions=None):
         """Host arrays in, host array out: frames f0 .. f1 - 1 of the clip stylized [F][Ho][Wo][3] with contents [F][Hc][Wc][3]
-        (F <= 32), filtered along time as guided_filter_time_batch_dev does -> uint8 [f1 - f0][Ho][Wo][3]"""
+        (F <= 32), filtered along time as guided_filter_time_batch_dev does (with positions [F][2]: as
+        guided_filter_motion_batch_dev does) -> uint8 [f1 - f0][Ho][Wo][3]"""
         s, c = _guided_clip(stylized_u8, contents_u8)
         r, e, t = check_guided_time(radius, eps_q, frames_t)
+        pos = None if positions is None else check_guided_motion(positions, s.shape[0])
         if not (1 <= s.shape[0] <= _lib.BATCH_MAX and 0 <= f0 < f1 <= s.shape[0]):
             raise ValueError('a clip takes 1 .. %d frames and a range 0 <= f0 < f1 <= frames, got %d frames and [%d, %d)'
                              % (_lib.BATCH_MAX, s.shape[0], f0, f1))
         out = np.empty((f1 - f0,) + s.shape[1:], np.uint8) if out is None else out
+        if pos is not None:
+            return self._host_batch([s, c], out, enqueue=lambda ds, dc, do: self.guided_filter_motion_batch_dev(
+                ds, s.shape[1], s.shape[2], dc, c.shape[1], c.shape[2], s.shape[0], r, e, t, pos, f0, f1, do))
         return self._host_batch([s, c], out, enqueue=lambda ds, dc, do: self.guided_filter_time_batch_dev(
             ds, s.shape[1], s.shape[2], dc, c.shape[1], c.shape[2], s.shape[0], r, e, t, f0, f1, do))
 

@@ -779,6 +779,69 @@ extern "C" int wct_guided_filter_time(wct_ctx* c, const uint8_t* stylized, int H
 
 extern "C" int wct_guided_time_max_radius(int frames_t) { return guided_time_max_radius(frames_t); }
 
+// Temporal guided smoothing along camera motion, op level (csrc/guided_motion.hip).  The estimator: the guide planes, the partial
+// sums and the steps live in the workspace of the guided ops, which the filter only uses afterwards on the same stream
+extern "C" int wct_motion_global_batch_dev(wct_ctx* c, const uint8_t* content, int Hc, int Wc, int F, int range, int32_t* pos_out) {
+  ARG_CHECK(c != nullptr);
+  if (!content || !pos_out) { wct_set_error("global motion: null pointer"); return WCT_ERR_ARG; }
+  TRY(motion_check(F, Hc, Wc, range));
+  HIP_TRY(hipSetDevice(c->device));
+  TRY(ensure(c, c->guided_ab, motion_workspace_bytes(F, Hc, Wc, range)));
+  const int32_t* steps_dev = nullptr;
+  int32_t steps[31 * 2];
+  {
+    // per pair: (2 range + 1)^2 candidates of Hc Wc / 4 byte differences; the planes written once and read once per candidate row
+    const double cand = (2.0 * range + 1) * (2.0 * range + 1);
+    ProfScope ps(c, 7, 0, (double)F * Hc * Wc * 4 + (double)(F - 1) * cand * Hc * Wc * 0.5);
+    TRY(launch_motion_global(content, F, Hc, Wc, range, c->guided_ab.p, &steps_dev, c->stream));
+  }
+  if (F > 1) TRY(fetch(c, steps, steps_dev, (size_t)(F - 1) * 8));
+  pos_out[0] = pos_out[1] = 0;
+  for (int f = 0; f + 1 < F; ++f) {
+    pos_out[2 * f + 2] = pos_out[2 * f] + steps[2 * f];
+    pos_out[2 * f + 3] = pos_out[2 * f + 1] + steps[2 * f + 1];
+  }
+  return WCT_OK;
+}
+
+extern "C" int wct_motion_global(wct_ctx* c, const uint8_t* contents, int Hc, int Wc, int F, int range, int32_t* pos_out) {
+  ARG_CHECK(c != nullptr);
+  if (!contents || !pos_out) { wct_set_error("global motion: null pointer"); return WCT_ERR_ARG; }
+  TRY(motion_check(F, Hc, Wc, range));                                                        // (before the staging buffer is sized)
+  HIP_TRY(hipSetDevice(c->device));
+  void* dc;
+  TRY(stage_in(c, 1, contents, (size_t)F * Hc * Wc * 3, &dc));
+  return wct_motion_global_batch_dev(c, (const uint8_t*)dc, Hc, Wc, F, range, pos_out);
+}
+
+extern "C" int wct_guided_filter_motion_batch_dev(wct_ctx* c, const uint8_t* stylized, int Ho, int Wo, const uint8_t* content, int Hc,
+                                                  int Wc, int F, int radius, int eps_q, int frames_t, const int32_t* pos, int f0, int f1,
+                                                  uint8_t* out) {
+  ARG_CHECK(c != nullptr);
+  if (!stylized || !content || !out) { wct_set_error("guided filter along motion: null image pointer"); return WCT_ERR_ARG; }
+  TRY(guided_motion_check(F, Ho, Wo, Hc, Wc, radius, eps_q, frames_t, f0, f1, pos));
+  HIP_TRY(hipSetDevice(c->device));
+  TRY(ensure(c, c->guided_ab, guided_workspace_bytes(F, Ho, Wo, GUIDE_GREY)));
+  // the traffic of wct_guided_filter_time_batch_dev: the same loads, shifted
+  const int n1 = (f1 + frames_t > F ? F : f1 + frames_t) - (f0 - frames_t < 0 ? 0 : f0 - frames_t), n2 = f1 - f0, win = 2 * frames_t + 1;
+  ProfScope ps(c, 7, 0, (double)Ho * Wo * (n1 * (win * 2 * 6 + 24.0) + n2 * (win * 2 * 24.0 + 3 + 3)));
+  return launch_guided_motion(stylized, content, F, Ho, Wo, Hc, Wc, radius, eps_q, frames_t, pos, f0, f1, c->guided_ab.p, out, c->stream);
+}
+
+extern "C" int wct_guided_filter_motion(wct_ctx* c, const uint8_t* stylized, int Ho, int Wo, const uint8_t* content, int Hc, int Wc, int F,
+                                        int radius, int eps_q, int frames_t, const int32_t* pos, uint8_t* out) {
+  ARG_CHECK(c != nullptr);
+  if (!stylized || !content || !out) { wct_set_error("guided filter along motion: null image pointer"); return WCT_ERR_ARG; }
+  TRY(guided_motion_check(F, Ho, Wo, Hc, Wc, radius, eps_q, frames_t, 0, F, pos));            // (before the staging buffers are sized)
+  HIP_TRY(hipSetDevice(c->device));
+  void *ds, *dc;
+  TRY(stage_in(c, 0, stylized, (size_t)F * Ho * Wo * 3, &ds));
+  TRY(stage_in(c, 1, content, (size_t)F * Hc * Wc * 3, &dc));
+  TRY(wct_guided_filter_motion_batch_dev(c, (uint8_t*)ds, Ho, Wo, (uint8_t*)dc, Hc, Wc, F, radius, eps_q, frames_t, pos, 0, F,
+                                         (uint8_t*)ds));
+  return fetch(c, out, ds, (size_t)F * Ho * Wo * 3);
+}
+
 // Seeded noise images for texture synthesis, op level (csrc/noise.hip): the refusals both calls share
 static int texture_noise_checks(int H, int W, int B, const void* out) {
   if (!out) { wct_set_error("texture noise: null output pointer"); return WCT_ERR_ARG; }

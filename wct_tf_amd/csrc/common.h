@@ -383,6 +383,21 @@ int guided_time_check(int F, int Ho, int Wo, int Hc, int Wc, int radius, int eps
 int guided_time_max_radius(int frames_t);                  // 64 / 51 / 40 / 33 at 0 .. 3 frames on each side, else 0
 int launch_guided_time(const uint8_t* stylized, const void* content, int content_f32, int F, int Ho, int Wo, int Hc, int Wc, int radius,
                        int eps_q, int frames_t, int f0, int f1, void* workspace, uint8_t* out, hipStream_t s);
+// ---- guided_motion.hip ----------------------------------------------------
+// Temporal guided smoothing along camera motion (guided_motion_rule.h): launch_guided_time with the window of every neighbouring
+// frame shifted by the difference of the positions pos [F][2] (py, px), host memory, read before the call returns.  Same clip,
+// range, workspace and aliasing.  guided_motion_check: what guided_time_check refuses, a null pos, or a step between two frames
+// above 16 on either axis.
+int guided_motion_check(int F, int Ho, int Wo, int Hc, int Wc, int radius, int eps_q, int frames_t, int f0, int f1, const int32_t* pos);
+int launch_guided_motion(const uint8_t* stylized, const uint8_t* content, int F, int Ho, int Wo, int Hc, int Wc, int radius, int eps_q,
+                         int frames_t, const int32_t* pos, int f0, int f1, void* workspace, uint8_t* out, hipStream_t s);
+// The estimator of those positions: one step per pair of consecutive contents [F][Hc][Wc][3] on the device, by exhaustive search
+// over |dy|, |dx| <= range.  Three launches (none for F = 1); *steps = where in the workspace the F - 1 steps (dy, dx) int32 will
+// be.  workspace: motion_workspace_bytes bytes.  motion_check: F outside 1 .. 32, a range outside 1 .. 16, Hc or Wc < 4 range, or
+// Hc * Wc > 2^28.
+int motion_check(int F, int Hc, int Wc, int range);
+size_t motion_workspace_bytes(int F, int Hc, int Wc, int range);
+int launch_motion_global(const uint8_t* content, int F, int Hc, int Wc, int range, void* workspace, const int32_t** steps, hipStream_t s);
 
 // ---- noise.hip ------------------------------------------------------------
 // Seeded noise for texture synthesis (noise_rule.h): out [B][H][W][3] uint8 on the device, image b = sample first_sample + b of

@@ -9,6 +9,7 @@ on libwct_hip.so.  Same names, argument meaning and array conventions:
 and, without a counterpart in the reference,
   content_colors_np(stylized_rgb, content_rgb)  luminance-only colour preservation (Gatys et al. 2016), applied to a result
   guided_filter_np(stylized_rgb, content_rgb, radius, eps_q, guide)   guided smoothing of a result with its content as guide (He et al.)
+  motion_global_np(contents, search)   one global integer translation per frame of a clip, for guided_filter_time_np(positions=)
   texture_noise_np(h, w, seed, sample=0, smooth=False)   the seeded noise image a texture starts from (webcam.py:191-192 --noise)
 """
 import numpy as np
@@ -134,16 +135,29 @@ def guided_filter_np(stylized, content, radius, eps_q, guide='grey', ctx=None):
     return ctx.guided_filter(stylized, content, radius, eps_q, guide=guide)
 
 
-def guided_filter_time_np(stylized, contents, radius, eps_q, frames_t, ctx=None):
+def guided_filter_time_np(stylized, contents, radius, eps_q, frames_t, ctx=None, positions=None):
     """Temporal guided smoothing of a stylized clip, against the flicker of frames that were stylized one by one: uint8
     [F][Ho][Wo][3] frames and [F][Hc][Wc][3] contents of any F -> uint8 [F][Ho][Wo][3], guided_filter_np's grey-guide filter with
     its box extended over the frames_t (0 .. 3) frames on each side of a frame and cut at the clip's ends (the integer rule of
     include/wct_hip.h, wct_guided_filter_time).  Where the content stands still the frames are averaged along time; where it
-    moves the result follows the content.  No motion compensation: a flat region that pans is averaged too.  radius 1 ..
-    64 / 51 / 40 / 33 at frames_t 0 / 1 / 2 / 3.  A clip of more than 32 frames goes in chunks of 32 - 4 frames_t frames with
-    halos of 2 frames_t and gives the whole clip's bytes."""
+    moves the result follows the content.  Without positions there is no motion compensation: a flat region that pans is averaged
+    too.  radius 1 .. 64 / 51 / 40 / 33 at frames_t 0 / 1 / 2 / 3.  A clip of more than 32 frames goes in chunks of 32 - 4 frames_t
+    frames with halos of 2 frames_t and gives the whole clip's bytes.
+    positions: int [F][2] (py, px), one global translation per frame, as motion_global_np estimates them: the window in every
+    neighbouring frame is shifted by the difference of the positions (wct_guided_filter_motion), so a clip that pans is averaged
+    along its motion.  Steps between consecutive frames of at most 16 on both axes."""
     ctx = ctx or default_context()
-    return ctx.guided_filter_time_clip(stylized, contents, radius, eps_q, frames_t)
+    return ctx.guided_filter_time_clip(stylized, contents, radius, eps_q, frames_t, positions=positions)
+
+
+def motion_global_np(contents, search=8, ctx=None):
+    """One global integer translation per frame of a clip (wct_motion_global): uint8 [F][Hc][Wc][3] contents of any F -> int32
+    [F][2] positions (py, px) from (0, 0), the sum of the steps between consecutive frames.  A step is the (dy, dx), |dy|, |dx| <=
+    search (1 .. 16), with the smallest mean absolute difference of the grey guides over the even pixels, by exhaustive search; at
+    equality the smallest step.  Both sides of a frame at least 4 search.  Not served: per-block or dense motion, sub-pixel
+    shifts, rotation and zoom."""
+    ctx = ctx or default_context()
+    return ctx.motion_global(contents, search)
 
 
 def texture_noise_np(h, w, seed, sample=0, smooth=False, ctx=None):

@@ -22,6 +22,9 @@ MI355X path.  Same flags.  Differences, all forced by the environment or by the 
   moves the result follows the input.  No motion compensation.  A clip is a run of consecutive frames of one size; every frame
   equals the whole-clip filter on the plain frames of its clip whatever `--batch` is (a sliding buffer of at most 32 + `--batch`
   frames, never the whole video).  Grey guide only; not with `--swap5`, `--keep-colors` or `--mask-path`.
+* `--guided-motion global [--guided-motion-range R]` (with `--guided-frames`) runs that filter along camera motion: one global
+  integer translation per frame, estimated from the input frames, shifts the window in every neighbouring frame, so a pan or a
+  handheld shot is averaged along its motion, not across it.  Frames still do not depend on `--batch`.
 * `--device-resize` (opt-in) applies `--content-size` on the device: the frames go up raw and are resized there, on the stream
   of the call that stylizes them, to the bytes Pillow's bilinear resize gives on the host -- the same frames come out.
 """
@@ -72,6 +75,15 @@ _FLAGS = [
                                      'on each side of a frame (0 .. 3; 0: off), within every run of consecutive frames of one size. '
                                      'The radius is then at most 51 / 40 / 33 at T = 1 / 2 / 3.  Grey guide only; not with --swap5, '
                                      '--keep-colors or --mask-path')),
+    (('--guided-motion',), dict(choices=['global'], default=None,
+                                help='run --guided-frames along camera motion: global estimates one integer translation per frame '
+                                     'from the input frames (exhaustive search, steps within --guided-motion-range) and shifts the '
+                                     'window in every neighbouring frame by it.  A scene cut yields an arbitrary shift, which the '
+                                     'filter treats like any edge.  Needs --guided-frames >= 1.  Per-block or dense motion, sub-pixel '
+                                     'shifts, rotation and zoom are not served')),
+    (('--guided-motion-range',), dict(type=int, default=None, metavar='R',
+                                      help='the search range of --guided-motion in pixels per frame (1 .. 16; default 8); both sides of '
+                                           'a frame must be at least 4 R')),
     (('--style-size',), dict(type=int, default=0, help='short side of the style image (0: as is)')),
     (('--crop-size',), dict(type=int, default=0, help='centre-crop the style image to a square of this side (0: no)')),
     (('--content-size',), dict(type=int, default=0, help='short side of every frame (0: as is)')),
@@ -197,6 +209,15 @@ def check_guided_frames_args(parser, args):
     t = getattr(args, 'guided_frames', 0)
     if not 0 <= t < len(GUIDED_TIME_MAX_RADIUS):
         parser.error('--guided-frames must be 0 (off) .. %d frames on each side, got %d' % (len(GUIDED_TIME_MAX_RADIUS) - 1, t))
+    motion, search = getattr(args, 'guided_motion', None), getattr(args, 'guided_motion_range', None)
+    if motion is not None and not t:
+        parser.error('--guided-motion needs --guided-frames >= 1 (it shifts the windows of that filter along time)')
+    if search is not None:
+        from ._lib import MOTION_MAX_RANGE
+        if motion is None or not t:
+            parser.error('--guided-motion-range needs --guided-motion with --guided-frames >= 1')
+        if not 1 <= search <= MOTION_MAX_RANGE:
+            parser.error('--guided-motion-range must be 1 .. %d, got %d' % (MOTION_MAX_RANGE, search))
     if not t:
         return
     if not args.guided_radius:
@@ -438,7 +459,10 @@ def stylize_frames(wct_model, frame_files, style_img, args, alpha_files=None):
 
     def smooth(plain, contents, f0, f1):
         """frames f0 .. f1 - 1 of a resident clip: the filter along time, then the colour op"""
-        outs = wct_model.sess.guided_filter_time_range(plain, contents, guided[0], guided[1], frames_t, f0, f1)
+        positions = None
+        if getattr(args, 'guided_motion', None) == 'global':  # the pairs of the resident clip: halo pairs come out the same again
+            positions = wct_model.sess.motion_global(contents, getattr(args, 'guided_motion_range', None) or 8)
+        outs = wct_model.sess.guided_filter_time_range(plain, contents, guided[0], guided[1], frames_t, f0, f1, positions=positions)
         return content_colors_frames(wct_model, outs, contents[f0:f1]) if colors else outs
 
     for group_files, outs, _, style_per_frame in (smooth_clips(batches(), frames_t, smooth) if frames_t else batches()):

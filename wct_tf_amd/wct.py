@@ -439,9 +439,30 @@ class WCT(object):
                 raise ValueError('guided_frames is not served with %s' % name)
         return True
 
-    def _predict_frames_smoothed(self, frames, style, guided, frames_t, content_colors, resize, kw):
+    @staticmethod
+    def _check_guided_motion(guided_motion, temporal, frames, resize):
+        """guided_motion of predict_frames, checked before any GPU call -> None, ('global', R) or int32 positions [N][2]"""
+        from .context import check_guided_motion, check_motion_search
+        if guided_motion is None:
+            return None
+        if not temporal:
+            raise ValueError('guided_motion needs guided_frames >= 1: it shifts the windows of that filter along time')
+        shape = np.shape(frames)
+        if len(shape) != 4 or shape[3] != 3:
+            raise ValueError('expected [F][H][W][3] frames, got shape %s' % (shape,))
+        if isinstance(guided_motion, str) or (isinstance(guided_motion, tuple) and len(guided_motion) == 2 and isinstance(guided_motion[0], str)):
+            name, search = (guided_motion, 8) if isinstance(guided_motion, str) else guided_motion
+            if name != 'global':
+                raise ValueError("guided_motion is None, 'global', ('global', R) or an int array [N][2] of positions, got %r: per-block or "
+                                 "dense motion, sub-pixel shifts, rotation and zoom are not served" % (guided_motion,))
+            h, w = check_resize(resize) if resize is not None else shape[1:3]
+            return ('global', check_motion_search(search, h, w))
+        return check_guided_motion(guided_motion, shape[0])
+
+    def _predict_frames_smoothed(self, frames, style, guided, frames_t, content_colors, resize, kw, motion=None):
         '''predict_frames with guided_frames >= 1: the plain frames of the call, filtered along time as one clip against their
-        contents (the resized ones with resize=), then the colour op'''
+        contents (the resized ones with resize=), then the colour op.  motion: None, ('global', R) -- the positions are estimated
+        from those contents -- or positions [N][2]'''
         if frames.ndim != 4 or frames.shape[3] != 3:
             raise ValueError('expected [F][H][W][3] frames, got shape %s' % (frames.shape,))
         if frames.dtype != np.uint8:
@@ -451,13 +472,14 @@ class WCT(object):
         plain = self.predict_frames(frames, style, resize=resize, **kw)
         contents = frames if resize is None else np.concatenate(
             [self.sess.resize_batch(frames[i:i + 32], resize) for i in range(0, len(frames), 32)], axis=0)
-        out = self.sess.guided_filter_time_clip(plain, contents, guided[0], guided[1], frames_t)
+        positions = self.sess.motion_global(contents, motion[1]) if isinstance(motion, tuple) else motion
+        out = self.sess.guided_filter_time_clip(plain, contents, guided[0], guided[1], frames_t, positions=positions)
         if content_colors:
             out = np.concatenate([self.sess.content_colors_batch(out[i:i + 32], contents[i:i + 32]) for i in range(0, len(out), 32)], axis=0)
         return out
 
     def predict_frames(self, frames, style, alpha=1, swap5=False, ss_alpha=1, adain=False, batch=16, warm=None,
-                       content_colors=False, resize=None, wrap=False, strengths=None, guided=None, guided_frames=0):
+                       content_colors=False, resize=None, wrap=False, strengths=None, guided=None, guided_frames=0, guided_motion=None):
         '''Stylize same-sized frames [F][H][W][3] with ONE style image (the loop of stylize_video.py:112-121,
            which calls predict() once per frame and so re-runs the style encoder, the style statistics and the
            style eigendecompositions every frame).  Here the style side runs once per batch of `batch` frames;
@@ -478,12 +500,22 @@ class WCT(object):
            per-frame filter fused into the batches.  With T >= 1 the batches run plain, then all frames of THIS call are filtered
            as one clip against their (resized) contents, then the colour op if content_colors: the result equals
            ops.guided_filter_time_np(predict_frames(frames, ...), contents, radius, eps_q, T), and content_colors_np after it, bit
-           for bit, whatever `batch` is.  The radius is at most 51 / 40 / 33 at T = 1 / 2 / 3.  No swap5 or wrap with it.'''
+           for bit, whatever `batch` is.  The radius is at most 51 / 40 / 33 at T = 1 / 2 / 3.  No swap5 or wrap with it.
+           guided_motion (needs guided_frames >= 1): the temporal filter along camera motion -- one global integer translation per
+           frame shifts the window in every neighbouring frame, so a clip that pans is averaged along its motion.  None, the
+           default: no shift.  'global' or ('global', R): the positions are estimated from the contents the filter guides with
+           (the resized ones with resize=; Context.motion_global, search range R = 8 by default, 1 .. 16).  An int array [F][2] of
+           (py, px): the caller's positions, steps of at most 16.  The result equals ops.guided_filter_time_np(plain frames,
+           contents, radius, eps_q, T, positions=ops.motion_global_np(contents, R)) bit for bit, whatever `batch` is.  A scene cut
+           yields an arbitrary step, which the filter treats like any edge.  Per-block or dense motion, sub-pixel shifts, rotation
+           and zoom are not served.'''
         guided = self._check_guided(guided)                                       # ValueError before any GPU call
         frames = np.asarray(frames)
-        if self._check_guided_frames(guided, guided_frames, swap5, wrap):
+        temporal = self._check_guided_frames(guided, guided_frames, swap5, wrap)
+        motion = self._check_guided_motion(guided_motion, temporal, frames, resize)
+        if temporal:
             return self._predict_frames_smoothed(frames, style, guided, int(guided_frames), content_colors, resize,
-                                                 dict(alpha=alpha, adain=adain, batch=batch, warm=warm, strengths=strengths))
+                                                 dict(alpha=alpha, adain=adain, batch=batch, warm=warm, strengths=strengths), motion)
         if strengths is not None:
             from ._lib import strength_maps_frames
             if frames.ndim != 4 or frames.shape[3] != 3:
