@@ -258,7 +258,8 @@ int wct_content_colors_batch_dev(wct_ctx* ctx, const uint8_t* stylized_dev, int 
  *   WCT_GUIDE_GREY gives their bytes.  wct_set_guided_guide: the guide of WCT_FLAG_GUIDED (initially WCT_GUIDE_GREY); every
  *   flagged frame equals wct_guided_filter_guide(the unflagged frame, the content, that guide) bit for bit.  A guide that is
  *   neither value is WCT_STATUS_ARG and keeps the earlier setting.
- * Not served: the subsampled "fast guided filter", the banded / texture / wrap calls, radii above 64, a guide other than the content. */
+ * Not served: the banded / texture / wrap calls, radii above 64, a guide other than the content.  (The subsampled "fast guided
+ * filter" is wct_guided_upsample below.) */
 int wct_guided_filter(wct_ctx* ctx, const uint8_t* stylized, int Ho, int Wo, const uint8_t* content, int Hc, int Wc, int radius,
                       int eps_q, uint8_t* out);
 int wct_guided_filter_batch_dev(wct_ctx* ctx, const uint8_t* stylized_dev, int Ho, int Wo, const uint8_t* content_dev, int Hc, int Wc,
@@ -429,6 +430,49 @@ int  wct_stylize_prepared_batch_dev(wct_ctx* ctx, const uint8_t* content_dev, in
 int  wct_stylize_prepared_mix(wct_ctx* ctx, const uint8_t* content, int Hc, int Wc, const wct_style* const* styles, int K,
                               const float* weights, const int* levels, int n_levels, float alpha, unsigned flags,
                               uint8_t* out);
+/* Guided upsampling (He, Sun, "Fast Guided Filter", 2015): stylize small, deliver at the content's size.  The guided filter's
+ * output a I + b is a linear function of the guide per pixel with smooth coefficients: they are computed on the small frame,
+ * interpolated, and evaluated against the FULL content, which returns every edge of the content at full sharpness.  Integers only
+ * (the rule, its bounds and the derivation of its distance from the float64 filter: csrc/guided_up_rule.h) -- s [h][w][3] the small
+ * stylized frame, c [hc][wc][3] the small content (hc <= h, wc <= w, the clamp above), C [H][W][3] the full content (H >= hc,
+ * W >= wc), radius and eps_q as in wct_guided_filter, in pixels of the small frame:
+ *   1. a_q, b_q on h x w: pass 1 of wct_guided_filter, unchanged
+ *   2. per small pixel and channel, n, SA = sum a_q, SB = sum b_q of pass 2's window:  am = rdiv(SA, n), bm = rdiv(SB, n)
+ *      (2^-12 units); only rows < hc and columns < wc are read afterwards (the rest of s is padding)
+ *   3. per axis, N the full length, m the small content length (hc or wc), P the full coordinate (half-pixel centres):
+ *        t = clamp((2P + 1) m - N, 0, 2N (m - 1)),  p0 = t div 2N,  f = rdiv((t - p0 2N) 256, 2N) (0 .. 256),  p1 = min(p0 + 1, m - 1)
+ *      the axis weights are 256 - f and f; with w_k their four products (sum 65536) and I the guide of C[Y][X]:
+ *        v = sum_k w_k (am_k I + bm_k),   out = clamp((v + 2^27) >> 28, 0, 255)        (>> arithmetic: no division at full size)
+ * A constant small frame comes back as that constant at every full size.  At H = hc, W = wc the result is within 1 grey level of
+ * wct_guided_filter, NOT bit-equal to it (am, bm are rounded once more).  Before the clamp the result is within
+ * 0.5 + 256 2^-12 + D 2^-8 of the float64 fast guided filter with the same guide, box and half-pixel bilinear map, D the spread
+ * (max - min) of the pixel's four (am_k I + bm_k) 2^-12.
+ * wct_guided_upsample: host pointers, blocking.  wct_guided_upsample_batch_dev: device pointers, B = 1 .. 32 frames [B][h][w][3],
+ *   contents [B][hc][wc][3] and [B][H][W][3], out [B][H][W][3]; three launches (pass 1, the means, the full-size pass),
+ *   asynchronous on the ctx stream; out must not overlap an input.  The 48 B per SMALL pixel between the launches live in the
+ *   workspace of wct_guided_filter.
+ * wct_stylize_prepared_upsampled / _batch_dev: full contents [B][H][W][3], a prepared style and a working size (hc, wc): the
+ *   contents are resized on the device (wct_resize_batch_dev; H == hc && W == wc skips it), stylized by the prepared batch chain
+ *   and quantised by the chain's own rule, upsampled against the full contents still resident, and with WCT_FLAG_CONTENT_COLORS
+ *   recoloured at full size against the full content.  The frame [B][H][W][3] equals wct_resize -> wct_stylize_prepared ->
+ *   wct_guided_upsample -> wct_content_colors bit for bit.  flags: those of wct_stylize_prepared; WCT_FLAG_GUIDED is
+ *   WCT_STATUS_ARG, and so is WCT_FLAG_IMAGES_F32 unless H == hc && W == wc (the resize takes uint8).
+ * WCT_STATUS_ARG with a message that names the argument, the ctx usable afterwards: H < hc or W < wc, h < hc or w < wc, a null
+ *   pointer, B outside 1 .. 32, a radius or eps_q out of range, B * H * W * 3 >= 2^31, an overlap, and whatever wct_resize refuses
+ *   (its LDS limit near H / hc = 42).
+ * Not served: the colour guide and the temporal box under upsampling; mixes, masks and strength maps in the fused driver (the
+ * stand-alone op takes any frame); down-scaling; ratios the resize refuses; full contents of 2^31 bytes and more. */
+int  wct_guided_upsample(wct_ctx* ctx, const uint8_t* stylized, int h, int w, const uint8_t* content_small, int hc, int wc,
+                         const uint8_t* content_full, int H, int W, int radius, int eps_q, uint8_t* out);
+int  wct_guided_upsample_batch_dev(wct_ctx* ctx, const uint8_t* stylized_dev, int h, int w, const uint8_t* content_small_dev, int hc,
+                                   int wc, const uint8_t* content_full_dev, int H, int W, int B, int radius, int eps_q,
+                                   uint8_t* out_dev);
+int  wct_stylize_prepared_upsampled(wct_ctx* ctx, const uint8_t* content, int H, int W, int hc, int wc, const wct_style* style,
+                                    const int* levels, int n_levels, float alpha, unsigned flags, int radius, int eps_q,
+                                    uint8_t* out);
+int  wct_stylize_prepared_upsampled_batch_dev(wct_ctx* ctx, const uint8_t* content_dev, int H, int W, int B, int hc, int wc,
+                                              const wct_style* style, const int* levels, int n_levels, float alpha, unsigned flags,
+                                              int radius, int eps_q, uint8_t* out_dev);
 /* Spatial control on prepared styles, and on a batch of frames with one label map each (a video with a segmentation per frame).
  * wct_stylize_prepared_masked = wct_stylize_masked's frame, bit for bit, for the same content, mask, levels, alpha and flags and
  *   the images the K handles were prepared from: host pointers, blocking, like wct_stylize_prepared.  It is the B = 1 case of

@@ -165,6 +165,64 @@ def _guided_images(stylized, content, ndim):
         raise ValueError(str(e).replace('content_colors', 'guided_filter'))
 
 
+def check_guided_upsample(guided_upsample):
+    """The refusals of guided_upsample=(short_side, radius, eps_q), before any library call: three integers, the short side of the
+    working size at least 1, the radius and eps_q those of check_guided (in pixels of the working size).  -> (short_side, radius, eps_q)"""
+    try:
+        side, r, e = tuple(guided_upsample)
+        if int(side) != side:
+            raise TypeError
+        side = int(side)
+    except (TypeError, ValueError):
+        raise ValueError('guided_upsample is (short_side, radius, eps_q), three integers, got %r' % (guided_upsample,))
+    if side < 1:
+        raise ValueError('the short side of guided_upsample must be at least 1, got %d' % side)
+    r, e = check_guided((r, e))
+    return side, r, e
+
+
+def upsample_work_size(h, w, short_side):
+    """The working size of an h x w content under guided_upsample: utils.resize_shape(h, w, short_side), or the content's own size
+    when its short side is short_side or less already (it is then worked on as it is: the op never scales down)"""
+    if min(h, w) <= short_side:
+        return int(h), int(w)
+    from .utils import resize_shape
+    return tuple(int(v) for v in resize_shape(h, w, short_side))
+
+
+def _upsample_images(stylized, content_small, content_full, ndim):
+    """The refusals of guided_upsample's images, before any library call: three uint8 arrays [...][.][.][3] of `ndim` dimensions,
+    the small frame at least as large as the small content, the full content at least as large as the small one
+    -> the three as contiguous uint8"""
+    arrs = []
+    for name, a in (('stylized', stylized), ('content_small', content_small), ('content_full', content_full)):
+        a = np.asarray(a)
+        if a.dtype != np.uint8:
+            raise ValueError('guided_upsample takes uint8 images, %s is %s' % (name, a.dtype))
+        if a.ndim != ndim or a.shape[-1] != 3 or a.size == 0:
+            raise ValueError('guided_upsample takes %s images, %s has shape %s' % ('[B][H][W][3]' if ndim == 4 else 'HxWx3', name, a.shape))
+        arrs.append(u8(a))
+    s, c, f = arrs
+    if s.shape[-3] < c.shape[-3] or s.shape[-2] < c.shape[-2]:
+        raise ValueError('stylized %dx%d is smaller than content_small %dx%d' % (s.shape[-3], s.shape[-2], c.shape[-3], c.shape[-2]))
+    if f.shape[-3] < c.shape[-3] or f.shape[-2] < c.shape[-2]:
+        raise ValueError('content_full %dx%d is smaller than content_small %dx%d: guided_upsample does not scale down'
+                         % (f.shape[-3], f.shape[-2], c.shape[-3], c.shape[-2]))
+    if ndim == 4 and not (s.shape[0] == c.shape[0] == f.shape[0] and 1 <= s.shape[0] <= _lib.BATCH_MAX):
+        raise ValueError('a batch takes 1 .. %d frames and as many contents of either size, got %d, %d and %d'
+                         % (_lib.BATCH_MAX, s.shape[0], c.shape[0], f.shape[0]))
+    return s, c, f
+
+
+def check_work_size(work_size, h, w):
+    """The working size (hc, wc) of a stylize_prepared_upsampled call on h x w contents: two positive integers, neither above the
+    content's.  -> (hc, wc)"""
+    hc, wc = check_resize(work_size)
+    if hc > h or wc > w:
+        raise ValueError('the working size %dx%d is larger than the %dx%d content: guided_upsample does not scale down' % (hc, wc, h, w))
+    return hc, wc
+
+
 def check_texture(size, passes=1, batch=1, seed=0, first_sample=0):
     """The refusals of a texture call, before any library call: a size (H, W) of two positive integers, 1 .. PASSES_MAX passes,
     1 .. BATCH_MAX samples per call, seed and sample indices that are uint32.  -> (H, W)"""
@@ -916,6 +974,77 @@ class Context(object):
             raise ValueError('a batch takes 1 .. %d frames and as many contents, got %d and %d' % (_lib.BATCH_MAX, s.shape[0], c.shape[0]))
         return self._host_batch([s, c], np.empty_like(s), in_place=True, enqueue=lambda ds, dc: self.guided_filter_batch_dev(
             ds, s.shape[1], s.shape[2], dc, c.shape[1], c.shape[2], s.shape[0], r, e, ds, guide=guide))
+
+    # ---- guided upsampling: a small frame delivered at the full content's size ----------------
+    def guided_upsample(self, stylized_u8, content_small_u8, content_full_u8, radius, eps_q):
+        """Guided upsampling (wct_guided_upsample; He, Sun, "Fast Guided Filter"): the small stylized frame [h][w][3], the small
+        content [hc][wc][3] it was made from (hc <= h, wc <= w) and the full content [H][W][3] (H >= hc, W >= wc), all uint8 ->
+        uint8 [H][W][3]: the guided filter's coefficients of the small pair, interpolated and evaluated against the full content.
+        radius and eps_q as in guided_filter, in pixels of the small frame.  The integer rule of include/wct_hip.h."""
+        s, c, f = _upsample_images(stylized_u8, content_small_u8, content_full_u8, 3)
+        r, e = check_guided((radius, eps_q))
+        out = np.empty_like(f)
+        check(self.lib.wct_guided_upsample(self.h, s.ctypes.data_as(_lib._U8), s.shape[0], s.shape[1], c.ctypes.data_as(_lib._U8),
+                                           c.shape[0], c.shape[1], f.ctypes.data_as(_lib._U8), f.shape[0], f.shape[1], r, e,
+                                           out.ctypes.data_as(_lib._U8)))
+        return out
+
+    def guided_upsample_batch_dev(self, stylized_dev, h, w, content_small_dev, hc, wc, content_full_dev, hf, wf, batch, radius, eps_q,
+                                  out_dev):
+        """guided_upsample for B frames resident in HBM (wct_guided_upsample_batch_dev): asynchronous; out_dev overlaps no input."""
+        r, e = check_guided((radius, eps_q))
+        check(self.lib.wct_guided_upsample_batch_dev(self.h, stylized_dev, int(h), int(w), content_small_dev, int(hc), int(wc),
+                                                     content_full_dev, int(hf), int(wf), int(batch), r, e, out_dev))
+
+    def guided_upsample_batch(self, stylized_u8, contents_small_u8, contents_full_u8, radius, eps_q):
+        """Host arrays in, host array out: [B][h][w][3], [B][hc][wc][3] and [B][H][W][3] uint8 (B <= 32) -> [B][H][W][3]."""
+        s, c, f = _upsample_images(stylized_u8, contents_small_u8, contents_full_u8, 4)
+        r, e = check_guided((radius, eps_q))
+        return self._host_batch([s, c, f], np.empty_like(f), enqueue=lambda ds, dc, df, do: self.guided_upsample_batch_dev(
+            ds, s.shape[1], s.shape[2], dc, c.shape[1], c.shape[2], df, f.shape[1], f.shape[2], s.shape[0], r, e, do))
+
+    def stylize_prepared_upsampled(self, content, style, relu_targets, work_size, radius, eps_q, alpha=1.0, adain=False, wct_mode='tf',
+                                   content_colors=False):
+        """Stylize small, deliver at the content's size (wct_stylize_prepared_upsampled): the uint8 content [H][W][3] is resized on
+        the device to work_size (hc, wc), stylized with the PreparedStyle, upsampled against the full content (guided_upsample with
+        radius, eps_q) and, with content_colors, recoloured at full size -> uint8 [H][W][3], the composition of resize,
+        stylize_prepared, guided_upsample and content_colors bit for bit.  work_size equal to the content's size skips the resize."""
+        check_prepared(self, [style], relu_targets)
+        c = np.asarray(content)
+        if c.dtype != np.uint8 or c.ndim != 3 or c.shape[-1] != 3 or c.size == 0:
+            raise ValueError('stylize_prepared_upsampled takes a uint8 HxWx3 content, got %s %s' % (c.dtype, c.shape))
+        c = u8(c)
+        hc, wc = check_work_size(work_size, c.shape[0], c.shape[1])
+        r, e = check_guided((radius, eps_q))
+        lv = _levels(relu_targets)
+        out = np.empty_like(c)
+        check(self.lib.wct_stylize_prepared_upsampled(self.h, c.ctypes.data_as(_lib._U8), c.shape[0], c.shape[1], hc, wc, style.h,
+                                                      (C.c_int * len(lv))(*lv), len(lv), float(alpha),
+                                                      _flags(adain, wct_mode, content_colors=content_colors), r, e,
+                                                      out.ctypes.data_as(_lib._U8)))
+        return out
+
+    def stylize_prepared_upsampled_batch_dev(self, content_dev, hf, wf, batch, work_size, style, relu_targets, radius, eps_q, alpha, out_dev,
+                                             adain=False, wct_mode='tf', content_colors=False):
+        """stylize_prepared_upsampled for B full contents [B][H][W][3] resident in HBM -> out_dev [B][H][W][3]; asynchronous
+        (wct_stylize_prepared_upsampled_batch_dev)."""
+        lv = check_prepared(self, [style], relu_targets)
+        hc, wc = check_work_size(work_size, hf, wf)
+        r, e = check_guided((radius, eps_q))
+        check(self.lib.wct_stylize_prepared_upsampled_batch_dev(self.h, content_dev, int(hf), int(wf), int(batch), hc, wc, style.h,
+                                                                (C.c_int * len(lv))(*lv), len(lv), float(alpha),
+                                                                _flags(adain, wct_mode, content_colors=content_colors), r, e, out_dev))
+
+    def stylize_prepared_upsampled_batch(self, contents_u8, style, relu_targets, work_size, radius, eps_q, alpha=1.0, adain=False,
+                                         wct_mode='tf', content_colors=False):
+        """Host arrays in, host array out: full contents [B][H][W][3] uint8 (B <= 32) -> [B][H][W][3] uint8."""
+        check_prepared(self, [style], relu_targets)
+        _, _, c = check_resize((1, 1), contents_u8)
+        hc, wc = check_work_size(work_size, c.shape[1], c.shape[2])
+        check_guided((radius, eps_q))
+        return self._host_batch([c], np.empty_like(c), enqueue=lambda dc, do: self.stylize_prepared_upsampled_batch_dev(
+            dc, c.shape[1], c.shape[2], c.shape[0], (hc, wc), style, relu_targets, radius, eps_q, alpha, do, adain=adain,
+            wct_mode=wct_mode, content_colors=content_colors))
 
     # ---- temporal guided smoothing: the filter's box across frames --------------------------
     def guided_filter_time(self, stylized_u8, contents_u8, radius, eps_q, frames_t, positions=None):

@@ -899,6 +899,84 @@ extern "C" int wct_stylize_prepared_batch_dev_warm(wct_ctx* c, const uint8_t* co
 }
 
 // ---------------------------------------------------------------------------
+// guided upsampling (guided_up_rule.h): stylize at a working size, deliver at the content's own size.  B full contents
+// [B][H][W][3] on the device -> resized to hc x wc (wct_resize_batch_dev; skipped at equal sizes) -> the prepared batch chain and
+// its own quantisation -> upsampled against the full contents still resident -> with WCT_FLAG_CONTENT_COLORS recoloured at full
+// size against them: the composition of the stand-alone calls, bit for bit.
+// ---------------------------------------------------------------------------
+static int upsampled_flags_ok(unsigned flags, bool resized) {
+  TRY(style_flags_ok(flags));
+  if (flags & WCT_FLAG_GUIDED) {
+    wct_set_error("upsampled: WCT_FLAG_GUIDED is not served on this path (the upsampling is the guided filter of the frame)");
+    return WCT_ERR_ARG;
+  }
+  if ((flags & WCT_FLAG_IMAGES_F32) && resized) {
+    wct_set_error("upsampled: WCT_FLAG_IMAGES_F32 with H x W other than the working size hc x wc (the resize takes uint8 images)");
+    return WCT_ERR_ARG;
+  }
+  return WCT_OK;
+}
+
+static int stylize_prepared_upsampled_dev(wct_ctx* c, const void* content, int H, int W, int B, int hc, int wc, const wct_style* style,
+                                          const int* levels, int n_levels, float alpha, unsigned flags, int radius, int eps_q,
+                                          uint8_t* out) {
+  HIP_TRY(hipSetDevice(c->device));
+  int h, w;
+  TRY(wct_output_size(hc, wc, levels, n_levels, &h, &w));
+  TRY(guided_up_check(B, h, w, hc, wc, H, W, radius, eps_q));
+  const bool resized = H != hc || W != wc;
+  TRY(upsampled_flags_ok(flags, resized));
+  const int f32 = (flags & WCT_FLAG_IMAGES_F32) ? 1 : 0;
+  const void* small = content;
+  if (resized) {
+    TRY(ensure(c, c->up_c, (size_t)B * hc * wc * 3));
+    TRY(wct_resize_batch_dev(c, (const uint8_t*)content, H, W, B, hc, wc, (uint8_t*)c->up_c.p));
+    small = c->up_c.p;
+  }
+  TRY(ensure(c, c->up_s, (size_t)B * h * w * 3));
+  TRY(stylize_prepared_dev(c, small, hc, wc, B, &style, 1, nullptr, levels, n_levels, alpha, flags & ~(unsigned)WCT_FLAG_CONTENT_COLORS,
+                           (uint8_t*)c->up_s.p));
+  TRY(run_guided_upsample(c, (const uint8_t*)c->up_s.p, small, content, f32, B, h, w, hc, wc, H, W, radius, eps_q, out));
+  if (!(flags & WCT_FLAG_CONTENT_COLORS)) return WCT_OK;
+  ProfScope ps(c, 7, 0, (double)B * H * W * 3 * (2 + (f32 ? 4 : 1)));
+  return launch_content_colors_u8_any(out, content, f32, B, H, W, H, W, out, c->stream);
+}
+
+extern "C" int wct_stylize_prepared_upsampled_batch_dev(wct_ctx* c, const uint8_t* content, int H, int W, int B, int hc, int wc,
+                                                        const wct_style* style, const int* levels, int n_levels, float alpha,
+                                                        unsigned flags, int radius, int eps_q, uint8_t* out) {
+  ARG_CHECK(c != nullptr);
+  if (!content || !out || !levels) { wct_set_error("upsampled: content_dev, out_dev or levels is a null pointer"); return WCT_ERR_ARG; }
+  if (B < 1 || B > 32) { wct_set_error("upsampled: B = %d frames, must be 1 .. 32", B); return WCT_ERR_ARG; }
+  ARG_CHECK(n_levels >= 1 && n_levels <= 16);
+  const size_t n = (size_t)B * H * W * 3 * sample_bytes(flags);
+  if (H >= 1 && W >= 1 && (const uint8_t*)content < out + (size_t)B * H * W * 3 && out < (const uint8_t*)content + n) {
+    wct_set_error("upsampled: out_dev overlaps content_dev");
+    return WCT_ERR_ARG;
+  }
+  return stylize_prepared_upsampled_dev(c, content, H, W, B, hc, wc, style, levels, n_levels, alpha, flags, radius, eps_q, out);
+}
+
+extern "C" int wct_stylize_prepared_upsampled(wct_ctx* c, const uint8_t* content, int H, int W, int hc, int wc, const wct_style* style,
+                                              const int* levels, int n_levels, float alpha, unsigned flags, int radius, int eps_q,
+                                              uint8_t* out) {
+  ARG_CHECK(c != nullptr);
+  if (!content || !out || !levels) { wct_set_error("upsampled: content, out or levels is a null pointer"); return WCT_ERR_ARG; }
+  ARG_CHECK(n_levels >= 1 && n_levels <= 16);
+  HIP_TRY(hipSetDevice(c->device));
+  TRY(eig_stale(c));
+  int h, w;
+  TRY(wct_output_size(hc, wc, levels, n_levels, &h, &w));
+  TRY(guided_up_check(1, h, w, hc, wc, H, W, radius, eps_q));                                  // (before the staging buffers are sized)
+  void* dc;
+  TRY(stage_in(c, 0, content, (size_t)H * W * 3 * sample_bytes(flags), &dc));
+  TRY(ensure(c, c->stage[2], (size_t)H * W * 3));
+  TRY(stylize_prepared_upsampled_dev(c, dc, H, W, 1, hc, wc, style, levels, n_levels, alpha, flags, radius, eps_q, (uint8_t*)c->stage[2].p));
+  TRY(fetch(c, out, c->stage[2].p, (size_t)H * W * 3));
+  return eig_status(c);
+}
+
+// ---------------------------------------------------------------------------
 // strength maps (strength_rule.h): the prepared-style calls with a per-pixel style strength -- the chain, the statistics and the
 // matrices of every level are the plain call's, the blend of every feature row takes the strength of its pixel
 // ---------------------------------------------------------------------------

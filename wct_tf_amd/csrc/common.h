@@ -369,6 +369,21 @@ int guided_check(int B, int Ho, int Wo, int Hc, int Wc, int radius, int eps_q, i
 size_t guided_workspace_bytes(int B, int Ho, int Wo, int guide);
 int launch_guided_filter(const uint8_t* stylized, const void* content, int content_f32, int B, int Ho, int Wo, int Hc, int Wc, int radius,
                          int eps_q, int guide, void* workspace, uint8_t* out, hipStream_t s);
+// launch_guided_ab: pass 1 alone under the grey guide -- ab [B][Ho][Wo][3][2] int32, guided_workspace_bytes(B, Ho, Wo, GUIDE_GREY)
+int launch_guided_ab(const uint8_t* stylized, const void* content, int content_f32, int B, int Ho, int Wo, int Hc, int Wc, int radius,
+                     int eps_q, void* ab, hipStream_t s);
+// ---- guided_up.hip --------------------------------------------------------
+// Guided upsampling (guided_up_rule.h): out [B][H][W][3] = the small stylized frames s [B][h][w][3], filtered with the small
+// contents c [B][hc][wc][3] as guide, delivered at the size of the full contents C [B][H][W][3] (both contents uint8, or with
+// content_f32 both fp32 in [0,1] quantised as launch_f32_to_u8 does).  Three launches: launch_guided_ab, the window means of the
+// coefficients, the full-size pass.  workspace: guided_up_workspace_bytes(B, h, w) bytes on the device (8-byte aligned); out
+// overlaps no input; any base address (whole-dword loads and stores where W % 4 == 0 and the bases allow them).
+// guided_up_check: B outside 1 .. 32, h < hc or w < wc, H < hc or W < wc, a radius or eps_q out of range, or B * H * W * 3
+// (or B * h * w * 3) >= 2^31 is WCT_ERR_ARG with a message that names the argument.
+int guided_up_check(int B, int h, int w, int hc, int wc, int H, int W, int radius, int eps_q);
+size_t guided_up_workspace_bytes(int B, int h, int w);
+int launch_guided_upsample(const uint8_t* stylized, const void* content_small, const void* content_full, int content_f32, int B, int h,
+                           int w, int hc, int wc, int H, int W, int radius, int eps_q, void* workspace, uint8_t* out, hipStream_t s);
 // ---- guided_color.hip: the two launches of the colour guide; launch_guided_filter has checked the arguments
 int launch_guided_color(const uint8_t* stylized, const void* content, int content_f32, int B, int Ho, int Wo, int Hc, int Wc, int radius,
                         int eps_q, void* workspace, uint8_t* out, hipStream_t s);

@@ -11,7 +11,8 @@
 // y - r - 1.  A segment warms up over the 2r rows in front of its first window.  Per row the column sums become inclusive prefix
 // sums across the block (a shuffle scan per wave, the wave totals through LDS), and the window sum of column t is
 // P[t + r] - P[t - r - 1].  Pass 1's sums are below 2^31 per window, and its prefixes (256 columns x 129 rows x 65025 < 2^31)
-// are kept mod 2^32; pass 2's are int64.  The nine 64-bit divisions of a pixel are the rule's own (plain C++).
+// are kept mod 2^32; pass 2's are int64 (window_sums_ab of guided_tile.h, which the means pass of guided_up.hip shares).  The nine
+// 64-bit divisions of a pixel are the rule's own (plain C++).  launch_guided_ab is pass 1 alone, for guided_up.hip.
 #include "guided_tile.h"
 #include "guided_rule.h"
 
@@ -65,37 +66,26 @@ __global__ __launch_bounds__(NT) void guided_out_kernel(const int32_t* ab, const
   __shared__ long long P[6][NT];
   __shared__ long long tot[6][NW];
   const Place pl = place(H, W, r, strips, segs);
-  const int t = threadIdx.x, x = pl.x;
-  const int32_t* abb = ab + (size_t)pl.b * H * W * 6;
+  const int x = pl.x;
   const CT* cb = c + (size_t)pl.b * Hc * Wc * 3;
   const int xc = x < Wc ? x : Wc - 1;
-  long long v[6] = {0, 0, 0, 0, 0, 0};                      // the column's window sums of (a_q, b_q) per channel
-  auto row = [&](int y, bool add) {
-    if (!pl.col) return;
-    const int32_t* p = abb + ((size_t)y * W + x) * 6;
-#pragma unroll
-    for (int k = 0; k < 6; ++k) v[k] += add ? (long long)p[k] : -(long long)p[k];
-  };
-  for (int y = pl.y0 - r < 0 ? 0 : pl.y0 - r; y < pl.y0 + r && y < H; ++y) row(y, true);
-  for (int y = pl.y0; y < pl.y1; ++y) {
-    if (y + r < H) row(y + r, true);
-    if (y > pl.y0 && y - r - 1 >= 0) row(y - r - 1, false);
-    long long w[6];
-#pragma unroll
-    for (int k = 0; k < 6; ++k) w[k] = v[k];
-    block_prefix<long long, 6>(w, P, tot);
-    if (!pl.owner) continue;
+  window_sums_ab(ab + (size_t)pl.b * H * W * 6, pl, H, W, r, P, tot, [&](int y, const int64_t (&S)[6]) {
     const CT* cp = cb + ((size_t)(y < Hc ? y : Hc - 1) * Wc + xc) * 3;
     const int I = wct_guided_guide(sample(cp), sample(cp + 1), sample(cp + 2));
     const int64_t n = (int64_t)wct_guided_extent(y, H, r) * wct_guided_extent(x, W, r);
     uint8_t* op = out + (((size_t)pl.b * H + y) * W + x) * 3;
 #pragma unroll
-    for (int ch = 0; ch < 3; ++ch) {
-      const int64_t SA = P[2 * ch][t + r] - (t - r - 1 >= 0 ? P[2 * ch][t - r - 1] : 0);
-      const int64_t SB = P[2 * ch + 1][t + r] - (t - r - 1 >= 0 ? P[2 * ch + 1][t - r - 1] : 0);
-      op[ch] = wct_guided_out(n, SA, SB, I);
-    }
-  }
+    for (int ch = 0; ch < 3; ++ch) op[ch] = wct_guided_out(n, S[2 * ch], S[2 * ch + 1], I);
+  });
+}
+
+template <typename CT>
+int launch_ab(const uint8_t* s, const CT* c, int32_t* ab, int B, int H, int W, int Hc, int Wc, int r, int eps_q, hipStream_t st) {
+  const int strips = cdiv(W, NT - 2 * r), segs = cdiv(H, SEG);
+  const dim3 grid((unsigned)B * strips * segs);
+  hipLaunchKernelGGL((guided_ab_kernel<CT>), grid, dim3(NT), 0, st, s, c, ab, H, W, Hc, Wc, r, eps_q, strips, segs);
+  HIP_TRY(hipGetLastError());
+  return WCT_OK;
 }
 
 template <typename CT>
@@ -103,8 +93,8 @@ int launch(const uint8_t* s, const CT* c, int32_t* ab, int B, int H, int W, int 
            hipStream_t st) {
   const int strips = cdiv(W, NT - 2 * r), segs = cdiv(H, SEG);
   const dim3 grid((unsigned)B * strips * segs);
-  hipLaunchKernelGGL((guided_ab_kernel<CT>), grid, dim3(NT), 0, st, s, c, ab, H, W, Hc, Wc, r, eps_q, strips, segs);
-  HIP_TRY(hipGetLastError());
+  int rc = launch_ab(s, c, ab, B, H, W, Hc, Wc, r, eps_q, st);
+  if (rc) return rc;
   hipLaunchKernelGGL((guided_out_kernel<CT>), grid, dim3(NT), 0, st, (const int32_t*)ab, c, out, H, W, Hc, Wc, r, strips, segs);
   HIP_TRY(hipGetLastError());
   return WCT_OK;
@@ -135,6 +125,15 @@ int guided_check(int B, int Ho, int Wo, int Hc, int Wc, int radius, int eps_q, i
 
 size_t guided_workspace_bytes(int B, int Ho, int Wo, int guide) {
   return (size_t)B * Ho * Wo * (guide == GUIDE_COLOR ? 12 : 6) * sizeof(int32_t);
+}
+
+int launch_guided_ab(const uint8_t* stylized, const void* content, int content_f32, int B, int Ho, int Wo, int Hc, int Wc, int radius,
+                     int eps_q, void* ab, hipStream_t s) {
+  ARG_CHECK(stylized && content && ab);
+  int rc = guided_check(B, Ho, Wo, Hc, Wc, radius, eps_q, GUIDE_GREY);
+  if (rc) return rc;
+  if (content_f32) return launch_ab(stylized, (const float*)content, (int32_t*)ab, B, Ho, Wo, Hc, Wc, radius, eps_q, s);
+  return launch_ab(stylized, (const uint8_t*)content, (int32_t*)ab, B, Ho, Wo, Hc, Wc, radius, eps_q, s);
 }
 
 int launch_guided_filter(const uint8_t* stylized, const void* content, int content_f32, int B, int Ho, int Wo, int Hc, int Wc, int radius,

@@ -16,7 +16,8 @@
 //     cov = n SIp - SI Sp, var = n SII - SI^2 (>= 0, Cauchy-Schwarz), den = var + eps_q n^2
 //     a_q = rdiv(cov 2^12, den), b_q = rdiv(Sp 2^12 - a_q SI, n)
 //   pass 2: SA = sum a_q, SB = sum b_q over the window; out = clamp(rdiv(SA I + SB, n 2^12), 0, 255)
-// Left out: the subsampled "fast guided filter", radii above 64.  The colour (3-channel) guide is guided_color_rule.h.
+// Left out: radii above 64.  The colour (3-channel) guide is guided_color_rule.h, the subsampled "fast guided filter"
+// guided_up_rule.h.
 #pragma once
 #include <stdint.h>
 #include "colors_rule.h"

@@ -1,4 +1,4 @@
-// What the kernels of guided.hip and guided_color.hip share: the tiling (a block of NT threads owns SEG rows of a strip of
+// What the kernels of guided.hip, guided_color.hip and guided_up.hip share: the tiling (a block of NT threads owns SEG rows of a strip of
 // NT - 2r columns of one frame, thread t owns column x0 - r + t with the halo), the block-wide prefix sums of a row, and the read
 // of a content sample.  Included inside each unit, so every name is local to it.
 #pragma once
@@ -54,5 +54,35 @@ __device__ __forceinline__ Place place(int H, int W, int r, int strips, int segs
   p.y0 = seg * SEG;
   p.y1 = p.y0 + SEG < H ? p.y0 + SEG : H;
   return p;
+}
+
+// The window sums of the grey guide's coefficient map abb [H][W][6] int32 (one frame) over the block's place: the column's
+// running vertical sums in registers, per row the block-wide prefix, and emit(y, S) for every pixel (y, pl.x) the block owns, S[6]
+// its window sums (a_q, b_q per channel).  What pass 2 of guided.hip and the means pass of guided_up.hip share.
+template <typename Emit>
+__device__ __forceinline__ void window_sums_ab(const int32_t* abb, const Place& pl, int H, int W, int r, long long (*P)[NT],
+                                               long long (*tot)[NW], Emit&& emit) {
+  const int t = threadIdx.x, x = pl.x;
+  long long v[6] = {0, 0, 0, 0, 0, 0};                      // the column's window sums of (a_q, b_q) per channel
+  auto row = [&](int y, bool add) {
+    if (!pl.col) return;
+    const int32_t* p = abb + ((size_t)y * W + x) * 6;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) v[k] += add ? (long long)p[k] : -(long long)p[k];
+  };
+  for (int y = pl.y0 - r < 0 ? 0 : pl.y0 - r; y < pl.y0 + r && y < H; ++y) row(y, true);
+  for (int y = pl.y0; y < pl.y1; ++y) {
+    if (y + r < H) row(y + r, true);
+    if (y > pl.y0 && y - r - 1 >= 0) row(y - r - 1, false);
+    long long w[6];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) w[k] = v[k];
+    block_prefix<long long, 6>(w, P, tot);
+    if (!pl.owner) continue;                                // (every thread has passed both barriers of the row)
+    int64_t S[6];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) S[k] = P[k][t + r] - (t - r - 1 >= 0 ? P[k][t - r - 1] : 0);
+    emit(y, S);
+  }
 }
 }  // namespace

@@ -14,7 +14,10 @@ with prepared styles and every other option.
 et al., "Guided Image Filtering"; the post-step of Li et al. 2018's fast photorealistic variant) -- edges where the content has
 them, averages where it is flat.  `--guided-guide color` guides it with the content's three channels where the default, `grey`,
 takes their grey: it also keeps an edge between two colours of equal luminance, at about three times the filter's cost.  Not in
-bands."""
+bands.
+`--guided-upsample` (with `--guided-radius` and `--content-size`) stylizes small and delivers at the content's size: the content is
+resized on the device to `--content-size`, stylized there, and the filter's coefficients are interpolated and evaluated against the
+full content (He & Sun, "Fast Guided Filter"), which returns the content's edges at full sharpness."""
 import argparse
 import os
 import time
@@ -50,6 +53,13 @@ _FLAGS = [
     (('--style-size',), dict(type=int, default=0, help='short side of the style image (0: as is)')),
     (('--crop-size',), dict(type=int, default=0, help='centre-crop the style image to a square of this side (0: no)')),
     (('--content-size',), dict(type=int, default=0, help='short side of the content image (0: as is)')),
+    (('--guided-upsample',), dict(action='store_true', default=False,
+                                  help='stylize small, deliver at the content\'s size (He & Sun, "Fast Guided Filter"): the content is '
+                                       'resized on the device to --content-size, stylized there, and upsampled against the full '
+                                       'content with the filter of --guided-radius / --guided-eps (in pixels of the working size); the '
+                                       'output has the content\'s own size.  Needs --guided-radius > 0 and --content-size > 0; goes '
+                                       'with --content-colors; not with --guided-guide color, --swap5, --keep-colors, --interp-styles, '
+                                       '--mask-path, --alpha-map, --band-rows > 0 or --passes > 1')),
     (('--passes',), dict(type=int, default=1, help='feed the result back in this many times')),
     (('-r', '--random'), dict(type=int, default=0, help='use this many randomly chosen styles of the style folder')),
     (('--alpha',), dict(type=float, default=1, help='style strength: blend of transformed and content features')),
@@ -166,6 +176,32 @@ def check_guided_args(parser, args):
         parser.error('--guided-radius with --passes > 1 needs --ss-stride 1 (a larger stride crops the content of every pass)')
 
 
+def check_upsample_args(parser, args, extra=()):
+    """--guided-upsample: what it needs and what it does not combine with (parser.error exits).  extra: further (option, given)
+    pairs of the calling command line"""
+    if not getattr(args, 'guided_upsample', False):
+        return
+    if not args.guided_radius > 0:
+        parser.error('--guided-upsample needs --guided-radius > 0 (the upsampling is that filter, in pixels of the working size)')
+    if not args.content_size > 0:
+        parser.error('--guided-upsample needs --content-size > 0 (the short side of the working size)')
+    on = [('--guided-guide color', getattr(args, 'guided_guide', None) == 'color'), ('--swap5', args.swap5),
+          ('--keep-colors', args.keep_colors), ('--interp-styles', getattr(args, 'interp_styles', None) is not None),
+          ('--mask-path', getattr(args, 'mask_path', None) is not None), ('--alpha-map', getattr(args, 'alpha_map', None) is not None),
+          ('--band-rows > 0', getattr(args, 'band_rows', 0) > 0), ('--passes > 1', args.passes > 1)] + list(extra)
+    for flag, given in on:
+        if given:
+            parser.error('--guided-upsample does not combine with %s: it takes one style, WCT or AdaIN, in one pass, under the grey '
+                         'guide' % flag)
+
+
+def upsample_of(args):
+    """(short_side, radius, eps_q) of --guided-upsample with --content-size and --guided-radius / --guided-eps; None: off"""
+    if not getattr(args, 'guided_upsample', False):
+        return None
+    return (args.content_size,) + tuple(guided_of(args)[:2])
+
+
 def guided_of(args):
     """(radius, eps_q) of --guided-radius / --guided-eps, eps in grey levels squared and at most 65025 -- (radius, eps_q, 'color')
     with --guided-guide color; None: off"""
@@ -261,7 +297,10 @@ def stylize_pair(model, content, style, args, prepared=None, alpha_grey=None):
     if args.keep_colors:
         from .ops import preserve_colors_np
         style = preserve_colors_np(style, content, ctx=model.sess)
-    if alpha_grey is not None:             # (one pass, no swap5, no bands: check_alpha_map_args)
+    if upsample_of(args) is not None:      # (one pass, one style, the content at its own size: check_upsample_args)
+        out = model.predict(content, style if prepared is None else prepared, args.alpha, adain=args.adain,
+                            content_colors=getattr(args, 'content_colors', False), guided_upsample=upsample_of(args))
+    elif alpha_grey is not None:           # (one pass, no swap5, no bands: check_alpha_map_args)
         out = model.predict(content, style if prepared is None else prepared, args.alpha, adain=args.adain,
                             content_colors=getattr(args, 'content_colors', False), strength=strength_map(alpha_grey, content.shape[:2]),
                             guided=guided_of(args))
@@ -428,6 +467,7 @@ def main(argv=None):
     check_guided_args(parser, args)
     check_band_args(parser, args)
     check_alpha_map_args(parser, args)
+    check_upsample_args(parser, args)
     if args.synthetic_weights is None and not args.checkpoints:
         parser.error('--checkpoints is required (stylize.py:17) unless --synthetic-weights SEED is given')
     if args.gpus > 0:
@@ -495,9 +535,12 @@ def main(argv=None):
     alpha_grey = load_alpha_map(args.alpha_map) if args.alpha_map is not None else None
     for cpath in contents:
         content = utils.get_img(cpath)
-        if args.content_size > 0:
-            content = utils.resize_to(content, args.content_size)
-        check_content_fits(parser, args, content, cpath)
+        if args.guided_upsample:           # the content goes up at its own size; the network sees --content-size
+            content = np.ascontiguousarray(content, np.uint8)
+        else:
+            if args.content_size > 0:
+                content = utils.resize_to(content, args.content_size)
+            check_content_fits(parser, args, content, cpath)
         for spath in styles:
             if spath not in loaded:
                 style = load_style(spath, args)

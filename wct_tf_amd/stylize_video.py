@@ -87,6 +87,13 @@ _FLAGS = [
     (('--style-size',), dict(type=int, default=0, help='short side of the style image (0: as is)')),
     (('--crop-size',), dict(type=int, default=0, help='centre-crop the style image to a square of this side (0: no)')),
     (('--content-size',), dict(type=int, default=0, help='short side of every frame (0: as is)')),
+    (('--guided-upsample',), dict(action='store_true', default=False,
+                                  help='stylize small, deliver at the frame\'s size (He & Sun, "Fast Guided Filter"): every raw frame '
+                                       'is resized on the device to --content-size, stylized there, and upsampled against itself with '
+                                       'the filter of --guided-radius / --guided-eps (in pixels of the working size); the output frames '
+                                       'have the input\'s size.  Needs --guided-radius > 0 and --content-size > 0; goes with '
+                                       '--content-colors; not with --guided-guide color, --guided-frames, --swap5, --keep-colors, '
+                                       '--mask-path, --alpha-map, --warm-start or --passes > 1')),
     (('--passes',), dict(type=int, default=1, help='feed the result back in this many times')),
     (('--device',), dict(default='/gpu:0', help='e.g. /gpu:0')),
     (('--alpha',), dict(type=float, default=1, help='style strength')),
@@ -375,7 +382,7 @@ def stylize_frames_masked(wct_model, frame_files, mask_files, styles, args):
 def stylize_frames(wct_model, frame_files, style_img, args, alpha_files=None):
     """Yield (frame_file, stylized uint8 image) in order; consecutive same-sized frames are batched.  alpha_files: the strength map
     file of every frame (--alpha-map), or None."""
-    from .stylize import load_alpha_map, strength_map, guided_of
+    from .stylize import load_alpha_map, strength_map, guided_of, upsample_of
     alpha_of = dict(zip(frame_files, alpha_files)) if alpha_files is not None else {}
 
     def strengths_of(files, shape_hw):
@@ -383,9 +390,11 @@ def stylize_frames(wct_model, frame_files, style_img, args, alpha_files=None):
         greys = {p: load_alpha_map(p) for p in {alpha_of[f] for f in files}}
         return np.stack([strength_map(greys[alpha_of[f]], shape_hw) for f in files])
 
+    upsample = upsample_of(args)                                  # --guided-upsample: the frames go up raw, at their own size
+
     def load(f):
         img = get_img(f)
-        if args.content_size > 0 and not getattr(args, 'device_resize', False):
+        if args.content_size > 0 and not getattr(args, 'device_resize', False) and upsample is None:
             img = resize_to(img, args.content_size)
         return img
 
@@ -410,6 +419,9 @@ def stylize_frames(wct_model, frame_files, style_img, args, alpha_files=None):
     def run(frames, style, files):
         """-> (the stylized frames, their contents at the size the network saw them)"""
         style = prepared if prepared is not None else style
+        if upsample is not None:                              # (one pass, no warm state, no maps: check_upsample_args)
+            return wct_model.predict_frames(np.ascontiguousarray(frames, np.uint8), style, args.alpha, adain=args.adain, batch=args.batch,
+                                            content_colors=colors, guided_upsample=upsample), frames
         size = device_size(args, frames)
         maps = strengths_of(files, size or frames.shape[1:3]) if alpha_files is not None else None     # (one pass: check_alpha_map_args)
         out = wct_model.predict_frames(frames, style, args.alpha, args.swap5, args.ss_alpha, args.adain, batch=args.batch, warm=warm,
@@ -487,6 +499,9 @@ def main(argv=None):
     check_guided_args(parser, args)
     check_resize_args(parser, args)
     check_alpha_map_args(parser, args)
+    from .stylize import check_upsample_args
+    check_upsample_args(parser, args, extra=[('--guided-frames', getattr(args, 'guided_frames', 0) > 0),
+                                              ('--warm-start', getattr(args, 'warm_start', False))])
     if args.synthetic_weights is None and not args.checkpoints:
         parser.error('--checkpoints is required (stylize.py:17) unless --synthetic-weights SEED is given')
     start = time.time()

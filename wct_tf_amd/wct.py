@@ -260,7 +260,7 @@ class WCT(object):
         return None if guided is None else check_guided(guided)
 
     def predict(self, content, style, alpha=1, swap5=False, ss_alpha=1, adain=False, warm=None, content_colors=False,
-                band_rows=None, strength=None, guided=None):
+                band_rows=None, strength=None, guided=None, guided_upsample=None):
         '''Stylize a single content/style pair; arrays in [0,255], returns uint8 HxWx3.
            The /255 preprocess and the clip*255 postprocess run inside the library
            (fused at the ends of the kernel chain).  `style` may be a PreparedStyle (prepare_style); with one, `warm` may be a
@@ -280,8 +280,19 @@ class WCT(object):
            equals ops.guided_filter_np(the plain frame, content, radius, eps_q) bit for bit, and with content_colors the colour op
            runs after it.  (radius, eps_q, 'color') guides with the three channels of `content` (guide='color' of the op), which
            also keeps an edge between two colours of equal luminance; (radius, eps_q, 'grey') is the two-element form.  Not
-           served in bands, with wrap or for textures: ValueError.'''
+           served in bands, with wrap or for textures: ValueError.
+           guided_upsample (here and in predict_frames): (short_side, radius, eps_q) -- stylize small, deliver at the content's size
+           (He & Sun, "Fast Guided Filter"; Context.stylize_prepared_upsampled).  The uint8 content is resized on the device to
+           utils.resize_shape(H, W, short_side) (a content whose short side is short_side or less is worked on as it is), stylized
+           there, and upsampled against the full content: the frame has the content's size and equals ops.guided_upsample_np(
+           predict(the resized content), the resized content, content, radius, eps_q) bit for bit, content_colors_np against the
+           full content after it.  A style image is prepared for the call.  No swap5, warm, bands, strength or guided with it:
+           ValueError.'''
         guided = self._check_guided(guided)                                       # ValueError before any GPU call
+        if guided_upsample is not None:
+            return self._predict_upsampled(np.asarray(content)[None], style, guided_upsample, alpha, adain, content_colors, 1,
+                                           dict(swap5=swap5, warm=warm is not None, band_rows=band_rows is not None and band_rows is not False,
+                                                strength=strength is not None, guided=guided is not None))[0]
         if strength is not None:
             from ._lib import strength_map
             content = np.asarray(content)
@@ -321,6 +332,31 @@ class WCT(object):
         # reference's preprocess does (wct.py:60-64) -- Context.stylize hands them over as float32 images
         return self.sess.stylize(content, style, self.relu_targets, alpha=alpha, adain=adain,
                                  wct_mode=self.wct_mode, swap5=bool(swap5), content_colors=content_colors, guided=guided)
+
+    def _predict_upsampled(self, frames, style, guided_upsample, alpha, adain, content_colors, batch, others):
+        '''predict / predict_frames with guided_upsample=(short_side, radius, eps_q): uint8 full frames [F][H][W][3] -> [F][H][W][3].
+           others: the options that do not go with it, by name -> whether they were given (ValueError before any GPU call)'''
+        from .context import check_guided_upsample, upsample_work_size
+        side, r, e = check_guided_upsample(guided_upsample)
+        for name, on in others.items():
+            if on:
+                raise ValueError('%s is not served with guided_upsample: one prepared style, WCT or AdaIN, content_colors' % name)
+        if frames.ndim != 4 or frames.shape[3] != 3 or frames.size == 0:
+            raise ValueError('guided_upsample takes HxWx3 contents, got shape %s' % (frames.shape[1:] if frames.shape[0] == 1 else frames.shape,))
+        if frames.dtype != np.uint8:
+            raise ValueError('guided_upsample takes uint8 contents (the resize on the device does), got %s' % frames.dtype)
+        work = upsample_work_size(frames.shape[1], frames.shape[2], side)
+        if isinstance(style, PreparedStyle):
+            check_prepared(self.sess, [style], self.relu_targets)
+        own = None if isinstance(style, PreparedStyle) else self.prepare_style(np.asarray(style), adain=adain)
+        try:
+            batch = max(1, min(32, int(batch)))
+            return np.concatenate([self.sess.stylize_prepared_upsampled_batch(
+                frames[i:i + batch], own or style, self.relu_targets, work, r, e, alpha=alpha, adain=adain, wct_mode=self.wct_mode,
+                content_colors=content_colors) for i in range(0, len(frames), batch)], axis=0)
+        finally:
+            if own is not None:
+                own.close()
 
     def predict_mix(self, content, styles, weights=None, alpha=1, adain=False, swap5=False, ss_alpha=1, content_colors=False,
                     guided=None):
@@ -479,7 +515,8 @@ class WCT(object):
         return out
 
     def predict_frames(self, frames, style, alpha=1, swap5=False, ss_alpha=1, adain=False, batch=16, warm=None,
-                       content_colors=False, resize=None, wrap=False, strengths=None, guided=None, guided_frames=0, guided_motion=None):
+                       content_colors=False, resize=None, wrap=False, strengths=None, guided=None, guided_frames=0, guided_motion=None,
+                       guided_upsample=None):
         '''Stylize same-sized frames [F][H][W][3] with ONE style image (the loop of stylize_video.py:112-121,
            which calls predict() once per frame and so re-runs the style encoder, the style statistics and the
            style eigendecompositions every frame).  Here the style side runs once per batch of `batch` frames;
@@ -508,9 +545,17 @@ class WCT(object):
            (py, px): the caller's positions, steps of at most 16.  The result equals ops.guided_filter_time_np(plain frames,
            contents, radius, eps_q, T, positions=ops.motion_global_np(contents, R)) bit for bit, whatever `batch` is.  A scene cut
            yields an arbitrary step, which the filter treats like any edge.  Per-block or dense motion, sub-pixel shifts, rotation
-           and zoom are not served.'''
+           and zoom are not served.
+           guided_upsample (short_side, radius, eps_q): as in predict -- every raw uint8 frame goes up at its own size, is resized
+           and stylized at the working size and upsampled against itself; frame f equals predict(frames[f], style,
+           guided_upsample=...) bit for bit, at the frames' size.  No swap5, warm, resize, wrap, strengths or guided* with it.'''
         guided = self._check_guided(guided)                                       # ValueError before any GPU call
         frames = np.asarray(frames)
+        if guided_upsample is not None:
+            return self._predict_upsampled(frames, style, guided_upsample, alpha, adain, content_colors, batch,
+                                           dict(swap5=swap5, warm=warm is not None, resize=resize is not None, wrap=wrap,
+                                                strengths=strengths is not None, guided=guided is not None,
+                                                guided_frames=bool(guided_frames), guided_motion=guided_motion is not None))
         temporal = self._check_guided_frames(guided, guided_frames, swap5, wrap)
         motion = self._check_guided_motion(guided_motion, temporal, frames, resize)
         if temporal:
