@@ -460,8 +460,9 @@ int  wct_stylize_prepared_mix(wct_ctx* ctx, const uint8_t* content, int Hc, int 
  * WCT_STATUS_ARG with a message that names the argument, the ctx usable afterwards: H < hc or W < wc, h < hc or w < wc, a null
  *   pointer, B outside 1 .. 32, a radius or eps_q out of range, B * H * W * 3 >= 2^31, an overlap, and whatever wct_resize refuses
  *   (its LDS limit near H / hc = 42).
- * Not served: the colour guide and the temporal box under upsampling; mixes, masks and strength maps in the fused driver (the
- * stand-alone op takes any frame); down-scaling; ratios the resize refuses; full contents of 2^31 bytes and more. */
+ * Not served: the temporal box under upsampling; mixes, masks and strength maps in the fused driver (the stand-alone op takes any
+ * frame); down-scaling; ratios the resize refuses; full contents of 2^31 bytes and more.  (The colour guide under upsampling is
+ * served by the wct_*_guide calls below.) */
 int  wct_guided_upsample(wct_ctx* ctx, const uint8_t* stylized, int h, int w, const uint8_t* content_small, int hc, int wc,
                          const uint8_t* content_full, int H, int W, int radius, int eps_q, uint8_t* out);
 int  wct_guided_upsample_batch_dev(wct_ctx* ctx, const uint8_t* stylized_dev, int h, int w, const uint8_t* content_small_dev, int hc,
@@ -473,6 +474,41 @@ int  wct_stylize_prepared_upsampled(wct_ctx* ctx, const uint8_t* content, int H,
 int  wct_stylize_prepared_upsampled_batch_dev(wct_ctx* ctx, const uint8_t* content_dev, int H, int W, int B, int hc, int wc,
                                               const wct_style* style, const int* levels, int n_levels, float alpha, unsigned flags,
                                               int radius, int eps_q, uint8_t* out_dev);
+/* Guided upsampling with a choice of guide: the four calls above with `int guide` as one more argument.  WCT_GUIDE_GREY gives their
+ * bytes through their kernels.  WCT_GUIDE_COLOR is the upsampling rule with the coefficients of the colour-guide filter, which
+ * keeps an edge between two colours of equal luminance at full sharpness (the rule, its bounds and the derivation of its distance
+ * from the float64 filter: csrc/guided_up_color_rule.h).  Notation as above:
+ *   1. a_q[i][p], b_q[p] on h x w: pass 1 of wct_guided_filter_guide(..., WCT_GUIDE_COLOR), unchanged (12 int32 per small pixel)
+ *   2. per small pixel, n, SA_ip = sum a_q[i][p], SB_p = sum b_q[p] of pass 2's window:  am[i][p] = rdiv(SA_ip, n),
+ *      bm[p] = rdiv(SB_p, n)  (2^-12 units, |am| <= 288400, |bm| <= 2.22e8); only rows < hc and columns < wc are read afterwards
+ *   3. the axis taps and weights of step 3 above, unchanged; with I_i the three channels of C[Y][X]:
+ *        v_p = sum_k w_k (sum_i am_k[i][p] I_i + bm_k[p]),   out_p = clamp((v_p + 2^27) >> 28, 0, 255)      (|v| < 2.91e13 < 2^45)
+ * A constant small frame comes back as that constant at every full size.  At H = hc, W = wc the result is within 1 grey level of
+ * wct_guided_filter_guide(..., WCT_GUIDE_COLOR), NOT bit-equal to it.  Before the clamp the result is within
+ * 0.5 + 766 2^-12 + 765 2^-35 + D 2^-8 + E(eps_q) of the float64 fast guided filter with the colour guide (np.linalg.solve on the
+ * small pair's window covariances, the same box and half-pixel bilinear map), D the spread of the pixel's four corner values and
+ * E(eps_q) = 255 sqrt(3) 2^-5 (sqrt(3) + 191.25 / sqrt(eps_q)) / (eps_q - 3 2^-5) the worst case of the colour rule's covariance
+ * quantisation: 0.0005 at eps_q = 65025, 0.2 at 650, above a grey level from eps_q of a few hundred downwards, where it is no
+ * useful bound (measured: at most 0.55 at eps_q >= 7, up to 0.78 at eps_q = 1).
+ * Three launches (the colour pass 1, the means of the twelve coefficient planes, the full-size pass); the 96 B per SMALL pixel
+ * between them live in the workspace of wct_guided_filter (16-byte aligned): the colour guide adds no limit beyond that size.
+ * wct_stylize_prepared_upsampled_guide / _batch_dev equal wct_resize -> wct_stylize_prepared -> wct_guided_upsample_guide ->
+ * wct_content_colors bit for bit; WCT_FLAG_IMAGES_F32 only without a resize, as above.
+ * WCT_STATUS_ARG: a guide that is neither of the two, with a message that names the argument; every refusal of the calls above,
+ *   with the same words.
+ * Not served: the temporal box under upsampling; mixes, masks and strength maps in the fused driver; down-scaling; full contents of
+ * 2^31 bytes and more. */
+int  wct_guided_upsample_guide(wct_ctx* ctx, const uint8_t* stylized, int h, int w, const uint8_t* content_small, int hc, int wc,
+                               const uint8_t* content_full, int H, int W, int radius, int eps_q, int guide, uint8_t* out);
+int  wct_guided_upsample_guide_batch_dev(wct_ctx* ctx, const uint8_t* stylized_dev, int h, int w, const uint8_t* content_small_dev,
+                                         int hc, int wc, const uint8_t* content_full_dev, int H, int W, int B, int radius, int eps_q,
+                                         int guide, uint8_t* out_dev);
+int  wct_stylize_prepared_upsampled_guide(wct_ctx* ctx, const uint8_t* content, int H, int W, int hc, int wc, const wct_style* style,
+                                          const int* levels, int n_levels, float alpha, unsigned flags, int radius, int eps_q,
+                                          int guide, uint8_t* out);
+int  wct_stylize_prepared_upsampled_guide_batch_dev(wct_ctx* ctx, const uint8_t* content_dev, int H, int W, int B, int hc, int wc,
+                                                    const wct_style* style, const int* levels, int n_levels, float alpha,
+                                                    unsigned flags, int radius, int eps_q, int guide, uint8_t* out_dev);
 /* Spatial control on prepared styles, and on a batch of frames with one label map each (a video with a segmentation per frame).
  * wct_stylize_prepared_masked = wct_stylize_masked's frame, bit for bit, for the same content, mask, levels, alpha and flags and
  *   the images the K handles were prepared from: host pointers, blocking, like wct_stylize_prepared.  It is the B = 1 case of

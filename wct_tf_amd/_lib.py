@@ -68,6 +68,10 @@ SIGNATURES = [
     ('wct_guided_upsample', C.c_int, [_P, _U8, C.c_int, C.c_int, _U8, C.c_int, C.c_int, _U8, C.c_int, C.c_int, C.c_int, C.c_int, _U8]),
     ('wct_guided_upsample_batch_dev', C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int,
                                                 C.c_int, _P]),
+    ('wct_guided_upsample_guide', C.c_int, [_P, _U8, C.c_int, C.c_int, _U8, C.c_int, C.c_int, _U8, C.c_int, C.c_int, C.c_int, C.c_int,
+                                            C.c_int, _U8]),
+    ('wct_guided_upsample_guide_batch_dev', C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int,
+                                                      C.c_int, C.c_int, C.c_int, _P]),
     ('wct_resize', C.c_int, [_P, _U8, C.c_int, C.c_int, C.c_int, C.c_int, _U8]),
     ('wct_resize_batch_dev', C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     ('wct_output_size', C.c_int, [C.c_int, C.c_int, _I, C.c_int, _I, _I]),
@@ -87,6 +91,10 @@ SIGNATURES = [
                                                  C.c_int, C.c_int, _U8]),
     ('wct_stylize_prepared_upsampled_batch_dev', C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _I, C.c_int, C.c_float,
                                                            C.c_uint, C.c_int, C.c_int, _P]),
+    ('wct_stylize_prepared_upsampled_guide', C.c_int, [_P, _U8, C.c_int, C.c_int, C.c_int, C.c_int, _P, _I, C.c_int, C.c_float, C.c_uint,
+                                                       C.c_int, C.c_int, C.c_int, _U8]),
+    ('wct_stylize_prepared_upsampled_guide_batch_dev', C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _I, C.c_int,
+                                                                 C.c_float, C.c_uint, C.c_int, C.c_int, C.c_int, _P]),
     ('wct_stylize_prepared_mix', C.c_int, [_P, _U8, C.c_int, C.c_int, _PP, C.c_int, _F, _I, C.c_int, C.c_float, C.c_uint, _U8]),
     ('wct_stylize_prepared_masked', C.c_int, [_P, _U8, C.c_int, C.c_int, _U8, _PP, C.c_int, _I, C.c_int, C.c_float, C.c_uint, _U8]),
     ('wct_stylize_prepared_masked_batch_dev', C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _U8, _PP, C.c_int, _I, C.c_int, C.c_float,

@@ -166,18 +166,25 @@ def _guided_images(stylized, content, ndim):
 
 
 def check_guided_upsample(guided_upsample):
-    """The refusals of guided_upsample=(short_side, radius, eps_q), before any library call: three integers, the short side of the
-    working size at least 1, the radius and eps_q those of check_guided (in pixels of the working size).  -> (short_side, radius, eps_q)"""
+    """The refusals of guided_upsample=(short_side, radius, eps_q) or (short_side, radius, eps_q, guide), before any library call:
+    three integers, the short side of the working size at least 1, the radius and eps_q those of check_guided (in pixels of the
+    working size), and the guide 'grey' (what the three-element form means) or 'color'.
+    -> (short_side, radius, eps_q), or (short_side, radius, eps_q, guide) as it was given"""
     try:
-        side, r, e = tuple(guided_upsample)
+        g = tuple(guided_upsample)
+        side, r, e = g[:3] if len(g) == 4 else g
         if int(side) != side:
             raise TypeError
         side = int(side)
     except (TypeError, ValueError):
-        raise ValueError('guided_upsample is (short_side, radius, eps_q), three integers, got %r' % (guided_upsample,))
+        raise ValueError("guided_upsample is (short_side, radius, eps_q), three integers, or (short_side, radius, eps_q, 'grey' or "
+                         "'color'), got %r" % (guided_upsample,))
     if side < 1:
         raise ValueError('the short side of guided_upsample must be at least 1, got %d' % side)
     r, e = check_guided((r, e))
+    if len(g) == 4:
+        check_guide(g[3])
+        return side, r, e, g[3]
     return side, r, e
 
 
@@ -976,38 +983,44 @@ class Context(object):
             ds, s.shape[1], s.shape[2], dc, c.shape[1], c.shape[2], s.shape[0], r, e, ds, guide=guide))
 
     # ---- guided upsampling: a small frame delivered at the full content's size ----------------
-    def guided_upsample(self, stylized_u8, content_small_u8, content_full_u8, radius, eps_q):
-        """Guided upsampling (wct_guided_upsample; He, Sun, "Fast Guided Filter"): the small stylized frame [h][w][3], the small
+    def guided_upsample(self, stylized_u8, content_small_u8, content_full_u8, radius, eps_q, guide='grey'):
+        """Guided upsampling (wct_guided_upsample_guide; He, Sun, "Fast Guided Filter"): the small stylized frame [h][w][3], the small
         content [hc][wc][3] it was made from (hc <= h, wc <= w) and the full content [H][W][3] (H >= hc, W >= wc), all uint8 ->
         uint8 [H][W][3]: the guided filter's coefficients of the small pair, interpolated and evaluated against the full content.
-        radius and eps_q as in guided_filter, in pixels of the small frame.  The integer rule of include/wct_hip.h."""
+        radius and eps_q as in guided_filter, in pixels of the small frame.  guide: 'grey', the grey of the contents, or 'color',
+        their three channels (which brings back an edge between two colours of equal luminance).  The integer rules of
+        include/wct_hip.h."""
         s, c, f = _upsample_images(stylized_u8, content_small_u8, content_full_u8, 3)
         r, e = check_guided((radius, eps_q))
+        g = check_guide(guide)
         out = np.empty_like(f)
-        check(self.lib.wct_guided_upsample(self.h, s.ctypes.data_as(_lib._U8), s.shape[0], s.shape[1], c.ctypes.data_as(_lib._U8),
-                                           c.shape[0], c.shape[1], f.ctypes.data_as(_lib._U8), f.shape[0], f.shape[1], r, e,
-                                           out.ctypes.data_as(_lib._U8)))
+        check(self.lib.wct_guided_upsample_guide(self.h, s.ctypes.data_as(_lib._U8), s.shape[0], s.shape[1], c.ctypes.data_as(_lib._U8),
+                                                 c.shape[0], c.shape[1], f.ctypes.data_as(_lib._U8), f.shape[0], f.shape[1], r, e, g,
+                                                 out.ctypes.data_as(_lib._U8)))
         return out
 
     def guided_upsample_batch_dev(self, stylized_dev, h, w, content_small_dev, hc, wc, content_full_dev, hf, wf, batch, radius, eps_q,
-                                  out_dev):
-        """guided_upsample for B frames resident in HBM (wct_guided_upsample_batch_dev): asynchronous; out_dev overlaps no input."""
+                                  out_dev, guide='grey'):
+        """guided_upsample for B frames resident in HBM (wct_guided_upsample_guide_batch_dev): asynchronous; out_dev overlaps no
+        input."""
         r, e = check_guided((radius, eps_q))
-        check(self.lib.wct_guided_upsample_batch_dev(self.h, stylized_dev, int(h), int(w), content_small_dev, int(hc), int(wc),
-                                                     content_full_dev, int(hf), int(wf), int(batch), r, e, out_dev))
+        g = check_guide(guide)
+        check(self.lib.wct_guided_upsample_guide_batch_dev(self.h, stylized_dev, int(h), int(w), content_small_dev, int(hc), int(wc),
+                                                           content_full_dev, int(hf), int(wf), int(batch), r, e, g, out_dev))
 
-    def guided_upsample_batch(self, stylized_u8, contents_small_u8, contents_full_u8, radius, eps_q):
+    def guided_upsample_batch(self, stylized_u8, contents_small_u8, contents_full_u8, radius, eps_q, guide='grey'):
         """Host arrays in, host array out: [B][h][w][3], [B][hc][wc][3] and [B][H][W][3] uint8 (B <= 32) -> [B][H][W][3]."""
         s, c, f = _upsample_images(stylized_u8, contents_small_u8, contents_full_u8, 4)
         r, e = check_guided((radius, eps_q))
+        check_guide(guide)
         return self._host_batch([s, c, f], np.empty_like(f), enqueue=lambda ds, dc, df, do: self.guided_upsample_batch_dev(
-            ds, s.shape[1], s.shape[2], dc, c.shape[1], c.shape[2], df, f.shape[1], f.shape[2], s.shape[0], r, e, do))
+            ds, s.shape[1], s.shape[2], dc, c.shape[1], c.shape[2], df, f.shape[1], f.shape[2], s.shape[0], r, e, do, guide=guide))
 
     def stylize_prepared_upsampled(self, content, style, relu_targets, work_size, radius, eps_q, alpha=1.0, adain=False, wct_mode='tf',
-                                   content_colors=False):
-        """Stylize small, deliver at the content's size (wct_stylize_prepared_upsampled): the uint8 content [H][W][3] is resized on
-        the device to work_size (hc, wc), stylized with the PreparedStyle, upsampled against the full content (guided_upsample with
-        radius, eps_q) and, with content_colors, recoloured at full size -> uint8 [H][W][3], the composition of resize,
+                                   content_colors=False, guide='grey'):
+        """Stylize small, deliver at the content's size (wct_stylize_prepared_upsampled_guide): the uint8 content [H][W][3] is resized
+        on the device to work_size (hc, wc), stylized with the PreparedStyle, upsampled against the full content (guided_upsample with
+        radius, eps_q and guide) and, with content_colors, recoloured at full size -> uint8 [H][W][3], the composition of resize,
         stylize_prepared, guided_upsample and content_colors bit for bit.  work_size equal to the content's size skips the resize."""
         check_prepared(self, [style], relu_targets)
         c = np.asarray(content)
@@ -1016,35 +1029,39 @@ class Context(object):
         c = u8(c)
         hc, wc = check_work_size(work_size, c.shape[0], c.shape[1])
         r, e = check_guided((radius, eps_q))
+        g = check_guide(guide)
         lv = _levels(relu_targets)
         out = np.empty_like(c)
-        check(self.lib.wct_stylize_prepared_upsampled(self.h, c.ctypes.data_as(_lib._U8), c.shape[0], c.shape[1], hc, wc, style.h,
-                                                      (C.c_int * len(lv))(*lv), len(lv), float(alpha),
-                                                      _flags(adain, wct_mode, content_colors=content_colors), r, e,
-                                                      out.ctypes.data_as(_lib._U8)))
+        check(self.lib.wct_stylize_prepared_upsampled_guide(self.h, c.ctypes.data_as(_lib._U8), c.shape[0], c.shape[1], hc, wc, style.h,
+                                                            (C.c_int * len(lv))(*lv), len(lv), float(alpha),
+                                                            _flags(adain, wct_mode, content_colors=content_colors), r, e, g,
+                                                            out.ctypes.data_as(_lib._U8)))
         return out
 
     def stylize_prepared_upsampled_batch_dev(self, content_dev, hf, wf, batch, work_size, style, relu_targets, radius, eps_q, alpha, out_dev,
-                                             adain=False, wct_mode='tf', content_colors=False):
+                                             adain=False, wct_mode='tf', content_colors=False, guide='grey'):
         """stylize_prepared_upsampled for B full contents [B][H][W][3] resident in HBM -> out_dev [B][H][W][3]; asynchronous
-        (wct_stylize_prepared_upsampled_batch_dev)."""
+        (wct_stylize_prepared_upsampled_guide_batch_dev)."""
         lv = check_prepared(self, [style], relu_targets)
         hc, wc = check_work_size(work_size, hf, wf)
         r, e = check_guided((radius, eps_q))
-        check(self.lib.wct_stylize_prepared_upsampled_batch_dev(self.h, content_dev, int(hf), int(wf), int(batch), hc, wc, style.h,
-                                                                (C.c_int * len(lv))(*lv), len(lv), float(alpha),
-                                                                _flags(adain, wct_mode, content_colors=content_colors), r, e, out_dev))
+        g = check_guide(guide)
+        check(self.lib.wct_stylize_prepared_upsampled_guide_batch_dev(self.h, content_dev, int(hf), int(wf), int(batch), hc, wc, style.h,
+                                                                      (C.c_int * len(lv))(*lv), len(lv), float(alpha),
+                                                                      _flags(adain, wct_mode, content_colors=content_colors), r, e, g,
+                                                                      out_dev))
 
     def stylize_prepared_upsampled_batch(self, contents_u8, style, relu_targets, work_size, radius, eps_q, alpha=1.0, adain=False,
-                                         wct_mode='tf', content_colors=False):
+                                         wct_mode='tf', content_colors=False, guide='grey'):
         """Host arrays in, host array out: full contents [B][H][W][3] uint8 (B <= 32) -> [B][H][W][3] uint8."""
         check_prepared(self, [style], relu_targets)
         _, _, c = check_resize((1, 1), contents_u8)
         hc, wc = check_work_size(work_size, c.shape[1], c.shape[2])
         check_guided((radius, eps_q))
+        check_guide(guide)
         return self._host_batch([c], np.empty_like(c), enqueue=lambda dc, do: self.stylize_prepared_upsampled_batch_dev(
             dc, c.shape[1], c.shape[2], c.shape[0], (hc, wc), style, relu_targets, radius, eps_q, alpha, do, adain=adain,
-            wct_mode=wct_mode, content_colors=content_colors))
+            wct_mode=wct_mode, content_colors=content_colors, guide=guide))
 
     # ---- temporal guided smoothing: the filter's box across frames --------------------------
     def guided_filter_time(self, stylized_u8, contents_u8, radius, eps_q, frames_t, positions=None):

@@ -120,7 +120,7 @@ struct wct_ctx {
   DevBuf guided_ab;                // guided smoothing (guided.hip, guided_color.hip): the coefficient map between the two passes,
                                    // 24 B per pixel under the grey guide, 48 B under the colour guide
   DevBuf up_c, up_s;               // guided upsampling in a stylize call (wct_stylize_prepared_upsampled*): the contents resized to the working
-                                   // size and the small stylized frames.  The op's two maps (48 B per SMALL pixel) live in guided_ab
+                                   // size and the small stylized frames.  The op's two maps (48 B per SMALL pixel, 96 B under the colour guide) live in guided_ab
   int guided_radius = 8, guided_eps = 650;   // what WCT_FLAG_GUIDED filters with (wct_set_guided; eps 0.01 of the [0,1]^2 convention)
   int guided_guide = WCT_GUIDE_GREY;         // ... and through which guide (wct_set_guided_guide)
   std::vector<wct_style*> styles;  // the live prepared styles of this context (wct_style_prepare .. wct_style_free)
@@ -284,10 +284,12 @@ int wrap_decoder_buffers(wct_ctx* c, int B, int h, int w, int level);
 int run_guided_filter(wct_ctx* c, const uint8_t* stylized, const void* content, int content_f32, int B, int Ho, int Wo, int Hc, int Wc,
                       int radius, int eps_q, int guide, uint8_t* out);
 
-// guided upsampling of B small uint8 frames on the device (guided_up.hip): its maps in c->guided_ab (ensured here); out overlaps
-// no input (the callers check or own the buffers)
+// guided upsampling of B small uint8 frames on the device (guided_up.hip, or guided_up_color.hip under WCT_GUIDE_COLOR): its maps
+// in c->guided_ab (ensured here); out overlaps no input (the callers check or own the buffers).  guided_up_guide_check: a guide
+// that is neither of the two is WCT_ERR_ARG with a message that names the argument
+int guided_up_guide_check(int guide);
 int run_guided_upsample(wct_ctx* c, const uint8_t* stylized, const void* content_small, const void* content_full, int content_f32, int B,
-                        int h, int w, int hc, int wc, int H, int W, int radius, int eps_q, uint8_t* out);
+                        int h, int w, int hc, int wc, int H, int W, int radius, int eps_q, int guide, uint8_t* out);
 
 // ---- api_stylize.hip ------------------------------------------------------
 int warm_live(const wct_ctx* c, const wct_warm* wm);     // WCT_ERR_STATE unless wm is a live warm state of c

@@ -748,16 +748,28 @@ extern "C" int wct_guided_filter(wct_ctx* c, const uint8_t* stylized, int Ho, in
   return wct_guided_filter_guide(c, stylized, Ho, Wo, content, Hc, Wc, radius, eps_q, WCT_GUIDE_GREY, out);
 }
 
-// Guided upsampling, op level (csrc/guided_up.hip).  run_guided_upsample: the three launches on B frames resident on the device;
-// wct_stylize_prepared_upsampled* end in it
+// Guided upsampling, op level (csrc/guided_up.hip, csrc/guided_up_color.hip).  run_guided_upsample: the three launches on B frames
+// resident on the device; wct_stylize_prepared_upsampled* end in it
+int guided_up_guide_check(int guide) {
+  if (guide == WCT_GUIDE_GREY || guide == WCT_GUIDE_COLOR) return WCT_OK;
+  wct_set_error("guided upsample: guide %d, must be WCT_GUIDE_GREY (%d) or WCT_GUIDE_COLOR (%d)", guide, WCT_GUIDE_GREY, WCT_GUIDE_COLOR);
+  return WCT_ERR_ARG;
+}
+
 int run_guided_upsample(wct_ctx* c, const uint8_t* stylized, const void* content_small, const void* content_full, int content_f32, int B,
-                        int h, int w, int hc, int wc, int H, int W, int radius, int eps_q, uint8_t* out) {
+                        int h, int w, int hc, int wc, int H, int W, int radius, int eps_q, int guide, uint8_t* out) {
   TRY(guided_up_check(B, h, w, hc, wc, H, W, radius, eps_q));
-  TRY(ensure(c, c->guided_ab, guided_up_workspace_bytes(B, h, w)));
+  TRY(guided_up_guide_check(guide));
+  const bool color = guide == WCT_GUIDE_COLOR;
+  TRY(ensure(c, c->guided_ab, color ? guided_up_color_workspace_bytes(B, h, w) : guided_up_workspace_bytes(B, h, w)));
   // per small pixel: s and c read twice and the map written (pass 1), the map read twice and the means written; per full pixel
   // the content read and the frame written; the means are read through the cache, once per pixel at ratio 1 and less above it
   const int cb = content_f32 ? 4 : 1;
-  ProfScope ps(c, 7, 0, (double)B * h * w * (2 * 3 + 2 * 3 * cb + 4 * 24.0) + (double)B * H * W * (3 * cb + 3) + (double)B * hc * wc * 24);
+  const double map = color ? 48.0 : 24.0;
+  ProfScope ps(c, 7, 0, (double)B * h * w * (2 * 3 + 2 * 3 * cb + 4 * map) + (double)B * H * W * (3 * cb + 3) + (double)B * hc * wc * map);
+  if (color)
+    return launch_guided_upsample_color(stylized, content_small, content_full, content_f32, B, h, w, hc, wc, H, W, radius, eps_q,
+                                        c->guided_ab.p, out, c->stream);
   return launch_guided_upsample(stylized, content_small, content_full, content_f32, B, h, w, hc, wc, H, W, radius, eps_q, c->guided_ab.p,
                                 out, c->stream);
 }
@@ -768,19 +780,20 @@ static bool bytes_overlap(const void* a, size_t na, const void* b, size_t nb) {
 }
 
 static int guided_upsample_checks(const void* stylized, const void* content_small, const void* content_full, const void* out, int B, int h,
-                                  int w, int hc, int wc, int H, int W, int radius, int eps_q) {
+                                  int w, int hc, int wc, int H, int W, int radius, int eps_q, int guide) {
   if (!stylized) { wct_set_error("guided upsample: stylized is a null pointer"); return WCT_ERR_ARG; }
   if (!content_small) { wct_set_error("guided upsample: content_small is a null pointer"); return WCT_ERR_ARG; }
   if (!content_full) { wct_set_error("guided upsample: content_full is a null pointer"); return WCT_ERR_ARG; }
   if (!out) { wct_set_error("guided upsample: out is a null pointer"); return WCT_ERR_ARG; }
-  return guided_up_check(B, h, w, hc, wc, H, W, radius, eps_q);
+  TRY(guided_up_check(B, h, w, hc, wc, H, W, radius, eps_q));
+  return guided_up_guide_check(guide);
 }
 
-extern "C" int wct_guided_upsample_batch_dev(wct_ctx* c, const uint8_t* stylized, int h, int w, const uint8_t* content_small, int hc,
-                                             int wc, const uint8_t* content_full, int H, int W, int B, int radius, int eps_q,
-                                             uint8_t* out) {
+extern "C" int wct_guided_upsample_guide_batch_dev(wct_ctx* c, const uint8_t* stylized, int h, int w, const uint8_t* content_small, int hc,
+                                                   int wc, const uint8_t* content_full, int H, int W, int B, int radius, int eps_q,
+                                                   int guide, uint8_t* out) {
   ARG_CHECK(c != nullptr);
-  TRY(guided_upsample_checks(stylized, content_small, content_full, out, B, h, w, hc, wc, H, W, radius, eps_q));
+  TRY(guided_upsample_checks(stylized, content_small, content_full, out, B, h, w, hc, wc, H, W, radius, eps_q, guide));
   const size_t nout = (size_t)B * H * W * 3;
   if (bytes_overlap(out, nout, stylized, (size_t)B * h * w * 3) || bytes_overlap(out, nout, content_small, (size_t)B * hc * wc * 3) ||
       bytes_overlap(out, nout, content_full, nout)) {
@@ -788,22 +801,34 @@ extern "C" int wct_guided_upsample_batch_dev(wct_ctx* c, const uint8_t* stylized
     return WCT_ERR_ARG;
   }
   HIP_TRY(hipSetDevice(c->device));
-  return run_guided_upsample(c, stylized, content_small, content_full, 0, B, h, w, hc, wc, H, W, radius, eps_q, out);
+  return run_guided_upsample(c, stylized, content_small, content_full, 0, B, h, w, hc, wc, H, W, radius, eps_q, guide, out);
 }
 
-extern "C" int wct_guided_upsample(wct_ctx* c, const uint8_t* stylized, int h, int w, const uint8_t* content_small, int hc, int wc,
-                                   const uint8_t* content_full, int H, int W, int radius, int eps_q, uint8_t* out) {
+extern "C" int wct_guided_upsample_batch_dev(wct_ctx* c, const uint8_t* stylized, int h, int w, const uint8_t* content_small, int hc,
+                                             int wc, const uint8_t* content_full, int H, int W, int B, int radius, int eps_q,
+                                             uint8_t* out) {
+  return wct_guided_upsample_guide_batch_dev(c, stylized, h, w, content_small, hc, wc, content_full, H, W, B, radius, eps_q, WCT_GUIDE_GREY,
+                                             out);
+}
+
+extern "C" int wct_guided_upsample_guide(wct_ctx* c, const uint8_t* stylized, int h, int w, const uint8_t* content_small, int hc, int wc,
+                                         const uint8_t* content_full, int H, int W, int radius, int eps_q, int guide, uint8_t* out) {
   ARG_CHECK(c != nullptr);
-  TRY(guided_upsample_checks(stylized, content_small, content_full, out, 1, h, w, hc, wc, H, W, radius, eps_q));   // (before the staging buffers are sized)
+  TRY(guided_upsample_checks(stylized, content_small, content_full, out, 1, h, w, hc, wc, H, W, radius, eps_q, guide));   // (before the staging buffers are sized)
   HIP_TRY(hipSetDevice(c->device));
   void *ds, *dc, *dC;
   TRY(stage_in(c, 0, stylized, (size_t)h * w * 3, &ds));
   TRY(stage_in(c, 1, content_small, (size_t)hc * wc * 3, &dc));
   TRY(stage_in(c, 2, content_full, (size_t)H * W * 3, &dC));
   TRY(ensure(c, c->stage[3], (size_t)H * W * 3));
-  TRY(wct_guided_upsample_batch_dev(c, (uint8_t*)ds, h, w, (uint8_t*)dc, hc, wc, (uint8_t*)dC, H, W, 1, radius, eps_q,
-                                    (uint8_t*)c->stage[3].p));
+  TRY(wct_guided_upsample_guide_batch_dev(c, (uint8_t*)ds, h, w, (uint8_t*)dc, hc, wc, (uint8_t*)dC, H, W, 1, radius, eps_q, guide,
+                                          (uint8_t*)c->stage[3].p));
   return fetch(c, out, c->stage[3].p, (size_t)H * W * 3);
+}
+
+extern "C" int wct_guided_upsample(wct_ctx* c, const uint8_t* stylized, int h, int w, const uint8_t* content_small, int hc, int wc,
+                                   const uint8_t* content_full, int H, int W, int radius, int eps_q, uint8_t* out) {
+  return wct_guided_upsample_guide(c, stylized, h, w, content_small, hc, wc, content_full, H, W, radius, eps_q, WCT_GUIDE_GREY, out);
 }
 
 // Temporal guided smoothing, op level (csrc/guided_time.hip): frames f0 .. f1 - 1 of a clip of F resident frames, the coefficient

@@ -918,12 +918,13 @@ static int upsampled_flags_ok(unsigned flags, bool resized) {
 }
 
 static int stylize_prepared_upsampled_dev(wct_ctx* c, const void* content, int H, int W, int B, int hc, int wc, const wct_style* style,
-                                          const int* levels, int n_levels, float alpha, unsigned flags, int radius, int eps_q,
+                                          const int* levels, int n_levels, float alpha, unsigned flags, int radius, int eps_q, int guide,
                                           uint8_t* out) {
   HIP_TRY(hipSetDevice(c->device));
   int h, w;
   TRY(wct_output_size(hc, wc, levels, n_levels, &h, &w));
   TRY(guided_up_check(B, h, w, hc, wc, H, W, radius, eps_q));
+  TRY(guided_up_guide_check(guide));
   const bool resized = H != hc || W != wc;
   TRY(upsampled_flags_ok(flags, resized));
   const int f32 = (flags & WCT_FLAG_IMAGES_F32) ? 1 : 0;
@@ -936,15 +937,15 @@ static int stylize_prepared_upsampled_dev(wct_ctx* c, const void* content, int H
   TRY(ensure(c, c->up_s, (size_t)B * h * w * 3));
   TRY(stylize_prepared_dev(c, small, hc, wc, B, &style, 1, nullptr, levels, n_levels, alpha, flags & ~(unsigned)WCT_FLAG_CONTENT_COLORS,
                            (uint8_t*)c->up_s.p));
-  TRY(run_guided_upsample(c, (const uint8_t*)c->up_s.p, small, content, f32, B, h, w, hc, wc, H, W, radius, eps_q, out));
+  TRY(run_guided_upsample(c, (const uint8_t*)c->up_s.p, small, content, f32, B, h, w, hc, wc, H, W, radius, eps_q, guide, out));
   if (!(flags & WCT_FLAG_CONTENT_COLORS)) return WCT_OK;
   ProfScope ps(c, 7, 0, (double)B * H * W * 3 * (2 + (f32 ? 4 : 1)));
   return launch_content_colors_u8_any(out, content, f32, B, H, W, H, W, out, c->stream);
 }
 
-extern "C" int wct_stylize_prepared_upsampled_batch_dev(wct_ctx* c, const uint8_t* content, int H, int W, int B, int hc, int wc,
-                                                        const wct_style* style, const int* levels, int n_levels, float alpha,
-                                                        unsigned flags, int radius, int eps_q, uint8_t* out) {
+extern "C" int wct_stylize_prepared_upsampled_guide_batch_dev(wct_ctx* c, const uint8_t* content, int H, int W, int B, int hc, int wc,
+                                                              const wct_style* style, const int* levels, int n_levels, float alpha,
+                                                              unsigned flags, int radius, int eps_q, int guide, uint8_t* out) {
   ARG_CHECK(c != nullptr);
   if (!content || !out || !levels) { wct_set_error("upsampled: content_dev, out_dev or levels is a null pointer"); return WCT_ERR_ARG; }
   if (B < 1 || B > 32) { wct_set_error("upsampled: B = %d frames, must be 1 .. 32", B); return WCT_ERR_ARG; }
@@ -954,12 +955,19 @@ extern "C" int wct_stylize_prepared_upsampled_batch_dev(wct_ctx* c, const uint8_
     wct_set_error("upsampled: out_dev overlaps content_dev");
     return WCT_ERR_ARG;
   }
-  return stylize_prepared_upsampled_dev(c, content, H, W, B, hc, wc, style, levels, n_levels, alpha, flags, radius, eps_q, out);
+  return stylize_prepared_upsampled_dev(c, content, H, W, B, hc, wc, style, levels, n_levels, alpha, flags, radius, eps_q, guide, out);
 }
 
-extern "C" int wct_stylize_prepared_upsampled(wct_ctx* c, const uint8_t* content, int H, int W, int hc, int wc, const wct_style* style,
-                                              const int* levels, int n_levels, float alpha, unsigned flags, int radius, int eps_q,
-                                              uint8_t* out) {
+extern "C" int wct_stylize_prepared_upsampled_batch_dev(wct_ctx* c, const uint8_t* content, int H, int W, int B, int hc, int wc,
+                                                        const wct_style* style, const int* levels, int n_levels, float alpha,
+                                                        unsigned flags, int radius, int eps_q, uint8_t* out) {
+  return wct_stylize_prepared_upsampled_guide_batch_dev(c, content, H, W, B, hc, wc, style, levels, n_levels, alpha, flags, radius, eps_q,
+                                                        WCT_GUIDE_GREY, out);
+}
+
+extern "C" int wct_stylize_prepared_upsampled_guide(wct_ctx* c, const uint8_t* content, int H, int W, int hc, int wc, const wct_style* style,
+                                                    const int* levels, int n_levels, float alpha, unsigned flags, int radius, int eps_q,
+                                                    int guide, uint8_t* out) {
   ARG_CHECK(c != nullptr);
   if (!content || !out || !levels) { wct_set_error("upsampled: content, out or levels is a null pointer"); return WCT_ERR_ARG; }
   ARG_CHECK(n_levels >= 1 && n_levels <= 16);
@@ -968,12 +976,21 @@ extern "C" int wct_stylize_prepared_upsampled(wct_ctx* c, const uint8_t* content
   int h, w;
   TRY(wct_output_size(hc, wc, levels, n_levels, &h, &w));
   TRY(guided_up_check(1, h, w, hc, wc, H, W, radius, eps_q));                                  // (before the staging buffers are sized)
+  TRY(guided_up_guide_check(guide));
   void* dc;
   TRY(stage_in(c, 0, content, (size_t)H * W * 3 * sample_bytes(flags), &dc));
   TRY(ensure(c, c->stage[2], (size_t)H * W * 3));
-  TRY(stylize_prepared_upsampled_dev(c, dc, H, W, 1, hc, wc, style, levels, n_levels, alpha, flags, radius, eps_q, (uint8_t*)c->stage[2].p));
+  TRY(stylize_prepared_upsampled_dev(c, dc, H, W, 1, hc, wc, style, levels, n_levels, alpha, flags, radius, eps_q, guide,
+                                     (uint8_t*)c->stage[2].p));
   TRY(fetch(c, out, c->stage[2].p, (size_t)H * W * 3));
   return eig_status(c);
+}
+
+extern "C" int wct_stylize_prepared_upsampled(wct_ctx* c, const uint8_t* content, int H, int W, int hc, int wc, const wct_style* style,
+                                              const int* levels, int n_levels, float alpha, unsigned flags, int radius, int eps_q,
+                                              uint8_t* out) {
+  return wct_stylize_prepared_upsampled_guide(c, content, H, W, hc, wc, style, levels, n_levels, alpha, flags, radius, eps_q, WCT_GUIDE_GREY,
+                                              out);
 }
 
 // ---------------------------------------------------------------------------

@@ -387,6 +387,19 @@ int launch_guided_upsample(const uint8_t* stylized, const void* content_small, c
 // ---- guided_color.hip: the two launches of the colour guide; launch_guided_filter has checked the arguments
 int launch_guided_color(const uint8_t* stylized, const void* content, int content_f32, int B, int Ho, int Wo, int Hc, int Wc, int radius,
                         int eps_q, void* workspace, uint8_t* out, hipStream_t s);
+// launch_guided_color_ab: pass 1 alone under the colour guide -- ab [B][Ho][Wo][12] int32, 16-byte aligned,
+// guided_workspace_bytes(B, Ho, Wo, GUIDE_COLOR)
+int launch_guided_color_ab(const uint8_t* stylized, const void* content, int content_f32, int B, int Ho, int Wo, int Hc, int Wc, int radius,
+                           int eps_q, void* ab, hipStream_t s);
+// ---- guided_up_color.hip --------------------------------------------------
+// Guided upsampling under the colour guide (guided_up_color_rule.h): the arguments, the refusals (guided_up_check) and the
+// contract of launch_guided_upsample.  Three launches: launch_guided_color_ab, the window means of the twelve coefficients, the
+// full-size pass.  workspace: guided_up_color_workspace_bytes(B, h, w) bytes on the device (96 B per small pixel, 16-byte aligned);
+// any base address of the images (whole 16-bit loads and stores where W is even and the bases allow them).
+size_t guided_up_color_workspace_bytes(int B, int h, int w);
+int launch_guided_upsample_color(const uint8_t* stylized, const void* content_small, const void* content_full, int content_f32, int B,
+                                 int h, int w, int hc, int wc, int H, int W, int radius, int eps_q, void* workspace, uint8_t* out,
+                                 hipStream_t s);
 // ---- guided_time.hip ------------------------------------------------------
 // Temporal guided smoothing (guided_time_rule.h): the grey-guide filter with its box extended over frames_t frames on each side,
 // on a clip of F frames [F][Ho][Wo][3] with contents [F][Hc][Wc][3] resident on the device.  out [f1 - f0][Ho][Wo][3] = the

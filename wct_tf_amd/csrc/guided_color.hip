@@ -5,7 +5,9 @@
 //           int32: a_q[i][p] at 3 i + p, b_q[p] at 9 + p (48 B per pixel, three 16-byte stores)
 //   pass 2: ab + c -> out [B][H][W][3] uint8; out may be s (pass 1 has consumed s before pass 2 writes)
 // Pass 1 keeps the 21 window sums of the rule per column, mod 2^32: every term is <= 65025, so the true sums stay below 2^31 and
-// the prefixes of a row (256 columns x 129 rows x 65025 < 2^31) too, as in guided.hip.  Pass 2 keeps 12 int64 sums.  The 27
+// the prefixes of a row (256 columns x 129 rows x 65025 < 2^31) too, as in guided.hip.  Pass 2 keeps 12 int64 sums
+// (window_sums_ab12 of guided_tile.h, which the means pass of guided_up_color.hip shares); launch_guided_color_ab is pass 1 alone,
+// for guided_up_color.hip.  The 27
 // 64-bit divisions of a pixel and its 3 x 3 solve are the rule's own (plain C++); halo threads leave the row before them.
 #include "guided_tile.h"
 #include "guided_color_rule.h"
@@ -63,63 +65,57 @@ __global__ __launch_bounds__(NT) void guided_color_out_kernel(const int32_t* ab,
   __shared__ long long P[KC][NT];
   __shared__ long long tot[KC][NW];
   const Place pl = place(H, W, r, strips, segs);
-  const int t = threadIdx.x, x = pl.x;
-  const int32_t* abb = ab + (size_t)pl.b * H * W * KC;
+  const int x = pl.x;
   const CT* cb = c + (size_t)pl.b * Hc * Wc * 3;
   const int xc = x < Wc ? x : Wc - 1;
-  long long v[KC];                                          // the column's window sums of the twelve coefficients
-#pragma unroll
-  for (int k = 0; k < KC; ++k) v[k] = 0;
-  auto row = [&](int y, bool add) {
-    if (!pl.col) return;
-    const int4* p = reinterpret_cast<const int4*>(abb + ((size_t)y * W + x) * KC);
-#pragma unroll
-    for (int k = 0; k < KC / 4; ++k) {
-      const int4 q = p[k];
-      const int e[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-      for (int j = 0; j < 4; ++j) v[4 * k + j] += add ? (long long)e[j] : -(long long)e[j];
-    }
-  };
-  for (int y = pl.y0 - r < 0 ? 0 : pl.y0 - r; y < pl.y0 + r && y < H; ++y) row(y, true);
-  for (int y = pl.y0; y < pl.y1; ++y) {
-    if (y + r < H) row(y + r, true);
-    if (y > pl.y0 && y - r - 1 >= 0) row(y - r - 1, false);
-    long long w[KC];
-#pragma unroll
-    for (int k = 0; k < KC; ++k) w[k] = v[k];
-    block_prefix<long long, KC>(w, P, tot);
-    if (!pl.owner) continue;
+  window_sums_ab12(ab + (size_t)pl.b * H * W * KC, pl, H, W, r, P, tot, [&](int y, auto win) {
     const CT* cp = cb + ((size_t)(y < Hc ? y : Hc - 1) * Wc + xc) * 3;
     const int I[3] = {sample(cp), sample(cp + 1), sample(cp + 2)};
     const int64_t n = (int64_t)wct_guided_extent(y, H, r) * wct_guided_extent(x, W, r);
     uint8_t* op = out + (((size_t)pl.b * H + y) * W + x) * 3;
-    auto win = [&](int k) -> int64_t { return P[k][t + r] - (t - r - 1 >= 0 ? P[k][t - r - 1] : 0); };
 #pragma unroll
     for (int ch = 0; ch < 3; ++ch) {
       const int64_t SA[3] = {win(ch), win(3 + ch), win(6 + ch)};
       op[ch] = wct_guided_color_out(n, SA, win(9 + ch), I);
     }
-  }
+  });
 }
 
 template <typename CT>
-int launch(const uint8_t* s, const CT* c, int32_t* ab, int B, int H, int W, int Hc, int Wc, int r, int eps_q, uint8_t* out,
-           hipStream_t st) {
+int launch_ab(const uint8_t* s, const CT* c, int32_t* ab, int B, int H, int W, int Hc, int Wc, int r, int eps_q, hipStream_t st) {
   const int strips = cdiv(W, NT - 2 * r), segs = cdiv(H, SEG);
   const dim3 grid((unsigned)B * strips * segs);
   hipLaunchKernelGGL((guided_color_ab_kernel<CT>), grid, dim3(NT), 0, st, s, c, ab, H, W, Hc, Wc, r, eps_q, strips, segs);
   HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL((guided_color_out_kernel<CT>), grid, dim3(NT), 0, st, (const int32_t*)ab, c, out, H, W, Hc, Wc, r, strips, segs);
+  return WCT_OK;
+}
+
+template <typename CT>
+int launch_out(const int32_t* ab, const CT* c, int B, int H, int W, int Hc, int Wc, int r, uint8_t* out, hipStream_t st) {
+  const int strips = cdiv(W, NT - 2 * r), segs = cdiv(H, SEG);
+  const dim3 grid((unsigned)B * strips * segs);
+  hipLaunchKernelGGL((guided_color_out_kernel<CT>), grid, dim3(NT), 0, st, ab, c, out, H, W, Hc, Wc, r, strips, segs);
   HIP_TRY(hipGetLastError());
   return WCT_OK;
 }
 }  // namespace
 
+int launch_guided_color_ab(const uint8_t* stylized, const void* content, int content_f32, int B, int Ho, int Wo, int Hc, int Wc, int radius,
+                           int eps_q, void* ab, hipStream_t s) {
+  ARG_CHECK(stylized && content && ab);
+  if (((uintptr_t)ab & 15) != 0) { wct_set_error("guided filter: the colour guide's workspace must be 16-byte aligned"); return WCT_ERR_ARG; }
+  int rc = guided_check(B, Ho, Wo, Hc, Wc, radius, eps_q, GUIDE_COLOR);
+  if (rc) return rc;
+  if (content_f32) return launch_ab(stylized, (const float*)content, (int32_t*)ab, B, Ho, Wo, Hc, Wc, radius, eps_q, s);
+  return launch_ab(stylized, (const uint8_t*)content, (int32_t*)ab, B, Ho, Wo, Hc, Wc, radius, eps_q, s);
+}
+
 int launch_guided_color(const uint8_t* stylized, const void* content, int content_f32, int B, int Ho, int Wo, int Hc, int Wc, int radius,
                         int eps_q, void* workspace, uint8_t* out, hipStream_t s) {
   ARG_CHECK(stylized && content && workspace && out);
-  if (((uintptr_t)workspace & 15) != 0) { wct_set_error("guided filter: the colour guide's workspace must be 16-byte aligned"); return WCT_ERR_ARG; }
-  if (content_f32) return launch(stylized, (const float*)content, (int32_t*)workspace, B, Ho, Wo, Hc, Wc, radius, eps_q, out, s);
-  return launch(stylized, (const uint8_t*)content, (int32_t*)workspace, B, Ho, Wo, Hc, Wc, radius, eps_q, out, s);
+  int rc = launch_guided_color_ab(stylized, content, content_f32, B, Ho, Wo, Hc, Wc, radius, eps_q, workspace, s);
+  if (rc) return rc;
+  const int32_t* ab = (const int32_t*)workspace;
+  if (content_f32) return launch_out(ab, (const float*)content, B, Ho, Wo, Hc, Wc, radius, out, s);
+  return launch_out(ab, (const uint8_t*)content, B, Ho, Wo, Hc, Wc, radius, out, s);
 }

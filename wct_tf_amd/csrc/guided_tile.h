@@ -1,4 +1,4 @@
-// What the kernels of guided.hip, guided_color.hip and guided_up.hip share: the tiling (a block of NT threads owns SEG rows of a strip of
+// What the kernels of guided.hip, guided_color.hip, guided_up.hip and guided_up_color.hip share: the tiling (a block of NT threads owns SEG rows of a strip of
 // NT - 2r columns of one frame, thread t owns column x0 - r + t with the halo), the block-wide prefix sums of a row, and the read
 // of a content sample.  Included inside each unit, so every name is local to it.
 #pragma once
@@ -83,6 +83,41 @@ __device__ __forceinline__ void window_sums_ab(const int32_t* abb, const Place& 
 #pragma unroll
     for (int k = 0; k < 6; ++k) S[k] = P[k][t + r] - (t - r - 1 >= 0 ? P[k][t - r - 1] : 0);
     emit(y, S);
+  }
+}
+
+// The same for the colour guide's coefficient map abb [H][W][12] int32 (one frame; 48 B per pixel from a 16-byte aligned base,
+// read as three int4): emit(y, win) for every pixel (y, pl.x) the block owns, win(k) the window sum of coefficient k.  What pass 2
+// of guided_color.hip and the means pass of guided_up_color.hip share.  P [12][NT] and tot [12][NW] are the block's.
+template <typename Emit>
+__device__ __forceinline__ void window_sums_ab12(const int32_t* abb, const Place& pl, int H, int W, int r, long long (*P)[NT],
+                                                 long long (*tot)[NW], Emit&& emit) {
+  constexpr int K = 12;
+  const int t = threadIdx.x, x = pl.x;
+  long long v[K];                                           // the column's window sums of the twelve coefficients
+#pragma unroll
+  for (int k = 0; k < K; ++k) v[k] = 0;
+  auto row = [&](int y, bool add) {
+    if (!pl.col) return;
+    const int4* p = reinterpret_cast<const int4*>(abb + ((size_t)y * W + x) * K);
+#pragma unroll
+    for (int k = 0; k < K / 4; ++k) {
+      const int4 q = p[k];
+      const int e[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+      for (int j = 0; j < 4; ++j) v[4 * k + j] += add ? (long long)e[j] : -(long long)e[j];
+    }
+  };
+  for (int y = pl.y0 - r < 0 ? 0 : pl.y0 - r; y < pl.y0 + r && y < H; ++y) row(y, true);
+  for (int y = pl.y0; y < pl.y1; ++y) {
+    if (y + r < H) row(y + r, true);
+    if (y > pl.y0 && y - r - 1 >= 0) row(y - r - 1, false);
+    long long w[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) w[k] = v[k];
+    block_prefix<long long, K>(w, P, tot);
+    if (!pl.owner) continue;                                // (every thread has passed both barriers of the row)
+    emit(y, [&](int k) -> int64_t { return P[k][t + r] - (t - r - 1 >= 0 ? P[k][t - r - 1] : 0); });
   }
 }
 }  // namespace

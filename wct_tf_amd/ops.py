@@ -9,7 +9,7 @@ on libwct_hip.so.  Same names, argument meaning and array conventions:
 and, without a counterpart in the reference,
   content_colors_np(stylized_rgb, content_rgb)  luminance-only colour preservation (Gatys et al. 2016), applied to a result
   guided_filter_np(stylized_rgb, content_rgb, radius, eps_q, guide)   guided smoothing of a result with its content as guide (He et al.)
-  guided_upsample_np(stylized, content_small, content_full, radius, eps_q)   a small result delivered at the full content's size (He & Sun)
+  guided_upsample_np(stylized, content_small, content_full, radius, eps_q, guide)   a small result delivered at the full content's size (He & Sun)
   motion_global_np(contents, search)   one global integer translation per frame of a clip, for guided_filter_time_np(positions=)
   texture_noise_np(h, w, seed, sample=0, smooth=False)   the seeded noise image a texture starts from (webcam.py:191-192 --noise)
 """
@@ -136,15 +136,16 @@ def guided_filter_np(stylized, content, radius, eps_q, guide='grey', ctx=None):
     return ctx.guided_filter(stylized, content, radius, eps_q, guide=guide)
 
 
-def guided_upsample_np(stylized, content_small, content_full, radius, eps_q, ctx=None):
+def guided_upsample_np(stylized, content_small, content_full, radius, eps_q, ctx=None, guide='grey'):
     """Guided upsampling of a small result (He, Sun, "Fast Guided Filter"): uint8 HxWx3 images -- the small stylized frame, the
     small content it was made from (never larger than the frame) and the full content (never smaller than the small one) -> uint8
     at the full content's size.  The guided filter's coefficients a, b of the small pair are averaged, interpolated and evaluated
     against the full content, so the frame gets every edge of the full content at full sharpness (the integer rule of
-    include/wct_hip.h, wct_guided_upsample).  radius 1 .. 64 and eps_q 1 .. 65025 as in guided_filter_np, in pixels of the small
-    frame.  Not served: the colour guide, down-scaling."""
+    include/wct_hip.h, wct_guided_upsample_guide).  radius 1 .. 64 and eps_q 1 .. 65025 as in guided_filter_np, in pixels of the
+    small frame.  guide: 'grey', or 'color' as in guided_filter_np: the three channels of the contents, which brings back an edge
+    between two colours of equal luminance.  Not served: down-scaling."""
     ctx = ctx or default_context()
-    return ctx.guided_upsample(stylized, content_small, content_full, radius, eps_q)
+    return ctx.guided_upsample(stylized, content_small, content_full, radius, eps_q, guide=guide)
 
 
 def guided_filter_time_np(stylized, contents, radius, eps_q, frames_t, ctx=None, positions=None):

@@ -17,7 +17,8 @@ takes their grey: it also keeps an edge between two colours of equal luminance, 
 bands.
 `--guided-upsample` (with `--guided-radius` and `--content-size`) stylizes small and delivers at the content's size: the content is
 resized on the device to `--content-size`, stylized there, and the filter's coefficients are interpolated and evaluated against the
-full content (He & Sun, "Fast Guided Filter"), which returns the content's edges at full sharpness."""
+full content (He & Sun, "Fast Guided Filter"), which returns the content's edges at full sharpness.  `--guided-upsample-guide color`
+does so against the content's three channels: edges between colours of equal luminance come back too."""
 import argparse
 import os
 import time
@@ -58,8 +59,12 @@ _FLAGS = [
                                        'resized on the device to --content-size, stylized there, and upsampled against the full '
                                        'content with the filter of --guided-radius / --guided-eps (in pixels of the working size); the '
                                        'output has the content\'s own size.  Needs --guided-radius > 0 and --content-size > 0; goes '
-                                       'with --content-colors; not with --guided-guide color, --swap5, --keep-colors, --interp-styles, '
-                                       '--mask-path, --alpha-map, --band-rows > 0 or --passes > 1')),
+                                       'with --content-colors and --guided-upsample-guide; not with --guided-guide color, --swap5, '
+                                       '--keep-colors, --interp-styles, --mask-path, --alpha-map, --band-rows > 0 or --passes > 1')),
+    (('--guided-upsample-guide',), dict(choices=['grey', 'color'], default=None,
+                                        help='the guide of --guided-upsample: grey (the default), the grey of the content, or color, '
+                                             'its three channels -- brings back edges between colours of equal luminance too.  Needs '
+                                             '--guided-upsample')),
     (('--passes',), dict(type=int, default=1, help='feed the result back in this many times')),
     (('-r', '--random'), dict(type=int, default=0, help='use this many randomly chosen styles of the style folder')),
     (('--alpha',), dict(type=float, default=1, help='style strength: blend of transformed and content features')),
@@ -180,6 +185,8 @@ def check_upsample_args(parser, args, extra=()):
     """--guided-upsample: what it needs and what it does not combine with (parser.error exits).  extra: further (option, given)
     pairs of the calling command line"""
     if not getattr(args, 'guided_upsample', False):
+        if getattr(args, 'guided_upsample_guide', None) is not None:
+            parser.error('--guided-upsample-guide needs --guided-upsample (it chooses the guide of that upsampling)')
         return
     if not args.guided_radius > 0:
         parser.error('--guided-upsample needs --guided-radius > 0 (the upsampling is that filter, in pixels of the working size)')
@@ -192,14 +199,17 @@ def check_upsample_args(parser, args, extra=()):
     for flag, given in on:
         if given:
             parser.error('--guided-upsample does not combine with %s: it takes one style, WCT or AdaIN, in one pass, under the grey '
-                         'guide' % flag)
+                         'guide%s' % (flag, ' (--guided-upsample-guide color chooses the guide of the upsampling)'
+                                      if flag == '--guided-guide color' else ''))
 
 
 def upsample_of(args):
-    """(short_side, radius, eps_q) of --guided-upsample with --content-size and --guided-radius / --guided-eps; None: off"""
+    """(short_side, radius, eps_q) of --guided-upsample with --content-size and --guided-radius / --guided-eps -- (short_side,
+    radius, eps_q, 'color') with --guided-upsample-guide color; None: off"""
     if not getattr(args, 'guided_upsample', False):
         return None
-    return (args.content_size,) + tuple(guided_of(args)[:2])
+    up = (args.content_size,) + tuple(guided_of(args)[:2])
+    return up + ('color',) if getattr(args, 'guided_upsample_guide', None) == 'color' else up
 
 
 def guided_of(args):

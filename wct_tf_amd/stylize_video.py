@@ -92,8 +92,12 @@ _FLAGS = [
                                        'is resized on the device to --content-size, stylized there, and upsampled against itself with '
                                        'the filter of --guided-radius / --guided-eps (in pixels of the working size); the output frames '
                                        'have the input\'s size.  Needs --guided-radius > 0 and --content-size > 0; goes with '
-                                       '--content-colors; not with --guided-guide color, --guided-frames, --swap5, --keep-colors, '
-                                       '--mask-path, --alpha-map, --warm-start or --passes > 1')),
+                                       '--content-colors and --guided-upsample-guide; not with --guided-guide color, --guided-frames, '
+                                       '--swap5, --keep-colors, --mask-path, --alpha-map, --warm-start or --passes > 1')),
+    (('--guided-upsample-guide',), dict(choices=['grey', 'color'], default=None,
+                                        help='the guide of --guided-upsample: grey (the default), the grey of the frame, or color, its '
+                                             'three channels -- brings back edges between colours of equal luminance too.  Needs '
+                                             '--guided-upsample')),
     (('--passes',), dict(type=int, default=1, help='feed the result back in this many times')),
     (('--device',), dict(default='/gpu:0', help='e.g. /gpu:0')),
     (('--alpha',), dict(type=float, default=1, help='style strength')),

@@ -286,8 +286,9 @@ class WCT(object):
            utils.resize_shape(H, W, short_side) (a content whose short side is short_side or less is worked on as it is), stylized
            there, and upsampled against the full content: the frame has the content's size and equals ops.guided_upsample_np(
            predict(the resized content), the resized content, content, radius, eps_q) bit for bit, content_colors_np against the
-           full content after it.  A style image is prepared for the call.  No swap5, warm, bands, strength or guided with it:
-           ValueError.'''
+           full content after it.  (short_side, radius, eps_q, 'color') upsamples under the colour guide (guide='color' of the op);
+           (short_side, radius, eps_q, 'grey') is the three-element form.  A style image is prepared for the call.  No swap5, warm,
+           bands, strength or guided with it: ValueError.'''
         guided = self._check_guided(guided)                                       # ValueError before any GPU call
         if guided_upsample is not None:
             return self._predict_upsampled(np.asarray(content)[None], style, guided_upsample, alpha, adain, content_colors, 1,
@@ -334,10 +335,12 @@ class WCT(object):
                                  wct_mode=self.wct_mode, swap5=bool(swap5), content_colors=content_colors, guided=guided)
 
     def _predict_upsampled(self, frames, style, guided_upsample, alpha, adain, content_colors, batch, others):
-        '''predict / predict_frames with guided_upsample=(short_side, radius, eps_q): uint8 full frames [F][H][W][3] -> [F][H][W][3].
+        '''predict / predict_frames with guided_upsample=(short_side, radius, eps_q[, guide]): uint8 full frames [F][H][W][3] -> [F][H][W][3].
            others: the options that do not go with it, by name -> whether they were given (ValueError before any GPU call)'''
         from .context import check_guided_upsample, upsample_work_size
-        side, r, e = check_guided_upsample(guided_upsample)
+        g = check_guided_upsample(guided_upsample)
+        side, r, e = g[:3]
+        guide = g[3] if len(g) == 4 else 'grey'
         for name, on in others.items():
             if on:
                 raise ValueError('%s is not served with guided_upsample: one prepared style, WCT or AdaIN, content_colors' % name)
@@ -353,7 +356,7 @@ class WCT(object):
             batch = max(1, min(32, int(batch)))
             return np.concatenate([self.sess.stylize_prepared_upsampled_batch(
                 frames[i:i + batch], own or style, self.relu_targets, work, r, e, alpha=alpha, adain=adain, wct_mode=self.wct_mode,
-                content_colors=content_colors) for i in range(0, len(frames), batch)], axis=0)
+                content_colors=content_colors, guide=guide) for i in range(0, len(frames), batch)], axis=0)
         finally:
             if own is not None:
                 own.close()
