@@ -460,9 +460,9 @@ int  wct_stylize_prepared_mix(wct_ctx* ctx, const uint8_t* content, int Hc, int 
  * WCT_STATUS_ARG with a message that names the argument, the ctx usable afterwards: H < hc or W < wc, h < hc or w < wc, a null
  *   pointer, B outside 1 .. 32, a radius or eps_q out of range, B * H * W * 3 >= 2^31, an overlap, and whatever wct_resize refuses
  *   (its LDS limit near H / hc = 42).
- * Not served: the temporal box under upsampling; mixes, masks and strength maps in the fused driver (the stand-alone op takes any
- * frame); down-scaling; ratios the resize refuses; full contents of 2^31 bytes and more.  (The colour guide under upsampling is
- * served by the wct_*_guide calls below.) */
+ * Not served: mixes, masks and strength maps in the fused driver (the stand-alone op takes any frame); down-scaling; ratios the
+ * resize refuses; full contents of 2^31 bytes and more.  (The colour guide under upsampling is served by the wct_*_guide calls
+ * below, the temporal box under upsampling by wct_guided_upsample_time.) */
 int  wct_guided_upsample(wct_ctx* ctx, const uint8_t* stylized, int h, int w, const uint8_t* content_small, int hc, int wc,
                          const uint8_t* content_full, int H, int W, int radius, int eps_q, uint8_t* out);
 int  wct_guided_upsample_batch_dev(wct_ctx* ctx, const uint8_t* stylized_dev, int h, int w, const uint8_t* content_small_dev, int hc,
@@ -496,8 +496,8 @@ int  wct_stylize_prepared_upsampled_batch_dev(wct_ctx* ctx, const uint8_t* conte
  * wct_content_colors bit for bit; WCT_FLAG_IMAGES_F32 only without a resize, as above.
  * WCT_STATUS_ARG: a guide that is neither of the two, with a message that names the argument; every refusal of the calls above,
  *   with the same words.
- * Not served: the temporal box under upsampling; mixes, masks and strength maps in the fused driver; down-scaling; full contents of
- * 2^31 bytes and more. */
+ * Not served: the colour guide along time (wct_guided_upsample_time takes the grey guide); mixes, masks and strength maps in the
+ * fused driver; down-scaling; full contents of 2^31 bytes and more. */
 int  wct_guided_upsample_guide(wct_ctx* ctx, const uint8_t* stylized, int h, int w, const uint8_t* content_small, int hc, int wc,
                                const uint8_t* content_full, int H, int W, int radius, int eps_q, int guide, uint8_t* out);
 int  wct_guided_upsample_guide_batch_dev(wct_ctx* ctx, const uint8_t* stylized_dev, int h, int w, const uint8_t* content_small_dev,
@@ -509,6 +509,45 @@ int  wct_stylize_prepared_upsampled_guide(wct_ctx* ctx, const uint8_t* content, 
 int  wct_stylize_prepared_upsampled_guide_batch_dev(wct_ctx* ctx, const uint8_t* content_dev, int H, int W, int B, int hc, int wc,
                                                     const wct_style* style, const int* levels, int n_levels, float alpha,
                                                     unsigned flags, int radius, int eps_q, int guide, uint8_t* out_dev);
+/* Temporal guided upsampling: guided upsampling above with the temporal box of wct_guided_filter_time, optionally along camera
+ * motion (wct_guided_filter_motion), where the coefficients are formed -- on the SMALL frames.  Video stylized at a small working
+ * size and delivered at its own size, without the flicker of the per-frame filter.  The rule, its bounds, identities and the
+ * derivation of its distance from the float64 filter: csrc/guided_up_time_rule.h.  A clip is F frames: s [F][h][w][3] the small
+ * stylized frames, c [F][hc][wc][3] the small contents, C [.][H][W][3] the full contents; T = frames_t is 0 .. 3; pos [F][2] int32
+ * (py, px) are positions in pixels of the small frame as in wct_guided_filter_motion, host memory, or NULL: equal positions.
+ *   1. a_q, b_q of (f, y, x): pass 1 of wct_guided_filter_motion on the small clip, unchanged -- the sums over the window of
+ *      (f, y, x), in each frame g of max(0, f - T) .. min(F - 1, f + T) the (2r + 1)^2 box centred at the shifted pixel, n its
+ *      pixels.  With pos NULL or equal positions that is pass 1 of wct_guided_filter_time.
+ *   2. am = rdiv(SA, n), bm = rdiv(SB, n): SA, SB the sums of a_q, b_q over the SAME 3-D window and n its count  (2^-12 units)
+ *   3. step 3 of wct_guided_upsample on frame f's own (am, bm) and frame f's full content, unchanged.  No other frame is read at
+ *      full size.
+ * |SA| < 33025 2^18 and |SB| < 2.3e12 (doubled plus n below 2^63), |am| < 2^18 and |bm| < 6.8e7 as in wct_guided_upsample: every bound
+ * of step 3 holds unchanged, and so does the distance from the float64 filter with the same window, 0.5 + 256 2^-12 + D 2^-8.
+ * T = 0, or F = 1 at any T, gives wct_guided_upsample_batch_dev's bytes.  A constant clip comes back as that constant.  At H = hc,
+ * W = wc the result is within 1 grey level of wct_guided_filter_time / _motion.  The parameters are those of
+ * wct_guided_filter_time: r <= 64 / 51 / 40 / 33 at T = 0 / 1 / 2 / 3.
+ * wct_guided_upsample_time: host pointers, blocking, the whole clip, F = 1 .. 32; content_full and out are [F][H][W][3].
+ * wct_guided_upsample_time_batch_dev: device frames, host positions (read before the call returns); F = 1 .. 32 resident SMALL
+ *   frames, 0 <= f0 < f1 <= F; content_full_dev [f1 - f0][H][W][3] holds the full contents of the delivered frames f0 .. f1 - 1 ONLY,
+ *   out_dev [f1 - f0][H][W][3] the delivered frames.  Three launches (pass 1 of the temporal or motion filter over frames
+ *   max(0, f0 - T) .. min(F, f1 + T) - 1, the window means, the full-size pass of wct_guided_upsample), asynchronous on the ctx
+ *   stream; out_dev must not overlap an input.  24 B per small pixel of the F frames and 24 B per small pixel of the delivered
+ *   frames live in the workspace of wct_guided_filter.
+ *   A frame depends on the small frames up to 2T away and on ONE full content, its own: a caller that wants the bytes of a longer
+ *   video gives 2T real SMALL frames of halo on each side of [f0, f1), except at the video's own ends.  A halo of T does not.
+ * WCT_STATUS_ARG with a message that names what was wrong, the ctx usable afterwards: a null image pointer, what
+ *   wct_guided_filter_time refuses on the small clip (F, the range, h < hc or w < wc, T, the radius for that T, eps_q,
+ *   F * h * w * 3 >= 2^31), what wct_guided_upsample refuses (H < hc or W < wc, (f1 - f0) * H * W * 3 >= 2^31), a step of pos above
+ *   16 on either axis, an overlap.
+ * Not served: the colour guide along time; a fused driver that keeps the full contents resident between the resize and the
+ * upsampling; mixes, masks and strength maps under upsampling; T above 3; per-block, sub-pixel or non-translational motion; fp32
+ * contents. */
+int  wct_guided_upsample_time(wct_ctx* ctx, const uint8_t* stylized, int h, int w, const uint8_t* content_small, int hc, int wc,
+                              const uint8_t* content_full, int H, int W, int F, int radius, int eps_q, int frames_t,
+                              const int32_t* pos, uint8_t* out);
+int  wct_guided_upsample_time_batch_dev(wct_ctx* ctx, const uint8_t* stylized_dev, int h, int w, const uint8_t* content_small_dev,
+                                        int hc, int wc, const uint8_t* content_full_dev, int H, int W, int F, int radius, int eps_q,
+                                        int frames_t, const int32_t* pos, int f0, int f1, uint8_t* out_dev);
 /* Spatial control on prepared styles, and on a batch of frames with one label map each (a video with a segmentation per frame).
  * wct_stylize_prepared_masked = wct_stylize_masked's frame, bit for bit, for the same content, mask, levels, alpha and flags and
  *   the images the K handles were prepared from: host pointers, blocking, like wct_stylize_prepared.  It is the B = 1 case of

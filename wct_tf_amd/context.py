@@ -221,6 +221,42 @@ def _upsample_images(stylized, content_small, content_full, ndim):
     return s, c, f
 
 
+def _upsample_time_full(contents_full, frames, contents_small):
+    """The refusals of the full contents of `frames` delivered frames, before any library call -> contiguous uint8 [frames][H][W][3]"""
+    f = np.asarray(contents_full)
+    if f.dtype != np.uint8:
+        raise ValueError('guided_upsample_time takes uint8 images, contents_full is %s' % f.dtype)
+    if f.ndim != 4 or f.shape[-1] != 3 or f.size == 0:
+        raise ValueError('guided_upsample_time takes [F][H][W][3] images, contents_full has shape %s' % (f.shape,))
+    if f.shape[0] != frames:
+        raise ValueError('guided_upsample_time takes one full content per delivered frame, got %d for %d frames' % (f.shape[0], frames))
+    c = contents_small
+    if f.shape[1] < c.shape[1] or f.shape[2] < c.shape[2]:
+        raise ValueError('contents_full %dx%d is smaller than contents_small %dx%d: guided_upsample_time does not scale down'
+                         % (f.shape[1], f.shape[2], c.shape[1], c.shape[2]))
+    return u8(f)
+
+
+def _upsample_time_clip(stylized, contents_small, contents_full):
+    """The refusals of a clip of small frames, its small and its full contents, before any library call: three uint8 arrays
+    [F][.][.][3] with the same F >= 1, the small frame at least as large as the small content, the full content at least as large
+    as the small one -> the three as contiguous uint8"""
+    try:
+        s, c = _guided_clip(stylized, contents_small)
+    except ValueError as e:
+        raise ValueError(str(e).replace('guided_filter_time', 'guided_upsample_time'))
+    return s, c, _upsample_time_full(contents_full, s.shape[0], c)
+
+
+def upsample_time_chunk(hf, wf, frames_t):
+    """The delivered frames of one chunk of guided_upsample_time_clip at full size hf x wf: 32 - 4 frames_t (the resident clip
+    with its halos is at most 32 small frames), lowered where that many full frames would reach 2^31 bytes"""
+    per = int(hf) * int(wf) * 3
+    if per >= 1 << 31:
+        raise ValueError('a full content of %dx%dx3 passes 2^31 bytes' % (hf, wf))
+    return max(1, min(_lib.BATCH_MAX - 4 * int(frames_t), ((1 << 31) - 1) // per))
+
+
 def check_work_size(work_size, h, w):
     """The working size (hc, wc) of a stylize_prepared_upsampled call on h x w contents: two positive integers, neither above the
     content's.  -> (hc, wc)"""
@@ -1176,6 +1212,77 @@ class Context(object):
                 ds, s.shape[1], s.shape[2], dc, c.shape[1], c.shape[2], s.shape[0], r, e, t, pos, f0, f1, do))
         return self._host_batch([s, c], out, enqueue=lambda ds, dc, do: self.guided_filter_time_batch_dev(
             ds, s.shape[1], s.shape[2], dc, c.shape[1], c.shape[2], s.shape[0], r, e, t, f0, f1, do))
+
+    # ---- temporal guided upsampling: the box across frames, delivered at full size -----------
+    def guided_upsample_time(self, stylized_u8, contents_small_u8, contents_full_u8, radius, eps_q, frames_t, positions=None):
+        """Temporal guided upsampling of a clip (wct_guided_upsample_time): small stylized frames [F][h][w][3], the small contents
+        [F][hc][wc][3] they were made from and the full contents [F][H][W][3], all uint8, F <= 32 -> uint8 [F][H][W][3]:
+        guided_upsample with its coefficients and their means formed over the frames_t (0 .. 3) frames on each side of a frame as
+        guided_filter_time forms them; frame f is then delivered against its own full content.  frames_t = 0, or one frame, is
+        guided_upsample_batch bit for bit.  The radius is at most 64 / 51 / 40 / 33 at frames_t 0 / 1 / 2 / 3.  The grey guide.
+        positions: int [F][2] (py, px) in pixels of the SMALL frame, as in guided_filter_time; None: no shift.  A longer clip:
+        guided_upsample_time_clip."""
+        s, c, f = _upsample_time_clip(stylized_u8, contents_small_u8, contents_full_u8)
+        r, e, t = check_guided_time(radius, eps_q, frames_t)
+        pos = None if positions is None else check_guided_motion(positions, s.shape[0])
+        if not 1 <= s.shape[0] <= _lib.BATCH_MAX:
+            raise ValueError('a clip takes 1 .. %d frames in one call, got %d (guided_upsample_time_clip takes any length)'
+                             % (_lib.BATCH_MAX, s.shape[0]))
+        out = np.empty_like(f)
+        check(self.lib.wct_guided_upsample_time(self.h, s.ctypes.data_as(_lib._U8), s.shape[1], s.shape[2], c.ctypes.data_as(_lib._U8),
+                                                c.shape[1], c.shape[2], f.ctypes.data_as(_lib._U8), f.shape[1], f.shape[2], s.shape[0],
+                                                r, e, t, None if pos is None else pos.ctypes.data_as(_lib._I),
+                                                out.ctypes.data_as(_lib._U8)))
+        return out
+
+    def guided_upsample_time_batch_dev(self, stylized_dev, h, w, content_small_dev, hc, wc, content_full_dev, hf, wf, frames, radius, eps_q,
+                                       frames_t, f0, f1, out_dev, positions=None):
+        """Frames f0 .. f1 - 1 of the clip of `frames` SMALL frames resident in HBM, delivered at full size
+        (wct_guided_upsample_time_batch_dev): content_full_dev [f1 - f0][hf][wf][3] holds the full contents of the delivered frames
+        only -> out_dev [f1 - f0][hf][wf][3].  Asynchronous; out_dev overlaps no input.  positions: int [frames][2] (host) or None.
+        The bytes of a longer video need 2 frames_t real small frames of halo on each side of [f0, f1)."""
+        r, e, t = check_guided_time(radius, eps_q, frames_t)
+        if not (1 <= int(frames) <= _lib.BATCH_MAX and 0 <= int(f0) < int(f1) <= int(frames)):
+            raise ValueError('a clip takes 1 .. %d frames and a range 0 <= f0 < f1 <= frames, got %d frames and [%d, %d)'
+                             % (_lib.BATCH_MAX, frames, f0, f1))
+        pos = None if positions is None else check_guided_motion(positions, frames)
+        check(self.lib.wct_guided_upsample_time_batch_dev(self.h, stylized_dev, int(h), int(w), content_small_dev, int(hc), int(wc),
+                                                          content_full_dev, int(hf), int(wf), int(frames), r, e, t,
+                                                          None if pos is None else pos.ctypes.data_as(_lib._I), int(f0), int(f1), out_dev))
+
+    def guided_upsample_time_range(self, stylized_u8, contents_small_u8, contents_full_u8, radius, eps_q, frames_t, f0, f1, out=None,
+                                   positions=None):
+        """Host arrays in, host array out: frames f0 .. f1 - 1 of the clip of small frames [F][h][w][3] with small contents
+        [F][hc][wc][3] (F <= 32), delivered against contents_full [f1 - f0][H][W][3], the full contents of those frames only ->
+        uint8 [f1 - f0][H][W][3]"""
+        s, c = _guided_clip(stylized_u8, contents_small_u8)
+        r, e, t = check_guided_time(radius, eps_q, frames_t)
+        pos = None if positions is None else check_guided_motion(positions, s.shape[0])
+        if not (1 <= s.shape[0] <= _lib.BATCH_MAX and 0 <= f0 < f1 <= s.shape[0]):
+            raise ValueError('a clip takes 1 .. %d frames and a range 0 <= f0 < f1 <= frames, got %d frames and [%d, %d)'
+                             % (_lib.BATCH_MAX, s.shape[0], f0, f1))
+        f = _upsample_time_full(contents_full_u8, f1 - f0, c)
+        out = np.empty_like(f) if out is None else out
+        return self._host_batch([s, c, f], out, enqueue=lambda ds, dc, df, do: self.guided_upsample_time_batch_dev(
+            ds, s.shape[1], s.shape[2], dc, c.shape[1], c.shape[2], df, f.shape[1], f.shape[2], s.shape[0], r, e, t, f0, f1, do,
+            positions=pos))
+
+    def guided_upsample_time_clip(self, stylized_u8, contents_small_u8, contents_full_u8, radius, eps_q, frames_t, positions=None):
+        """guided_upsample_time for a clip of any length: chunks of at most 32 - 4 frames_t delivered frames -- fewer where that many
+        full frames would reach 2^31 bytes --, each uploaded with 2 frames_t SMALL frames of halo on each side (fewer at the clip's
+        ends) and the full contents of its own frames only.  The whole clip's bytes, whatever the chunking: a frame depends on no
+        small frame further than 2 frames_t away and on its own full content."""
+        s, c, f = _upsample_time_clip(stylized_u8, contents_small_u8, contents_full_u8)
+        r, e, t = check_guided_time(radius, eps_q, frames_t)
+        pos = None if positions is None else check_guided_motion(positions, s.shape[0])
+        step = upsample_time_chunk(f.shape[1], f.shape[2], t)
+        n, out = s.shape[0], np.empty_like(f)
+        for f0 in range(0, n, step):
+            f1 = min(n, f0 + step)
+            g0, g1 = max(0, f0 - 2 * t), min(n, f1 + 2 * t)
+            self.guided_upsample_time_range(s[g0:g1], c[g0:g1], f[f0:f1], r, e, t, f0 - g0, f1 - g0, out=out[f0:f1],
+                                            positions=None if pos is None else pos[g0:g1])
+        return out
 
     # ---- on-device resize: Pillow's bilinear bytes ------------------------------------------
     def resize(self, img_u8, size):

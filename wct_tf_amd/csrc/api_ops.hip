@@ -925,6 +925,59 @@ extern "C" int wct_guided_filter_motion(wct_ctx* c, const uint8_t* stylized, int
   return fetch(c, out, ds, (size_t)F * Ho * Wo * 3);
 }
 
+// Temporal guided upsampling, op level (csrc/guided_up_time.hip): frames f0 .. f1 - 1 of a clip of F resident small frames, delivered
+// against their full contents; the coefficient map of the clip and the means of the delivered frames in the workspace of the
+// guided ops
+static int guided_upsample_time_checks(const void* stylized, const void* content_small, const void* content_full, const void* out, int F,
+                                       int h, int w, int hc, int wc, int H, int W, int radius, int eps_q, int frames_t, int f0, int f1,
+                                       const int32_t* pos) {
+  if (!stylized) { wct_set_error("guided upsample along time: stylized is a null pointer"); return WCT_ERR_ARG; }
+  if (!content_small) { wct_set_error("guided upsample along time: content_small is a null pointer"); return WCT_ERR_ARG; }
+  if (!content_full) { wct_set_error("guided upsample along time: content_full is a null pointer"); return WCT_ERR_ARG; }
+  if (!out) { wct_set_error("guided upsample along time: out is a null pointer"); return WCT_ERR_ARG; }
+  return guided_up_time_check(F, h, w, hc, wc, H, W, radius, eps_q, frames_t, f0, f1, pos);
+}
+
+extern "C" int wct_guided_upsample_time_batch_dev(wct_ctx* c, const uint8_t* stylized, int h, int w, const uint8_t* content_small, int hc,
+                                                  int wc, const uint8_t* content_full, int H, int W, int F, int radius, int eps_q,
+                                                  int frames_t, const int32_t* pos, int f0, int f1, uint8_t* out) {
+  ARG_CHECK(c != nullptr);
+  TRY(guided_upsample_time_checks(stylized, content_small, content_full, out, F, h, w, hc, wc, H, W, radius, eps_q, frames_t, f0, f1, pos));
+  const size_t nout = (size_t)(f1 - f0) * H * W * 3;
+  if (bytes_overlap(out, nout, stylized, (size_t)F * h * w * 3) || bytes_overlap(out, nout, content_small, (size_t)F * hc * wc * 3) ||
+      bytes_overlap(out, nout, content_full, nout)) {
+    wct_set_error("guided upsample along time: out overlaps an input (a full pixel reads small pixels that other blocks have long left)");
+    return WCT_ERR_ARG;
+  }
+  HIP_TRY(hipSetDevice(c->device));
+  TRY(ensure(c, c->guided_ab, guided_up_time_workspace_bytes(F, h, w, f0, f1)));
+  // per small pixel of the n1 frames of pass 1: s and c read twice in each frame of the window, the map written; of the n2 delivered
+  // frames: the map read twice in each frame of the window, the means written; per full pixel the content read and the frame
+  // written, the means read through the cache
+  const int n1 = (f1 + frames_t > F ? F : f1 + frames_t) - (f0 - frames_t < 0 ? 0 : f0 - frames_t), n2 = f1 - f0, win = 2 * frames_t + 1;
+  ProfScope ps(c, 7, 0, (double)h * w * (n1 * (win * 2 * 6 + 24.0) + n2 * (win * 2 * 24.0 + 24.0)) + (double)n2 * H * W * 6 +
+                            (double)n2 * hc * wc * 24.0);
+  return launch_guided_upsample_time(stylized, content_small, content_full, F, h, w, hc, wc, H, W, radius, eps_q, frames_t, pos, f0, f1,
+                                     c->guided_ab.p, out, c->stream);
+}
+
+extern "C" int wct_guided_upsample_time(wct_ctx* c, const uint8_t* stylized, int h, int w, const uint8_t* content_small, int hc, int wc,
+                                        const uint8_t* content_full, int H, int W, int F, int radius, int eps_q, int frames_t,
+                                        const int32_t* pos, uint8_t* out) {
+  ARG_CHECK(c != nullptr);
+  TRY(guided_upsample_time_checks(stylized, content_small, content_full, out, F, h, w, hc, wc, H, W, radius, eps_q, frames_t, 0, F,
+                                  pos));                                                      // (before the staging buffers are sized)
+  HIP_TRY(hipSetDevice(c->device));
+  void *ds, *dc, *dC;
+  TRY(stage_in(c, 0, stylized, (size_t)F * h * w * 3, &ds));
+  TRY(stage_in(c, 1, content_small, (size_t)F * hc * wc * 3, &dc));
+  TRY(stage_in(c, 2, content_full, (size_t)F * H * W * 3, &dC));
+  TRY(ensure(c, c->stage[3], (size_t)F * H * W * 3));
+  TRY(wct_guided_upsample_time_batch_dev(c, (uint8_t*)ds, h, w, (uint8_t*)dc, hc, wc, (uint8_t*)dC, H, W, F, radius, eps_q, frames_t, pos,
+                                         0, F, (uint8_t*)c->stage[3].p));
+  return fetch(c, out, c->stage[3].p, (size_t)F * H * W * 3);
+}
+
 // Seeded noise images for texture synthesis, op level (csrc/noise.hip): the refusals both calls share
 static int texture_noise_checks(int H, int W, int B, const void* out) {
   if (!out) { wct_set_error("texture noise: null output pointer"); return WCT_ERR_ARG; }

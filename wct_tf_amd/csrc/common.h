@@ -384,6 +384,10 @@ int guided_up_check(int B, int h, int w, int hc, int wc, int H, int W, int radiu
 size_t guided_up_workspace_bytes(int B, int h, int w);
 int launch_guided_upsample(const uint8_t* stylized, const void* content_small, const void* content_full, int content_f32, int B, int h,
                            int w, int hc, int wc, int H, int W, int radius, int eps_q, void* workspace, uint8_t* out, hipStream_t s);
+// launch_guided_up_full: the full-size pass alone -- mean [B][h][w][3][2] int32 (8-byte aligned) + content_full [B][H][W][3] uint8 ->
+// out [B][H][W][3]; the caller has checked the arguments (guided_up_check)
+int launch_guided_up_full(const int32_t* mean, const uint8_t* content_full, uint8_t* out, int B, int H, int W, int h, int w, int hc, int wc,
+                          hipStream_t s);
 // ---- guided_color.hip: the two launches of the colour guide; launch_guided_filter has checked the arguments
 int launch_guided_color(const uint8_t* stylized, const void* content, int content_f32, int B, int Ho, int Wo, int Hc, int Wc, int radius,
                         int eps_q, void* workspace, uint8_t* out, hipStream_t s);
@@ -411,6 +415,9 @@ int guided_time_check(int F, int Ho, int Wo, int Hc, int Wc, int radius, int eps
 int guided_time_max_radius(int frames_t);                  // 64 / 51 / 40 / 33 at 0 .. 3 frames on each side, else 0
 int launch_guided_time(const uint8_t* stylized, const void* content, int content_f32, int F, int Ho, int Wo, int Hc, int Wc, int radius,
                        int eps_q, int frames_t, int f0, int f1, void* workspace, uint8_t* out, hipStream_t s);
+// launch_guided_time_ab: pass 1 alone on uint8 contents -- ab [F][Ho][Wo][3][2] int32, the frames max(0, f0 - T) .. min(F, f1 + T) - 1
+int launch_guided_time_ab(const uint8_t* stylized, const uint8_t* content, int F, int Ho, int Wo, int Hc, int Wc, int radius, int eps_q,
+                          int frames_t, int f0, int f1, int32_t* ab, hipStream_t s);
 // ---- guided_motion.hip ----------------------------------------------------
 // Temporal guided smoothing along camera motion (guided_motion_rule.h): launch_guided_time with the window of every neighbouring
 // frame shifted by the difference of the positions pos [F][2] (py, px), host memory, read before the call returns.  Same clip,
@@ -419,6 +426,9 @@ int launch_guided_time(const uint8_t* stylized, const void* content, int content
 int guided_motion_check(int F, int Ho, int Wo, int Hc, int Wc, int radius, int eps_q, int frames_t, int f0, int f1, const int32_t* pos);
 int launch_guided_motion(const uint8_t* stylized, const uint8_t* content, int F, int Ho, int Wo, int Hc, int Wc, int radius, int eps_q,
                          int frames_t, const int32_t* pos, int f0, int f1, void* workspace, uint8_t* out, hipStream_t s);
+// launch_guided_motion_ab: pass 1 alone -- ab as launch_guided_time_ab writes it, under the positions
+int launch_guided_motion_ab(const uint8_t* stylized, const uint8_t* content, int F, int Ho, int Wo, int Hc, int Wc, int radius, int eps_q,
+                            int frames_t, const int32_t* pos, int f0, int f1, int32_t* ab, hipStream_t s);
 // The estimator of those positions: one step per pair of consecutive contents [F][Hc][Wc][3] on the device, by exhaustive search
 // over |dy|, |dx| <= range.  Three launches (none for F = 1); *steps = where in the workspace the F - 1 steps (dy, dx) int32 will
 // be.  workspace: motion_workspace_bytes bytes.  motion_check: F outside 1 .. 32, a range outside 1 .. 16, Hc or Wc < 4 range, or
@@ -426,6 +436,21 @@ int launch_guided_motion(const uint8_t* stylized, const uint8_t* content, int F,
 int motion_check(int F, int Hc, int Wc, int range);
 size_t motion_workspace_bytes(int F, int Hc, int Wc, int range);
 int launch_motion_global(const uint8_t* content, int F, int Hc, int Wc, int range, void* workspace, const int32_t** steps, hipStream_t s);
+// ---- guided_up_time.hip ---------------------------------------------------
+// Temporal guided upsampling (guided_up_time_rule.h): out [f1 - f0][H][W][3] = frames f0 .. f1 - 1 of the clip of F small stylized
+// frames s [F][h][w][3] with small contents c [F][hc][wc][3], the coefficients formed over the 3-D window of frames_t frames on
+// each side -- shifted by the differences of pos [F][2] (host memory, read before the call returns) unless pos is null --,
+// delivered against content_full [f1 - f0][H][W][3], the full contents of the delivered frames only.  Three launches: pass 1 of
+// the temporal (or motion) filter, the window means, the full-size pass of guided_up.hip.  workspace:
+// guided_up_time_workspace_bytes bytes (24 B per small pixel of the F frames and of the delivered ones, 8-byte aligned); out
+// overlaps no input.  guided_up_time_check: what guided_time_check refuses on the small clip, what guided_up_check refuses on
+// f1 - f0 delivered frames, or a step of pos above 16 on either axis.
+int guided_up_time_check(int F, int h, int w, int hc, int wc, int H, int W, int radius, int eps_q, int frames_t, int f0, int f1,
+                         const int32_t* pos);
+size_t guided_up_time_workspace_bytes(int F, int h, int w, int f0, int f1);
+int launch_guided_upsample_time(const uint8_t* stylized, const uint8_t* content_small, const uint8_t* content_full, int F, int h, int w,
+                                int hc, int wc, int H, int W, int radius, int eps_q, int frames_t, const int32_t* pos, int f0, int f1,
+                                void* workspace, uint8_t* out, hipStream_t s);
 
 // ---- noise.hip ------------------------------------------------------------
 // Seeded noise for texture synthesis (noise_rule.h): out [B][H][W][3] uint8 on the device, image b = sample first_sample + b of

@@ -286,6 +286,22 @@ int launch_guided_motion(const uint8_t* stylized, const uint8_t* content, int F,
   return WCT_OK;
 }
 
+int launch_guided_motion_ab(const uint8_t* stylized, const uint8_t* content, int F, int Ho, int Wo, int Hc, int Wc, int radius, int eps_q,
+                            int frames_t, const int32_t* pos, int f0, int f1, int32_t* ab, hipStream_t st) {
+  ARG_CHECK(stylized && content && ab);
+  int rc = guided_motion_check(F, Ho, Wo, Hc, Wc, radius, eps_q, frames_t, f0, f1, pos);
+  if (rc) return rc;
+  MotionPos mp;
+  for (int f = 0; f < 32; ++f)
+    for (int k = 0; k < 2; ++k) mp.p[f][k] = f < F ? (int32_t)((int64_t)pos[2 * f + k] - pos[k]) : 0;
+  const int strips = cdiv(Wo, NT - 2 * radius), segs = cdiv(Ho, SEG);
+  const int g0 = f0 - frames_t < 0 ? 0 : f0 - frames_t, g1 = f1 + frames_t > F ? F : f1 + frames_t;
+  hipLaunchKernelGGL(guided_motion_ab_kernel, dim3((unsigned)(g1 - g0) * strips * segs), dim3(NT), 0, st, stylized, content, ab, mp, F,
+                     frames_t, g0, Ho, Wo, Hc, Wc, radius, eps_q, strips, segs);
+  HIP_TRY(hipGetLastError());
+  return WCT_OK;
+}
+
 int motion_check(int F, int Hc, int Wc, int range) {
   if (F < 1 || F > 32) { wct_set_error("global motion: a clip of F = %d frames, must be 1 .. 32", F); return WCT_ERR_ARG; }
   if (range < 1 || range > WCT_MOTION_MAX_RANGE) {

@@ -151,6 +151,19 @@ int guided_time_check(int F, int Ho, int Wo, int Hc, int Wc, int radius, int eps
 
 int guided_time_max_radius(int frames_t) { return wct_guided_time_radius_limit(frames_t); }
 
+int launch_guided_time_ab(const uint8_t* stylized, const uint8_t* content, int F, int Ho, int Wo, int Hc, int Wc, int radius, int eps_q,
+                          int frames_t, int f0, int f1, int32_t* ab, hipStream_t s) {
+  ARG_CHECK(stylized && content && ab);
+  int rc = guided_time_check(F, Ho, Wo, Hc, Wc, radius, eps_q, frames_t, f0, f1);
+  if (rc) return rc;
+  const int strips = cdiv(Wo, NT - 2 * radius), segs = cdiv(Ho, SEG);
+  const int g0 = f0 - frames_t < 0 ? 0 : f0 - frames_t, g1 = f1 + frames_t > F ? F : f1 + frames_t;
+  hipLaunchKernelGGL((guided_time_ab_kernel<uint8_t>), dim3((unsigned)(g1 - g0) * strips * segs), dim3(NT), 0, s, stylized, content, ab, F,
+                     frames_t, g0, Ho, Wo, Hc, Wc, radius, eps_q, strips, segs);
+  HIP_TRY(hipGetLastError());
+  return WCT_OK;
+}
+
 int launch_guided_time(const uint8_t* stylized, const void* content, int content_f32, int F, int Ho, int Wo, int Hc, int Wc, int radius,
                        int eps_q, int frames_t, int f0, int f1, void* workspace, uint8_t* out, hipStream_t s) {
   ARG_CHECK(stylized && content && workspace && out);

@@ -173,6 +173,19 @@ void launch_full(const int32_t* mean, const CT* C, uint8_t* out, int B, int H, i
                      hc, wc, tiles_x, tiles_y);
 }
 
+// the full-size launch over mean [B][h][w][3][2] and C [B][H][W][3], the variant chosen by W, the bases and the axes
+template <typename CT>
+int select_full(const int32_t* mean, const CT* C, uint8_t* out, int B, int H, int W, int h, int w, int hc, int wc, hipStream_t st) {
+  const bool vec = W % 4 == 0 && (uintptr_t)C % 4 == 0 && (uintptr_t)out % 4 == 0;
+  const bool a32 = wct_guided_up_axis32_ok(W, wc) && wct_guided_up_axis32_ok(H, hc);
+  if (vec && a32) launch_full<CT, true, true>(mean, C, out, B, H, W, h, w, hc, wc, st);
+  else if (vec) launch_full<CT, true, false>(mean, C, out, B, H, W, h, w, hc, wc, st);
+  else if (a32) launch_full<CT, false, true>(mean, C, out, B, H, W, h, w, hc, wc, st);
+  else launch_full<CT, false, false>(mean, C, out, B, H, W, h, w, hc, wc, st);
+  HIP_TRY(hipGetLastError());
+  return WCT_OK;
+}
+
 template <typename CT>
 int launch(const uint8_t* s, const CT* c, const CT* C, int B, int h, int w, int hc, int wc, int H, int W, int r, int eps_q, void* workspace,
            uint8_t* out, hipStream_t st) {
@@ -184,16 +197,15 @@ int launch(const uint8_t* s, const CT* c, const CT* C, int B, int h, int w, int 
   hipLaunchKernelGGL(guided_up_mean_kernel, dim3((unsigned)B * strips * segs), dim3(NT), 0, st, (const int32_t*)ab, mean, h, w, r, strips,
                      segs);
   HIP_TRY(hipGetLastError());
-  const bool vec = W % 4 == 0 && (uintptr_t)C % 4 == 0 && (uintptr_t)out % 4 == 0;
-  const bool a32 = wct_guided_up_axis32_ok(W, wc) && wct_guided_up_axis32_ok(H, hc);
-  if (vec && a32) launch_full<CT, true, true>(mean, C, out, B, H, W, h, w, hc, wc, st);
-  else if (vec) launch_full<CT, true, false>(mean, C, out, B, H, W, h, w, hc, wc, st);
-  else if (a32) launch_full<CT, false, true>(mean, C, out, B, H, W, h, w, hc, wc, st);
-  else launch_full<CT, false, false>(mean, C, out, B, H, W, h, w, hc, wc, st);
-  HIP_TRY(hipGetLastError());
-  return WCT_OK;
+  return select_full(mean, C, out, B, H, W, h, w, hc, wc, st);
 }
 }  // namespace
+
+int launch_guided_up_full(const int32_t* mean, const uint8_t* content_full, uint8_t* out, int B, int H, int W, int h, int w, int hc, int wc,
+                          hipStream_t s) {
+  ARG_CHECK(mean && content_full && out);
+  return select_full(mean, content_full, out, B, H, W, h, w, hc, wc, s);
+}
 
 int guided_up_check(int B, int h, int w, int hc, int wc, int H, int W, int radius, int eps_q) {
   if (B < 1 || B > 32) { wct_set_error("guided upsample: B = %d frames, must be 1 .. 32", B); return WCT_ERR_ARG; }

@@ -28,8 +28,8 @@
 //     value by at most e times the spread of its four corners: 2 * 2^-9 D = D 2^-8.
 // (8-bit weights are kept: on smooth coefficients D is a fraction of a grey level, and the product w_k (am_k I + bm_k) then stays
 // where the 2^-12 coefficient roundings already are; finer weights buy nothing the 0.5 of the last rounding does not hide.)
-// Left out: the temporal box under upsampling, down-scaling (H < hc or W < wc), full contents of 2^31 bytes and more.  (The colour
-// guide under upsampling is guided_up_color_rule.h, on this header's axis taps and final shift.)
+// Left out: down-scaling (H < hc or W < wc), full contents of 2^31 bytes and more.  (The colour guide under upsampling is
+// guided_up_color_rule.h, on this header's axis taps and final shift; the temporal box under upsampling is guided_up_time_rule.h.)
 #pragma once
 #include "guided_rule.h"
 

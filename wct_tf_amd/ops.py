@@ -10,6 +10,7 @@ and, without a counterpart in the reference,
   content_colors_np(stylized_rgb, content_rgb)  luminance-only colour preservation (Gatys et al. 2016), applied to a result
   guided_filter_np(stylized_rgb, content_rgb, radius, eps_q, guide)   guided smoothing of a result with its content as guide (He et al.)
   guided_upsample_np(stylized, content_small, content_full, radius, eps_q, guide)   a small result delivered at the full content's size (He & Sun)
+  guided_upsample_time_np(stylized, contents_small, contents_full, radius, eps_q, frames_t, positions)   a small clip delivered at full size, the box across frames (NumPy, on the host)
   motion_global_np(contents, search)   one global integer translation per frame of a clip, for guided_filter_time_np(positions=)
   texture_noise_np(h, w, seed, sample=0, smooth=False)   the seeded noise image a texture starts from (webcam.py:191-192 --noise)
 """
@@ -146,6 +147,66 @@ def guided_upsample_np(stylized, content_small, content_full, radius, eps_q, ctx
     between two colours of equal luminance.  Not served: down-scaling."""
     ctx = ctx or default_context()
     return ctx.guided_upsample(stylized, content_small, content_full, radius, eps_q, guide=guide)
+
+
+def guided_upsample_time_np(stylized, contents_small, contents_full, radius, eps_q, frames_t, positions=None):
+    """Temporal guided upsampling of a small stylized clip, the rule of include/wct_hip.h (wct_guided_upsample_time) written out in
+    NumPy int64 -- it runs on the host, without the library, and gives the bytes of Context.guided_upsample_time_clip: uint8 small
+    frames [F][h][w][3], the small contents [F][hc][wc][3] they were made from and the full contents [F][H][W][3] of any F -> uint8
+    [F][H][W][3].  The coefficients of guided_upsample_np and their means are formed over the (2 radius + 1)^2 box in each of the
+    frames_t (0 .. 3) frames on each side of a frame, as guided_filter_time_np forms them, so flat static areas stop flickering;
+    frame f is then interpolated and evaluated against its own full content, which returns every edge at full sharpness.
+    frames_t = 0, or one frame, is guided_upsample_np per frame.  radius 1 .. 64 / 51 / 40 / 33 at frames_t 0 / 1 / 2 / 3, in pixels
+    of the small frame.  positions: int [F][2] (py, px) in pixels of the small frame, as motion_global_np estimates them on the
+    small contents; None: no shift.  The grey guide only.  Not served: the colour guide along time, down-scaling."""
+    from .context import _upsample_time_clip, check_guided_motion, check_guided_time
+    s, c, full = _upsample_time_clip(stylized, contents_small, contents_full)
+    r, e, t = check_guided_time(radius, eps_q, frames_t)
+    nf, h, w = s.shape[:3]
+    hc, wc = c.shape[1:3]
+    hf, wf = full.shape[1:3]
+    pos = (np.zeros((nf, 2), np.int32) if positions is None else check_guided_motion(positions, nf)).astype(np.int64)
+    rdiv = lambda a, b: (2 * a + b) // (2 * b)
+    luma = lambda img: (img.astype(np.int64) @ np.array([77, 150, 29], np.int64) + 128) >> 8
+
+    def box3(a):                                      # [F][h][w] -> the sums over the shifted boxes of the frames of the time window
+        p = np.zeros((nf, h + 1, w + 1), np.int64)
+        p[:, 1:, 1:] = a.cumsum(1).cumsum(2)
+        out = np.zeros_like(a)
+        for f in range(nf):
+            for g in range(max(0, f - t), min(nf - 1, f + t) + 1):
+                cy, cx = np.arange(h) + pos[g, 0] - pos[f, 0], np.arange(w) + pos[g, 1] - pos[f, 1]
+                y0, x0 = np.clip(cy - r, 0, h), np.clip(cx - r, 0, w)
+                y1, x1 = np.maximum(np.clip(cy + r + 1, 0, h), y0), np.maximum(np.clip(cx + r + 1, 0, w), x0)
+                q = p[g]
+                out[f] += q[y1[:, None], x1[None, :]] - q[y0[:, None], x1[None, :]] - q[y1[:, None], x0[None, :]] + q[y0[:, None], x0[None, :]]
+        return out
+
+    def taps(n, m):                                   # the axis taps of guided_upsample_np
+        P = np.arange(n, dtype=np.int64)
+        tt = np.clip((2 * P + 1) * m - n, 0, 2 * n * (m - 1))
+        p0 = tt // (2 * n)
+        return p0, np.minimum(p0 + 1, m - 1), rdiv((tt - p0 * 2 * n) * 256, 2 * n)
+
+    guide = luma(c[:, np.minimum(np.arange(h), hc - 1)][:, :, np.minimum(np.arange(w), wc - 1)])
+    n = box3(np.ones((nf, h, w), np.int64))
+    si, sii = box3(guide), box3(guide * guide)
+    y0, y1, fy = taps(hf, hc)
+    x0, x1, fx = taps(wf, wc)
+    big = luma(full)
+    out = np.empty_like(full)
+    for ch in range(3):
+        p = s[..., ch].astype(np.int64)
+        sp, sip = box3(p), box3(guide * p)
+        a_q = rdiv((n * sip - si * sp) << 12, n * sii - si * si + e * n * n)
+        b_q = rdiv((sp << 12) - a_q * si, n)
+        am, bm = rdiv(box3(a_q), n), rdiv(box3(b_q), n)
+        v = 0
+        for ys, wy in ((y0, 256 - fy), (y1, fy)):
+            for xs, wx in ((x0, 256 - fx), (x1, fx)):
+                v = v + (am[:, ys[:, None], xs[None, :]] * big + bm[:, ys[:, None], xs[None, :]]) * (wy[:, None] * wx[None, :])
+        out[..., ch] = np.clip((v + (1 << 27)) >> 28, 0, 255)
+    return out
 
 
 def guided_filter_time_np(stylized, contents, radius, eps_q, frames_t, ctx=None, positions=None):

@@ -25,6 +25,11 @@ MI355X path.  Same flags.  Differences, all forced by the environment or by the 
 * `--guided-motion global [--guided-motion-range R]` (with `--guided-frames`) runs that filter along camera motion: one global
   integer translation per frame, estimated from the input frames, shifts the window in every neighbouring frame, so a pan or a
   handheld shot is averaged along its motion, not across it.  Frames still do not depend on `--batch`.
+* `--guided-upsample --guided-upsample-frames T` (1 .. 3) delivers frames stylized at `--content-size` at their own size without
+  the flicker of the per-frame upsampling: the coefficients are formed over the T frames on each side of a frame of the SMALL
+  clip, every frame is evaluated against itself.  `--guided-upsample-motion global [--guided-upsample-motion-range R]` shifts
+  those windows along camera motion, estimated at the working size.  The buffer holds small frames (2T behind and in front of a
+  chunk) and the full frames not yet delivered, never the whole video; frames do not depend on `--batch`.  Grey guide only.
 * `--device-resize` (opt-in) applies `--content-size` on the device: the frames go up raw and are resized there, on the stream
   of the call that stylizes them, to the bytes Pillow's bilinear resize gives on the host -- the same frames come out.
 """
@@ -92,12 +97,25 @@ _FLAGS = [
                                        'is resized on the device to --content-size, stylized there, and upsampled against itself with '
                                        'the filter of --guided-radius / --guided-eps (in pixels of the working size); the output frames '
                                        'have the input\'s size.  Needs --guided-radius > 0 and --content-size > 0; goes with '
-                                       '--content-colors and --guided-upsample-guide; not with --guided-guide color, --guided-frames, '
+                                       '--content-colors, --guided-upsample-guide and --guided-upsample-frames; not with --guided-guide color, --guided-frames, '
                                        '--swap5, --keep-colors, --mask-path, --alpha-map, --warm-start or --passes > 1')),
     (('--guided-upsample-guide',), dict(choices=['grey', 'color'], default=None,
                                         help='the guide of --guided-upsample: grey (the default), the grey of the frame, or color, its '
                                              'three channels -- brings back edges between colours of equal luminance too.  Needs '
                                              '--guided-upsample')),
+    (('--guided-upsample-frames',), dict(type=int, default=0, metavar='T',
+                                         help='--guided-upsample with the temporal box, against flicker at full size: the coefficients '
+                                              'of the upsampling are formed over the T frames on each side of a frame of the SMALL clip '
+                                              '(0 .. 3; 0: off), within every run of consecutive frames of one size; every frame is then '
+                                              'delivered against itself.  The radius is then at most 51 / 40 / 33 at T = 1 / 2 / 3.  Needs '
+                                              '--guided-upsample; grey guide only')),
+    (('--guided-upsample-motion',), dict(choices=['global'], default=None,
+                                         help='run --guided-upsample-frames along camera motion: one integer translation per frame, '
+                                              'estimated on the frames at the working size (steps within '
+                                              '--guided-upsample-motion-range).  Needs --guided-upsample-frames >= 1')),
+    (('--guided-upsample-motion-range',), dict(type=int, default=None, metavar='R',
+                                               help='the search range of --guided-upsample-motion in pixels of the working size per '
+                                                    'frame (1 .. 16; default 8); both sides of the working size must be at least 4 R')),
     (('--passes',), dict(type=int, default=1, help='feed the result back in this many times')),
     (('--device',), dict(default='/gpu:0', help='e.g. /gpu:0')),
     (('--alpha',), dict(type=float, default=1, help='style strength')),
@@ -242,6 +260,34 @@ def check_guided_frames_args(parser, args):
             parser.error('--guided-frames does not combine with %s' % flag)
 
 
+def check_upsample_time_args(parser, args):
+    """--guided-upsample-frames / -motion / -motion-range: their ranges, what they need and what they refuse (parser.error exits)"""
+    from ._lib import GUIDED_TIME_MAX_RADIUS, MOTION_MAX_RANGE
+    t = getattr(args, 'guided_upsample_frames', 0)
+    motion, search = getattr(args, 'guided_upsample_motion', None), getattr(args, 'guided_upsample_motion_range', None)
+    up = getattr(args, 'guided_upsample', False)
+    for flag, given in (('--guided-upsample-frames', t != 0), ('--guided-upsample-motion', motion is not None),
+                        ('--guided-upsample-motion-range', search is not None)):
+        if given and not up:
+            parser.error('%s needs --guided-upsample (it extends that upsampling along time)' % flag)
+    if not 0 <= t < len(GUIDED_TIME_MAX_RADIUS):
+        parser.error('--guided-upsample-frames must be 0 (off) .. %d frames on each side, got %d' % (len(GUIDED_TIME_MAX_RADIUS) - 1, t))
+    if motion is not None and not t:
+        parser.error('--guided-upsample-motion needs --guided-upsample-frames >= 1 (it shifts the windows of that box along time)')
+    if search is not None:
+        if motion is None:
+            parser.error('--guided-upsample-motion-range needs --guided-upsample-motion with --guided-upsample-frames >= 1')
+        if not 1 <= search <= MOTION_MAX_RANGE:
+            parser.error('--guided-upsample-motion-range must be 1 .. %d, got %d' % (MOTION_MAX_RANGE, search))
+    if not t:
+        return
+    if args.guided_radius > GUIDED_TIME_MAX_RADIUS[t]:
+        parser.error('--guided-radius must be at most %d with --guided-upsample-frames %d, got %d'
+                     % (GUIDED_TIME_MAX_RADIUS[t], t, args.guided_radius))
+    if getattr(args, 'guided_upsample_guide', None) == 'color':
+        parser.error('--guided-upsample-frames goes with the grey guide: --guided-upsample-guide color has no form along time')
+
+
 def check_resize_args(parser, args):
     """--device-resize: the combinations it refuses (parser.error exits)"""
     if not args.device_resize:
@@ -306,6 +352,47 @@ def smooth_clips(batches, frames_t, op, window=32):
                 yield item
             buf, done = [], 0
         buf.extend(zip(files, plain, contents, extras))
+        for item in flush(False):
+            yield item
+    for item in flush(True):
+        yield item
+
+
+def upsample_clips(batches, frames_t, op, window=32):
+    """--guided-upsample-frames T on a stream of batches, in the manner of smooth_clips: `batches` yields (files, small stylized
+    frames [B][..], small contents [B][..], full contents [B][..], per-frame extras) in order; a clip is a maximal run of
+    consecutive frames of one size.  Yields (files, delivered full-size frames, extras), each frame equal to the whole-clip op
+    wherever the batches were cut, by op(small stylized [F], small contents [F], full contents [f1 - f0], f0, f1) -> frames
+    f0 .. f1 - 1 of a resident clip of F <= `window` small frames.  The buffer holds the small frames of one chunk, 2T behind it
+    and what has arrived in front of it, and the full contents of the undelivered frames only: never the whole video."""
+    from .context import upsample_time_chunk
+    halo = 2 * frames_t
+    buf, done = [], 0                      # [file, small stylized, small content, full content or None, extra]; buf[:done] were delivered
+
+    def flush(final):
+        nonlocal buf, done
+        while True:
+            ready = len(buf) if final else len(buf) - halo          # frames whose look-ahead is there
+            full = next(b[3] for b in buf[done:]) if done < len(buf) else None
+            step = window - 4 * frames_t if full is None else min(window - 4 * frames_t, upsample_time_chunk(full.shape[0], full.shape[1], 0))
+            if ready - done < (1 if final else step):
+                return
+            f0, f1 = done, min(ready, done + step)
+            g0, g1 = max(0, f0 - halo), min(len(buf), f1 + halo)
+            outs = op(np.stack([b[1] for b in buf[g0:g1]]), np.stack([b[2] for b in buf[g0:g1]]), np.stack([b[3] for b in buf[f0:f1]]),
+                      f0 - g0, f1 - g0)
+            yield [b[0] for b in buf[f0:f1]], outs, [b[4] for b in buf[f0:f1]]
+            for b in buf[f0:f1]:
+                b[3] = None                                         # delivered: only its small frames stay, as halo
+            drop = max(0, f1 - halo)
+            buf, done = buf[drop:], f1 - drop
+
+    for files, plain, small, full, extras in batches:
+        if buf and (plain.shape[1:] != buf[-1][1].shape or small.shape[1:] != buf[-1][2].shape or full.shape[1:] != buf[-1][5]):
+            for item in flush(True):                                # the clip has ended
+                yield item
+            buf, done = [], 0
+        buf.extend([f, p, c, C, e, C.shape] for f, p, c, C, e in zip(files, plain, small, full, extras))
         for item in flush(False):
             yield item
     for item in flush(True):
@@ -420,6 +507,20 @@ def stylize_frames(wct_model, frame_files, style_img, args, alpha_files=None):
     frames_t = getattr(args, 'guided_frames', 0)
     guided_here, colors_here = (None, False) if frames_t else (guided, colors)
 
+    # --guided-upsample-frames T: the frames are resized and stylized plain at the working size, batch by batch, and delivered at
+    # full size from a sliding buffer of small frames (upsample_clips), then the colour op: no frame depends on the batches
+    up_t = getattr(args, 'guided_upsample_frames', 0) if upsample is not None else 0
+
+    def run_small(frames, style):
+        """-> (the frames stylized plain at the working size, their contents at that size)"""
+        from .context import upsample_time_chunk, upsample_work_size
+        frames = np.ascontiguousarray(frames, np.uint8)
+        work = upsample_work_size(frames.shape[1], frames.shape[2], upsample[0])
+        step = min(32, upsample_time_chunk(frames.shape[1], frames.shape[2], 0))
+        small = np.concatenate([wct_model.sess.resize_batch(frames[k:k + step], work) for k in range(0, len(frames), step)], axis=0)
+        return wct_model.predict_frames(small, prepared if prepared is not None else style, args.alpha, adain=args.adain,
+                                        batch=args.batch), small
+
     def run(frames, style, files):
         """-> (the stylized frames, their contents at the size the network saw them)"""
         style = prepared if prepared is not None else style
@@ -469,6 +570,9 @@ def stylize_frames(wct_model, frame_files, style_img, args, alpha_files=None):
                 if guided and args.passes > 1:
                     outs = guided_frames(wct_model, outs, frames, guided)
                 yield group_files, outs, frames, list(styles)
+            elif up_t:
+                outs, small = run_small(frames, style_img)
+                yield group_files, outs, small, frames, [style_img] * len(group)
             else:
                 outs, contents = run(frames, style_img, group_files)
                 yield group_files, outs, contents, [style_img] * len(group)
@@ -481,7 +585,19 @@ def stylize_frames(wct_model, frame_files, style_img, args, alpha_files=None):
         outs = wct_model.sess.guided_filter_time_range(plain, contents, guided[0], guided[1], frames_t, f0, f1, positions=positions)
         return content_colors_frames(wct_model, outs, contents[f0:f1]) if colors else outs
 
-    for group_files, outs, _, style_per_frame in (smooth_clips(batches(), frames_t, smooth) if frames_t else batches()):
+    def deliver(plain, small, full, f0, f1):
+        """frames f0 .. f1 - 1 of a resident clip of small frames, at full size against `full`, then the colour op"""
+        positions = None
+        if getattr(args, 'guided_upsample_motion', None) == 'global':
+            positions = wct_model.sess.motion_global(small, getattr(args, 'guided_upsample_motion_range', None) or 8)
+        outs = wct_model.sess.guided_upsample_time_range(plain, small, full, upsample[1], upsample[2], up_t, f0, f1, positions=positions)
+        return content_colors_frames(wct_model, outs, full) if colors else outs
+
+    if up_t:
+        stream = ((files, outs, None, styles) for files, outs, styles in upsample_clips(batches(), up_t, deliver))
+    else:
+        stream = smooth_clips(batches(), frames_t, smooth) if frames_t else batches()
+    for group_files, outs, _, style_per_frame in stream:
         for f, o, s in zip(group_files, outs, style_per_frame):
             if args.concat:                                   # stylize_video.py:129-132
                 o = np.hstack([_imresize(s, (o.shape[0], o.shape[0])), o])
@@ -504,8 +620,9 @@ def main(argv=None):
     check_resize_args(parser, args)
     check_alpha_map_args(parser, args)
     from .stylize import check_upsample_args
-    check_upsample_args(parser, args, extra=[('--guided-frames', getattr(args, 'guided_frames', 0) > 0),
+    check_upsample_args(parser, args, extra=[('--guided-frames (use --guided-upsample-frames)', getattr(args, 'guided_frames', 0) > 0),
                                               ('--warm-start', getattr(args, 'warm_start', False))])
+    check_upsample_time_args(parser, args)
     if args.synthetic_weights is None and not args.checkpoints:
         parser.error('--checkpoints is required (stylize.py:17) unless --synthetic-weights SEED is given')
     start = time.time()

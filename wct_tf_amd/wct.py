@@ -361,6 +361,53 @@ class WCT(object):
             if own is not None:
                 own.close()
 
+    @staticmethod
+    def _check_upsample_time(guided_upsample, frames_t, motion, others, shape):
+        """guided_upsample_frames / guided_upsample_motion of predict_frames, checked before any GPU call
+        -> (side, r, e, T, None | ('global', R) | int32 positions [N][2])"""
+        from .context import check_guided_motion, check_guided_time, check_guided_upsample, check_motion_search, upsample_work_size
+        g = check_guided_upsample(guided_upsample)
+        side, r, e = g[:3]
+        if len(g) == 4 and g[3] != 'grey':
+            raise ValueError("guided_upsample_frames goes with the grey guide: the 'color' guide has no form along time")
+        r, e, t = check_guided_time(r, e, frames_t)
+        for name, on in others.items():
+            if on:
+                raise ValueError('%s is not served with guided_upsample: one prepared style, WCT or AdaIN, content_colors%s'
+                                 % (name, ' (along time: guided_upsample_frames / guided_upsample_motion)' if name.startswith('guided_') else ''))
+        if len(shape) != 4 or shape[3] != 3 or 0 in shape:
+            raise ValueError('guided_upsample takes [F][H][W][3] contents, got shape %s' % (shape,))
+        if motion is None:
+            return side, r, e, t, None
+        if isinstance(motion, str) or (isinstance(motion, tuple) and len(motion) == 2 and isinstance(motion[0], str)):
+            name, search = (motion, 8) if isinstance(motion, str) else motion
+            if name != 'global':
+                raise ValueError("guided_upsample_motion is None, 'global', ('global', R) or an int array [N][2] of positions, got %r: "
+                                 "per-block or dense motion, sub-pixel shifts, rotation and zoom are not served" % (motion,))
+            hc, wc = upsample_work_size(shape[1], shape[2], side)
+            return side, r, e, t, ('global', check_motion_search(search, hc, wc))
+        return side, r, e, t, check_guided_motion(motion, shape[0])
+
+    def _predict_upsampled_time(self, frames, style, guided_upsample, frames_t, motion, alpha, adain, content_colors, batch, others):
+        '''predict_frames with guided_upsample and guided_upsample_frames >= 1: the frames resized to the working size on the device,
+        stylized plain there, the positions estimated on the small contents when asked, all frames of the call delivered as one
+        clip (Context.guided_upsample_time_clip), then the colour op against the full contents'''
+        from .context import upsample_time_chunk, upsample_work_size
+        side, r, e, t, motion = self._check_upsample_time(guided_upsample, frames_t, motion, others, np.shape(frames))
+        if frames.dtype != np.uint8:
+            raise ValueError('guided_upsample takes uint8 contents (the resize on the device does), got %s' % frames.dtype)
+        work = upsample_work_size(frames.shape[1], frames.shape[2], side)
+        if isinstance(style, PreparedStyle):
+            check_prepared(self.sess, [style], self.relu_targets)
+        step = min(32, upsample_time_chunk(frames.shape[1], frames.shape[2], 0))      # full frames of one upload
+        small = np.concatenate([self.sess.resize_batch(frames[i:i + step], work) for i in range(0, len(frames), step)], axis=0)
+        plain = self.predict_frames(small, style, alpha=alpha, adain=adain, batch=batch)
+        positions = self.sess.motion_global(small, motion[1]) if isinstance(motion, tuple) else motion
+        out = self.sess.guided_upsample_time_clip(plain, small, frames, r, e, t, positions=positions)
+        if content_colors:
+            out = np.concatenate([self.sess.content_colors_batch(out[i:i + step], frames[i:i + step]) for i in range(0, len(out), step)], axis=0)
+        return out
+
     def predict_mix(self, content, styles, weights=None, alpha=1, adain=False, swap5=False, ss_alpha=1, content_colors=False,
                     guided=None):
         '''Stylize with a weighted mix of several styles (Li et al. 2017, sec. 4.2; the reference's README TODO
@@ -519,7 +566,7 @@ class WCT(object):
 
     def predict_frames(self, frames, style, alpha=1, swap5=False, ss_alpha=1, adain=False, batch=16, warm=None,
                        content_colors=False, resize=None, wrap=False, strengths=None, guided=None, guided_frames=0, guided_motion=None,
-                       guided_upsample=None):
+                       guided_upsample=None, guided_upsample_frames=0, guided_upsample_motion=None):
         '''Stylize same-sized frames [F][H][W][3] with ONE style image (the loop of stylize_video.py:112-121,
            which calls predict() once per frame and so re-runs the style encoder, the style statistics and the
            style eigendecompositions every frame).  Here the style side runs once per batch of `batch` frames;
@@ -551,9 +598,29 @@ class WCT(object):
            and zoom are not served.
            guided_upsample (short_side, radius, eps_q): as in predict -- every raw uint8 frame goes up at its own size, is resized
            and stylized at the working size and upsampled against itself; frame f equals predict(frames[f], style,
-           guided_upsample=...) bit for bit, at the frames' size.  No swap5, warm, resize, wrap, strengths or guided* with it.'''
+           guided_upsample=...) bit for bit, at the frames' size.  No swap5, warm, resize, wrap, strengths or guided* with it.
+           guided_upsample_frames T (0 .. 3; needs guided_upsample, the grey guide): guided upsampling with the temporal box -- the
+           frames are resized to the working size on the device and stylized plain there, then all frames of THIS call are
+           delivered as one clip: the coefficients of the upsampling and their means are formed over the T frames on each side of
+           a frame of the SMALL clip (ops.guided_upsample_time_np), every frame is evaluated against its own full content, then the
+           colour op if content_colors.  The result equals ops.guided_upsample_time_np(predict_frames(small contents, ...), small
+           contents, frames, radius, eps_q, T), and content_colors_np after it, bit for bit, whatever `batch` is.  0, the default,
+           is the call above, untouched; T >= 1 on one frame gives its bytes.  The radius is at most 51 / 40 / 33 at T = 1 / 2 / 3.
+           guided_upsample_motion (needs guided_upsample_frames >= 1): as guided_motion, in pixels of the SMALL frames -- None,
+           'global' or ('global', R) (Context.motion_global on the small contents), or an int array [F][2] of positions.'''
         guided = self._check_guided(guided)                                       # ValueError before any GPU call
         frames = np.asarray(frames)
+        if guided_upsample is None and (guided_upsample_frames or guided_upsample_motion is not None):
+            raise ValueError('guided_upsample_frames and guided_upsample_motion need guided_upsample=(short_side, radius, eps_q): they '
+                             'extend that call along time')
+        if guided_upsample is not None and not guided_upsample_frames and guided_upsample_motion is not None:
+            raise ValueError('guided_upsample_motion needs guided_upsample_frames >= 1: it shifts the windows of that box along time')
+        if guided_upsample is not None and guided_upsample_frames:
+            return self._predict_upsampled_time(frames, style, guided_upsample, guided_upsample_frames, guided_upsample_motion, alpha,
+                                                adain, content_colors, batch,
+                                                dict(swap5=swap5, warm=warm is not None, resize=resize is not None, wrap=wrap,
+                                                     strengths=strengths is not None, guided=guided is not None,
+                                                     guided_frames=bool(guided_frames), guided_motion=guided_motion is not None))
         if guided_upsample is not None:
             return self._predict_upsampled(frames, style, guided_upsample, alpha, adain, content_colors, batch,
                                            dict(swap5=swap5, warm=warm is not None, resize=resize is not None, wrap=wrap,
