@@ -291,7 +291,8 @@ int wct_set_guided_guide(wct_ctx* ctx, int guide);
  *   own ends.  A halo of T frames does not give them.
  * A null pointer, F outside 1 .. 32, a range that is not 0 <= f0 < f1 <= F, Ho < Hc, Wo < Wc, parameters outside the above, or
  * F * Ho * Wo * 3 >= 2^31 is WCT_STATUS_ARG with a message and leaves the ctx usable.
- * Not served: the colour guide along time, T above 3, motion compensation of any kind (a flat region that pans has its stylized
+ * The colour guide along time is wct_guided_filter_time_guide below.
+ * Not served: T above 3, motion compensation of any kind (a flat region that pans has its stylized
  * texture averaged along time), WCT_FLAG_GUIDED along time (a frame would need frames that come after it). */
 int wct_guided_filter_time(wct_ctx* ctx, const uint8_t* stylized, int Ho, int Wo, const uint8_t* content, int Hc, int Wc, int F,
                            int radius, int eps_q, int frames_t, uint8_t* out);
@@ -326,7 +327,8 @@ int wct_guided_time_max_radius(int frames_t);
  *   passes (a ctx serves one stream, so this is the natural order).
  * A null pointer, what wct_guided_filter_time refuses, a step above 16, a range outside 1 .. 16, Hc or Wc below 4 range or
  * Hc Wc > 2^28 is WCT_STATUS_ARG with a message that names it, and leaves the ctx usable.
- * Not served: per-block or dense motion, sub-pixel shifts, rotation and zoom, the colour guide along time. */
+ * The colour guide along time and along motion is wct_guided_filter_time_guide below.
+ * Not served: per-block or dense motion, sub-pixel shifts, rotation and zoom. */
 int wct_motion_global(wct_ctx* ctx, const uint8_t* contents, int Hc, int Wc, int F, int range, int32_t* pos_out);
 int wct_motion_global_batch_dev(wct_ctx* ctx, const uint8_t* content_dev, int Hc, int Wc, int F, int range, int32_t* pos_out);
 int wct_guided_filter_motion(wct_ctx* ctx, const uint8_t* stylized, int Ho, int Wo, const uint8_t* content, int Hc, int Wc, int F,
@@ -334,6 +336,35 @@ int wct_guided_filter_motion(wct_ctx* ctx, const uint8_t* stylized, int Ho, int 
 int wct_guided_filter_motion_batch_dev(wct_ctx* ctx, const uint8_t* stylized_dev, int Ho, int Wo, const uint8_t* content_dev, int Hc,
                                        int Wc, int F, int radius, int eps_q, int frames_t, const int32_t* pos, int f0, int f1,
                                        uint8_t* out_dev);
+/* Temporal guided smoothing under a chosen guide: the two temporal filters above with the guide as one more argument, and with
+ * WCT_GUIDE_COLOR the colour guide along time -- the 3 x 3 rule of wct_guided_filter_guide over the 3-D, optionally shifted, window
+ * of wct_guided_filter_motion, for a video whose content has edges between colours of equal luminance (which the grey guide
+ * blurs) and flickers on its flat areas (which the per-frame colour guide leaves).  The rule and its bounds:
+ * csrc/guided_color_time_rule.h.  Clip, T, positions, window and n are those of wct_guided_filter_motion; pos == NULL means no
+ * motion (every position equal), the window and n of wct_guided_filter_time.  I(f, y, x) = (p.R, p.G, p.B) of the clamped content
+ * pixel of frame f:
+ *   pass 1:    the 21 window sums S_i, S_ij (i <= j), S_ch, S_i,ch over that window; V, M, c, adj, det, u, k, a_q[i][ch] and
+ *              b_q[ch] of (f, y, x) by the formulas of the colour guide above with this n
+ *   pass 2:    out.ch(f, y, x) = clamp(rdiv(sum_i I_i(f, y, x) sum a_q[i][ch] + sum b_q[ch], n 2^12), 0, 255), the sums over the
+ *              same window
+ * T = 0, or a one-frame clip, is wct_guided_filter_guide_batch_dev with WCT_GUIDE_COLOR, bit for bit.  Equal positions, whatever
+ * their value, give the bytes of pos == NULL.  A constant clip comes back exactly.  Parameters, radius limits (r <= 64 / 51 / 40 /
+ * 33 at T = 0 .. 3, n <= 33025), the steps of at most 16 and the 2T halo of a longer video are those above; the result stays
+ * within the distance of csrc/guided_color_rule.h (no n in it) of the float64 filter on the same window.
+ * WCT_GUIDE_GREY gives the bytes of wct_guided_filter_time (pos == NULL) or wct_guided_filter_motion (otherwise).
+ * wct_guided_filter_time_guide: host pointers, blocking, the whole clip, F = 1 .. 32.
+ * wct_guided_filter_time_guide_batch_dev: device frames, host positions (read before the call returns) or NULL, two launches,
+ *   asynchronous on the ctx stream; frames f0 .. f1 - 1 of THIS clip; out_dev may be stylized_dev + f0 Ho Wo 3.  The 48 B per
+ *   pixel of the F frames (twice the grey guide's) live in the workspace of wct_guided_filter, sized before any launch.
+ * A guide that is neither value, a null image pointer, or what wct_guided_filter_time / wct_guided_filter_motion refuse is
+ * WCT_STATUS_ARG with their message and leaves the ctx usable; a workspace that cannot be had is the allocation's own status.
+ * Not served: the colour guide along time under upsampling, fp32 contents, T above 3, per-block or sub-pixel motion, a motion
+ * estimator on colour (wct_motion_global works on the grey guide). */
+int wct_guided_filter_time_guide(wct_ctx* ctx, const uint8_t* stylized, int Ho, int Wo, const uint8_t* content, int Hc, int Wc, int F,
+                                 int radius, int eps_q, int frames_t, int guide, const int32_t* pos, uint8_t* out);
+int wct_guided_filter_time_guide_batch_dev(wct_ctx* ctx, const uint8_t* stylized_dev, int Ho, int Wo, const uint8_t* content_dev, int Hc,
+                                           int Wc, int F, int radius, int eps_q, int frames_t, int guide, const int32_t* pos, int f0,
+                                           int f1, uint8_t* out_dev);
 /* On-device resize (the reference's resize_to, utils.py:55-67, behind --content-size, stylize_video.py:29; webcam.py:163,189
  * resizes every frame by --scale): img [H][W][3] uint8 -> [h][w][3] uint8, the bytes of Pillow's Image.resize((w, h), Image.BILINEAR).
  * Pillow's 8-bit resampler is an integer rule.  Per axis (`in` the input length, `out` the output length; everything up to the

@@ -65,6 +65,10 @@ SIGNATURES = [
     ('wct_guided_filter_motion', C.c_int, [_P, _U8, C.c_int, C.c_int, _U8, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _I, _U8]),
     ('wct_guided_filter_motion_batch_dev', C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                                      _I, C.c_int, C.c_int, _P]),
+    ('wct_guided_filter_time_guide', C.c_int, [_P, _U8, C.c_int, C.c_int, _U8, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                               _I, _U8]),
+    ('wct_guided_filter_time_guide_batch_dev', C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                         C.c_int, _I, C.c_int, C.c_int, _P]),
     ('wct_guided_upsample', C.c_int, [_P, _U8, C.c_int, C.c_int, _U8, C.c_int, C.c_int, _U8, C.c_int, C.c_int, C.c_int, C.c_int, _U8]),
     ('wct_guided_upsample_batch_dev', C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int,
                                                 C.c_int, _P]),

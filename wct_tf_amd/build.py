@@ -12,7 +12,7 @@ LIB = os.path.join(HERE, 'libwct_hip.so')
 WCT_UNITS = ['stats_gemm.hip', 'eigh.hip', 'spectral.hip', 'wct.hip', 'mask.hip', 'style_swap.hip', 'warm.hip']
 # the C ABI and its host-side orchestration, one unit per concern (csrc/api.h is what they share)
 API_UNITS = ['api_ctx.hip', 'api_weights.hip', 'api_drivers.hip', 'api_ops.hip', 'api_stylize.hip', 'api_train.hip']
-SOURCES = API_UNITS + ['conv.hip', 'conv_wino.hip', 'coral.hip', 'colors.hip', 'guided.hip', 'guided_color.hip', 'guided_time.hip', 'guided_motion.hip', 'guided_up.hip', 'guided_up_color.hip', 'guided_up_time.hip', 'noise.hip', 'resize.hip', 'banded.hip', 'wrap.hip', 'train.hip'] + WCT_UNITS
+SOURCES = API_UNITS + ['conv.hip', 'conv_wino.hip', 'coral.hip', 'colors.hip', 'guided.hip', 'guided_color.hip', 'guided_time.hip', 'guided_motion.hip', 'guided_color_time.hip', 'guided_up.hip', 'guided_up_color.hip', 'guided_up_time.hip', 'noise.hip', 'resize.hip', 'banded.hip', 'wrap.hip', 'train.hip'] + WCT_UNITS
 
 
 STAMP = LIB + '.src.sha256'

@@ -1100,20 +1100,29 @@ class Context(object):
             wct_mode=wct_mode, content_colors=content_colors, guide=guide))
 
     # ---- temporal guided smoothing: the filter's box across frames --------------------------
-    def guided_filter_time(self, stylized_u8, contents_u8, radius, eps_q, frames_t, positions=None):
+    def guided_filter_time(self, stylized_u8, contents_u8, radius, eps_q, frames_t, positions=None, guide='grey'):
         """Temporal guided smoothing of a clip (wct_guided_filter_time): stylized [F][Ho][Wo][3] and contents [F][Hc][Wc][3] uint8,
         F <= 32 -> uint8 [F][Ho][Wo][3], the grey-guide filter of guided_filter with its box extended over the frames_t (0 .. 3)
         frames on each side of a frame, cut at the clip's ends.  frames_t = 0 is guided_filter_batch.  The radius is at most
         64 / 51 / 40 / 33 at frames_t 0 / 1 / 2 / 3.  A longer clip: ops.guided_filter_time_np.
         positions: int [F][2] (py, px), one global translation per frame (motion_global estimates them) -- the window in every
-        neighbouring frame is shifted by the difference of the positions (wct_guided_filter_motion); None: no shift."""
+        neighbouring frame is shifted by the difference of the positions (wct_guided_filter_motion); None: no shift.
+        guide: 'grey', or 'color' -- the three content channels as guide along time, with or without positions
+        (wct_guided_filter_time_guide), which keeps an edge between two colours of equal luminance."""
         s, c = _guided_clip(stylized_u8, contents_u8)
         r, e, t = check_guided_time(radius, eps_q, frames_t)
+        g = check_guide(guide)
         pos = None if positions is None else check_guided_motion(positions, s.shape[0])
         if not 1 <= s.shape[0] <= _lib.BATCH_MAX:
             raise ValueError('a clip takes 1 .. %d frames in one call, got %d (ops.guided_filter_time_np takes any length)'
                              % (_lib.BATCH_MAX, s.shape[0]))
         out = np.empty_like(s)
+        if g != _lib.GUIDE_GREY:
+            check(self.lib.wct_guided_filter_time_guide(self.h, s.ctypes.data_as(_lib._U8), s.shape[1], s.shape[2],
+                                                        c.ctypes.data_as(_lib._U8), c.shape[1], c.shape[2], s.shape[0], r, e, t, g,
+                                                        None if pos is None else pos.ctypes.data_as(_lib._I),
+                                                        out.ctypes.data_as(_lib._U8)))
+            return out
         if pos is not None:
             check(self.lib.wct_guided_filter_motion(self.h, s.ctypes.data_as(_lib._U8), s.shape[1], s.shape[2], c.ctypes.data_as(_lib._U8),
                                                     c.shape[1], c.shape[2], s.shape[0], r, e, t, pos.ctypes.data_as(_lib._I),
@@ -1123,26 +1132,40 @@ class Context(object):
                                               c.shape[1], c.shape[2], s.shape[0], r, e, t, out.ctypes.data_as(_lib._U8)))
         return out
 
-    def guided_filter_time_batch_dev(self, stylized_dev, ho, wo, content_dev, hc, wc, frames, radius, eps_q, frames_t, f0, f1, out_dev):
+    def guided_filter_time_batch_dev(self, stylized_dev, ho, wo, content_dev, hc, wc, frames, radius, eps_q, frames_t, f0, f1, out_dev,
+                                     guide='grey'):
         """Frames f0 .. f1 - 1 of the clip of `frames` frames resident in HBM, filtered along time as a clip of its own
         (wct_guided_filter_time_batch_dev) -> out_dev [f1 - f0][ho][wo][3]: asynchronous; out_dev may be the address of frame f0 of
-        stylized_dev.  The bytes of a longer video need 2 frames_t real frames of halo on each side of [f0, f1)."""
+        stylized_dev.  The bytes of a longer video need 2 frames_t real frames of halo on each side of [f0, f1).  guide 'color':
+        the colour guide along time (wct_guided_filter_time_guide_batch_dev with null positions)."""
         r, e, t = check_guided_time(radius, eps_q, frames_t)
+        g = check_guide(guide)
         if not (1 <= int(frames) <= _lib.BATCH_MAX and 0 <= int(f0) < int(f1) <= int(frames)):
             raise ValueError('a clip takes 1 .. %d frames and a range 0 <= f0 < f1 <= frames, got %d frames and [%d, %d)'
                              % (_lib.BATCH_MAX, frames, f0, f1))
+        if g != _lib.GUIDE_GREY:
+            check(self.lib.wct_guided_filter_time_guide_batch_dev(self.h, stylized_dev, int(ho), int(wo), content_dev, int(hc), int(wc),
+                                                                  int(frames), r, e, t, g, None, int(f0), int(f1), out_dev))
+            return
         check(self.lib.wct_guided_filter_time_batch_dev(self.h, stylized_dev, int(ho), int(wo), content_dev, int(hc), int(wc), int(frames),
                                                         r, e, t, int(f0), int(f1), out_dev))
 
     def guided_filter_motion_batch_dev(self, stylized_dev, ho, wo, content_dev, hc, wc, frames, radius, eps_q, frames_t, positions, f0, f1,
-                                       out_dev):
+                                       out_dev, guide='grey'):
         """guided_filter_time_batch_dev with positions int [frames][2] (host): the window of every neighbouring frame shifted by
-        the difference of the positions (wct_guided_filter_motion_batch_dev).  Asynchronous; the same aliasing and halo."""
+        the difference of the positions (wct_guided_filter_motion_batch_dev).  Asynchronous; the same aliasing and halo.  guide
+        'color': the colour guide along motion (wct_guided_filter_time_guide_batch_dev with these positions)."""
         r, e, t = check_guided_time(radius, eps_q, frames_t)
+        g = check_guide(guide)
         if not (1 <= int(frames) <= _lib.BATCH_MAX and 0 <= int(f0) < int(f1) <= int(frames)):
             raise ValueError('a clip takes 1 .. %d frames and a range 0 <= f0 < f1 <= frames, got %d frames and [%d, %d)'
                              % (_lib.BATCH_MAX, frames, f0, f1))
         pos = check_guided_motion(positions, frames)
+        if g != _lib.GUIDE_GREY:
+            check(self.lib.wct_guided_filter_time_guide_batch_dev(self.h, stylized_dev, int(ho), int(wo), content_dev, int(hc), int(wc),
+                                                                  int(frames), r, e, t, g, pos.ctypes.data_as(_lib._I), int(f0), int(f1),
+                                                                  out_dev))
+            return
         check(self.lib.wct_guided_filter_motion_batch_dev(self.h, stylized_dev, int(ho), int(wo), content_dev, int(hc), int(wc), int(frames),
                                                           r, e, t, pos.ctypes.data_as(_lib._I), int(f0), int(f1), out_dev))
 
@@ -1180,28 +1203,30 @@ class Context(object):
         entries of _lib.GUIDED_TIME_MAX_RADIUS; 0 for a frames_t outside 0 .. 3"""
         return int(self.lib.wct_guided_time_max_radius(int(frames_t)))
 
-    def guided_filter_time_clip(self, stylized_u8, contents_u8, radius, eps_q, frames_t, positions=None):
+    def guided_filter_time_clip(self, stylized_u8, contents_u8, radius, eps_q, frames_t, positions=None, guide='grey'):
         """guided_filter_time for a clip of any length: chunks of at most 32 - 4 frames_t output frames, each uploaded with
         2 frames_t frames of halo on each side (fewer at the clip's ends) and filtered as a clip of its own -- the whole clip's
         bytes, since a frame depends on no frame further than 2 frames_t away.  positions [F][2]: sliced with every chunk (only
-        their differences count)."""
+        their differences count).  guide: as in guided_filter_time."""
         s, c = _guided_clip(stylized_u8, contents_u8)
         r, e, t = check_guided_time(radius, eps_q, frames_t)
+        check_guide(guide)
         pos = None if positions is None else check_guided_motion(positions, s.shape[0])
         n, step, out = s.shape[0], _lib.BATCH_MAX - 4 * t, np.empty_like(s)
         for f0 in range(0, n, step):
             f1 = min(n, f0 + step)
             g0, g1 = max(0, f0 - 2 * t), min(n, f1 + 2 * t)
             self.guided_filter_time_range(s[g0:g1], c[g0:g1], r, e, t, f0 - g0, f1 - g0, out=out[f0:f1],
-                                          positions=None if pos is None else pos[g0:g1])
+                                          positions=None if pos is None else pos[g0:g1], guide=guide)
         return out
 
-    def guided_filter_time_range(self, stylized_u8, contents_u8, radius, eps_q, frames_t, f0, f1, out=None, positions=None):
+    def guided_filter_time_range(self, stylized_u8, contents_u8, radius, eps_q, frames_t, f0, f1, out=None, positions=None, guide='grey'):
         """Host arrays in, host array out: frames f0 .. f1 - 1 of the clip stylized [F][Ho][Wo][3] with contents [F][Hc][Wc][3]
         (F <= 32), filtered along time as guided_filter_time_batch_dev does (with positions [F][2]: as
-        guided_filter_motion_batch_dev does) -> uint8 [f1 - f0][Ho][Wo][3]"""
+        guided_filter_motion_batch_dev does) -> uint8 [f1 - f0][Ho][Wo][3].  guide: as in guided_filter_time."""
         s, c = _guided_clip(stylized_u8, contents_u8)
         r, e, t = check_guided_time(radius, eps_q, frames_t)
+        check_guide(guide)
         pos = None if positions is None else check_guided_motion(positions, s.shape[0])
         if not (1 <= s.shape[0] <= _lib.BATCH_MAX and 0 <= f0 < f1 <= s.shape[0]):
             raise ValueError('a clip takes 1 .. %d frames and a range 0 <= f0 < f1 <= frames, got %d frames and [%d, %d)'
@@ -1209,9 +1234,9 @@ class Context(object):
         out = np.empty((f1 - f0,) + s.shape[1:], np.uint8) if out is None else out
         if pos is not None:
             return self._host_batch([s, c], out, enqueue=lambda ds, dc, do: self.guided_filter_motion_batch_dev(
-                ds, s.shape[1], s.shape[2], dc, c.shape[1], c.shape[2], s.shape[0], r, e, t, pos, f0, f1, do))
+                ds, s.shape[1], s.shape[2], dc, c.shape[1], c.shape[2], s.shape[0], r, e, t, pos, f0, f1, do, guide=guide))
         return self._host_batch([s, c], out, enqueue=lambda ds, dc, do: self.guided_filter_time_batch_dev(
-            ds, s.shape[1], s.shape[2], dc, c.shape[1], c.shape[2], s.shape[0], r, e, t, f0, f1, do))
+            ds, s.shape[1], s.shape[2], dc, c.shape[1], c.shape[2], s.shape[0], r, e, t, f0, f1, do, guide=guide))
 
     # ---- temporal guided upsampling: the box across frames, delivered at full size -----------
     def guided_upsample_time(self, stylized_u8, contents_small_u8, contents_full_u8, radius, eps_q, frames_t, positions=None):

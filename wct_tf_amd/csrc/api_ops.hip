@@ -925,6 +925,61 @@ extern "C" int wct_guided_filter_motion(wct_ctx* c, const uint8_t* stylized, int
   return fetch(c, out, ds, (size_t)F * Ho * Wo * 3);
 }
 
+// Temporal guided smoothing under a chosen guide, op level: WCT_GUIDE_GREY routes to the two ops above (with or without
+// positions), WCT_GUIDE_COLOR to csrc/guided_color_time.hip, whose coefficient map of the whole clip (48 B per pixel, twice the
+// grey one) sits in the same workspace, sized before any launch
+static int guided_time_guide_check(int guide) {
+  if (guide == WCT_GUIDE_GREY || guide == WCT_GUIDE_COLOR) return WCT_OK;
+  wct_set_error("guided filter along time: guide %d, must be WCT_GUIDE_GREY (%d) or WCT_GUIDE_COLOR (%d)", guide, WCT_GUIDE_GREY,
+                WCT_GUIDE_COLOR);
+  return WCT_ERR_ARG;
+}
+
+extern "C" int wct_guided_filter_time_guide_batch_dev(wct_ctx* c, const uint8_t* stylized, int Ho, int Wo, const uint8_t* content, int Hc,
+                                                      int Wc, int F, int radius, int eps_q, int frames_t, int guide, const int32_t* pos,
+                                                      int f0, int f1, uint8_t* out) {
+  ARG_CHECK(c != nullptr);
+  TRY(guided_time_guide_check(guide));
+  if (guide == WCT_GUIDE_GREY)
+    return pos ? wct_guided_filter_motion_batch_dev(c, stylized, Ho, Wo, content, Hc, Wc, F, radius, eps_q, frames_t, pos, f0, f1, out)
+               : wct_guided_filter_time_batch_dev(c, stylized, Ho, Wo, content, Hc, Wc, F, radius, eps_q, frames_t, f0, f1, out);
+  if (!stylized || !content || !out) { wct_set_error("guided filter along time: null image pointer"); return WCT_ERR_ARG; }
+  TRY(guided_color_time_check(F, Ho, Wo, Hc, Wc, radius, eps_q, frames_t, f0, f1, pos));
+  // (the check keeps F Ho Wo 3 below 2^31, so the product below is below 2^35; the test stands for a size_t of 32 bits)
+  const unsigned long long pixels = (unsigned long long)F * (unsigned long long)Ho * (unsigned long long)Wo;
+  if (pixels > (unsigned long long)SIZE_MAX / 48) {
+    wct_set_error("guided filter along time: the colour guide's workspace of %d frames of %dx%d at 48 B per pixel overflows size_t", F, Ho,
+                  Wo);
+    return WCT_ERR_ARG;
+  }
+  HIP_TRY(hipSetDevice(c->device));
+  TRY(ensure(c, c->guided_ab, guided_workspace_bytes(F, Ho, Wo, GUIDE_COLOR)));
+  // per pixel of the n1 frames of pass 1: s and c read twice in each of the up to 2T + 1 frames of the window, the map written;
+  // of the n2 frames of pass 2: the map read twice in each frame of the window, c read, the frame written
+  const int n1 = (f1 + frames_t > F ? F : f1 + frames_t) - (f0 - frames_t < 0 ? 0 : f0 - frames_t), n2 = f1 - f0, win = 2 * frames_t + 1;
+  ProfScope ps(c, 7, 0, (double)Ho * Wo * (n1 * (win * 2 * 6 + 48.0) + n2 * (win * 2 * 48.0 + 3 + 3)));
+  return launch_guided_color_time(stylized, content, F, Ho, Wo, Hc, Wc, radius, eps_q, frames_t, pos, f0, f1, c->guided_ab.p, out,
+                                  c->stream);
+}
+
+extern "C" int wct_guided_filter_time_guide(wct_ctx* c, const uint8_t* stylized, int Ho, int Wo, const uint8_t* content, int Hc, int Wc,
+                                            int F, int radius, int eps_q, int frames_t, int guide, const int32_t* pos, uint8_t* out) {
+  ARG_CHECK(c != nullptr);
+  TRY(guided_time_guide_check(guide));
+  if (guide == WCT_GUIDE_GREY)
+    return pos ? wct_guided_filter_motion(c, stylized, Ho, Wo, content, Hc, Wc, F, radius, eps_q, frames_t, pos, out)
+               : wct_guided_filter_time(c, stylized, Ho, Wo, content, Hc, Wc, F, radius, eps_q, frames_t, out);
+  if (!stylized || !content || !out) { wct_set_error("guided filter along time: null image pointer"); return WCT_ERR_ARG; }
+  TRY(guided_color_time_check(F, Ho, Wo, Hc, Wc, radius, eps_q, frames_t, 0, F, pos));         // (before the staging buffers are sized)
+  HIP_TRY(hipSetDevice(c->device));
+  void *ds, *dc;
+  TRY(stage_in(c, 0, stylized, (size_t)F * Ho * Wo * 3, &ds));
+  TRY(stage_in(c, 1, content, (size_t)F * Hc * Wc * 3, &dc));
+  TRY(wct_guided_filter_time_guide_batch_dev(c, (uint8_t*)ds, Ho, Wo, (uint8_t*)dc, Hc, Wc, F, radius, eps_q, frames_t, guide, pos, 0, F,
+                                             (uint8_t*)ds));
+  return fetch(c, out, ds, (size_t)F * Ho * Wo * 3);
+}
+
 // Temporal guided upsampling, op level (csrc/guided_up_time.hip): frames f0 .. f1 - 1 of a clip of F resident small frames, delivered
 // against their full contents; the coefficient map of the clip and the means of the delivered frames in the workspace of the
 // guided ops

@@ -436,6 +436,17 @@ int launch_guided_motion_ab(const uint8_t* stylized, const uint8_t* content, int
 int motion_check(int F, int Hc, int Wc, int range);
 size_t motion_workspace_bytes(int F, int Hc, int Wc, int range);
 int launch_motion_global(const uint8_t* content, int F, int Hc, int Wc, int range, void* workspace, const int32_t** steps, hipStream_t s);
+// ---- guided_color_time.hip ------------------------------------------------
+// Temporal guided smoothing with the colour guide (guided_color_time_rule.h): launch_guided_motion with the three content channels
+// as guide -- uint8 contents, the same clip, range and aliasing; pos may be null (no motion: every position zero).  Two launches.
+// workspace: guided_workspace_bytes(F, Ho, Wo, GUIDE_COLOR) bytes, 16-byte aligned (48 B per pixel of the clip).
+// guided_color_time_check: guided_motion_check with positions, guided_time_check without, so their messages stay in front.
+int guided_color_time_check(int F, int Ho, int Wo, int Hc, int Wc, int radius, int eps_q, int frames_t, int f0, int f1, const int32_t* pos);
+int launch_guided_color_time(const uint8_t* stylized, const uint8_t* content, int F, int Ho, int Wo, int Hc, int Wc, int radius, int eps_q,
+                             int frames_t, const int32_t* pos, int f0, int f1, void* workspace, uint8_t* out, hipStream_t s);
+// launch_guided_color_time_ab: pass 1 alone -- ab [F][Ho][Wo][12] int32, the frames max(0, f0 - T) .. min(F, f1 + T) - 1
+int launch_guided_color_time_ab(const uint8_t* stylized, const uint8_t* content, int F, int Ho, int Wo, int Hc, int Wc, int radius, int eps_q,
+                                int frames_t, const int32_t* pos, int f0, int f1, int32_t* ab, hipStream_t s);
 // ---- guided_up_time.hip ---------------------------------------------------
 // Temporal guided upsampling (guided_up_time_rule.h): out [f1 - f0][H][W][3] = frames f0 .. f1 - 1 of the clip of F small stylized
 // frames s [F][h][w][3] with small contents c [F][hc][wc][3], the coefficients formed over the 3-D window of frames_t frames on

@@ -25,7 +25,8 @@
 //              ceil(Wc / 2) <= (Hc + 1)(Wc + 1) / 4 < 2^26.1 and SAD <= 255 cnt, so a product is < 255 * 2^52.2 < 2^61 < 2^63: int64
 //   at equality the smaller (dy^2 + dx^2, dy, dx) wins, so a flat or an unchanged pair gives (0, 0)
 //   pos[0] = (0, 0), pos[f + 1] = pos[f] + d_f
-// Left out: per-block or dense motion, sub-pixel shifts, rotation and zoom, the colour guide along time.
+// Left out: per-block or dense motion, sub-pixel shifts, rotation and zoom.  The colour guide along time and along motion:
+// guided_color_time_rule.h.
 #pragma once
 #include "guided_time_rule.h"
 

@@ -24,7 +24,7 @@
 //   |b_q| <= (255 * 4096 + 2^18 * 255) + 1 < 6.8e7: both terms are per-pixel means, no n in them; int32
 //   pass 2: |SA| < 33025 * 2^18 = 8.7e9, |SA I| < 2.21e12, |SB| < 33025 * 6.8e7 = 2.25e12: |SA I + SB| < 4.5e12;
 //           the divisor n 2^12 <= 1.36e8, doubled in rdiv: every term far below 2^63
-// Left out: T above 3, the colour guide along time, any motion compensation.
+// Left out: T above 3, any motion compensation (guided_motion_rule.h).  The colour guide along time: guided_color_time_rule.h.
 #pragma once
 #include "guided_rule.h"
 

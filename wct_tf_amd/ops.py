@@ -209,7 +209,7 @@ def guided_upsample_time_np(stylized, contents_small, contents_full, radius, eps
     return out
 
 
-def guided_filter_time_np(stylized, contents, radius, eps_q, frames_t, ctx=None, positions=None):
+def guided_filter_time_np(stylized, contents, radius, eps_q, frames_t, ctx=None, positions=None, guide='grey'):
     """Temporal guided smoothing of a stylized clip, against the flicker of frames that were stylized one by one: uint8
     [F][Ho][Wo][3] frames and [F][Hc][Wc][3] contents of any F -> uint8 [F][Ho][Wo][3], guided_filter_np's grey-guide filter with
     its box extended over the frames_t (0 .. 3) frames on each side of a frame and cut at the clip's ends (the integer rule of
@@ -219,9 +219,11 @@ def guided_filter_time_np(stylized, contents, radius, eps_q, frames_t, ctx=None,
     frames with halos of 2 frames_t and gives the whole clip's bytes.
     positions: int [F][2] (py, px), one global translation per frame, as motion_global_np estimates them: the window in every
     neighbouring frame is shifted by the difference of the positions (wct_guided_filter_motion), so a clip that pans is averaged
-    along its motion.  Steps between consecutive frames of at most 16 on both axes."""
+    along its motion.  Steps between consecutive frames of at most 16 on both axes.
+    guide: 'grey', or 'color' -- the three content channels as guide (wct_guided_filter_time_guide), with or without positions: the
+    clip keeps an edge between two colours of equal luminance, which the grey guide blurs, and still stops flickering."""
     ctx = ctx or default_context()
-    return ctx.guided_filter_time_clip(stylized, contents, radius, eps_q, frames_t, positions=positions)
+    return ctx.guided_filter_time_clip(stylized, contents, radius, eps_q, frames_t, positions=positions, guide=guide)
 
 
 def motion_global_np(contents, search=8, ctx=None):

@@ -21,7 +21,9 @@ MI355X path.  Same flags.  Differences, all forced by the environment or by the 
   the flicker of frames stylized one by one: where the input stands still the stylized frames are averaged along time, where it
   moves the result follows the input.  No motion compensation.  A clip is a run of consecutive frames of one size; every frame
   equals the whole-clip filter on the plain frames of its clip whatever `--batch` is (a sliding buffer of at most 32 + `--batch`
-  frames, never the whole video).  Grey guide only; not with `--swap5`, `--keep-colors` or `--mask-path`.
+  frames, never the whole video).  Not with `--swap5`, `--keep-colors` or `--mask-path`.  `--guided-frames-guide color` guides
+  it with the frames' three channels instead of their grey (the default), which keeps an edge between two colours of equal
+  luminance along time too; `--guided-guide` stays the guide of the per-frame filter and does not combine with `--guided-frames`.
 * `--guided-motion global [--guided-motion-range R]` (with `--guided-frames`) runs that filter along camera motion: one global
   integer translation per frame, estimated from the input frames, shifts the window in every neighbouring frame, so a pan or a
   handheld shot is averaged along its motion, not across it.  Frames still do not depend on `--batch`.
@@ -78,8 +80,13 @@ _FLAGS = [
     (('--guided-frames',), dict(type=int, default=0, metavar='T',
                                 help='temporal guided smoothing, against flicker: the box of --guided-radius also covers the T frames '
                                      'on each side of a frame (0 .. 3; 0: off), within every run of consecutive frames of one size. '
-                                     'The radius is then at most 51 / 40 / 33 at T = 1 / 2 / 3.  Grey guide only; not with --swap5, '
-                                     '--keep-colors or --mask-path')),
+                                     'The radius is then at most 51 / 40 / 33 at T = 1 / 2 / 3.  Its guide is --guided-frames-guide '
+                                     '(not --guided-guide); not with --swap5, --keep-colors or --mask-path')),
+    (('--guided-frames-guide',), dict(choices=['grey', 'color'], default=None,
+                                      help='the guide of --guided-frames: grey (the default), the grey of the input frames, or color, '
+                                           'their three channels -- keeps edges between colours of equal luminance along time too.  '
+                                           'Needs --guided-frames >= 1; goes with --guided-motion (estimated on the grey guide); not '
+                                           'with --guided-upsample')),
     (('--guided-motion',), dict(choices=['global'], default=None,
                                 help='run --guided-frames along camera motion: global estimates one integer translation per frame '
                                      'from the input frames (exhaustive search, steps within --guided-motion-range) and shifts the '
@@ -241,6 +248,12 @@ def check_guided_frames_args(parser, args):
     motion, search = getattr(args, 'guided_motion', None), getattr(args, 'guided_motion_range', None)
     if motion is not None and not t:
         parser.error('--guided-motion needs --guided-frames >= 1 (it shifts the windows of that filter along time)')
+    if getattr(args, 'guided_frames_guide', None) is not None:
+        if getattr(args, 'guided_upsample', False):
+            parser.error('--guided-frames-guide does not combine with --guided-upsample: the colour guide along time is not served '
+                         'under upsampling')
+        if not t:
+            parser.error('--guided-frames-guide needs --guided-frames >= 1 (it chooses the guide of that filter along time)')
     if search is not None:
         from ._lib import MOTION_MAX_RANGE
         if motion is None or not t:
@@ -254,7 +267,8 @@ def check_guided_frames_args(parser, args):
     if args.guided_radius > GUIDED_TIME_MAX_RADIUS[t]:
         parser.error('--guided-radius must be at most %d with --guided-frames %d, got %d' % (GUIDED_TIME_MAX_RADIUS[t], t, args.guided_radius))
     if args.guided_guide == 'color':
-        parser.error('--guided-frames goes with the grey guide: --guided-guide color has no form along time')
+        parser.error('--guided-frames goes with the grey guide of --guided-guide: --guided-guide color has no form along time '
+                     '(--guided-frames-guide color chooses the guide of the filter along time)')
     for flag, on in (('--swap5', args.swap5), ('--keep-colors', args.keep_colors), ('--mask-path', args.mask_path is not None)):
         if on:
             parser.error('--guided-frames does not combine with %s' % flag)
@@ -581,8 +595,9 @@ def stylize_frames(wct_model, frame_files, style_img, args, alpha_files=None):
         """frames f0 .. f1 - 1 of a resident clip: the filter along time, then the colour op"""
         positions = None
         if getattr(args, 'guided_motion', None) == 'global':  # the pairs of the resident clip: halo pairs come out the same again
-            positions = wct_model.sess.motion_global(contents, getattr(args, 'guided_motion_range', None) or 8)
-        outs = wct_model.sess.guided_filter_time_range(plain, contents, guided[0], guided[1], frames_t, f0, f1, positions=positions)
+            positions = wct_model.sess.motion_global(contents, getattr(args, 'guided_motion_range', None) or 8)   # (on the grey guide)
+        outs = wct_model.sess.guided_filter_time_range(plain, contents, guided[0], guided[1], frames_t, f0, f1, positions=positions,
+                                                       guide=getattr(args, 'guided_frames_guide', None) or 'grey')
         return content_colors_frames(wct_model, outs, contents[f0:f1]) if colors else outs
 
     def deliver(plain, small, full, f0, f1):

@@ -508,18 +508,27 @@ class WCT(object):
                 h.close()
 
     @staticmethod
-    def _check_guided_frames(guided, guided_frames, swap5, wrap):
-        '''guided_frames of predict_frames, checked before any GPU call -> whether the frames take the temporal route'''
-        from .context import check_guided_time
+    def _check_guided_frames(guided, guided_frames, swap5, wrap, guided_frames_guide=None):
+        '''guided_frames and guided_frames_guide of predict_frames, checked before any GPU call -> whether the frames take the
+        temporal route'''
+        from .context import check_guide, check_guided_time
+        if guided_frames_guide is not None:
+            check_guide(guided_frames_guide)
         if guided is None:
             if guided_frames:
                 raise ValueError('guided_frames needs guided=(radius, eps_q): it extends that filter along time')
+            if guided_frames_guide is not None:
+                raise ValueError('guided_frames_guide needs guided=(radius, eps_q) and guided_frames >= 1: it chooses the guide of that '
+                                 'filter along time')
             return False
         t = check_guided_time(guided[0], guided[1], guided_frames)[2]
         if t == 0:
+            if guided_frames_guide is not None:
+                raise ValueError('guided_frames_guide needs guided_frames >= 1: it chooses the guide of that filter along time')
             return False
         if len(guided) == 3 and guided[2] != 'grey':
-            raise ValueError("guided_frames goes with the grey guide: the 'color' guide has no form along time")
+            raise ValueError("guided_frames goes with the grey guide of guided=: the 'color' guide of the per-frame filter has no form "
+                             "along time (guided_frames_guide='color' chooses the guide of the filter along time)")
         for name, on in (('swap5', swap5), ('wrap', wrap)):
             if on:
                 raise ValueError('guided_frames is not served with %s' % name)
@@ -545,10 +554,10 @@ class WCT(object):
             return ('global', check_motion_search(search, h, w))
         return check_guided_motion(guided_motion, shape[0])
 
-    def _predict_frames_smoothed(self, frames, style, guided, frames_t, content_colors, resize, kw, motion=None):
+    def _predict_frames_smoothed(self, frames, style, guided, frames_t, content_colors, resize, kw, motion=None, guide='grey'):
         '''predict_frames with guided_frames >= 1: the plain frames of the call, filtered along time as one clip against their
         contents (the resized ones with resize=), then the colour op.  motion: None, ('global', R) -- the positions are estimated
-        from those contents -- or positions [N][2]'''
+        from those contents (on the grey guide, whatever `guide` is) -- or positions [N][2]; guide: that of the filter along time'''
         if frames.ndim != 4 or frames.shape[3] != 3:
             raise ValueError('expected [F][H][W][3] frames, got shape %s' % (frames.shape,))
         if frames.dtype != np.uint8:
@@ -559,14 +568,14 @@ class WCT(object):
         contents = frames if resize is None else np.concatenate(
             [self.sess.resize_batch(frames[i:i + 32], resize) for i in range(0, len(frames), 32)], axis=0)
         positions = self.sess.motion_global(contents, motion[1]) if isinstance(motion, tuple) else motion
-        out = self.sess.guided_filter_time_clip(plain, contents, guided[0], guided[1], frames_t, positions=positions)
+        out = self.sess.guided_filter_time_clip(plain, contents, guided[0], guided[1], frames_t, positions=positions, guide=guide)
         if content_colors:
             out = np.concatenate([self.sess.content_colors_batch(out[i:i + 32], contents[i:i + 32]) for i in range(0, len(out), 32)], axis=0)
         return out
 
     def predict_frames(self, frames, style, alpha=1, swap5=False, ss_alpha=1, adain=False, batch=16, warm=None,
                        content_colors=False, resize=None, wrap=False, strengths=None, guided=None, guided_frames=0, guided_motion=None,
-                       guided_upsample=None, guided_upsample_frames=0, guided_upsample_motion=None):
+                       guided_upsample=None, guided_upsample_frames=0, guided_upsample_motion=None, guided_frames_guide=None):
         '''Stylize same-sized frames [F][H][W][3] with ONE style image (the loop of stylize_video.py:112-121,
            which calls predict() once per frame and so re-runs the style encoder, the style statistics and the
            style eigendecompositions every frame).  Here the style side runs once per batch of `batch` frames;
@@ -596,6 +605,11 @@ class WCT(object):
            contents, radius, eps_q, T, positions=ops.motion_global_np(contents, R)) bit for bit, whatever `batch` is.  A scene cut
            yields an arbitrary step, which the filter treats like any edge.  Per-block or dense motion, sub-pixel shifts, rotation
            and zoom are not served.
+           guided_frames_guide (needs guided_frames >= 1): the guide of the filter along time -- None or 'grey', the grey of the
+           contents, or 'color', their three channels (Context.guided_filter_time(..., guide='color')), which keeps an edge between
+           two colours of equal luminance that the grey guide blurs.  It goes with guided_motion (the positions are estimated on
+           the grey guide), runs before content_colors, and the result equals ops.guided_filter_time_np(plain frames, contents,
+           radius, eps_q, T, positions=..., guide='color') bit for bit, whatever `batch` is.  Not served with guided_upsample.
            guided_upsample (short_side, radius, eps_q): as in predict -- every raw uint8 frame goes up at its own size, is resized
            and stylized at the working size and upsampled against itself; frame f equals predict(frames[f], style,
            guided_upsample=...) bit for bit, at the frames' size.  No swap5, warm, resize, wrap, strengths or guided* with it.
@@ -620,17 +634,20 @@ class WCT(object):
                                                 adain, content_colors, batch,
                                                 dict(swap5=swap5, warm=warm is not None, resize=resize is not None, wrap=wrap,
                                                      strengths=strengths is not None, guided=guided is not None,
-                                                     guided_frames=bool(guided_frames), guided_motion=guided_motion is not None))
+                                                     guided_frames=bool(guided_frames), guided_motion=guided_motion is not None,
+                                                     guided_frames_guide=guided_frames_guide is not None))
         if guided_upsample is not None:
             return self._predict_upsampled(frames, style, guided_upsample, alpha, adain, content_colors, batch,
                                            dict(swap5=swap5, warm=warm is not None, resize=resize is not None, wrap=wrap,
                                                 strengths=strengths is not None, guided=guided is not None,
-                                                guided_frames=bool(guided_frames), guided_motion=guided_motion is not None))
-        temporal = self._check_guided_frames(guided, guided_frames, swap5, wrap)
+                                                guided_frames=bool(guided_frames), guided_motion=guided_motion is not None,
+                                                     guided_frames_guide=guided_frames_guide is not None))
+        temporal = self._check_guided_frames(guided, guided_frames, swap5, wrap, guided_frames_guide)
         motion = self._check_guided_motion(guided_motion, temporal, frames, resize)
         if temporal:
             return self._predict_frames_smoothed(frames, style, guided, int(guided_frames), content_colors, resize,
-                                                 dict(alpha=alpha, adain=adain, batch=batch, warm=warm, strengths=strengths), motion)
+                                                 dict(alpha=alpha, adain=adain, batch=batch, warm=warm, strengths=strengths), motion,
+                                                 guide=guided_frames_guide or 'grey')
         if strengths is not None:
             from ._lib import strength_maps_frames
             if frames.ndim != 4 or frames.shape[3] != 3:
